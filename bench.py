@@ -7,11 +7,23 @@ the batched mini-LM loop-closure solve and the pose-graph Levenberg-Marquardt so
 resident in HBM before the timed region starts.
 
     python bench.py --gpus 1 --steps K --warmup W                         (default workload: BASELINE config 3)
+    python bench.py --gpus 1 --steps K --warmup W --full                  (+ every extra leg listed below)
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR      (+ the last timed step's results as DIR/*.npy)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (one rank per GPU, RCCL)
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with the extra `roofline` and `cpu_baseline`
-objects.  The CPU baseline is the oracle (oracle/liboracle.so, a single-threaded C restatement of the reference:
-the reference itself needs OpenCV/GTSAM and cannot be built here) timed on a bounded sample of the same workload.
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times the steps and
+prints the line; nothing else runs on the GPU.  With --full the line also carries the extra objects the rounds report:
+`roofline` (+ stages, every kernel, breakdown_ms, the pose-graph critical path) from a profiled pass, the all-pairs matcher
+and SIFT-descriptor side legs, `pcie_inclusive`, `throughput_surveys_in_flight`, `throughput_one_survey_per_gpu` (several
+ranks) and `cpu_baseline` with the parity of the GPU path on the CPU sample.  The CPU baseline is the oracle (oracle/liboracle.so,
+a single-threaded C restatement of the reference: the reference itself needs OpenCV/GTSAM and cannot be built here) timed on a
+bounded sample of the same workload.  The --no-roofline, --no-side-legs, --pcie-steps, --jobs-in-flight and --cpu-frames switches
+thin out a --full run.
+
+--dump-outputs DIR writes what the timed path returned in its last timed step (rank 0): poses.npy (every ping's optimised pose,
+R row-major + t, float64; above DUMP_MAX_BYTES a fixed seeded sample of rows, whose indices go to poses_rows.npy) and
+pg_stats.npy (the pose-graph LM's statistics, float64).  The inputs depend on the arguments only, so two builds compare
+output for output.
 """
 import argparse
 import json
@@ -33,6 +45,21 @@ WORKLOADS = {
     "smoke": dict(F=6, N=700, M=480, name="6 synthetic 700x480 frames (not a BASELINE config)"),
 }
 HBM_PEAK_GBS = 8000.0   # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy ceiling)
+DUMP_MAX_BYTES = 48 << 20     # --dump-outputs: poses beyond this are sampled (C3: 38.4 MB whole; C5: 384 MB -> a sample)
+
+
+def dump_outputs(out_dir, poses, stats):
+    """the last timed step's results as float64 .npy files; a fixed seeded sample of pose rows when the whole set is too large"""
+    os.makedirs(out_dir, exist_ok=True)
+    poses = np.asarray(poses, np.float64)
+    if poses.nbytes > DUMP_MAX_BYTES:
+        rows = np.sort(np.random.default_rng(20240601).choice(len(poses), DUMP_MAX_BYTES // poses[0].nbytes, replace=False))
+        np.save(os.path.join(out_dir, "poses_rows.npy"), rows.astype(np.float64))
+        poses = poses[rows]
+    elif os.path.exists(os.path.join(out_dir, "poses_rows.npy")):
+        os.remove(os.path.join(out_dir, "poses_rows.npy"))          # (left by an earlier, sampled dump into the same folder)
+    np.save(os.path.join(out_dir, "poses.npy"), np.ascontiguousarray(poses))
+    np.save(os.path.join(out_dir, "pg_stats.npy"), np.asarray(stats, np.float64))
 
 
 def cpu_baseline(sv, wl, n_frames, threads=1):
@@ -193,6 +220,9 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default=os.environ.get("DSSS_WORKLOAD", "C3"), choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true", help="also run every extra leg after the timed steps (profiled roofline pass, side legs, PCIe-inclusive and "
+                                                        "surveys-in-flight legs, one survey per GPU, CPU baseline + parity); the switches below thin it out")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the results of the last timed step (poses, pose-graph stats) to DIR/*.npy")
     ap.add_argument("--cpu-frames", type=int, default=24, help="frames in the CPU baseline sample (0 = skip); 24 frames of C3 are about 10 s of one core")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-side-legs", action="store_true", help="skip the legs that run extra passes after the timed steps (all-pairs matcher, SIFT descriptor): a kernel trace of the command then ends with the timed steps and the profiled pass")
@@ -283,13 +313,20 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        _, stats = pipe.run(survey)
+        est, stats = pipe.run(survey)
     barrier()
     dt = time.perf_counter() - t0
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        dump_outputs(args.dump_outputs, est, stats)     # (est is a page-locked buffer of the context: written out before any further solve)
+
+    # ---- everything below runs with --full only: passes outside the timed region that the headline does not need
+    full = args.full
+    if not full:
+        args.no_roofline, args.no_side_legs, args.pcie_steps, args.jobs_in_flight, args.cpu_frames = True, True, 0, 1, 0
 
     # ---- per-kernel timing pass (HIP events on the library's stream), outside the timed region
     breakdown, roof, roof_groups, roof_all, work = None, None, None, None, None
@@ -404,11 +441,13 @@ def main():
                     "note": "sum over the panel levels of the schedule of the longest DEPENDENT f64 chain of each level (4-column pivot blocks: 570 cycles of pivot arithmetic + two matrix products at "
                             "102 cycles result-to-operand; row solve 2 products per block; back-substitution 312 cycles per block), times the LM trials: the floor of the level-by-level factorisation "
                             "on this chip whatever the launch structure -- the measured stage is `roofline.ms_per_step`"}
-    nkp = [pipe.ctx.features_get(f)[0].shape[0] for f in mine[:8]]
-    tot_rows, tot_kp7 = pipe.ctx.match_total()
-    active_pairs = sum(1 for p in range(len(pipe.src)) if pipe.ctx.pair_is_active(p))
-    pairs_per_rank, active_per_rank = [len(pipe.src)], [active_pairs]
-    if world > 1:       # pairs go to the owner of their TARGET frame (contiguous blocks): rank r holds ~(2r+1)/world^2 of the dense pair list, but the
+    nkp, tot_rows, tot_kp7, active_pairs, pairs_per_rank, active_per_rank = [], None, None, None, None, None
+    if full:
+        nkp = [pipe.ctx.features_get(f)[0].shape[0] for f in mine[:8]]
+        tot_rows, tot_kp7 = pipe.ctx.match_total()
+        active_pairs = sum(1 for p in range(len(pipe.src)) if pipe.ctx.pair_is_active(p))
+        pairs_per_rank, active_per_rank = [len(pipe.src)], [active_pairs]
+    if full and world > 1:       # pairs go to the owner of their TARGET frame (contiguous blocks): rank r holds ~(2r+1)/world^2 of the dense pair list, but the
         t = torch.zeros((2, world), dtype=torch.int64, device="cuda"); t[0, rank] = len(pipe.src); t[1, rank] = active_pairs   # ACTIVE pairs (the only ones that cost anything) follow the survey's geometry
         dist.all_reduce(t); pairs_per_rank, active_per_rank = t[0].tolist(), t[1].tolist(); active_pairs = int(sum(active_per_rank))
 
@@ -518,16 +557,20 @@ def main():
             "value": F * args.steps / dt, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
             "dtype": "u8/int32 (extract, match) + f64 (geo gate, LM)", "data": "synthetic",
-            "config": {"workload": wl["name"], "frames": F, "pings": N, "bins": M, "pairs": F * (F - 1) // 2, "active_pairs": active_pairs,
-                       "active_pairs_note": "pairs whose geo bounding boxes intersect; the others are provably empty (FEAmatcher.cpp:84) and skipped",
-                       "input": "raw float64 frames resident in HBM before the timed region (PCIe-inclusive figure: pcie_inclusive)",
+            "config": {"workload": wl["name"], "frames": F, "pings": N, "bins": M, "pairs": F * (F - 1) // 2,
+                       "input": "raw float64 frames resident in HBM before the timed region (PCIe-inclusive figure, with --full: pcie_inclusive)",
                        "harness": "the argument arrays of dsss_frames_set (ids, sizes, per-frame pointers) are built once before the clock, as a C++ caller holds them; every C-ABI call of a step is timed, on every step; no result or analysis is carried between steps",
-                       "pairs_per_rank": pairs_per_rank, "active_pairs_per_rank": active_per_rank, "kp_per_frame": int(np.mean(nkp)) if nkp else 0, "matches_rank0": tot_rows, "lc_problems_rank0": tot_kp7,
                        "pg_stats": [float(s) for s in stats] if stats is not None else None,
                        "parallelism": "contiguous frame blocks over %d rank(s): RCCL all-gather of features, pairs to the owner of the target frame, pose graph sharded with one RCCL all-reduce of the reduced Hessian per LM trial" % world},
-            "roofline": roof, "roofline_stages": roof_groups, "roofline_all_kernels": roof_all, "breakdown_ms": breakdown, "work_per_step": work, "pcie_inclusive": pcie, "throughput_surveys_in_flight": inflight,
-            "match_allpairs": match_allpairs, "sift128": sift_leg,
+            "full": full,
         }
+        if full:
+            out["config"].update({"active_pairs": active_pairs,
+                                  "active_pairs_note": "pairs whose geo bounding boxes intersect; the others are provably empty (FEAmatcher.cpp:84) and skipped",
+                                  "pairs_per_rank": pairs_per_rank, "active_pairs_per_rank": active_per_rank, "kp_per_frame": int(np.mean(nkp)) if nkp else 0,
+                                  "matches_rank0": tot_rows, "lc_problems_rank0": tot_kp7})
+            out.update({"roofline": roof, "roofline_stages": roof_groups, "roofline_all_kernels": roof_all, "breakdown_ms": breakdown, "work_per_step": work, "pcie_inclusive": pcie,
+                        "throughput_surveys_in_flight": inflight, "match_allpairs": match_allpairs, "sift128": sift_leg})
         if replicas is not None:
             out["throughput_one_survey_per_gpu"] = replicas
         if crit is not None:      # the dependent-chain floor belongs to the factorisation stage; the headline carries it when that stage IS the headline

@@ -4,7 +4,7 @@ other=$1; shift
 for i in 1 2; do
   for lib in "$other" ""; do
     if [ -n "$lib" ]; then export DSSS_LIB=$(realpath $lib); else unset DSSS_LIB; fi
-    python bench.py --steps 4 --warmup 1 --cpu-frames 0 --pcie-steps 0 --jobs-in-flight 1 2>/dev/null | KEYS="$*" python -c "
+    python bench.py --full --steps 4 --warmup 1 --cpu-frames 0 --pcie-steps 0 --jobs-in-flight 1 2>/dev/null | KEYS="$*" python -c "
 import sys,json,os
 keys=os.environ.get('KEYS','lc match').split()
 for l in sys.stdin:

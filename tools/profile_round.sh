@@ -6,7 +6,7 @@
 TAG=${1:-r06}
 ONLY_STATS=${2:-0}      # 1: the kernel-trace pass and its timelines only
 export TMPDIR=/tmp; cd "$(cd "$(dirname "$0")/.." && pwd)"
-B="python3 bench.py --steps 3 --warmup 1 --cpu-frames 0 --pcie-steps 0 --jobs-in-flight 1 --no-side-legs"      # (the side legs would put extra passes behind the timed steps: the timelines below count steps from the end of the trace)
+B="python3 bench.py --full --steps 3 --warmup 1 --cpu-frames 0 --pcie-steps 0 --jobs-in-flight 1 --no-side-legs"      # (the side legs would put extra passes behind the timed steps: the timelines below count steps from the end of the trace)
 rocprofv3 --kernel-trace --stats -d gpurun_out/${TAG}_stats -o ${TAG} --output-format csv -- $B > gpurun_out/${TAG}_bench_under_rocprof.log 2>&1
 if [ "$ONLY_STATS" != "1" ]; then
 P="python3 bench.py --steps 1 --warmup 0 --cpu-frames 0 --no-roofline --pcie-steps 0 --jobs-in-flight 1"

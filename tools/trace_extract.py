@@ -5,7 +5,7 @@ rows = list(csv.DictReader(open(sys.argv[1])))
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
 # the last row_reduce launch starts the last extraction
 starts = [i for i, r in enumerate(rows) if r["Kernel_Name"].startswith("row_reduce_kernel")]
-i0 = starts[-int(__import__("os").environ.get("STEP_FROM_END", "1"))]          # STEP_FROM_END=2: the last TIMED step of a default bench.py run (the very last pass is the profiled one)
+i0 = starts[-int(__import__("os").environ.get("STEP_FROM_END", "1"))]          # STEP_FROM_END=2: the last TIMED step of a bench.py --full run (the very last pass is the profiled one)
 t0 = int(rows[i0]["Start_Timestamp"])
 _k = int(__import__("os").environ.get("STEP_FROM_END", "1"))
 _i1 = starts[-_k + 1] if _k > 1 else len(rows)

@@ -5,7 +5,7 @@ rows = list(csv.DictReader(open(sys.argv[1])))
 mingap = float(sys.argv[2]) if len(sys.argv) > 2 else 20.0
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
 starts = [i for i, r in enumerate(rows) if r["Kernel_Name"].startswith("row_reduce_kernel")]
-i0 = starts[-int(__import__("os").environ.get("STEP_FROM_END", "1"))]          # STEP_FROM_END=2: the last TIMED step of a default bench.py run (the very last pass is the profiled one)
+i0 = starts[-int(__import__("os").environ.get("STEP_FROM_END", "1"))]          # STEP_FROM_END=2: the last TIMED step of a bench.py --full run (the very last pass is the profiled one)
 t0 = int(rows[i0]["Start_Timestamp"])
 busy_end = t0; busy = 0.0; gaps = []
 last = rows[i0]["Kernel_Name"]

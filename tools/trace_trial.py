@@ -11,7 +11,7 @@ with open(sys.argv[1]) as f:
 rows.sort()
 idx = [i for i, x in enumerate(rows) if x[2] == "pg_assemble_kernel"]
 import os
-back = int(os.environ.get("TRIAL_FROM_END", "3"))        # TRIAL_FROM_END=8: a trial of the last TIMED step of a default bench.py run (five trials per step; the last pass is the profiled one)
+back = int(os.environ.get("TRIAL_FROM_END", "3"))        # TRIAL_FROM_END=8: a trial of the last TIMED step of a bench.py --full run (five trials per step; the last pass is the profiled one)
 a, b = idx[-back], idx[-back + 1]
 t0 = rows[a][0]
 print("one trial span %.3f ms" % ((rows[b][0] - t0) / 1e6))
