@@ -115,8 +115,6 @@ struct dsss_ctx {
     void* mt_cells = nullptr; size_t mt_cells_bytes = 0; unsigned long long mt_evals_host = 0;
     // LC results
     dsss_lc* lcs = nullptr; size_t lcs_cap = 0; bool has_lc = false;
-    // pose-graph scratch
-    void* pg_state = nullptr;
     // per-geometry extraction tables (dsss_extract.hip owns the type; freed through geoms_free by dsss_destroy)
     void* geoms = nullptr; void (*geoms_free)(void*) = nullptr;
     dsss_comm* comm = nullptr;          // ranks of one job (dsss_comm_init): null = single process
@@ -134,8 +132,6 @@ struct dsss_ctx {
     void* pg_stage = nullptr; size_t pg_stage_cap = 0;          // page-locked staging of the analysis tables: one upload per solve (pg_dev::flush)
     // online use (dsss_posegraph_update): the estimate of the previous update stays on the device, the LC edges accumulate
     void* pg_warm = nullptr; size_t pg_warm_cap = 0; int pg_warm_n = 0;   // pose_t[pg_warm_n]
-    bool pg_online = false;             // set by dsss_posegraph_update: pg_solve_impl starts from pg_warm and leaves its result there
-    int pg_win_f0 = 0, pg_win_p0 = 0;   // dsss_posegraph_update_window: first frame / first global pose of the window being solved (0: the whole graph)
     std::vector<dsss_lc_edge> pg_inc_edges; unsigned long long lc_gen = 0, pg_inc_gen = 0;    // lc_gen counts LC result sets; the last one consumed
     dsss_prof prof;
 };

@@ -53,7 +53,7 @@ private:
     pg_pool()
     {
         const unsigned hc = std::thread::hardware_concurrency();
-        int n = hc > 1 ? (int)std::min(23u, hc - 1) : 0;      // (the analysis of a C3-size graph forks eight ways; graphs of several hundred thousand separators use them all: dsss_pg.hip, sym_threads)
+        int n = hc > 1 ? (int)std::min(23u, hc - 1) : 0;      // (the analysis of a C3-size graph forks eight ways; graphs of several hundred thousand separators use them all: sym_threads)
         for (int i = 0; i < n; ++i) workers.emplace_back([this] { run(); });
     }
     void run()
@@ -525,7 +525,7 @@ void pg_symbolic(int ns, const std::vector<std::pair<int, int>>& edges, int ncha
 {
     S = pg_sym();
     S.ns = ns; S.nparts = std::max(1, nparts);
-    const bool tv = getenv("DSSS_PG_VERBOSE") != nullptr && !opt.to_be_joined;      // (the parts of pg_symbolic_parts report together)
+    const bool tv = opt.verbose && !opt.to_be_joined;      // (the parts of pg_symbolic_parts report together)
     auto tnow = [] { return std::chrono::steady_clock::now(); };
     auto tms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     const auto q0 = tnow();
@@ -926,7 +926,7 @@ void pg_symbolic(int ns, const std::vector<std::pair<int, int>>& edges, int ncha
     }
     const auto fC = tnow();
     if (!opt.to_be_joined) sym_levels(S);
-    if (tv && atoi(getenv("DSSS_PG_VERBOSE")) >= 2 && !opt.to_be_joined) {      // critical path of the schedule, root first
+    if (tv && opt.verbose >= 2) {      // critical path of the schedule, root first
         int f = -1;
         for (int g = 0; g < nf; ++g) if (S.f_level0[g] + S.f_npan[g] == S.nlev) f = g;
         while (f >= 0) {
@@ -1021,11 +1021,30 @@ void pg_build_schedule(const pg_sym& S, int part_lo, int part_hi, pg_sched& out)
     }
 }
 
-void pg_sym_opts_env(pg_sym_opts& opt)
+pg_switches pg_switches_read()
 {
-    if (getenv("DSSS_PG_ND_BOTH")) opt.nd_both_axes = atoi(getenv("DSSS_PG_ND_BOTH"));
-    if (getenv("DSSS_PG_LEAF")) opt.leaf = atoi(getenv("DSSS_PG_LEAF"));
-    if (getenv("DSSS_PG_ND_INDEX")) opt.nd_index_cuts = atoi(getenv("DSSS_PG_ND_INDEX"));      // (tools/sym_time.py, tools/pg_sweep.sh: the chain-order cut candidate on / off)
+    pg_switches sw;
+    if (const char* v = getenv("DSSS_PG_BIN_COST")) sw.bin_cost = sw.opt.bin_cost = atof(v);
+    if (const char* v = getenv("DSSS_PG_LEAF")) sw.opt.leaf = atoi(v);
+    if (const char* v = getenv("DSSS_PG_ND_BOTH")) sw.opt.nd_both_axes = atoi(v);
+    if (const char* v = getenv("DSSS_PG_ND_INDEX")) sw.opt.nd_index_cuts = atoi(v);
+    if (const char* v = getenv("DSSS_PG_PARTS_ANALYSIS")) sw.parts = atoi(v);
+    if (const char* v = getenv("DSSS_SYM_THREADS")) sw.threads = atoi(v);
+    if (const char* v = getenv("DSSS_PG_LOCAL")) sw.local = atoi(v) != 0;
+    if (const char* v = getenv("DSSS_PG_VERBOSE")) sw.opt.verbose = std::max(1, atoi(v));
+    return sw;
+}
+
+int pg_cheapest_gap(const int* pos, const std::vector<int>& cross, int target, int width, int after, int* cost)
+{
+    const int m = (int)cross.size() - 1, lo = std::max(target - width, after + 1);
+    auto start = [&](int i) { return pos ? pos[i - 1] + 1 : i; };
+    int best = -1; long long bdist = 0;
+    for (int i = std::max(1, pos ? (int)(std::lower_bound(pos, pos + m, lo - 1) - pos) + 1 : lo); i < m && start(i) <= target + width; ++i) {
+        const long long d = std::llabs((long long)start(i) - target);
+        if (best < 0 || cross[i] < *cost || (cross[i] == *cost && d < bdist)) { *cost = cross[i]; bdist = d; best = start(i); }
+    }
+    return best;
 }
 
 // ------------------------------------------------------------------ host twin of the numeric phase (CPU tests only)
@@ -1152,6 +1171,15 @@ int pg_host_solve(const pg_sym& S, int ne, const std::vector<std::pair<int, int>
 
 // ------------------------------------------------------------------ C ABI of the host twin (CPU test-suite; include/dsss.h)
 #include "../../include/dsss.h"
+// a host twin's statistics (stats8[5]: s5) and its return code from pg_host_solve's
+static int twin_result(const pg_sym& S, int rc, int64_t s5, int64_t* stats8)
+{
+    if (stats8) {
+        stats8[0] = S.nnzL; stats8[1] = (int64_t)S.f_c0.size(); stats8[2] = S.npanels; stats8[3] = S.nlev;
+        stats8[4] = S.front_doubles; stats8[5] = s5; stats8[6] = (int64_t)S.bincols.size(); stats8[7] = S.max_front_n;
+    }
+    return rc == 0 ? DSSS_OK : (rc == -1 ? DSSS_E_NUMERIC : DSSS_E_STATE);
+}
 extern "C" int dsss_host_pg_solve(int ns, const int32_t* edge_a, const int32_t* edge_b, int nedges, const double* cx, const double* cy,
                                   const int32_t* part, int nparts, const double* aval, const double* rhs, double* x, int64_t* stats8)
 {
@@ -1162,27 +1190,23 @@ extern "C" int dsss_host_pg_solve(int ns, const int32_t* edge_a, const int32_t* 
         if (edge_a[e] < 0 || edge_a[e] >= ns || edge_b[e] < 0 || edge_b[e] >= ns) return DSSS_E_ARG;
         if (e < ns - 1 && (edge_a[e] != e || edge_b[e] != e + 1)) return DSSS_E_ARG;       // the chain couplings come first
     }
-    pg_sym S; pg_sym_opts opt;
-    if (getenv("DSSS_PG_BIN_COST")) opt.bin_cost = atof(getenv("DSSS_PG_BIN_COST"));
-    if (getenv("DSSS_PG_LEAF")) opt.leaf = atoi(getenv("DSSS_PG_LEAF"));
-    if (getenv("DSSS_PG_ND_BOTH")) opt.nd_both_axes = atoi(getenv("DSSS_PG_ND_BOTH"));
-    pg_sym_opts_env(opt);
-    if (getenv("DSSS_SYM_THREADS")) opt.threads = std::max(1, atoi(getenv("DSSS_SYM_THREADS")));
+    pg_sym S;
+    const pg_switches sw = pg_switches_read();
+    pg_sym_opts opt = sw.opt;
+    if (sw.threads) opt.threads = std::max(1, *sw.threads);
     opt.lists_on_device = x == nullptr;                     // analysis only: as the product runs it (the bins' lists are built on the device there)
     pg_symbolic(ns, edges, ns - 1, cx, cy, part, nparts, opt, S);
     if (S.ownership_violations) return DSSS_E_STATE;        // a lower-rank end of a cross-rank factor outside the interface
     if (!x) {      // (what the product builds next; timed with the analysis by tools/sym_time.py)
         const auto t0 = std::chrono::steady_clock::now();
         pg_sched so, si; pg_build_schedule(S, 0, std::max(1, nparts), so); if (nparts > 1) pg_build_schedule(S, -1, 0, si);
-        if (getenv("DSSS_PG_VERBOSE")) fprintf(stderr, "[dsss pg symbolic] launch lists %.2f ms (%zu assembly rows, %zu panel steps, %zu tiles)\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(),
-                                               so.asmrow_front.size() + si.asmrow_front.size(), so.lv_front.size() + si.lv_front.size(), so.tile_item.size() + si.tile_item.size());
+        if (opt.verbose)
+            fprintf(stderr, "[dsss pg symbolic] launch lists %.2f ms (%zu assembly rows, %zu panel steps, %zu tiles)\n",
+                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(),
+                    so.asmrow_front.size() + si.asmrow_front.size(), so.lv_front.size() + si.lv_front.size(), so.tile_item.size() + si.tile_item.size());
     }
     const int rc = x ? pg_host_solve(S, nedges - (ns - 1), edges, aval, rhs, x) : 0;
-    if (stats8) {
-        stats8[0] = S.nnzL; stats8[1] = (int64_t)S.f_c0.size(); stats8[2] = S.npanels; stats8[3] = S.nlev;
-        stats8[4] = S.front_doubles; stats8[5] = S.comm_doubles; stats8[6] = (int64_t)S.bincols.size(); stats8[7] = S.max_front_n;
-    }
-    return rc == 0 ? DSSS_OK : (rc == -1 ? DSSS_E_NUMERIC : DSSS_E_STATE);
+    return twin_result(S, rc, S.comm_doubles, stats8);
 }
 
 // the same with a PRESCRIBED interface (pg_sym_opts::iface_last): the analysis one rank of several runs on its own separators + the
@@ -1196,9 +1220,7 @@ extern "C" int dsss_host_pg_solve_local(int ns, const int32_t* edge_a, const int
         edges[e] = { edge_a[e], edge_b[e] };
         if (edge_a[e] < 0 || edge_a[e] >= ns || edge_b[e] < 0 || edge_b[e] >= ns || edge_a[e] == edge_b[e]) return DSSS_E_ARG;
     }
-    pg_sym S; pg_sym_opts opt;
-    if (getenv("DSSS_PG_BIN_COST")) opt.bin_cost = atof(getenv("DSSS_PG_BIN_COST"));
-    pg_sym_opts_env(opt);
+    pg_sym S; pg_sym_opts opt = pg_switches_read().opt;
     for (int q = 0; q < nlast; ++q) {
         if (iface_last[q] < 0 || iface_last[q] >= ns || (q > 0 && iface_last[q] <= iface_last[q - 1])) return DSSS_E_ARG;
         opt.iface_last.push_back(iface_last[q]);
@@ -1213,11 +1235,7 @@ extern "C" int dsss_host_pg_solve_local(int ns, const int32_t* edge_a, const int
         if (!S.comm_kind.empty()) return DSSS_E_STATE;
     }
     const int rc = pg_host_solve(S, nedges, edges, aval, rhs, x);
-    if (stats8) {
-        stats8[0] = S.nnzL; stats8[1] = (int64_t)S.f_c0.size(); stats8[2] = S.npanels; stats8[3] = S.nlev;
-        stats8[4] = S.front_doubles; stats8[5] = (int64_t)S.comm_vals.size(); stats8[6] = (int64_t)S.bincols.size(); stats8[7] = S.max_front_n;
-    }
-    return rc == 0 ? DSSS_OK : (rc == -1 ? DSSS_E_NUMERIC : DSSS_E_STATE);
+    return twin_result(S, rc, (int64_t)S.comm_vals.size(), stats8);
 }
 
 // ------------------------------------------------------------------ one rank analysed by parts (dsss_pg_sym.h)
@@ -1225,7 +1243,7 @@ bool pg_symbolic_parts(int ns, const std::vector<std::pair<int, int>>& edges, in
                        const int* part, int K, int max_iface, const pg_sym_opts& opt, pg_sym& G)
 {
     (void)nchain;
-    const bool tv = getenv("DSSS_PG_VERBOSE") != nullptr;
+    const bool tv = opt.verbose;
     const auto q0 = std::chrono::steady_clock::now();
     auto ms_since = [](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count(); };
     // the interface: nodes with a neighbour in a higher part (every edge between two parts has its lower end here)
@@ -1415,6 +1433,100 @@ bool pg_symbolic_parts(int ns, const std::vector<std::pair<int, int>>& edges, in
     return true;
 }
 
+// ------------------------------------------------------------------ the analysis of the device solve (dsss_pg_sym.h)
+// RANK-LOCAL ANALYSIS (round 6; several ranks).  Rounds 2 - 5 had every rank order and analyse the WHOLE reduced graph -- 2.6 ms of serial
+// host work per solve at C3 whatever the number of GPUs, and arenas for everybody's fronts.  Now a rank analyses its OWN separators plus
+// the interface: I = the separators with a neighbour on a higher rank (exactly the nodes whose diagonal blocks take contributions from
+// two ranks -- the ownership rule of the numeric phase; every edge between two ranks has its lower end in I, so without I the ranks'
+// interiors do not touch).  Every rank holds all edges, so every rank finds the same I.  The local graph is ordered by the nested
+// dissection with I PRESCRIBED last as one dense front (pg_sym_opts::iface_last): a rank eliminates its interior, what is left on I
+// is its share of the reduced Hessian, the ranks' interface fronts -- identical in layout -- are summed IN PLACE by the all-reduce, and
+// every rank factorises the sum and substitutes back into its interior.  No structure is exchanged at all.  Kernels index separators
+// and values globally (chain order), so the local tables are translated once: perm_g / dest_g / ifslot_g / ifsep_g and the fronts'
+// value references.  A dense interface of more than PG_LOCAL_IFACE_MAX nodes (or DSSS_PG_LOCAL=0) keeps the replicated analysis with
+// its interface TREE; so does one rank holding several partitions (world == 1: the tests of the partition logic).
+void pg_analyse(int ns, const std::vector<std::pair<int, int>>& edges, const double* cx, const double* cy, const int* part, int nparts,
+                int part_lo, int part_hi, int world, int rank, const pg_switches& sw, pg_sym_opts opt, pg_analysis& A)
+{
+    // ranges per parallel phase of the analysis: eight for a graph of C3's size (more forks cost what they gain at 23 k separators; 16 gain
+    // another 10 % on an idle 128-core host), up to twenty-four from a few hundred thousand separators on (C5: 635 k), where a phase is
+    // milliseconds of work.  The worker pool holds up to 23 threads.
+    auto sym_threads = [&](int m) { return sw.threads && *sw.threads > 0 ? *sw.threads : (int)std::min(m >= 131072 ? 24u : 8u, std::max(1u, std::thread::hardware_concurrency())); };
+    opt.bin_cost = sw.bin_cost.value_or(PG_BIN_COST_DEVICE);
+    opt.threads = sym_threads(ns);
+    pg_sym& S = A.S;
+    std::vector<int> loc_of, glob_of, ledge_g;
+    std::vector<std::pair<int, int>> ledges;
+    if (world > 1 && sw.local) {
+        std::vector<int> rank_of_part(nparts, 0);
+        for (int r = 0; r < world; ++r) for (int p = (int)((long long)nparts * r / world); p < (int)((long long)nparts * (r + 1) / world); ++p) rank_of_part[p] = r;
+        std::vector<char> isif(ns, 0);
+        for (const auto& e : edges) {
+            const int ra = rank_of_part[part[e.first]], rb = rank_of_part[part[e.second]];
+            if (ra < rb) isif[e.first] = 1; else if (rb < ra) isif[e.second] = 1;
+        }
+        int nif_l = 0; for (int k = 0; k < ns; ++k) nif_l += isif[k];
+        if (nif_l <= PG_LOCAL_IFACE_MAX) {
+            A.local = true;
+            loc_of.assign(ns, -1);
+            for (int k = 0; k < ns; ++k)
+                if (isif[k] || rank_of_part[part[k]] == rank) { loc_of[k] = (int)glob_of.size(); if (isif[k]) opt.iface_last.push_back(loc_of[k]); glob_of.push_back(k); }
+            for (size_t g = 0; g < edges.size(); ++g) {
+                const int a = loc_of[edges[g].first], b = loc_of[edges[g].second];
+                if (a >= 0 && b >= 0 && a != b) { ledges.push_back({ a, b }); ledge_g.push_back((int)g); }
+            }
+        }
+    }
+    if (A.local) {
+        const int nsl = (int)glob_of.size();
+        std::vector<double> cxl(nsl), cyl(nsl);
+        const std::function<void()> coords = opt.before_order;
+        opt.before_order = [&] { if (coords) coords(); for (int i = 0; i < nsl; ++i) { cxl[i] = cx[glob_of[i]]; cyl[i] = cy[glob_of[i]]; } };
+        opt.on_bottom_ready = nullptr; opt.on_lists_ready = nullptr;      // (nothing goes up early: the tables below come last)
+        if (!sw.bin_cost && nsl < 16384) opt.bin_cost = PG_BIN_COST_RANK;
+        opt.threads = sym_threads(nsl);
+        pg_symbolic(nsl, ledges, 0, cxl.data(), cyl.data(), nullptr, 1, opt, S);
+        pg_build_schedule(S, 0, 1, A.SO);
+        pg_build_schedule(S, -1, 0, A.SI);
+        const int nval_g = ns + (int)edges.size();
+        A.perm_g.assign(ns, -1); A.dest_g.assign(nval_g, -1); A.ifslot_g.assign(ns, -1);
+        for (int i = 0; i < nsl; ++i) { A.perm_g[glob_of[i]] = S.perm[i]; A.dest_g[glob_of[i]] = S.dest_bin[i]; }
+        for (size_t le = 0; le < ledges.size(); ++le) A.dest_g[ns + ledge_g[le]] = S.dest_bin[nsl + le];
+        for (int& v : S.fa_src) v = v >= S.nval ? nval_g + (v - S.nval) : (v < nsl ? glob_of[v] : ns + ledge_g[v - nsl]);
+        for (size_t q = 0; q < S.iface_seps.size(); ++q) { const int k = glob_of[S.iface_seps[q]]; A.ifsep_g.push_back(k); A.ifslot_g[k] = (int)q; }
+        return;
+    }
+    // ONE rank, one partition: the analysis BY PARTS (pg_symbolic_parts, round 6).  The phases of pg_symbolic gain nothing from threads at
+    // C3's size (one thread 4.0 ms, eight 3.4: a dozen fork / joins around 0.1 - 0.3 ms of work each), whole parts do: the chain order is
+    // cut into K parts where few loop closures cross (the gap with the fewest spanning loop closures within a third of a part of the
+    // equal-count position: one difference array over the separators prices them all), every part is ordered and analysed on its own
+    // thread with the interface between the parts as the last dense front, and the tables are joined.
+    bool by_parts = false;
+    // (parts of about a thousand separators, at most 8, up to C3's size -- C2: 3 292 separators in 3 parts, step 7.6 -> 6.6 ms --; 16 from 64 k separators on)
+    int K = sw.parts ? *sw.parts : (ns >= 1500 ? (ns < 65536 ? std::min(8, std::max(2, ns / 1000)) : 16) : 0);
+    // (the parts need threads of their own: on a host with fewer than four the one graph is the shorter analysis)
+    if (!sw.parts) { const int hw = (int)std::thread::hardware_concurrency(); K = hw >= 4 ? std::min(K, hw) : 0; }
+    if (nparts == 1 && K >= 2 && (int)edges.size() > ns - 1) {
+        K = std::min(K, ns / 8);
+        std::vector<int> cross(ns + 1, 0), vpart(ns, 0);
+        for (size_t g = (size_t)ns - 1; g < edges.size(); ++g) { const auto [a, b] = edges[g]; cross[std::min(a, b) + 1]++; cross[std::max(a, b) + 1]--; }
+        for (int k = 1; k <= ns; ++k) cross[k] += cross[k - 1];      // cross[g]: loop closures that span the gap between separators g - 1 and g
+        int prev = 0, p_cur = 0;
+        std::vector<int> starts;
+        for (int p = 1; p < K; ++p) {
+            int bcost = 0;
+            const int best = pg_cheapest_gap(nullptr, cross, (int)((long long)ns * p / K), ns / K / 3, prev, &bcost);
+            if (best > prev && bcost <= std::max(PG_PARTS_CUT_MAX, ns / 16384)) { starts.push_back(best); prev = best; }      // (an expensive boundary is left out: its two parts stay one)
+        }
+        for (int k = 0; k < ns; ++k) { while (p_cur < (int)starts.size() && k >= starts[p_cur]) ++p_cur; vpart[k] = p_cur; }
+        if (!starts.empty()) by_parts = pg_symbolic_parts(ns, edges, ns - 1, cx, cy, vpart.data(), (int)starts.size() + 1, PG_PARTS_IFACE_MAX, opt, S);
+    }
+    if (!by_parts) pg_symbolic(ns, edges, ns - 1, cx, cy, nparts > 1 ? part : nullptr, nparts, opt, S);
+    // launch lists: this rank's interior fronts, then (after the all-reduce) the replicated interface fronts
+    pg_build_schedule(S, part_lo, part_hi, A.SO);
+    if (nparts > 1) pg_build_schedule(S, -1, 0, A.SI);
+}
+
 // host twin entry: one rank analysed by K parts of equal size in the chain order (CPU test-suite)
 extern "C" int dsss_host_pg_solve_parts(int ns, const int32_t* edge_a, const int32_t* edge_b, int nedges, const double* cx, const double* cy,
                                         int K, const double* aval, const double* rhs, double* x, int64_t* stats8)
@@ -1426,16 +1538,10 @@ extern "C" int dsss_host_pg_solve_parts(int ns, const int32_t* edge_a, const int
         if (edge_a[e] < 0 || edge_a[e] >= ns || edge_b[e] < 0 || edge_b[e] >= ns) return DSSS_E_ARG;
         if (e < ns - 1 && (edge_a[e] != e || edge_b[e] != e + 1)) return DSSS_E_ARG;
     }
-    pg_sym S; pg_sym_opts opt;
-    if (getenv("DSSS_PG_BIN_COST")) opt.bin_cost = atof(getenv("DSSS_PG_BIN_COST"));
-    pg_sym_opts_env(opt);
+    pg_sym S; pg_sym_opts opt = pg_switches_read().opt;
     std::vector<int> part(ns);
     for (int k = 0; k < ns; ++k) part[k] = (int)((long long)k * K / ns);
     if (!pg_symbolic_parts(ns, edges, ns - 1, cx, cy, part.data(), K, ns, opt, S)) return DSSS_E_STATE;
     const int rc = pg_host_solve(S, nedges - (ns - 1), edges, aval, rhs, x);
-    if (stats8) {
-        stats8[0] = S.nnzL; stats8[1] = (int64_t)S.f_c0.size(); stats8[2] = S.npanels; stats8[3] = S.nlev;
-        stats8[4] = S.front_doubles; stats8[5] = 0; stats8[6] = (int64_t)S.bincols.size(); stats8[7] = S.max_front_n;
-    }
-    return rc == 0 ? DSSS_OK : (rc == -1 ? DSSS_E_NUMERIC : DSSS_E_STATE);
+    return twin_result(S, rc, 0, stats8);
 }

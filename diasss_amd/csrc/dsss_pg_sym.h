@@ -19,6 +19,7 @@
 // (/root/reference/src/core/optimizer.cpp:134-139, 265-279).
 #pragma once
 #include <functional>
+#include <optional>
 #include <vector>
 
 // fn(t) for t in [0, T) on the process-wide worker pool of the analysis (threads that outlive the call: no thread is created per
@@ -26,6 +27,14 @@
 void dsss_pool_run(int T, const std::function<void(int)>& fn);
 
 #define PG_PW 16                        // panel width in block columns (96 scalar columns)
+#define PG_PARTS_CUT_MAX 12             // analysis by parts: loop closures a boundary between two parts may cross (each puts a separator into the interface)
+#define PG_PARTS_IFACE_MAX 256          // one rank analysed by parts (pg_symbolic_parts): separators of the interface between the parts, one dense front
+#define PG_LOCAL_IFACE_MAX 160          // rank-local analysis (pg_analyse): separators of the ONE dense interface front (960 scalar columns, 7.4 MB summed
+                                        // per trial); beyond, the replicated analysis with its interface tree
+
+// Work bound of a binned subtree without DSSS_PG_BIN_COST: the host twins (CPU tests, tools); the device solve (optimum at C3: 500 - 700);
+// a rank-local analysis of < 16 k separators, whose share of the bins leaves most of the chip empty (slowest rank of 8 at C3: 12.2 -> 11.5 ms)
+constexpr double PG_BIN_COST_HOST = 1000, PG_BIN_COST_DEVICE = 600, PG_BIN_COST_RANK = 120;
 
 struct pg_sym {
     int ns = 0, nparts = 1;
@@ -112,7 +121,7 @@ struct pg_sym_opts {
     int nd_both_axes = 64;              // node sets of at least this size try the median cut along both axes and keep the smaller separator
     int nd_index_cuts = 1;              // a third cut candidate of every node set: the cheapest cut of the CHAIN ORDER with both sides between a third and two thirds of the set (dsss_pg_sym.cpp, nd_order).  0 = coordinate medians only: the ordering of rounds 2 - 4
     bool nd_geo_first = true;           // a node set that spans several ranks may take a geometric cut when its separator is smaller than the rank cut's (its separator is interface then)
-    double bin_cost = 1000;             // work bound of a binned subtree
+    double bin_cost = PG_BIN_COST_HOST; // work bound of a binned subtree
     double pack_cost = 0;               // work bound of a BIN (several subtrees packed together); 0 = bin_cost
     int threads = 4;
     // relaxed amalgamation of a front into its parent (columns adjacent): accepted when it adds at most relax_zero_blocks
@@ -137,9 +146,23 @@ struct pg_sym_opts {
     std::vector<int> iface_last;
     bool to_be_joined = false;          // pg_symbolic_parts: the panel levels and the per-row views of the fronts are built once, on the joined tables
     bool iface_plain = false;           // with iface_last: the interface values stay ordinary values of the value array (no summed slots): one rank analysing by parts (pg_symbolic_parts)
+    int verbose = 0;                    // DSSS_PG_VERBOSE: phase times; 2 and up: the critical path of the schedule as well
 };
 
-void pg_sym_opts_env(pg_sym_opts& opt);    // DSSS_PG_ND_BOTH / DSSS_PG_LEAF overrides (analysis knobs kept for tools/pg_sweep.sh)
+// The pose-graph switches (environment variables), read afresh on every call: tests flip them between the calls on one context.
+struct pg_switches {
+    pg_sym_opts opt;                                // DSSS_PG_BIN_COST, _LEAF, _ND_BOTH, _ND_INDEX, _VERBOSE (at least 1 when set) over the defaults
+    std::optional<double> bin_cost;                 // DSSS_PG_BIN_COST, if set (the device solve has defaults of its own)
+    std::optional<int> parts, threads;              // DSSS_PG_PARTS_ANALYSIS (parts of one rank's analysis; 0: one graph), DSSS_SYM_THREADS
+    bool local = true;                              // DSSS_PG_LOCAL=0: several ranks keep the replicated analysis
+};
+pg_switches pg_switches_read();
+
+// The cheapest gap of a chain of nodes at ascending positions pos[0 .. m) (pos == nullptr: pos[i] = i), where cross[i] counts the
+// loop closures that span the gap between node i - 1 and node i: among the gaps whose next part would start at s = pos[i - 1] + 1
+// with s > after and |s - target| <= width, the one of least cross[i], the nearest to target on ties (the first of those).  Returns s
+// and its cost, or -1.  (The partition boundaries of the device solve; the cuts of the analysis by parts.)
+int pg_cheapest_gap(const int* pos, const std::vector<int>& cross, int target, int width, int after, int* cost);
 
 // edges: pairs of chain-order separator indices, the ns-1 chain couplings (k, k+1) first, then the LC edges.
 // part[k] (may be null): rank that owns separator k, non-decreasing in k.  cx, cy: DR positions of the separators.
@@ -154,6 +177,18 @@ void pg_symbolic(int ns, const std::vector<std::pair<int, int>>& edges, int ncha
 // each: one thread 4.0 ms, eight 3.4); whole parts do.  Returns false (S untouched) when the interface is wider than max_iface separators.
 bool pg_symbolic_parts(int ns, const std::vector<std::pair<int, int>>& edges, int nchain, const double* cx, const double* cy,
                        const int* part, int K, int max_iface, const pg_sym_opts& opt, pg_sym& S);
+
+// The analysis of the device solve (dsss_pg.hip) and how it is chosen: the rank-local analysis (several ranks), the analysis by parts
+// (one rank, one partition, a large graph) or the one graph.  edges: as pg_symbolic's, chain first; part[k]: partition of separator k;
+// partitions [part_lo, part_hi) of nparts are this rank's.  opt: the caller's hooks (before_order, on_bottom_ready, on_lists_ready).
+struct pg_analysis {
+    pg_sym S;
+    pg_sched SO, SI;                    // launch lists: this rank's interior fronts; the interface fronts (after the all-reduce)
+    bool local = false;                 // rank-local: S covers this rank's separators and the interface only, translated below
+    std::vector<int> perm_g, dest_g, ifslot_g, ifsep_g;     // (rank-local) S's permutation, destinations and interface in global indices
+};
+void pg_analyse(int ns, const std::vector<std::pair<int, int>>& edges, const double* cx, const double* cy, const int* part, int nparts,
+                int part_lo, int part_hi, int world, int rank, const pg_switches& sw, pg_sym_opts opt, pg_analysis& A);
 
 // Host twin of the numeric phase, used by the CPU test-suite only (the product path is dsss_pg.hip): factorises the matrix
 // given by `aval` (36 doubles per value index, see dest_bin) and solves for `rhs` (6 per separator, chain order).  Returns 0

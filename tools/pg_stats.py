@@ -17,7 +17,7 @@ a, b, N, F = d["a"], d["b"], int(d["N"]), int(d["F"])
 n = N * F
 sv = Survey(F, N, 1024 if N == 2000 else 512, seed=20240601 + (1 if N == 2000 else 0))
 dr = np.concatenate([sv.inputs(f)[0] for f in range(F)])
-# the TRUE separators of the two-level chain elimination (dsss_pg.hip, pg_solve_impl): LC-touched poses, both ends, partition
+# the TRUE separators of the two-level chain elimination (dsss_pg.hip, pg_solve::separators): LC-touched poses, both ends, partition
 # ends, and one pose every 16 chunks inside gaps of 16 chunks or more
 is_sep = np.zeros(n, bool); is_sep[0] = is_sep[-1] = True; is_sep[a] = True; is_sep[b] = True
 fpr = (F + nparts - 1) // nparts

@@ -27,7 +27,7 @@ if which in ("c3", "c5real"):
     dr = np.concatenate([sv.inputs(f)[0] for f in range(F)])
     is_sep = np.zeros(n, bool); is_sep[0] = is_sep[-1] = True; is_sep[a] = True; is_sep[b] = True
     pb = [(F * q // nparts) * N for q in range(nparts)] + [n]
-    if nparts > 1 and os.environ.get("SYM_MOVE", "1") != "0":          # the boundaries move to their cheapest cuts (pg_solve_impl)
+    if nparts > 1 and os.environ.get("SYM_MOVE", "1") != "0":          # the boundaries move to their cheapest cuts (pg_solve::move_boundaries)
         ends = np.nonzero(is_sep)[0]
         lo = np.searchsorted(ends, np.minimum(a, b)); hi = np.searchsorted(ends, np.maximum(a, b))
         cross = np.zeros(len(ends) + 2, np.int64); np.add.at(cross, lo + 1, 1); np.add.at(cross, hi + 1, -1); cross = np.cumsum(cross)
@@ -44,7 +44,7 @@ if which in ("c3", "c5real"):
         print("partition boundaries", pb[1:-1], "crossing loop closures", [int(cross[np.searchsorted(ends, x - 1) + 1]) for x in pb[1:-1]])
     for q in range(1, nparts):
         is_sep[pb[q] - 1] = True
-    # gaps of 16 chunks or more get separators of their own (pg_solve_impl): the first chunk end at least 256 poses after the last one
+    # gaps of 16 chunks or more get separators of their own (pg_solve::separators): the first chunk end at least 256 poses after the last one
     marked = np.nonzero(is_sep)[0]
     fill = []
     for lo, hi in zip(marked[:-1], marked[1:]):
