@@ -87,11 +87,7 @@ private:
 template <class F> void par_ranges(int n, int T, F fn)          // fn(t, lo, hi) over T contiguous ranges of [0, n)
 {
     T = std::max(1, std::min(T, std::max(n, 1)));
-    pg_pool& P = pg_pool::get();
-    std::vector<pg_pool::task> tk(T > 1 ? T - 1 : 0);
-    for (int t = 1; t < T; ++t) { tk[t - 1].fn = [&fn, n, T, t] { fn(t, (int)((long long)n * t / T), (int)((long long)n * (t + 1) / T)); }; P.fork(&tk[t - 1]); }
-    fn(0, 0, (int)((long long)n / T));
-    for (auto& x : tk) P.join(&x);
+    dsss_pool_run(T, [&](int t) { fn(t, (int)((long long)n * t / T), (int)((long long)n * (t + 1) / T)); });
 }
 
 } // namespace
@@ -107,7 +103,6 @@ void dsss_pool_run(int T, const std::function<void(int)>& fn)
 }
 
 namespace {
-
 // nested dissection with vertex separators taken from the lower half.  The order of a subtree is [A][B][separator]; A and B
 // never touch, so the first PG_ND_PAR levels run their two halves on two host threads and the same tree of ranges later
 // drives the parallel column-structure pass.  While a node set spans several ranks the cut is the rank boundary (lower
@@ -129,6 +124,223 @@ struct nd_ctx {
 struct nd_timer { std::atomic<long long>* a; std::chrono::steady_clock::time_point t0;
                   nd_timer(std::atomic<long long>* tns, int k) : a(tns ? tns + k : nullptr) { if (a) t0 = std::chrono::steady_clock::now(); }
                   ~nd_timer() { if (a) *a += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count(); } };
+// The separator of a split (sides are marked in sd: 1 lower half, 2 upper half): a lower-half node with a neighbour in the upper half --
+// except that of a cut edge between nodes of DIFFERENT ranks it is always the lower-rank end that goes into the separator.  The numeric
+// phase relies on that: a factor belongs to the rank of its higher pose and adds to the diagonal block of the lower one, which therefore
+// has to be an interface separator (summed over the ranks).  Rank cuts satisfy it by themselves (lower ranks are the lower half).
+// nd_cut_node: v (lower half) is in it; a lower-rank upper neighbour is marked 4 and counted in cnt instead (multi only: else nothing is written)
+bool nd_cut_node(const nd_ctx& C, bool multi, char* sd, int v, size_t& cnt)
+{
+    bool cut = false;
+    for (int q = C.adj_ptr[v]; q < C.adj_ptr[v + 1]; ++q) {
+        const int u = C.adj_idx[q];
+        if (sd[u] != 2 && sd[u] != 4) continue;
+        if (multi && C.part[u] < C.part[v]) { if (sd[u] == 2) { sd[u] = 4; ++cnt; } }      // the upper-half end has the lower rank
+        else { cut = true; if (!multi) break; }
+    }
+    return cut;
+}
+// the size of that separator over the nodes nd[0, n); a, s: when given, receive the lower-half nodes outside / inside it
+size_t nd_count_sep(const nd_ctx& C, bool multi, char* sd, const int* nd, size_t n, std::vector<int>* a = nullptr, std::vector<int>* s = nullptr)
+{
+    size_t cnt = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const int v = nd[i];
+        if (sd[v] != 1) continue;
+        if (nd_cut_node(C, multi, sd, v, cnt)) { ++cnt; if (s) s->push_back(v); } else if (a) a->push_back(v);
+    }
+    return cnt;
+}
+// the split of nd into its first h nodes and the rest, marked in sd (C.side, or C.side2 for a candidate evaluated on another thread);
+// b: when given, receives the upper half without its separator nodes
+size_t nd_boundary(const nd_ctx& C, bool multi, char* sd, const std::vector<int>& nd, size_t h, std::vector<int>* a = nullptr, std::vector<int>* s = nullptr, std::vector<int>* b = nullptr)
+{
+    for (size_t i = 0; i < nd.size(); ++i) sd[nd[i]] = i < h ? 1 : 2;
+    const size_t cnt = nd_count_sep(C, multi, sd, nd.data(), h, a, s);
+    if (s || b) for (size_t i = h; i < nd.size(); ++i) { const int u = nd[i]; if (sd[u] == 4) { if (s) s->push_back(u); } else if (b) b->push_back(u); }
+    return cnt;
+}
+// split at the median of the (coordinate, index) total order; only the two halves matter, not their inner order
+// (round 4: the selection runs on a contiguous array of (coordinate, index) pairs -- through the index array every comparison was two
+// dependent loads into the coordinate table, and the top of the recursion, where one or two threads hold most of the nodes, is the
+// serial part of the ordering.  The two halves are determined by the total order alone: same sets, same elimination order.)
+void nd_median_split(const nd_ctx& C, std::vector<int>& nd, bool bx)
+{
+    const double* key = bx ? C.cx : C.cy;
+    const size_t h2 = nd.size() / 2;
+    if (nd.size() < 96) {
+        std::nth_element(nd.begin(), nd.begin() + h2, nd.end(), [&](int a, int b) {
+            const double ka = key[a], kb = key[b];
+            return ka != kb ? ka < kb : a < b; });
+        return;
+    }
+    std::vector<std::pair<double, int>> kv(nd.size());
+    for (size_t i = 0; i < nd.size(); ++i) kv[i] = { key[nd[i]], nd[i] };
+    std::nth_element(kv.begin(), kv.begin() + h2, kv.end());       // pair order = (coordinate, index): the comparator above
+    for (size_t i = 0; i < nd.size(); ++i) nd[i] = kv[i].second;
+}
+// A CANDIDATE is only counted, not carried out: the element of rank h2 of the (coordinate, index) order is found through a
+// histogram of the coordinates (one pass over a contiguous copy of the keys, then a selection inside ONE bucket), the halves are
+// marked by comparing with it, and the separator is counted from the marks -- three light passes instead of a selection that moves
+// 16-byte pairs about.  Only the winner is partitioned.  Same halves (they are determined by the total order), same counts.
+// axis 0 = y, 1 = x: median cuts of the dead-reckoned coordinates.  2 = a cut of the CHAIN ORDER (round 5, nd_chain_cut below): a
+// survey is a lawn-mower chain, consecutive separators lie on one leg, so a cut of the chain order runs BETWEEN two legs (or through
+// one leg at ONE chain edge) and costs the loop closures that cross it.  The median of y does the same only on paper -- the median
+// node sits in the middle of some leg whose dead-reckoned y wanders by centimetres, and the cut zig-zags through that leg's chain
+// edges -- and, worse, it is taken wherever the median happens to fall.
+struct cut_cand { int bx; double pk; int pi; size_t cnt; size_t half; };
+bool nd_less(double k, int v, double pk, int pi) { return k != pk ? k < pk : v < pi; }
+// the median cut of nd along axis bx (coordinates within [lo, hi]); kx: scratch of the keys, sd: scratch of the marks
+cut_cand nd_count_cut(const nd_ctx& C, bool multi, const std::vector<int>& nd, int bx, double lo, double hi, std::vector<double>& kx, char* sd)
+{
+    const double* key = bx == 1 ? C.cx : C.cy;
+    const size_t m = nd.size(), h2 = m / 2;
+    kx.resize(m);
+    // (sets of 64 k nodes and more -- the top of the recursion at C5's 635 k separators, where one or two threads hold everything --
+    // run their passes over ranges of the set; same marks, same counts)
+    const int TP = (m >= 65536 && !multi) ? std::max(1, C.threads) : 1;
+    par_ranges((int)m, TP, [&](int, int a0, int a1) { for (int i = a0; i < a1; ++i) kx[i] = key[nd[i]]; });
+    cut_cand cc{ bx, 0.0, 0, 0, h2 };
+    constexpr int NB = 1024;
+    if (hi > lo && std::isfinite(hi - lo)) {
+        const double scale = NB / (hi - lo);
+        auto bucket = [&](double k) { const int b = (int)((k - lo) * scale); return b < 0 ? 0 : (b >= NB ? NB - 1 : b); };      // monotone in k
+        unsigned hist[NB] = { 0 };
+        if (TP > 1) {
+            std::vector<unsigned> ph((size_t)TP * NB, 0u);
+            par_ranges((int)m, TP, [&](int t, int a0, int a1) { unsigned* h = ph.data() + (size_t)t * NB; for (int i = a0; i < a1; ++i) h[bucket(kx[i])]++; });
+            for (int t = 0; t < TP; ++t) for (int q = 0; q < NB; ++q) hist[q] += ph[(size_t)t * NB + q];
+        } else for (size_t i = 0; i < m; ++i) hist[bucket(kx[i])]++;
+        size_t below = 0; int b = 0;
+        while (below + hist[b] <= h2) below += hist[b++];              // the bucket that holds rank h2 (h2 < m)
+        std::vector<std::pair<double, int>> in;
+        in.reserve(hist[b]);
+        for (size_t i = 0; i < m; ++i) if (bucket(kx[i]) == b) in.push_back({ kx[i], nd[i] });
+        std::nth_element(in.begin(), in.begin() + (h2 - below), in.end());
+        cc.pk = in[h2 - below].first; cc.pi = in[h2 - below].second;
+    } else {                                                          // all coordinates equal (or not finite): the order is the index order
+        std::vector<std::pair<double, int>> in(m);
+        for (size_t i = 0; i < m; ++i) in[i] = { kx[i], nd[i] };
+        std::nth_element(in.begin(), in.begin() + h2, in.end());
+        cc.pk = in[h2].first; cc.pi = in[h2].second;
+    }
+    par_ranges((int)m, TP, [&](int, int a0, int a1) { for (int i = a0; i < a1; ++i) sd[nd[i]] = nd_less(kx[i], nd[i], cc.pk, cc.pi) ? 1 : 2; });
+    if (TP > 1) {                                                     // (one partition: the marks are only read here)
+        std::vector<size_t> pc(TP, 0);
+        par_ranges((int)m, TP, [&](int t, int a0, int a1) {
+            size_t c2 = 0;
+            for (int i = a0; i < a1; ++i) { const int v = nd[i]; if (sd[v] == 1 && nd_cut_node(C, false, sd, v, c2)) ++c2; }
+            pc[t] = c2;
+        });
+        for (size_t c2 : pc) cc.cnt += c2;
+    } else cc.cnt = nd_count_sep(C, multi, sd, nd.data(), m);
+    par_ranges((int)m, TP, [&](int, int a0, int a1) { for (int i = a0; i < a1; ++i) sd[nd[i]] = 0; });
+    return cc;
+}
+// The chain-order candidate.  Node sets are kept in ascending index order (every split is a stable partition), so a cut of the
+// chain order is a position p of the list: nodes [0, p) below, [p, m) above.  A node of rank r whose highest neighbour inside the
+// set has rank R > r is a separator node of every cut r < p <= R: one difference array prices ALL positions in one pass over the
+// edges, and the cheapest position of the balance window [m / 3, 2 m / 3] is the candidate (the one nearest the middle among equals).
+// On the C5 graph the cost of a cut between two legs varies from 23 to 740 separator nodes with the pair of legs it runs between
+// (few loop closures where two legs barely overlap); the median position is rarely a cheap one.  With this candidate the C3 graph
+// factorises in 12 panel levels instead of 29 (0.6 instead of 2.1 GFLOP, largest front 49 instead of 140 block rows), the C5 graph
+// in 37 instead of 169 (30 instead of 457 GFLOP, 172 instead of 1 184 block rows).
+cut_cand nd_chain_cut(const nd_ctx& C, const std::vector<int>& nd)
+{
+    const size_t m = nd.size(), h2 = m / 2;
+    cut_cand cc{ 2, 0.0, 0, (size_t)-1, h2 };
+    const int TP = m >= 65536 ? std::max(1, C.threads) : 1;
+    par_ranges((int)m, TP, [&](int, int a0, int a1) { for (int r = a0; r < a1; ++r) C.pos[nd[r]] = r; });
+    std::vector<int> diff(m + 2, 0);
+    par_ranges((int)m, TP, [&](int, int a0, int a1) {
+        for (int r = a0; r < a1; ++r) {
+            const int v = nd[r];
+            int R = -1;
+            for (int q = C.adj_ptr[v]; q < C.adj_ptr[v + 1]; ++q) { const int pu = C.pos[C.adj_idx[q]]; if (pu > R) R = pu; }      // (neighbours outside the set sit in separators: -1)
+            if (R > r) {
+                if (TP > 1) { __atomic_fetch_add(&diff[(size_t)r + 1], 1, __ATOMIC_RELAXED); __atomic_fetch_sub(&diff[(size_t)R + 1], 1, __ATOMIC_RELAXED); }
+                else { diff[(size_t)r + 1]++; diff[(size_t)R + 1]--; }
+            }
+        }
+    });
+    const size_t lo = std::max<size_t>(1, m / 3), hi = std::min(m - 1, m - m / 3);      // (windows of +-2 / 5 / 10 / 17 / 25 % of the set: C3 17 / 14 / 12 / 12 / 13 panel levels, C5 59 / 41 / 47 / 37 / 35)
+    long long run = 0;
+    for (size_t p2 = 1; p2 <= hi; ++p2) {
+        run += diff[p2];
+        if (p2 < lo) continue;
+        const size_t c = (size_t)run, dist = p2 > h2 ? p2 - h2 : h2 - p2, bdist = cc.half > h2 ? cc.half - h2 : h2 - cc.half;
+        if (c < cc.cnt || (c == cc.cnt && dist < bdist)) { cc.cnt = c; cc.half = p2; }
+    }
+    cc.pi = nd[cc.half];
+    return cc;
+}
+void nd_carry_out(const nd_ctx& C, std::vector<int>& nd, const cut_cand& cc)      // lower half first, both halves in ascending index order
+{
+    if (cc.bx == 2) return;                                           // (a position of the sorted list: nothing moves)
+    const double* key = cc.bx == 1 ? C.cx : C.cy;
+    std::stable_partition(nd.begin(), nd.end(), [&](int v) { return nd_less(key[v], v, cc.pk, cc.pi); });
+}
+// candidates besides the rank cut: the median cut along the longer extent and -- for sets of at least both_axes nodes -- along the other
+// axis too, and the chain-order cut.  A survey is a long strip of parallel legs: the cut across the longer extent is not the cheaper one
+// once a piece holds few legs (a cut between legs costs the loop closures of two legs, a cut across them one pose per leg), and rank cuts
+// are cuts between legs.  The smallest separator wins; ties go to the rank cut (best, half on entry), then to the longer extent.  The
+// winner is carried out (nodes: lower half first) and leaves its size in best, its lower half's size in half.  (With geo_first off a multi-rank
+// set always takes its rank cut: every rank's interior is then ONE range of the order, the layout of rounds 1-2.)
+void nd_geo_cut(const nd_ctx& C, bool multi, std::vector<int>& nodes, int depth, size_t& best, size_t& half)
+{
+    nd_timer tm(C.tns, 1);
+    const int total = (int)nodes.size();
+    double x0 = 1e300, x1 = -1e300, y0 = 1e300, y1 = -1e300; int i0 = 1 << 30, i1 = -1;
+    for (int v : nodes) { x0 = std::min(x0, C.cx[v]); x1 = std::max(x1, C.cx[v]); y0 = std::min(y0, C.cy[v]); y1 = std::max(y1, C.cy[v]); i0 = std::min(i0, v); i1 = std::max(i1, v); }
+    const bool byx = (x1 - x0) >= (y1 - y0);
+    const size_t h2 = nodes.size() / 2;
+    const double lo_of[3] = { y0, x0, (double)i0 }, hi_of[3] = { y1, x1, (double)i1 };           // [bx]
+    const bool idx_cand = C.index_cuts && total >= C.both_axes && total >= 96;      // (only from 512 / 2 048 / 4 096 / 16 384 nodes on: C3 13 / 13 / 14 / 35 panel levels instead of 12, C5 35 / 36 / 37 / 44 instead of 35 -- the big sets matter most, the small ones still count)
+    // The chain-order candidate goes first, and a very cheap one (at most 1/1024 of the set) ends the search: at the top of the recursion --
+    // the serial part of the ordering -- it costs one pass over the set's edges and wins anyway (C3: 1 to 7 separator nodes where the
+    // coordinate medians cost 26 to 207), the coordinate candidates are a histogram selection and a counting pass each.
+    cut_cand c3{};
+    if (idx_cand) {
+        c3 = nd_chain_cut(C, nodes);
+        if (c3.cnt < best && c3.cnt * 1024 <= (size_t)total) { best = c3.cnt; half = c3.half; return; }      // (1/64 took cuts of 700 nodes where the cut across 79 k nodes of C5 costs 140: twice the flops)
+    }
+    std::vector<double> keys;                                          // (one candidate at a time per call; the second one of a large set brings its own)
+    if (!multi && total < C.both_axes) { nd_median_split(C, nodes, byx); half = h2; }       // the only candidate: nothing to compare
+    else if (nodes.size() < 96) {
+        std::vector<int> cand;
+        for (int pass = 0; pass < (total >= C.both_axes ? 2 : 1); ++pass) {
+            cand = nodes;
+            nd_median_split(C, cand, pass == 0 ? byx : !byx);
+            const size_t c = nd_boundary(C, multi, C.side, cand, h2);
+            if (c < best) { best = c; nodes.swap(cand); half = h2; }
+        }
+    }
+    else if (total >= C.both_axes && total >= 4096 && depth <= PG_ND_PAR) {
+        // both axes, large set: the two candidates are counted at the same time (the top of the recursion is the serial part of the
+        // ordering); the marks of a node set are private to the call that holds it, the second candidate marks in side2
+        cut_cand c2{};
+        std::vector<double> keys2;
+        pg_pool::task tk; tk.fn = [&] { c2 = nd_count_cut(C, multi, nodes, (int)!byx, lo_of[!byx], hi_of[!byx], keys2, C.side2); };
+        pg_pool::get().fork(&tk);
+        const cut_cand c1 = nd_count_cut(C, multi, nodes, (int)byx, lo_of[byx], hi_of[byx], keys, C.side);
+        pg_pool::get().join(&tk);
+        const cut_cand* win = nullptr;
+        if (c1.cnt < best) { best = c1.cnt; win = &c1; }
+        if (c2.cnt < best) { best = c2.cnt; win = &c2; }
+        if (idx_cand && c3.cnt < best) { best = c3.cnt; win = &c3; }
+        if (win) { nd_carry_out(C, nodes, *win); half = win->half; }
+    }
+    else {
+        cut_cand wc{}; bool have = false;
+        for (int pass = 0; pass < (total >= C.both_axes ? 2 : 1); ++pass) {
+            const int bx = pass == 0 ? (int)byx : (int)!byx;
+            const cut_cand c = nd_count_cut(C, multi, nodes, bx, lo_of[bx], hi_of[bx], keys, C.side);
+            if (c.cnt < best) { best = c.cnt; wc = c; have = true; }
+        }
+        if (idx_cand && c3.cnt < best) { best = c3.cnt; wc = c3; have = true; }
+        if (have) { nd_carry_out(C, nodes, wc); half = wc.half; }
+    }
+}
 int nd_order(std::vector<int>& nodes, const nd_ctx& C, std::vector<int>& order, int depth)
 {
     auto new_node = [&](int a, int b, int size) { std::lock_guard<std::mutex> g(*C.mu); C.pool->push_back({ a, b, size }); return (int)C.pool->size() - 1; };
@@ -140,231 +352,16 @@ int nd_order(std::vector<int>& nodes, const nd_ctx& C, std::vector<int>& order, 
     const bool multi = pmax > pmin;
     if (!multi && total <= C.leaf) { nd_timer tm(C.tns, 4); std::sort(nodes.begin(), nodes.end()); for (int v : nodes) order.push_back(v); return depth <= PG_ND_PAR ? new_node(-1, -1, total) : -1; }
     std::vector<int> A, B, S;
-    // The separator of a split (sides are marked in C.side): a lower-half node with a neighbour in the upper half -- except that of a
-    // cut edge between nodes of DIFFERENT ranks it is always the lower-rank end that goes into the separator.  The numeric phase relies
-    // on that: a factor belongs to the rank of its higher pose and adds to the diagonal block of the lower one, which therefore has to
-    // be an interface separator (summed over the ranks).  Rank cuts satisfy it by themselves (lower ranks are the lower half).
-    // b: when given, receives the upper half without its separator nodes.
-    // (sd: the scratch marks of the split -- C.side, or C.side2 for the second candidate, which is evaluated on another thread)
-    auto boundary = [&](const std::vector<int>& nd, size_t h, std::vector<int>* a, std::vector<int>* s, std::vector<int>* b = nullptr, char* sd = nullptr) {
-        if (!sd) sd = C.side;
-        for (size_t i = 0; i < nd.size(); ++i) sd[nd[i]] = i < h ? 1 : 2;
-        size_t cnt = 0;
-        for (size_t i = 0; i < h; ++i) {
-            const int v = nd[i];
-            bool cut = false;
-            for (int q = C.adj_ptr[v]; q < C.adj_ptr[v + 1]; ++q) {
-                const int u = C.adj_idx[q];
-                if (sd[u] != 2 && sd[u] != 4) continue;
-                if (multi && C.part[u] < C.part[v]) { if (sd[u] == 2) { sd[u] = 4; ++cnt; } }      // the upper-half end has the lower rank
-                else cut = true;
-            }
-            if (cut) { ++cnt; if (s) s->push_back(v); } else if (a) a->push_back(v);
-        }
-        if (s || b) for (size_t i = h; i < nd.size(); ++i) { const int u = nd[i]; if (sd[u] == 4) { if (s) s->push_back(u); } else if (b) b->push_back(u); }
-        return cnt;
-    };
-    // candidates: the rank cut (lower ranks first) while the set spans several ranks; the median cut along the longer extent, and --
-    // for sets of at least both_axes nodes -- along the other axis too.  A survey is a long strip of parallel legs: the cut across the
-    // longer extent is not the cheaper one once a piece holds few legs (a cut between legs costs the loop closures of two legs, a cut
-    // across them one pose per leg), and rank cuts are cuts between legs.  The smallest separator wins; ties go to the rank cut, then
-    // to the longer extent.  (With geo_first off a multi-rank set always takes its rank cut: every rank's interior is then ONE range
-    // of the order, the layout of rounds 1-2.)
+    // candidates: the rank cut (lower ranks first) while the set spans several ranks, then nd_geo_cut's
     size_t half = 0, best = (size_t)-1;
-    std::vector<int> cand;
     if (multi) {
         const int pmid = (pmin + pmax + 1) / 2;
         half = std::stable_partition(nodes.begin(), nodes.end(), [&](int v) { return C.part[v] < pmid; }) - nodes.begin();
-        best = boundary(nodes, half, nullptr, nullptr);
+        best = nd_boundary(C, multi, C.side, nodes, half);
     }
-    const bool geo = !multi || (C.geo_first && total > C.leaf);
-    if (geo) {
-        nd_timer tm(C.tns, 1);
-        double x0 = 1e300, x1 = -1e300, y0 = 1e300, y1 = -1e300; int i0 = 1 << 30, i1 = -1;
-        for (int v : nodes) { x0 = std::min(x0, C.cx[v]); x1 = std::max(x1, C.cx[v]); y0 = std::min(y0, C.cy[v]); y1 = std::max(y1, C.cy[v]); i0 = std::min(i0, v); i1 = std::max(i1, v); }
-        const bool byx = (x1 - x0) >= (y1 - y0);
-        const size_t h2 = nodes.size() / 2;
-        // split at the median of the (coordinate, index) total order; only the two halves matter, not their inner order
-        // (round 4: the selection runs on a contiguous array of (coordinate, index) pairs -- through the index array every comparison was two
-        // dependent loads into the coordinate table, and the top of the recursion, where one or two threads hold most of the nodes, is the
-        // serial part of the ordering.  The two halves are determined by the total order alone: same sets, same elimination order.)
-        auto split = [&](std::vector<int>& nd, bool bx) {
-            const double* key = bx ? C.cx : C.cy;
-            if (nd.size() < 96) {
-                std::nth_element(nd.begin(), nd.begin() + h2, nd.end(), [&](int a, int b) {
-                    const double ka = key[a], kb = key[b];
-                    return ka != kb ? ka < kb : a < b; });
-                return;
-            }
-            std::vector<std::pair<double, int>> kv(nd.size());
-            for (size_t i = 0; i < nd.size(); ++i) kv[i] = { key[nd[i]], nd[i] };
-            std::nth_element(kv.begin(), kv.begin() + h2, kv.end());       // pair order = (coordinate, index): the comparator above
-            for (size_t i = 0; i < nd.size(); ++i) nd[i] = kv[i].second;
-        };
-        // A CANDIDATE is only counted, not carried out: the element of rank h2 of the (coordinate, index) order is found through a
-        // histogram of the coordinates (one pass over a contiguous copy of the keys, then a selection inside ONE bucket), the halves are
-        // marked by comparing with it, and the separator is counted from the marks -- three light passes instead of a selection that moves
-        // 16-byte pairs about.  Only the winner is partitioned.  Same halves (they are determined by the total order), same counts.
-        // axis 0 = y, 1 = x: median cuts of the dead-reckoned coordinates.  2 = a cut of the CHAIN ORDER (round 5, chain_cut below): a
-        // survey is a lawn-mower chain, consecutive separators lie on one leg, so a cut of the chain order runs BETWEEN two legs (or through
-        // one leg at ONE chain edge) and costs the loop closures that cross it.  The median of y does the same only on paper -- the median
-        // node sits in the middle of some leg whose dead-reckoned y wanders by centimetres, and the cut zig-zags through that leg's chain
-        // edges -- and, worse, it is taken wherever the median happens to fall.
-        struct cut_cand { int bx; double pk; int pi; size_t cnt; size_t half; };
-        std::vector<double> keys;                                          // (one candidate at a time per call; the second one of a large set brings its own)
-        auto less_than = [](double k, int v, double pk, int pi) { return k != pk ? k < pk : v < pi; };
-        auto count_cut = [&](const std::vector<int>& nd, int bx, double lo, double hi, std::vector<double>& kx, char* sd) {
-            const double* key = bx == 1 ? C.cx : C.cy;
-            const size_t m = nd.size();
-            kx.resize(m);
-            // (sets of 64 k nodes and more -- the top of the recursion at C5's 635 k separators, where one or two threads hold everything --
-            // run their passes over ranges of the set; same marks, same counts)
-            const int TP = (m >= 65536 && !multi) ? std::max(1, C.threads) : 1;
-            par_ranges((int)m, TP, [&](int, int a0, int a1) { for (int i = a0; i < a1; ++i) kx[i] = key[nd[i]]; });
-            cut_cand cc{ bx, 0.0, 0, 0, h2 };
-            constexpr int NB = 1024;
-            if (hi > lo && std::isfinite(hi - lo)) {
-                const double scale = NB / (hi - lo);
-                auto bucket = [&](double k) { const int b = (int)((k - lo) * scale); return b < 0 ? 0 : (b >= NB ? NB - 1 : b); };      // monotone in k
-                unsigned hist[NB] = { 0 };
-                if (TP > 1) {
-                    std::vector<unsigned> ph((size_t)TP * NB, 0u);
-                    par_ranges((int)m, TP, [&](int t, int a0, int a1) { unsigned* h = ph.data() + (size_t)t * NB; for (int i = a0; i < a1; ++i) h[bucket(kx[i])]++; });
-                    for (int t = 0; t < TP; ++t) for (int q = 0; q < NB; ++q) hist[q] += ph[(size_t)t * NB + q];
-                } else for (size_t i = 0; i < m; ++i) hist[bucket(kx[i])]++;
-                size_t below = 0; int b = 0;
-                while (below + hist[b] <= h2) below += hist[b++];              // the bucket that holds rank h2 (h2 < m)
-                std::vector<std::pair<double, int>> in;
-                in.reserve(hist[b]);
-                for (size_t i = 0; i < m; ++i) if (bucket(kx[i]) == b) in.push_back({ kx[i], nd[i] });
-                std::nth_element(in.begin(), in.begin() + (h2 - below), in.end());
-                cc.pk = in[h2 - below].first; cc.pi = in[h2 - below].second;
-            } else {                                                          // all coordinates equal (or not finite): the order is the index order
-                std::vector<std::pair<double, int>> in(m);
-                for (size_t i = 0; i < m; ++i) in[i] = { kx[i], nd[i] };
-                std::nth_element(in.begin(), in.begin() + h2, in.end());
-                cc.pk = in[h2].first; cc.pi = in[h2].second;
-            }
-            par_ranges((int)m, TP, [&](int, int a0, int a1) { for (int i = a0; i < a1; ++i) sd[nd[i]] = less_than(kx[i], nd[i], cc.pk, cc.pi) ? 1 : 2; });
-            size_t cnt = 0;
-            if (TP > 1) {                                                     // (one partition: the marks are only read here)
-                std::vector<size_t> pc(TP, 0);
-                par_ranges((int)m, TP, [&](int t, int a0, int a1) {
-                    size_t c2 = 0;
-                    for (int i = a0; i < a1; ++i) {
-                        const int v = nd[i];
-                        if (sd[v] != 1) continue;
-                        for (int q = C.adj_ptr[v]; q < C.adj_ptr[v + 1]; ++q) if (sd[C.adj_idx[q]] == 2) { ++c2; break; }
-                    }
-                    pc[t] = c2;
-                });
-                for (size_t c2 : pc) cnt += c2;
-            } else
-            for (size_t i = 0; i < m; ++i) {
-                const int v = nd[i];
-                if (sd[v] != 1) continue;
-                bool cut = false;
-                for (int q = C.adj_ptr[v]; q < C.adj_ptr[v + 1]; ++q) {
-                    const int u = C.adj_idx[q];
-                    if (sd[u] != 2 && sd[u] != 4) continue;
-                    if (multi && C.part[u] < C.part[v]) { if (sd[u] == 2) { sd[u] = 4; ++cnt; } }
-                    else cut = true;
-                }
-                if (cut) ++cnt;
-            }
-            par_ranges((int)m, TP, [&](int, int a0, int a1) { for (int i = a0; i < a1; ++i) sd[nd[i]] = 0; });
-            cc.cnt = cnt;
-            return cc;
-        };
-        // The chain-order candidate.  Node sets are kept in ascending index order (every split is a stable partition), so a cut of the
-        // chain order is a position p of the list: nodes [0, p) below, [p, m) above.  A node of rank r whose highest neighbour inside the
-        // set has rank R > r is a separator node of every cut r < p <= R: one difference array prices ALL positions in one pass over the
-        // edges, and the cheapest position of the balance window [m / 3, 2 m / 3] is the candidate (the one nearest the middle among equals).
-        // On the C5 graph the cost of a cut between two legs varies from 23 to 740 separator nodes with the pair of legs it runs between
-        // (few loop closures where two legs barely overlap); the median position is rarely a cheap one.  With this candidate the C3 graph
-        // factorises in 12 panel levels instead of 29 (0.6 instead of 2.1 GFLOP, largest front 49 instead of 140 block rows), the C5 graph
-        // in 37 instead of 169 (30 instead of 457 GFLOP, 172 instead of 1 184 block rows).
-        auto chain_cut = [&](const std::vector<int>& nd) {
-            const size_t m = nd.size();
-            cut_cand cc{ 2, 0.0, 0, (size_t)-1, h2 };
-            const int TP = m >= 65536 ? std::max(1, C.threads) : 1;
-            par_ranges((int)m, TP, [&](int, int a0, int a1) { for (int r = a0; r < a1; ++r) C.pos[nd[r]] = r; });
-            std::vector<int> diff(m + 2, 0);
-            par_ranges((int)m, TP, [&](int, int a0, int a1) {
-                for (int r = a0; r < a1; ++r) {
-                    const int v = nd[r];
-                    int R = -1;
-                    for (int q = C.adj_ptr[v]; q < C.adj_ptr[v + 1]; ++q) { const int pu = C.pos[C.adj_idx[q]]; if (pu > R) R = pu; }      // (neighbours outside the set sit in separators: -1)
-                    if (R > r) {
-                        if (TP > 1) { __atomic_fetch_add(&diff[(size_t)r + 1], 1, __ATOMIC_RELAXED); __atomic_fetch_sub(&diff[(size_t)R + 1], 1, __ATOMIC_RELAXED); }
-                        else { diff[(size_t)r + 1]++; diff[(size_t)R + 1]--; }
-                    }
-                }
-            });
-            const size_t lo = std::max<size_t>(1, m / 3), hi = std::min(m - 1, m - m / 3);      // (windows of +-2 / 5 / 10 / 17 / 25 % of the set: C3 17 / 14 / 12 / 12 / 13 panel levels, C5 59 / 41 / 47 / 37 / 35)
-            long long run = 0;
-            for (size_t p2 = 1; p2 <= hi; ++p2) {
-                run += diff[p2];
-                if (p2 < lo) continue;
-                const size_t c = (size_t)run, dist = p2 > h2 ? p2 - h2 : h2 - p2, bdist = cc.half > h2 ? cc.half - h2 : h2 - cc.half;
-                if (c < cc.cnt || (c == cc.cnt && dist < bdist)) { cc.cnt = c; cc.half = p2; }
-            }
-            cc.pi = nd[cc.half];
-            return cc;
-        };
-        auto carry_out = [&](std::vector<int>& nd, const cut_cand& cc) {      // lower half first, both halves in ascending index order
-            if (cc.bx == 2) return;                                           // (a position of the sorted list: nothing moves)
-            const double* key = cc.bx == 1 ? C.cx : C.cy;
-            std::stable_partition(nd.begin(), nd.end(), [&](int v) { return less_than(key[v], v, cc.pk, cc.pi); });
-        };
-        const double lo_of[3] = { y0, x0, (double)i0 }, hi_of[3] = { y1, x1, (double)i1 };           // [bx]
-        const bool idx_cand = C.index_cuts && total >= C.both_axes && total >= 96;      // (only from 512 / 2 048 / 4 096 / 16 384 nodes on: C3 13 / 13 / 14 / 35 panel levels instead of 12, C5 35 / 36 / 37 / 44 instead of 35 -- the big sets matter most, the small ones still count)
-        // The chain-order candidate goes first, and a very cheap one (at most 1/1024 of the set) ends the search: at the top of the recursion --
-        // the serial part of the ordering -- it costs one pass over the set's edges and wins anyway (C3: 1 to 7 separator nodes where the
-        // coordinate medians cost 26 to 207), the coordinate candidates are a histogram selection and a counting pass each.
-        cut_cand c3{}; bool chain_done = false;
-        if (idx_cand) {
-            c3 = chain_cut(nodes);
-            if (c3.cnt < best && c3.cnt * 1024 <= (size_t)total) { best = c3.cnt; half = c3.half; chain_done = true; }      // (1/64 took cuts of 700 nodes where the cut across 79 k nodes of C5 costs 140: twice the flops)
-        }
-        if (chain_done) {}
-        else if (!multi && total < C.both_axes) { split(nodes, byx); half = h2; }       // the only candidate: nothing to compare
-        else if (nodes.size() < 96) {
-            for (int pass = 0; pass < (total >= C.both_axes ? 2 : 1); ++pass) {
-                cand = nodes;
-                split(cand, pass == 0 ? byx : !byx);
-                const size_t c = boundary(cand, h2, nullptr, nullptr);
-                if (c < best) { best = c; nodes.swap(cand); half = h2; }
-            }
-        }
-        else if (total >= C.both_axes && total >= 4096 && depth <= PG_ND_PAR) {
-            // both axes, large set: the two candidates are counted at the same time (the top of the recursion is the serial part of the
-            // ordering); the marks of a node set are private to the call that holds it, the second candidate marks in side2
-            cut_cand c2{};
-            std::vector<double> keys2;
-            pg_pool::task tk; tk.fn = [&] { c2 = count_cut(nodes, (int)!byx, lo_of[!byx], hi_of[!byx], keys2, C.side2); };
-            pg_pool::get().fork(&tk);
-            const cut_cand c1 = count_cut(nodes, (int)byx, lo_of[byx], hi_of[byx], keys, C.side);
-            pg_pool::get().join(&tk);
-            const cut_cand* win = nullptr;
-            if (c1.cnt < best) { best = c1.cnt; win = &c1; }
-            if (c2.cnt < best) { best = c2.cnt; win = &c2; }
-            if (idx_cand && c3.cnt < best) { best = c3.cnt; win = &c3; }
-            if (win) { carry_out(nodes, *win); half = win->half; }
-        }
-        else {
-            cut_cand wc{}; bool have = false;
-            for (int pass = 0; pass < (total >= C.both_axes ? 2 : 1); ++pass) {
-                const int bx = pass == 0 ? (int)byx : (int)!byx;
-                const cut_cand c = count_cut(nodes, bx, lo_of[bx], hi_of[bx], keys, C.side);
-                if (c.cnt < best) { best = c.cnt; wc = c; have = true; }
-            }
-            if (idx_cand && c3.cnt < best) { best = c3.cnt; wc = c3; have = true; }
-            if (have) { carry_out(nodes, wc); half = wc.half; }
-        }
-    }
+    if (!multi || (C.geo_first && total > C.leaf)) nd_geo_cut(C, multi, nodes, depth, best, half);
     { nd_timer tm(C.tns, 2);
-    boundary(nodes, half, &A, &S, &B);
+    nd_boundary(C, multi, C.side, nodes, half, &A, &S, &B);
     for (int v : nodes) C.side[v] = 0; }
     if (multi) {
         // A factor belongs to the rank of its higher pose and adds to the diagonal block of the lower one too, so a node with a
@@ -405,7 +402,6 @@ int nd_order(std::vector<int>& nodes, const nd_ctx& C, std::vector<int>& order, 
     for (int v : S) order.push_back(v);
     return depth <= PG_ND_PAR ? new_node(na, nb, total) : -1;
 }
-
 // column structures of the range [lo, lo + size) of the elimination order described by tree node `t`, children merged
 // into parents (elimination tree built on the fly).  A column whose parent lies outside the range hands the
 // (parent, column) pair up to its caller.  No per-column allocations: the row lists of one call go into that call's pool
@@ -453,11 +449,6 @@ void col_structs(const cs_ctx& C, int t, int lo, int size, std::vector<std::pair
         }
     }
 }
-
-} // namespace
-
-
-namespace {
 // panel levels of the fronts (children have smaller indices than their parents)
 void sym_levels(pg_sym& S)
 {
@@ -476,64 +467,91 @@ void sym_levels(pg_sym& S)
     for (int f = 0; f < nf; ++f) { S.asm_ptr[S.f_level0[f] + 1]++; for (int k = 0; k < S.f_npan[f]; ++k) S.lv_ptr[S.f_level0[f] + k + 1]++; }
     for (int l = 0; l < S.nlev; ++l) { S.lv_ptr[l + 1] += S.lv_ptr[l]; S.asm_ptr[l + 1] += S.asm_ptr[l]; }
     S.lv_front.resize(np); S.lv_step.resize(np); S.asm_front.resize(nf);
-    {
-        std::vector<int> fp(S.lv_ptr.begin(), S.lv_ptr.end() - 1), fq(S.asm_ptr.begin(), S.asm_ptr.end() - 1);
-        for (int f = 0; f < nf; ++f) {
-            S.asm_front[fq[S.f_level0[f]]++] = f;
-            for (int k = 0; k < S.f_npan[f]; ++k) { const int at = fp[S.f_level0[f] + k]++; S.lv_front[at] = f; S.lv_step[at] = k; }
-        }
+    std::vector<int> fp(S.lv_ptr.begin(), S.lv_ptr.end() - 1), fq(S.asm_ptr.begin(), S.asm_ptr.end() - 1);
+    for (int f = 0; f < nf; ++f) {
+        S.asm_front[fq[S.f_level0[f]]++] = f;
+        for (int k = 0; k < S.f_npan[f]; ++k) { const int at = fp[S.f_level0[f] + k]++; S.lv_front[at] = f; S.lv_step[at] = k; }
     }
 }
-
-// per-row views of the fronts for the assembly kernel
+// per-row views of the fronts for the assembly kernel: work items of the assembly and of the trailing update
 void sym_row_views(pg_sym& S, int T)
 {
     const int nf = (int)S.f_c0.size();
-    // ---- per-row views for the assembly, work items of the assembly and of the trailing update
-    {
-        const int nrows_all = S.f_rowptr[nf];
-        S.fa_rowptr.assign(nrows_all + 1, 0);
-        S.xr_ptr.assign(nrows_all + 1, 0);
-        // (a front's block rows are its own range of both views: counts and fills run by ranges of fronts, the two prefix sums between them
-        // are one pass each)
-        par_ranges(nf, T, [&](int, int lo, int hi) {
-            for (int f = lo; f < hi; ++f) {
-                for (int e = S.fa_ptr[f]; e < S.fa_ptr[f + 1]; ++e) S.fa_rowptr[S.f_rowptr[f] + S.fa_row[e] + 1]++;
-                for (int c = S.ch_ptr[f]; c < S.ch_ptr[f + 1]; ++c) { const long long r0 = S.ch_relptr[c], r1 = S.ch_relptr[c + 1]; for (long long q = r0; q < r1; ++q) S.xr_ptr[S.f_rowptr[f] + S.rel[q] + 1]++; }
+    const int nrows_all = S.f_rowptr[nf];
+    S.fa_rowptr.assign(nrows_all + 1, 0);
+    S.xr_ptr.assign(nrows_all + 1, 0);
+    // (a front's block rows are its own range of both views: counts and fills run by ranges of fronts, the two prefix sums between them
+    // are one pass each)
+    par_ranges(nf, T, [&](int, int lo, int hi) {
+        for (int f = lo; f < hi; ++f) {
+            for (int e = S.fa_ptr[f]; e < S.fa_ptr[f + 1]; ++e) S.fa_rowptr[S.f_rowptr[f] + S.fa_row[e] + 1]++;
+            for (int c = S.ch_ptr[f]; c < S.ch_ptr[f + 1]; ++c) { const long long r0 = S.ch_relptr[c], r1 = S.ch_relptr[c + 1]; for (long long q = r0; q < r1; ++q) S.xr_ptr[S.f_rowptr[f] + S.rel[q] + 1]++; }
+        }
+    });
+    // entries are sorted by (front, row): the CSR offsets are global positions in fa_*
+    for (int i = 0; i < nrows_all; ++i) { S.fa_rowptr[i + 1] += S.fa_rowptr[i]; S.xr_ptr[i + 1] += S.xr_ptr[i]; }
+    S.xr_child.resize(S.xr_ptr[nrows_all]); S.xr_row.resize(S.xr_ptr[nrows_all]);
+    par_ranges(nf, T, [&](int, int lo, int hi) {
+        std::vector<int> fp;
+        for (int f = lo; f < hi; ++f) {
+            const int r0f = S.f_rowptr[f], nr = S.f_n[f];
+            fp.assign(S.xr_ptr.begin() + r0f, S.xr_ptr.begin() + r0f + nr);
+            for (int c = S.ch_ptr[f]; c < S.ch_ptr[f + 1]; ++c) {                                   // children in their fixed order
+                const long long r0 = S.ch_relptr[c], r1 = S.ch_relptr[c + 1];
+                for (long long q = r0; q < r1; ++q) { const int at = fp[S.rel[q]]++; S.xr_child[at] = c; S.xr_row[at] = (int)(q - r0); }
             }
-        });
-        // entries are sorted by (front, row): the CSR offsets are global positions in fa_*
-        for (int i = 0; i < nrows_all; ++i) { S.fa_rowptr[i + 1] += S.fa_rowptr[i]; S.xr_ptr[i + 1] += S.xr_ptr[i]; }
-        S.xr_child.resize(S.xr_ptr[nrows_all]); S.xr_row.resize(S.xr_ptr[nrows_all]);
-        par_ranges(nf, T, [&](int, int lo, int hi) {
-            std::vector<int> fp;
-            for (int f = lo; f < hi; ++f) {
-                const int r0f = S.f_rowptr[f], nr = S.f_n[f];
-                fp.assign(S.xr_ptr.begin() + r0f, S.xr_ptr.begin() + r0f + nr);
-                for (int c = S.ch_ptr[f]; c < S.ch_ptr[f + 1]; ++c) {                                   // children in their fixed order
-                    const long long r0 = S.ch_relptr[c], r1 = S.ch_relptr[c + 1];
-                    for (long long q = r0; q < r1; ++q) { const int at = fp[S.rel[q]]++; S.xr_child[at] = c; S.xr_row[at] = (int)(q - r0); }
-                }
-            }
-        });
-    }
+        }
+    });
 }
-} // namespace
-
-void pg_symbolic(int ns, const std::vector<std::pair<int, int>>& edges, int nchain, const double* cx, const double* cy,
-                 const int* part, int nparts, const pg_sym_opts& opt, pg_sym& S)
+// the nodes with a neighbour in a higher part (every edge between two parts has its lower end here): per node 1 or 0
+std::vector<char> upper_neighbour_nodes(int ns, const std::vector<std::pair<int, int>>& edges, const int* part)
 {
-    S = pg_sym();
-    S.ns = ns; S.nparts = std::max(1, nparts);
-    const bool tv = opt.verbose && !opt.to_be_joined;      // (the parts of pg_symbolic_parts report together)
-    auto tnow = [] { return std::chrono::steady_clock::now(); };
-    auto tms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-    const auto q0 = tnow();
-    const int T = std::max(1, opt.threads);
-    // adjacency in CSR form, rows sorted and deduplicated
-    std::vector<int> adj_ptr(ns + 1, 0), adj_idx;
+    std::vector<char> up(ns, 0);
+    for (const auto& e : edges) { const int pa = part[e.first], pb = part[e.second]; if (pa < pb) up[e.first] = 1; else if (pb < pa) up[e.second] = 1; }
+    return up;
+}
+// sum over the s columns of a front of n block rows of 216 (m^2 + 3 m) + 72, m = n - 1 - j: in closed form and in integers (the
+// column-by-column sum is a sum of integers below 2^53, i.e. exact: the same double, so the same merge decisions; as a loop it made
+// every merge test of a growing front linear in its width -- 0.3 of the 0.5 ms of this phase, which the GPU waits for)
+double front_flops(double s_, double n_)
+{
+    const long long s = (long long)s_, n = (long long)n_, hi = n - 1, lo = n - s - 1;         // m runs over lo + 1 .. hi
+    auto Q = [](long long k) { return k <= 0 ? 0LL : k * (k + 1) * (2 * k + 1) / 6; };
+    auto T1 = [](long long k) { return k <= 0 ? 0LL : k * (k + 1) / 2; };
+    return s <= 0 ? 0.0 : (double)(216 * ((Q(hi) - Q(lo)) + 3 * (T1(hi) - T1(lo))) + 72 * s);
+}
+// pg_symbolic stage by stage; the members are grouped by the stage that fills them
+struct sym_run {
+    using clock = std::chrono::steady_clock;
+    const int ns; const std::vector<std::pair<int, int>>& edges; const double* cx; const double* cy; const pg_sym_opts& opt; pg_sym& S;
+    const int* part;                                       // rank of every separator, null with one partition
+    const bool one;                                        // one partition: the hooks run, the bottom tables may run beside the fronts
+    const int T, nlast, nval;
+    const bool tv;                                         // phase times to stderr (the parts of pg_symbolic_parts report together)
+    enum { t_start, t_adj, t_order, t_cols, t_rowidx, t_flags, t_fork, t_super, t_children, t_entries, t_levels, t_views, t_count };
+    clock::time_point tp[t_count];
+    std::vector<int> adj_ptr, adj_idx;                     // adjacency: CSR, rows sorted and deduplicated
+    std::vector<nd_tree> tree; int root = -1;              // order: the tree of ranges of the nested dissection and its root,
+    std::vector<char> iface;                               //   the interface separators (rank-level separators, the prescribed interface)
+    std::vector<int> kid_head, kid_next;                   // columns: children of every column in the elimination tree (linked lists)
+    std::vector<double> sub_cost;                          // bins: work of the subtree below every column;
+    std::vector<char> sub_ok;                              //   the binned columns;
+    std::vector<int> root_of, roots, idx_of_root, bin_of_root;   // subtree root of every binned column, the roots in bin order, their index into S.broot and their bin;
+    std::vector<int> v_row, v_col, v_tr;                   //   block H(row, col) every value lands in, and whether transposed
+    std::vector<int> f_last; int nf = 0;                   // fronts: first column of the last supernode merged into every front
+    // the bottom tables as a task of the pool beside the fronts; declared last, so joined before any member it reads goes away
+    struct joiner { pg_pool::task t; bool on = false; ~joiner() { if (on) pg_pool::get().join(&t); } } bottom;
+    sym_run(int ns_, const std::vector<std::pair<int, int>>& edges_, const double* cx_, const double* cy_, const int* part_, int nparts, const pg_sym_opts& opt_, pg_sym& S_)
+        : ns(ns_), edges(edges_), cx(cx_), cy(cy_), opt(opt_), S(S_), part(nparts > 1 ? part_ : nullptr), one(nparts <= 1),
+          T(std::max(1, opt_.threads)), nlast((int)opt_.iface_last.size()), nval(ns_ + (int)edges_.size()), tv(opt_.verbose && !opt_.to_be_joined)
+    { S = pg_sym(); S.ns = ns; S.nparts = std::max(1, nparts); tp[t_start] = clock::now(); }
+    double ms(int a, int b) const { return std::chrono::duration<double, std::milli>(tp[b] - tp[a]).count(); }
+    double ms_since(int a) const { return std::chrono::duration<double, std::milli>(clock::now() - tp[a]).count(); }
+    int csz(int j) const { return S.colptr[j + 1] - S.colptr[j]; }
+    void adjacency()
     {   // rows are tiny (two chain neighbours + the loop closures of the pose): insertion sort and duplicate removal in place, rows
         // compacted behind each other (std::sort + std::unique + a vector insert per row cost a millisecond at 23 k rows)
+        adj_ptr.assign(ns + 1, 0);
         for (auto& e : edges) if (e.first != e.second) { adj_ptr[e.first + 1]++; adj_ptr[e.second + 1]++; }
         for (int i = 0; i < ns; ++i) adj_ptr[i + 1] += adj_ptr[i];
         adj_idx.resize(adj_ptr[ns]);
@@ -554,9 +572,7 @@ void pg_symbolic(int ns, const std::vector<std::pair<int, int>>& edges, int ncha
         }
         adj_ptr[ns] = w;
         adj_idx.resize(w);
-    }
-    const int nlast = (int)opt.iface_last.size();
-    if (nlast > 0) {
+        if (nlast == 0) return;
         // the prescribed interface is a clique: every interface row gets all the other interface nodes (merged into its sorted row)
         std::vector<int> ap(ns + 1, 0), ai;
         std::vector<char> is_last(ns, 0);
@@ -575,113 +591,115 @@ void pg_symbolic(int ns, const std::vector<std::pair<int, int>>& edges, int ncha
         ap[ns] = (int)ai.size();
         adj_ptr.swap(ap); adj_idx.swap(ai);
     }
-    if (opt.before_order) opt.before_order();
-    const auto q0a = tnow();
-    std::vector<nd_tree> pool; std::mutex mu;
-    std::vector<char> iface(ns, 0);
-    int root = -1;
+    // the elimination order (nested dissection; the prescribed interface last), the ranks of the columns
+    void order()
     {
+        std::mutex mu;
+        iface.assign(ns, 0);
         std::vector<int> nodes; nodes.reserve(ns);
         for (int v : opt.iface_last) iface[v] = 1;
         for (int v = 0; v < ns; ++v) if (!iface[v]) nodes.push_back(v);
         std::vector<char> side(ns, 0), side2(ns, 0);
         S.order.reserve(ns);
-        std::vector<char> forced(ns, 0);
+        const std::vector<char> upper = part ? upper_neighbour_nodes(ns, edges, part) : std::vector<char>();
         std::vector<int> pos_scratch(ns, -1);
-        if (S.nparts > 1 && part) for (int v = 0; v < ns; ++v) for (int q = adj_ptr[v]; q < adj_ptr[v + 1]; ++q) if (part[adj_idx[q]] > part[v]) { forced[v] = 1; break; }
-        std::atomic<long long> nd_ns[8];
-        for (auto& a : nd_ns) a = 0;
-        nd_ctx C{ adj_ptr.data(), adj_idx.data(), cx, cy, side.data(), side2.data(), opt.leaf, opt.nd_both_axes, opt.nd_geo_first, S.nparts > 1 ? part : nullptr, iface.data(), forced.data(), &pool, &mu, tv ? nd_ns : nullptr, opt.nd_index_cuts != 0, pos_scratch.data(), T };
+        std::atomic<long long> nd_ns[8] = {};
+        nd_ctx C{ adj_ptr.data(), adj_idx.data(), cx, cy, side.data(), side2.data(), opt.leaf, opt.nd_both_axes, opt.nd_geo_first, part, iface.data(), upper.data(), &tree, &mu, tv ? nd_ns : nullptr, opt.nd_index_cuts != 0, pos_scratch.data(), T };
         root = nd_order(nodes, C, S.order, 0);
         if (nlast > 0) {        // the prescribed interface behind everything else; in the tree of ranges: a root whose second half is empty
             for (int v : opt.iface_last) S.order.push_back(v);
-            pool.push_back({ -1, -1, 0 });
-            pool.push_back({ root, (int)pool.size() - 1, ns });
-            root = (int)pool.size() - 1;
+            tree.push_back({ -1, -1, 0 });
+            tree.push_back({ root, (int)tree.size() - 1, ns });
+            root = (int)tree.size() - 1;
         }
         if (tv) fprintf(stderr, "[dsss pg symbolic] nd_order thread-time: candidates %.2f ms, final boundary %.2f ms, leaves %.2f ms\n", nd_ns[1] / 1e6, nd_ns[2] / 1e6, nd_ns[4] / 1e6);
+        tp[t_order] = clock::now();
+        S.perm.assign(ns, 0);
+        for (int i = 0; i < ns; ++i) S.perm[S.order[i]] = i;
+        S.col_part.assign(ns, 0);
+        for (int j = 0; j < ns; ++j) { const int v = S.order[j]; S.col_part[j] = iface[v] ? -1 : (part ? part[v] : 0); }
+        if (part) for (int v = 0; v < ns; ++v) S.ownership_violations += upper[v] && !iface[v];
     }
-    const auto q1 = tnow();
-    S.perm.assign(ns, 0);
-    for (int i = 0; i < ns; ++i) S.perm[S.order[i]] = i;
-    S.col_part.assign(ns, 0);
-    for (int j = 0; j < ns; ++j) { const int v = S.order[j]; S.col_part[j] = iface[v] ? -1 : (part && S.nparts > 1 ? part[v] : 0); }
-    if (part && S.nparts > 1)
-        for (int v = 0; v < ns; ++v) if (!iface[v]) for (int q = adj_ptr[v]; q < adj_ptr[v + 1]; ++q) if (part[adj_idx[q]] > part[v]) { S.ownership_violations++; break; }
-    std::vector<cref> cols(ns);
-    S.parent.assign(ns, -1);
-    std::vector<int> kid_head(ns, -1), kid_next(ns, -1);
-    std::vector<std::vector<int>> pools(pool.size() + 1);
+    // column structures of L and the elimination tree
+    void columns()
     {
-        cs_ctx C{ adj_ptr.data(), adj_idx.data(), S.order.data(), S.perm.data(), &pool, &pools, cols.data(), kid_head.data(), kid_next.data(), S.parent.data() };
+        std::vector<cref> cols(ns);
+        S.parent.assign(ns, -1);
+        kid_head.assign(ns, -1); kid_next.assign(ns, -1);
+        std::vector<std::vector<int>> pools(tree.size() + 1);
+        const cs_ctx C{ adj_ptr.data(), adj_idx.data(), S.order.data(), S.perm.data(), &tree, &pools, cols.data(), kid_head.data(), kid_next.data(), S.parent.data() };
         std::vector<std::pair<int, int>> up;
         col_structs(C, root, 0, ns, up, 0);
-    }
-    const auto q2 = tnow();
-    S.colptr.assign(ns + 1, 0);
-    for (int j = 0; j < ns; ++j) S.colptr[j + 1] = S.colptr[j] + cols[j].n;
-    auto csz = [&](int j) { return S.colptr[j + 1] - S.colptr[j]; };
-    S.rowidx.resize(S.colptr[ns]);
-    S.nnzL = S.colptr[ns];
-    par_ranges(ns, T, [&](int, int lo, int hi) {
-        for (int k = lo; k < hi; ++k) { const int* d = pools[cols[k].pool].data() + cols[k].off; std::copy(d, d + cols[k].n, S.rowidx.begin() + S.colptr[k]); }
-    });
-    const auto f0 = tnow();
-    const std::vector<int>& parent = S.parent;
-    // ---- bottom subtrees -> bins (one workgroup each); only interior columns of one rank, at most 42 blocks per column
-    std::vector<double> sub_cost(ns, 0);
-    std::vector<char> sub_ok(ns, 0);
-    std::vector<int> nsrc(ns, 0);                          // number of source columns of every column = its count of off-diagonal blocks in row j
-    {   // a histogram per range of source columns, then summed (788 k scattered increments at C3: a third of this phase when serial)
-        std::vector<std::vector<int>> part_h(T > 1 ? T - 1 : 0);
-        par_ranges(ns, T, [&](int t, int lo, int hi) {
-            int* h = nsrc.data();
-            if (t > 0) { part_h[t - 1].assign(ns, 0); h = part_h[t - 1].data(); }
-            for (int k = lo; k < hi; ++k) for (int q = S.colptr[k] + 1; q < S.colptr[k + 1]; ++q) h[S.rowidx[q]]++;
+        tp[t_cols] = clock::now();
+        S.colptr.assign(ns + 1, 0);
+        for (int j = 0; j < ns; ++j) S.colptr[j + 1] = S.colptr[j] + cols[j].n;
+        S.rowidx.resize(S.colptr[ns]);
+        S.nnzL = S.colptr[ns];
+        par_ranges(ns, T, [&](int, int lo, int hi) {
+            for (int k = lo; k < hi; ++k) { const int* d = pools[cols[k].pool].data() + cols[k].off; std::copy(d, d + cols[k].n, S.rowidx.begin() + S.colptr[k]); }
         });
-        par_ranges(ns, T, [&](int, int lo, int hi) { for (auto& h : part_h) if (!h.empty()) for (int j = lo; j < hi; ++j) nsrc[j] += h[j]; });
+        tp[t_rowidx] = clock::now();
     }
-    for (int j = 0; j < ns; ++j) {
-        const int mj = csz(j);
-        double cst = nsrc[j] + 20.0; bool ok = mj <= 42 && S.col_part[j] >= 0;
-        for (int k = kid_head[j]; k >= 0; k = kid_next[k]) { cst += sub_cost[k]; ok = ok && sub_ok[k]; }
-        sub_cost[j] = cst; sub_ok[j] = ok && cst <= opt.bin_cost;
-    }
-    S.binned.assign(sub_ok.begin(), sub_ok.end());
-    std::vector<int> root_of(ns, -1);                       // subtree root of every binned column
-    for (int j = ns - 1; j >= 0; --j) {
-        if (!sub_ok[j]) continue;
-        const int par = parent[j];
-        root_of[j] = (par >= 0 && sub_ok[par]) ? root_of[par] : j;
-    }
-    S.root_of = root_of;
-    if (opt.on_lists_ready && nparts <= 1) opt.on_lists_ready();       // colptr, rowidx, binned, root_of: final
-    // subtree roots in bin order, and the roots that hand an update matrix up (the fronts of the top need these; the packing itself not)
-    std::vector<int> roots;
-    for (int j = 0; j < ns; ++j) if (sub_ok[j] && root_of[j] == j) roots.push_back(j);
-    // (a rank's interior may be several ranges of the order when geometric cuts come before rank cuts: its bins stay one range)
-    std::stable_sort(roots.begin(), roots.end(), [&](int a, int b) { return S.col_part[a] < S.col_part[b]; });
-    std::vector<int> idx_of_root(ns, -1);
-    for (int r : roots) if (csz(r) > 1) { idx_of_root[r] = (int)S.broot.size(); S.broot.push_back(r); S.broot_b.push_back(csz(r) - 1); }
-    // where the assembled blocks go: value index k < ns diagonal of separator k, then the chain couplings, then the LC edges
-    const int ne = (int)edges.size() - nchain, nval = ns + nchain + ne;
-    S.dest_bin.assign(nval, -1);
-    std::vector<int> v_row(nval), v_col(nval), v_tr(nval);
-    par_ranges(nval, T, [&](int, int lo, int hi) {
-        for (int v = lo; v < hi; ++v) {
-            int pa, pb;                                   // block H(a, b): rows of a, columns of b
-            if (v < ns) { pa = pb = S.perm[v]; }
-            else { const auto& e = edges[v - ns]; pa = S.perm[e.first]; pb = S.perm[e.second]; }
-            v_row[v] = std::max(pa, pb); v_col[v] = std::min(pa, pb); v_tr[v] = (pa >= pb) ? 0 : 1;
+    // ---- bottom subtrees -> bins (one workgroup each); only interior columns of one rank, at most 42 blocks per column
+    void bins()
+    {
+        sub_cost.assign(ns, 0); sub_ok.assign(ns, 0);
+        std::vector<int> nsrc(ns, 0);                          // number of source columns of every column = its count of off-diagonal blocks in row j
+        {   // a histogram per range of source columns, then summed (788 k scattered increments at C3: a third of this phase when serial)
+            std::vector<std::vector<int>> part_h(T > 1 ? T - 1 : 0);
+            par_ranges(ns, T, [&](int t, int lo, int hi) {
+                int* h = nsrc.data();
+                if (t > 0) { part_h[t - 1].assign(ns, 0); h = part_h[t - 1].data(); }
+                for (int k = lo; k < hi; ++k) for (int q = S.colptr[k] + 1; q < S.colptr[k + 1]; ++q) h[S.rowidx[q]]++;
+            });
+            par_ranges(ns, T, [&](int, int lo, int hi) { for (auto& h : part_h) if (!h.empty()) for (int j = lo; j < hi; ++j) nsrc[j] += h[j]; });
         }
-    });
-    S.nval = nval;
-    const auto f1 = tnow();
-    // ---- THE BOTTOM TABLES (bin packing, the bins' index lists unless the caller builds them, the destinations of the values that go
-    // into binned columns) and THE TOP (fronts and schedule, below) do not depend on each other: with one partition the bottom runs as a
-    // task of the pool beside the top, and hands itself over (on_bottom_ready) as soon as it is complete
-    std::vector<int> bin_of_root(ns, -1);
-    auto bottom_tables = [&] {
+        for (int j = 0; j < ns; ++j) {
+            const int mj = csz(j);
+            double cst = nsrc[j] + 20.0; bool ok = mj <= 42 && S.col_part[j] >= 0;
+            for (int k = kid_head[j]; k >= 0; k = kid_next[k]) { cst += sub_cost[k]; ok = ok && sub_ok[k]; }
+            sub_cost[j] = cst; sub_ok[j] = ok && cst <= opt.bin_cost;
+        }
+        S.binned.assign(sub_ok.begin(), sub_ok.end());
+        root_of.assign(ns, -1);
+        for (int j = ns - 1; j >= 0; --j) {
+            if (!sub_ok[j]) continue;
+            const int par = S.parent[j];
+            root_of[j] = (par >= 0 && sub_ok[par]) ? root_of[par] : j;
+        }
+        S.root_of = root_of;
+        if (opt.on_lists_ready && one) opt.on_lists_ready();       // colptr, rowidx, binned, root_of: final
+        // subtree roots in bin order, and the roots that hand an update matrix up (the fronts of the top need these; the packing itself not)
+        for (int j = 0; j < ns; ++j) if (sub_ok[j] && root_of[j] == j) roots.push_back(j);
+        // (a rank's interior may be several ranges of the order when geometric cuts come before rank cuts: its bins stay one range)
+        std::stable_sort(roots.begin(), roots.end(), [&](int a, int b) { return S.col_part[a] < S.col_part[b]; });
+        idx_of_root.assign(ns, -1);
+        for (int r : roots) if (csz(r) > 1) { idx_of_root[r] = (int)S.broot.size(); S.broot.push_back(r); S.broot_b.push_back(csz(r) - 1); }
+        // where the assembled blocks go: value index k < ns diagonal of separator k, then the edges (chain couplings first, if any)
+        S.dest_bin.assign(nval, -1);
+        v_row.resize(nval); v_col.resize(nval); v_tr.resize(nval);
+        par_ranges(nval, T, [&](int, int lo, int hi) {
+            for (int v = lo; v < hi; ++v) {
+                int pa, pb;                                   // block H(a, b): rows of a, columns of b
+                if (v < ns) { pa = pb = S.perm[v]; }
+                else { const auto& e = edges[v - ns]; pa = S.perm[e.first]; pb = S.perm[e.second]; }
+                v_row[v] = std::max(pa, pb); v_col[v] = std::min(pa, pb); v_tr[v] = (pa >= pb) ? 0 : 1;
+            }
+        });
+        S.nval = nval;
+        tp[t_flags] = clock::now();
+        // ---- THE BOTTOM TABLES (bin packing, the bins' index lists unless the caller builds them, the destinations of the values that go
+        // into binned columns) and THE TOP (fronts and schedule, below) do not depend on each other: with one partition the bottom runs as
+        // a task of the pool beside the top, and hands itself over (on_bottom_ready) as soon as it is complete
+        bin_of_root.assign(ns, -1);
+        if (one && T > 1) { bottom.t.fn = [this] { bottom_tables(); }; pg_pool::get().fork(&bottom.t); bottom.on = true; }
+        else bottom_tables();
+        tp[t_fork] = clock::now();
+        if (tv) fprintf(stderr, "[dsss pg symbolic] bins: flags + roots + value coordinates %.2f ms; bottom tables %s%s\n", ms(t_rowidx, t_flags), bottom.on ? "as a task beside the fronts" : "in line",
+                        opt.lists_on_device ? " (lists and root indices: on the device)" : "");
+    }
+    void bottom_tables()
+    {
         {   // greedy packing of whole subtrees into bins, subtrees taken in ascending root order, never across ranks
             const double pack = opt.pack_cost > 0 ? opt.pack_cost : opt.bin_cost;
             int nbins = 0; double fill = pack + 1; int cur_part = -2;
@@ -763,45 +781,27 @@ void pg_symbolic(int ns, const std::vector<std::pair<int, int>>& edges, int ncha
                                                 return (int)(std::lower_bound(b, e, row) - S.rowidx.begin()); };
             par_ranges(nval, T, [&](int, int lo, int hi) { for (int v = lo; v < hi; ++v) if (sub_ok[v_col[v]]) S.dest_bin[v] = (find(v_row[v], v_col[v]) << 1) | v_tr[v]; });
         }
-        if (opt.on_bottom_ready && nparts <= 1) opt.on_bottom_ready();
-    };
-    pg_pool::task bottom_task; bool bottom_forked = false;
-    if (nparts <= 1 && T > 1) { bottom_task.fn = bottom_tables; pg_pool::get().fork(&bottom_task); bottom_forked = true; }
-    else bottom_tables();
-    struct bottom_joiner { pg_pool::task* t; bool on; ~bottom_joiner() { if (on) pg_pool::get().join(t); } } bottom_join{ &bottom_task, bottom_forked };      // (before anything of this function goes away)
-    const auto q3 = tnow();
-    if (tv) fprintf(stderr, "[dsss pg symbolic] bins: flags + roots + value coordinates %.2f ms; bottom tables %s%s\n", tms(f0, f1), bottom_forked ? "as a task beside the fronts" : "in line",
-                    opt.lists_on_device ? " (lists and root indices: on the device)" : "");
+        if (opt.on_bottom_ready && one) opt.on_bottom_ready();
+    }
     // ---- top: supernodes of the remaining columns become fronts.  Fundamental supernodes (consecutive columns with nested
     // structure) first; then RELAXED amalgamation along the column order: a front whose columns end where its parent's begin is
     // merged into the parent when that adds few explicit zero blocks -- every merge removes a level of the schedule, and the
     // levels (one dependent launch sequence each) are what the factorisation time is made of.
-    S.front_of_col.assign(ns, -1);
+    void supernodes()
     {
+        S.front_of_col.assign(ns, -1);
         struct fnd { int c0, s, n; };                       // fundamental supernodes, ascending
         std::vector<fnd> fund;
         for (int j = 0; j < ns; ++j) {
             if (sub_ok[j]) continue;
-            const bool chain = !fund.empty() && fund.back().c0 + fund.back().s == j && parent[j - 1] == j && csz(j) + 1 == csz(j - 1) && S.col_part[j] == S.col_part[j - 1];
+            const bool chain = !fund.empty() && fund.back().c0 + fund.back().s == j && S.parent[j - 1] == j && csz(j) + 1 == csz(j - 1) && S.col_part[j] == S.col_part[j - 1];
             if (chain) fund.back().s++;
             else fund.push_back({ j, 1, csz(j) });
         }
-        // sum over the s columns of a front of n block rows of 216 (m^2 + 3 m) + 72, m = n - 1 - j: in closed form and in integers (the
-        // column-by-column sum is a sum of integers below 2^53, i.e. exact: the same double, so the same merge decisions; as a loop it made
-        // every merge test of a growing front linear in its width -- 0.3 of the 0.5 ms of this phase, which the GPU waits for)
-        auto flops_of = [](double s_, double n_) {
-            const long long s = (long long)s_, n = (long long)n_;
-            auto Q = [](long long k) { return k <= 0 ? 0LL : k * (k + 1) * (2 * k + 1) / 6; };
-            auto T1 = [](long long k) { return k <= 0 ? 0LL : k * (k + 1) / 2; };
-            if (s <= 0) return 0.0;
-            const long long hi = n - 1, lo = n - s - 1;         // m runs over lo + 1 .. hi
-            return (double)(216 * ((Q(hi) - Q(lo)) + 3 * (T1(hi) - T1(lo))) + 72 * s);
-        };
         // The merge decisions need sizes and ONE row of a front -- its first boundary row -- and the rows of a front are its own columns
         // (consecutive) followed by the boundary of the LAST supernode merged into it: decided here in one cheap pass (f_last = that
         // supernode's first column), the row lists are then written by all threads (at C5 they are 13 M entries: 8 ms when one thread
         // copied them while it decided).
-        std::vector<int> f_last;
         for (const fnd& g : fund) {
             bool merged = false;
             if (!S.f_c0.empty()) {
@@ -811,7 +811,7 @@ void pg_symbolic(int ns, const std::vector<std::pair<int, int>>& edges, int ncha
                 const int bfirst = bc > 0 ? S.rowidx[S.colptr[lastc] + (csz(lastc) - bc)] : -1;
                 if (S.f_c0[c] + sc == g.c0 && bc > 0 && bfirst >= g.c0 && bfirst < g.c0 + g.s && S.f_part[c] == S.col_part[g.c0]) {
                     const double zeros = (double)(g.n - bc) * sc;                     // explicit zero blocks the merge puts into L
-                    const double f_sep = flops_of(sc, nc) + flops_of(g.s, g.n), f_mrg = flops_of(sc + g.s, sc + g.n);
+                    const double f_sep = front_flops(sc, nc) + front_flops(g.s, g.n), f_mrg = front_flops(sc + g.s, sc + g.n);
                     const bool one_panel = sc + g.s <= PG_PW;
                     // a merge that removes a panel step (the two column counts round up to fewer panels together) is worth a bounded
                     // amount of extra arithmetic whatever the ratio: a level costs about 100 us of dependent launches, i.e. more than
@@ -826,25 +826,21 @@ void pg_symbolic(int ns, const std::vector<std::pair<int, int>>& edges, int ncha
             }
             if (!merged) { S.f_c0.push_back(g.c0); S.f_s.push_back(g.s); S.f_n.push_back(g.n); S.f_part.push_back(S.col_part[g.c0]); f_last.push_back(g.c0); }
         }
-        {
-            const int nfr = (int)S.f_c0.size();
-            S.f_rowptr.assign(nfr + 1, 0);
-            for (int f = 0; f < nfr; ++f) S.f_rowptr[f + 1] = S.f_rowptr[f] + S.f_n[f];
-            S.f_rows.resize(S.f_rowptr[nfr]);
-            par_ranges(nfr, T, [&](int, int lo, int hi) {
-                for (int f = lo; f < hi; ++f) {
-                    int* out = S.f_rows.data() + S.f_rowptr[f];
-                    const int sc = S.f_s[f], bc = S.f_n[f] - sc, lastc = f_last[f];
-                    for (int q = 0; q < sc; ++q) out[q] = S.f_c0[f] + q;
-                    std::copy(S.rowidx.begin() + S.colptr[lastc] + (csz(lastc) - bc), S.rowidx.begin() + S.colptr[lastc + 1], out + sc);
-                }
-            });
-        }
-        for (size_t f = 0; f < S.f_c0.size(); ++f) for (int c = 0; c < S.f_s[f]; ++c) S.front_of_col[S.f_c0[f] + c] = (int)f;
-    }
-    const int nf = (int)S.f_c0.size();
-    S.f_ld.resize(nf); S.f_off.resize(nf); S.f_roff.resize(nf); S.f_parent.assign(nf, -1);
-    {
+        nf = (int)S.f_c0.size();
+        S.f_rowptr.assign(nf + 1, 0);
+        for (int f = 0; f < nf; ++f) S.f_rowptr[f + 1] = S.f_rowptr[f] + S.f_n[f];
+        S.f_rows.resize(S.f_rowptr[nf]);
+        par_ranges(nf, T, [&](int, int lo, int hi) {
+            for (int f = lo; f < hi; ++f) {
+                int* out = S.f_rows.data() + S.f_rowptr[f];
+                const int sc = S.f_s[f], bc = S.f_n[f] - sc, lastc = f_last[f];
+                for (int q = 0; q < sc; ++q) out[q] = S.f_c0[f] + q;
+                std::copy(S.rowidx.begin() + S.colptr[lastc] + (csz(lastc) - bc), S.rowidx.begin() + S.colptr[lastc + 1], out + sc);
+            }
+        });
+        for (int f = 0; f < nf; ++f) for (int c = 0; c < S.f_s[f]; ++c) S.front_of_col[S.f_c0[f] + c] = f;
+        // the front arena and the parents
+        S.f_ld.resize(nf); S.f_off.resize(nf); S.f_roff.resize(nf); S.f_parent.assign(nf, -1);
         long long o = 0, ro = 0;
         for (int f = 0; f < nf; ++f) {
             const int ld = (6 * S.f_n[f] + 15) & ~15;
@@ -852,16 +848,16 @@ void pg_symbolic(int ns, const std::vector<std::pair<int, int>>& edges, int ncha
             S.f_roff[f] = ro; ro += ld;
             S.max_front_n = std::max(S.max_front_n, S.f_n[f]);
             if (S.f_n[f] > S.f_s[f]) S.f_parent[f] = S.front_of_col[S.f_rows[S.f_rowptr[f] + S.f_s[f]]];
-            S.flops_fronts += [&] { double fl = 0; for (int j = 0; j < S.f_s[f]; ++j) { const double m = S.f_n[f] - j - 1; fl += 216.0 * (m * m + 3 * m) + 72.0; } return fl; }();      // (once per front: linear in total)
+            S.flops_fronts += front_flops(S.f_s[f], S.f_n[f]);
         }
         S.front_doubles = o; S.frhs_doubles = ro;
+        tp[t_super] = clock::now();
     }
-    const auto fA = tnow();
     // children (bin roots first, then fronts, both ascending) and their boundary -> parent row maps
+    void children()
     {
-        std::vector<int> cnt(nf + 1, 0);
-        std::vector<int> broot_front(S.broot.size());
-        for (size_t i = 0; i < S.broot.size(); ++i) { const int p = parent[S.broot[i]]; broot_front[i] = S.front_of_col[p]; cnt[broot_front[i] + 1]++; }
+        std::vector<int> cnt(nf + 1, 0), broot_front(S.broot.size());
+        for (size_t i = 0; i < S.broot.size(); ++i) { const int p = S.parent[S.broot[i]]; broot_front[i] = S.front_of_col[p]; cnt[broot_front[i] + 1]++; }
         for (int f = 0; f < nf; ++f) if (S.f_parent[f] >= 0) cnt[S.f_parent[f] + 1]++;
         S.ch_ptr.assign(nf + 1, 0);
         for (int f = 0; f < nf; ++f) S.ch_ptr[f + 1] = S.ch_ptr[f] + cnt[f + 1];
@@ -886,9 +882,10 @@ void pg_symbolic(int ns, const std::vector<std::pair<int, int>>& edges, int ncha
                 }
             }
         });
+        tp[t_children] = clock::now();
     }
-    const auto fB = tnow();
     // ---- where the assembled blocks go, second half: the original entries of every front
+    void entries()
     {
         std::vector<int> cnt(nf + 1, 0);
         for (int v = 0; v < nval; ++v) if (!sub_ok[v_col[v]]) cnt[S.front_of_col[v_col[v]] + 1]++;
@@ -910,7 +907,7 @@ void pg_symbolic(int ns, const std::vector<std::pair<int, int>>& edges, int ncha
             });
         }
         par_ranges(nf, T, [&](int, int lo, int hi) {
-            std::vector<int> idx, a, b, c2, d;
+            std::vector<int> idx, tmp;
             for (int f = lo; f < hi; ++f) {
                 const int b0 = S.fa_ptr[f], n = S.fa_ptr[f + 1] - b0;
                 idx.resize(n); std::iota(idx.begin(), idx.end(), 0);
@@ -918,28 +915,31 @@ void pg_symbolic(int ns, const std::vector<std::pair<int, int>>& edges, int ncha
                     if (S.fa_row[b0 + x] != S.fa_row[b0 + y]) return S.fa_row[b0 + x] < S.fa_row[b0 + y];
                     if (S.fa_col[b0 + x] != S.fa_col[b0 + y]) return S.fa_col[b0 + x] < S.fa_col[b0 + y];
                     return S.fa_src[b0 + x] < S.fa_src[b0 + y]; });
-                a.resize(n); b.resize(n); c2.resize(n); d.resize(n);
-                for (int i = 0; i < n; ++i) { a[i] = S.fa_src[b0 + idx[i]]; b[i] = S.fa_row[b0 + idx[i]]; c2[i] = S.fa_col[b0 + idx[i]]; d[i] = S.fa_tr[b0 + idx[i]]; }
-                for (int i = 0; i < n; ++i) { S.fa_src[b0 + i] = a[i]; S.fa_row[b0 + i] = b[i]; S.fa_col[b0 + i] = c2[i]; S.fa_tr[b0 + i] = d[i]; }
+                for (std::vector<int>* v : { &S.fa_src, &S.fa_row, &S.fa_col, &S.fa_tr }) { tmp.resize(n); for (int i = 0; i < n; ++i) tmp[i] = (*v)[b0 + idx[i]]; std::copy(tmp.begin(), tmp.end(), v->begin() + b0); }
             }
         });
+        tp[t_entries] = clock::now();
     }
-    const auto fC = tnow();
-    if (!opt.to_be_joined) sym_levels(S);
-    if (tv && opt.verbose >= 2) {      // critical path of the schedule, root first
-        int f = -1;
-        for (int g = 0; g < nf; ++g) if (S.f_level0[g] + S.f_npan[g] == S.nlev) f = g;
-        while (f >= 0) {
-            fprintf(stderr, "[dsss pg path] front %d: cols %d rows %d panels %d levels %d..%d part %d children %d\n", f, S.f_s[f], S.f_n[f], S.f_npan[f], S.f_level0[f], S.f_level0[f] + S.f_npan[f] - 1, S.f_part[f], S.ch_ptr[f + 1] - S.ch_ptr[f]);
-            int nxt = -1;
-            for (int c = S.ch_ptr[f]; c < S.ch_ptr[f + 1]; ++c) if (!S.ch_kind[c]) { const int g = S.ch_id[c]; if (S.f_level0[g] + S.f_npan[g] == S.f_level0[f]) nxt = g; }
-            f = nxt;
+    // panel levels and per-row views (once, on the joined tables, for the parts of pg_symbolic_parts)
+    void schedule()
+    {
+        if (!opt.to_be_joined) sym_levels(S);
+        if (tv && opt.verbose >= 2) {      // critical path of the schedule, root first
+            int f = -1;
+            for (int g = 0; g < nf; ++g) if (S.f_level0[g] + S.f_npan[g] == S.nlev) f = g;
+            while (f >= 0) {
+                fprintf(stderr, "[dsss pg path] front %d: cols %d rows %d panels %d levels %d..%d part %d children %d\n", f, S.f_s[f], S.f_n[f], S.f_npan[f], S.f_level0[f], S.f_level0[f] + S.f_npan[f] - 1, S.f_part[f], S.ch_ptr[f + 1] - S.ch_ptr[f]);
+                int nxt = -1;
+                for (int c = S.ch_ptr[f]; c < S.ch_ptr[f + 1]; ++c) if (!S.ch_kind[c]) { const int g = S.ch_id[c]; if (S.f_level0[g] + S.f_npan[g] == S.f_level0[f]) nxt = g; }
+                f = nxt;
+            }
         }
+        tp[t_levels] = clock::now();
+        if (!opt.to_be_joined) sym_row_views(S, T);
+        tp[t_views] = clock::now();
     }
-    const auto fD = tnow();
-    if (!opt.to_be_joined) sym_row_views(S, T);
-    const auto fE = tnow();
-    // ---- children that cross from a rank's interior into the interface
+    // ---- children that cross from a rank's interior into the interface, the values of interface fronts, the interface separators
+    void interface()
     {
         long long o = 0;
         for (int f = 0; f < nf; ++f) {
@@ -954,11 +954,9 @@ void pg_symbolic(int ns, const std::vector<std::pair<int, int>>& edges, int ncha
             }
         }
         S.comm_doubles = o;
-        // original values of interface fronts and the interface separators
-        S.nval = nval;
         if (S.nparts > 1 || nlast > 0) {
             std::vector<int> slot_of(nval, -1);
-            for (int f = 0; f < nf && !opt.iface_plain; ++f) {
+            for (int f = 0; f < nf && !opt.to_be_joined; ++f) {
                 if (S.f_part[f] >= 0) continue;
                 for (int e = S.fa_ptr[f]; e < S.fa_ptr[f + 1]; ++e) {
                     const int v = S.fa_src[e];
@@ -969,20 +967,33 @@ void pg_symbolic(int ns, const std::vector<std::pair<int, int>>& edges, int ncha
             for (int k = 0; k < ns; ++k) if (S.col_part[S.perm[k]] < 0) S.iface_seps.push_back(k);
         }
     }
-    if (bottom_join.on) { pg_pool::get().join(&bottom_task); bottom_join.on = false; }      // the bottom tables are complete from here on
-    // statistics
-    for (int j = 0; j < ns; ++j) { const double m = csz(j) - 1; S.flops_factor += 36.0 * 6.0 * (m * m + 3 * m) + 72.0; }
-    if (tv) fprintf(stderr, "[dsss pg symbolic] fronts+schedule: supernodes %.2f, children+rel %.2f, destinations+entries %.2f, schedule %.2f, row views %.2f, rest %.2f ms\n", tms(q3, fA), tms(fA, fB), tms(fB, fC), tms(fC, fD), tms(fD, fE), tms(fE, tnow()));
-    if (tv) {
-        long long zeros = 0;
+    void finish()
+    {
+        if (bottom.on) { pg_pool::get().join(&bottom.t); bottom.on = false; }      // the bottom tables are complete from here on
+        for (int j = 0; j < ns; ++j) { const double m = csz(j) - 1; S.flops_factor += 36.0 * 6.0 * (m * m + 3 * m) + 72.0; }
+        if (!tv) return;
+        fprintf(stderr, "[dsss pg symbolic] fronts+schedule: supernodes %.2f, children+rel %.2f, destinations+entries %.2f, schedule %.2f, row views %.2f, rest %.2f ms\n", ms(t_fork, t_super), ms(t_super, t_children), ms(t_children, t_entries), ms(t_entries, t_levels), ms(t_levels, t_views), ms_since(t_views));
         int big = 0;
-        for (int f = 0; f < nf; ++f) { if (S.f_n[f] > 100) ++big; zeros += 0; }
+        for (int f = 0; f < nf; ++f) if (S.f_n[f] > 100) ++big;
         fprintf(stderr, "[dsss pg symbolic] adjacency %.2f + ND %.2f ms, column structures %.1f ms, bins+lists %.1f ms, fronts+schedule %.1f ms | ns %d nnzL %lld bins %d (%zu cols, %zu roots, U %.1f MB) fronts %d (>100 rows: %d, max %d) panels %d levels %d front arena %.1f MB comm %.1f MB front GFLOP %.1f (column count %.1f)\n",
-                tms(q0, q0a), tms(q0a, q1), tms(q1, q2), tms(q2, q3), tms(q3, tnow()), ns, S.nnzL, (int)S.binptr.size() - 1, S.bincols.size(), S.broot.size(), S.ubin_doubles * 8e-6,
+                ms(t_start, t_adj), ms(t_adj, t_order), ms(t_order, t_cols), ms(t_cols, t_fork), ms_since(t_fork), ns, S.nnzL, (int)S.binptr.size() - 1, S.bincols.size(), S.broot.size(), S.ubin_doubles * 8e-6,
                 nf, big, S.max_front_n, S.npanels, S.nlev, S.front_doubles * 8e-6, S.comm_doubles * 8e-6, S.flops_fronts * 1e-9, S.flops_factor * 1e-9);
     }
+};
+// The analysis of one graph: ordering, column structures, bins, fronts and schedule.  edges: pairs of separator indices (a value index
+// each, behind the ns diagonal blocks); with a rank partition the ns - 1 chain couplings (k, k + 1) come first, then the LC edges.
+// part[k] (may be null): rank that owns separator k, non-decreasing in k.  cx, cy: DR positions of the separators.
+void pg_symbolic(int ns, const std::vector<std::pair<int, int>>& edges, const double* cx, const double* cy, const int* part, int nparts,
+                 const pg_sym_opts& opt, pg_sym& S)
+{
+    sym_run R(ns, edges, cx, cy, part, nparts, opt, S);
+    R.adjacency();
+    if (opt.before_order) opt.before_order();
+    R.tp[sym_run::t_adj] = sym_run::clock::now();
+    R.order(); R.columns(); R.bins();
+    R.supernodes(); R.children(); R.entries(); R.schedule(); R.interface(); R.finish();
 }
-
+// the launch lists of the fronts whose part lies in [part_lo, part_hi) (dsss_pg_sym.h: pg_sched); (-1, 0) selects the interface fronts
 void pg_build_schedule(const pg_sym& S, int part_lo, int part_hi, pg_sched& out)
 {
     out = pg_sched();
@@ -1021,34 +1032,7 @@ void pg_build_schedule(const pg_sym& S, int part_lo, int part_hi, pg_sched& out)
     }
 }
 
-pg_switches pg_switches_read()
-{
-    pg_switches sw;
-    if (const char* v = getenv("DSSS_PG_BIN_COST")) sw.bin_cost = sw.opt.bin_cost = atof(v);
-    if (const char* v = getenv("DSSS_PG_LEAF")) sw.opt.leaf = atoi(v);
-    if (const char* v = getenv("DSSS_PG_ND_BOTH")) sw.opt.nd_both_axes = atoi(v);
-    if (const char* v = getenv("DSSS_PG_ND_INDEX")) sw.opt.nd_index_cuts = atoi(v);
-    if (const char* v = getenv("DSSS_PG_PARTS_ANALYSIS")) sw.parts = atoi(v);
-    if (const char* v = getenv("DSSS_SYM_THREADS")) sw.threads = atoi(v);
-    if (const char* v = getenv("DSSS_PG_LOCAL")) sw.local = atoi(v) != 0;
-    if (const char* v = getenv("DSSS_PG_VERBOSE")) sw.opt.verbose = std::max(1, atoi(v));
-    return sw;
-}
-
-int pg_cheapest_gap(const int* pos, const std::vector<int>& cross, int target, int width, int after, int* cost)
-{
-    const int m = (int)cross.size() - 1, lo = std::max(target - width, after + 1);
-    auto start = [&](int i) { return pos ? pos[i - 1] + 1 : i; };
-    int best = -1; long long bdist = 0;
-    for (int i = std::max(1, pos ? (int)(std::lower_bound(pos, pos + m, lo - 1) - pos) + 1 : lo); i < m && start(i) <= target + width; ++i) {
-        const long long d = std::llabs((long long)start(i) - target);
-        if (best < 0 || cross[i] < *cost || (cross[i] == *cost && d < bdist)) { *cost = cross[i]; bdist = d; best = start(i); }
-    }
-    return best;
-}
-
 // ------------------------------------------------------------------ host twin of the numeric phase (CPU tests only)
-namespace {
 int h_chol(double* A, int n, int ld)          // in-place lower Cholesky of the leading n x n block
 {
     for (int j = 0; j < n; ++j) {
@@ -1060,11 +1044,11 @@ int h_chol(double* A, int n, int ld)          // in-place lower Cholesky of the 
     }
     return 0;
 }
-} // namespace
-
-int pg_host_solve(const pg_sym& S, int ne, const std::vector<std::pair<int, int>>& edges, const double* aval, const double* rhs, double* xout)
+// Host twin of the numeric phase, used by the CPU test-suite only (the product path is dsss_pg.hip): factorises the matrix
+// given by `aval` (36 doubles per value index, see dest_bin) and solves for `rhs` (6 per separator, chain order).  Returns 0
+// or -1 when a pivot is not positive.
+int pg_host_solve(const pg_sym& S, const double* aval, const double* rhs, double* xout)
 {
-    (void)edges; (void)ne;
     const int ns = S.ns, nf = (int)S.f_c0.size();
     auto csz = [&](int j) { return S.colptr[j + 1] - S.colptr[j]; };
     std::vector<double> L((size_t)S.nnzL * 36, 0.0), x((size_t)ns * 6, 0.0), F((size_t)S.front_doubles, 0.0), R((size_t)S.frhs_doubles, 0.0), U((size_t)S.ubin_doubles, 0.0);
@@ -1168,127 +1152,118 @@ int pg_host_solve(const pg_sym& S, int ne, const std::vector<std::pair<int, int>
     for (int k = 0; k < ns; ++k) for (int a = 0; a < 6; ++a) xout[(size_t)k * 6 + a] = x[(size_t)S.perm[k] * 6 + a];
     return 0;
 }
-
-// ------------------------------------------------------------------ C ABI of the host twin (CPU test-suite; include/dsss.h)
-#include "../../include/dsss.h"
-// a host twin's statistics (stats8[5]: s5) and its return code from pg_host_solve's
-static int twin_result(const pg_sym& S, int rc, int64_t s5, int64_t* stats8)
-{
-    if (stats8) {
-        stats8[0] = S.nnzL; stats8[1] = (int64_t)S.f_c0.size(); stats8[2] = S.npanels; stats8[3] = S.nlev;
-        stats8[4] = S.front_doubles; stats8[5] = s5; stats8[6] = (int64_t)S.bincols.size(); stats8[7] = S.max_front_n;
-    }
-    return rc == 0 ? DSSS_OK : (rc == -1 ? DSSS_E_NUMERIC : DSSS_E_STATE);
-}
-extern "C" int dsss_host_pg_solve(int ns, const int32_t* edge_a, const int32_t* edge_b, int nedges, const double* cx, const double* cy,
-                                  const int32_t* part, int nparts, const double* aval, const double* rhs, double* x, int64_t* stats8)
-{
-    if (ns < 1 || nedges < ns - 1 || !edge_a || !edge_b || !cx || !cy || (x && (!aval || !rhs))) return DSSS_E_ARG;      // x == NULL: analysis only
-    std::vector<std::pair<int, int>> edges(nedges);
-    for (int e = 0; e < nedges; ++e) {
-        edges[e] = { edge_a[e], edge_b[e] };
-        if (edge_a[e] < 0 || edge_a[e] >= ns || edge_b[e] < 0 || edge_b[e] >= ns) return DSSS_E_ARG;
-        if (e < ns - 1 && (edge_a[e] != e || edge_b[e] != e + 1)) return DSSS_E_ARG;       // the chain couplings come first
-    }
-    pg_sym S;
-    const pg_switches sw = pg_switches_read();
-    pg_sym_opts opt = sw.opt;
-    if (sw.threads) opt.threads = std::max(1, *sw.threads);
-    opt.lists_on_device = x == nullptr;                     // analysis only: as the product runs it (the bins' lists are built on the device there)
-    pg_symbolic(ns, edges, ns - 1, cx, cy, part, nparts, opt, S);
-    if (S.ownership_violations) return DSSS_E_STATE;        // a lower-rank end of a cross-rank factor outside the interface
-    if (!x) {      // (what the product builds next; timed with the analysis by tools/sym_time.py)
-        const auto t0 = std::chrono::steady_clock::now();
-        pg_sched so, si; pg_build_schedule(S, 0, std::max(1, nparts), so); if (nparts > 1) pg_build_schedule(S, -1, 0, si);
-        if (opt.verbose)
-            fprintf(stderr, "[dsss pg symbolic] launch lists %.2f ms (%zu assembly rows, %zu panel steps, %zu tiles)\n",
-                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(),
-                    so.asmrow_front.size() + si.asmrow_front.size(), so.lv_front.size() + si.lv_front.size(), so.tile_item.size() + si.tile_item.size());
-    }
-    const int rc = x ? pg_host_solve(S, nedges - (ns - 1), edges, aval, rhs, x) : 0;
-    return twin_result(S, rc, S.comm_doubles, stats8);
-}
-
-// the same with a PRESCRIBED interface (pg_sym_opts::iface_last): the analysis one rank of several runs on its own separators + the
-// interface nodes.  Any edge list (no chain prefix); iface_last ascending.
-extern "C" int dsss_host_pg_solve_local(int ns, const int32_t* edge_a, const int32_t* edge_b, int nedges, const double* cx, const double* cy,
-                                        const int32_t* iface_last, int nlast, const double* aval, const double* rhs, double* x, int64_t* stats8)
-{
-    if (ns < 1 || nedges < 0 || (nedges > 0 && (!edge_a || !edge_b)) || !cx || !cy || nlast < 0 || nlast > ns || (nlast > 0 && !iface_last) || !x || !aval || !rhs) return DSSS_E_ARG;
-    std::vector<std::pair<int, int>> edges(nedges);
-    for (int e = 0; e < nedges; ++e) {
-        edges[e] = { edge_a[e], edge_b[e] };
-        if (edge_a[e] < 0 || edge_a[e] >= ns || edge_b[e] < 0 || edge_b[e] >= ns || edge_a[e] == edge_b[e]) return DSSS_E_ARG;
-    }
-    pg_sym S; pg_sym_opts opt = pg_switches_read().opt;
-    for (int q = 0; q < nlast; ++q) {
-        if (iface_last[q] < 0 || iface_last[q] >= ns || (q > 0 && iface_last[q] <= iface_last[q - 1])) return DSSS_E_ARG;
-        opt.iface_last.push_back(iface_last[q]);
-    }
-    pg_symbolic(ns, edges, 0, cx, cy, nullptr, 1, opt, S);
-    // the interface is the LAST front, dense over exactly the prescribed nodes
-    if (nlast > 0) {
-        const int nf = (int)S.f_c0.size();
-        if (nf < 1 || S.f_part[nf - 1] != -1 || S.f_s[nf - 1] != nlast || S.f_n[nf - 1] != nlast || S.f_c0[nf - 1] != ns - nlast) return DSSS_E_STATE;
-        for (int f = 0; f + 1 < nf; ++f) if (S.f_part[f] < 0) return DSSS_E_STATE;
-        for (int q = 0; q < nlast; ++q) if (S.order[ns - nlast + q] != iface_last[q] || (int)S.iface_seps.size() != nlast || S.iface_seps[q] != iface_last[q]) return DSSS_E_STATE;
-        if (!S.comm_kind.empty()) return DSSS_E_STATE;
-    }
-    const int rc = pg_host_solve(S, nedges, edges, aval, rhs, x);
-    return twin_result(S, rc, (int64_t)S.comm_vals.size(), stats8);
-}
-
-// ------------------------------------------------------------------ one rank analysed by parts (dsss_pg_sym.h)
-bool pg_symbolic_parts(int ns, const std::vector<std::pair<int, int>>& edges, int nchain, const double* cx, const double* cy,
-                       const int* part, int K, int max_iface, const pg_sym_opts& opt, pg_sym& G)
-{
-    (void)nchain;
-    const bool tv = opt.verbose;
-    const auto q0 = std::chrono::steady_clock::now();
-    auto ms_since = [](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count(); };
-    // the interface: nodes with a neighbour in a higher part (every edge between two parts has its lower end here)
-    std::vector<char> isif(ns, 0);
-    for (const auto& e : edges) { const int pa = part[e.first], pb = part[e.second]; if (pa < pb) isif[e.first] = 1; else if (pb < pa) isif[e.second] = 1; }
-    std::vector<int> I, iidx(ns, -1);
-    for (int k = 0; k < ns; ++k) if (isif[k]) { iidx[k] = (int)I.size(); I.push_back(k); }
-    const int nif = (int)I.size();
-    if (nif > max_iface || K < 2) return false;
-    struct part_t {
-        pg_sym S; std::vector<int> glob_of, ledge_g; std::vector<std::pair<int, int>> ledges; std::vector<double> cx, cy; std::vector<int> loc_of;
-        int nint = 0, nfi = 0;                                     // interior columns, interior fronts
-        long long c0 = 0, nnz0 = 0, f0 = 0, b0 = 0, br0 = 0, ch0 = 0, rel0 = 0, fa0 = 0, fd0 = 0, fr0 = 0, ub0 = 0, bc0 = 0, rl0 = 0, frow0 = 0;
-        long long nnz = 0, nchI = 0, nrelI = 0, nfaI = 0, nrows = 0;   // interior: factor blocks, children, rel entries, original entries, front rows
-    };
-    std::vector<part_t> P(K);
-    std::once_flag coords_once;                                    // (the coordinates may still be on their way: the parts build their graphs first, ONE of them waits, the others behind it)
-    const double t_pre = ms_since(q0);
-    // ---- phase 1: every part on its own
-    dsss_pool_run(K, [&](int p) {
-        part_t& Q = P[p];
-        Q.loc_of.assign(ns, -1);
-        pg_sym_opts o = opt;
-        o.threads = ns >= 131072 ? std::max(1, opt.threads / K) : 1;      // (a part of a C5-size graph is itself large enough for ranges; at C3's size forks cost what they gain)
-        o.before_order = nullptr; o.on_bottom_ready = nullptr; o.on_lists_ready = nullptr; o.iface_plain = true; o.to_be_joined = true; o.iface_last.clear();
+bool iface_front_last(const pg_sym& S, int nif)      // the last front of S is the dense interface front: its last nif columns, part -1
+{ const int nf = (int)S.f_c0.size(); return nf >= 1 && S.f_part[nf - 1] == -1 && S.f_s[nf - 1] == nif && S.f_n[nf - 1] == nif && S.f_c0[nf - 1] == S.ns - nif; }
+// The subgraph induced by one part's separators (owner[k] == me) and the interface (iface[k]), in ascending global order: what a rank of
+// the rank-local analysis and a part of pg_symbolic_parts analyse.  The interface nodes are its prescribed interface (pg_sym_opts::iface_last).
+struct pg_subgraph {
+    int ns_g = 0;                                          // separators of the whole graph
+    std::vector<int> glob_of, ledge_g, iface_last;         // global index of every local separator and of every local edge; the interface (local)
+    std::vector<std::pair<int, int>> ledges;               // the edges between local separators (no self edges), in global order
+    std::vector<double> cx, cy;                            // local coordinates: sized here, filled by copy_coords (they may still be on their way)
+    pg_subgraph() = default;
+    pg_subgraph(int ns, const std::vector<std::pair<int, int>>& edges, const std::vector<char>& iface, const int* owner, int me) : ns_g(ns)
+    {
+        std::vector<int> loc_of(ns, -1);
         for (int k = 0; k < ns; ++k)
-            if (isif[k] || part[k] == p) { Q.loc_of[k] = (int)Q.glob_of.size(); if (isif[k]) o.iface_last.push_back(Q.loc_of[k]); Q.glob_of.push_back(k); }
+            if (iface[k] || owner[k] == me) { loc_of[k] = (int)glob_of.size(); if (iface[k]) iface_last.push_back(loc_of[k]); glob_of.push_back(k); }
         for (size_t g = 0; g < edges.size(); ++g) {
-            const int a = Q.loc_of[edges[g].first], b = Q.loc_of[edges[g].second];
-            if (a >= 0 && b >= 0 && a != b) { Q.ledges.push_back({ a, b }); Q.ledge_g.push_back((int)g); }
+            const int a = loc_of[edges[g].first], b = loc_of[edges[g].second];
+            if (a >= 0 && b >= 0 && a != b) { ledges.push_back({ a, b }); ledge_g.push_back((int)g); }
         }
-        const int nsl = (int)Q.glob_of.size();
-        Q.cx.resize(nsl); Q.cy.resize(nsl);
-        std::call_once(coords_once, [&] { if (opt.before_order) opt.before_order(); });
-        for (int i = 0; i < nsl; ++i) { Q.cx[i] = cx[Q.glob_of[i]]; Q.cy[i] = cy[Q.glob_of[i]]; }
-        pg_symbolic(nsl, Q.ledges, 0, Q.cx.data(), Q.cy.data(), nullptr, 1, o, Q.S);
-        Q.nint = nsl - nif;
-    });
-    const double t_parts = ms_since(q0);
-    // ---- offsets of every index space
+        cx.resize(glob_of.size()); cy.resize(glob_of.size());
+    }
+    int size() const { return (int)glob_of.size(); }
+    void copy_coords(const double* gx, const double* gy) { for (int i = 0; i < size(); ++i) { cx[i] = gx[glob_of[i]]; cy[i] = gy[glob_of[i]]; } }
+    int val_g(int v) const { return v < size() ? glob_of[v] : ns_g + ledge_g[v - size()]; }      // local value index -> global: separators, then edges
+};
+
+// ------------------------------------------------------------------ one rank analysed by parts
+// One part's tables and where its share goes in the joined ones (every index space: the parts' interiors behind each other).
+struct part_t {
+    pg_subgraph g; pg_sym S;
+    int nint = 0, nfi = 0;                                     // interior columns, interior fronts
     long long c0 = 0, nnz0 = 0, f0 = 0, b0 = 0, br0 = 0, ch0 = 0, rel0 = 0, fa0 = 0, fd0 = 0, fr0 = 0, ub0 = 0, bc0 = 0, rl0 = 0, frow0 = 0;
-    for (int p = 0; p < K; ++p) {
-        part_t& Q = P[p]; const pg_sym& S = Q.S;
+    long long nnz = 0, nchI = 0, nrelI = 0, nfaI = 0, nrows = 0;   // interior: factor blocks, children, rel entries, original entries, front rows
+    long long chI0 = 0, relI0 = 0;                             // its children of the interface front and their rel entries: behind the parts before it
+};
+// the joined tables: interface columns from cI on, its front last (nfG - 1) with children, rel and original entries behind the interiors
+struct parts_join { int nif, cI, nfG; bool host_lists; long long ch0, rel0, fa0; };
+// one part writes its share of the joined tables (first: the part that copies the interface front's own values, listed by every part)
+void join_part(const part_t& Q, const parts_join& J, bool first, pg_sym& G)
+{
+    const pg_sym& S = Q.S;
+    const int nint = Q.nint, nfG = J.nfG;
+    auto colmap = [&](int j) { return j < nint ? (int)Q.c0 + j : J.cI + (j - nint); };
+    for (int j = 0; j < nint; ++j) {
+        const int c = (int)Q.c0 + j, v = Q.g.glob_of[S.order[j]];
+        G.order[c] = v; G.perm[v] = c;
+        const int b = S.colptr[j], m = S.colptr[j + 1] - b;
+        G.colptr[c + 1] = m;                                                  // (sizes now, the prefix sum below)
+        int* out = G.rowidx.data() + Q.nnz0 + b;
+        for (int q = 0; q < m; ++q) out[q] = colmap(S.rowidx[b + q]);
+        G.parent[c] = S.parent[j] >= 0 ? colmap(S.parent[j]) : -1;
+        G.binned[c] = S.binned[j];
+        G.root_of[c] = S.root_of[j] >= 0 ? (int)Q.c0 + S.root_of[j] : -1;
+        G.broot_of_col[c] = S.broot_of_col.empty() || S.broot_of_col[j] < 0 ? -1 : (int)Q.br0 + S.broot_of_col[j];
+        G.front_of_col[c] = S.front_of_col[j] < 0 ? -1 : (S.front_of_col[j] >= Q.nfi ? nfG - 1 : (int)Q.f0 + S.front_of_col[j]);
+        if (J.host_lists) {
+            G.rlptr[c + 1] = S.rlptr[j + 1] - S.rlptr[j];
+            for (int t = S.rlptr[j]; t < S.rlptr[j + 1]; ++t) { const long long at = Q.rl0 + t; G.rlcol[at] = (int)Q.c0 + S.rlcol[t]; G.rlpos[at] = (int)(Q.nnz0 + S.rlpos[t]); G.rlrow[at] = (int)Q.c0 + S.rlrow[t]; }
+            G.anc_first[c] = S.anc_first[j];
+            for (int q = 0; q < m; ++q) G.anc_rel[Q.nnz0 + b + q] = S.anc_rel[b + q];
+        }
+    }
+    // bins and their roots
+    const int nb = (int)S.binptr.size() - 1;
+    for (int b = 0; b < nb; ++b) {
+        G.binptr[Q.b0 + b + 1] = S.binptr[b + 1] - S.binptr[b];
+        G.bin_work[Q.b0 + b] = S.bin_work[b];
+        G.binroot_ptr[Q.b0 + b + 1] = S.binroot_ptr[b + 1] - S.binroot_ptr[b];
+    }
+    for (size_t i = 0; i < S.bincols.size(); ++i) G.bincols[Q.bc0 + i] = (int)Q.c0 + S.bincols[i];
+    for (size_t i = 0; i < S.broot.size(); ++i) {
+        G.broot[Q.br0 + i] = (int)Q.c0 + S.broot[i]; G.broot_b[Q.br0 + i] = S.broot_b[i]; G.broot_uoff[Q.br0 + i] = Q.ub0 + S.broot_uoff[i];
+        G.binroot_idx[Q.br0 + i] = (int)Q.br0 + S.binroot_idx[i];
+    }
+    // interior fronts
+    for (int f = 0; f < Q.nfi; ++f) {
+        const int g = (int)Q.f0 + f;
+        G.f_c0[g] = (int)Q.c0 + S.f_c0[f]; G.f_s[g] = S.f_s[f]; G.f_n[g] = S.f_n[f]; G.f_ld[g] = S.f_ld[f];
+        G.f_off[g] = Q.fd0 + S.f_off[f]; G.f_roff[g] = Q.fr0 + S.f_roff[f];
+        G.f_parent[g] = S.f_parent[f] < 0 ? -1 : (S.f_parent[f] >= Q.nfi ? nfG - 1 : (int)Q.f0 + S.f_parent[f]);
+        G.f_rowptr[g + 1] = S.f_n[f];
+        int* out = G.f_rows.data() + Q.frow0 + S.f_rowptr[f];
+        for (int q = 0; q < S.f_n[f]; ++q) out[q] = colmap(S.f_rows[S.f_rowptr[f] + q]);
+        G.ch_ptr[g + 1] = S.ch_ptr[f + 1] - S.ch_ptr[f];
+        G.fa_ptr[g + 1] = S.fa_ptr[f + 1] - S.fa_ptr[f];
+    }
+    auto put_children = [&](int c_lo, int c_hi, long long at, long long rel_at) {
+        for (int c = c_lo; c < c_hi; ++c, ++at) {
+            G.ch_kind[at] = S.ch_kind[c]; G.ch_id[at] = S.ch_kind[c] ? (int)Q.br0 + S.ch_id[c] : (int)Q.f0 + S.ch_id[c];
+            const long long r0 = S.ch_relptr[c], r1 = S.ch_relptr[c + 1];
+            G.ch_relptr[at + 1] = r1 - r0;                                    // (sizes now, the prefix sum below)
+            for (long long q = r0; q < r1; ++q) G.rel[rel_at + (q - r0)] = S.rel[q];
+            rel_at += r1 - r0;
+        }
+    };
+    put_children(0, (int)Q.nchI, Q.ch0, Q.rel0);
+    if (J.nif > 0) put_children(S.ch_ptr[Q.nfi], S.ch_ptr[Q.nfi + 1], J.ch0 + Q.chI0, J.rel0 + Q.relI0);
+    auto put_entries = [&](int e_lo, int e_hi, long long at) {
+        for (int e = e_lo; e < e_hi; ++e, ++at) { G.fa_src[at] = Q.g.val_g(S.fa_src[e]); G.fa_row[at] = S.fa_row[e]; G.fa_col[at] = S.fa_col[e]; G.fa_tr[at] = S.fa_tr[e]; }
+    };
+    put_entries(0, (int)Q.nfaI, Q.fa0);
+    if (J.nif > 0 && first) put_entries(S.fa_ptr[Q.nfi], S.fa_ptr[Q.nfi + 1], J.fa0);      // (the interface's own values: every part lists them all, one copy counts)
+    // destinations of the values whose column is one of this part's interior columns (the interface's own stay -1: front)
+    for (int v = 0; v < (int)S.dest_bin.size(); ++v) if (S.dest_bin[v] >= 0) G.dest_bin[Q.g.val_g(v)] = (int)(((Q.nnz0 + (S.dest_bin[v] >> 1)) << 1) | (S.dest_bin[v] & 1));
+}
+// the offsets of every part's share, then the joined tables sized (nothing written yet but the fills of the assign()s)
+parts_join parts_layout(std::vector<part_t>& P, int ns, int nvalG, int nif, bool host_lists, pg_sym& G)
+{
+    long long c0 = 0, nnz0 = 0, f0 = 0, b0 = 0, br0 = 0, ch0 = 0, rel0 = 0, fa0 = 0, fd0 = 0, fr0 = 0, ub0 = 0, bc0 = 0, rl0 = 0, frow0 = 0, chI = 0, relI = 0;
+    for (part_t& Q : P) {
+        const pg_sym& S = Q.S;
         const int nf = (int)S.f_c0.size();
-        if (nif > 0 && (nf < 1 || S.f_part[nf - 1] != -1 || S.f_s[nf - 1] != nif || S.f_n[nf - 1] != nif || S.f_c0[nf - 1] != Q.nint)) return false;      // (the interface must be the last, dense front of every part)
         Q.nfi = nif > 0 ? nf - 1 : nf;
         Q.nnz = S.colptr[Q.nint];
         Q.nchI = S.ch_ptr[Q.nfi]; Q.nrelI = S.ch_relptr[Q.nchI]; Q.nfaI = S.fa_ptr[Q.nfi]; Q.nrows = S.f_rowptr[Q.nfi];
@@ -1296,22 +1271,16 @@ bool pg_symbolic_parts(int ns, const std::vector<std::pair<int, int>>& edges, in
         c0 += Q.nint; nnz0 += Q.nnz; f0 += Q.nfi; b0 += (long long)S.binptr.size() - 1; br0 += (long long)S.broot.size(); ch0 += Q.nchI; rel0 += Q.nrelI; fa0 += Q.nfaI;
         fd0 += Q.nfi < nf ? S.f_off[Q.nfi] : S.front_doubles; fr0 += Q.nfi < nf ? S.f_roff[Q.nfi] : S.frhs_doubles; ub0 += S.ubin_doubles; bc0 += (long long)S.bincols.size();
         rl0 += S.rlptr.empty() ? 0 : S.rlptr[Q.nint]; frow0 += Q.nrows;
+        // children / rel / original entries of the interface front: the parts' own, behind each other
+        Q.chI0 = chI; Q.relI0 = relI;
+        if (nif > 0) { chI += S.ch_ptr[Q.nfi + 1] - S.ch_ptr[Q.nfi]; relI += S.ch_relptr[S.ch_ptr[Q.nfi + 1]] - S.ch_relptr[S.ch_ptr[Q.nfi]]; }
     }
     const int cI = (int)c0, nfG = (int)f0 + (nif > 0 ? 1 : 0), nbG = (int)b0, nbrG = (int)br0;
-    const long long nnzI = (long long)nif * (nif + 1) / 2, nnzG = nnz0 + nnzI;
-    // children / rel / original entries of the interface front: the parts' own, behind each other
-    long long chI = 0, relI = 0;
-    std::vector<long long> chI0(K, 0), relI0(K, 0);
-    for (int p = 0; p < K; ++p) {
-        const pg_sym& S = P[p].S;
-        chI0[p] = chI; relI0[p] = relI;
-        if (nif > 0) { chI += S.ch_ptr[P[p].nfi + 1] - S.ch_ptr[P[p].nfi]; relI += S.ch_relptr[S.ch_ptr[P[p].nfi + 1]] - S.ch_relptr[S.ch_ptr[P[p].nfi]]; }
-    }
+    const long long nnzG = nnz0 + (long long)nif * (nif + 1) / 2;
     const long long faI = nif > 0 ? P[0].S.fa_ptr[P[0].nfi + 1] - P[0].S.fa_ptr[P[0].nfi] : 0;
-    const bool host_lists = !opt.lists_on_device;
     G = pg_sym();
     G.ns = ns; G.nparts = 1;
-    G.nval = ns + (int)edges.size();
+    G.nval = nvalG;
     G.perm.assign(ns, -1); G.order.assign(ns, -1);
     G.colptr.assign(ns + 1, 0); G.rowidx.resize(nnzG); G.parent.assign(ns, -1); G.col_part.assign(ns, 0);
     G.binned.assign(ns, 0); G.root_of.assign(ns, -1); G.broot_of_col.assign(ns, -1); G.front_of_col.assign(ns, -1);
@@ -1324,87 +1293,8 @@ bool pg_symbolic_parts(int ns, const std::vector<std::pair<int, int>>& edges, in
     G.ch_ptr.assign(nfG + 1, 0); G.ch_kind.resize(ch0 + chI); G.ch_id.resize(ch0 + chI); G.ch_relptr.assign(ch0 + chI + 1, 0); G.rel.resize(rel0 + relI);
     G.fa_ptr.assign(nfG + 1, 0); G.fa_src.resize(fa0 + faI); G.fa_row.resize(fa0 + faI); G.fa_col.resize(fa0 + faI); G.fa_tr.resize(fa0 + faI);
     G.dest_bin.assign(G.nval, -1);
-    // ---- phase 2: every part writes its share of the joined tables
-    dsss_pool_run(K, [&](int p) {
-        const part_t& Q = P[p]; const pg_sym& S = Q.S;
-        const int nint = Q.nint;
-        auto colmap = [&](int j) { return j < nint ? (int)Q.c0 + j : cI + (j - nint); };
-        auto valmap = [&](int v) { const int nsl = (int)Q.glob_of.size(); return v < nsl ? Q.glob_of[v] : ns + Q.ledge_g[v - nsl]; };
-        for (int j = 0; j < nint; ++j) {
-            const int c = (int)Q.c0 + j, v = Q.glob_of[S.order[j]];
-            G.order[c] = v; G.perm[v] = c;
-            const int b = S.colptr[j], m = S.colptr[j + 1] - b;
-            G.colptr[c + 1] = m;                                                  // (sizes now, the prefix sum below)
-            int* out = G.rowidx.data() + Q.nnz0 + b;
-            for (int q = 0; q < m; ++q) out[q] = colmap(S.rowidx[b + q]);
-            G.parent[c] = S.parent[j] >= 0 ? colmap(S.parent[j]) : -1;
-            G.binned[c] = S.binned[j];
-            G.root_of[c] = S.root_of[j] >= 0 ? (int)Q.c0 + S.root_of[j] : -1;
-            G.broot_of_col[c] = S.broot_of_col.empty() || S.broot_of_col[j] < 0 ? -1 : (int)Q.br0 + S.broot_of_col[j];
-            G.front_of_col[c] = S.front_of_col[j] < 0 ? -1 : (S.front_of_col[j] >= Q.nfi ? nfG - 1 : (int)Q.f0 + S.front_of_col[j]);
-            if (host_lists) {
-                G.rlptr[c + 1] = S.rlptr[j + 1] - S.rlptr[j];
-                for (int t = S.rlptr[j]; t < S.rlptr[j + 1]; ++t) { const long long at = Q.rl0 + t; G.rlcol[at] = (int)Q.c0 + S.rlcol[t]; G.rlpos[at] = (int)(Q.nnz0 + S.rlpos[t]); G.rlrow[at] = (int)Q.c0 + S.rlrow[t]; }
-                G.anc_first[c] = S.anc_first[j];
-                for (int q = 0; q < m; ++q) G.anc_rel[Q.nnz0 + b + q] = S.anc_rel[b + q];
-            }
-        }
-        // bins and their roots
-        const int nb = (int)S.binptr.size() - 1;
-        for (int b = 0; b < nb; ++b) {
-            G.binptr[Q.b0 + b + 1] = S.binptr[b + 1] - S.binptr[b];
-            G.bin_work[Q.b0 + b] = S.bin_work[b];
-            G.binroot_ptr[Q.b0 + b + 1] = S.binroot_ptr[b + 1] - S.binroot_ptr[b];
-        }
-        for (size_t i = 0; i < S.bincols.size(); ++i) G.bincols[Q.bc0 + i] = (int)Q.c0 + S.bincols[i];
-        for (size_t i = 0; i < S.broot.size(); ++i) {
-            G.broot[Q.br0 + i] = (int)Q.c0 + S.broot[i]; G.broot_b[Q.br0 + i] = S.broot_b[i]; G.broot_uoff[Q.br0 + i] = Q.ub0 + S.broot_uoff[i];
-            G.binroot_idx[Q.br0 + i] = (int)Q.br0 + S.binroot_idx[i];
-        }
-        // interior fronts
-        for (int f = 0; f < Q.nfi; ++f) {
-            const int g = (int)Q.f0 + f;
-            G.f_c0[g] = (int)Q.c0 + S.f_c0[f]; G.f_s[g] = S.f_s[f]; G.f_n[g] = S.f_n[f]; G.f_ld[g] = S.f_ld[f];
-            G.f_off[g] = Q.fd0 + S.f_off[f]; G.f_roff[g] = Q.fr0 + S.f_roff[f];
-            G.f_parent[g] = S.f_parent[f] < 0 ? -1 : (S.f_parent[f] >= Q.nfi ? nfG - 1 : (int)Q.f0 + S.f_parent[f]);
-            G.f_rowptr[g + 1] = S.f_n[f];
-            int* out = G.f_rows.data() + Q.frow0 + S.f_rowptr[f];
-            for (int q = 0; q < S.f_n[f]; ++q) out[q] = colmap(S.f_rows[S.f_rowptr[f] + q]);
-            G.ch_ptr[g + 1] = S.ch_ptr[f + 1] - S.ch_ptr[f];
-            G.fa_ptr[g + 1] = S.fa_ptr[f + 1] - S.fa_ptr[f];
-        }
-        auto put_children = [&](int c_lo, int c_hi, long long at, long long rel_at) {
-            for (int c = c_lo; c < c_hi; ++c, ++at) {
-                G.ch_kind[at] = S.ch_kind[c]; G.ch_id[at] = S.ch_kind[c] ? (int)Q.br0 + S.ch_id[c] : (int)Q.f0 + S.ch_id[c];
-                const long long r0 = S.ch_relptr[c], r1 = S.ch_relptr[c + 1];
-                G.ch_relptr[at + 1] = r1 - r0;                                    // (sizes now, the prefix sum below)
-                for (long long q = r0; q < r1; ++q) G.rel[rel_at + (q - r0)] = S.rel[q];
-                rel_at += r1 - r0;
-            }
-        };
-        put_children(0, (int)Q.nchI, Q.ch0, Q.rel0);
-        if (nif > 0) put_children(S.ch_ptr[Q.nfi], S.ch_ptr[Q.nfi + 1], ch0 + chI0[p], rel0 + relI0[p]);
-        auto put_entries = [&](int e_lo, int e_hi, long long at) {
-            for (int e = e_lo; e < e_hi; ++e, ++at) { G.fa_src[at] = valmap(S.fa_src[e]); G.fa_row[at] = S.fa_row[e]; G.fa_col[at] = S.fa_col[e]; G.fa_tr[at] = S.fa_tr[e]; }
-        };
-        put_entries(0, (int)Q.nfaI, Q.fa0);
-        if (nif > 0 && p == 0) put_entries(S.fa_ptr[Q.nfi], S.fa_ptr[Q.nfi + 1], fa0);      // (the interface's own values: every part lists them all, one copy counts)
-        // destinations of the values whose column is one of this part's interior columns (the interface's own stay -1: front)
-        for (int v = 0; v < (int)S.dest_bin.size(); ++v) if (S.dest_bin[v] >= 0) G.dest_bin[valmap(v)] = (int)(((Q.nnz0 + (S.dest_bin[v] >> 1)) << 1) | (S.dest_bin[v] & 1));
-    });
-    // ---- the interface columns and their front; prefix sums; orders
-    for (int i = 0; i < nif; ++i) { const int c = cI + i; G.order[c] = I[i]; G.perm[I[i]] = c; G.colptr[c + 1] = nif - i; G.parent[c] = i + 1 < nif ? c + 1 : -1; G.front_of_col[c] = nfG - 1; }
-    for (int c = 0; c < ns; ++c) G.colptr[c + 1] += G.colptr[c];
-    { long long at = nnz0; for (int i = 0; i < nif; ++i) for (int r = i; r < nif; ++r) G.rowidx[at++] = cI + r; }
     G.nnzL = nnzG;
-    for (int b = 0; b < nbG; ++b) { G.binptr[b + 1] += G.binptr[b]; G.binroot_ptr[b + 1] += G.binroot_ptr[b]; }
-    if (host_lists) {
-        for (int c = 0; c < ns; ++c) G.rlptr[c + 1] += G.rlptr[c];
-        G.mapptr.assign(ns + 1, 0);
-        for (int c = 0; c < ns; ++c) G.mapptr[c + 1] = G.mapptr[c] + (long long)(G.rlptr[c + 1] - G.rlptr[c]) * (long long)(G.colptr[c + 1] - G.colptr[c]);
-    }
-    for (int b = 0; b < nbG; ++b) G.bin_perm[b] = b;
-    std::stable_sort(G.bin_perm.begin(), G.bin_perm.end(), [&](int x, int y) { return G.bin_work[x] > G.bin_work[y]; });
+    // the interface front: its own columns, its children's counts; the arenas end behind it
     if (nif > 0) {
         const int g = nfG - 1, ld = (6 * nif + 15) & ~15;
         G.f_c0[g] = cI; G.f_s[g] = nif; G.f_n[g] = nif; G.f_ld[g] = ld; G.f_off[g] = fd0; G.f_roff[g] = fr0; G.f_parent[g] = -1;
@@ -1413,13 +1303,62 @@ bool pg_symbolic_parts(int ns, const std::vector<std::pair<int, int>>& edges, in
         G.ch_ptr[g + 1] = (int)chI; G.fa_ptr[g + 1] = (int)faI;
         G.front_doubles = fd0 + (long long)ld * ld; G.frhs_doubles = fr0 + ld;
     } else { G.front_doubles = fd0; G.frhs_doubles = fr0; }
+    return { nif, cI, nfG, host_lists, ch0, rel0, fa0 };
+}
+// ONE rank, analysed BY PARTS (round 6).  part[k]: part of separator k, non-decreasing, K parts.  The interface -- the separators with a
+// neighbour in a higher part -- is prescribed as the last, dense front; every part's own separators + the interface are ordered and analysed
+// independently of the other parts, all parts at the same time on the worker pool, and the results are joined into ONE ordinary
+// single-partition pg_sym (columns [part 0][part 1]...[interface], arenas and index spaces behind each other, the interface front taking
+// the children of all parts; see pg_analyse).  Returns false (G untouched) when the interface is wider than max_iface separators.
+bool pg_symbolic_parts(int ns, const std::vector<std::pair<int, int>>& edges, const double* cx, const double* cy,
+                       const int* part, int K, int max_iface, const pg_sym_opts& opt, pg_sym& G)
+{
+    const bool tv = opt.verbose;
+    const auto q0 = std::chrono::steady_clock::now();
+    auto ms_since = [](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count(); };
+    const std::vector<char> isif = upper_neighbour_nodes(ns, edges, part);      // (every edge between two parts has its lower end here)
+    std::vector<int> I;
+    for (int k = 0; k < ns; ++k) if (isif[k]) I.push_back(k);
+    const int nif = (int)I.size();
+    if (nif > max_iface || K < 2) return false;
+    std::vector<part_t> P(K);
+    std::once_flag coords_once;                                    // (the coordinates may still be on their way: the parts build their graphs first, ONE of them waits, the others behind it)
+    const double t_pre = ms_since(q0);
+    // ---- phase 1: every part on its own
+    dsss_pool_run(K, [&](int p) {
+        part_t& Q = P[p];
+        Q.g = pg_subgraph(ns, edges, isif, part, p);
+        pg_sym_opts o = opt;
+        o.threads = ns >= 131072 ? std::max(1, opt.threads / K) : 1;      // (a part of a C5-size graph is itself large enough for ranges; at C3's size forks cost what they gain)
+        o.before_order = nullptr; o.on_bottom_ready = nullptr; o.on_lists_ready = nullptr; o.to_be_joined = true; o.iface_last = Q.g.iface_last;
+        std::call_once(coords_once, [&] { if (opt.before_order) opt.before_order(); });
+        Q.g.copy_coords(cx, cy);
+        pg_symbolic(Q.g.size(), Q.g.ledges, Q.g.cx.data(), Q.g.cy.data(), nullptr, 1, o, Q.S);
+        Q.nint = Q.g.size() - nif;
+    });
+    const double t_parts = ms_since(q0);
+    for (const part_t& Q : P) if (nif > 0 && !iface_front_last(Q.S, nif)) return false;      // (the interface must be the last, dense front of every part)
+    const parts_join J = parts_layout(P, ns, ns + (int)edges.size(), nif, !opt.lists_on_device, G);
+    // ---- phase 2: every part writes its share of the joined tables
+    dsss_pool_run(K, [&](int p) { join_part(P[p], J, p == 0, G); });
+    // ---- the interface columns; prefix sums; orders
+    const int cI = J.cI, nfG = J.nfG, nbG = (int)G.binptr.size() - 1;
+    for (int i = 0; i < nif; ++i) { const int c = cI + i; G.order[c] = I[i]; G.perm[I[i]] = c; G.colptr[c + 1] = nif - i; G.parent[c] = i + 1 < nif ? c + 1 : -1; G.front_of_col[c] = nfG - 1; }
+    for (int c = 0; c < ns; ++c) { G.colptr[c + 1] += G.colptr[c]; if (J.host_lists) G.rlptr[c + 1] += G.rlptr[c]; }
+    { long long at = G.nnzL - (long long)nif * (nif + 1) / 2; for (int i = 0; i < nif; ++i) for (int r = i; r < nif; ++r) G.rowidx[at++] = cI + r; }
+    for (int b = 0; b < nbG; ++b) { G.binptr[b + 1] += G.binptr[b]; G.binroot_ptr[b + 1] += G.binroot_ptr[b]; }
+    if (J.host_lists) {
+        G.mapptr.assign(ns + 1, 0);
+        for (int c = 0; c < ns; ++c) G.mapptr[c + 1] = G.mapptr[c] + (long long)(G.rlptr[c + 1] - G.rlptr[c]) * (long long)(G.colptr[c + 1] - G.colptr[c]);
+    }
+    for (int b = 0; b < nbG; ++b) G.bin_perm[b] = b;
+    std::stable_sort(G.bin_perm.begin(), G.bin_perm.end(), [&](int x, int y) { return G.bin_work[x] > G.bin_work[y]; });
     for (int f = 0; f < nfG; ++f) { G.f_rowptr[f + 1] += G.f_rowptr[f]; G.ch_ptr[f + 1] += G.ch_ptr[f]; G.fa_ptr[f + 1] += G.fa_ptr[f]; }
     for (size_t c = 0; c + 1 < G.ch_relptr.size(); ++c) G.ch_relptr[c + 1] += G.ch_relptr[c];
     // statistics: the parts counted the interface columns once each
-    double if_cols = 0, if_front = 0;
-    for (int i = 0; i < nif; ++i) { const double m = nif - 1 - i; if_cols += 36.0 * 6.0 * (m * m + 3 * m) + 72.0; if_front += 216.0 * (m * m + 3 * m) + 72.0; }
-    for (int p = 0; p < K; ++p) { G.flops_factor += P[p].S.flops_factor - if_cols; G.flops_fronts += P[p].S.flops_fronts - (nif > 0 ? if_front : 0); }
-    G.flops_factor += if_cols; G.flops_fronts += nif > 0 ? if_front : 0;
+    const double if_fl = front_flops(nif, nif);                      // (the interface's columns and its front count the same)
+    for (int p = 0; p < K; ++p) { G.flops_factor += P[p].S.flops_factor - if_fl; G.flops_fronts += P[p].S.flops_fronts - if_fl; }
+    G.flops_factor += if_fl; G.flops_fronts += if_fl;
     for (int f = 0; f < nfG; ++f) G.max_front_n = std::max(G.max_front_n, G.f_n[f]);
     const double t_join = ms_since(q0);
     if (opt.on_lists_ready) opt.on_lists_ready();
@@ -1428,9 +1367,36 @@ bool pg_symbolic_parts(int ns, const std::vector<std::pair<int, int>>& edges, in
     sym_row_views(G, std::max(1, opt.threads));
     if (tv) { fprintf(stderr, "[dsss pg symbolic] separators per part:"); for (auto& q : P) fprintf(stderr, " %d", q.nint); fprintf(stderr, "\n"); }
     if (tv) fprintf(stderr, "[dsss pg symbolic] %d parts + an interface of %d: interface %.2f ms, the parts (their graphs, the wait for the coordinates, the analyses; largest %d separators) %.2f ms, joined %.2f ms, levels and row views %.2f ms | ns %d nnzL %lld bins %d fronts %d (max %d rows) panels %d levels %d front arena %.1f MB\n",
-                    K, nif, t_pre, [&] { int m = 0; for (auto& q : P) m = std::max(m, (int)q.glob_of.size()); return m; }(), t_parts - t_pre, t_join - t_parts, ms_since(q0) - t_join, ns, G.nnzL,
+                    K, nif, t_pre, [&] { int m = 0; for (auto& q : P) m = std::max(m, q.g.size()); return m; }(), t_parts - t_pre, t_join - t_parts, ms_since(q0) - t_join, ns, G.nnzL,
                     nbG, nfG, G.max_front_n, G.npanels, G.nlev, G.front_doubles * 8e-6);
     return true;
+}
+
+} // namespace
+
+pg_switches pg_switches_read()
+{
+    pg_switches sw;
+    if (const char* v = getenv("DSSS_PG_BIN_COST")) sw.bin_cost = sw.opt.bin_cost = atof(v);
+    if (const char* v = getenv("DSSS_PG_LEAF")) sw.opt.leaf = atoi(v);
+    if (const char* v = getenv("DSSS_PG_ND_BOTH")) sw.opt.nd_both_axes = atoi(v);
+    if (const char* v = getenv("DSSS_PG_ND_INDEX")) sw.opt.nd_index_cuts = atoi(v);
+    if (const char* v = getenv("DSSS_PG_PARTS_ANALYSIS")) sw.parts = atoi(v);
+    if (const char* v = getenv("DSSS_SYM_THREADS")) sw.threads = atoi(v);
+    if (const char* v = getenv("DSSS_PG_LOCAL")) sw.local = atoi(v) != 0;
+    if (const char* v = getenv("DSSS_PG_VERBOSE")) sw.opt.verbose = std::max(1, atoi(v));
+    return sw;
+}
+int pg_cheapest_gap(const int* pos, const std::vector<int>& cross, int target, int width, int after, int* cost)
+{
+    const int m = (int)cross.size() - 1, lo = std::max(target - width, after + 1);
+    auto start = [&](int i) { return pos ? pos[i - 1] + 1 : i; };
+    int best = -1; long long bdist = 0;
+    for (int i = std::max(1, pos ? (int)(std::lower_bound(pos, pos + m, lo - 1) - pos) + 1 : lo); i < m && start(i) <= target + width; ++i) {
+        const long long d = std::llabs((long long)start(i) - target);
+        if (best < 0 || cross[i] < *cost || (cross[i] == *cost && d < bdist)) { *cost = cross[i]; bdist = d; best = start(i); }
+    }
+    return best;
 }
 
 // ------------------------------------------------------------------ the analysis of the device solve (dsss_pg_sym.h)
@@ -1455,57 +1421,42 @@ void pg_analyse(int ns, const std::vector<std::pair<int, int>>& edges, const dou
     opt.bin_cost = sw.bin_cost.value_or(PG_BIN_COST_DEVICE);
     opt.threads = sym_threads(ns);
     pg_sym& S = A.S;
-    std::vector<int> loc_of, glob_of, ledge_g;
-    std::vector<std::pair<int, int>> ledges;
     if (world > 1 && sw.local) {
-        std::vector<int> rank_of_part(nparts, 0);
+        std::vector<int> rank_of_part(nparts, 0), rank_of(ns);
         for (int r = 0; r < world; ++r) for (int p = (int)((long long)nparts * r / world); p < (int)((long long)nparts * (r + 1) / world); ++p) rank_of_part[p] = r;
-        std::vector<char> isif(ns, 0);
-        for (const auto& e : edges) {
-            const int ra = rank_of_part[part[e.first]], rb = rank_of_part[part[e.second]];
-            if (ra < rb) isif[e.first] = 1; else if (rb < ra) isif[e.second] = 1;
-        }
-        int nif_l = 0; for (int k = 0; k < ns; ++k) nif_l += isif[k];
-        if (nif_l <= PG_LOCAL_IFACE_MAX) {
+        for (int k = 0; k < ns; ++k) rank_of[k] = rank_of_part[part[k]];
+        const std::vector<char> isif = upper_neighbour_nodes(ns, edges, rank_of.data());
+        if (std::count(isif.begin(), isif.end(), 1) <= PG_LOCAL_IFACE_MAX) {
             A.local = true;
-            loc_of.assign(ns, -1);
-            for (int k = 0; k < ns; ++k)
-                if (isif[k] || rank_of_part[part[k]] == rank) { loc_of[k] = (int)glob_of.size(); if (isif[k]) opt.iface_last.push_back(loc_of[k]); glob_of.push_back(k); }
-            for (size_t g = 0; g < edges.size(); ++g) {
-                const int a = loc_of[edges[g].first], b = loc_of[edges[g].second];
-                if (a >= 0 && b >= 0 && a != b) { ledges.push_back({ a, b }); ledge_g.push_back((int)g); }
-            }
+            pg_subgraph L(ns, edges, isif, rank_of.data(), rank);
+            const int nsl = L.size();
+            const std::function<void()> coords = opt.before_order;
+            opt.before_order = [&] { if (coords) coords(); L.copy_coords(cx, cy); };
+            opt.on_bottom_ready = nullptr; opt.on_lists_ready = nullptr;      // (nothing goes up early: the tables below come last)
+            opt.iface_last = L.iface_last;
+            if (!sw.bin_cost && nsl < 16384) opt.bin_cost = PG_BIN_COST_RANK;
+            opt.threads = sym_threads(nsl);
+            pg_symbolic(nsl, L.ledges, L.cx.data(), L.cy.data(), nullptr, 1, opt, S);
+            pg_build_schedule(S, 0, 1, A.SO);
+            pg_build_schedule(S, -1, 0, A.SI);
+            const int nval_g = ns + (int)edges.size();
+            A.perm_g.assign(ns, -1); A.dest_g.assign(nval_g, -1); A.ifslot_g.assign(ns, -1);
+            for (int i = 0; i < nsl; ++i) A.perm_g[L.glob_of[i]] = S.perm[i];
+            for (int v = 0; v < (int)S.dest_bin.size(); ++v) A.dest_g[L.val_g(v)] = S.dest_bin[v];
+            for (int& v : S.fa_src) v = v >= S.nval ? nval_g + (v - S.nval) : L.val_g(v);
+            for (size_t q = 0; q < S.iface_seps.size(); ++q) { const int k = L.glob_of[S.iface_seps[q]]; A.ifsep_g.push_back(k); A.ifslot_g[k] = (int)q; }
+            return;
         }
-    }
-    if (A.local) {
-        const int nsl = (int)glob_of.size();
-        std::vector<double> cxl(nsl), cyl(nsl);
-        const std::function<void()> coords = opt.before_order;
-        opt.before_order = [&] { if (coords) coords(); for (int i = 0; i < nsl; ++i) { cxl[i] = cx[glob_of[i]]; cyl[i] = cy[glob_of[i]]; } };
-        opt.on_bottom_ready = nullptr; opt.on_lists_ready = nullptr;      // (nothing goes up early: the tables below come last)
-        if (!sw.bin_cost && nsl < 16384) opt.bin_cost = PG_BIN_COST_RANK;
-        opt.threads = sym_threads(nsl);
-        pg_symbolic(nsl, ledges, 0, cxl.data(), cyl.data(), nullptr, 1, opt, S);
-        pg_build_schedule(S, 0, 1, A.SO);
-        pg_build_schedule(S, -1, 0, A.SI);
-        const int nval_g = ns + (int)edges.size();
-        A.perm_g.assign(ns, -1); A.dest_g.assign(nval_g, -1); A.ifslot_g.assign(ns, -1);
-        for (int i = 0; i < nsl; ++i) { A.perm_g[glob_of[i]] = S.perm[i]; A.dest_g[glob_of[i]] = S.dest_bin[i]; }
-        for (size_t le = 0; le < ledges.size(); ++le) A.dest_g[ns + ledge_g[le]] = S.dest_bin[nsl + le];
-        for (int& v : S.fa_src) v = v >= S.nval ? nval_g + (v - S.nval) : (v < nsl ? glob_of[v] : ns + ledge_g[v - nsl]);
-        for (size_t q = 0; q < S.iface_seps.size(); ++q) { const int k = glob_of[S.iface_seps[q]]; A.ifsep_g.push_back(k); A.ifslot_g[k] = (int)q; }
-        return;
     }
     // ONE rank, one partition: the analysis BY PARTS (pg_symbolic_parts, round 6).  The phases of pg_symbolic gain nothing from threads at
     // C3's size (one thread 4.0 ms, eight 3.4: a dozen fork / joins around 0.1 - 0.3 ms of work each), whole parts do: the chain order is
     // cut into K parts where few loop closures cross (the gap with the fewest spanning loop closures within a third of a part of the
     // equal-count position: one difference array over the separators prices them all), every part is ordered and analysed on its own
-    // thread with the interface between the parts as the last dense front, and the tables are joined.
+    // thread with the interface between the parts as the last dense front, and the tables are joined.  K depends on the graph alone (it
+    // fixes the elimination order): the host's threads only decide how many parts run at once.
     bool by_parts = false;
     // (parts of about a thousand separators, at most 8, up to C3's size -- C2: 3 292 separators in 3 parts, step 7.6 -> 6.6 ms --; 16 from 64 k separators on)
     int K = sw.parts ? *sw.parts : (ns >= 1500 ? (ns < 65536 ? std::min(8, std::max(2, ns / 1000)) : 16) : 0);
-    // (the parts need threads of their own: on a host with fewer than four the one graph is the shorter analysis)
-    if (!sw.parts) { const int hw = (int)std::thread::hardware_concurrency(); K = hw >= 4 ? std::min(K, hw) : 0; }
     if (nparts == 1 && K >= 2 && (int)edges.size() > ns - 1) {
         K = std::min(K, ns / 8);
         std::vector<int> cross(ns + 1, 0), vpart(ns, 0);
@@ -1519,29 +1470,97 @@ void pg_analyse(int ns, const std::vector<std::pair<int, int>>& edges, const dou
             if (best > prev && bcost <= std::max(PG_PARTS_CUT_MAX, ns / 16384)) { starts.push_back(best); prev = best; }      // (an expensive boundary is left out: its two parts stay one)
         }
         for (int k = 0; k < ns; ++k) { while (p_cur < (int)starts.size() && k >= starts[p_cur]) ++p_cur; vpart[k] = p_cur; }
-        if (!starts.empty()) by_parts = pg_symbolic_parts(ns, edges, ns - 1, cx, cy, vpart.data(), (int)starts.size() + 1, PG_PARTS_IFACE_MAX, opt, S);
+        if (!starts.empty()) by_parts = pg_symbolic_parts(ns, edges, cx, cy, vpart.data(), (int)starts.size() + 1, PG_PARTS_IFACE_MAX, opt, S);
     }
-    if (!by_parts) pg_symbolic(ns, edges, ns - 1, cx, cy, nparts > 1 ? part : nullptr, nparts, opt, S);
+    if (!by_parts) pg_symbolic(ns, edges, cx, cy, part, nparts, opt, S);
     // launch lists: this rank's interior fronts, then (after the all-reduce) the replicated interface fronts
     pg_build_schedule(S, part_lo, part_hi, A.SO);
     if (nparts > 1) pg_build_schedule(S, -1, 0, A.SI);
 }
 
+// ------------------------------------------------------------------ C ABI of the host twin (CPU test-suite; include/dsss.h)
+#include "../../include/dsss.h"
+// the edge list of a host twin, checked: both ends of every edge in [0, ns), no self edges unless self, and with chain the ns - 1 chain
+// couplings (k, k + 1) first.  False: the arguments are refused.
+static bool twin_edges(int ns, const int32_t* edge_a, const int32_t* edge_b, int nedges, bool chain, bool self, std::vector<std::pair<int, int>>& edges)
+{
+    edges.resize(nedges);
+    for (int e = 0; e < nedges; ++e) {
+        const int a = edge_a[e], b = edge_b[e];
+        if (a < 0 || a >= ns || b < 0 || b >= ns || (!self && a == b) || (chain && e < ns - 1 && (a != e || b != e + 1))) return false;
+        edges[e] = { a, b };
+    }
+    return true;
+}
+// a host twin's statistics (stats8[5]: s5) and its return code from pg_host_solve's
+static int twin_result(const pg_sym& S, int rc, int64_t s5, int64_t* stats8)
+{
+    if (stats8) {
+        stats8[0] = S.nnzL; stats8[1] = (int64_t)S.f_c0.size(); stats8[2] = S.npanels; stats8[3] = S.nlev;
+        stats8[4] = S.front_doubles; stats8[5] = s5; stats8[6] = (int64_t)S.bincols.size(); stats8[7] = S.max_front_n;
+    }
+    return rc == 0 ? DSSS_OK : (rc == -1 ? DSSS_E_NUMERIC : DSSS_E_STATE);
+}
+extern "C" int dsss_host_pg_solve(int ns, const int32_t* edge_a, const int32_t* edge_b, int nedges, const double* cx, const double* cy,
+                                  const int32_t* part, int nparts, const double* aval, const double* rhs, double* x, int64_t* stats8)
+{
+    if (ns < 1 || nedges < ns - 1 || !edge_a || !edge_b || !cx || !cy || (x && (!aval || !rhs))) return DSSS_E_ARG;      // x == NULL: analysis only
+    std::vector<std::pair<int, int>> edges;
+    if (!twin_edges(ns, edge_a, edge_b, nedges, true, true, edges)) return DSSS_E_ARG;
+    pg_sym S;
+    const pg_switches sw = pg_switches_read();
+    pg_sym_opts opt = sw.opt;
+    if (sw.threads) opt.threads = std::max(1, *sw.threads);
+    opt.lists_on_device = x == nullptr;                     // analysis only: as the product runs it (the bins' lists are built on the device there)
+    pg_symbolic(ns, edges, cx, cy, part, nparts, opt, S);
+    if (S.ownership_violations) return DSSS_E_STATE;        // a lower-rank end of a cross-rank factor outside the interface
+    if (!x) {      // (what the product builds next; timed with the analysis by tools/sym_time.py)
+        const auto t0 = std::chrono::steady_clock::now();
+        pg_sched so, si; pg_build_schedule(S, 0, std::max(1, nparts), so); if (nparts > 1) pg_build_schedule(S, -1, 0, si);
+        if (opt.verbose)
+            fprintf(stderr, "[dsss pg symbolic] launch lists %.2f ms (%zu assembly rows, %zu panel steps, %zu tiles)\n",
+                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(),
+                    so.asmrow_front.size() + si.asmrow_front.size(), so.lv_front.size() + si.lv_front.size(), so.tile_item.size() + si.tile_item.size());
+    }
+    const int rc = x ? pg_host_solve(S, aval, rhs, x) : 0;
+    return twin_result(S, rc, S.comm_doubles, stats8);
+}
+// the same with a PRESCRIBED interface (pg_sym_opts::iface_last): the analysis one rank of several runs on its own separators + the
+// interface nodes.  Any edge list (no chain prefix); iface_last ascending.
+extern "C" int dsss_host_pg_solve_local(int ns, const int32_t* edge_a, const int32_t* edge_b, int nedges, const double* cx, const double* cy,
+                                        const int32_t* iface_last, int nlast, const double* aval, const double* rhs, double* x, int64_t* stats8)
+{
+    if (ns < 1 || nedges < 0 || (nedges > 0 && (!edge_a || !edge_b)) || !cx || !cy || nlast < 0 || nlast > ns || (nlast > 0 && !iface_last) || !x || !aval || !rhs) return DSSS_E_ARG;
+    std::vector<std::pair<int, int>> edges;
+    if (!twin_edges(ns, edge_a, edge_b, nedges, false, false, edges)) return DSSS_E_ARG;
+    pg_sym S; pg_sym_opts opt = pg_switches_read().opt;
+    for (int q = 0; q < nlast; ++q) {
+        if (iface_last[q] < 0 || iface_last[q] >= ns || (q > 0 && iface_last[q] <= iface_last[q - 1])) return DSSS_E_ARG;
+        opt.iface_last.push_back(iface_last[q]);
+    }
+    pg_symbolic(ns, edges, cx, cy, nullptr, 1, opt, S);
+    // the interface is the LAST front, dense over exactly the prescribed nodes
+    if (nlast > 0) {
+        const int nf = (int)S.f_c0.size();
+        if (!iface_front_last(S, nlast)) return DSSS_E_STATE;
+        for (int f = 0; f + 1 < nf; ++f) if (S.f_part[f] < 0) return DSSS_E_STATE;
+        for (int q = 0; q < nlast; ++q) if (S.order[ns - nlast + q] != iface_last[q] || (int)S.iface_seps.size() != nlast || S.iface_seps[q] != iface_last[q]) return DSSS_E_STATE;
+        if (!S.comm_kind.empty()) return DSSS_E_STATE;
+    }
+    const int rc = pg_host_solve(S, aval, rhs, x);
+    return twin_result(S, rc, (int64_t)S.comm_vals.size(), stats8);
+}
 // host twin entry: one rank analysed by K parts of equal size in the chain order (CPU test-suite)
 extern "C" int dsss_host_pg_solve_parts(int ns, const int32_t* edge_a, const int32_t* edge_b, int nedges, const double* cx, const double* cy,
                                         int K, const double* aval, const double* rhs, double* x, int64_t* stats8)
 {
     if (ns < 1 || nedges < ns - 1 || !edge_a || !edge_b || !cx || !cy || K < 2 || !x || !aval || !rhs) return DSSS_E_ARG;
-    std::vector<std::pair<int, int>> edges(nedges);
-    for (int e = 0; e < nedges; ++e) {
-        edges[e] = { edge_a[e], edge_b[e] };
-        if (edge_a[e] < 0 || edge_a[e] >= ns || edge_b[e] < 0 || edge_b[e] >= ns) return DSSS_E_ARG;
-        if (e < ns - 1 && (edge_a[e] != e || edge_b[e] != e + 1)) return DSSS_E_ARG;
-    }
+    std::vector<std::pair<int, int>> edges;
+    if (!twin_edges(ns, edge_a, edge_b, nedges, true, true, edges)) return DSSS_E_ARG;
     pg_sym S; pg_sym_opts opt = pg_switches_read().opt;
     std::vector<int> part(ns);
     for (int k = 0; k < ns; ++k) part[k] = (int)((long long)k * K / ns);
-    if (!pg_symbolic_parts(ns, edges, ns - 1, cx, cy, part.data(), K, ns, opt, S)) return DSSS_E_STATE;
-    const int rc = pg_host_solve(S, nedges - (ns - 1), edges, aval, rhs, x);
+    if (!pg_symbolic_parts(ns, edges, cx, cy, part.data(), K, ns, opt, S)) return DSSS_E_STATE;
+    const int rc = pg_host_solve(S, aval, rhs, x);
     return twin_result(S, rc, 0, stats8);
 }

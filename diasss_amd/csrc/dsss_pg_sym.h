@@ -113,8 +113,6 @@ struct pg_sched {
     std::vector<int> max_w6, max_rows;                         // per level: scalar columns of its widest panel step, scalar rows below its tallest one (the dependent chains of the level)
     int max_n6 = 6;
 };
-// part_lo <= front part < part_hi selects fronts; (-1, 0) selects the interface fronts
-void pg_build_schedule(const pg_sym& S, int part_lo, int part_hi, pg_sched& out);
 
 struct pg_sym_opts {
     int leaf = 24;                      // nested-dissection leaf size
@@ -144,8 +142,8 @@ struct pg_sym_opts {
     // interface out the same way: the front is summed over the ranks as it is); the nested dissection orders the other nodes only.
     // Their columns get col_part -1, their values the interface codes of dest_bin; no update matrix is packed for a collective.
     std::vector<int> iface_last;
-    bool to_be_joined = false;          // pg_symbolic_parts: the panel levels and the per-row views of the fronts are built once, on the joined tables
-    bool iface_plain = false;           // with iface_last: the interface values stay ordinary values of the value array (no summed slots): one rank analysing by parts (pg_symbolic_parts)
+    bool to_be_joined = false;          // a part of pg_symbolic_parts: the panel levels and the per-row views are built once, on the joined tables, and
+                                        // the interface values stay ordinary values of the value array (no summed slots)
     int verbose = 0;                    // DSSS_PG_VERBOSE: phase times; 2 and up: the critical path of the schedule as well
 };
 
@@ -164,23 +162,10 @@ pg_switches pg_switches_read();
 // and its cost, or -1.  (The partition boundaries of the device solve; the cuts of the analysis by parts.)
 int pg_cheapest_gap(const int* pos, const std::vector<int>& cross, int target, int width, int after, int* cost);
 
-// edges: pairs of chain-order separator indices, the ns-1 chain couplings (k, k+1) first, then the LC edges.
-// part[k] (may be null): rank that owns separator k, non-decreasing in k.  cx, cy: DR positions of the separators.
-void pg_symbolic(int ns, const std::vector<std::pair<int, int>>& edges, int nchain, const double* cx, const double* cy,
-                 const int* part, int nparts, const pg_sym_opts& opt, pg_sym& S);
-
-// ONE rank, analysed BY PARTS (round 6).  part[k]: part of separator k, non-decreasing, K parts.  The interface -- the separators with a
-// neighbour in a higher part -- is prescribed as the last, dense front; every part's own separators + the interface are ordered and analysed
-// independently of the other parts, all parts at the same time on the worker pool, and the results are joined into ONE ordinary
-// single-partition pg_sym (columns [part 0][part 1]...[interface], arenas and index spaces behind each other, the interface front taking
-// the children of all parts).  The phases of pg_symbolic do not speed up with threads at C3's size (a dozen fork / joins of 0.1 ms of work
-// each: one thread 4.0 ms, eight 3.4); whole parts do.  Returns false (S untouched) when the interface is wider than max_iface separators.
-bool pg_symbolic_parts(int ns, const std::vector<std::pair<int, int>>& edges, int nchain, const double* cx, const double* cy,
-                       const int* part, int K, int max_iface, const pg_sym_opts& opt, pg_sym& S);
-
 // The analysis of the device solve (dsss_pg.hip) and how it is chosen: the rank-local analysis (several ranks), the analysis by parts
-// (one rank, one partition, a large graph) or the one graph.  edges: as pg_symbolic's, chain first; part[k]: partition of separator k;
-// partitions [part_lo, part_hi) of nparts are this rank's.  opt: the caller's hooks (before_order, on_bottom_ready, on_lists_ready).
+// (one rank, one partition, a large graph) or the one graph.  edges: chain-order separator pairs, the ns - 1 couplings (k, k + 1) first, then
+// the LC edges; cx, cy: DR positions; part[k]: partition of separator k (non-decreasing), [part_lo, part_hi) of nparts are this rank's.  opt: the
+// caller's hooks (before_order, on_bottom_ready, on_lists_ready).
 struct pg_analysis {
     pg_sym S;
     pg_sched SO, SI;                    // launch lists: this rank's interior fronts; the interface fronts (after the all-reduce)
@@ -189,8 +174,3 @@ struct pg_analysis {
 };
 void pg_analyse(int ns, const std::vector<std::pair<int, int>>& edges, const double* cx, const double* cy, const int* part, int nparts,
                 int part_lo, int part_hi, int world, int rank, const pg_switches& sw, pg_sym_opts opt, pg_analysis& A);
-
-// Host twin of the numeric phase, used by the CPU test-suite only (the product path is dsss_pg.hip): factorises the matrix
-// given by `aval` (36 doubles per value index, see dest_bin) and solves for `rhs` (6 per separator, chain order).  Returns 0
-// or -1 when a pivot is not positive.
-int pg_host_solve(const pg_sym& S, int ne, const std::vector<std::pair<int, int>>& edges, const double* aval, const double* rhs, double* x);

@@ -268,3 +268,53 @@ def test_host_solver_under_thread_sanitizer(tmp_path):
     out = subprocess.run(norand + ["bash", os.path.join(ROOT, "tools", "sanitize", "run.sh"), "tsan"], capture_output=True, text=True, timeout=900,
                          env=dict(os.environ, TMPDIR=str(tmp_path)))
     assert out.returncode == 0 and "sanitizers: clean" in out.stdout, out.stdout[-2000:] + out.stderr[-3000:]
+
+
+def _values(ns, ea, eb, seed):
+    """block values of an SPD system (block diagonal dominance) without the dense matrix, for graphs too large for numpy's solve"""
+    rng = np.random.default_rng(seed)
+    ne = len(ea)
+    aval = np.zeros((ns + ne, 36))
+    aval[ns:] = rng.normal(0, 0.3, (ne, 36))
+    deg = np.bincount(ea, minlength=ns) + np.bincount(eb, minlength=ns)
+    aval[:ns] = (np.eye(6).ravel()[None, :] * (2.5 * deg + 1.0)[:, None])
+    return aval, rng.normal(0, 1, (ns, 6))
+
+
+@pytest.mark.parametrize("nparts", [1, 3])
+def test_host_solve_is_bit_identical_for_any_thread_count(nparts, monkeypatch):
+    """DSSS_SYM_THREADS (the ranges per parallel phase of the analysis, the pool's tasks) changes how fast the analysis runs, never
+    what it computes: the solution and the statistics of a lawn-mower graph of 4 000 separators are bit-identical for 1, 3 and 8
+    threads, with one partition and with three."""
+    legs, per_leg = 40, 100
+    ns, chords, cx, cy = _lawnmower(legs, per_leg, 12)
+    ea = np.array(list(range(ns - 1)) + [c[0] for c in chords], np.int32)
+    eb = np.array(list(range(1, ns)) + [c[1] for c in chords], np.int32)
+    aval, rhs = _values(ns, ea, eb, 13)
+    part = None if nparts == 1 else (np.arange(ns) // per_leg * nparts // legs).astype(np.int32)
+    runs = []
+    for threads in ("1", "3", "8"):
+        monkeypatch.setenv("DSSS_SYM_THREADS", threads)
+        runs.append(_solve(ea, eb, aval, rhs, cx, cy, part, nparts))
+    assert np.all(np.isfinite(runs[0][0]))
+    for x, st in runs[1:]:
+        assert np.array_equal(x, runs[0][0]) and np.array_equal(st, runs[0][1])
+
+
+def test_large_analysis_is_the_same_for_any_thread_count(monkeypatch):
+    """Node sets of 65 536 separators and more run the passes of the ordering by ranges (key copies, histograms, marks, counts, the
+    chain-order cut's difference array): the analysis alone (x = NULL, as the product runs it) of a lawn-mower graph of 72 000
+    separators gives the same statistics with 1 and with 8 threads."""
+    from diasss_amd import capi
+    L = capi.lib()
+    ns, chords, cx, cy = _lawnmower(100, 720, 14, density=0.3)
+    ea = np.array(list(range(ns - 1)) + [c[0] for c in chords], np.int32)
+    eb = np.array(list(range(1, ns)) + [c[1] for c in chords], np.int32)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    stats = []
+    for threads in ("1", "8"):
+        monkeypatch.setenv("DSSS_SYM_THREADS", threads)
+        st = np.zeros(8, np.int64)
+        assert L.dsss_host_pg_solve(ns, p(ea), p(eb), len(ea), p(cx), p(cy), None, 1, None, None, None, p(st)) == 0
+        stats.append(st)
+    assert stats[0][0] > 0 and np.array_equal(stats[0], stats[1]), [s.tolist() for s in stats]
