@@ -48,8 +48,14 @@ class PGParams(C.Structure):
                 ("add_noise", C.c_int32)]
 
 
+class MosaicParams(C.Structure):
+    """dsss_mosaic_params: cell (ix, iy) covers [x0 + ix cell, x0 + (ix + 1) cell) x [y0 + iy cell, ...); layers are H x W"""
+    _fields_ = [("x0", C.c_double), ("y0", C.c_double), ("cell", C.c_double), ("W", C.c_int32), ("H", C.c_int32),
+                ("use_mask", C.c_int32), ("pad_", C.c_int32)]
+
+
 class DsssError(RuntimeError):
-    pass
+    code = None          # the DSSS_E_* value where the error came from the library
 
 
 class FramesArgs:
@@ -154,6 +160,20 @@ def _ptr(a):
     return C.c_void_p(int(a))
 
 
+def mosaic_grid(bbox4, cell):
+    """dsss_mosaic_grid: the MosaicParams of the grid that covers bbox4 = (xmin, xmax, ymin, ymax) with cells of edge `cell` (use_mask = 1).
+    Host arithmetic, no context."""
+    bb = np.ascontiguousarray(bbox4, np.float64); assert bb.shape == (4,)
+    p = MosaicParams()
+    L = lib()
+    rc = L.dsss_mosaic_grid(_ptr(bb), C.c_double(cell), C.byref(p))
+    if rc != 0:
+        e = DsssError("dsss_mosaic_grid: %s (bbox %s, cell %r)" % (L.dsss_strerror(rc).decode(), bb.tolist(), cell))
+        e.code = rc
+        raise e
+    return p
+
+
 class Context:
     """thin RAII wrapper over dsss_ctx"""
 
@@ -181,8 +201,10 @@ class Context:
 
     def _chk(self, rc, what):
         if rc != 0:
-            raise DsssError("%s: %s (%s)" % (what, self.L.dsss_strerror(rc).decode(),
-                                             self.L.dsss_last_error(self.h).decode()))
+            e = DsssError("%s: %s (%s)" % (what, self.L.dsss_strerror(rc).decode(),
+                                           self.L.dsss_last_error(self.h).decode()))
+            e.code = rc
+            raise e
 
     # ---- params
     def default_params(self):
@@ -494,6 +516,44 @@ class Context:
         lv = np.zeros((max(n.value, 1), 4), np.int32)
         self._chk(self.L.dsss_posegraph_schedule_get(self.h, _ptr(lv), n.value, C.byref(n), C.byref(t)), "dsss_posegraph_schedule_get")
         return lv[:n.value], t.value
+
+    # ---- mosaic
+    @staticmethod
+    def _mosaic_traj(ids, rpy6, ping_off):
+        ids = np.ascontiguousarray(ids, np.int32)
+        if rpy6 is not None:
+            rpy6 = np.ascontiguousarray(rpy6, np.float64); assert rpy6.ndim == 2 and rpy6.shape[1] == 6
+        if ping_off is not None:
+            ping_off = np.ascontiguousarray(ping_off, np.int32); assert ping_off.shape == ids.shape
+        return ids, rpy6, ping_off
+
+    def mosaic_bounds(self, ids, rpy6=None, ping_off=None):
+        """union of the frames' geo extremes under the trajectory (rpy6 rows "r p y x y z", frame ids[i] from row ping_off[i]; None: the
+        dead-reckoning poses the frames were set with) -> (xmin, xmax, ymin, ymax)"""
+        ids, rpy6, ping_off = self._mosaic_traj(ids, rpy6, ping_off)
+        bb = np.zeros(4, np.float64)
+        self._chk(self.L.dsss_mosaic_bounds(self.h, _ptr(ids), len(ids), _ptr(rpy6), _ptr(ping_off), _ptr(bb)), "dsss_mosaic_bounds")
+        return bb
+
+    def mosaic_render(self, ids, params, rpy6=None, ping_off=None, download=True):
+        """the frames' normalised images binned into the grid `params` -> (sum, cnt, img): H x W uint32, uint32, uint8.
+        download=False renders on the device only and returns None (timing)."""
+        ids, rpy6, ping_off = self._mosaic_traj(ids, rpy6, ping_off)
+        out = (np.empty((params.H, params.W), np.uint32), np.empty((params.H, params.W), np.uint32),
+               np.empty((params.H, params.W), np.uint8)) if download else (None, None, None)
+        self._chk(self.L.dsss_mosaic_render(self.h, _ptr(ids), len(ids), _ptr(rpy6), _ptr(ping_off), C.byref(params),
+                                            _ptr(out[0]), _ptr(out[1]), _ptr(out[2])), "dsss_mosaic_render")
+        return out if download else None
+
+    def mosaic_consistency(self, ids, params, rpy6=None, ping_off=None):
+        """what overlapping frames say about a cell -> (nfr, s1, s2, score): frames that see the cell, sum and sum of squares of their
+        mean grey levels (H x W uint32), and the pooled standard deviation over the cells seen by two frames or more"""
+        ids, rpy6, ping_off = self._mosaic_traj(ids, rpy6, ping_off)
+        nfr, s1, s2 = (np.empty((params.H, params.W), np.uint32) for _ in range(3))
+        score = C.c_double(0.0)
+        self._chk(self.L.dsss_mosaic_consistency(self.h, _ptr(ids), len(ids), _ptr(rpy6), _ptr(ping_off), C.byref(params),
+                                                 _ptr(nfr), _ptr(s1), _ptr(s2), C.byref(score)), "dsss_mosaic_consistency")
+        return nfr, s1, s2, score.value
 
     # ---- instrumentation
     def profile(self, on=True):

@@ -133,6 +133,7 @@ struct dsss_ctx {
     // online use (dsss_posegraph_update): the estimate of the previous update stays on the device, the LC edges accumulate
     void* pg_warm = nullptr; size_t pg_warm_cap = 0; int pg_warm_n = 0;   // pose_t[pg_warm_n]
     std::vector<dsss_lc_edge> pg_inc_edges; unsigned long long lc_gen = 0, pg_inc_gen = 0;    // lc_gen counts LC result sets; the last one consumed
+    void* mosaic_buf = nullptr; size_t mosaic_cap = 0;          // device scratch of dsss_mosaic_*: accumulators, output layers, job table, trajectory rows (kept between calls)
     dsss_prof prof;
 };
 
@@ -208,16 +209,25 @@ __host__ __device__ inline void dsss_sincos(double x, double* s, double* c)
     else { *s = -cr; *c = sr; }
 }
 
-// Frame::GetGeoImg for one bin (frame.cpp:126-165); port column 0 clamps the one-past-the-end read
+// Frame::GetGeoImg for one bin (frame.cpp:126-165); port column 0 clamps the one-past-the-end read.  In two steps, because the bearing of
+// a side is the same for every bin of a ping: a kernel that walks a whole ping (dsss_mosaic.hip) takes the first step once per side.
+__host__ __device__ inline void dsss_geo_side(const double* P, bool starboard, double* s, double* c)      // P: the ping's pose row
+{
+    dsss_sincos(starboard ? P[2] + DSSS_PI_REF / 2 : P[2] - DSSS_PI_REF / 2, s, c);
+}
+__host__ __device__ inline void dsss_geo_bin(const double* P, const double* gr, int M, int col, double s, double c, double* x, double* y)
+{
+    int half = M / 2, idx;
+    if (col >= half) idx = col - half;
+    else { idx = half - col; if (idx > half - 1) idx = half - 1; }
+    *x = (P[3] - 0.0) + gr[idx] * c;
+    *y = (P[4] - 0.0) + gr[idx] * s;
+}
 __host__ __device__ inline void dsss_geo_at(const double* pose6, const double* gr, int M, int row, int col,
                                             double* x, double* y)
 {
     const double* P = pose6 + (size_t)row * 6;
-    int half = M / 2, idx; double ang;
-    if (col >= half) { idx = col - half; ang = P[2] + DSSS_PI_REF / 2; }
-    else { idx = half - col; if (idx > half - 1) idx = half - 1; ang = P[2] - DSSS_PI_REF / 2; }
     double s, c;
-    dsss_sincos(ang, &s, &c);
-    *x = (P[3] - 0.0) + gr[idx] * c;
-    *y = (P[4] - 0.0) + gr[idx] * s;
+    dsss_geo_side(P, col >= M / 2, &s, &c);
+    dsss_geo_bin(P, gr, M, col, s, c, x, y);
 }

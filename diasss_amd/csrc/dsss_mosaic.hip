@@ -1,0 +1,362 @@
+// diasss_amd/csrc/dsss_mosaic.hip -- georeferenced mosaic and overlap-consistency map (include/dsss.h, section "mosaic").
+// The reference has no counterpart: it stops at the trajectory file.  What goes into the mosaic is on the device when the solve
+// returns (normalised waterfall, filter mask, geometry), so the map is a forward scatter of the pixels into a grid of integer
+// accumulators.  Integers because the result has to be the same whatever the order of the frames and from call to call.
+#include "dsss_internal.h"
+#include <algorithm>
+
+#define MOSAIC_MAX_CELLS (1ll << 28)
+#define MOSAIC_MAX_SAMPLES (1u << 24)      // per cell: 255 * 2^24 < 2^32, the u32 sum cannot wrap below it
+
+namespace {
+
+// one frame of a launch: its pose rows (the frame's own or the caller's trajectory), geometry and images; blk0 = its first workgroup
+struct mosaic_job { const double* pose; const double* gr; const uint8_t* img; const uint8_t* mask; int N, M, blk0, pad; };
+// the grid (x0, y0, cell, W, H: where a point falls and whether it is kept) and the window of it the accumulators cover
+// (ox, oy, bw, bh: the whole grid for the mosaic, one frame's cell bounding box for the consistency map)
+struct mosaic_win { double x0, y0, cell; int W, H, ox, oy, bw, bh, use_mask; };
+
+// One workgroup per ping, one wavefront per 64 consecutive bins.  The bearing of each side is evaluated once per ping (dsss_geo_side)
+// and shared through LDS; the bins then cost a multiply-add and two divisions each.  Consecutive bins of a ping walk through the
+// grid, so lanes that hit the cell of their neighbour form runs: (sum, count) is reduced within a run with a segmented scan over
+// the wavefront and the last lane of the run issues ONE 64-bit atomic without return, count in the high word and sum in the low
+// one.  A wavefront adds at most 64 x 255 to a sum, and below 2^24 samples per cell (checked by mosaic_unpack_kernel) the low word
+// cannot carry into the high one.  (One atomic per pixel took 13.3 ms where this takes 6.7: DESIGN.md section 4, "Mosaic".)
+__global__ __launch_bounds__(256) void mosaic_scatter_kernel(const mosaic_job* __restrict__ jobs, int njobs, mosaic_win G,
+                                                             unsigned long long* __restrict__ acc)
+{
+    __shared__ double s_sc[4];
+    int lo = 0, hi = njobs - 1;
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (jobs[mid].blk0 <= (int)blockIdx.x) lo = mid; else hi = mid - 1; }
+    const mosaic_job J = jobs[lo];
+    const int row = (int)blockIdx.x - J.blk0, M = J.M, half = M / 2;
+    if (row >= J.N) return;                                                        // (uniform per workgroup; cannot happen with the host's blk0)
+    const double* P = J.pose + (size_t)row * 6;
+    if (threadIdx.x < 2) dsss_geo_side(P, threadIdx.x == 1, &s_sc[2 * threadIdx.x], &s_sc[2 * threadIdx.x + 1]);
+    __syncthreads();
+    const uint8_t* __restrict__ img = J.img + (size_t)row * M;
+    const uint8_t* __restrict__ mask = J.mask + (size_t)row * M;
+    const int lane = threadIdx.x & 63;
+    for (int c0 = 0; c0 < M; c0 += 256) {
+        const int col = c0 + (int)threadIdx.x;
+        int key = -1; unsigned v = 0;                                              // v: count << 16 | sum within the wavefront
+        if (col < M && (!G.use_mask || mask[col] != 0)) {
+            const int side = col >= half;
+            double x, y;
+            dsss_geo_bin(P, J.gr, M, col, s_sc[2 * side], s_sc[2 * side + 1], &x, &y);
+            const double fx = floor((x - G.x0) / G.cell), fy = floor((y - G.y0) / G.cell);
+            if (fx >= 0.0 && fx < (double)G.W && fy >= 0.0 && fy < (double)G.H) {  // on the f64 values: NaN, infinite and huge points drop out here
+                const int ix = (int)fx - G.ox, iy = (int)fy - G.oy;
+                if (ix >= 0 && ix < G.bw && iy >= 0 && iy < G.bh) { key = iy * G.bw + ix; v = (1u << 16) | img[col]; }
+            }
+        }
+        const int prev = __shfl_up(key, 1);
+        const bool head = lane == 0 || prev != key;
+        const unsigned long long hb = __ballot(head);
+        const int start = 63 - __clzll((long long)(hb & (~0ull >> (63 - lane))));   // first lane of this lane's run
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) { const unsigned t = __shfl_up(v, d); if (lane - d >= start) v += t; }
+        const bool tail = lane == 63 || ((hb >> (lane + 1)) & 1ull);
+        if (tail && key >= 0) atomicAdd(&acc[key], ((unsigned long long)(v >> 16) << 32) | (v & 0xffffu));
+    }
+}
+
+// accumulators -> the host layers' layout; flags a cell over the sample limit (also run with no outputs, as the check alone)
+__global__ __launch_bounds__(256) void mosaic_unpack_kernel(const unsigned long long* __restrict__ acc, size_t n, uint32_t* __restrict__ sum,
+                                                            uint32_t* __restrict__ cnt, uint8_t* __restrict__ img, int* __restrict__ flag)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const unsigned long long a = acc[i];
+    const uint32_t c = (uint32_t)(a >> 32), s = (uint32_t)a;
+    if (c > MOSAIC_MAX_SAMPLES) *flag = 1;
+    if (sum) sum[i] = s;
+    if (cnt) cnt[i] = c;
+    if (img) img[i] = c ? (uint8_t)((s + c / 2) / c) : (uint8_t)0;
+}
+
+// one frame's window folded into the three layers of the consistency map: one frame at a time, so plain stores
+__global__ __launch_bounds__(256) void mosaic_fold_kernel(const unsigned long long* __restrict__ win, mosaic_win G, uint32_t* __restrict__ nfr,
+                                                          uint32_t* __restrict__ s1, uint32_t* __restrict__ s2, int* __restrict__ flag)
+{
+    const size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= (size_t)G.bw * G.bh) return;
+    const unsigned long long a = win[j];
+    const uint32_t c = (uint32_t)(a >> 32), s = (uint32_t)a;
+    if (c == 0) return;
+    if (c > MOSAIC_MAX_SAMPLES) *flag = 1;
+    const uint32_t m = (s + c / 2) / c;
+    const int jy = (int)(j / G.bw), jx = (int)(j - (size_t)jy * G.bw);
+    const size_t g = (size_t)(G.oy + jy) * G.W + (G.ox + jx);
+    nfr[g] += 1; s1[g] += m; s2[g] += m * m;
+}
+
+struct carve { size_t off = 0; size_t take(size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; } };
+
+int mosaic_reserve(dsss_ctx* c, size_t bytes)
+{
+    if (c->mosaic_cap >= bytes) return DSSS_OK;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    hipFree(c->mosaic_buf); c->mosaic_buf = nullptr; c->mosaic_cap = 0;
+    HIPCHK(c, hipMalloc(&c->mosaic_buf, bytes));
+    c->mosaic_cap = bytes;
+    return DSSS_OK;
+}
+
+int mosaic_check_frames(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, bool need_img, size_t* rows)
+{
+    if (!ids || n < 1) DSSS_FAIL(c, DSSS_E_ARG, "mosaic: no frame ids");
+    if (rpy6 && !ping_off) DSSS_FAIL(c, DSSS_E_ARG, "mosaic: a trajectory needs ping_off");
+    std::vector<char> seen(c->max_frames, 0);
+    size_t total = 0;
+    for (int i = 0; i < n; ++i) {
+        const int id = ids[i];
+        if (id < 0 || id >= c->max_frames) DSSS_FAIL(c, DSSS_E_ARG, "frame id %d out of range [0,%d)", id, c->max_frames);
+        if (seen[id]) DSSS_FAIL(c, DSSS_E_ARG, "mosaic: frame %d listed twice", id);
+        seen[id] = 1;
+        if (rpy6 && ping_off[i] < 0) DSSS_FAIL(c, DSSS_E_ARG, "mosaic: ping_off[%d] = %d", i, ping_off[i]);
+        const dsss_frame& f = c->frames[id];
+        if (!f.has_geom || !f.h_geo) DSSS_FAIL(c, DSSS_E_STATE, "frame %d has no geometry", id);
+        if (need_img && (!f.has_norm || !f.lvl[0] || !f.mask)) DSSS_FAIL(c, DSSS_E_STATE, "frame %d not extracted yet", id);
+        total += (size_t)f.N;
+    }
+    if (total > 0x7fffffffull) DSSS_FAIL(c, DSSS_E_ARG, "mosaic: %zu pings in one call", total);
+    *rows = total;
+    return DSSS_OK;
+}
+
+int mosaic_check_params(dsss_ctx* c, const dsss_mosaic_params* p)
+{
+    if (!p) DSSS_FAIL(c, DSSS_E_ARG, "mosaic: no grid");
+    if (!(p->cell > 0.0) || !std::isfinite(p->cell)) DSSS_FAIL(c, DSSS_E_ARG, "mosaic: cell = %g", p->cell);
+    if (p->W < 1 || p->H < 1 || (long long)p->W * p->H > MOSAIC_MAX_CELLS) DSSS_FAIL(c, DSSS_E_ARG, "mosaic: grid %d x %d", p->W, p->H);
+    return DSSS_OK;
+}
+
+// geo extremes of one frame under the given pose rows: x = px + g c is monotone in g for a fixed bearing, so only the smallest and the
+// largest ground range of a side can be extreme (what geo_bbox_kernel evaluates).  On the host: two bearings per ping, off the hot
+// path, and the same arithmetic bit for bit.  Non-finite points compare false and are left out.
+void frame_extent(const dsss_frame& f, const double* rows, double* bb)
+{
+    const double* gr = f.h_geo + (size_t)f.N * 7;
+    const int M = f.M, half = M / 2;
+    int col_min[2], col_max[2];      // columns of the smallest / largest ground range per side
+    const double origin[6] = { 0, 0, 0, 0, 0, 0 };
+    for (int side = 0; side < 2; ++side) {
+        const int c_lo = side ? half : 0, c_hi = side ? M : half;
+        int cmin = c_lo, cmax = c_lo; double gmin = INFINITY, gmax = -INFINITY;
+        for (int col = c_lo; col < c_hi; ++col) {
+            double g, unused; dsss_geo_bin(origin, gr, M, col, 0.0, 1.0, &g, &unused);      // the bin's ground range: pose 0, bearing 0
+            if (g < gmin) { gmin = g; cmin = col; }
+            if (g > gmax) { gmax = g; cmax = col; }
+        }
+        col_min[side] = cmin; col_max[side] = cmax;
+    }
+    for (int row = 0; row < f.N; ++row) {
+        const double* P = rows + (size_t)row * 6;
+        for (int side = 0; side < 2; ++side) {
+            double s, co; dsss_geo_side(P, side == 1, &s, &co);
+            for (int e = 0; e < 2; ++e) {
+                double x, y; dsss_geo_bin(P, gr, M, e ? col_max[side] : col_min[side], s, co, &x, &y);
+                bb[0] = x < bb[0] ? x : bb[0]; bb[1] = x > bb[1] ? x : bb[1];
+                bb[2] = y < bb[2] ? y : bb[2]; bb[3] = y > bb[3] ? y : bb[3];
+            }
+        }
+    }
+}
+
+// cells [a, b] of one axis that the points lo .. hi can fall into; false when none of them lies on the grid
+bool cell_range(double lo, double hi, double origin, double cell, int n, int* a, int* b)
+{
+    const double fl = floor((lo - origin) / cell), fh = floor((hi - origin) / cell);
+    if (!(fh >= 0.0) || !(fl < (double)n)) return false;
+    *a = fl < 0.0 ? 0 : (int)fl; *b = fh >= (double)n ? n - 1 : (int)fh;
+    return true;
+}
+
+// the caller's trajectory rows of the listed frames go up packed in the order of ids (neighbouring frames that are neighbours in
+// rpy6 too share a copy); dev_rows[i] = where frame i reads its rows
+int upload_rows(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, double* d_rows, std::vector<const double*>& dev_rows)
+{
+    dev_rows.resize(n);
+    if (!rpy6) { for (int i = 0; i < n; ++i) dev_rows[i] = c->frames[ids[i]].pose6; return DSSS_OK; }
+    size_t off = 0;
+    for (int i = 0; i < n;) {
+        int j = i; size_t len = 0;
+        do { dev_rows[j] = d_rows + (off + len) * 6; len += (size_t)c->frames[ids[j]].N; ++j; }
+        while (j < n && (size_t)ping_off[j] == (size_t)ping_off[j - 1] + (size_t)c->frames[ids[j - 1]].N);
+        HIPCHK(c, hipMemcpyAsync(d_rows + off * 6, rpy6 + (size_t)ping_off[i] * 6, len * 6 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        off += len; i = j;
+    }
+    return DSSS_OK;
+}
+
+void launch_scatter(dsss_ctx* c, const mosaic_job* d_jobs, int njobs, int blocks, const mosaic_win& G, unsigned long long* acc)
+{
+    hipLaunchKernelGGL(mosaic_scatter_kernel, dim3((unsigned)blocks), dim3(256), 0, c->stream, d_jobs, njobs, G, acc);
+}
+
+} // namespace
+
+extern "C" {
+
+int dsss_mosaic_grid(const double* bbox4, double cell, dsss_mosaic_params* out)
+{
+    if (!bbox4 || !out) return DSSS_E_ARG;
+    if (!(cell > 0.0) || !std::isfinite(cell)) return DSSS_E_ARG;
+    for (int k = 0; k < 4; ++k) if (!std::isfinite(bbox4[k])) return DSSS_E_ARG;
+    if (bbox4[1] < bbox4[0] || bbox4[3] < bbox4[2]) return DSSS_E_ARG;
+    const double x0 = floor(bbox4[0] / cell) * cell, y0 = floor(bbox4[2] / cell) * cell;
+    const double w = floor((bbox4[1] - x0) / cell) + 1.0, h = floor((bbox4[3] - y0) / cell) + 1.0;
+    if (!(w >= 1.0) || !(h >= 1.0) || !(w * h <= (double)MOSAIC_MAX_CELLS)) return DSSS_E_ARG;
+    out->x0 = x0; out->y0 = y0; out->cell = cell; out->W = (int32_t)w; out->H = (int32_t)h; out->use_mask = 1; out->pad_ = 0;
+    return DSSS_OK;
+}
+
+int dsss_mosaic_bounds(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, double* bbox4)
+{
+    if (!c || !bbox4) return DSSS_E_ARG;
+    size_t rows = 0;
+    int rc = mosaic_check_frames(c, ids, n, rpy6, ping_off, false, &rows); if (rc) return rc;
+    double bb[4] = { INFINITY, -INFINITY, INFINITY, -INFINITY };
+    for (int i = 0; i < n; ++i) {
+        const dsss_frame& f = c->frames[ids[i]];
+        frame_extent(f, rpy6 ? rpy6 + (size_t)ping_off[i] * 6 : f.h_geo, bb);
+    }
+    memcpy(bbox4, bb, sizeof bb);
+    return DSSS_OK;
+}
+
+int dsss_mosaic_render(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, const dsss_mosaic_params* p,
+                       uint32_t* sum_host, uint32_t* cnt_host, uint8_t* img_host)
+{
+    if (!c) return DSSS_E_ARG;
+    size_t rows = 0;
+    int rc = mosaic_check_frames(c, ids, n, rpy6, ping_off, true, &rows); if (rc) return rc;
+    rc = mosaic_check_params(c, p); if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t cells = (size_t)p->W * p->H;
+    carve L;
+    const size_t o_acc = L.take(cells * 8), o_sum = L.take(sum_host ? cells * 4 : 0), o_cnt = L.take(cnt_host ? cells * 4 : 0),
+                 o_img = L.take(img_host ? cells : 0), o_jobs = L.take((size_t)n * sizeof(mosaic_job)), o_rows = L.take(rpy6 ? rows * 6 * sizeof(double) : 0),
+                 o_flag = L.take(sizeof(int));
+    rc = mosaic_reserve(c, L.off); if (rc) return rc;
+    char* B = static_cast<char*>(c->mosaic_buf);
+    unsigned long long* acc = reinterpret_cast<unsigned long long*>(B + o_acc);
+    uint32_t* d_sum = sum_host ? reinterpret_cast<uint32_t*>(B + o_sum) : nullptr;
+    uint32_t* d_cnt = cnt_host ? reinterpret_cast<uint32_t*>(B + o_cnt) : nullptr;
+    uint8_t* d_img = img_host ? reinterpret_cast<uint8_t*>(B + o_img) : nullptr;
+    mosaic_job* d_jobs = reinterpret_cast<mosaic_job*>(B + o_jobs);
+    int* d_flag = reinterpret_cast<int*>(B + o_flag);
+    std::vector<const double*> dev_rows;
+    rc = upload_rows(c, ids, n, rpy6, ping_off, reinterpret_cast<double*>(B + o_rows), dev_rows); if (rc) return rc;
+    HIPCHK(c, hipMemsetAsync(acc, 0, cells * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_flag, 0, sizeof(int), c->stream));
+    const mosaic_win G{ p->x0, p->y0, p->cell, p->W, p->H, 0, 0, p->W, p->H, p->use_mask != 0 };
+    const unsigned ublocks = (unsigned)((cells + 255) / 256);
+    // launches of at most 2^31 samples, the sample limit checked between them: a cell's count then stays far below 2^32 until the
+    // check sees it, so the packed accumulator cannot wrap unnoticed whatever the number of frames
+    std::vector<mosaic_job> jobs(n);
+    int j0 = 0;
+    while (j0 < n) {
+        int j1 = j0, blocks = 0; size_t samples = 0;
+        while (j1 < n) {
+            const dsss_frame& f = c->frames[ids[j1]];
+            const size_t s = (size_t)f.N * f.M;
+            if (j1 > j0 && samples + s > (1ull << 31)) break;
+            jobs[j1] = mosaic_job{ dev_rows[j1], f.gr, f.lvl[0], f.mask, f.N, f.M, blocks, 0 };
+            blocks += f.N; samples += s; ++j1;
+        }
+        HIPCHK(c, hipMemcpyAsync(d_jobs + j0, jobs.data() + j0, (size_t)(j1 - j0) * sizeof(mosaic_job), hipMemcpyHostToDevice, c->stream));
+        launch_scatter(c, d_jobs + j0, j1 - j0, blocks, G, acc);
+        HIPCHK(c, hipGetLastError());
+        if (j1 < n) { hipLaunchKernelGGL(mosaic_unpack_kernel, dim3(ublocks), dim3(256), 0, c->stream, acc, cells, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint8_t*)nullptr, d_flag); HIPCHK(c, hipGetLastError()); }
+        j0 = j1;
+    }
+    hipLaunchKernelGGL(mosaic_unpack_kernel, dim3(ublocks), dim3(256), 0, c->stream, acc, cells, d_sum, d_cnt, d_img, d_flag);
+    HIPCHK(c, hipGetLastError());
+    int flag = 0;
+    HIPCHK(c, hipMemcpyAsync(&flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (flag) DSSS_FAIL(c, DSSS_E_CAPACITY, "mosaic: a cell received more than 2^24 samples (cell %g too coarse for these frames)", p->cell);
+    if (sum_host) HIPCHK(c, hipMemcpyAsync(sum_host, d_sum, cells * 4, hipMemcpyDeviceToHost, c->stream));
+    if (cnt_host) HIPCHK(c, hipMemcpyAsync(cnt_host, d_cnt, cells * 4, hipMemcpyDeviceToHost, c->stream));
+    if (img_host) HIPCHK(c, hipMemcpyAsync(img_host, d_img, cells, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return DSSS_OK;
+}
+
+int dsss_mosaic_consistency(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, const dsss_mosaic_params* p,
+                            uint32_t* nfr_host, uint32_t* s1_host, uint32_t* s2_host, double* score_host)
+{
+    if (!c) return DSSS_E_ARG;
+    size_t rows = 0;
+    int rc = mosaic_check_frames(c, ids, n, rpy6, ping_off, true, &rows); if (rc) return rc;
+    rc = mosaic_check_params(c, p); if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t cells = (size_t)p->W * p->H;
+    // every frame is rendered alone into a window of the grid: the cells its geo extremes can reach
+    std::vector<mosaic_win> wins(n); std::vector<char> on_grid(n, 0);
+    size_t win_cells = 1;
+    for (int i = 0; i < n; ++i) {
+        const dsss_frame& f = c->frames[ids[i]];
+        double bb[4] = { INFINITY, -INFINITY, INFINITY, -INFINITY };
+        frame_extent(f, rpy6 ? rpy6 + (size_t)ping_off[i] * 6 : f.h_geo, bb);
+        int ax, bx, ay, by;
+        if (!cell_range(bb[0], bb[1], p->x0, p->cell, p->W, &ax, &bx) || !cell_range(bb[2], bb[3], p->y0, p->cell, p->H, &ay, &by)) continue;
+        on_grid[i] = 1;
+        wins[i] = mosaic_win{ p->x0, p->y0, p->cell, p->W, p->H, ax, ay, bx - ax + 1, by - ay + 1, p->use_mask != 0 };
+        win_cells = std::max(win_cells, (size_t)wins[i].bw * wins[i].bh);
+    }
+    carve L;
+    const size_t o_lay = L.take(cells * 12), o_win = L.take(win_cells * 8), o_jobs = L.take((size_t)n * sizeof(mosaic_job)),
+                 o_rows = L.take(rpy6 ? rows * 6 * sizeof(double) : 0), o_flag = L.take(sizeof(int));
+    rc = mosaic_reserve(c, L.off); if (rc) return rc;
+    char* B = static_cast<char*>(c->mosaic_buf);
+    uint32_t* d_nfr = reinterpret_cast<uint32_t*>(B + o_lay); uint32_t* d_s1 = d_nfr + cells; uint32_t* d_s2 = d_s1 + cells;
+    unsigned long long* d_win = reinterpret_cast<unsigned long long*>(B + o_win);
+    mosaic_job* d_jobs = reinterpret_cast<mosaic_job*>(B + o_jobs);
+    int* d_flag = reinterpret_cast<int*>(B + o_flag);
+    std::vector<const double*> dev_rows;
+    rc = upload_rows(c, ids, n, rpy6, ping_off, reinterpret_cast<double*>(B + o_rows), dev_rows); if (rc) return rc;
+    std::vector<mosaic_job> jobs(n);
+    for (int i = 0; i < n; ++i) { const dsss_frame& f = c->frames[ids[i]]; jobs[i] = mosaic_job{ dev_rows[i], f.gr, f.lvl[0], f.mask, f.N, f.M, 0, 0 }; }
+    HIPCHK(c, hipMemcpyAsync(d_jobs, jobs.data(), (size_t)n * sizeof(mosaic_job), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_nfr, 0, cells * 12, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_flag, 0, sizeof(int), c->stream));
+    for (int i = 0; i < n; ++i) {
+        if (!on_grid[i]) continue;
+        const size_t wc = (size_t)wins[i].bw * wins[i].bh;
+        HIPCHK(c, hipMemsetAsync(d_win, 0, wc * 8, c->stream));
+        launch_scatter(c, d_jobs + i, 1, jobs[i].N, wins[i], d_win);
+        hipLaunchKernelGGL(mosaic_fold_kernel, dim3((unsigned)((wc + 255) / 256)), dim3(256), 0, c->stream, d_win, wins[i], d_nfr, d_s1, d_s2, d_flag);
+        HIPCHK(c, hipGetLastError());
+    }
+    int flag = 0;
+    HIPCHK(c, hipMemcpyAsync(&flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (flag) DSSS_FAIL(c, DSSS_E_CAPACITY, "mosaic: a cell received more than 2^24 samples of one frame (cell %g too coarse)", p->cell);
+    // the score needs the three layers whether the caller wants them or not
+    std::vector<uint32_t> own[3];
+    uint32_t* host[3] = { nfr_host, s1_host, s2_host };
+    if (!score_host && !nfr_host && !s1_host && !s2_host) return DSSS_OK;
+    for (int k = 0; k < 3; ++k) {
+        if (!host[k]) { if (!score_host) continue; own[k].resize(cells); host[k] = own[k].data(); }
+        HIPCHK(c, hipMemcpyAsync(host[k], d_nfr + (size_t)k * cells, cells * 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (score_host) {
+        double num = 0.0, den = 0.0;
+        for (size_t g = 0; g < cells; ++g) {
+            const uint32_t k = host[0][g];
+            if (k < 2) continue;
+            const double a = (double)host[1][g];
+            num += (double)host[2][g] - a * a / (double)k;
+            den += (double)(k - 1);
+        }
+        *score_host = (den > 0.0 && num > 0.0) ? sqrt(num / den) : 0.0;
+    }
+    return DSSS_OK;
+}
+
+} // extern "C"

@@ -253,6 +253,36 @@ int dsss_host_pg_solve_local(int ns, const int32_t* edge_a, const int32_t* edge_
 int dsss_host_pg_solve_parts(int ns, const int32_t* edge_a, const int32_t* edge_b, int nedges, const double* cx, const double* cy,
                              int K, const double* aval36, const double* rhs6, double* x6_host, int64_t* stats8);
 
+/* ------------------------------------------------------------------ mosaic (new: the reference ends at the trajectory file,
+ * optimizer.cpp:1164-1214, and has no mosaic -- there is no reference line to cite for anything in this section)
+ * The frames' normalised waterfalls (Frame::norm_img) binned into one georeferenced grid under a trajectory, and the disagreement of
+ * overlapping frames about a cell as a trajectory-quality measure that needs neither an oracle run nor annotations.
+ * Grid: cell (ix, iy) covers [x0 + ix cell, x0 + (ix+1) cell) x [y0 + iy cell, y0 + (iy+1) cell), layers are H x W row-major (index
+ * iy W + ix), W H <= 2^28.  A pixel (row, col) of a frame lies at dsss_frame_get_geo's point for the given pose rows and falls into
+ * ix = floor((x - x0) / cell), iy = floor((y - y0) / cell), evaluated and range-tested in f64: points outside the grid and non-finite
+ * ones are dropped.  use_mask != 0 drops the pixels the filter mask rejects (flt_mask == 0, where DetectFeature drops keypoints).
+ * Trajectory: rpy6 = HOST rows "r p y x y z" as dsss_posegraph_solve writes to rpy6_host, frame ids[i] reads the N_i rows from row
+ * ping_off[i]; rpy6 == NULL: the pose6 the frames were set with (ping_off may then be NULL).  Altitudes are not used.
+ * Every accumulator is an integer: results do not depend on the order of ids and are identical from call to call.  Single rank: a
+ * rank renders the frames whose images it holds (after dsss_extract*; DSSS_E_STATE otherwise).  ids must be distinct.                */
+typedef struct { double x0, y0, cell; int32_t W, H; int32_t use_mask; int32_t pad_; } dsss_mosaic_params;
+/* the grid that covers bbox4 = xmin,xmax,ymin,ymax with cells of edge `cell`: x0 = floor(xmin / cell) cell, W = floor((xmax - x0) / cell) + 1,
+ * the same in y, use_mask = 1.  Pure host arithmetic, no context.  DSSS_E_ARG: cell <= 0 or not finite, a box that is not finite, W H > 2^28 */
+int dsss_mosaic_grid(const double* bbox4, double cell, dsss_mosaic_params* out);
+/* union of the frames' geo extremes (the minMaxLoc pairs of dsss_frame_bbox) under the given trajectory: xmin,xmax,ymin,ymax */
+int dsss_mosaic_bounds(dsss_ctx*, const int* ids, int n, const double* rpy6, const int* ping_off, double* bbox4_host);
+/* sum: sum of the normalised u8 values that fell into the cell, cnt: their number (uint32, H x W); img = cnt ? (sum + cnt / 2) / cnt : 0
+ * (uint8, H x W).  Any output may be NULL (all NULL: the mosaic is rendered on the device and nothing is downloaded).
+ * DSSS_E_CAPACITY when a cell received more than 2^24 samples (below that the uint32 sum cannot wrap).                              */
+int dsss_mosaic_render(dsss_ctx*, const int* ids, int n, const double* rpy6, const int* ping_off,
+                       const dsss_mosaic_params*, uint32_t* sum_host, uint32_t* cnt_host, uint8_t* img_host);
+/* every frame rendered alone, m_f = (sum_f + cnt_f / 2) / cnt_f where cnt_f > 0; per cell nfr = frames with cnt_f > 0, s1 = sum of m_f,
+ * s2 = sum of m_f^2 (uint32, H x W; any may be NULL).  score = sqrt(sum_{nfr >= 2} (s2 - s1^2 / nfr) / sum_{nfr >= 2} (nfr - 1)): the pooled
+ * standard deviation, in grey levels, of what overlapping frames say about a cell (f64, cells in index order; 0 without overlap).    */
+int dsss_mosaic_consistency(dsss_ctx*, const int* ids, int n, const double* rpy6, const int* ping_off,
+                            const dsss_mosaic_params*, uint32_t* nfr_host, uint32_t* s1_host, uint32_t* s2_host,
+                            double* score_host);
+
 /* ------------------------------------------------------------------ instrumentation
  * accumulated GPU time (ms, HIP events on the context stream) and launch count per kernel family        */
 #define DSSS_K_ROW_REDUCE   0   /* row_reduce_kernel: one f64 read of the waterfall */
