@@ -50,6 +50,18 @@ LC_DTYPE = np.dtype([("rel", "<f8", (12,)), ("var", "<f8", (6,)), ("score", "<f8
                      ("_pad", "<i4"), ("err0", "<f8"), ("err1", "<f8")])
 
 
+class LMTrace(C.Structure):
+    _fields_ = [("iters", C.c_int), ("chol_fail", C.c_int), ("rejected", C.c_int), ("lammax_exit", C.c_int),
+                ("stop_nosuccess", C.c_int), ("iter_cap", C.c_int), ("lin_neg", C.c_int), ("marg_fail", C.c_int),
+                ("margin", C.c_double)]
+
+
+LMTRACE_DTYPE = np.dtype([("iters", "<i4"), ("chol_fail", "<i4"), ("rejected", "<i4"), ("lammax_exit", "<i4"),
+                          ("stop_nosuccess", "<i4"), ("iter_cap", "<i4"), ("lin_neg", "<i4"), ("marg_fail", "<i4"),
+                          ("margin", "<f8")])
+TRACE_COUNTERS = ("iters", "chol_fail", "rejected", "lammax_exit", "stop_nosuccess", "iter_cap", "lin_neg", "marg_fail")
+
+
 class LCEdge(C.Structure):
     _fields_ = [("a", C.c_int), ("b", C.c_int), ("rel", C.c_double * 12), ("var", C.c_double * 6)]
 
@@ -301,6 +313,59 @@ def lc_solve(kp7, pose_s, alt_s, gr_s, Ms, pose_t, alt_t, gr_t, Mt):
     lib().orc_lc_solve(dp(kp7), n, dp(pose_s), dp(alt_s), dp(gr_s), pose_s.shape[0], Ms,
                        dp(pose_t), dp(alt_t), dp(gr_t), pose_t.shape[0], Mt, out.ctypes.data_as(C.POINTER(LC)))
     return out[:n].copy()
+
+
+def lc_solve_trace(kp7, pose_s, alt_s, gr_s, Ms, pose_t, alt_t, gr_t, Mt, want_J=False):
+    """orc_lc_solve_trace: (lcs, trace[LMTRACE_DTYPE]) or, with want_J, (lcs, trace, J n x 16 x 15, r n x 16) at the final values"""
+    kp7 = np.ascontiguousarray(kp7, np.float64).reshape(-1, 7)
+    n = len(kp7)
+    out = np.zeros(max(n, 1), LC_DTYPE); tr = np.zeros(max(n, 1), LMTRACE_DTYPE)
+    assert LC_DTYPE.itemsize == C.sizeof(LC) and LMTRACE_DTYPE.itemsize == C.sizeof(LMTrace)
+    J = np.zeros((max(n, 1), 16, 15)) if want_J else None; r = np.zeros((max(n, 1), 16)) if want_J else None
+    pose_s = np.ascontiguousarray(pose_s, np.float64); pose_t = np.ascontiguousarray(pose_t, np.float64)
+    alt_s = np.ascontiguousarray(alt_s, np.float64); gr_s = np.ascontiguousarray(gr_s, np.float64)
+    alt_t = np.ascontiguousarray(alt_t, np.float64); gr_t = np.ascontiguousarray(gr_t, np.float64)
+    lib().orc_lc_solve_trace(dp(kp7), n, dp(pose_s), dp(alt_s), dp(gr_s), pose_s.shape[0], Ms,
+                             dp(pose_t), dp(alt_t), dp(gr_t), pose_t.shape[0], Mt, out.ctypes.data_as(C.POINTER(LC)),
+                             tr.ctypes.data_as(C.POINTER(LMTrace)), dp(J) if want_J else None, dp(r) if want_J else None)
+    if want_J:
+        return out[:n].copy(), tr[:n].copy(), J[:n].copy(), r[:n].copy()
+    return out[:n].copy(), tr[:n].copy()
+
+
+def triangulate_trace(kp7, pose_s, alt_s, gr_s, Ms, pose_t, alt_t, gr_t, Mt):
+    """orc_triangulate_trace: (n x 7 as triangulate(), trace[LMTRACE_DTYPE])"""
+    kp7 = np.ascontiguousarray(kp7, np.float64).reshape(-1, 7)
+    n = len(kp7)
+    out = np.zeros((max(n, 1), 7)); tr = np.zeros(max(n, 1), LMTRACE_DTYPE)
+    pose_s = np.ascontiguousarray(pose_s, np.float64); pose_t = np.ascontiguousarray(pose_t, np.float64)
+    alt_s = np.ascontiguousarray(alt_s, np.float64); gr_s = np.ascontiguousarray(gr_s, np.float64)
+    alt_t = np.ascontiguousarray(alt_t, np.float64); gr_t = np.ascontiguousarray(gr_t, np.float64)
+    lib().orc_triangulate_trace(dp(kp7), n, dp(pose_s), dp(alt_s), dp(gr_s), pose_s.shape[0], Ms,
+                                dp(pose_t), dp(alt_t), dp(gr_t), pose_t.shape[0], Mt, dp(out), tr.ctypes.data_as(C.POINTER(LMTrace)))
+    return out[:n].copy(), tr[:n].copy()
+
+
+def triangulate_one_trace(kp7, Tp_s, Tp_t, lm_ini):
+    """orc_triangulate_one_trace with identity sensor offsets: (point, trace record)"""
+    Ts = Pose(); Ts.R[0] = Ts.R[4] = Ts.R[8] = 1.0
+    Ps = Pose(); Pt = Pose()
+    for k in range(9):
+        Ps.R[k] = float(Tp_s[k]); Pt.R[k] = float(Tp_t[k])
+    for k in range(3):
+        Ps.t[k] = float(Tp_s[9 + k]); Pt.t[k] = float(Tp_t[9 + k])
+    kp7 = np.ascontiguousarray(kp7, np.float64); ini = np.ascontiguousarray(lm_ini, np.float64); out = np.zeros(3)
+    tr = np.zeros(1, LMTRACE_DTYPE)
+    lib().orc_triangulate_one_trace(dp(kp7), C.byref(Ts), C.byref(Ts), C.byref(Ps), C.byref(Pt), dp(ini), dp(out),
+                                    tr.ctypes.data_as(C.POINTER(LMTrace)))
+    return out, tr[0].copy()
+
+
+def pose12(p6):
+    """Pose3(Rot3::Rodrigues(r, p, y), Point3(x, y, z)) as 12 doubles (R row-major, t)"""
+    T = Pose()
+    lib().orc_pose_from_rodrigues(dp(np.ascontiguousarray(p6, np.float64)), C.byref(T))
+    return np.concatenate([np.array(T.R), np.array(T.t)])
 
 
 def triangulate(kp7, pose_s, alt_s, gr_s, Ms, pose_t, alt_t, gr_t, Mt):

@@ -188,12 +188,37 @@ typedef struct { double rel[12]; double var[6]; double score; int iters; double 
 int orc_lc_solve(const double* kp7, int n, const double* pose6_s, const double* alt_s, const double* gr_s, int Ns, int Ms,
                  const double* pose6_t, const double* alt_t, const double* gr_t, int Nt, int Mt, orc_lc* out);
 
+/* The path one LM run took (mini-LM of orc_lc_solve, 3-DoF LM of orc_triangulate_one): events counted over the run, and the smallest
+ * relative margin |a - b| / max(|a|, |b|) by which any of its decisions fell (fid against minFid, |costChange| against relTol * err,
+ * linChange against eps * oldLin, and the relative and absolute terms of the outer stopping rule; err <= 0 has no relative margin, comparisons with a non-finite side are left out).
+ * A run whose margin is near 1e-16 is decided by the last ulp of libm. */
+typedef struct {
+    int iters;            /* accepted steps */
+    int chol_fail;        /* damped system not positive definite (or not finite) */
+    int rejected;         /* trial refused, lambda raised */
+    int lammax_exit;      /* lambda reached lamMax: the run gives up */
+    int stop_nosuccess;   /* trial refused and |costChange| < relTol * err: inner loop left without a step */
+    int iter_cap;         /* maxIterations reached */
+    int lin_neg;          /* linChange < 0 */
+    int marg_fail;        /* Cholesky of the marginal's information matrix failed: var = NaN (orc_lc_solve only) */
+    double margin;
+} orc_lm_trace;
+/* orc_lc_solve with the trace of every row (n entries) and, optionally (NULL to skip), the whitened Jacobian (n x 16 x 15, row-major) and
+ * residual (n x 16) at the final values.  Same loop, same outputs as orc_lc_solve. */
+int orc_lc_solve_trace(const double* kp7, int n, const double* pose6_s, const double* alt_s, const double* gr_s, int Ns, int Ms,
+                       const double* pose6_t, const double* alt_t, const double* gr_t, int Nt, int Mt, orc_lc* out,
+                       orc_lm_trace* trace, double* J_out, double* r_out);
+
 /* ---------------------------------------------------------------- pose graph (optimizer.cpp:101-279, batch LM replaces iSAM2) */
 /* LMTriaFactor + TriangulateOneLandmark (LMtriangulatefactor.cpp:10-27, optimizer.cpp:984-1021, call site :907-921) */
 int orc_triangulate_one(const double kp7[7], const orc_pose* Ts_s, const orc_pose* Ts_t, const orc_pose* Tp_s, const orc_pose* Tp_t,
                         const double lm_ini[3], double out[3]);
 int orc_triangulate(const double* kp7, int n, const double* pose6_s, const double* alt_s, const double* gr_s, int Ns, int Ms,
                     const double* pose6_t, const double* alt_t, const double* gr_t, int Nt, int Mt, double* out7);
+int orc_triangulate_one_trace(const double kp7[7], const orc_pose* Ts_s, const orc_pose* Ts_t, const orc_pose* Tp_s, const orc_pose* Tp_t,
+                              const double lm_ini[3], double out[3], orc_lm_trace* trace);
+int orc_triangulate_trace(const double* kp7, int n, const double* pose6_s, const double* alt_s, const double* gr_s, int Ns, int Ms,
+                          const double* pose6_t, const double* alt_t, const double* gr_t, int Nt, int Mt, double* out7, orc_lm_trace* trace);
 typedef struct { int a, b; double rel[12]; double var[6]; } orc_lc_edge; /* BetweenFactor(X_a, X_b, rel, Variances(var)) */
 typedef struct {
     int max_iters; double rel_tol, abs_tol; double lambda0, lambda_factor, lambda_max; double min_fidelity;

@@ -128,8 +128,50 @@ static void mini_retract(const mini_vals* v, const double* d, mini_vals* o)
     orc_pose_retract(&v->X2, d + 9, &o->X2);
 }
 
+/* ---- the trace of a path (orc_lm_trace, orc.h): counters of every exit the LM loops below can take and the smallest relative
+ * margin of their decisions.  Every line of it sits behind `if (tr)` and touches no value of the solve: the plain entry points
+ * pass NULL and run the same loop. */
+static void tr_margin(orc_lm_trace* tr, double a, double b)
+{
+    if (!isfinite(a) || !isfinite(b)) return;          /* a comparison with inf / NaN is not decided by the last ulp */
+    const double s = fabs(a) > fabs(b) ? fabs(a) : fabs(b);
+    const double mg = s > 0 ? fabs(a - b) / s : 0.0;
+    if (mg < tr->margin) tr->margin = mg;
+}
+static void tr_init(orc_lm_trace* tr) { if (tr) { memset(tr, 0, sizeof *tr); tr->margin = INFINITY; } }
+/* one inner decision of either LM: ok = the damped system factored */
+static void tr_trial(orc_lm_trace* tr, int ok, double oldLin, double linChange, double err, double newErr, int success, int stop,
+                     double lambda_next, double lamMax, double minFid, double relTol)
+{
+    if (!tr) return;
+    if (!ok) ++tr->chol_fail;
+    else {
+        tr_margin(tr, linChange, 2.220446049250313e-16 * oldLin);
+        if (linChange < 0) ++tr->lin_neg;
+        else {
+            const double costChange = err - newErr;
+            if (linChange > 2.220446049250313e-16 * oldLin) tr_margin(tr, costChange / linChange, minFid);
+            tr_margin(tr, fabs(costChange), relTol * err);
+        }
+    }
+    if (success) return;
+    if (!stop) { ++tr->rejected; if (lambda_next >= lamMax) ++tr->lammax_exit; }
+    else ++tr->stop_nosuccess;
+}
+/* the outer stopping rule, evaluated after an inner loop ended */
+static void tr_outer(orc_lm_trace* tr, int iters, int maxIter, double cur, double err, double relTol, double absTol)
+{
+    if (!tr) return;
+    tr->iters = iters;
+    if (iters >= maxIter) { ++tr->iter_cap; return; }
+    /* (err <= 0 has no relative margin: it is 1 unless err is exactly 0.  cur = 0 or a non-finite side: tr_margin leaves the term out,
+     * no last ulp decides such a comparison) */
+    tr_margin(tr, (cur - err) / cur, relTol);
+    tr_margin(tr, cur - err, absTol);
+}
+
 /* GTSAM LevenbergMarquardtOptimizer::optimize with default params */
-static int mini_lm(const mini_t* m, mini_vals* v, double* err0, double* err1)
+static int mini_lm(const mini_t* m, mini_vals* v, double* err0, double* err1, orc_lm_trace* tr)
 {
     const double relTol = 1e-5, absTol = 1e-5, lamMax = 1e5, minFid = 1e-3;
     const int maxIter = 100;
@@ -137,6 +179,7 @@ static int mini_lm(const mini_t* m, mini_vals* v, double* err0, double* err1)
     int iters = 0;
     double err = mini_err(m, v);
     *err0 = err;
+    tr_init(tr);
     if (err <= 0) { *err1 = err; return 0; }
     double cur;
     do {
@@ -162,7 +205,7 @@ static int mini_lm(const mini_t* m, mini_vals* v, double* err0, double* err1)
             for (int a = 0; a < MDIM; ++a) { A[a * MDIM + a] += lambda; d[a] = -g[a]; }
             int ok = chol(A, MDIM) == 0;
             int success = 0, stop = 0;
-            double newErr = 0; mini_vals nv;
+            double newErr = 0, linChange = 0; mini_vals nv;
             if (ok) {
                 chol_solve(A, MDIM, d);
                 double newLin = 0;
@@ -172,7 +215,7 @@ static int mini_lm(const mini_t* m, mini_vals* v, double* err0, double* err1)
                     newLin += s * s;
                 }
                 newLin *= 0.5;
-                double linChange = oldLin - newLin;
+                linChange = oldLin - newLin;
                 if (linChange >= 0) {
                     mini_retract(v, d, &nv);
                     newErr = mini_err(m, &nv);
@@ -184,18 +227,21 @@ static int mini_lm(const mini_t* m, mini_vals* v, double* err0, double* err1)
                     if (fabs(costChange) < relTol * err) stop = 1;
                 }
             }
+            tr_trial(tr, ok, oldLin, linChange, err, newErr, success, stop, lambda * 10, lamMax, minFid, relTol);
             if (success) { *v = nv; err = newErr; lambda /= 10; ++iters; break; }
             else if (!stop) { lambda *= 10; if (lambda >= lamMax) break; }
             else break;
         }
+        tr_outer(tr, iters, maxIter, cur, err, relTol, absTol);
     } while (iters < maxIter && !((err <= 0) || ((cur - err) / cur <= relTol) || ((cur - err) <= absTol)) && isfinite(cur));
     *err1 = err;
     return iters;
 }
 
-/* LoopClosingTFs (optimizer.cpp:641-982), graph_option = 0 */
-int orc_lc_solve(const double* kp7, int n, const double* pose6_s, const double* alt_s, const double* gr_s, int Ns, int Ms,
-                 const double* pose6_t, const double* alt_t, const double* gr_t, int Nt, int Mt, orc_lc* out)
+/* LoopClosingTFs (optimizer.cpp:641-982), graph_option = 0.  trace / J_out (n x 16 x 15) / r_out (n x 16): optional, see orc_lc_solve_trace */
+static int lc_solve_impl(const double* kp7, int n, const double* pose6_s, const double* alt_s, const double* gr_s, int Ns, int Ms,
+                         const double* pose6_t, const double* alt_t, const double* gr_t, int Nt, int Mt, orc_lc* out,
+                         orc_lm_trace* trace, double* J_out, double* r_out)
 {
     const double PI = ORC_PI_REF;
     const double sigma_r = 0.1, alpha_bw = 0.1 * PI / 180;
@@ -234,7 +280,8 @@ int orc_lc_solve(const double* kp7, int n, const double* pose6_s, const double* 
         v.L[2] = ((pose6_s[(size_t)id_s * 6 + 5] - alt_s[id_s]) + (pose6_t[(size_t)id_t * 6 + 5] - alt_t[id_t])) / 2;
         v.X1 = Tp_s; v.X2 = Tp_t;
         orc_lc* o = &out[i];
-        o->iters = mini_lm(&m, &v, &o->err0, &o->err1);
+        orc_lm_trace* tr = trace ? &trace[i] : NULL;
+        o->iters = mini_lm(&m, &v, &o->err0, &o->err1, tr);
         /* eval_1 (:853-896) */
         orc_pose cti, new_pose;
         orc_pose_inverse(&cps_t, &cti);
@@ -273,7 +320,9 @@ int orc_lc_solve(const double* kp7, int n, const double* pose6_s, const double* 
                 chol_solve(H, MDIM, e);
                 o->var[c] = e[9 + c];
             }
-        } else for (int c = 0; c < 6; ++c) o->var[c] = NAN;
+        } else { for (int c = 0; c < 6; ++c) o->var[c] = NAN; if (tr) ++tr->marg_fail; }
+        if (J_out) memcpy(J_out + (size_t)i * MROWS * MDIM, J, sizeof J);      /* (chol ran on H: J and r are still the final linearisation) */
+        if (r_out) memcpy(r_out + (size_t)i * MROWS, r, sizeof r);
         /* (Tp_s * cps_s^-1).between(X2 * cps_t^-1) (:958) */
         orc_pose csi, src, rel;
         orc_pose_inverse(&cps_s, &csi);
@@ -283,6 +332,17 @@ int orc_lc_solve(const double* kp7, int n, const double* pose6_s, const double* 
         memcpy(o->rel + 9, rel.t, sizeof(double) * 3);
     }
     return n;
+}
+int orc_lc_solve(const double* kp7, int n, const double* pose6_s, const double* alt_s, const double* gr_s, int Ns, int Ms,
+                 const double* pose6_t, const double* alt_t, const double* gr_t, int Nt, int Mt, orc_lc* out)
+{
+    return lc_solve_impl(kp7, n, pose6_s, alt_s, gr_s, Ns, Ms, pose6_t, alt_t, gr_t, Nt, Mt, out, NULL, NULL, NULL);
+}
+int orc_lc_solve_trace(const double* kp7, int n, const double* pose6_s, const double* alt_s, const double* gr_s, int Ns, int Ms,
+                       const double* pose6_t, const double* alt_t, const double* gr_t, int Nt, int Mt, orc_lc* out,
+                       orc_lm_trace* trace, double* J_out, double* r_out)
+{
+    return lc_solve_impl(kp7, n, pose6_s, alt_s, gr_s, Ns, Ms, pose6_t, alt_t, gr_t, Nt, Mt, out, trace, J_out, r_out);
 }
 
 /* ---- LMTriaFactor (LMtriangulatefactor.cpp:10-27) + Optimizer::TriangulateOneLandmark (optimizer.cpp:984-1021):
@@ -307,8 +367,8 @@ static double tri_err(const tri_t* m, const double* p)
     double s = 0; for (int i = 0; i < TROWS; ++i) s += r[i] * r[i];
     return 0.5 * s;
 }
-int orc_triangulate_one(const double kp7[7], const orc_pose* Ts_s, const orc_pose* Ts_t, const orc_pose* Tp_s, const orc_pose* Tp_t,
-                        const double lm_ini[3], double out[3])
+static int tri_one_impl(const double kp7[7], const orc_pose* Ts_s, const orc_pose* Ts_t, const orc_pose* Tp_s, const orc_pose* Tp_t,
+                        const double lm_ini[3], double out[3], orc_lm_trace* tr)
 {
     const double PI = ORC_PI_REF, sigma_r = 0.1, alpha_bw = 0.1 * PI / 180;
     tri_t m;
@@ -323,6 +383,7 @@ int orc_triangulate_one(const double kp7[7], const orc_pose* Ts_s, const orc_pos
     const double relTol = 1e-5, absTol = 1e-5, lamMax = 1e5, minFid = 1e-3;
     double lambda = 1e-5, err = tri_err(&m, p), cur;
     int iters = 0;
+    tr_init(tr);
     if (err > 0) do {
         cur = err;
         double r[TROWS], J[TROWS * 3], H[9], g[3];
@@ -339,13 +400,13 @@ int orc_triangulate_one(const double kp7[7], const orc_pose* Ts_s, const orc_pos
             memcpy(A, H, sizeof A);
             for (int a = 0; a < 3; ++a) { A[a * 3 + a] += lambda; d[a] = -g[a]; }
             int ok = chol(A, 3) == 0, success = 0, stop = 0;
-            double newErr = 0, np_[3];
+            double newErr = 0, linChange = 0, np_[3];
             if (ok) {
                 chol_solve(A, 3, d);
                 double newLin = 0;
                 for (int k = 0; k < TROWS; ++k) { double s = r[k]; for (int a = 0; a < 3; ++a) s += J[k * 3 + a] * d[a]; newLin += s * s; }
                 newLin *= 0.5;
-                const double linChange = oldLin - newLin;
+                linChange = oldLin - newLin;
                 if (linChange >= 0) {
                     for (int a = 0; a < 3; ++a) np_[a] = p[a] + d[a];
                     newErr = tri_err(&m, np_);
@@ -354,19 +415,31 @@ int orc_triangulate_one(const double kp7[7], const orc_pose* Ts_s, const orc_pos
                     if (fabs(costChange) < relTol * err) stop = 1;
                 }
             }
+            tr_trial(tr, ok, oldLin, linChange, err, newErr, success, stop, lambda * 10, lamMax, minFid, relTol);
             if (success) { for (int a = 0; a < 3; ++a) p[a] = np_[a]; err = newErr; lambda /= 10; ++iters; break; }
             else if (!stop) { lambda *= 10; if (lambda >= lamMax) break; }
             else break;
         }
+        tr_outer(tr, iters, 100, cur, err, relTol, absTol);
     } while (iters < 100 && !((err <= 0) || ((cur - err) / cur <= relTol) || ((cur - err) <= absTol)) && isfinite(cur));
     for (int a = 0; a < 3; ++a) out[a] = p[a];
     return iters;
 }
+int orc_triangulate_one(const double kp7[7], const orc_pose* Ts_s, const orc_pose* Ts_t, const orc_pose* Tp_s, const orc_pose* Tp_t,
+                        const double lm_ini[3], double out[3])
+{
+    return tri_one_impl(kp7, Ts_s, Ts_t, Tp_s, Tp_t, lm_ini, out, NULL);
+}
+int orc_triangulate_one_trace(const double kp7[7], const orc_pose* Ts_s, const orc_pose* Ts_t, const orc_pose* Tp_s, const orc_pose* Tp_t,
+                              const double lm_ini[3], double out[3], orc_lm_trace* trace)
+{
+    return tri_one_impl(kp7, Ts_s, Ts_t, Tp_s, Tp_t, lm_ini, out, trace);
+}
 
 /* the call site in LoopClosingTFs (optimizer.cpp:907-921, eval_2): landmark triangulated from the (yaw-compensated,
  * sticky) DR poses of both pings, initialised as in :789-795; out7 = [x y z | |range_s err| |plane_s| |range_t err| |plane_t|] */
-int orc_triangulate(const double* kp7, int n, const double* pose6_s, const double* alt_s, const double* gr_s, int Ns, int Ms,
-                    const double* pose6_t, const double* alt_t, const double* gr_t, int Nt, int Mt, double* out7)
+static int triangulate_impl(const double* kp7, int n, const double* pose6_s, const double* alt_s, const double* gr_s, int Ns, int Ms,
+                            const double* pose6_t, const double* alt_t, const double* gr_t, int Nt, int Mt, double* out7, orc_lm_trace* trace)
 {
     const double PI = ORC_PI_REF;
     orc_pose cps_s, cps_t, ident;
@@ -389,10 +462,20 @@ int orc_triangulate(const double* kp7, int n, const double* pose6_s, const doubl
         L0[0] = (gsx + gtx) / 2; L0[1] = (gsy + gty) / 2;
         L0[2] = ((pose6_s[(size_t)id_s * 6 + 5] - alt_s[id_s]) + (pose6_t[(size_t)id_t * 6 + 5] - alt_t[id_t])) / 2;
         double* o = out7 + (size_t)i * 7;
-        orc_triangulate_one(kp, &ident, &ident, &Tp_s, &Tp_t, L0, o);
+        tri_one_impl(kp, &ident, &ident, &Tp_s, &Tp_t, L0, o, trace ? &trace[i] : NULL);
         double e[2];
         orc_sss_factor(o, &Tp_s, &ident, kp[2], 0.0, e, NULL, NULL); o[3] = fabs(e[0]); o[4] = fabs(e[1]);
         orc_sss_factor(o, &Tp_t, &ident, kp[5], 0.0, e, NULL, NULL); o[5] = fabs(e[0]); o[6] = fabs(e[1]);
     }
     return n;
+}
+int orc_triangulate(const double* kp7, int n, const double* pose6_s, const double* alt_s, const double* gr_s, int Ns, int Ms,
+                    const double* pose6_t, const double* alt_t, const double* gr_t, int Nt, int Mt, double* out7)
+{
+    return triangulate_impl(kp7, n, pose6_s, alt_s, gr_s, Ns, Ms, pose6_t, alt_t, gr_t, Nt, Mt, out7, NULL);
+}
+int orc_triangulate_trace(const double* kp7, int n, const double* pose6_s, const double* alt_s, const double* gr_s, int Ns, int Ms,
+                          const double* pose6_t, const double* alt_t, const double* gr_t, int Nt, int Mt, double* out7, orc_lm_trace* trace)
+{
+    return triangulate_impl(kp7, n, pose6_s, alt_s, gr_s, Ns, Ms, pose6_t, alt_t, gr_t, Nt, Mt, out7, trace);
 }

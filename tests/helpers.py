@@ -43,3 +43,248 @@ def paired_features(N, M, n, seed, flip_bits=12, reverse=False, margin=100):
         for b in bits:
             db[i, b // 8] ^= np.uint8(1 << (b % 8))
     return ka, da, kb, db
+
+
+# ---------------------------------------------------------------- hard cases of the loop-closure and triangulation LMs
+LC_N, LC_M = 700, 480
+_LC_CACHE = {}          # lc_cases by seed and oracle references by (group, list): computed once per session, arrays read-only, results never edited
+
+
+def lc_bin_ok(b, M=LC_M):
+    """bins the library's range check admits and GetKpsPairs can emit: [1, M) and at least 20 off nadir"""
+    b = np.asarray(b)
+    return (b >= 1) & (b < M) & (np.abs(b - M // 2) >= 20)
+
+
+def lc_slant(frame, ping, b, M=LC_M):
+    pose, alt, gr = frame
+    return np.sqrt(alt[ping] ** 2 + gr[abs(int(b) - M // 2)] ** 2)
+
+
+class _Geo:
+    """geo image of a frame (orc.geo_img) with a nearest-point search over the admissible bins"""
+
+    _made = {}
+
+    @classmethod
+    def of(cls, orc, frame):
+        """one search tree per frame object (a tree costs 0.3 s and lc_cases asks for the same three frames a dozen times).  The key is the id
+        of the frame's pose array; the entry holds the frame itself, so that the array stays alive and its id cannot be handed to another one."""
+        k = id(frame[0])
+        if k not in cls._made:
+            cls._made[k] = (frame, cls(orc, frame))
+        return cls._made[k][1]
+
+    def __init__(self, orc, frame, M=LC_M):
+        from scipy.spatial import cKDTree
+        self.gx, self.gy = orc.geo_img(frame[0], frame[2], M)
+        ok = lc_bin_ok(np.arange(M), M)
+        self.cols = np.nonzero(ok)[0]
+        pts = np.stack([self.gx[:, ok].ravel(), self.gy[:, ok].ravel()], 1)
+        self.tree = cKDTree(pts)
+
+    def nearest(self, x, y):
+        d, k = self.tree.query(np.stack([np.atleast_1d(x), np.atleast_1d(y)], 1))
+        return d, k // len(self.cols), self.cols[k % len(self.cols)]
+
+
+def _row(fs, ft, ps, bs, pt, bt):
+    return [ps, bs, lc_slant(fs, ps, bs), pt, bt, lc_slant(ft, pt, bt), 0.0]
+
+
+def lc_consistent_rows(orc, fs, ft, n, rng, max_dist=0.05, t_ping=None, geo_t=None):
+    """n kp7 rows that see one ground point from both frames: a random source ping / bin, the target ping / bin whose geo point is
+    nearest (within max_dist), slant ranges from altitude and ground range.  t_ping: optional predicate on the target ping."""
+    gs = _Geo.of(orc, fs); gt = geo_t or _Geo.of(orc, ft)
+    N = len(fs[0])
+    rows = []
+    for _ in range(20):
+        ps = rng.integers(0, N, 4000); bs = rng.choice(gs.cols, 4000)
+        d, pt, bt = gt.nearest(gs.gx[ps, bs], gs.gy[ps, bs])
+        keep = d <= max_dist
+        if t_ping is not None:
+            keep &= t_ping(pt)
+        for k in np.nonzero(keep)[0]:
+            rows.append(_row(fs, ft, int(ps[k]), int(bs[k]), int(pt[k]), int(bt[k])))
+            if len(rows) == n:
+                return np.array(rows)
+    raise AssertionError("only %d of %d consistent rows found" % (len(rows), n))
+
+
+def lc_cases(orc, seed=0):
+    """Named groups of kp7 lists that drive the mini-LM (and the triangulation LM) through every exit it has.
+    Returns {name: dict(frames=[(pose, alt, gr), ...], lists=[(src slot, tgt slot, kp7 (n x 7, n <= 64)), ...])}; frames come from
+    track(700, 480, leg, seed=9).  Every row passes the library's range check (ping in [0, N), bin in [1, M), |bin - M/2| >= 20)."""
+    if seed in _LC_CACHE:
+        return _LC_CACHE[seed]
+    N, M, n = LC_N, LC_M, 40
+    sub = lambda i: np.random.default_rng([4000 + seed, i])          # a stream per group: changing one group leaves the others as they are
+    rng = sub(0)
+    f0, f1, f2 = (track(N, M, leg, seed=9) for leg in range(3))
+    r01 = lc_consistent_rows(orc, f0, f1, n, rng)
+    r02 = lc_consistent_rows(orc, f0, f2, n, rng)
+    r12 = lc_consistent_rows(orc, f1, f2, n, rng)
+    G = {}
+    G["consistent-opposite"] = dict(frames=[f0, f1], lists=[(0, 1, r01)])
+    G["consistent-same"] = dict(frames=[f0, f1, f2], lists=[(0, 2, r02)])
+    rng = sub(1)
+    noisy = r01.copy(); noisy[:, 2] += rng.normal(0, 20, n); noisy[:, 5] += rng.normal(0, 20, n)
+    G["noisy-slant"] = dict(frames=[f0, f1], lists=[(0, 1, noisy)])
+    p22 = f1[0].copy(); p22[:, 2] = 2.2                                # over 2 pi / 3: flipped, but the heading is not the reverse
+    # (64 rows of their own: one row in twenty of this group runs into the 100-iteration cap, and three of them are wanted)
+    G["wrong-flip"] = dict(frames=[f0, (p22, f1[1], f1[2])], lists=[(0, 1, lc_consistent_rows(orc, f0, f1, 64, sub(7)))])
+    tiny = r01.copy(); tiny[:, 2] = 1e-3
+    G["tiny-slant"] = dict(frames=[f0, f1], lists=[(0, 1, tiny)])
+    long_ = r01.copy(); long_[:, 5] *= 3
+    G["long-slant"] = dict(frames=[f0, f1], lists=[(0, 1, long_)])
+    zero = r01.copy(); zero[:, 2] = 0.0
+    G["zero-slant"] = dict(frames=[f0, f1], lists=[(0, 1, zero)])
+    # target = the source frame again in another slot: the baseline between a ping and its copy is exactly zero, so sig_odo[3], sig_odo[4] and
+    # the triangulation's sig_p[2] sit on their 1e-9 clamps.  The nearest target point of a source ping / bin is that same ping / bin; with it
+    # both sss factors see the landmark from one pose along one ray, its 3 x 3 block of the information matrix has rank 2, and whether the
+    # marginal's Cholesky finds the third pivot positive is settled by rounding alone; ini = 0 exactly, so the score is 0 / fin - 2: NaN
+    # when fin = 0 too, -2 otherwise.  Measured on 256 random rows of this kind: 66 % are knife-edge by lc_reference's one-ulp test, every
+    # row with a non-finite score among them (moving the target's x makes ini > 0), and no variant of the group tried (copy shifted by
+    # 1e-10 m in x or y, by 1 m in z) brings the share under 40 %.  The same ping seen 10 bins further out IS decided by the oracle (256
+    # of 256 path-stable, variances finite, clamps active).  The group is therefore 58 rows of the second kind and 6 of the first, all random,
+    # none looked at: at most 6 of 64 can be knife-edge, and those 6 carry the NaN variances and the NaN scores of the group.
+    f0c = tuple(a.copy() for a in f0)
+    rng = sub(2)
+    adm = np.nonzero(lc_bin_ok(np.arange(M)))[0]
+    zb = []
+    for i in range(64):
+        p = int(rng.integers(0, N)); b = int(rng.choice(adm))
+        same = i % 10 == 5
+        bt = b if same else (b + 10 if b + 10 < M and lc_bin_ok(b + 10) else b - 10)
+        zb.append(_row(f0, f0c, p, b, p, bt))
+    zb = np.array(zb)
+    zb_same = np.arange(64) % 10 == 5
+    G["zero-baseline"] = dict(frames=[f0, f0c], lists=[(0, 1, zb)], same_point=zb_same)
+    rng = sub(3)
+    pt_ = f0[0].copy(); pt_[:, 0] = 0.3; pt_[:, 1] = -0.2
+    ft_ = (pt_, f0[1], f0[2])
+    G["tilted"] = dict(frames=[ft_, f1], lists=[(0, 1, lc_consistent_rows(orc, ft_, f1, n, rng))])
+    # sticky flip switching on in the middle of a list: target yaw 0.5 below N / 2 (no flip), 2.5 above (flip); after the first row
+    # above the threshold come rows with the small yaw again, which stay flipped (optimizer.cpp:650,700-703)
+    rng = sub(4)
+    pm = f1[0].copy(); pm[:, 2] = np.where(np.arange(N) < N // 2, 0.5, 2.5)
+    fm = (pm, f1[1], f1[2]); gm = _Geo.of(orc, fm)
+    lo = lc_consistent_rows(orc, f0, fm, 20, rng, t_ping=lambda p: p < N // 2, geo_t=gm)
+    hi = lc_consistent_rows(orc, f0, fm, 4, rng, t_ping=lambda p: p >= N // 2, geo_t=gm)
+    G["mid-list-flip"] = dict(frames=[f0, fm], lists=[(0, 1, np.concatenate([lo[:12], hi[:1], lo[12:], hi[1:]]))], switch=12)
+    # the borders the range check admits, on the source side and on the target side; the partner is the nearest admissible point
+    rng = sub(5)
+    g0, g1 = _Geo.of(orc, f0), _Geo.of(orc, f1)
+    edge = []
+    for b in (1, M - 1, M // 2 - 20, M // 2 + 20):
+        for p in rng.integers(0, N, 3):
+            _, pt, bt = g1.nearest(g0.gx[p, b], g0.gy[p, b]); edge.append(_row(f0, f1, int(p), b, int(pt[0]), int(bt[0])))
+            _, pq, bq = g0.nearest(g1.gx[p, b], g1.gy[p, b]); edge.append(_row(f0, f1, int(pq[0]), int(bq[0]), int(p), b))
+    for p in (0, N - 1):
+        for b in rng.choice(g0.cols, 3):
+            _, pt, bt = g1.nearest(g0.gx[p, b], g0.gy[p, b]); edge.append(_row(f0, f1, p, int(b), int(pt[0]), int(bt[0])))
+            _, pq, bq = g0.nearest(g1.gx[p, b], g1.gy[p, b]); edge.append(_row(f0, f1, int(pq[0]), int(bq[0]), p, int(b)))
+    G["edges"] = dict(frames=[f0, f1], lists=[(0, 1, np.array(edge))])
+    # lists that do not fill a wavefront (four problems each)
+    G["ragged"] = dict(frames=[f0, f1, f2], lists=[(0, 1, noisy[:1]), (0, 1, r01[3:5]), (0, 2, r02[:3]),
+                                                   (0, 1, np.concatenate([tiny[5:7], zero[7:9], long_[9:10]])),
+                                                   (0, 2, np.concatenate([r02[10:14], r02[20:23] * [1, 1, 1, 1, 1, 3, 1]]))])
+    # one launch over pairs with different frames and flip flags, an empty list, a reversed pair; every wavefront straddles two pairs
+    r21 = r12[:, [3, 4, 5, 0, 1, 2, 6]]
+    t12 = r12[5:10].copy(); t12[3:, 2] = 1e-3
+    G["pairs"] = dict(frames=[f0, f1, f2], lists=[(0, 1, noisy[10:13]), (0, 2, r02[:0]), (1, 2, t12), (2, 1, r21[20:21]),
+                                                  (0, 1, np.concatenate([r01[20:22], zero[22:24], long_[24:26], noisy[26:27]]))])
+    # what a survey with bad matches hands to the selection: frame 2 is a copy of frame 0 (zero baseline against it).  The good rows see a
+    # point that dead reckoning puts 0.5 m further along the track in the target frame: the mini-LM closes that gap, the score is positive
+    # and the row becomes an edge (rows built from the DR poses themselves have nothing to gain and score below 0).
+    rng = sub(6)
+    def shifted(fs, ft, n):
+        gs, gt = _Geo.of(orc, fs), _Geo.of(orc, ft)
+        rows = []
+        while len(rows) < n:
+            p = int(rng.integers(0, N)); b = int(rng.choice(gs.cols))
+            d, pt, bt = gt.nearest(gs.gx[p, b] + 0.5, gs.gy[p, b])
+            if d[0] <= 0.05:
+                rows.append(_row(fs, ft, p, b, int(pt[0]), int(bt[0])))
+        return np.array(rows)
+    s01 = shifted(f0, f1, 24); z01 = s01.copy(); z01[:, 2] = 0.0
+    s12 = shifted(f1, f0c, 12)
+    zsel = np.concatenate([zb[:9], zb[zb_same][1:3], zb[9:18], zb[zb_same][3:]])[:24]          # all six same-point rows among 24
+    G["select"] = dict(frames=[f0, f1, f0c], lists=[(0, 1, np.concatenate([s01[:12], z01[12:18], s01[18:]])), (0, 2, zsel), (1, 2, s12)])
+    for g in G.values():
+        for s, t, k in g["lists"]:
+            assert k.shape[1] == 7 and len(k) <= 64
+            assert ((k[:, 0] >= 0) & (k[:, 0] < N) & (k[:, 3] >= 0) & (k[:, 3] < N) & lc_bin_ok(k[:, 1]) & lc_bin_ok(k[:, 4])).all()
+            k.setflags(write=False)                          # the groups are shared by every test of a session: nobody edits them in place
+        for f in g["frames"]:
+            for a in f:
+                a.setflags(write=False)
+    _LC_CACHE[seed] = G
+    return G
+
+
+def _spread(stack):
+    """largest difference among the runs, element-wise (NaN where every run is NaN counts as 0)"""
+    with np.errstate(all="ignore"):
+        import warnings
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            d = np.nanmax(stack, 0) - np.nanmin(stack, 0)
+    return np.where(np.isfinite(d), d, 0.0)
+
+
+def _nonfinite_code(a):
+    """0 finite, 1 NaN, 2 +inf, 3 -inf"""
+    a = np.asarray(a)
+    return np.where(np.isnan(a), 1, np.where(np.isposinf(a), 2, np.where(np.isneginf(a), 3, 0)))
+
+
+def _neighbours(kp7, pose_t):
+    """the row itself and its six one-ulp neighbours: both slant ranges and the target pings' x, each up and down"""
+    yield kp7, pose_t
+    for col in (2, 5):
+        for to in (np.inf, -np.inf):
+            k = kp7.copy(); k[:, col] = np.nextafter(k[:, col], to); yield k, pose_t
+    for to in (np.inf, -np.inf):
+        p = pose_t.copy(); p[:, 3] = np.nextafter(p[:, 3], to); yield kp7, p
+
+
+def lc_reference(orc, frames, s, t, kp7, key=None):
+    """The oracle on one list, and what the oracle itself can say about every row: its trace, whether its path survives a one-ulp move
+    of the inputs (path-stable: same iteration count, counters and non-finite pattern in all seven runs) and, per output element, the
+    spread among the seven.  Decided on the oracle alone.  dict(lcs, trace, stable, spread={rel, var, err1, score})"""
+    if key is not None and ("lc", key) in _LC_CACHE:
+        return _LC_CACHE[("lc", key)]
+    (ps, as_, gs), (pt, at, gt) = frames[s], frames[t]
+    runs = [orc.lc_solve_trace(k, ps, as_, gs, LC_M, p, at, gt, LC_M) for k, p in _neighbours(np.asarray(kp7, np.float64), pt)]
+    lcs, tr = runs[0]
+    stable = np.ones(len(lcs), bool)
+    for l2, t2 in runs[1:]:
+        for c in orc.TRACE_COUNTERS:
+            stable &= t2[c] == tr[c]
+        for f in ("rel", "var", "score", "err1"):
+            same = _nonfinite_code(l2[f]) == _nonfinite_code(lcs[f])
+            stable &= same.reshape(len(lcs), -1).all(1)
+    spread = {f: _spread(np.stack([r[0][f] for r in runs])) for f in ("rel", "var", "err1", "score")}
+    out = dict(lcs=lcs, trace=tr, stable=stable, spread=spread)
+    if key is not None:
+        _LC_CACHE[("lc", key)] = out
+    return out
+
+
+def tri_reference(orc, frames, s, t, kp7, key=None):
+    """lc_reference for orc_triangulate: dict(out (n x 7), trace, stable, spread (n x 7))"""
+    if key is not None and ("tri", key) in _LC_CACHE:
+        return _LC_CACHE[("tri", key)]
+    (ps, as_, gs), (pt, at, gt) = frames[s], frames[t]
+    runs = [orc.triangulate_trace(k, ps, as_, gs, LC_M, p, at, gt, LC_M) for k, p in _neighbours(np.asarray(kp7, np.float64), pt)]
+    out, tr = runs[0]
+    stable = np.ones(len(out), bool)
+    for o2, t2 in runs[1:]:
+        for c in orc.TRACE_COUNTERS:
+            stable &= t2[c] == tr[c]
+        stable &= (_nonfinite_code(o2) == _nonfinite_code(out)).all(1)
+    res = dict(out=out, trace=tr, stable=stable, spread=_spread(np.stack([r[0] for r in runs])))
+    if key is not None:
+        _LC_CACHE[("tri", key)] = res
+    return res
