@@ -54,6 +54,11 @@ class MosaicParams(C.Structure):
                 ("use_mask", C.c_int32), ("pad_", C.c_int32)]
 
 
+class PGGateParams(C.Structure):
+    """dsss_pg_gate_params: chi-square gate, the factor between the worst kept edge and the threshold of a round, solves at most"""
+    _fields_ = [("gate", C.c_double), ("decade", C.c_double), ("max_solves", C.c_int32), ("pad_", C.c_int32)]
+
+
 class DsssError(RuntimeError):
     code = None          # the DSSS_E_* value where the error came from the library
 
@@ -139,6 +144,13 @@ def lib():
         L.dsss_comm_init_callback.argtypes = [C.c_void_p, C.c_int, C.c_int, COMM_FN, C.c_void_p]
         L.dsss_comm_init_device_callback.argtypes = [C.c_void_p, C.c_int, C.c_int, COMM_DEV_FN, C.c_void_p]
         L.dsss_comm_frame_owner.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.dsss_posegraph_edge_report.restype = C.c_int
+        L.dsss_posegraph_edge_report.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.dsss_pg_gate_params_default.restype = None
+        L.dsss_pg_gate_params_default.argtypes = [C.POINTER(PGGateParams)]
+        L.dsss_posegraph_solve_gated.restype = C.c_int
+        L.dsss_posegraph_solve_gated.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(PGGateParams), C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
         _LIB = L
     return _LIB
 
@@ -508,6 +520,37 @@ class Context:
         self._chk(self.L.dsss_posegraph_solve_edges(self.h, _ptr(dr6), len(dr6), _ptr(edges), len(edges), _ptr(poses), _ptr(stats)),
                   "dsss_posegraph_solve_edges")
         return poses, stats
+
+    def posegraph_edge_report(self, dr6, edges, poses12):
+        """dsss_posegraph_edge_report: every factor of the graph (dr6 chain + edges) evaluated at poses12 (total x 12; a numpy array or a
+        torch tensor, host or device) -> (chi2[ne], r6[ne, 6] whitened residuals, sums3 = 0.5 sum r^2 of the chain, of the loop closures,
+        and their sum, the LM objective)"""
+        dr6 = np.ascontiguousarray(dr6, np.float64).reshape(-1, 6)
+        edges = np.ascontiguousarray(edges, LCEDGE_DTYPE)
+        if isinstance(poses12, np.ndarray) or not hasattr(poses12, "data_ptr"):
+            poses12 = np.ascontiguousarray(poses12, np.float64).reshape(-1, 12)
+        if len(poses12) != len(dr6) or (hasattr(poses12, "data_ptr") and (str(poses12.dtype) != "torch.float64" or poses12.numel() != len(dr6) * 12)):
+            raise ValueError("posegraph_edge_report: poses12 must be %d x 12 float64" % len(dr6))
+        ne = len(edges)
+        chi2 = np.zeros(ne, np.float64); r6 = np.zeros((ne, 6), np.float64); sums = np.zeros(3, np.float64)
+        self._chk(self.L.dsss_posegraph_edge_report(self.h, _ptr(dr6), len(dr6), _ptr(edges), ne, _ptr(poses12), _ptr(chi2), _ptr(r6), _ptr(sums)),
+                  "dsss_posegraph_edge_report")
+        return chi2, r6, sums
+
+    def gate_params_default(self):
+        g = PGGateParams(); self.L.dsss_pg_gate_params_default(C.byref(g)); return g
+
+    def posegraph_solve_gated(self, dr6, edges, gate=None):
+        """dsss_posegraph_solve_gated: solve, drop the worst decade of the closures whose chi2 exceeds the gate, solve again (gate: a
+        PGGateParams, None = the defaults) -> (poses, stats of the last solve, keep[ne] bool, chi2[ne] of ALL edges at the result, solves)"""
+        dr6 = np.ascontiguousarray(dr6, np.float64).reshape(-1, 6)
+        edges = np.ascontiguousarray(edges, LCEDGE_DTYPE)
+        ne = len(edges)
+        poses = np.zeros((len(dr6), 12), np.float64); stats = np.zeros(4, np.float64)
+        keep = np.zeros(ne, np.uint8); chi2 = np.zeros(ne, np.float64); ns = C.c_int(0)
+        self._chk(self.L.dsss_posegraph_solve_gated(self.h, _ptr(dr6), len(dr6), _ptr(edges), ne, C.byref(gate) if gate is not None else None,
+                                                    _ptr(poses), _ptr(stats), _ptr(keep), _ptr(chi2), C.byref(ns)), "dsss_posegraph_solve_gated")
+        return poses, stats, keep.astype(bool), chi2, ns.value
 
     def posegraph_schedule(self):
         """panel levels of the last solve: (levels[n][4] = items, widest panel columns, tallest rows below, interface flag; trials)"""

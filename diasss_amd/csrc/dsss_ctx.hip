@@ -139,6 +139,7 @@ void dsss_destroy(dsss_ctx* c)
     if (c->pg_scal_host) hipHostFree(c->pg_scal_host);
     if (c->pg_warm) hipFree(c->pg_warm);
     hipFree(c->mosaic_buf);
+    hipFree(c->pgr_buf);
     if (c->geoms && c->geoms_free) c->geoms_free(c->geoms);
     if (c->ex_pinned) hipHostFree(c->ex_pinned);
     if (c->bbox_pinned) hipHostFree(c->bbox_pinned);

@@ -134,6 +134,7 @@ struct dsss_ctx {
     void* pg_warm = nullptr; size_t pg_warm_cap = 0; int pg_warm_n = 0;   // pose_t[pg_warm_n]
     std::vector<dsss_lc_edge> pg_inc_edges; unsigned long long lc_gen = 0, pg_inc_gen = 0;    // lc_gen counts LC result sets; the last one consumed
     void* mosaic_buf = nullptr; size_t mosaic_cap = 0;          // device scratch of dsss_mosaic_*: accumulators, output layers, job table, trajectory rows (kept between calls)
+    void* pgr_buf = nullptr; size_t pgr_cap = 0;                // device scratch of dsss_posegraph_edge_report (dsss_pg_report.hip), kept between calls
     dsss_prof prof;
 };
 

@@ -4,69 +4,7 @@
 // trajectory rows (optimizer.cpp:1164-1214).  Everything here runs at -ffp-contract=off.
 #include "dsss_pg_kernels.h"
 #include "dsss_pg_dev.h"
-// ------------------------------------------------------------------ factors
-// factor k < n: k == 0 prior on X0 (measurement DR0), else Between(X_{k-1}, X_k); factor n + e: LC edge e.
-// r = whitened residual, Ji = whitened Jacobian wrt the first pose (-W Ad(h^-1)); the Jacobian wrt the second
-// pose is W itself (BetweenFactor with GTSAM_SLOW_BUT_CORRECT_BETWEENFACTOR off, PriorFactor H = I).
-// WJ is a template parameter and the arrays are indexed by unrolled loops only: r and Ji stay in registers (with a run-time `Ji != nullptr` the
-// compiler kept the 36 + 2 doubles in 304 bytes of private memory per thread -- 125 MB of scratch traffic per launch at C3, the reason the
-// kernel wrote 243 MB for 138 MB of residuals and Jacobians).  Same operations in the same order: same bits.
-template <bool WJ>
-__device__ __forceinline__ void factor_eval(int k, int n, const pose_t* X, const pose_t* meas, const pg_weights& W,
-                                            const int* ea, const int* eb, const pose_t* emeas, const double* ew,
-                                            double (&r)[6], double (&Ji)[36])
-{
-    double xi[6];
-    if (k == 0) {
-        pose_t d;
-        pose_between(&meas[0], &X[0], &d);
-        pose_log(&d, xi);
-#pragma unroll
-        for (int a = 0; a < 6; ++a) r[a] = xi[a] * W.prior[a];
-        if (WJ) {
-#pragma unroll
-            for (int a = 0; a < 36; ++a) Ji[a] = 0.0;
-        }
-        return;
-    }
-    int i, j; const pose_t* m; double w[6];
-    if (k < n) {
-        i = k - 1; j = k; m = &meas[k];
-#pragma unroll
-        for (int a = 0; a < 6; ++a) w[a] = W.odo[a];
-    } else {
-        const int e = k - n; i = ea[e]; j = eb[e]; m = &emeas[e];
-#pragma unroll
-        for (int a = 0; a < 6; ++a) w[a] = ew[(size_t)e * 6 + a];
-    }
-    pose_t h, er;
-    pose_between(&X[i], &X[j], &h);
-    pose_between(m, &h, &er);
-    pose_log(&er, xi);
-#pragma unroll
-    for (int a = 0; a < 6; ++a) r[a] = xi[a] * w[a];
-    if (WJ) {
-        pose_t hi; double Ad[36];
-        pose_inverse(&h, &hi);
-        pose_adjoint(&hi, Ad);
-#pragma unroll
-        for (int a = 0; a < 6; ++a)
-#pragma unroll
-            for (int b = 0; b < 6; ++b) Ji[a * 6 + b] = -Ad[a * 6 + b] * w[a];
-    }
-}
-
-// deterministic block sum: wave shuffle tree then the 4 wave sums in order
-__device__ inline double block_sum256(double v, double* s_w)
-{
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
-}
-
+// (the factors themselves -- factor_eval -- and the fixed block sum live in dsss_pg_dev.h: the report kernel of dsss_pg_report.hip evaluates the same ones)
 // Ownership with several ranks (dsss_comm.hip): a rank owns the poses [mp0, mp1); chain factor k belongs to the owner of pose k,
 // LC edge (a, b) to the owner of its HIGHER pose eo = max(a, b) -- the rule the analysis builds the interface on (dsss_pg_sym.cpp:
 // "a factor belongs to the rank of its higher pose and adds to the diagonal block of the lower one").  The pipeline's own edges

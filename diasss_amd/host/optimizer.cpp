@@ -10,6 +10,9 @@
 #include <iostream>
 #include <stdexcept>
 #include <algorithm>
+#include <array>
+#include <limits>
+#include <map>
 
 namespace Diasss
 {
@@ -18,6 +21,7 @@ bool Optimizer::USE_ANNO = 0;
 bool Optimizer::ADD_LC = 1;
 bool Optimizer::ONLINE = 0;
 int Optimizer::ONLINE_WINDOW = 0;
+double Optimizer::LC_GATE = 0;
 bool Optimizer::EVAL_1 = 0;
 bool Optimizer::EVAL_2 = 0;
 
@@ -147,6 +151,35 @@ void Optimizer::TrajOptimizationAll(std::vector<Frame> &AllFrames)
         }
         n_edges = dsss_posegraph_online_edges(c);
         std::cout << "online: " << updates << " updates, " << trials << " accepted LM steps in all" << std::endl;
+    } else if (ADD_LC && LC_GATE > 0) {
+        // the chi-square gated solve (no reference counterpart): the selected closures and the frames' dead-reckoning rows go through
+        // dsss_posegraph_solve_gated, which drops the closures that disagree with the trajectory they helped to produce
+        std::vector<dsss_lc_edge> ed((size_t)std::max<size_t>(kp7.size() / 7, 1));
+        Device::check(dsss_posegraph_select(c, (int)F, ed.data(), (int)ed.size(), &n_edges), "dsss_posegraph_select");
+        std::vector<double> dr;
+        for (size_t i = 0; i < F; i++) dr.insert(dr.end(), AllFrames[i].dr_poses.ptr<double>(), AllFrames[i].dr_poses.ptr<double>() + (size_t)AllFrames[i].dr_poses.rows * 6);
+        dsss_pg_gate_params gp;
+        dsss_pg_gate_params_default(&gp);
+        gp.gate = LC_GATE;
+        std::vector<uint8_t> keep((size_t)std::max(n_edges, 1));
+        std::vector<double> chi2((size_t)std::max(n_edges, 1));
+        int n_solves = 0;
+        Device::check(dsss_posegraph_solve_gated(c, dr.data(), id_sum, ed.data(), n_edges, &gp, poses12.data(), stats, keep.data(), chi2.data(), &n_solves),
+                      "dsss_posegraph_solve_gated");
+        // one line per frame pair that lost an edge: frames, edges kept / total, largest chi2 (at the returned trajectory)
+        auto frame_of = [&](int pose) { size_t f = 0; while (f + 1 < F && pose > unique_id[f].back()) ++f; return (int)f; };
+        std::map<std::pair<int,int>, std::array<double,3>> per_pair;      // kept, total, largest chi2
+        int n_kept = 0;
+        for (int e = 0; e < n_edges; e++) {
+            std::array<double,3> &q = per_pair[std::make_pair(frame_of(ed[e].a), frame_of(ed[e].b))];
+            q[0] += keep[e]; q[1] += 1; q[2] = std::max(q[2], std::isfinite(chi2[e]) ? chi2[e] : std::numeric_limits<double>::infinity());
+            n_kept += keep[e];
+        }
+        for (const auto &kv : per_pair)
+            if (kv.second[0] < kv.second[1])
+                std::cout << "LC gate: frames " << kv.first.first << " - " << kv.first.second << ": kept " << (int)kv.second[0] << " / " << (int)kv.second[1]
+                          << " closures, largest chi2 " << kv.second[2] << std::endl;
+        std::cout << "LC gate " << LC_GATE << ": " << n_kept << " of " << n_edges << " closures kept after " << n_solves << " solves" << std::endl;
     } else if (ADD_LC) {
         Device::check(dsss_posegraph_solve(c, (int)F, poses12.data(), nullptr, stats), "dsss_posegraph_solve");
         std::vector<dsss_lc_edge> tmp((size_t)std::max<size_t>(kp7.size() / 7, 1));

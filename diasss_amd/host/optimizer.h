@@ -27,6 +27,7 @@ namespace Diasss
         static bool ADD_LC;
         static bool ONLINE;      // frame-by-frame updates (the reference's iSAM2 loop, optimizer.cpp:134-272) instead of one batch solve
         static int ONLINE_WINDOW; // > 0 with ONLINE: an update solves only the last ONLINE_WINDOW frames, conditioned on the frozen rest (dsss_posegraph_update_window); the last update is global
+        static double LC_GATE;    // > 0 (batch solve only, ONLINE off): the chi-square gated solve with this gate (dsss_posegraph_solve_gated; 22.458 = 6 dof at p = 0.999); 0 = off, the plain solve
         // the two annotation evaluators of EvaluateByAnnosAll; the reference hard-codes both to 0 (optimizer.cpp:1579)
         static bool EVAL_1;
         static bool EVAL_2;

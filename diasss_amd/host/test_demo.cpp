@@ -31,6 +31,7 @@ int main(int argc, char** argv)
             else if (k == "--use-anno") Optimizer::USE_ANNO = atoi(v.c_str()) != 0;      // optimizer.cpp:26 hard-codes 1 (hand annotations); default here 0
             else if (k == "--add-lc") Optimizer::ADD_LC = atoi(v.c_str()) != 0;
             else if (k == "--online-window") Optimizer::ONLINE_WINDOW = atoi(v.c_str());      // with --online 1: updates solve the last N frames only (incremental), the last one is global
+            else if (k == "--lc-gate") Optimizer::LC_GATE = atof(v.c_str());      // > 0: chi-square gated batch solve (22.458 = 6 dof at p = 0.999); closures that disagree with the trajectory are dropped
             else if (k == "--online") Optimizer::ONLINE = atoi(v.c_str()) != 0;      // frame-by-frame updates as the reference's iSAM2 loop does (default: one batch solve)
             else if (k == "--eval") { Optimizer::EVAL_1 = (atoi(v.c_str()) & 1) != 0; Optimizer::EVAL_2 = (atoi(v.c_str()) & 2) != 0; }      // optimizer.cpp:1579 hard-codes both off
         }

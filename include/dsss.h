@@ -234,6 +234,29 @@ int dsss_posegraph_schedule_get(dsss_ctx*, int* levels4_host, int cap_levels, in
 int dsss_posegraph_solve_edges(dsss_ctx*, const double* dr6, int total, const dsss_lc_edge* edges, int ne,
                                double* poses12_host, double* stats4_host);
 
+/* ------------------------------------------------------------------ loop-closure residual report and chi-square gated solve (new: the
+ * reference hands every selected closure to the optimiser, optimizer.cpp:203-258, and never asks whether it agrees with the result)
+ * every factor of the pose graph (dr6 chain + edges, exactly the graph dsss_posegraph_solve_edges builds) evaluated at poses12
+ * (total x 12, R row-major | t; host or device pointer).  chi2_host[ne], r6_host[ne x 6] (may be NULL),
+ * sums3_host (may be NULL) = { 0.5 sum over the chain factors, 0.5 sum over the loop closures, their sum = the LM objective }.
+ * r6[e][a] = Log(rel_e^-1 X_a^-1 X_b)[a] / sqrt(var_e[a]), chi2[e] = sum_a r6[e][a]^2 (a = 0..5 in order).  The sums are fixed-order
+ * trees: identical from call to call.  total >= 1, ne == 0 is valid.  DSSS_E_ARG: an edge index out of range or a == b, a variance that is
+ * not positive and finite, a rel that is not finite.  Single rank (DSSS_E_STATE with a communicator of more than one rank).          */
+int dsss_posegraph_edge_report(dsss_ctx*, const double* dr6, int total, const dsss_lc_edge* edges, int ne,
+                               const double* poses12, double* chi2_host, double* r6_host, double* sums3_host);
+
+/* The gated solve.  All edges start kept; repeat: (1) dsss_posegraph_solve_edges on the kept edges, compacted in their original order;
+ * (2) report the kept edges at the result, m = their largest chi2 (a non-finite one counts as +inf); (3) m <= gate, or this was solve
+ * number max_solves: stop; (4) drop every kept edge with chi2 > max(gate, m / decade), go to (1).  (m = +inf drops nothing and stops.)
+ * poses12_host and stats4_host are those of the last solve, keep_host the final mask, chi2_host ALL ne edges (dropped ones included) at
+ * the returned trajectory, n_solves_host the number of solves; with every edge dropped the last solve is the chain alone.
+ * params NULL: the defaults.  DSSS_E_ARG: gate not above 0, decade not above 1, max_solves < 1, and what the report rejects.  Single rank. */
+typedef struct { double gate, decade; int32_t max_solves, pad_; } dsss_pg_gate_params;
+void dsss_pg_gate_params_default(dsss_pg_gate_params*);   /* gate 22.458 (chi-square, 6 dof, p = 0.999), decade 10, max_solves 8 */
+int dsss_posegraph_solve_gated(dsss_ctx*, const double* dr6, int total, const dsss_lc_edge* edges, int ne,
+                               const dsss_pg_gate_params*, double* poses12_host, double* stats4_host,
+                               uint8_t* keep_host /* ne */, double* chi2_host /* ne, may be NULL */, int* n_solves_host);
+
 /* Host twin of the pose-graph linear solve (ordering + symbolic analysis + multifrontal factorisation of the reduced
  * system, diasss_amd/csrc/dsss_pg_sym.cpp) so that the CPU test-suite can pin the analysis the device kernels run on without
  * a GPU; the hot path runs the numeric phase in dsss_pg.hip.  Matrix: ns block variables (6x6 blocks); value index v < ns is
