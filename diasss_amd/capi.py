@@ -54,6 +54,21 @@ class MosaicParams(C.Structure):
                 ("use_mask", C.c_int32), ("pad_", C.c_int32)]
 
 
+class RegParams(C.Structure):
+    """dsss_reg_params: search radius in cells (0..16) and the fewest overlapping cells a shift needs to be usable"""
+    _fields_ = [("radius", C.c_int32), ("min_cells", C.c_int32)]
+
+
+class RegResult(C.Structure):
+    """dsss_reg_result: peak shift in cells, offset in metres (sub-cell), ZNCC and overlapping cells at the peak and at zero shift,
+    on_border = 1 when the peak lies on the border of the search square"""
+    _fields_ = [("dx", C.c_int32), ("dy", C.c_int32), ("off_x", C.c_double), ("off_y", C.c_double), ("zncc", C.c_double),
+                ("zncc0", C.c_double), ("n", C.c_int64), ("n0", C.c_int64), ("on_border", C.c_int32), ("pad_", C.c_int32)]
+
+
+REG_DTYPE = np.dtype(RegResult)          # the rows Context.mosaic_register returns
+
+
 class PGGateParams(C.Structure):
     """dsss_pg_gate_params: chi-square gate, the factor between the worst kept edge and the threshold of a round, solves at most"""
     _fields_ = [("gate", C.c_double), ("decade", C.c_double), ("max_solves", C.c_int32), ("pad_", C.c_int32)]
@@ -151,6 +166,13 @@ def lib():
         L.dsss_posegraph_solve_gated.restype = C.c_int
         L.dsss_posegraph_solve_gated.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(PGGateParams), C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
+        L.dsss_reg_params_default.restype = None
+        L.dsss_reg_params_default.argtypes = [C.POINTER(RegParams)]
+        L.dsss_mosaic_register.restype = C.c_int
+        L.dsss_mosaic_register.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(MosaicParams), C.c_void_p, C.c_void_p,
+                                           C.c_int, C.POINTER(RegParams), C.c_void_p, C.c_void_p]
+        L.dsss_mosaic_register_peak.restype = C.c_int
+        L.dsss_mosaic_register_peak.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.POINTER(RegResult)]
         _LIB = L
     return _LIB
 
@@ -184,6 +206,27 @@ def mosaic_grid(bbox4, cell):
         e.code = rc
         raise e
     return p
+
+
+def reg_params_default():
+    r = RegParams(); lib().dsss_reg_params_default(C.byref(r)); return r
+
+
+def mosaic_register_peak(sums, radius, min_cells, cell):
+    """dsss_mosaic_register_peak: the score, peak, tie and sub-cell rules on one pair's table of shift sums ((2 radius + 1)^2 x 6 uint64,
+    dy-major; n, Sa, Sb, Sab, Saa, Sbb) -> RegResult.  Host arithmetic, no context."""
+    L = lib()
+    out = RegResult()
+    if sums is not None:
+        sums = np.ascontiguousarray(sums, np.uint64)
+        if 0 <= int(radius) <= 16 and sums.size != (2 * int(radius) + 1) ** 2 * 6:
+            raise ValueError("mosaic_register_peak: %d sums for radius %d" % (sums.size, radius))
+    rc = L.dsss_mosaic_register_peak(_ptr(sums), int(radius), int(min_cells), C.c_double(cell), C.byref(out))
+    if rc != 0:
+        e = DsssError("dsss_mosaic_register_peak: %s (radius %r, min_cells %r, cell %r)" % (L.dsss_strerror(rc).decode(), radius, min_cells, cell))
+        e.code = rc
+        raise e
+    return out
 
 
 class Context:
@@ -597,6 +640,22 @@ class Context:
         self._chk(self.L.dsss_mosaic_consistency(self.h, _ptr(ids), len(ids), _ptr(rpy6), _ptr(ping_off), C.byref(params),
                                                  _ptr(nfr), _ptr(s1), _ptr(s2), C.byref(score)), "dsss_mosaic_consistency")
         return nfr, s1, s2, score.value
+
+    def mosaic_register(self, ids, params, pairs, reg=None, rpy6=None, ping_off=None, want_sums=False):
+        """dense overlap registration of the frame pairs `pairs` = [(a, b), ...] (frame ids, both in ids) under the trajectory: frame b slid
+        over frame a within reg.radius cells (reg: a RegParams, None = the defaults) -> rows of REG_DTYPE, one per pair: the peak shift
+        in cells, the offset in metres that b lies from where the overlap says it belongs, ZNCC and cells at the peak and at zero shift.
+        want_sums=True returns (rows, sums) with sums[npairs, 2 r + 1, 2 r + 1, 6] uint64 (dy, dx; n, Sa, Sb, Sab, Saa, Sbb)."""
+        ids, rpy6, ping_off = self._mosaic_traj(ids, rpy6, ping_off)
+        pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        pa = np.ascontiguousarray(pairs[:, 0]); pb = np.ascontiguousarray(pairs[:, 1])
+        r = reg if reg is not None else reg_params_default()
+        S = 2 * max(0, min(int(r.radius), 16)) + 1
+        out = np.zeros(len(pairs), REG_DTYPE)
+        sums = np.zeros((len(pairs), S, S, 6), np.uint64) if want_sums else None
+        self._chk(self.L.dsss_mosaic_register(self.h, _ptr(ids), len(ids), _ptr(rpy6), _ptr(ping_off), C.byref(params), _ptr(pa), _ptr(pb),
+                                              len(pairs), C.byref(r), _ptr(out), _ptr(sums)), "dsss_mosaic_register")
+        return (out, sums) if want_sums else out
 
     # ---- instrumentation
     def profile(self, on=True):

@@ -2,19 +2,10 @@
 // The reference has no counterpart: it stops at the trajectory file.  What goes into the mosaic is on the device when the solve
 // returns (normalised waterfall, filter mask, geometry), so the map is a forward scatter of the pixels into a grid of integer
 // accumulators.  Integers because the result has to be the same whatever the order of the frames and from call to call.
-#include "dsss_internal.h"
+#include "dsss_mosaic_int.h"
 #include <algorithm>
 
-#define MOSAIC_MAX_CELLS (1ll << 28)
-#define MOSAIC_MAX_SAMPLES (1u << 24)      // per cell: 255 * 2^24 < 2^32, the u32 sum cannot wrap below it
-
 namespace {
-
-// one frame of a launch: its pose rows (the frame's own or the caller's trajectory), geometry and images; blk0 = its first workgroup
-struct mosaic_job { const double* pose; const double* gr; const uint8_t* img; const uint8_t* mask; int N, M, blk0, pad; };
-// the grid (x0, y0, cell, W, H: where a point falls and whether it is kept) and the window of it the accumulators cover
-// (ox, oy, bw, bh: the whole grid for the mosaic, one frame's cell bounding box for the consistency map)
-struct mosaic_win { double x0, y0, cell; int W, H, ox, oy, bw, bh, use_mask; };
 
 // One workgroup per ping, one wavefront per 64 consecutive bins.  The bearing of each side is evaluated once per ping (dsss_geo_side)
 // and shared through LDS; the bins then cost a multiply-add and two divisions each.  Consecutive bins of a ping walk through the
@@ -91,8 +82,9 @@ __global__ __launch_bounds__(256) void mosaic_fold_kernel(const unsigned long lo
     nfr[g] += 1; s1[g] += m; s2[g] += m * m;
 }
 
-struct carve { size_t off = 0; size_t take(size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; } };
+} // namespace
 
+// ---- host helpers shared with dsss_mosaic_reg.hip (dsss_mosaic_int.h)
 int mosaic_reserve(dsss_ctx* c, size_t bytes)
 {
     if (c->mosaic_cap >= bytes) return DSSS_OK;
@@ -195,8 +187,6 @@ void launch_scatter(dsss_ctx* c, const mosaic_job* d_jobs, int njobs, int blocks
 {
     hipLaunchKernelGGL(mosaic_scatter_kernel, dim3((unsigned)blocks), dim3(256), 0, c->stream, d_jobs, njobs, G, acc);
 }
-
-} // namespace
 
 extern "C" {
 

@@ -1,0 +1,25 @@
+// diasss_amd/csrc/dsss_mosaic_int.h -- what dsss_mosaic.hip (mosaic, consistency map) and dsss_mosaic_reg.hip (overlap registration)
+// share: the job and window records of mosaic_scatter_kernel, the argument checks, a frame's window of the grid, the upload of a
+// caller's trajectory and the scatter launch.  The definitions are in dsss_mosaic.hip.
+#pragma once
+#include "dsss_internal.h"
+
+#define MOSAIC_MAX_CELLS (1ll << 28)
+#define MOSAIC_MAX_SAMPLES (1u << 24)      // per cell: 255 * 2^24 < 2^32, the u32 sum cannot wrap below it
+
+// one frame of a launch: its pose rows (the frame's own or the caller's trajectory), geometry and images; blk0 = its first workgroup
+struct mosaic_job { const double* pose; const double* gr; const uint8_t* img; const uint8_t* mask; int N, M, blk0, pad; };
+// the grid (x0, y0, cell, W, H: where a point falls and whether it is kept) and the window of it the accumulators cover
+// (ox, oy, bw, bh: the whole grid for the mosaic, one frame's cell bounding box for the consistency map and the registration)
+struct mosaic_win { double x0, y0, cell; int W, H, ox, oy, bw, bh, use_mask; };
+
+// carves mosaic_buf into 256-byte aligned pieces
+struct carve { size_t off = 0; size_t take(size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; } };
+
+int mosaic_reserve(dsss_ctx* c, size_t bytes);
+int mosaic_check_frames(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, bool need_img, size_t* rows);
+int mosaic_check_params(dsss_ctx* c, const dsss_mosaic_params* p);
+void frame_extent(const dsss_frame& f, const double* rows, double* bb);
+bool cell_range(double lo, double hi, double origin, double cell, int n, int* a, int* b);
+int upload_rows(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, double* d_rows, std::vector<const double*>& dev_rows);
+void launch_scatter(dsss_ctx* c, const mosaic_job* d_jobs, int njobs, int blocks, const mosaic_win& G, unsigned long long* acc);

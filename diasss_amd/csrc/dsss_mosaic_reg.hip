@@ -1,0 +1,305 @@
+// diasss_amd/csrc/dsss_mosaic_reg.hip -- dense overlap registration of frame pairs (include/dsss.h, section "mosaic", "overlap
+// registration").  Every frame of a pair is rendered alone into its window of the grid (mosaic_scatter_kernel, as the consistency map
+// does) and kept as one u16 per cell; mosaic_corr_kernel slides frame b over frame a and accumulates, per shift, the six integer sums
+// of the zero-normalised cross-correlation.  Score, peak, tie and sub-cell rules are host arithmetic on that table
+// (dsss_mosaic_register_peak), exact in integers up to one conversion per quantity, so a result is the same whatever the order of
+// frames, pairs, tiles and atomics.
+#include "dsss_mosaic_int.h"
+#include <algorithm>
+
+#define REG_MAX_RADIUS 16
+#define REG_TILE 32                        // a workgroup stages 32 x 32 cells of a and the (32 + 2 r)^2 halo of b
+#define REG_HALO (REG_TILE + 2 * REG_MAX_RADIUS)
+#define REG_STRIP 8                        // tiles (along x) a workgroup walks before it flushes: 8 x 1024 x 255^2 < 2^32, the u32 partials cannot wrap
+#define REG_MAX_THREADS 1024
+#define REG_SLOTS 2                        // shifts per thread: (2 x 16 + 1)^2 = 1089 <= 2 x 1024
+
+namespace {
+
+// one pair: the two mean layers with their windows (grid cells), the region of a's cells that is walked (a's window cut with b's
+// window dilated by the radius) as tiles, blk0 = its first workgroup, and where its sums go
+struct reg_job {
+    const uint16_t* la; const uint16_t* lb; unsigned long long* out;
+    int aox, aoy, abw, abh, box, boy, bbw, bbh;
+    int rx0, ry0, rx1, ry1;                // region, inclusive
+    int tiles_x, strips_x, blk0, pad;
+};
+
+// 64-bit accumulators of one frame's window -> u16 per cell: validity in the high byte, m_f = (sum + cnt / 2) / cnt in the low one
+__global__ __launch_bounds__(256) void mosaic_mean_kernel(const unsigned long long* __restrict__ win, size_t n, uint16_t* __restrict__ lay,
+                                                          int* __restrict__ flag)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const unsigned long long a = win[i];
+    const uint32_t c = (uint32_t)(a >> 32), s = (uint32_t)a;
+    if (c > MOSAIC_MAX_SAMPLES) *flag = 1;
+    lay[i] = c ? (uint16_t)(0x100u | ((s + c / 2) / c)) : (uint16_t)0;
+}
+
+// One workgroup per strip of REG_STRIP tiles of a's cells.  Per tile the a cells and the halo of b go into LDS as u16 (cells outside a
+// window, and with it outside the grid, as 0 = invalid), with one bit per a cell in s_am.  A thread owns up to two shifts (dx fastest,
+// so neighbouring lanes read neighbouring half-words of b) and walks the tile for each: the a operand is the same address in every
+// lane and goes through a scalar register, rows and groups of eight cells without a valid a cell are skipped by scalar branches, and
+// invalid cells inside a group contribute 0 through the validity factors.  The six u32 partials of a shift live in registers over the
+// whole strip and leave as 64-bit atomics without return -- integers, so their order is irrelevant -- and only where n > 0.
+__global__ __launch_bounds__(REG_MAX_THREADS) void mosaic_corr_kernel(const reg_job* __restrict__ jobs, int njobs, int radius)
+{
+    __shared__ __attribute__((aligned(16))) uint16_t s_a[REG_TILE * REG_TILE];
+    __shared__ __attribute__((aligned(16))) uint16_t s_b[REG_HALO * REG_HALO];
+    __shared__ uint32_t s_am[REG_TILE];
+    int lo = 0, hi = njobs - 1;
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (jobs[mid].blk0 <= (int)blockIdx.x) lo = mid; else hi = mid - 1; }
+    const reg_job J = jobs[lo];
+    const int wg = (int)blockIdx.x - J.blk0;
+    const int ty = wg / J.strips_x, tx0 = (wg - ty * J.strips_x) * REG_STRIP;
+    const int tx1 = min(tx0 + REG_STRIP, J.tiles_x);
+    const int S = 2 * radius + 1, nshift = S * S, hs = REG_TILE + 2 * radius;
+    const int nt = (int)blockDim.x, t = (int)threadIdx.x;
+    int boff[REG_SLOTS]; bool act[REG_SLOTS];
+    uint32_t pn[REG_SLOTS], pa[REG_SLOTS], pb[REG_SLOTS], pab[REG_SLOTS], paa[REG_SLOTS], pbb[REG_SLOTS];
+#pragma unroll
+    for (int k = 0; k < REG_SLOTS; ++k) {
+        const int s = t + k * nt;
+        act[k] = s < nshift;
+        const int sy = act[k] ? s / S : 0, sx = act[k] ? s - sy * S : 0;     // dy + radius, dx + radius
+        boff[k] = sy * hs + sx;
+        pn[k] = pa[k] = pb[k] = pab[k] = paa[k] = pbb[k] = 0;
+    }
+    const int gy0 = J.ry0 + ty * REG_TILE;
+    for (int tx = tx0; tx < tx1; ++tx) {
+        const int gx0 = J.rx0 + tx * REG_TILE;
+        __syncthreads();                                                        // the previous tile has been walked
+        for (int i = t; i < REG_TILE * REG_TILE; i += nt) {
+            const int y = i >> 5, x = i & 31, gx = gx0 + x, gy = gy0 + y;
+            uint16_t v = 0;
+            if (gx <= J.rx1 && gy <= J.ry1) v = J.la[(size_t)(gy - J.aoy) * J.abw + (gx - J.aox)];      // the region lies inside a's window
+            s_a[i] = v;
+            const unsigned long long bal = __ballot(v != 0);                    // 64 cells = two rows of the tile per wavefront
+            if ((i & 63) == 0) { s_am[y] = (uint32_t)bal; s_am[y + 1] = (uint32_t)(bal >> 32); }
+        }
+        for (int i = t; i < hs * hs; i += nt) {
+            const int y = i / hs, x = i - y * hs;
+            const int bx = gx0 + x - radius - J.box, by = gy0 + y - radius - J.boy;
+            s_b[i] = (bx >= 0 && bx < J.bbw && by >= 0 && by < J.bbh) ? J.lb[(size_t)by * J.bbw + bx] : (uint16_t)0;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < REG_SLOTS; ++k) {
+            if (!act[k]) continue;
+            for (int y = 0; y < REG_TILE; ++y) {
+                const uint32_t m = __builtin_amdgcn_readfirstlane(s_am[y]);
+                if (!m) continue;
+                const uint16_t* brow = s_b + y * hs + boff[k];
+                for (int x8 = 0; x8 < REG_TILE; x8 += 8) {
+                    if (!((m >> x8) & 0xffu)) continue;
+                    const uint4 av = *reinterpret_cast<const uint4*>(&s_a[y * REG_TILE + x8]);
+                    const uint32_t aw[4] = { av.x, av.y, av.z, av.w };
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) {
+                        const uint32_t a = __builtin_amdgcn_readfirstlane((aw[j >> 1] >> (16 * (j & 1))) & 0xffffu);
+                        const uint32_t va = a >> 8, ma = a & 0xffu;             // an invalid a cell is 0: va = ma = 0
+                        const uint32_t b = brow[x8 + j];
+                        const uint32_t vb = b >> 8, mb = b & 0xffu;             // an invalid b cell is 0 too
+                        pn[k] += vb * va; pa[k] += vb * ma; pb[k] += mb * va;
+                        pab[k] += ma * mb; paa[k] += vb * (ma * ma); pbb[k] += (mb * va) * mb;
+                    }
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < REG_SLOTS; ++k) {
+        if (!act[k] || pn[k] == 0) continue;                                    // n == 0: the other five are 0 as well
+        unsigned long long* o = J.out + (size_t)(t + k * nt) * 6;
+        atomicAdd(o + 0, (unsigned long long)pn[k]); atomicAdd(o + 1, (unsigned long long)pa[k]); atomicAdd(o + 2, (unsigned long long)pb[k]);
+        atomicAdd(o + 3, (unsigned long long)pab[k]); atomicAdd(o + 4, (unsigned long long)paa[k]); atomicAdd(o + 5, (unsigned long long)pbb[k]);
+    }
+}
+
+// exact integer -> the nearest double, ties to even (what Python's float() of an int does): below 2^64 the hardware conversion is that
+// already; above, the value is cut to 64 bits with a sticky bit first, which leaves the rounding of the 53-bit result unchanged
+double i128_to_double(__int128 v)
+{
+    const bool neg = v < 0;
+    unsigned __int128 u = neg ? (unsigned __int128)0 - (unsigned __int128)v : (unsigned __int128)v;
+    double d;
+    if ((u >> 64) == 0) d = (double)(uint64_t)u;
+    else {
+        const int sh = 64 - __builtin_clzll((uint64_t)(u >> 64));            // bits above the low 64
+        const uint64_t top = (uint64_t)(u >> sh);
+        const bool sticky = (u & (((unsigned __int128)1 << sh) - 1)) != 0;
+        d = ldexp((double)(top | (sticky ? 1ull : 0ull)), sh);
+    }
+    return neg ? -d : d;
+}
+
+struct reg_score { double z; bool ok; };
+
+reg_score score_of(const uint64_t* s6, int min_cells)
+{
+    const __int128 n = s6[0], Sa = s6[1], Sb = s6[2], Sab = s6[3], Saa = s6[4], Sbb = s6[5];
+    const __int128 num = n * Sab - Sa * Sb, da = n * Saa - Sa * Sa, db = n * Sbb - Sb * Sb;
+    if (s6[0] < (uint64_t)min_cells || da <= 0 || db <= 0) return { -2.0, false };
+    return { i128_to_double(num) / sqrt(i128_to_double(da) * i128_to_double(db)), true };
+}
+
+int peak_of(const uint64_t* sums, int radius, int min_cells, double cell, dsss_reg_result* out)
+{
+    const int S = 2 * radius + 1;
+    std::vector<reg_score> z((size_t)S * S);
+    for (int s = 0; s < S * S; ++s) z[s] = score_of(sums + (size_t)s * 6, min_cells);
+    bool found = false; int bx = 0, by = 0;
+    for (int dy = -radius; dy <= radius; ++dy)
+        for (int dx = -radius; dx <= radius; ++dx) {
+            const reg_score& q = z[(size_t)(dy + radius) * S + (dx + radius)];
+            if (!q.ok) continue;
+            bool better = !found;
+            if (found) {
+                const double zb = z[(size_t)(by + radius) * S + (bx + radius)].z;
+                const int d2 = dx * dx + dy * dy, b2 = bx * bx + by * by;
+                better = q.z > zb || (q.z == zb && (d2 < b2 || (d2 == b2 && (dy < by || (dy == by && dx < bx)))));
+            }
+            if (better) { found = true; bx = dx; by = dy; }
+        }
+    const size_t zero = (size_t)radius * S + radius;
+    memset(out, 0, sizeof *out);
+    out->zncc0 = z[zero].z; out->n0 = (int64_t)sums[zero * 6];
+    if (!found) { out->zncc = -2.0; out->n = out->n0; return DSSS_OK; }
+    const size_t pk = (size_t)(by + radius) * S + (bx + radius);
+    out->dx = bx; out->dy = by; out->zncc = z[pk].z; out->n = (int64_t)sums[pk * 6];
+    out->on_border = (abs(bx) == radius || abs(by) == radius) ? 1 : 0;
+    double px = 0.0, py = 0.0;
+    if (!out->on_border) {
+        const double z0 = z[pk].z;
+        const reg_score xm = z[pk - 1], xp = z[pk + 1], ym = z[pk - S], yp = z[pk + S];
+        if (xm.ok && xp.ok) { const double den = xm.z - 2.0 * z0 + xp.z; if (den < 0.0) px = 0.5 * (xm.z - xp.z) / den; }
+        if (ym.ok && yp.ok) { const double den = ym.z - 2.0 * z0 + yp.z; if (den < 0.0) py = 0.5 * (ym.z - yp.z) / den; }
+    }
+    out->off_x = ((double)bx + px) * cell; out->off_y = ((double)by + py) * cell;
+    return DSSS_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+void dsss_reg_params_default(dsss_reg_params* p) { if (p) { p->radius = 8; p->min_cells = 256; } }
+
+int dsss_mosaic_register_peak(const uint64_t* sums, int radius, int min_cells, double cell, dsss_reg_result* out)
+{
+    if (!sums || !out || radius < 0 || radius > REG_MAX_RADIUS || min_cells < 1 || !(cell > 0.0) || !std::isfinite(cell)) return DSSS_E_ARG;
+    return peak_of(sums, radius, min_cells, cell, out);
+}
+
+int dsss_mosaic_register(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, const dsss_mosaic_params* p,
+                         const int* pair_a, const int* pair_b, int npairs, const dsss_reg_params* rp,
+                         dsss_reg_result* out_host, uint64_t* sums_host)
+{
+    if (!c) return DSSS_E_ARG;
+    if (dsss_comm_world(c) > 1) DSSS_FAIL(c, DSSS_E_STATE, "mosaic: registration runs on a single rank (communicator of %d)", dsss_comm_world(c));
+    size_t rows = 0;
+    int rc = mosaic_check_frames(c, ids, n, rpy6, ping_off, true, &rows); if (rc) return rc;
+    rc = mosaic_check_params(c, p); if (rc) return rc;
+    dsss_reg_params R; dsss_reg_params_default(&R);
+    if (rp) R = *rp;
+    if (R.radius < 0 || R.radius > REG_MAX_RADIUS) DSSS_FAIL(c, DSSS_E_ARG, "register: radius %d outside 0..%d", R.radius, REG_MAX_RADIUS);
+    if (R.min_cells < 1) DSSS_FAIL(c, DSSS_E_ARG, "register: min_cells = %d", R.min_cells);
+    if (npairs < 0) DSSS_FAIL(c, DSSS_E_ARG, "register: npairs = %d", npairs);
+    if (npairs > 0 && (!pair_a || !pair_b || !out_host)) DSSS_FAIL(c, DSSS_E_ARG, "register: %d pairs without %s", npairs, out_host ? "their frames" : "a result array");
+    std::vector<int> slot(c->max_frames, -1);                                  // frame id -> its index in ids
+    for (int i = 0; i < n; ++i) slot[ids[i]] = i;
+    std::vector<char> used(n, 0);
+    for (int k = 0; k < npairs; ++k) {
+        const int a = pair_a[k], b = pair_b[k];
+        if (a < 0 || a >= c->max_frames || slot[a] < 0 || b < 0 || b >= c->max_frames || slot[b] < 0)
+            DSSS_FAIL(c, DSSS_E_ARG, "register: pair %d = (%d, %d) names a frame that is not listed", k, a, b);
+        if (a == b) DSSS_FAIL(c, DSSS_E_ARG, "register: pair %d is frame %d with itself", k, a);
+        used[slot[a]] = used[slot[b]] = 1;
+    }
+    if (npairs == 0) return DSSS_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const int r = R.radius, S = 2 * r + 1, nshift = S * S;
+    // the window of every frame that occurs in a pair: the cells its geo extremes can reach (as the consistency map's)
+    std::vector<mosaic_win> wins(n); std::vector<char> on_grid(n, 0); std::vector<size_t> lay_off(n, 0);
+    size_t win_cells = 1, lay_cells = 0;
+    for (int i = 0; i < n; ++i) {
+        if (!used[i]) continue;
+        const dsss_frame& f = c->frames[ids[i]];
+        double bb[4] = { INFINITY, -INFINITY, INFINITY, -INFINITY };
+        frame_extent(f, rpy6 ? rpy6 + (size_t)ping_off[i] * 6 : f.h_geo, bb);
+        int ax, bx, ay, by;
+        if (!cell_range(bb[0], bb[1], p->x0, p->cell, p->W, &ax, &bx) || !cell_range(bb[2], bb[3], p->y0, p->cell, p->H, &ay, &by)) continue;
+        on_grid[i] = 1;
+        wins[i] = mosaic_win{ p->x0, p->y0, p->cell, p->W, p->H, ax, ay, bx - ax + 1, by - ay + 1, p->use_mask != 0 };
+        const size_t wc = (size_t)wins[i].bw * wins[i].bh;
+        win_cells = std::max(win_cells, wc);
+        lay_off[i] = lay_cells; lay_cells += (wc + 127) & ~(size_t)127;        // layers start on 256 bytes
+    }
+    const size_t table = (size_t)npairs * nshift * 6;
+    carve L;
+    const size_t o_lay = L.take(lay_cells * 2), o_win = L.take(win_cells * 8), o_jobs = L.take((size_t)n * sizeof(mosaic_job)),
+                 o_rows = L.take(rpy6 ? rows * 6 * sizeof(double) : 0), o_pairs = L.take((size_t)npairs * sizeof(reg_job)),
+                 o_tab = L.take((table + 1) * 8);                               // the sums and, behind them, the sample-limit flag: one download
+    rc = mosaic_reserve(c, L.off); if (rc) return rc;
+    char* B = static_cast<char*>(c->mosaic_buf);
+    uint16_t* d_lay = reinterpret_cast<uint16_t*>(B + o_lay);
+    unsigned long long* d_win = reinterpret_cast<unsigned long long*>(B + o_win);
+    mosaic_job* d_jobs = reinterpret_cast<mosaic_job*>(B + o_jobs);
+    reg_job* d_pairs = reinterpret_cast<reg_job*>(B + o_pairs);
+    unsigned long long* d_tab = reinterpret_cast<unsigned long long*>(B + o_tab);
+    int* d_flag = reinterpret_cast<int*>(d_tab + table);
+    std::vector<const double*> dev_rows;
+    rc = upload_rows(c, ids, n, rpy6, ping_off, reinterpret_cast<double*>(B + o_rows), dev_rows); if (rc) return rc;
+    std::vector<mosaic_job> jobs(n);
+    for (int i = 0; i < n; ++i) { const dsss_frame& f = c->frames[ids[i]]; jobs[i] = mosaic_job{ dev_rows[i], f.gr, f.lvl[0], f.mask, f.N, f.M, 0, 0 }; }
+    HIPCHK(c, hipMemcpyAsync(d_jobs, jobs.data(), (size_t)n * sizeof(mosaic_job), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_tab, 0, (table + 1) * 8, c->stream));
+    // 1. mean layers: scatter into the 64-bit window, pack into the frame's resident u16 layer
+    for (int i = 0; i < n; ++i) {
+        if (!on_grid[i]) continue;
+        const size_t wc = (size_t)wins[i].bw * wins[i].bh;
+        HIPCHK(c, hipMemsetAsync(d_win, 0, wc * 8, c->stream));
+        launch_scatter(c, d_jobs + i, 1, jobs[i].N, wins[i], d_win);
+        hipLaunchKernelGGL(mosaic_mean_kernel, dim3((unsigned)((wc + 255) / 256)), dim3(256), 0, c->stream, d_win, wc, d_lay + lay_off[i], d_flag);
+        HIPCHK(c, hipGetLastError());
+    }
+    // 2. all pairs in one launch
+    std::vector<reg_job> pj; pj.reserve(npairs);
+    long long blocks = 0;
+    for (int k = 0; k < npairs; ++k) {
+        const int ia = slot[pair_a[k]], ib = slot[pair_b[k]];
+        if (!on_grid[ia] || !on_grid[ib]) continue;
+        const mosaic_win& A = wins[ia]; const mosaic_win& Bw = wins[ib];
+        const int rx0 = std::max(A.ox, Bw.ox - r), rx1 = std::min(A.ox + A.bw - 1, Bw.ox + Bw.bw - 1 + r);
+        const int ry0 = std::max(A.oy, Bw.oy - r), ry1 = std::min(A.oy + A.bh - 1, Bw.oy + Bw.bh - 1 + r);
+        if (rx1 < rx0 || ry1 < ry0) continue;                                   // the windows do not come within the radius: all sums stay 0
+        reg_job J;
+        J.la = d_lay + lay_off[ia]; J.lb = d_lay + lay_off[ib]; J.out = d_tab + (size_t)k * nshift * 6;
+        J.aox = A.ox; J.aoy = A.oy; J.abw = A.bw; J.abh = A.bh; J.box = Bw.ox; J.boy = Bw.oy; J.bbw = Bw.bw; J.bbh = Bw.bh;
+        J.rx0 = rx0; J.ry0 = ry0; J.rx1 = rx1; J.ry1 = ry1;
+        J.tiles_x = (rx1 - rx0) / REG_TILE + 1; J.strips_x = (J.tiles_x + REG_STRIP - 1) / REG_STRIP;
+        J.blk0 = (int)blocks; J.pad = 0;
+        blocks += (long long)J.strips_x * ((ry1 - ry0) / REG_TILE + 1);
+        if (blocks > 0x7fffffffll) DSSS_FAIL(c, DSSS_E_ARG, "register: %d pairs are more than one launch takes", npairs);
+        pj.push_back(J);
+    }
+    if (!pj.empty()) {
+        const int slots = (nshift + REG_MAX_THREADS - 1) / REG_MAX_THREADS;    // 1, or 2 from radius 16 on
+        const int threads = (((nshift + slots - 1) / slots) + 63) & ~63;
+        HIPCHK(c, hipMemcpyAsync(d_pairs, pj.data(), pj.size() * sizeof(reg_job), hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(mosaic_corr_kernel, dim3((unsigned)blocks), dim3((unsigned)threads), 0, c->stream, d_pairs, (int)pj.size(), r);
+        HIPCHK(c, hipGetLastError());
+    }
+    std::vector<uint64_t> own;
+    uint64_t* tab = nullptr;
+    own.resize(table + 1); tab = own.data();
+    HIPCHK(c, hipMemcpyAsync(tab, d_tab, (table + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if ((int)tab[table]) DSSS_FAIL(c, DSSS_E_CAPACITY, "mosaic: a cell received more than 2^24 samples of one frame (cell %g too coarse)", p->cell);
+    for (int k = 0; k < npairs; ++k) peak_of(tab + (size_t)k * nshift * 6, r, R.min_cells, p->cell, out_host + k);
+    if (sums_host) memcpy(sums_host, tab, table * 8);
+    return DSSS_OK;
+}
+
+} // extern "C"

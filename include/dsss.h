@@ -306,6 +306,41 @@ int dsss_mosaic_consistency(dsss_ctx*, const int* ids, int n, const double* rpy6
                             const dsss_mosaic_params*, uint32_t* nfr_host, uint32_t* s1_host, uint32_t* s2_host,
                             double* score_host);
 
+/* ---- overlap registration: how far, in metres and in which direction, frame b lies from where its overlap with frame a says it belongs.
+ * An independent, metric, per-pair measure of a trajectory (the consistency score has no unit of length, the edge report measures the
+ * loop closures against the trajectory they produced).  All quantities are integers up to the final score, so results do not depend on
+ * the order of frames, pairs, tiles or atomics and are identical from call to call.
+ * Mean layer: for a frame f under the given trajectory and grid, cnt_f, sum_f and m_f = (sum_f + cnt_f / 2) / cnt_f are exactly those
+ *   of dsss_mosaic_consistency (same binning, same mask rule).  A cell is valid for f iff cnt_f > 0; cells outside the grid are invalid.
+ * Shift sums: for a pair (a, b) and a shift (dx, dy), |dx|, |dy| <= radius, V = the grid cells (ix, iy) where a is valid at (ix, iy) and
+ *   b is valid at (ix + dx, iy + dy).  Six uint64 sums over V, in this order: n = |V|, Sa = sum m_a, Sb = sum m_b, Sab = sum m_a m_b,
+ *   Saa = sum m_a^2, Sbb = sum m_b^2, with m_b taken at the shifted cell.  Shifts are ordered dy-major: index
+ *   (dy + radius) (2 radius + 1) + (dx + radius).
+ * Score: num = n Sab - Sa Sb, da = n Saa - Sa^2, db = n Sbb - Sb^2 are evaluated exactly in integers (128 bit), each converted ONCE to
+ *   the nearest double (ties to even), and zncc = num / sqrt(da db) in f64.  A shift is usable iff n >= min_cells, da > 0 and db > 0;
+ *   zncc = -2 otherwise.
+ * Peak: the usable shift with the largest zncc; ties go to the smallest dx^2 + dy^2, then the smallest dy, then the smallest dx.  No
+ *   usable shift: dx = dy = 0, zncc = -2, n = n0, offsets 0, on_border = 0.
+ * Sub-cell offset: per axis a parabola through the peak and its two neighbours on that axis, p = 0.5 (z- - z+) / (z- - 2 z0 + z+)
+ *   (evaluated left to right in f64); p = 0 on both axes when the peak is on the border of the search square, and on an axis where a
+ *   neighbour is not usable or the denominator is not below 0.  off = ((dx + px) cell, (dy + py) cell) in metres.                    */
+typedef struct { int32_t radius, min_cells; } dsss_reg_params;            /* radius 0..16 cells; default 8, 256 */
+typedef struct { int32_t dx, dy; double off_x, off_y;                     /* peak in cells, offset in metres (sub-cell) */
+                 double zncc, zncc0; int64_t n, n0;                       /* at the peak / at zero shift */
+                 int32_t on_border, pad_; } dsss_reg_result;              /* 1: peak at |dx| or |dy| == radius, the true offset may lie beyond */
+void dsss_reg_params_default(dsss_reg_params*);
+/* ids, rpy6, ping_off, the grid and the state rules are those of dsss_mosaic_consistency; pair_a[k], pair_b[k] are frame ids that both
+ * occur in ids; the parameters may be NULL (the defaults).  sums_host: npairs x (2 radius + 1)^2 x 6, may be NULL.
+ * DSSS_E_ARG: a pair member not in ids, a == b, radius outside 0..16, min_cells < 1, npairs < 0, out_host NULL with npairs > 0
+ * (npairs == 0 is valid).  DSSS_E_STATE: frames not extracted, or a communicator of more than one rank.  DSSS_E_CAPACITY: a cell
+ * received more than 2^24 samples of one frame.  The results are those of dsss_mosaic_register_peak on the pair's table.            */
+int  dsss_mosaic_register(dsss_ctx*, const int* ids, int n, const double* rpy6, const int* ping_off, const dsss_mosaic_params*,
+                          const int* pair_a, const int* pair_b, int npairs, const dsss_reg_params*,
+                          dsss_reg_result* out_host /* npairs */, uint64_t* sums_host /* npairs x (2r+1)^2 x 6, may be NULL */);
+/* pure host arithmetic, no context (as dsss_mosaic_grid): the score, peak, tie and sub-cell rules on a table of (2 radius + 1)^2 x 6
+ * sums.  DSSS_E_ARG: a NULL pointer, radius outside 0..16, min_cells < 1, cell <= 0 or not finite                                   */
+int  dsss_mosaic_register_peak(const uint64_t* sums, int radius, int min_cells, double cell, dsss_reg_result* out);
+
 /* ------------------------------------------------------------------ instrumentation
  * accumulated GPU time (ms, HIP events on the context stream) and launch count per kernel family        */
 #define DSSS_K_ROW_REDUCE   0   /* row_reduce_kernel: one f64 read of the waterfall */
