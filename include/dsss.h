@@ -222,7 +222,10 @@ int dsss_posegraph_update(dsss_ctx*, int nframes, double* poses12_host, double* 
  * estimates: one or two LM trials) gives the batch optimum, which is all the reference ever reads (calculateEstimate after the loop, :279).
 * poses12_host / rpy6_host (either may be NULL: nothing is downloaded) receive ALL pings of frames 0 .. nframes-1.  Falls back to the global
  * form while there is no frozen part (nframes <= window_frames); a window that would start in frames no update has covered (window_frames = 1:
- * the new frame alone) is extended backwards to the last frame that has an estimate, which anchors it.  Loop closures must end in the later ping (the pipeline's do).          */
+ * the new frame alone) is extended backwards to the last frame that has an estimate, which anchors it.  Loop closures must end in the later ping (the pipeline's do).
+ * The window is its own LM problem: its prior (sigma 1e-6) measures the PREVIOUS ESTIMATE of its first ping, not that ping's dead-reckoned
+ * pose; pings no update has covered start at DR o noise and draw their noise by WINDOW-LOCAL index (ping i of the window takes the draws
+ * 6 i .. 6 i + 5 of the one normal stream, as ping i of a batch solve does).                                                          */
 int dsss_posegraph_update_window(dsss_ctx*, int nframes, int window_frames, double* poses12_host, double* rpy6_host, double* stats4_host);
 int dsss_posegraph_reset(dsss_ctx*);
 int dsss_posegraph_online_edges(dsss_ctx*);      /* loop closures accumulated so far (>= 0) */

@@ -476,6 +476,41 @@ def pg_solve(dr, edges, params=None, solver="envelope", refine=0, log=None, full
     return out, stats
 
 
+PG_TRACE_COLS = 5          # ORC_PG_TRACE_COLS: err before the trial, err after it, costChange / linChange, lambda, accepted
+
+
+def pg_solve_init(dr, edges, params=None, x0=None, prior=None, solver="envelope", refine=0, log=None, full_refine=0, trace_cap=256):
+    """orc_pg_solve_init: the LM of pg_solve started at x0 (n_init x 12: the first n_init poses; the others start at DR o noise or DR)
+    with the prior measuring `prior` (12 doubles; None: DR[0]).  Returns (poses, stats, trace): trace holds one row of PG_TRACE_COLS per
+    trial whose linearised change was non-negative, in order.  solver as in pg_solve."""
+    dr = np.ascontiguousarray(dr, np.float64).reshape(-1, 6)
+    p = params or pg_params()
+    out = np.zeros((len(dr), 12), np.float64); stats = np.zeros(4, np.float64)
+    edges = np.ascontiguousarray(edges)
+    x0 = np.zeros((0, 12)) if x0 is None else np.ascontiguousarray(x0, np.float64).reshape(-1, 12)
+    assert len(x0) <= len(dr)
+    prior = None if prior is None else np.ascontiguousarray(prior, np.float64).reshape(12)
+    trace = np.full((max(int(trace_cap), 1), PG_TRACE_COLS), np.nan)
+    L = lib()
+    L.orc_pg_set_reduced_solver.argtypes = [C.c_void_p]
+    L.orc_pg_solve_init.argtypes = [c_dp, C.c_int, C.POINTER(LCEdge), C.c_int, C.POINTER(PGParams), c_dp, C.c_int, c_dp, c_dp, C.c_int, c_dp, c_dp]
+    cb = None
+    if solver == "sparse":
+        cb = _make_reduced_solver(refine, log)
+        L.orc_pg_set_reduced_solver(C.cast(cb, C.c_void_p))
+    else:
+        assert solver == "envelope"
+    L.orc_pg_set_full_refine(int(full_refine))
+    try:
+        L.orc_pg_solve_init(dp(dr), len(dr), edges.ctypes.data_as(C.POINTER(LCEdge)), len(edges), C.byref(p),
+                            dp(x0) if len(x0) else None, len(x0), dp(prior) if prior is not None else None,
+                            dp(trace), len(trace), dp(out), dp(stats))
+    finally:
+        L.orc_pg_set_reduced_solver(None)
+        L.orc_pg_set_full_refine(0)
+    return out, stats, trace[~np.isnan(trace[:, 0])].copy()
+
+
 def pg_error_at(dr, edges, poses12):
     """0.5 sum |r|^2 of the pose graph (dr, edges) at the poses `poses12` (total x 12)"""
     dr = np.ascontiguousarray(dr, np.float64).reshape(-1, 6)

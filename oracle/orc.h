@@ -232,6 +232,12 @@ int orc_pg_select_lc(int F, const int* frame_rows, int npairs, const int* pair_s
 /* batch LM over all pings; dr = total x 6 (roll,pitch,yaw,x,y,z); out poses total x 12 (R row-major, t) */
 int orc_pg_solve(const double* dr, int total, const orc_lc_edge* edges, int ne, const orc_pg_params* p,
                  double* out12, double* stats /* [iters, err0, err1, lambda] */);
+/* the same LM from a caller-supplied start (poses 0..n_init-1 = x0_12) and prior (prior12, or DR[0] when NULL), with an optional
+ * per-trial trace: one update of the online protocol (see orc_posegraph.c).  orc_pg_solve is this with n_init = 0 and NULLs. */
+#define ORC_PG_TRACE_COLS 5   /* err before, err after, costChange / linChange, lambda, accepted */
+int orc_pg_solve_init(const double* dr, int total, const orc_lc_edge* edges, int ne, const orc_pg_params* p,
+                      const double* x0_12, int n_init, const double* prior12, double* trace, int trace_cap,
+                      double* out12, double* stats /* [iters, err0, err1, lambda] */);
 /* the same graph's LM objective evaluated at given poses (total x 12), for full-size checks of a solver's answer */
 /* optional second linear solver of the reduced (separator) system of orc_pg_solve: see orc_posegraph.c */
 typedef int (*orc_pg_reduced_solver_fn)(int ns, int nblk, const int* bi, const int* bj, const double* blk36, double* rhs);

@@ -351,8 +351,15 @@ static int pg_solve(const pg_t* g, double lambda, double* delta, const double* n
     return fail ? -1 : 0;
 }
 
-int orc_pg_solve(const double* dr, int total, const orc_lc_edge* edges, int ne, const orc_pg_params* p,
-                 double* out12, double* stats)
+/* The LM of orc_pg_solve with a caller-supplied start and prior: one update of the online protocol as a fully defined problem.
+ * Poses 0 .. n_init-1 start at x0_12 (n_init x 12, R row-major then t); poses n_init .. total-1 start at DR o noise (add_noise) or
+ * at DR, pose i drawing z[6i .. 6i+5] of the ONE orc_normal_fill(z, 6 total) stream whatever n_init is.  The prior measures prior12
+ * (12 doubles) when it is not NULL, DR[0] otherwise.  trace (optional, trace_cap rows of ORC_PG_TRACE_COLS doubles) receives one row
+ * per trial whose linearised change was non-negative -- every accept / stop decision of the loop: [err before the trial, err after
+ * it, costChange / linChange, lambda of the trial, 1 if accepted else 0]; rows beyond the last trial are left untouched. */
+int orc_pg_solve_init(const double* dr, int total, const orc_lc_edge* edges, int ne, const orc_pg_params* p,
+                      const double* x0_12, int n_init, const double* prior12, double* trace, int trace_cap,
+                      double* out12, double* stats)
 {
     const double PI = ORC_PI_REF;
     /* odometry sigmas (optimizer.cpp:24,28) */
@@ -383,8 +390,14 @@ int orc_pg_solve(const double* dr, int total, const orc_lc_edge* edges, int ne, 
         }
         free(z);
     } else memcpy(X, DR, sizeof(orc_pose) * n);
+    if (n_init > n) n_init = n;
+    for (int i = 0; i < n_init; ++i) {
+        memcpy(X[i].R, x0_12 + (size_t)i * 12, sizeof(double) * 9);
+        memcpy(X[i].t, x0_12 + (size_t)i * 12 + 9, sizeof(double) * 3);
+    }
     /* factors */
     g.f[0].i = -1; g.f[0].j = 0; g.f[0].meas = DR[0];
+    if (prior12) { memcpy(g.f[0].meas.R, prior12, sizeof(double) * 9); memcpy(g.f[0].meas.t, prior12 + 9, sizeof(double) * 3); }
     for (int k = 0; k < 6; ++k) g.f[0].w[k] = 1.0 / 0.000001;
     for (int i = 1; i < n; ++i) {
         g.f[i].i = i - 1; g.f[i].j = i;
@@ -400,7 +413,7 @@ int orc_pg_solve(const double* dr, int total, const orc_lc_edge* edges, int ne, 
     }
     /* LM (same loop as the mini problems) */
     double lambda = p->lambda0;
-    int iters = 0;
+    int iters = 0, ntrace = 0;
     double err = pg_error(&g, X);
     double err0 = err, cur;
     double* delta = (double*)malloc(sizeof(double) * 6 * (size_t)n);
@@ -462,6 +475,10 @@ int orc_pg_solve(const double* dr, int total, const orc_lc_edge* edges, int ne, 
                     double costChange = err - newErr;
                     if (linChange > 2.220446049250313e-16 * oldLin) success = (costChange / linChange) > p->min_fidelity;
                     if (fabs(costChange) < p->rel_tol * err) stop = 1;
+                    if (trace && ntrace < trace_cap) {
+                        double* row = trace + (size_t)ntrace++ * ORC_PG_TRACE_COLS;
+                        row[0] = err; row[1] = newErr; row[2] = costChange / linChange; row[3] = lambda; row[4] = success;
+                    }
                 }
             }
             if (success) { memcpy(X, Xn, sizeof(orc_pose) * n); err = newErr; lambda /= p->lambda_factor; ++iters; break; }
@@ -476,6 +493,12 @@ int orc_pg_solve(const double* dr, int total, const orc_lc_edge* edges, int ne, 
     if (stats) { stats[0] = iters; stats[1] = err0; stats[2] = err; stats[3] = lambda; }
     free(delta); free(g.f); free(g.r); free(g.Ji); free(g.Jj); free(DR); free(X); free(Xn);
     return iters;
+}
+
+int orc_pg_solve(const double* dr, int total, const orc_lc_edge* edges, int ne, const orc_pg_params* p,
+                 double* out12, double* stats)
+{
+    return orc_pg_solve_init(dr, total, edges, ne, p, NULL, 0, NULL, NULL, 0, out12, stats);
 }
 
 /* The LM objective 0.5 sum |r|^2 of the graph orc_pg_solve builds from (dr, edges), evaluated at the poses `x12` (total x 12,
