@@ -21,6 +21,19 @@ void dsss_prof_flush(dsss_ctx* c)
     c->prof.pending.clear();
 }
 
+// the one reader of the environment outside the pose graph (pg_switches_read, dsss_pg_sym.cpp, is the other)
+dsss_switches dsss_switches_read()
+{
+    dsss_switches sw;
+    if (const char* v = getenv("DSSS_EX_SCRATCH_MB")) sw.ex_scratch_mb = (size_t)std::max(1, atoi(v));
+    if (const char* v = getenv("DSSS_EX_UPLOAD_BATCH")) sw.ex_upload_batch = std::max(1, atoi(v));
+    sw.ex_verbose = getenv("DSSS_EX_VERBOSE") != nullptr;
+    if (const char* v = getenv("DSSS_FS_THREADS")) sw.fs_threads = atoi(v);
+    if (const char* v = getenv("DSSS_MT_GRID")) sw.mt_grid = atoi(v) != 0;
+    sw.sift_hist_dump = getenv("DSSS_SIFT_HIST_DUMP");
+    return sw;
+}
+
 extern "C" {
 
 void dsss_mask_params_default(dsss_mask_params* p) { p->factor = 2.5; p->width = 10; p->r = 6; p->side = 150; }
@@ -444,6 +457,7 @@ int dsss_frames_set(dsss_ctx* c, int n, const int* ids, const double* const* raw
     if (!c || n < 0 || (n > 0 && (!ids || !N || !M || !pose6 || !alt || !grange))) return DSSS_E_ARG;
     if (n == 0) return DSSS_OK;
     const auto t0 = std::chrono::steady_clock::now();
+    const dsss_switches sw = dsss_switches_read();
     HIPCHK(c, hipSetDevice(c->device));
     int rc = dsss_ensure_store(c); if (rc) return rc;
     // the geometry of the whole call goes through ONE pinned staging area and ONE upload (200 separate 116 KB copies
@@ -490,10 +504,9 @@ int dsss_frames_set(dsss_ctx* c, int n, const int* ids, const double* const* raw
     }
     HIPCHK(c, hipEventRecord(c->xev[0], c->stream));        // whatever is queued so far may still read the buffer's previous contents
     const auto t1 = std::chrono::steady_clock::now();
-    if (raw) dsss_extract_eager(c, ids, n);
+    if (raw) dsss_extract_eager(c, ids, n, sw);
     const auto t2 = std::chrono::steady_clock::now();
-    const int T_env = getenv("DSSS_FS_THREADS") ? atoi(getenv("DSSS_FS_THREADS")) : 0;
-    const int T = T_env > 0 ? T_env : (n >= 16 ? 4 : 1);       // (eight threads were slower than four: the pointer-attribute queries of frame_fill serialise)
+    const int T = sw.fs_threads > 0 ? sw.fs_threads : (n >= 16 ? 4 : 1);       // (eight threads were slower than four: the pointer-attribute queries of frame_fill serialise)
     std::vector<hipError_t> errs(T, hipSuccess);
     auto work = [&](int t) { for (int i = t; i < n; i += T) { const hipError_t e = frame_fill(c, ids[i], G.h + off[i], pose6[i], alt[i], grange[i]); if (e != hipSuccess) errs[t] = e; } };
     dsss_pool_run(T, work);
@@ -503,7 +516,7 @@ int dsss_frames_set(dsss_ctx* c, int n, const int* ids, const double* const* raw
     HIPCHK(c, hipMemcpyAsync(G.d, G.h, total * sizeof(double), hipMemcpyHostToDevice, c->xs[1]));
     HIPCHK(c, hipEventRecord(G.ev, c->xs[1]));
     HIPCHK(c, hipStreamWaitEvent(c->stream, G.ev, 0));      // every later consumer of the geometry is ordered behind the upload
-    if (getenv("DSSS_EX_VERBOSE")) { auto us = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
+    if (sw.ex_verbose) { auto us = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
         fprintf(stderr, "[dsss frames_set] %d frames in %.1f us: bookkeeping %.1f, eager extraction queued %.1f, geometry packed (%d threads) %.1f, upload queued %.1f\n", n, us(t0, std::chrono::steady_clock::now()), us(t0, t1), us(t1, t2), T, us(t2, t3), us(t3, std::chrono::steady_clock::now())); }
     return DSSS_OK;
 }

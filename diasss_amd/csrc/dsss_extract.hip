@@ -1055,104 +1055,122 @@ static ex_layout make_layout(int N, const level_geom& g, int kcap, bool sift)
 
 #define EX_BATCH 256
 
-// extraction of a list of frames, batched: every stage is one launch for the whole batch (the pyramid: one per level),
-// about twenty launches and one host synchronisation per batch of up to EX_BATCH frames.
-// phase 0: the whole extraction.  Phases 1 and 2 split it at the one kernel that needs the frame GEOMETRY (mask_filter_kernel: the geo
-// sample of the surviving keypoints): phase 1 enqueues everything before it and returns without waiting, phase 2 enqueues the rest and
-// finishes -- dsss_frames_set starts phase 1 while it still packs and uploads the geometry (dsss_extract_eager below), as the
+// the four tables of a batch of up to B frames: quadtree instances (at 0), quadtree frames, the batch table, error flags.  They lie behind
+// the slots of ex_scratch on the device and, at the same offsets, at the start of ex_pinned on the host; all before `err` is uploaded
+struct ex_tables {
+    size_t fr, exf, err, total;
+    explicit ex_tables(size_t B) : fr(align_up(sizeof(qt_inst) * B * DSSS_MAX_LEVELS, 256)), exf(fr + align_up(sizeof(qt_frame) * B, 256)),
+                                   err(exf + align_up(sizeof(ex_frame) * B, 256)), total(err + align_up(sizeof(int) * B, 256)) {}
+};
+// what the launches of one batch are sized by: the frames [b0, b0 + nb) of the list and the largest of each of their dimensions
+struct ex_batch {
+    int b0 = 0, nb = 0, maxN = 0, max_levels = 0, max_cw = 8, max_ch = 8; size_t max_tot = 0; double w_tot = 0;
+    int max_rows[DSSS_MAX_LEVELS] = { 0 }, max_cols[DSSS_MAX_LEVELS] = { 0 }, lev_cnt[DSSS_MAX_LEVELS] = { 0 };      // lev_cnt[l]: frames that have level l
+};
+
+// Extraction of a list of frames, batched: every stage is one launch for the whole batch (the pyramid: one per level), about twenty
+// launches and one host synchronisation per batch of up to EX_BATCH frames.  The stages are cut at the one kernel that needs the frame
+// GEOMETRY (mask_filter_kernel: the geo sample of the surviving keypoints): enqueue_head is everything before it, enqueue_tail the rest.
+// Three callers: run() is the whole extraction; start() enqueues the head and returns without waiting, resume() enqueues the tail of a
+// started list and finishes -- dsss_frames_set starts while it still packs and uploads the geometry (dsss_extract_eager below), as the
 // reference's Frame constructor runs DetectFeature itself (frame.cpp:45-52).  Both need the frames to fit one batch, images in HBM.
-static int extract_frames_impl(dsss_ctx* c, const int* ids, int n, bool keep_taps, int phase = 0)
-{
-    if (n <= 0) return DSSS_OK;
-    const bool doA = phase != 2, doB = phase != 1;
-    const bool sift = c->op.descriptor == DSSS_DESC_SIFT128;
-    int rc = sift ? dsss_ensure_sift_store(c) : dsss_ensure_store(c); if (rc) return rc;
-    std::vector<level_geom*> G(n);
-    size_t slot_bytes = 0;
-    std::vector<ex_layout> Ls(n);
-    for (int i = 0; i < n; ++i) {
-        dsss_frame& f = c->frames[ids[i]];
-        if (!f.has_geom || !f.has_raw) DSSS_FAIL(c, DSSS_E_STATE, "frame %d has no raw image (dsss_frame_set with raw != NULL first)", ids[i]);
-        rc = get_geom(c, f.N, f.M, &G[i]); if (rc) return rc;
-        rc = ensure_frame_images(c, f, *G[i]); if (rc) return rc;
-        Ls[i] = make_layout(f.N, *G[i], c->kcap, sift);
-        slot_bytes = std::max(slot_bytes, Ls[i].total);
+struct ex_run {
+    dsss_ctx* const c; const int* const ids; const int n; const dsss_switches& sw; const bool sift; const hipStream_t st;      // ---- the call
+    // ---- the plan: per-frame geometry tables and slot layouts, frames per batch
+    std::vector<level_geom*> G; std::vector<ex_layout> Ls; size_t slot_bytes = 0; int B = 1; bool any_pending = false;
+    // ---- the reserved memory: slots and tables on the device, the tables and the downloads in pinned host memory
+    ex_tables T{ 0 }; char *S0, *T0, *P0; qt_inst *d_inst, *h_inst; qt_frame *d_fr, *h_fr; ex_frame *d_exf, *h_exf;
+    int *d_errs, *h_err, *h_nkp;                      // h_err: [B] error flags, then h_nkp: [max_frames] keypoint counts
+    ex_run(dsss_ctx* c_, const int* ids_, int n_, const dsss_switches& sw_) : c(c_), ids(ids_), n(n_), sw(sw_), sift(c_->op.descriptor == DSSS_DESC_SIFT128), st(c_->stream) {}
+
+    int run(bool keep_taps) {
+        int rc = plan(); if (rc) return rc;
+        if (any_pending) HIPCHK(c, upload(0, 0));
+        if ((rc = reserve())) return rc;
+        const bool exv = sw.ex_verbose && any_pending;
+        double tv_issue = 0, tv_sync = 0, tv_wait = 0; int tv_n = 0; auto tv_now = [] { return std::chrono::steady_clock::now(); };
+        auto us = [](auto a, auto b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
+        for (int b0 = 0, bk = 0; b0 < n; b0 += B, ++bk) {
+            const auto tv0 = tv_now();
+            if (any_pending && b0 + B < n) HIPCHK(c, upload(b0 + B, bk + 1));             // next batch's images start moving now
+            if (any_pending) HIPCHK(c, hipStreamWaitEvent(st, up_ev(bk), 0));              // this batch's images are in HBM before its kernels read them
+            ex_batch bt = { b0, std::min(B, n - b0) };
+            if ((rc = fill_tables(bt)) || (rc = enqueue_head(bt)) || (rc = enqueue_tail(bt, b0 + B >= n))) return rc;
+            const auto tv1 = tv_now();
+            if (exv) (void)hipEventSynchronize(up_ev(bk));
+            const auto tv2 = tv_now();
+            if ((rc = finish(bt))) return rc;
+            if (exv) { tv_issue += us(tv0, tv1); tv_wait += us(tv1, tv2); tv_sync += us(tv2, tv_now()); ++tv_n; }
+            if (keep_taps && (rc = read_taps(bt))) return rc;
+        }
+        if (exv && tv_n) fprintf(stderr, "[dsss extract] %d batches of %d: per batch host issue %.0f us, wait for the batch's upload %.0f us, kernels after it %.0f us\n", tv_n, B, tv_issue / tv_n, tv_wait / tv_n, tv_sync / tv_n);
+        return DSSS_OK;
     }
-    // slots of one batch share one scratch allocation: bound it (24 GB) instead of the frame count alone
-    // (DSSS_EX_SCRATCH_MB: tools/emulate_ranks.py puts the contexts of EIGHT ranks on one device)
-    const size_t scratch_mb = getenv("DSSS_EX_SCRATCH_MB") ? (size_t)std::max(1, atoi(getenv("DSSS_EX_SCRATCH_MB"))) : 24576;
-    int B = (int)std::max<size_t>(1, std::min<size_t>(std::min(n, EX_BATCH), (scratch_mb << 20) / std::max<size_t>(slot_bytes, 1)));
-    // frames whose page-locked host image has not been uploaded yet: smaller batches, the upload of batch k+1 runs on the copy
-    // stream (xs[1]) under the kernels of batch k (PCIe: 16 B per pixel against ~6 ns of kernels per pixel, so the copies set the pace)
-    bool any_pending = false;
-    for (int i = 0; i < n; ++i) any_pending = any_pending || c->frames[ids[i]].raw_pending;
-    if (any_pending) { const int sb = getenv("DSSS_EX_UPLOAD_BATCH") ? std::max(1, atoi(getenv("DSSS_EX_UPLOAD_BATCH"))) : 8; B = std::min(B, sb); }
-    if (phase != 0 && (any_pending || B < n)) DSSS_FAIL(c, DSSS_E_STATE, "two-phase extraction needs one batch of device-resident images");
-    hipEvent_t up_ev[2] = { c->xev[1], c->xev[2] };
-    auto upload_batch = [&](int b0, hipEvent_t ev) -> hipError_t {
+    int start() {
+        int rc = plan(); if (rc || (rc = reserve()) || (rc = one_resident_batch())) return rc;
+        ex_batch bt = { 0, n };
+        return (rc = fill_tables(bt)) ? rc : enqueue_head(bt);
+    }
+    int resume() {      // the tail reads the device copy of the tables that start() uploaded: nothing is filled, the pinned tables are not touched
+        int rc = plan(); if (rc || (rc = reserve()) || (rc = one_resident_batch())) return rc;
+        const ex_batch bt = { 0, n };
+        return (rc = enqueue_tail(bt, true)) ? rc : finish(bt);
+    }
+    int one_resident_batch() { if (any_pending || B < n) DSSS_FAIL(c, DSSS_E_STATE, "two-phase extraction needs one batch of device-resident images"); return DSSS_OK; }
+    int plan() {      // the store, per-geometry tables and per-frame layouts, the batch size
+        int rc = sift ? dsss_ensure_sift_store(c) : dsss_ensure_store(c); if (rc) return rc; G.resize(n); Ls.resize(n);
+        for (int i = 0; i < n; ++i) {
+            dsss_frame& f = c->frames[ids[i]];
+            if (!f.has_geom || !f.has_raw) DSSS_FAIL(c, DSSS_E_STATE, "frame %d has no raw image (dsss_frame_set with raw != NULL first)", ids[i]);
+            if ((rc = get_geom(c, f.N, f.M, &G[i])) || (rc = ensure_frame_images(c, f, *G[i]))) return rc;
+            Ls[i] = make_layout(f.N, *G[i], c->kcap, sift);
+            slot_bytes = std::max(slot_bytes, Ls[i].total); any_pending = any_pending || f.raw_pending;
+        }
+        // slots of one batch share one scratch allocation: bound it (24 GB) instead of the frame count alone
+        // (DSSS_EX_SCRATCH_MB: tools/emulate_ranks.py puts the contexts of EIGHT ranks on one device)
+        B = (int)std::max<size_t>(1, std::min<size_t>(std::min(n, EX_BATCH), (sw.ex_scratch_mb << 20) / std::max<size_t>(slot_bytes, 1)));
+        // frames whose page-locked host image has not been uploaded yet: smaller batches, the upload of batch k+1 runs on the copy
+        // stream (xs[1]) under the kernels of batch k (PCIe: 16 B per pixel against ~6 ns of kernels per pixel, so the copies set the pace)
+        if (any_pending) B = std::min(B, sw.ex_upload_batch);
+        return DSSS_OK;
+    }
+    int reserve() {      // grow the scratch and its pinned mirror, carve the tables out of both
+        T = ex_tables(B);
+        const size_t need = slot_bytes * B + T.total, pin_need = T.total + sizeof(int) * ((size_t)B + c->max_frames) + 64;
+        if (c->ex_scratch_bytes < need) {
+            HIPCHK(c, hipStreamSynchronize(c->stream)); hipFree(c->ex_scratch); c->ex_scratch = nullptr; c->ex_scratch_bytes = 0;
+            HIPCHK(c, hipMalloc(&c->ex_scratch, need)); c->ex_scratch_bytes = need;
+        }
+        if (c->ex_pinned_bytes < pin_need) {
+            HIPCHK(c, hipStreamSynchronize(c->stream)); if (c->ex_pinned) hipHostFree(c->ex_pinned); c->ex_pinned = nullptr; c->ex_pinned_bytes = 0;
+            HIPCHK(c, hipHostMalloc(&c->ex_pinned, pin_need, hipHostMallocDefault)); c->ex_pinned_bytes = pin_need;
+        }
+        S0 = (char*)c->ex_scratch; T0 = S0 + slot_bytes * B; P0 = (char*)c->ex_pinned;
+        d_inst = (qt_inst*)T0; d_fr = (qt_frame*)(T0 + T.fr); d_exf = (ex_frame*)(T0 + T.exf); d_errs = (int*)(T0 + T.err);
+        h_inst = (qt_inst*)P0; h_fr = (qt_frame*)(P0 + T.fr); h_exf = (ex_frame*)(P0 + T.exf); h_err = (int*)(P0 + T.total); h_nkp = h_err + B;
+        return DSSS_OK;
+    }
+    // ---- upload: the page-locked host images of the batch at b0 go up on the copy stream, one of two events in turn fires behind them
+    hipEvent_t up_ev(int bk) const { return c->xev[1 + (bk & 1)]; }
+    hipError_t upload(int b0, int bk) {
         hipError_t e = hipSuccess;
-        for (int s2 = b0; s2 < std::min(n, b0 + B) && e == hipSuccess; ++s2) {
-            dsss_frame& f = c->frames[ids[s2]];
-            if (!f.raw_pending) continue;
-            e = hipMemcpyAsync(f.raw_owned, f.raw_host, (size_t)f.N * f.M * sizeof(double), hipMemcpyHostToDevice, c->xs[1]);
+        for (int s = b0; s < std::min(n, b0 + B) && e == hipSuccess; ++s) {
+            dsss_frame& f = c->frames[ids[s]];
+            if (f.raw_pending) e = hipMemcpyAsync(f.raw_owned, f.raw_host, (size_t)f.N * f.M * sizeof(double), hipMemcpyHostToDevice, c->xs[1]);
             f.raw_pending = false;
         }
-        if (e == hipSuccess) e = hipEventRecord(ev, c->xs[1]);
-        return e;
-    };
-    if (any_pending) HIPCHK(c, upload_batch(0, up_ev[0]));
-    const size_t inst_bytes = align_up(sizeof(qt_inst) * (size_t)B * DSSS_MAX_LEVELS, 256), qfr_bytes = align_up(sizeof(qt_frame) * (size_t)B, 256);
-    const size_t exf_bytes = align_up(sizeof(ex_frame) * (size_t)B, 256), err_bytes = align_up(sizeof(int) * (size_t)B, 256);
-    const size_t tab_bytes = inst_bytes + qfr_bytes + exf_bytes + err_bytes;
-    const size_t need = slot_bytes * B + tab_bytes;
-    if (c->ex_scratch_bytes < need) {
-        HIPCHK(c, hipStreamSynchronize(c->stream)); hipFree(c->ex_scratch); c->ex_scratch = nullptr; c->ex_scratch_bytes = 0;
-        HIPCHK(c, hipMalloc(&c->ex_scratch, need)); c->ex_scratch_bytes = need;
+        return e == hipSuccess ? hipEventRecord(up_ev(bk), c->xs[1]) : e;
     }
-    const size_t pin_need = tab_bytes + sizeof(int) * ((size_t)B + c->max_frames) + 64;
-    if (c->ex_pinned_bytes < pin_need) {
-        HIPCHK(c, hipStreamSynchronize(c->stream)); if (c->ex_pinned) hipHostFree(c->ex_pinned); c->ex_pinned = nullptr; c->ex_pinned_bytes = 0;
-        HIPCHK(c, hipHostMalloc(&c->ex_pinned, pin_need, hipHostMallocDefault)); c->ex_pinned_bytes = pin_need;
-    }
-    char* S0 = (char*)c->ex_scratch;
-    char* T0 = S0 + slot_bytes * B;                            // device tables: quadtree instances, quadtree frames, batch table, error flags
-    qt_inst* d_inst = (qt_inst*)T0;
-    qt_frame* d_fr = (qt_frame*)(T0 + inst_bytes);
-    ex_frame* d_exf = (ex_frame*)(T0 + inst_bytes + qfr_bytes);
-    int* d_errs = (int*)(T0 + inst_bytes + qfr_bytes + exf_bytes);
-    char* P0 = (char*)c->ex_pinned;                            // the same tables in pinned host memory, one upload per batch
-    qt_inst* h_inst = (qt_inst*)P0;
-    qt_frame* h_fr = (qt_frame*)(P0 + inst_bytes);
-    ex_frame* h_exf = (ex_frame*)(P0 + inst_bytes + qfr_bytes);
-    int* h_err = (int*)(P0 + tab_bytes);                       // [B] error flags, then [max_frames] keypoint counts
-    int* h_nkp = h_err + B;
-    const hipStream_t st = c->stream;
-
-    const bool exv = getenv("DSSS_EX_VERBOSE") != nullptr && any_pending;
-    double tv_issue = 0, tv_sync = 0, tv_wait = 0; int tv_n = 0;
-    auto tv_now = [] { return std::chrono::steady_clock::now(); };
-    for (int b0 = 0, bk = 0; b0 < n; b0 += B, ++bk) {
-        const int nb = std::min(B, n - b0);
-        const auto tv0 = tv_now();
-        if (any_pending) {
-            if (b0 + B < n) HIPCHK(c, upload_batch(b0 + B, up_ev[(bk + 1) & 1]));      // next batch's images start moving now
-            HIPCHK(c, hipStreamWaitEvent(st, up_ev[bk & 1], 0));                       // this batch's images are in HBM before its kernels read them
-        }
-        int maxN = 0, maxNM4 = 0, max_cells = 0, max_levels = 0, max_cw = 8, max_ch = 8;
-        int lev_cnt[DSSS_MAX_LEVELS] = { 0 };           // frames that have level l
-        size_t max_tot = 0;
-        int max_rows[DSSS_MAX_LEVELS] = { 0 }, max_cols[DSSS_MAX_LEVELS] = { 0 };
-        double w_tot = 0;
-        for (int s = 0; s < nb; ++s) {
-            const int id = ids[b0 + s];
-            dsss_frame& f = c->frames[id];
-            const level_geom& g = *G[b0 + s];
-            const ex_layout& L = Ls[b0 + s];
-            char* S = S0 + slot_bytes * s;
-            ex_frame& e = h_exf[s];
-            e.raw = f.raw; e.N = f.N; e.M = f.M;
+    int fill_tables(ex_batch& bt) {      // the ex_frame / qt_inst / qt_frame rows of one batch in the pinned tables, and the batch's maxima
+        // The pinned tables may still feed the upload of the previous enqueue_head.  After run() and after resume() that upload was
+        // synchronised with its batch, so the event has fired; only a start() that was DROPPED (dsss_frames_set, then the extraction
+        // of another list or a second dsss_frames_set) leaves a copy in flight that this can actually wait for
+        if (c->ex_tab_uploaded) HIPCHK(c, hipEventSynchronize(c->ex_side_ev[2]));
+        for (int s = 0; s < bt.nb; ++s) {
+            const int id = ids[bt.b0 + s]; dsss_frame& f = c->frames[id]; const level_geom& g = *G[bt.b0 + s]; const ex_layout& L = Ls[bt.b0 + s];
+            char* S = S0 + slot_bytes * s; ex_frame& e = h_exf[s];
+            e.raw = f.raw; e.N = f.N; e.M = f.M; e.mask = f.mask; e.nlevels = g.nlevels; e.pose6 = f.pose6; e.gr = f.gr;
             e.rowsum = (double*)(S + L.rowsum); e.rowmin = (double*)(S + L.rowmin); e.stats = (double*)(S + L.stats);
-            e.mask = f.mask; e.nlevels = g.nlevels;
             for (int l = 0; l < DSSS_MAX_LEVELS; ++l) { e.lvl[l] = l < g.nlevels ? f.lvl[l] : nullptr; e.rows[l] = l < g.nlevels ? g.rows[l] : 0; e.cols[l] = l < g.nlevels ? g.cols[l] : 0; }
             e.cells = g.d_cells; e.ncells = (int)g.cells.size(); e.cell_cap = g.cell_cap;
             for (int l = 0; l <= DSSS_MAX_LEVELS; ++l) e.cell_begin[l] = g.cell_begin[std::min(l, g.nlevels)];
@@ -1162,163 +1180,145 @@ static int extract_frames_impl(dsss_ctx* c, const int* ids, int n, bool keep_tap
             for (int l = 0; l < DSSS_MAX_LEVELS; ++l) { e.xt[l] = g.d_xt[l]; e.yt[l] = g.d_yt[l]; }
             e.kptmp = (dsss_kp*)(S + L.kptmp); e.dtmp = (uint8_t*)(S + L.dtmp);
             e.d128tmp = sift ? (uint8_t*)(S + L.d128tmp) : nullptr; e.d128out = sift ? c->desc128 + (size_t)id * c->kcap * 128 : nullptr;
-            e.pose6 = f.pose6; e.gr = f.gr;
             e.err = d_errs + s; e.kout = c->kps + (size_t)id * c->kcap; e.dout = c->desc + (size_t)id * c->kcap * 32; e.geo = c->geo + (size_t)id * c->kcap * 2; e.count = c->nkp_dev + id;
-            maxN = std::max(maxN, f.N); max_tot = std::max(max_tot, (size_t)f.N * f.M); max_cells = std::max(max_cells, e.ncells); max_levels = std::max(max_levels, g.nlevels);
-            max_cw = std::max(max_cw, g.cell_wmax); max_ch = std::max(max_ch, g.cell_hmax);
-            for (int l = 0; l < g.nlevels; ++l) { max_rows[l] = std::max(max_rows[l], g.rows[l]); max_cols[l] = std::max(max_cols[l], g.cols[l]); }
-            w_tot += (double)f.N * f.M;
+            bt.maxN = std::max(bt.maxN, f.N); bt.max_tot = std::max(bt.max_tot, (size_t)f.N * f.M); bt.max_levels = std::max(bt.max_levels, g.nlevels);
+            bt.max_cw = std::max(bt.max_cw, g.cell_wmax); bt.max_ch = std::max(bt.max_ch, g.cell_hmax); bt.w_tot += (double)f.N * f.M;
+            for (int l = 0; l < g.nlevels; ++l) { bt.max_rows[l] = std::max(bt.max_rows[l], g.rows[l]); bt.max_cols[l] = std::max(bt.max_cols[l], g.cols[l]); }
             // quadtree descriptors, level-major: the instances of level l are one launch
+            int* const out_idx = (int*)(S + L.out_idx); int* const out_n = (int*)(S + L.out_n);
             for (int l = 0; l < g.nlevels; ++l) {
-                qt_inst& q = h_inst[(size_t)l * B + lev_cnt[l]++];
-                q.offs = e.offs; q.cell_begin = g.cell_begin[l]; q.cell_end = g.cell_begin[l + 1];
-                q.xs = e.xs; q.ys = e.ys; q.rs = e.rs;
+                qt_inst& q = h_inst[(size_t)l * B + bt.lev_cnt[l]++];
+                q.offs = e.offs; q.cell_begin = g.cell_begin[l]; q.cell_end = g.cell_begin[l + 1]; q.xs = e.xs; q.ys = e.ys; q.rs = e.rs;
                 q.W = (g.cols[l] - EDGE_T + 3) - (EDGE_T - 3); q.H = (g.rows[l] - EDGE_T + 3) - (EDGE_T - 3); q.quota = g.quota[l];
                 q.keys0 = (unsigned long long*)(S + L.keys0); q.keys1 = (unsigned long long*)(S + L.keys1); q.work = (int*)(S + L.work[l]);
-                q.list_cap = L.list_cap[l]; q.pool_cap = L.pool_cap[l];
-                q.out_idx = (int*)(S + L.out_idx) + (size_t)l * L.out_cap; q.out_n = (int*)(S + L.out_n) + l; q.out_cap = L.out_cap;
-                q.err = d_errs + s; q.cand_cap = L.cand_cap;
+                q.list_cap = L.list_cap[l]; q.pool_cap = L.pool_cap[l]; q.err = e.err; q.cand_cap = L.cand_cap;
+                q.out_idx = out_idx + (size_t)l * L.out_cap; q.out_n = out_n + l; q.out_cap = L.out_cap;
             }
             qt_frame& qf = h_fr[s];
             qf.nlevels = g.nlevels; qf.out_cap = L.out_cap; qf.kcap = c->kcap; qf.min_border = EDGE_T - 3;
-            qf.out_idx = (int*)(S + L.out_idx); qf.out_n = (int*)(S + L.out_n);
-            qf.xs = e.xs; qf.ys = e.ys; qf.rs = e.rs;
-            qf.kin = (kp_in*)(S + L.kin); qf.nk = (int*)(S + L.nk); qf.err = d_errs + s;
+            qf.out_idx = out_idx; qf.out_n = out_n; qf.xs = e.xs; qf.ys = e.ys; qf.rs = e.rs; qf.kin = (kp_in*)(S + L.kin); qf.nk = (int*)(S + L.nk); qf.err = e.err;
         }
-        (void)maxNM4;
-        if (doA) {
-        HIPCHK(c, hipMemcpyAsync(T0, P0, tab_bytes - err_bytes, hipMemcpyHostToDevice, st));
+        return DSSS_OK;
+    }
+    int enqueue_head(const ex_batch& bt) {      // everything that does not need the frame geometry
+        const int nb = bt.nb; const double w_tot = bt.w_tot;
+        HIPCHK(c, hipMemcpyAsync(T0, P0, T.err, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipEventRecord(c->ex_side_ev[2], st)); c->ex_tab_uploaded = true;      // once it fired the pinned tables may be written again (fill_tables)
         HIPCHK(c, hipMemsetAsync(d_errs, 0, sizeof(int) * nb, st));
-        { dsss_scope sc(c, DSSS_K_ROW_REDUCE, 8.0 * w_tot);
-          hipLaunchKernelGGL(row_reduce_kernel, dim3((maxN + 3) / 4, nb), dim3(256), 0, st, d_exf); }
+        { dsss_scope sc(c, DSSS_K_ROW_REDUCE, 8.0 * w_tot); hipLaunchKernelGGL(row_reduce_kernel, dim3((bt.maxN + 3) / 4, nb), dim3(256), 0, st, d_exf); }
         { dsss_scope sc(c, DSSS_K_PRE_MISC, 1.0 * w_tot, 2);
           hipLaunchKernelGGL(final_reduce_kernel, dim3(nb), dim3(64), 0, st, d_exf, (double)(float)c->mp.factor);
-          hipLaunchKernelGGL(mask_init_kernel, dim3((unsigned)((max_tot / 16 + 256) / 256), nb), dim3(256), 0, st, d_exf, c->mp.width, c->mp.side, (double)c->mp.side * 0.6); }
-        { dsss_scope sc(c, DSSS_K_NORMALIZE, 9.0 * w_tot);
-          hipLaunchKernelGGL(normalize_kernel, dim3((unsigned)((max_tot / 4 + 256) / 256), nb), dim3(256), 0, st, d_exf, c->mp.r); }
-        { dsss_scope sc(c, DSSS_K_PYRAMID, (1.906 + 2.74) * w_tot, std::max(max_levels - 1, 1));
-          for (int l = 1; l < max_levels; ++l) {
+          hipLaunchKernelGGL(mask_init_kernel, dim3((unsigned)((bt.max_tot / 16 + 256) / 256), nb), dim3(256), 0, st, d_exf, c->mp.width, c->mp.side, (double)c->mp.side * 0.6); }
+        { dsss_scope sc(c, DSSS_K_NORMALIZE, 9.0 * w_tot); hipLaunchKernelGGL(normalize_kernel, dim3((unsigned)((bt.max_tot / 4 + 256) / 256), nb), dim3(256), 0, st, d_exf, c->mp.r); }
+        { dsss_scope sc(c, DSSS_K_PYRAMID, (1.906 + 2.74) * w_tot, std::max(bt.max_levels - 1, 1));
+          for (int l = 1; l < bt.max_levels; ++l) {
               bool strips = false, rest = false;
-              for (int s2 = 0; s2 < nb; ++s2) { const level_geom& g = *G[b0 + s2]; if (l < g.nlevels) (g.strips[l] ? strips : rest) = true; }
-              if (strips) hipLaunchKernelGGL(resize_strip_kernel, dim3((unsigned)(((size_t)((max_cols[l] + 3) / 4) * ((max_rows[l] + RS_R - 1) / RS_R) + 255) / 256), nb), dim3(256), 0, st, d_exf, l);
-              if (rest) hipLaunchKernelGGL(resize_kernel, dim3((unsigned)(((size_t)max_cols[l] * max_rows[l] / 4 + 256 * RS_K) / (256 * RS_K)), nb), dim3(256), 0, st, d_exf, l, strips ? 1 : 0);
+              for (int s = 0; s < nb; ++s) { const level_geom& g = *G[bt.b0 + s]; if (l < g.nlevels) (g.strips[l] ? strips : rest) = true; }
+              if (strips) hipLaunchKernelGGL(resize_strip_kernel, dim3((unsigned)(((size_t)((bt.max_cols[l] + 3) / 4) * ((bt.max_rows[l] + RS_R - 1) / RS_R) + 255) / 256), nb), dim3(256), 0, st, d_exf, l);
+              if (rest) hipLaunchKernelGGL(resize_kernel, dim3((unsigned)(((size_t)bt.max_cols[l] * bt.max_rows[l] / 4 + 256 * RS_K) / (256 * RS_K)), nb), dim3(256), 0, st, d_exf, l, strips ? 1 : 0);
           } }
-        // FAST, candidate compaction and the quadtree run BY GROUPS OF LEVELS.  A quadtree instance is one workgroup whose time is the latency
-        // of its own level's candidates (1.4 ms on level 0 of a 2000 x 1024 frame, whatever the number of frames) during which most of the
-        // chip idles, so the levels are pipelined over four streams:
-        //     main            FAST of group 0, 1, ... back to back (the groups are independent of each other)
-        //     xs[2], xs[3]    per group, once its FAST is done: offsets (a chain over the groups: one more event) + candidate gather + the
-        //                     quadtrees of its levels; the groups alternate between the two streams
-        // and the main stream picks the results up after the last group.  Groups: levels 0 .. 4 alone, the small top levels together
-        // (every launch ends with a partly empty chip).  Two side streams, not more: the runtime folds streams onto four hardware queues,
-        // and a quadtree that shares its queue with the next group's gather holds it up.
-        const int solo_levels = 5;
-        const int fstride = max_cw <= 40 ? 40 : CELL_STRIDE, fwave = (2 * max_ch * fstride + 15) & ~15;      // window + arc values of one wavefront
-        const hipStream_t s_qt[2] = { c->xs[2], c->xs[3] };
         bool qt_used[2] = { false, false };
-        int prev_group = -1;
-        int ngroups = 0;
-        for (int lo = 0; lo < max_levels; ++ngroups) {
-            const int hi = lo < solo_levels ? lo + 1 : max_levels;
+        const int rc = level_groups(bt, qt_used); if (rc) return rc;
+        { dsss_scope sc(c, DSSS_K_QUADTREE, 0, bt.max_levels);        // (with the level pipeline: what compaction and quadtrees leave exposed after the last FAST launch)
+          for (int k = 0; k < 2; ++k) if (qt_used[k]) { HIPCHK(c, hipEventRecord(c->ex_side_ev[k], c->xs[2 + k])); HIPCHK(c, hipStreamWaitEvent(st, c->ex_side_ev[k], 0)); }
+          dsss_launch_quadtree_collect(st, d_fr, nb); }
+        { dsss_scope sc(c, DSSS_K_DESC, (double)nb * c->op.nfeatures * (49.0 * 49.0 + 56.0)); hipLaunchKernelGGL(orient_desc_kernel, dim3((c->kcap + 3) / 4, nb), dim3(256), 0, st, d_exf); }
+        if (sift) { dsss_scope sc(c, DSSS_K_SIFT, (double)nb * c->op.nfeatures * (71.0 * 71.0 + 128.0));
+          dsss_launch_sift_desc(c, st, d_exf, c->kcap, nb, sw.sift_hist_dump); }               // N4: the 128-element rows at the same keypoints (dsss_sift.hip)
+        HIPCHK(c, hipGetLastError());
+        return DSSS_OK;
+    }
+    // FAST, candidate compaction and the quadtree run BY GROUPS OF LEVELS.  A quadtree instance is one workgroup whose time is the latency
+    // of its own level's candidates (1.4 ms on level 0 of a 2000 x 1024 frame, whatever the number of frames) during which most of the
+    // chip idles, so the levels are pipelined over four streams:
+    //     main            FAST of group 0, 1, ... back to back (the groups are independent of each other)
+    //     xs[2], xs[3]    per group, once its FAST is done: offsets (a chain over the groups: one more event) + candidate gather + the
+    //                     quadtrees of its levels; the groups alternate between the two streams
+    // and the main stream picks the results up after the last group (enqueue_head: qt_used names the side streams it waits for).  Groups:
+    // levels 0 .. 4 alone, the small top levels together (every launch ends with a partly empty chip).  Two side streams, not more: the
+    // runtime folds streams onto four hardware queues, and a quadtree that shares its queue with the next group's gather holds it up.
+    int level_groups(const ex_batch& bt, bool qt_used[2]) {
+        const int nb = bt.nb, solo_levels = 5;
+        const int fstride = bt.max_cw <= 40 ? 40 : CELL_STRIDE, fwave = (2 * bt.max_ch * fstride + 15) & ~15;      // window + arc values of one wavefront
+        int prev_group = -1, ngroups = 0;
+        for (int lo = 0; lo < bt.max_levels; ++ngroups) {
+            const int hi = lo < solo_levels ? lo + 1 : bt.max_levels;
             int cells = 0;                               // the most cells a frame has in the group
-            for (int s2 = 0; s2 < nb; ++s2) { const level_geom& g = *G[b0 + s2]; cells = std::max(cells, g.cell_begin[std::min(hi, g.nlevels)] - g.cell_begin[std::min(lo, g.nlevels)]); }
+            for (int s = 0; s < nb; ++s) { const level_geom& g = *G[bt.b0 + s]; cells = std::max(cells, g.cell_begin[std::min(hi, g.nlevels)] - g.cell_begin[std::min(lo, g.nlevels)]); }
             if (cells > 0) {
-                { dsss_scope sc(c, DSSS_K_FAST, lo == 0 ? 2.906 * w_tot : 0.0);
+                { dsss_scope sc(c, DSSS_K_FAST, lo == 0 ? 2.906 * bt.w_tot : 0.0);
                   if (fstride == 40) hipLaunchKernelGGL(fast_cells_kernel<40>, dim3((cells + 3) / 4, nb), dim3(256), 4 * fwave, st, d_exf, lo, hi, c->op.ini_th, c->op.min_th, fwave);
                   else hipLaunchKernelGGL(fast_cells_kernel<CELL_STRIDE>, dim3((cells + 3) / 4, nb), dim3(256), 4 * fwave, st, d_exf, lo, hi, c->op.ini_th, c->op.min_th, fwave); }
-                const int k = ngroups & 1;
-                const hipStream_t ss = s_qt[k];
-                {
-                    HIPCHK(c, hipEventRecord(c->ex_lev_ev[ngroups], st)); HIPCHK(c, hipStreamWaitEvent(ss, c->ex_lev_ev[ngroups], 0));
-                    if (prev_group >= 0) HIPCHK(c, hipStreamWaitEvent(ss, c->ex_cmp_ev[prev_group], 0));      // this group's offsets start where the previous group's end
-                }
+                const int k = ngroups & 1; const hipStream_t ss = c->xs[2 + k];
+                HIPCHK(c, hipEventRecord(c->ex_lev_ev[ngroups], st)); HIPCHK(c, hipStreamWaitEvent(ss, c->ex_lev_ev[ngroups], 0));
+                if (prev_group >= 0) HIPCHK(c, hipStreamWaitEvent(ss, c->ex_cmp_ev[prev_group], 0));      // this group's offsets start where the previous group's end
                 hipLaunchKernelGGL(scan_counts_kernel, dim3(nb), dim3(256), 0, ss, d_exf, lo, hi);
-                HIPCHK(c, hipEventRecord(c->ex_cmp_ev[ngroups], ss));
-                prev_group = ngroups;
+                HIPCHK(c, hipEventRecord(c->ex_cmp_ev[ngroups], ss)); prev_group = ngroups;
                 hipLaunchKernelGGL(gather_cand_kernel, dim3((cells + GC_CELLS - 1) / GC_CELLS, nb), dim3(256), 0, ss, d_exf, lo, hi);
-                for (int l = lo; l < hi; ++l) if (lev_cnt[l] > 0) dsss_launch_quadtree(ss, d_inst + (size_t)l * B, lev_cnt[l]);
+                for (int l = lo; l < hi; ++l) if (bt.lev_cnt[l] > 0) dsss_launch_quadtree(ss, d_inst + (size_t)l * B, bt.lev_cnt[l]);
                 qt_used[k] = true;
             }
             lo = hi;
         }
-        { dsss_scope sc(c, DSSS_K_QUADTREE, 0, max_levels);        // (with the level pipeline: what compaction and quadtrees leave exposed after the last FAST launch)
-          for (int k = 0; k < 2; ++k) if (qt_used[k]) { HIPCHK(c, hipEventRecord(c->ex_side_ev[k], s_qt[k])); HIPCHK(c, hipStreamWaitEvent(st, c->ex_side_ev[k], 0)); }
-          dsss_launch_quadtree_collect(st, d_fr, nb); }
-        { dsss_scope sc(c, DSSS_K_DESC, (double)nb * c->op.nfeatures * (49.0 * 49.0 + 56.0));
-          hipLaunchKernelGGL(orient_desc_kernel, dim3((c->kcap + 3) / 4, nb), dim3(256), 0, st, d_exf); }
-        if (sift) { dsss_scope sc(c, DSSS_K_SIFT, (double)nb * c->op.nfeatures * (71.0 * 71.0 + 128.0));
-          dsss_launch_sift_desc(c, st, d_exf, c->kcap, nb); }               // N4: the 128-element rows at the same keypoints (dsss_sift.hip)
+        return DSSS_OK;
+    }
+    int enqueue_tail(const ex_batch& bt, bool last) {      // the kernel that samples the geometry, and the downloads
+        { dsss_scope sc(c, DSSS_K_FILTER); hipLaunchKernelGGL(mask_filter_kernel, dim3(bt.nb), dim3(256), 0, st, d_exf); }
         HIPCHK(c, hipGetLastError());
-        }       // doA
-        if (!doB) return DSSS_OK;                    // (phase 1: one batch)
-        { dsss_scope sc(c, DSSS_K_FILTER);
-          hipLaunchKernelGGL(mask_filter_kernel, dim3(nb), dim3(256), 0, st, d_exf); }
-        HIPCHK(c, hipGetLastError());
-        if (b0 + B >= n) { const int rb = dsss_bboxes_enqueue(c); if (rb) return rb; }      // the geo boxes the matcher will ask for ride on this batch's synchronisation
-        HIPCHK(c, hipMemcpyAsync(h_err, d_errs, sizeof(int) * nb, hipMemcpyDeviceToHost, st));
+        if (last) { const int rb = dsss_bboxes_enqueue(c); if (rb) return rb; }      // the geo boxes the matcher will ask for ride on this batch's synchronisation
+        HIPCHK(c, hipMemcpyAsync(h_err, d_errs, sizeof(int) * bt.nb, hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipMemcpyAsync(h_nkp, c->nkp_dev, sizeof(int) * c->max_frames, hipMemcpyDeviceToHost, st));
-        const auto tv1 = tv_now();
-        if (exv && any_pending) { (void)hipEventSynchronize(up_ev[bk & 1]); }
-        const auto tv2 = tv_now();
-        HIPCHK(c, hipStreamSynchronize(st));         // one synchronisation per batch of up to EX_BATCH frames
-        if (exv) { const auto tv3 = tv_now(); auto us = [](auto a, auto b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
-                   tv_issue += us(tv0, tv1); tv_wait += us(tv1, tv2); tv_sync += us(tv2, tv3); ++tv_n; }
-        for (int s = 0; s < nb; ++s) {
-            dsss_frame& f = c->frames[ids[b0 + s]];
-            if (h_err[s]) DSSS_FAIL(c, DSSS_E_CAPACITY, "frame %d: extraction capacity exceeded (code %d; 7 = FAST candidates, else quadtree lists)", ids[b0 + s], h_err[s]);
-            f.nkp = h_nkp[ids[b0 + s]]; f.has_feat = true; f.has_norm = true; f.has_sift = sift;
+        return DSSS_OK;
+    }
+    int finish(const ex_batch& bt) {      // the one synchronisation per batch of up to EX_BATCH frames, then the error flags and the frames' state
+        HIPCHK(c, hipStreamSynchronize(st));
+        for (int s = 0; s < bt.nb; ++s) {
+            const int id = ids[bt.b0 + s]; dsss_frame& f = c->frames[id];
+            if (h_err[s]) DSSS_FAIL(c, DSSS_E_CAPACITY, "frame %d: extraction capacity exceeded (code %d; 7 = FAST candidates, else quadtree lists)", id, h_err[s]);
+            f.nkp = h_nkp[id]; f.has_feat = true; f.has_norm = true; f.has_sift = sift;
         }
-        if (keep_taps) {                             // stage tap for the parity tests: FAST candidates per level
-            for (int s = 0; s < nb; ++s) {
-                dsss_frame& f = c->frames[ids[b0 + s]];
-                const level_geom& g = *G[b0 + s];
-                const ex_layout& L = Ls[b0 + s];
-                char* S = S0 + slot_bytes * s;
-                const int ncells = (int)g.cells.size();
-                std::vector<int> offs(ncells + 1);
-                HIPCHK(c, hipMemcpy(offs.data(), S + L.offs, sizeof(int) * (ncells + 1), hipMemcpyDeviceToHost));
-                const int ncand = std::min(offs[ncells], L.cand_cap);
-                std::vector<float> xs(ncand), ys(ncand), rs(ncand);
-                if (ncand) {
-                    HIPCHK(c, hipMemcpy(xs.data(), S + L.xs, sizeof(float) * ncand, hipMemcpyDeviceToHost));
-                    HIPCHK(c, hipMemcpy(ys.data(), S + L.ys, sizeof(float) * ncand, hipMemcpyDeviceToHost));
-                    HIPCHK(c, hipMemcpy(rs.data(), S + L.rs, sizeof(float) * ncand, hipMemcpyDeviceToHost));
-                }
-                for (int l = 0; l < g.nlevels; ++l) {
-                    const int b = std::min(offs[g.cell_begin[l]], ncand), e = std::min(offs[g.cell_begin[l + 1]], ncand);
-                    f.cand_x[l].assign(xs.begin() + b, xs.begin() + e); f.cand_y[l].assign(ys.begin() + b, ys.begin() + e); f.cand_r[l].assign(rs.begin() + b, rs.begin() + e);
-                }
+        return DSSS_OK;
+    }
+    int read_taps(const ex_batch& bt) {      // stage tap for the parity tests, the FAST candidates per level
+        for (int s = 0; s < bt.nb; ++s) {
+            dsss_frame& f = c->frames[ids[bt.b0 + s]]; const level_geom& g = *G[bt.b0 + s]; const ex_layout& L = Ls[bt.b0 + s];
+            char* S = S0 + slot_bytes * s; const int ncells = (int)g.cells.size();
+            std::vector<int> offs(ncells + 1);
+            HIPCHK(c, hipMemcpy(offs.data(), S + L.offs, sizeof(int) * (ncells + 1), hipMemcpyDeviceToHost));
+            const int ncand = std::min(offs[ncells], L.cand_cap);
+            const size_t src[3] = { L.xs, L.ys, L.rs }; std::vector<float>* const dst[3] = { f.cand_x, f.cand_y, f.cand_r };
+            std::vector<float> v(ncand);
+            for (int k = 0; k < 3; ++k) {
+                if (ncand) HIPCHK(c, hipMemcpy(v.data(), S + src[k], sizeof(float) * ncand, hipMemcpyDeviceToHost));
+                for (int l = 0; l < g.nlevels; ++l) dst[k][l].assign(v.begin() + std::min(offs[g.cell_begin[l]], ncand), v.begin() + std::min(offs[g.cell_begin[l + 1]], ncand));
             }
         }
+        return DSSS_OK;
     }
-    if (exv && tv_n) fprintf(stderr, "[dsss extract] %d batches of %d: per batch host issue %.0f us, wait for the batch's upload %.0f us, kernels after it %.0f us\n", tv_n, B, tv_issue / tv_n, tv_wait / tv_n, tv_sync / tv_n);
-    return DSSS_OK;
-}
+};
 
 // Error exits of the batch loop can leave asynchronous uploads FROM CALLER MEMORY queued on the copy stream (the upload of batch
 // k + 1 is issued before the kernels of batch k have run): no error is returned before those copies have finished, so the caller's
 // page-locked images are free again whenever dsss_extract* returns, with or without an error (include/dsss.h, dsss_frame_set).
-static int extract_frames(dsss_ctx* c, const int* ids, int n, bool keep_taps)
+static int extract_frames(dsss_ctx* c, const int* ids, int n, bool keep_taps, const dsss_switches& sw)
 {
-    // the frames dsss_frames_set already started on (phase 1): only the tail is left.  Anything else drops that start (its kernels
+    if (n <= 0) { c->ex_eager_valid = false; return DSSS_OK; }
+    // the frames dsss_frames_set already started on: only the tail is left.  Anything else drops that start (its kernels
     // are queued on the context's stream ahead of whatever follows; their results are simply overwritten)
-    int phase = 0;
-    if (c->ex_eager_valid) {
-        const bool same = !keep_taps && (int)c->ex_eager_ids.size() == n && std::equal(ids, ids + n, c->ex_eager_ids.begin())
-                          && memcmp(&c->ex_eager_op, &c->op, sizeof c->op) == 0 && memcmp(&c->ex_eager_mp, &c->mp, sizeof c->mp) == 0;
-        c->ex_eager_valid = false;
-        if (same) phase = 2;
-    }
-    const int rc = extract_frames_impl(c, ids, n, keep_taps, phase);
+    const bool started = c->ex_eager_valid && !keep_taps && (int)c->ex_eager_ids.size() == n && std::equal(ids, ids + n, c->ex_eager_ids.begin())
+                         && memcmp(&c->ex_eager_op, &c->op, sizeof c->op) == 0 && memcmp(&c->ex_eager_mp, &c->mp, sizeof c->mp) == 0;
+    c->ex_eager_valid = false;
+    ex_run x(c, ids, n, sw);
+    const int rc = started ? x.resume() : x.run(keep_taps);
     if (rc != DSSS_OK) { for (int k = 0; k < 4; ++k) (void)hipStreamSynchronize(c->xs[k]); (void)hipStreamSynchronize(c->stream); (void)hipGetLastError(); }
     return rc;
 }
 
-// dsss_frames_set: start the extraction of the frames whose images are in HBM (see extract_frames_impl).  Not an error if it cannot.
-void dsss_extract_eager(dsss_ctx* c, const int* ids, int n)
+// dsss_frames_set: start the extraction of the frames whose images are in HBM (ex_run::start).  Not an error if it cannot.
+void dsss_extract_eager(dsss_ctx* c, const int* ids, int n, const dsss_switches& sw)
 {
     c->ex_eager_valid = false;
-    const bool exv = getenv("DSSS_EX_VERBOSE") != nullptr;
+    const bool exv = sw.ex_verbose;
     if (n <= 0 || n > EX_BATCH) { if (exv) fprintf(stderr, "[dsss extract] no early start: %d frames in the call\n", n); return; }
     std::vector<int> mine;
     for (int i = 0; i < n; ++i) {
@@ -1328,7 +1328,7 @@ void dsss_extract_eager(dsss_ctx* c, const int* ids, int n)
         mine.push_back(ids[i]);
     }
     if (mine.empty()) return;
-    if (extract_frames_impl(c, mine.data(), (int)mine.size(), false, 1) != DSSS_OK) { if (exv) fprintf(stderr, "[dsss extract] no early start: %s\n", c->err.c_str()); (void)hipGetLastError(); return; }      // (the full path will report what is wrong)
+    if (ex_run(c, mine.data(), (int)mine.size(), sw).start() != DSSS_OK) { if (exv) fprintf(stderr, "[dsss extract] no early start: %s\n", c->err.c_str()); (void)hipGetLastError(); return; }      // (the full path will report what is wrong)
     c->ex_eager_ids.swap(mine); c->ex_eager_op = c->op; c->ex_eager_mp = c->mp; c->ex_eager_valid = true;
 }
 
@@ -1339,7 +1339,7 @@ int dsss_extract(dsss_ctx* c, int id, int* n_kp)
     if (!c) return DSSS_E_ARG;
     if (id < 0 || id >= c->max_frames) DSSS_FAIL(c, DSSS_E_ARG, "frame id %d out of range", id);
     HIPCHK(c, hipSetDevice(c->device));
-    int rc = extract_frames(c, &id, 1, true);
+    int rc = extract_frames(c, &id, 1, true, dsss_switches_read());
     if (rc) return rc;
     if (n_kp) *n_kp = c->frames[id].nkp;
     return DSSS_OK;
@@ -1350,7 +1350,7 @@ int dsss_extract_many(dsss_ctx* c, const int* ids, int n)
     if (!c || (n > 0 && !ids)) return DSSS_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     for (int i = 0; i < n; ++i) if (ids[i] < 0 || ids[i] >= c->max_frames) DSSS_FAIL(c, DSSS_E_ARG, "frame id %d out of range", ids[i]);
-    return extract_frames(c, ids, n, false);
+    return extract_frames(c, ids, n, false, dsss_switches_read());
 }
 
 int dsss_host_quadtree(const float* x, const float* y, const float* resp, int n, int minX, int maxX, int minY, int maxY,

@@ -65,7 +65,7 @@ struct dsss_ctx {
     hipStream_t stream = nullptr;
     hipStream_t xs[4] = {nullptr, nullptr, nullptr, nullptr};   // extra streams: frames of one extraction batch overlap on them
     hipEvent_t xev[4] = {nullptr, nullptr, nullptr, nullptr}; hipEvent_t xev_main = nullptr;
-    hipEvent_t ex_lev_ev[DSSS_MAX_LEVELS] = {}, ex_cmp_ev[DSSS_MAX_LEVELS] = {}; hipEvent_t ex_side_ev[3] = {};    // extraction: FAST of level group g done (main stream), its candidate offsets known (side stream); quadtrees of a side stream done
+    hipEvent_t ex_lev_ev[DSSS_MAX_LEVELS] = {}, ex_cmp_ev[DSSS_MAX_LEVELS] = {}; hipEvent_t ex_side_ev[3] = {};    // extraction: FAST of level group g done (main stream), its candidate offsets known (side stream); quadtrees of a side stream done; [2]: the batch tables uploaded
     std::string err;
     dsss_mask_params mp;
     dsss_orb_params op;
@@ -91,6 +91,7 @@ struct dsss_ctx {
     // extraction scratch (grown on demand)
     void* ex_scratch = nullptr; size_t ex_scratch_bytes = 0;
     void* ex_pinned = nullptr; size_t ex_pinned_bytes = 0;
+    bool ex_tab_uploaded = false;      // ex_side_ev[2] has been recorded: the upload of the pinned batch tables may be waited for
     // extraction started by dsss_frames_set (everything but the kernel that needs the geometry): for which frames, under which parameters
     bool ex_eager_valid = false; std::vector<int> ex_eager_ids; dsss_orb_params ex_eager_op; dsss_mask_params ex_eager_mp;
     std::vector<dsss_geo_batch> gbatches;
@@ -163,11 +164,23 @@ struct dsss_scope {
     }
 };
 
-void dsss_extract_eager(dsss_ctx* c, const int* ids, int n);      // dsss_frames_set: start extracting the frames whose images are in HBM
+// The DSSS_* environment switches outside the pose graph (those: pg_switches, dsss_pg_sym.h).  Read ONCE PER CALL by the C entry that
+// needs them (dsss_frames_set, dsss_extract, dsss_extract_many, dsss_match_pairs) and handed down: one process may flip them between calls.
+struct dsss_switches {
+    size_t ex_scratch_mb = 24576;            // DSSS_EX_SCRATCH_MB: bound of the extraction's batch scratch, max(1, atoi)
+    int ex_upload_batch = 8;                 // DSSS_EX_UPLOAD_BATCH: frames per batch while host images are still streamed in, max(1, atoi)
+    bool ex_verbose = false;                 // DSSS_EX_VERBOSE: set at all
+    int fs_threads = 0;                      // DSSS_FS_THREADS: atoi; not above 0 = dsss_frames_set's own rule
+    bool mt_grid = true;                     // DSSS_MT_GRID: off only when set and atoi == 0
+    const char* sift_hist_dump = nullptr;    // DSSS_SIFT_HIST_DUMP: the path
+};
+dsss_switches dsss_switches_read();      // dsss_ctx.hip
+
+void dsss_extract_eager(dsss_ctx* c, const int* ids, int n, const dsss_switches& sw);      // dsss_frames_set: start extracting the frames whose images are in HBM
 int dsss_ensure_store(dsss_ctx* c);                 // allocate the feature store for the current kcap
 int dsss_ensure_sift_store(dsss_ctx* c);            // ... and the 128-byte rows + the window table (DSSS_DESC_SIFT128)
 struct ex_frame;
-void dsss_launch_sift_desc(dsss_ctx* c, hipStream_t st, const ex_frame* d_exf, int kcap, int nb);      // dsss_sift.hip
+void dsss_launch_sift_desc(dsss_ctx* c, hipStream_t st, const ex_frame* d_exf, int kcap, int nb, const char* hist_dump);      // dsss_sift.hip; hist_dump: dsss_switches::sift_hist_dump
 int dsss_frame_geo_bbox(dsss_ctx* c, int id);       // device computation of the geo bounding box (asynchronous)
 int dsss_bboxes_enqueue(dsss_ctx* c);               // queue the pending boxes on the context's stream (no synchronisation)
 int dsss_sync_bboxes(dsss_ctx* c);                  // make dsss_frame::bbox valid on the host

@@ -600,6 +600,7 @@ int dsss_match_pairs(dsss_ctx* c, const int* src_ids, const int* tgt_ids, int np
 {
     if (!c || npairs < 0 || (npairs > 0 && (!src_ids || !tgt_ids))) return DSSS_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
+    const dsss_switches sw = dsss_switches_read();
     c->npairs = npairs; c->has_lc = false;
     c->pair_s.assign(src_ids, src_ids + npairs); c->pair_t.assign(tgt_ids, tgt_ids + npairs);
     c->pair_active.assign(npairs, -1);
@@ -665,7 +666,7 @@ int dsss_match_pairs(dsss_ctx* c, const int* src_ids, const int* tgt_ids, int np
     // non-finite box or radius, or a box of more than 2^22 cells) and as the A/B switch DSSS_MT_GRID=0
     bool evals_pending = false;
     std::function<hipError_t()> gcount;                // (profile on) counts the grid's evaluations, launched after the matcher's scope has closed
-    bool use_grid = !(getenv("DSSS_MT_GRID") && atoi(getenv("DSSS_MT_GRID")) == 0) && std::isfinite(c->mt.radius) && c->mt.radius > 0;
+    bool use_grid = sw.mt_grid && std::isfinite(c->mt.radius) && c->mt.radius > 0;
     const double cs = c->mt.radius / MT_SUB * (1.0 + 1.0 / 1048576.0), inv_cs = 1.0 / cs;      // the hair: 1e-6 of a cell against 1e-13 of rounding
     std::vector<mt_grid> gtab; std::vector<int> gframes; size_t gcells = 0;
     if (use_grid) {

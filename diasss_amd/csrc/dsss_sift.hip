@@ -215,13 +215,12 @@ __global__ __launch_bounds__(256) void sift_desc_kernel(const ex_frame* __restri
     }
 }
 
-void dsss_launch_sift_desc(dsss_ctx* c, hipStream_t st, const ex_frame* d_exf, int kcap, int nb)
+void dsss_launch_sift_desc(dsss_ctx* c, hipStream_t st, const ex_frame* d_exf, int kcap, int nb, const char* dump)
 {
     // DSSS_SIFT_HIST_DUMP=<file> (diagnostic, tests/test_gpu_sift.py): the raw 2^-12 fixed-point histograms of every pre-filter keypoint of the
     // batch, int32[nb][kcap][128], written after the launch -- the parity bar UNDER the rounded bytes (a one-unit difference in one of a
     // keypoint's 13 000 rounded shares moves an output byte only once in a few thousand keypoints: the bare v_sqrt_f32 behind __fsqrt_rn did)
     int* dbg = nullptr;
-    const char* dump = getenv("DSSS_SIFT_HIST_DUMP");
     if (dump && hipMalloc(&dbg, (size_t)nb * kcap * 128 * sizeof(int)) != hipSuccess) { (void)hipGetLastError(); dbg = nullptr; }
     if (dbg) (void)hipMemsetAsync(dbg, 0, (size_t)nb * kcap * 128 * sizeof(int), st);
     hipLaunchKernelGGL(sift_desc_kernel, dim3(kcap, nb), dim3(256), 0, st, d_exf, c->sift_w, dbg, kcap);

@@ -178,6 +178,115 @@ def test_eager_extraction_started_by_frames_set_and_its_fallbacks(ctx, orc):
     set_all(); assert ctx.extract(1) > 0; ctx.extract_many(ids); check()        # a single-frame extraction in between
 
 
+E_ARG, E_STATE = -2, -4
+FIELDS = ("x", "y", "size", "angle", "response", "octave")
+
+
+def _assert_oracle(ctx, orc, fid, frame, po=None):
+    """keypoints, descriptors and geo of frame `fid` are bit for bit the oracle's"""
+    raw, pose, alt, gr = frame
+    kps, desc, _, _ = orc.detect_feature(raw, None, po) if po is not None else orc.detect_feature(raw)
+    g_kps, g_desc, g_geo = ctx.features_get(fid)
+    assert len(g_kps) == len(kps) and len(kps) > 50
+    for fld in FIELDS:
+        assert (g_kps[fld] == kps[fld]).all(), (fid, fld)
+    assert (g_desc == desc).all(), fid
+    assert (np.asarray(g_geo).reshape(-1, 2) == np.asarray(orc.geo_at_kps(pose, gr, raw.shape[1], kps)).reshape(-1, 2)).all(), fid
+
+
+def _set_many(ctx, ids, frames, raws):
+    ctx.frames_set(ids, raws, [f[0].shape[0] for f in frames], [f[0].shape[1] for f in frames], [f[1] for f in frames], [f[2] for f in frames], [f[3] for f in frames])
+
+
+def test_ragged_eager_start_equals_oracle_and_whole_run(ctx, orc):
+    """three device-resident frames of three geometries, both resize kernels in the started half (scale 1.334: strips fit 500 x 300, not
+    500 x 302): dsss_frames_set starts, dsss_extract_many resumes -- the oracle's features, and those of the whole-run path bit for bit"""
+    import torch
+    mp, op, mt, pg = ctx.default_params()
+    op.nfeatures = 500; op.nlevels = 4; op.scale = 1.334
+    ctx.set_params(orb=op)
+    try:
+        frames = [_frame(N, M, 31 + i, hot=False) for i, (N, M) in enumerate(((500, 300), (500, 302), (640, 400)))]
+        dev = [torch.from_numpy(f[0]).cuda() for f in frames]
+        ids = [0, 1, 2]
+        _set_many(ctx, ids, frames, dev)
+        ctx.extract_many(ids)                                                       # start + resume
+        po = orc.orb_params(); po.nfeatures = 500; po.nlevels = 4; po.scale = 1.334
+        split = []
+        for k in ids:
+            _assert_oracle(ctx, orc, k, frames[k], po)
+            split.append([np.asarray(a).tobytes() for a in ctx.features_get(k)])
+        for k in ids:                                                               # the whole run, frame by frame
+            raw, pose, alt, gr = frames[k]
+            ctx.frame_set(k, dev[k], raw.shape[0], raw.shape[1], pose, alt, gr)
+            assert ctx.extract(k) > 50
+            assert [np.asarray(a).tobytes() for a in ctx.features_get(k)] == split[k], k
+    finally:
+        ctx.set_params(orb=ctx.default_params()[1])
+
+
+def test_start_and_resume_issue_what_the_whole_run_issues(ctx):
+    """the profile's launch counts and work figures of every extraction family are the same whether dsss_frames_set starts the
+    extraction and dsss_extract_many resumes it, or dsss_extract_many runs all of it"""
+    import torch
+    N, M = 640, 400
+    frames = [_frame(N, M, 40 + k, hot=False) for k in range(3)]
+    dev = [torch.from_numpy(f[0]).cuda() for f in frames]
+    ids = [0, 1, 2]
+    families = ("row_reduce", "pre_misc", "normalize", "pyramid", "fast", "fast_compact", "quadtree", "desc", "filter", "sift")
+    ctx.profile(True)
+    try:
+        ctx.profile_reset()
+        _set_many(ctx, ids, frames, dev)
+        ctx.extract_many(ids)
+        split = ctx.profile_get()
+        ctx.profile_reset()
+        for k in ids: ctx.frame_set(k, dev[k], N, M, frames[k][1], frames[k][2], frames[k][3])
+        ctx.extract_many(ids)
+        whole = ctx.profile_get()
+    finally:
+        ctx.profile(False)
+    for fam in families:
+        print(fam, split[fam][1:], whole[fam][1:])
+        assert split[fam][1] == whole[fam][1], "launches of %s: %d started + resumed, %d whole run" % (fam, split[fam][1], whole[fam][1])
+        assert split[fam][2] == whole[fam][2], "work of %s: %r started + resumed, %r whole run" % (fam, split[fam][2], whole[fam][2])
+    assert all(whole[fam][1] > 0 for fam in ("row_reduce", "pyramid", "fast", "quadtree", "desc", "filter"))
+
+
+def test_error_exits_of_start_and_resume_leave_a_usable_context(ctx, orc):
+    """host-side refusals (they return before any launch) on either side of an early start; the context extracts correctly afterwards"""
+    import torch
+    from diasss_amd.capi import DsssError
+    N, M = 640, 400
+    frames = [_frame(N, M, 50 + k, hot=False) for k in range(4)]
+    dev = [torch.from_numpy(f[0]).cuda() for f in frames]
+    ids = [0, 1, 2, 3]
+    _set_many(ctx, ids, frames, [dev[0], None, dev[2], None])                       # two frames carry no image: the start covers the other two
+    ctx.extract_many([0, 2])                                                        # (resume)
+    for k in (0, 2): _assert_oracle(ctx, orc, k, frames[k])
+    with pytest.raises(DsssError) as ei:
+        ctx.extract_many(ids)
+    assert ei.value.code == E_STATE and "no raw image" in str(ei.value)
+    ctx.extract_many([0, 2])                                                        # (whole run)
+    for k in (0, 2): _assert_oracle(ctx, orc, k, frames[k])
+    # a frame too small for the top pyramid level: at eight levels and 1.2 the last one of 200 x 200 is 56 x 56, below 2 * 19 + 31 = 69
+    mp, op, mt, pg = ctx.default_params()
+    op.nlevels = 8
+    assert round(200 / 1.2 ** 7) < 2 * 19 + 31 <= round(200 / 1.2 ** 5)                 # (the default six levels would fit)
+    ctx.set_params(orb=op)
+    try:
+        small = _frame(200, 200, 60, hot=False)
+        _set_many(ctx, [0], [small], [torch.from_numpy(small[0]).cuda()])           # succeeds: the early start declines silently
+        with pytest.raises(DsssError) as ei:
+            ctx.extract_many([0])
+        assert ei.value.code == E_ARG and "too small" in str(ei.value)
+    finally:
+        ctx.set_params(orb=ctx.default_params()[1])
+    _set_many(ctx, [0], [frames[1]], [dev[1]])
+    ctx.extract_many([0])
+    _assert_oracle(ctx, orc, 0, frames[1])
+
+
 def test_full_geo_image_on_request(ctx, orc):
     """Frame::geo_img as the reference holds it (frame.cpp:126-165: the N x M pair) through dsss_frame_get_geo -- the hot path only
     ever uses its extremes (dsss_frame_bbox) and its samples at the keypoints; a caller that reads the field gets the full image,
