@@ -233,7 +233,11 @@ int dsss_posegraph_online_edges(dsss_ctx*);      /* loop closures accumulated so
  * context, four ints per level in launch order -- panel steps on the level, scalar columns of its widest panel, scalar rows below its
  * tallest one, 1 for a level of the replicated interface tree -- and the number of factorisations (LM trials) that solve ran.        */
 int dsss_posegraph_schedule_get(dsss_ctx*, int* levels4_host, int cap_levels, int* n_levels, int* n_trials);
-/* stand-alone form: explicit DR chain + edges                                                               */
+/* stand-alone form: explicit DR chain + edges.  total >= 2: a graph of one pose has nothing to solve and is refused with DSSS_E_ARG, as an
+ * edge out of range or with a == b is, before anything is launched.  A variance that is not finite and positive is DSSS_E_NUMERIC, found later,
+ * once the dead reckoning is on the device and the analysis has started, but before any factor is linearised.  Any variance that is finite and positive is taken; one so small that the
+ * normal equations are not finite makes every trial's factorisation fail: lambda walks to lambda_max and the start values come back
+ * (stats4 = { 0, err0, err0, lambda }).                                                                          */
 int dsss_posegraph_solve_edges(dsss_ctx*, const double* dr6, int total, const dsss_lc_edge* edges, int ne,
                                double* poses12_host, double* stats4_host);
 

@@ -431,7 +431,9 @@ def _make_reduced_solver(refine, log):
             r = np.concatenate([rows.ravel(), cols[off].ravel()])
             c = np.concatenate([cols.ravel(), rows[off].ravel()])
             v = np.concatenate([B.ravel(), B[off].ravel()])
-            A = sp.coo_matrix((v, (r, c)), shape=(ns * 6, ns * 6)).tocsc()
+            if not (np.all(np.isfinite(v)) and np.all(np.isfinite(b))):         # an overflowed system is a failed factorisation, not an exception
+                return -1
+            A =sp.coo_matrix((v, (r, c)), shape=(ns * 6, ns * 6)).tocsc()
             lu = spla.splu(A, permc_spec="MMD_AT_PLUS_A", diag_pivot_thresh=0.0, options=dict(SymmetricMode=True))
             b0 = b.copy()
             x = lu.solve(b0)
@@ -479,10 +481,9 @@ def pg_solve(dr, edges, params=None, solver="envelope", refine=0, log=None, full
 PG_TRACE_COLS = 5          # ORC_PG_TRACE_COLS: err before the trial, err after it, costChange / linChange, lambda, accepted
 
 
-def pg_solve_init(dr, edges, params=None, x0=None, prior=None, solver="envelope", refine=0, log=None, full_refine=0, trace_cap=256):
-    """orc_pg_solve_init: the LM of pg_solve started at x0 (n_init x 12: the first n_init poses; the others start at DR o noise or DR)
-    with the prior measuring `prior` (12 doubles; None: DR[0]).  Returns (poses, stats, trace): trace holds one row of PG_TRACE_COLS per
-    trial whose linearised change was non-negative, in order.  solver as in pg_solve."""
+def _pg_lm_run(dr, edges, params, x0, prior, solver, refine, log, full_refine, call):
+    """the preparation shared by pg_solve_init and pg_solve_path: contiguous arguments, the reduced solver and full_refine set for the one
+    call and reset after it.  call(L, dr, n, edges, ne, params, x0, n_init, prior, out, stats) runs the entry point; returns (out, stats)."""
     dr = np.ascontiguousarray(dr, np.float64).reshape(-1, 6)
     p = params or pg_params()
     out = np.zeros((len(dr), 12), np.float64); stats = np.zeros(4, np.float64)
@@ -490,10 +491,8 @@ def pg_solve_init(dr, edges, params=None, x0=None, prior=None, solver="envelope"
     x0 = np.zeros((0, 12)) if x0 is None else np.ascontiguousarray(x0, np.float64).reshape(-1, 12)
     assert len(x0) <= len(dr)
     prior = None if prior is None else np.ascontiguousarray(prior, np.float64).reshape(12)
-    trace = np.full((max(int(trace_cap), 1), PG_TRACE_COLS), np.nan)
     L = lib()
     L.orc_pg_set_reduced_solver.argtypes = [C.c_void_p]
-    L.orc_pg_solve_init.argtypes = [c_dp, C.c_int, C.POINTER(LCEdge), C.c_int, C.POINTER(PGParams), c_dp, C.c_int, c_dp, c_dp, C.c_int, c_dp, c_dp]
     cb = None
     if solver == "sparse":
         cb = _make_reduced_solver(refine, log)
@@ -502,13 +501,45 @@ def pg_solve_init(dr, edges, params=None, x0=None, prior=None, solver="envelope"
         assert solver == "envelope"
     L.orc_pg_set_full_refine(int(full_refine))
     try:
-        L.orc_pg_solve_init(dp(dr), len(dr), edges.ctypes.data_as(C.POINTER(LCEdge)), len(edges), C.byref(p),
-                            dp(x0) if len(x0) else None, len(x0), dp(prior) if prior is not None else None,
-                            dp(trace), len(trace), dp(out), dp(stats))
+        call(L, dp(dr), len(dr), edges.ctypes.data_as(C.POINTER(LCEdge)), len(edges), C.byref(p),
+             dp(x0) if len(x0) else None, len(x0), dp(prior) if prior is not None else None, dp(out), dp(stats))
     finally:
         L.orc_pg_set_reduced_solver(None)
         L.orc_pg_set_full_refine(0)
+    return out, stats
+
+
+def pg_solve_init(dr, edges, params=None, x0=None, prior=None, solver="envelope", refine=0, log=None, full_refine=0, trace_cap=256):
+    """orc_pg_solve_init: the LM of pg_solve started at x0 (n_init x 12: the first n_init poses; the others start at DR o noise or DR)
+    with the prior measuring `prior` (12 doubles; None: DR[0]).  Returns (poses, stats, trace): trace holds one row of PG_TRACE_COLS per
+    trial whose linearised change was non-negative, in order.  solver as in pg_solve."""
+    trace = np.full((max(int(trace_cap), 1), PG_TRACE_COLS), np.nan)
+
+    def call(L, dr_, n, e, ne, p, x0_, n_init, prior_, out, stats):
+        L.orc_pg_solve_init.argtypes = [c_dp, C.c_int, C.POINTER(LCEdge), C.c_int, C.POINTER(PGParams), c_dp, C.c_int, c_dp, c_dp, C.c_int, c_dp, c_dp]
+        L.orc_pg_solve_init(dr_, n, e, ne, p, x0_, n_init, prior_, dp(trace), len(trace), out, stats)
+    out, stats = _pg_lm_run(dr, edges, params, x0, prior, solver, refine, log, full_refine, call)
     return out, stats, trace[~np.isnan(trace[:, 0])].copy()
+
+
+PG_PATH_COLS = 6           # ORC_PG_PATH_COLS: the trace's five (NaN where the trial did not get that far) and the trial's kind
+PG_TRIAL_DECIDED, PG_TRIAL_LIN_NEG, PG_TRIAL_FACTOR_FAILED = 0, 1, 2
+
+
+def pg_solve_path(dr, edges, params=None, x0=None, prior=None, solver="envelope", refine=0, log=None, full_refine=0, path_cap=1024):
+    """orc_pg_solve_path: pg_solve_init with EVERY trial on record.  Returns (poses, stats, trace, path, ntrials): poses, stats and trace
+    as pg_solve_init returns them; path holds one row of PG_PATH_COLS per trial, the failed factorisations and the trials whose linearised
+    change was negative included; ntrials counts the trials whatever path_cap is."""
+    cap = max(int(path_cap), 1)
+    trace = np.full((cap, PG_TRACE_COLS), np.nan); path = np.full((cap, PG_PATH_COLS), np.nan)
+    ntrials = C.c_int(0)
+
+    def call(L, dr_, n, e, ne, p, x0_, n_init, prior_, out, stats):
+        L.orc_pg_solve_path.argtypes = [c_dp, C.c_int, C.POINTER(LCEdge), C.c_int, C.POINTER(PGParams), c_dp, C.c_int, c_dp, c_dp, C.c_int,
+                                        c_dp, C.c_int, C.POINTER(C.c_int), c_dp, c_dp]
+        L.orc_pg_solve_path(dr_, n, e, ne, p, x0_, n_init, prior_, dp(trace), cap, dp(path), cap, C.byref(ntrials), out, stats)
+    out, stats = _pg_lm_run(dr, edges, params, x0, prior, solver, refine, log, full_refine, call)
+    return out, stats, trace[~np.isnan(trace[:, 0])].copy(), path[~np.isnan(path[:, 5])].copy(), ntrials.value
 
 
 def pg_error_at(dr, edges, poses12):

@@ -238,6 +238,15 @@ int orc_pg_solve(const double* dr, int total, const orc_lc_edge* edges, int ne, 
 int orc_pg_solve_init(const double* dr, int total, const orc_lc_edge* edges, int ne, const orc_pg_params* p,
                       const double* x0_12, int n_init, const double* prior12, double* trace, int trace_cap,
                       double* out12, double* stats /* [iters, err0, err1, lambda] */);
+/* orc_pg_solve_init with the whole path next to the trace: one row per trial, the failed factorisations and the trials with a negative
+ * linearised change included, and the number of trials.  Poses, stats and trace are those of orc_pg_solve_init (which is this with NULLs). */
+#define ORC_PG_PATH_COLS 6    /* the trace's five (NaN where the trial did not get that far), kind of the trial */
+#define ORC_PG_TRIAL_DECIDED 0
+#define ORC_PG_TRIAL_LIN_NEG 1
+#define ORC_PG_TRIAL_FACTOR_FAILED 2
+int orc_pg_solve_path(const double* dr, int total, const orc_lc_edge* edges, int ne, const orc_pg_params* p,
+                      const double* x0_12, int n_init, const double* prior12, double* trace, int trace_cap,
+                      double* path, int path_cap, int* ntrials, double* out12, double* stats /* [iters, err0, err1, lambda] */);
 /* the same graph's LM objective evaluated at given poses (total x 12), for full-size checks of a solver's answer */
 /* optional second linear solver of the reduced (separator) system of orc_pg_solve: see orc_posegraph.c */
 typedef int (*orc_pg_reduced_solver_fn)(int ns, int nblk, const int* bi, const int* bj, const double* blk36, double* rhs);

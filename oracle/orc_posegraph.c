@@ -356,10 +356,14 @@ static int pg_solve(const pg_t* g, double lambda, double* delta, const double* n
  * at DR, pose i drawing z[6i .. 6i+5] of the ONE orc_normal_fill(z, 6 total) stream whatever n_init is.  The prior measures prior12
  * (12 doubles) when it is not NULL, DR[0] otherwise.  trace (optional, trace_cap rows of ORC_PG_TRACE_COLS doubles) receives one row
  * per trial whose linearised change was non-negative -- every accept / stop decision of the loop: [err before the trial, err after
- * it, costChange / linChange, lambda of the trial, 1 if accepted else 0]; rows beyond the last trial are left untouched. */
-int orc_pg_solve_init(const double* dr, int total, const orc_lc_edge* edges, int ne, const orc_pg_params* p,
+ * it, costChange / linChange, lambda of the trial, 1 if accepted else 0]; rows beyond the last trial are left untouched.
+ * path (optional, path_cap rows of ORC_PG_PATH_COLS doubles) receives one row for EVERY trial, in order: the five columns of the trace
+ * (err after and the ratio are NaN where the trial never evaluated them) and the trial's kind -- ORC_PG_TRIAL_DECIDED (it is also a
+ * row of the trace), ORC_PG_TRIAL_LIN_NEG (the linearised change was negative or not finite: lambda grows), ORC_PG_TRIAL_FACTOR_FAILED
+ * (the damped normal equations did not factorise: lambda grows).  *ntrials (optional) receives the number of trials whatever path_cap is. */
+int orc_pg_solve_path(const double* dr, int total, const orc_lc_edge* edges, int ne, const orc_pg_params* p,
                       const double* x0_12, int n_init, const double* prior12, double* trace, int trace_cap,
-                      double* out12, double* stats)
+                      double* path, int path_cap, int* ntrials, double* out12, double* stats)
 {
     const double PI = ORC_PI_REF;
     /* odometry sigmas (optimizer.cpp:24,28) */
@@ -413,7 +417,7 @@ int orc_pg_solve_init(const double* dr, int total, const orc_lc_edge* edges, int
     }
     /* LM (same loop as the mini problems) */
     double lambda = p->lambda0;
-    int iters = 0, ntrace = 0;
+    int iters = 0, ntrace = 0, npath = 0;
     double err = pg_error(&g, X);
     double err0 = err, cur;
     double* delta = (double*)malloc(sizeof(double) * 6 * (size_t)n);
@@ -452,8 +456,9 @@ int orc_pg_solve_init(const double* dr, int total, const orc_lc_edge* edges, int
                 if (ok) for (size_t q = 0; q < (size_t)n * 6; ++q) delta[q] += c[q];
                 free(rho); free(nr); free(c);
             }
-            int success = 0, stop = 0;
-            double newErr = 0;
+            int success = 0, stop = 0, kind = ok ? ORC_PG_TRIAL_LIN_NEG : ORC_PG_TRIAL_FACTOR_FAILED;
+            double newErr = 0, ratio = NAN;
+            const double lambda_trial = lambda;
             if (ok) {
                 double newLin = 0;
                 for (int k = 0; k < g.nf; ++k) {
@@ -473,6 +478,7 @@ int orc_pg_solve_init(const double* dr, int total, const orc_lc_edge* edges, int
                     for (int i = 0; i < n; ++i) orc_pose_retract(&X[i], delta + (size_t)i * 6, &Xn[i]);
                     newErr = pg_error(&g, Xn);
                     double costChange = err - newErr;
+                    kind = ORC_PG_TRIAL_DECIDED; ratio = costChange / linChange;
                     if (linChange > 2.220446049250313e-16 * oldLin) success = (costChange / linChange) > p->min_fidelity;
                     if (fabs(costChange) < p->rel_tol * err) stop = 1;
                     if (trace && ntrace < trace_cap) {
@@ -481,6 +487,11 @@ int orc_pg_solve_init(const double* dr, int total, const orc_lc_edge* edges, int
                     }
                 }
             }
+            if (path && npath < path_cap) {
+                double* row = path + (size_t)npath * ORC_PG_PATH_COLS;
+                row[0] = err; row[1] = kind == ORC_PG_TRIAL_DECIDED ? newErr : NAN; row[2] = ratio; row[3] = lambda_trial; row[4] = success; row[5] = kind;
+            }
+            ++npath;
             if (success) { memcpy(X, Xn, sizeof(orc_pose) * n); err = newErr; lambda /= p->lambda_factor; ++iters; break; }
             else if (!stop) { lambda *= p->lambda_factor; if (lambda >= p->lambda_max) break; }
             else break;
@@ -491,8 +502,16 @@ int orc_pg_solve_init(const double* dr, int total, const orc_lc_edge* edges, int
         memcpy(out12 + (size_t)i * 12 + 9, X[i].t, sizeof(double) * 3);
     }
     if (stats) { stats[0] = iters; stats[1] = err0; stats[2] = err; stats[3] = lambda; }
+    if (ntrials) *ntrials = npath;
     free(delta); free(g.f); free(g.r); free(g.Ji); free(g.Jj); free(DR); free(X); free(Xn);
     return iters;
+}
+
+int orc_pg_solve_init(const double* dr, int total, const orc_lc_edge* edges, int ne, const orc_pg_params* p,
+                      const double* x0_12, int n_init, const double* prior12, double* trace, int trace_cap,
+                      double* out12, double* stats)
+{
+    return orc_pg_solve_path(dr, total, edges, ne, p, x0_12, n_init, prior12, trace, trace_cap, NULL, 0, NULL, out12, stats);
 }
 
 int orc_pg_solve(const double* dr, int total, const orc_lc_edge* edges, int ne, const orc_pg_params* p,
