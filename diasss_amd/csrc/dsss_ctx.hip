@@ -110,21 +110,6 @@ static void free_frame(dsss_frame& f)
     f = dsss_frame();
 }
 
-static void free_match(dsss_ctx* c)
-{
-    hipFree(c->act_s); hipFree(c->act_t); hipFree(c->corres_nn); hipFree(c->corres);
-    hipFree(c->scc_hist); hipFree(c->scc_count); hipFree(c->scc_model);
-    hipFree(c->row_cnt); hipFree(c->kp7_cnt); hipFree(c->row_off); hipFree(c->kp7_off);
-    hipFree(c->rows6); hipFree(c->kp7); hipFree(c->kp7_pair); hipFree(c->kp7_flip);
-    c->act_s = c->act_t = nullptr; c->corres_nn = c->corres = nullptr;
-    c->scc_hist = c->scc_count = nullptr; c->scc_model = nullptr;
-    c->row_cnt = c->kp7_cnt = c->row_off = c->kp7_off = nullptr;
-    c->rows6 = c->kp7 = nullptr; c->kp7_pair = nullptr; c->kp7_flip = nullptr;
-    c->match_cap_pairs = 0; c->rows_cap = 0;
-    hipFree(c->mt_gs_geo); hipFree(c->mt_gs_desc); hipFree(c->mt_gs_idx); hipFree(c->mt_cells);
-    c->mt_gs_geo = nullptr; c->mt_gs_desc = nullptr; c->mt_gs_idx = nullptr; c->mt_cells = nullptr; c->mt_gs_cap = 0; c->mt_cells_bytes = 0;
-}
-
 static void free_store(dsss_ctx* c)
 {
     hipFree(c->desc128); c->desc128 = nullptr;
@@ -142,8 +127,8 @@ void dsss_destroy(dsss_ctx* c)
     for (auto& f : c->frames) free_frame(f);
     for (auto& G : c->gbatches) { hipFree(G.d); if (G.h) hipHostFree(G.h); if (G.ev) hipEventDestroy(G.ev); }
     c->gbatches.clear();
-    free_match(c); free_store(c);
-    hipFree(c->lcs); hipFree(c->ex_scratch); hipFree(c->mt_aux); hipFree(c->tmp_dev); hipFree(c->sift_w);
+    dsss_mt_free(c); free_store(c);
+    hipFree(c->lcs); hipFree(c->ex_scratch); hipFree(c->tmp_dev); hipFree(c->sift_w);
     hipFree(c->ag_buf); if (c->ag_host) hipHostFree(c->ag_host); hipFree(c->xch_dev);
     if (c->pg_edges_host) hipHostFree(c->pg_edges_host);
     if (c->pg_ab_host) hipHostFree(c->pg_ab_host);
@@ -185,7 +170,7 @@ int dsss_set_params(dsss_ctx* c, const dsss_mask_params* mp, const dsss_orb_para
             DSSS_FAIL(c, DSSS_E_ARG, "orb params out of range");
         int k = kcap_for(*op);
         if (k != c->kcap) {
-            if (c->kps) { HIPCHK(c, hipStreamSynchronize(c->stream)); free_store(c); free_match(c); for (auto& f : c->frames) { f.has_feat = false; f.has_sift = false; } }
+            if (c->kps) { HIPCHK(c, hipStreamSynchronize(c->stream)); free_store(c); dsss_mt_free(c); for (auto& f : c->frames) { f.has_feat = false; f.has_sift = false; } }
             c->kcap = k;
         }
         c->op = *op;

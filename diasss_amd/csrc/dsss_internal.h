@@ -102,7 +102,7 @@ struct dsss_ctx {
     const double** d_ptrs = nullptr;                   // [3][max_frames]: alt, gr, pose6 device pointers
     int npairs = 0, nactive = 0;
     std::vector<int> pair_s, pair_t, pair_active;   // pair_active[p] = active index or -1
-    int* act_s = nullptr; int* act_t = nullptr;     // device [nactive]
+    int* act_s = nullptr; int* act_t = nullptr;     // device [nactive]; with kp7_off the per-pair index family (pair_idx_cap): both dsss_match_pairs and dsss_lc_solve_pairs fill it
     int32_t* corres_nn = nullptr;       // [2*nactive][kcap]
     int32_t* corres = nullptr;          // [2*nactive][kcap]
     int* scc_hist = nullptr; int* scc_count = nullptr; double* scc_model = nullptr; // [2*nactive]
@@ -110,7 +110,8 @@ struct dsss_ctx {
     std::vector<int> h_row_off, h_kp7_off;
     double* rows6 = nullptr; double* kp7 = nullptr; int* kp7_pair = nullptr; uint8_t* kp7_flip = nullptr;
     int total_rows = 0, total_kp7 = 0;
-    size_t match_cap_pairs = 0, rows_cap = 0;
+    size_t pair_idx_cap = 0, match_cap_pairs = 0, rows_cap = 0;   // pairs of act_s / act_t / kp7_off; of the matcher's own per-pair buffers; rows of rows6 / kp7 / kp7_pair / kp7_flip
+    bool corres_valid = false;          // corres_nn / corres / scc_* belong to the current result set (dsss_match_pairs', not dsss_lc_solve_pairs')
     // geo grid of the matcher: keypoints of the active pairs' frames sorted by cell (geo, descriptor, original index), cell offsets + tables
     double* mt_gs_geo = nullptr; uint8_t* mt_gs_desc = nullptr; int* mt_gs_idx = nullptr; size_t mt_gs_cap = 0;
     void* mt_cells = nullptr; size_t mt_cells_bytes = 0; unsigned long long mt_evals_host = 0;
@@ -185,6 +186,13 @@ int dsss_frame_geo_bbox(dsss_ctx* c, int id);       // device computation of the
 int dsss_bboxes_enqueue(dsss_ctx* c);               // queue the pending boxes on the context's stream (no synchronisation)
 int dsss_sync_bboxes(dsss_ctx* c);                  // make dsss_frame::bbox valid on the host
 int dsss_frame_kp_geo(dsss_ctx* c, int id, int n);  // geo lookup of the stored keypoints (frame.cpp:126-165)
+// the device buffers of a pair result set have ONE owner, dsss_match.hip: each reserve grows one family (synchronise, free + null, allocate, then publish the capacity)
+int dsss_mt_reserve_pair_index(dsss_ctx* c, size_t npairs);   // act_s, act_t, kp7_off: what lc_kernel and dsss_posegraph_select read per pair
+int dsss_mt_reserve_pair_match(dsss_ctx* c, size_t npairs);   // corres_nn, corres, scc_*, row_cnt, kp7_cnt, row_off: the matcher's own, 2 * npairs * kcap correspondences
+int dsss_mt_reserve_rows(dsss_ctx* c, size_t n);              // rows6, kp7, kp7_pair, kp7_flip for n rows (+ 1024 when it grows)
+int dsss_mt_upload_ptr_tables(dsss_ctx* c);                   // grows mt_aux, sets d_ptrs and queues the upload of the [3][max_frames] pointer tables
+void dsss_mt_clear_results(dsss_ctx* c);                      // the EMPTY result set: no pairs, no rows, has_lc = false
+void dsss_mt_free(dsss_ctx* c);                               // every buffer above and the geo grid's, and the result set they held (dsss_destroy, dsss_set_params)
 void dsss_pg_free(dsss_ctx* c);
 void dsss_comm_free(dsss_ctx* c);
 int dsss_comm_rank(const dsss_ctx* c);

@@ -509,20 +509,21 @@ __global__ __launch_bounds__(64) void tri_kernel(const double* __restrict__ kp7,
     sss_factor(p, &Tp_t, kp[5], 0.0, e, nullptr, nullptr); o[5] = fabs(e[0]); o[6] = fabs(e[1]);
 }
 
-static int ensure_ptr_tables(dsss_ctx* c)
+// caller-supplied kp7 rows: pings and bins index altitude / ground-range tables on the device, so they are range-checked on the host first
+// (GetKpsPairs never emits |bin - M/2| < 20, optimizer.cpp:602-609; bin - M/2 == M/2 is the one-past-the-end read).  pair < 0: no pair to name.
+static int check_kp7_rows(dsss_ctx* c, const dsss_frame& fs, const dsss_frame& ft, const double* rows, int n, int pair)
 {
-    const int F = c->max_frames;
-    std::vector<const double*> hp(3 * (size_t)F, nullptr);
-    for (int f = 0; f < F; ++f) { hp[f] = c->frames[f].alt; hp[F + f] = c->frames[f].gr; hp[2 * F + f] = c->frames[f].pose6; }
-    const size_t need = hp.size() * sizeof(double*) + 2 * (size_t)c->mt.scc_iters * sizeof(uint32_t);
-    if (c->mt_aux_bytes < need) {
-        HIPCHK(c, hipStreamSynchronize(c->stream)); hipFree(c->mt_aux); c->mt_aux = nullptr; c->mt_aux_bytes = 0;
-        HIPCHK(c, hipMalloc(&c->mt_aux, need)); c->mt_aux_bytes = need;
+    for (int i = 0; i < n; ++i) {
+        const double* k = rows + (size_t)i * 7;
+        if (k[0] >= 0 && k[0] < fs.N && k[3] >= 0 && k[3] < ft.N && k[1] >= 1 && k[1] < fs.M && k[4] >= 1 && k[4] < ft.M) continue;
+        char who[32] = ""; if (pair >= 0) snprintf(who, sizeof who, "pair %d ", pair);
+        DSSS_FAIL(c, DSSS_E_ARG, "%skp7 row %d: ping/bin outside the frames (%g,%g | %g,%g)", who, i, k[0], k[1], k[3], k[4]);
     }
-    c->d_ptrs = (const double**)c->mt_aux;
-    HIPCHK(c, hipMemcpyAsync((void*)c->d_ptrs, hp.data(), hp.size() * sizeof(double*), hipMemcpyHostToDevice, c->stream));
     return DSSS_OK;
 }
+
+// a temporary device allocation of one call: freed on every way out of it
+struct dev_tmp { void* p = nullptr; hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes); } ~dev_tmp() { hipFree(p); } };
 
 extern "C" {
 
@@ -531,18 +532,20 @@ int dsss_lc_solve_all(dsss_ctx* c)
     if (!c) return DSSS_E_ARG;
     HIPCHK(c, hipSetDevice(c->device));
     const int n = c->total_kp7;
-    c->has_lc = true; ++c->lc_gen;
-    if (n == 0) return DSSS_OK;
+    c->has_lc = false;
     if ((size_t)n > c->lcs_cap) {
-        HIPCHK(c, hipStreamSynchronize(c->stream)); hipFree(c->lcs); c->lcs = nullptr;
+        HIPCHK(c, hipStreamSynchronize(c->stream)); hipFree(c->lcs); c->lcs = nullptr; c->lcs_cap = 0;
+        HIPCHK(c, hipMalloc(&c->lcs, ((size_t)n + 1024) * sizeof(dsss_lc)));
         c->lcs_cap = (size_t)n + 1024;
-        HIPCHK(c, hipMalloc(&c->lcs, c->lcs_cap * sizeof(dsss_lc)));
     }
     const int F = c->max_frames;
-    dsss_scope sc(c, DSSS_K_LC);
-    hipLaunchKernelGGL(lc_kernel, dim3((n + 3) / 4), dim3(64), 0, c->stream, c->kp7, n, c->kp7_pair, c->kp7_flip, c->act_s, c->act_t,
-                       0, 0, 0, c->d_ptrs, c->d_ptrs + F, c->d_ptrs + 2 * F, c->cols_dev, c->lcs);
-    HIPCHK(c, hipGetLastError());
+    if (n > 0) {
+        dsss_scope sc(c, DSSS_K_LC);
+        hipLaunchKernelGGL(lc_kernel, dim3((n + 3) / 4), dim3(64), 0, c->stream, c->kp7, n, c->kp7_pair, c->kp7_flip, c->act_s, c->act_t,
+                           0, 0, 0, c->d_ptrs, c->d_ptrs + F, c->d_ptrs + 2 * F, c->cols_dev, c->lcs);
+        HIPCHK(c, hipGetLastError());
+    }
+    c->has_lc = true; ++c->lc_gen;      // an LC result set exists once its launch is queued (none for an empty one)
     return DSSS_OK;
 }
 
@@ -568,6 +571,7 @@ int dsss_lc_get(dsss_ctx* c, int pair, dsss_lc* out, int cap, int* nout)
 int dsss_lc_solve_pairs(dsss_ctx* c, const int* src_ids, const int* tgt_ids, int npairs, const double* kp7, const int* pair_off)
 {
     if (!c || npairs < 0 || (npairs > 0 && (!src_ids || !tgt_ids || !pair_off))) return DSSS_E_ARG;
+    dsss_mt_clear_results(c);            // whatever fails from here on leaves an EMPTY result set (include/dsss.h)
     HIPCHK(c, hipSetDevice(c->device));
     const int n = npairs > 0 ? pair_off[npairs] : 0;
     if (n < 0 || (n > 0 && !kp7)) return DSSS_E_ARG;
@@ -575,61 +579,39 @@ int dsss_lc_solve_pairs(dsss_ctx* c, const int* src_ids, const int* tgt_ids, int
         const int s = src_ids[p], t = tgt_ids[p];
         if (s < 0 || s >= c->max_frames || t < 0 || t >= c->max_frames || s == t) DSSS_FAIL(c, DSSS_E_ARG, "pair %d: bad frame ids (%d,%d)", p, s, t);
         if (!c->frames[s].has_geom || !c->frames[t].has_geom) DSSS_FAIL(c, DSSS_E_STATE, "pair %d: frames need dsss_frame_set first", p);
-        if (pair_off[p + 1] < pair_off[p]) DSSS_FAIL(c, DSSS_E_ARG, "pair_off is not ascending at pair %d", p);
+        if (pair_off[p + 1] < pair_off[p] || pair_off[0] != 0) DSSS_FAIL(c, DSSS_E_ARG, "pair_off does not start at 0 or is not ascending at pair %d", p);
     }
     int rc = dsss_sync_bboxes(c); if (rc) return rc;
-    rc = ensure_ptr_tables(c); if (rc) return rc;
-    // every listed pair is "active" here: the bookkeeping below is what dsss_match_pairs leaves behind
-    c->npairs = npairs; c->nactive = npairs; c->has_lc = false;
-    c->pair_s.assign(src_ids, src_ids + npairs); c->pair_t.assign(tgt_ids, tgt_ids + npairs);
-    c->pair_active.resize(npairs);
-    for (int p = 0; p < npairs; ++p) c->pair_active[p] = p;
-    c->h_kp7_off.assign(pair_off, pair_off + npairs + 1);
-    c->h_row_off.assign(npairs + 1, 0);
-    c->total_rows = 0; c->total_kp7 = n;
-    if (npairs == 0 || n == 0) { c->has_lc = true; ++c->lc_gen; return DSSS_OK; }
+    if ((rc = dsss_mt_upload_ptr_tables(c))) return rc;
     std::vector<double> h((size_t)n * 7);
-    HIPCHK(c, hipMemcpy(h.data(), kp7, h.size() * sizeof(double), hipMemcpyDefault));
+    if (n > 0) HIPCHK(c, hipMemcpy(h.data(), kp7, h.size() * sizeof(double), hipMemcpyDefault));
     std::vector<int> h_pair(n); std::vector<uint8_t> h_flip(n);
     const double thr = 2 * DSSS_PI_REF / 3;                         // optimizer.cpp:697-703: sticky within one LoopClosingTFs call
-    for (int p = 0; p < npairs; ++p) {
+    for (int p = 0; p < npairs && n > 0; ++p) {
         const dsss_frame &fs = c->frames[src_ids[p]], &ft = c->frames[tgt_ids[p]];
         if (!fs.h_geo || !ft.h_geo) DSSS_FAIL(c, DSSS_E_STATE, "pair %d: host copy of the DR poses missing", p);
+        if ((rc = check_kp7_rows(c, fs, ft, h.data() + (size_t)pair_off[p] * 7, pair_off[p + 1] - pair_off[p], p))) return rc;
         uint8_t flip = 0;
         for (int i = pair_off[p]; i < pair_off[p + 1]; ++i) {
             const double* k = h.data() + (size_t)i * 7;
-            const bool ok = k[0] >= 0 && k[0] < fs.N && k[3] >= 0 && k[3] < ft.N && k[1] >= 1 && k[1] < fs.M && k[4] >= 1 && k[4] < ft.M;
-            if (!ok) DSSS_FAIL(c, DSSS_E_ARG, "pair %d kp7 row %d: ping/bin outside the frames", p, i - pair_off[p]);
             if (std::fabs(fs.h_geo[(size_t)(int)k[0] * 6 + 2]) > thr) flip |= 1;
             if (std::fabs(ft.h_geo[(size_t)(int)k[3] * 6 + 2]) > thr) flip |= 2;
             h_pair[i] = p; h_flip[i] = flip;
         }
     }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if ((size_t)npairs > c->match_cap_pairs) {
-        c->match_cap_pairs = 0;
-        hipFree(c->act_s); c->act_s = nullptr; hipFree(c->act_t); c->act_t = nullptr; hipFree(c->kp7_off); c->kp7_off = nullptr;
-        hipFree(c->corres_nn); c->corres_nn = nullptr; hipFree(c->corres); c->corres = nullptr;
-        hipFree(c->scc_hist); c->scc_hist = nullptr; hipFree(c->scc_count); c->scc_count = nullptr; hipFree(c->scc_model); c->scc_model = nullptr;
-        hipFree(c->row_cnt); c->row_cnt = nullptr; hipFree(c->kp7_cnt); c->kp7_cnt = nullptr; hipFree(c->row_off); c->row_off = nullptr;
-        HIPCHK(c, hipMalloc(&c->act_s, npairs * sizeof(int))); HIPCHK(c, hipMalloc(&c->act_t, npairs * sizeof(int)));
-        HIPCHK(c, hipMalloc(&c->kp7_off, (npairs + 1) * sizeof(int)));
-        // (the matcher's own per-pair buffers are re-created by the next dsss_match_pairs: capacity stays 0)
+    if (n > 0) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));                // queued kernels may still read the buffers written below
+        if ((rc = dsss_mt_reserve_pair_index(c, npairs)) || (rc = dsss_mt_reserve_rows(c, n))) return rc;      // (no correspondences: the matcher's own per-pair buffers are not touched)
+        HIPCHK(c, hipMemcpy(c->act_s, src_ids, npairs * sizeof(int), hipMemcpyHostToDevice)); HIPCHK(c, hipMemcpy(c->act_t, tgt_ids, npairs * sizeof(int), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(c->kp7_off, pair_off, (npairs + 1) * sizeof(int), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(c->kp7, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(c->kp7_pair, h_pair.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice)); HIPCHK(c, hipMemcpy(c->kp7_flip, h_flip.data(), (size_t)n, hipMemcpyHostToDevice));
     }
-    if ((size_t)n > c->rows_cap) {
-        c->rows_cap = 0;
-        hipFree(c->rows6); c->rows6 = nullptr; hipFree(c->kp7); c->kp7 = nullptr; hipFree(c->kp7_pair); c->kp7_pair = nullptr; hipFree(c->kp7_flip); c->kp7_flip = nullptr;
-        const size_t want = (size_t)n + 1024;
-        HIPCHK(c, hipMalloc(&c->rows6, want * 6 * sizeof(double))); HIPCHK(c, hipMalloc(&c->kp7, want * 7 * sizeof(double)));
-        HIPCHK(c, hipMalloc(&c->kp7_pair, want * sizeof(int))); HIPCHK(c, hipMalloc(&c->kp7_flip, want));
-        c->rows_cap = want;
-    }
-    HIPCHK(c, hipMemcpy(c->act_s, src_ids, npairs * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->act_t, tgt_ids, npairs * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->kp7_off, pair_off, (npairs + 1) * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->kp7, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->kp7_pair, h_pair.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->kp7_flip, h_flip.data(), (size_t)n, hipMemcpyHostToDevice));
+    // publish: every listed pair is "active", in the caller's order, with no matcher rows and no correspondences (corres_valid stays false)
+    c->npairs = c->nactive = npairs; c->total_kp7 = n;
+    c->pair_s.assign(src_ids, src_ids + npairs); c->pair_t.assign(tgt_ids, tgt_ids + npairs);
+    c->pair_active.resize(npairs); for (int p = 0; p < npairs; ++p) c->pair_active[p] = p;
+    c->h_row_off.assign(npairs + 1, 0); if (npairs > 0) c->h_kp7_off.assign(pair_off, pair_off + npairs + 1);
     return dsss_lc_solve_all(c);
 }
 
@@ -640,34 +622,24 @@ int dsss_lc_solve(dsss_ctx* c, int id_s, int id_t, const double* kp7, int n, dss
     if (!c->frames[id_s].has_geom || !c->frames[id_t].has_geom) DSSS_FAIL(c, DSSS_E_STATE, "frames need dsss_frame_set first");
     if (n == 0) return DSSS_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    {   // caller-supplied kp7: pings and bins index altitude / ground-range tables on the device, so range-check them here
-        // (GetKpsPairs never emits |bin - M/2| < 20, optimizer.cpp:602-609; bin - M/2 == M/2 is the one-past-the-end read)
-        std::vector<double> h((size_t)n * 7);
-        HIPCHK(c, hipMemcpy(h.data(), kp7, h.size() * sizeof(double), hipMemcpyDefault));
-        const dsss_frame &fs = c->frames[id_s], &ft = c->frames[id_t];
-        for (int i = 0; i < n; ++i) {
-            const double* k = h.data() + (size_t)i * 7;
-            const bool ok = k[0] >= 0 && k[0] < fs.N && k[3] >= 0 && k[3] < ft.N && k[1] >= 1 && k[1] < fs.M && k[4] >= 1 && k[4] < ft.M;
-            if (!ok) DSSS_FAIL(c, DSSS_E_ARG, "kp7 row %d: ping/bin outside the frames (%g,%g | %g,%g)", i, k[0], k[1], k[3], k[4]);
-        }
-    }
-    int rc = dsss_sync_bboxes(c); if (rc) return rc;          // also publishes the frames' N and M to the device tables
-    rc = ensure_ptr_tables(c); if (rc) return rc;
-    double* d_kp7 = nullptr; dsss_lc* d_out = nullptr;
-    HIPCHK(c, hipMalloc(&d_kp7, (size_t)n * 7 * sizeof(double)));
-    HIPCHK(c, hipMalloc(&d_out, (size_t)n * sizeof(dsss_lc)));
-    HIPCHK(c, hipMemcpyAsync(d_kp7, kp7, (size_t)n * 7 * sizeof(double), hipMemcpyDefault, c->stream));
+    std::vector<double> h((size_t)n * 7);                      // host copy (the caller's pointer may be a device pointer): checked, then uploaded
+    HIPCHK(c, hipMemcpy(h.data(), kp7, h.size() * sizeof(double), hipMemcpyDefault));
+    int rc = check_kp7_rows(c, c->frames[id_s], c->frames[id_t], h.data(), n, -1); if (rc) return rc;
+    if ((rc = dsss_sync_bboxes(c))) return rc;                 // also publishes the frames' N and M to the device tables
+    if ((rc = dsss_mt_upload_ptr_tables(c))) return rc;
+    dev_tmp d_kp7, d_out;
+    HIPCHK(c, d_kp7.alloc(h.size() * sizeof(double)));
+    HIPCHK(c, d_out.alloc((size_t)n * sizeof(dsss_lc)));
+    HIPCHK(c, hipMemcpyAsync(d_kp7.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
     const int F = c->max_frames;
     {
         dsss_scope sc(c, DSSS_K_LC);
-        hipLaunchKernelGGL(lc_kernel, dim3((n + 3) / 4), dim3(64), 0, c->stream, d_kp7, n, (const int*)nullptr, (const uint8_t*)nullptr,
-                           (const int*)nullptr, (const int*)nullptr, id_s, id_t, 0, c->d_ptrs, c->d_ptrs + F, c->d_ptrs + 2 * F, c->cols_dev, d_out);
+        hipLaunchKernelGGL(lc_kernel, dim3((n + 3) / 4), dim3(64), 0, c->stream, (const double*)d_kp7.p, n, (const int*)nullptr, (const uint8_t*)nullptr,
+                           (const int*)nullptr, (const int*)nullptr, id_s, id_t, 0, c->d_ptrs, c->d_ptrs + F, c->d_ptrs + 2 * F, c->cols_dev, (dsss_lc*)d_out.p);
     }
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, (size_t)n * sizeof(dsss_lc), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    hipFree(d_kp7); hipFree(d_out);
-    HIPCHK(c, e);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(out, d_out.p, (size_t)n * sizeof(dsss_lc), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return DSSS_OK;
 }
 
@@ -683,23 +655,15 @@ int dsss_triangulate(dsss_ctx* c, int id_s, int id_t, const double* kp7, int n, 
     HIPCHK(c, hipSetDevice(c->device));
     std::vector<double> h((size_t)n * 7);
     HIPCHK(c, hipMemcpy(h.data(), kp7, h.size() * sizeof(double), hipMemcpyDefault));
-    for (int i = 0; i < n; ++i) {
-        const double* k = h.data() + (size_t)i * 7;
-        const bool ok = k[0] >= 0 && k[0] < fs.N && k[3] >= 0 && k[3] < ft.N && k[1] >= 1 && k[1] < fs.M && k[4] >= 1 && k[4] < ft.M;
-        if (!ok) DSSS_FAIL(c, DSSS_E_ARG, "kp7 row %d: ping/bin outside the frames", i);
-    }
-    double* d_kp7 = nullptr; double* d_out = nullptr;
-    HIPCHK(c, hipMalloc(&d_kp7, h.size() * sizeof(double)));
-    hipError_t e = hipMalloc(&d_out, h.size() * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpyAsync(d_kp7, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(tri_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, d_kp7, n, fs.pose6, fs.alt, fs.gr, fs.M, ft.pose6, ft.alt, ft.gr, ft.M, (const double*)nullptr, d_out);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(out7, d_out, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    hipFree(d_kp7); hipFree(d_out);
-    HIPCHK(c, e);
+    int rc = check_kp7_rows(c, fs, ft, h.data(), n, -1); if (rc) return rc;
+    dev_tmp d_kp7, d_out;
+    HIPCHK(c, d_kp7.alloc(h.size() * sizeof(double)));
+    HIPCHK(c, d_out.alloc(h.size() * sizeof(double)));
+    HIPCHK(c, hipMemcpyAsync(d_kp7.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(tri_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, (const double*)d_kp7.p, n, fs.pose6, fs.alt, fs.gr, fs.M, ft.pose6, ft.alt, ft.gr, ft.M, (const double*)nullptr, (double*)d_out.p);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(out7, d_out.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return DSSS_OK;
 }
 
@@ -710,20 +674,16 @@ int dsss_triangulate_poses(dsss_ctx* c, const double* kp7, const double* in27, i
     if (!c || n < 0 || (n > 0 && (!kp7 || !in27 || !out7))) return DSSS_E_ARG;
     if (n == 0) return DSSS_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    double* d = nullptr;
-    HIPCHK(c, hipMalloc(&d, (size_t)n * (7 + 27 + 7) * sizeof(double)));
-    double* d_kp7 = d; double* d_in = d + (size_t)n * 7; double* d_out = d_in + (size_t)n * 27;
-    hipError_t e = hipMemcpyAsync(d_kp7, kp7, (size_t)n * 7 * sizeof(double), hipMemcpyDefault, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_in, in27, (size_t)n * 27 * sizeof(double), hipMemcpyDefault, c->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(tri_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, d_kp7, n, (const double*)nullptr, (const double*)nullptr, (const double*)nullptr, 0,
-                           (const double*)nullptr, (const double*)nullptr, (const double*)nullptr, 0, (const double*)d_in, d_out);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(out7, d_out, (size_t)n * 7 * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    hipFree(d);
-    HIPCHK(c, e);
+    dev_tmp d;
+    HIPCHK(c, d.alloc((size_t)n * (7 + 27 + 7) * sizeof(double)));
+    double* d_kp7 = (double*)d.p; double* d_in = d_kp7 + (size_t)n * 7; double* d_out = d_in + (size_t)n * 27;
+    HIPCHK(c, hipMemcpyAsync(d_kp7, kp7, (size_t)n * 7 * sizeof(double), hipMemcpyDefault, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_in, in27, (size_t)n * 27 * sizeof(double), hipMemcpyDefault, c->stream));
+    hipLaunchKernelGGL(tri_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, d_kp7, n, (const double*)nullptr, (const double*)nullptr, (const double*)nullptr, 0,
+                       (const double*)nullptr, (const double*)nullptr, (const double*)nullptr, 0, (const double*)d_in, d_out);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(out7, d_out, (size_t)n * 7 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return DSSS_OK;
 }
 

@@ -4,7 +4,7 @@
 // ConsistentCheck (:323-405) + RobustMatching rows (:35-45) + Optimizer::GetKpsPairs (optimizer.cpp:575-639)
 // as ordered block compactions.  Integer results are bit-exact against oracle/orc_match.c.
 #include "dsss_internal.h"
-#include <functional>
+#include <type_traits>
 
 #define MT_TILE 256          // threads per block = keypoints of A per block = B entries per LDS tile
 
@@ -594,205 +594,268 @@ static double gate_threshold(double radius)
     return t;
 }
 
+// ------------------------------------------------------------------ the device buffers of a pair result set (dsss_internal.h)
+// Allocated and freed HERE only, one family per capacity field.  Every reserve: synchronise the stream (a queued kernel may still read the old buffers), free + null,
+// and publish the new capacity only after every allocation of the family succeeded -- a failed hipMalloc leaves capacity 0 and null pointers: the next call starts over, dsss_destroy is safe.
+static void free_pair_index(dsss_ctx* c) { c->pair_idx_cap = 0; DSSS_FREE0(c->act_s); DSSS_FREE0(c->act_t); DSSS_FREE0(c->kp7_off); }
+static void free_pair_match(dsss_ctx* c)
+{
+    c->match_cap_pairs = 0; DSSS_FREE0(c->corres_nn); DSSS_FREE0(c->corres); DSSS_FREE0(c->scc_hist); DSSS_FREE0(c->scc_count); DSSS_FREE0(c->scc_model);
+    DSSS_FREE0(c->row_cnt); DSSS_FREE0(c->kp7_cnt); DSSS_FREE0(c->row_off);
+}
+static void free_rows(dsss_ctx* c) { c->rows_cap = 0; DSSS_FREE0(c->rows6); DSSS_FREE0(c->kp7); DSSS_FREE0(c->kp7_pair); DSSS_FREE0(c->kp7_flip); }
+static void free_aux(dsss_ctx* c) { c->mt_aux_bytes = 0; c->d_ptrs = nullptr; DSSS_FREE0(c->mt_aux); }
+static void free_grid_sorted(dsss_ctx* c) { c->mt_gs_cap = 0; DSSS_FREE0(c->mt_gs_geo); DSSS_FREE0(c->mt_gs_desc); DSSS_FREE0(c->mt_gs_idx); }
+static void free_grid_cells(dsss_ctx* c) { c->mt_cells_bytes = 0; DSSS_FREE0(c->mt_cells); }
+int dsss_mt_reserve_pair_index(dsss_ctx* c, size_t np)
+{
+    if (np <= c->pair_idx_cap) return DSSS_OK;
+    HIPCHK(c, hipStreamSynchronize(c->stream)); free_pair_index(c);
+    HIPCHK(c, hipMalloc(&c->act_s, np * sizeof(int))); HIPCHK(c, hipMalloc(&c->act_t, np * sizeof(int))); HIPCHK(c, hipMalloc(&c->kp7_off, (np + 1) * sizeof(int)));
+    c->pair_idx_cap = np; return DSSS_OK;
+}
+int dsss_mt_reserve_pair_match(dsss_ctx* c, size_t np)
+{
+    if (np <= c->match_cap_pairs) return DSSS_OK;
+    HIPCHK(c, hipStreamSynchronize(c->stream)); free_pair_match(c);
+    HIPCHK(c, hipMalloc(&c->corres_nn, 2 * np * c->kcap * sizeof(int32_t))); HIPCHK(c, hipMalloc(&c->corres, 2 * np * c->kcap * sizeof(int32_t)));
+    HIPCHK(c, hipMalloc(&c->scc_hist, 2 * np * sizeof(int))); HIPCHK(c, hipMalloc(&c->scc_count, 2 * np * sizeof(int)));
+    HIPCHK(c, hipMalloc(&c->scc_model, 2 * np * sizeof(double)));
+    HIPCHK(c, hipMalloc(&c->row_cnt, np * sizeof(int))); HIPCHK(c, hipMalloc(&c->kp7_cnt, np * sizeof(int))); HIPCHK(c, hipMalloc(&c->row_off, (np + 1) * sizeof(int)));
+    c->match_cap_pairs = np; return DSSS_OK;
+}
+int dsss_mt_reserve_rows(dsss_ctx* c, size_t n)
+{
+    if (n <= c->rows_cap) return DSSS_OK;
+    HIPCHK(c, hipStreamSynchronize(c->stream)); free_rows(c);
+    const size_t want = n + 1024;
+    HIPCHK(c, hipMalloc(&c->rows6, want * 6 * sizeof(double))); HIPCHK(c, hipMalloc(&c->kp7, want * 7 * sizeof(double)));
+    HIPCHK(c, hipMalloc(&c->kp7_pair, want * sizeof(int))); HIPCHK(c, hipMalloc(&c->kp7_flip, want));
+    c->rows_cap = want; return DSSS_OK;
+}
+// mt_aux = the [3][max_frames] device pointers alt, gr, pose6 (d_ptrs; small, rebuilt per call), then the 2 * scc_iters words of the cv::RNG stream
+static uint32_t* aux_rng_words(dsss_ctx* c) { return (uint32_t*)((char*)c->mt_aux + 3 * (size_t)c->max_frames * sizeof(double*)); }
+int dsss_mt_upload_ptr_tables(dsss_ctx* c)
+{
+    const int F = c->max_frames;
+    std::vector<const double*> hp(3 * (size_t)F, nullptr);
+    for (int f = 0; f < F; ++f) { hp[f] = c->frames[f].alt; hp[F + f] = c->frames[f].gr; hp[2 * F + f] = c->frames[f].pose6; }
+    const size_t need = hp.size() * sizeof(double*) + 2 * (size_t)c->mt.scc_iters * sizeof(uint32_t);
+    if (c->mt_aux_bytes < need) {
+        HIPCHK(c, hipStreamSynchronize(c->stream)); free_aux(c);
+        HIPCHK(c, hipMalloc(&c->mt_aux, need)); c->mt_aux_bytes = need;
+    }
+    c->d_ptrs = (const double**)c->mt_aux;
+    HIPCHK(c, hipMemcpyAsync((void*)c->d_ptrs, hp.data(), hp.size() * sizeof(double*), hipMemcpyHostToDevice, c->stream));
+    return DSSS_OK;
+}
+
+// the geo grid's own buffers (matcher only): the sorted copies of [F][kcap] keypoints, and tables + cell offsets with a quarter of headroom
+static int reserve_grid(dsss_ctx* c, size_t FK, size_t cells_bytes)
+{
+    if (c->mt_gs_cap != FK) {
+        HIPCHK(c, hipStreamSynchronize(c->stream)); free_grid_sorted(c);
+        HIPCHK(c, hipMalloc(&c->mt_gs_geo, FK * 2 * sizeof(double))); HIPCHK(c, hipMalloc(&c->mt_gs_desc, FK * 32)); HIPCHK(c, hipMalloc(&c->mt_gs_idx, FK * sizeof(int)));
+        c->mt_gs_cap = FK;
+    }
+    if (c->mt_cells_bytes < cells_bytes) {
+        HIPCHK(c, hipStreamSynchronize(c->stream)); free_grid_cells(c);
+        HIPCHK(c, hipMalloc(&c->mt_cells, cells_bytes + cells_bytes / 4)); c->mt_cells_bytes = cells_bytes + cells_bytes / 4;
+    }
+    return DSSS_OK;
+}
+void dsss_mt_clear_results(dsss_ctx* c)
+{
+    c->npairs = c->nactive = 0; c->total_rows = c->total_kp7 = 0; c->has_lc = false; c->corres_valid = false;
+    c->pair_s.clear(); c->pair_t.clear(); c->pair_active.clear(); c->h_row_off.assign(1, 0); c->h_kp7_off.assign(1, 0);
+}
+void dsss_mt_free(dsss_ctx* c)
+{
+    dsss_mt_clear_results(c);            // the bookkeeping describes these buffers
+    free_pair_index(c); free_pair_match(c); free_rows(c); free_aux(c); free_grid_sorted(c); free_grid_cells(c);
+}
+
+// dsss_match_params::use_l2 -> the kernels' MODE, chosen in ONE place: fn gets it as a compile-time constant
+template <class Fn> static void with_mode(int use_l2, Fn&& fn)
+{
+    if (use_l2 == 2) fn(std::integral_constant<int, 2>()); else if (use_l2) fn(std::integral_constant<int, 1>()); else fn(std::integral_constant<int, 0>());
+}
+
+// ------------------------------------------------------------------ host flow of dsss_match_pairs
+// In the manner of ex_run (dsss_extract.hip): the call's state and one method per stage, in the order of run().  Everything is built in the run's own
+// members; the context's result set is written by publish() alone, after the last launch.
+struct mt_run {
+    dsss_ctx* const c; const int* const src; const int* const tgt; const int npairs; const dsss_switches sw;      // ---- the call
+    const int F; const size_t K; const int iters;
+    // ---- the plan: active pairs, launch sizes, the gate, the matcher's algorithmic work, the grid's host half
+    std::vector<int> as, at, active; int na = 0, max_nkp = 0; double T = 0, evals = 0;
+    bool use_grid = false; double inv_cs = 0; std::vector<mt_grid> gtab; std::vector<int> gframes; size_t gcells = 0;
+    // ---- views into mt_cells (grid only; d_evals: profile only) and the downloaded offsets
+    mt_grid* d_tab = nullptr; int *d_frames = nullptr, *d_start = nullptr, *d_cur = nullptr; unsigned long long* d_evals = nullptr;
+    std::vector<int> h_row_off, h_kp7_off;
+    mt_run(dsss_ctx* c_, const int* s_, const int* t_, int n_) : c(c_), src(s_), tgt(t_), npairs(n_), sw(dsss_switches_read()), F(c_->max_frames), K(c_->kcap), iters(c_->mt.scc_iters) {}
+    int run() {
+        int rc = plan(); if (rc) return rc;
+        if (na > 0) {
+            use_grid = plan_grid();
+            if ((rc = reserve()) || (rc = upload_tables()) || (rc = enqueue_nn()) || (rc = enqueue_scc()) || (rc = enqueue_row_counts()) || (rc = finish())) return rc;
+        }
+        publish(); return DSSS_OK;
+    }
+
+    int plan() {
+        int rc = dsss_sync_bboxes(c); if (rc) return rc;
+        active.assign(npairs, -1);
+        for (int p = 0; p < npairs; ++p) {
+            const int s = src[p], t = tgt[p];
+            if (s < 0 || s >= F || t < 0 || t >= F || s == t) DSSS_FAIL(c, DSSS_E_ARG, "pair %d: bad frame ids (%d,%d)", p, s, t);
+            const dsss_frame &a = c->frames[s], &b = c->frames[t];
+            if (!a.has_feat || !b.has_feat) DSSS_FAIL(c, DSSS_E_STATE, "pair %d: frames %d/%d have no features", p, s, t);
+            if (c->mt.use_l2 == 2 && (!a.has_sift || !b.has_sift)) DSSS_FAIL(c, DSSS_E_STATE, "pair %d: use_l2 = 2 needs the 128-element rows of frames %d/%d (dsss_orb_params.descriptor = DSSS_DESC_SIFT128)", p, s, t);
+            // a keypoint outside the other frame's geo box is skipped (FEAmatcher.cpp:84), so disjoint boxes match nothing
+            const bool disjoint = a.bbox[1] < b.bbox[0] || b.bbox[1] < a.bbox[0] || a.bbox[3] < b.bbox[2] || b.bbox[3] < a.bbox[2];
+            if (disjoint || a.nkp == 0 || b.nkp == 0) continue;
+            active[p] = (int)as.size(); as.push_back(s); at.push_back(t);
+            evals += 2.0 * a.nkp * b.nkp;      // algorithmic work of the matcher: gate + Hamming evaluations = sum over the directed active pairs of Na x Nb
+        }
+        na = (int)as.size();
+        h_row_off.assign(na + 1, 0); h_kp7_off.assign(na + 1, 0);
+        for (int f = 0; f < F; ++f) if (c->frames[f].has_feat) max_nkp = std::max(max_nkp, c->frames[f].nkp);
+        T = gate_threshold(c->mt.radius);
+        if (na > 0 && scc_lds() > 150 * 1024) DSSS_FAIL(c, DSSS_E_CAPACITY, "SCC kernel needs %zu B of LDS", scc_lds());
+        return DSSS_OK;
+    }
+    size_t scc_lds() const { return K * 8 + (size_t)iters * 4; }
+
+    // geo grid over the frames of the active pairs (match_grid_kernel); the all-pairs kernel stays for a degenerate geometry (a
+    // non-finite box or radius, or a box of more than 2^22 cells) and as the A/B switch DSSS_MT_GRID=0
+    bool plan_grid() {
+        if (!(sw.mt_grid && std::isfinite(c->mt.radius) && c->mt.radius > 0)) return false;
+        const double cs = c->mt.radius / MT_SUB * (1.0 + 1.0 / 1048576.0); inv_cs = 1.0 / cs;      // the hair: 1e-6 of a cell against 1e-13 of rounding
+        gtab.assign(F, mt_grid{ 0, 0, 0, 0 });
+        std::vector<char> seen(F, 0);
+        for (int a2 = 0; a2 < na; ++a2)
+            for (int f : { as[a2], at[a2] }) {
+                if (seen[f]) continue; else seen[f] = 1;
+                const double* b = c->frames[f].bbox;
+                const double w = (b[1] - b[0]) * inv_cs, h = (b[3] - b[2]) * inv_cs;
+                if (!(std::isfinite(b[0]) && std::isfinite(b[2]) && w >= 0 && h >= 0 && (w + 1) * (h + 1) < 4194304.0)) return false;
+                mt_grid& g = gtab[f];
+                g.W = (int)w + 1; g.H = (int)h + 1; g.off = (int)gcells; gcells += (size_t)g.W * g.H + 1;
+                gframes.push_back(f);
+            }
+        return gcells < (size_t)1 << 30;
+    }
+
+    int reserve() {
+        int rc;
+        if ((rc = dsss_mt_reserve_pair_index(c, na)) || (rc = dsss_mt_reserve_pair_match(c, na)) || !use_grid) return rc;
+        if ((rc = reserve_grid(c, (size_t)F * K, 2 * gcells * sizeof(int) + (size_t)F * sizeof(mt_grid) + (size_t)F * sizeof(int) + 16))) return rc;
+        char* base = (char*)c->mt_cells;
+        d_tab = (mt_grid*)base;                                                   // [F] (16-byte entries first: alignment)
+        d_frames = (int*)(base + (size_t)F * sizeof(mt_grid));                    // [frames of the active pairs]
+        d_start = d_frames + F; d_cur = d_start + gcells;
+        if (c->prof.on) d_evals = (unsigned long long*)(((uintptr_t)(d_cur + gcells) + 7) & ~(uintptr_t)7);
+        return DSSS_OK;
+    }
+
+    int upload_tables() {
+        HIPCHK(c, hipMemcpyAsync(c->act_s, as.data(), na * sizeof(int), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->act_t, at.data(), na * sizeof(int), hipMemcpyHostToDevice, c->stream));
+        int rc = dsss_mt_upload_ptr_tables(c); if (rc) return rc;
+        std::vector<uint32_t> raw(2 * (size_t)iters);
+        { uint64_t st = 0xffffffffu; for (auto& r : raw) { st = (uint64_t)(uint32_t)st * 4164903690U + (uint32_t)(st >> 32); r = (uint32_t)st; } }
+        HIPCHK(c, hipMemcpyAsync(aux_rng_words(c), raw.data(), raw.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        if (!use_grid) return DSSS_OK;
+        if (d_evals) HIPCHK(c, hipMemsetAsync(d_evals, 0, sizeof(unsigned long long), c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_tab, gtab.data(), (size_t)F * sizeof(mt_grid), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_frames, gframes.data(), gframes.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+        return DSSS_OK;
+    }
+
+    int enqueue_nn() {
+        const dsss_match_params& m = c->mt;
+        const dim3 grid((max_nkp + MT_TILE - 1) / MT_TILE, 2 * na);
+        if (use_grid) {
+            dsss_scope sc(c, DSSS_K_MATCH, evals, 2);
+            const dim3 ggrid((max_nkp + MT_TILE / MT_LPQ - 1) / (MT_TILE / MT_LPQ), 2 * na);
+            hipLaunchKernelGGL(mt_grid_build_kernel, dim3((unsigned)gframes.size()), dim3(MTG_THREADS), 0, c->stream, d_frames, d_tab, c->nkp_dev, c->desc, c->geo,
+                               c->bbox_dev, (int)K, inv_cs, d_start, d_cur, (double2*)c->mt_gs_geo, (uint4*)c->mt_gs_desc, c->mt_gs_idx);
+            const uint4* sdesc = (const uint4*)(m.use_l2 == 2 ? c->desc128 : c->mt_gs_desc);      // MODE 2 reads the store's 128-byte rows
+            with_mode(m.use_l2, [&](auto mode) {
+                hipLaunchKernelGGL(match_grid_kernel<decltype(mode)::value>, ggrid, dim3(MT_TILE), 0, c->stream, c->act_s, c->act_t, c->nkp_dev, c->bbox_dev, d_tab,
+                                   d_start, (const double2*)c->mt_gs_geo, sdesc, c->mt_gs_idx, (int)K, inv_cs, T, m.bound_same, m.bound_diff, m.l2_bound, m.ratio, c->corres_nn); });
+            HIPCHK(c, hipGetLastError());
+        } else {
+            dsss_scope sc(c, DSSS_K_MATCH, evals);
+            if (c->prof.on) c->prof.work[DSSS_K_MATCH_DONE] += evals;      // the all-pairs kernel performs every evaluation it is credited with
+            with_mode(m.use_l2, [&](auto mode) {
+                hipLaunchKernelGGL(match_nn_kernel<decltype(mode)::value>, grid, dim3(MT_TILE), 0, c->stream, c->act_s, c->act_t, c->nkp_dev,
+                                   m.use_l2 == 2 ? c->desc128 : c->desc, c->geo, c->bbox_dev, (int)K, T, m.bound_same, m.bound_diff, m.l2_bound, m.ratio, c->corres_nn); });
+            HIPCHK(c, hipGetLastError());
+        }
+        if (!d_evals) return DSSS_OK;
+        // (profile on) the grid's evaluations, counted behind the matcher's closed scope; finish() adds them to the work done
+        hipLaunchKernelGGL(mt_grid_count_kernel, grid, dim3(MT_TILE), 0, c->stream, c->act_s, c->act_t, c->nkp_dev, c->bbox_dev, d_tab, d_start, (const double2*)c->mt_gs_geo, (int)K, inv_cs, d_evals);
+        HIPCHK(c, hipMemcpyAsync(&c->mt_evals_host, d_evals, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+        return DSSS_OK;
+    }
+
+    int enqueue_scc() {
+        dsss_scope sc(c, DSSS_K_SCC);
+        hipLaunchKernelGGL(scc_kernel, dim3(2 * na), dim3(256), scc_lds(), c->stream, c->act_s, c->act_t, c->nkp_dev, c->rows_dev, c->kps, (int)K,
+                           aux_rng_words(c), iters, c->mt.pix_err, c->corres_nn, c->corres, c->scc_hist, c->scc_count, c->scc_model);
+        HIPCHK(c, hipGetLastError());
+        return DSSS_OK;
+    }
+
+    template <bool WRITE> hipError_t launch_rows() {      // the count pass (nothing but row_cnt / kp7_cnt written) and the write pass
+        const double* const* P = c->d_ptrs;
+        hipLaunchKernelGGL(pair_rows_kernel<WRITE>, dim3(na), dim3(256), 0, c->stream, c->act_s, c->act_t, c->nkp_dev, c->rows_dev, c->cols_dev,
+                           c->kps, (int)K, c->corres, c->scc_hist, c->scc_model, c->mt.merge_thr, P, P + F, P + 2 * F, c->row_cnt, c->kp7_cnt,
+                           WRITE ? c->row_off : nullptr, WRITE ? c->kp7_off : nullptr, WRITE ? c->rows6 : nullptr, WRITE ? c->kp7 : nullptr,
+                           WRITE ? c->kp7_pair : nullptr, WRITE ? c->kp7_flip : nullptr);
+        return hipGetLastError();
+    }
+    int enqueue_row_counts() {
+        dsss_scope sc(c, DSSS_K_ROWS);
+        HIPCHK(c, launch_rows<false>());
+        hipLaunchKernelGGL(scan2_kernel, dim3(1), dim3(256), 0, c->stream, c->row_cnt, c->kp7_cnt, na, c->row_off, c->kp7_off);
+        HIPCHK(c, hipGetLastError());
+        return DSSS_OK;
+    }
+
+    // the one synchronisation of the call: the totals size the row buffers of the write pass
+    int finish() {
+        HIPCHK(c, hipMemcpyAsync(h_row_off.data(), c->row_off, (na + 1) * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(h_kp7_off.data(), c->kp7_off, (na + 1) * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (d_evals) c->prof.work[DSSS_K_MATCH_DONE] += (double)c->mt_evals_host;
+        int rc = dsss_mt_reserve_rows(c, h_row_off[na]); if (rc) return rc;
+        if (h_row_off[na] > 0) {
+            dsss_scope sc(c, DSSS_K_ROWS);
+            HIPCHK(c, launch_rows<true>());
+        }
+        return DSSS_OK;
+    }
+
+    void publish() {
+        c->npairs = npairs; c->nactive = na;
+        c->pair_s.assign(src, src + npairs); c->pair_t.assign(tgt, tgt + npairs); c->pair_active.swap(active);
+        c->total_rows = h_row_off[na]; c->total_kp7 = h_kp7_off[na];
+        c->h_row_off.swap(h_row_off); c->h_kp7_off.swap(h_kp7_off);
+        c->corres_valid = true;           // (has_lc stays false: dsss_lc_solve_all has not seen these rows)
+    }
+};
+
 extern "C" {
 
 int dsss_match_pairs(dsss_ctx* c, const int* src_ids, const int* tgt_ids, int npairs)
 {
     if (!c || npairs < 0 || (npairs > 0 && (!src_ids || !tgt_ids))) return DSSS_E_ARG;
+    dsss_mt_clear_results(c);            // whatever fails from here on leaves an EMPTY result set (include/dsss.h)
     HIPCHK(c, hipSetDevice(c->device));
-    const dsss_switches sw = dsss_switches_read();
-    c->npairs = npairs; c->has_lc = false;
-    c->pair_s.assign(src_ids, src_ids + npairs); c->pair_t.assign(tgt_ids, tgt_ids + npairs);
-    c->pair_active.assign(npairs, -1);
-    { int rc = dsss_sync_bboxes(c); if (rc) return rc; }
-    std::vector<int> as, at;
-    for (int p = 0; p < npairs; ++p) {
-        const int s = src_ids[p], t = tgt_ids[p];
-        if (s < 0 || s >= c->max_frames || t < 0 || t >= c->max_frames || s == t) DSSS_FAIL(c, DSSS_E_ARG, "pair %d: bad frame ids (%d,%d)", p, s, t);
-        const dsss_frame &a = c->frames[s], &b = c->frames[t];
-        if (!a.has_feat || !b.has_feat) DSSS_FAIL(c, DSSS_E_STATE, "pair %d: frames %d/%d have no features", p, s, t);
-        if (c->mt.use_l2 == 2 && (!a.has_sift || !b.has_sift)) DSSS_FAIL(c, DSSS_E_STATE, "pair %d: use_l2 = 2 needs the 128-element rows of frames %d/%d (dsss_orb_params.descriptor = DSSS_DESC_SIFT128)", p, s, t);
-        // a keypoint outside the other frame's geo box is skipped (FEAmatcher.cpp:84), so disjoint boxes match nothing
-        const bool disjoint = a.bbox[1] < b.bbox[0] || b.bbox[1] < a.bbox[0] || a.bbox[3] < b.bbox[2] || b.bbox[3] < a.bbox[2];
-        if (!disjoint && a.nkp > 0 && b.nkp > 0) { c->pair_active[p] = (int)as.size(); as.push_back(s); at.push_back(t); }
-    }
-    const int na = (int)as.size();
-    c->nactive = na; c->total_rows = 0; c->total_kp7 = 0;
-    c->h_row_off.assign(na + 1, 0); c->h_kp7_off.assign(na + 1, 0);
-    if (na == 0) return DSSS_OK;
-    const size_t K = c->kcap;
-    if ((size_t)na > c->match_cap_pairs) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        // free + null first and publish the new capacity only after every allocation succeeded, so that a failed
-        // hipMalloc leaves the context consistent (capacity 0, null pointers: the next call starts over, dsss_destroy is safe)
-        c->match_cap_pairs = 0;
-        DSSS_FREE0(c->act_s); DSSS_FREE0(c->act_t); DSSS_FREE0(c->corres_nn); DSSS_FREE0(c->corres);
-        DSSS_FREE0(c->scc_hist); DSSS_FREE0(c->scc_count); DSSS_FREE0(c->scc_model);
-        DSSS_FREE0(c->row_cnt); DSSS_FREE0(c->kp7_cnt); DSSS_FREE0(c->row_off); DSSS_FREE0(c->kp7_off);
-        HIPCHK(c, hipMalloc(&c->act_s, na * sizeof(int))); HIPCHK(c, hipMalloc(&c->act_t, na * sizeof(int)));
-        HIPCHK(c, hipMalloc(&c->corres_nn, 2 * (size_t)na * K * sizeof(int32_t)));
-        HIPCHK(c, hipMalloc(&c->corres, 2 * (size_t)na * K * sizeof(int32_t)));
-        HIPCHK(c, hipMalloc(&c->scc_hist, 2 * na * sizeof(int))); HIPCHK(c, hipMalloc(&c->scc_count, 2 * na * sizeof(int)));
-        HIPCHK(c, hipMalloc(&c->scc_model, 2 * na * sizeof(double)));
-        HIPCHK(c, hipMalloc(&c->row_cnt, na * sizeof(int))); HIPCHK(c, hipMalloc(&c->kp7_cnt, na * sizeof(int)));
-        HIPCHK(c, hipMalloc(&c->row_off, (na + 1) * sizeof(int))); HIPCHK(c, hipMalloc(&c->kp7_off, (na + 1) * sizeof(int)));
-        c->match_cap_pairs = na;
-    }
-    HIPCHK(c, hipMemcpyAsync(c->act_s, as.data(), na * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->act_t, at.data(), na * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    // per-frame pointer tables + RNG stream (small, rebuilt per call)
-    const int F = c->max_frames;
-    std::vector<const double*> hp(3 * (size_t)F, nullptr);
-    for (int f = 0; f < F; ++f) { hp[f] = c->frames[f].alt; hp[F + f] = c->frames[f].gr; hp[2 * F + f] = c->frames[f].pose6; }
-    const int iters = c->mt.scc_iters;
-    std::vector<uint32_t> raw(2 * (size_t)iters);
-    { uint64_t st = 0xffffffffu; for (auto& r : raw) { st = (uint64_t)(uint32_t)st * 4164903690U + (uint32_t)(st >> 32); r = (uint32_t)st; } }
-    const size_t aux_bytes = hp.size() * sizeof(double*) + raw.size() * sizeof(uint32_t);
-    if (c->mt_aux_bytes < aux_bytes) {
-        HIPCHK(c, hipStreamSynchronize(c->stream)); hipFree(c->mt_aux);
-        c->mt_aux = nullptr; c->mt_aux_bytes = 0;
-        HIPCHK(c, hipMalloc(&c->mt_aux, aux_bytes)); c->mt_aux_bytes = aux_bytes;
-    }
-    const double** d_ptrs = (const double**)c->mt_aux;
-    c->d_ptrs = d_ptrs;
-    uint32_t* d_raw = (uint32_t*)((char*)c->mt_aux + hp.size() * sizeof(double*));
-    HIPCHK(c, hipMemcpyAsync(d_ptrs, hp.data(), hp.size() * sizeof(double*), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_raw, raw.data(), raw.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    int max_nkp = 0;
-    for (int f = 0; f < F; ++f) if (c->frames[f].has_feat) max_nkp = std::max(max_nkp, c->frames[f].nkp);
-    const dim3 grid((max_nkp + MT_TILE - 1) / MT_TILE, 2 * na);
-    const double T = gate_threshold(c->mt.radius);
-    // geo grid over the frames of the active pairs (match_grid_kernel); the all-pairs kernel stays for a degenerate geometry (a
-    // non-finite box or radius, or a box of more than 2^22 cells) and as the A/B switch DSSS_MT_GRID=0
-    bool evals_pending = false;
-    std::function<hipError_t()> gcount;                // (profile on) counts the grid's evaluations, launched after the matcher's scope has closed
-    bool use_grid = sw.mt_grid && std::isfinite(c->mt.radius) && c->mt.radius > 0;
-    const double cs = c->mt.radius / MT_SUB * (1.0 + 1.0 / 1048576.0), inv_cs = 1.0 / cs;      // the hair: 1e-6 of a cell against 1e-13 of rounding
-    std::vector<mt_grid> gtab; std::vector<int> gframes; size_t gcells = 0;
-    if (use_grid) {
-        gtab.assign(F, mt_grid{ 0, 0, 0, 0 });
-        std::vector<char> seen(F, 0);
-        for (int a2 = 0; a2 < na && use_grid; ++a2)
-            for (int f : { as[a2], at[a2] }) {
-                if (seen[f]) continue;
-                seen[f] = 1;
-                const double* b = c->frames[f].bbox;
-                const double w = (b[1] - b[0]) * inv_cs, h = (b[3] - b[2]) * inv_cs;
-                if (!(std::isfinite(b[0]) && std::isfinite(b[2]) && w >= 0 && h >= 0 && (w + 1) * (h + 1) < 4194304.0)) { use_grid = false; break; }
-                mt_grid& g = gtab[f];
-                g.W = (int)w + 1; g.H = (int)h + 1; g.off = (int)gcells;
-                gcells += (size_t)g.W * g.H + 1;
-                gframes.push_back(f);
-            }
-        if (gcells >= (size_t)1 << 30) use_grid = false;
-    }
-    if (use_grid) {
-        if (c->mt_gs_cap != (size_t)F * K) {
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            c->mt_gs_cap = 0;
-            DSSS_FREE0(c->mt_gs_geo); DSSS_FREE0(c->mt_gs_desc); DSSS_FREE0(c->mt_gs_idx);
-            HIPCHK(c, hipMalloc(&c->mt_gs_geo, (size_t)F * K * 2 * sizeof(double)));
-            HIPCHK(c, hipMalloc(&c->mt_gs_desc, (size_t)F * K * 32));
-            HIPCHK(c, hipMalloc(&c->mt_gs_idx, (size_t)F * K * sizeof(int)));
-            c->mt_gs_cap = (size_t)F * K;
-        }
-        const size_t need = 2 * gcells * sizeof(int) + (size_t)F * sizeof(mt_grid) + (size_t)F * sizeof(int) + 16;
-        if (c->mt_cells_bytes < need) {
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            c->mt_cells_bytes = 0;
-            DSSS_FREE0(c->mt_cells);
-            HIPCHK(c, hipMalloc(&c->mt_cells, need + need / 4));
-            c->mt_cells_bytes = need + need / 4;
-        }
-        char* base = (char*)c->mt_cells;
-        mt_grid* d_tab = (mt_grid*)base;                                          // [F] (16-byte entries first: alignment)
-        int* d_frames = (int*)(base + (size_t)F * sizeof(mt_grid));               // [frames of the active pairs]
-        int* d_start = d_frames + F; int* d_cur = d_start + gcells;
-        unsigned long long* d_evals = c->prof.on ? (unsigned long long*)(((uintptr_t)(d_cur + gcells) + 7) & ~(uintptr_t)7) : nullptr;
-        if (d_evals) HIPCHK(c, hipMemsetAsync(d_evals, 0, sizeof(unsigned long long), c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_tab, gtab.data(), (size_t)F * sizeof(mt_grid), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_frames, gframes.data(), gframes.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-        double evals = 0;
-        for (int a2 = 0; a2 < na; ++a2) evals += 2.0 * c->frames[as[a2]].nkp * c->frames[at[a2]].nkp;
-        dsss_scope sc(c, DSSS_K_MATCH, evals, 2);
-        const dim3 ggrid((max_nkp + MT_TILE / MT_LPQ - 1) / (MT_TILE / MT_LPQ), 2 * na);
-        hipLaunchKernelGGL(mt_grid_build_kernel, dim3((unsigned)gframes.size()), dim3(MTG_THREADS), 0, c->stream, d_frames, d_tab, c->nkp_dev, c->desc, c->geo,
-                           c->bbox_dev, (int)K, inv_cs, d_start, d_cur, (double2*)c->mt_gs_geo, (uint4*)c->mt_gs_desc, c->mt_gs_idx);
-        if (c->mt.use_l2 == 2)
-            hipLaunchKernelGGL(match_grid_kernel<2>, ggrid, dim3(MT_TILE), 0, c->stream, c->act_s, c->act_t, c->nkp_dev, c->bbox_dev, d_tab, d_start,
-                               (const double2*)c->mt_gs_geo, (const uint4*)c->desc128, c->mt_gs_idx, (int)K, inv_cs, T, c->mt.bound_same, c->mt.bound_diff,
-                               c->mt.l2_bound, c->mt.ratio, c->corres_nn);
-        else if (c->mt.use_l2)
-            hipLaunchKernelGGL(match_grid_kernel<1>, ggrid, dim3(MT_TILE), 0, c->stream, c->act_s, c->act_t, c->nkp_dev, c->bbox_dev, d_tab, d_start,
-                               (const double2*)c->mt_gs_geo, (const uint4*)c->mt_gs_desc, c->mt_gs_idx, (int)K, inv_cs, T, c->mt.bound_same, c->mt.bound_diff,
-                               c->mt.l2_bound, c->mt.ratio, c->corres_nn);
-        else
-            hipLaunchKernelGGL(match_grid_kernel<0>, ggrid, dim3(MT_TILE), 0, c->stream, c->act_s, c->act_t, c->nkp_dev, c->bbox_dev, d_tab, d_start,
-                               (const double2*)c->mt_gs_geo, (const uint4*)c->mt_gs_desc, c->mt_gs_idx, (int)K, inv_cs, T, c->mt.bound_same, c->mt.bound_diff,
-                               c->mt.l2_bound, c->mt.ratio, c->corres_nn);
-        HIPCHK(c, hipGetLastError());
-        evals_pending = d_evals != nullptr;
-        if (d_evals) { gcount = [=]() {
-            hipLaunchKernelGGL(mt_grid_count_kernel, grid, dim3(MT_TILE), 0, c->stream, c->act_s, c->act_t, c->nkp_dev, c->bbox_dev, d_tab, d_start, (const double2*)c->mt_gs_geo, (int)K, inv_cs, d_evals);
-            return hipMemcpyAsync(&c->mt_evals_host, d_evals, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream); }; }
-    } else {
-        // algorithmic work of the matcher: gate + Hamming evaluations = sum over the directed active pairs of Na x Nb
-        double evals = 0;
-        for (int a2 = 0; a2 < na; ++a2) evals += 2.0 * c->frames[as[a2]].nkp * c->frames[at[a2]].nkp;
-        dsss_scope sc(c, DSSS_K_MATCH, evals);
-        if (c->prof.on) c->prof.work[DSSS_K_MATCH_DONE] += evals;      // the all-pairs kernel performs every evaluation it is credited with
-        if (c->mt.use_l2 == 2)
-            hipLaunchKernelGGL(match_nn_kernel<2>, grid, dim3(MT_TILE), 0, c->stream, c->act_s, c->act_t, c->nkp_dev, c->desc128, c->geo,
-                               c->bbox_dev, (int)K, T, c->mt.bound_same, c->mt.bound_diff, c->mt.l2_bound, c->mt.ratio, c->corres_nn);
-        else if (c->mt.use_l2)
-            hipLaunchKernelGGL(match_nn_kernel<1>, grid, dim3(MT_TILE), 0, c->stream, c->act_s, c->act_t, c->nkp_dev, c->desc, c->geo,
-                               c->bbox_dev, (int)K, T, c->mt.bound_same, c->mt.bound_diff, c->mt.l2_bound, c->mt.ratio, c->corres_nn);
-        else
-            hipLaunchKernelGGL(match_nn_kernel<0>, grid, dim3(MT_TILE), 0, c->stream, c->act_s, c->act_t, c->nkp_dev, c->desc, c->geo,
-                               c->bbox_dev, (int)K, T, c->mt.bound_same, c->mt.bound_diff, c->mt.l2_bound, c->mt.ratio, c->corres_nn);
-        HIPCHK(c, hipGetLastError());
-    }
-    if (gcount) HIPCHK(c, gcount());
-    {
-        dsss_scope sc(c, DSSS_K_SCC);
-        const size_t sh = K * 8 + (size_t)iters * 4;
-        if (sh > 150 * 1024) DSSS_FAIL(c, DSSS_E_CAPACITY, "SCC kernel needs %zu B of LDS", sh);
-        hipLaunchKernelGGL(scc_kernel, dim3(2 * na), dim3(256), sh, c->stream, c->act_s, c->act_t, c->nkp_dev, c->rows_dev, c->kps, (int)K,
-                           d_raw, iters, c->mt.pix_err, c->corres_nn, c->corres, c->scc_hist, c->scc_count, c->scc_model);
-        HIPCHK(c, hipGetLastError());
-    }
-    {
-        dsss_scope sc(c, DSSS_K_ROWS);
-        hipLaunchKernelGGL(pair_rows_kernel<false>, dim3(na), dim3(256), 0, c->stream, c->act_s, c->act_t, c->nkp_dev, c->rows_dev, c->cols_dev,
-                           c->kps, (int)K, c->corres, c->scc_hist, c->scc_model, c->mt.merge_thr, d_ptrs, d_ptrs + F, d_ptrs + 2 * F,
-                           c->row_cnt, c->kp7_cnt, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-        HIPCHK(c, hipGetLastError());
-        hipLaunchKernelGGL(scan2_kernel, dim3(1), dim3(256), 0, c->stream, c->row_cnt, c->kp7_cnt, na, c->row_off, c->kp7_off);
-        HIPCHK(c, hipGetLastError());
-    }
-    HIPCHK(c, hipMemcpyAsync(c->h_row_off.data(), c->row_off, (na + 1) * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->h_kp7_off.data(), c->kp7_off, (na + 1) * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (evals_pending) c->prof.work[DSSS_K_MATCH_DONE] += (double)c->mt_evals_host;
-    c->total_rows = c->h_row_off[na]; c->total_kp7 = c->h_kp7_off[na];
-    if ((size_t)c->total_rows > c->rows_cap) {
-        const size_t want = (size_t)c->total_rows + 1024;
-        c->rows_cap = 0;
-        DSSS_FREE0(c->rows6); DSSS_FREE0(c->kp7); DSSS_FREE0(c->kp7_pair); DSSS_FREE0(c->kp7_flip);
-        HIPCHK(c, hipMalloc(&c->rows6, want * 6 * sizeof(double)));
-        HIPCHK(c, hipMalloc(&c->kp7, want * 7 * sizeof(double)));
-        HIPCHK(c, hipMalloc(&c->kp7_pair, want * sizeof(int)));
-        HIPCHK(c, hipMalloc(&c->kp7_flip, want));
-        c->rows_cap = want;
-    }
-    if (c->total_rows > 0) {
-        dsss_scope sc(c, DSSS_K_ROWS);
-        hipLaunchKernelGGL(pair_rows_kernel<true>, dim3(na), dim3(256), 0, c->stream, c->act_s, c->act_t, c->nkp_dev, c->rows_dev, c->cols_dev,
-                           c->kps, (int)K, c->corres, c->scc_hist, c->scc_model, c->mt.merge_thr, d_ptrs, d_ptrs + F, d_ptrs + 2 * F,
-                           c->row_cnt, c->kp7_cnt, c->row_off, c->kp7_off, c->rows6, c->kp7, c->kp7_pair, c->kp7_flip);
-        HIPCHK(c, hipGetLastError());
-    }
-    return DSSS_OK;
+    return mt_run(c, src_ids, tgt_ids, npairs).run();
 }
 
 int dsss_match_get_dir(dsss_ctx* c, int pair, int dir, int32_t* corres_nn, int32_t* corres, int cap, int* hist, int* count, double* model)
@@ -803,6 +866,7 @@ int dsss_match_get_dir(dsss_ctx* c, int pair, int dir, int32_t* corres_nn, int32
     const int n = c->frames[fa].nkp;
     if (cap < n) DSSS_FAIL(c, DSSS_E_CAPACITY, "caller capacity %d < %d", cap, n);
     const int a = c->pair_active[pair];
+    if (a >= 0 && !c->corres_valid) DSSS_FAIL(c, DSSS_E_STATE, "pair %d: the result set is dsss_lc_solve_pairs', which has no correspondences", pair);
     if (a < 0) {
         for (int i = 0; i < n; ++i) { if (corres_nn) corres_nn[i] = -1; if (corres) corres[i] = -1; }
         if (hist) *hist = 0; if (count) *count = 0; if (model) *model = 0;
@@ -818,33 +882,23 @@ int dsss_match_get_dir(dsss_ctx* c, int pair, int dir, int32_t* corres_nn, int32
     return DSSS_OK;
 }
 
-int dsss_match_get_rows(dsss_ctx* c, int pair, double* rows6, int cap, int* nrows)
+// one pair's rows of rows6 / kp7 (width doubles each) to the host; off: the host copy of the active pairs' offsets into the buffer
+static int get_pair_rows(dsss_ctx* c, int pair, std::vector<int> dsss_ctx::*off_, double* dsss_ctx::*dev, int width, double* out, int cap, int* nout)
 {
     if (!c) return DSSS_E_ARG;
     if (pair < 0 || pair >= c->npairs) DSSS_FAIL(c, DSSS_E_ARG, "pair %d out of range", pair);
+    const std::vector<int>& off = c->*off_;
     const int a = c->pair_active[pair];
-    const int n = a < 0 ? 0 : c->h_row_off[a + 1] - c->h_row_off[a];
-    if (nrows) *nrows = n;
-    if (n == 0 || !rows6) return DSSS_OK;
+    const int n = a < 0 ? 0 : off[a + 1] - off[a];
+    if (nout) *nout = n;
+    if (n == 0 || !out) return DSSS_OK;
     if (cap < n) DSSS_FAIL(c, DSSS_E_CAPACITY, "caller capacity %d < %d rows", cap, n);
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(rows6, c->rows6 + (size_t)c->h_row_off[a] * 6, (size_t)n * 6 * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(out, c->*dev + (size_t)off[a] * width, (size_t)n * width * sizeof(double), hipMemcpyDeviceToHost));
     return DSSS_OK;
 }
-
-int dsss_match_get_kp7(dsss_ctx* c, int pair, double* kp7, int cap, int* nout)
-{
-    if (!c) return DSSS_E_ARG;
-    if (pair < 0 || pair >= c->npairs) DSSS_FAIL(c, DSSS_E_ARG, "pair %d out of range", pair);
-    const int a = c->pair_active[pair];
-    const int n = a < 0 ? 0 : c->h_kp7_off[a + 1] - c->h_kp7_off[a];
-    if (nout) *nout = n;
-    if (n == 0 || !kp7) return DSSS_OK;
-    if (cap < n) DSSS_FAIL(c, DSSS_E_CAPACITY, "caller capacity %d < %d", cap, n);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(kp7, c->kp7 + (size_t)c->h_kp7_off[a] * 7, (size_t)n * 7 * sizeof(double), hipMemcpyDeviceToHost));
-    return DSSS_OK;
-}
+int dsss_match_get_rows(dsss_ctx* c, int pair, double* rows6, int cap, int* nrows) { return get_pair_rows(c, pair, &dsss_ctx::h_row_off, &dsss_ctx::rows6, 6, rows6, cap, nrows); }
+int dsss_match_get_kp7(dsss_ctx* c, int pair, double* kp7, int cap, int* nout) { return get_pair_rows(c, pair, &dsss_ctx::h_kp7_off, &dsss_ctx::kp7, 7, kp7, cap, nout); }
 
 int dsss_match_pair_active(dsss_ctx* c, int pair, int* active)
 {

@@ -171,14 +171,20 @@ int dsss_features_unpack(dsss_ctx*, int id, const void* dev_or_host_buf);
  * One call = FEAmatcher::RobustMatching for every listed (source,target) pair, batched on the device:
  * GeoNearNeighSearch both directions (:52-321) + ConsistentCheck (:323-405) + the rows RobustMatching appends
  * to Frame::corres_kps (:35-45) + Optimizer::GetKpsPairs (optimizer.cpp:575-639) on those rows.
- * Results stay on the device; the getters copy one pair out.                                               */
+ * Results stay on the device; the getters copy one pair out.
+ * The RESULT SET of a context (pairs, rows, kp7 lists, LC results) is replaced as a whole by dsss_match_pairs and by dsss_lc_solve_pairs:
+ * either call first empties it, builds the new one aside and publishes it last.  A call that is refused (DSSS_E_ARG, DSSS_E_STATE, ...) or
+ * fails after its argument check therefore leaves an EMPTY set: every getter answers DSSS_E_ARG ("pair out of range"), dsss_match_total
+ * gives (0, 0) and dsss_lc_solve_all launches nothing.                                                       */
 int dsss_match_pairs(dsss_ctx*, const int* src_ids, const int* tgt_ids, int npairs);
 int dsss_match_get_dir(dsss_ctx*, int pair, int dir /*0: s->t, 1: t->s*/, int32_t* corres_nn_host,
                        int32_t* corres_host, int cap, int* scc_hist, int* scc_count, double* scc_model);
 int dsss_match_get_rows(dsss_ctx*, int pair, double* rows6_host, int cap, int* nrows);   /* [id_s,id_t,y_s,x_s,y_t,x_t] */
 int dsss_match_get_kp7(dsss_ctx*, int pair, double* kp7_host, int cap, int* n);          /* Vector7 of optimizer.cpp:625 */
 int dsss_match_total(dsss_ctx*, int* total_rows, int* total_kp7);
-/* 0 when the geo bounding boxes of the pair are disjoint: every keypoint is then skipped by FEAmatcher.cpp:84, no kernel runs */
+/* (dsss_match_get_dir: DSSS_E_STATE for an active pair when the result set is dsss_lc_solve_pairs', which has no correspondences;
+ * dsss_match_get_rows then gives zero rows.)
+ * 0 when the geo bounding boxes of the pair are disjoint: every keypoint is then skipped by FEAmatcher.cpp:84, no kernel runs */
 int dsss_match_pair_active(dsss_ctx*, int pair, int* active_host);
 /* FEAmatcher::DescriptorDistance (FEAmatcher.h:33) on device-resident descriptors of two frames */
 int dsss_descriptor_distance(dsss_ctx*, int id_a, int ia, int id_b, int ib, int* dist_host);
@@ -192,7 +198,9 @@ int dsss_lc_solve(dsss_ctx*, int id_s, int id_t, const double* kp7, int n, dsss_
 /* the same for the kp7 lists of MANY pairs in one launch (the pair loop of TrajOptimizationAll, optimizer.cpp:35-97,
  * with kp7 built by the caller's GetKpsPairs from corres_kps or -- USE_ANNO = 1, optimizer.cpp:26,42-53 -- anno_kps).
  * kp7: pair_off[npairs] x 7 (host or device); pair_off: npairs + 1 ascending offsets (host).  Results stay on the device
- * as after dsss_match_pairs + dsss_lc_solve_all: dsss_lc_get / dsss_posegraph_select / dsss_posegraph_solve follow.     */
+ * as after dsss_match_pairs + dsss_lc_solve_all: dsss_lc_get / dsss_posegraph_select / dsss_posegraph_solve follow.
+ * It replaces the result set under the rule stated at dsss_match_pairs (empty after a refused call); every listed pair is active, with
+ * its kp7 rows, no matcher rows and no correspondences.  pair_off[0] must be 0.                                          */
 int dsss_lc_solve_pairs(dsss_ctx*, const int* src_ids, const int* tgt_ids, int npairs, const double* kp7, const int* pair_off_host);
 /* LMTriaFactor + Optimizer::TriangulateOneLandmark (LMtriangulatefactor.cpp:10-27; optimizer.h:56-59, optimizer.cpp:984-1021)
  * for every kp7 row of one pair, as LoopClosingTFs calls it (optimizer.cpp:907-921: yaw-compensated DR poses, landmark

@@ -243,3 +243,68 @@ def test_range_check_on_all_entry_points(ctx, orc, cases):
             assert ctx.triangulate(s, t, k).tobytes() == tri0.tobytes()
             ctx.lc_solve_pairs([s], [t], [k])
             assert ctx.lc_get(0).tobytes() == pairs0.tobytes()
+
+
+E_ARG, E_STATE = -2, -4
+
+
+def test_refused_lc_solve_pairs_leaves_an_empty_result_set(orc, cases):
+    """dsss_lc_solve_pairs refused for one bad kp7 row (as in test_range_check_on_all_entry_points) of its second pair: the context holds an
+    empty result set -- not the new offsets over rows that were never uploaded -- and the next valid call gives the bytes it gave before.
+    Own context: every capacity starts at 0."""
+    from diasss_amd import capi
+    from tests.test_gpu_matcher import _assert_empty_result_set, _refused
+    g = cases["consistent-opposite"]
+    s, t, k = g["lists"][0]
+    k = k[:7]
+    bad = k.copy(); bad[5, 1] = float(LC_M)
+    c = capi.Context(max_frames=4)
+    try:
+        _load(c, g["frames"])
+        c.lc_solve_pairs([s, s], [t, t], [k, k[:3]])
+        first = [c.lc_get(0).tobytes(), c.lc_get(1).tobytes()]
+        assert len(c.lc_get(0)) == 7 and len(c.lc_get(1)) == 3
+        _refused(E_ARG, lambda: c.lc_solve_pairs([s, s, s], [t, t, t], [k, bad, k]))
+        _assert_empty_result_set(c)
+        c.lc_solve_pairs([s, s], [t, t], [k, k[:3]])
+        assert [c.lc_get(0).tobytes(), c.lc_get(1).tobytes()] == first
+    finally:
+        c.close()
+
+
+def test_pair_buffers_grow_in_both_orders(orc, cases):
+    """dsss_lc_solve_pairs first on a fresh context (it allocates the pair index and the row buffers, no correspondences), then the matcher
+    (which grows its own buffers beside them), then dsss_lc_solve_pairs twice more (nothing to grow) and a matcher call below the capacity:
+    the same bytes every time, the matcher on the oracle, and no correspondences to read while the result set is dsss_lc_solve_pairs'."""
+    from diasss_amd import capi
+    from tests.test_gpu_matcher import _check_pair, _mkframes, _refused, _same_leg_pair
+    g = cases["pairs"]
+    lists = g["lists"]
+    src = [l[0] for l in lists]; tgt = [l[1] for l in lists]; kl = [l[2] for l in lists]
+    c = capi.Context(max_frames=4)
+    try:
+        def lc_pairs():
+            c.lc_solve_pairs(src, tgt, kl)
+            got = [c.lc_get(p) for p in range(len(lists))]
+            assert [len(x) for x in got] == [3, 0, 5, 1, 7]
+            return [x.tobytes() for x in got]
+        _load(c, g["frames"])
+        first = lc_pairs()
+        _refused(E_STATE, lambda: c.match_dir(0, 0))
+        assert len(c.match_rows(0)) == 0
+        fr = dict(enumerate(_mkframes(orc, c, (64, 64, 64))))
+        c.match_pairs([0, 0, 1], [1, 2, 2])
+        for p, (i, j) in enumerate(((0, 1), (0, 2), (1, 2))):
+            _check_pair(c, orc, p, i, j, fr)
+        c.lc_solve_all()
+        assert [len(c.lc_get(p)) for p in range(3)] == [len(c.match_kp7(p)) for p in range(3)]
+        _load(c, g["frames"])
+        assert lc_pairs() == first
+        assert lc_pairs() == first
+        fr = _same_leg_pair(orc, c, 64)                           # one pair, with rows: the write pass into the row buffers dsss_lc_solve_pairs allocated
+        c.match_pairs([0], [2])
+        assert _check_pair(c, orc, 0, 0, 2, fr) > 0
+        c.lc_solve_all()
+        assert len(c.lc_get(0)) == len(c.match_kp7(0)) > 0
+    finally:
+        c.close()

@@ -247,3 +247,90 @@ def test_matcher_radius_sweep(ctx, orc, radius):
         os.environ.pop("DSSS_MT_GRID", None)
         mt.radius = 8.0
         ctx.set_params(match=mt)
+
+
+E_ARG, E_STATE = -2, -4                     # include/dsss.h
+
+
+def _refused(code, call):
+    from diasss_amd import capi
+    with pytest.raises(capi.DsssError) as ei:
+        call()
+    assert ei.value.code == code, ei.value
+
+
+def _assert_empty_result_set(c):
+    """what a refused dsss_match_pairs / dsss_lc_solve_pairs leaves behind (include/dsss.h): no pair is in range for any getter"""
+    assert c.match_total() == (0, 0)
+    for p in (0, 2):
+        for get in (c.match_kp7, c.match_rows, lambda q: c.match_dir(q, 0), c.pair_is_active, c.lc_get):
+            _refused(E_ARG, lambda: get(p))
+    c.lc_solve_all()                                              # nothing to launch over; still no pair to read
+    _refused(E_ARG, lambda: c.lc_get(0))
+
+
+def test_refused_match_leaves_an_empty_result_set(orc):
+    """dsss_match_pairs refused at its LAST pair (s == t: DSSS_E_ARG; a frame without features: DSSS_E_STATE), after the pairs before it have
+    been selected: the context holds an empty result set, not the new pair list over the previous call's offsets, and the next valid call
+    gives the bytes it gave before.  Own context: every capacity starts at 0."""
+    from diasss_amd import capi
+    c = capi.Context(max_frames=4)
+    try:
+        _mkframes(orc, c, (64, 64, 64))                           # frame 3 is never set
+        def keep():
+            return [c.match_rows(0).tobytes(), c.match_kp7(0).tobytes()] + [np.asarray(v).tobytes() for d in (0, 1) for v in c.match_dir(0, d)]
+        def rounds(s0, t0):
+            c.match_pairs([s0], [t0])
+            first = keep()
+            for src, tgt, code in (([0, 0, 1, 1], [1, 2, 2, 1], E_ARG), ([0, 0, 1], [1, 2, 3], E_STATE)):
+                _refused(code, lambda: c.match_pairs(src, tgt))
+                _assert_empty_result_set(c)
+                c.match_pairs([s0], [t0])
+                assert keep() == first
+        rounds(0, 1)                                              # legs apart: an active pair without rows
+        _same_leg_pair(orc, c, 64)                                # frames 0 and 2 replaced: the same with rows and kp7 lists on the device
+        rounds(0, 2)
+        assert len(c.match_rows(0)) > 0 and len(c.match_kp7(0)) > 0
+    finally:
+        c.close()
+
+
+def _same_leg_pair(orc, c, n, N=700, M=480):
+    """frames 0 and 2 on leg 0, 0.3 m apart, the second with the first's keypoints moved by a few pixels and bits (as test_matcher_sizes): rows"""
+    from tests import helpers as H
+    pose, alt, gr = H.track(N, M, 0, seed=3)
+    pose2 = pose.copy(); pose2[:, 4] += 0.3
+    kps, desc = H.random_features(N, M, n, 50 + 10 * n)
+    rng = np.random.default_rng(n)
+    kps2, desc2 = kps.copy(), desc.copy()
+    for i in range(n):
+        for b in rng.choice(256, rng.integers(0, 20), replace=False):
+            desc2[i, b // 8] ^= np.uint8(1 << (b % 8))
+    kps2["y"] += rng.integers(-3, 4, n).astype(np.float32)
+    fr = {}
+    for f, (p, k, d) in ((0, (pose, kps, desc)), (2, (pose2, kps2, desc2))):
+        c.frame_set(f, None, N, M, p, alt, gr)
+        c.features_set(f, N, M, k, d)
+        fr[f] = dict(N=N, M=M, pose=p, alt=alt, gr=gr, kps=k, desc=d, geo=orc.geo_at_kps(p, gr, M, k), bb=orc.geo_bbox(p, gr, M))
+    return fr
+
+
+@pytest.mark.parametrize("grid", ["1", "0"])
+def test_match_launch_accounting(orc, grid, monkeypatch):
+    """the launches and the work the matcher's scopes record for one active pair: grid build + matcher (or the all-pairs kernel alone),
+    SCC, the two row passes; work = the 2 Na Nb evaluations of the all-pairs formulation, and the evaluations actually done are counted"""
+    from diasss_amd import capi
+    monkeypatch.setenv("DSSS_MT_GRID", grid)
+    c = capi.Context(max_frames=4)
+    try:
+        fr = _same_leg_pair(orc, c, 64)
+        c.profile(True); c.profile_reset()
+        c.match_pairs([0], [2])
+        assert _check_pair(c, orc, 0, 0, 2, fr) > 0
+        prof = c.profile_get()
+        assert prof["match"][1] == (2 if grid == "1" else 1)
+        assert prof["scc"][1] == 1 and prof["rows"][1] == 2
+        assert prof["match"][2] == 2 * 64 * 64
+        assert prof["match_done"][2] > 0
+    finally:
+        c.close()
