@@ -48,7 +48,7 @@ struct dsss_comm {
     void* nccl = nullptr;                                              // ncclComm_t
     dsss_comm_fn cb = nullptr; void* cb_user = nullptr;
     dsss_comm_dev_fn dcb = nullptr;                                    // transport that works on the DEVICE buffer, ordered on the stream
-    double* h_stage = nullptr; size_t h_cap = 0;                       // pinned staging of the callback transport
+    dsss_buf h_stage{"comm h_stage", DSSS_PINNED};                                    // pinned staging of the callback transport
     double bytes = 0; long long calls = 0;
 };
 
@@ -57,7 +57,6 @@ void dsss_comm_free(dsss_ctx* c)
     dsss_comm* m = c->comm;
     if (!m) return;
     if (m->nccl && g_rccl.destroy) g_rccl.destroy(m->nccl);
-    if (m->h_stage) hipHostFree(m->h_stage);
     delete m; c->comm = nullptr;
 }
 int dsss_comm_rank(const dsss_ctx* c) { return c->comm ? c->comm->rank : 0; }
@@ -79,12 +78,11 @@ int dsss_comm_allreduce(dsss_ctx* c, double* dev, size_t n, hipStream_t st)
         return DSSS_OK;
     }
     if (m->cb) {
-        if (m->h_cap < n) { if (m->h_stage) hipHostFree(m->h_stage); m->h_stage = nullptr; m->h_cap = 0;
-                            HIPCHK(c, hipHostMalloc(&m->h_stage, n * sizeof(double), hipHostMallocDefault)); m->h_cap = n; }
-        HIPCHK(c, hipMemcpyAsync(m->h_stage, dev, n * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (const int rc = m->h_stage.reserve(c, n * sizeof(double))) return rc;
+        HIPCHK(c, hipMemcpyAsync(m->h_stage.p, dev, n * sizeof(double), hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipStreamSynchronize(st));
-        if (m->cb(m->cb_user, 0, m->h_stage, n) != 0) DSSS_FAIL(c, DSSS_E_COMM, "all-reduce callback failed");
-        HIPCHK(c, hipMemcpyAsync(dev, m->h_stage, n * sizeof(double), hipMemcpyHostToDevice, st));
+        if (m->cb(m->cb_user, 0, m->h_stage.as<double>(), n) != 0) DSSS_FAIL(c, DSSS_E_COMM, "all-reduce callback failed");
+        HIPCHK(c, hipMemcpyAsync(dev, m->h_stage.p, n * sizeof(double), hipMemcpyHostToDevice, st));
         return DSSS_OK;
     }
     return DSSS_OK;                                                    // world 1 without a transport: nothing to sum
@@ -108,12 +106,11 @@ int dsss_comm_allgather(dsss_ctx* c, void* recv_dev, size_t bytes, hipStream_t s
     }
     if (m->cb) {
         const size_t tot = bytes * m->world, nd = (tot + 7) / 8;
-        if (m->h_cap < nd) { if (m->h_stage) hipHostFree(m->h_stage); m->h_stage = nullptr; m->h_cap = 0;
-                             HIPCHK(c, hipHostMalloc(&m->h_stage, nd * sizeof(double), hipHostMallocDefault)); m->h_cap = nd; }
-        HIPCHK(c, hipMemcpyAsync((char*)m->h_stage + (size_t)m->rank * bytes, (const char*)recv_dev + (size_t)m->rank * bytes, bytes, hipMemcpyDeviceToHost, st));
+        if (const int rc = m->h_stage.reserve(c, nd * sizeof(double))) return rc;
+        HIPCHK(c, hipMemcpyAsync(m->h_stage.as<char>() + (size_t)m->rank * bytes, (const char*)recv_dev + (size_t)m->rank * bytes, bytes, hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipStreamSynchronize(st));
-        if (m->cb(m->cb_user, 1, m->h_stage, bytes) != 0) DSSS_FAIL(c, DSSS_E_COMM, "all-gather callback failed");
-        HIPCHK(c, hipMemcpyAsync(recv_dev, m->h_stage, tot, hipMemcpyHostToDevice, st));
+        if (m->cb(m->cb_user, 1, m->h_stage.as<double>(), bytes) != 0) DSSS_FAIL(c, DSSS_E_COMM, "all-gather callback failed");
+        HIPCHK(c, hipMemcpyAsync(recv_dev, m->h_stage.p, tot, hipMemcpyHostToDevice, st));
     }
     return DSSS_OK;
 }

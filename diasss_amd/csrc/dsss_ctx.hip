@@ -101,23 +101,26 @@ int dsss_create(int device, int max_frames, dsss_ctx** out)
     return DSSS_OK;
 }
 
-static void free_frame(dsss_frame& f)
+// the families of this file (dsss_internal.h: one capacity, every member allocated or none)
+static std::array<dsss_fam_slot, 2> pack_family(dsss_frame& f, size_t pack = 0) { return {{ dsss_slot(f.d_pack, pack * sizeof(double)), dsss_slot(f.h_pack, pack * sizeof(double), DSSS_PINNED) }}; }
+static std::array<dsss_fam_slot, 2> gbatch_family(dsss_geo_batch& G, size_t total = 0) { return {{ dsss_slot(G.d, total * sizeof(double)), dsss_slot(G.h, total * sizeof(double), DSSS_PINNED) }}; }
+static std::array<dsss_fam_slot, 7> store_family(dsss_ctx* c)
 {
-    hipFree(f.raw_owned); hipFree(f.d_pack); hipFree(f.mask);
-    if (f.h_pack) hipHostFree(f.h_pack);
-    if (f.pack_ev) hipEventDestroy(f.pack_ev);
-    for (int l = 0; l < DSSS_MAX_LEVELS; ++l) hipFree(f.lvl[l]);
-    f = dsss_frame();
+    const size_t F = (size_t)c->max_frames, K = (size_t)c->kcap;
+    return {{ dsss_slot(c->kps, F * K * sizeof(dsss_kp)), dsss_slot(c->desc, F * K * 32), dsss_slot(c->geo, F * K * 2 * sizeof(double)), dsss_slot(c->nkp_dev, F * sizeof(int)),
+              dsss_slot(c->rows_dev, F * sizeof(int)), dsss_slot(c->cols_dev, F * sizeof(int)), dsss_slot(c->bbox_dev, F * 4 * sizeof(double)) }};
 }
 
-static void free_store(dsss_ctx* c)
+static void free_frame(dsss_frame& f)
 {
-    hipFree(c->desc128); c->desc128 = nullptr;
-    hipFree(c->kps); hipFree(c->desc); hipFree(c->geo); hipFree(c->nkp_dev); hipFree(c->rows_dev);
-    hipFree(c->cols_dev); hipFree(c->bbox_dev);
-    c->kps = nullptr; c->desc = nullptr; c->geo = nullptr; c->nkp_dev = nullptr; c->rows_dev = nullptr;
-    c->cols_dev = nullptr; c->bbox_dev = nullptr;
+    dsss_family_release(f.pack_cap, pack_family(f));
+    hipFree(f.mask);
+    if (f.pack_ev) hipEventDestroy(f.pack_ev);
+    for (int l = 0; l < DSSS_MAX_LEVELS; ++l) hipFree(f.lvl[l]);
+    f = dsss_frame();                    // (move assignment: releases raw_owned)
 }
+
+static void free_store(dsss_ctx* c) { c->desc128.release(); dsss_family_release(c->store_cap, store_family(c)); }
 
 void dsss_destroy(dsss_ctx* c)
 {
@@ -125,23 +128,10 @@ void dsss_destroy(dsss_ctx* c)
     hipSetDevice(c->device);
     hipStreamSynchronize(c->stream);
     for (auto& f : c->frames) free_frame(f);
-    for (auto& G : c->gbatches) { hipFree(G.d); if (G.h) hipHostFree(G.h); if (G.ev) hipEventDestroy(G.ev); }
+    for (auto& G : c->gbatches) { dsss_family_release(G.cap, gbatch_family(G)); if (G.ev) hipEventDestroy(G.ev); }
     c->gbatches.clear();
     dsss_mt_free(c); free_store(c);
-    hipFree(c->lcs); hipFree(c->ex_scratch); hipFree(c->tmp_dev); hipFree(c->sift_w);
-    hipFree(c->ag_buf); if (c->ag_host) hipHostFree(c->ag_host); hipFree(c->xch_dev);
-    if (c->pg_edges_host) hipHostFree(c->pg_edges_host);
-    if (c->pg_ab_host) hipHostFree(c->pg_ab_host);
-    if (c->xch_host) hipHostFree(c->xch_host);
-    if (c->pg_stage) hipHostFree(c->pg_stage);
-    if (c->pg_scal_host) hipHostFree(c->pg_scal_host);
-    if (c->pg_warm) hipFree(c->pg_warm);
-    hipFree(c->mosaic_buf);
-    hipFree(c->pgr_buf);
     if (c->geoms && c->geoms_free) c->geoms_free(c->geoms);
-    if (c->ex_pinned) hipHostFree(c->ex_pinned);
-    if (c->bbox_pinned) hipHostFree(c->bbox_pinned);
-    hipFree(c->bbox_jobs_dev); if (c->bbox_jobs_pinned) hipHostFree(c->bbox_jobs_pinned);
     dsss_pg_free(c); dsss_comm_free(c);
     hipEventDestroy(c->prof.e0); hipEventDestroy(c->prof.e1);
     dsss_prof_flush(c);
@@ -170,7 +160,7 @@ int dsss_set_params(dsss_ctx* c, const dsss_mask_params* mp, const dsss_orb_para
             DSSS_FAIL(c, DSSS_E_ARG, "orb params out of range");
         int k = kcap_for(*op);
         if (k != c->kcap) {
-            if (c->kps) { HIPCHK(c, hipStreamSynchronize(c->stream)); free_store(c); dsss_mt_free(c); for (auto& f : c->frames) { f.has_feat = false; f.has_sift = false; } }
+            if (c->store_cap) { HIPCHK(c, hipStreamSynchronize(c->stream)); free_store(c); dsss_mt_free(c); for (auto& f : c->frames) { f.has_feat = false; f.has_sift = false; } }
             c->kcap = k;
         }
         c->op = *op;
@@ -187,15 +177,9 @@ int dsss_set_params(dsss_ctx* c, const dsss_mask_params* mp, const dsss_orb_para
 
 int dsss_ensure_store(dsss_ctx* c)
 {
-    if (c->kps) return DSSS_OK;
+    if (c->store_cap) return DSSS_OK;
     size_t F = (size_t)c->max_frames, K = (size_t)c->kcap;
-    HIPCHK(c, hipMalloc(&c->kps, F * K * sizeof(dsss_kp)));
-    HIPCHK(c, hipMalloc(&c->desc, F * K * 32));
-    HIPCHK(c, hipMalloc(&c->geo, F * K * 2 * sizeof(double)));
-    HIPCHK(c, hipMalloc(&c->nkp_dev, F * sizeof(int)));
-    HIPCHK(c, hipMalloc(&c->rows_dev, F * sizeof(int)));
-    HIPCHK(c, hipMalloc(&c->cols_dev, F * sizeof(int)));
-    HIPCHK(c, hipMalloc(&c->bbox_dev, F * 4 * sizeof(double)));
+    if (const int rc = dsss_family_alloc(c, "feature store", c->store_cap, F * K, store_family(c))) return rc;      // a failed call leaves NO store: the next one starts over
     HIPCHK(c, hipMemsetAsync(c->nkp_dev, 0, F * sizeof(int), c->stream));
     HIPCHK(c, hipMemsetAsync(c->rows_dev, 0, F * sizeof(int), c->stream));
     HIPCHK(c, hipMemsetAsync(c->cols_dev, 0, F * sizeof(int), c->stream));
@@ -209,8 +193,8 @@ int dsss_ensure_sift_store(dsss_ctx* c)
     int rc = dsss_ensure_store(c); if (rc) return rc;
     if (!c->desc128) {
         const size_t bytes = (size_t)c->max_frames * c->kcap * 128;
-        HIPCHK(c, hipMalloc(&c->desc128, bytes));
-        HIPCHK(c, hipMemsetAsync(c->desc128, 0, bytes, c->stream));
+        if ((rc = c->desc128.reserve(c, bytes))) return rc;
+        HIPCHK(c, hipMemsetAsync(c->desc128.p, 0, bytes, c->stream));
     }
     if (!c->sift_w) {
         // exp(-k / 512) by repeated multiplication in double: the loop of oracle/orc_sift.c:orc_sift_weights, same bits
@@ -219,8 +203,8 @@ int dsss_ensure_sift_store(dsss_ctx* c)
         const double q = 0.9980487811074755;
         double v = 1.0;
         for (int k = 0; k < n; ++k) { w[k] = (float)v; v = v * q; }
-        HIPCHK(c, hipMalloc(&c->sift_w, n * sizeof(float)));
-        HIPCHK(c, hipMemcpy(c->sift_w, w.data(), n * sizeof(float), hipMemcpyHostToDevice));
+        if ((rc = c->sift_w.reserve(c, n * sizeof(float)))) return rc;
+        HIPCHK(c, hipMemcpy(c->sift_w.p, w.data(), n * sizeof(float), hipMemcpyHostToDevice));
     }
     return DSSS_OK;
 }
@@ -290,20 +274,20 @@ int dsss_frame_geo_bbox(dsss_ctx* c, int id)
 int dsss_bboxes_enqueue(dsss_ctx* c)
 {
     if (!c->bbox_pending || c->bbox_inflight) return DSSS_OK;
-    if (!c->bbox_pinned) HIPCHK(c, hipHostMalloc((void**)&c->bbox_pinned, (size_t)c->max_frames * 4 * sizeof(double), hipHostMallocDefault));
-    if (!c->bbox_jobs_pinned) HIPCHK(c, hipHostMalloc((void**)&c->bbox_jobs_pinned, (size_t)c->max_frames * sizeof(bbox_job), hipHostMallocDefault));
-    bbox_job* jobs = static_cast<bbox_job*>(c->bbox_jobs_pinned);
+    int rc;
+    if ((rc = c->bbox_pinned.reserve(c, (size_t)c->max_frames * 4 * sizeof(double))) || (rc = c->bbox_jobs_pinned.reserve(c, (size_t)c->max_frames * sizeof(bbox_job)))) return rc;
+    bbox_job* jobs = c->bbox_jobs_pinned.as<bbox_job>();
     c->bbox_inflight_ids.clear();
     for (int f = 0; f < c->max_frames; ++f)
         if (c->frames[f].bbox_async) { const dsss_frame& fr = c->frames[f]; jobs[c->bbox_inflight_ids.size()] = bbox_job{ fr.pose6, fr.gr, fr.N, fr.M, f, 0 }; c->bbox_inflight_ids.push_back(f); }
     c->bbox_pending = false;
     const size_t nj = c->bbox_inflight_ids.size();
     if (nj == 0) return DSSS_OK;
-    if (!c->bbox_jobs_dev) HIPCHK(c, hipMalloc(&c->bbox_jobs_dev, (size_t)c->max_frames * sizeof(bbox_job)));
-    bbox_job* d_jobs = static_cast<bbox_job*>(c->bbox_jobs_dev);
+    if ((rc = c->bbox_jobs_dev.reserve(c, (size_t)c->max_frames * sizeof(bbox_job)))) return rc;
+    bbox_job* d_jobs = c->bbox_jobs_dev.as<bbox_job>();
     hipError_t e = hipMemcpyAsync(d_jobs, jobs, nj * sizeof(bbox_job), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) { hipLaunchKernelGGL(geo_bbox_kernel, dim3((unsigned)nj), dim3(256), 0, c->stream, d_jobs, c->bbox_dev, c->rows_dev, c->cols_dev); e = hipGetLastError(); }
-    if (e == hipSuccess) e = hipMemcpyAsync(c->bbox_pinned, c->bbox_dev, (size_t)c->max_frames * 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->bbox_pinned.p, c->bbox_dev, (size_t)c->max_frames * 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream);
     if (e != hipSuccess) { c->bbox_pending = true; HIPCHK(c, e); }
     c->bbox_inflight = true;
     return DSSS_OK;
@@ -317,7 +301,7 @@ int dsss_sync_bboxes(dsss_ctx* c)
         if (c->bbox_inflight) {
             HIPCHK(c, hipStreamSynchronize(c->stream));
             for (int id : c->bbox_inflight_ids)
-                if (c->frames[id].bbox_async) { memcpy(c->frames[id].bbox, c->bbox_pinned + (size_t)id * 4, 4 * sizeof(double)); c->frames[id].bbox_async = false; }      // (not a box the caller has set itself since: dsss_features_set)
+                if (c->frames[id].bbox_async) { memcpy(c->frames[id].bbox, c->bbox_pinned.as<double>() + (size_t)id * 4, 4 * sizeof(double)); c->frames[id].bbox_async = false; }      // (not a box the caller has set itself since: dsss_features_set)
             c->bbox_inflight = false; c->bbox_inflight_ids.clear();
         }
     }
@@ -365,12 +349,7 @@ static int frame_prepare(dsss_ctx* c, int id, int N, int M, const double* pose6,
     f.N = N; f.M = M;
     const size_t pack = (size_t)N * 6 + N + M / 2;
     if (f.pack_cap < pack) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        hipFree(f.d_pack); if (f.h_pack) hipHostFree(f.h_pack);
-        f.d_pack = nullptr; f.h_pack = nullptr;
-        HIPCHK(c, hipMalloc(&f.d_pack, pack * sizeof(double)));
-        HIPCHK(c, hipHostMalloc((void**)&f.h_pack, pack * sizeof(double), hipHostMallocDefault));
-        f.pack_cap = pack;
+        if (const int rc = dsss_family_alloc(c, "frame d_pack / h_pack", f.pack_cap, pack, pack_family(f, pack))) return rc;
     }
     f.pose6 = f.d_pack; f.alt = f.d_pack + (size_t)N * 6; f.gr = f.alt + N; f.h_geo = f.h_pack;
     if (f.pack_ev) HIPCHK(c, hipEventSynchronize(f.pack_ev));        // the pinned staging area may still feed the previous upload
@@ -410,15 +389,15 @@ static int frame_submit(dsss_ctx* c, int id, const double* raw, bool own_upload)
         f.raw_pending = false; f.raw_host = nullptr;
         if (on_dev) { f.raw = raw; }
         else {
-            if (!f.raw_owned) HIPCHK(c, hipMalloc(&f.raw_owned, (size_t)N * M * sizeof(double)));
+            if (!f.raw_owned) { if (const int rc = f.raw_owned.reserve(c, (size_t)N * M * sizeof(double))) return rc; }
             const bool pinned = (hipPointerGetAttributes(&at, raw) == hipSuccess) && at.type == hipMemoryTypeHost;
             (void)hipGetLastError();
             // a page-locked image is not copied here: the extraction streams it in, sub-batch by sub-batch, on a copy stream while
             // the kernels of the previous sub-batch run (the caller keeps the buffer alive until dsss_extract* returns).  Pageable
             // memory cannot be copied asynchronously: it goes up now.
             if (pinned) { f.raw_host = raw; f.raw_pending = true; }
-            else HIPCHK(c, hipMemcpy(f.raw_owned, raw, (size_t)N * M * sizeof(double), hipMemcpyHostToDevice));
-            f.raw = f.raw_owned;
+            else HIPCHK(c, hipMemcpy(f.raw_owned.p, raw, (size_t)N * M * sizeof(double), hipMemcpyHostToDevice));
+            f.raw = f.raw_owned.as<double>();
         }
         f.has_raw = true;
     } else f.has_raw = false;
@@ -466,12 +445,7 @@ int dsss_frames_set(dsss_ctx* c, int n, const int* ids, const double* const* raw
         for (size_t k = 0; k < c->gbatches.size() && b < 0; ++k) if (c->gbatches[k].refs == 0) b = (int)k;     // grow an idle one
         if (b < 0) { c->gbatches.push_back(dsss_geo_batch()); b = (int)c->gbatches.size() - 1; }
         dsss_geo_batch& G = c->gbatches[b];
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        hipFree(G.d); if (G.h) hipHostFree(G.h);
-        G.d = nullptr; G.h = nullptr; G.cap = 0;
-        HIPCHK(c, hipMalloc(&G.d, total * sizeof(double)));
-        HIPCHK(c, hipHostMalloc((void**)&G.h, total * sizeof(double), hipHostMallocDefault));
-        G.cap = total;
+        if ((rc = dsss_family_alloc(c, "geometry batch", G.cap, total, gbatch_family(G, total)))) return rc;
         if (!G.ev) HIPCHK(c, hipEventCreateWithFlags(&G.ev, hipEventDisableTiming));
     }
     dsss_geo_batch& G = c->gbatches[b];
@@ -553,7 +527,7 @@ int dsss_features_set_sift(dsss_ctx* c, int id, const float* d128, int n)
     int rc = dsss_ensure_sift_store(c); if (rc) return rc;
     std::vector<uint8_t> b((size_t)n * 128);
     for (size_t i = 0; i < b.size(); ++i) { const float v = std::nearbyint(d128[i]); b[i] = (uint8_t)(v < 0 ? 0 : v > 255 ? 255 : v); }
-    if (n > 0) HIPCHK(c, hipMemcpy(c->desc128 + (size_t)id * c->kcap * 128, b.data(), b.size(), hipMemcpyHostToDevice));
+    if (n > 0) HIPCHK(c, hipMemcpy(c->desc128.as<uint8_t>() + (size_t)id * c->kcap * 128, b.data(), b.size(), hipMemcpyHostToDevice));
     f.has_sift = true;
     return DSSS_OK;
 }
@@ -570,7 +544,7 @@ int dsss_features_get_sift(dsss_ctx* c, int id, float* d128, int cap, int* n)
         if (!d128) return DSSS_E_ARG;
         std::vector<uint8_t> b((size_t)f.nkp * 128);
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipMemcpy(b.data(), c->desc128 + (size_t)id * c->kcap * 128, b.size(), hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(b.data(), c->desc128.as<uint8_t>() + (size_t)id * c->kcap * 128, b.size(), hipMemcpyDeviceToHost));
         for (size_t i = 0; i < b.size(); ++i) d128[i] = (float)b[i];
     }
     return DSSS_OK;
@@ -626,14 +600,14 @@ int dsss_frame_get_geo(dsss_ctx* c, int id, double* x_host, double* y_host)
     if (!f.has_geom) DSSS_FAIL(c, DSSS_E_STATE, "frame %d has no geometry", id);
     HIPCHK(c, hipSetDevice(c->device));
     const size_t n = (size_t)f.N * f.M;
-    double* d = nullptr;
-    HIPCHK(c, hipMalloc(&d, 2 * n * sizeof(double)));
+    dsss_buf tmp("dsss_frame_get_geo image");      // of this call
+    if (const int rc = tmp.reserve(c, 2 * n * sizeof(double))) return rc;
+    double* d = tmp.as<double>();
     hipLaunchKernelGGL(geo_image_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, f.pose6, f.gr, f.N, f.M, d, d + n);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(x_host, d, n * sizeof(double), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(y_host, d + n, n * sizeof(double), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    hipFree(d);
     HIPCHK(c, e);
     return DSSS_OK;
 }
@@ -684,7 +658,7 @@ int dsss_features_pack(dsss_ctx* c, int id, void* buf)
     HIPCHK(c, hipMemcpyAsync(p + 48 + K * sizeof(dsss_kp) + K * 32, c->geo + id * K * 2, K * 16, hipMemcpyDefault, c->stream));
     if (c->op.descriptor == DSSS_DESC_SIFT128) {
         if (!f.has_sift) DSSS_FAIL(c, DSSS_E_STATE, "frame %d has no SIFT rows", id);
-        HIPCHK(c, hipMemcpyAsync(p + 48 + K * sizeof(dsss_kp) + K * 48, c->desc128 + (size_t)id * K * 128, K * 128, hipMemcpyDefault, c->stream));
+        HIPCHK(c, hipMemcpyAsync(p + 48 + K * sizeof(dsss_kp) + K * 48, c->desc128.as<uint8_t>() + (size_t)id * K * 128, K * 128, hipMemcpyDefault, c->stream));
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return DSSS_OK;
@@ -700,7 +674,7 @@ int dsss_features_unpack(dsss_ctx* c, int id, const void* buf)
                                (const double*)(p + 48 + K * sizeof(dsss_kp) + K * 32), bbox, hdr[0]);
     if (rc == DSSS_OK && c->op.descriptor == DSSS_DESC_SIFT128) {
         rc = dsss_ensure_sift_store(c); if (rc) return rc;
-        HIPCHK(c, hipMemcpy(c->desc128 + (size_t)id * K * 128, p + 48 + K * sizeof(dsss_kp) + K * 48, K * 128, hipMemcpyDefault));
+        HIPCHK(c, hipMemcpy(c->desc128.as<uint8_t>() + (size_t)id * K * 128, p + 48 + K * sizeof(dsss_kp) + K * 48, K * 128, hipMemcpyDefault));
         c->frames[id].has_sift = true;
     }
     return rc;
@@ -765,22 +739,13 @@ int dsss_features_allgather(dsss_ctx* c, int nframes)
     int per = 0;
     for (int r = 0; r < world; ++r) per = std::max(per, (int)((long long)nframes * (r + 1) / world - (long long)nframes * r / world));
     const size_t slice = (size_t)per * nb;
-    if (c->ag_cap < slice * world) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        hipFree(c->ag_buf); c->ag_buf = nullptr; c->ag_cap = 0;
-        HIPCHK(c, hipMalloc(&c->ag_buf, slice * world)); c->ag_cap = slice * world;
-    }
     const size_t hbytes = (size_t)c->max_frames * (3 * sizeof(int) + 4 * sizeof(double)) + 16;
-    if (c->ag_host_cap < hbytes) {
-        if (c->ag_host) hipHostFree(c->ag_host);
-        c->ag_host = nullptr; c->ag_host_cap = 0;
-        HIPCHK(c, hipHostMalloc(&c->ag_host, hbytes, hipHostMallocDefault)); c->ag_host_cap = hbytes;
-    }
-    char* d_buf = static_cast<char*>(c->ag_buf);
+    { int r1; if ((r1 = c->ag_buf.reserve(c, slice * world)) || (r1 = c->ag_host.reserve(c, hbytes))) return r1; }
+    char* d_buf = c->ag_buf.as<char>();
     const hipStream_t st = c->stream;
     const dim3 grid(8, nframes);
     uint8_t* d128 = nullptr;
-    if (c->op.descriptor == DSSS_DESC_SIFT128) { int r2 = dsss_ensure_sift_store(c); if (r2) return r2; d128 = c->desc128; }
+    if (c->op.descriptor == DSSS_DESC_SIFT128) { int r2 = dsss_ensure_sift_store(c); if (r2) return r2; d128 = c->desc128.as<uint8_t>(); }
     hipLaunchKernelGGL(ag_copy_kernel, grid, dim3(256), 0, st, nframes, world, rank, 0, d_buf, slice, nb, c->kcap, c->kps, c->desc, c->geo, c->nkp_dev, c->rows_dev, c->cols_dev, c->bbox_dev, d128);
     HIPCHK(c, hipGetLastError());
     int rc = dsss_comm_allgather(c, d_buf, slice, st);
@@ -788,7 +753,7 @@ int dsss_features_allgather(dsss_ctx* c, int nframes)
     hipLaunchKernelGGL(ag_copy_kernel, grid, dim3(256), 0, st, nframes, world, rank, 1, d_buf, slice, nb, c->kcap, c->kps, c->desc, c->geo, c->nkp_dev, c->rows_dev, c->cols_dev, c->bbox_dev, d128);
     HIPCHK(c, hipGetLastError());
     // the host's view of the gathered frames: counts, sizes and boxes in one download
-    int* h_n = static_cast<int*>(c->ag_host); int* h_r = h_n + c->max_frames; int* h_c = h_r + c->max_frames;
+    int* h_n = c->ag_host.as<int>(); int* h_r = h_n + c->max_frames; int* h_c = h_r + c->max_frames;
     double* h_bb = reinterpret_cast<double*>(h_c + c->max_frames + (c->max_frames & 1));
     HIPCHK(c, hipMemcpyAsync(h_n, c->nkp_dev, sizeof(int) * nframes, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipMemcpyAsync(h_r, c->rows_dev, sizeof(int) * nframes, hipMemcpyDeviceToHost, st));

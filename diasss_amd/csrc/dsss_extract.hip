@@ -1137,15 +1137,9 @@ struct ex_run {
     int reserve() {      // grow the scratch and its pinned mirror, carve the tables out of both
         T = ex_tables(B);
         const size_t need = slot_bytes * B + T.total, pin_need = T.total + sizeof(int) * ((size_t)B + c->max_frames) + 64;
-        if (c->ex_scratch_bytes < need) {
-            HIPCHK(c, hipStreamSynchronize(c->stream)); hipFree(c->ex_scratch); c->ex_scratch = nullptr; c->ex_scratch_bytes = 0;
-            HIPCHK(c, hipMalloc(&c->ex_scratch, need)); c->ex_scratch_bytes = need;
-        }
-        if (c->ex_pinned_bytes < pin_need) {
-            HIPCHK(c, hipStreamSynchronize(c->stream)); if (c->ex_pinned) hipHostFree(c->ex_pinned); c->ex_pinned = nullptr; c->ex_pinned_bytes = 0;
-            HIPCHK(c, hipHostMalloc(&c->ex_pinned, pin_need, hipHostMallocDefault)); c->ex_pinned_bytes = pin_need;
-        }
-        S0 = (char*)c->ex_scratch; T0 = S0 + slot_bytes * B; P0 = (char*)c->ex_pinned;
+        int rc;
+        if ((rc = c->ex_scratch.reserve(c, need)) || (rc = c->ex_pinned.reserve(c, pin_need))) return rc;
+        S0 = c->ex_scratch.as<char>(); T0 = S0 + slot_bytes * B; P0 = c->ex_pinned.as<char>();
         d_inst = (qt_inst*)T0; d_fr = (qt_frame*)(T0 + T.fr); d_exf = (ex_frame*)(T0 + T.exf); d_errs = (int*)(T0 + T.err);
         h_inst = (qt_inst*)P0; h_fr = (qt_frame*)(P0 + T.fr); h_exf = (ex_frame*)(P0 + T.exf); h_err = (int*)(P0 + T.total); h_nkp = h_err + B;
         return DSSS_OK;
@@ -1156,7 +1150,7 @@ struct ex_run {
         hipError_t e = hipSuccess;
         for (int s = b0; s < std::min(n, b0 + B) && e == hipSuccess; ++s) {
             dsss_frame& f = c->frames[ids[s]];
-            if (f.raw_pending) e = hipMemcpyAsync(f.raw_owned, f.raw_host, (size_t)f.N * f.M * sizeof(double), hipMemcpyHostToDevice, c->xs[1]);
+            if (f.raw_pending) e = hipMemcpyAsync(f.raw_owned.p, f.raw_host, (size_t)f.N * f.M * sizeof(double), hipMemcpyHostToDevice, c->xs[1]);
             f.raw_pending = false;
         }
         return e == hipSuccess ? hipEventRecord(up_ev(bk), c->xs[1]) : e;
@@ -1179,7 +1173,7 @@ struct ex_run {
             e.kin = (kp_in*)(S + L.kin); e.nk = (int*)(S + L.nk); e.lrows = g.d_lrows; e.lscale = g.d_lscale;
             for (int l = 0; l < DSSS_MAX_LEVELS; ++l) { e.xt[l] = g.d_xt[l]; e.yt[l] = g.d_yt[l]; }
             e.kptmp = (dsss_kp*)(S + L.kptmp); e.dtmp = (uint8_t*)(S + L.dtmp);
-            e.d128tmp = sift ? (uint8_t*)(S + L.d128tmp) : nullptr; e.d128out = sift ? c->desc128 + (size_t)id * c->kcap * 128 : nullptr;
+            e.d128tmp = sift ? (uint8_t*)(S + L.d128tmp) : nullptr; e.d128out = sift ? c->desc128.as<uint8_t>() + (size_t)id * c->kcap * 128 : nullptr;
             e.err = d_errs + s; e.kout = c->kps + (size_t)id * c->kcap; e.dout = c->desc + (size_t)id * c->kcap * 32; e.geo = c->geo + (size_t)id * c->kcap * 2; e.count = c->nkp_dev + id;
             bt.maxN = std::max(bt.maxN, f.N); bt.max_tot = std::max(bt.max_tot, (size_t)f.N * f.M); bt.max_levels = std::max(bt.max_levels, g.nlevels);
             bt.max_cw = std::max(bt.max_cw, g.cell_wmax); bt.max_ch = std::max(bt.max_ch, g.cell_hmax); bt.w_tot += (double)f.N * f.M;

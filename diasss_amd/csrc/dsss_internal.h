@@ -5,19 +5,62 @@
 #include <cstdio>
 #include <cstring>
 #include <cmath>
+#include <cassert>
+#include <array>
 #include <string>
+#include <utility>
 #include <vector>
 #include "../../include/dsss.h"
 
 #define DSSS_MAX_LEVELS 8
 #define DSSS_PI_REF 3.14159265359   // the reference's PI macro (frame.cpp:16, FEAmatcher.cpp:11, optimizer.cpp:19)
 
+struct dsss_ctx;
+int dsss_hip_fail(dsss_ctx* c, hipError_t e, const char* file, int line, const char* call);      // what HIPCHK does on a failure: fills c->err, returns DSSS_E_HIP
+int dsss_alloc_fail(dsss_ctx* c, hipError_t e, const char* name, const char* step, size_t bytes);   // the same for a failed growth: names the buffer, the step and the size
+
+// ---- ownership of the memory a context keeps between calls: ONE rule, written here once.
+// Growing a buffer: synchronise the context's stream (a queued kernel or copy may still use the old block; nothing can use a block that
+// does not exist, so a first allocation does not synchronise), free, null the pointer and zero the capacity, allocate, and publish the
+// capacity only after the allocation succeeded.  A failed allocation leaves a null pointer and capacity 0 -- never what hipMalloc left in
+// its output -- so the next call starts over and destruction is safe.
+inline hipError_t dsss_mem_alloc(void** p, size_t bytes, bool pinned) { return pinned ? hipHostMalloc(p, bytes, hipHostMallocDefault) : hipMalloc(p, bytes); }
+inline void dsss_mem_free(void* p, bool pinned) { if (p) { if (pinned) (void)hipHostFree(p); else (void)hipFree(p); } }
+
+// one buffer: pointer, capacity in bytes; its name (for dsss_last_error) and its kind, device or page-locked, are fixed where it is declared.
+// Move-only -- an assignment moves the block between two buffers of ONE kind and leaves name and kind alone; the destructor frees.
+// How much slack to allocate stays with the caller: reserve() takes the bytes needed and the bytes to allocate when those do not suffice.
+struct dsss_buf {
+    void* p = nullptr; size_t cap = 0; const char* const name; const bool pinned;
+    explicit dsss_buf(const char* name_, bool pinned_ = false) : name(name_), pinned(pinned_) {}
+    dsss_buf(dsss_buf&& o) noexcept : p(o.p), cap(o.cap), name(o.name), pinned(o.pinned) { o.p = nullptr; o.cap = 0; }
+    dsss_buf& operator=(dsss_buf&& o) noexcept { assert(pinned == o.pinned); if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; } return *this; }
+    dsss_buf(const dsss_buf&) = delete; dsss_buf& operator=(const dsss_buf&) = delete;
+    ~dsss_buf() { release(); }
+    void release() { dsss_mem_free(p, pinned); p = nullptr; cap = 0; }
+    template <class T> T* as() const { return static_cast<T*>(p); }
+    explicit operator bool() const { return p != nullptr; }
+    int reserve(dsss_ctx* c, size_t need_bytes, size_t alloc_bytes);
+    int reserve(dsss_ctx* c, size_t bytes) { return reserve(c, bytes, bytes); }
+    int reserve_keep(dsss_ctx* c, size_t need_bytes, size_t alloc_bytes, size_t keep_bytes);      // ... and carries the first keep_bytes over (device memory)
+};
+constexpr bool DSSS_PINNED = true;
+
+// a family: several typed pointers that live and die under ONE capacity (the feature store, the matcher's result sets, a frame's
+// d_pack / h_pack).  The members stay named, typed pointers, because kernels and getters read them by name; the owner lists them as slots.
+struct dsss_fam_slot { void** pp; size_t bytes; bool pinned; };
+// (the member's address as void**, the form hipMalloc itself takes: every T* here has the representation of void*, and the member is only
+// ever written through this view with a pointer the runtime returned, or null)
+template <class T> inline dsss_fam_slot dsss_slot(T*& p, size_t bytes = 0, bool pinned = false) { return { reinterpret_cast<void**>(&p), bytes, pinned }; }
+template <class Fam> inline void dsss_family_release(size_t& cap, const Fam& fam) { cap = 0; for (const dsss_fam_slot& s : fam) { dsss_mem_free(*s.pp, s.pinned); *s.pp = nullptr; } }
+template <class Fam> int dsss_family_alloc(dsss_ctx* c, const char* name, size_t& cap, size_t new_cap, const Fam& fam);      // the rule above for every member; on ANY failure all are freed and null, cap == 0
+
 struct dsss_frame {
     int N = 0, M = 0;
     bool has_geom = false, has_raw = false, has_feat = false, has_norm = false;
     bool has_sift = false;            // the frame's rows of desc128 are valid (extracted with DSSS_DESC_SIFT128 or imported)
     const double* raw = nullptr;      // device; borrowed when the caller passed a device pointer
-    double* raw_owned = nullptr;      // device; owned copy of a host image
+    dsss_buf raw_owned{"raw_owned"};  // device; owned copy of a host image (N x M doubles)
     const double* raw_host = nullptr; // page-locked host image whose upload is still pending (dsss_extract_many streams it in under the kernels)
     bool raw_pending = false;
     double* pose6 = nullptr;          // device N x 6
@@ -25,7 +68,7 @@ struct dsss_frame {
     double* gr = nullptr;             // device M/2
     double* h_pack = nullptr;         // pinned host copy [pose6 N*6 | alt N | gr M/2] (also the pose-graph DR input)
     double* d_pack = nullptr;         // device copy, pose6 / alt / gr point into it
-    size_t pack_cap = 0;
+    size_t pack_cap = 0;              // doubles of the d_pack / h_pack family
     hipEvent_t pack_ev = nullptr;     // recorded after the upload of h_pack: the staging area is reusable once it fired
     const double* h_geo = nullptr;    // host view of [pose6 | alt | gr]: h_pack, or a slice of a dsss_frames_set batch
     int gbatch = -1;                  // batch of dsss_frames_set the geometry lives in, -1: own d_pack / h_pack
@@ -41,7 +84,7 @@ struct dsss_frame {
 };
 
 // geometry of a whole dsss_frames_set call: one pinned staging area, one device buffer, ONE upload
-struct dsss_geo_batch { double* d = nullptr; double* h = nullptr; size_t cap = 0; int refs = 0; hipEvent_t ev = nullptr; };
+struct dsss_geo_batch { double* d = nullptr; double* h = nullptr; size_t cap = 0; /* family: doubles of d (device) and h (pinned) */ int refs = 0; hipEvent_t ev = nullptr; };
 
 struct dsss_comm;                        // dsss_comm.hip
 
@@ -75,22 +118,22 @@ struct dsss_ctx {
     int kcap = 0;                       // per-frame feature capacity (multiple of 64)
     std::vector<dsss_frame> frames;
     // feature store, device, frame-major with stride kcap
+    size_t store_cap = 0;               // the store family (kps, desc, geo, nkp_dev, rows_dev, cols_dev, bbox_dev): max_frames * kcap it was built for, 0 = none
     dsss_kp* kps = nullptr;             // [F][kcap]
     uint8_t* desc = nullptr;            // [F][kcap][32]
-    uint8_t* desc128 = nullptr;         // [F][kcap][128]: the integer-valued floats of DSSS_DESC_SIFT128 kept as bytes; allocated on first use
-    float* sift_w = nullptr;            // Gaussian window table of the SIFT descriptor, exp(-k / 512) (dsss_sift.hip)
+    dsss_buf desc128{"desc128"};                   // [F][kcap][128]: the integer-valued floats of DSSS_DESC_SIFT128 kept as bytes; allocated on first use
+    dsss_buf sift_w{"sift_w"};                    // Gaussian window table of the SIFT descriptor, exp(-k / 512) (dsss_sift.hip)
     double* geo = nullptr;              // [F][kcap][2]
     int* nkp_dev = nullptr;             // [F]
     int* rows_dev = nullptr;            // [F] pings per frame
     int* cols_dev = nullptr;            // [F]
     double* bbox_dev = nullptr;         // [F][4]
-    double* bbox_pinned = nullptr;      // [F][4] pinned host mirror, filled asynchronously
+    dsss_buf bbox_pinned{"bbox_pinned", DSSS_PINNED};  // [F][4] pinned host mirror, filled asynchronously
     bool bbox_pending = false;          // frames whose box has not been launched yet
-    bool bbox_inflight = false; std::vector<int> bbox_inflight_ids; void* bbox_jobs_pinned = nullptr;      // boxes queued on the stream (dsss_bboxes_enqueue), not yet copied into dsss_frame::bbox
-    void* bbox_jobs_dev = nullptr;      // [max_frames] job records of dsss_sync_bboxes (a hipMalloc / hipFree pair per call cost 0.15 ms)
+    bool bbox_inflight = false; std::vector<int> bbox_inflight_ids; dsss_buf bbox_jobs_pinned{"bbox_jobs_pinned", DSSS_PINNED};      // boxes queued on the stream (dsss_bboxes_enqueue), not yet copied into dsss_frame::bbox
+    dsss_buf bbox_jobs_dev{"bbox_jobs_dev"};             // [max_frames] job records of dsss_sync_bboxes (a hipMalloc / hipFree pair per call cost 0.15 ms)
     // extraction scratch (grown on demand)
-    void* ex_scratch = nullptr; size_t ex_scratch_bytes = 0;
-    void* ex_pinned = nullptr; size_t ex_pinned_bytes = 0;
+    dsss_buf ex_scratch{"ex_scratch"}, ex_pinned{"ex_pinned", DSSS_PINNED};
     bool ex_tab_uploaded = false;      // ex_side_ev[2] has been recorded: the upload of the pinned batch tables may be waited for
     // extraction started by dsss_frames_set (everything but the kernel that needs the geometry): for which frames, under which parameters
     bool ex_eager_valid = false; std::vector<int> ex_eager_ids; dsss_orb_params ex_eager_op; dsss_mask_params ex_eager_mp;
@@ -98,7 +141,7 @@ struct dsss_ctx {
     // pose-graph solver arena: device chunks kept between solves (dsss_pg.hip), bump-allocated, reset per solve
     std::vector<std::pair<void*, size_t>> pg_chunks; size_t pg_chunk_cur = 0, pg_chunk_off = 0;
     // matcher state
-    void* mt_aux = nullptr; size_t mt_aux_bytes = 0;   // per-frame pointer tables + cv::RNG stream
+    dsss_buf mt_aux{"mt_aux"};                                   // per-frame pointer tables + cv::RNG stream
     const double** d_ptrs = nullptr;                   // [3][max_frames]: alt, gr, pose6 device pointers
     int npairs = 0, nactive = 0;
     std::vector<int> pair_s, pair_t, pair_active;   // pair_active[p] = active index or -1
@@ -114,36 +157,85 @@ struct dsss_ctx {
     bool corres_valid = false;          // corres_nn / corres / scc_* belong to the current result set (dsss_match_pairs', not dsss_lc_solve_pairs')
     // geo grid of the matcher: keypoints of the active pairs' frames sorted by cell (geo, descriptor, original index), cell offsets + tables
     double* mt_gs_geo = nullptr; uint8_t* mt_gs_desc = nullptr; int* mt_gs_idx = nullptr; size_t mt_gs_cap = 0;
-    void* mt_cells = nullptr; size_t mt_cells_bytes = 0; unsigned long long mt_evals_host = 0;
+    dsss_buf mt_cells{"mt_cells"}; unsigned long long mt_evals_host = 0;
     // LC results
-    dsss_lc* lcs = nullptr; size_t lcs_cap = 0; bool has_lc = false;
+    dsss_buf lcs{"lcs"}; bool has_lc = false;  // dsss_lc[total_kp7 (+ 1024)]
     // per-geometry extraction tables (dsss_extract.hip owns the type; freed through geoms_free by dsss_destroy)
     void* geoms = nullptr; void (*geoms_free)(void*) = nullptr;
     dsss_comm* comm = nullptr;          // ranks of one job (dsss_comm_init): null = single process
     int pg_parts = 0;                   // pose-graph partitions (0: one per rank); > ranks only to exercise the interface logic on few GPUs
-    int* tmp_dev = nullptr;             // 64 ints of device scratch for one-value results (dsss_descriptor_distance)
-    void* ag_buf = nullptr; size_t ag_cap = 0;                  // staging of dsss_features_allgather: world x (frames per rank) packed records, kept between calls
-    void* ag_host = nullptr; size_t ag_host_cap = 0;            // page-locked landing place of the gathered headers (keypoint counts, boxes, sizes)
-    double* xch_dev = nullptr; size_t xch_cap = 0;              // device scratch of the loop-closure exchange between ranks (dsss_posegraph_solve)
-    void* pg_edges_host = nullptr; size_t pg_edges_cap = 0;     // page-locked staging of the selected LC edges (dsss_posegraph_solve)
-    int* pg_ab_host = nullptr; size_t pg_ab_cap = 0;      // their end points as packed (a, b) pairs
-    void* xch_host = nullptr; size_t xch_host_cap = 0;          // page-locked landing place of the gathered edge records of all ranks (bytes)
-    double* pg_scal_host = nullptr;                             // page-locked landing place of the LM trial's scalars (8 doubles)
+    dsss_buf tmp_dev{"tmp_dev"};                   // 64 ints of device scratch for one-value results (dsss_descriptor_distance)
+    dsss_buf ag_buf{"ag_buf"};                                            // staging of dsss_features_allgather: world x (frames per rank) packed records, kept between calls
+    dsss_buf ag_host{"ag_host", DSSS_PINNED};                              // page-locked landing place of the gathered headers (keypoint counts, boxes, sizes)
+    dsss_buf xch_dev{"xch_dev"};                                           // device scratch of the loop-closure exchange between ranks (dsss_posegraph_solve)
+    dsss_buf pg_edges_host{"pg_edges_host", DSSS_PINNED};                        // page-locked staging of the selected LC edges (dsss_posegraph_solve)
+    dsss_buf pg_ab_host{"pg_ab_host", DSSS_PINNED};                     // their end points as packed (a, b) pairs
+    dsss_buf xch_host{"xch_host", DSSS_PINNED};                             // page-locked landing place of the gathered edge records of all ranks (bytes)
+    dsss_buf pg_scal_host{"pg_scal_host", DSSS_PINNED};                         // page-locked landing place of the LM trial's scalars (8 doubles)
     std::vector<int> pg_last_levels;                            // schedule of the last solve, four ints per panel level: items, widest panel (scalar columns), tallest rows below, this rank's or the interface's (dsss_posegraph_schedule_get)
     int pg_last_trials = 0;                                     // factorisations of the last solve
-    void* pg_stage = nullptr; size_t pg_stage_cap = 0;          // page-locked staging of the analysis tables: one upload per solve (pg_dev::flush)
+    dsss_buf pg_stage{"pg_stage", DSSS_PINNED};                             // page-locked staging of the analysis tables: one upload per solve (pg_dev::flush)
     // online use (dsss_posegraph_update): the estimate of the previous update stays on the device, the LC edges accumulate
-    void* pg_warm = nullptr; size_t pg_warm_cap = 0; int pg_warm_n = 0;   // pose_t[pg_warm_n]
+    dsss_buf pg_warm{"pg_warm"}; int pg_warm_n = 0;   // pose_t[pg_warm_n]
     std::vector<dsss_lc_edge> pg_inc_edges; unsigned long long lc_gen = 0, pg_inc_gen = 0;    // lc_gen counts LC result sets; the last one consumed
-    void* mosaic_buf = nullptr; size_t mosaic_cap = 0;          // device scratch of dsss_mosaic_*: accumulators, output layers, job table, trajectory rows (kept between calls)
-    void* pgr_buf = nullptr; size_t pgr_cap = 0;                // device scratch of dsss_posegraph_edge_report (dsss_pg_report.hip), kept between calls
+    dsss_buf mosaic_buf{"mosaic_buf"};                                        // device scratch of dsss_mosaic_*: accumulators, output layers, job table, trajectory rows (kept between calls)
+    dsss_buf pgr_buf{"pgr_buf"};                                           // device scratch of dsss_posegraph_edge_report (dsss_pg_report.hip), kept between calls
     dsss_prof prof;
 };
 
 #define DSSS_FAIL(ctx, code, ...) do { char _b[512]; snprintf(_b, sizeof _b, __VA_ARGS__); (ctx)->err = _b; return (code); } while (0)
-#define HIPCHK(ctx, call) do { hipError_t _e = (call); if (_e != hipSuccess) { \
-    char _b[512]; snprintf(_b, sizeof _b, "%s:%d %s -> %s", __FILE__, __LINE__, #call, hipGetErrorString(_e)); \
-    (ctx)->err = _b; return DSSS_E_HIP; } } while (0)
+#define HIPCHK(ctx, call) do { hipError_t _e = (call); if (_e != hipSuccess) return dsss_hip_fail((ctx), _e, __FILE__, __LINE__, #call); } while (0)
+inline int dsss_hip_fail(dsss_ctx* c, hipError_t e, const char* file, int line, const char* call)
+{
+    char b[512]; snprintf(b, sizeof b, "%s:%d %s -> %s", file, line, call, hipGetErrorString(e));
+    c->err = b; return DSSS_E_HIP;
+}
+
+inline int dsss_alloc_fail(dsss_ctx* c, hipError_t e, const char* name, const char* step, size_t bytes)
+{
+    char b[512]; snprintf(b, sizeof b, "%s: %s (%zu bytes) -> %s", name, step, bytes, hipGetErrorString(e));
+    c->err = b; return DSSS_E_HIP;
+}
+
+inline int dsss_buf::reserve(dsss_ctx* c, size_t need_bytes, size_t alloc_bytes)
+{
+    if (cap >= need_bytes) return DSSS_OK;
+    hipError_t e = p ? hipStreamSynchronize(c->stream) : hipSuccess;
+    if (e != hipSuccess) { release(); return dsss_alloc_fail(c, e, name, "hipStreamSynchronize before the old block goes", alloc_bytes); }
+    release();                                              // whatever fails from here on leaves p == nullptr, cap == 0
+    void* q = nullptr;
+    if ((e = dsss_mem_alloc(&q, alloc_bytes, pinned)) != hipSuccess) return dsss_alloc_fail(c, e, name, pinned ? "hipHostMalloc" : "hipMalloc", alloc_bytes);
+    p = q; cap = alloc_bytes;
+    return DSSS_OK;
+}
+// the new block is complete before the old one goes: a failure leaves the buffer as it was
+inline int dsss_buf::reserve_keep(dsss_ctx* c, size_t need_bytes, size_t alloc_bytes, size_t keep_bytes)
+{
+    if (cap >= need_bytes) return DSSS_OK;
+    hipError_t e = p ? hipStreamSynchronize(c->stream) : hipSuccess;
+    if (e != hipSuccess) return dsss_alloc_fail(c, e, name, "hipStreamSynchronize before the old block goes", alloc_bytes);
+    dsss_buf nw(name, pinned);
+    if ((e = dsss_mem_alloc(&nw.p, alloc_bytes, pinned)) != hipSuccess) { nw.p = nullptr; return dsss_alloc_fail(c, e, name, pinned ? "hipHostMalloc" : "hipMalloc", alloc_bytes); }
+    nw.cap = alloc_bytes;
+    if (keep_bytes > 0 && p && (e = hipMemcpy(nw.p, p, keep_bytes, hipMemcpyDeviceToDevice)) != hipSuccess) return dsss_alloc_fail(c, e, name, "copy of the kept prefix", keep_bytes);      // (nw frees itself)
+    *this = std::move(nw);
+    return DSSS_OK;
+}
+template <class Fam> int dsss_family_alloc(dsss_ctx* c, const char* name, size_t& cap, size_t new_cap, const Fam& fam)
+{
+    bool any = false;
+    for (const dsss_fam_slot& s : fam) any = any || *s.pp != nullptr;
+    hipError_t e = any ? hipStreamSynchronize(c->stream) : hipSuccess;
+    dsss_family_release(cap, fam);
+    if (e != hipSuccess) return dsss_alloc_fail(c, e, name, "hipStreamSynchronize before the old blocks go", 0);
+    for (const dsss_fam_slot& s : fam) {
+        void* q = nullptr;
+        if ((e = dsss_mem_alloc(&q, s.bytes, s.pinned)) != hipSuccess) { dsss_family_release(cap, fam); return dsss_alloc_fail(c, e, name, s.pinned ? "hipHostMalloc" : "hipMalloc", s.bytes); }
+        *s.pp = q;
+    }
+    cap = new_cap;
+    return DSSS_OK;
+}
 
 // kernel-family timing with HIP events on the context stream (dsss_profile_*)
 struct dsss_scope {

@@ -522,9 +522,6 @@ static int check_kp7_rows(dsss_ctx* c, const dsss_frame& fs, const dsss_frame& f
     return DSSS_OK;
 }
 
-// a temporary device allocation of one call: freed on every way out of it
-struct dev_tmp { void* p = nullptr; hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes); } ~dev_tmp() { hipFree(p); } };
-
 extern "C" {
 
 int dsss_lc_solve_all(dsss_ctx* c)
@@ -533,16 +530,12 @@ int dsss_lc_solve_all(dsss_ctx* c)
     HIPCHK(c, hipSetDevice(c->device));
     const int n = c->total_kp7;
     c->has_lc = false;
-    if ((size_t)n > c->lcs_cap) {
-        HIPCHK(c, hipStreamSynchronize(c->stream)); hipFree(c->lcs); c->lcs = nullptr; c->lcs_cap = 0;
-        HIPCHK(c, hipMalloc(&c->lcs, ((size_t)n + 1024) * sizeof(dsss_lc)));
-        c->lcs_cap = (size_t)n + 1024;
-    }
+    if (const int rc = c->lcs.reserve(c, (size_t)n * sizeof(dsss_lc), ((size_t)n + 1024) * sizeof(dsss_lc))) return rc;
     const int F = c->max_frames;
     if (n > 0) {
         dsss_scope sc(c, DSSS_K_LC);
         hipLaunchKernelGGL(lc_kernel, dim3((n + 3) / 4), dim3(64), 0, c->stream, c->kp7, n, c->kp7_pair, c->kp7_flip, c->act_s, c->act_t,
-                           0, 0, 0, c->d_ptrs, c->d_ptrs + F, c->d_ptrs + 2 * F, c->cols_dev, c->lcs);
+                           0, 0, 0, c->d_ptrs, c->d_ptrs + F, c->d_ptrs + 2 * F, c->cols_dev, c->lcs.as<dsss_lc>());
         HIPCHK(c, hipGetLastError());
     }
     c->has_lc = true; ++c->lc_gen;      // an LC result set exists once its launch is queued (none for an empty one)
@@ -560,7 +553,7 @@ int dsss_lc_get(dsss_ctx* c, int pair, dsss_lc* out, int cap, int* nout)
     if (n == 0 || !out) return DSSS_OK;
     if (cap < n) DSSS_FAIL(c, DSSS_E_CAPACITY, "caller capacity %d < %d", cap, n);
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(out, c->lcs + c->h_kp7_off[a], (size_t)n * sizeof(dsss_lc), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(out, c->lcs.as<dsss_lc>() + c->h_kp7_off[a], (size_t)n * sizeof(dsss_lc), hipMemcpyDeviceToHost));
     return DSSS_OK;
 }
 
@@ -627,9 +620,8 @@ int dsss_lc_solve(dsss_ctx* c, int id_s, int id_t, const double* kp7, int n, dss
     int rc = check_kp7_rows(c, c->frames[id_s], c->frames[id_t], h.data(), n, -1); if (rc) return rc;
     if ((rc = dsss_sync_bboxes(c))) return rc;                 // also publishes the frames' N and M to the device tables
     if ((rc = dsss_mt_upload_ptr_tables(c))) return rc;
-    dev_tmp d_kp7, d_out;
-    HIPCHK(c, d_kp7.alloc(h.size() * sizeof(double)));
-    HIPCHK(c, d_out.alloc((size_t)n * sizeof(dsss_lc)));
+    dsss_buf d_kp7("dsss_lc_solve kp7"), d_out("dsss_lc_solve results");      // of this call: freed on every way out of it
+    if ((rc = d_kp7.reserve(c, h.size() * sizeof(double))) || (rc = d_out.reserve(c, (size_t)n * sizeof(dsss_lc)))) return rc;
     HIPCHK(c, hipMemcpyAsync(d_kp7.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
     const int F = c->max_frames;
     {
@@ -656,9 +648,8 @@ int dsss_triangulate(dsss_ctx* c, int id_s, int id_t, const double* kp7, int n, 
     std::vector<double> h((size_t)n * 7);
     HIPCHK(c, hipMemcpy(h.data(), kp7, h.size() * sizeof(double), hipMemcpyDefault));
     int rc = check_kp7_rows(c, fs, ft, h.data(), n, -1); if (rc) return rc;
-    dev_tmp d_kp7, d_out;
-    HIPCHK(c, d_kp7.alloc(h.size() * sizeof(double)));
-    HIPCHK(c, d_out.alloc(h.size() * sizeof(double)));
+    dsss_buf d_kp7("dsss_triangulate kp7"), d_out("dsss_triangulate results");      // of this call
+    if ((rc = d_kp7.reserve(c, h.size() * sizeof(double))) || (rc = d_out.reserve(c, h.size() * sizeof(double)))) return rc;
     HIPCHK(c, hipMemcpyAsync(d_kp7.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(tri_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, (const double*)d_kp7.p, n, fs.pose6, fs.alt, fs.gr, fs.M, ft.pose6, ft.alt, ft.gr, ft.M, (const double*)nullptr, (double*)d_out.p);
     HIPCHK(c, hipGetLastError());
@@ -674,8 +665,8 @@ int dsss_triangulate_poses(dsss_ctx* c, const double* kp7, const double* in27, i
     if (!c || n < 0 || (n > 0 && (!kp7 || !in27 || !out7))) return DSSS_E_ARG;
     if (n == 0) return DSSS_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    dev_tmp d;
-    HIPCHK(c, d.alloc((size_t)n * (7 + 27 + 7) * sizeof(double)));
+    dsss_buf d("dsss_triangulate_poses scratch");      // of this call
+    if (const int rc = d.reserve(c, (size_t)n * (7 + 27 + 7) * sizeof(double))) return rc;
     double* d_kp7 = (double*)d.p; double* d_in = d_kp7 + (size_t)n * 7; double* d_out = d_in + (size_t)n * 27;
     HIPCHK(c, hipMemcpyAsync(d_kp7, kp7, (size_t)n * 7 * sizeof(double), hipMemcpyDefault, c->stream));
     HIPCHK(c, hipMemcpyAsync(d_in, in27, (size_t)n * 27 * sizeof(double), hipMemcpyDefault, c->stream));

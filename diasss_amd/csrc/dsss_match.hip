@@ -583,8 +583,6 @@ __global__ void hamming_one_kernel(const uint8_t* a, const uint8_t* b, int* out)
     *out = d;
 }
 
-#define DSSS_FREE0(p) do { hipFree(p); (p) = nullptr; } while (0)
-
 // threshold T with sqrt(d) < radius  <=>  d < T for correctly rounded sqrt
 static double gate_threshold(double radius)
 {
@@ -595,57 +593,30 @@ static double gate_threshold(double radius)
 }
 
 // ------------------------------------------------------------------ the device buffers of a pair result set (dsss_internal.h)
-// Allocated and freed HERE only, one family per capacity field.  Every reserve: synchronise the stream (a queued kernel may still read the old buffers), free + null,
-// and publish the new capacity only after every allocation of the family succeeded -- a failed hipMalloc leaves capacity 0 and null pointers: the next call starts over, dsss_destroy is safe.
-static void free_pair_index(dsss_ctx* c) { c->pair_idx_cap = 0; DSSS_FREE0(c->act_s); DSSS_FREE0(c->act_t); DSSS_FREE0(c->kp7_off); }
-static void free_pair_match(dsss_ctx* c)
+// Allocated and freed HERE only, one family per capacity field, by the family rule of dsss_internal.h (dsss_family_alloc): synchronise, free + null, allocate, and
+// publish the capacity only after every allocation of the family succeeded.  Each family is listed ONCE, with the sizes for `n` of its capacity's unit.
+static std::array<dsss_fam_slot, 3> pair_index_family(dsss_ctx* c, size_t np = 0) { return {{ dsss_slot(c->act_s, np * sizeof(int)), dsss_slot(c->act_t, np * sizeof(int)), dsss_slot(c->kp7_off, (np + 1) * sizeof(int)) }}; }
+static std::array<dsss_fam_slot, 8> pair_match_family(dsss_ctx* c, size_t np = 0)
 {
-    c->match_cap_pairs = 0; DSSS_FREE0(c->corres_nn); DSSS_FREE0(c->corres); DSSS_FREE0(c->scc_hist); DSSS_FREE0(c->scc_count); DSSS_FREE0(c->scc_model);
-    DSSS_FREE0(c->row_cnt); DSSS_FREE0(c->kp7_cnt); DSSS_FREE0(c->row_off);
+    return {{ dsss_slot(c->corres_nn, 2 * np * c->kcap * sizeof(int32_t)), dsss_slot(c->corres, 2 * np * c->kcap * sizeof(int32_t)), dsss_slot(c->scc_hist, 2 * np * sizeof(int)), dsss_slot(c->scc_count, 2 * np * sizeof(int)),
+              dsss_slot(c->scc_model, 2 * np * sizeof(double)), dsss_slot(c->row_cnt, np * sizeof(int)), dsss_slot(c->kp7_cnt, np * sizeof(int)), dsss_slot(c->row_off, (np + 1) * sizeof(int)) }};
 }
-static void free_rows(dsss_ctx* c) { c->rows_cap = 0; DSSS_FREE0(c->rows6); DSSS_FREE0(c->kp7); DSSS_FREE0(c->kp7_pair); DSSS_FREE0(c->kp7_flip); }
-static void free_aux(dsss_ctx* c) { c->mt_aux_bytes = 0; c->d_ptrs = nullptr; DSSS_FREE0(c->mt_aux); }
-static void free_grid_sorted(dsss_ctx* c) { c->mt_gs_cap = 0; DSSS_FREE0(c->mt_gs_geo); DSSS_FREE0(c->mt_gs_desc); DSSS_FREE0(c->mt_gs_idx); }
-static void free_grid_cells(dsss_ctx* c) { c->mt_cells_bytes = 0; DSSS_FREE0(c->mt_cells); }
-int dsss_mt_reserve_pair_index(dsss_ctx* c, size_t np)
-{
-    if (np <= c->pair_idx_cap) return DSSS_OK;
-    HIPCHK(c, hipStreamSynchronize(c->stream)); free_pair_index(c);
-    HIPCHK(c, hipMalloc(&c->act_s, np * sizeof(int))); HIPCHK(c, hipMalloc(&c->act_t, np * sizeof(int))); HIPCHK(c, hipMalloc(&c->kp7_off, (np + 1) * sizeof(int)));
-    c->pair_idx_cap = np; return DSSS_OK;
-}
-int dsss_mt_reserve_pair_match(dsss_ctx* c, size_t np)
-{
-    if (np <= c->match_cap_pairs) return DSSS_OK;
-    HIPCHK(c, hipStreamSynchronize(c->stream)); free_pair_match(c);
-    HIPCHK(c, hipMalloc(&c->corres_nn, 2 * np * c->kcap * sizeof(int32_t))); HIPCHK(c, hipMalloc(&c->corres, 2 * np * c->kcap * sizeof(int32_t)));
-    HIPCHK(c, hipMalloc(&c->scc_hist, 2 * np * sizeof(int))); HIPCHK(c, hipMalloc(&c->scc_count, 2 * np * sizeof(int)));
-    HIPCHK(c, hipMalloc(&c->scc_model, 2 * np * sizeof(double)));
-    HIPCHK(c, hipMalloc(&c->row_cnt, np * sizeof(int))); HIPCHK(c, hipMalloc(&c->kp7_cnt, np * sizeof(int))); HIPCHK(c, hipMalloc(&c->row_off, (np + 1) * sizeof(int)));
-    c->match_cap_pairs = np; return DSSS_OK;
-}
-int dsss_mt_reserve_rows(dsss_ctx* c, size_t n)
-{
-    if (n <= c->rows_cap) return DSSS_OK;
-    HIPCHK(c, hipStreamSynchronize(c->stream)); free_rows(c);
-    const size_t want = n + 1024;
-    HIPCHK(c, hipMalloc(&c->rows6, want * 6 * sizeof(double))); HIPCHK(c, hipMalloc(&c->kp7, want * 7 * sizeof(double)));
-    HIPCHK(c, hipMalloc(&c->kp7_pair, want * sizeof(int))); HIPCHK(c, hipMalloc(&c->kp7_flip, want));
-    c->rows_cap = want; return DSSS_OK;
-}
+static std::array<dsss_fam_slot, 4> rows_family(dsss_ctx* c, size_t want = 0) { return {{ dsss_slot(c->rows6, want * 6 * sizeof(double)), dsss_slot(c->kp7, want * 7 * sizeof(double)), dsss_slot(c->kp7_pair, want * sizeof(int)), dsss_slot(c->kp7_flip, want) }}; }
+static std::array<dsss_fam_slot, 3> grid_sorted_family(dsss_ctx* c, size_t FK = 0) { return {{ dsss_slot(c->mt_gs_geo, FK * 2 * sizeof(double)), dsss_slot(c->mt_gs_desc, FK * 32), dsss_slot(c->mt_gs_idx, FK * sizeof(int)) }}; }
+int dsss_mt_reserve_pair_index(dsss_ctx* c, size_t np) { return np <= c->pair_idx_cap ? DSSS_OK : dsss_family_alloc(c, "pair index", c->pair_idx_cap, np, pair_index_family(c, np)); }
+int dsss_mt_reserve_pair_match(dsss_ctx* c, size_t np) { return np <= c->match_cap_pairs ? DSSS_OK : dsss_family_alloc(c, "pair match buffers", c->match_cap_pairs, np, pair_match_family(c, np)); }
+int dsss_mt_reserve_rows(dsss_ctx* c, size_t n) { return n <= c->rows_cap ? DSSS_OK : dsss_family_alloc(c, "match rows", c->rows_cap, n + 1024, rows_family(c, n + 1024)); }
 // mt_aux = the [3][max_frames] device pointers alt, gr, pose6 (d_ptrs; small, rebuilt per call), then the 2 * scc_iters words of the cv::RNG stream
-static uint32_t* aux_rng_words(dsss_ctx* c) { return (uint32_t*)((char*)c->mt_aux + 3 * (size_t)c->max_frames * sizeof(double*)); }
+static uint32_t* aux_rng_words(dsss_ctx* c) { return (uint32_t*)(c->mt_aux.as<char>() + 3 * (size_t)c->max_frames * sizeof(double*)); }
 int dsss_mt_upload_ptr_tables(dsss_ctx* c)
 {
     const int F = c->max_frames;
     std::vector<const double*> hp(3 * (size_t)F, nullptr);
     for (int f = 0; f < F; ++f) { hp[f] = c->frames[f].alt; hp[F + f] = c->frames[f].gr; hp[2 * F + f] = c->frames[f].pose6; }
     const size_t need = hp.size() * sizeof(double*) + 2 * (size_t)c->mt.scc_iters * sizeof(uint32_t);
-    if (c->mt_aux_bytes < need) {
-        HIPCHK(c, hipStreamSynchronize(c->stream)); free_aux(c);
-        HIPCHK(c, hipMalloc(&c->mt_aux, need)); c->mt_aux_bytes = need;
-    }
-    c->d_ptrs = (const double**)c->mt_aux;
+    c->d_ptrs = nullptr;                 // a view into mt_aux: none while that may fail
+    if (const int rc = c->mt_aux.reserve(c, need)) return rc;
+    c->d_ptrs = c->mt_aux.as<const double*>();
     HIPCHK(c, hipMemcpyAsync((void*)c->d_ptrs, hp.data(), hp.size() * sizeof(double*), hipMemcpyHostToDevice, c->stream));
     return DSSS_OK;
 }
@@ -653,16 +624,8 @@ int dsss_mt_upload_ptr_tables(dsss_ctx* c)
 // the geo grid's own buffers (matcher only): the sorted copies of [F][kcap] keypoints, and tables + cell offsets with a quarter of headroom
 static int reserve_grid(dsss_ctx* c, size_t FK, size_t cells_bytes)
 {
-    if (c->mt_gs_cap != FK) {
-        HIPCHK(c, hipStreamSynchronize(c->stream)); free_grid_sorted(c);
-        HIPCHK(c, hipMalloc(&c->mt_gs_geo, FK * 2 * sizeof(double))); HIPCHK(c, hipMalloc(&c->mt_gs_desc, FK * 32)); HIPCHK(c, hipMalloc(&c->mt_gs_idx, FK * sizeof(int)));
-        c->mt_gs_cap = FK;
-    }
-    if (c->mt_cells_bytes < cells_bytes) {
-        HIPCHK(c, hipStreamSynchronize(c->stream)); free_grid_cells(c);
-        HIPCHK(c, hipMalloc(&c->mt_cells, cells_bytes + cells_bytes / 4)); c->mt_cells_bytes = cells_bytes + cells_bytes / 4;
-    }
-    return DSSS_OK;
+    if (c->mt_gs_cap != FK) { if (const int rc = dsss_family_alloc(c, "geo grid sorted copies", c->mt_gs_cap, FK, grid_sorted_family(c, FK))) return rc; }
+    return c->mt_cells.reserve(c, cells_bytes, cells_bytes + cells_bytes / 4);
 }
 void dsss_mt_clear_results(dsss_ctx* c)
 {
@@ -672,7 +635,8 @@ void dsss_mt_clear_results(dsss_ctx* c)
 void dsss_mt_free(dsss_ctx* c)
 {
     dsss_mt_clear_results(c);            // the bookkeeping describes these buffers
-    free_pair_index(c); free_pair_match(c); free_rows(c); free_aux(c); free_grid_sorted(c); free_grid_cells(c);
+    dsss_family_release(c->pair_idx_cap, pair_index_family(c)); dsss_family_release(c->match_cap_pairs, pair_match_family(c)); dsss_family_release(c->rows_cap, rows_family(c));
+    dsss_family_release(c->mt_gs_cap, grid_sorted_family(c)); c->d_ptrs = nullptr; c->mt_aux.release(); c->mt_cells.release();
 }
 
 // dsss_match_params::use_l2 -> the kernels' MODE, chosen in ONE place: fn gets it as a compile-time constant
@@ -751,7 +715,7 @@ struct mt_run {
         int rc;
         if ((rc = dsss_mt_reserve_pair_index(c, na)) || (rc = dsss_mt_reserve_pair_match(c, na)) || !use_grid) return rc;
         if ((rc = reserve_grid(c, (size_t)F * K, 2 * gcells * sizeof(int) + (size_t)F * sizeof(mt_grid) + (size_t)F * sizeof(int) + 16))) return rc;
-        char* base = (char*)c->mt_cells;
+        char* base = c->mt_cells.as<char>();
         d_tab = (mt_grid*)base;                                                   // [F] (16-byte entries first: alignment)
         d_frames = (int*)(base + (size_t)F * sizeof(mt_grid));                    // [frames of the active pairs]
         d_start = d_frames + F; d_cur = d_start + gcells;
@@ -781,7 +745,7 @@ struct mt_run {
             const dim3 ggrid((max_nkp + MT_TILE / MT_LPQ - 1) / (MT_TILE / MT_LPQ), 2 * na);
             hipLaunchKernelGGL(mt_grid_build_kernel, dim3((unsigned)gframes.size()), dim3(MTG_THREADS), 0, c->stream, d_frames, d_tab, c->nkp_dev, c->desc, c->geo,
                                c->bbox_dev, (int)K, inv_cs, d_start, d_cur, (double2*)c->mt_gs_geo, (uint4*)c->mt_gs_desc, c->mt_gs_idx);
-            const uint4* sdesc = (const uint4*)(m.use_l2 == 2 ? c->desc128 : c->mt_gs_desc);      // MODE 2 reads the store's 128-byte rows
+            const uint4* sdesc = (const uint4*)(m.use_l2 == 2 ? c->desc128.as<uint8_t>() : c->mt_gs_desc);      // MODE 2 reads the store's 128-byte rows
             with_mode(m.use_l2, [&](auto mode) {
                 hipLaunchKernelGGL(match_grid_kernel<decltype(mode)::value>, ggrid, dim3(MT_TILE), 0, c->stream, c->act_s, c->act_t, c->nkp_dev, c->bbox_dev, d_tab,
                                    d_start, (const double2*)c->mt_gs_geo, sdesc, c->mt_gs_idx, (int)K, inv_cs, T, m.bound_same, m.bound_diff, m.l2_bound, m.ratio, c->corres_nn); });
@@ -791,7 +755,7 @@ struct mt_run {
             if (c->prof.on) c->prof.work[DSSS_K_MATCH_DONE] += evals;      // the all-pairs kernel performs every evaluation it is credited with
             with_mode(m.use_l2, [&](auto mode) {
                 hipLaunchKernelGGL(match_nn_kernel<decltype(mode)::value>, grid, dim3(MT_TILE), 0, c->stream, c->act_s, c->act_t, c->nkp_dev,
-                                   m.use_l2 == 2 ? c->desc128 : c->desc, c->geo, c->bbox_dev, (int)K, T, m.bound_same, m.bound_diff, m.l2_bound, m.ratio, c->corres_nn); });
+                                   m.use_l2 == 2 ? c->desc128.as<uint8_t>() : c->desc, c->geo, c->bbox_dev, (int)K, T, m.bound_same, m.bound_diff, m.l2_bound, m.ratio, c->corres_nn); });
             HIPCHK(c, hipGetLastError());
         }
         if (!d_evals) return DSSS_OK;
@@ -922,8 +886,8 @@ int dsss_descriptor_distance(dsss_ctx* c, int id_a, int ia, int id_b, int ib, in
     if (id_a < 0 || id_a >= c->max_frames || id_b < 0 || id_b >= c->max_frames) DSSS_FAIL(c, DSSS_E_ARG, "frame id out of range");
     if (!c->frames[id_a].has_feat || !c->frames[id_b].has_feat || ia < 0 || ib < 0 || ia >= c->frames[id_a].nkp || ib >= c->frames[id_b].nkp)
         DSSS_FAIL(c, DSSS_E_ARG, "descriptor index out of range");
-    if (!c->tmp_dev) HIPCHK(c, hipMalloc(&c->tmp_dev, 64 * sizeof(int)));      // once per context, not per call
-    int* d_out = c->tmp_dev;
+    if (const int rc = c->tmp_dev.reserve(c, 64 * sizeof(int))) return rc;      // once per context, not per call
+    int* d_out = c->tmp_dev.as<int>();
     hipLaunchKernelGGL(hamming_one_kernel, dim3(1), dim3(1), 0, c->stream, c->desc + ((size_t)id_a * c->kcap + ia) * 32,
                        c->desc + ((size_t)id_b * c->kcap + ib) * 32, d_out);
     hipError_t e = hipMemcpyAsync(dist, d_out, sizeof(int), hipMemcpyDeviceToHost, c->stream);

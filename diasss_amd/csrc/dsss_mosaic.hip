@@ -85,16 +85,6 @@ __global__ __launch_bounds__(256) void mosaic_fold_kernel(const unsigned long lo
 } // namespace
 
 // ---- host helpers shared with dsss_mosaic_reg.hip (dsss_mosaic_int.h)
-int mosaic_reserve(dsss_ctx* c, size_t bytes)
-{
-    if (c->mosaic_cap >= bytes) return DSSS_OK;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    hipFree(c->mosaic_buf); c->mosaic_buf = nullptr; c->mosaic_cap = 0;
-    HIPCHK(c, hipMalloc(&c->mosaic_buf, bytes));
-    c->mosaic_cap = bytes;
-    return DSSS_OK;
-}
-
 int mosaic_check_frames(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, bool need_img, size_t* rows)
 {
     if (!ids || n < 1) DSSS_FAIL(c, DSSS_E_ARG, "mosaic: no frame ids");
@@ -230,8 +220,8 @@ int dsss_mosaic_render(dsss_ctx* c, const int* ids, int n, const double* rpy6, c
     const size_t o_acc = L.take(cells * 8), o_sum = L.take(sum_host ? cells * 4 : 0), o_cnt = L.take(cnt_host ? cells * 4 : 0),
                  o_img = L.take(img_host ? cells : 0), o_jobs = L.take((size_t)n * sizeof(mosaic_job)), o_rows = L.take(rpy6 ? rows * 6 * sizeof(double) : 0),
                  o_flag = L.take(sizeof(int));
-    rc = mosaic_reserve(c, L.off); if (rc) return rc;
-    char* B = static_cast<char*>(c->mosaic_buf);
+    rc = c->mosaic_buf.reserve(c, L.off); if (rc) return rc;
+    char* B = c->mosaic_buf.as<char>();
     unsigned long long* acc = reinterpret_cast<unsigned long long*>(B + o_acc);
     uint32_t* d_sum = sum_host ? reinterpret_cast<uint32_t*>(B + o_sum) : nullptr;
     uint32_t* d_cnt = cnt_host ? reinterpret_cast<uint32_t*>(B + o_cnt) : nullptr;
@@ -301,8 +291,8 @@ int dsss_mosaic_consistency(dsss_ctx* c, const int* ids, int n, const double* rp
     carve L;
     const size_t o_lay = L.take(cells * 12), o_win = L.take(win_cells * 8), o_jobs = L.take((size_t)n * sizeof(mosaic_job)),
                  o_rows = L.take(rpy6 ? rows * 6 * sizeof(double) : 0), o_flag = L.take(sizeof(int));
-    rc = mosaic_reserve(c, L.off); if (rc) return rc;
-    char* B = static_cast<char*>(c->mosaic_buf);
+    rc = c->mosaic_buf.reserve(c, L.off); if (rc) return rc;
+    char* B = c->mosaic_buf.as<char>();
     uint32_t* d_nfr = reinterpret_cast<uint32_t*>(B + o_lay); uint32_t* d_s1 = d_nfr + cells; uint32_t* d_s2 = d_s1 + cells;
     unsigned long long* d_win = reinterpret_cast<unsigned long long*>(B + o_win);
     mosaic_job* d_jobs = reinterpret_cast<mosaic_job*>(B + o_jobs);

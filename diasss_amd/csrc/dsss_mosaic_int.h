@@ -16,7 +16,6 @@ struct mosaic_win { double x0, y0, cell; int W, H, ox, oy, bw, bh, use_mask; };
 // carves mosaic_buf into 256-byte aligned pieces
 struct carve { size_t off = 0; size_t take(size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; } };
 
-int mosaic_reserve(dsss_ctx* c, size_t bytes);
 int mosaic_check_frames(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, bool need_img, size_t* rows);
 int mosaic_check_params(dsss_ctx* c, const dsss_mosaic_params* p);
 void frame_extent(const dsss_frame& f, const double* rows, double* bb);

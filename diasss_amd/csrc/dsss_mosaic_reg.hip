@@ -241,8 +241,8 @@ int dsss_mosaic_register(dsss_ctx* c, const int* ids, int n, const double* rpy6,
     const size_t o_lay = L.take(lay_cells * 2), o_win = L.take(win_cells * 8), o_jobs = L.take((size_t)n * sizeof(mosaic_job)),
                  o_rows = L.take(rpy6 ? rows * 6 * sizeof(double) : 0), o_pairs = L.take((size_t)npairs * sizeof(reg_job)),
                  o_tab = L.take((table + 1) * 8);                               // the sums and, behind them, the sample-limit flag: one download
-    rc = mosaic_reserve(c, L.off); if (rc) return rc;
-    char* B = static_cast<char*>(c->mosaic_buf);
+    rc = c->mosaic_buf.reserve(c, L.off); if (rc) return rc;
+    char* B = c->mosaic_buf.as<char>();
     uint16_t* d_lay = reinterpret_cast<uint16_t*>(B + o_lay);
     unsigned long long* d_win = reinterpret_cast<unsigned long long*>(B + o_win);
     mosaic_job* d_jobs = reinterpret_cast<mosaic_job*>(B + o_jobs);

@@ -70,14 +70,8 @@ struct pg_dev {
         if (stage_ev_live) { hipEventSynchronize(stage_ev); stage_ev_live = false; }      // the previous upload out of the staging area has left it
         char* dev = nullptr;
         if (alloc(c, &dev, pend_total)) return rc;
-        if (c->pg_stage_cap < pend_total) {
-            if (c->pg_stage) hipHostFree(c->pg_stage);
-            c->pg_stage = nullptr; c->pg_stage_cap = 0;
-            const size_t cap = pend_total + pend_total / 4;
-            HIPCHK(c, hipHostMalloc(&c->pg_stage, cap, hipHostMallocDefault));
-            c->pg_stage_cap = cap;
-        }
-        char* stage = static_cast<char*>(c->pg_stage);
+        if (const int r = c->pg_stage.reserve(c, pend_total, pend_total + pend_total / 4)) return r;
+        char* stage = c->pg_stage.as<char>();
         const int T = pend_total > ((size_t)1 << 20) ? 4 : 1;
         dsss_pool_run(T, [&](int t) { for (size_t k = t; k < pending.size(); k += T) if (pending[k].bytes) memcpy(stage + pending[k].off, pending[k].src, pending[k].bytes); });
         HIPCHK(c, hipMemcpyAsync(dev, stage, pend_total, hipMemcpyHostToDevice, st));
@@ -455,12 +449,13 @@ struct pg_solve {
             host3[0] = h4[0]; host3[1] = h4[1]; host3[2] = h4[2]; *failed = h4[3] != 0.0;
         } else {
             // into page-locked memory: a copy to the caller's stack is staged by the runtime and waits for it twice per trial
-            if (!c->pg_scal_host) HIPCHK(c, hipHostMalloc((void**)&c->pg_scal_host, 8 * sizeof(double), hipHostMallocDefault));
-            HIPCHK(c, hipMemcpyAsync(c->pg_scal_host, d_scal, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
-            HIPCHK(c, hipMemcpyAsync(c->pg_scal_host + 4, d_fail, sizeof(int), hipMemcpyDeviceToHost, st));
+            if (const int r = c->pg_scal_host.reserve(c, 8 * sizeof(double))) return r;
+            double* const scal_host = c->pg_scal_host.as<double>();
+            HIPCHK(c, hipMemcpyAsync(scal_host, d_scal, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+            HIPCHK(c, hipMemcpyAsync(scal_host + 4, d_fail, sizeof(int), hipMemcpyDeviceToHost, st));
             HIPCHK(c, hipStreamSynchronize(st));
-            host3[0] = c->pg_scal_host[0]; host3[1] = c->pg_scal_host[1]; host3[2] = c->pg_scal_host[2];
-            *failed = *reinterpret_cast<const int*>(c->pg_scal_host + 4);
+            host3[0] = scal_host[0]; host3[1] = scal_host[1]; host3[2] = scal_host[2];
+            *failed = *reinterpret_cast<const int*>(scal_host + 4);
         }
         return DSSS_OK;
     }
@@ -492,7 +487,7 @@ struct pg_solve {
         // online use (dsss_posegraph_update): the pings the previous update covered start from its estimate, the new ones where
         // the reference puts them (dead reckoning o noise, optimizer.cpp:150-160)
         if (win.online && c->pg_warm_n > win.p0) {
-            const pose_t* warm = static_cast<const pose_t*>(c->pg_warm) + win.p0;
+            const pose_t* warm = c->pg_warm.as<const pose_t>() + win.p0;
             HIPCHK(c, hipMemcpyAsync(d_X, warm, (size_t)std::min(n, c->pg_warm_n - win.p0) * sizeof(pose_t), hipMemcpyDeviceToDevice, st));
             // a window is CONDITIONED on the frozen part of the trajectory through its first pose: the prior (sigma 1e-6) holds it where the
             // previous update left it instead of at its dead-reckoned pose
@@ -851,22 +846,12 @@ struct pg_solve {
         const int p0 = win.p0;
         if (win.online) {
             const size_t all = (size_t)p0 + (size_t)n;
-            if (c->pg_warm_cap < all) {
-                HIPCHK(c, hipStreamSynchronize(st));
-                const size_t cap = all + all / 2 + 1024;                        // the graph grows by a frame per update
-                void* nw = nullptr;
-                HIPCHK(c, hipMalloc(&nw, cap * sizeof(pose_t)));
-                if (p0 > 0 && c->pg_warm) {                                     // (a window keeps the frozen part in front of it)
-                    const hipError_t e = hipMemcpy(nw, c->pg_warm, (size_t)p0 * sizeof(pose_t), hipMemcpyDeviceToDevice);
-                    if (e != hipSuccess) { hipFree(nw); HIPCHK(c, e); }
-                }
-                if (c->pg_warm) hipFree(c->pg_warm);
-                c->pg_warm = nw; c->pg_warm_cap = cap;
-            }
-            HIPCHK(c, hipMemcpyAsync(static_cast<pose_t*>(c->pg_warm) + p0, d_X, (size_t)n * sizeof(pose_t), hipMemcpyDeviceToDevice, st));
+            // the graph grows by a frame per update; a window keeps the frozen part in front of it
+            if (const int r = c->pg_warm.reserve_keep(c, all * sizeof(pose_t), (all + all / 2 + 1024) * sizeof(pose_t), (size_t)p0 * sizeof(pose_t))) return r;
+            HIPCHK(c, hipMemcpyAsync(c->pg_warm.as<pose_t>() + p0, d_X, (size_t)n * sizeof(pose_t), hipMemcpyDeviceToDevice, st));
             c->pg_warm_n = (int)all;
         }
-        const pose_t* d_out = p0 > 0 ? static_cast<const pose_t*>(c->pg_warm) : d_X;      // a window reports the whole trajectory
+        const pose_t* d_out = p0 > 0 ? c->pg_warm.as<const pose_t>() : d_X;      // a window reports the whole trajectory
         const int n_out = p0 + n;
         if (poses12)        // pose_t is 12 contiguous doubles (R row-major, t): straight into the caller's buffer
             HIPCHK(c, hipMemcpyAsync(poses12, d_out, (size_t)n_out * sizeof(pose_t), hipMemcpyDeviceToHost, st));
@@ -998,31 +983,26 @@ static int pg_select_impl(dsss_ctx* c, int nframes, dsss_lc_edge* edges, int cap
         rc = dv.alloc(c, &d_edges, (size_t)cap); if (rc) return rc;
         if (ends) {
             rc = dv.alloc(c, &d_ab, (size_t)cap); if (rc) return rc;
-            if (c->pg_ab_cap < (size_t)cap) {
-                if (c->pg_ab_host) hipHostFree(c->pg_ab_host);
-                c->pg_ab_host = nullptr; c->pg_ab_cap = 0;
-                HIPCHK(c, hipHostMalloc((void**)&c->pg_ab_host, (size_t)cap * sizeof(int2), hipHostMallocDefault));
-                c->pg_ab_cap = (size_t)cap;
-            }
+            if ((rc = c->pg_ab_host.reserve(c, (size_t)cap * sizeof(int2)))) return rc;
         }
         hipStream_t st = c->stream;
         HIPCHK(c, hipMemsetAsync(d_slot, 0, (size_t)total * sizeof(unsigned long long), st));
         HIPCHK(c, hipMemcpyAsync(d_off, off.data(), (nframes + 1) * sizeof(int), hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(lc_select_kernel, dim3((n + 255) / 256), dim3(256), 0, st, c->kp7, n, c->kp7_pair, c->kp7_off, c->act_t, d_off, d_slot);
-        hipLaunchKernelGGL(lc_edge_flag_kernel, dim3((total + 255) / 256), dim3(256), 0, st, d_slot, total, c->kp7_off, c->lcs, d_flags);
+        hipLaunchKernelGGL(lc_edge_flag_kernel, dim3((total + 255) / 256), dim3(256), 0, st, d_slot, total, c->kp7_off, c->lcs.as<dsss_lc>(), d_flags);
         hipLaunchKernelGGL(pg_flag_blocksum_kernel, dim3(nb), dim3(256), 0, st, d_flags, (long long)total, d_bsum);
         hipLaunchKernelGGL(pg_flag_scan_kernel, dim3(1), dim3(256), 0, st, d_bsum, nb, d_total);
-        hipLaunchKernelGGL(lc_edge_compact_kernel, dim3(nb), dim3(256), 0, st, d_flags, d_bsum, d_slot, total, c->kp7_off, c->kp7, c->lcs, c->act_s, d_off, cap, d_edges, d_ab);
+        hipLaunchKernelGGL(lc_edge_compact_kernel, dim3(nb), dim3(256), 0, st, d_flags, d_bsum, d_slot, total, c->kp7_off, c->kp7, c->lcs.as<dsss_lc>(), c->act_s, d_off, cap, d_edges, d_ab);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipMemcpyAsync(&ne, d_total, sizeof(int), hipMemcpyDeviceToHost, st));
         const int pre = std::min(cap, PG_AB_PREFIX);               // the count is not known yet: the first pairs travel with it
-        if (ends) HIPCHK(c, hipMemcpyAsync(c->pg_ab_host, d_ab, (size_t)pre * sizeof(int2), hipMemcpyDeviceToHost, st));
+        if (ends) HIPCHK(c, hipMemcpyAsync(c->pg_ab_host.p, d_ab, (size_t)pre * sizeof(int2), hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipStreamSynchronize(st));
         if (ne > cap) { dv.release(); DSSS_FAIL(c, DSSS_E_CAPACITY, "more than %d LC edges", cap); }
         if (ends) {
-            if (ne > pre) { HIPCHK(c, hipMemcpyAsync(c->pg_ab_host + 2 * (size_t)pre, d_ab + pre, (size_t)(ne - pre) * sizeof(int2), hipMemcpyDeviceToHost, st)); HIPCHK(c, hipStreamSynchronize(st)); }
+            if (ne > pre) { HIPCHK(c, hipMemcpyAsync(c->pg_ab_host.as<int>() + 2 * (size_t)pre, d_ab + pre, (size_t)(ne - pre) * sizeof(int2), hipMemcpyDeviceToHost, st)); HIPCHK(c, hipStreamSynchronize(st)); }
             if (ne > 0) HIPCHK(c, hipMemcpyAsync(edges, d_edges, (size_t)ne * sizeof(dsss_lc_edge), hipMemcpyDeviceToHost, st));
-            *ends = c->pg_ab_host;
+            *ends = c->pg_ab_host.as<int>();
         }
         else if (ne > 0) HIPCHK(c, hipMemcpy(edges, d_edges, (size_t)ne * sizeof(dsss_lc_edge), hipMemcpyDeviceToHost));
         dv.release();                                              // synchronises the stream: REQUIRED before the arena is reused (see above)
@@ -1041,16 +1021,9 @@ static int pg_exchange_edges(dsss_ctx* c, dsss_lc_edge** edges, int* n_edges)
     dsss_lc_edge* edges_p = *edges;
     int ne = *n_edges, rc;
     std::vector<double> cnt(world, 0.0); cnt[rank] = ne;
-    auto xch = [&](size_t n) -> int {                    // device scratch of the exchange, kept by the context (a hipMalloc / hipFree pair per call cost 0.3 ms)
-        if (c->xch_cap >= n) return DSSS_OK;
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        hipFree(c->xch_dev); c->xch_dev = nullptr; c->xch_cap = 0;
-        const size_t cap = n + n / 2 + 1024;
-        HIPCHK(c, hipMalloc(&c->xch_dev, cap * sizeof(double))); c->xch_cap = cap;
-        return DSSS_OK;
-    };
+    auto xch = [&](size_t n) { return c->xch_dev.reserve(c, n * sizeof(double), (n + n / 2 + 1024) * sizeof(double)); };      // device scratch of the exchange, kept by the context (a hipMalloc / hipFree pair per call cost 0.3 ms)
     rc = xch(world); if (rc) return rc;
-    double* d_tmp = c->xch_dev;
+    double* d_tmp = c->xch_dev.as<double>();
     hipError_t e = hipMemcpyAsync(d_tmp, cnt.data(), world * sizeof(double), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) { rc = dsss_comm_allreduce(c, d_tmp, world, c->stream); if (rc) return rc; }
     if (e == hipSuccess) e = hipMemcpyAsync(cnt.data(), d_tmp, world * sizeof(double), hipMemcpyDeviceToHost, c->stream);
@@ -1067,13 +1040,8 @@ static int pg_exchange_edges(dsss_ctx* c, dsss_lc_edge** edges, int* n_edges)
     if (tot > 0) {
         const size_t slice = maxc * sizeof(dsss_lc_edge), all = slice * (size_t)world;
         rc = xch((2 * all + sizeof(double) - 1) / sizeof(double)); if (rc) return rc;
-        if (c->xch_host_cap < all) {
-            if (c->xch_host) hipHostFree(c->xch_host);
-            c->xch_host = nullptr; c->xch_host_cap = 0;
-            HIPCHK(c, hipHostMalloc(&c->xch_host, all + all / 2, hipHostMallocDefault));
-            c->xch_host_cap = all + all / 2;
-        }
-        char* d_all = reinterpret_cast<char*>(c->xch_dev);
+        if ((rc = c->xch_host.reserve(c, all, all + all / 2))) return rc;
+        char* d_all = c->xch_dev.as<char>();
         char* d_cmp = d_all + all;
         e = hipSuccess;
         if (ne > 0) e = hipMemcpyAsync(d_all + slice * (size_t)rank, edges_p, (size_t)ne * sizeof(dsss_lc_edge), hipMemcpyHostToDevice, c->stream);
@@ -1084,10 +1052,10 @@ static int pg_exchange_edges(dsss_ctx* c, dsss_lc_edge** edges, int* n_edges)
             if (k) e = hipMemcpyAsync(d_cmp + w * sizeof(dsss_lc_edge), d_all + slice * (size_t)r, k * sizeof(dsss_lc_edge), hipMemcpyDeviceToDevice, c->stream);
             w += k;
         }
-        if (e == hipSuccess) e = hipMemcpyAsync(c->xch_host, d_cmp, tot * sizeof(dsss_lc_edge), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(c->xch_host.p, d_cmp, tot * sizeof(dsss_lc_edge), hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         HIPCHK(c, e);
-        edges_p = static_cast<dsss_lc_edge*>(c->xch_host);
+        edges_p = c->xch_host.as<dsss_lc_edge>();
     }
     ne = (int)tot;
     bool ascending = true;
@@ -1125,13 +1093,8 @@ int dsss_posegraph_solve(dsss_ctx* c, int nframes, double* poses12, double* rpy6
     // the selected edges come back into a page-locked buffer the context keeps (a fresh 7 MB vector per solve cost a millisecond of
     // page faults, and a pageable destination halves the copy rate)
     const size_t ecap = (size_t)std::max(c->total_kp7, 1);
-    if (c->pg_edges_cap < ecap) {
-        if (c->pg_edges_host) hipHostFree(c->pg_edges_host);
-        c->pg_edges_host = nullptr; c->pg_edges_cap = 0;
-        HIPCHK(c, hipHostMalloc(&c->pg_edges_host, ecap * sizeof(dsss_lc_edge), hipHostMallocDefault));
-        c->pg_edges_cap = ecap;
-    }
-    dsss_lc_edge* edges_p = static_cast<dsss_lc_edge*>(c->pg_edges_host);
+    if (const int r = c->pg_edges_host.reserve(c, ecap * sizeof(dsss_lc_edge))) return r;
+    dsss_lc_edge* edges_p = c->pg_edges_host.as<dsss_lc_edge>();
     int ne = 0;
     const double t_dr = ms(t0);
     const auto t1 = std::chrono::steady_clock::now();
@@ -1237,7 +1200,7 @@ static int pg_update_impl(dsss_ctx* c, int nframes, int window_frames, double* p
         rg = gv.alloc(c, &d_g, idx.size()); if (rg) { gv.release(); return rg; }
         std::vector<pose_t> g(idx.size());
         hipError_t e = hipMemcpyAsync(d_idx, idx.data(), idx.size() * sizeof(int), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) { hipLaunchKernelGGL(pg_gather_pose_kernel, dim3(((int)idx.size() + 255) / 256), dim3(256), 0, c->stream, (int)idx.size(), d_idx, static_cast<const pose_t*>(c->pg_warm), d_g); e = hipGetLastError(); }
+        if (e == hipSuccess) { hipLaunchKernelGGL(pg_gather_pose_kernel, dim3(((int)idx.size() + 255) / 256), dim3(256), 0, c->stream, (int)idx.size(), d_idx, c->pg_warm.as<const pose_t>(), d_g); e = hipGetLastError(); }
         if (e == hipSuccess) e = hipMemcpyAsync(g.data(), d_g, g.size() * sizeof(pose_t), hipMemcpyDeviceToHost, c->stream);
         gv.release();                                       // (synchronises the stream: the poses are on the host, the arena is free again)
         HIPCHK(c, e);

@@ -42,17 +42,6 @@ __global__ __launch_bounds__(256) void pg_report_kernel(int n, int ne, const pos
 
 namespace {
 
-// the context keeps the report's device scratch between calls (dsss_ctx::pgr_buf)
-int pgr_reserve(dsss_ctx* c, size_t bytes)
-{
-    if (c->pgr_cap >= bytes) return DSSS_OK;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    hipFree(c->pgr_buf); c->pgr_buf = nullptr; c->pgr_cap = 0;
-    HIPCHK(c, hipMalloc(&c->pgr_buf, bytes + bytes / 4));
-    c->pgr_cap = bytes + bytes / 4;
-    return DSSS_OK;
-}
-
 // the checks of dsss_posegraph_solve_edges on one edge (pg_solve::plan, upload_dr)
 int pgr_check_edges(dsss_ctx* c, const dsss_lc_edge* edges, int ne, int n)
 {
@@ -79,8 +68,8 @@ int pgr_run(dsss_ctx* c, const double* dr6, int n, const dsss_lc_edge* edges, in
                  o_c = o_r + up((size_t)ne * 6 * sizeof(double)), o_p = o_c + up((size_t)ne * sizeof(double)),
                  o_s = o_p + up((size_t)2 * nblk * sizeof(double)), o_a = o_s + up(2 * sizeof(double)),
                  o_b = o_a + up((size_t)ne * sizeof(int)), total = o_b + up((size_t)ne * sizeof(int));
-    if (const int rc = pgr_reserve(c, total)) return rc;
-    char* B = static_cast<char*>(c->pgr_buf);
+    if (const int rc = c->pgr_buf.reserve(c, total, total + total / 4)) return rc;      // the context keeps the report's device scratch between calls
+    char* B = c->pgr_buf.as<char>();
     pose_t *d_X = (pose_t*)(B + o_X), *d_D = (pose_t*)(B + o_D), *d_M = (pose_t*)(B + o_M), *d_EM = (pose_t*)(B + o_EM);
     double *d_dr = (double*)(B + o_dr), *d_ew = (double*)(B + o_ew), *d_r = (double*)(B + o_r), *d_c = (double*)(B + o_c),
            *d_p = (double*)(B + o_p), *d_s = (double*)(B + o_s);

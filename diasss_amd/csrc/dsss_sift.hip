@@ -220,16 +220,16 @@ void dsss_launch_sift_desc(dsss_ctx* c, hipStream_t st, const ex_frame* d_exf, i
     // DSSS_SIFT_HIST_DUMP=<file> (diagnostic, tests/test_gpu_sift.py): the raw 2^-12 fixed-point histograms of every pre-filter keypoint of the
     // batch, int32[nb][kcap][128], written after the launch -- the parity bar UNDER the rounded bytes (a one-unit difference in one of a
     // keypoint's 13 000 rounded shares moves an output byte only once in a few thousand keypoints: the bare v_sqrt_f32 behind __fsqrt_rn did)
-    int* dbg = nullptr;
-    if (dump && hipMalloc(&dbg, (size_t)nb * kcap * 128 * sizeof(int)) != hipSuccess) { (void)hipGetLastError(); dbg = nullptr; }
+    dsss_buf dbg_buf("sift histogram dump");      // of this call; a failure is not an error: no dump, and the context's last error stays what it was
+    if (dump) { const std::string err = c->err; if (dbg_buf.reserve(c, (size_t)nb * kcap * 128 * sizeof(int))) { (void)hipGetLastError(); c->err = err; } }
+    int* dbg = dbg_buf.as<int>();
     if (dbg) (void)hipMemsetAsync(dbg, 0, (size_t)nb * kcap * 128 * sizeof(int), st);
-    hipLaunchKernelGGL(sift_desc_kernel, dim3(kcap, nb), dim3(256), 0, st, d_exf, c->sift_w, dbg, kcap);
+    hipLaunchKernelGGL(sift_desc_kernel, dim3(kcap, nb), dim3(256), 0, st, d_exf, c->sift_w.as<float>(), dbg, kcap);
     if (dbg) {
         std::vector<int> h((size_t)nb * kcap * 128);
         if (hipStreamSynchronize(st) == hipSuccess && hipMemcpy(h.data(), dbg, h.size() * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess) {
             FILE* fp = fopen(dump, "wb");
             if (fp) { fwrite(h.data(), sizeof(int), h.size(), fp); fclose(fp); }
         }
-        hipFree(dbg);
     }
 }

@@ -1,4 +1,6 @@
 """shared builders for the parity tests (seeded, small)"""
+import ctypes
+
 import numpy as np
 from oracle import binding as O
 
@@ -288,3 +290,43 @@ def tri_reference(orc, frames, s, t, kp7, key=None):
     if key is not None:
         _LC_CACHE[("tri", key)] = res
     return res
+
+
+# ---------------------------------------------------------------- small inputs shared by several GPU test modules
+MOSAIC_SIZES = ((640, 400), (500, 700))          # the two legs of the mosaic tests: the smallest sizes test_gpu_extract.py extracts at
+
+
+def survey_frame(N, M, seed, hot=True):
+    """raw image and DR inputs of frame 1 of a two-frame synthetic survey (the extraction tests' frame)"""
+    from diasss_amd.synth import Survey
+    sv = Survey(2, N, M, seed=seed)
+    raw = sv.frame(1).numpy().copy()
+    if hot:   # a few "sensor buggy line" pixels inside the valid area (frame.cpp:98-103)
+        rng = np.random.default_rng(seed)
+        for _ in range(5):
+            raw[rng.integers(160, N - 160), rng.integers(100, M - 100)] = 4.0 * raw.mean()
+        raw[200, 150] = 3.0 * raw.mean()
+    pose, alt, gr = sv.inputs(1)
+    return raw, pose, alt, gr
+
+
+def pg_edge(orc, dr, a, b, dy, var=(1e-6, 1e-6, 1e-5, 1e-3, 0.5, 1e-2)):
+    e = np.zeros(1, orc.LCEDGE_DTYPE)
+    e["a"] = a; e["b"] = b
+    Ta, Tb, Tr = orc.Pose(), orc.Pose(), orc.Pose()
+    orc.lib().orc_pose_from_rodrigues(orc.dp(np.ascontiguousarray(dr[a])), ctypes.byref(Ta))
+    orc.lib().orc_pose_from_rodrigues(orc.dp(np.ascontiguousarray(dr[b])), ctypes.byref(Tb))
+    orc.lib().orc_pose_between(ctypes.byref(Ta), ctypes.byref(Tb), ctypes.byref(Tr))
+    rel = np.concatenate([np.array(Tr.R), np.array(Tr.t)]); rel[10] += dy
+    e["rel"][0] = rel; e["var"][0] = var
+    return e
+
+
+def pg_small_graph(orc):
+    """the 300-pose chain of test_posegraph_edges_api_small_cases with its 9-edge case: duplicates, reversed edges, neighbouring poses"""
+    n = 300
+    dr = np.zeros((n, 6)); dr[:, 3] = 0.05 * np.arange(n); dr[:, 2] = 0.01 * np.sin(np.arange(n) / 30.0)
+    dr[150:, 2] += 3.14159265359; dr[150:, 4] += 5.0; dr[150:, 3] = dr[149, 3] - 0.05 * np.arange(150)
+    spec = [(240, 60, 0.08), (10, 290, 0.2), (60, 240, -0.1), (290, 10, 0.22), (10, 290, 0.25), (60, 240, -0.05), (149, 150, 0.05),
+            (150, 149, -0.02), (10, 290, 0.21)]
+    return dr, np.concatenate([pg_edge(orc, dr, a, b, dy) for a, b, dy in spec])

@@ -3,6 +3,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from tests.helpers import survey_frame as _frame
+
 pytestmark = pytest.mark.gpu
 
 
@@ -12,19 +14,6 @@ def ctx():
     c = capi.Context(max_frames=4)
     yield c
     c.close()
-
-
-def _frame(N, M, seed, hot=True):
-    from diasss_amd.synth import Survey
-    sv = Survey(2, N, M, seed=seed)
-    raw = sv.frame(1).numpy().copy()
-    if hot:   # a few "sensor buggy line" pixels inside the valid area (frame.cpp:98-103)
-        rng = np.random.default_rng(seed)
-        for _ in range(5):
-            raw[rng.integers(160, N - 160), rng.integers(100, M - 100)] = 4.0 * raw.mean()
-        raw[200, 150] = 3.0 * raw.mean()
-    pose, alt, gr = sv.inputs(1)
-    return raw, pose, alt, gr
 
 
 @pytest.mark.parametrize("N,M,seed", [(640, 400, 3), (500, 700, 4), (1000, 512, 5)])

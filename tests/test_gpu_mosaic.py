@@ -8,7 +8,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 E_ARG, E_STATE = -2, -4
-SIZES = ((640, 400), (500, 700))          # the smallest sizes test_gpu_extract.py extracts at
+from tests.helpers import MOSAIC_SIZES as SIZES
 
 
 # ---------------------------------------------------------------- numpy reference

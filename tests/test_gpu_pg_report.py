@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from tests import pg_report_ref as R
+from tests.helpers import pg_edge as _edge, pg_small_graph as _small_graph
 
 pytestmark = pytest.mark.gpu
 
@@ -17,28 +18,6 @@ def ctx():
     c = capi.Context(max_frames=2)
     yield c
     c.close()
-
-
-def _edge(orc, dr, a, b, dy, var=(1e-6, 1e-6, 1e-5, 1e-3, 0.5, 1e-2)):
-    e = np.zeros(1, orc.LCEDGE_DTYPE)
-    e["a"] = a; e["b"] = b
-    Ta, Tb, Tr = orc.Pose(), orc.Pose(), orc.Pose()
-    orc.lib().orc_pose_from_rodrigues(orc.dp(np.ascontiguousarray(dr[a])), C.byref(Ta))
-    orc.lib().orc_pose_from_rodrigues(orc.dp(np.ascontiguousarray(dr[b])), C.byref(Tb))
-    orc.lib().orc_pose_between(C.byref(Ta), C.byref(Tb), C.byref(Tr))
-    rel = np.concatenate([np.array(Tr.R), np.array(Tr.t)]); rel[10] += dy
-    e["rel"][0] = rel; e["var"][0] = var
-    return e
-
-
-def _small_graph(orc):
-    """the 300-pose chain of test_posegraph_edges_api_small_cases with its 9-edge case: duplicates, reversed edges, neighbouring poses"""
-    n = 300
-    dr = np.zeros((n, 6)); dr[:, 3] = 0.05 * np.arange(n); dr[:, 2] = 0.01 * np.sin(np.arange(n) / 30.0)
-    dr[150:, 2] += 3.14159265359; dr[150:, 4] += 5.0; dr[150:, 3] = dr[149, 3] - 0.05 * np.arange(150)
-    spec = [(240, 60, 0.08), (10, 290, 0.2), (60, 240, -0.1), (290, 10, 0.22), (10, 290, 0.25), (60, 240, -0.05), (149, 150, 0.05),
-            (150, 149, -0.02), (10, 290, 0.21)]
-    return dr, np.concatenate([_edge(orc, dr, a, b, dy) for a, b, dy in spec])
 
 
 def _check_report(orc, dr, edges, poses12, got, what):
