@@ -33,6 +33,9 @@ __device__ inline double wave_fixed_sum_tail(double p0, double p1)
     return v;
 }
 
+// (a borrowed device image is only known to be 8-byte aligned, and with it every row of its even number of bins: the pair load says so,
+// as u32_unaligned does for the FAST windows; normalize_kernel checks the address instead)
+typedef double f64x2_a8 __attribute__((ext_vector_type(2), aligned(8)));
 __global__ __launch_bounds__(256) void row_reduce_kernel(const ex_frame* __restrict__ frs)
 {
     const ex_frame& f = frs[blockIdx.y];
@@ -44,7 +47,7 @@ __global__ __launch_bounds__(256) void row_reduce_kernel(const ex_frame* __restr
     double p0 = 0.0, p1 = 0.0, mn = INFINITY;
     for (int j = 2 * lane; j < M; j += 128) {
         if (j + 1 < M) {
-            const double2 v = *reinterpret_cast<const double2*>(r + j);
+            const f64x2_a8 v = *reinterpret_cast<const f64x2_a8*>(r + j);
             p0 += v.x; p1 += v.y;
             mn = v.x < mn ? v.x : mn; mn = v.y < mn ? v.y : mn;
         } else { const double a = r[j]; p0 += a; mn = a < mn ? a : mn; }
@@ -983,6 +986,15 @@ static int get_geom(dsss_ctx* c, int N, int M, level_geom** out)
         for (int l = 0; l < g->nlevels; ++l)
             if (g->rows[l] < 2 * EDGE_T + 31 || g->cols[l] < 2 * EDGE_T + 31)
                 DSSS_FAIL(c, DSSS_E_ARG, "level %d (%d x %d) too small for 30-px FAST cells", l, g->rows[l], g->cols[l]);
+        // what the quadtrees can keep: a level ends within three nodes of its quota, except that its first pass divides every root
+        // whatever the quota is -- up to four nodes a root.  The keypoint store is sized by nfeatures alone (kcap), so a geometry
+        // whose roots could overrun it is refused here, before anything is launched
+        long long keep = 0;
+        for (int l = 0; l < g->nlevels; ++l)
+            keep += std::max(g->quota[l] + 3, 4 * qt_n_roots(g->cols[l] - 2 * (EDGE_T - 3), g->rows[l] - 2 * (EDGE_T - 3)));
+        if (keep > c->kcap)
+            DSSS_FAIL(c, DSSS_E_ARG, "%d x %d frame: the quadtree roots of its levels (one per round(W / H) of a level) can keep %lld keypoints, the store of nfeatures = %d holds %d; raise nfeatures",
+                      N, M, keep, c->op.nfeatures, c->kcap);
         HIPCHK(c, hipMalloc(&g->d_cells, sizeof(fast_cell) * std::max<size_t>(g->cells.size(), 1)));
         HIPCHK(c, hipMalloc(&g->d_lrows, sizeof(int) * DSSS_MAX_LEVELS));
         HIPCHK(c, hipMalloc(&g->d_lscale, sizeof(float) * DSSS_MAX_LEVELS));
@@ -1042,7 +1054,10 @@ static ex_layout make_layout(int N, const level_geom& g, int kcap, bool sift)
     L.xs = take(sizeof(float) * L.cand_cap); L.ys = take(sizeof(float) * L.cand_cap); L.rs = take(sizeof(float) * L.cand_cap);
     L.keys0 = take(sizeof(unsigned long long) * L.cand_cap); L.keys1 = take(sizeof(unsigned long long) * L.cand_cap);
     for (int l = 0; l < DSSS_MAX_LEVELS; ++l) {
-        L.list_cap[l] = 4 * g.quota[l] + 128; L.pool_cap[l] = 16 * g.quota[l] + 1024;
+        // the first pass divides every root whatever the quota is, so a level with R roots lists up to 4 R nodes and pools 5 R before
+        // the quota says anything (one root: the sizes the quota alone gives); pcnt, 4 * list_cap ints, holds the R root counts
+        const int extra = l < g.nlevels ? qt_n_roots(g.cols[l] - 2 * (EDGE_T - 3), g.rows[l] - 2 * (EDGE_T - 3)) - 1 : 0;
+        L.list_cap[l] = 4 * g.quota[l] + 128 + 4 * extra; L.pool_cap[l] = 16 * g.quota[l] + 1024 + 8 * extra;
         L.work[l] = l < g.nlevels ? take(sizeof(int) * ((size_t)8 * L.pool_cap[l] + (size_t)10 * L.list_cap[l])) : 0;
     }
     L.out_idx = take(sizeof(int) * (size_t)DSSS_MAX_LEVELS * L.out_cap); L.out_n = take(sizeof(int) * DSSS_MAX_LEVELS);

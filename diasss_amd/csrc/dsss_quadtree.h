@@ -4,6 +4,10 @@
 
 struct qt_kp_in { float x, y, resp; int level; };
 
+// initial nodes of DistributeOctTree on a level whose FAST range is W x H (ORBextractor.cpp:543-546): round(W / H) in float, at least
+// one.  The kernel and the layout of its work area (make_layout in dsss_extract.hip) both take it from here.
+__host__ __device__ inline int qt_n_roots(int W, int H) { const int n = (int)roundf((float)W / (float)H); return n < 1 ? 1 : n; }
+
 struct qt_inst {                 // one (frame, level)
     const int* offs;             // candidate offsets per FAST cell of the frame (scan_counts_kernel output)
     int cell_begin, cell_end;    // cells of this level
@@ -11,7 +15,7 @@ struct qt_inst {                 // one (frame, level)
     int W, H, quota;             // maxBorderX - minBorderX, maxBorderY - minBorderY, mnFeaturesPerLevel[level]
     unsigned long long *keys0, *keys1;   // frame-wide ping-pong key arrays (candidate capacity each); key = y << 48 | x << 32 | candidate index
     int* work;                   // 8*pool_cap + 10*list_cap ints
-    int list_cap, pool_cap;
+    int list_cap, pool_cap;      // both hold the level's roots and their children on top of what the quota needs
     int* out_idx; int* out_n; int out_cap;
     int* err;
     int cand_cap;                // capacity of xs / ys / rs / keys0 / keys1 (candidates of the whole frame)

@@ -10,7 +10,7 @@
 //     new list = reverse(children created this round) ++ (old list minus the divided parents);
 //   * ties in the size sort use creation order (the reference compares heap addresses; same rule as the oracle and
 //     the host routine in quadtree.cpp);
-//   * nIni = max(1, round(w/h)) (the reference divides by zero for tall levels).
+//   * nIni = max(1, round(w/h)) (the reference divides by zero for tall levels), as the oracle and quadtree.cpp have it: qt_n_roots.
 // Output: the kept candidate of every node (first maximum response in key order), in list order.
 #include "dsss_internal.h"
 #include "dsss_quadtree.h"
@@ -192,9 +192,7 @@ __global__ __launch_bounds__(QT_THREADS) void quadtree_kernel(const qt_inst* __r
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 
     // ---- initial nodes (:543-585)
-    int nIni = (int)roundf((float)I.W / (float)I.H);
-    if (nIni < 1) nIni = 1;
-    if (nIni > 32) nIni = 32;
+    const int nIni = qt_n_roots(I.W, I.H);            // never clamped from above: make_layout sizes pool, lists and pcnt for the level's roots
     const float hX = (float)I.W / nIni;
     if (nIni == 1) {
         if (N <= 1)                                  // (with a quota above one the pre-sort below writes the keys)

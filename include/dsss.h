@@ -131,7 +131,13 @@ int dsss_frame_set(dsss_ctx*, int id, const double* raw, int N, int M,
 int dsss_frames_set(dsss_ctx*, int n, const int* ids, const double* const* raw, const int* N, const int* M,
                     const double* const* pose6, const double* const* alt, const double* const* grange);
 /* GetNormalizeSSS + GetFilteredMask + DetectFeature (frame.cpp:57-124,167-203) with the ORB descriptor
- * configuration of thirdparty/ORBextractor.cpp (operator() :1049-1113).  Features stay on the device.       */
+ * configuration of thirdparty/ORBextractor.cpp (operator() :1049-1113).  Features stay on the device.
+ * Accepted geometries: N, M below 65536, N M below 2^31, every pyramid level at least 69 px each way (DSSS_E_ARG otherwise).  The
+ * quadtree of a level starts with max(1, round(W / H)) nodes for a FAST range of W x H, as the reference has it, whatever that
+ * number is (a frame of 69 pings has one per 37 bins); no level is culled by another tree for its width.  The first pass divides every
+ * root whatever the quota is, so a level of R roots can keep 4 R keypoints: a frame for which the sum over its levels of
+ * max(quota + 3, 4 R) exceeds the keypoint store of the ORB parameters in force, ((nfeatures + 3 nlevels + 63) / 64 + 1) 64, is
+ * refused with DSSS_E_ARG (raise nfeatures).                                                                                          */
 int dsss_extract(dsss_ctx*, int id, int* n_kp_host);
 int dsss_extract_many(dsss_ctx*, const int* ids, int n);      /* same, pipelined over frames */
 /* stage taps for parity tests (host outputs; any may be NULL) */
