@@ -7,6 +7,7 @@
 #include "dsss_internal.h"
 #include "dsss_quadtree.h"
 #include "dsss_extract.h"
+#include "dsss_wave.h"
 #include <algorithm>
 #include <map>
 #include <memory>
@@ -27,10 +28,7 @@ int dsss_quadtree_cull(const float* xs, const float* ys, const float* resp, int 
 // butterfly) so that 2.5*mean is reproducible bit for bit.  One wave per ping, 16-byte loads.
 __device__ inline double wave_fixed_sum_tail(double p0, double p1)
 {
-    double v = p0 + p1;
-#pragma unroll
-    for (int k = 32; k >= 1; k >>= 1) v = v + __shfl_xor(v, k, 64);
-    return v;
+    return dsss_wave_sum(p0 + p1);
 }
 
 // (a borrowed device image is only known to be 8-byte aligned, and with it every row of its even number of bins: the pair load says so,
@@ -434,22 +432,6 @@ __device__ inline uint32_t fast_arc4(const uint8_t* __restrict__ w, int xg, int 
     return out;
 }
 
-__device__ inline int block_scan_excl256(int v, int* total, int* s_w)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(inc, o, 64); if (lane >= o) inc += t; }
-    __syncthreads();
-    if (lane == 63) s_w[w] = inc;
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { const int t = s_w[k]; if (k < w) base += t; tot += t; }
-    *total = tot;
-    return base + inc - v;
-}
-
 // ONE WAVEFRONT per cell window (ORBextractor.cpp:789-816), four cells per workgroup: FAST at iniThFAST, retried at
 // minThFAST if the cell is empty, non-max suppression inside the window only, keypoints emitted row-major.  The wavefront
 // owns a slice of LDS (window + arc values) and nothing of it is shared, so there is no workgroup barrier and no block scan:
@@ -607,7 +589,7 @@ __global__ __launch_bounds__(256) void scan_counts_kernel(const ex_frame* __rest
         const int i = c0 + threadIdx.x;
         const int v = i < n ? counts[i] : 0;
         int tot;
-        const int p = block_scan_excl256(v, &tot, s_w);
+        const int p = dsss_block_scan_excl<4, int>(v, &tot, s_w);
         if (i < n) offs[i] = base + p;
         base += tot;
     }
@@ -741,8 +723,7 @@ __global__ __launch_bounds__(256) void orient_desc_kernel(const ex_frame* __rest
             m10 = (int)__builtin_amdgcn_udot4(pix, c_ic.wu[t], (unsigned)m10, false);
             msum += (int)rs; m01 += (ri - HALF_PATCH) * (int)rs;
         }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) { m10 += __shfl_xor(m10, o, 64); m01 += __shfl_xor(m01, o, 64); msum += __shfl_xor(msum, o, 64); }
+    m10 = dsss_wave_sum(m10); m01 = dsss_wave_sum(m01); msum = dsss_wave_sum(msum);
     m10 -= HALF_PATCH * msum;
     const float angle = fast_atan2_dev((float)m01, (float)m10);
     // separable 13-tap blur, 8.8 fixed point (taps: oracle/orc_orb.c:orc_gauss13_taps).  The taps go through the packed dot products: a lane
@@ -834,7 +815,7 @@ __global__ __launch_bounds__(256) void mask_filter_kernel(const ex_frame* __rest
         dsss_kp kp; bool keep = false;
         if (i < n) { kp = kin[i]; keep = mask[(size_t)(int)kp.y * M + (int)kp.x] != 0; }
         int tot;
-        const int pos = block_scan_excl256(keep, &tot, s_w);
+        const int pos = dsss_block_scan_excl<4, int>(keep, &tot, s_w);
         if (keep) {
             const int o = base + pos;
             kout[o] = kp;

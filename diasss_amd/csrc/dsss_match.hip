@@ -4,6 +4,7 @@
 // ConsistentCheck (:323-405) + RobustMatching rows (:35-45) + Optimizer::GetKpsPairs (optimizer.cpp:575-639)
 // as ordered block compactions.  Integer results are bit-exact against oracle/orc_match.c.
 #include "dsss_internal.h"
+#include "dsss_wave.h"
 #include <type_traits>
 
 #define MT_TILE 256          // threads per block = keypoints of A per block = B entries per LDS tile
@@ -162,7 +163,6 @@ __global__ __launch_bounds__(MTG_THREADS) void mt_grid_build_kernel(
     int* __restrict__ start_all, int* __restrict__ cur_all, double2* __restrict__ s_geo, uint4* __restrict__ s_desc, int* __restrict__ s_idx)
 {
     __shared__ int s_w[MTG_THREADS / 64];
-    __shared__ int s_base;
     const int f = frames[blockIdx.x];
     const mt_grid T = tab[f];
     const int n = nkp[f], cells = T.W * T.H;
@@ -170,29 +170,22 @@ __global__ __launch_bounds__(MTG_THREADS) void mt_grid_build_kernel(
     const double ox = bbox[f * 4 + 0], oy = bbox[f * 4 + 2];
     const double2* __restrict__ g = reinterpret_cast<const double2*>(geo) + (size_t)f * kcap;
     for (int i = threadIdx.x; i <= cells; i += MTG_THREADS) cur[i] = 0;
-    if (threadIdx.x == 0) s_base = 0;
     __syncthreads();
     for (int i = threadIdx.x; i < n; i += MTG_THREADS) {
         const double2 p = g[i];
         atomicAdd(&cur[mt_cell(p.y, oy, inv_cs, T.H) * T.W + mt_cell(p.x, ox, inv_cs, T.W)], 1);
     }
     __syncthreads();
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    int run = 0;
     for (int c0 = 0; c0 < cells; c0 += MTG_THREADS) {
         const int i = c0 + threadIdx.x;
         const int v = i < cells ? __hip_atomic_load(&cur[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;      // (counted by atomics at L2: not through this CU's vector cache)
-        int inc = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(inc, o, 64); if (lane >= o) inc += t; }
-        if (lane == 63) s_w[wv] = inc;
-        __syncthreads();
-        int base = s_base;
-        for (int k = 0; k < wv; ++k) base += s_w[k];
-        if (i < cells) { start[i] = base + inc - v; cur[i] = base + inc - v; }
-        __syncthreads();
-        if (threadIdx.x == MTG_THREADS - 1) s_base = base + inc;
-        __syncthreads();
+        int tot;
+        const int pos = run + dsss_block_scan_excl<MTG_THREADS / 64, int>(v, &tot, s_w);
+        if (i < cells) { start[i] = pos; cur[i] = pos; }
+        run += tot;
     }
+    __syncthreads();                                 // (every cur[] is in place before another thread's atomic moves it)
     if (threadIdx.x == 0) start[cells] = n;
     const uint4* __restrict__ d = reinterpret_cast<const uint4*>(desc + (size_t)f * kcap * 32);
     const size_t ob = (size_t)f * kcap;
@@ -357,23 +350,6 @@ __global__ __launch_bounds__(MT_TILE) void mt_grid_count_kernel(
     if (threadIdx.x == 0 && s_tot) atomicAdd(n_evals, s_tot);
 }
 
-// ------------------------------------------------------------------ block scan helper (256 threads = 4 waves)
-__device__ inline int block_scan_excl(int v, int* total, int* s_w)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { int t = __shfl_up(inc, o, 64); if (lane >= o) inc += t; }
-    __syncthreads();                     // protect s_w from the previous call
-    if (lane == 63) s_w[w] = inc;
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { int t = s_w[k]; if (k < w) base += t; tot += t; }
-    *total = tot;
-    return base + inc - v;
-}
-
 // ------------------------------------------------------------------ K10: SCC_x (FEAmatcher.cpp:186-248)
 // one block per directed active pair; hypotheses are independent given the fixed cv::RNG stream (the reference
 // default-constructs the generator on every call, :59), so each lane evaluates whole hypotheses and the
@@ -408,7 +384,7 @@ __global__ __launch_bounds__(256) void scc_kernel(
         const int i = c0 + threadIdx.x;
         const int m = (i < na) ? nn[i] : -1;
         int tot;
-        const int pos = block_scan_excl(m != -1, &tot, s_w);
+        const int pos = dsss_block_scan_excl<4, int>(m != -1, &tot, s_w);
         if (m != -1) {
             const float ya = ka[i].y, yb = kb[m].y;
             id_loc[base + pos] = i;
@@ -515,7 +491,7 @@ __global__ __launch_bounds__(256) void pair_rows_kernel(
             }
             const bool valid = src >= 0;
             int tot;
-            const int pos = block_scan_excl(valid, &tot, s_w);
+            const int pos = dsss_block_scan_excl<4, int>(valid, &tot, s_w);
             double ys = 0, xs = 0, yt = 0, xt = 0;
             if (valid) {
                 ys = (double)ks[src].y; xs = (double)ks[src].x; yt = (double)kt[tgt].y; xt = (double)kt[tgt].x;
@@ -532,14 +508,14 @@ __global__ __launch_bounds__(256) void pair_rows_kernel(
                 v7 = !(abs(bs - ngr_s) < 20 || abs(bt - ngr_t) < 20);
             }
             int tot7;
-            const int pos7 = block_scan_excl(v7, &tot7, s_w);
+            const int pos7 = dsss_block_scan_excl<4, int>(v7, &tot7, s_w);
             // sticky yaw compensation flags of LoopClosingTFs (optimizer.cpp:650,698-703): prefix OR in list order
             const double thr = 2 * DSSS_PI_REF / 3;
             const int fs_here = v7 && fabs(pose_s[(size_t)ps * 6 + 2]) > thr;
             const int ft_here = v7 && fabs(pose_t[(size_t)pt * 6 + 2]) > thr;
             int tfs, tft;
-            const int pre_s = block_scan_excl(fs_here, &tfs, s_w) + fs_here;
-            const int pre_t = block_scan_excl(ft_here, &tft, s_w) + ft_here;
+            const int pre_s = dsss_block_scan_excl<4, int>(fs_here, &tfs, s_w) + fs_here;
+            const int pre_t = dsss_block_scan_excl<4, int>(ft_here, &tft, s_w) + ft_here;
             if (WRITE && v7) {
                 const size_t o = (size_t)(ko + kbase + pos7);
                 int gis = abs(bs - ngr_s), git = abs(bt - ngr_t);
@@ -566,8 +542,8 @@ __global__ void scan2_kernel(const int* __restrict__ a, const int* __restrict__ 
         const int i = c0 + threadIdx.x;
         const int va = i < n ? a[i] : 0, vb = i < n ? b[i] : 0;
         int ta, tb;
-        const int pa = block_scan_excl(va, &ta, s_w);
-        const int pb = block_scan_excl(vb, &tb, s_w);
+        const int pa = dsss_block_scan_excl<4, int>(va, &ta, s_w);
+        const int pb = dsss_block_scan_excl<4, int>(vb, &tb, s_w);
         if (i < n) { oa[i] = ba + pa; ob[i] = bb + pb; }
         ba += ta; bb += tb;
     }

@@ -904,47 +904,7 @@ __global__ __launch_bounds__(256) void lc_edge_flag_kernel(const unsigned long l
     }
     flags[g] = f;
 }
-// edges in ascending target pose id (the reference's loop order), ordered compaction over blocks of 4096 poses
-__global__ __launch_bounds__(256) void lc_edge_compact_kernel(const int* __restrict__ flags, const int* __restrict__ bsum, const unsigned long long* __restrict__ slot,
-                                                              int total, const int* __restrict__ kp7_off, const double* __restrict__ kp7,
-                                                              const dsss_lc* __restrict__ lcs, const int* __restrict__ act_s, const int* __restrict__ frame_off,
-                                                              int cap, dsss_lc_edge* __restrict__ edges, int2* __restrict__ ab)
-{
-    __shared__ int s_w[4];
-    __shared__ int s_run;
-    const int i0 = blockIdx.x * 4096;
-    if (threadIdx.x == 0) s_run = bsum[blockIdx.x];
-    __syncthreads();
-    for (int c0 = 0; c0 < 4096; c0 += 256) {
-        const int g = i0 + c0 + threadIdx.x;
-        const int f = g < total ? flags[g] : 0;
-        const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-        int inc = f;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(inc, o, 64); if (lane >= o) inc += t; }
-        __syncthreads();
-        if (lane == 63) s_w[w] = inc;
-        __syncthreads();
-        int base = s_run;
-        for (int k = 0; k < w; ++k) base += s_w[k];
-        const int pos = base + inc - f;
-        if (f && pos < cap) {
-            const unsigned long long key = slot[g];
-            const int p = (int)(key >> 32) - 1, k = (int)(0xffffffffu - (unsigned)(key & 0xffffffffu));
-            const int i = kp7_off[p] + k;
-            dsss_lc_edge ed;
-            ed.a = frame_off[act_s[p]] + (int)kp7[(size_t)i * 7 + 0];
-            ed.b = g;
-            for (int q = 0; q < 12; ++q) ed.rel[q] = lcs[i].rel[q];
-            for (int q = 0; q < 6; ++q) ed.var[q] = lcs[i].var[q];
-            edges[pos] = ed;
-            if (ab) ab[pos] = make_int2(ed.a, ed.b);
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) s_run += s_w[0] + s_w[1] + s_w[2] + s_w[3];
-        __syncthreads();
-    }
-}
+// (lc_edge_compact_kernel, the ordered compaction behind it, sits beside its twin in dsss_pg_chain.hip)
 
 // ends != NULL (dsss_posegraph_solve, one rank): the END POINTS of the edges also come back as packed (a, b) pairs in the context's
 // page-locked buffer (*ends): the first passes of the solve (separators, partition boundaries, reduced edges) walk 8 bytes per edge

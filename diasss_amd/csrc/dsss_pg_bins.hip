@@ -48,39 +48,24 @@ template <typename T, int VAL>
 __global__ __launch_bounds__(1024) void pg_scan_block_kernel(int n, const int* __restrict__ cnt, const int* __restrict__ colptr, T* __restrict__ out, T* __restrict__ block_sum)
 {
     __shared__ T s_w[16];
-    const int i = blockIdx.x * 1024 + threadIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    T v = 0;
+    const int i = blockIdx.x * 1024 + threadIdx.x;
+    T v = 0, tot;
     if (i < n) v = VAL == 0 ? (T)cnt[i] : (T)cnt[i] * (T)(colptr[i + 1] - colptr[i]);
-    T inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const T t = __shfl_up(inc, o, 64); if (lane >= o) inc += t; }
-    if (lane == 63) s_w[w] = inc;
-    __syncthreads();
-    T base = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) { const T t = s_w[k]; if (k < w) base += t; tot += t; }
-    if (i < n) out[i] = base + inc - v;
+    const T pos = dsss_block_scan_excl<16, T>(v, &tot, s_w);
+    if (i < n) out[i] = pos;
     if (threadIdx.x == 0) block_sum[blockIdx.x] = tot;
 }
 template <typename T>
 __global__ __launch_bounds__(1024) void pg_scan_tops_kernel(int nblocks, T* __restrict__ block_sum, T* __restrict__ total)
 {
     __shared__ T s_w[16];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     T carry = 0;
     for (int b0 = 0; b0 < nblocks; b0 += 1024) {
         const int i = b0 + threadIdx.x;
         const T v = i < nblocks ? block_sum[i] : (T)0;
-        T inc = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const T t = __shfl_up(inc, o, 64); if (lane >= o) inc += t; }
-        __syncthreads();
-        if (lane == 63) s_w[w] = inc;
-        __syncthreads();
-        T base = 0, tot = 0;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) { const T t = s_w[k]; if (k < w) base += t; tot += t; }
-        if (i < nblocks) block_sum[i] = carry + base + inc - v;
+        T tot;
+        const T pos = dsss_block_scan_excl<16, T>(v, &tot, s_w);
+        if (i < nblocks) block_sum[i] = carry + pos;
         carry += tot;
     }
     if (threadIdx.x == 0) *total = carry;
@@ -387,9 +372,8 @@ __global__ __launch_bounds__(64) void pg_bwd_subtree_kernel(const int* __restric
             const double* B = Lvals + (size_t)p * 36; const double* xi = x + (size_t)rowidx[p] * 6;
             for (int a = 0; a < 6; ++a) { double s = 0; for (int b = 0; b < 6; ++b) s += B[b * 6 + a] * xi[b]; acc[a] += s; }
         }
-        for (int a = 0; a < 6; ++a)
 #pragma unroll
-            for (int o = 32; o >= 1; o >>= 1) acc[a] += __shfl_xor(acc[a], o, 64);
+        for (int a = 0; a < 6; ++a) acc[a] = dsss_wave_sum(acc[a]);
         if (lane == 0) {
             double v[6], xj[6];
 #pragma unroll

@@ -713,8 +713,7 @@ __global__ __launch_bounds__(256) void pg_flag_blocksum_kernel(const int* __rest
     const long long i0 = (long long)blockIdx.x * 4096;
     int acc = 0;
     for (int k = threadIdx.x; k < 4096; k += 256) if (i0 + k < n) acc += flags[i0 + k];
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    acc = dsss_wave_sum(acc);
     if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (threadIdx.x == 0) bsum[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
@@ -723,32 +722,49 @@ __global__ __launch_bounds__(256) void pg_flag_scan_kernel(int* __restrict__ bsu
 {
     if (threadIdx.x == 0) { int run = 0; for (int i = 0; i < nb; ++i) { const int v = bsum[i]; bsum[i] = run; run += v; } *total = run; }
 }
-__global__ __launch_bounds__(256) void pg_flag_compact_kernel(const int* __restrict__ flags, const double* __restrict__ pairs, long long n,
-                                                              const int* __restrict__ bsum, long long need_pairs, double* __restrict__ normals)
+// the compaction of one block of 4096 flags, shared by the two kernels below: store(i, pos) for every set flag i, pos = its rank among
+// the set flags of the whole list (bsum[] holds the ranks at the block starts).  The rank so far is carried in a register.
+template <typename STORE>
+__device__ inline void pg_compact_block(const int* __restrict__ flags, long long n, const int* __restrict__ bsum, STORE store)
 {
     __shared__ int s_w[4];
-    __shared__ int s_run;
     const long long i0 = (long long)blockIdx.x * 4096;
-    if (threadIdx.x == 0) s_run = bsum[blockIdx.x];
-    __syncthreads();
+    int run = bsum[blockIdx.x];
     for (int c = 0; c < 4096; c += 256) {
         const long long i = i0 + c + threadIdx.x;
         const int f = (i < n) ? flags[i] : 0;
-        const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-        int inc = f;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(inc, o, 64); if (lane >= o) inc += t; }
-        __syncthreads();
-        if (lane == 63) s_w[w] = inc;
-        __syncthreads();
-        int base = s_run;
-        for (int k = 0; k < w; ++k) base += s_w[k];
-        const long long pos = (long long)base + inc - f;
-        if (f && pos < need_pairs) { normals[2 * pos] = pairs[2 * i]; normals[2 * pos + 1] = pairs[2 * i + 1]; }
-        __syncthreads();
-        if (threadIdx.x == 0) s_run += s_w[0] + s_w[1] + s_w[2] + s_w[3];
-        __syncthreads();
+        int tot;
+        const int pos = run + dsss_block_scan_excl<4, int>(f, &tot, s_w);
+        if (f) store(i, pos);
+        run += tot;
     }
+}
+__global__ __launch_bounds__(256) void pg_flag_compact_kernel(const int* __restrict__ flags, const double* __restrict__ pairs, long long n,
+                                                              const int* __restrict__ bsum, long long need_pairs, double* __restrict__ normals)
+{
+    pg_compact_block(flags, n, bsum, [&](long long i, int pos) {
+        if (pos < need_pairs) { normals[2 * (size_t)pos] = pairs[2 * i]; normals[2 * (size_t)pos + 1] = pairs[2 * i + 1]; }
+    });
+}
+// edges in ascending target pose id (the reference's loop order), ordered compaction over blocks of 4096 poses
+__global__ __launch_bounds__(256) void lc_edge_compact_kernel(const int* __restrict__ flags, const int* __restrict__ bsum, const unsigned long long* __restrict__ slot,
+                                                              int total, const int* __restrict__ kp7_off, const double* __restrict__ kp7,
+                                                              const dsss_lc* __restrict__ lcs, const int* __restrict__ act_s, const int* __restrict__ frame_off,
+                                                              int cap, dsss_lc_edge* __restrict__ edges, int2* __restrict__ ab)
+{
+    pg_compact_block(flags, total, bsum, [&](long long g, int pos) {
+        if (pos >= cap) return;
+        const unsigned long long key = slot[g];
+        const int p = (int)(key >> 32) - 1, k = (int)(0xffffffffu - (unsigned)(key & 0xffffffffu));
+        const int i = kp7_off[p] + k;
+        dsss_lc_edge ed;
+        ed.a = frame_off[act_s[p]] + (int)kp7[(size_t)i * 7 + 0];
+        ed.b = (int)g;
+        for (int q = 0; q < 12; ++q) ed.rel[q] = lcs[i].rel[q];
+        for (int q = 0; q < 6; ++q) ed.var[q] = lcs[i].var[q];
+        edges[pos] = ed;
+        if (ab) ab[pos] = make_int2(ed.a, ed.b);
+    });
 }
 // DR rows of the frames (device copies kept by dsss_frame_set) into one array, frame after frame
 __global__ __launch_bounds__(256) void pg_gather_dr_kernel(const unsigned long long* __restrict__ fptr, const int* __restrict__ foff, double* __restrict__ out)

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "dsss_pg_kernels.h"
+#include "dsss_wave.h"
 
 // ------------------------------------------------------------------ small dense helpers (6x6 row-major)
 // 6 x 6 Cholesky with the reciprocal of a correctly rounded square root (one sqrt and one division per pivot), ri[j] = 1 / L[j][j]: for the bins, whose 17 k columns
@@ -107,8 +108,7 @@ __device__ __forceinline__ void factor_eval(int k, int n, const pose_t* X, const
 // deterministic block sum: wave shuffle tree then the 4 wave sums in order
 __device__ inline double block_sum256(double v, double* s_w)
 {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    v = dsss_wave_sum(v);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
     __syncthreads();

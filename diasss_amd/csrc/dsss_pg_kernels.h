@@ -53,6 +53,8 @@ __global__ void pg_rng_attempts_kernel(long long nattempts, double* __restrict__
 __global__ void pg_flag_blocksum_kernel(const int* __restrict__ flags, long long n, int* __restrict__ bsum);
 __global__ void pg_flag_scan_kernel(int* __restrict__ bsum, int nb, int* __restrict__ total);
 __global__ void pg_flag_compact_kernel(const int* __restrict__ flags, const double* __restrict__ pairs, long long n, const int* __restrict__ bsum, long long need_pairs, double* __restrict__ normals);
+__global__ void lc_edge_compact_kernel(const int* __restrict__ flags, const int* __restrict__ bsum, const unsigned long long* __restrict__ slot, int total, const int* __restrict__ kp7_off, const double* __restrict__ kp7,
+                                       const dsss_lc* __restrict__ lcs, const int* __restrict__ act_s, const int* __restrict__ frame_off, int cap, dsss_lc_edge* __restrict__ edges, int2* __restrict__ ab);
 __global__ void pg_gather_dr_kernel(const unsigned long long* __restrict__ fptr, const int* __restrict__ foff, double* __restrict__ out);
 __global__ void pg_gather_pose_kernel(int n, const int* __restrict__ idx, const pose_t* __restrict__ X, pose_t* __restrict__ out);
 __global__ void pg_sep_xy_kernel(int ns, const int* __restrict__ sep_pose, const double* __restrict__ dr6, double* __restrict__ xy);

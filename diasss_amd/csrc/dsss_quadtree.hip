@@ -14,6 +14,7 @@
 // Output: the kept candidate of every node (first maximum response in key order), in list order.
 #include "dsss_internal.h"
 #include "dsss_quadtree.h"
+#include "dsss_wave.h"
 
 struct qnode { int x0, y0, x1, y1; int kbeg, kcnt; int buf; int leaf; };   // 32 B
 
@@ -23,22 +24,6 @@ struct qnode { int x0, y0, x1, y1; int kbeg, kcnt; int buf; int leaf; };   // 32
 #define QT_THREADS 1024
 #define QT_WAVES (QT_THREADS / 64)
 #define QT_RANK_CAP 4096                           // expandable nodes whose (size, id) pairs fit the LDS staging of the rank pass
-__device__ inline int qt_block_scan(int v, int* total, int* s_w)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(inc, o, 64); if (lane >= o) inc += t; }
-    __syncthreads();
-    if (lane == 63) s_w[w] = inc;
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < QT_WAVES; ++k) { const int t = s_w[k]; if (k < w) base += t; tot += t; }
-    *total = tot;
-    return base + inc - v;
-}
-
 // ExtractorNode::DivideNode (:481-537): stable 4-way partition of a node's key segment from its buffer into the other
 // one; cnt[0..3] = keys of n1..n4 (top-left, top-right, bottom-left, bottom-right).  The key -> coordinate loads are
 // streamed with QT_ILP chunks of 64 keys in flight per wave: a pass over the level costs (keys / (1024 x QT_ILP)) round trips.
@@ -278,7 +263,7 @@ __global__ __launch_bounds__(QT_THREADS) void quadtree_kernel(const qt_inst* __r
 #pragma unroll
             for (int u = 0; u < 4; ++u) { v[u] = b0 + u < nb ? s_off[b0 + u] : 0; sum += v[u]; }
             int tot;
-            int run = qt_block_scan(sum, &tot, s_w);
+            int run = dsss_block_scan_excl<QT_WAVES, int>(sum, &tot, s_w);
             __syncthreads();
 #pragma unroll
             for (int u = 0; u < 4; ++u) if (b0 + u < nb) { s_off[b0 + u] = run; run += v[u]; }
@@ -320,7 +305,7 @@ __global__ __launch_bounds__(QT_THREADS) void quadtree_kernel(const qt_inst* __r
             const int id = i < S ? L[i] : -1;
             const int isp = (id >= 0 && !(pool[id].leaf & 1)) ? 1 : 0, isl = (id >= 0 && (pool[id].leaf & 1)) ? 1 : 0;
             int tp, tl;
-            const int rp = qt_block_scan(isp, &tp, s_w), rl = qt_block_scan(isl, &tl, s_w);
+            const int rp = dsss_block_scan_excl<QT_WAVES, int>(isp, &tp, s_w), rl = dsss_block_scan_excl<QT_WAVES, int>(isl, &tl, s_w);
             if (isp) parents[np + rp] = id;
             if (isl) flags[nl + rl] = id;            // flags[] doubles as the leaf list here
             np += tp; nl += tl;
@@ -360,7 +345,7 @@ __global__ __launch_bounds__(QT_THREADS) void quadtree_kernel(const qt_inst* __r
             int ne = 0, nx = 0, cnt[4] = { 0, 0, 0, 0 };
             if (r < np) for (int c = 0; c < 4; ++c) { cnt[c] = pcnt[4 * r + c]; ne += cnt[c] > 0; nx += cnt[c] > 1; }
             int te, tx;
-            const int qe = qt_block_scan(ne, &te, s_w), qx = qt_block_scan(nx, &tx, s_w);
+            const int qe = dsss_block_scan_excl<QT_WAVES, int>(ne, &te, s_w), qx = dsss_block_scan_excl<QT_WAVES, int>(nx, &tx, s_w);
             if (r < np) {
                 const qnode P = pool[parents[r]];
                 int q = Cn + qe, x = nexp + qx;
@@ -445,7 +430,7 @@ __global__ __launch_bounds__(QT_THREADS) void quadtree_kernel(const qt_inst* __r
             int d = 0;
             if (r < m) { for (int c = 0; c < 4; ++c) d += pcnt[4 * r + c] > 0; d -= 1; }
             int td;
-            const int ex = qt_block_scan(d, &td, s_w);
+            const int ex = dsss_block_scan_excl<QT_WAVES, int>(d, &td, s_w);
             if (r < m && run + ex + d >= N) atomicMin(&s_t, r);
             run += td;
             __syncthreads();
@@ -458,7 +443,7 @@ __global__ __launch_bounds__(QT_THREADS) void quadtree_kernel(const qt_inst* __r
             int ne = 0, nx = 0, cnt[4] = { 0, 0, 0, 0 };
             if (r <= t) for (int c = 0; c < 4; ++c) { cnt[c] = pcnt[4 * r + c]; ne += cnt[c] > 0; nx += cnt[c] > 1; }
             int te, tx;
-            const int qe = qt_block_scan(ne, &te, s_w), qx = qt_block_scan(nx, &tx, s_w);
+            const int qe = dsss_block_scan_excl<QT_WAVES, int>(ne, &te, s_w), qx = dsss_block_scan_excl<QT_WAVES, int>(nx, &tx, s_w);
             if (r <= t) {
                 const qnode P = pool[order[r]];
                 int q = Cn + qe, x = nexp + qx;
@@ -479,7 +464,7 @@ __global__ __launch_bounds__(QT_THREADS) void quadtree_kernel(const qt_inst* __r
             const int id = i < S ? L[i] : -1;
             const int keep = (id >= 0 && pool[id].kcnt >= 0) ? 1 : 0;
             int tk;
-            const int rk = qt_block_scan(keep, &tk, s_w);
+            const int rk = dsss_block_scan_excl<QT_WAVES, int>(keep, &tk, s_w);
             if (keep) { if (Cn + kept + rk < cap) Ln[Cn + kept + rk] = id; }
             kept += tk;
         }

@@ -17,6 +17,7 @@
 // Measured at C3 (400 k keypoints): 13.4 ms (byte loads, scalar blur taps, divergent sample loop) -> 7.3 (dword loads, dot-product blur,
 // compaction) -> 5.9 ms (lanes spread over the list); what is left is the 8 LDS atomics per live sample (12.8 k per keypoint).
 #include "dsss_extract.h"
+#include "dsss_wave.h"
 
 #define SRAD 28                // window radius: cvRound(8 sqrt 2 (4 + 1) / 2)
 #define SW 57                  // samples per side
@@ -191,9 +192,7 @@ __global__ __launch_bounds__(256) void sift_desc_kernel(const ex_frame* __restri
         if (o < 2) h += sHist[idx + 8 + o];
     }
     if (dbg && tid < 128) dbg[((size_t)blockIdx.y * dbg_kcap + k) * 128 + tid] = (int)h;
-    unsigned long long s = (unsigned long long)(h * h);
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
+    const unsigned long long s = dsss_wave_sum((unsigned long long)(h * h));
     if ((tid & 63) == 0) sSum[tid >> 6] = s;
     __syncthreads();
     const unsigned long long s_all = sSum[0] + sSum[1];
@@ -201,9 +200,7 @@ __global__ __launch_bounds__(256) void sift_desc_kernel(const ex_frame* __restri
     const long long thr = (long long)(nrm * 0.2);
     const long long v = h < thr ? h : thr;
     __syncthreads();
-    unsigned long long s2 = tid < 128 ? (unsigned long long)(v * v) : 0ull;
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) s2 += __shfl_xor(s2, o, 64);
+    const unsigned long long s2 = dsss_wave_sum(tid < 128 ? (unsigned long long)(v * v) : 0ull);
     if ((tid & 63) == 0) sSum[tid >> 6] = s2;
     __syncthreads();
     double den = sqrt((double)(sSum[0] + sSum[1]));

@@ -225,6 +225,53 @@ def lc_cases(orc, seed=0):
     return G
 
 
+LC_SEAM_N = 1400
+LC_SEAM_RESIDUES = (0, 63, 64, 255)
+LC_SEAM_POSES = (4095, 4096, 4097, 4199)
+
+
+def lc_seam_case(orc):
+    """Loop closures whose target poses sit on the seams of the ordered compaction behind dsss_posegraph_select (blocks of 4096 poses scanned
+    in chunks of 256 by wavefronts of 64).  Three frames track(1400, LC_M, leg, seed=9): 4 200 pings, more than one block and no multiple of
+    256.  Wanted are the global poses g >= 1400 with g mod 256 in LC_SEAM_RESIDUES, plus LC_SEAM_POSES; every pair (0,1), (0,2), (1,2) whose
+    target frame holds a wanted pose gets two rows for it, built like `shifted` of lc_cases: the source point whose image 0.5 m further
+    along the track is nearest to a point of the wanted target ping, within 0.05 m (such a row scores above 0 and becomes an edge).
+    Returns dict(frames, lists, wanted, lcs, edges): lcs and edges are the oracle's (orc_lc_solve per list, orc_pg_select_lc)."""
+    if "seam" in _LC_CACHE:
+        return _LC_CACHE["seam"]
+    N, M = LC_SEAM_N, LC_M
+    frames = [track(N, M, leg, seed=9) for leg in range(3)]
+    geo = [_Geo(orc, f) for f in frames]
+    wanted = sorted({g for g in range(N, 3 * N) if g % 256 in LC_SEAM_RESIDUES} | set(LC_SEAM_POSES))
+    rng = np.random.default_rng(5)
+    lists = []
+    for s, t in ((0, 1), (0, 2), (1, 2)):
+        gs, gt = geo[s], geo[t]
+        rows = []
+        for g in wanted:
+            if g // N != t:
+                continue
+            pt, found = g - t * N, 0
+            for _ in range(200):
+                bt = int(rng.choice(gt.cols))                       # a point of the wanted ping, and the source point that lands on it
+                _, p, b = gs.nearest(gt.gx[pt, bt] - 0.5, gt.gy[pt, bt])
+                d, pt2, bt2 = gt.nearest(gs.gx[p[0], b[0]] + 0.5, gs.gy[p[0], b[0]])
+                if d[0] <= 0.05 and int(pt2[0]) == pt:
+                    rows.append(_row(frames[s], frames[t], int(p[0]), int(b[0]), pt, int(bt2[0])))
+                    found += 1
+                    if found == 2:
+                        break
+            assert found == 2, (s, t, g)
+        lists.append((s, t, np.array(rows)))
+    lcs = [orc.lc_solve(k, *frames[s], M, *frames[t], M) for s, t, k in lists]
+    off = np.cumsum([0] + [len(l[2]) for l in lists])
+    edges = orc.pg_select_lc([N] * 3, [l[0] for l in lists], [l[1] for l in lists], off, np.concatenate([l[2] for l in lists]), np.concatenate(lcs))
+    for a in [x for f in frames for x in f] + [l[2] for l in lists] + lcs + [edges]:
+        a.setflags(write=False)
+    _LC_CACHE["seam"] = dict(frames=frames, lists=lists, wanted=wanted, lcs=lcs, edges=edges)
+    return _LC_CACHE["seam"]
+
+
 def _spread(stack):
     """largest difference among the runs, element-wise (NaN where every run is NaN counts as 0)"""
     with np.errstate(all="ignore"):

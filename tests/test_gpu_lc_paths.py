@@ -10,7 +10,7 @@ the largest deviation it saw next to the largest it would have allowed."""
 import numpy as np
 import pytest
 
-from tests.helpers import LC_M, LC_N, _nonfinite_code, _spread, lc_cases, lc_reference, tri_reference
+from tests.helpers import LC_M, LC_N, LC_SEAM_N, _nonfinite_code, _spread, lc_cases, lc_reference, lc_seam_case, tri_reference
 
 pytestmark = pytest.mark.gpu
 
@@ -218,6 +218,34 @@ def test_selection_and_solve_after_bad_rows(ctx, orc, cases):
     g_out, _, g_stats = ctx.posegraph_solve(3, 3 * LC_N, want_rpy=False)
     assert g_stats[0] == o_stats[0]
     assert np.abs(g_out - o_out).max() < 1e-6
+
+
+def test_selection_at_the_scan_seams(orc):
+    """helpers.lc_seam_case (its preconditions: tests/test_lc_paths_cpu.py): 4 200 poses, edges at the first and last thread of a scan chunk,
+    on both sides of a wavefront boundary, around the block seam 4096 and at the last pose.  The selection gives the oracle's edges in the
+    oracle's order; a buffer of exactly that many edges takes the same list; one edge less is DSSS_E_CAPACITY, after which the context
+    repeats the full call with the same bits.  Own context: the frames are longer than the module's."""
+    from diasss_amd import capi
+    E_CAPACITY = -5
+    g = lc_seam_case(orc)
+    o_edges = g["edges"]; ne = len(o_edges)
+    c = capi.Context(max_frames=4)
+    try:
+        for f, (pose, alt, gr) in enumerate(g["frames"]):
+            c.frame_set(f, None, LC_SEAM_N, LC_M, pose, alt, gr)
+        c.lc_solve_pairs([l[0] for l in g["lists"]], [l[1] for l in g["lists"]], [l[2] for l in g["lists"]])
+        g_edges = c.posegraph_select(3)
+        assert len(g_edges) == ne
+        assert (g_edges["a"] == o_edges["a"]).all() and (g_edges["b"] == o_edges["b"]).all()
+        print("seam selection: %d edges, max |rel - oracle| %.2e" % (ne, np.abs(g_edges["rel"] - o_edges["rel"]).max()))
+        assert np.allclose(g_edges["rel"], o_edges["rel"], rtol=0, atol=1e-9)
+        assert c.posegraph_select(3, cap=ne).tobytes() == g_edges.tobytes()
+        with pytest.raises(capi.DsssError) as ei:
+            c.posegraph_select(3, cap=ne - 1)
+        assert ei.value.code == E_CAPACITY
+        assert c.posegraph_select(3).tobytes() == g_edges.tobytes()
+    finally:
+        c.close()
 
 
 def test_range_check_on_all_entry_points(ctx, orc, cases):

@@ -223,6 +223,65 @@ def test_matcher_geo_grid_corner_cases(ctx, orc, kind, grid, monkeypatch):
     assert (nn >= 0).sum() > 10
 
 
+@pytest.mark.parametrize("WH", [(1, 1), (31, 33), (32, 32), (41, 25), (64, 48), (1, 2049)])
+def test_matcher_geo_grid_chunk_seams(ctx, orc, WH, monkeypatch):
+    """the build of the geo grid (mt_grid_build_kernel: one workgroup scans the cell counts 1 024 cells at a time and carries the running
+    total from chunk to chunk) on boxes of 1, 1 023, 1 024, 1 025, 3 072 and 2 049 cells: one cell, one cell short of a chunk, exactly a
+    chunk, one cell into the second, three whole chunks, and a one-column grid of two chunks and a cell.  The query frame has keypoints
+    in the first and in the last cell of every chunk; the other frame has the same cells but for the last cell before one chunk
+    boundary, which it leaves empty (where there is a boundary).  Explicit geo points and boxes, few distinct descriptors; the grid
+    against the oracle, and the all-pairs kernel (DSSS_MT_GRID=0) against the grid."""
+    from tests import helpers as H
+    W, H_ = WH
+    N, M, r, CHUNK = 700, 480, 8.0, 1024
+    cs = r / 2 * (1.0 + 1.0 / 1048576.0); inv_cs = 1.0 / cs
+    x0, y0 = -20.0, 5.0
+    bb = np.array([x0, x0 + (W - 0.5) * cs, y0, y0 + (H_ - 0.5) * cs])
+    assert int((bb[1] - bb[0]) / cs) + 1 == int((bb[1] - bb[0]) * inv_cs) + 1 == W        # plan_grid's cell counts (it multiplies by 1 / cs)
+    assert int((bb[3] - bb[2]) / cs) + 1 == int((bb[3] - bb[2]) * inv_cs) + 1 == H_
+    cells = W * H_
+    assert cells == {(1, 1): 1, (31, 33): 1023, (32, 32): 1024, (41, 25): 1025, (64, 48): 3072, (1, 2049): 2049}[WH]
+    rng = np.random.default_rng(100 * W + H_)
+    seams = sorted({c for c0 in range(0, cells, CHUNK) for c in (c0, min(c0 + CHUNK, cells) - 1)})
+    others = np.setdiff1d(np.arange(cells), seams)
+    occ_a = np.concatenate([seams, rng.choice(others, min(len(others), 300), replace=False)]).astype(np.int64)
+    hole = CHUNK - 1 if cells > CHUNK else -1                      # the last cell of the first chunk: empty in the base frame, the next cell is not
+    occ_b = occ_a[occ_a != hole]
+
+    def points(occ, per_cell):
+        cell = np.repeat(occ, per_cell)
+        u = rng.uniform(0.1, 0.4, (len(cell), 2))                   # inside the cell, and inside the box in the last column and row too
+        G = np.stack([x0 + (cell % W + u[:, 0]) * cs, y0 + (cell // W + u[:, 1]) * cs], 1)
+        got = ((G[:, 1] - y0) * inv_cs).astype(int) * W + ((G[:, 0] - x0) * inv_cs).astype(int)
+        assert (got == cell).all() and (G[:, 0] <= bb[1]).all() and (G[:, 1] <= bb[3]).all()
+        return G[rng.permutation(len(G))]
+    A, B = (points(occ_a, 3), points(occ_b, 4)) if cells > 1 else (points(occ_a, 300), points(occ_b, 400))
+    assert len(A) <= 2000 and len(B) <= 2000
+    palette = rng.integers(0, 256, (4, 32), dtype=np.uint8)
+    fr = {}
+    for f, G in ((0, A), (2, B)):
+        n = len(G)
+        pose, alt, gr = H.track(N, M, 0, seed=3)
+        kps, _ = H.random_features(N, M, n, 7 + f)
+        desc = palette[rng.integers(0, 4, n)].copy()
+        flip = rng.integers(0, 3, n)
+        for i in range(n):
+            for b in rng.choice(256, flip[i], replace=False):
+                desc[i, b // 8] ^= np.uint8(1 << (b % 8))
+        ctx.frame_set(f, None, N, M, pose, alt, gr)
+        ctx.features_set(f, N, M, kps, desc, geo=G, bbox=bb)
+        fr[f] = dict(N=N, M=M, pose=pose, alt=alt, gr=gr, kps=kps, desc=desc, geo=np.ascontiguousarray(G), bb=bb)
+    monkeypatch.setenv("DSSS_MT_GRID", "1")
+    ctx.match_pairs([0], [2])
+    _check_pair(ctx, orc, 0, 0, 2, fr)
+    nn_grid = [ctx.match_dir(0, d)[0].copy() for d in (0, 1)]
+    assert (nn_grid[0][:len(A)] >= 0).sum() > 10 and (nn_grid[1][:len(B)] >= 0).sum() > 10
+    monkeypatch.setenv("DSSS_MT_GRID", "0")
+    ctx.match_pairs([0], [2])
+    for d in (0, 1):
+        assert (ctx.match_dir(0, d)[0] == nn_grid[d]).all()
+
+
 @pytest.mark.parametrize("radius", [0.004, 0.5, 8.0, 50.0, 1000.0])
 def test_matcher_radius_sweep(ctx, orc, radius):
     """the search radius from far below the keypoint spacing (the geo box would hold more than 2^22 cells: the call falls back to the

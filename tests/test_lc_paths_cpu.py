@@ -4,7 +4,7 @@ take the exits they are built for, and the oracle has to be able to decide them.
 import numpy as np
 import pytest
 
-from tests.helpers import LC_M, lc_cases, lc_reference, tri_reference
+from tests.helpers import LC_M, LC_SEAM_N, LC_SEAM_POSES, LC_SEAM_RESIDUES, lc_cases, lc_reference, lc_seam_case, tri_reference
 
 EXITS = ("rejected", "lammax_exit", "stop_nosuccess", "iter_cap", "chol_fail", "marg_fail")
 
@@ -123,6 +123,26 @@ def test_at_most_a_tenth_of_a_group_is_knife_edge(refs):
             st = np.concatenate([r[what]["stable"] for r in lists])
             print("%-20s %s knife-edge %d of %d" % (name, ("lc", "tri")[what], (~st).sum(), len(st)))
             assert (~st).sum() <= 0.10 * len(st), (name, what)
+
+
+def test_selection_seam_case_reaches_every_seam(orc):
+    """helpers.lc_seam_case on the oracle alone, before the device's ordered compaction is held to it (tests/test_gpu_lc_paths.py): the
+    oracle's selection has an edge whose target pose is the first (g mod 256 = 0) and the last (255) thread of a scan chunk, the last lane
+    of a wavefront and the first of the next (63, 64), and edges at the poses around the block seam 4096 and at the very last pose 4199."""
+    g = lc_seam_case(orc)
+    assert [len(f[0]) for f in g["frames"]] == [LC_SEAM_N] * 3 and 3 * LC_SEAM_N > 4096 and (3 * LC_SEAM_N) % 256 != 0
+    assert [(s, t) for s, t, _ in g["lists"]] == [(0, 1), (0, 2), (1, 2)]
+    for (s, t, k), lcs in zip(g["lists"], g["lcs"]):
+        assert len(k) == len(lcs) == 2 * sum(w // LC_SEAM_N == t for w in g["wanted"])
+    score = np.concatenate([l["score"] for l in g["lcs"]])
+    b = g["edges"]["b"]
+    print("seam case: %d rows, %d with score > 0, %d edges, per residue %s"
+          % (len(score), (score > 0).sum(), len(b), {r: int((b % 256 == r).sum()) for r in LC_SEAM_RESIDUES}))
+    assert (np.diff(b) > 0).all() and set(b.tolist()) <= set(g["wanted"])
+    for r in LC_SEAM_RESIDUES:
+        assert (b % 256 == r).any(), r
+    for p in LC_SEAM_POSES:
+        assert p in b, p
 
 
 def _inv_longdouble(A):
