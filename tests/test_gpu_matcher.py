@@ -176,8 +176,23 @@ def test_matcher_geo_grid_corner_cases(ctx, orc, kind, grid, monkeypatch):
     radius (excluded: strict <) and one ulp inside it, diagonal neighbours either side of it, every keypoint in ONE cell, points on the
     cell borders and on the far edges of the box; few distinct descriptors, so that the minimum is tied all the time (lowest index wins,
     second = best).  Explicit geo points and boxes through dsss_features_set."""
+    _geo_grid_corner_case(ctx, orc, kind, grid, 0, monkeypatch)
+
+
+@pytest.mark.parametrize("kind", ["lattice", "cluster", "cell_edges"])
+@pytest.mark.parametrize("grid", ["1", "0"])
+def test_matcher_geo_grid_corner_cases_l2(ctx, orc, kind, grid, monkeypatch):
+    """the same geometry and descriptors through the L2-on-bytes instantiation (use_l2 = 1), whose fold has the same tie rule on distances that
+    are square roots of integers.  On the oracle the palette of four descriptors gives the L2 rule 407, 84 and 208 accepted matches in
+    direction 1 (Hamming: 398, 46, 160), with best = second on 23, 211 and 1 283 of the keypoints with several candidates: no wider palette
+    is needed for "more than 10 accepted" (asserted on the CPU: test_matcher_tail_cpu.py::test_corner_case_geometry_under_both_descriptor_rules)."""
+    _geo_grid_corner_case(ctx, orc, kind, grid, 1, monkeypatch)
+
+
+def geo_grid_corner_frames(kind):
+    """the two frames (ids 0 and 2) of a corner-case geometry, no device involved: tests/test_matcher_tail_cpu.py holds the oracle's acceptance
+    counts under both descriptor rules on them"""
     from tests import helpers as H
-    monkeypatch.setenv("DSSS_MT_GRID", grid)
     N, M = 700, 480
     rng = np.random.default_rng({"lattice": 1, "cluster": 2, "cell_edges": 3}[kind])
     bb = np.array([-20.0, 100.0, 5.0, 65.0])                    # x0 x1 y0 y1
@@ -214,12 +229,27 @@ def test_matcher_geo_grid_corner_cases(ctx, orc, kind, grid, monkeypatch):
         for i in range(n):
             for b in rng.choice(256, flip[i], replace=False):
                 desc[i, b // 8] ^= np.uint8(1 << (b % 8))
-        ctx.frame_set(f, None, N, M, pose, alt, gr)
-        ctx.features_set(f, N, M, kps, desc, geo=G, bbox=bb)
         fr[f] = dict(N=N, M=M, pose=pose, alt=alt, gr=gr, kps=kps, desc=desc, geo=np.ascontiguousarray(G), bb=bb)
-    ctx.match_pairs([0], [2])
-    _check_pair(ctx, orc, 0, 0, 2, fr)
-    nn = ctx.match_dir(0, 0)[0][:len(A)]
+    return fr
+
+
+def _geo_grid_corner_case(ctx, orc, kind, grid, use_l2, monkeypatch):
+    monkeypatch.setenv("DSSS_MT_GRID", grid)
+    fr = geo_grid_corner_frames(kind)
+    for f, a in fr.items():
+        ctx.frame_set(f, None, a["N"], a["M"], a["pose"], a["alt"], a["gr"])
+        ctx.features_set(f, a["N"], a["M"], a["kps"], a["desc"], geo=a["geo"], bbox=a["bb"])
+    mp, op, mt, pg = ctx.default_params()
+    mt.use_l2 = use_l2
+    op_ = orc.match_params(); op_.use_l2 = use_l2
+    ctx.set_params(match=mt)
+    try:
+        ctx.match_pairs([0], [2])
+        _check_pair(ctx, orc, 0, 0, 2, fr, op_)
+        nn = ctx.match_dir(0, 0)[0][:len(fr[0]["kps"])]
+    finally:
+        mt.use_l2 = 0
+        ctx.set_params(match=mt)
     assert (nn >= 0).sum() > 10
 
 
