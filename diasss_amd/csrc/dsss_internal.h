@@ -345,3 +345,5 @@ __host__ __device__ inline void dsss_geo_at(const double* pose6, const double* g
     dsss_geo_side(P, col >= M / 2, &s, &c);
     dsss_geo_bin(P, gr, M, col, s, c, x, y);
 }
+// a DR yaw that switches the sticky pi-yaw compensation of LoopClosingTFs on (optimizer.cpp:697-703)
+__host__ __device__ inline bool dsss_yaw_flips(double yaw) { return fabs(yaw) > 2 * DSSS_PI_REF / 3; }

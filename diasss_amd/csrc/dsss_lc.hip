@@ -6,6 +6,8 @@
 // oracle/orc_lc.c.  f64 VALU: 15 x 15 systems are far too small for MFMA; 16 lanes per problem.
 #include "dsss_internal.h"
 #include "dsss_pose.h"
+#include "dsss_lm.h"
+#include <algorithm>
 
 #define MR 16
 #define MD 15
@@ -17,26 +19,20 @@ struct mini_prob {
 };
 struct mini_val { double L[3]; pose_t X1, X2; };
 
-// ---- 16 lanes per problem, four problems per wavefront.  The pose algebra (a few hundred dependent flops) is evaluated
-// redundantly by every lane of the group; the 16 x 15 Jacobian and the 15 x 15 systems live in LDS with one row per lane,
-// and every sum keeps the element-wise order of oracle/orc_lc.c (k ascending), so results equal the one-thread version
-// bit for bit while the serial chains shrink from O(15^3) to O(15^2) and nothing spills to scratch.
+// ---- 16 lanes per problem, four problems per wavefront.  The 16 x 15 Jacobian and the 15 x 15 systems live in LDS with one row per lane; every sum
+// keeps the element-wise order of oracle/orc_lc.c (k ascending): the one-thread version's bits, with serial chains of O(15^2) instead of O(15^3).
 #define LG 16                  // lanes per problem
 #define LS 16                  // LDS row stride (doubles)
-// The problem's constants and its current / trial values live in LDS too: every lane of the group holds the same 100 doubles,
-// and kept in registers (200 VGPRs of the 512) they were what held the kernel at one wavefront per SIMD with 110 spills.
-// H and its Cholesky factor share one 15 x 16 array: H keeps its lower triangle ([i][j], j <= i), the factor goes into the other half
-// transposed and shifted by a column (L(i, k), k <= i, at [k][i + 1]) -- H survives the retries of a trial with a larger lambda, and
-// 4.9 KB per problem instead of 6.8 let eight workgroups share a compute unit's LDS (two wavefronts per SIMD).
+// The problem's constants and its current / trial values live in LDS too (the same 100 doubles on every lane: in registers they held the kernel at one
+// wavefront per SIMD).  H and its Cholesky factor share one 15 x 16 array: H keeps its lower triangle ([i][j], j <= i), the factor goes into the other
+// half transposed and shifted by a column (L(i, k), k <= i, at [k][i + 1]) -- H survives the retries of a trial with a larger lambda, and 4.9 KB per
+// problem let eight workgroups share a compute unit's LDS (two wavefronts per SIMD).
 #define LIDX(i, k) ((k) * LS + (i) + 1)
 struct lc_lds { double J[MR * LS]; double H[MD * LS]; double r[MR]; mini_prob m; mini_val v, nv; };
 
-// The pose algebra of a problem is a chain of a few hundred dependent f64 operations (two Logmaps with acos / sin / tan, two sss
-// factors with a square root and divisions) that every lane of the group used to run in full: 75 % of the kernel's cycles (in-kernel
-// stamps, round 3).  The factors come in PAIRS of the same code on different data -- prior / between (Logmap of a relative pose),
-// source / target sss factor, retraction of X1 / X2, the two DR poses of the set-up -- so lanes 0..7 of the group run the first of
-// a pair and lanes 8..15 the second, at the same time, and the results cross by one shuffle each.  Every value is produced by the
-// same operations in the same order as before: the output is bit-identical.
+// The pose algebra (two Logmaps with acos / sin / tan, two sss factors: a few hundred dependent f64 operations, 75 % of the kernel's cycles) comes in
+// PAIRS of the same code on different data -- prior / between, source / target sss factor, retraction of X1 / X2, the two DR poses of the set-up --
+// so lanes 0..7 of the group run the first of a pair and lanes 8..15 the second, and the results cross by one shuffle each.
 __device__ inline void lc_bcast_pose(const pose_t& mine, int src, pose_t* out)
 {
 #pragma unroll
@@ -122,7 +118,9 @@ __device__ static void mini_lin(const mini_prob& m, const mini_val& v, double* r
     }
     if (J) __builtin_amdgcn_wave_barrier();
 }
-__device__ static double mini_err(const mini_prob& m, const mini_val& v, int lane)
+// Out of line on purpose: inlined at its two call sites it costs lc_kernel 42 VGPRs and 25 spills.  mini_lin stays with the inliner, which takes it into
+// mini_err and calls it from the kernel: forced out of line as well, mini_err would call it and the scratch grows from 64 to 208 B per lane.
+__device__ static __noinline__ double mini_err(const mini_prob& m, const mini_val& v, int lane)
 {
     double r[MR];
     mini_lin(m, v, r, nullptr, lane);
@@ -197,52 +195,40 @@ __device__ static void chol15_solve(const double* L, double* b)
     }
 }
 
-// kp7: n x 7; per problem: frame pointers (pose6 / alt / gr of source and target), M of both, flip flags
-__global__ __launch_bounds__(64, 2) void lc_kernel(const double* __restrict__ kp7, int n,
-                                                const int* __restrict__ kp7_pair, const uint8_t* __restrict__ kp7_flip,
-                                                const int* __restrict__ act_s, const int* __restrict__ act_t,
-                                                int single_s, int single_t, int single_flip,
-                                                const double* const* __restrict__ alt_ptr, const double* const* __restrict__ gr_ptr,
-                                                const double* const* __restrict__ pose_ptr, const int* __restrict__ fcols,
-                                                dsss_lc* __restrict__ out)
+// ------------------------------------------------------------------ what lc_kernel and tri_kernel share
+// the pi-yaw compensation of one side (optimizer.cpp:650,697-703) from its flag bit; rebuilt where needed, not kept in registers across an LM
+__device__ inline void lc_comp_pose(bool on, pose_t* C)
 {
-    __shared__ lc_lds s_all[64 / LG];
-    const int grp = threadIdx.x / LG, lane = threadIdx.x % LG;
-    const int i = blockIdx.x * (64 / LG) + grp;
-    if (i >= n) return;                                     // whole groups leave together
-    lc_lds& S = s_all[grp];
+    const double flipv[3] = { 0, 0, DSSS_PI_REF };
+    pose_identity(C); if (on) so3_exp(flipv, C->R);
+}
+// sigmas of an SssPointFactor (:685): sigma_r = 0.1, slant * alpha_bw with alpha_bw = 0.1 degrees
+__device__ inline void lc_sss_sigmas(double slant, double* sig) { sig[0] = 0.1; sig[1] = slant * (0.1 * DSSS_PI_REF / 180); }
+// landmark start (:789-795): midpoint of the two geo samples, mean of the two pings' depths below their altitudes
+__device__ inline void lc_landmark_start(const double* geo_s, const double* geo_t, double z_s, double alt_s, double z_t, double alt_t, double* L)
+{
+    L[0] = (geo_s[0] + geo_t[0]) / 2; L[1] = (geo_s[1] + geo_t[1]) / 2; L[2] = ((z_s - alt_s) + (z_t - alt_t)) / 2;
+}
+
+// ------------------------------------------------------------------ lc_kernel, stage by stage (each inlined into the kernel)
+// the context's per-frame device tables, indexed by frame slot
+struct lc_tables { const double* const* __restrict__ alt; const double* const* __restrict__ gr; const double* const* __restrict__ pose; const int* __restrict__ cols; };
+static lc_tables lc_tables_of(const dsss_ctx* c) { const int F = c->max_frames; return { c->d_ptrs, c->d_ptrs + F, c->d_ptrs + 2 * F, c->cols_dev }; }
+
+// set-up (:685-795): DR poses with the compensation, sigmas and the landmark start into LDS (S.m, S.v); geo[4]: the two points' geo samples
+__device__ inline void lc_setup(lc_lds& S, const lc_tables& T, const double* kp, int fs, int ft, int flip, int lane, double* geo)
+{
     const double PI = DSSS_PI_REF;
-    const double* kp = kp7 + (size_t)i * 7;
-    const int fs = kp7_pair ? act_s[kp7_pair[i]] : single_s, ft = kp7_pair ? act_t[kp7_pair[i]] : single_t;
-    int flip = kp7_flip ? kp7_flip[i] : 0;
-    const double* pose_s = pose_ptr[fs]; const double* pose_t_ = pose_ptr[ft];
+    const double* pose_s = T.pose[fs]; const double* pose_t_ = T.pose[ft];
     const int id_s = (int)kp[0], id_t = (int)kp[3];
-    if (!kp7_flip) {
-        // stand-alone call: the sticky compensation (optimizer.cpp:650,700-703) is resolved over the caller's list
-        const double thr = 2 * PI / 3;
-        for (int k = 0; k <= i; ++k) {
-            const double* q = kp7 + (size_t)k * 7;
-            if (fabs(pose_s[(size_t)(int)q[0] * 6 + 2]) > thr) flip |= 1;
-            if (fabs(pose_t_[(size_t)(int)q[3] * 6 + 2]) > thr) flip |= 2;
-        }
-        (void)single_flip;
-    }
-    pose_t cps_s, cps_t;
-    pose_identity(&cps_s); pose_identity(&cps_t);
-    const double flipv[3] = { 0, 0, PI };
-    if (flip & 1) so3_exp(flipv, cps_s.R);
-    if (flip & 2) so3_exp(flipv, cps_t.R);
-    const double sigma_r = 0.1, alpha_bw = 0.1 * PI / 180;     // :685
-    mini_prob m;                                            // built in registers, parked in LDS below (S.m)
-    m.slant_s = kp[2]; m.slant_t = kp[5];
-    m.sig_s[0] = sigma_r; m.sig_s[1] = kp[2] * alpha_bw;
-    m.sig_t[0] = sigma_r; m.sig_t[1] = kp[5] * alpha_bw;
+    const bool hb = (lane & 8) != 0;                       // lanes 0..7: the source ping's pose and geo sample, lanes 8..15: the target's
+    mini_prob m;                                            // built in registers
+    m.slant_s = kp[2]; m.slant_t = kp[5]; lc_sss_sigmas(kp[2], m.sig_s); lc_sss_sigmas(kp[5], m.sig_t);
     pose_t Tp_s, Tp_t, Tp_st;
-    const bool hb0 = (lane & 8) != 0;                       // lanes 0..7: the source ping's pose and geo sample, lanes 8..15: the target's
     {
         pose_t Pm, Cm, Tm;
-        pose_from_rodrigues(hb0 ? pose_t_ + (size_t)id_t * 6 : pose_s + (size_t)id_s * 6, &Pm);
-        lc_select_pose(hb0, cps_s, cps_t, &Cm);
+        pose_from_rodrigues(hb ? pose_t_ + (size_t)id_t * 6 : pose_s + (size_t)id_s * 6, &Pm);
+        lc_comp_pose(flip & (hb ? 2 : 1), &Cm);
         pose_compose(&Pm, &Cm, &Tm);
         lc_bcast_pose(Tm, 0, &Tp_s); lc_bcast_pose(Tm, 8, &Tp_t);
     }
@@ -252,121 +238,102 @@ __global__ __launch_bounds__(64, 2) void lc_kernel(const double* __restrict__ kp
     m.sig_odo[3] = fabs(Tp_st.t[0] * 2); m.sig_odo[4] = fabs(Tp_st.t[1] / 10); m.sig_odo[5] = 0.1;
     for (int k = 3; k < 5; ++k) if (m.sig_odo[k] < 1e-9) m.sig_odo[k] = 1e-9;
     m.prior = Tp_s; m.odo = Tp_st;
-    const int Ms = fcols[fs], Mt = fcols[ft];
-    const int id_ss = (int)kp[1], id_tt = (int)kp[4];
-    double gsx, gsy, gtx, gty;
-    {
-        double gx, gy;
-        dsss_geo_at(hb0 ? pose_t_ : pose_s, hb0 ? gr_ptr[ft] : gr_ptr[fs], hb0 ? Mt : Ms, hb0 ? id_t : id_s, hb0 ? id_tt : id_ss, &gx, &gy);
-        gsx = __shfl(gx, 0, LG); gsy = __shfl(gy, 0, LG); gtx = __shfl(gx, 8, LG); gty = __shfl(gy, 8, LG);
-    }
+    double gx, gy;
+    dsss_geo_at(hb ? pose_t_ : pose_s, hb ? T.gr[ft] : T.gr[fs], hb ? T.cols[ft] : T.cols[fs], hb ? id_t : id_s, hb ? (int)kp[4] : (int)kp[1], &gx, &gy);
+    geo[0] = __shfl(gx, 0, LG); geo[1] = __shfl(gy, 0, LG); geo[2] = __shfl(gx, 8, LG); geo[3] = __shfl(gy, 8, LG);
     mini_val v;
-    v.L[0] = (gsx + gtx) / 2; v.L[1] = (gsy + gty) / 2;                                                    // :792-795
-    v.L[2] = ((pose_s[(size_t)id_s * 6 + 5] - alt_ptr[fs][id_s]) + (pose_t_[(size_t)id_t * 6 + 5] - alt_ptr[ft][id_t])) / 2;
+    lc_landmark_start(geo, geo + 2, pose_s[(size_t)id_s * 6 + 5], T.alt[fs][id_s], pose_t_[(size_t)id_t * 6 + 5], T.alt[ft][id_t], v.L);
     v.X1 = Tp_s; v.X2 = Tp_t;
     if (lane == 0) { S.m = m; S.v = v; }
     __builtin_amdgcn_wave_barrier();                        // the group's lanes sit in one wavefront: its LDS operations execute in program order
-    const mini_prob& M_ = S.m; const mini_val& V_ = S.v;
-    // ---- LevenbergMarquardtOptimizer::optimize, default params
-    const double relTol = 1e-5, absTol = 1e-5, lamMax = 1e5, minFid = 1e-3;
-    double lambda = 1e-5;
-    int iters = 0;
-    double err = mini_err(M_, V_, lane);
-    const double err0 = err;
+}
+// one trial: solve (H + lambda I) d = -g, linear error at d, retraction into S.nv, error there.  Failed Cholesky, rising linear model: refused, no stop
+__device__ inline lm_verdict lc_trial(lc_lds& S, const lm_rule& R, double g_mine, double lambda, double oldLin, double err, int lane, double* newErr)
+{
+    const lm_verdict refused = { false, false };
+    if (chol15(S.H, lambda, S.H, lane) != 0) return refused;
     double d[MD];
-    const double* r = S.r;                                  // (LDS; written by mini_lin)
-    if (err > 0) {
-        double cur;
-        do {
-            cur = err;
-            mini_lin(M_, V_, S.r, S.J, lane);
-            const double g_mine = normal_eq(S.J, r, S.H, lane);
-            double oldLin = 0;
 #pragma unroll
-            for (int k = 0; k < MR; ++k) oldLin += r[k] * r[k];
-            oldLin *= 0.5;
-            for (;;) {
-                const bool ok = chol15(S.H, lambda, S.H, lane) == 0;
-                bool success = false, stop = false;
-                double newErr = 0;
-                if (ok) {
+    for (int a = 0; a < MD; ++a) d[a] = -__shfl(g_mine, a, LG);
+    chol15_solve(S.H, d);
+    double sk = S.r[lane];                                  // lane k: row k of J d + r
 #pragma unroll
-                    for (int a = 0; a < MD; ++a) d[a] = -__shfl(g_mine, a, LG);
-                    chol15_solve(S.H, d);
-                    double sk = r[lane];                                // lane k: row k of J d + r
+    for (int a = 0; a < MD; ++a) sk += S.J[lane * LS + a] * d[a];
+    double newLin = 0;
 #pragma unroll
-                    for (int a = 0; a < MD; ++a) sk += S.J[lane * LS + a] * d[a];
-                    double newLin = 0;
+    for (int k = 0; k < MR; ++k) { const double t = __shfl(sk, k, LG); newLin += t * t; }
+    newLin *= 0.5;
+    if (!lm_descends(oldLin, newLin)) return refused;
+    {   // the trial values go to LDS (S.nv); the registers that held them are free again afterwards
+        const bool hb = (lane & 8) != 0;                    // lanes 0..7 retract X1, lanes 8..15 X2
+        pose_t Xn; double dx[6];
+        const pose_t* X = hb ? &S.v.X2 : &S.v.X1;
 #pragma unroll
-                    for (int k = 0; k < MR; ++k) { const double t = __shfl(sk, k, LG); newLin += t * t; }
-                    newLin *= 0.5;
-                    const double linChange = oldLin - newLin;
-                    if (linChange >= 0) {
-                        {   // the trial values go to LDS (S.nv); the registers that held them are free again afterwards
-                            const bool hb = (lane & 8) != 0;                  // lanes 0..7 retract X1, lanes 8..15 X2
-                            pose_t Xn; double dx[6];
-                            const pose_t* X = hb ? &V_.X2 : &V_.X1;
-#pragma unroll
-                            for (int a = 0; a < 6; ++a) dx[a] = hb ? d[9 + a] : d[3 + a];
-                            pose_retract(X, dx, &Xn);
-                            if (lane == 0) { for (int a = 0; a < 3; ++a) S.nv.L[a] = V_.L[a] + d[a]; S.nv.X1 = Xn; }
-                            if (lane == 8) S.nv.X2 = Xn;
-                            __builtin_amdgcn_wave_barrier();
-                        }
-                        newErr = mini_err(M_, S.nv, lane);
-                        const double costChange = err - newErr;
-                        if (linChange > 2.220446049250313e-16 * oldLin) success = (costChange / linChange) > minFid;
-                        if (fabs(costChange) < relTol * err) stop = true;
-                    }
-                }
-                if (success) {
-                    {   // v = nv, element-wise by the lanes of the group (27 doubles)
-                        const double* src = reinterpret_cast<const double*>(&S.nv); double* dst = reinterpret_cast<double*>(&S.v);
-                        const double e0 = src[lane], e1 = lane + LG < (int)(sizeof(mini_val) / sizeof(double)) ? src[lane + LG] : 0.0;
-                        __builtin_amdgcn_wave_barrier();
-                        dst[lane] = e0; if (lane + LG < (int)(sizeof(mini_val) / sizeof(double))) dst[lane + LG] = e1;
-                        __builtin_amdgcn_wave_barrier();
-                    }
-                    err = newErr; lambda /= 10; ++iters; break;
-                }
-                else if (!stop) { lambda *= 10; if (lambda >= lamMax) break; }
-                else break;
-            }
-        } while (iters < 100 && !((err <= 0) || ((cur - err) / cur <= relTol) || ((cur - err) <= absTol)) && isfinite(cur));
+        for (int a = 0; a < 6; ++a) dx[a] = hb ? d[9 + a] : d[3 + a];
+        pose_retract(X, dx, &Xn);
+        if (lane == 0) { for (int a = 0; a < 3; ++a) S.nv.L[a] = S.v.L[a] + d[a]; S.nv.X1 = Xn; }
+        if (lane == 8) S.nv.X2 = Xn;
+        __builtin_amdgcn_wave_barrier();
     }
-    dsss_lc o;
-    o.iters = iters; o.pad_ = 0; o.err0 = err0; o.err1 = err;
-    // eval_1 (:853-896)
-    pose_t cti, new_pose;
-    {   // the yaw compensations are rebuilt from the flags here rather than kept in registers across the LM loop
-        pose_t cq; pose_identity(&cq);
-        if (flip & 2) so3_exp(flipv, cq.R);
-        pose_inverse(&cq, &cti);
-    }
-    pose_compose(&V_.X2, &cti, &new_pose);
-    const double x_o = gsx - gtx, y_o = gsy - gty;
-    const double ini = sqrt(x_o * x_o + y_o * y_o);
-    double rpy[3];
-    pose_rpy(&new_pose, rpy);
-    const double* gr_t = gr_ptr[ft];
-    double lx, ly;
-    if (kp[4] < Mt / 2) {
-        const int gi = Mt / 2 - (int)kp[4];
-        lx = new_pose.t[0] + gr_t[gi] * cos(rpy[2] + PI / 2 - PI);
-        ly = new_pose.t[1] + gr_t[gi] * sin(rpy[2] + PI / 2 - PI);
-    } else {
-        const int gi = (int)kp[4] - Mt / 2;
-        lx = new_pose.t[0] + gr_t[gi] * cos(rpy[2] - PI / 2 - PI);
-        ly = new_pose.t[1] + gr_t[gi] * sin(rpy[2] - PI / 2 - PI);
-    }
-    const double x_n = gsx - lx, y_n = gsy - ly;
-    const double fin = sqrt(x_n * x_n + y_n * y_n);
-    o.score = ini / fin - 2;
-    // Marginals(graph, result).marginalCovariance(X2).diagonal() (:956-959): lane c < 6 solves for unit vector 9 + c
-    mini_lin(M_, V_, S.r, S.J, lane);
-    (void)normal_eq(S.J, r, S.H, lane);
+    *newErr = mini_err(S.m, S.nv, lane);
+    return lm_judge(R, oldLin, newLin, err, *newErr);
+}
+// v = nv, element-wise by the lanes of the group (27 doubles)
+__device__ inline void lc_take_trial(lc_lds& S, int lane)
+{
+    const double* src = reinterpret_cast<const double*>(&S.nv); double* dst = reinterpret_cast<double*>(&S.v);
+    const double e0 = src[lane], e1 = lane + LG < (int)(sizeof(mini_val) / sizeof(double)) ? src[lane + LG] : 0.0;
+    __builtin_amdgcn_wave_barrier();
+    dst[lane] = e0; if (lane + LG < (int)(sizeof(mini_val) / sizeof(double))) dst[lane + LG] = e1;
+    __builtin_amdgcn_wave_barrier();
+}
+// LevenbergMarquardtOptimizer::optimize, default params (:815-822), on S.v; *err_io: the error at S.v; returns the accepted steps
+__device__ inline int lc_lm(lc_lds& S, int lane, double* err_io)
+{
+    const lm_rule R = lm_gtsam_defaults();
+    double lambda = 1e-5, err = *err_io, cur;
+    int iters = 0;
+    if (err > 0) do {
+        cur = err;
+        mini_lin(S.m, S.v, S.r, S.J, lane);
+        const double g_mine = normal_eq(S.J, S.r, S.H, lane);
+        double oldLin = 0;
+#pragma unroll
+        for (int k = 0; k < MR; ++k) oldLin += S.r[k] * S.r[k];
+        oldLin *= 0.5;
+        for (;;) {
+            double newErr = 0;
+            const lm_verdict v = lc_trial(S, R, g_mine, lambda, oldLin, err, lane, &newErr);
+            if (v.success) { lc_take_trial(S, lane); err = newErr; lm_accepted(R, &lambda); ++iters; break; }
+            if (v.stop || lm_refused(R, &lambda)) break;
+        }
+    } while (lm_continue(R, iters, cur, err));
+    *err_io = err; return iters;
+}
+// eval_1 (:853-896): *new_pose = X2 without its compensation; score = ini / final - 2, the source sample's distance to the target's before and after
+__device__ inline double lc_score(const lc_lds& S, const double* kp, const double* gr_t, int Mt, int flip, const double* geo, pose_t* new_pose)
+{
+    const double PI = DSSS_PI_REF;
+    pose_t cq, cti;
+    lc_comp_pose(flip & 2, &cq); pose_inverse(&cq, &cti);
+    pose_compose(&S.v.X2, &cti, new_pose);
+    const double x_o = geo[0] - geo[2], y_o = geo[1] - geo[3], ini = sqrt(x_o * x_o + y_o * y_o);
+    double rpy[3]; pose_rpy(new_pose, rpy);
+    const bool port = kp[4] < Mt / 2;
+    const int gi = port ? Mt / 2 - (int)kp[4] : (int)kp[4] - Mt / 2;
+    const double bearing = port ? rpy[2] + PI / 2 - PI : rpy[2] - PI / 2 - PI;
+    const double lx = new_pose->t[0] + gr_t[gi] * cos(bearing), ly = new_pose->t[1] + gr_t[gi] * sin(bearing);
+    const double x_n = geo[0] - lx, y_n = geo[1] - ly;
+    return ini / sqrt(x_n * x_n + y_n * y_n) - 2;
+}
+// Marginals(graph, result).marginalCovariance(X2).diagonal() (:956-959): lane c < 6 solves for unit vector 9 + c; NaN where H at S.v does not factor
+__device__ inline void lc_marginal_var(lc_lds& S, int lane, double* var)
+{
+    mini_lin(S.m, S.v, S.r, S.J, lane);
+    (void)normal_eq(S.J, S.r, S.H, lane);
     double var_mine = NAN;
     if (chol15(S.H, 0.0, S.H, lane) == 0) {
+        double d[MD];
 #pragma unroll
         for (int a = 0; a < MD; ++a) d[a] = (a == 9 + lane) ? 1.0 : 0.0;
         chol15_solve(S.H, d);
@@ -375,17 +342,39 @@ __global__ __launch_bounds__(64, 2) void lc_kernel(const double* __restrict__ kp
         for (int a = 9; a < MD; ++a) if (a == 9 + lane) var_mine = d[a];
     }
 #pragma unroll
-    for (int c2 = 0; c2 < 6; ++c2) o.var[c2] = __shfl(var_mine, c2, LG);
-    pose_t csi, src, rel;
-    {
-        pose_t cq; pose_identity(&cq);
-        if (flip & 1) so3_exp(flipv, cq.R);
-        pose_inverse(&cq, &csi);
-    }
-    pose_compose(&M_.prior, &csi, &src);                         // m.prior = Tp_s
-    pose_between(&src, &new_pose, &rel);                         // :958
-    for (int a = 0; a < 9; ++a) o.rel[a] = rel.R[a];
-    for (int a = 0; a < 3; ++a) o.rel[9 + a] = rel.t[a];
+    for (int c2 = 0; c2 < 6; ++c2) var[c2] = __shfl(var_mine, c2, LG);
+}
+// the measurement (:958): new_pose relative to the source's DR pose without its compensation (S.m.prior = Tp_s)
+__device__ inline void lc_rel_pose(const lc_lds& S, int flip, const pose_t& new_pose, double* rel12)
+{
+    pose_t cq, csi, src, rel;
+    lc_comp_pose(flip & 1, &cq); pose_inverse(&cq, &csi);
+    pose_compose(&S.m.prior, &csi, &src); pose_between(&src, &new_pose, &rel);
+    for (int a = 0; a < 9; ++a) rel12[a] = rel.R[a];
+    for (int a = 0; a < 3; ++a) rel12[9 + a] = rel.t[a];
+}
+
+// kp7: n x 7, kp7_flip: the sticky compensation flags of every row (bit 0 source, bit 1 target; made by the matcher or by lc_sticky_flags).
+// The frames of row i: slots act_s / act_t[kp7_pair[i]], or single_s / single_t for every row when kp7_pair is null.
+__global__ __launch_bounds__(64, 2) void lc_kernel(const double* __restrict__ kp7, int n, const int* __restrict__ kp7_pair, const uint8_t* __restrict__ kp7_flip,
+                                                const int* __restrict__ act_s, const int* __restrict__ act_t, int single_s, int single_t, lc_tables T, dsss_lc* __restrict__ out)
+{
+    __shared__ lc_lds s_all[64 / LG];
+    const int grp = threadIdx.x / LG, lane = threadIdx.x % LG;
+    const int i = blockIdx.x * (64 / LG) + grp;
+    if (i >= n) return;                                     // whole groups leave together
+    lc_lds& S = s_all[grp];
+    const double* kp = kp7 + (size_t)i * 7;
+    const int fs = kp7_pair ? act_s[kp7_pair[i]] : single_s, ft = kp7_pair ? act_t[kp7_pair[i]] : single_t;
+    const int flip = kp7_flip[i];
+    double geo[4]; dsss_lc o;
+    lc_setup(S, T, kp, fs, ft, flip, lane, geo);                              // :685-795
+    o.pad_ = 0; o.err0 = o.err1 = mini_err(S.m, S.v, lane);
+    o.iters = lc_lm(S, lane, &o.err1);                                        // :815-822
+    pose_t new_pose;
+    o.score = lc_score(S, kp, T.gr[ft], T.cols[ft], flip, geo, &new_pose);    // :853-896
+    lc_marginal_var(S, lane, o.var);                                          // :956-959
+    lc_rel_pose(S, flip, new_pose, o.rel);                                    // :958
     if (lane == 0) out[i] = o;
 }
 
@@ -395,15 +384,45 @@ __global__ __launch_bounds__(64, 2) void lc_kernel(const double* __restrict__ kp
 // (10, 10, |xy baseline| / 100).  Call site :907-921 (eval_2): DR poses with the sticky yaw compensation, landmark
 // initialised as in :789-795; the four consistency figures printed there are returned next to the point.
 // One thread per problem: 7 x 3 Jacobian and a 3 x 3 system in registers; same operation order as oracle/orc_lc.c.
-__device__ static void tri_lin(const pose_t& Tp_s, const pose_t& Tp_t, double slant_s, double slant_t, const double* sig_s, const double* sig_t,
-                               const double* sig_p, const double* ini, const double* p, double* r, double* J)
+struct tri_frame { const double* pose; const double* alt; const double* gr; int M; };      // device tables of one frame (unused, null, in the explicit-poses form)
+struct tri_prob { pose_t Tp_s, Tp_t; double slant_s, slant_t, sig_s[2], sig_t[2], sig_p[3], ini[3]; };
+
+// set-up: poses and start point -- the caller's (q, a row of the n x 27 form) or the DR poses with the compensation -- and the sigmas
+__device__ inline void tri_setup(tri_prob& P, const double* kp, const tri_frame& s, const tri_frame& t, int flip, const double* q)
+{
+    if (q) {                                                        // TriangulateOneLandmark with the caller's poses and start point
+        for (int k = 0; k < 9; ++k) { P.Tp_s.R[k] = q[k]; P.Tp_t.R[k] = q[12 + k]; }
+        for (int k = 0; k < 3; ++k) { P.Tp_s.t[k] = q[9 + k]; P.Tp_t.t[k] = q[21 + k]; P.ini[k] = q[24 + k]; }
+    } else {
+        const int id_s = (int)kp[0], id_t = (int)kp[3];
+        pose_t cps_s, cps_t, Ps, Pt;
+        lc_comp_pose(flip & 1, &cps_s); lc_comp_pose(flip & 2, &cps_t);
+        pose_from_rodrigues(s.pose + (size_t)id_s * 6, &Ps); pose_from_rodrigues(t.pose + (size_t)id_t * 6, &Pt);
+        pose_compose(&Ps, &cps_s, &P.Tp_s); pose_compose(&Pt, &cps_t, &P.Tp_t);
+        double geo_s[2], geo_t[2];
+        dsss_geo_at(s.pose, s.gr, s.M, id_s, (int)kp[1], &geo_s[0], &geo_s[1]);
+        dsss_geo_at(t.pose, t.gr, t.M, id_t, (int)kp[4], &geo_t[0], &geo_t[1]);
+        lc_landmark_start(geo_s, geo_t, s.pose[(size_t)id_s * 6 + 5], s.alt[id_s], t.pose[(size_t)id_t * 6 + 5], t.alt[id_t], P.ini);
+    }
+    P.slant_s = kp[2]; P.slant_t = kp[5]; lc_sss_sigmas(kp[2], P.sig_s); lc_sss_sigmas(kp[5], P.sig_t);
+    const double dx = P.Tp_s.t[0] - P.Tp_t.t[0], dy = P.Tp_s.t[1] - P.Tp_t.t[1];
+    P.sig_p[0] = 10.0; P.sig_p[1] = 10.0; P.sig_p[2] = sqrt(dx * dx + dy * dy) / 100;
+    if (P.sig_p[2] < 1e-9) P.sig_p[2] = 1e-9;
+}
+__device__ static void tri_lin(const tri_prob& P, const double* p, double* r, double* J)
 {
     double ee[2], H1[6], H2[12];
-    sss_factor(p, &Tp_s, slant_s, 0.0, ee, J ? H1 : nullptr, H2);
-    for (int i = 0; i < 2; ++i) { r[i] = ee[i] / sig_s[i]; if (J) for (int j = 0; j < 3; ++j) J[i * 3 + j] = H1[3 * i + j] / sig_s[i]; }
-    sss_factor(p, &Tp_t, slant_t, 0.0, ee, J ? H1 : nullptr, H2);
-    for (int i = 0; i < 2; ++i) { r[2 + i] = ee[i] / sig_t[i]; if (J) for (int j = 0; j < 3; ++j) J[(2 + i) * 3 + j] = H1[3 * i + j] / sig_t[i]; }
-    for (int i = 0; i < 3; ++i) { r[4 + i] = (p[i] - ini[i]) / sig_p[i]; if (J) for (int j = 0; j < 3; ++j) J[(4 + i) * 3 + j] = (i == j) ? 1.0 / sig_p[i] : 0.0; }
+    sss_factor(p, &P.Tp_s, P.slant_s, 0.0, ee, J ? H1 : nullptr, H2);
+    for (int i = 0; i < 2; ++i) { r[i] = ee[i] / P.sig_s[i]; if (J) for (int j = 0; j < 3; ++j) J[i * 3 + j] = H1[3 * i + j] / P.sig_s[i]; }
+    sss_factor(p, &P.Tp_t, P.slant_t, 0.0, ee, J ? H1 : nullptr, H2);
+    for (int i = 0; i < 2; ++i) { r[2 + i] = ee[i] / P.sig_t[i]; if (J) for (int j = 0; j < 3; ++j) J[(2 + i) * 3 + j] = H1[3 * i + j] / P.sig_t[i]; }
+    for (int i = 0; i < 3; ++i) { r[4 + i] = (p[i] - P.ini[i]) / P.sig_p[i]; if (J) for (int j = 0; j < 3; ++j) J[(4 + i) * 3 + j] = (i == j) ? 1.0 / P.sig_p[i] : 0.0; }
+}
+__device__ static double tri_err(const tri_prob& P, const double* p)
+{
+    double rr[7], t = 0;
+    tri_lin(P, p, rr, nullptr); for (int k = 0; k < 7; ++k) t += rr[k] * rr[k];
+    return 0.5 * t;
 }
 __device__ static int tri_chol3(double* A)
 {
@@ -416,58 +435,16 @@ __device__ static int tri_chol3(double* A)
     }
     return 0;
 }
-__global__ __launch_bounds__(64) void tri_kernel(const double* __restrict__ kp7, int n, const double* __restrict__ pose_s, const double* __restrict__ alt_s,
-                                                 const double* __restrict__ gr_s, int Ms, const double* __restrict__ pose_t_, const double* __restrict__ alt_t,
-                                                 const double* __restrict__ gr_t, int Mt, const double* __restrict__ explicit27, double* __restrict__ out7)
+// the 3-DoF LM on the landmark p (optimizer.cpp:1003-1010), GTSAM defaults
+__device__ inline void tri_lm(const tri_prob& P, double* p)
 {
-    const int i = blockIdx.x * 64 + threadIdx.x;
-    if (i >= n) return;
-    const double PI = DSSS_PI_REF, thr = 2 * PI / 3;
-    int flip = 0;                                                   // sticky over the caller's list (optimizer.cpp:650,700-703)
-    if (!explicit27) for (int k = 0; k <= i; ++k) {
-        const double* q = kp7 + (size_t)k * 7;
-        if (fabs(pose_s[(size_t)(int)q[0] * 6 + 2]) > thr) flip |= 1;
-        if (fabs(pose_t_[(size_t)(int)q[3] * 6 + 2]) > thr) flip |= 2;
-    }
-    const double* kp = kp7 + (size_t)i * 7;
-    const int id_s = (int)kp[0], id_t = (int)kp[3];
-    pose_t cps_s, cps_t, Ps, Pt, Tp_s, Tp_t;
-    pose_identity(&cps_s); pose_identity(&cps_t);
-    const double flipv[3] = { 0, 0, PI };
-    if (flip & 1) so3_exp(flipv, cps_s.R);
-    if (flip & 2) so3_exp(flipv, cps_t.R);
-    double ini[3];
-    if (explicit27) {                                               // TriangulateOneLandmark with the caller's poses and start point
-        const double* q = explicit27 + (size_t)i * 27;
-        for (int k = 0; k < 9; ++k) { Tp_s.R[k] = q[k]; Tp_t.R[k] = q[12 + k]; }
-        for (int k = 0; k < 3; ++k) { Tp_s.t[k] = q[9 + k]; Tp_t.t[k] = q[21 + k]; ini[k] = q[24 + k]; }
-    } else {
-        pose_from_rodrigues(pose_s + (size_t)id_s * 6, &Ps);
-        pose_from_rodrigues(pose_t_ + (size_t)id_t * 6, &Pt);
-        pose_compose(&Ps, &cps_s, &Tp_s);
-        pose_compose(&Pt, &cps_t, &Tp_t);
-        double gsx, gsy, gtx, gty;
-        dsss_geo_at(pose_s, gr_s, Ms, id_s, (int)kp[1], &gsx, &gsy);
-        dsss_geo_at(pose_t_, gr_t, Mt, id_t, (int)kp[4], &gtx, &gty);
-        ini[0] = (gsx + gtx) / 2; ini[1] = (gsy + gty) / 2;
-        ini[2] = ((pose_s[(size_t)id_s * 6 + 5] - alt_s[id_s]) + (pose_t_[(size_t)id_t * 6 + 5] - alt_t[id_t])) / 2;
-    }
-    const double sigma_r = 0.1, alpha_bw = 0.1 * PI / 180;
-    const double sig_s[2] = { sigma_r, kp[2] * alpha_bw }, sig_t[2] = { sigma_r, kp[5] * alpha_bw };
-    const double dx = Tp_s.t[0] - Tp_t.t[0], dy = Tp_s.t[1] - Tp_t.t[1];
-    double sig_p[3] = { 10.0, 10.0, sqrt(dx * dx + dy * dy) / 100 };
-    if (sig_p[2] < 1e-9) sig_p[2] = 1e-9;
-    double p[3] = { ini[0], ini[1], ini[2] };
-    const double relTol = 1e-5, absTol = 1e-5, lamMax = 1e5, minFid = 1e-3;
-    double r[7], J[21];
-    auto err_of = [&](const double* q) { double rr[7]; tri_lin(Tp_s, Tp_t, kp[2], kp[5], sig_s, sig_t, sig_p, ini, q, rr, nullptr);
-                                         double t = 0; for (int k = 0; k < 7; ++k) t += rr[k] * rr[k]; return 0.5 * t; };
-    double lambda = 1e-5, err = err_of(p), cur;
+    const lm_rule R = lm_gtsam_defaults();
+    double lambda = 1e-5, err = tri_err(P, p), cur;
     int iters = 0;
     if (err > 0) do {
         cur = err;
-        double H[9], g[3];
-        tri_lin(Tp_s, Tp_t, kp[2], kp[5], sig_s, sig_t, sig_p, ini, p, r, J);
+        double r[7], J[21], H[9], g[3];
+        tri_lin(P, p, r, J);
         for (int a = 0; a < 3; ++a) {
             double t = 0; for (int k = 0; k < 7; ++k) t += J[k * 3 + a] * r[k];
             g[a] = t;
@@ -475,40 +452,46 @@ __global__ __launch_bounds__(64) void tri_kernel(const double* __restrict__ kp7,
         }
         double oldLin = 0; for (int k = 0; k < 7; ++k) oldLin += r[k] * r[k];
         oldLin *= 0.5;
-        for (;;) {
-            double A[9], d[3], np_[3] = { 0, 0, 0 };
+        for (;;) {                                                  // one trial per pass; a failed Cholesky and a rising linear model are refused, no stop
+            double A[9], d[3], np_[3] = { 0, 0, 0 }, newErr = 0, newLin = 0;
+            lm_verdict v = { false, false };
             for (int a = 0; a < 9; ++a) A[a] = H[a];
             for (int a = 0; a < 3; ++a) { A[a * 3 + a] += lambda; d[a] = -g[a]; }
-            const bool ok = tri_chol3(A) == 0;
-            bool success = false, stop = false;
-            double newErr = 0;
-            if (ok) {
+            if (tri_chol3(A) == 0) {
                 for (int a = 0; a < 3; ++a) { double t = d[a]; for (int k = 0; k < a; ++k) t -= A[a * 3 + k] * d[k]; d[a] = t / A[a * 3 + a]; }
                 for (int a = 2; a >= 0; --a) { double t = d[a]; for (int k = a + 1; k < 3; ++k) t -= A[k * 3 + a] * d[k]; d[a] = t / A[a * 3 + a]; }
-                double newLin = 0;
                 for (int k = 0; k < 7; ++k) { double t = r[k]; for (int a = 0; a < 3; ++a) t += J[k * 3 + a] * d[a]; newLin += t * t; }
                 newLin *= 0.5;
-                const double linChange = oldLin - newLin;
-                if (linChange >= 0) {
+                if (lm_descends(oldLin, newLin)) {
                     for (int a = 0; a < 3; ++a) np_[a] = p[a] + d[a];
-                    newErr = err_of(np_);
-                    const double costChange = err - newErr;
-                    if (linChange > 2.220446049250313e-16 * oldLin) success = (costChange / linChange) > minFid;
-                    if (fabs(costChange) < relTol * err) stop = true;
+                    newErr = tri_err(P, np_);
+                    v = lm_judge(R, oldLin, newLin, err, newErr);
                 }
             }
-            if (success) { for (int a = 0; a < 3; ++a) p[a] = np_[a]; err = newErr; lambda /= 10; ++iters; break; }
-            else if (!stop) { lambda *= 10; if (lambda >= lamMax) break; }
-            else break;
+            if (v.success) { for (int a = 0; a < 3; ++a) p[a] = np_[a]; err = newErr; lm_accepted(R, &lambda); ++iters; break; }
+            if (v.stop || lm_refused(R, &lambda)) break;
         }
-    } while (iters < 100 && !((err <= 0) || ((cur - err) / cur <= relTol) || ((cur - err) <= absTol)) && isfinite(cur));
-    double* o = out7 + (size_t)i * 7;
+    } while (lm_continue(R, iters, cur, err));
+}
+// flips: the rows' sticky flags (lc_sticky_flags), null only with explicit27 (n x 27: the caller's poses and start points)
+__global__ __launch_bounds__(64) void tri_kernel(const double* __restrict__ kp7, int n, const uint8_t* __restrict__ flips, tri_frame fs, tri_frame ft,
+                                                 const double* __restrict__ explicit27, double* __restrict__ out7)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const double* kp = kp7 + (size_t)i * 7;
+    tri_prob P;
+    tri_setup(P, kp, fs, ft, flips ? flips[i] : 0, explicit27 ? explicit27 + (size_t)i * 27 : nullptr);      // :907-915, :789-795
+    double p[3] = { P.ini[0], P.ini[1], P.ini[2] };
+    tri_lm(P, p);                                                                                            // :984-1021
+    double* o = out7 + (size_t)i * 7;                               // the point and the four consistency figures (:916-921)
     o[0] = p[0]; o[1] = p[1]; o[2] = p[2];
     double e[2];
-    sss_factor(p, &Tp_s, kp[2], 0.0, e, nullptr, nullptr); o[3] = fabs(e[0]); o[4] = fabs(e[1]);
-    sss_factor(p, &Tp_t, kp[5], 0.0, e, nullptr, nullptr); o[5] = fabs(e[0]); o[6] = fabs(e[1]);
+    sss_factor(p, &P.Tp_s, P.slant_s, 0.0, e, nullptr, nullptr); o[3] = fabs(e[0]); o[4] = fabs(e[1]);
+    sss_factor(p, &P.Tp_t, P.slant_t, 0.0, e, nullptr, nullptr); o[5] = fabs(e[0]); o[6] = fabs(e[1]);
 }
 
+// ------------------------------------------------------------------ host side
 // caller-supplied kp7 rows: pings and bins index altitude / ground-range tables on the device, so they are range-checked on the host first
 // (GetKpsPairs never emits |bin - M/2| < 20, optimizer.cpp:602-609; bin - M/2 == M/2 is the one-past-the-end read).  pair < 0: no pair to name.
 static int check_kp7_rows(dsss_ctx* c, const dsss_frame& fs, const dsss_frame& ft, const double* rows, int n, int pair)
@@ -521,6 +504,59 @@ static int check_kp7_rows(dsss_ctx* c, const dsss_frame& fs, const dsss_frame& f
     }
     return DSSS_OK;
 }
+// sticky yaw compensation flags of ONE LoopClosingTFs call (optimizer.cpp:650,697-703): prefix OR over its n checked rows, bit 0 source, bit 1 target
+static void lc_sticky_flags(const dsss_frame& fs, const dsss_frame& ft, const double* rows, int n, uint8_t* flip)
+{
+    uint8_t f = 0;
+    for (int i = 0; i < n; ++i) {
+        const double* k = rows + (size_t)i * 7;
+        if (dsss_yaw_flips(fs.h_geo[(size_t)(int)k[0] * 6 + 2])) f |= 1;
+        if (dsss_yaw_flips(ft.h_geo[(size_t)(int)k[3] * 6 + 2])) f |= 2;
+        flip[i] = f;
+    }
+}
+// dsss_lc_solve and dsss_triangulate before anything reaches the device: frames, host copy of the rows (kp7 may be a device pointer), range check, flags
+static int lc_one_list(dsss_ctx* c, int id_s, int id_t, const double* kp7, int n, std::vector<double>* h, std::vector<uint8_t>* flip)
+{
+    if (id_s < 0 || id_s >= c->max_frames || id_t < 0 || id_t >= c->max_frames) DSSS_FAIL(c, DSSS_E_ARG, "frame id out of range");
+    const dsss_frame &fs = c->frames[id_s], &ft = c->frames[id_t];
+    if (!fs.has_geom || !ft.has_geom) DSSS_FAIL(c, DSSS_E_STATE, "frames need dsss_frame_set first");
+    if (!fs.h_geo || !ft.h_geo) DSSS_FAIL(c, DSSS_E_STATE, "host copy of the DR poses missing");
+    if (n == 0) return DSSS_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    h->resize((size_t)n * 7); flip->resize(n);
+    HIPCHK(c, hipMemcpy(h->data(), kp7, h->size() * sizeof(double), hipMemcpyDefault));
+    if (const int rc = check_kp7_rows(c, fs, ft, h->data(), n, -1)) return rc;
+    lc_sticky_flags(fs, ft, h->data(), n, flip->data());
+    return DSSS_OK;
+}
+// queues lc_kernel over n > 0 rows on the context's stream; the pointer tables are up (dsss_mt_upload_ptr_tables)
+static int lc_launch(dsss_ctx* c, const double* kp7, int n, const int* kp7_pair, const uint8_t* kp7_flip, const int* act_s, const int* act_t, int single_s, int single_t,
+                     dsss_lc* out)
+{
+    dsss_scope sc(c, DSSS_K_LC);
+    hipLaunchKernelGGL(lc_kernel, dim3((n + 3) / 4), dim3(64), 0, c->stream, kp7, n, kp7_pair, kp7_flip, act_s, act_t, single_s, single_t, lc_tables_of(c), out);
+    HIPCHK(c, hipGetLastError());
+    return DSSS_OK;
+}
+// the two triangulation calls: rows and flags (or explicit poses) up into ONE buffer of this call, freed on every way out; tri_kernel; results down
+static int tri_run(dsss_ctx* c, const double* kp7, int n, const uint8_t* h_flip, const tri_frame& fs, const tri_frame& ft, const double* in27, double* out7)
+{
+    const size_t nd = (size_t)n * (7 + 7 + (in27 ? 27 : 0));
+    dsss_buf d("triangulation rows, inputs and results");
+    if (const int rc = d.reserve(c, nd * sizeof(double) + (h_flip ? (size_t)n : 0))) return rc;
+    double* d_kp7 = d.as<double>(); double* d_out = d_kp7 + (size_t)n * 7; double* d_in = in27 ? d_out + (size_t)n * 7 : nullptr;
+    uint8_t* d_flip = h_flip ? reinterpret_cast<uint8_t*>(d_kp7 + nd) : nullptr;
+    HIPCHK(c, hipMemcpyAsync(d_kp7, kp7, (size_t)n * 7 * sizeof(double), hipMemcpyDefault, c->stream));
+    if (d_in) HIPCHK(c, hipMemcpyAsync(d_in, in27, (size_t)n * 27 * sizeof(double), hipMemcpyDefault, c->stream));
+    if (d_flip) HIPCHK(c, hipMemcpyAsync(d_flip, h_flip, (size_t)n, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(tri_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, (const double*)d_kp7, n, (const uint8_t*)d_flip, fs, ft, (const double*)d_in, d_out);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(out7, d_out, (size_t)n * 7 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return DSSS_OK;
+}
+static tri_frame tri_frame_of(const dsss_frame& f) { return { f.pose6, f.alt, f.gr, f.M }; }
 
 extern "C" {
 
@@ -531,13 +567,8 @@ int dsss_lc_solve_all(dsss_ctx* c)
     const int n = c->total_kp7;
     c->has_lc = false;
     if (const int rc = c->lcs.reserve(c, (size_t)n * sizeof(dsss_lc), ((size_t)n + 1024) * sizeof(dsss_lc))) return rc;
-    const int F = c->max_frames;
-    if (n > 0) {
-        dsss_scope sc(c, DSSS_K_LC);
-        hipLaunchKernelGGL(lc_kernel, dim3((n + 3) / 4), dim3(64), 0, c->stream, c->kp7, n, c->kp7_pair, c->kp7_flip, c->act_s, c->act_t,
-                           0, 0, 0, c->d_ptrs, c->d_ptrs + F, c->d_ptrs + 2 * F, c->cols_dev, c->lcs.as<dsss_lc>());
-        HIPCHK(c, hipGetLastError());
-    }
+    if (n > 0)
+        if (const int rc = lc_launch(c, c->kp7, n, c->kp7_pair, c->kp7_flip, c->act_s, c->act_t, 0, 0, c->lcs.as<dsss_lc>())) return rc;
     c->has_lc = true; ++c->lc_gen;      // an LC result set exists once its launch is queued (none for an empty one)
     return DSSS_OK;
 }
@@ -579,18 +610,13 @@ int dsss_lc_solve_pairs(dsss_ctx* c, const int* src_ids, const int* tgt_ids, int
     std::vector<double> h((size_t)n * 7);
     if (n > 0) HIPCHK(c, hipMemcpy(h.data(), kp7, h.size() * sizeof(double), hipMemcpyDefault));
     std::vector<int> h_pair(n); std::vector<uint8_t> h_flip(n);
-    const double thr = 2 * DSSS_PI_REF / 3;                         // optimizer.cpp:697-703: sticky within one LoopClosingTFs call
-    for (int p = 0; p < npairs && n > 0; ++p) {
+    for (int p = 0; p < npairs && n > 0; ++p) {                    // the flags are sticky within one LoopClosingTFs call: per pair
         const dsss_frame &fs = c->frames[src_ids[p]], &ft = c->frames[tgt_ids[p]];
+        const int o = pair_off[p], np = pair_off[p + 1] - o;
         if (!fs.h_geo || !ft.h_geo) DSSS_FAIL(c, DSSS_E_STATE, "pair %d: host copy of the DR poses missing", p);
-        if ((rc = check_kp7_rows(c, fs, ft, h.data() + (size_t)pair_off[p] * 7, pair_off[p + 1] - pair_off[p], p))) return rc;
-        uint8_t flip = 0;
-        for (int i = pair_off[p]; i < pair_off[p + 1]; ++i) {
-            const double* k = h.data() + (size_t)i * 7;
-            if (std::fabs(fs.h_geo[(size_t)(int)k[0] * 6 + 2]) > thr) flip |= 1;
-            if (std::fabs(ft.h_geo[(size_t)(int)k[3] * 6 + 2]) > thr) flip |= 2;
-            h_pair[i] = p; h_flip[i] = flip;
-        }
+        if ((rc = check_kp7_rows(c, fs, ft, h.data() + (size_t)o * 7, np, p))) return rc;
+        lc_sticky_flags(fs, ft, h.data() + (size_t)o * 7, np, h_flip.data() + o);
+        std::fill(h_pair.begin() + o, h_pair.begin() + o + np, p);
     }
     if (n > 0) {
         HIPCHK(c, hipStreamSynchronize(c->stream));                // queued kernels may still read the buffers written below
@@ -611,25 +637,15 @@ int dsss_lc_solve_pairs(dsss_ctx* c, const int* src_ids, const int* tgt_ids, int
 int dsss_lc_solve(dsss_ctx* c, int id_s, int id_t, const double* kp7, int n, dsss_lc* out)
 {
     if (!c || n < 0 || (n > 0 && (!kp7 || !out))) return DSSS_E_ARG;
-    if (id_s < 0 || id_s >= c->max_frames || id_t < 0 || id_t >= c->max_frames) DSSS_FAIL(c, DSSS_E_ARG, "frame id out of range");
-    if (!c->frames[id_s].has_geom || !c->frames[id_t].has_geom) DSSS_FAIL(c, DSSS_E_STATE, "frames need dsss_frame_set first");
-    if (n == 0) return DSSS_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    std::vector<double> h((size_t)n * 7);                      // host copy (the caller's pointer may be a device pointer): checked, then uploaded
-    HIPCHK(c, hipMemcpy(h.data(), kp7, h.size() * sizeof(double), hipMemcpyDefault));
-    int rc = check_kp7_rows(c, c->frames[id_s], c->frames[id_t], h.data(), n, -1); if (rc) return rc;
+    std::vector<double> h; std::vector<uint8_t> flip;
+    int rc = lc_one_list(c, id_s, id_t, kp7, n, &h, &flip); if (rc || n == 0) return rc;
     if ((rc = dsss_sync_bboxes(c))) return rc;                 // also publishes the frames' N and M to the device tables
     if ((rc = dsss_mt_upload_ptr_tables(c))) return rc;
-    dsss_buf d_kp7("dsss_lc_solve kp7"), d_out("dsss_lc_solve results");      // of this call: freed on every way out of it
-    if ((rc = d_kp7.reserve(c, h.size() * sizeof(double))) || (rc = d_out.reserve(c, (size_t)n * sizeof(dsss_lc)))) return rc;
+    dsss_buf d_kp7("dsss_lc_solve kp7"), d_flip("dsss_lc_solve flags"), d_out("dsss_lc_solve results");      // of this call: freed on every way out of it
+    if ((rc = d_kp7.reserve(c, h.size() * sizeof(double))) || (rc = d_flip.reserve(c, flip.size())) || (rc = d_out.reserve(c, (size_t)n * sizeof(dsss_lc)))) return rc;
     HIPCHK(c, hipMemcpyAsync(d_kp7.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    const int F = c->max_frames;
-    {
-        dsss_scope sc(c, DSSS_K_LC);
-        hipLaunchKernelGGL(lc_kernel, dim3((n + 3) / 4), dim3(64), 0, c->stream, (const double*)d_kp7.p, n, (const int*)nullptr, (const uint8_t*)nullptr,
-                           (const int*)nullptr, (const int*)nullptr, id_s, id_t, 0, c->d_ptrs, c->d_ptrs + F, c->d_ptrs + 2 * F, c->cols_dev, (dsss_lc*)d_out.p);
-    }
-    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(d_flip.p, flip.data(), flip.size(), hipMemcpyHostToDevice, c->stream));
+    if ((rc = lc_launch(c, d_kp7.as<double>(), n, nullptr, d_flip.as<uint8_t>(), nullptr, nullptr, id_s, id_t, d_out.as<dsss_lc>()))) return rc;
     HIPCHK(c, hipMemcpyAsync(out, d_out.p, (size_t)n * sizeof(dsss_lc), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return DSSS_OK;
@@ -640,22 +656,9 @@ int dsss_lc_solve(dsss_ctx* c, int id_s, int id_t, const double* kp7, int n, dss
 int dsss_triangulate(dsss_ctx* c, int id_s, int id_t, const double* kp7, int n, double* out7)
 {
     if (!c || n < 0 || (n > 0 && (!kp7 || !out7))) return DSSS_E_ARG;
-    if (id_s < 0 || id_s >= c->max_frames || id_t < 0 || id_t >= c->max_frames) DSSS_FAIL(c, DSSS_E_ARG, "frame id out of range");
-    const dsss_frame &fs = c->frames[id_s], &ft = c->frames[id_t];
-    if (!fs.has_geom || !ft.has_geom) DSSS_FAIL(c, DSSS_E_STATE, "frames need dsss_frame_set first");
-    if (n == 0) return DSSS_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    std::vector<double> h((size_t)n * 7);
-    HIPCHK(c, hipMemcpy(h.data(), kp7, h.size() * sizeof(double), hipMemcpyDefault));
-    int rc = check_kp7_rows(c, fs, ft, h.data(), n, -1); if (rc) return rc;
-    dsss_buf d_kp7("dsss_triangulate kp7"), d_out("dsss_triangulate results");      // of this call
-    if ((rc = d_kp7.reserve(c, h.size() * sizeof(double))) || (rc = d_out.reserve(c, h.size() * sizeof(double)))) return rc;
-    HIPCHK(c, hipMemcpyAsync(d_kp7.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(tri_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, (const double*)d_kp7.p, n, fs.pose6, fs.alt, fs.gr, fs.M, ft.pose6, ft.alt, ft.gr, ft.M, (const double*)nullptr, (double*)d_out.p);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(out7, d_out.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return DSSS_OK;
+    std::vector<double> h; std::vector<uint8_t> flip;
+    const int rc = lc_one_list(c, id_s, id_t, kp7, n, &h, &flip); if (rc || n == 0) return rc;
+    return tri_run(c, h.data(), n, flip.data(), tri_frame_of(c->frames[id_s]), tri_frame_of(c->frames[id_t]), nullptr, out7);
 }
 
 // the same with the caller's own poses: Optimizer::TriangulateOneLandmark(kps_pair, Ts_s, Ts_t, Tp_s, Tp_t, lm_ini) with
@@ -665,17 +668,7 @@ int dsss_triangulate_poses(dsss_ctx* c, const double* kp7, const double* in27, i
     if (!c || n < 0 || (n > 0 && (!kp7 || !in27 || !out7))) return DSSS_E_ARG;
     if (n == 0) return DSSS_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    dsss_buf d("dsss_triangulate_poses scratch");      // of this call
-    if (const int rc = d.reserve(c, (size_t)n * (7 + 27 + 7) * sizeof(double))) return rc;
-    double* d_kp7 = (double*)d.p; double* d_in = d_kp7 + (size_t)n * 7; double* d_out = d_in + (size_t)n * 27;
-    HIPCHK(c, hipMemcpyAsync(d_kp7, kp7, (size_t)n * 7 * sizeof(double), hipMemcpyDefault, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_in, in27, (size_t)n * 27 * sizeof(double), hipMemcpyDefault, c->stream));
-    hipLaunchKernelGGL(tri_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, d_kp7, n, (const double*)nullptr, (const double*)nullptr, (const double*)nullptr, 0,
-                       (const double*)nullptr, (const double*)nullptr, (const double*)nullptr, 0, (const double*)d_in, d_out);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(out7, d_out, (size_t)n * 7 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return DSSS_OK;
+    return tri_run(c, kp7, n, nullptr, tri_frame{}, tri_frame{}, in27, out7);
 }
 
 } // extern "C"

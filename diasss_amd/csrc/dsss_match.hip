@@ -510,9 +510,8 @@ __global__ __launch_bounds__(256) void pair_rows_kernel(
             int tot7;
             const int pos7 = dsss_block_scan_excl<4, int>(v7, &tot7, s_w);
             // sticky yaw compensation flags of LoopClosingTFs (optimizer.cpp:650,698-703): prefix OR in list order
-            const double thr = 2 * DSSS_PI_REF / 3;
-            const int fs_here = v7 && fabs(pose_s[(size_t)ps * 6 + 2]) > thr;
-            const int ft_here = v7 && fabs(pose_t[(size_t)pt * 6 + 2]) > thr;
+            const int fs_here = v7 && dsss_yaw_flips(pose_s[(size_t)ps * 6 + 2]);
+            const int ft_here = v7 && dsss_yaw_flips(pose_t[(size_t)pt * 6 + 2]);
             int tfs, tft;
             const int pre_s = dsss_block_scan_excl<4, int>(fs_here, &tfs, s_w) + fs_here;
             const int pre_t = dsss_block_scan_excl<4, int>(ft_here, &tft, s_w) + ft_here;

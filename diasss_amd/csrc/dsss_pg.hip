@@ -15,6 +15,7 @@
 //      extend-add of the children's update matrices, panel Cholesky / row solve / trailing update on the f64 matrix cores;
 //   4. back-substitution through the segments.
 #include "dsss_internal.h"
+#include "dsss_lm.h"
 #include <utility>
 #include "dsss_pg_kernels.h"
 #include <algorithm>
@@ -783,6 +784,7 @@ struct pg_solve {
 
     // ---- the LM loop: acceptance, the lambda schedule, GTSAM's stop rule
     int lm_loop() {
+        const lm_rule R = { c->pg.rel_tol, c->pg.abs_tol, c->pg.lambda_max, c->pg.min_fidelity, c->pg.lambda_factor, c->pg.max_iters };
         double cur = 0;
         if (will_iterate) do {                        // NonlinearOptimizer::defaultOptimize returns before iterating when maxIterations is reached
             cur = err;
@@ -802,23 +804,12 @@ struct pg_solve {
                 HIPCHK(c, hipGetLastError());
                 double h[3]; int failed = 0;
                 if (const int rc = reduce_scalars(h, &failed)) return rc;
-                const bool ok = !failed && std::isfinite(h[1]);
-                bool success = false, stop = false;
-                double newErr = 0;
-                if (ok) {
-                    const double linChange = oldLin - h[1];
-                    if (linChange >= 0) {
-                        newErr = h[2];
-                        const double costChange = err - newErr;
-                        if (linChange > 2.220446049250313e-16 * oldLin) success = (costChange / linChange) > c->pg.min_fidelity;
-                        if (std::fabs(costChange) < c->pg.rel_tol * err) stop = true;
-                    }
-                }
-                if (success) { std::swap(d_X, d_Xn); std::swap(d_r, d_r2); std::swap(d_Ji, d_Ji2); pre_lin = true; err = newErr; lambda /= c->pg.lambda_factor; ++iters; break; }
-                else if (!stop) { lambda *= c->pg.lambda_factor; if (lambda >= c->pg.lambda_max) break; }
-                else break;
+                // (a failed factorisation or a non-finite linear error is a refused trial that does not stop)
+                const lm_verdict v = !failed && std::isfinite(h[1]) ? lm_judge(R, oldLin, h[1], err, h[2]) : lm_verdict{ false, false };
+                if (v.success) { std::swap(d_X, d_Xn); std::swap(d_r, d_r2); std::swap(d_Ji, d_Ji2); pre_lin = true; err = h[2]; lm_accepted(R, &lambda); ++iters; break; }
+                if (v.stop || lm_refused(R, &lambda)) break;
             }
-        } while (iters < c->pg.max_iters && !((err <= 0) || ((cur - err) / cur <= c->pg.rel_tol) || ((cur - err) <= c->pg.abs_tol)) && std::isfinite(cur));
+        } while (lm_continue(R, iters, cur, err));
         return DSSS_OK;
     }
 

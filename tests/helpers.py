@@ -94,9 +94,9 @@ def _row(fs, ft, ps, bs, pt, bt):
     return [ps, bs, lc_slant(fs, ps, bs), pt, bt, lc_slant(ft, pt, bt), 0.0]
 
 
-def lc_consistent_rows(orc, fs, ft, n, rng, max_dist=0.05, t_ping=None, geo_t=None):
+def lc_consistent_rows(orc, fs, ft, n, rng, max_dist=0.05, t_ping=None, geo_t=None, s_ping=None):
     """n kp7 rows that see one ground point from both frames: a random source ping / bin, the target ping / bin whose geo point is
-    nearest (within max_dist), slant ranges from altitude and ground range.  t_ping: optional predicate on the target ping."""
+    nearest (within max_dist), slant ranges from altitude and ground range.  t_ping, s_ping: optional predicates on the target / source ping."""
     gs = _Geo.of(orc, fs); gt = geo_t or _Geo.of(orc, ft)
     N = len(fs[0])
     rows = []
@@ -106,6 +106,8 @@ def lc_consistent_rows(orc, fs, ft, n, rng, max_dist=0.05, t_ping=None, geo_t=No
         keep = d <= max_dist
         if t_ping is not None:
             keep &= t_ping(pt)
+        if s_ping is not None:
+            keep &= s_ping(ps)
         for k in np.nonzero(keep)[0]:
             rows.append(_row(fs, ft, int(ps[k]), int(bs[k]), int(pt[k]), int(bt[k])))
             if len(rows) == n:
@@ -174,6 +176,13 @@ def lc_cases(orc, seed=0):
     lo = lc_consistent_rows(orc, f0, fm, 20, rng, t_ping=lambda p: p < N // 2, geo_t=gm)
     hi = lc_consistent_rows(orc, f0, fm, 4, rng, t_ping=lambda p: p >= N // 2, geo_t=gm)
     G["mid-list-flip"] = dict(frames=[f0, fm], lists=[(0, 1, np.concatenate([lo[:12], hi[:1], lo[12:], hi[1:]]))], switch=12)
+    # the same with the yaw step on the SOURCE frame (flag bit 0): 24 rows, switch at row 12
+    rng = sub(8)
+    ps_ = f0[0].copy(); ps_[:, 2] = np.where(np.arange(N) < N // 2, 0.5, 2.5)
+    fms = (ps_, f0[1], f0[2])
+    lo = lc_consistent_rows(orc, fms, f1, 20, rng, s_ping=lambda p: p < N // 2)
+    hi = lc_consistent_rows(orc, fms, f1, 4, rng, s_ping=lambda p: p >= N // 2)
+    G["mid-list-flip-src"] = dict(frames=[fms, f1], lists=[(0, 1, np.concatenate([lo[:12], hi[:1], lo[12:], hi[1:]]))], switch=12)
     # the borders the range check admits, on the source side and on the target side; the partner is the nearest admissible point
     rng = sub(5)
     g0, g1 = _Geo.of(orc, f0), _Geo.of(orc, f1)
@@ -223,6 +232,21 @@ def lc_cases(orc, seed=0):
                 a.setflags(write=False)
     _LC_CACHE[seed] = G
     return G
+
+
+def lc_long_flip_list(orc):
+    """65 rows over the frames of lc_cases' mid-list-flip group: more than one block of tri_kernel (64 problems).  The target's yaw crosses
+    2 pi / 3 at row 63, the last of the first block; row 64, the only one of the second block, has the small yaw again and is flipped only
+    because the flag is sticky over the whole list.  dict(frames, list=(0, 1, kp7), switch=63)"""
+    if "long-flip" not in _LC_CACHE:
+        g = lc_cases(orc, 0)["mid-list-flip"]
+        f0, fm = g["frames"]
+        rng = np.random.default_rng([4000, 9]); gm = _Geo.of(orc, fm)
+        lo = lc_consistent_rows(orc, f0, fm, 64, rng, t_ping=lambda p: p < LC_N // 2, geo_t=gm)
+        hi = lc_consistent_rows(orc, f0, fm, 1, rng, t_ping=lambda p: p >= LC_N // 2, geo_t=gm)
+        k = np.concatenate([lo[:63], hi, lo[63:]]); k.setflags(write=False)
+        _LC_CACHE["long-flip"] = dict(frames=g["frames"], list=(0, 1, k), switch=63)
+    return _LC_CACHE["long-flip"]
 
 
 LC_SEAM_N = 1400

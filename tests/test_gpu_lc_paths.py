@@ -10,12 +10,12 @@ the largest deviation it saw next to the largest it would have allowed."""
 import numpy as np
 import pytest
 
-from tests.helpers import LC_M, LC_N, LC_SEAM_N, _nonfinite_code, _spread, lc_cases, lc_reference, lc_seam_case, tri_reference
+from tests.helpers import LC_M, LC_N, LC_SEAM_N, _nonfinite_code, _spread, lc_cases, lc_long_flip_list, lc_reference, lc_seam_case, tri_reference
 
 pytestmark = pytest.mark.gpu
 
 GROUPS = ("consistent-opposite", "consistent-same", "noisy-slant", "wrong-flip", "tiny-slant", "long-slant", "zero-slant", "zero-baseline",
-          "tilted", "mid-list-flip", "edges", "ragged", "pairs", "select")
+          "tilted", "mid-list-flip", "mid-list-flip-src", "edges", "ragged", "pairs", "select")
 TRI_GROUPS = ("noisy-slant", "wrong-flip", "tiny-slant", "zero-slant", "zero-baseline")
 
 
@@ -115,30 +115,110 @@ def test_lc_solve_pairs_straddling_wavefronts(ctx, orc, cases):
     _report("pairs (one launch)", stat)
 
 
-def test_sticky_flip_that_switches_on_mid_list(ctx, orc, cases):
-    """the target's yaw crosses 2 pi / 3 at row `switch` of the list; the rows after it have the small yaw again and stay flipped
-    (optimizer.cpp:650,700-703).  Stand-alone form = pairs form byte for byte; both = the oracle; and the rows behind the switch differ from what
-    they give in a list that starts behind it exactly where the oracle's differ."""
-    g = cases["mid-list-flip"]
+def _differs(a, b):
+    return np.array([x.tobytes() != y.tobytes() for x, y in zip(a, b)])
+
+
+def _lc_switch_mid_list(ctx, orc, cases, name, col):
+    """the list of group `name`, whose yaw (of the pings in kp7 column col: 0 source, 3 target) crosses 2 pi / 3 at row `switch`"""
+    g = cases[name]
     _load(ctx, g["frames"])
     s, t, k = g["lists"][0]; sw = g["switch"]
-    pt = g["frames"][t][0]
-    yaw = np.abs(pt[k[:, 3].astype(int), 2])
+    pose = g["frames"][t if col == 3 else s][0]
+    yaw = np.abs(pose[k[:, col].astype(int), 2])
     assert (yaw[:sw] < 2).all() and yaw[sw] > 2.2 and (yaw[sw + 1:sw + 9] < 2).all()
     alone = ctx.lc_solve(s, t, k)
     ctx.lc_solve_pairs([s], [t], [k])
     assert ctx.lc_get(0).tobytes() == alone.tobytes()
-    ref = lc_reference(orc, g["frames"], s, t, k, key=("mid-list-flip", 0))
+    ref = lc_reference(orc, g["frames"], s, t, k, key=(name, 0))
     stat = {}
-    _check_lc("mid-list-flip", alone, ref, stat)
+    _check_lc(name, alone, ref, stat)
     tail = k[sw + 1:]
     g_tail = ctx.lc_solve(s, t, tail)
-    r_tail = lc_reference(orc, g["frames"], s, t, tail, key=("mid-list-flip", "tail"))
-    _check_lc("mid-list-flip tail", g_tail, r_tail, stat)
-    d_dev = np.array([a.tobytes() != b.tobytes() for a, b in zip(g_tail, alone[sw + 1:])])
-    d_orc = np.array([a.tobytes() != b.tobytes() for a, b in zip(r_tail["lcs"], ref["lcs"][sw + 1:])])
+    r_tail = lc_reference(orc, g["frames"], s, t, tail, key=(name, "tail"))
+    _check_lc(name + " tail", g_tail, r_tail, stat)
+    d_dev = _differs(g_tail, alone[sw + 1:])
+    d_orc = _differs(r_tail["lcs"], ref["lcs"][sw + 1:])
     assert (d_dev == d_orc).all() and d_orc[:8].all() and not d_orc[8:].any()
-    _report("mid-list-flip", stat)
+    _report(name, stat)
+
+
+def test_sticky_flip_that_switches_on_mid_list(ctx, orc, cases):
+    """the target's yaw crosses 2 pi / 3 at row `switch` of the list; the rows after it have the small yaw again and stay flipped
+    (optimizer.cpp:650,700-703).  Stand-alone form = pairs form byte for byte; both = the oracle; and the rows behind the switch differ from what
+    they give in a list that starts behind it exactly where the oracle's differ."""
+    _lc_switch_mid_list(ctx, orc, cases, "mid-list-flip", 3)
+
+
+def test_sticky_flip_that_switches_on_mid_list_source_side(ctx, orc, cases):
+    """the same with the step in the SOURCE frame's yaw (flag bit 0): 24 rows, switch at row 12"""
+    g = cases["mid-list-flip-src"]
+    assert len(g["lists"][0][2]) == 24 and g["switch"] == 12
+    _lc_switch_mid_list(ctx, orc, cases, "mid-list-flip-src", 0)
+
+
+def _check_tri(got, ref, what, stat):
+    """dsss_triangulate against tri_reference: the non-finite pattern on every row, path-stable rows within max(1e-9, 16 x spread)"""
+    st = ref["stable"]
+    assert got.shape == ref["out"].shape
+    assert (np.isfinite(got) == np.isfinite(ref["out"])).all()
+    _within(got[st], ref["out"][st], np.maximum(1e-9, 16 * ref["spread"][st]), what, stat)
+
+
+@pytest.mark.parametrize("name", ("mid-list-flip", "mid-list-flip-src"))
+def test_triangulate_sticky_flip_mid_list(ctx, orc, cases, name):
+    """dsss_triangulate takes the sticky flags of its list as dsss_lc_solve does: the full list and the rows behind the switch alone, each
+    against orc_triangulate, and the two device results differ on exactly the rows where the oracle's differ (the eight small-yaw rows)"""
+    g = cases[name]
+    _load(ctx, g["frames"])
+    s, t, k = g["lists"][0]; sw = g["switch"]
+    stat = {}
+    full = ctx.triangulate(s, t, k)
+    ref = tri_reference(orc, g["frames"], s, t, k, key=(name, 0))
+    _check_tri(full, ref, "triangulate", stat)
+    tail = k[sw + 1:]
+    g_tail = ctx.triangulate(s, t, tail)
+    r_tail = tri_reference(orc, g["frames"], s, t, tail, key=(name, "tail"))
+    _check_tri(g_tail, r_tail, "triangulate tail", stat)
+    d_dev = _differs(g_tail, full[sw + 1:])
+    d_orc = _differs(r_tail["out"], ref["out"][sw + 1:])
+    assert (d_dev == d_orc).all() and d_orc[:8].all() and not d_orc[8:].any()
+    _report(name + " (tri)", stat)
+
+
+def test_one_row_lists(ctx, orc, cases):
+    """lists of ONE row through dsss_lc_solve and dsss_triangulate, against the oracle on the same one-row list: a row below the yaw threshold (no
+    flag) and the row at the switch, flagged by itself -- on the target side (bit 1, mid-list-flip) and on the source side (bit 0, mid-list-flip-src)"""
+    stat = {}
+    for name, rows in (("mid-list-flip", (0, None)), ("mid-list-flip-src", (None,))):
+        g = cases[name]
+        _load(ctx, g["frames"])
+        s, t, k = g["lists"][0]
+        for i in (g["switch"] if r is None else r for r in rows):
+            one = k[i:i + 1]
+            got = ctx.lc_solve(s, t, one)
+            assert len(got) == 1
+            _check_lc((name, "one row", i), got, lc_reference(orc, g["frames"], s, t, one, key=(name, "row", i)), stat)
+            _check_tri(ctx.triangulate(s, t, one), tri_reference(orc, g["frames"], s, t, one, key=(name, "row", i)), "triangulate", stat)
+    _report("one-row lists", stat)
+
+
+def test_triangulate_flag_crosses_into_the_second_block(ctx, orc):
+    """65 rows (helpers.lc_long_flip_list): tri_kernel's second block holds row 64 alone, and its flag was switched on by row 63 of the first.
+    Against orc_triangulate on the whole list; row 64 alone (no flag) gives other bits, on the device as on the oracle."""
+    g = lc_long_flip_list(orc)
+    _load(ctx, g["frames"])
+    s, t, k = g["list"]
+    assert len(k) == 65 and g["switch"] == 63
+    stat = {}
+    full = ctx.triangulate(s, t, k)
+    ref = tri_reference(orc, g["frames"], s, t, k, key=("long-flip", 0))
+    _check_tri(full, ref, "triangulate", stat)
+    last = ctx.triangulate(s, t, k[64:])
+    r_last = tri_reference(orc, g["frames"], s, t, k[64:], key=("long-flip", "last"))
+    _check_tri(last, r_last, "triangulate last row", stat)
+    assert r_last["out"].tobytes() != ref["out"][64:].tobytes() and last.tobytes() != full[64:].tobytes()
+    _report("65 rows (tri)", stat)
 
 
 def _tri_one_reference(orc, kp7, in27):

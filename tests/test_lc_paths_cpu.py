@@ -4,7 +4,7 @@ take the exits they are built for, and the oracle has to be able to decide them.
 import numpy as np
 import pytest
 
-from tests.helpers import LC_M, LC_SEAM_N, LC_SEAM_POSES, LC_SEAM_RESIDUES, lc_cases, lc_reference, lc_seam_case, tri_reference
+from tests.helpers import LC_M, LC_SEAM_N, LC_SEAM_POSES, LC_SEAM_RESIDUES, lc_cases, lc_long_flip_list, lc_reference, lc_seam_case, tri_reference
 
 EXITS = ("rejected", "lammax_exit", "stop_nosuccess", "iter_cap", "chol_fail", "marg_fail")
 
@@ -123,6 +123,41 @@ def test_at_most_a_tenth_of_a_group_is_knife_edge(refs):
             st = np.concatenate([r[what]["stable"] for r in lists])
             print("%-20s %s knife-edge %d of %d" % (name, ("lc", "tri")[what], (~st).sum(), len(st)))
             assert (~st).sum() <= 0.10 * len(st), (name, what)
+
+
+@pytest.mark.parametrize("name,col", (("mid-list-flip", 3), ("mid-list-flip-src", 0)))
+def test_mid_list_switch_groups(orc, refs, name, col):
+    """the two sticky-flag groups are what the device tests take them for: 24 rows; the yaw of the pings in kp7 column col (3 target, 0 source)
+    is small up to row 12, large at row 12, small on the next eight rows and large on the last three; and the oracle gives the eight small-yaw
+    rows behind the switch other bits in the full list than in the list that starts behind the switch -- loop closure and triangulation --
+    and the last three the same bits.  (Knife-edge rows of the groups: test_at_most_a_tenth_of_a_group_is_knife_edge.)"""
+    g = lc_cases(orc, 0)[name]
+    s, t, k = g["lists"][0]; sw = g["switch"]
+    assert len(k) == 24 and sw == 12
+    yaw = np.abs(g["frames"][t if col == 3 else s][0][k[:, col].astype(int), 2])
+    assert (yaw[:sw] < 2).all() and yaw[sw] > 2.2 and (yaw[sw + 1:sw + 9] < 2).all() and (yaw[sw + 9:] > 2.2).all()
+    lc, tri = refs[name][0]
+    tail = k[sw + 1:]
+    lc_t = lc_reference(orc, g["frames"], s, t, tail, key=(name, "tail")); tri_t = tri_reference(orc, g["frames"], s, t, tail, key=(name, "tail"))
+    for full, part in ((lc["lcs"][sw + 1:], lc_t["lcs"]), (tri["out"][sw + 1:], tri_t["out"])):
+        d = np.array([a.tobytes() != b.tobytes() for a, b in zip(full, part)])
+        assert d[:8].all() and not d[8:].any(), (name, d)
+    print("%-20s tail alone: knife-edge lc %d tri %d of %d" % (name, (~lc_t["stable"]).sum(), (~tri_t["stable"]).sum(), len(tail)))
+
+
+def test_long_flip_list(orc):
+    """helpers.lc_long_flip_list: 65 rows, the target's yaw large at row 63 only; the oracle's triangulation of row 64 in the list differs from
+    that of row 64 alone (the flag is sticky), and at most a tenth of the rows is knife-edge"""
+    g = lc_long_flip_list(orc)
+    s, t, k = g["list"]
+    assert len(k) == 65 and g["switch"] == 63
+    yaw = np.abs(g["frames"][t][0][k[:, 3].astype(int), 2])
+    assert (yaw[:63] < 2).all() and yaw[63] > 2.2 and yaw[64] < 2
+    ref = tri_reference(orc, g["frames"], s, t, k, key=("long-flip", 0))
+    last = tri_reference(orc, g["frames"], s, t, k[64:], key=("long-flip", "last"))
+    assert last["out"].tobytes() != ref["out"][64:].tobytes()
+    print("long-flip: knife-edge %d of 65" % (~ref["stable"]).sum())
+    assert (~ref["stable"]).sum() <= 6 and ref["stable"][64] and last["stable"][0]
 
 
 def test_selection_seam_case_reaches_every_seam(orc):
