@@ -11,6 +11,8 @@
 //     pg_front_diag4_kernel    L11 = chol(A11) in 4-column pivot blocks, their inverses Linv, y = L11^-1 b      one workgroup per panel
 //     pg_front_trsm2_kernel    L21 = A21 L11^-T, b2 -= L21 y                              one wavefront per 16 rows
 //     pg_front_syrk_kernel     A22 -= L21 L21^T                                           64 x 64 tiles of the trailing part
+//     pg_front_rsu_kernel      the two above fused per tile, on the levels with few tiles: the same helpers, hence the same bits
+//     pg_front_bwd_part_kernel partial sums of L21^T x2 for the tall panels
 //     pg_front_bwd2_kernel     x1 = L11^-T (y1 - L21^T x2)
 // all dense products on v_mfma_f64_16x16x4_f64.  What is left in F22 after the last panel is the front's update matrix.
 
@@ -77,25 +79,72 @@ __device__ inline double pg_readlane(double v, int lane)
     return __hiloint2double(hi, lo);
 }
 
+// one item of a level's panel list: the 96-column step it_step[item] of front it_front[item].  The helpers below take it BY VALUE: behind a
+// reference its fields stay loads until the helper is inlined, and rsu<64> came out with 140 more instructions and other guards.
+struct pg_panel {
+    pg_front fd;
+    int col0, n, p, ld;             // first column, columns (at most 96), global panel id (its Tinv blocks), leading dimension of the front
+    int row0, nrows;                // first row below the panel, rows below it
+};
+__device__ __forceinline__ pg_panel pg_panel_load(const pg_front* __restrict__ FD, const int* __restrict__ it_front, const int* __restrict__ it_step, int item)
+{
+    pg_panel P;
+    P.fd = FD[it_front[item]];
+    const int step = it_step[item];
+    P.col0 = 96 * step; P.n = min(96, P.fd.s6 - P.col0); P.p = P.fd.pan0 + step; P.ld = P.fd.ld;
+    P.row0 = P.col0 + P.n; P.nrows = P.fd.n6 - P.row0;
+    return P;
+}
+
+// ---- A22 -= L21 L21^T on rows i0 .. i0 + 15 of tile column tj of the trailing part (tiles of TS columns: TS / 16 blocks of 16 x 16), by
+// one wavefront: pg_strip_load brings the blocks of C in, pg_strip_update multiplies and stores.  K = the panel's 96 columns: 24
+// v_mfma_f64_16x16x4_f64 per block, B operands from the TS rows of L21 in LDS (sB, row stride PG_SYRK_LD), A operand ks = aop(ks):
+// -L21[i0 + (l & 15)][4 ks + (l >> 4)].  A is the front, `on` switches the whole load off (uniform per wavefront).
+#define PG_SYRK_LD 98
+template <int TS>
+__device__ __forceinline__ void pg_strip_load(pg_d4 (&acc)[TS / 16], const double* __restrict__ A, const pg_panel P, bool on, int i0, int tj, int l)
+{
+#pragma unroll
+    for (int c = 0; c < TS / 16; ++c) {
+        const int j0 = TS * tj + 16 * c, jr = j0 + (l & 15);
+        const double* __restrict__ Cp = A + (size_t)(P.row0 + i0 + (l >> 4)) * P.ld + P.row0 + j0 + (l & 15);
+#pragma unroll
+        for (int v = 0; v < 4; ++v) acc[c][v] = (on && i0 < P.nrows && j0 <= i0 + 15 && i0 + (l >> 4) + 4 * v < P.nrows && jr < P.nrows) ? Cp[(size_t)(4 * v) * P.ld] : 0.0;
+    }
+}
+template <int TS, typename AOP>
+__device__ __forceinline__ void pg_strip_update(const pg_d4 (&acc)[TS / 16], AOP aop, const double* sB, double* __restrict__ A, const pg_panel P, int i0, int tj, int l)
+{
+#pragma unroll
+    for (int c = 0; c < TS / 16; ++c) {
+        const int j0 = TS * tj + 16 * c;
+        if (j0 >= P.nrows || j0 > i0 + 15) break;            // beyond the front, or entirely above the diagonal (uniform per wavefront)
+        const int jr = j0 + (l & 15);
+        const double* __restrict__ sb = sB + (16 * c + (l & 15)) * PG_SYRK_LD + (l >> 4);
+        double* __restrict__ Cp = A + (size_t)(P.row0 + i0 + (l >> 4)) * P.ld + P.row0 + j0 + (l & 15);
+        pg_d4 r = acc[c];
+#pragma unroll
+        for (int ks = 0; ks < 24; ++ks) r = __builtin_amdgcn_mfma_f64_16x16x4f64(aop(ks), sb[4 * ks], r, 0, 0, 0);
+#pragma unroll
+        for (int v = 0; v < 4; ++v) if (i0 + (l >> 4) + 4 * v < P.nrows && jr < P.nrows) Cp[(size_t)(4 * v) * P.ld] = r[v];
+    }
+}
+
 // A22 -= L21 L21^T on the trailing part of the front (rows and columns beyond the panel): one workgroup per 64 x 64 tile of
 // the lower triangle (exact tile list from the host), one wavefront per 16 rows of the tile.  The 64 rows of L21 that form the
 // tile's COLUMNS are staged once in LDS (coalesced 16-byte loads, conflict-free row stride) and serve all four wavefronts
-// as MFMA B operands; every wavefront keeps its own 16 x 96 slab of L21 in 24 A-operand registers.  K = the panel's 96
-// columns: 24 v_mfma_f64_16x16x4_f64 per 16 x 16 block.
-#define PG_SYRK_LD 98
+// as MFMA B operands; every wavefront keeps its own 16 x 96 slab of L21 in 24 A-operand registers.
 __global__ __launch_bounds__(256) void pg_front_syrk_kernel(const int* __restrict__ it_front, const int* __restrict__ it_step, const pg_front* __restrict__ FD,
                                                             const int* __restrict__ tile_item, const int* __restrict__ tile_ij, double* __restrict__ F)
 {
     __shared__ double sB[64 * PG_SYRK_LD];
-    const int item = tile_item[blockIdx.x], ij = tile_ij[blockIdx.x], ti = ij >> 16, tj = ij & 0xffff;
-    const pg_front fd = FD[it_front[item]];
-    const int step = it_step[item], col0 = 96 * step;
-    const int n = min(96, fd.s6 - col0), ld = fd.ld;
-    const int row0 = col0 + n, nrows = fd.n6 - row0;
+    const int ij = tile_ij[blockIdx.x], ti = ij >> 16, tj = ij & 0xffff;
+    const pg_panel P = pg_panel_load(FD, it_front, it_step, tile_item[blockIdx.x]);
+    const int n = P.n, ld = P.ld, nrows = P.nrows;
     const int wave = threadIdx.x >> 6, l = threadIdx.x & 63;
-    double* __restrict__ A = F + fd.off;
+    double* __restrict__ A = F + P.fd.off;
     {   // rows 64 tj .. 64 tj + 63 of L21 -> LDS, 48 x 16 bytes per row (ld and col0 are multiples of 16 scalars, rows 16-byte aligned)
-        const double2* __restrict__ src = reinterpret_cast<const double2*>(A + (size_t)(row0 + 64 * tj) * ld + col0);
+        const double2* __restrict__ src = reinterpret_cast<const double2*>(A + (size_t)(P.row0 + 64 * tj) * ld + P.col0);
         const int ld2 = ld >> 1, n2 = n >> 1, rows_here = min(64, nrows - 64 * tj);
         double2 v[12];
 #pragma unroll
@@ -114,35 +163,17 @@ __global__ __launch_bounds__(256) void pg_front_syrk_kernel(const int* __restric
     double a[24];
     pg_d4 acc[4];
     {
-        const double* __restrict__ Ai = A + (size_t)(row0 + min(ir, nrows - 1)) * ld + col0;
+        const double* __restrict__ Ai = A + (size_t)(P.row0 + min(ir, nrows - 1)) * ld + P.col0;
 #pragma unroll
-        for (int ks = 0; ks < 24; ++ks) { const int k = 4 * ks + (l >> 4); a[ks] = (ir < nrows && k < n) ? Ai[k] : 0.0; }      // (the sign further down: negated inside the conditional, every one of the 24 loads waited for its own round trip -- s_waitcnt vmcnt(0) after each)
+        for (int ks = 0; ks < 24; ++ks) { const int k = 4 * ks + (l >> 4); a[ks] = (ir < nrows && k < n) ? Ai[k] : 0.0; }      // negated below, after all 24 loads are issued: a negation here makes each load wait for its own round trip
         // the four 16 x 16 blocks of C this wavefront updates come in with the operands: one round trip to memory, not five
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const int j0 = 64 * tj + 16 * c, jr = j0 + (l & 15);
-            const double* __restrict__ Cp = A + (size_t)(row0 + i0 + (l >> 4)) * ld + row0 + j0 + (l & 15);
-#pragma unroll
-            for (int v = 0; v < 4; ++v) acc[c][v] = (i0 < nrows && j0 <= i0 + 15 && i0 + (l >> 4) + 4 * v < nrows && jr < nrows) ? Cp[(size_t)(4 * v) * ld] : 0.0;
-        }
+        pg_strip_load<64>(acc, A, P, true, i0, tj, l);
     }
 #pragma unroll
     for (int ks = 0; ks < 24; ++ks) a[ks] = -a[ks];
     __syncthreads();
     if (i0 >= nrows) return;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const int j0 = 64 * tj + 16 * c;
-        if (j0 >= nrows || j0 > i0 + 15) break;              // beyond the front, or entirely above the diagonal (uniform per wavefront)
-        const int jr = j0 + (l & 15);
-        const double* __restrict__ sb = sB + (16 * c + (l & 15)) * PG_SYRK_LD + (l >> 4);
-        double* __restrict__ Cp = A + (size_t)(row0 + i0 + (l >> 4)) * ld + row0 + j0 + (l & 15);
-        pg_d4 r = acc[c];
-#pragma unroll
-        for (int ks = 0; ks < 24; ++ks) r = __builtin_amdgcn_mfma_f64_16x16x4f64(a[ks], sb[4 * ks], r, 0, 0, 0);
-#pragma unroll
-        for (int v = 0; v < 4; ++v) if (i0 + (l >> 4) + 4 * v < nrows && jr < nrows) Cp[(size_t)(4 * v) * ld] = r[v];
-    }
+    pg_strip_update<64>(acc, [&](int ks) { return a[ks]; }, sB, A, P, i0, tj, l);
 }
 
 // ---- panel kernels without an explicit inverse: the 96 x 96 panel lives in registers as 16 x 16
@@ -157,39 +188,10 @@ __global__ __launch_bounds__(256) void pg_front_syrk_kernel(const int* __restric
 // No explicit L11^-1: the kernels below the panel (row solve, back-substitution) repeat the same 4-column
 // steps with the stored Linv blocks.  The right-hand side rides along as row 96 of the matrix (tile row 6): the Cholesky factor
 // of the augmented matrix carries y = L11^-1 b in that row.
-__device__ inline double pg_rsqrt(double x)
-{
-    double r = __builtin_amdgcn_rsq(x);            // v_rsq_f64 seed, two Newton steps
-    r = r * (1.5 - 0.5 * x * r * r);
-    r = r * (1.5 - 0.5 * x * r * r);
-    return r;
-}
-// Cholesky of the 4 x 4 block m (lower, row-major 10 values m00 m10 m11 m20 m21 m22 m30 m31 m32 m33) and the inverse of its
-// factor: li = [i00 i10 i11 i20 i21 i22 i30 i31 i32 i33]
-__device__ inline int pg_chol4_inv(const double* m, double* li)
-{
-    int bad = 0;
-    double d0 = m[0]; if (!(d0 > 0) || !isfinite(d0)) { bad = 1; d0 = 1.0; }
-    const double r0 = pg_rsqrt(d0);
-    const double l10 = m[1] * r0, l20 = m[3] * r0, l30 = m[6] * r0;
-    double d1 = m[2] - l10 * l10; if (!(d1 > 0) || !isfinite(d1)) { bad = 1; d1 = 1.0; }
-    const double r1 = pg_rsqrt(d1);
-    const double l21 = (m[4] - l20 * l10) * r1, l31 = (m[7] - l30 * l10) * r1;
-    double d2 = m[5] - l20 * l20 - l21 * l21; if (!(d2 > 0) || !isfinite(d2)) { bad = 1; d2 = 1.0; }
-    const double r2 = pg_rsqrt(d2);
-    const double l32 = (m[8] - l30 * l20 - l31 * l21) * r2;
-    double d3 = m[9] - l30 * l30 - l31 * l31 - l32 * l32; if (!(d3 > 0) || !isfinite(d3)) { bad = 1; d3 = 1.0; }
-    const double r3 = pg_rsqrt(d3);
-    li[0] = r0; li[2] = r1; li[5] = r2; li[9] = r3;
-    li[1] = -(l10 * r0) * r1;
-    li[3] = -(l20 * r0 + l21 * li[1]) * r2; li[4] = -(l21 * r1) * r2;
-    li[6] = -(l30 * r0 + l31 * li[1] + l32 * li[3]) * r3; li[7] = -(l31 * r1 + l32 * li[4]) * r3; li[8] = -(l32 * r2) * r3;
-    return bad;
-}
 // workgroup barrier that orders LDS traffic only (__syncthreads() also waits for the global stores in flight)
 #define PG_LDS_BARRIER() do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory"); } while (0)
 // ---- The panel factorisation on FOUR wavefronts (tile column I = tile row I of the matrix belongs to wavefront I mod 4: at most nine tiles
-// and a quarter of the updates each), as a PIPELINE.  The plain form (rounds 1 - 4, removed in round 5: per 4-column block the pivot
+// and a quarter of the updates each), as a PIPELINE.  The plain form (per 4-column block the pivot
 // wavefront's Cholesky + inverse -> barrier -> LP of every tile column -> barrier -> updates) costs two workgroup barriers
 // and two LDS round trips on the one chain that matters: pivot block -> Cholesky + inverse -> LP of the pivot tile -> update of the
 // pivot tile -> next pivot block (1 950 cycles per block, 870 of them the Cholesky).  Here the owner of the pivot tile runs that
@@ -202,7 +204,7 @@ __device__ inline int pg_chol4_inv(const double* m, double* li)
 // When the pivot tile changes, its new owner catches up on the one update it trails by (again from its own registers).
 // U and L of a region do not feed C, so the compiler is free to fill the Cholesky's dependency bubbles with their matrix-core
 // work.  The tile count NT = ceil(n / 16) is a template parameter: straight-line code, no runtime guards inside the pipeline.
-// Every tile receives the same updates in the same order as in the two-barrier form: the result was bit-identical to it.
+// Every tile receives the same updates in the same order as in the plain form.
 struct pg_d4_lds { double lp[3][7][64]; double li[2][16]; int bad; };
 // The trailing work of region R on wavefront W, as a compile-time list of matrix-core operations: kind 1 = update U(R - 2) of tile
 // (T2, I), kind 2 = LP of block R - 1 for tile column I (with the catch-up update when I becomes the pivot tile), 0 = end of list.
@@ -239,30 +241,27 @@ constexpr pg_lag_desc pg_lag_get(int W, int NT, int R, int want)
     }
     return { 0, 0, 0 };
 }
+// the tiles of a wavefront's tile column: S0 for the first (I = W), S1 for the second (I = W + 4)
+template <bool FIRST, typename TS0, typename TS1>
+__device__ __forceinline__ auto& pg_d4_tiles(TS0& S0, TS1& S1)
+{
+    if constexpr (FIRST) return S0; else return S1;
+}
 template <int W, int NT, int R, int IDX, typename TS0, typename TS1>
 __device__ __forceinline__ void pg_d4_lag_one(pg_d4_lds& sh, TS0& S0, TS1& S1, const double* aop, double B0, double B1, double lopL, int l)
 {
     constexpr pg_lag_desc d = pg_lag_get(W, NT, R, IDX);
-    constexpr int I0 = W;
+    auto& S = pg_d4_tiles<d.I == W>(S0, S1);
     if constexpr (d.kind == 1) {
-        if constexpr (d.I == I0) S0[d.T2] = __builtin_amdgcn_mfma_f64_16x16x4f64(aop[d.T2], B0, S0[d.T2], 0, 0, 0);
-        else S1[d.T2] = __builtin_amdgcn_mfma_f64_16x16x4f64(aop[d.T2], B1, S1[d.T2], 0, 0, 0);
+        S[d.T2] = __builtin_amdgcn_mfma_f64_16x16x4f64(aop[d.T2], d.I == W ? B0 : B1, S[d.T2], 0, 0, 0);
     } else if constexpr (d.kind == 2) {
         constexpr int k = R - 1, t = k / 4, b = k % 4, rb = k % 3;
         const pg_d4 zero4 = { 0.0, 0.0, 0.0, 0.0 };
-        if constexpr (d.I == I0) {
-            const pg_d4 r4 = __builtin_amdgcn_mfma_f64_16x16x4f64(lopL, S0[t][b], zero4, 0, 0, 0);
-            const double v = r4[0];
-            S0[t][b] = v;
-            sh.lp[rb][d.I][l] = v;
-            if constexpr (b == 3 && d.I == t + 1 && d.I < NT) S0[d.I] = __builtin_amdgcn_mfma_f64_16x16x4f64(-v, v, S0[d.I], 0, 0, 0);      // next pivot tile: its update of block k now
-        } else {
-            const pg_d4 r4 = __builtin_amdgcn_mfma_f64_16x16x4f64(lopL, S1[t][b], zero4, 0, 0, 0);
-            const double v = r4[0];
-            S1[t][b] = v;
-            sh.lp[rb][d.I][l] = v;
-            if constexpr (b == 3 && d.I == t + 1 && d.I < NT) S1[d.I] = __builtin_amdgcn_mfma_f64_16x16x4f64(-v, v, S1[d.I], 0, 0, 0);
-        }
+        const pg_d4 r4 = __builtin_amdgcn_mfma_f64_16x16x4f64(lopL, S[t][b], zero4, 0, 0, 0);
+        const double v = r4[0];
+        S[t][b] = v;
+        sh.lp[rb][d.I][l] = v;
+        if constexpr (b == 3 && d.I == t + 1 && d.I < NT) S[d.I] = __builtin_amdgcn_mfma_f64_16x16x4f64(-v, v, S[d.I], 0, 0, 0);      // next pivot tile: its update of block k now
     }
 }
 template <int W, int NT, int R, int LO, int HI, typename TS0, typename TS1>
@@ -300,9 +299,9 @@ __device__ __forceinline__ void pg_d4_region(pg_d4_lds& sh, TS0& S0, TS1& S1, do
     // instructions (a wavefront issues in order: a product placed there costs an issue slot, its 64 cycles run beside the chain)
     if constexpr (piv_now) {
         constexpr int t = R / 4, b = R % 4, rb = R % 3;
+        auto& S = pg_d4_tiles<(t < 4)>(S0, S1);                          // the pivot tile's column is this wavefront's first (t = W) or second (t = W + 4)
         double m[10], li[10];
-        double dv;
-        if constexpr (t < 4) dv = S0[t][b]; else dv = S1[t][b];
+        const double dv = S[t][b];
         {
             int e = 0;
 #pragma unroll
@@ -314,7 +313,8 @@ __device__ __forceinline__ void pg_d4_region(pg_d4_lds& sh, TS0& S0, TS1& S1, do
 // that neither the optimiser nor the scheduler can lift the product above this point of the chain
 #define PG_SLOT(i, cv) do { if constexpr (steady) { asm volatile("" : "+v"(B0), "+v"(B1), "+v"(lopL) : "v"(cv)); pg_d4_lag<W, NT, R, (i), (i) + 1>(sh, S0, S1, aop, B0, B1, lopL, l); } } while (0)
 #define PG_RSQ(x, rv, s0) do { rv = __builtin_amdgcn_rsq(x); PG_SLOT(s0, rv); rv = rv * (1.5 - 0.5 * x * rv * rv); PG_SLOT((s0) + 1, rv); rv = rv * (1.5 - 0.5 * x * rv * rv); } while (0)
-        {   // pg_chol4_inv with the slots
+        {   // Cholesky of the 4 x 4 block m (lower, row-major 10 values m00 m10 m11 m20 m21 m22 m30 m31 m32 m33) and the inverse of its
+            // factor: li = [i00 i10 i11 i20 i21 i22 i30 i31 i32 i33]; 1 / sqrt by PG_RSQ: v_rsq_f64 seed, two Newton steps
             double d0 = m[0]; if (!(d0 > 0) || !isfinite(d0)) { bad = 1; d0 = 1.0; }
             double r0, r1, r2, r3;
             PG_RSQ(d0, r0, 0);
@@ -350,23 +350,13 @@ __device__ __forceinline__ void pg_d4_region(pg_d4_lds& sh, TS0& S0, TS1& S1, do
         const double lop = j < 4 ? sh.li[R & 1][j * 4 + q] : 0.0;      // A operand of Linv x P^T: lane (i, m) = Linv[i][m]
         const int rj = j - 4 * b;
         const pg_d4 zero4 = { 0.0, 0.0, 0.0, 0.0 };
-        if constexpr (t < 4) {
-            const pg_d4 r4 = __builtin_amdgcn_mfma_f64_16x16x4f64(lop, S0[t][b], zero4, 0, 0, 0);
-            double v = r4[0];
-            if (rj < 0 || (rj < 4 && q > rj)) v = 0.0;               // rows above the block; zeros of L44
-            S0[t][b] = v;
-            sh.lp[rb][t][l] = v;
-            const double a = j < 4 * b + 4 ? 0.0 : -v;               // only the rows below the pivot block are updated
-            S0[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, v, S0[t], 0, 0, 0);
-        } else {
-            const pg_d4 r4 = __builtin_amdgcn_mfma_f64_16x16x4f64(lop, S1[t][b], zero4, 0, 0, 0);
-            double v = r4[0];
-            if (rj < 0 || (rj < 4 && q > rj)) v = 0.0;
-            S1[t][b] = v;
-            sh.lp[rb][t][l] = v;
-            const double a = j < 4 * b + 4 ? 0.0 : -v;
-            S1[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, v, S1[t], 0, 0, 0);
-        }
+        const pg_d4 r4 = __builtin_amdgcn_mfma_f64_16x16x4f64(lop, S[t][b], zero4, 0, 0, 0);
+        double v = r4[0];
+        if (rj < 0 || (rj < 4 && q > rj)) v = 0.0;                   // rows above the block; zeros of L44
+        S[t][b] = v;
+        sh.lp[rb][t][l] = v;
+        const double a = j < 4 * b + 4 ? 0.0 : -v;                   // only the rows below the pivot block are updated
+        S[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, v, S[t], 0, 0, 0);
     }
     if constexpr (piv_now) {                 // Linv for the kernels below the panel, off the chain
         if (l < 16) tout[(4 * (R / 4) + (R % 4)) * 16 + l] = sh.li[R & 1][l];
@@ -442,12 +432,11 @@ __global__ __launch_bounds__(256) void pg_front_diag4_kernel(const int* __restri
                                                              double* __restrict__ F, double* __restrict__ R, int* __restrict__ fail, double* __restrict__ Tinv)
 {
     __shared__ pg_d4_lds sh;
-    const pg_front fd = FD[it_front[blockIdx.x]];
-    const int step = it_step[blockIdx.x], col0 = 96 * step;
-    const int n = min(96, fd.s6 - col0), p = fd.pan0 + step, ld = fd.ld;
-    double* __restrict__ A = F + fd.off + (size_t)col0 * ld + col0;
-    double* __restrict__ rr = R + fd.roff + col0;
-    double* __restrict__ tout = Tinv + (size_t)p * PG_NB4 * 16;
+    const pg_panel P = pg_panel_load(FD, it_front, it_step, blockIdx.x);
+    const int n = P.n, ld = P.ld;
+    double* __restrict__ A = F + P.fd.off + (size_t)P.col0 * ld + P.col0;
+    double* __restrict__ rr = R + P.fd.roff + P.col0;
+    double* __restrict__ tout = Tinv + (size_t)P.p * PG_NB4 * 16;
     const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
     if (threadIdx.x == 0) sh.bad = 0;
     if (threadIdx.x < 32) sh.li[threadIdx.x >> 4][threadIdx.x & 15] = 0.0;     // the zeros above the diagonal of Linv stay
@@ -464,42 +453,30 @@ __global__ __launch_bounds__(256) void pg_front_diag4_kernel(const int* __restri
     if (sh.bad && threadIdx.x == 0) *fail = 1;
 }
 
-// L21 = A21 L11^-T for a slab of 16 rows per wavefront, by the same 4-column steps: LP = P Linv^T (three shuffles), then the
-// later columns of the slab lose LP L11[later rows][pivot columns]^T (one MFMA per 16 columns, A operand straight from L11).
-// Forward substitution rides along: b2 -= L21 y.
+// ---- The row solve L21 = A21 L11^-T, b2 -= L21 y on a slab of 16 rows per wavefront, in three parts that pg_front_trsm2_kernel and
+// pg_front_rsu_kernel share: staging of the panel, the 4-column steps, the forward-substitution tail.
 #define PG_T2_LD 97
-__global__ __launch_bounds__(256) void pg_front_trsm2_kernel(const int* __restrict__ it_front, const int* __restrict__ it_step, const pg_front* __restrict__ FD,
-                                                             double* __restrict__ F, double* __restrict__ R, const double* __restrict__ Tinv)
+// the panel -> LDS, by a workgroup of NTH threads: sL = L11 (lower triangle, row stride PG_T2_LD), the A operands of every update;
+// sT = its 4 x 4 inverse blocks; sY = its y.  L11 goes global -> registers -> LDS: all its loads are in flight before the first store.
+template <int NTH>
+__device__ __forceinline__ void pg_stage_panel(const pg_panel P, const double* __restrict__ F, const double* __restrict__ R, const double* __restrict__ Tinv,
+                                               double* sL, double* sT, double* sY)
 {
-    __shared__ double sL[(PG_PW * 6) * PG_T2_LD];      // L11 of the panel (lower triangle), the A operands of every update
-    __shared__ double sT[PG_NB4 * 16];                 // the 4 x 4 inverse blocks
-    __shared__ double sY[PG_PW * 6];
-    const pg_front fd = FD[it_front[blockIdx.x]];
-    const int step = it_step[blockIdx.x], col0 = 96 * step;
-    const int n = min(96, fd.s6 - col0), p = fd.pan0 + step, ld = fd.ld;
-    const int row0 = col0 + n, nrows = fd.n6 - row0;
-    if ((int)blockIdx.y * 64 >= nrows) return;     // workgroup-uniform
-    const int l = threadIdx.x & 63, c = l & 15, q = l >> 4;
-    const int rowbase = ((int)blockIdx.y * 4 + (int)(threadIdx.x >> 6)) * 16;
-    const bool rok = rowbase + c < nrows;
-    double* __restrict__ Arow = F + fd.off + (size_t)(row0 + min(max(rowbase + c, 0), nrows - 1)) * ld + col0;
-    pg_d4 S[6];                                    // the slab's own rows are requested first: their latency hides behind the staging of L11
+    const double* __restrict__ L11 = F + P.fd.off + (size_t)P.col0 * P.ld + P.col0;
+    constexpr int NE = 96 * 96 / NTH;
+    double v[NE];
 #pragma unroll
-    for (int T = 0; T < 6; ++T)
+    for (int e = 0; e < NE; ++e) { const int id = e * NTH + threadIdx.x, r = id / 96, cc = id - 96 * r; v[e] = (r < P.n && cc <= r) ? L11[(size_t)r * P.ld + cc] : 0.0; }
 #pragma unroll
-        for (int v = 0; v < 4; ++v) { const int col = 16 * T + q + 4 * v; S[T][v] = (rok && col < n) ? Arow[col] : 0.0; }
-    {
-        const double* __restrict__ L11 = F + fd.off + (size_t)col0 * ld + col0;
-        double v[36];
-#pragma unroll
-        for (int e = 0; e < 36; ++e) { const int id = e * 256 + threadIdx.x, r = id / 96, cc = id - 96 * r; v[e] = (r < n && cc <= r) ? L11[(size_t)r * ld + cc] : 0.0; }
-#pragma unroll
-        for (int e = 0; e < 36; ++e) { const int id = e * 256 + threadIdx.x, r = id / 96, cc = id - 96 * r; sL[r * PG_T2_LD + cc] = v[e]; }
-        for (int e = threadIdx.x; e < PG_NB4 * 16; e += 256) sT[e] = Tinv[(size_t)p * PG_NB4 * 16 + e];
-        if (threadIdx.x < 96) sY[threadIdx.x] = (int)threadIdx.x < n ? R[fd.roff + col0 + threadIdx.x] : 0.0;
-    }
-    __syncthreads();
-    if (rowbase >= nrows) return;                  // wavefront-uniform
+    for (int e = 0; e < NE; ++e) { const int id = e * NTH + threadIdx.x, r = id / 96, cc = id - 96 * r; sL[r * PG_T2_LD + cc] = v[e]; }
+    for (int e = threadIdx.x; e < PG_NB4 * 16; e += NTH) sT[e] = Tinv[(size_t)P.p * PG_NB4 * 16 + e];
+    if (threadIdx.x < 96) sY[threadIdx.x] = (int)threadIdx.x < P.n ? R[P.fd.roff + P.col0 + threadIdx.x] : 0.0;
+}
+// the slab S (tile T, register v of lane (c, q) = row c, column 16 T + q + 4 v) by the 4-column steps of the panel kernel: LP = P Linv^T
+// through the matrix core, then the later columns of the slab lose LP L11[later rows][pivot columns]^T (one MFMA per 16 columns, A
+// operand straight from L11).
+__device__ __forceinline__ void pg_rowsolve_steps(pg_d4 (&S)[6], const double* sL, const double* sT, int n, int c, int q)
+{
     // The operands of a 4-column step do not depend on the step before: they are read from LDS one step ahead, so that the matrix
     // core never waits for an LDS round trip between two dependent products (it did, 130 cycles per product).
     double lop_n, a_n[6];
@@ -523,7 +500,6 @@ __global__ __launch_bounds__(256) void pg_front_trsm2_kernel(const int* __restri
 #pragma unroll
             for (int T2 = 0; T2 < 6; ++T2) a[T2] = a_n[T2];
             if (b < 3) fetch(t, b + 1); else if (t < 5) fetch(t + 1, 0);
-            // LP = P Linv^T through the matrix core (see pg_front_diag2_kernel)
             const pg_d4 zero4 = { 0.0, 0.0, 0.0, 0.0 };
             const pg_d4 r4 = __builtin_amdgcn_mfma_f64_16x16x4f64(lop, S[t][b], zero4, 0, 0, 0);
             const double LP = r4[0];
@@ -532,29 +508,62 @@ __global__ __launch_bounds__(256) void pg_front_trsm2_kernel(const int* __restri
             for (int T2 = t; T2 < 6; ++T2) S[T2] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[T2], LP, S[T2], 0, 0, 0);
         }
     }
+}
+// the solved slab's L21 rows go to Lrow (this lane's row, at the panel's first column; stored where rok) and their share of the forward
+// substitution leaves the right-hand side: Rslab[c] -= L21[row c] . y, Rslab = the right-hand side at the slab's first row
+__device__ __forceinline__ void pg_rowsolve_tail(const pg_d4 (&S)[6], const double* sY, int n, int l, bool rok, double* __restrict__ Lrow, double* __restrict__ Rslab)
+{
+    const int c = l & 15, q = l >> 4;
     double dot = 0;
 #pragma unroll
     for (int T = 0; T < 6; ++T)
 #pragma unroll
         for (int v = 0; v < 4; ++v) {
             const int col = 16 * T + q + 4 * v;
-            if (col < n) { if (rok) Arow[col] = S[T][v]; dot += S[T][v] * sY[col]; }
+            if (col < n) { if (rok) Lrow[col] = S[T][v]; dot += S[T][v] * sY[col]; }
         }
     dot += __shfl_xor(dot, 16, 64);
     dot += __shfl_xor(dot, 32, 64);
-    if (l < 16 && rok) R[fd.roff + row0 + rowbase + c] -= dot;
+    if (l < 16 && rok) Rslab[c] -= dot;
+}
+
+// L21 = A21 L11^-T in place, one wavefront per 16 rows; forward substitution rides along: b2 -= L21 y.
+__global__ __launch_bounds__(256) void pg_front_trsm2_kernel(const int* __restrict__ it_front, const int* __restrict__ it_step, const pg_front* __restrict__ FD,
+                                                             double* __restrict__ F, double* __restrict__ R, const double* __restrict__ Tinv)
+{
+    __shared__ double sL[(PG_PW * 6) * PG_T2_LD];
+    __shared__ double sT[PG_NB4 * 16];
+    __shared__ double sY[PG_PW * 6];
+    const pg_panel P = pg_panel_load(FD, it_front, it_step, blockIdx.x);
+    const int n = P.n, nrows = P.nrows;
+    if ((int)blockIdx.y * 64 >= nrows) return;     // workgroup-uniform
+    const int l = threadIdx.x & 63, c = l & 15, q = l >> 4;
+    const int rowbase = ((int)blockIdx.y * 4 + (int)(threadIdx.x >> 6)) * 16;
+    const bool rok = rowbase + c < nrows;
+    double* __restrict__ Arow = F + P.fd.off + (size_t)(P.row0 + min(max(rowbase + c, 0), nrows - 1)) * P.ld + P.col0;
+    pg_d4 S[6];                                    // the slab's own rows are requested first: their latency hides behind the staging of L11
+#pragma unroll
+    for (int T = 0; T < 6; ++T)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) { const int col = 16 * T + q + 4 * v; S[T][v] = (rok && col < n) ? Arow[col] : 0.0; }
+    pg_stage_panel<256>(P, F, R, Tinv, sL, sT, sY);
+    __syncthreads();
+    if (rowbase >= nrows) return;                  // wavefront-uniform
+    pg_rowsolve_steps(S, sL, sT, n, c, q);
+    pg_rowsolve_tail(S, sY, n, l, rok, Arow, R + P.fd.roff + P.row0 + rowbase);
 }
 
 // ---- Row solve and trailing update FUSED per 64 x 64 tile (levels with at most PG_RSU_MAX_TILES tiles: every level but the few at the
 // bottom of the front tree).  pg_front_trsm2_kernel followed by pg_front_syrk_kernel costs two dependent launches per level, each with
 // its ~10 us floor (arrival of the data the previous kernel wrote, prologue, strided stores), for a few microseconds of products.
 // Here the workgroup of tile (ti, tj) solves BOTH row chunks it needs itself -- wavefronts 0..3 chunk ti (kept in registers: the tile
-// registers ARE the A operands of the update), wavefronts 4..7 chunk tj (into LDS, the B operands) -- by the very steps of
-// pg_front_trsm2_kernel, then updates the tile by the steps of pg_front_syrk_kernel: the same products in the same order, bit for bit.
+// registers ARE the A operands of the update), wavefronts 4..7 chunk tj (into LDS, the B operands) -- through pg_rowsolve_steps, then
+// updates the tile through pg_strip_update: the code of the two separate kernels, hence the same products in the same order, bit for bit
+// (a front walks through all three forms as it shrinks).
 // A chunk is solved once per tile that needs it (redundant flops on idle matrix cores); the diagonal tile (ti, ti) of a chunk stores
 // its L21 rows and folds them into the right-hand side.  L21 goes to a SECOND front arena (FL): the tiles of a level run concurrently
-// and read A21 in place, which an in-place store would pull from under them (the race that stopped round 2's version of this).
-// TS = 64: the tile list of the level as it is (512 threads).  TS = 32 (round 4): every 64 x 64 tile of the list is cut into its (up to) four
+// and read A21 in place, which an in-place store would pull from under them.
+// TS = 64: the tile list of the level as it is (512 threads).  TS = 32: every 64 x 64 tile of the list is cut into its (up to) four
 // 32 x 32 quarters, one workgroup of 256 threads each (blockIdx & 3 = quarter; the quarters above the diagonal or beyond the front leave at
 // once).  On the levels near the root a launch holds a handful of tiles on a 256-CU chip, and what a workgroup costs there is what ONE
 // compute unit can pull and multiply: in-kernel variants with parts switched off put the fused kernel at 6.4 us (empty launch, with the
@@ -567,17 +576,15 @@ __global__ __launch_bounds__(TS * 8) void pg_front_rsu_kernel(const int* __restr
                                                               double* __restrict__ F, double* __restrict__ FL, double* __restrict__ R, const double* __restrict__ Tinv)
 {
     constexpr int NW = TS / 16, NTH = TS * 8;          // wavefronts per chunk, threads
-    __shared__ double sL[(PG_PW * 6) * PG_T2_LD];      // L11 of the panel (lower triangle), the A operands of every solve step
-    __shared__ double sT[PG_NB4 * 16];                 // the 4 x 4 inverse blocks
+    __shared__ double sL[(PG_PW * 6) * PG_T2_LD];
+    __shared__ double sT[PG_NB4 * 16];
     __shared__ double sY[PG_PW * 6];
     __shared__ double sB[TS * PG_SYRK_LD];             // solved chunk tj: the B operands of the update
     const int tix = TS == 64 ? (int)blockIdx.x : (int)(blockIdx.x >> 2);
-    const int item = tile_item[tix], ij = tile_ij[tix];
+    const int ij = tile_ij[tix];
     int ti = ij >> 16, tj = ij & 0xffff;
-    const pg_front fd = FD[it_front[item]];
-    const int step = it_step[item], col0 = 96 * step;
-    const int n = min(96, fd.s6 - col0), p = fd.pan0 + step, ld = fd.ld;
-    const int row0 = col0 + n, nrows = fd.n6 - row0;
+    const pg_panel P = pg_panel_load(FD, it_front, it_step, tile_item[tix]);
+    const int n = P.n, nrows = P.nrows;
     if (TS == 32) {
         const int sub = blockIdx.x & 3;
         ti = 2 * ti + (sub >> 1); tj = 2 * tj + (sub & 1);
@@ -590,8 +597,8 @@ __global__ __launch_bounds__(TS * 8) void pg_front_rsu_kernel(const int* __restr
     const int rowbase = ((grp_i ? ti : tj) * NW + w4) * 16;
     const bool rok = rowbase + c < nrows;
     const bool solve = grp_i || !diag;                 // on a diagonal tile the second group has nothing to solve
-    double* __restrict__ A = F + fd.off;
-    const double* __restrict__ Arow = A + (size_t)(row0 + min(max(rowbase + c, 0), nrows - 1)) * ld + col0;
+    double* __restrict__ A = F + P.fd.off;
+    const double* __restrict__ Arow = A + (size_t)(P.row0 + min(max(rowbase + c, 0), nrows - 1)) * P.ld + P.col0;
     pg_d4 S[6];                                        // the slab's own rows are requested first: their latency hides behind the staging of L11
 #pragma unroll
     for (int T = 0; T < 6; ++T)
@@ -600,55 +607,10 @@ __global__ __launch_bounds__(TS * 8) void pg_front_rsu_kernel(const int* __restr
     // the tile of C this wavefront updates comes in with the operands too (first group only)
     const int i0 = TS * ti + 16 * w4;
     pg_d4 acc[NW];
-#pragma unroll
-    for (int cb = 0; cb < NW; ++cb) {
-        const int j0 = TS * tj + 16 * cb, jr = j0 + (l & 15);
-        const double* __restrict__ Cp = A + (size_t)(row0 + i0 + (l >> 4)) * ld + row0 + j0 + (l & 15);
-#pragma unroll
-        for (int v = 0; v < 4; ++v) acc[cb][v] = (grp_i && i0 < nrows && j0 <= i0 + 15 && i0 + (l >> 4) + 4 * v < nrows && jr < nrows) ? Cp[(size_t)(4 * v) * ld] : 0.0;
-    }
-    {
-        const double* __restrict__ L11 = A + (size_t)col0 * ld + col0;
-        constexpr int NE = 96 * 96 / NTH;
-        double v[NE];
-#pragma unroll
-        for (int e = 0; e < NE; ++e) { const int id = e * NTH + threadIdx.x, r = id / 96, cc = id - 96 * r; v[e] = (r < n && cc <= r) ? L11[(size_t)r * ld + cc] : 0.0; }
-#pragma unroll
-        for (int e = 0; e < NE; ++e) { const int id = e * NTH + threadIdx.x, r = id / 96, cc = id - 96 * r; sL[r * PG_T2_LD + cc] = v[e]; }
-        for (int e = threadIdx.x; e < PG_NB4 * 16; e += NTH) sT[e] = Tinv[(size_t)p * PG_NB4 * 16 + e];
-        if (threadIdx.x < 96) sY[threadIdx.x] = (int)threadIdx.x < n ? R[fd.roff + col0 + threadIdx.x] : 0.0;
-    }
+    pg_strip_load<TS>(acc, A, P, grp_i, i0, tj, l);
+    pg_stage_panel<NTH>(P, F, R, Tinv, sL, sT, sY);
     __syncthreads();
-    if (solve && rowbase < nrows) {                    // wavefront-uniform: the 4-column steps of pg_front_trsm2_kernel
-        double lop_n, a_n[6];
-        auto fetch = [&](int t, int b) {
-            lop_n = c < 4 ? sT[(4 * t + b) * 16 + c * 4 + q] : 0.0;
-#pragma unroll
-            for (int T2 = 0; T2 < 6; ++T2) {
-                const int ri = 16 * T2 + c, ck = 16 * t + 4 * b + q;
-                a_n[T2] = (T2 > t || (T2 == t && c > 4 * b + 3)) ? -sL[ri * PG_T2_LD + ck] : 0.0;
-            }
-        };
-        fetch(0, 0);
-#pragma unroll
-        for (int t = 0; t < 6; ++t) {
-            if (16 * t >= n) break;
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                const double lop = lop_n;
-                double a[6];
-#pragma unroll
-                for (int T2 = 0; T2 < 6; ++T2) a[T2] = a_n[T2];
-                if (b < 3) fetch(t, b + 1); else if (t < 5) fetch(t + 1, 0);
-                const pg_d4 zero4 = { 0.0, 0.0, 0.0, 0.0 };
-                const pg_d4 r4 = __builtin_amdgcn_mfma_f64_16x16x4f64(lop, S[t][b], zero4, 0, 0, 0);
-                const double LP = r4[0];
-                S[t][b] = LP;
-#pragma unroll
-                for (int T2 = t; T2 < 6; ++T2) S[T2] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[T2], LP, S[T2], 0, 0, 0);
-            }
-        }
-    }
+    if (solve && rowbase < nrows) pg_rowsolve_steps(S, sL, sT, n, c, q);      // wavefront-uniform
     // chunk tj -> LDS in row-major order (the B operands); on a diagonal tile the first group's rows are that chunk
     if (diag ? grp_i : !grp_i) {
 #pragma unroll
@@ -656,37 +618,12 @@ __global__ __launch_bounds__(TS * 8) void pg_front_rsu_kernel(const int* __restr
 #pragma unroll
             for (int v = 0; v < 4; ++v) sB[(16 * w4 + c) * PG_SYRK_LD + 16 * T + q + 4 * v] = S[T][v];
     }
-    if (diag && grp_i && rowbase < nrows) {            // the chunk's L21 rows for the back-substitution, and their share of the forward solve
-        double* __restrict__ Lrow = FL + fd.off + (size_t)(row0 + min(rowbase + c, nrows - 1)) * ld + col0;
-        double dot = 0;
-#pragma unroll
-        for (int T = 0; T < 6; ++T)
-#pragma unroll
-            for (int v = 0; v < 4; ++v) {
-                const int col = 16 * T + q + 4 * v;
-                if (col < n) { if (rok) Lrow[col] = S[T][v]; dot += S[T][v] * sY[col]; }
-            }
-        dot += __shfl_xor(dot, 16, 64);
-        dot += __shfl_xor(dot, 32, 64);
-        if (l < 16 && rok) R[fd.roff + row0 + rowbase + c] -= dot;
-    }
+    if (diag && grp_i && rowbase < nrows)              // the chunk's L21 rows for the back-substitution, and their share of the forward solve
+        pg_rowsolve_tail(S, sY, n, l, rok, FL + P.fd.off + (size_t)(P.row0 + min(rowbase + c, nrows - 1)) * P.ld + P.col0, R + P.fd.roff + P.row0 + rowbase);
     __syncthreads();
     if (!grp_i || i0 >= nrows) return;
-    // A22 -= L21 L21^T on the tile: the steps of pg_front_syrk_kernel; A operand k = 4 ks + (l >> 4) of row (l & 15) is register (ks & 3) of
-    // tile register ks >> 2 of this very lane
-#pragma unroll
-    for (int cb = 0; cb < NW; ++cb) {
-        const int j0 = TS * tj + 16 * cb;
-        if (j0 >= nrows || j0 > i0 + 15) break;
-        const int jr = j0 + (l & 15);
-        const double* __restrict__ sb = sB + (16 * cb + (l & 15)) * PG_SYRK_LD + (l >> 4);
-        double* __restrict__ Cp = A + (size_t)(row0 + i0 + (l >> 4)) * ld + row0 + j0 + (l & 15);
-        pg_d4 r = acc[cb];
-#pragma unroll
-        for (int ks = 0; ks < 24; ++ks) r = __builtin_amdgcn_mfma_f64_16x16x4f64(-S[ks >> 2][ks & 3], sb[4 * ks], r, 0, 0, 0);
-#pragma unroll
-        for (int v = 0; v < 4; ++v) if (i0 + (l >> 4) + 4 * v < nrows && jr < nrows) Cp[(size_t)(4 * v) * ld] = r[v];
-    }
+    // A operand k = 4 ks + (l >> 4) of row (l & 15) is register (ks & 3) of tile register ks >> 2 of this very lane
+    pg_strip_update<TS>(acc, [&](int ks) { return -S[ks >> 2][ks & 3]; }, sB, A, P, i0, tj, l);
 }
 
 // x1 = L11^-T (y1 - L21^T x2) for one panel: one workgroup of 1024 threads.  x2 (the rows below the panel) is gathered into LDS,
@@ -696,38 +633,50 @@ __global__ __launch_bounds__(TS * 8) void pg_front_rsu_kernel(const int* __restr
 // workgroup pulls it through one compute unit at 30 - 50 GB/s -- 100 us and more per panel on the levels where the root front is alone.
 // For panels with more than PG_BWD_SPLIT rows below them the product is split over workgroups of PG_BWD_RC rows each (this kernel:
 // partial column sums, folded in slot order), and pg_front_bwd2_kernel adds the partial sums in chunk order instead of streaming L21.
+
+// one slot's share of a column sum of L21^T x2: rows slot, slot + 10, ... < nr of the column at Ab (row stride ld) times sx, streamed with
+// sixteen loads in flight (then, with MID40, four), even and odd loads into two accumulators
+template <bool MID40>
+__device__ __forceinline__ double pg_colsum_stream(const double* __restrict__ Ab, int ld, const double* sx, int slot, int nr)
+{
+    double acc0 = 0, acc1 = 0;
+    int i = slot;
+    for (; i + 150 < nr; i += 160) {
+        double a16[16];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) a16[u] = Ab[(size_t)(i + 10 * u) * ld];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) { if (u & 1) acc1 += a16[u] * sx[i + 10 * u]; else acc0 += a16[u] * sx[i + 10 * u]; }
+    }
+    if constexpr (MID40)
+        for (; i + 30 < nr; i += 40) {
+            double a4[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) a4[u] = Ab[(size_t)(i + 10 * u) * ld];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) { if (u & 1) acc1 += a4[u] * sx[i + 10 * u]; else acc0 += a4[u] * sx[i + 10 * u]; }
+        }
+    for (; i < nr; i += 10) acc0 += Ab[(size_t)i * ld] * sx[i];
+    return acc0 + acc1;
+}
 __global__ __launch_bounds__(1024) void pg_front_bwd_part_kernel(const int* __restrict__ it_front, const int* __restrict__ it_step, const pg_front* __restrict__ FD,
                                                                  const int* __restrict__ f_rows, const double* __restrict__ FL, const double* __restrict__ x,
                                                                  double* __restrict__ part, int maxchunks)
 {
     __shared__ double sx[PG_BWD_RC];
     __shared__ double s_acc[10 * (PG_PW * 6)];
-    const pg_front fd = FD[it_front[blockIdx.y]];
-    const int step = it_step[blockIdx.y], col0 = 96 * step;
-    const int n = min(96, fd.s6 - col0), ld = fd.ld;
-    const int row0 = col0 + n, nrows = fd.n6 - row0;
-    if (nrows <= PG_BWD_SPLIT) return;
+    const pg_panel P = pg_panel_load(FD, it_front, it_step, blockIdx.y);
+    if (P.nrows <= PG_BWD_SPLIT) return;
     const int r0 = blockIdx.x * PG_BWD_RC;
-    if (r0 >= nrows) return;
-    const int nr = min(PG_BWD_RC, nrows - r0);
-    for (int i = threadIdx.x; i < nr; i += 1024) { const int g = row0 + r0 + i; sx[i] = x[(size_t)f_rows[fd.rowptr + g / 6] * 6 + g % 6]; }
+    if (r0 >= P.nrows) return;
+    const int nr = min(PG_BWD_RC, P.nrows - r0);
+    for (int i = threadIdx.x; i < nr; i += 1024) { const int g = P.row0 + r0 + i; sx[i] = x[(size_t)f_rows[P.fd.rowptr + g / 6] * 6 + g % 6]; }
     __syncthreads();
     const int slot = threadIdx.x / 96, cc = threadIdx.x - slot * 96;
     if (slot < 10) {
-        double acc0 = 0, acc1 = 0;
-        if (cc < n) {
-            const double* __restrict__ Ab = FL + fd.off + (size_t)(row0 + r0) * ld + col0 + cc;
-            int i = slot;
-            for (; i + 150 < nr; i += 160) {                   // sixteen loads in flight
-                double a16[16];
-#pragma unroll
-                for (int u = 0; u < 16; ++u) a16[u] = Ab[(size_t)(i + 10 * u) * ld];
-#pragma unroll
-                for (int u = 0; u < 16; ++u) { if (u & 1) acc1 += a16[u] * sx[i + 10 * u]; else acc0 += a16[u] * sx[i + 10 * u]; }
-            }
-            for (; i < nr; i += 10) acc0 += Ab[(size_t)i * ld] * sx[i];
-        }
-        s_acc[slot * (PG_PW * 6) + cc] = acc0 + acc1;
+        double sum = 0;
+        if (cc < P.n) sum = pg_colsum_stream<false>(FL + P.fd.off + (size_t)(P.row0 + r0) * P.ld + P.col0 + cc, P.ld, sx, slot, nr);
+        s_acc[slot * (PG_PW * 6) + cc] = sum;
     }
     __syncthreads();
     if (threadIdx.x < 96) {
@@ -745,15 +694,14 @@ __global__ __launch_bounds__(1024) void pg_front_bwd2_kernel(const int* __restri
     double* sT = s_bw + (PG_PW * 6) * PG_BWD2_LD;  // the panel's 4 x 4 inverse blocks: a global load per block would sit on the serial chain of wave 0
     double* s_acc = sT + PG_NB4 * 16;
     double* sx = s_acc + 10 * (PG_PW * 6);
-    const pg_front fd = FD[it_front[blockIdx.x]];
-    const int step = it_step[blockIdx.x], col0 = 96 * step;
-    const int n = min(96, fd.s6 - col0), p = fd.pan0 + step, ld = fd.ld;
-    const int row0 = col0 + n, nrows = fd.n6 - row0;
+    const pg_panel P = pg_panel_load(FD, it_front, it_step, blockIdx.x);
+    const pg_front& fd = P.fd;
+    const int col0 = P.col0, n = P.n, ld = P.ld, row0 = P.row0, nrows = P.nrows;
     double lreg[9];
     { const double* __restrict__ L11 = F + fd.off + (size_t)col0 * ld + col0;
 #pragma unroll
       for (int e = 0; e < 9; ++e) { const int id = e * 1024 + threadIdx.x, r = id / 96, cc = id - 96 * r; lreg[e] = (r < n && cc <= r) ? L11[(size_t)r * ld + cc] : 0.0; } }
-    if (threadIdx.x < PG_NB4 * 16) sT[threadIdx.x] = Tinv[(size_t)p * PG_NB4 * 16 + threadIdx.x];
+    if (threadIdx.x < PG_NB4 * 16) sT[threadIdx.x] = Tinv[(size_t)P.p * PG_NB4 * 16 + threadIdx.x];
     const bool split = part != nullptr && nrows > PG_BWD_SPLIT;      // the product came in as partial sums (pg_front_bwd_part_kernel)
     const bool big = nrows > PG_BWD2_SX;           // only the largest interface fronts: x2 does not fit the LDS, read it through the row map
     if (!big && !split) for (int i = threadIdx.x; i < nrows; i += 1024) { const int g = row0 + i; sx[i] = x[(size_t)f_rows[fd.rowptr + g / 6] * 6 + g % 6]; }
@@ -761,36 +709,18 @@ __global__ __launch_bounds__(1024) void pg_front_bwd2_kernel(const int* __restri
     {
         const int slot = threadIdx.x / 96, cc = threadIdx.x - slot * 96;
         if (slot < 10) {
-            double acc0 = 0, acc1 = 0;
+            double sum = 0;
+            const double* __restrict__ Ab = FL + fd.off + (size_t)row0 * ld + col0 + cc;          // L21: in place, or in the second arena where the level ran the fused row solve + update
             if (split) {
                 if (slot == 0 && cc < n) {
                     const int nch = (nrows + PG_BWD_RC - 1) / PG_BWD_RC;
                     const double* __restrict__ pp = part + (size_t)blockIdx.x * maxchunks * 96 + cc;
-                    for (int ch = 0; ch < nch; ++ch) acc0 += pp[(size_t)ch * 96];
+                    for (int ch = 0; ch < nch; ++ch) sum += pp[(size_t)ch * 96];
                 }
-            } else if (cc < n && !big) {
-                const double* __restrict__ Ab = FL + fd.off + (size_t)row0 * ld + col0 + cc;      // L21: in place, or in the second arena where the level ran the fused row solve + update
-                int i = slot;
-                for (; i + 150 < nrows; i += 160) {                // sixteen loads in flight
-                    double a16[16];
-#pragma unroll
-                    for (int u = 0; u < 16; ++u) a16[u] = Ab[(size_t)(i + 10 * u) * ld];
-#pragma unroll
-                    for (int u = 0; u < 16; ++u) { if (u & 1) acc1 += a16[u] * sx[i + 10 * u]; else acc0 += a16[u] * sx[i + 10 * u]; }
-                }
-                for (; i + 30 < nrows; i += 40) {
-                    double a4[4];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) a4[u] = Ab[(size_t)(i + 10 * u) * ld];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) { if (u & 1) acc1 += a4[u] * sx[i + 10 * u]; else acc0 += a4[u] * sx[i + 10 * u]; }
-                }
-                for (; i < nrows; i += 10) acc0 += Ab[(size_t)i * ld] * sx[i];
-            } else if (cc < n) {
-                const double* __restrict__ Ab = FL + fd.off + (size_t)row0 * ld + col0 + cc;      // L21: in place, or in the second arena where the level ran the fused row solve + update
-                for (int i = slot; i < nrows; i += 10) { const int g = row0 + i; acc0 += Ab[(size_t)i * ld] * x[(size_t)f_rows[fd.rowptr + g / 6] * 6 + g % 6]; }
-            }
-            s_acc[slot * (PG_PW * 6) + cc] = acc0 + acc1;
+            } else if (cc < n && !big) sum = pg_colsum_stream<true>(Ab, ld, sx, slot, nrows);
+            else if (cc < n)
+                for (int i = slot; i < nrows; i += 10) { const int g = row0 + i; sum += Ab[(size_t)i * ld] * x[(size_t)f_rows[fd.rowptr + g / 6] * 6 + g % 6]; }
+            s_acc[slot * (PG_PW * 6) + cc] = sum;
         }
     }
 #pragma unroll

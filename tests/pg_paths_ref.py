@@ -326,10 +326,11 @@ def twin_stats(dr, e):
 
 # a front of f block rows has 6 f - 96 rows below its first 96-column panel: pg_front_bwd_part_kernel runs above PG_BWD_SPLIT = 2048 rows
 # (f >= 358), and the 64 x 64 tiles of that trailing block number nt (nt + 1) / 2 with nt = ceil(rows / 64): above PG_RSU32_MAX_TILES = 80
-# from nt = 13 (f >= 145).  (dsss_pg_kernels.h; pg_build_schedule.)
+# from nt = 13 (f >= 145), above PG_RSU_MAX_TILES = 320 (row solve and update as two launches) from nt = 25.  (dsss_pg_kernels.h;
+# pg_build_schedule.)
 FRONT_ROWS_FOR_BWD_SPLIT = 358
 FRONT_ROWS_FOR_RSU32 = 145
-PG_BWD_SPLIT, PG_RSU32_MAX_TILES = 2048, 80
+PG_BWD_SPLIT, PG_RSU32_MAX_TILES, PG_RSU_MAX_TILES = 2048, 80, 320
 
 
 def level_tiles_at_least(rows):

@@ -105,6 +105,8 @@ def test_topology(orc, ctx, name):
         if name == "random_pairs":
             assert lv[:, 2].max() > P.PG_BWD_SPLIT                              # pg_front_bwd_part_kernel ran
             assert P.level_tiles_at_least(lv[:, 2].max()) > P.PG_RSU32_MAX_TILES    # a level left the 32 x 32 quarters
+            # ... and the fused kernel altogether: the front runs trsm2 + syrk, then rsu<64>, then rsu<32> as it shrinks
+            assert P.level_tiles_at_least(lv[:, 2].max()) > P.PG_RSU_MAX_TILES
         else:
             assert lv[:, 0].sum() > 2 and lv[:, 1].max() == 96                  # more than two 96-column panel steps
 

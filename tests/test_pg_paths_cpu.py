@@ -98,6 +98,8 @@ def test_host_twin_reports_the_intended_fronts(orc):
     for name, s in st.items():
         print("%-16s nnzL %6d fronts %3d panels %3d levels %3d binned columns %4d largest front %4d block rows" % (name, s[0], s[1], s[2], s[3], s[6], s[7]))
     assert st["random_pairs"][7] >= P.FRONT_ROWS_FOR_BWD_SPLIT > P.FRONT_ROWS_FOR_RSU32
+    # ... and for a level above PG_RSU_MAX_TILES: separate row solve and update first, then the fused kernel at 64 x 64, then its quarters
+    assert P.level_tiles_at_least(6 * st["random_pairs"][7] - 96) > P.PG_RSU_MAX_TILES
     n, ne = P.RANDOM_PAIRS
     smaller = P._random_pairs(orc, n - 50, int(0.75 * (n - 50)))
     assert P.twin_stats(*smaller[:2])[7] < P.FRONT_ROWS_FOR_BWD_SPLIT           # ... and one step down the grid it is not
