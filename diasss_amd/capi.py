@@ -78,18 +78,49 @@ class DsssError(RuntimeError):
     code = None          # the DSSS_E_* value where the error came from the library
 
 
-class FramesArgs:
-    """argument arrays of dsss_frames_set (see Context.frames_args)"""
+# dsss_raw_type: the element type of a raw waterfall
+RAW_F64, RAW_F32, RAW_U16, RAW_U8 = 0, 1, 2, 3
+_RAW_SIZE = {RAW_F64: 8, RAW_F32: 4, RAW_U16: 2, RAW_U8: 1}
+_RAW_OF_DTYPE = {"float64": RAW_F64, "float32": RAW_F32, "uint16": RAW_U16, "uint8": RAW_U8}
 
-    def __init__(self, ids, raws, Ns, Ms, poses, alts, grs):
+
+def raw_type_of(a, raw_type=None):
+    """dsss_raw_type of a waterfall (numpy array or torch tensor), from its dtype.  torch has no uint16 arithmetic on every build: a
+    u16 image may come as a tensor whose storage is viewed as int16, with raw_type=RAW_U16 given explicitly (an explicit type must
+    have the element size of the array's dtype).  Any dtype but uint8, uint16, float32, float64 raises TypeError."""
+    name = str(a.dtype).replace("torch.", "")
+    if raw_type is None:
+        if name not in _RAW_OF_DTYPE:
+            raise TypeError("raw waterfall of dtype %s: uint8, uint16, float32 or float64 expected" % name)
+        return _RAW_OF_DTYPE[name]
+    raw_type = int(raw_type)
+    itemsize = a.dtype.itemsize if isinstance(a, np.ndarray) else a.element_size()
+    if _RAW_SIZE.get(raw_type) != itemsize:
+        raise TypeError("raw_type %d does not have the element size of dtype %s" % (raw_type, name))
+    return raw_type
+
+
+class FramesArgs:
+    """argument arrays of dsss_frames_set_typed (see Context.frames_args)"""
+
+    def __init__(self, ids, raws, Ns, Ms, poses, alts, grs, raw_types=None):
         n = self.n = len(ids)
-        if not (len(raws) == len(Ns) == len(Ms) == len(poses) == len(alts) == len(grs) == n):
+        if not (len(raws) == len(Ns) == len(Ms) == len(poses) == len(alts) == len(grs) == n) or (raw_types is not None and len(raw_types) != n):
             raise ValueError("frames_set: the per-frame lists differ in length")
         _torch = sys.modules.get("torch")                      # (only a caller that has torch can hand tensors over)
+        # the type of every image from its own dtype (a list may mix them), or as given
+        self.raw_type = np.fromiter((RAW_F64 if a is None else raw_type_of(a, None if raw_types is None else raw_types[i])
+                                     for i, a in enumerate(raws)), np.int32, n)
 
-        def addr(a, what, shape=None):
+        def addr(a, what, shape=None, typed=False):
             if a is None:
                 return 0
+            if typed:                                          # a raw image: its dtype was checked above
+                if not (a.flags.c_contiguous if isinstance(a, np.ndarray) else a.is_contiguous()):
+                    raise TypeError("frames_set: %s must be contiguous" % what)
+                if shape is not None and tuple(a.shape) != shape:
+                    raise ValueError("frames_set: %s has shape %s, expected %s" % (what, tuple(a.shape), shape))
+                return a.__array_interface__["data"][0] if isinstance(a, np.ndarray) else a.data_ptr()
             if isinstance(a, np.ndarray):
                 if a.dtype != np.float64 or not a.flags.c_contiguous:
                     raise TypeError("frames_set: %s must be a C-contiguous float64 array" % what)
@@ -104,7 +135,7 @@ class FramesArgs:
                 return a.data_ptr()                            # host (pinned or pageable) or device: the library asks the runtime which
             raise TypeError("frames_set: %s must be None, a numpy array or a torch tensor" % what)
         self.ids = np.ascontiguousarray(ids, np.int32); self.N = np.ascontiguousarray(Ns, np.int32); self.M = np.ascontiguousarray(Ms, np.int32)
-        self.p_raw = np.fromiter((addr(a, "raw[%d]" % i, (int(self.N[i]), int(self.M[i]))) for i, a in enumerate(raws)), np.uintp, n)
+        self.p_raw = np.fromiter((addr(a, "raw[%d]" % i, (int(self.N[i]), int(self.M[i])), True) for i, a in enumerate(raws)), np.uintp, n)
         self.p_pose = np.fromiter((addr(a, "pose[%d]" % i, (int(self.N[i]), 6)) for i, a in enumerate(poses)), np.uintp, n)
         self.p_alt = np.fromiter((addr(a, "alt[%d]" % i, (int(self.N[i]),)) for i, a in enumerate(alts)), np.uintp, n)
         self.p_gr = np.fromiter((addr(a, "grange[%d]" % i, (int(self.M[i]) // 2,)) for i, a in enumerate(grs)), np.uintp, n)
@@ -156,6 +187,12 @@ def lib():
         L.dsss_stream.argtypes = [C.c_void_p]
         L.dsss_features_pack_bytes.restype = C.c_size_t
         L.dsss_features_pack_bytes.argtypes = [C.c_void_p]
+        L.dsss_raw_type_size.restype = C.c_size_t
+        L.dsss_raw_type_size.argtypes = [C.c_int]
+        L.dsss_frame_set_typed.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.dsss_frames_set_typed.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 8
+        L.dsss_frame_raw_info.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]
+        L.dsss_frame_raw_stats.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.dsss_comm_init_callback.argtypes = [C.c_void_p, C.c_int, C.c_int, COMM_FN, C.c_void_p]
         L.dsss_comm_init_device_callback.argtypes = [C.c_void_p, C.c_int, C.c_int, COMM_DEV_FN, C.c_void_p]
         L.dsss_comm_frame_owner.argtypes = [C.c_void_p, C.c_int, C.c_int]
@@ -179,6 +216,11 @@ def lib():
 
 COMM_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t)
 COMM_DEV_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p)
+
+
+def raw_type_size(raw_type):
+    """dsss_raw_type_size: bytes per sample of a dsss_raw_type, 0 for anything else"""
+    return int(lib().dsss_raw_type_size(int(raw_type)))
 
 
 def _ptr(a):
@@ -334,27 +376,44 @@ class Context:
         self._chk(self.L.dsss_set_pg_partitions(self.h, int(nparts)), "dsss_set_pg_partitions")
 
     # ---- frames
-    def frame_set(self, fid, raw, N, M, pose6, alt, gr):
+    def frame_set(self, fid, raw, N, M, pose6, alt, gr, raw_type=None):
+        """dsss_frame_set_typed.  raw: None, a numpy array or a torch tensor (host or device) of uint8, uint16, float32 or float64, taken as
+        it is; raw_type only for a tensor whose dtype cannot say it (raw_type_of)."""
         pose6 = np.ascontiguousarray(pose6, np.float64); alt = np.ascontiguousarray(alt, np.float64)
         gr = np.ascontiguousarray(gr, np.float64)
         assert pose6.shape == (N, 6) and alt.shape == (N,) and gr.shape == (M // 2,)
+        rt = RAW_F64 if raw is None else raw_type_of(raw, raw_type)
         if isinstance(raw, np.ndarray):
-            raw = np.ascontiguousarray(raw, np.float64); assert raw.shape == (N, M)
+            raw = np.ascontiguousarray(raw); assert raw.shape == (N, M)
         self._keep = getattr(self, "_keep", {}); self._keep[fid] = raw      # keep device tensors alive
-        self._chk(self.L.dsss_frame_set(self.h, fid, _ptr(raw), N, M, _ptr(pose6), _ptr(alt), _ptr(gr)), "dsss_frame_set")
+        self._chk(self.L.dsss_frame_set_typed(self.h, fid, _ptr(raw), rt, N, M, _ptr(pose6), _ptr(alt), _ptr(gr)), "dsss_frame_set_typed")
 
-    def frames_args(self, ids, raws, Ns, Ms, poses, alts, grs):
-        """The ARGUMENT ARRAYS of dsss_frames_set (ids, sizes, four arrays of per-frame pointers) built and validated once: what a C++
-        caller of the C ABI simply holds.  Host arrays must be float64 and C-contiguous, raws may hold None, host arrays or CUDA tensors
-        (float64, contiguous).  The object keeps every array alive; frames_set(args) is then the bare C call."""
-        return FramesArgs(ids, raws, Ns, Ms, poses, alts, grs)
+    def frames_args(self, ids, raws, Ns, Ms, poses, alts, grs, raw_types=None):
+        """The ARGUMENT ARRAYS of dsss_frames_set_typed (ids, types, sizes, four arrays of per-frame pointers) built and validated once:
+        what a C++ caller of the C ABI simply holds.  Geometry arrays must be float64 and C-contiguous; raws may hold None, host arrays
+        or CUDA tensors (contiguous; uint8, uint16, float32 or float64, each frame its own: raw_type_of).  The object keeps every array
+        alive; frames_set(args) is then the bare C call."""
+        return FramesArgs(ids, raws, Ns, Ms, poses, alts, grs, raw_types)
 
-    def frames_set(self, ids, raws=None, Ns=None, Ms=None, poses=None, alts=None, grs=None):
-        """dsss_frames_set: one call for many frames.  Either the seven per-frame lists, or one FramesArgs built by frames_args()."""
-        a = ids if isinstance(ids, FramesArgs) else FramesArgs(ids, raws, Ns, Ms, poses, alts, grs)
+    def frames_set(self, ids, raws=None, Ns=None, Ms=None, poses=None, alts=None, grs=None, raw_types=None):
+        """dsss_frames_set_typed: one call for many frames.  Either the seven per-frame lists, or one FramesArgs built by frames_args()."""
+        a = ids if isinstance(ids, FramesArgs) else FramesArgs(ids, raws, Ns, Ms, poses, alts, grs, raw_types)
         self._keep = getattr(self, "_keep", {})
         self._keep.update(a.keep)                              # the library borrows device images until the frame is set again
-        self._chk(self.L.dsss_frames_set(self.h, a.n, _ptr(a.ids), _ptr(a.p_raw), _ptr(a.N), _ptr(a.M), _ptr(a.p_pose), _ptr(a.p_alt), _ptr(a.p_gr)), "dsss_frames_set")
+        self._chk(self.L.dsss_frames_set_typed(self.h, a.n, _ptr(a.ids), _ptr(a.p_raw), _ptr(a.raw_type), _ptr(a.N), _ptr(a.M), _ptr(a.p_pose), _ptr(a.p_alt), _ptr(a.p_gr)), "dsss_frames_set_typed")
+
+    def frame_raw_info(self, fid):
+        """dsss_frame_raw_info: (raw_type, where, owned_bytes); where: 0 none, 1 borrowed device pointer, 2 owned device copy, 3 owned copy
+        whose upload from a page-locked host image is still pending."""
+        t = C.c_int(0); w = C.c_int(0); b = C.c_size_t(0)
+        self._chk(self.L.dsss_frame_raw_info(self.h, int(fid), C.byref(t), C.byref(w), C.byref(b)), "dsss_frame_raw_info")
+        return t.value, w.value, b.value
+
+    def frame_raw_stats(self, fid):
+        """dsss_frame_raw_stats: (mean, min) of the raw image as the extraction computes them."""
+        out = np.zeros(2, np.float64)
+        self._chk(self.L.dsss_frame_raw_stats(self.h, int(fid), _ptr(out)), "dsss_frame_raw_stats")
+        return float(out[0]), float(out[1])
 
     def extract(self, fid):
         n = C.c_int(0)

@@ -372,7 +372,7 @@ static hipError_t frame_fill(dsss_ctx* c, int id, double* dst_pack, const double
     if (e == hipSuccess) e = to_host(dst_pack + (size_t)f.N * 7, grange, (size_t)(f.M / 2));
     return e;
 }
-static int frame_submit(dsss_ctx* c, int id, const double* raw, bool own_upload)
+static int frame_submit(dsss_ctx* c, int id, const void* raw, int raw_type, bool own_upload)
 {
     dsss_frame& f = c->frames[id];
     const int N = f.N, M = f.M;
@@ -386,40 +386,61 @@ static int frame_submit(dsss_ctx* c, int id, const double* raw, bool own_upload)
         hipPointerAttribute_t at;
         bool on_dev = (hipPointerGetAttributes(&at, raw) == hipSuccess) && at.type == hipMemoryTypeDevice;
         (void)hipGetLastError();
-        f.raw_pending = false; f.raw_host = nullptr;
+        f.raw_pending = false; f.raw_host = nullptr; f.raw_type = raw_type;
         if (on_dev) { f.raw = raw; }
         else {
-            if (!f.raw_owned) { if (const int rc = f.raw_owned.reserve(c, (size_t)N * M * sizeof(double))) return rc; }
+            // the owned copy holds N M elements of THIS type: the same geometry set again with a wider type grows it (dsss_buf's
+            // rule: synchronise, free, allocate, publish), a narrower one keeps the block
+            if (const int rc = f.raw_owned.reserve(c, f.raw_bytes())) { f.has_raw = false; f.raw = nullptr; return rc; }      // (a failed growth leaves no block: the frame has no image)
             const bool pinned = (hipPointerGetAttributes(&at, raw) == hipSuccess) && at.type == hipMemoryTypeHost;
             (void)hipGetLastError();
             // a page-locked image is not copied here: the extraction streams it in, sub-batch by sub-batch, on a copy stream while
             // the kernels of the previous sub-batch run (the caller keeps the buffer alive until dsss_extract* returns).  Pageable
             // memory cannot be copied asynchronously: it goes up now.
             if (pinned) { f.raw_host = raw; f.raw_pending = true; }
-            else HIPCHK(c, hipMemcpy(f.raw_owned.p, raw, (size_t)N * M * sizeof(double), hipMemcpyHostToDevice));
-            f.raw = f.raw_owned.as<double>();
+            else HIPCHK(c, hipMemcpy(f.raw_owned.p, raw, f.raw_bytes(), hipMemcpyHostToDevice));
+            f.raw = f.raw_owned.p;
         }
         f.has_raw = true;
     } else f.has_raw = false;
     return dsss_frame_geo_bbox(c, id);
 }
 
+size_t dsss_raw_type_size(int raw_type)
+{
+    switch (raw_type) { case DSSS_RAW_F64: return 8; case DSSS_RAW_F32: return 4; case DSSS_RAW_U16: return 2; case DSSS_RAW_U8: return 1; default: return 0; }
+}
+
 int dsss_frame_set(dsss_ctx* c, int id, const double* raw, int N, int M, const double* pose6, const double* alt,
                    const double* grange)
 {
+    return dsss_frame_set_typed(c, id, raw, DSSS_RAW_F64, N, M, pose6, alt, grange);
+}
+
+int dsss_frame_set_typed(dsss_ctx* c, int id, const void* raw, int raw_type, int N, int M, const double* pose6, const double* alt,
+                         const double* grange)
+{
     if (!c) return DSSS_E_ARG;
+    if (!dsss_raw_type_size(raw_type)) DSSS_FAIL(c, DSSS_E_ARG, "unknown raw type %d", raw_type);
     HIPCHK(c, hipSetDevice(c->device));
     int rc = dsss_ensure_store(c); if (rc) return rc;
     rc = frame_prepare(c, id, N, M, pose6, alt, grange); if (rc) return rc;
     HIPCHK(c, frame_fill(c, id, c->frames[id].h_pack, pose6, alt, grange));
-    return frame_submit(c, id, raw, true);
+    return frame_submit(c, id, raw, raw_type, true);
 }
 
 int dsss_frames_set(dsss_ctx* c, int n, const int* ids, const double* const* raw, const int* N, const int* M,
                     const double* const* pose6, const double* const* alt, const double* const* grange)
 {
+    return dsss_frames_set_typed(c, n, ids, reinterpret_cast<const void* const*>(raw), nullptr, N, M, pose6, alt, grange);
+}
+
+int dsss_frames_set_typed(dsss_ctx* c, int n, const int* ids, const void* const* raw, const int* raw_type, const int* N, const int* M,
+                          const double* const* pose6, const double* const* alt, const double* const* grange)
+{
     if (!c || n < 0 || (n > 0 && (!ids || !N || !M || !pose6 || !alt || !grange))) return DSSS_E_ARG;
     if (n == 0) return DSSS_OK;
+    if (raw_type) for (int i = 0; i < n; ++i) if (!dsss_raw_type_size(raw_type[i])) DSSS_FAIL(c, DSSS_E_ARG, "unknown raw type %d (frame %d)", raw_type[i], ids[i]);      // before any frame is touched
     const auto t0 = std::chrono::steady_clock::now();
     const dsss_switches sw = dsss_switches_read();
     HIPCHK(c, hipSetDevice(c->device));
@@ -459,7 +480,7 @@ int dsss_frames_set(dsss_ctx* c, int n, const int* ids, const double* const* raw
         dsss_frame& f = c->frames[ids[i]];
         f.gbatch = b; G.refs++;
         f.pose6 = G.d + off[i]; f.alt = f.pose6 + (size_t)f.N * 6; f.gr = f.alt + f.N; f.h_geo = G.h + off[i];
-        rc = frame_submit(c, ids[i], raw ? raw[i] : nullptr, false); if (rc) return rc;
+        rc = frame_submit(c, ids[i], raw ? raw[i] : nullptr, raw_type ? raw_type[i] : DSSS_RAW_F64, false); if (rc) return rc;
     }
     HIPCHK(c, hipEventRecord(c->xev[0], c->stream));        // whatever is queued so far may still read the buffer's previous contents
     const auto t1 = std::chrono::steady_clock::now();
@@ -477,6 +498,18 @@ int dsss_frames_set(dsss_ctx* c, int n, const int* ids, const double* const* raw
     HIPCHK(c, hipStreamWaitEvent(c->stream, G.ev, 0));      // every later consumer of the geometry is ordered behind the upload
     if (sw.ex_verbose) { auto us = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
         fprintf(stderr, "[dsss frames_set] %d frames in %.1f us: bookkeeping %.1f, eager extraction queued %.1f, geometry packed (%d threads) %.1f, upload queued %.1f\n", n, us(t0, std::chrono::steady_clock::now()), us(t0, t1), us(t1, t2), T, us(t2, t3), us(t3, std::chrono::steady_clock::now())); }
+    return DSSS_OK;
+}
+
+int dsss_frame_raw_info(dsss_ctx* c, int id, int* raw_type, int* where, size_t* owned_bytes)
+{
+    if (!c) return DSSS_E_ARG;
+    if (id < 0 || id >= c->max_frames) DSSS_FAIL(c, DSSS_E_ARG, "frame id %d out of range [0,%d)", id, c->max_frames);
+    const dsss_frame& f = c->frames[id];
+    const bool owned = f.has_raw && f.raw == f.raw_owned.p;
+    if (raw_type) *raw_type = f.raw_type;
+    if (where) *where = !f.has_raw ? 0 : !owned ? 1 : f.raw_pending ? 3 : 2;
+    if (owned_bytes) *owned_bytes = owned ? f.raw_bytes() : 0;
     return DSSS_OK;
 }
 

@@ -11,9 +11,10 @@ struct fast_cell { int level, x0, y0, w, h, offx, offy, pad; };
 struct resize_xtab { int sx; short a0, a1; };     // cv::resize tables: source column (sx + 1 is read only when a1 != 0), 11-bit weights
 struct resize_ytab { int ya, yb; short b0, b1; };
 struct ex_frame {
-    const double* raw; int N, M;
+    const void* raw; int N, M;                // N x M elements of raw_type, row stride M, aligned to the element only
     double* rowsum; double* rowmin; double* stats;
     uint8_t* mask; uint8_t* lvl[DSSS_MAX_LEVELS]; int rows[DSSS_MAX_LEVELS], cols[DSSS_MAX_LEVELS]; int nlevels;
+    int raw_type;                             // dsss_raw_type; read by the two kernels that read raw (it sits where the record had padding)
     const fast_cell* cells; int ncells, cell_cap;
     int cell_begin[DSSS_MAX_LEVELS + 1];      // cells of level l: [cell_begin[l], cell_begin[l + 1])
     uint32_t* cand; int* counts; int* offs; float* xs; float* ys; float* rs; int cand_cap;

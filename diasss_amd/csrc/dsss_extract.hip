@@ -31,29 +31,92 @@ __device__ inline double wave_fixed_sum_tail(double p0, double p1)
     return dsss_wave_sum(p0 + p1);
 }
 
-// (a borrowed device image is only known to be 8-byte aligned, and with it every row of its even number of bins: the pair load says so,
-// as u32_unaligned does for the FAST windows; normalize_kernel checks the address instead)
-typedef double f64x2_a8 __attribute__((ext_vector_type(2), aligned(8)));
-__global__ __launch_bounds__(256) void row_reduce_kernel(const ex_frame* __restrict__ frs)
+// The raw image comes in four element types (dsss_raw_type); only this kernel and normalize_kernel read it, each in one FORM per
+// type.  Every form produces what the f64 form produces on (double)sample, bit for bit:
+//   f64, f32   the sum of a row depends on its order, so both keep ONE assignment: lane L adds elements 2L + 128k into p0 and
+//              2L + 1 + 128k into p1, k ascending, then the butterfly -- one pair load per lane and iteration (8 bytes of f32);
+//   u16, u8    every partial sum is an integer below 2^47 (a sample below 2^16, a frame below 2^31 samples), which the f64 tree adds
+//              exactly in any order: these forms sum in integers, in 16-byte loads, and convert once.
+// The kernels are templates over the type: one launch per type PRESENT in the batch, over all its slots, and with MIXED a slot of
+// another type returns at once.  A batch of f64 frames, the headline, runs <DSSS_RAW_F64, false>: the f64 form and nothing else.
+// (a borrowed device image is only known to be aligned to its element, and with it every row of its even number of bins to a pair: the
+// pair load says so, as u32_unaligned does for the FAST windows; normalize_kernel checks the address instead)
+template <class E>
+__device__ __forceinline__ void row_reduce_float(const ex_frame& f)
 {
-    const ex_frame& f = frs[blockIdx.y];
-    const double* __restrict__ raw = f.raw; const int N = f.N, M = f.M;
+    typedef E E2 __attribute__((ext_vector_type(2), aligned(sizeof(E))));      // (declared here: a typedef's alignment does not survive a template argument)
+    const E* __restrict__ raw = static_cast<const E*>(f.raw); const int N = f.N, M = f.M;
     double* __restrict__ rowsum = f.rowsum; double* __restrict__ rowmin = f.rowmin;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= N) return;
-    const double* r = raw + (size_t)row * M;
+    const E* r = raw + (size_t)row * M;
     double p0 = 0.0, p1 = 0.0, mn = INFINITY;
     for (int j = 2 * lane; j < M; j += 128) {
         if (j + 1 < M) {
-            const f64x2_a8 v = *reinterpret_cast<const f64x2_a8*>(r + j);
+            const E2 v = *reinterpret_cast<const E2*>(r + j);
             p0 += v.x; p1 += v.y;
             mn = v.x < mn ? v.x : mn; mn = v.y < mn ? v.y : mn;
-        } else { const double a = r[j]; p0 += a; mn = a < mn ? a : mn; }
+        } else { const E a = r[j]; p0 += a; mn = a < mn ? a : mn; }
     }
     const double s = wave_fixed_sum_tail(p0, p1);
 #pragma unroll
     for (int k = 32; k >= 1; k >>= 1) { const double o = __shfl_xor(mn, k, 64); mn = o < mn ? o : mn; }
     if (lane == 0) { rowsum[row] = s; rowmin[row] = mn; }
+}
+
+// sum and minimum of the elements of one 32-bit word
+template <class E> __device__ __forceinline__ void word_sum_min(uint32_t w, uint32_t& s, uint32_t& m);
+template <> __device__ __forceinline__ void word_sum_min<uint8_t>(uint32_t w, uint32_t& s, uint32_t& m)
+{
+    s = __builtin_amdgcn_sad_u8(w, 0u, s);
+    const uint32_t a = w & 255u, b = (w >> 8) & 255u, c = (w >> 16) & 255u, d = w >> 24;
+    m = a < m ? a : m; m = b < m ? b : m; m = c < m ? c : m; m = d < m ? d : m;
+}
+template <> __device__ __forceinline__ void word_sum_min<uint16_t>(uint32_t w, uint32_t& s, uint32_t& m)
+{
+    const uint32_t a = w & 65535u, b = w >> 16;
+    s += a + b; m = a < m ? a : m; m = b < m ? b : m;
+}
+// One wave per ping.  The row starts at any element: up to 15 bytes of head, one element per lane, bring the address to a multiple of
+// 16; then 16-byte loads, lane-strided; then a tail shorter than one load, one element per lane.  A load's sum is below 2^20; lanes
+// and wave add them in 64 bits (the widest accepted row, 65 534 bins of 65 535, comes within a bit of 2^32: no case to argue).
+template <class E>
+__device__ __forceinline__ void row_reduce_int(const ex_frame& f)
+{
+    constexpr int PER = 16 / (int)sizeof(E);
+    const E* __restrict__ raw = static_cast<const E*>(f.raw); const int N = f.N, M = f.M;
+    double* __restrict__ rowsum = f.rowsum; double* __restrict__ rowmin = f.rowmin;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= N) return;
+    const E* r = raw + (size_t)row * M;
+    int head = (int)((0 - reinterpret_cast<uintptr_t>(r)) & 15) / (int)sizeof(E);
+    head = head < M ? head : M;
+    const int nch = (M - head) / PER, t0 = head + nch * PER;
+    unsigned long long acc = 0; uint32_t mn = 0xffffffffu;
+    if (lane < head) { const uint32_t a = r[lane]; acc = a; mn = a; }
+    if (t0 + lane < M) { const uint32_t a = r[t0 + lane]; acc += a; mn = a < mn ? a : mn; }
+    const uint4* __restrict__ body = reinterpret_cast<const uint4*>(r + head);
+    for (int k = lane; k < nch; k += 64) {
+        const uint4 w = body[k];
+        uint32_t s = 0;
+        word_sum_min<E>(w.x, s, mn); word_sum_min<E>(w.y, s, mn); word_sum_min<E>(w.z, s, mn); word_sum_min<E>(w.w, s, mn);
+        acc += s;
+    }
+    acc = dsss_wave_sum(acc);
+#pragma unroll
+    for (int k = 32; k >= 1; k >>= 1) { const uint32_t o = __shfl_xor(mn, k, 64); mn = o < mn ? o : mn; }
+    if (lane == 0) { rowsum[row] = (double)acc; rowmin[row] = (double)mn; }
+}
+
+template <int T, bool MIXED>
+__global__ __launch_bounds__(256) void row_reduce_kernel(const ex_frame* __restrict__ frs)
+{
+    const ex_frame& f = frs[blockIdx.y];
+    if (MIXED && f.raw_type != T) return;
+    if constexpr (T == DSSS_RAW_F64) row_reduce_float<double>(f);
+    else if constexpr (T == DSSS_RAW_F32) row_reduce_float<float>(f);
+    else if constexpr (T == DSSS_RAW_U16) row_reduce_int<uint16_t>(f);
+    else row_reduce_int<uint8_t>(f);
 }
 
 // stats[0] = mean, stats[1] = min, stats[2] = 2.5*mean (normalisation ceiling), stats[3] = mask threshold
@@ -99,25 +162,44 @@ __global__ __launch_bounds__(256) void mask_init_kernel(const ex_frame* __restri
 }
 
 // Frame::GetNormalizeSSS (frame.cpp:67-78) + the hot-pixel eraser of GetFilteredMask (:98-103).
-// 4 pixels per thread: 2 x 16-byte loads, one 4-byte store.  Erasures only ever write 0, so the scatter is race free.
+// A thread takes G consecutive pixels (flat index: a group may wrap into the next ping, the last one is short) so that a lane loads
+// 16 or 32 bytes and stores at least 4: f64 4 pixels (2 x 16-byte loads, one 4-byte store), f32 4 (16 in, 4 out), u16 8 (16 in, 8 out),
+// u8 16 (16 in, 16 out).  The arithmetic per pixel is one text for every type, on the widened sample.  A base that is not 16-byte
+// aligned (a borrowed pointer) takes the element loads.  Erasures only ever write 0, so the scatter is race free.
+template <int T> struct raw_elem { typedef double type; };
+template <> struct raw_elem<DSSS_RAW_F32> { typedef float type; };
+template <> struct raw_elem<DSSS_RAW_U16> { typedef uint16_t type; };
+template <> struct raw_elem<DSSS_RAW_U8> { typedef uint8_t type; };
+// pixels per thread of a type's form
+constexpr int normalize_group(int raw_type) { return raw_type == DSSS_RAW_U8 ? 16 : raw_type == DSSS_RAW_U16 ? 8 : 4; }
+template <int T, bool MIXED>
 __global__ __launch_bounds__(256) void normalize_kernel(const ex_frame* __restrict__ frs, int er)
 {
+    typedef typename raw_elem<T>::type E; constexpr int G = normalize_group(T);
+    static_assert(G * sizeof(E) == 16 || (G == 4 && sizeof(E) == 8), "one or two 16-byte loads per thread");
     const ex_frame& f = frs[blockIdx.y];
-    const double* __restrict__ raw = f.raw; const int N = f.N, M = f.M;
+    if (MIXED && f.raw_type != T) return;
+    const E* __restrict__ raw = static_cast<const E*>(f.raw); const int N = f.N, M = f.M;
     const double* __restrict__ stats = f.stats; uint8_t* __restrict__ norm = f.lvl[0]; uint8_t* __restrict__ mask = f.mask;
     const size_t total = (size_t)N * M;
-    const size_t i0 = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    const size_t i0 = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * G;
     if (i0 >= total) return;
     const double mn = stats[1], den = stats[2] - stats[1], thr = stats[3];
-    double v[4];
-    const int cnt = (int)((total - i0) < 4 ? (total - i0) : 4);
-    if (cnt == 4 && ((reinterpret_cast<uintptr_t>(raw + i0) & 15) == 0)) {
-        const double2 a = *reinterpret_cast<const double2*>(raw + i0), b = *reinterpret_cast<const double2*>(raw + i0 + 2);
-        v[0] = a.x; v[1] = a.y; v[2] = b.x; v[3] = b.y;
-    } else for (int k = 0; k < 4; ++k) v[k] = k < cnt ? raw[i0 + k] : 0.0;
-    uint8_t q[4];
+    double v[G];
+    const int cnt = (int)((total - i0) < G ? (total - i0) : G);
+    if (cnt == G && ((reinterpret_cast<uintptr_t>(raw + i0) & 15) == 0)) {
+        if constexpr (sizeof(E) == 8) {
+            const double2 a = *reinterpret_cast<const double2*>(raw + i0), b = *reinterpret_cast<const double2*>(raw + i0 + 2);
+            v[0] = a.x; v[1] = a.y; v[2] = b.x; v[3] = b.y;
+        } else {
+            union { uint4 w; E e[G]; } u; u.w = *reinterpret_cast<const uint4*>(raw + i0);
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
+            for (int k = 0; k < G; ++k) v[k] = (double)u.e[k];
+        }
+    } else for (int k = 0; k < G; ++k) v[k] = k < cnt ? (double)raw[i0 + k] : 0.0;
+    uint8_t q[G];
+#pragma unroll
+    for (int k = 0; k < G; ++k) {
         double o = (v[k] - mn) / den * 255.0;
         if (o > 255.0) o = 255.0;
         int r = (int)rint(o);                       // convertTo(CV_8U): saturate_cast<uchar>(cvRound())
@@ -130,10 +212,17 @@ __global__ __launch_bounds__(256) void normalize_kernel(const ex_frame* __restri
                     for (int y = pj - er; y < pj + er && y < M; ++y) mask[(size_t)x * M + y] = 0;
         }
     }
-    if (cnt == 4 && ((i0 & 3) == 0)) *reinterpret_cast<uchar4*>(norm + i0) = make_uchar4(q[0], q[1], q[2], q[3]);
-    else for (int k = 0; k < cnt; ++k) norm[i0 + k] = q[k];
+    if (cnt == G && ((i0 & 3) == 0)) {              // (the level image is 256-byte aligned, i0 a multiple of G)
+        if constexpr (G == 4) *reinterpret_cast<uchar4*>(norm + i0) = make_uchar4(q[0], q[1], q[2], q[3]);
+        else {
+            uint32_t w[G / 4];
+#pragma unroll
+            for (int k = 0; k < G / 4; ++k) w[k] = (uint32_t)q[4 * k] | ((uint32_t)q[4 * k + 1] << 8) | ((uint32_t)q[4 * k + 2] << 16) | ((uint32_t)q[4 * k + 3] << 24);
+            if constexpr (G == 8) *reinterpret_cast<uint2*>(norm + i0) = make_uint2(w[0], w[1]);
+            else *reinterpret_cast<uint4*>(norm + i0) = make_uint4(w[0], w[1], w[2], w[3]);
+        }
+    } else for (int k = 0; k < cnt; ++k) norm[i0 + k] = q[k];
 }
-
 // ------------------------------------------------------------------ K2: cv::resize INTER_LINEAR, CV_8UC1
 // (ORBextractor.cpp:1128).  11-bit fixed point exactly as OpenCV's scalar path: see oracle/orc_orb.c.
 __device__ inline int cvfloorf_dev(float v) { const int i = (int)v; return i - (v < (float)i); }
@@ -1059,8 +1148,29 @@ struct ex_tables {
                                    err(exf + align_up(sizeof(ex_frame) * B, 256)), total(err + align_up(sizeof(int) * B, 256)) {}
 };
 // what the launches of one batch are sized by: the frames [b0, b0 + nb) of the list and the largest of each of their dimensions
+// The launches of the two kernels that read the raw image: one per type in `types` (bit t: dsss_raw_type t), each over every slot of the
+// batch.  Only f64 in it: the f64 form without the type check.
+static void launch_row_reduce(unsigned types, dim3 grid, hipStream_t st, const ex_frame* d_exf)
+{
+    if (types == 1u << DSSS_RAW_F64) { hipLaunchKernelGGL((row_reduce_kernel<DSSS_RAW_F64, false>), grid, dim3(256), 0, st, d_exf); return; }
+    if (types & (1u << DSSS_RAW_F64)) hipLaunchKernelGGL((row_reduce_kernel<DSSS_RAW_F64, true>), grid, dim3(256), 0, st, d_exf);
+    if (types & (1u << DSSS_RAW_F32)) hipLaunchKernelGGL((row_reduce_kernel<DSSS_RAW_F32, true>), grid, dim3(256), 0, st, d_exf);
+    if (types & (1u << DSSS_RAW_U16)) hipLaunchKernelGGL((row_reduce_kernel<DSSS_RAW_U16, true>), grid, dim3(256), 0, st, d_exf);
+    if (types & (1u << DSSS_RAW_U8)) hipLaunchKernelGGL((row_reduce_kernel<DSSS_RAW_U8, true>), grid, dim3(256), 0, st, d_exf);
+}
+static void launch_normalize(unsigned types, const size_t max_groups[4], int nb, hipStream_t st, const ex_frame* d_exf, int er)
+{
+    auto grid = [&](int t) { return dim3((unsigned)((max_groups[t] + 256) / 256), nb); };      // sized by the type's own largest frame
+    if (types == 1u << DSSS_RAW_F64) { hipLaunchKernelGGL((normalize_kernel<DSSS_RAW_F64, false>), grid(DSSS_RAW_F64), dim3(256), 0, st, d_exf, er); return; }
+    if (types & (1u << DSSS_RAW_F64)) hipLaunchKernelGGL((normalize_kernel<DSSS_RAW_F64, true>), grid(DSSS_RAW_F64), dim3(256), 0, st, d_exf, er);
+    if (types & (1u << DSSS_RAW_F32)) hipLaunchKernelGGL((normalize_kernel<DSSS_RAW_F32, true>), grid(DSSS_RAW_F32), dim3(256), 0, st, d_exf, er);
+    if (types & (1u << DSSS_RAW_U16)) hipLaunchKernelGGL((normalize_kernel<DSSS_RAW_U16, true>), grid(DSSS_RAW_U16), dim3(256), 0, st, d_exf, er);
+    if (types & (1u << DSSS_RAW_U8)) hipLaunchKernelGGL((normalize_kernel<DSSS_RAW_U8, true>), grid(DSSS_RAW_U8), dim3(256), 0, st, d_exf, er);
+}
+
 struct ex_batch {
     int b0 = 0, nb = 0, maxN = 0, max_levels = 0, max_cw = 8, max_ch = 8; size_t max_tot = 0; double w_tot = 0;
+    unsigned types = 0; double w_raw = 0; size_t max_groups[4] = { 0, 0, 0, 0 };      // bit t: a raw image of dsss_raw_type t / bytes of the raw images / per type, the most pixel groups normalize_kernel has in a frame
     int max_rows[DSSS_MAX_LEVELS] = { 0 }, max_cols[DSSS_MAX_LEVELS] = { 0 }, lev_cnt[DSSS_MAX_LEVELS] = { 0 };      // lev_cnt[l]: frames that have level l
 };
 
@@ -1146,7 +1256,7 @@ struct ex_run {
         hipError_t e = hipSuccess;
         for (int s = b0; s < std::min(n, b0 + B) && e == hipSuccess; ++s) {
             dsss_frame& f = c->frames[ids[s]];
-            if (f.raw_pending) e = hipMemcpyAsync(f.raw_owned.p, f.raw_host, (size_t)f.N * f.M * sizeof(double), hipMemcpyHostToDevice, c->xs[1]);
+            if (f.raw_pending) e = hipMemcpyAsync(f.raw_owned.p, f.raw_host, f.raw_bytes(), hipMemcpyHostToDevice, c->xs[1]);
             f.raw_pending = false;
         }
         return e == hipSuccess ? hipEventRecord(up_ev(bk), c->xs[1]) : e;
@@ -1159,7 +1269,7 @@ struct ex_run {
         for (int s = 0; s < bt.nb; ++s) {
             const int id = ids[bt.b0 + s]; dsss_frame& f = c->frames[id]; const level_geom& g = *G[bt.b0 + s]; const ex_layout& L = Ls[bt.b0 + s];
             char* S = S0 + slot_bytes * s; ex_frame& e = h_exf[s];
-            e.raw = f.raw; e.N = f.N; e.M = f.M; e.mask = f.mask; e.nlevels = g.nlevels; e.pose6 = f.pose6; e.gr = f.gr;
+            e.raw = f.raw; e.raw_type = f.raw_type; e.N = f.N; e.M = f.M; e.mask = f.mask; e.nlevels = g.nlevels; e.pose6 = f.pose6; e.gr = f.gr;
             e.rowsum = (double*)(S + L.rowsum); e.rowmin = (double*)(S + L.rowmin); e.stats = (double*)(S + L.stats);
             for (int l = 0; l < DSSS_MAX_LEVELS; ++l) { e.lvl[l] = l < g.nlevels ? f.lvl[l] : nullptr; e.rows[l] = l < g.nlevels ? g.rows[l] : 0; e.cols[l] = l < g.nlevels ? g.cols[l] : 0; }
             e.cells = g.d_cells; e.ncells = (int)g.cells.size(); e.cell_cap = g.cell_cap;
@@ -1173,6 +1283,7 @@ struct ex_run {
             e.err = d_errs + s; e.kout = c->kps + (size_t)id * c->kcap; e.dout = c->desc + (size_t)id * c->kcap * 32; e.geo = c->geo + (size_t)id * c->kcap * 2; e.count = c->nkp_dev + id;
             bt.maxN = std::max(bt.maxN, f.N); bt.max_tot = std::max(bt.max_tot, (size_t)f.N * f.M); bt.max_levels = std::max(bt.max_levels, g.nlevels);
             bt.max_cw = std::max(bt.max_cw, g.cell_wmax); bt.max_ch = std::max(bt.max_ch, g.cell_hmax); bt.w_tot += (double)f.N * f.M;
+            bt.types |= 1u << f.raw_type; bt.w_raw += (double)f.raw_bytes(); bt.max_groups[f.raw_type] = std::max(bt.max_groups[f.raw_type], (size_t)f.N * f.M / normalize_group(f.raw_type));
             for (int l = 0; l < g.nlevels; ++l) { bt.max_rows[l] = std::max(bt.max_rows[l], g.rows[l]); bt.max_cols[l] = std::max(bt.max_cols[l], g.cols[l]); }
             // quadtree descriptors, level-major: the instances of level l are one launch
             int* const out_idx = (int*)(S + L.out_idx); int* const out_n = (int*)(S + L.out_n);
@@ -1195,11 +1306,11 @@ struct ex_run {
         HIPCHK(c, hipMemcpyAsync(T0, P0, T.err, hipMemcpyHostToDevice, st));
         HIPCHK(c, hipEventRecord(c->ex_side_ev[2], st)); c->ex_tab_uploaded = true;      // once it fired the pinned tables may be written again (fill_tables)
         HIPCHK(c, hipMemsetAsync(d_errs, 0, sizeof(int) * nb, st));
-        { dsss_scope sc(c, DSSS_K_ROW_REDUCE, 8.0 * w_tot); hipLaunchKernelGGL(row_reduce_kernel, dim3((bt.maxN + 3) / 4, nb), dim3(256), 0, st, d_exf); }
+        { dsss_scope sc(c, DSSS_K_ROW_REDUCE, bt.w_raw); launch_row_reduce(bt.types, dim3((bt.maxN + 3) / 4, nb), st, d_exf); }
         { dsss_scope sc(c, DSSS_K_PRE_MISC, 1.0 * w_tot, 2);
           hipLaunchKernelGGL(final_reduce_kernel, dim3(nb), dim3(64), 0, st, d_exf, (double)(float)c->mp.factor);
           hipLaunchKernelGGL(mask_init_kernel, dim3((unsigned)((bt.max_tot / 16 + 256) / 256), nb), dim3(256), 0, st, d_exf, c->mp.width, c->mp.side, (double)c->mp.side * 0.6); }
-        { dsss_scope sc(c, DSSS_K_NORMALIZE, 9.0 * w_tot); hipLaunchKernelGGL(normalize_kernel, dim3((unsigned)((bt.max_tot / 4 + 256) / 256), nb), dim3(256), 0, st, d_exf, c->mp.r); }
+        { dsss_scope sc(c, DSSS_K_NORMALIZE, bt.w_raw + w_tot); launch_normalize(bt.types, bt.max_groups, nb, st, d_exf, c->mp.r); }
         { dsss_scope sc(c, DSSS_K_PYRAMID, (1.906 + 2.74) * w_tot, std::max(bt.max_levels - 1, 1));
           for (int l = 1; l < bt.max_levels; ++l) {
               bool strips = false, rest = false;
@@ -1351,6 +1462,33 @@ int dsss_host_quadtree(const float* x, const float* y, const float* resp, int n,
     dsss_quadtree_cull(x, y, resp, n, minX, maxX, minY, maxY, quota, keep);
     for (size_t i = 0; i < keep.size(); ++i) keep_idx[i] = keep[i];
     if (n_keep) *n_keep = (int)keep.size();
+    return DSSS_OK;
+}
+
+// the row reduce and the final reduce of ONE frame, the kernels of the extraction, into a buffer of its own: [record | rowsum | rowmin | stats]
+int dsss_frame_raw_stats(dsss_ctx* c, int id, double* stats2)
+{
+    if (!c || !stats2) return DSSS_E_ARG;
+    if (id < 0 || id >= c->max_frames) DSSS_FAIL(c, DSSS_E_ARG, "frame id %d out of range", id);
+    dsss_frame& f = c->frames[id];
+    if (!f.has_geom || !f.has_raw) DSSS_FAIL(c, DSSS_E_STATE, "frame %d has no raw image (dsss_frame_set with raw != NULL first)", id);
+    if (f.raw_pending) DSSS_FAIL(c, DSSS_E_STATE, "frame %d: the upload of its page-locked image is still pending (dsss_extract* first)", id);
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t rec = (sizeof(ex_frame) + 255) & ~(size_t)255, rows = ((size_t)f.N * sizeof(double) + 255) & ~(size_t)255;
+    dsss_buf tmp{"raw_stats"};
+    if (const int rc = tmp.reserve(c, rec + 2 * rows + 4 * sizeof(double))) return rc;
+    ex_frame e = {};
+    e.raw = f.raw; e.raw_type = f.raw_type; e.N = f.N; e.M = f.M;
+    e.rowsum = (double*)(tmp.as<char>() + rec); e.rowmin = (double*)(tmp.as<char>() + rec + rows); e.stats = (double*)(tmp.as<char>() + rec + 2 * rows);
+    double out[2] = { 0, 0 };
+    HIPCHK(c, hipMemcpyAsync(tmp.p, &e, sizeof e, hipMemcpyHostToDevice, c->stream));
+    launch_row_reduce(1u << f.raw_type, dim3((f.N + 3) / 4, 1), c->stream, tmp.as<ex_frame>());
+    hipLaunchKernelGGL(final_reduce_kernel, dim3(1), dim3(64), 0, c->stream, tmp.as<ex_frame>(), (double)(float)c->mp.factor);
+    hipError_t he = hipGetLastError();
+    if (he == hipSuccess) he = hipMemcpyAsync(out, e.stats, sizeof out, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t hs = hipStreamSynchronize(c->stream);      // (e and out are on this stack: nothing returns before the stream is done with them)
+    HIPCHK(c, he); HIPCHK(c, hs);
+    stats2[0] = out[0]; stats2[1] = out[1];
     return DSSS_OK;
 }
 

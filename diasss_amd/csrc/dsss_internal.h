@@ -59,10 +59,12 @@ struct dsss_frame {
     int N = 0, M = 0;
     bool has_geom = false, has_raw = false, has_feat = false, has_norm = false;
     bool has_sift = false;            // the frame's rows of desc128 are valid (extracted with DSSS_DESC_SIFT128 or imported)
-    const double* raw = nullptr;      // device; borrowed when the caller passed a device pointer
-    dsss_buf raw_owned{"raw_owned"};  // device; owned copy of a host image (N x M doubles)
-    const double* raw_host = nullptr; // page-locked host image whose upload is still pending (dsss_extract_many streams it in under the kernels)
+    const void* raw = nullptr;        // device; borrowed when the caller passed a device pointer
+    int raw_type = DSSS_RAW_F64;      // element type of raw (dsss_raw_type)
+    dsss_buf raw_owned{"raw_owned"};  // device; owned copy of a host image (at least raw_bytes(): a re-set with a wider type regrows it, a narrower one keeps the block)
+    const void* raw_host = nullptr;   // page-locked host image whose upload is still pending (dsss_extract_many streams it in under the kernels)
     bool raw_pending = false;
+    size_t raw_bytes() const { return (size_t)N * M * dsss_raw_type_size(raw_type); }
     double* pose6 = nullptr;          // device N x 6
     double* alt = nullptr;            // device N
     double* gr = nullptr;             // device M/2

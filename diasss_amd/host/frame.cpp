@@ -13,10 +13,22 @@ Frame::Frame(const int &id, const cv::Mat &mImg, const cv::Mat &mPose, const std
     raw_img = mImg; dr_poses = mPose; altitudes = vAltt; ground_ranges = vGrange; img_id = id; anno_kps = mAnno;
     tf_stb = {0, 0, 0}; tf_port = {0, 0, 0};                                  // frame.cpp:38-39
     dsss_ctx* c = Device::ctx();
-    Device::check(dsss_frame_set(c, id, mImg.ptr<double>(), mImg.rows, mImg.cols, mPose.ptr<double>(), vAltt.data(), vGrange.data()),
-                  "dsss_frame_set");
+    // the waterfall goes down in the type it has (CV_8U, CV_16U, CV_32F or CV_64F): the library widens on the device, with the
+    // results of the CV_64F image of the same samples
+    const int raw_type = RawType(mImg);
+    if (raw_type < 0) throw std::runtime_error("Frame: the waterfall must be CV_8U, CV_16U, CV_32F or CV_64F");
+    Device::check(dsss_frame_set_typed(c, id, mImg.ptr<unsigned char>(), raw_type, mImg.rows, mImg.cols, mPose.ptr<double>(), vAltt.data(), vGrange.data()),
+                  "dsss_frame_set_typed");
     geo_img = GetGeoImg(mImg.rows, mImg.cols, mPose, vGrange, tf_stb, tf_port);
     DetectFeature(norm_img, flt_mask, kps, dst);
+}
+
+int Frame::RawType(const cv::Mat &mImg)
+{
+    switch (mImg.type()) {
+    case CV_64F: return DSSS_RAW_F64; case CV_32F: return DSSS_RAW_F32; case CV_16U: return DSSS_RAW_U16; case CV_8U: return DSSS_RAW_U8;
+    default: return -1;
+    }
 }
 
 void Frame::DetectFeature(const cv::Mat &, const cv::Mat &, std::vector<cv::KeyPoint> &out_kps, cv::Mat &out_dst)

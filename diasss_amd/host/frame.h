@@ -14,7 +14,7 @@ namespace Diasss
 
     public:
 
-        // Constructor (frame.h:19-20): id, CV_64F NxM waterfall, CV_64F Nx6 DR poses, altitudes[N], ground ranges[M/2], annotations
+        // Constructor (frame.h:19-20): id, NxM waterfall (CV_64F as the reference loads it, or CV_8U / CV_16U / CV_32F as recorded: handed down untouched), CV_64F Nx6 DR poses, altitudes[N], ground ranges[M/2], annotations
         Frame(const int &id, const cv::Mat &mImg, const cv::Mat &mPose, const std::vector<double> &vAltt,
               const std::vector<double> &vGrange, const cv::Mat &mAnno);
 
@@ -47,6 +47,7 @@ namespace Diasss
         // The reference hard-codes its descriptor: the live call is the SIFT one (ORBextractor.cpp:1097-1098), whose output is lost.
         // false (default): the ORB configuration; true: ORB keypoints + the 128-float rows (DSSS_DESC_SIFT128).  Set before constructing frames.
         static bool USE_SIFT;
+        static int RawType(const cv::Mat &mImg);      // dsss_raw_type of a waterfall's cv type, -1 when the library does not take it
         cv::Mat corres_kps;            // rows: frame_id, ref_frame_id, kp_y, kp_x, kp_ref_y, kp_ref_x (CV_64F)
         cv::Mat est_poses;
 

@@ -3,6 +3,8 @@
 //   test_demo --image DIR --pose DIR --altitude DIR --groundrange DIR [--annotation DIR] [--min-overlap X] [--descriptor orb|orb-l2|sift] [--use-anno 0|1] [--add-lc 0|1] [--eval 0..3]
 //       the reference's own layout (diasss2.cpp:33-66) through Util::LoadInputData: OpenCV FileStorage XML / YAML + txt
 //   test_demo <dir with frame_%03d.bin> [min_overlap]
+//   either form: --raw-type u8|u16|f32|f64 hands every loaded waterfall to Frame in that sample type (f64: as loaded); a sample the type
+//   cannot hold exactly ends the run with a message
 //       flat binary dumps written by tools/export_survey.py:
 //       frame_%03d.bin = int32 N, int32 M, f64 raw[N*M], f64 pose[N*6], f64 alt[N], f64 gr[M/2]
 #include <cstdio>
@@ -17,8 +19,20 @@ using namespace Diasss;
 
 int main(int argc, char** argv)
 {
-    if (argc < 2) { std::cout << "usage: test_demo <dir with frame_%03d.bin> [min_overlap]  |  test_demo --image D --pose D --altitude D --groundrange D [--annotation D]" << std::endl; return 0; }
+    if (argc < 2) { std::cout << "usage: test_demo <dir with frame_%03d.bin> [min_overlap]  |  test_demo --image D --pose D --altitude D --groundrange D [--annotation D]  |  either with --raw-type u8|u16|f32|f64" << std::endl; return 0; }
     float MIN_OVERLAP = 0.4f;                                                    // diasss2.cpp:28
+    int raw_cv_type = CV_64F;
+    for (int a = 1; a + 1 < argc; ++a) if (std::string(argv[a]) == "--raw-type") {
+        const std::string v = argv[a + 1];
+        if (v == "u8") raw_cv_type = CV_8U; else if (v == "u16") raw_cv_type = CV_16U; else if (v == "f32") raw_cv_type = CV_32F; else if (v == "f64") raw_cv_type = CV_64F;
+        else { std::cout << "--raw-type " << v << ": u8, u16, f32 or f64" << std::endl; return 1; }
+    }
+    auto typed = [&](const cv::Mat &img, size_t i, cv::Mat &out) {
+        std::string why;
+        if (Util::ConvertRaw(img, raw_cv_type, out, why)) return true;
+        std::cout << "frame " << i << ": --raw-type refused, " << why << std::endl;
+        return false;
+    };
     std::vector<Frame> test_frames;
     const bool folders = std::string(argv[1]).rfind("--", 0) == 0;
     if (folders) {
@@ -40,11 +54,12 @@ int main(int argc, char** argv)
         Util::LoadInputData(dI, dP, dA, dG, dN, vmImgs, vmPoses, vvAltts, vvGranges, vmAnnos);
         if (vmPoses.size() != vmImgs.size() || vvAltts.size() != vmImgs.size() || vvGranges.size() != vmImgs.size()) { std::cout << "folder sizes differ" << std::endl; return 1; }
         for (size_t i = 0; i < vmImgs.size(); ++i) {                             // diasss2.cpp:83-86
-            cv::Mat anno = i < vmAnnos.size() ? vmAnnos[i] : cv::Mat();
-            test_frames.push_back(Frame((int)i, vmImgs[i], vmPoses[i], vvAltts[i], vvGranges[i], anno));
+            cv::Mat anno = i < vmAnnos.size() ? vmAnnos[i] : cv::Mat(), img;
+            if (!typed(vmImgs[i], i, img)) return 1;
+            test_frames.push_back(Frame((int)i, img, vmPoses[i], vvAltts[i], vvGranges[i], anno));
             std::cout << "frame " << i << ": " << vmImgs[i].rows << " x " << vmImgs[i].cols << ", " << test_frames.back().kps.size() << " keypoints" << std::endl;
         }
-    } else if (argc > 2) MIN_OVERLAP = (float)atof(argv[2]);
+    } else if (argc > 2 && std::string(argv[2]).rfind("--", 0) != 0) MIN_OVERLAP = (float)atof(argv[2]);
     for (int i = 0; !folders; ++i) {
         char path[512];
         snprintf(path, sizeof path, "%s/frame_%03d.bin", argv[1], i);
@@ -57,7 +72,9 @@ int main(int argc, char** argv)
         size_t ok = fread(img.data(), 8, (size_t)N * M, f) + fread(pose.data(), 8, (size_t)N * 6, f) + fread(alt.data(), 8, N, f) + fread(gr.data(), 8, M / 2, f);
         fclose(f);
         if (ok != (size_t)N * M + (size_t)N * 6 + N + M / 2) { std::cout << "short read: " << path << std::endl; return 1; }
-        test_frames.push_back(Frame(i, img, pose, alt, gr, anno));
+        cv::Mat timg;
+        if (!typed(img, (size_t)i, timg)) return 1;
+        test_frames.push_back(Frame(i, timg, pose, alt, gr, anno));
         std::cout << "frame " << i << ": " << N << " x " << M << ", " << test_frames.back().kps.size() << " keypoints" << std::endl;
     }
     for (size_t i = 0; i < test_frames.size(); i++)

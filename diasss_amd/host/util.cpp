@@ -4,6 +4,7 @@
 #include "filestorage.h"
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <filesystem>
 #include <fstream>
 #include <iostream>
@@ -89,3 +90,38 @@ void Util::LoadInputData(const std::string &strImageFolder, const std::string &s
 }
 
 } // namespace Diasss
+
+namespace Diasss
+{
+
+template <typename T> static bool convert_exact(const cv::Mat &src, cv::Mat &out, std::string &why)
+{
+    for (int i = 0; i < src.rows; ++i) {
+        const double *s = src.ptr<double>(i); T *d = out.ptr<T>(i);
+        for (int j = 0; j < src.cols; ++j) {
+            const double v = s[j];
+            bool ok;                                                              // (the range first: a cast out of range is undefined)
+            if (sizeof(T) == 4) ok = v != v || std::isinf(v) || (std::fabs(v) <= 3.4028234663852886e38 && (double)(T)v == v);      // a float NaN or infinity is the double's
+            else ok = v >= 0.0 && v <= (sizeof(T) == 1 ? 255.0 : 65535.0) && (double)(T)v == v;
+            if (!ok) {
+                char b[160]; snprintf(b, sizeof b, "sample (%d, %d) = %.17g is not representable", i, j, v);
+                why = b; return false;
+            }
+            d[j] = (T)v;
+        }
+    }
+    return true;
+}
+
+bool Util::ConvertRaw(const cv::Mat &img64, int cv_type, cv::Mat &out, std::string &why)
+{
+    if (img64.type() != CV_64F) { why = "the loaded waterfall is not CV_64F"; return false; }
+    if (cv_type == CV_64F) { out = img64; return true; }
+    out = cv::Mat(img64.rows, img64.cols, cv_type);
+    if (cv_type == CV_32F) return convert_exact<float>(img64, out, why);
+    if (cv_type == CV_16U) return convert_exact<unsigned short>(img64, out, why);
+    if (cv_type == CV_8U) return convert_exact<unsigned char>(img64, out, why);
+    why = "unknown sample type"; return false;
+}
+
+}

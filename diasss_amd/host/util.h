@@ -22,6 +22,9 @@ namespace Diasss
                                   const std::string &strGroundRangeFolder, const std::string &strAnnotationFolder,
                                   std::vector<cv::Mat> &vmImgs, std::vector<cv::Mat> &vmPoses, std::vector<std::vector<double>> &vvAltts,
                                   std::vector<std::vector<double>> &vvGranges, std::vector<cv::Mat> &vmAnnos);
+        // a CV_64F waterfall in the sample type a sonar records (CV_8U, CV_16U, CV_32F; CV_64F is the image itself).  Exact or not at all:
+        // false, with the first sample that the type cannot hold in `why`, instead of rounding or clamping it.
+        static bool ConvertRaw(const cv::Mat &img64, int cv_type, cv::Mat &out, std::string &why);
     };
 
 }

@@ -90,7 +90,8 @@ class Pipeline:
     def prepare(self, raws, poses, alts, grs):
         """the argument arrays of dsss_frames_set for one survey, built and validated ONCE (capi.FramesArgs: what a C++ caller of the C ABI
         holds anyway); run(prepared) / set_frames(prepared) then go straight to the C call.  raws[f] may be None for frames this rank
-        does not extract."""
+        does not extract.  A waterfall goes down in its own sample type (uint8, uint16, float32 or float64, frame by frame): nothing is
+        widened here, and the results are those of the float64 image of the same samples."""
         N = [p.shape[0] for p in poses]; M = [2 * len(g) for g in grs]
         args = self.ctx.frames_args(list(range(self.F)), raws, N, M, poses, alts, grs) if hasattr(self.ctx, "frames_args") else None
         return dict(args=args, N=N, M=M, raws=raws, poses=poses, alts=alts, grs=grs)

@@ -41,6 +41,20 @@ def seafloor_tile(seed, P=2048):
     return np.clip(tex, 0.15, 2.3).astype(np.float32)
 
 
+def quantise(img, dtype):
+    """a float64 waterfall in another sample type (Survey.frame)"""
+    name = str(np.dtype(dtype)) if not isinstance(dtype, (str, torch.dtype)) else str(dtype).replace("torch.", "")
+    if name == "float64":
+        return img
+    if name == "float32":
+        return img.to(torch.float32)
+    if name == "uint16":
+        return torch.clamp(torch.round(img), 0, 65535).to(torch.uint16)
+    if name == "uint8":
+        return torch.clamp(torch.round(img / 16), 0, 255).to(torch.uint8)
+    raise TypeError("waterfall dtype %s: uint8, uint16, float32 or float64 expected" % name)
+
+
 class Survey:
     """F legs of N pings x M bins."""
 
@@ -101,8 +115,12 @@ class Survey:
         b = T[iv1, iu] * (1 - fu) + T[iv1, iu1] * fu
         return a * (1 - fv) + b * fv
 
-    def frame(self, f):
-        """raw N x M float64 waterfall of leg f rendered from the TRUE poses (torch tensor on self.device)"""
+    def frame(self, f, dtype=None):
+        """raw N x M waterfall of leg f rendered from the TRUE poses (torch tensor on self.device).  dtype None: float64, as rendered.
+        Otherwise the same waterfall as a sonar would record it (a torch or numpy dtype, or its name): "uint16" rounds and clamps
+        to 65535, "uint8" rounds a sixteenth of the value and clamps to 255, "float32" rounds to the nearest float."""
+        if dtype is not None:
+            return quantise(self.frame(f), dtype)
         N, M = self.N, self.M
         half = M // 2
         dev = self.device

@@ -130,6 +130,25 @@ int dsss_frame_set(dsss_ctx*, int id, const double* raw, int N, int M,
  * list of frames or dsss_extract make the extraction run again from the start.                                                          */
 int dsss_frames_set(dsss_ctx*, int n, const int* ids, const double* const* raw, const int* N, const int* M,
                     const double* const* pose6, const double* const* alt, const double* const* grange);
+/* TYPED WATERFALLS.  Side-scan samples are 8- or 16-bit integers, or floats: the raw image may be handed over as it is instead of
+ * widened to double on the host.  Results are those of the double path on (double)sample, bit for bit (every widening is exact; NaN and
+ * infinities of a float behave as their doubles do).  dsss_frame_set / dsss_frames_set are the DSSS_RAW_F64 case of these; residency,
+ * lifetime and the eager start are the same for every type, and one dsss_frames_set_typed call may mix types.  A device pointer need only
+ * be aligned to its element.  An unknown raw_type is DSSS_E_ARG before anything is touched.                                             */
+typedef enum { DSSS_RAW_F64 = 0, DSSS_RAW_F32 = 1, DSSS_RAW_U16 = 2, DSSS_RAW_U8 = 3 } dsss_raw_type;
+size_t dsss_raw_type_size(int raw_type);                       /* 8, 4, 2, 1; 0 for anything else.  Needs no context */
+int dsss_frame_set_typed(dsss_ctx*, int id, const void* raw, int raw_type, int N, int M,
+                         const double* pose6, const double* alt, const double* grange);
+int dsss_frames_set_typed(dsss_ctx*, int n, const int* ids, const void* const* raw, const int* raw_type /* n; NULL: all DSSS_RAW_F64 */,
+                          const int* N, const int* M, const double* const* pose6, const double* const* alt,
+                          const double* const* grange);
+/* what the context holds for a frame (any output may be NULL): the type, where the image lives (0 none, 1 borrowed device pointer,
+ * 2 owned device copy, 3 owned device copy whose upload from a page-locked host image is still pending), the bytes of the owned copy,
+ * N M dsss_raw_type_size (0 when borrowed or none)                                                                                      */
+int dsss_frame_raw_info(dsss_ctx*, int id, int* raw_type, int* where, size_t* owned_bytes);
+/* mean and minimum of the raw image as the extraction computes them (the fixed summation tree), on demand, off the hot path:
+ * stats2_host = { mean, min }.  DSSS_E_STATE while the frame has no image or its upload is still pending.                               */
+int dsss_frame_raw_stats(dsss_ctx*, int id, double* stats2_host);
 /* GetNormalizeSSS + GetFilteredMask + DetectFeature (frame.cpp:57-124,167-203) with the ORB descriptor
  * configuration of thirdparty/ORBextractor.cpp (operator() :1049-1113).  Features stay on the device.
  * Accepted geometries: N, M below 65536, N M below 2^31, every pyramid level at least 69 px each way (DSSS_E_ARG otherwise).  The
