@@ -69,6 +69,21 @@ class RegResult(C.Structure):
 REG_DTYPE = np.dtype(RegResult)          # the rows Context.mosaic_register returns
 
 
+class RegSeg(C.Structure):
+    """dsss_reg_seg: one (pair, segment) row of the registration by segments: pair = index into the pair list, pings [p0, p1) of the
+    pair's frame b, r = the RegResult of the segment's table, sx, sy = sum of ix, iy over the overlapping cells at the peak shift"""
+    _fields_ = [("pair", C.c_int32), ("seg", C.c_int32), ("p0", C.c_int32), ("p1", C.c_int32), ("r", RegResult),
+                ("sx", C.c_int64), ("sy", C.c_int64)]
+
+
+REGSEG_DTYPE = np.dtype(RegSeg)          # the rows Context.mosaic_register_segments returns (field "r" is a REG_DTYPE record)
+
+
+class RegEdgeParams(C.Structure):
+    """dsss_reg_edge_params: the lowest ZNCC of an accepted segment, sigma of the offset in cells, of the height (m), of the rotation (rad)"""
+    _fields_ = [("min_zncc", C.c_double), ("sigma_xy_cells", C.c_double), ("sigma_z", C.c_double), ("sigma_rot", C.c_double)]
+
+
 class PGGateParams(C.Structure):
     """dsss_pg_gate_params: chi-square gate, the factor between the worst kept edge and the threshold of a round, solves at most"""
     _fields_ = [("gate", C.c_double), ("decade", C.c_double), ("max_solves", C.c_int32), ("pad_", C.c_int32)]
@@ -210,6 +225,17 @@ def lib():
                                            C.c_int, C.POINTER(RegParams), C.c_void_p, C.c_void_p]
         L.dsss_mosaic_register_peak.restype = C.c_int
         L.dsss_mosaic_register_peak.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.POINTER(RegResult)]
+        L.dsss_mosaic_register_segments.restype = C.c_int
+        L.dsss_mosaic_register_segments.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(MosaicParams), C.c_void_p, C.c_void_p,
+                                                    C.c_int, C.c_int, C.POINTER(RegParams), C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p]
+        L.dsss_reg_edge_params_default.restype = None
+        L.dsss_reg_edge_params_default.argtypes = [C.POINTER(RegEdgeParams)]
+        L.dsss_register_edge.restype = C.c_int
+        L.dsss_register_edge.argtypes = [C.c_void_p, C.POINTER(MosaicParams), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                         C.POINTER(RegEdgeParams), C.c_void_p]
+        L.dsss_mosaic_register_edges.restype = C.c_int
+        L.dsss_mosaic_register_edges.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(MosaicParams), C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_int, C.POINTER(RegEdgeParams), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
         _LIB = L
     return _LIB
 
@@ -269,6 +295,32 @@ def mosaic_register_peak(sums, radius, min_cells, cell):
         e.code = rc
         raise e
     return out
+
+
+def reg_edge_params_default():
+    e = RegEdgeParams(); lib().dsss_reg_edge_params_default(C.byref(e)); return e
+
+
+def register_edge(seg, grid, rows_a, base_a, rows_b, base_b, params=None):
+    """dsss_register_edge: one row of REGSEG_DTYPE (or a RegSeg) as a pose-graph edge.  rows_a, rows_b: the "r p y x y z" rows of the
+    pair's two frames under the registered trajectory, base_a, base_b: the pose-graph index of each frame's first ping, params: a
+    RegEdgeParams (None = the defaults) -> a record of LCEDGE_DTYPE, or None when the segment is rejected.  Host arithmetic, no context."""
+    L = lib()
+    if seg is not None and not isinstance(seg, RegSeg):
+        seg = RegSeg.from_buffer_copy(np.asarray(seg, REGSEG_DTYPE).tobytes())
+    if rows_a is not None:
+        rows_a = np.ascontiguousarray(rows_a, np.float64).reshape(-1, 6)
+    if rows_b is not None:
+        rows_b = np.ascontiguousarray(rows_b, np.float64).reshape(-1, 6)
+    edge = np.zeros(1, LCEDGE_DTYPE)
+    rc = L.dsss_register_edge(C.byref(seg) if seg is not None else None, C.byref(grid) if grid is not None else None,
+                              _ptr(rows_a), 0 if rows_a is None else len(rows_a), int(base_a), _ptr(rows_b), 0 if rows_b is None else len(rows_b),
+                              int(base_b), C.byref(params) if params is not None else None, _ptr(edge))
+    if rc < 0:
+        e = DsssError("dsss_register_edge: %s" % L.dsss_strerror(rc).decode())
+        e.code = rc
+        raise e
+    return edge[0] if rc == 1 else None
 
 
 class Context:
@@ -715,6 +767,47 @@ class Context:
         self._chk(self.L.dsss_mosaic_register(self.h, _ptr(ids), len(ids), _ptr(rpy6), _ptr(ping_off), C.byref(params), _ptr(pa), _ptr(pb),
                                               len(pairs), C.byref(r), _ptr(out), _ptr(sums)), "dsss_mosaic_register")
         return (out, sums) if want_sums else out
+
+    def mosaic_register_segments(self, ids, params, pairs, seg_pings, reg=None, rpy6=None, ping_off=None, want_sums=False, cap=None):
+        """the registration of mosaic_register with frame b of every pair cut into segments of seg_pings pings, each slid over the whole
+        of frame a -> rows of REGSEG_DTYPE, by pair and then by segment: the pair's index, the segment and its pings [p0, p1), the
+        record r of the segment's table, and the centroid sums sx, sy of the overlapping cells at the peak.  want_sums=True returns
+        (rows, sums) with sums[nseg, 2 r + 1, 2 r + 1, 6] uint64.  cap: room for that many rows (None: as many as there will be)."""
+        ids, rpy6, ping_off = self._mosaic_traj(ids, rpy6, ping_off)
+        pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        pa = np.ascontiguousarray(pairs[:, 0]); pb = np.ascontiguousarray(pairs[:, 1])
+        r = reg if reg is not None else reg_params_default()
+        S = 2 * max(0, min(int(r.radius), 16)) + 1
+        args = (self.h, _ptr(ids), len(ids), _ptr(rpy6), _ptr(ping_off), C.byref(params), _ptr(pa), _ptr(pb), len(pairs), int(seg_pings), C.byref(r))
+        nseg = C.c_int(0)
+        if cap is None:                                    # the library counts the rows before it launches anything: ask with no room
+            one = np.zeros(1, REGSEG_DTYPE)
+            rc = self.L.dsss_mosaic_register_segments(*args, _ptr(one), 0, C.byref(nseg), None)
+            if rc != -5:                                   # DSSS_E_CAPACITY: nseg rows are needed; 0: there are none; anything else is an error
+                self._chk(rc, "dsss_mosaic_register_segments")
+            cap = nseg.value
+        out = np.zeros(max(cap, 1), REGSEG_DTYPE)
+        sums = np.zeros((max(cap, 1), S, S, 6), np.uint64) if want_sums else None
+        self._chk(self.L.dsss_mosaic_register_segments(*args, _ptr(out), int(cap), C.byref(nseg), _ptr(sums)), "dsss_mosaic_register_segments")
+        out = out[:nseg.value]
+        return (out, sums[:nseg.value]) if want_sums else out
+
+    def mosaic_register_edges(self, ids, params, pairs, segs, edge_params=None, rpy6=None, ping_off=None, cap=None):
+        """register_edge on every row of segs (REGSEG_DTYPE, as mosaic_register_segments returned them for `pairs`) under the trajectory
+        that was registered -> (edges, edge_seg): the accepted rows as LCEDGE_DTYPE records over the pose-graph indices ping_off[i] + ping
+        (ping_off None: the frames of ids one behind the other), and the row each edge came from.  Launches no GPU work."""
+        ids, rpy6, ping_off = self._mosaic_traj(ids, rpy6, ping_off)
+        pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        pa = np.ascontiguousarray(pairs[:, 0]); pb = np.ascontiguousarray(pairs[:, 1])
+        segs = np.ascontiguousarray(segs, REGSEG_DTYPE)
+        if len(segs) and (segs["pair"].min() < 0 or segs["pair"].max() >= len(pairs)):
+            raise ValueError("mosaic_register_edges: a row names a pair outside the %d given" % len(pairs))
+        cap = len(segs) if cap is None else int(cap)
+        edges = np.zeros(max(cap, 1), LCEDGE_DTYPE); src = np.zeros(max(cap, 1), np.int32); ne = C.c_int(0)
+        self._chk(self.L.dsss_mosaic_register_edges(self.h, _ptr(ids), len(ids), _ptr(rpy6), _ptr(ping_off), C.byref(params), _ptr(pa), _ptr(pb),
+                                                    _ptr(segs), len(segs), C.byref(edge_params) if edge_params is not None else None,
+                                                    _ptr(edges), _ptr(src), cap, C.byref(ne)), "dsss_mosaic_register_edges")
+        return edges[:ne.value].copy(), src[:ne.value].copy()
 
     # ---- instrumentation
     def profile(self, on=True):

@@ -181,6 +181,7 @@ struct dsss_ctx {
     dsss_buf pg_warm{"pg_warm"}; int pg_warm_n = 0;   // pose_t[pg_warm_n]
     std::vector<dsss_lc_edge> pg_inc_edges; unsigned long long lc_gen = 0, pg_inc_gen = 0;    // lc_gen counts LC result sets; the last one consumed
     dsss_buf mosaic_buf{"mosaic_buf"};                                        // device scratch of dsss_mosaic_*: accumulators, output layers, job table, trajectory rows (kept between calls)
+    dsss_buf mosaic_pinned{"mosaic_pinned", DSSS_PINNED};                     // page-locked landing area of the segment registration's table of sums (140 MB at the headline size: a pageable copy into fresh memory cost more than the kernels)
     dsss_buf pgr_buf{"pgr_buf"};                                           // device scratch of dsss_posegraph_edge_report (dsss_pg_report.hip), kept between calls
     dsss_prof prof;
 };

@@ -13,8 +13,13 @@ namespace {
 // the wavefront and the last lane of the run issues ONE 64-bit atomic without return, count in the high word and sum in the low
 // one.  A wavefront adds at most 64 x 255 to a sum, and below 2^24 samples per cell (checked by mosaic_unpack_kernel) the low word
 // cannot carry into the high one.  (One atomic per pixel took 13.3 ms where this takes 6.7: DESIGN.md section 4, "Mosaic".)
-__global__ __launch_bounds__(256) void mosaic_scatter_kernel(const mosaic_job* __restrict__ jobs, int njobs, mosaic_win G,
-                                                             unsigned long long* __restrict__ acc)
+//
+// SEG: the segmented form of the registration's segment layers.  The ping's segment (row / seg_pings) selects the window (ox, oy, bw, bh
+// of G are replaced by the segment's) and the accumulator area (acc + the segment's offset), so one launch renders every segment of a
+// frame; everything else, the arithmetic of a sample included, is the one body.
+template <bool SEG>
+__device__ __forceinline__ void mosaic_scatter_body(const mosaic_job* __restrict__ jobs, int njobs, mosaic_win G, unsigned long long* __restrict__ acc,
+                                                    const mosaic_seg* __restrict__ segs, int seg_pings)
 {
     __shared__ double s_sc[4];
     int lo = 0, hi = njobs - 1;
@@ -22,6 +27,11 @@ __global__ __launch_bounds__(256) void mosaic_scatter_kernel(const mosaic_job* _
     const mosaic_job J = jobs[lo];
     const int row = (int)blockIdx.x - J.blk0, M = J.M, half = M / 2;
     if (row >= J.N) return;                                                        // (uniform per workgroup; cannot happen with the host's blk0)
+    if (SEG) {
+        const mosaic_seg sg = segs[row / seg_pings];
+        if (sg.bw <= 0) return;                                                    // a segment with no cell on the grid (uniform per workgroup)
+        G.ox = sg.ox; G.oy = sg.oy; G.bw = sg.bw; G.bh = sg.bh; acc += sg.off;
+    }
     const double* P = J.pose + (size_t)row * 6;
     if (threadIdx.x < 2) dsss_geo_side(P, threadIdx.x == 1, &s_sc[2 * threadIdx.x], &s_sc[2 * threadIdx.x + 1]);
     __syncthreads();
@@ -50,6 +60,18 @@ __global__ __launch_bounds__(256) void mosaic_scatter_kernel(const mosaic_job* _
         const bool tail = lane == 63 || ((hb >> (lane + 1)) & 1ull);
         if (tail && key >= 0) atomicAdd(&acc[key], ((unsigned long long)(v >> 16) << 32) | (v & 0xffffu));
     }
+}
+
+__global__ __launch_bounds__(256) void mosaic_scatter_kernel(const mosaic_job* __restrict__ jobs, int njobs, mosaic_win G,
+                                                             unsigned long long* __restrict__ acc)
+{
+    mosaic_scatter_body<false>(jobs, njobs, G, acc, nullptr, 1);
+}
+
+__global__ __launch_bounds__(256) void mosaic_scatter_seg_kernel(const mosaic_job* __restrict__ jobs, int njobs, mosaic_win G,
+                                                                 unsigned long long* __restrict__ acc, const mosaic_seg* __restrict__ segs, int seg_pings)
+{
+    mosaic_scatter_body<true>(jobs, njobs, G, acc, segs, seg_pings);
 }
 
 // accumulators -> the host layers' layout; flags a cell over the sample limit (also run with no outputs, as the check alone)
@@ -118,7 +140,10 @@ int mosaic_check_params(dsss_ctx* c, const dsss_mosaic_params* p)
 // geo extremes of one frame under the given pose rows: x = px + g c is monotone in g for a fixed bearing, so only the smallest and the
 // largest ground range of a side can be extreme (what geo_bbox_kernel evaluates).  On the host: two bearings per ping, off the hot
 // path, and the same arithmetic bit for bit.  Non-finite points compare false and are left out.
-void frame_extent(const dsss_frame& f, const double* rows, double* bb)
+void frame_extent(const dsss_frame& f, const double* rows, double* bb) { frame_extent_rows(f, rows, 0, f.N, bb); }
+
+// the same over the pings [r0, r1) of the frame (the registration's segments)
+void frame_extent_rows(const dsss_frame& f, const double* rows, int r0, int r1, double* bb)
 {
     const double* gr = f.h_geo + (size_t)f.N * 7;
     const int M = f.M, half = M / 2;
@@ -134,7 +159,7 @@ void frame_extent(const dsss_frame& f, const double* rows, double* bb)
         }
         col_min[side] = cmin; col_max[side] = cmax;
     }
-    for (int row = 0; row < f.N; ++row) {
+    for (int row = r0; row < r1; ++row) {
         const double* P = rows + (size_t)row * 6;
         for (int side = 0; side < 2; ++side) {
             double s, co; dsss_geo_side(P, side == 1, &s, &co);
@@ -176,6 +201,11 @@ int upload_rows(dsss_ctx* c, const int* ids, int n, const double* rpy6, const in
 void launch_scatter(dsss_ctx* c, const mosaic_job* d_jobs, int njobs, int blocks, const mosaic_win& G, unsigned long long* acc)
 {
     hipLaunchKernelGGL(mosaic_scatter_kernel, dim3((unsigned)blocks), dim3(256), 0, c->stream, d_jobs, njobs, G, acc);
+}
+
+void launch_scatter_seg(dsss_ctx* c, const mosaic_job* d_job, int blocks, const mosaic_win& G, unsigned long long* acc, const mosaic_seg* d_segs, int seg_pings)
+{
+    hipLaunchKernelGGL(mosaic_scatter_seg_kernel, dim3((unsigned)blocks), dim3(256), 0, c->stream, d_job, 1, G, acc, d_segs, seg_pings);
 }
 
 extern "C" {

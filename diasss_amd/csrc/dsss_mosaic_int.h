@@ -12,6 +12,9 @@ struct mosaic_job { const double* pose; const double* gr; const uint8_t* img; co
 // the grid (x0, y0, cell, W, H: where a point falls and whether it is kept) and the window of it the accumulators cover
 // (ox, oy, bw, bh: the whole grid for the mosaic, one frame's cell bounding box for the consistency map and the registration)
 struct mosaic_win { double x0, y0, cell; int W, H, ox, oy, bw, bh, use_mask; };
+// one segment of a frame in the segmented scatter: its window of the grid (bw = 0: no cell of it lies on the grid) and where its
+// accumulators start, in cells, behind the frame's first
+struct mosaic_seg { int ox, oy, bw, bh; unsigned long long off; };
 
 // carves mosaic_buf into 256-byte aligned pieces
 struct carve { size_t off = 0; size_t take(size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; } };
@@ -19,6 +22,9 @@ struct carve { size_t off = 0; size_t take(size_t bytes) { const size_t o = off;
 int mosaic_check_frames(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, bool need_img, size_t* rows);
 int mosaic_check_params(dsss_ctx* c, const dsss_mosaic_params* p);
 void frame_extent(const dsss_frame& f, const double* rows, double* bb);
+void frame_extent_rows(const dsss_frame& f, const double* rows, int r0, int r1, double* bb);      // pings [r0, r1) only
 bool cell_range(double lo, double hi, double origin, double cell, int n, int* a, int* b);
 int upload_rows(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, double* d_rows, std::vector<const double*>& dev_rows);
 void launch_scatter(dsss_ctx* c, const mosaic_job* d_jobs, int njobs, int blocks, const mosaic_win& G, unsigned long long* acc);
+// the segmented form for ONE frame (d_job: its record, blk0 = 0; blocks = its pings): ping p goes into d_segs[p / seg_pings]
+void launch_scatter_seg(dsss_ctx* c, const mosaic_job* d_job, int blocks, const mosaic_win& G, unsigned long long* acc, const mosaic_seg* d_segs, int seg_pings);

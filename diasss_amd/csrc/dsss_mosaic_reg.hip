@@ -4,7 +4,12 @@
 // of the zero-normalised cross-correlation.  Score, peak, tie and sub-cell rules are host arithmetic on that table
 // (dsss_mosaic_register_peak), exact in integers up to one conversion per quantity, so a result is the same whatever the order of
 // frames, pairs, tiles and atomics.
+// Dense loop closures ("dense loop closures" in the header): the same registration with frame b cut into segments of pings
+// (dsss_mosaic_register_segments: one segmented scatter and one pack per frame, the correlation kernel through its job table,
+// mosaic_centroid_kernel for where the overlap lies), and a segment's offset as a pose-graph edge (dsss_register_edge, host arithmetic).
 #include "dsss_mosaic_int.h"
+#include "dsss_pose.h"
+#include "dsss_wave.h"
 #include <algorithm>
 
 #define REG_MAX_RADIUS 16
@@ -13,6 +18,8 @@
 #define REG_STRIP 8                        // tiles (along x) a workgroup walks before it flushes: 8 x 1024 x 255^2 < 2^32, the u32 partials cannot wrap
 #define REG_MAX_THREADS 1024
 #define REG_SLOTS 2                        // shifts per thread: (2 x 16 + 1)^2 = 1089 <= 2 x 1024
+#define CEN_TW 64                          // a workgroup of mosaic_centroid_kernel looks at 64 x 16 cells of a
+#define CEN_TH 16
 
 namespace {
 
@@ -117,6 +124,42 @@ __global__ __launch_bounds__(REG_MAX_THREADS) void mosaic_corr_kernel(const reg_
     }
 }
 
+// one (pair, segment) row with a peak: the two layers (windows as in reg_job), the a cells whose cell shifted by the peak (dx, dy) lies
+// in b's window as tiles of CEN_TW x CEN_TH, blk0 = its first workgroup, out = n, sum ix, sum iy
+struct cen_job {
+    const uint16_t* la; const uint16_t* lb; unsigned long long* out;
+    int aox, aoy, abw, box, boy, bbw;
+    int rx0, ry0, rx1, ry1;                // region, inclusive
+    int dx, dy, tiles_x, blk0;
+};
+
+// The centroid sums at the peak: n, sum ix, sum iy over the cells where a is valid and b is valid at the shifted cell, ix and iy in
+// grid cells.  One workgroup per tile, a thread looks at CEN_TH / 4 cells one below the other (a wavefront reads 64 neighbouring
+// half-words of a row), the three sums are added up over the wavefront (dsss_wave_sum) and leave as 64-bit atomics without return,
+// only where n > 0.  Integers: the order is irrelevant.  A tile holds 1024 cells with ix, iy < 2^28, so its sums fit 2^38.
+__global__ __launch_bounds__(256) void mosaic_centroid_kernel(const cen_job* __restrict__ jobs, int njobs)
+{
+    int lo = 0, hi = njobs - 1;
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (jobs[mid].blk0 <= (int)blockIdx.x) lo = mid; else hi = mid - 1; }
+    const cen_job J = jobs[lo];
+    const int wg = (int)blockIdx.x - J.blk0;
+    const int ty = wg / J.tiles_x, tx = wg - ty * J.tiles_x;
+    const int gx = J.rx0 + tx * CEN_TW + ((int)threadIdx.x & 63);
+    unsigned long long n = 0, sx = 0, sy = 0;
+    if (gx <= J.rx1) {
+#pragma unroll
+        for (int k = 0; k < CEN_TH / 4; ++k) {
+            const int gy = J.ry0 + ty * CEN_TH + 4 * k + ((int)threadIdx.x >> 6);
+            if (gy > J.ry1) continue;
+            const uint16_t a = J.la[(size_t)(gy - J.aoy) * J.abw + (gx - J.aox)];                          // the region lies inside a's window
+            const uint16_t b = J.lb[(size_t)(gy + J.dy - J.boy) * J.bbw + (gx + J.dx - J.box)];            // and, shifted, inside b's
+            if (a != 0 && b != 0) { n += 1; sx += (unsigned long long)gx; sy += (unsigned long long)gy; }
+        }
+    }
+    n = dsss_wave_sum(n); sx = dsss_wave_sum(sx); sy = dsss_wave_sum(sy);
+    if (((int)threadIdx.x & 63) == 0 && n != 0) { atomicAdd(J.out + 0, n); atomicAdd(J.out + 1, sx); atomicAdd(J.out + 2, sy); }
+}
+
 // exact integer -> the nearest double, ties to even (what Python's float() of an int does): below 2^64 the hardware conversion is that
 // already; above, the value is cut to 64 bits with a sticky bit first, which leaves the rounding of the 53-bit result unchanged
 double i128_to_double(__int128 v)
@@ -180,6 +223,75 @@ int peak_of(const uint64_t* sums, int radius, int min_cells, double cell, dsss_r
     return DSSS_OK;
 }
 
+// ---- what dsss_mosaic_register and dsss_mosaic_register_segments share on the host
+// the argument rules of both entries; R = the parameters in force, slot = frame id -> its index in ids, rows = pings of all frames
+int reg_check(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, const dsss_mosaic_params* p, const int* pair_a,
+              const int* pair_b, int npairs, const dsss_reg_params* rp, const void* out_host, dsss_reg_params* R, std::vector<int>& slot, size_t* rows)
+{
+    if (dsss_comm_world(c) > 1) DSSS_FAIL(c, DSSS_E_STATE, "mosaic: registration runs on a single rank (communicator of %d)", dsss_comm_world(c));
+    int rc = mosaic_check_frames(c, ids, n, rpy6, ping_off, true, rows); if (rc) return rc;
+    rc = mosaic_check_params(c, p); if (rc) return rc;
+    dsss_reg_params_default(R);
+    if (rp) *R = *rp;
+    if (R->radius < 0 || R->radius > REG_MAX_RADIUS) DSSS_FAIL(c, DSSS_E_ARG, "register: radius %d outside 0..%d", R->radius, REG_MAX_RADIUS);
+    if (R->min_cells < 1) DSSS_FAIL(c, DSSS_E_ARG, "register: min_cells = %d", R->min_cells);
+    if (npairs < 0) DSSS_FAIL(c, DSSS_E_ARG, "register: npairs = %d", npairs);
+    if (npairs > 0 && (!pair_a || !pair_b || !out_host)) DSSS_FAIL(c, DSSS_E_ARG, "register: %d pairs without %s", npairs, out_host ? "their frames" : "a result array");
+    slot.assign(c->max_frames, -1);
+    for (int i = 0; i < n; ++i) slot[ids[i]] = i;
+    for (int k = 0; k < npairs; ++k) {
+        const int a = pair_a[k], b = pair_b[k];
+        if (a < 0 || a >= c->max_frames || slot[a] < 0 || b < 0 || b >= c->max_frames || slot[b] < 0)
+            DSSS_FAIL(c, DSSS_E_ARG, "register: pair %d = (%d, %d) names a frame that is not listed", k, a, b);
+        if (a == b) DSSS_FAIL(c, DSSS_E_ARG, "register: pair %d is frame %d with itself", k, a);
+    }
+    return DSSS_OK;
+}
+
+// the window of the pings [r0, r1) of a frame: the cells their geo extremes can reach (as the consistency map's); false: none on the grid
+bool reg_window(const dsss_frame& f, const double* rows, int r0, int r1, const dsss_mosaic_params* p, mosaic_win* w)
+{
+    double bb[4] = { INFINITY, -INFINITY, INFINITY, -INFINITY };
+    frame_extent_rows(f, rows, r0, r1, bb);
+    int ax, bx, ay, by;
+    if (!cell_range(bb[0], bb[1], p->x0, p->cell, p->W, &ax, &bx) || !cell_range(bb[2], bb[3], p->y0, p->cell, p->H, &ay, &by)) return false;
+    *w = mosaic_win{ p->x0, p->y0, p->cell, p->W, p->H, ax, ay, bx - ax + 1, by - ay + 1, p->use_mask != 0 };
+    return true;
+}
+
+// the job of layer la (window A) against layer lb (window Bw) with its sums at out, appended to pj; *blocks = workgroups so far.
+// Windows that do not come within the radius give no job: all sums stay 0.  False: more workgroups than one launch takes.
+bool reg_push_job(std::vector<reg_job>& pj, long long* blocks, const uint16_t* la, const mosaic_win& A, const uint16_t* lb, const mosaic_win& Bw,
+                  int r, unsigned long long* out)
+{
+    const int rx0 = std::max(A.ox, Bw.ox - r), rx1 = std::min(A.ox + A.bw - 1, Bw.ox + Bw.bw - 1 + r);
+    const int ry0 = std::max(A.oy, Bw.oy - r), ry1 = std::min(A.oy + A.bh - 1, Bw.oy + Bw.bh - 1 + r);
+    if (rx1 < rx0 || ry1 < ry0) return true;
+    reg_job J;
+    J.la = la; J.lb = lb; J.out = out;
+    J.aox = A.ox; J.aoy = A.oy; J.abw = A.bw; J.abh = A.bh; J.box = Bw.ox; J.boy = Bw.oy; J.bbw = Bw.bw; J.bbh = Bw.bh;
+    J.rx0 = rx0; J.ry0 = ry0; J.rx1 = rx1; J.ry1 = ry1;
+    J.tiles_x = (rx1 - rx0) / REG_TILE + 1; J.strips_x = (J.tiles_x + REG_STRIP - 1) / REG_STRIP;
+    J.blk0 = (int)*blocks; J.pad = 0;
+    *blocks += (long long)J.strips_x * ((ry1 - ry0) / REG_TILE + 1);
+    if (*blocks > 0x7fffffffll) return false;
+    pj.push_back(J);
+    return true;
+}
+
+// all jobs in one launch
+int reg_launch_corr(dsss_ctx* c, const std::vector<reg_job>& pj, long long blocks, reg_job* d_pairs, int r)
+{
+    if (pj.empty()) return DSSS_OK;
+    const int nshift = (2 * r + 1) * (2 * r + 1);
+    const int slots = (nshift + REG_MAX_THREADS - 1) / REG_MAX_THREADS;        // 1, or 2 from radius 16 on
+    const int threads = (((nshift + slots - 1) / slots) + 63) & ~63;
+    HIPCHK(c, hipMemcpyAsync(d_pairs, pj.data(), pj.size() * sizeof(reg_job), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(mosaic_corr_kernel, dim3((unsigned)blocks), dim3((unsigned)threads), 0, c->stream, d_pairs, (int)pj.size(), r);
+    HIPCHK(c, hipGetLastError());
+    return DSSS_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -197,26 +309,11 @@ int dsss_mosaic_register(dsss_ctx* c, const int* ids, int n, const double* rpy6,
                          dsss_reg_result* out_host, uint64_t* sums_host)
 {
     if (!c) return DSSS_E_ARG;
-    if (dsss_comm_world(c) > 1) DSSS_FAIL(c, DSSS_E_STATE, "mosaic: registration runs on a single rank (communicator of %d)", dsss_comm_world(c));
     size_t rows = 0;
-    int rc = mosaic_check_frames(c, ids, n, rpy6, ping_off, true, &rows); if (rc) return rc;
-    rc = mosaic_check_params(c, p); if (rc) return rc;
-    dsss_reg_params R; dsss_reg_params_default(&R);
-    if (rp) R = *rp;
-    if (R.radius < 0 || R.radius > REG_MAX_RADIUS) DSSS_FAIL(c, DSSS_E_ARG, "register: radius %d outside 0..%d", R.radius, REG_MAX_RADIUS);
-    if (R.min_cells < 1) DSSS_FAIL(c, DSSS_E_ARG, "register: min_cells = %d", R.min_cells);
-    if (npairs < 0) DSSS_FAIL(c, DSSS_E_ARG, "register: npairs = %d", npairs);
-    if (npairs > 0 && (!pair_a || !pair_b || !out_host)) DSSS_FAIL(c, DSSS_E_ARG, "register: %d pairs without %s", npairs, out_host ? "their frames" : "a result array");
-    std::vector<int> slot(c->max_frames, -1);                                  // frame id -> its index in ids
-    for (int i = 0; i < n; ++i) slot[ids[i]] = i;
+    dsss_reg_params R; std::vector<int> slot;                                   // slot: frame id -> its index in ids
+    int rc = reg_check(c, ids, n, rpy6, ping_off, p, pair_a, pair_b, npairs, rp, out_host, &R, slot, &rows); if (rc) return rc;
     std::vector<char> used(n, 0);
-    for (int k = 0; k < npairs; ++k) {
-        const int a = pair_a[k], b = pair_b[k];
-        if (a < 0 || a >= c->max_frames || slot[a] < 0 || b < 0 || b >= c->max_frames || slot[b] < 0)
-            DSSS_FAIL(c, DSSS_E_ARG, "register: pair %d = (%d, %d) names a frame that is not listed", k, a, b);
-        if (a == b) DSSS_FAIL(c, DSSS_E_ARG, "register: pair %d is frame %d with itself", k, a);
-        used[slot[a]] = used[slot[b]] = 1;
-    }
+    for (int k = 0; k < npairs; ++k) used[slot[pair_a[k]]] = used[slot[pair_b[k]]] = 1;
     if (npairs == 0) return DSSS_OK;
     HIPCHK(c, hipSetDevice(c->device));
     const int r = R.radius, S = 2 * r + 1, nshift = S * S;
@@ -226,12 +323,8 @@ int dsss_mosaic_register(dsss_ctx* c, const int* ids, int n, const double* rpy6,
     for (int i = 0; i < n; ++i) {
         if (!used[i]) continue;
         const dsss_frame& f = c->frames[ids[i]];
-        double bb[4] = { INFINITY, -INFINITY, INFINITY, -INFINITY };
-        frame_extent(f, rpy6 ? rpy6 + (size_t)ping_off[i] * 6 : f.h_geo, bb);
-        int ax, bx, ay, by;
-        if (!cell_range(bb[0], bb[1], p->x0, p->cell, p->W, &ax, &bx) || !cell_range(bb[2], bb[3], p->y0, p->cell, p->H, &ay, &by)) continue;
+        if (!reg_window(f, rpy6 ? rpy6 + (size_t)ping_off[i] * 6 : f.h_geo, 0, f.N, p, &wins[i])) continue;
         on_grid[i] = 1;
-        wins[i] = mosaic_win{ p->x0, p->y0, p->cell, p->W, p->H, ax, ay, bx - ax + 1, by - ay + 1, p->use_mask != 0 };
         const size_t wc = (size_t)wins[i].bw * wins[i].bh;
         win_cells = std::max(win_cells, wc);
         lay_off[i] = lay_cells; lay_cells += (wc + 127) & ~(size_t)127;        // layers start on 256 bytes
@@ -270,27 +363,10 @@ int dsss_mosaic_register(dsss_ctx* c, const int* ids, int n, const double* rpy6,
     for (int k = 0; k < npairs; ++k) {
         const int ia = slot[pair_a[k]], ib = slot[pair_b[k]];
         if (!on_grid[ia] || !on_grid[ib]) continue;
-        const mosaic_win& A = wins[ia]; const mosaic_win& Bw = wins[ib];
-        const int rx0 = std::max(A.ox, Bw.ox - r), rx1 = std::min(A.ox + A.bw - 1, Bw.ox + Bw.bw - 1 + r);
-        const int ry0 = std::max(A.oy, Bw.oy - r), ry1 = std::min(A.oy + A.bh - 1, Bw.oy + Bw.bh - 1 + r);
-        if (rx1 < rx0 || ry1 < ry0) continue;                                   // the windows do not come within the radius: all sums stay 0
-        reg_job J;
-        J.la = d_lay + lay_off[ia]; J.lb = d_lay + lay_off[ib]; J.out = d_tab + (size_t)k * nshift * 6;
-        J.aox = A.ox; J.aoy = A.oy; J.abw = A.bw; J.abh = A.bh; J.box = Bw.ox; J.boy = Bw.oy; J.bbw = Bw.bw; J.bbh = Bw.bh;
-        J.rx0 = rx0; J.ry0 = ry0; J.rx1 = rx1; J.ry1 = ry1;
-        J.tiles_x = (rx1 - rx0) / REG_TILE + 1; J.strips_x = (J.tiles_x + REG_STRIP - 1) / REG_STRIP;
-        J.blk0 = (int)blocks; J.pad = 0;
-        blocks += (long long)J.strips_x * ((ry1 - ry0) / REG_TILE + 1);
-        if (blocks > 0x7fffffffll) DSSS_FAIL(c, DSSS_E_ARG, "register: %d pairs are more than one launch takes", npairs);
-        pj.push_back(J);
+        if (!reg_push_job(pj, &blocks, d_lay + lay_off[ia], wins[ia], d_lay + lay_off[ib], wins[ib], r, d_tab + (size_t)k * nshift * 6))
+            DSSS_FAIL(c, DSSS_E_ARG, "register: %d pairs are more than one launch takes", npairs);
     }
-    if (!pj.empty()) {
-        const int slots = (nshift + REG_MAX_THREADS - 1) / REG_MAX_THREADS;    // 1, or 2 from radius 16 on
-        const int threads = (((nshift + slots - 1) / slots) + 63) & ~63;
-        HIPCHK(c, hipMemcpyAsync(d_pairs, pj.data(), pj.size() * sizeof(reg_job), hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(mosaic_corr_kernel, dim3((unsigned)blocks), dim3((unsigned)threads), 0, c->stream, d_pairs, (int)pj.size(), r);
-        HIPCHK(c, hipGetLastError());
-    }
+    rc = reg_launch_corr(c, pj, blocks, d_pairs, r); if (rc) return rc;
     std::vector<uint64_t> own;
     uint64_t* tab = nullptr;
     own.resize(table + 1); tab = own.data();
@@ -299,6 +375,247 @@ int dsss_mosaic_register(dsss_ctx* c, const int* ids, int n, const double* rpy6,
     if ((int)tab[table]) DSSS_FAIL(c, DSSS_E_CAPACITY, "mosaic: a cell received more than 2^24 samples of one frame (cell %g too coarse)", p->cell);
     for (int k = 0; k < npairs; ++k) peak_of(tab + (size_t)k * nshift * 6, r, R.min_cells, p->cell, out_host + k);
     if (sums_host) memcpy(sums_host, tab, table * 8);
+    return DSSS_OK;
+}
+
+// The segments of frame b against the whole of frame a.  Per frame that occurs as b: ONE segmented scatter into the accumulators of all
+// its segments (each segment its own window, one behind the other) and ONE mosaic_mean_kernel over that whole area, whatever the number
+// of segments and of pairs that name the frame; the layers use the accumulators' offsets, so the pack needs no segment table.  The
+// correlation is mosaic_corr_kernel with one job per (pair, segment); the peaks are decided on the host, then mosaic_centroid_kernel
+// runs once over the rows that have one.
+int dsss_mosaic_register_segments(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, const dsss_mosaic_params* p,
+                                  const int* pair_a, const int* pair_b, int npairs, int seg_pings, const dsss_reg_params* rp,
+                                  dsss_reg_seg* out_host, int cap, int* nseg_host, uint64_t* sums_host)
+{
+    if (!c) return DSSS_E_ARG;
+    size_t rows = 0;
+    dsss_reg_params R; std::vector<int> slot;
+    int rc = reg_check(c, ids, n, rpy6, ping_off, p, pair_a, pair_b, npairs, rp, out_host, &R, slot, &rows); if (rc) return rc;
+    if (seg_pings < 1) DSSS_FAIL(c, DSSS_E_ARG, "register: seg_pings = %d", seg_pings);
+    if (!nseg_host || cap < 0) DSSS_FAIL(c, DSSS_E_ARG, "register: %s", nseg_host ? "negative capacity" : "nowhere to write the number of segments");
+    auto segs_of = [&](int i) { return (int)(((long long)c->frames[ids[i]].N + seg_pings - 1) / seg_pings); };
+    auto seg_end = [&](int s, int N) { return (int)std::min((long long)(s + 1) * seg_pings, (long long)N); };
+    long long total = 0;
+    for (int k = 0; k < npairs; ++k) total += segs_of(slot[pair_b[k]]);
+    if (total > 0x7fffffffll) DSSS_FAIL(c, DSSS_E_ARG, "register: %lld segments", total);
+    *nseg_host = (int)total;                                                    // also when there is no room for them: the caller learns how many
+    if (total > cap) DSSS_FAIL(c, DSSS_E_CAPACITY, "register: %lld segments, room for %d", total, cap);
+    if (total == 0) return DSSS_OK;
+    const int nseg = (int)total;
+    std::vector<char> as_a(n, 0), as_b(n, 0);
+    for (int k = 0; k < npairs; ++k) { as_a[slot[pair_a[k]]] = 1; as_b[slot[pair_b[k]]] = 1; }
+    HIPCHK(c, hipSetDevice(c->device));
+    const int r = R.radius, S = 2 * r + 1, nshift = S * S;
+    // windows: the whole frame where it occurs as a, every segment where it occurs as b
+    std::vector<mosaic_win> wins(n); std::vector<char> on_grid(n, 0); std::vector<size_t> lay_off(n, 0), seg_lay(n, 0), seg_cells(n, 0);
+    std::vector<int> seg0(n, 0);                                                // a frame's first segment in sw / hseg
+    std::vector<mosaic_win> sw; std::vector<mosaic_seg> hseg;
+    size_t win_cells = 1, lay_cells = 0;
+    for (int i = 0; i < n; ++i) {
+        const dsss_frame& f = c->frames[ids[i]];
+        const double* fr = rpy6 ? rpy6 + (size_t)ping_off[i] * 6 : f.h_geo;
+        if (as_a[i] && reg_window(f, fr, 0, f.N, p, &wins[i])) {
+            on_grid[i] = 1;
+            const size_t wc = (size_t)wins[i].bw * wins[i].bh;
+            win_cells = std::max(win_cells, wc);
+            lay_off[i] = lay_cells; lay_cells += (wc + 127) & ~(size_t)127;    // layers start on 256 bytes
+        }
+        if (!as_b[i]) continue;
+        seg0[i] = (int)sw.size();
+        size_t cells = 0;
+        for (int s = 0; s < segs_of(i); ++s) {
+            mosaic_win w{ p->x0, p->y0, p->cell, p->W, p->H, 0, 0, 0, 0, p->use_mask != 0 };      // bw = 0: not on the grid
+            reg_window(f, fr, s * seg_pings, seg_end(s, f.N), p, &w);
+            sw.push_back(w); hseg.push_back(mosaic_seg{ w.ox, w.oy, w.bw, w.bh, (unsigned long long)cells });
+            cells += ((size_t)w.bw * w.bh + 127) & ~(size_t)127;
+        }
+        seg_cells[i] = cells; win_cells = std::max(win_cells, cells);
+        seg_lay[i] = lay_cells; lay_cells += cells;
+    }
+    const size_t table = (size_t)nseg * nshift * 6;
+    carve L;
+    const size_t o_lay = L.take(lay_cells * 2), o_win = L.take(win_cells * 8), o_jobs = L.take((size_t)n * sizeof(mosaic_job)),
+                 o_rows = L.take(rpy6 ? rows * 6 * sizeof(double) : 0), o_segs = L.take(hseg.size() * sizeof(mosaic_seg)),
+                 o_pairs = L.take((size_t)nseg * sizeof(reg_job)), o_cj = L.take((size_t)nseg * sizeof(cen_job)),
+                 o_cen = L.take((size_t)nseg * 3 * 8), o_tab = L.take((table + 1) * 8);      // the sums and, behind them, the sample-limit flag
+    rc = c->mosaic_buf.reserve(c, L.off); if (rc) return rc;
+    char* B = c->mosaic_buf.as<char>();
+    uint16_t* d_lay = reinterpret_cast<uint16_t*>(B + o_lay);
+    unsigned long long* d_win = reinterpret_cast<unsigned long long*>(B + o_win);
+    mosaic_job* d_jobs = reinterpret_cast<mosaic_job*>(B + o_jobs);
+    mosaic_seg* d_segs = reinterpret_cast<mosaic_seg*>(B + o_segs);
+    reg_job* d_pairs = reinterpret_cast<reg_job*>(B + o_pairs);
+    cen_job* d_cj = reinterpret_cast<cen_job*>(B + o_cj);
+    unsigned long long* d_cen = reinterpret_cast<unsigned long long*>(B + o_cen);
+    unsigned long long* d_tab = reinterpret_cast<unsigned long long*>(B + o_tab);
+    int* d_flag = reinterpret_cast<int*>(d_tab + table);
+    std::vector<const double*> dev_rows;
+    rc = upload_rows(c, ids, n, rpy6, ping_off, reinterpret_cast<double*>(B + o_rows), dev_rows); if (rc) return rc;
+    std::vector<mosaic_job> jobs(n);
+    for (int i = 0; i < n; ++i) { const dsss_frame& f = c->frames[ids[i]]; jobs[i] = mosaic_job{ dev_rows[i], f.gr, f.lvl[0], f.mask, f.N, f.M, 0, 0 }; }
+    HIPCHK(c, hipMemcpyAsync(d_jobs, jobs.data(), (size_t)n * sizeof(mosaic_job), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_segs, hseg.data(), hseg.size() * sizeof(mosaic_seg), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_tab, 0, (table + 1) * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_cen, 0, (size_t)nseg * 3 * 8, c->stream));
+    // 1. mean layers: a frame's whole layer where it is an a, the layers of all its segments (one scatter, one pack) where it is a b
+    const mosaic_win grid{ p->x0, p->y0, p->cell, p->W, p->H, 0, 0, 0, 0, p->use_mask != 0 };
+    for (int i = 0; i < n; ++i) {
+        if (on_grid[i]) {
+            const size_t wc = (size_t)wins[i].bw * wins[i].bh;
+            HIPCHK(c, hipMemsetAsync(d_win, 0, wc * 8, c->stream));
+            launch_scatter(c, d_jobs + i, 1, jobs[i].N, wins[i], d_win);
+            hipLaunchKernelGGL(mosaic_mean_kernel, dim3((unsigned)((wc + 255) / 256)), dim3(256), 0, c->stream, d_win, wc, d_lay + lay_off[i], d_flag);
+            HIPCHK(c, hipGetLastError());
+        }
+        if (as_b[i] && seg_cells[i]) {
+            const size_t wc = seg_cells[i];
+            HIPCHK(c, hipMemsetAsync(d_win, 0, wc * 8, c->stream));
+            launch_scatter_seg(c, d_jobs + i, jobs[i].N, grid, d_win, d_segs + seg0[i], seg_pings);
+            hipLaunchKernelGGL(mosaic_mean_kernel, dim3((unsigned)((wc + 255) / 256)), dim3(256), 0, c->stream, d_win, wc, d_lay + seg_lay[i], d_flag);
+            HIPCHK(c, hipGetLastError());
+        }
+    }
+    // 2. one correlation job per (pair, segment), all in one launch; the rows are laid out here, by pair and then by segment
+    memset(out_host, 0, (size_t)nseg * sizeof(dsss_reg_seg));
+    std::vector<reg_job> pj; pj.reserve(nseg);
+    std::vector<int> row_a(nseg), row_g(nseg);                                  // a row's frame a (index in ids) and its segment in sw / hseg
+    long long blocks = 0;
+    int row = 0;
+    for (int k = 0; k < npairs; ++k) {
+        const int ia = slot[pair_a[k]], ib = slot[pair_b[k]];
+        const int Nb = c->frames[ids[ib]].N;
+        for (int s = 0; s < segs_of(ib); ++s, ++row) {
+            dsss_reg_seg& o = out_host[row];
+            o.pair = k; o.seg = s; o.p0 = s * seg_pings; o.p1 = seg_end(s, Nb);
+            const int g = seg0[ib] + s;
+            row_a[row] = ia; row_g[row] = g;
+            if (!on_grid[ia] || sw[g].bw == 0) continue;
+            if (!reg_push_job(pj, &blocks, d_lay + lay_off[ia], wins[ia], d_lay + seg_lay[ib] + hseg[g].off, sw[g], r, d_tab + (size_t)row * nshift * 6))
+                DSSS_FAIL(c, DSSS_E_ARG, "register: %d segments are more than one launch takes", nseg);
+        }
+    }
+    rc = reg_launch_corr(c, pj, blocks, d_pairs, r); if (rc) return rc;
+    rc = c->mosaic_pinned.reserve(c, (table + 1) * 8); if (rc) return rc;
+    const uint64_t* tab = c->mosaic_pinned.as<uint64_t>();
+    HIPCHK(c, hipMemcpyAsync(c->mosaic_pinned.p, d_tab, (table + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if ((int)tab[table]) DSSS_FAIL(c, DSSS_E_CAPACITY, "mosaic: a cell received more than 2^24 samples of one frame (cell %g too coarse)", p->cell);
+    // 3. peaks on the host, then the centroid sums of the rows that have one: one launch, one download
+    std::vector<cen_job> cj;
+    long long cblocks = 0;
+    for (row = 0; row < nseg; ++row) {
+        dsss_reg_result& q = out_host[row].r;
+        peak_of(tab + (size_t)row * nshift * 6, r, R.min_cells, p->cell, &q);
+        if (!(q.zncc > -2.0)) continue;                                         // no usable shift: sx = sy = 0
+        const mosaic_win& A = wins[row_a[row]]; const mosaic_win& Bw = sw[row_g[row]];
+        cen_job J;
+        J.la = d_lay + lay_off[row_a[row]]; J.lb = d_lay + seg_lay[slot[pair_b[out_host[row].pair]]] + hseg[row_g[row]].off;
+        J.out = d_cen + (size_t)row * 3;
+        J.aox = A.ox; J.aoy = A.oy; J.abw = A.bw; J.box = Bw.ox; J.boy = Bw.oy; J.bbw = Bw.bw;
+        J.rx0 = std::max(A.ox, Bw.ox - q.dx); J.rx1 = std::min(A.ox + A.bw - 1, Bw.ox + Bw.bw - 1 - q.dx);
+        J.ry0 = std::max(A.oy, Bw.oy - q.dy); J.ry1 = std::min(A.oy + A.bh - 1, Bw.oy + Bw.bh - 1 - q.dy);
+        if (J.rx1 < J.rx0 || J.ry1 < J.ry0) continue;                           // (cannot be: a usable shift has cells; the check below reports it)
+        J.dx = q.dx; J.dy = q.dy; J.tiles_x = (J.rx1 - J.rx0) / CEN_TW + 1; J.blk0 = (int)cblocks;
+        cblocks += (long long)J.tiles_x * ((J.ry1 - J.ry0) / CEN_TH + 1);
+        if (cblocks > 0x7fffffffll) DSSS_FAIL(c, DSSS_E_ARG, "register: %d segments are more than one launch takes", nseg);
+        cj.push_back(J);
+    }
+    if (!cj.empty()) {
+        std::vector<uint64_t> cen((size_t)nseg * 3);
+        HIPCHK(c, hipMemcpyAsync(d_cj, cj.data(), cj.size() * sizeof(cen_job), hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(mosaic_centroid_kernel, dim3((unsigned)cblocks), dim3(256), 0, c->stream, d_cj, (int)cj.size());
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(cen.data(), d_cen, cen.size() * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        for (row = 0; row < nseg; ++row) {
+            dsss_reg_seg& o = out_host[row];
+            if (!(o.r.zncc > -2.0)) continue;
+            if ((int64_t)cen[(size_t)row * 3] != o.r.n)
+                DSSS_FAIL(c, DSSS_E_NUMERIC, "register: internal error, row %d has %lld cells at its peak and %lld in its centroid", row,
+                          (long long)o.r.n, (long long)cen[(size_t)row * 3]);
+            o.sx = (int64_t)cen[(size_t)row * 3 + 1]; o.sy = (int64_t)cen[(size_t)row * 3 + 2];
+        }
+    }
+    if (sums_host) memcpy(sums_host, tab, table * 8);
+    return DSSS_OK;
+}
+
+void dsss_reg_edge_params_default(dsss_reg_edge_params* e) { if (e) { e->min_zncc = 0.5; e->sigma_xy_cells = 1.0; e->sigma_z = 10.0; e->sigma_rot = 1.0; } }
+
+int dsss_register_edge(const dsss_reg_seg* s, const dsss_mosaic_params* grid, const double* rows_a, int Na, int base_a,
+                       const double* rows_b, int Nb, int base_b, const dsss_reg_edge_params* ep, dsss_lc_edge* edge)
+{
+    dsss_reg_edge_params E; dsss_reg_edge_params_default(&E);
+    if (ep) E = *ep;
+    if (!s || !grid || !rows_a || !rows_b || !edge || Na < 1 || Nb < 1) return DSSS_E_ARG;
+    if (s->p0 < 0 || s->p0 >= s->p1 || s->p1 > Nb) return DSSS_E_ARG;
+    if (!(grid->cell > 0.0) || !std::isfinite(grid->cell)) return DSSS_E_ARG;
+    const double sig[3] = { E.sigma_xy_cells, E.sigma_z, E.sigma_rot };
+    for (double v : sig) if (!(v > 0.0) || !std::isfinite(v)) return DSSS_E_ARG;
+    if (!(s->r.zncc >= E.min_zncc) || s->r.on_border != 0) return 0;
+    if (s->r.n <= 0) return DSSS_E_ARG;
+    const double cell = grid->cell;
+    const double cx = grid->x0 + ((double)s->sx / (double)s->r.n + 0.5) * cell, cy = grid->y0 + ((double)s->sy / (double)s->r.n + 0.5) * cell;
+    // the ping whose scan line (through the ping, across the heading) passes nearest the point: the lowest index among equals
+    auto anchor = [](const double* rows, int r0, int r1, double px, double py) {
+        int best = r0; double dbest = INFINITY;
+        for (int i = r0; i < r1; ++i) {
+            const double* P = rows + (size_t)i * 6;
+            const double d = fabs(cos(P[2]) * (px - P[3]) + sin(P[2]) * (py - P[4]));
+            if (d < dbest) { dbest = d; best = i; }
+        }
+        return best;
+    };
+    const int i = anchor(rows_a, 0, Na, cx, cy);
+    const int j = anchor(rows_b, s->p0, s->p1, cx + s->r.off_x, cy + s->r.off_y);     // b's rendering lies off from where it belongs
+    pose_t Xa, Xb, rel;
+    pose_from_rodrigues(rows_a + (size_t)i * 6, &Xa);
+    pose_from_rodrigues(rows_b + (size_t)j * 6, &Xb);
+    Xb.t[0] -= s->r.off_x; Xb.t[1] -= s->r.off_y;
+    const long long ga = (long long)base_a + i, gb = (long long)base_b + j;
+    if (ga < 0 || gb < 0 || ga > 0x7fffffffll || gb > 0x7fffffffll) return DSSS_E_ARG;
+    if (ga < gb) { edge->a = (int32_t)ga; edge->b = (int32_t)gb; pose_between(&Xa, &Xb, &rel); }
+    else { edge->a = (int32_t)gb; edge->b = (int32_t)ga; pose_between(&Xb, &Xa, &rel); }
+    memcpy(edge->rel, rel.R, 9 * sizeof(double)); memcpy(edge->rel + 9, rel.t, 3 * sizeof(double));
+    const double sxy = E.sigma_xy_cells * cell;
+    edge->var[0] = edge->var[1] = edge->var[2] = E.sigma_rot * E.sigma_rot;
+    edge->var[3] = edge->var[4] = sxy * sxy; edge->var[5] = E.sigma_z * E.sigma_z;
+    return 1;
+}
+
+int dsss_mosaic_register_edges(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, const dsss_mosaic_params* p,
+                               const int* pair_a, const int* pair_b, const dsss_reg_seg* segs, int nsegs, const dsss_reg_edge_params* ep,
+                               dsss_lc_edge* edges_host, int32_t* edge_seg_host, int cap, int* n_edges)
+{
+    if (!c) return DSSS_E_ARG;
+    if (dsss_comm_world(c) > 1) DSSS_FAIL(c, DSSS_E_STATE, "mosaic: registration runs on a single rank (communicator of %d)", dsss_comm_world(c));
+    size_t rows = 0;
+    int rc = mosaic_check_frames(c, ids, n, rpy6, ping_off, false, &rows); if (rc) return rc;
+    rc = mosaic_check_params(c, p); if (rc) return rc;
+    if (nsegs < 0 || cap < 0 || !n_edges) DSSS_FAIL(c, DSSS_E_ARG, "register: nsegs = %d, cap = %d%s", nsegs, cap, n_edges ? "" : ", nowhere to write the number of edges");
+    if (nsegs > 0 && (!pair_a || !pair_b || !segs)) DSSS_FAIL(c, DSSS_E_ARG, "register: %d segments without %s", nsegs, segs ? "their pairs" : "their rows");
+    std::vector<int> slot(c->max_frames, -1), base(n);
+    int run = 0;
+    for (int i = 0; i < n; ++i) { slot[ids[i]] = i; base[i] = ping_off ? ping_off[i] : run; run += c->frames[ids[i]].N; }
+    int ne = 0;
+    for (int k = 0; k < nsegs; ++k) {
+        if (segs[k].pair < 0) DSSS_FAIL(c, DSSS_E_ARG, "register: row %d names pair %d", k, segs[k].pair);
+        const int a = pair_a[segs[k].pair], b = pair_b[segs[k].pair];
+        if (a < 0 || a >= c->max_frames || slot[a] < 0 || b < 0 || b >= c->max_frames || slot[b] < 0)
+            DSSS_FAIL(c, DSSS_E_ARG, "register: row %d, pair (%d, %d) names a frame that is not listed", k, a, b);
+        const int ia = slot[a], ib = slot[b];
+        const dsss_frame& fa = c->frames[a]; const dsss_frame& fb = c->frames[b];
+        dsss_lc_edge e;
+        rc = dsss_register_edge(segs + k, p, rpy6 ? rpy6 + (size_t)ping_off[ia] * 6 : fa.h_geo, fa.N, base[ia],
+                                rpy6 ? rpy6 + (size_t)ping_off[ib] * 6 : fb.h_geo, fb.N, base[ib], ep, &e);
+        if (rc < 0) DSSS_FAIL(c, rc, "register: row %d (pair %d, segment %d, pings %d..%d) is not a valid segment result", k, segs[k].pair, segs[k].seg, segs[k].p0, segs[k].p1);
+        if (rc == 0) continue;
+        if (ne >= cap || !edges_host) DSSS_FAIL(c, DSSS_E_CAPACITY, "register: more than %d edges", edges_host ? cap : 0);
+        edges_host[ne] = e;
+        if (edge_seg_host) edge_seg_host[ne] = k;
+        ++ne;
+    }
+    *n_edges = ne;
     return DSSS_OK;
 }
 

@@ -381,6 +381,55 @@ int  dsss_mosaic_register(dsss_ctx*, const int* ids, int n, const double* rpy6, 
  * sums.  DSSS_E_ARG: a NULL pointer, radius outside 0..16, min_cells < 1, cell <= 0 or not finite                                   */
 int  dsss_mosaic_register_peak(const uint64_t* sums, int radius, int min_cells, double cell, dsss_reg_result* out);
 
+/* ---- dense loop closures: the registration by SEGMENTS of frame b, and a segment's offset as a pose-graph edge.  One offset per pair
+ * of frames is too coarse for a drift that changes along the track; a segment of some tens of pings gives one offset per stretch of it.
+ * Segments: for pair k, frame b = pair_b[k] with N_b pings is cut into ceil(N_b / seg_pings) segments [s seg_pings, min((s + 1) seg_pings, N_b)).
+ * Segment layer: cnt, sum, m = (sum + cnt / 2) / cnt and validity as defined above, from the samples of that segment's pings only.
+ * Table: the six shift sums of (whole frame a, segment of b), as defined above.  Record: r is what dsss_mosaic_register_peak returns
+ *   on that table.  Order: rows by pair, then by segment; *nseg_host is their number.
+ * Centroid sums: V = the grid cells (ix, iy) where a is valid and the segment is valid at (ix + dx, iy + dy), for the peak (dx, dy);
+ *   sx = sum of ix, sy = sum of iy over V, so |V| = r.n.  Both are 0 when no shift is usable.
+ * Everything is an integer up to the score: results do not depend on the order of pairs, segments, tiles or atomics and are identical
+ * from call to call.  The segment layers of a frame are rendered once per call, however many pairs name it as b.
+ * DSSS_E_ARG: seg_pings < 1, nseg_host NULL, cap < 0.  DSSS_E_CAPACITY: cap below the number of rows, decided before anything is
+ * launched (*nseg_host holds the number then, too: a call with cap = 0 asks for it).  DSSS_E_NUMERIC: the centroid's cell count differs from r.n (an internal error).  Every other rule (frames, pairs, radius,
+ * state, single rank, 2^24 samples) is that of dsss_mosaic_register.                                                                  */
+typedef struct { int32_t pair, seg, p0, p1;      /* index into pair_a / pair_b; segment number; pings [p0, p1) of frame pair_b[pair] */
+                 dsss_reg_result r;              /* exactly the record dsss_mosaic_register_peak gives for this segment's table */
+                 int64_t sx, sy; } dsss_reg_seg; /* sum of ix, sum of iy over V at the peak shift (0, 0 when no shift is usable) */
+int  dsss_mosaic_register_segments(dsss_ctx*, const int* ids, int n, const double* rpy6, const int* ping_off, const dsss_mosaic_params*,
+                                   const int* pair_a, const int* pair_b, int npairs, int seg_pings, const dsss_reg_params*,
+                                   dsss_reg_seg* out_host, int cap, int* nseg_host, uint64_t* sums_host /* nseg x (2r+1)^2 x 6, may be NULL */);
+/* From a segment result to a pose-graph edge: pure host arithmetic, no context.  rows_a (Na x 6), rows_b (Nb x 6) are the "r p y x y z"
+ * rows of the two frames under the trajectory that was registered, base_a / base_b the pose-graph index of each frame's first ping.
+ * Accepted iff r.zncc >= min_zncc and r.on_border == 0 (no usable peak has zncc -2).
+ * Overlap centre: c = (x0 + (sx / n + 0.5) cell, y0 + (sy / n + 0.5) cell), in f64 in exactly this order, n = r.n.
+ * Anchor pings, the pings whose scan line passes nearest the overlap centre: i = argmin over [0, Na) of
+ *   |cos(yaw_i) (c_x - x_i) + sin(yaw_i) (c_y - y_i)|, j the same over [p0, p1) of b with the point c + (off_x, off_y), because b's
+ *   rendering lies off from where it belongs; ties go to the lowest index.
+ * Measurement: X_a = Pose3(Rot3::Rodrigues(r, p, y), (x, y, z)) of rows_a[i], X_b' the same of rows_b[j] with its translation moved
+ *   by (-off_x, -off_y, 0).  With ga = base_a + i and gb = base_b + j: ga < gb gives the edge (ga, gb, X_a^-1 X_b'), otherwise
+ *   (gb, ga, X_b'^-1 X_a).
+ * Variance: (s_rot^2, s_rot^2, s_rot^2, s_xy^2, s_xy^2, s_z^2) with s_xy = sigma_xy_cells cell: rotation and height are measured
+ *   weakly at their current values, the registration says nothing about them.
+ * Defaults: min_zncc 0.5, sigma_xy_cells 1 (one cell is the quantisation of the search), sigma_z 10 m, sigma_rot 1 rad: the values
+ *   of a feasibility check on a synthetic survey, NONE of them tuned on real data.
+ * Returns 1 and fills *edge when the segment is accepted, 0 when it is rejected, DSSS_E_ARG for a NULL pointer (the parameters may be
+ * NULL: the defaults), Na or Nb < 1, pings outside 0 <= p0 < p1 <= Nb, a cell or a sigma that is not positive and finite, an accepted
+ * peak with n <= 0, a pose-graph index outside int32.                                                                               */
+typedef struct { double min_zncc, sigma_xy_cells, sigma_z, sigma_rot; } dsss_reg_edge_params;   /* defaults 0.5, 1.0, 10.0 (m), 1.0 (rad) */
+void dsss_reg_edge_params_default(dsss_reg_edge_params*);
+int  dsss_register_edge(const dsss_reg_seg* s, const dsss_mosaic_params* grid, const double* rows_a, int Na, int base_a,
+                        const double* rows_b, int Nb, int base_b, const dsss_reg_edge_params*, dsss_lc_edge* edge);
+/* dsss_register_edge on every row of segs, in order; it launches no GPU work.  The rows are the caller's trajectory (rpy6, ping_off as
+ * above), the frames' own pose6 when rpy6 == NULL; base is ping_off[i], or, when ping_off == NULL, the running sum of N over ids in
+ * order.  segs[k].pair indexes pair_a / pair_b as it did in dsss_mosaic_register_segments.  edge_seg_host[e] (may be NULL) is the row
+ * edge e came from.  Frames need their geometry only.  DSSS_E_CAPACITY: more accepted rows than cap.  DSSS_E_STATE: a communicator of
+ * more than one rank.  DSSS_E_ARG: what dsss_register_edge refuses, a pair member not in ids, a negative pair index.                 */
+int  dsss_mosaic_register_edges(dsss_ctx*, const int* ids, int n, const double* rpy6, const int* ping_off, const dsss_mosaic_params*,
+                                const int* pair_a, const int* pair_b, const dsss_reg_seg* segs, int nsegs, const dsss_reg_edge_params*,
+                                dsss_lc_edge* edges_host, int32_t* edge_seg_host /* may be NULL */, int cap, int* n_edges);
+
 /* ------------------------------------------------------------------ instrumentation
  * accumulated GPU time (ms, HIP events on the context stream) and launch count per kernel family        */
 #define DSSS_K_ROW_REDUCE   0   /* row_reduce_kernel: one f64 read of the waterfall */

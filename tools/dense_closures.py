@@ -1,0 +1,105 @@
+#!/usr/bin/env python3
+"""Dense loop closures on a synthetic survey: the segments of every frame pair with overlapping geo boxes are registered under the
+solved trajectory (dsss_mosaic_register_segments), the accepted offsets become pose-graph edges (dsss_mosaic_register_edges), the
+trajectory is solved again with them next to the feature-based closures, and the segments are registered once more under the result.
+    python tools/dense_closures.py --frames 200 --rows 2000 --cols 1024 --cell 0.1 [--seg-pings 80] [--radius 8] [--calls 5] [--timeout 1500]
+Steps: 1. pipeline and dsss_posegraph_solve; 2. segments under the solved trajectory; 3. edges; 4. the edges of dsss_posegraph_select
+with the new ones behind them; 5. dsss_posegraph_solve_edges on the frames' dead-reckoning rows; 6. segments under the result.
+Prints one JSON line: segments and accepted edges; median and 95th percentile of |offset| in metres over the segments with a peak, the
+median ZNCC at zero shift and the consistency score, each before (solved trajectory) and after (solved again); the wall time of the
+segment call and of dsss_mosaic_register on the same pairs in the same process (the whole-frame form, the only existing code the new
+call's time can be set against), each the median of --calls synchronised calls after one warm-up.
+The GPU work runs in a child process under a time limit (--timeout seconds); this process never opens the device."""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--frames", type=int, default=200); ap.add_argument("--rows", type=int, default=2000)
+ap.add_argument("--cols", type=int, default=1024); ap.add_argument("--cell", type=float, default=0.1)
+ap.add_argument("--seg-pings", type=int, default=80)
+ap.add_argument("--radius", type=int, default=8); ap.add_argument("--min-cells", type=int, default=256)
+ap.add_argument("--calls", type=int, default=5); ap.add_argument("--timeout", type=float, default=1500.0)
+ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)
+a = ap.parse_args()
+if a.calls < 5:
+    sys.exit("--calls must be at least 5")
+
+if not a.worker:
+    try:
+        sys.exit(subprocess.run([sys.executable, os.path.abspath(__file__), "--worker"] + sys.argv[1:], timeout=a.timeout).returncode)
+    except subprocess.TimeoutExpired:
+        sys.exit("dense_closures: the GPU step did not finish within %g s" % a.timeout)
+
+import numpy as np                               # noqa: E402
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from diasss_amd import capi                      # noqa: E402
+from diasss_amd.pipeline import Pipeline         # noqa: E402
+from diasss_amd.synth import Survey              # noqa: E402
+
+F, N, M = a.frames, a.rows, a.cols
+sv = Survey(F, N, M, seed=20240601 + 2, device="cuda:0")
+raws = [sv.frame(f) for f in range(F)]
+ins = [sv.inputs(f) for f in range(F)]
+pipe = Pipeline(F, device=0)
+pipe.run(raws, [i[0] for i in ins], [i[1] for i in ins], [i[2] for i in ins])
+ctx = pipe.ctx
+_, rpy, stats = ctx.posegraph_solve(F, F * N, want_rpy=True)                      # 1
+ids = np.arange(F, dtype=np.int32); off = (ids * N).astype(np.int32)
+p = capi.mosaic_grid(ctx.mosaic_bounds(ids), a.cell)              # one grid for both trajectories: the dead-reckoning extent
+boxes = [ctx.mosaic_bounds([f]) for f in range(F)]
+pairs = [(i, j) for i in range(F) for j in range(i + 1, F)
+         if boxes[i][0] <= boxes[j][1] and boxes[j][0] <= boxes[i][1] and boxes[i][2] <= boxes[j][3] and boxes[j][2] <= boxes[i][3]]
+reg = capi.RegParams(a.radius, a.min_cells)
+res = dict(frames=F, rows=N, cols=M, cell=a.cell, grid=[p.W, p.H], radius=a.radius, min_cells=a.min_cells, seg_pings=a.seg_pings, pairs=len(pairs),
+           calls=a.calls, lm_iterations=int(stats[0]))
+if not pairs:
+    print(json.dumps(res)); pipe.close(); sys.exit(0)
+
+
+def timed(fn):
+    fn()
+    ts = []
+    for _ in range(a.calls):
+        t0 = time.perf_counter(); fn(); ts.append(time.perf_counter() - t0)
+    return round(1e3 * float(np.median(ts)), 3), round(1e3 * float(min(ts)), 3)
+
+
+def describe(segs, traj):
+    r = segs["r"]
+    ok = r["zncc"] > -2.0
+    d = np.hypot(r["off_x"][ok], r["off_y"][ok])
+    z0 = r["zncc0"][r["zncc0"] > -2.0]
+    return dict(with_peak=int(ok.sum()), on_border=int((r["on_border"][ok] != 0).sum()),
+                offset_median_m=float(np.median(d)) if ok.any() else None, offset_p95_m=float(np.percentile(d, 95)) if ok.any() else None,
+                zncc0_median=float(np.median(z0)) if len(z0) else None, consistency=float(ctx.mosaic_consistency(ids, p, rpy6=traj, ping_off=off)[3]))
+
+
+def rows_of(poses12):
+    """total x 12 (R row-major, t) -> "r p y x y z" (Rot3::rpy, as dsss_posegraph_solve writes its rpy6 rows)"""
+    P = poses12
+    return np.ascontiguousarray(np.stack([np.arctan2(P[:, 7], P[:, 8]), np.arctan2(-P[:, 6], np.hypot(P[:, 7], P[:, 8])), np.arctan2(P[:, 3], P[:, 0]),
+                                          P[:, 9], P[:, 10], P[:, 11]], 1))
+
+
+res["segments_ms"], res["segments_ms_min"] = timed(lambda: ctx.mosaic_register_segments(ids, p, pairs, a.seg_pings, reg=reg, rpy6=rpy, ping_off=off))
+res["whole_frame_ms"], res["whole_frame_ms_min"] = timed(lambda: ctx.mosaic_register(ids, p, pairs, reg=reg, rpy6=rpy, ping_off=off))
+before = ctx.mosaic_register_segments(ids, p, pairs, a.seg_pings, reg=reg, rpy6=rpy, ping_off=off)      # 2
+new, src = ctx.mosaic_register_edges(ids, p, pairs, before, rpy6=rpy, ping_off=off)                      # 3
+old = ctx.posegraph_select(F)                                                                            # 4
+dr = np.ascontiguousarray(np.concatenate([i[0] for i in ins]))
+t0 = time.perf_counter()
+poses, stats2 = ctx.posegraph_solve_edges(dr, np.concatenate([old, new]))                                # 5
+solve_ms = 1e3 * (time.perf_counter() - t0)
+again = rows_of(poses)
+after = ctx.mosaic_register_segments(ids, p, pairs, a.seg_pings, reg=reg, rpy6=again, ping_off=off)      # 6
+true = np.ascontiguousarray(np.concatenate(sv.poses_true))
+res.update(segments=len(before), feature_edges=len(old), accepted_edges=len(new), lm_iterations_again=int(stats2[0]), solve_again_ms=round(solve_ms, 3),
+           before=describe(before, rpy), after=describe(after, again),
+           consistency_dr=float(ctx.mosaic_consistency(ids, p)[3]), consistency_true=float(ctx.mosaic_consistency(ids, p, rpy6=true, ping_off=off)[3]))
+print(json.dumps(res))
+pipe.close()
