@@ -74,6 +74,7 @@ __global__ void pg_rl_sort_kernel(int ns, const int* __restrict__ rlptr, int* __
 __global__ void pg_fill_map_kernel(int* __restrict__ upd_map, const long long* __restrict__ total);
 __global__ void pg_anc_rel_kernel(int ns, const int* __restrict__ colptr, const int* __restrict__ rowidx, const char* __restrict__ binned, const int* __restrict__ root_of, int* __restrict__ anc_first, int* __restrict__ anc_rel);
 __global__ void pg_factor_subtree_kernel(const int* __restrict__ bin_perm, const int* __restrict__ binptr, const int* __restrict__ bincols, const int* __restrict__ colptr, const int* __restrict__ rlptr, const int* __restrict__ rlcol, const int* __restrict__ rlpos, const long long* __restrict__ mapptr, const int* __restrict__ upd_map, double* __restrict__ Lvals, double* __restrict__ x, int* __restrict__ fail, const int* __restrict__ binroot_ptr, const int* __restrict__ binroot_idx, const int* __restrict__ broot_b, const long long* __restrict__ broot_uoff, const int* __restrict__ broot_of_col, const int* __restrict__ anc_first, const int* __restrict__ anc_rel, double* __restrict__ ubin, double* __restrict__ rdiag);
+__global__ void pg_factor_subtree_serial_kernel(const int* __restrict__ bin_perm, const int* __restrict__ binptr, const int* __restrict__ bincols, const int* __restrict__ colptr, const int* __restrict__ rlptr, const int* __restrict__ rlcol, const int* __restrict__ rlpos, const long long* __restrict__ mapptr, const int* __restrict__ upd_map, double* __restrict__ Lvals, double* __restrict__ x, int* __restrict__ fail, const int* __restrict__ binroot_ptr, const int* __restrict__ binroot_idx, const int* __restrict__ broot_b, const long long* __restrict__ broot_uoff, const int* __restrict__ broot_of_col, const int* __restrict__ anc_first, const int* __restrict__ anc_rel, double* __restrict__ ubin, double* __restrict__ rdiag);      // DSSS_PG_BINS=serial
 __global__ void pg_bwd_subtree_kernel(const int* __restrict__ bin_perm, const int* __restrict__ binptr, const int* __restrict__ bincols, const int* __restrict__ colptr, const int* __restrict__ rowidx, const double* __restrict__ Lvals, double* __restrict__ x, const double* __restrict__ rdiag);
 // ---- dsss_pg_fronts.hip
 __global__ void pg_front_asm_kernel(const int* __restrict__ it_front, const int* __restrict__ it_row, const pg_front* __restrict__ FD, const pg_child* __restrict__ CH, const int* __restrict__ rel, const int* __restrict__ xr_ptr, const int* __restrict__ xr_child, const int* __restrict__ xr_row, const int* __restrict__ fa_rowptr, const int* __restrict__ fa_src, const int* __restrict__ fa_col, const int* __restrict__ fa_tr, const double* __restrict__ aval, const double* __restrict__ x, double* __restrict__ F, double* __restrict__ R);

@@ -1385,6 +1385,7 @@ pg_switches pg_switches_read()
     if (const char* v = getenv("DSSS_SYM_THREADS")) sw.threads = atoi(v);
     if (const char* v = getenv("DSSS_PG_LOCAL")) sw.local = atoi(v) != 0;
     if (const char* v = getenv("DSSS_PG_VERBOSE")) sw.opt.verbose = std::max(1, atoi(v));
+    if (const char* v = getenv("DSSS_PG_BINS")) sw.bins_serial = strcmp(v, "serial") == 0;
     return sw;
 }
 int pg_cheapest_gap(const int* pos, const std::vector<int>& cross, int target, int width, int after, int* cost)
@@ -1524,6 +1525,44 @@ extern "C" int dsss_host_pg_solve(int ns, const int32_t* edge_a, const int32_t* 
     }
     const int rc = x ? pg_host_solve(S, aval, rhs, x) : 0;
     return twin_result(S, rc, S.comm_doubles, stats8);
+}
+// the bins of the one-graph analysis as the device solve orders it (its bin cost, lists on the host), seen branch by branch of pg_factor_subtree_kernel
+extern "C" int dsss_host_pg_bins_profile(int ns, const int32_t* edge_a, const int32_t* edge_b, int nedges, const double* cx, const double* cy, int64_t* prof12)
+{
+    if (ns < 1 || nedges < ns - 1 || !edge_a || !edge_b || !cx || !cy || !prof12) return DSSS_E_ARG;
+    std::vector<std::pair<int, int>> edges;
+    if (!twin_edges(ns, edge_a, edge_b, nedges, true, true, edges)) return DSSS_E_ARG;
+    pg_sym S;
+    const pg_switches sw = pg_switches_read();
+    pg_sym_opts opt = sw.opt;
+    if (sw.threads) opt.threads = std::max(1, *sw.threads);
+    opt.bin_cost = sw.bin_cost.value_or(PG_BIN_COST_DEVICE);
+    pg_symbolic(ns, edges, cx, cy, nullptr, 1, opt, S);
+    int64_t* p = prof12;
+    for (int k = 0; k < 12; ++k) p[k] = 0;
+    const int nb = (int)S.binptr.size() - 1;
+    p[0] = nb; p[1] = (int64_t)S.bincols.size();
+    for (int b = 0; b < nb; ++b) {
+        const int lo = S.binptr[b], hi = S.binptr[b + 1];
+        if (hi - lo == 1) ++p[2];
+        p[8] = std::max<int64_t>(p[8], S.binroot_ptr[b + 1] - S.binroot_ptr[b]);
+        p[10] = std::max<int64_t>(p[10], hi - lo);
+        for (int ci = lo; ci < hi; ++ci) {
+            const int j = S.bincols[ci], T = S.rlptr[j + 1] - S.rlptr[j], m = S.colptr[j + 1] - S.colptr[j];
+            bool fresh = false;
+            if (ci > lo) {
+                const int jp = S.bincols[ci - 1], Tp = S.rlptr[jp + 1] - S.rlptr[jp];
+                fresh = T > 0 && S.rlcol[S.rlptr[j + 1] - 1] == jp;
+                if (T == 0 && Tp > 0) ++p[3];
+                if (fresh) ++p[4]; else if (T > 0) ++p[5];
+                if (S.broot_of_col[j] >= 0 && S.broot_of_col[j] == S.broot_of_col[jp] && m - S.anc_first[j] > 0 && S.colptr[jp + 1] - S.colptr[jp] - S.anc_first[jp] > 0) ++p[9];
+            }
+            p[6] = std::max<int64_t>(p[6], T - (fresh ? 1 : 0));
+            p[7] = std::max<int64_t>(p[7], m);
+            p[11] = std::max<int64_t>(p[11], T);
+        }
+    }
+    return DSSS_OK;
 }
 // the same with a PRESCRIBED interface (pg_sym_opts::iface_last): the analysis one rank of several runs on its own separators + the
 // interface nodes.  Any edge list (no chain prefix); iface_last ascending.

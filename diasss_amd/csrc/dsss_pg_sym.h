@@ -153,6 +153,7 @@ struct pg_switches {
     std::optional<double> bin_cost;                 // DSSS_PG_BIN_COST, if set (the device solve has defaults of its own)
     std::optional<int> parts, threads;              // DSSS_PG_PARTS_ANALYSIS (parts of one rank's analysis; 0: one graph), DSSS_SYM_THREADS
     bool local = true;                              // DSSS_PG_LOCAL=0: several ranks keep the replicated analysis
+    bool bins_serial = false;                       // DSSS_PG_BINS=serial: the bins' columns phase after phase (pg_factor_subtree_serial_kernel), what the pipelined kernel is held to
 };
 pg_switches pg_switches_read();
 

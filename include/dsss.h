@@ -315,6 +315,13 @@ int dsss_host_pg_solve_local(int ns, const int32_t* edge_a, const int32_t* edge_
  * ns-1 edges must be the chain.                                                                                               */
 int dsss_host_pg_solve_parts(int ns, const int32_t* edge_a, const int32_t* edge_b, int nedges, const double* cx, const double* cy,
                              int K, const double* aval36, const double* rhs6, double* x6_host, int64_t* stats8);
+/* What the binned subtrees of the analysis look like to pg_factor_subtree_kernel (the one-graph analysis with the device solve's
+ * bin cost, as dsss_pg.hip runs it below 1 500 variables): which branches of the kernel a graph reaches.  prof12: bins; binned columns;
+ * bins of one column; columns without updates directly after one with updates; columns whose predecessor in the bin is one of their
+ * sources; columns with updates whose predecessor is none; most updates of a column NOT counting such a predecessor; most blocks of a
+ * column; most roots of a bin; pairs of consecutive columns of a bin that both add to the same root's update matrix; most columns
+ * of a bin; most updates of a column.                                                                                         */
+int dsss_host_pg_bins_profile(int ns, const int32_t* edge_a, const int32_t* edge_b, int nedges, const double* cx, const double* cy, int64_t* prof12);
 
 /* ------------------------------------------------------------------ mosaic (new: the reference ends at the trajectory file,
  * optimizer.cpp:1164-1214, and has no mosaic -- there is no reference line to cite for anything in this section)
