@@ -411,10 +411,12 @@ def pg_select_lc(frame_rows, pair_s, pair_t, pair_off, kp7, lcs):
 _REDUCED_FN = C.CFUNCTYPE(C.c_int, C.c_int, C.c_int, c_ip, c_ip, c_dp, c_dp)
 
 
-def _make_reduced_solver(refine, log):
+def _make_reduced_solver(refine, log, post=None):
     """The reduced (separator) system of orc_pg_solve through scipy's sparse LU (SuperLU, symmetric mode) instead of the
     envelope Cholesky: what lets the oracle's own LM run at the size of BASELINE config 3 / 4 in a minute.  `refine`
-    steps of iterative refinement with the residual accumulated in long double."""
+    steps of iterative refinement with the residual accumulated in long double.  `post` (optional): post(ns, x) -> x, applied to
+    every reduced solution (ns x 6 values, separator-major) before it goes back into the C loop -- how a test plants a faulty
+    linear solve (tests/test_pg_step_cpu.py); unused, nothing changes."""
     import scipy.sparse as sp
     import scipy.sparse.linalg as spla
 
@@ -442,6 +444,8 @@ def _make_reduced_solver(refine, log):
                 res = b0.astype(np.longdouble)
                 np.subtract.at(res, Ac.row, Ac.data.astype(np.longdouble) * x[Ac.col].astype(np.longdouble))
                 x = x + lu.solve(res.astype(np.float64))
+            if post is not None:
+                x = np.ascontiguousarray(post(ns, x), np.float64).reshape(ns * 6)
             if not np.all(np.isfinite(x)):
                 return -1
             b[:] = x
@@ -454,9 +458,10 @@ def _make_reduced_solver(refine, log):
     return _REDUCED_FN(solve)
 
 
-def pg_solve(dr, edges, params=None, solver="envelope", refine=0, log=None, full_refine=0):
+def pg_solve(dr, edges, params=None, solver="envelope", refine=0, log=None, full_refine=0, reduced_post=None):
     """orc_pg_solve.  solver = "envelope" (the C file's own exact skyline Cholesky; small graphs) or "sparse" (the same LM loop,
-    chain condensation and back-substitution with the reduced system solved by scipy's sparse LU: full-size graphs)."""
+    chain condensation and back-substitution with the reduced system solved by scipy's sparse LU: full-size graphs).
+    reduced_post: the `post` of _make_reduced_solver (sparse only)."""
     dr = np.ascontiguousarray(dr, np.float64).reshape(-1, 6)
     p = params or pg_params()
     out = np.zeros((len(dr), 12), np.float64); stats = np.zeros(4, np.float64)
@@ -465,10 +470,10 @@ def pg_solve(dr, edges, params=None, solver="envelope", refine=0, log=None, full
     L.orc_pg_set_reduced_solver.argtypes = [C.c_void_p]
     cb = None
     if solver == "sparse":
-        cb = _make_reduced_solver(refine, log)
+        cb = _make_reduced_solver(refine, log, reduced_post)
         L.orc_pg_set_reduced_solver(C.cast(cb, C.c_void_p))
     else:
-        assert solver == "envelope"
+        assert solver == "envelope" and reduced_post is None
     L.orc_pg_set_full_refine(int(full_refine))
     try:
         L.orc_pg_solve(dp(dr), len(dr), edges.ctypes.data_as(C.POINTER(LCEdge)), len(edges), C.byref(p), dp(out), dp(stats))
@@ -481,7 +486,7 @@ def pg_solve(dr, edges, params=None, solver="envelope", refine=0, log=None, full
 PG_TRACE_COLS = 5          # ORC_PG_TRACE_COLS: err before the trial, err after it, costChange / linChange, lambda, accepted
 
 
-def _pg_lm_run(dr, edges, params, x0, prior, solver, refine, log, full_refine, call):
+def _pg_lm_run(dr, edges, params, x0, prior, solver, refine, log, full_refine, call, reduced_post=None):
     """the preparation shared by pg_solve_init and pg_solve_path: contiguous arguments, the reduced solver and full_refine set for the one
     call and reset after it.  call(L, dr, n, edges, ne, params, x0, n_init, prior, out, stats) runs the entry point; returns (out, stats)."""
     dr = np.ascontiguousarray(dr, np.float64).reshape(-1, 6)
@@ -495,10 +500,10 @@ def _pg_lm_run(dr, edges, params, x0, prior, solver, refine, log, full_refine, c
     L.orc_pg_set_reduced_solver.argtypes = [C.c_void_p]
     cb = None
     if solver == "sparse":
-        cb = _make_reduced_solver(refine, log)
+        cb = _make_reduced_solver(refine, log, reduced_post)
         L.orc_pg_set_reduced_solver(C.cast(cb, C.c_void_p))
     else:
-        assert solver == "envelope"
+        assert solver == "envelope" and reduced_post is None
     L.orc_pg_set_full_refine(int(full_refine))
     try:
         call(L, dp(dr), len(dr), edges.ctypes.data_as(C.POINTER(LCEdge)), len(edges), C.byref(p),
@@ -509,16 +514,17 @@ def _pg_lm_run(dr, edges, params, x0, prior, solver, refine, log, full_refine, c
     return out, stats
 
 
-def pg_solve_init(dr, edges, params=None, x0=None, prior=None, solver="envelope", refine=0, log=None, full_refine=0, trace_cap=256):
+def pg_solve_init(dr, edges, params=None, x0=None, prior=None, solver="envelope", refine=0, log=None, full_refine=0, trace_cap=256,
+                  reduced_post=None):
     """orc_pg_solve_init: the LM of pg_solve started at x0 (n_init x 12: the first n_init poses; the others start at DR o noise or DR)
     with the prior measuring `prior` (12 doubles; None: DR[0]).  Returns (poses, stats, trace): trace holds one row of PG_TRACE_COLS per
-    trial whose linearised change was non-negative, in order.  solver as in pg_solve."""
+    trial whose linearised change was non-negative, in order.  solver and reduced_post as in pg_solve."""
     trace = np.full((max(int(trace_cap), 1), PG_TRACE_COLS), np.nan)
 
     def call(L, dr_, n, e, ne, p, x0_, n_init, prior_, out, stats):
         L.orc_pg_solve_init.argtypes = [c_dp, C.c_int, C.POINTER(LCEdge), C.c_int, C.POINTER(PGParams), c_dp, C.c_int, c_dp, c_dp, C.c_int, c_dp, c_dp]
         L.orc_pg_solve_init(dr_, n, e, ne, p, x0_, n_init, prior_, dp(trace), len(trace), out, stats)
-    out, stats = _pg_lm_run(dr, edges, params, x0, prior, solver, refine, log, full_refine, call)
+    out, stats = _pg_lm_run(dr, edges, params, x0, prior, solver, refine, log, full_refine, call, reduced_post)
     return out, stats, trace[~np.isnan(trace[:, 0])].copy()
 
 
@@ -526,7 +532,8 @@ PG_PATH_COLS = 6           # ORC_PG_PATH_COLS: the trace's five (NaN where the t
 PG_TRIAL_DECIDED, PG_TRIAL_LIN_NEG, PG_TRIAL_FACTOR_FAILED = 0, 1, 2
 
 
-def pg_solve_path(dr, edges, params=None, x0=None, prior=None, solver="envelope", refine=0, log=None, full_refine=0, path_cap=1024):
+def pg_solve_path(dr, edges, params=None, x0=None, prior=None, solver="envelope", refine=0, log=None, full_refine=0, path_cap=1024,
+                  reduced_post=None):
     """orc_pg_solve_path: pg_solve_init with EVERY trial on record.  Returns (poses, stats, trace, path, ntrials): poses, stats and trace
     as pg_solve_init returns them; path holds one row of PG_PATH_COLS per trial, the failed factorisations and the trials whose linearised
     change was negative included; ntrials counts the trials whatever path_cap is."""
@@ -538,7 +545,7 @@ def pg_solve_path(dr, edges, params=None, x0=None, prior=None, solver="envelope"
         L.orc_pg_solve_path.argtypes = [c_dp, C.c_int, C.POINTER(LCEdge), C.c_int, C.POINTER(PGParams), c_dp, C.c_int, c_dp, c_dp, C.c_int,
                                         c_dp, C.c_int, C.POINTER(C.c_int), c_dp, c_dp]
         L.orc_pg_solve_path(dr_, n, e, ne, p, x0_, n_init, prior_, dp(trace), cap, dp(path), cap, C.byref(ntrials), out, stats)
-    out, stats = _pg_lm_run(dr, edges, params, x0, prior, solver, refine, log, full_refine, call)
+    out, stats = _pg_lm_run(dr, edges, params, x0, prior, solver, refine, log, full_refine, call, reduced_post)
     return out, stats, trace[~np.isnan(trace[:, 0])].copy(), path[~np.isnan(path[:, 5])].copy(), ntrials.value
 
 

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from tests import pg_paths_ref as P
+from tests.pg_step_ref import _reduced
 
 pytestmark = pytest.mark.gpu
 
@@ -26,27 +27,6 @@ def ctx():
     c = capi.Context(max_frames=2)
     yield c
     c.close()
-
-
-def _reduced(dr, e, chunk=16):
-    """the reduced graph as pg_solve::separators builds it: the poses a closure touches and the two ends, plus, in a gap of more than 16 chunks, the
-    first chunk end at least 16 chunks after the last separator; the chain of the separators first, then one chord per closure"""
-    n = len(dr)
-    true = np.unique(np.concatenate([[0, n - 1], e["a"], e["b"]])).astype(np.int64)
-    sep, last, run = [], 0, 16 * chunk
-    for b in true:
-        while True:
-            nx = (last + run + chunk - 1) // chunk * chunk
-            if nx >= b:
-                break
-            sep.append(nx); last = nx
-        sep.append(int(b)); last = int(b)
-    sep = np.array(sep, np.int64)
-    idx = -np.ones(n, np.int64); idx[sep] = np.arange(len(sep))
-    ns = len(sep)
-    ea = np.concatenate([np.arange(ns - 1), idx[e["a"]]]).astype(np.int32)
-    eb = np.concatenate([np.arange(1, ns), idx[e["b"]]]).astype(np.int32)
-    return ns, ea, eb, np.ascontiguousarray(dr[sep, 3]), np.ascontiguousarray(dr[sep, 4])
 
 
 def _profile(dr, e):
