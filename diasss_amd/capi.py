@@ -84,6 +84,26 @@ class RegEdgeParams(C.Structure):
     _fields_ = [("min_zncc", C.c_double), ("sigma_xy_cells", C.c_double), ("sigma_z", C.c_double), ("sigma_rot", C.c_double)]
 
 
+class RegYawParams(C.Structure):
+    """dsss_reg_yaw_params: the fan of rotations a segment is registered under: nyaw angles (odd, 1..17), step radians apart, about 0"""
+    _fields_ = [("nyaw", C.c_int32), ("pad_", C.c_int32), ("step", C.c_double)]
+
+
+class RegSegYaw(C.Structure):
+    """dsss_reg_seg_yaw: s = the RegSeg of the chosen angle k, yaw_on_border = 1 when k is the first or the last angle of the fan, theta =
+    the chosen angle, theta_hat = the angle refined by a parabola through the neighbours' ZNCC, zncc_k0 = the peak ZNCC without rotation"""
+    _fields_ = [("s", RegSeg), ("k", C.c_int32), ("yaw_on_border", C.c_int32), ("theta", C.c_double), ("theta_hat", C.c_double),
+                ("zncc_k0", C.c_double)]
+
+
+REGSEGYAW_DTYPE = np.dtype(RegSegYaw)    # the rows Context.mosaic_register_segments_yaw returns (field "s" is a REGSEG_DTYPE record)
+
+
+class RegEdgeYawParams(C.Structure):
+    """dsss_reg_edge_yaw_params: e = the RegEdgeParams, fan = the fan the rows were registered with, sigma of the yaw in steps of the fan"""
+    _fields_ = [("e", RegEdgeParams), ("fan", RegYawParams), ("sigma_yaw_steps", C.c_double)]
+
+
 class PGGateParams(C.Structure):
     """dsss_pg_gate_params: chi-square gate, the factor between the worst kept edge and the threshold of a round, solves at most"""
     _fields_ = [("gate", C.c_double), ("decade", C.c_double), ("max_solves", C.c_int32), ("pad_", C.c_int32)]
@@ -236,6 +256,25 @@ def lib():
         L.dsss_mosaic_register_edges.restype = C.c_int
         L.dsss_mosaic_register_edges.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(MosaicParams), C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_int, C.POINTER(RegEdgeParams), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        L.dsss_reg_yaw_params_default.restype = None
+        L.dsss_reg_yaw_params_default.argtypes = [C.POINTER(RegYawParams)]
+        L.dsss_register_rotate_rows.restype = C.c_int
+        L.dsss_register_rotate_rows.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p]
+        L.dsss_register_yaw_peak.restype = C.c_int
+        L.dsss_register_yaw_peak.argtypes = [C.c_void_p, C.c_int, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double),
+                                             C.POINTER(C.c_double)]
+        L.dsss_mosaic_register_segments_yaw.restype = C.c_int
+        L.dsss_mosaic_register_segments_yaw.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(MosaicParams), C.c_void_p,
+                                                        C.c_void_p, C.c_int, C.c_int, C.POINTER(RegParams), C.POINTER(RegYawParams), C.c_void_p, C.c_int,
+                                                        C.POINTER(C.c_int), C.c_void_p]
+        L.dsss_reg_edge_yaw_params_default.restype = None
+        L.dsss_reg_edge_yaw_params_default.argtypes = [C.POINTER(RegEdgeYawParams)]
+        L.dsss_register_edge_yaw.restype = C.c_int
+        L.dsss_register_edge_yaw.argtypes = [C.c_void_p, C.POINTER(MosaicParams), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                             C.POINTER(RegEdgeYawParams), C.c_void_p]
+        L.dsss_mosaic_register_edges_yaw.restype = C.c_int
+        L.dsss_mosaic_register_edges_yaw.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(MosaicParams), C.c_void_p, C.c_void_p,
+                                                     C.c_void_p, C.c_int, C.POINTER(RegEdgeYawParams), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
         _LIB = L
     return _LIB
 
@@ -320,6 +359,64 @@ def register_edge(seg, grid, rows_a, base_a, rows_b, base_b, params=None):
         e = DsssError("dsss_register_edge: %s" % L.dsss_strerror(rc).decode())
         e.code = rc
         raise e
+    return edge[0] if rc == 1 else None
+
+
+def reg_yaw_params_default():
+    y = RegYawParams(); lib().dsss_reg_yaw_params_default(C.byref(y)); return y
+
+
+def reg_edge_yaw_params_default():
+    e = RegEdgeYawParams(); lib().dsss_reg_edge_yaw_params_default(C.byref(e)); return e
+
+
+def _host_error(L, name, rc):
+    e = DsssError("%s: %s" % (name, L.dsss_strerror(rc).decode()))
+    e.code = rc
+    return e
+
+
+def register_rotate_rows(rows_b, p0, p1, theta):
+    """dsss_register_rotate_rows: the pings [p0, p1) of the "r p y x y z" rows rows_b turned by theta (radians) about the position of ping
+    (p0 + p1) // 2 -> (p1 - p0) x 6.  theta == 0 copies the rows.  Host arithmetic, no context."""
+    L = lib()
+    if rows_b is not None:
+        rows_b = np.ascontiguousarray(rows_b, np.float64).reshape(-1, 6)
+    out = np.zeros((max(int(p1) - int(p0), 1), 6), np.float64)
+    rc = L.dsss_register_rotate_rows(_ptr(rows_b), 0 if rows_b is None else len(rows_b), int(p0), int(p1), C.c_double(theta), _ptr(out))
+    if rc != 0:
+        raise _host_error(L, "dsss_register_rotate_rows", rc)
+    return out
+
+
+def register_yaw_peak(per_angle, step):
+    """dsss_register_yaw_peak: the angle rule on the records of one (pair, segment) under the nyaw = len(per_angle) angles of a fan
+    (REG_DTYPE rows) -> (k, yaw_on_border, theta, theta_hat).  Host arithmetic, no context."""
+    L = lib()
+    per_angle = np.ascontiguousarray(per_angle, REG_DTYPE)
+    k = C.c_int32(0); border = C.c_int32(0); theta = C.c_double(0.0); hat = C.c_double(0.0)
+    rc = L.dsss_register_yaw_peak(_ptr(per_angle), len(per_angle), C.c_double(step), C.byref(k), C.byref(border), C.byref(theta), C.byref(hat))
+    if rc != 0:
+        raise _host_error(L, "dsss_register_yaw_peak", rc)
+    return k.value, border.value, theta.value, hat.value
+
+
+def register_edge_yaw(seg, grid, rows_a, base_a, rows_b, base_b, params=None):
+    """dsss_register_edge_yaw: register_edge for one row of REGSEGYAW_DTYPE (or a RegSegYaw); params: a RegEdgeYawParams that names the
+    fan the row was registered with (None = the defaults, a fan of one angle) -> a record of LCEDGE_DTYPE, or None when the row is rejected."""
+    L = lib()
+    if seg is not None and not isinstance(seg, RegSegYaw):
+        seg = RegSegYaw.from_buffer_copy(np.asarray(seg, REGSEGYAW_DTYPE).tobytes())
+    if rows_a is not None:
+        rows_a = np.ascontiguousarray(rows_a, np.float64).reshape(-1, 6)
+    if rows_b is not None:
+        rows_b = np.ascontiguousarray(rows_b, np.float64).reshape(-1, 6)
+    edge = np.zeros(1, LCEDGE_DTYPE)
+    rc = L.dsss_register_edge_yaw(C.byref(seg) if seg is not None else None, C.byref(grid) if grid is not None else None,
+                                  _ptr(rows_a), 0 if rows_a is None else len(rows_a), int(base_a), _ptr(rows_b), 0 if rows_b is None else len(rows_b),
+                                  int(base_b), C.byref(params) if params is not None else None, _ptr(edge))
+    if rc < 0:
+        raise _host_error(L, "dsss_register_edge_yaw", rc)
     return edge[0] if rc == 1 else None
 
 
@@ -807,6 +904,48 @@ class Context:
         self._chk(self.L.dsss_mosaic_register_edges(self.h, _ptr(ids), len(ids), _ptr(rpy6), _ptr(ping_off), C.byref(params), _ptr(pa), _ptr(pb),
                                                     _ptr(segs), len(segs), C.byref(edge_params) if edge_params is not None else None,
                                                     _ptr(edges), _ptr(src), cap, C.byref(ne)), "dsss_mosaic_register_edges")
+        return edges[:ne.value].copy(), src[:ne.value].copy()
+
+    def mosaic_register_segments_yaw(self, ids, params, pairs, seg_pings, yaw=None, reg=None, rpy6=None, ping_off=None, want_sums=False, cap=None):
+        """mosaic_register_segments with every segment registered under the angles of the fan `yaw` (a RegYawParams, None = the default
+        of one angle) as well -> rows of REGSEGYAW_DTYPE: s = the row of the best angle k, with theta, theta_hat, yaw_on_border and the
+        unrotated angle's ZNCC.  want_sums=True returns (rows, sums) with sums[nseg, nyaw, 2 r + 1, 2 r + 1, 6] uint64."""
+        ids, rpy6, ping_off = self._mosaic_traj(ids, rpy6, ping_off)
+        pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        pa = np.ascontiguousarray(pairs[:, 0]); pb = np.ascontiguousarray(pairs[:, 1])
+        r = reg if reg is not None else reg_params_default()
+        y = yaw if yaw is not None else reg_yaw_params_default()
+        S = 2 * max(0, min(int(r.radius), 16)) + 1
+        A = max(1, min(int(y.nyaw), 17))
+        args = (self.h, _ptr(ids), len(ids), _ptr(rpy6), _ptr(ping_off), C.byref(params), _ptr(pa), _ptr(pb), len(pairs), int(seg_pings), C.byref(r),
+                C.byref(y))
+        nseg = C.c_int(0)
+        if cap is None:                                    # the library counts the rows before it launches anything: ask with no room
+            one = np.zeros(1, REGSEGYAW_DTYPE)
+            rc = self.L.dsss_mosaic_register_segments_yaw(*args, _ptr(one), 0, C.byref(nseg), None)
+            if rc != -5:                                   # DSSS_E_CAPACITY: nseg rows are needed; 0: there are none; anything else is an error
+                self._chk(rc, "dsss_mosaic_register_segments_yaw")
+            cap = nseg.value
+        out = np.zeros(max(cap, 1), REGSEGYAW_DTYPE)
+        sums = np.zeros((max(cap, 1), A, S, S, 6), np.uint64) if want_sums else None
+        self._chk(self.L.dsss_mosaic_register_segments_yaw(*args, _ptr(out), int(cap), C.byref(nseg), _ptr(sums)), "dsss_mosaic_register_segments_yaw")
+        out = out[:nseg.value]
+        return (out, sums[:nseg.value]) if want_sums else out
+
+    def mosaic_register_edges_yaw(self, ids, params, pairs, segs, edge_params=None, rpy6=None, ping_off=None, cap=None):
+        """mosaic_register_edges for the rows of mosaic_register_segments_yaw (REGSEGYAW_DTYPE); edge_params: a RegEdgeYawParams that names
+        the fan the rows were registered with -> (edges, edge_seg).  The edges measure the heading too.  Launches no GPU work."""
+        ids, rpy6, ping_off = self._mosaic_traj(ids, rpy6, ping_off)
+        pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        pa = np.ascontiguousarray(pairs[:, 0]); pb = np.ascontiguousarray(pairs[:, 1])
+        segs = np.ascontiguousarray(segs, REGSEGYAW_DTYPE)
+        if len(segs) and (segs["s"]["pair"].min() < 0 or segs["s"]["pair"].max() >= len(pairs)):
+            raise ValueError("mosaic_register_edges_yaw: a row names a pair outside the %d given" % len(pairs))
+        cap = len(segs) if cap is None else int(cap)
+        edges = np.zeros(max(cap, 1), LCEDGE_DTYPE); src = np.zeros(max(cap, 1), np.int32); ne = C.c_int(0)
+        self._chk(self.L.dsss_mosaic_register_edges_yaw(self.h, _ptr(ids), len(ids), _ptr(rpy6), _ptr(ping_off), C.byref(params), _ptr(pa), _ptr(pb),
+                                                        _ptr(segs), len(segs), C.byref(edge_params) if edge_params is not None else None,
+                                                        _ptr(edges), _ptr(src), cap, C.byref(ne)), "dsss_mosaic_register_edges_yaw")
         return edges[:ne.value].copy(), src[:ne.value].copy()
 
     # ---- instrumentation

@@ -348,5 +348,17 @@ __host__ __device__ inline void dsss_geo_at(const double* pose6, const double* g
     dsss_geo_side(P, col >= M / 2, &s, &c);
     dsss_geo_bin(P, gr, M, col, s, c, x, y);
 }
+// One ping of a segment rotated by theta about the pivot (cx, cy) (include/dsss.h, "dense loop closures with a yaw fan"): s, c =
+// dsss_sincos(theta).  The only place this arithmetic is written: mosaic_scatter_fan_kernel, the windows of rotated segments and
+// dsss_register_rotate_rows call it.  theta == 0 copies the row, so the unrotated angle is the existing registration bit for bit.
+__host__ __device__ inline void dsss_rotate_row(const double* row, double cx, double cy, double theta, double s, double c, double* out)
+{
+    out[0] = row[0]; out[1] = row[1]; out[5] = row[5];
+    if (theta == 0.0) { out[2] = row[2]; out[3] = row[3]; out[4] = row[4]; return; }
+    const double dx = row[3] - cx, dy = row[4] - cy;
+    out[3] = cx + (c * dx - s * dy);
+    out[4] = cy + (s * dx + c * dy);
+    out[2] = row[2] + theta;
+}
 // a DR yaw that switches the sticky pi-yaw compensation of LoopClosingTFs on (optimizer.cpp:697-703)
 __host__ __device__ inline bool dsss_yaw_flips(double yaw) { return fabs(yaw) > 2 * DSSS_PI_REF / 3; }

@@ -16,7 +16,8 @@ namespace {
 //
 // SEG: the segmented form of the registration's segment layers.  The ping's segment (row / seg_pings) selects the window (ox, oy, bw, bh
 // of G are replaced by the segment's) and the accumulator area (acc + the segment's offset), so one launch renders every segment of a
-// frame; everything else, the arithmetic of a sample included, is the one body.
+// frame; everything else, the arithmetic of a sample included (mosaic_scatter_samples, dsss_mosaic_int.h: the registration's yaw fan
+// runs it too), is the one body.
 template <bool SEG>
 __device__ __forceinline__ void mosaic_scatter_body(const mosaic_job* __restrict__ jobs, int njobs, mosaic_win G, unsigned long long* __restrict__ acc,
                                                     const mosaic_seg* __restrict__ segs, int seg_pings)
@@ -25,7 +26,7 @@ __device__ __forceinline__ void mosaic_scatter_body(const mosaic_job* __restrict
     int lo = 0, hi = njobs - 1;
     while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (jobs[mid].blk0 <= (int)blockIdx.x) lo = mid; else hi = mid - 1; }
     const mosaic_job J = jobs[lo];
-    const int row = (int)blockIdx.x - J.blk0, M = J.M, half = M / 2;
+    const int row = (int)blockIdx.x - J.blk0;
     if (row >= J.N) return;                                                        // (uniform per workgroup; cannot happen with the host's blk0)
     if (SEG) {
         const mosaic_seg sg = segs[row / seg_pings];
@@ -35,31 +36,7 @@ __device__ __forceinline__ void mosaic_scatter_body(const mosaic_job* __restrict
     const double* P = J.pose + (size_t)row * 6;
     if (threadIdx.x < 2) dsss_geo_side(P, threadIdx.x == 1, &s_sc[2 * threadIdx.x], &s_sc[2 * threadIdx.x + 1]);
     __syncthreads();
-    const uint8_t* __restrict__ img = J.img + (size_t)row * M;
-    const uint8_t* __restrict__ mask = J.mask + (size_t)row * M;
-    const int lane = threadIdx.x & 63;
-    for (int c0 = 0; c0 < M; c0 += 256) {
-        const int col = c0 + (int)threadIdx.x;
-        int key = -1; unsigned v = 0;                                              // v: count << 16 | sum within the wavefront
-        if (col < M && (!G.use_mask || mask[col] != 0)) {
-            const int side = col >= half;
-            double x, y;
-            dsss_geo_bin(P, J.gr, M, col, s_sc[2 * side], s_sc[2 * side + 1], &x, &y);
-            const double fx = floor((x - G.x0) / G.cell), fy = floor((y - G.y0) / G.cell);
-            if (fx >= 0.0 && fx < (double)G.W && fy >= 0.0 && fy < (double)G.H) {  // on the f64 values: NaN, infinite and huge points drop out here
-                const int ix = (int)fx - G.ox, iy = (int)fy - G.oy;
-                if (ix >= 0 && ix < G.bw && iy >= 0 && iy < G.bh) { key = iy * G.bw + ix; v = (1u << 16) | img[col]; }
-            }
-        }
-        const int prev = __shfl_up(key, 1);
-        const bool head = lane == 0 || prev != key;
-        const unsigned long long hb = __ballot(head);
-        const int start = 63 - __clzll((long long)(hb & (~0ull >> (63 - lane))));   // first lane of this lane's run
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const unsigned t = __shfl_up(v, d); if (lane - d >= start) v += t; }
-        const bool tail = lane == 63 || ((hb >> (lane + 1)) & 1ull);
-        if (tail && key >= 0) atomicAdd(&acc[key], ((unsigned long long)(v >> 16) << 32) | (v & 0xffffu));
-    }
+    mosaic_scatter_samples(P, s_sc, J, row, G, acc);
 }
 
 __global__ __launch_bounds__(256) void mosaic_scatter_kernel(const mosaic_job* __restrict__ jobs, int njobs, mosaic_win G,

@@ -16,6 +16,40 @@ struct mosaic_win { double x0, y0, cell; int W, H, ox, oy, bw, bh, use_mask; };
 // accumulators start, in cells, behind the frame's first
 struct mosaic_seg { int ox, oy, bw, bh; unsigned long long off; };
 
+// The samples of one ping, by the 256 threads of its workgroup (mosaic_scatter_kernel's comment in dsss_mosaic.hip): P = the ping's
+// pose row, sc = sin and cos of the bearing of the port and of the starboard side (dsss_geo_side on P, in LDS), row = the ping's row
+// in the frame's images, G = grid and window, acc = the window's accumulators.  The one place a sample is binned on the device.
+__device__ __forceinline__ void mosaic_scatter_samples(const double* P, const double* sc, const mosaic_job& J, int row, const mosaic_win& G,
+                                                       unsigned long long* __restrict__ acc)
+{
+    const int M = J.M, half = M / 2;
+    const uint8_t* __restrict__ img = J.img + (size_t)row * M;
+    const uint8_t* __restrict__ mask = J.mask + (size_t)row * M;
+    const int lane = threadIdx.x & 63;
+    for (int c0 = 0; c0 < M; c0 += 256) {
+        const int col = c0 + (int)threadIdx.x;
+        int key = -1; unsigned v = 0;                                              // v: count << 16 | sum within the wavefront
+        if (col < M && (!G.use_mask || mask[col] != 0)) {
+            const int side = col >= half;
+            double x, y;
+            dsss_geo_bin(P, J.gr, M, col, sc[2 * side], sc[2 * side + 1], &x, &y);
+            const double fx = floor((x - G.x0) / G.cell), fy = floor((y - G.y0) / G.cell);
+            if (fx >= 0.0 && fx < (double)G.W && fy >= 0.0 && fy < (double)G.H) {  // on the f64 values: NaN, infinite and huge points drop out here
+                const int ix = (int)fx - G.ox, iy = (int)fy - G.oy;
+                if (ix >= 0 && ix < G.bw && iy >= 0 && iy < G.bh) { key = iy * G.bw + ix; v = (1u << 16) | img[col]; }
+            }
+        }
+        const int prev = __shfl_up(key, 1);
+        const bool head = lane == 0 || prev != key;
+        const unsigned long long hb = __ballot(head);
+        const int start = 63 - __clzll((long long)(hb & (~0ull >> (63 - lane))));   // first lane of this lane's run
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) { const unsigned t = __shfl_up(v, d); if (lane - d >= start) v += t; }
+        const bool tail = lane == 63 || ((hb >> (lane + 1)) & 1ull);
+        if (tail && key >= 0) atomicAdd(&acc[key], ((unsigned long long)(v >> 16) << 32) | (v & 0xffffu));
+    }
+}
+
 // carves mosaic_buf into 256-byte aligned pieces
 struct carve { size_t off = 0; size_t take(size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; } };
 

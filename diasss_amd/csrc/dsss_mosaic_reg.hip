@@ -7,6 +7,9 @@
 // Dense loop closures ("dense loop closures" in the header): the same registration with frame b cut into segments of pings
 // (dsss_mosaic_register_segments: one segmented scatter and one pack per frame, the correlation kernel through its job table,
 // mosaic_centroid_kernel for where the overlap lies), and a segment's offset as a pose-graph edge (dsss_register_edge, host arithmetic).
+// With a yaw fan ("dense loop closures with a yaw fan"): every segment rendered under a fan of small rotations as well
+// (mosaic_scatter_fan_kernel: one scatter per frame for all its segments and angles), the correlation once per angle, the angle rule
+// on the host (dsss_register_yaw_peak) and an edge that measures the heading too (dsss_register_edge_yaw).
 #include "dsss_mosaic_int.h"
 #include "dsss_pose.h"
 #include "dsss_wave.h"
@@ -160,6 +163,33 @@ __global__ __launch_bounds__(256) void mosaic_centroid_kernel(const cen_job* __r
     if (((int)threadIdx.x & 63) == 0 && n != 0) { atomicAdd(J.out + 0, n); atomicAdd(J.out + 1, sx); atomicAdd(J.out + 2, sy); }
 }
 
+// one (segment, angle) of a frame in the fan scatter: the window of the segment's pings rotated by theta about the pivot (cx, cy)
+// (bw = 0: no cell of it lies on the grid), where its accumulators start, in cells, behind the frame's first, and s, c = dsss_sincos(theta)
+struct mosaic_fan { int ox, oy, bw, bh; unsigned long long off; double cx, cy, theta, s, c; };
+
+// mosaic_scatter_seg_kernel with one more degree of freedom, the angle: a workgroup is a (ping, angle), angles next to each other so
+// that the workgroups that read a ping's image row run together.  The entry of (ping / seg_pings, angle) selects window and
+// accumulators as a segment does there; the ping's row is rotated into LDS (dsss_rotate_row: the trajectory is never rotated on the
+// host and uploaded), the bearings come from the rotated yaw, and the samples are binned by the one body (mosaic_scatter_samples).
+// One launch renders every segment of a frame under every angle of the fan.
+__global__ __launch_bounds__(256) void mosaic_scatter_fan_kernel(const mosaic_job* __restrict__ job, mosaic_win G, unsigned long long* __restrict__ acc,
+                                                                 const mosaic_fan* __restrict__ fan, int seg_pings, int nyaw)
+{
+    __shared__ double s_sc[4], s_row[2][6];                                        // the rotated row once per side: the two lanes that need it for the bearing write it
+    const mosaic_job J = *job;
+    const int row = (int)(blockIdx.x / (unsigned)nyaw), k = (int)(blockIdx.x - (unsigned)row * (unsigned)nyaw);
+    if (row >= J.N) return;                                                        // (uniform per workgroup; cannot happen with the host's grid)
+    const mosaic_fan F = fan[(size_t)(row / seg_pings) * nyaw + k];
+    if (F.bw <= 0) return;                                                         // nothing of this segment under this angle on the grid (uniform)
+    G.ox = F.ox; G.oy = F.oy; G.bw = F.bw; G.bh = F.bh; acc += F.off;
+    if (threadIdx.x < 2) {
+        dsss_rotate_row(J.pose + (size_t)row * 6, F.cx, F.cy, F.theta, F.s, F.c, s_row[threadIdx.x]);
+        dsss_geo_side(s_row[threadIdx.x], threadIdx.x == 1, &s_sc[2 * threadIdx.x], &s_sc[2 * threadIdx.x + 1]);
+    }
+    __syncthreads();
+    mosaic_scatter_samples(s_row[0], s_sc, J, row, G, acc);
+}
+
 // exact integer -> the nearest double, ties to even (what Python's float() of an int does): below 2^64 the hardware conversion is that
 // already; above, the value is cut to 64 bits with a sticky bit first, which leaves the rounding of the 53-bit result unchanged
 double i128_to_double(__int128 v)
@@ -289,6 +319,157 @@ int reg_launch_corr(dsss_ctx* c, const std::vector<reg_job>& pj, long long block
     HIPCHK(c, hipMemcpyAsync(d_pairs, pj.data(), pj.size() * sizeof(reg_job), hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(mosaic_corr_kernel, dim3((unsigned)blocks), dim3((unsigned)threads), 0, c->stream, d_pairs, (int)pj.size(), r);
     HIPCHK(c, hipGetLastError());
+    return DSSS_OK;
+}
+
+// the centroid job of a row with the peak q (layers and windows as in reg_push_job), its sums at out, appended to cj; *blocks =
+// workgroups so far.  False: more workgroups than one launch takes.
+bool cen_push_job(std::vector<cen_job>& cj, long long* blocks, const uint16_t* la, const mosaic_win& A, const uint16_t* lb, const mosaic_win& Bw,
+                  const dsss_reg_result& q, unsigned long long* out)
+{
+    cen_job J;
+    J.la = la; J.lb = lb; J.out = out;
+    J.aox = A.ox; J.aoy = A.oy; J.abw = A.bw; J.box = Bw.ox; J.boy = Bw.oy; J.bbw = Bw.bw;
+    J.rx0 = std::max(A.ox, Bw.ox - q.dx); J.rx1 = std::min(A.ox + A.bw - 1, Bw.ox + Bw.bw - 1 - q.dx);
+    J.ry0 = std::max(A.oy, Bw.oy - q.dy); J.ry1 = std::min(A.oy + A.bh - 1, Bw.oy + Bw.bh - 1 - q.dy);
+    if (J.rx1 < J.rx0 || J.ry1 < J.ry0) return true;                            // (cannot be: a usable shift has cells; the callers' check of n reports it)
+    J.dx = q.dx; J.dy = q.dy; J.tiles_x = (J.rx1 - J.rx0) / CEN_TW + 1; J.blk0 = (int)*blocks;
+    *blocks += (long long)J.tiles_x * ((J.ry1 - J.ry0) / CEN_TH + 1);
+    if (*blocks > 0x7fffffffll) return false;
+    cj.push_back(J);
+    return true;
+}
+
+// all centroid jobs in one launch, and the nseg x 3 sums back in cen (d_cen was cleared before)
+int reg_launch_centroids(dsss_ctx* c, const std::vector<cen_job>& cj, long long cblocks, cen_job* d_cj, const unsigned long long* d_cen, std::vector<uint64_t>& cen)
+{
+    HIPCHK(c, hipMemcpyAsync(d_cj, cj.data(), cj.size() * sizeof(cen_job), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(mosaic_centroid_kernel, dim3((unsigned)cblocks), dim3(256), 0, c->stream, d_cj, (int)cj.size());
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(cen.data(), d_cen, cen.size() * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return DSSS_OK;
+}
+
+// ---- the yaw fan
+#define REG_MAX_YAW 17
+
+bool fan_ok(int nyaw, double step) { return nyaw >= 1 && nyaw <= REG_MAX_YAW && (nyaw & 1) && step > 0.0 && std::isfinite(step); }
+double fan_theta(int k, int nyaw, double step) { return (double)(k - (nyaw - 1) / 2) * step; }
+
+// the pings [p0, p1) of rows_b rotated by theta about the position of ping (p0 + p1) / 2 -> out, (p1 - p0) x 6
+void rotate_rows(const double* rows_b, int p0, int p1, double theta, double* out)
+{
+    const double* piv = rows_b + (size_t)(((long long)p0 + p1) / 2) * 6;
+    double s, co; dsss_sincos(theta, &s, &co);
+    for (int i = p0; i < p1; ++i) dsss_rotate_row(rows_b + (size_t)i * 6, piv[3], piv[4], theta, s, co, out + (size_t)(i - p0) * 6);
+}
+
+// the angle rule of the header, "dense loop closures with a yaw fan": the one place it is written
+void yaw_peak_of(const dsss_reg_result* z, int nyaw, double step, int32_t* k, int32_t* border, double* theta, double* theta_hat)
+{
+    const int mid = (nyaw - 1) / 2;
+    int best = -1;
+    for (int i = 0; i < nyaw; ++i) {
+        if (!(z[i].zncc > -2.0)) continue;
+        if (best < 0 || z[i].zncc > z[best].zncc || (z[i].zncc == z[best].zncc && abs(i - mid) < abs(best - mid))) best = i;   // equals at one distance: the lower k came first
+    }
+    if (best < 0) { *k = mid; *border = 0; *theta = 0.0; *theta_hat = 0.0; return; }
+    *k = best; *border = (nyaw > 1 && (best == 0 || best == nyaw - 1)) ? 1 : 0;
+    *theta = fan_theta(best, nyaw, step);
+    double q = 0.0;
+    if (!*border && nyaw > 1 && z[best - 1].zncc > -2.0 && z[best + 1].zncc > -2.0) {
+        const double zm = z[best - 1].zncc, z0 = z[best].zncc, zp = z[best + 1].zncc;
+        const double den = zm - 2.0 * z0 + zp;
+        if (den < 0.0) q = 0.5 * (zm - zp) / den;
+    }
+    *theta_hat = *theta + q * step;
+}
+
+// dsss_register_edge and dsss_register_edge_yaw: the segment row s as an edge, its pings rotated by theta where the anchor ping is
+// looked for and by theta_hat where it is measured (both 0: the rows as they are), s_yaw = the sigma of the yaw
+int edge_of(const dsss_reg_seg* s, const dsss_mosaic_params* grid, const double* rows_a, int Na, int base_a, const double* rows_b, int Nb, int base_b,
+            const dsss_reg_edge_params& E, double theta, double theta_hat, double s_yaw, dsss_lc_edge* edge)
+{
+    if (!s || !grid || !rows_a || !rows_b || !edge || Na < 1 || Nb < 1) return DSSS_E_ARG;
+    if (s->p0 < 0 || s->p0 >= s->p1 || s->p1 > Nb) return DSSS_E_ARG;
+    if (!(grid->cell > 0.0) || !std::isfinite(grid->cell)) return DSSS_E_ARG;
+    const double sig[4] = { E.sigma_xy_cells, E.sigma_z, E.sigma_rot, s_yaw };
+    for (double v : sig) if (!(v > 0.0) || !std::isfinite(v)) return DSSS_E_ARG;
+    if (!std::isfinite(theta) || !std::isfinite(theta_hat)) return DSSS_E_ARG;
+    if (!(s->r.zncc >= E.min_zncc) || s->r.on_border != 0) return 0;
+    if (s->r.n <= 0) return DSSS_E_ARG;
+    const double cell = grid->cell;
+    const double cx = grid->x0 + ((double)s->sx / (double)s->r.n + 0.5) * cell, cy = grid->y0 + ((double)s->sy / (double)s->r.n + 0.5) * cell;
+    // the ping whose scan line (through the ping, across the heading) passes nearest the point: the lowest index among equals
+    auto anchor = [](const double* rows, int r0, int r1, double px, double py) {
+        int best = r0; double dbest = INFINITY;
+        for (int i = r0; i < r1; ++i) {
+            const double* P = rows + (size_t)i * 6;
+            const double d = fabs(cos(P[2]) * (px - P[3]) + sin(P[2]) * (py - P[4]));
+            if (d < dbest) { dbest = d; best = i; }
+        }
+        return best;
+    };
+    const int i = anchor(rows_a, 0, Na, cx, cy);
+    std::vector<double> rot((size_t)(s->p1 - s->p0) * 6);                       // the segment's rows under theta (theta == 0: a copy)
+    rotate_rows(rows_b, s->p0, s->p1, theta, rot.data());
+    const int j = s->p0 + anchor(rot.data(), 0, s->p1 - s->p0, cx + s->r.off_x, cy + s->r.off_y);      // b's rendering lies off from where it belongs
+    double rowj[6], sh, ch;                                                     // row j of the rows under theta_hat
+    const double* piv = rows_b + (size_t)(((long long)s->p0 + s->p1) / 2) * 6;
+    dsss_sincos(theta_hat, &sh, &ch);
+    dsss_rotate_row(rows_b + (size_t)j * 6, piv[3], piv[4], theta_hat, sh, ch, rowj);
+    pose_t Xa, Xb, rel;
+    pose_from_rodrigues(rows_a + (size_t)i * 6, &Xa);
+    pose_from_rodrigues(rowj, &Xb);
+    Xb.t[0] -= s->r.off_x; Xb.t[1] -= s->r.off_y;
+    const long long ga = (long long)base_a + i, gb = (long long)base_b + j;
+    if (ga < 0 || gb < 0 || ga > 0x7fffffffll || gb > 0x7fffffffll) return DSSS_E_ARG;
+    if (ga < gb) { edge->a = (int32_t)ga; edge->b = (int32_t)gb; pose_between(&Xa, &Xb, &rel); }
+    else { edge->a = (int32_t)gb; edge->b = (int32_t)ga; pose_between(&Xb, &Xa, &rel); }
+    memcpy(edge->rel, rel.R, 9 * sizeof(double)); memcpy(edge->rel + 9, rel.t, 3 * sizeof(double));
+    const double sxy = E.sigma_xy_cells * cell;
+    edge->var[0] = edge->var[1] = E.sigma_rot * E.sigma_rot; edge->var[2] = s_yaw * s_yaw;
+    edge->var[3] = edge->var[4] = sxy * sxy; edge->var[5] = E.sigma_z * E.sigma_z;
+    return 1;
+}
+
+// the row loop of dsss_mosaic_register_edges and dsss_mosaic_register_edges_yaw: seg_of(k) = the (pair, segment) part of row k,
+// edge_fn(k, rows_a, Na, base_a, rows_b, Nb, base_b, &e) = what dsss_register_edge(_yaw) says about it
+template <class SegOf, class EdgeFn>
+int edges_loop(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, const dsss_mosaic_params* p, const int* pair_a, const int* pair_b,
+               bool have_segs, int nsegs, dsss_lc_edge* edges_host, int32_t* edge_seg_host, int cap, int* n_edges, SegOf seg_of, EdgeFn edge_fn)
+{
+    if (!c) return DSSS_E_ARG;
+    if (dsss_comm_world(c) > 1) DSSS_FAIL(c, DSSS_E_STATE, "mosaic: registration runs on a single rank (communicator of %d)", dsss_comm_world(c));
+    size_t rows = 0;
+    int rc = mosaic_check_frames(c, ids, n, rpy6, ping_off, false, &rows); if (rc) return rc;
+    rc = mosaic_check_params(c, p); if (rc) return rc;
+    if (nsegs < 0 || cap < 0 || !n_edges) DSSS_FAIL(c, DSSS_E_ARG, "register: nsegs = %d, cap = %d%s", nsegs, cap, n_edges ? "" : ", nowhere to write the number of edges");
+    if (nsegs > 0 && (!pair_a || !pair_b || !have_segs)) DSSS_FAIL(c, DSSS_E_ARG, "register: %d segments without %s", nsegs, have_segs ? "their pairs" : "their rows");
+    std::vector<int> slot(c->max_frames, -1), base(n);
+    int run = 0;
+    for (int i = 0; i < n; ++i) { slot[ids[i]] = i; base[i] = ping_off ? ping_off[i] : run; run += c->frames[ids[i]].N; }
+    int ne = 0;
+    for (int k = 0; k < nsegs; ++k) {
+        const dsss_reg_seg& sg = seg_of(k);
+        if (sg.pair < 0) DSSS_FAIL(c, DSSS_E_ARG, "register: row %d names pair %d", k, sg.pair);
+        const int a = pair_a[sg.pair], b = pair_b[sg.pair];
+        if (a < 0 || a >= c->max_frames || slot[a] < 0 || b < 0 || b >= c->max_frames || slot[b] < 0)
+            DSSS_FAIL(c, DSSS_E_ARG, "register: row %d, pair (%d, %d) names a frame that is not listed", k, a, b);
+        const int ia = slot[a], ib = slot[b];
+        const dsss_frame& fa = c->frames[a]; const dsss_frame& fb = c->frames[b];
+        dsss_lc_edge e;
+        rc = edge_fn(k, rpy6 ? rpy6 + (size_t)ping_off[ia] * 6 : fa.h_geo, fa.N, base[ia],
+                     rpy6 ? rpy6 + (size_t)ping_off[ib] * 6 : fb.h_geo, fb.N, base[ib], &e);
+        if (rc < 0) DSSS_FAIL(c, rc, "register: row %d (pair %d, segment %d, pings %d..%d) is not a valid segment result", k, sg.pair, sg.seg, sg.p0, sg.p1);
+        if (rc == 0) continue;
+        if (ne >= cap || !edges_host) DSSS_FAIL(c, DSSS_E_CAPACITY, "register: more than %d edges", edges_host ? cap : 0);
+        edges_host[ne] = e;
+        if (edge_seg_host) edge_seg_host[ne] = k;
+        ++ne;
+    }
+    *n_edges = ne;
     return DSSS_OK;
 }
 
@@ -507,26 +688,13 @@ int dsss_mosaic_register_segments(dsss_ctx* c, const int* ids, int n, const doub
         dsss_reg_result& q = out_host[row].r;
         peak_of(tab + (size_t)row * nshift * 6, r, R.min_cells, p->cell, &q);
         if (!(q.zncc > -2.0)) continue;                                         // no usable shift: sx = sy = 0
-        const mosaic_win& A = wins[row_a[row]]; const mosaic_win& Bw = sw[row_g[row]];
-        cen_job J;
-        J.la = d_lay + lay_off[row_a[row]]; J.lb = d_lay + seg_lay[slot[pair_b[out_host[row].pair]]] + hseg[row_g[row]].off;
-        J.out = d_cen + (size_t)row * 3;
-        J.aox = A.ox; J.aoy = A.oy; J.abw = A.bw; J.box = Bw.ox; J.boy = Bw.oy; J.bbw = Bw.bw;
-        J.rx0 = std::max(A.ox, Bw.ox - q.dx); J.rx1 = std::min(A.ox + A.bw - 1, Bw.ox + Bw.bw - 1 - q.dx);
-        J.ry0 = std::max(A.oy, Bw.oy - q.dy); J.ry1 = std::min(A.oy + A.bh - 1, Bw.oy + Bw.bh - 1 - q.dy);
-        if (J.rx1 < J.rx0 || J.ry1 < J.ry0) continue;                           // (cannot be: a usable shift has cells; the check below reports it)
-        J.dx = q.dx; J.dy = q.dy; J.tiles_x = (J.rx1 - J.rx0) / CEN_TW + 1; J.blk0 = (int)cblocks;
-        cblocks += (long long)J.tiles_x * ((J.ry1 - J.ry0) / CEN_TH + 1);
-        if (cblocks > 0x7fffffffll) DSSS_FAIL(c, DSSS_E_ARG, "register: %d segments are more than one launch takes", nseg);
-        cj.push_back(J);
+        if (!cen_push_job(cj, &cblocks, d_lay + lay_off[row_a[row]], wins[row_a[row]], d_lay + seg_lay[slot[pair_b[out_host[row].pair]]] + hseg[row_g[row]].off,
+                          sw[row_g[row]], q, d_cen + (size_t)row * 3))
+            DSSS_FAIL(c, DSSS_E_ARG, "register: %d segments are more than one launch takes", nseg);
     }
     if (!cj.empty()) {
         std::vector<uint64_t> cen((size_t)nseg * 3);
-        HIPCHK(c, hipMemcpyAsync(d_cj, cj.data(), cj.size() * sizeof(cen_job), hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(mosaic_centroid_kernel, dim3((unsigned)cblocks), dim3(256), 0, c->stream, d_cj, (int)cj.size());
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(cen.data(), d_cen, cen.size() * 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
+        rc = reg_launch_centroids(c, cj, cblocks, d_cj, d_cen, cen); if (rc) return rc;
         for (row = 0; row < nseg; ++row) {
             dsss_reg_seg& o = out_host[row];
             if (!(o.r.zncc > -2.0)) continue;
@@ -547,76 +715,257 @@ int dsss_register_edge(const dsss_reg_seg* s, const dsss_mosaic_params* grid, co
 {
     dsss_reg_edge_params E; dsss_reg_edge_params_default(&E);
     if (ep) E = *ep;
-    if (!s || !grid || !rows_a || !rows_b || !edge || Na < 1 || Nb < 1) return DSSS_E_ARG;
-    if (s->p0 < 0 || s->p0 >= s->p1 || s->p1 > Nb) return DSSS_E_ARG;
-    if (!(grid->cell > 0.0) || !std::isfinite(grid->cell)) return DSSS_E_ARG;
-    const double sig[3] = { E.sigma_xy_cells, E.sigma_z, E.sigma_rot };
-    for (double v : sig) if (!(v > 0.0) || !std::isfinite(v)) return DSSS_E_ARG;
-    if (!(s->r.zncc >= E.min_zncc) || s->r.on_border != 0) return 0;
-    if (s->r.n <= 0) return DSSS_E_ARG;
-    const double cell = grid->cell;
-    const double cx = grid->x0 + ((double)s->sx / (double)s->r.n + 0.5) * cell, cy = grid->y0 + ((double)s->sy / (double)s->r.n + 0.5) * cell;
-    // the ping whose scan line (through the ping, across the heading) passes nearest the point: the lowest index among equals
-    auto anchor = [](const double* rows, int r0, int r1, double px, double py) {
-        int best = r0; double dbest = INFINITY;
-        for (int i = r0; i < r1; ++i) {
-            const double* P = rows + (size_t)i * 6;
-            const double d = fabs(cos(P[2]) * (px - P[3]) + sin(P[2]) * (py - P[4]));
-            if (d < dbest) { dbest = d; best = i; }
-        }
-        return best;
-    };
-    const int i = anchor(rows_a, 0, Na, cx, cy);
-    const int j = anchor(rows_b, s->p0, s->p1, cx + s->r.off_x, cy + s->r.off_y);     // b's rendering lies off from where it belongs
-    pose_t Xa, Xb, rel;
-    pose_from_rodrigues(rows_a + (size_t)i * 6, &Xa);
-    pose_from_rodrigues(rows_b + (size_t)j * 6, &Xb);
-    Xb.t[0] -= s->r.off_x; Xb.t[1] -= s->r.off_y;
-    const long long ga = (long long)base_a + i, gb = (long long)base_b + j;
-    if (ga < 0 || gb < 0 || ga > 0x7fffffffll || gb > 0x7fffffffll) return DSSS_E_ARG;
-    if (ga < gb) { edge->a = (int32_t)ga; edge->b = (int32_t)gb; pose_between(&Xa, &Xb, &rel); }
-    else { edge->a = (int32_t)gb; edge->b = (int32_t)ga; pose_between(&Xb, &Xa, &rel); }
-    memcpy(edge->rel, rel.R, 9 * sizeof(double)); memcpy(edge->rel + 9, rel.t, 3 * sizeof(double));
-    const double sxy = E.sigma_xy_cells * cell;
-    edge->var[0] = edge->var[1] = edge->var[2] = E.sigma_rot * E.sigma_rot;
-    edge->var[3] = edge->var[4] = sxy * sxy; edge->var[5] = E.sigma_z * E.sigma_z;
-    return 1;
+    return edge_of(s, grid, rows_a, Na, base_a, rows_b, Nb, base_b, E, 0.0, 0.0, E.sigma_rot, edge);
 }
 
 int dsss_mosaic_register_edges(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, const dsss_mosaic_params* p,
                                const int* pair_a, const int* pair_b, const dsss_reg_seg* segs, int nsegs, const dsss_reg_edge_params* ep,
                                dsss_lc_edge* edges_host, int32_t* edge_seg_host, int cap, int* n_edges)
 {
-    if (!c) return DSSS_E_ARG;
-    if (dsss_comm_world(c) > 1) DSSS_FAIL(c, DSSS_E_STATE, "mosaic: registration runs on a single rank (communicator of %d)", dsss_comm_world(c));
-    size_t rows = 0;
-    int rc = mosaic_check_frames(c, ids, n, rpy6, ping_off, false, &rows); if (rc) return rc;
-    rc = mosaic_check_params(c, p); if (rc) return rc;
-    if (nsegs < 0 || cap < 0 || !n_edges) DSSS_FAIL(c, DSSS_E_ARG, "register: nsegs = %d, cap = %d%s", nsegs, cap, n_edges ? "" : ", nowhere to write the number of edges");
-    if (nsegs > 0 && (!pair_a || !pair_b || !segs)) DSSS_FAIL(c, DSSS_E_ARG, "register: %d segments without %s", nsegs, segs ? "their pairs" : "their rows");
-    std::vector<int> slot(c->max_frames, -1), base(n);
-    int run = 0;
-    for (int i = 0; i < n; ++i) { slot[ids[i]] = i; base[i] = ping_off ? ping_off[i] : run; run += c->frames[ids[i]].N; }
-    int ne = 0;
-    for (int k = 0; k < nsegs; ++k) {
-        if (segs[k].pair < 0) DSSS_FAIL(c, DSSS_E_ARG, "register: row %d names pair %d", k, segs[k].pair);
-        const int a = pair_a[segs[k].pair], b = pair_b[segs[k].pair];
-        if (a < 0 || a >= c->max_frames || slot[a] < 0 || b < 0 || b >= c->max_frames || slot[b] < 0)
-            DSSS_FAIL(c, DSSS_E_ARG, "register: row %d, pair (%d, %d) names a frame that is not listed", k, a, b);
-        const int ia = slot[a], ib = slot[b];
-        const dsss_frame& fa = c->frames[a]; const dsss_frame& fb = c->frames[b];
-        dsss_lc_edge e;
-        rc = dsss_register_edge(segs + k, p, rpy6 ? rpy6 + (size_t)ping_off[ia] * 6 : fa.h_geo, fa.N, base[ia],
-                                rpy6 ? rpy6 + (size_t)ping_off[ib] * 6 : fb.h_geo, fb.N, base[ib], ep, &e);
-        if (rc < 0) DSSS_FAIL(c, rc, "register: row %d (pair %d, segment %d, pings %d..%d) is not a valid segment result", k, segs[k].pair, segs[k].seg, segs[k].p0, segs[k].p1);
-        if (rc == 0) continue;
-        if (ne >= cap || !edges_host) DSSS_FAIL(c, DSSS_E_CAPACITY, "register: more than %d edges", edges_host ? cap : 0);
-        edges_host[ne] = e;
-        if (edge_seg_host) edge_seg_host[ne] = k;
-        ++ne;
-    }
-    *n_edges = ne;
+    return edges_loop(c, ids, n, rpy6, ping_off, p, pair_a, pair_b, segs != nullptr, nsegs, edges_host, edge_seg_host, cap, n_edges,
+                      [&](int k) -> const dsss_reg_seg& { return segs[k]; },
+                      [&](int k, const double* ra, int Na, int ba, const double* rb, int Nb, int bb, dsss_lc_edge* e) {
+                          return dsss_register_edge(segs + k, p, ra, Na, ba, rb, Nb, bb, ep, e); });
+}
+
+// ---- dense loop closures with a yaw fan
+void dsss_reg_yaw_params_default(dsss_reg_yaw_params* y) { if (y) { y->nyaw = 1; y->pad_ = 0; y->step = 0.01; } }
+
+int dsss_register_rotate_rows(const double* rows_b, int Nb, int p0, int p1, double theta, double* out)
+{
+    if (!rows_b || !out || p0 < 0 || p0 >= p1 || p1 > Nb || !std::isfinite(theta)) return DSSS_E_ARG;
+    rotate_rows(rows_b, p0, p1, theta, out);
     return DSSS_OK;
+}
+
+int dsss_register_yaw_peak(const dsss_reg_result* per_angle, int nyaw, double step, int32_t* k, int32_t* yaw_on_border, double* theta, double* theta_hat)
+{
+    if (!per_angle || !k || !yaw_on_border || !theta || !theta_hat || !fan_ok(nyaw, step)) return DSSS_E_ARG;
+    yaw_peak_of(per_angle, nyaw, step, k, yaw_on_border, theta, theta_hat);
+    return DSSS_OK;
+}
+
+// dsss_mosaic_register_segments under every angle of the fan.  Per frame that occurs as b: ONE memset, ONE mosaic_scatter_fan_kernel into
+// the accumulators of all its (segment, angle) windows and ONE mosaic_mean_kernel over that whole area; the windows of the rotated
+// segments come from the host's twin of the kernel's rotation (rotate_rows -> dsss_rotate_row).  The correlation runs in PASSES, one
+// per angle, each mosaic_corr_kernel with one job per (pair, segment) and one download of a table of ONE angle's size: the
+// page-locked landing area stays what the translation-only call needs instead of nyaw times that, and the peaks of a pass are
+// decided on the host while nothing else needs the host.  The centroid runs once, for the chosen angle of every row.
+int dsss_mosaic_register_segments_yaw(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, const dsss_mosaic_params* p,
+                                      const int* pair_a, const int* pair_b, int npairs, int seg_pings, const dsss_reg_params* rp,
+                                      const dsss_reg_yaw_params* yp, dsss_reg_seg_yaw* out_host, int cap, int* nseg_host, uint64_t* sums_host)
+{
+    if (!c) return DSSS_E_ARG;
+    size_t rows = 0;
+    dsss_reg_params R; std::vector<int> slot;
+    int rc = reg_check(c, ids, n, rpy6, ping_off, p, pair_a, pair_b, npairs, rp, out_host, &R, slot, &rows); if (rc) return rc;
+    if (seg_pings < 1) DSSS_FAIL(c, DSSS_E_ARG, "register: seg_pings = %d", seg_pings);
+    if (!nseg_host || cap < 0) DSSS_FAIL(c, DSSS_E_ARG, "register: %s", nseg_host ? "negative capacity" : "nowhere to write the number of segments");
+    dsss_reg_yaw_params Y; dsss_reg_yaw_params_default(&Y);
+    if (yp) Y = *yp;
+    if (!fan_ok(Y.nyaw, Y.step)) DSSS_FAIL(c, DSSS_E_ARG, "register: a fan of %d angles, %g rad apart (an odd number up to %d, a positive step)", Y.nyaw, Y.step, REG_MAX_YAW);
+    const int nyaw = Y.nyaw, mid = (nyaw - 1) / 2;
+    auto segs_of = [&](int i) { return (int)(((long long)c->frames[ids[i]].N + seg_pings - 1) / seg_pings); };
+    auto seg_end = [&](int s, int N) { return (int)std::min((long long)(s + 1) * seg_pings, (long long)N); };
+    long long total = 0;
+    for (int k = 0; k < npairs; ++k) {
+        const int ib = slot[pair_b[k]];
+        if ((long long)c->frames[ids[ib]].N * nyaw > 0x7fffffffll) DSSS_FAIL(c, DSSS_E_ARG, "register: frame %d has %d pings, too many for %d angles in one launch", ids[ib], c->frames[ids[ib]].N, nyaw);
+        total += segs_of(ib);
+    }
+    if (total > 0x7fffffffll) DSSS_FAIL(c, DSSS_E_ARG, "register: %lld segments", total);
+    *nseg_host = (int)total;                                                    // also when there is no room for them: the caller learns how many
+    if (total > cap) DSSS_FAIL(c, DSSS_E_CAPACITY, "register: %lld segments, room for %d", total, cap);
+    if (total == 0) return DSSS_OK;
+    const int nseg = (int)total;
+    std::vector<char> as_a(n, 0), as_b(n, 0);
+    for (int k = 0; k < npairs; ++k) { as_a[slot[pair_a[k]]] = 1; as_b[slot[pair_b[k]]] = 1; }
+    const int r = R.radius, S = 2 * r + 1, nshift = S * S;
+    // windows: the whole frame where it occurs as a, every (segment, angle) where it occurs as b
+    std::vector<mosaic_win> wins(n); std::vector<char> on_grid(n, 0); std::vector<size_t> lay_off(n, 0), fan_lay(n, 0), fan_cells(n, 0);
+    std::vector<size_t> fan0(n, 0);                                             // a frame's first entry in sw / hfan; (segment s, angle k) is entry s nyaw + k behind it
+    std::vector<mosaic_win> sw; std::vector<mosaic_fan> hfan;
+    std::vector<double> rot;
+    size_t win_cells = 1, lay_cells = 0;
+    for (int i = 0; i < n; ++i) {
+        const dsss_frame& f = c->frames[ids[i]];
+        const double* fr = rpy6 ? rpy6 + (size_t)ping_off[i] * 6 : f.h_geo;
+        if (as_a[i] && reg_window(f, fr, 0, f.N, p, &wins[i])) {
+            on_grid[i] = 1;
+            const size_t wc = (size_t)wins[i].bw * wins[i].bh;
+            win_cells = std::max(win_cells, wc);
+            lay_off[i] = lay_cells; lay_cells += (wc + 127) & ~(size_t)127;    // layers start on 256 bytes
+        }
+        if (!as_b[i]) continue;
+        fan0[i] = sw.size();
+        size_t cells = 0;
+        for (int s = 0; s < segs_of(i); ++s) {
+            const int p0 = s * seg_pings, p1 = seg_end(s, f.N);
+            const double* piv = fr + (size_t)(((long long)p0 + p1) / 2) * 6;
+            rot.resize((size_t)(p1 - p0) * 6);
+            for (int k = 0; k < nyaw; ++k) {
+                mosaic_win w{ p->x0, p->y0, p->cell, p->W, p->H, 0, 0, 0, 0, p->use_mask != 0 };  // bw = 0: not on the grid
+                mosaic_fan F; F.cx = piv[3]; F.cy = piv[4]; F.theta = fan_theta(k, nyaw, Y.step);
+                dsss_sincos(F.theta, &F.s, &F.c);
+                rotate_rows(fr, p0, p1, F.theta, rot.data());
+                reg_window(f, rot.data(), 0, p1 - p0, p, &w);
+                F.ox = w.ox; F.oy = w.oy; F.bw = w.bw; F.bh = w.bh; F.off = (unsigned long long)cells;
+                sw.push_back(w); hfan.push_back(F);
+                cells += ((size_t)w.bw * w.bh + 127) & ~(size_t)127;
+            }
+        }
+        fan_cells[i] = cells; win_cells = std::max(win_cells, cells);
+        fan_lay[i] = lay_cells; lay_cells += cells;
+    }
+    const size_t table = (size_t)nseg * nshift * 6;                             // one angle's sums
+    HIPCHK(c, hipSetDevice(c->device));
+    carve L;
+    const size_t o_lay = L.take(lay_cells * 2), o_win = L.take(win_cells * 8), o_jobs = L.take((size_t)n * sizeof(mosaic_job)),
+                 o_rows = L.take(rpy6 ? rows * 6 * sizeof(double) : 0), o_fan = L.take(hfan.size() * sizeof(mosaic_fan)),
+                 o_pairs = L.take((size_t)nseg * sizeof(reg_job)), o_cj = L.take((size_t)nseg * sizeof(cen_job)),
+                 o_cen = L.take((size_t)nseg * 3 * 8), o_tab = L.take((table + 1) * 8);      // the sums and, behind them, the sample-limit flag
+    rc = c->mosaic_buf.reserve(c, L.off); if (rc) return rc;
+    rc = c->mosaic_pinned.reserve(c, (table + 1) * 8); if (rc) return rc;
+    char* B = c->mosaic_buf.as<char>();
+    uint16_t* d_lay = reinterpret_cast<uint16_t*>(B + o_lay);
+    unsigned long long* d_win = reinterpret_cast<unsigned long long*>(B + o_win);
+    mosaic_job* d_jobs = reinterpret_cast<mosaic_job*>(B + o_jobs);
+    mosaic_fan* d_fan = reinterpret_cast<mosaic_fan*>(B + o_fan);
+    reg_job* d_pairs = reinterpret_cast<reg_job*>(B + o_pairs);
+    cen_job* d_cj = reinterpret_cast<cen_job*>(B + o_cj);
+    unsigned long long* d_cen = reinterpret_cast<unsigned long long*>(B + o_cen);
+    unsigned long long* d_tab = reinterpret_cast<unsigned long long*>(B + o_tab);
+    int* d_flag = reinterpret_cast<int*>(d_tab + table);
+    // the rows and every pass's jobs, laid out by pair and then by segment, before anything is launched: what one launch cannot take
+    // is refused here.  A row's centroid region lies inside the correlation region of its angle, so the largest of those bounds it.
+    memset(out_host, 0, (size_t)nseg * sizeof(dsss_reg_seg_yaw));
+    std::vector<std::vector<reg_job>> pj(nyaw);
+    std::vector<long long> blocks(nyaw, 0);
+    std::vector<int> row_a(nseg); std::vector<size_t> row_g(nseg);              // a row's frame a (index in ids) and its segment's first entry in sw / hfan
+    long long cen_bound = 0;
+    int row = 0;
+    for (int k = 0; k < npairs; ++k) {
+        const int ia = slot[pair_a[k]], ib = slot[pair_b[k]];
+        const int Nb = c->frames[ids[ib]].N;
+        for (int s = 0; s < segs_of(ib); ++s, ++row) {
+            dsss_reg_seg& o = out_host[row].s;
+            o.pair = k; o.seg = s; o.p0 = s * seg_pings; o.p1 = seg_end(s, Nb);
+            const size_t g = fan0[ib] + (size_t)s * nyaw;
+            row_a[row] = ia; row_g[row] = g;
+            if (!on_grid[ia]) continue;
+            long long most = 0;
+            for (int a = 0; a < nyaw; ++a) {
+                if (sw[g + a].bw == 0) continue;
+                const size_t before = pj[a].size();
+                if (!reg_push_job(pj[a], &blocks[a], d_lay + lay_off[ia], wins[ia], d_lay + fan_lay[ib] + hfan[g + a].off, sw[g + a], r, d_tab + (size_t)row * nshift * 6))
+                    DSSS_FAIL(c, DSSS_E_ARG, "register: %d segments are more than one launch takes", nseg);
+                if (pj[a].size() == before) continue;
+                const reg_job& J = pj[a].back();
+                most = std::max(most, (long long)((J.rx1 - J.rx0) / CEN_TW + 2) * ((J.ry1 - J.ry0) / CEN_TH + 2));
+            }
+            cen_bound += most;
+        }
+    }
+    if (cen_bound > 0x7fffffffll) DSSS_FAIL(c, DSSS_E_ARG, "register: %d segments are more than one launch takes", nseg);
+    std::vector<const double*> dev_rows;
+    rc = upload_rows(c, ids, n, rpy6, ping_off, reinterpret_cast<double*>(B + o_rows), dev_rows); if (rc) return rc;
+    std::vector<mosaic_job> jobs(n);
+    for (int i = 0; i < n; ++i) { const dsss_frame& f = c->frames[ids[i]]; jobs[i] = mosaic_job{ dev_rows[i], f.gr, f.lvl[0], f.mask, f.N, f.M, 0, 0 }; }
+    HIPCHK(c, hipMemcpyAsync(d_jobs, jobs.data(), (size_t)n * sizeof(mosaic_job), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_fan, hfan.data(), hfan.size() * sizeof(mosaic_fan), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_flag, 0, 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_cen, 0, (size_t)nseg * 3 * 8, c->stream));
+    // 1. mean layers: a frame's whole layer where it is an a, the layers of all its segments under all angles (one scatter, one pack) where it is a b
+    const mosaic_win grid{ p->x0, p->y0, p->cell, p->W, p->H, 0, 0, 0, 0, p->use_mask != 0 };
+    for (int i = 0; i < n; ++i) {
+        if (on_grid[i]) {
+            const size_t wc = (size_t)wins[i].bw * wins[i].bh;
+            HIPCHK(c, hipMemsetAsync(d_win, 0, wc * 8, c->stream));
+            launch_scatter(c, d_jobs + i, 1, jobs[i].N, wins[i], d_win);
+            hipLaunchKernelGGL(mosaic_mean_kernel, dim3((unsigned)((wc + 255) / 256)), dim3(256), 0, c->stream, d_win, wc, d_lay + lay_off[i], d_flag);
+            HIPCHK(c, hipGetLastError());
+        }
+        if (as_b[i] && fan_cells[i]) {
+            const size_t wc = fan_cells[i];
+            HIPCHK(c, hipMemsetAsync(d_win, 0, wc * 8, c->stream));
+            hipLaunchKernelGGL(mosaic_scatter_fan_kernel, dim3((unsigned)jobs[i].N * (unsigned)nyaw), dim3(256), 0, c->stream, d_jobs + i, grid, d_win,
+                               d_fan + fan0[i], seg_pings, nyaw);
+            hipLaunchKernelGGL(mosaic_mean_kernel, dim3((unsigned)((wc + 255) / 256)), dim3(256), 0, c->stream, d_win, wc, d_lay + fan_lay[i], d_flag);
+            HIPCHK(c, hipGetLastError());
+        }
+    }
+    // 2. one pass per angle: the table cleared, one correlation job per (pair, segment), one download, the records of the angle
+    const uint64_t* tab = c->mosaic_pinned.as<uint64_t>();
+    std::vector<dsss_reg_result> per((size_t)nseg * nyaw);
+    for (int a = 0; a < nyaw; ++a) {
+        HIPCHK(c, hipMemsetAsync(d_tab, 0, table * 8, c->stream));
+        rc = reg_launch_corr(c, pj[a], blocks[a], d_pairs, r); if (rc) return rc;
+        HIPCHK(c, hipMemcpyAsync(c->mosaic_pinned.p, d_tab, (table + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if ((int)tab[table]) DSSS_FAIL(c, DSSS_E_CAPACITY, "mosaic: a cell received more than 2^24 samples of one frame (cell %g too coarse)", p->cell);
+        for (row = 0; row < nseg; ++row) {
+            peak_of(tab + (size_t)row * nshift * 6, r, R.min_cells, p->cell, &per[(size_t)row * nyaw + a]);
+            if (sums_host) memcpy(sums_host + ((size_t)row * nyaw + a) * nshift * 6, tab + (size_t)row * nshift * 6, (size_t)nshift * 6 * 8);
+        }
+    }
+    // 3. the angle of every row on the host, then the centroid sums of the rows that have one under that angle: one launch, one download
+    std::vector<cen_job> cj;
+    long long cblocks = 0;
+    for (row = 0; row < nseg; ++row) {
+        dsss_reg_seg_yaw& o = out_host[row];
+        const dsss_reg_result* z = per.data() + (size_t)row * nyaw;
+        yaw_peak_of(z, nyaw, Y.step, &o.k, &o.yaw_on_border, &o.theta, &o.theta_hat);
+        o.s.r = z[o.k]; o.zncc_k0 = z[mid].zncc;
+        if (!(o.s.r.zncc > -2.0)) continue;                                     // no usable shift under any angle: sx = sy = 0
+        const size_t g = row_g[row] + o.k;
+        if (!cen_push_job(cj, &cblocks, d_lay + lay_off[row_a[row]], wins[row_a[row]], d_lay + fan_lay[slot[pair_b[o.s.pair]]] + hfan[g].off, sw[g], o.s.r,
+                          d_cen + (size_t)row * 3))
+            DSSS_FAIL(c, DSSS_E_NUMERIC, "register: internal error, the centroid of %d segments takes more workgroups than was bounded", nseg);
+    }
+    if (!cj.empty()) {
+        std::vector<uint64_t> cen((size_t)nseg * 3);
+        rc = reg_launch_centroids(c, cj, cblocks, d_cj, d_cen, cen); if (rc) return rc;
+        for (row = 0; row < nseg; ++row) {
+            dsss_reg_seg& o = out_host[row].s;
+            if (!(o.r.zncc > -2.0)) continue;
+            if ((int64_t)cen[(size_t)row * 3] != o.r.n)
+                DSSS_FAIL(c, DSSS_E_NUMERIC, "register: internal error, row %d has %lld cells at its peak and %lld in its centroid", row,
+                          (long long)o.r.n, (long long)cen[(size_t)row * 3]);
+            o.sx = (int64_t)cen[(size_t)row * 3 + 1]; o.sy = (int64_t)cen[(size_t)row * 3 + 2];
+        }
+    }
+    return DSSS_OK;
+}
+
+void dsss_reg_edge_yaw_params_default(dsss_reg_edge_yaw_params* e)
+{
+    if (e) { dsss_reg_edge_params_default(&e->e); dsss_reg_yaw_params_default(&e->fan); e->sigma_yaw_steps = 1.0; }
+}
+
+int dsss_register_edge_yaw(const dsss_reg_seg_yaw* s, const dsss_mosaic_params* grid, const double* rows_a, int Na, int base_a,
+                           const double* rows_b, int Nb, int base_b, const dsss_reg_edge_yaw_params* ep, dsss_lc_edge* edge)
+{
+    dsss_reg_edge_yaw_params E; dsss_reg_edge_yaw_params_default(&E);
+    if (ep) E = *ep;
+    if (!s || !fan_ok(E.fan.nyaw, E.fan.step) || !(E.sigma_yaw_steps > 0.0) || !std::isfinite(E.sigma_yaw_steps)) return DSSS_E_ARG;
+    const double s_yaw = E.fan.nyaw == 1 ? E.e.sigma_rot : E.sigma_yaw_steps * E.fan.step;
+    // the row's own acceptance comes first in edge_of; a fan row on the border of the fan is rejected after it was found valid
+    dsss_lc_edge e;
+    const int rc = edge_of(&s->s, grid, rows_a, Na, base_a, rows_b, Nb, base_b, E.e, s->theta, s->theta_hat, s_yaw, edge ? &e : nullptr);
+    if (rc != 1) return rc;
+    if (s->yaw_on_border != 0) return 0;
+    *edge = e;
+    return 1;
+}
+
+int dsss_mosaic_register_edges_yaw(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, const dsss_mosaic_params* p,
+                                   const int* pair_a, const int* pair_b, const dsss_reg_seg_yaw* segs, int nsegs, const dsss_reg_edge_yaw_params* ep,
+                                   dsss_lc_edge* edges_host, int32_t* edge_seg_host, int cap, int* n_edges)
+{
+    return edges_loop(c, ids, n, rpy6, ping_off, p, pair_a, pair_b, segs != nullptr, nsegs, edges_host, edge_seg_host, cap, n_edges,
+                      [&](int k) -> const dsss_reg_seg& { return segs[k].s; },
+                      [&](int k, const double* ra, int Na, int ba, const double* rb, int Nb, int bb, dsss_lc_edge* e) {
+                          return dsss_register_edge_yaw(segs + k, p, ra, Na, ba, rb, Nb, bb, ep, e); });
 }
 
 } // extern "C"

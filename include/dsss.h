@@ -437,6 +437,65 @@ int  dsss_mosaic_register_edges(dsss_ctx*, const int* ids, int n, const double* 
                                 const int* pair_a, const int* pair_b, const dsss_reg_seg* segs, int nsegs, const dsss_reg_edge_params*,
                                 dsss_lc_edge* edges_host, int32_t* edge_seg_host /* may be NULL */, int cap, int* n_edges);
 
+/* ---- dense loop closures with a yaw fan: the segments registered under a fan of small rotations as well, so that an edge measures
+ * the heading too.  Dead reckoning accumulates heading error, and a segment rendered under the wrong heading correlates badly at
+ * every shift; the closures above slide a segment in x and y only and say nothing about yaw (sigma_rot = 1 rad).
+ * Fan: nyaw angles, nyaw odd and in 1..17, theta_k = (k - mid) step with mid = (nyaw - 1) / 2, k = 0 .. nyaw - 1 (the integer k - mid
+ *   converted to f64, times step); step > 0 and finite, in radians.  Defaults: nyaw 1 (the registration above), step 0.01 rad -- a
+ *   value that has NOT been tuned on any data.
+ * Rotated rows: the pings [p0, p1) of rows_b turned by theta about the position of ping pm = (p0 + p1) / 2, (cx, cy) = (rows_b[pm][3],
+ *   rows_b[pm][4]).  (s, c) = the library's deterministic sin / cos of theta (Cody-Waite reduction, fdlibm polynomials, plain IEEE
+ *   multiplies and adds: the oracle's orc_sincos bit for bit).  Per ping, in f64, in exactly this order and unfused:
+ *   dx = x - cx, dy = y - cy, x' = cx + (c dx - s dy), y' = cy + (s dx + c dy), yaw' = yaw + theta; r, p and z are unchanged.
+ *   theta == 0 copies the rows unchanged (NOT cx + (x - cx)).
+ * Fan registration: for every (pair, segment, k) the segment layer is the one defined above, rendered under the segment's rows rotated
+ *   by theta_k; its table and its record are those defined above (dsss_mosaic_register_peak).
+ * Angle rule (dsss_register_yaw_peak): a record is usable iff its zncc > -2.  k* = the usable record with the largest zncc; ties go to
+ *   the smallest |k - mid|, then to the lowest k.  yaw_on_border = (nyaw > 1 and (k* == 0 or k* == nyaw - 1)).  theta = theta_{k*},
+ *   theta_hat = theta + q step with q = 0.5 (z- - z+) / (z- - 2 z0 + z+) (left to right in f64) on the peak znccs of k* - 1, k*, k* + 1;
+ *   q = 0 on the border, when a neighbour is not usable or when the denominator is not below 0.  No usable record: k* = mid,
+ *   yaw_on_border = 0, theta = theta_hat = 0.
+ * Row: s = the (pair, segment) row above with the record and the centroid sums of angle k*, k = k*, zncc_k0 = the peak zncc of the
+ *   unrotated angle (k = mid; -2 when it has no usable shift).  With nyaw == 1 every s equals dsss_mosaic_register_segments' row bit
+ *   for bit.  Order of rows as above.  sums_host (may be NULL): nseg x nyaw x (2 radius + 1)^2 x 6.
+ * Everything is an integer up to the scores.  A frame that is a b is rendered once per call for all its segments and angles.
+ * Errors: those of dsss_mosaic_register_segments, and DSSS_E_ARG for a fan outside the rules above (the fan may be NULL: the
+ * default) or for frames of more than 2^31 / nyaw pings.  Every argument and capacity error is decided before anything is launched. */
+typedef struct { int32_t nyaw; int32_t pad_; double step; } dsss_reg_yaw_params;      /* defaults 1, 0.01 rad (untuned) */
+typedef struct { dsss_reg_seg s;                      /* the row of angle k* */
+                 int32_t k, yaw_on_border;            /* k*; 1: the best angle is the first or the last of the fan, the true one may lie beyond */
+                 double theta, theta_hat, zncc_k0; } dsss_reg_seg_yaw;
+void dsss_reg_yaw_params_default(dsss_reg_yaw_params*);
+/* pure host arithmetic, no context: out = (p1 - p0) x 6.  DSSS_E_ARG: a NULL pointer, pings outside 0 <= p0 < p1 <= Nb, theta not finite */
+int  dsss_register_rotate_rows(const double* rows_b, int Nb, int p0, int p1, double theta, double* out);
+/* pure host arithmetic, no context: the angle rule on the nyaw records of one (pair, segment).  DSSS_E_ARG: a NULL pointer, a fan
+ * outside the rules above                                                                                                       */
+int  dsss_register_yaw_peak(const dsss_reg_result* per_angle, int nyaw, double step, int32_t* k, int32_t* yaw_on_border,
+                            double* theta, double* theta_hat);
+int  dsss_mosaic_register_segments_yaw(dsss_ctx*, const int* ids, int n, const double* rpy6, const int* ping_off, const dsss_mosaic_params*,
+                                       const int* pair_a, const int* pair_b, int npairs, int seg_pings, const dsss_reg_params*,
+                                       const dsss_reg_yaw_params*, dsss_reg_seg_yaw* out_host, int cap, int* nseg_host,
+                                       uint64_t* sums_host /* nseg x nyaw x (2r+1)^2 x 6, may be NULL */);
+/* From a fan row to a pose-graph edge that measures the heading: dsss_register_edge with these changes.
+ * Accepted iff dsss_register_edge accepts s AND yaw_on_border == 0.  Overlap centre c and anchor ping i of a: as above.
+ * Anchor ping j of the segment: the same rule on the rows [p0, p1) of b rotated by theta (theta_{k*}: the rows the chosen layer was
+ *   rendered under) and the point c + (off_x, off_y).
+ * Measurement: X_b' = the Rodrigues pose of row j of the rows rotated by theta_hat, its translation moved by (-off_x, -off_y, 0); the
+ *   direction rule is unchanged.
+ * Variance: (s_rot^2, s_rot^2, s_yaw^2, s_xy^2, s_xy^2, s_z^2) with s_yaw = sigma_yaw_steps step (default one step: the quantisation of
+ *   the search, as one cell is for x and y).  With fan.nyaw == 1, s_yaw = s_rot and the edge equals dsss_register_edge's bit for bit.
+ * fan = the fan the rows were registered with.  DSSS_E_ARG: what dsss_register_edge refuses, a fan outside the rules, sigma_yaw_steps
+ * not positive and finite, theta or theta_hat not finite.                                                                       */
+typedef struct { dsss_reg_edge_params e; dsss_reg_yaw_params fan; double sigma_yaw_steps; } dsss_reg_edge_yaw_params;   /* defaults: e's, the fan's, 1.0 */
+void dsss_reg_edge_yaw_params_default(dsss_reg_edge_yaw_params*);
+int  dsss_register_edge_yaw(const dsss_reg_seg_yaw* s, const dsss_mosaic_params* grid, const double* rows_a, int Na, int base_a,
+                            const double* rows_b, int Nb, int base_b, const dsss_reg_edge_yaw_params*, dsss_lc_edge* edge);
+/* dsss_register_edge_yaw on every row of segs, in order; it launches no GPU work.  Everything else as dsss_mosaic_register_edges. */
+int  dsss_mosaic_register_edges_yaw(dsss_ctx*, const int* ids, int n, const double* rpy6, const int* ping_off, const dsss_mosaic_params*,
+                                    const int* pair_a, const int* pair_b, const dsss_reg_seg_yaw* segs, int nsegs,
+                                    const dsss_reg_edge_yaw_params*, dsss_lc_edge* edges_host, int32_t* edge_seg_host /* may be NULL */,
+                                    int cap, int* n_edges);
+
 /* ------------------------------------------------------------------ instrumentation
  * accumulated GPU time (ms, HIP events on the context stream) and launch count per kernel family        */
 #define DSSS_K_ROW_REDUCE   0   /* row_reduce_kernel: one f64 read of the waterfall */

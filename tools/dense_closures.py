@@ -3,12 +3,17 @@
 solved trajectory (dsss_mosaic_register_segments), the accepted offsets become pose-graph edges (dsss_mosaic_register_edges), the
 trajectory is solved again with them next to the feature-based closures, and the segments are registered once more under the result.
     python tools/dense_closures.py --frames 200 --rows 2000 --cols 1024 --cell 0.1 [--seg-pings 80] [--radius 8] [--calls 5] [--timeout 1500]
+                                   [--yaw-fan NYAW [--yaw-step RAD]]
 Steps: 1. pipeline and dsss_posegraph_solve; 2. segments under the solved trajectory; 3. edges; 4. the edges of dsss_posegraph_select
 with the new ones behind them; 5. dsss_posegraph_solve_edges on the frames' dead-reckoning rows; 6. segments under the result.
 Prints one JSON line: segments and accepted edges; median and 95th percentile of |offset| in metres over the segments with a peak, the
 median ZNCC at zero shift and the consistency score, each before (solved trajectory) and after (solved again); the wall time of the
 segment call and of dsss_mosaic_register on the same pairs in the same process (the whole-frame form, the only existing code the new
 call's time can be set against), each the median of --calls synchronised calls after one warm-up.
+--yaw-fan NYAW (odd, above 1) registers every segment under a fan of NYAW rotations --yaw-step radians apart as well
+(dsss_mosaic_register_segments_yaw) and turns the rows into edges that measure the heading (dsss_mosaic_register_edges_yaw): the same
+report, with the median and 95th percentile of |theta_hat| over the segments with a peak and the rows on the border of the fan, before
+and after, and the wall time of the fan call next to the translation-only call's.
 The GPU work runs in a child process under a time limit (--timeout seconds); this process never opens the device."""
 import argparse
 import json
@@ -22,11 +27,14 @@ ap.add_argument("--frames", type=int, default=200); ap.add_argument("--rows", ty
 ap.add_argument("--cols", type=int, default=1024); ap.add_argument("--cell", type=float, default=0.1)
 ap.add_argument("--seg-pings", type=int, default=80)
 ap.add_argument("--radius", type=int, default=8); ap.add_argument("--min-cells", type=int, default=256)
+ap.add_argument("--yaw-fan", type=int, default=1); ap.add_argument("--yaw-step", type=float, default=0.01)
 ap.add_argument("--calls", type=int, default=5); ap.add_argument("--timeout", type=float, default=1500.0)
 ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)
 a = ap.parse_args()
 if a.calls < 5:
     sys.exit("--calls must be at least 5")
+if a.yaw_fan < 1 or a.yaw_fan > 17 or a.yaw_fan % 2 == 0 or not a.yaw_step > 0:
+    sys.exit("--yaw-fan must be odd and in 1..17, --yaw-step positive")
 
 if not a.worker:
     try:
@@ -69,7 +77,29 @@ def timed(fn):
     return round(1e3 * float(np.median(ts)), 3), round(1e3 * float(min(ts)), 3)
 
 
+FAN = a.yaw_fan > 1
+yaw = capi.RegYawParams(a.yaw_fan, 0, a.yaw_step)
+
+
+def register(traj):
+    if FAN:
+        return ctx.mosaic_register_segments_yaw(ids, p, pairs, a.seg_pings, yaw=yaw, reg=reg, rpy6=traj, ping_off=off)
+    return ctx.mosaic_register_segments(ids, p, pairs, a.seg_pings, reg=reg, rpy6=traj, ping_off=off)
+
+
 def describe(segs, traj):
+    fan = {}
+    if FAN:
+        ok = segs["s"]["r"]["zncc"] > -2.0
+        t = np.abs(segs["theta_hat"][ok])
+        fan = dict(theta_hat_median_rad=float(np.median(t)) if ok.any() else None, theta_hat_p95_rad=float(np.percentile(t, 95)) if ok.any() else None,
+                   on_yaw_border=int((segs["yaw_on_border"][ok] != 0).sum()), zncc_median=float(np.median(segs["s"]["r"]["zncc"][ok])) if ok.any() else None,
+                   zncc_unrotated_median=float(np.median(segs["zncc_k0"][segs["zncc_k0"] > -2.0])) if (segs["zncc_k0"] > -2.0).any() else None)
+        segs = segs["s"]
+    return dict(_describe(segs, traj), **fan)
+
+
+def _describe(segs, traj):
     r = segs["r"]
     ok = r["zncc"] > -2.0
     d = np.hypot(r["off_x"][ok], r["off_y"][ok])
@@ -88,15 +118,22 @@ def rows_of(poses12):
 
 res["segments_ms"], res["segments_ms_min"] = timed(lambda: ctx.mosaic_register_segments(ids, p, pairs, a.seg_pings, reg=reg, rpy6=rpy, ping_off=off))
 res["whole_frame_ms"], res["whole_frame_ms_min"] = timed(lambda: ctx.mosaic_register(ids, p, pairs, reg=reg, rpy6=rpy, ping_off=off))
-before = ctx.mosaic_register_segments(ids, p, pairs, a.seg_pings, reg=reg, rpy6=rpy, ping_off=off)      # 2
-new, src = ctx.mosaic_register_edges(ids, p, pairs, before, rpy6=rpy, ping_off=off)                      # 3
+if FAN:
+    res["yaw_fan"], res["yaw_step"] = a.yaw_fan, a.yaw_step
+    res["segments_yaw_ms"], res["segments_yaw_ms_min"] = timed(lambda: register(rpy))
+before = register(rpy)                                                                                   # 2
+if FAN:                                                                                                  # 3
+    new, src = ctx.mosaic_register_edges_yaw(ids, p, pairs, before, edge_params=capi.RegEdgeYawParams(capi.reg_edge_params_default(), yaw, 1.0),
+                                             rpy6=rpy, ping_off=off)
+else:
+    new, src = ctx.mosaic_register_edges(ids, p, pairs, before, rpy6=rpy, ping_off=off)
 old = ctx.posegraph_select(F)                                                                            # 4
 dr = np.ascontiguousarray(np.concatenate([i[0] for i in ins]))
 t0 = time.perf_counter()
 poses, stats2 = ctx.posegraph_solve_edges(dr, np.concatenate([old, new]))                                # 5
 solve_ms = 1e3 * (time.perf_counter() - t0)
 again = rows_of(poses)
-after = ctx.mosaic_register_segments(ids, p, pairs, a.seg_pings, reg=reg, rpy6=again, ping_off=off)      # 6
+after = register(again)                                                                                 # 6
 true = np.ascontiguousarray(np.concatenate(sv.poses_true))
 res.update(segments=len(before), feature_edges=len(old), accepted_edges=len(new), lm_iterations_again=int(stats2[0]), solve_again_ms=round(solve_ms, 3),
            before=describe(before, rpy), after=describe(after, again),
