@@ -104,6 +104,22 @@ class RegEdgeYawParams(C.Structure):
     _fields_ = [("e", RegEdgeParams), ("fan", RegYawParams), ("sigma_yaw_steps", C.c_double)]
 
 
+class RegPyrParams(C.Structure):
+    """dsss_reg_pyr_params: the cell pyramid a segment is registered over: levels (1..4; 1 = the flat registration), and the radius in
+    cells of the refinement below the top level (1..16)"""
+    _fields_ = [("levels", C.c_int32), ("refine", C.c_int32)]
+
+
+class RegSegPyr(C.Structure):
+    """dsss_reg_seg_pyr: s = the RegSeg of the finest level with a usable peak (on_border = 1 unless the row finished at level 0 away from
+    every border), level = that level (-1: none), border_mask = bit l set when level l's peak lay on the border of its square,
+    lx, ly, lz = the total shift in cells of level l and the peak ZNCC per level (0, 0, -2: not reached)"""
+    _fields_ = [("s", RegSeg), ("level", C.c_int32), ("border_mask", C.c_int32), ("lx", C.c_int32 * 4), ("ly", C.c_int32 * 4), ("lz", C.c_double * 4)]
+
+
+REGSEGPYR_DTYPE = np.dtype(RegSegPyr)    # the rows Context.mosaic_register_segments_pyr returns (field "s" is a REGSEG_DTYPE record)
+
+
 class PGGateParams(C.Structure):
     """dsss_pg_gate_params: chi-square gate, the factor between the worst kept edge and the threshold of a round, solves at most"""
     _fields_ = [("gate", C.c_double), ("decade", C.c_double), ("max_solves", C.c_int32), ("pad_", C.c_int32)]
@@ -275,6 +291,15 @@ def lib():
         L.dsss_mosaic_register_edges_yaw.restype = C.c_int
         L.dsss_mosaic_register_edges_yaw.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(MosaicParams), C.c_void_p, C.c_void_p,
                                                      C.c_void_p, C.c_int, C.POINTER(RegEdgeYawParams), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        L.dsss_reg_pyr_params_default.restype = None
+        L.dsss_reg_pyr_params_default.argtypes = [C.POINTER(RegPyrParams)]
+        L.dsss_register_pyr_step.restype = C.c_int
+        L.dsss_register_pyr_step.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.POINTER(RegResult),
+                                             C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.dsss_mosaic_register_segments_pyr.restype = C.c_int
+        L.dsss_mosaic_register_segments_pyr.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(MosaicParams), C.c_void_p,
+                                                        C.c_void_p, C.c_int, C.c_int, C.POINTER(RegParams), C.POINTER(RegPyrParams), C.c_void_p, C.c_int,
+                                                        C.POINTER(C.c_int), C.c_void_p]
         _LIB = L
     return _LIB
 
@@ -418,6 +443,28 @@ def register_edge_yaw(seg, grid, rows_a, base_a, rows_b, base_b, params=None):
     if rc < 0:
         raise _host_error(L, "dsss_register_edge_yaw", rc)
     return edge[0] if rc == 1 else None
+
+
+def reg_pyr_params_default():
+    q = RegPyrParams(); lib().dsss_reg_pyr_params_default(C.byref(q)); return q
+
+
+def register_pyr_step(sums, radius, min_cells, cell, level, cx, cy):
+    """dsss_register_pyr_step: the level rule of the cell pyramid on one table of shift sums ((2 radius + 1)^2 x 6 uint64) of level
+    `level` around the centre (cx, cy); min_cells and cell are the level-0 values -> (RegResult with the centre added, usable, next):
+    next = the centre (2 tx, 2 ty) of the level below, None at level 0 or without a usable shift.  Host arithmetic, no context."""
+    L = lib()
+    out = RegResult()
+    if sums is not None:
+        sums = np.ascontiguousarray(sums, np.uint64)
+        if 0 <= int(radius) <= 16 and sums.size != (2 * int(radius) + 1) ** 2 * 6:
+            raise ValueError("register_pyr_step: %d sums for radius %d" % (sums.size, radius))
+    usable = C.c_int32(0); nx = C.c_int32(0); ny = C.c_int32(0)
+    rc = L.dsss_register_pyr_step(_ptr(sums), int(radius), int(min_cells), C.c_double(cell), int(level), int(cx), int(cy), C.byref(out),
+                                  C.byref(usable), C.byref(nx), C.byref(ny))
+    if rc != 0:
+        raise _host_error(L, "dsss_register_pyr_step", rc)
+    return out, usable.value, ((nx.value, ny.value) if usable.value and int(level) > 0 else None)
 
 
 class Context:
@@ -947,6 +994,34 @@ class Context:
                                                         _ptr(segs), len(segs), C.byref(edge_params) if edge_params is not None else None,
                                                         _ptr(edges), _ptr(src), cap, C.byref(ne)), "dsss_mosaic_register_edges_yaw")
         return edges[:ne.value].copy(), src[:ne.value].copy()
+
+    def mosaic_register_segments_pyr(self, ids, params, pairs, seg_pings, pyr=None, reg=None, rpy6=None, ping_off=None, want_sums=False, cap=None):
+        """mosaic_register_segments coarse to fine over the cell pyramid `pyr` (a RegPyrParams, None = the default of one level): the top
+        level searches reg.radius of its cells, every level below pyr.refine cells around twice the shift found above -> rows of
+        REGSEGPYR_DTYPE: s = the row of the finest level with a usable peak (accepted by mosaic_register_edges only when it finished at
+        level 0 away from every border), level, border_mask and the shift and ZNCC per level.  want_sums=True returns (rows, sums)
+        with sums[nseg, (2 r + 1)^2 + (levels - 1) (2 refine + 1)^2, 6] uint64: the top level's table, then those of the levels below."""
+        ids, rpy6, ping_off = self._mosaic_traj(ids, rpy6, ping_off)
+        pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        pa = np.ascontiguousarray(pairs[:, 0]); pb = np.ascontiguousarray(pairs[:, 1])
+        r = reg if reg is not None else reg_params_default()
+        q = pyr if pyr is not None else reg_pyr_params_default()
+        S = 2 * max(0, min(int(r.radius), 16)) + 1
+        lv = max(1, min(int(q.levels), 4)); Sr = 2 * max(0, min(int(q.refine), 16)) + 1
+        args = (self.h, _ptr(ids), len(ids), _ptr(rpy6), _ptr(ping_off), C.byref(params), _ptr(pa), _ptr(pb), len(pairs), int(seg_pings), C.byref(r),
+                C.byref(q))
+        nseg = C.c_int(0)
+        if cap is None:                                    # the library counts the rows before it launches anything: ask with no room
+            one = np.zeros(1, REGSEGPYR_DTYPE)
+            rc = self.L.dsss_mosaic_register_segments_pyr(*args, _ptr(one), 0, C.byref(nseg), None)
+            if rc != -5:                                   # DSSS_E_CAPACITY: nseg rows are needed; 0: there are none; anything else is an error
+                self._chk(rc, "dsss_mosaic_register_segments_pyr")
+            cap = nseg.value
+        out = np.zeros(max(cap, 1), REGSEGPYR_DTYPE)
+        sums = np.zeros((max(cap, 1), S * S + (lv - 1) * Sr * Sr, 6), np.uint64) if want_sums else None
+        self._chk(self.L.dsss_mosaic_register_segments_pyr(*args, _ptr(out), int(cap), C.byref(nseg), _ptr(sums)), "dsss_mosaic_register_segments_pyr")
+        out = out[:nseg.value]
+        return (out, sums[:nseg.value]) if want_sums else out
 
     # ---- instrumentation
     def profile(self, on=True):

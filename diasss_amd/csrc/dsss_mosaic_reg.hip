@@ -10,6 +10,9 @@
 // With a yaw fan ("dense loop closures with a yaw fan"): every segment rendered under a fan of small rotations as well
 // (mosaic_scatter_fan_kernel: one scatter per frame for all its segments and angles), the correlation once per angle, the angle rule
 // on the host (dsss_register_yaw_peak) and an edge that measures the heading too (dsss_register_edge_yaw).
+// Over a cell pyramid ("dense loop closures over a cell pyramid"): the segments registered coarse to fine (dsss_mosaic_register_segments_pyr:
+// mosaic_pyr_kernel writes the pooled layers of all levels in one pass over a frame's accumulators, the correlation runs once per level
+// around each row's centre, the level rule is host arithmetic in one place, dsss_register_pyr_step).
 #include "dsss_mosaic_int.h"
 #include "dsss_pose.h"
 #include "dsss_wave.h"
@@ -45,6 +48,90 @@ __global__ __launch_bounds__(256) void mosaic_mean_kernel(const unsigned long lo
     const uint32_t c = (uint32_t)(a >> 32), s = (uint32_t)a;
     if (c > MOSAIC_MAX_SAMPLES) *flag = 1;
     lay[i] = c ? (uint16_t)(0x100u | ((s + c / 2) / c)) : (uint16_t)0;
+}
+
+// ---- the pyramid of mean layers ("dense loop closures over a cell pyramid" in the header)
+#define PYR_MAX_LEVELS 4
+#define PYR_TW 64                          // a workgroup of mosaic_pyr_kernel owns 64 x 32 fine cells, aligned to 8 = 2^(PYR_MAX_LEVELS - 1) in grid coordinates
+#define PYR_TH 32
+#define PYR_ROWS 8                         // fine cells one below the other per thread: the vertical partners of every level are its own registers
+
+// one area of a frame (its whole window where it is an a, one segment's window where it is a b): where its accumulators start behind
+// the frame's first, its window in fine grid cells, where the u16 layer of each level starts, tiles and blk0 = its first workgroup.
+// The window of level l is what the fine window covers: ox_l = ox >> l, bw_l = ((ox + bw - 1) >> l) - ox_l + 1, the same in y.
+struct pyr_job {
+    unsigned long long acc; unsigned long long lay[PYR_MAX_LEVELS];
+    int ox, oy, bw, bh, bx0, by0, tiles_x, blk0;                               // (bx0, by0) = (ox, oy) rounded down to a multiple of 8
+};
+
+// one level's cells of a thread: NV values one below the other, pooled over 2^l x 2^l fine cells and equal in the 2^l lanes of a group;
+// the first lane of a group writes validity << 8 | m.  (X0, Y0) = the level's cell of the thread's first value, in grid coordinates.
+template <int NV> __device__ __forceinline__ void pyr_store(const unsigned long long (&c)[NV], const unsigned long long (&s)[NV], const pyr_job& J, int l,
+                                                            int X0, int Y0, bool first, uint16_t* __restrict__ lay)
+{
+    const int oxl = J.ox >> l, oyl = J.oy >> l, bwl = ((J.ox + J.bw - 1) >> l) - oxl + 1, bhl = ((J.oy + J.bh - 1) >> l) - oyl + 1;
+    const int x = X0 - oxl;
+    if (!first || x < 0 || x >= bwl) return;
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+        const int y = Y0 + j - oyl;
+        if (y < 0 || y >= bhl) continue;
+        lay[J.lay[l] + (size_t)y * bwl + x] = c[j] ? (uint16_t)(0x100u | (unsigned)((s[j] + c[j] / 2) / c[j])) : (uint16_t)0;
+    }
+}
+
+// the next level from 2 NV values per thread: the vertical partner is the thread's next value, the horizontal one the lane 2^l away
+template <int NV> __device__ __forceinline__ void pyr_down(const unsigned long long (&ci)[2 * NV], const unsigned long long (&si)[2 * NV],
+                                                           unsigned long long (&co)[NV], unsigned long long (&so)[NV], int partner)
+{
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+        unsigned long long c = ci[2 * j] + ci[2 * j + 1], s = si[2 * j] + si[2 * j + 1];
+        c += __shfl_xor(c, partner, 64); s += __shfl_xor(s, partner, 64);
+        co[j] = c; so[j] = s;
+    }
+}
+
+// 64-bit accumulators (count high, sum low) of the areas of one frame -> the u16 layers of all `levels` levels in one pass: every
+// accumulator is read once (a wavefront reads 64 neighbouring ones of a row), level 0 is mosaic_mean_kernel's value and flag bit for
+// bit, and the pooled counts and sums of the levels above are added up in 64 bits in registers (down a thread's eight rows) and by lane
+// exchange (across 2, 4, 8 lanes).  Pooling is by grid coordinates: a tile starts on a multiple of 8 whatever the window's origin,
+// and cells outside the window read as empty.
+__global__ __launch_bounds__(256) void mosaic_pyr_kernel(const pyr_job* __restrict__ jobs, int njobs, int levels, const unsigned long long* __restrict__ acc,
+                                                         uint16_t* __restrict__ lay, int* __restrict__ flag)
+{
+    int lo = 0, hi = njobs - 1;
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (jobs[mid].blk0 <= (int)blockIdx.x) lo = mid; else hi = mid - 1; }
+    const pyr_job J = jobs[lo];
+    const int wg = (int)blockIdx.x - J.blk0;
+    const int ty = wg / J.tiles_x, tx = wg - ty * J.tiles_x;
+    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+    const int gx = J.bx0 + tx * PYR_TW + lane, gy0 = J.by0 + ty * PYR_TH + wave * PYR_ROWS;            // gy0 is a multiple of 8
+    const int x = gx - J.ox;
+    const unsigned long long* __restrict__ win = acc + J.acc;
+    unsigned long long c0[PYR_ROWS], s0[PYR_ROWS];
+    bool over = false;
+#pragma unroll
+    for (int k = 0; k < PYR_ROWS; ++k) {
+        const int y = gy0 + k - J.oy;
+        unsigned long long a = 0;
+        if (x >= 0 && x < J.bw && y >= 0 && y < J.bh) a = win[(size_t)y * J.bw + x];
+        const uint32_t c = (uint32_t)(a >> 32), s = (uint32_t)a;
+        over |= c > MOSAIC_MAX_SAMPLES;
+        c0[k] = c; s0[k] = s;
+        if (x >= 0 && x < J.bw && y >= 0 && y < J.bh) lay[J.lay[0] + (size_t)y * J.bw + x] = c ? (uint16_t)(0x100u | ((s + c / 2) / c)) : (uint16_t)0;
+    }
+    if (over) *flag = 1;
+    if (levels < 2) return;                                                    // (uniform: no lane leaves before the exchanges it takes part in)
+    unsigned long long c1[4], s1[4], c2[2], s2[2], c3[1], s3[1];
+    pyr_down<4>(c0, s0, c1, s1, 1);
+    pyr_store<4>(c1, s1, J, 1, gx >> 1, gy0 >> 1, (lane & 1) == 0, lay);
+    if (levels < 3) return;
+    pyr_down<2>(c1, s1, c2, s2, 2);
+    pyr_store<2>(c2, s2, J, 2, gx >> 2, gy0 >> 2, (lane & 3) == 0, lay);
+    if (levels < 4) return;
+    pyr_down<1>(c2, s2, c3, s3, 4);
+    pyr_store<1>(c3, s3, J, 3, gx >> 3, gy0 >> 3, (lane & 7) == 0, lay);
 }
 
 // One workgroup per strip of REG_STRIP tiles of a's cells.  Per tile the a cells and the halo of b go into LDS as u16 (cells outside a
@@ -471,6 +558,36 @@ int edges_loop(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int
     }
     *n_edges = ne;
     return DSSS_OK;
+}
+
+// ---- the cell pyramid
+#define PYR_MAX_CENTRE (1 << 28)           // |cx|, |cy| of a level's centre: twice the centre plus the radius stays an int32
+
+bool pyr_ok(const dsss_reg_pyr_params& P) { return P.levels >= 1 && P.levels <= PYR_MAX_LEVELS && (P.levels == 1 || (P.refine >= 1 && P.refine <= REG_MAX_RADIUS)); }
+
+// the level rule of the header, "dense loop closures over a cell pyramid": the one place it is written.  sums = the table of level
+// `level` around the centre (cx, cy); min_cells and cell are the level-0 values.
+void pyr_step_of(const uint64_t* sums, int radius, int min_cells, double cell, int level, int cx, int cy, dsss_reg_result* out, int32_t* usable,
+                 int32_t* ncx, int32_t* ncy)
+{
+    const double cell_l = ldexp(cell, level);
+    peak_of(sums, radius, std::max(1, min_cells >> (2 * level)), cell_l, out);
+    *usable = out->zncc > -2.0 ? 1 : 0;
+    if (!*usable) return;                                                       // the no-usable-shift record as it is: no centre is added to it
+    out->dx += cx; out->dy += cy;
+    const double mx = (double)cx * cell_l, my = (double)cy * cell_l;            // one multiply and one add each, unfused (-ffp-contract=off)
+    out->off_x = out->off_x + mx; out->off_y = out->off_y + my;
+    if (level > 0) { *ncx = 2 * out->dx; *ncy = 2 * out->dy; }
+}
+
+// the window of level l that the fine window w covers (only ox, oy, bw, bh differ), moved by (-cx, -cy)
+mosaic_win pyr_window(const mosaic_win& w, int l, int cx, int cy)
+{
+    mosaic_win q = w;
+    q.ox = w.ox >> l; q.oy = w.oy >> l;
+    q.bw = ((w.ox + w.bw - 1) >> l) - q.ox + 1; q.bh = ((w.oy + w.bh - 1) >> l) - q.oy + 1;
+    q.ox -= cx; q.oy -= cy;
+    return q;
 }
 
 } // namespace
@@ -966,6 +1083,227 @@ int dsss_mosaic_register_edges_yaw(dsss_ctx* c, const int* ids, int n, const dou
                       [&](int k) -> const dsss_reg_seg& { return segs[k].s; },
                       [&](int k, const double* ra, int Na, int ba, const double* rb, int Nb, int bb, dsss_lc_edge* e) {
                           return dsss_register_edge_yaw(segs + k, p, ra, Na, ba, rb, Nb, bb, ep, e); });
+}
+
+// ---- dense loop closures over a cell pyramid
+void dsss_reg_pyr_params_default(dsss_reg_pyr_params* q) { if (q) { q->levels = 1; q->refine = 3; } }
+
+int dsss_register_pyr_step(const uint64_t* sums, int radius, int min_cells, double cell, int level, int cx, int cy,
+                           dsss_reg_result* out, int32_t* usable, int32_t* ncx, int32_t* ncy)
+{
+    if (!sums || !out || !usable || !ncx || !ncy || radius < 0 || radius > REG_MAX_RADIUS || min_cells < 1 || !(cell > 0.0) || !std::isfinite(cell) ||
+        level < 0 || level >= PYR_MAX_LEVELS || cx < -PYR_MAX_CENTRE || cx > PYR_MAX_CENTRE || cy < -PYR_MAX_CENTRE || cy > PYR_MAX_CENTRE) return DSSS_E_ARG;
+    pyr_step_of(sums, radius, min_cells, cell, level, cx, cy, out, usable, ncx, ncy);
+    return DSSS_OK;
+}
+
+// dsss_mosaic_register_segments coarse to fine.  Per frame: ONE memset, the unchanged scatter kernels into the accumulators of its whole
+// window (where it is an a) and of all its segments (where it is a b), and ONE mosaic_pyr_kernel over all those areas that writes
+// the layers of every level; the layers of all levels stay resident.  Per level, from the top: mosaic_corr_kernel with one job per row
+// that is still alive (the segment's window moved by minus the row's centre), one download of that level's tables, the level rule on
+// the host (pyr_step_of).  mosaic_centroid_kernel runs once, at the total shift, for the rows that finished at level 0.  What one
+// launch cannot take is bounded and refused before anything is launched.
+int dsss_mosaic_register_segments_pyr(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, const dsss_mosaic_params* p,
+                                      const int* pair_a, const int* pair_b, int npairs, int seg_pings, const dsss_reg_params* rp,
+                                      const dsss_reg_pyr_params* pp, dsss_reg_seg_pyr* out_host, int cap, int* nseg_host, uint64_t* sums_host)
+{
+    if (!c) return DSSS_E_ARG;
+    size_t rows = 0;
+    dsss_reg_params R; std::vector<int> slot;
+    int rc = reg_check(c, ids, n, rpy6, ping_off, p, pair_a, pair_b, npairs, rp, out_host, &R, slot, &rows); if (rc) return rc;
+    if (seg_pings < 1) DSSS_FAIL(c, DSSS_E_ARG, "register: seg_pings = %d", seg_pings);
+    if (!nseg_host || cap < 0) DSSS_FAIL(c, DSSS_E_ARG, "register: %s", nseg_host ? "negative capacity" : "nowhere to write the number of segments");
+    dsss_reg_pyr_params P; dsss_reg_pyr_params_default(&P);
+    if (pp) P = *pp;
+    if (!pyr_ok(P)) DSSS_FAIL(c, DSSS_E_ARG, "register: a pyramid of %d levels refined within %d cells (1..%d levels, 1..%d cells)", P.levels, P.refine, PYR_MAX_LEVELS, REG_MAX_RADIUS);
+    const int L = P.levels;
+    auto segs_of = [&](int i) { return (int)(((long long)c->frames[ids[i]].N + seg_pings - 1) / seg_pings); };
+    auto seg_end = [&](int s, int N) { return (int)std::min((long long)(s + 1) * seg_pings, (long long)N); };
+    long long total = 0;
+    for (int k = 0; k < npairs; ++k) total += segs_of(slot[pair_b[k]]);
+    if (total > 0x7fffffffll) DSSS_FAIL(c, DSSS_E_ARG, "register: %lld segments", total);
+    *nseg_host = (int)total;                                                    // also when there is no room for them: the caller learns how many
+    if (total > cap) DSSS_FAIL(c, DSSS_E_CAPACITY, "register: %lld segments, room for %d", total, cap);
+    if (total == 0) return DSSS_OK;
+    const int nseg = (int)total;
+    std::vector<char> as_a(n, 0), as_b(n, 0);
+    for (int k = 0; k < npairs; ++k) { as_a[slot[pair_a[k]]] = 1; as_b[slot[pair_b[k]]] = 1; }
+    auto radius_of = [&](int l) { return l == L - 1 ? R.radius : P.refine; };
+    auto nshift_of = [&](int l) { const int S = 2 * radius_of(l) + 1; return (size_t)S * S; };
+    // areas: the whole frame where it occurs as a, every segment where it occurs as b; an area's accumulators lie behind the frame's
+    // first, its layers of all levels in d_lay
+    struct area_lay { size_t off[PYR_MAX_LEVELS]; };
+    std::vector<mosaic_win> wins(n); std::vector<char> on_grid(n, 0); std::vector<area_lay> a_lay(n);
+    std::vector<int> seg0(n, 0), job0(n, 0), njobs(n, 0);                       // a frame's first segment in sw / hseg, its areas in hpj
+    std::vector<size_t> a_cells(n, 0), acc_cells(n, 0); std::vector<long long> pyr_blocks(n, 0);
+    std::vector<mosaic_win> sw; std::vector<mosaic_seg> hseg; std::vector<area_lay> seg_lay; std::vector<pyr_job> hpj;
+    size_t win_cells = 1, lay_cells = 0;
+    auto add_area = [&](int i, const mosaic_win& w, size_t acc, area_lay* lay) {
+        pyr_job J;
+        J.acc = (unsigned long long)acc; J.ox = w.ox; J.oy = w.oy; J.bw = w.bw; J.bh = w.bh; J.bx0 = w.ox & ~7; J.by0 = w.oy & ~7;
+        for (int l = 0; l < PYR_MAX_LEVELS; ++l) {
+            lay->off[l] = J.lay[l] = lay_cells;
+            if (l >= L) continue;
+            const mosaic_win q = pyr_window(w, l, 0, 0);
+            lay_cells += ((size_t)q.bw * q.bh + 127) & ~(size_t)127;            // layers start on 256 bytes
+        }
+        J.tiles_x = (w.ox + w.bw - 1 - J.bx0) / PYR_TW + 1; J.blk0 = (int)pyr_blocks[i];
+        pyr_blocks[i] += (long long)J.tiles_x * ((w.oy + w.bh - 1 - J.by0) / PYR_TH + 1);
+        if (pyr_blocks[i] <= 0x7fffffffll) { hpj.push_back(J); ++njobs[i]; }   // (more is refused below, before anything is launched)
+    };
+    for (int i = 0; i < n; ++i) {
+        const dsss_frame& f = c->frames[ids[i]];
+        const double* fr = rpy6 ? rpy6 + (size_t)ping_off[i] * 6 : f.h_geo;
+        job0[i] = (int)hpj.size();
+        if (as_a[i] && reg_window(f, fr, 0, f.N, p, &wins[i])) {
+            on_grid[i] = 1;
+            add_area(i, wins[i], 0, &a_lay[i]);
+            a_cells[i] = ((size_t)wins[i].bw * wins[i].bh + 127) & ~(size_t)127;
+        }
+        size_t cells = 0;
+        if (as_b[i]) {
+            seg0[i] = (int)sw.size();
+            for (int s = 0; s < segs_of(i); ++s) {
+                mosaic_win w{ p->x0, p->y0, p->cell, p->W, p->H, 0, 0, 0, 0, p->use_mask != 0 };  // bw = 0: not on the grid
+                area_lay al{};
+                if (reg_window(f, fr, s * seg_pings, seg_end(s, f.N), p, &w)) add_area(i, w, a_cells[i] + cells, &al);
+                sw.push_back(w); seg_lay.push_back(al); hseg.push_back(mosaic_seg{ w.ox, w.oy, w.bw, w.bh, (unsigned long long)cells });
+                cells += ((size_t)w.bw * w.bh + 127) & ~(size_t)127;
+            }
+        }
+        acc_cells[i] = a_cells[i] + cells; win_cells = std::max(win_cells, acc_cells[i]);
+        if (pyr_blocks[i] > 0x7fffffffll) DSSS_FAIL(c, DSSS_E_ARG, "register: the areas of frame %d are more than one launch takes", ids[i]);
+    }
+    // the rows, by pair and then by segment, and what the launches of every level and of the centroid can need at most: a level's
+    // region lies inside the segment's window of that level dilated by the radius, the centroid's inside the segment's fine window
+    memset(out_host, 0, (size_t)nseg * sizeof(dsss_reg_seg_pyr));
+    std::vector<int> row_a(nseg), row_b(nseg), row_g(nseg);                     // a row's frames (index in ids) and its segment in sw / hseg
+    {
+        long long bound[PYR_MAX_LEVELS] = { 0, 0, 0, 0 }, cen_bound = 0;
+        int row = 0;
+        for (int k = 0; k < npairs; ++k) {
+            const int ia = slot[pair_a[k]], ib = slot[pair_b[k]];
+            const int Nb = c->frames[ids[ib]].N;
+            for (int s = 0; s < segs_of(ib); ++s, ++row) {
+                dsss_reg_seg_pyr& o = out_host[row];
+                o.s.pair = k; o.s.seg = s; o.s.p0 = s * seg_pings; o.s.p1 = seg_end(s, Nb);
+                o.level = -1;
+                for (int l = 0; l < PYR_MAX_LEVELS; ++l) o.lz[l] = -2.0;
+                const int g = seg0[ib] + s;
+                row_a[row] = ia; row_b[row] = ib; row_g[row] = g;
+                if (!on_grid[ia] || sw[g].bw == 0) continue;
+                for (int l = 0; l < L; ++l) {
+                    const mosaic_win A = pyr_window(wins[ia], l, 0, 0), Bw = pyr_window(sw[g], l, 0, 0);
+                    const long long w = std::min(A.bw, Bw.bw + 2 * radius_of(l)), h = std::min(A.bh, Bw.bh + 2 * radius_of(l));
+                    bound[l] += (((w - 1) / REG_TILE + 1) + REG_STRIP - 1) / REG_STRIP * ((h - 1) / REG_TILE + 1);
+                }
+                cen_bound += (long long)((std::min(wins[ia].bw, sw[g].bw) - 1) / CEN_TW + 1) * ((std::min(wins[ia].bh, sw[g].bh) - 1) / CEN_TH + 1);
+            }
+        }
+        for (int l = 0; l < L; ++l)
+            if (bound[l] > 0x7fffffffll || cen_bound > 0x7fffffffll) DSSS_FAIL(c, DSSS_E_ARG, "register: %d segments are more than one launch takes", nseg);
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t nshift_max = std::max(nshift_of(L - 1), nshift_of(0));
+    const size_t table_max = (size_t)nseg * nshift_max * 6;
+    carve Cv;
+    const size_t o_lay = Cv.take(lay_cells * 2), o_win = Cv.take(win_cells * 8), o_jobs = Cv.take((size_t)n * sizeof(mosaic_job)),
+                 o_rows = Cv.take(rpy6 ? rows * 6 * sizeof(double) : 0), o_segs = Cv.take(hseg.size() * sizeof(mosaic_seg)),
+                 o_pj = Cv.take(hpj.size() * sizeof(pyr_job)), o_pairs = Cv.take((size_t)nseg * sizeof(reg_job)), o_cj = Cv.take((size_t)nseg * sizeof(cen_job)),
+                 o_cen = Cv.take((size_t)nseg * 3 * 8), o_tab = Cv.take((1 + table_max) * 8);      // the sample-limit flag and, behind it, one level's sums
+    rc = c->mosaic_buf.reserve(c, Cv.off); if (rc) return rc;
+    rc = c->mosaic_pinned.reserve(c, (1 + table_max) * 8); if (rc) return rc;
+    char* B = c->mosaic_buf.as<char>();
+    uint16_t* d_lay = reinterpret_cast<uint16_t*>(B + o_lay);
+    unsigned long long* d_win = reinterpret_cast<unsigned long long*>(B + o_win);
+    mosaic_job* d_jobs = reinterpret_cast<mosaic_job*>(B + o_jobs);
+    mosaic_seg* d_segs = reinterpret_cast<mosaic_seg*>(B + o_segs);
+    pyr_job* d_pj = reinterpret_cast<pyr_job*>(B + o_pj);
+    reg_job* d_pairs = reinterpret_cast<reg_job*>(B + o_pairs);
+    cen_job* d_cj = reinterpret_cast<cen_job*>(B + o_cj);
+    unsigned long long* d_cen = reinterpret_cast<unsigned long long*>(B + o_cen);
+    unsigned long long* d_tab = reinterpret_cast<unsigned long long*>(B + o_tab) + 1;
+    int* d_flag = reinterpret_cast<int*>(B + o_tab);
+    std::vector<const double*> dev_rows;
+    rc = upload_rows(c, ids, n, rpy6, ping_off, reinterpret_cast<double*>(B + o_rows), dev_rows); if (rc) return rc;
+    std::vector<mosaic_job> jobs(n);
+    for (int i = 0; i < n; ++i) { const dsss_frame& f = c->frames[ids[i]]; jobs[i] = mosaic_job{ dev_rows[i], f.gr, f.lvl[0], f.mask, f.N, f.M, 0, 0 }; }
+    HIPCHK(c, hipMemcpyAsync(d_jobs, jobs.data(), (size_t)n * sizeof(mosaic_job), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_segs, hseg.data(), hseg.size() * sizeof(mosaic_seg), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_pj, hpj.data(), hpj.size() * sizeof(pyr_job), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_flag, 0, 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_cen, 0, (size_t)nseg * 3 * 8, c->stream));
+    // 1. the layers of all levels: per frame one memset, its scatters and one pyramid launch over all its areas
+    const mosaic_win grid{ p->x0, p->y0, p->cell, p->W, p->H, 0, 0, 0, 0, p->use_mask != 0 };
+    for (int i = 0; i < n; ++i) {
+        if (!njobs[i]) continue;
+        HIPCHK(c, hipMemsetAsync(d_win, 0, acc_cells[i] * 8, c->stream));
+        if (on_grid[i]) launch_scatter(c, d_jobs + i, 1, jobs[i].N, wins[i], d_win);
+        if (acc_cells[i] > a_cells[i]) launch_scatter_seg(c, d_jobs + i, jobs[i].N, grid, d_win + a_cells[i], d_segs + seg0[i], seg_pings);
+        hipLaunchKernelGGL(mosaic_pyr_kernel, dim3((unsigned)pyr_blocks[i]), dim3(256), 0, c->stream, d_pj + job0[i], njobs[i], L, d_win, d_lay, d_flag);
+        HIPCHK(c, hipGetLastError());
+    }
+    // 2. level by level from the top: the rows still alive around their centres, one launch, one download, the level rule on the host
+    const uint64_t* tab = c->mosaic_pinned.as<uint64_t>() + 1;
+    const size_t row_sums = (nshift_of(L - 1) + (size_t)(L - 1) * nshift_of(0)) * 6;
+    std::vector<char> alive(nseg, 1); std::vector<int32_t> cx(nseg, 0), cy(nseg, 0);
+    std::vector<reg_job> pj; pj.reserve(nseg);
+    for (int l = L - 1; l >= 0; --l) {
+        const int r = radius_of(l); const size_t tsz = nshift_of(l) * 6;
+        pj.clear();
+        long long blocks = 0;
+        for (int row = 0; row < nseg; ++row) {
+            const int ia = row_a[row], g = row_g[row];
+            if (!alive[row] || !on_grid[ia] || sw[g].bw == 0) continue;
+            if (!reg_push_job(pj, &blocks, d_lay + a_lay[ia].off[l], pyr_window(wins[ia], l, 0, 0), d_lay + seg_lay[g].off[l], pyr_window(sw[g], l, cx[row], cy[row]),
+                              r, d_tab + (size_t)row * tsz))
+                DSSS_FAIL(c, DSSS_E_NUMERIC, "register: internal error, level %d of %d segments takes more workgroups than was bounded", l, nseg);
+        }
+        HIPCHK(c, hipMemsetAsync(d_tab, 0, (size_t)nseg * tsz * 8, c->stream));
+        rc = reg_launch_corr(c, pj, blocks, d_pairs, r); if (rc) return rc;
+        HIPCHK(c, hipMemcpyAsync(c->mosaic_pinned.p, d_flag, (1 + (size_t)nseg * tsz) * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if ((int)tab[-1]) DSSS_FAIL(c, DSSS_E_CAPACITY, "mosaic: a cell received more than 2^24 samples of one frame (cell %g too coarse)", p->cell);
+        const size_t at = l == L - 1 ? 0 : (nshift_of(L - 1) + (size_t)(L - 2 - l) * nshift_of(0)) * 6;      // this level's table within a row of sums_host
+        for (int row = 0; row < nseg; ++row) {
+            if (sums_host) {
+                if (alive[row]) memcpy(sums_host + (size_t)row * row_sums + at, tab + (size_t)row * tsz, tsz * 8);
+                else memset(sums_host + (size_t)row * row_sums + at, 0, tsz * 8);
+            }
+            if (!alive[row]) continue;
+            dsss_reg_seg_pyr& o = out_host[row];
+            dsss_reg_result q; int32_t usable = 0, nx = 0, ny = 0;
+            pyr_step_of(tab + (size_t)row * tsz, r, R.min_cells, p->cell, l, cx[row], cy[row], &q, &usable, &nx, &ny);
+            if (!usable) { alive[row] = 0; if (l == L - 1) o.s.r = q; continue; }              // no level has a usable peak: the top level's record
+            o.s.r = q; o.level = l; o.lx[l] = q.dx; o.ly[l] = q.dy; o.lz[l] = q.zncc;
+            if (q.on_border) o.border_mask |= 1 << l;
+            cx[row] = nx; cy[row] = ny;
+        }
+    }
+    // 3. the centroid sums at the total shift of the rows that finished at level 0: one launch, one download
+    std::vector<cen_job> cj;
+    long long cblocks = 0;
+    for (int row = 0; row < nseg; ++row) {
+        dsss_reg_seg_pyr& o = out_host[row];
+        if (o.level < 0) continue;                                              // the no-usable-shift record stays as it is
+        if (o.level == 0 && !cen_push_job(cj, &cblocks, d_lay + a_lay[row_a[row]].off[0], wins[row_a[row]], d_lay + seg_lay[row_g[row]].off[0], sw[row_g[row]], o.s.r,
+                                          d_cen + (size_t)row * 3))
+            DSSS_FAIL(c, DSSS_E_NUMERIC, "register: internal error, the centroid of %d segments takes more workgroups than was bounded", nseg);
+        o.s.r.on_border = (o.border_mask != 0 || o.level != 0) ? 1 : 0;
+    }
+    if (!cj.empty()) {
+        std::vector<uint64_t> cen((size_t)nseg * 3);
+        rc = reg_launch_centroids(c, cj, cblocks, d_cj, d_cen, cen); if (rc) return rc;
+        for (int row = 0; row < nseg; ++row) {
+            dsss_reg_seg& o = out_host[row].s;
+            if (out_host[row].level != 0) continue;
+            if ((int64_t)cen[(size_t)row * 3] != o.r.n)
+                DSSS_FAIL(c, DSSS_E_NUMERIC, "register: internal error, row %d has %lld cells at its peak and %lld in its centroid", row,
+                          (long long)o.r.n, (long long)cen[(size_t)row * 3]);
+            o.sx = (int64_t)cen[(size_t)row * 3 + 1]; o.sy = (int64_t)cen[(size_t)row * 3 + 2];
+        }
+    }
+    return DSSS_OK;
 }
 
 } // extern "C"

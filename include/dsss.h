@@ -496,6 +496,54 @@ int  dsss_mosaic_register_edges_yaw(dsss_ctx*, const int* ids, int n, const doub
                                     const dsss_reg_edge_yaw_params*, dsss_lc_edge* edges_host, int32_t* edge_seg_host /* may be NULL */,
                                     int cap, int* n_edges);
 
+/* ---- dense loop closures over a cell pyramid: the segments registered coarse to fine, so that the capture range is no longer the
+ * radius.  A flat search reaches radius <= 16 cells and its table grows with radius^2; a survey under dead reckoning drifts by metres.
+ * With L levels the top level, with cells of 2^(L-1) cell, searches the full radius and every level below refines within `refine`
+ * cells around twice the shift found above: about 2^(L-1) radius fine cells are reached.
+ * Parameters: levels L in 1..4, refine in 1..16 (ignored when L == 1).  Defaults: levels 1 (the registration by segments above),
+ *   refine 3 -- a value that has NOT been tuned on any data.
+ * Pooled layers: level l has cells of cell_l = cell 2^l (exact), W_l = ceil(W / 2^l), H_l = ceil(H / 2^l).  For a frame or a segment with
+ *   the level-0 accumulators cnt, sum defined above: cnt_l(jx, jy) = the sum of cnt over the grid cells with ix >> l == jx and
+ *   iy >> l == jy, sum_l the same of sum.  The cell is valid iff cnt_l > 0, and m = (sum_l + cnt_l / 2) / cnt_l in integers.  Level 0 is
+ *   the mean layer above bit for bit.  The only capacity rule is level 0's (2^24 samples per fine cell); pooled counts and sums are
+ *   kept in 64 bits and cannot wrap.  The definition is the pooling: it differs from a render under the coarse grid only in samples
+ *   beyond W, H, which stay dropped.
+ * Search, per (pair, segment) row, for l = L-1 down to 0: the centre (cx_l, cy_l) is (0, 0) at the top; the radius r_l is reg.radius
+ *   at the top and refine below; min_cells_l = max(1, min_cells >> 2l).  The table T_l holds the six shift sums between whole a and
+ *   the segment, both pooled to level l, for the shifts (cx_l + dx, cy_l + dy), |dx|, |dy| <= r_l, stored dy-major by the relative
+ *   (dx, dy) as above.  rec_l = dsss_mosaic_register_peak(T_l, r_l, min_cells_l, cell_l).  rec_l.zncc == -2: the search of this row
+ *   stops.  Otherwise t_l = (cx_l + rec_l.dx, cy_l + rec_l.dy), bit l of border_mask is set iff rec_l.on_border, and for l > 0 the
+ *   next centre is (cx_{l-1}, cy_{l-1}) = 2 t_l.
+ * Row: level = the finest level with a usable peak, -1 for none.  lx[l], ly[l] = t_l and lz[l] = the peak zncc of level l; levels not
+ *   reached or without a usable peak hold 0, 0, -2.  s.pair, seg, p0, p1 as in dsss_mosaic_register_segments.  s.r = rec_level with
+ *   dx, dy replaced by t_level, off_x = rec.off_x + (double)cx cell_level (one multiply and one add, unfused; the same in y; a centre
+ *   of 0 leaves rec's offset as it is), zncc0 and n0 those of the table's centre shift, and on_border = (border_mask != 0 or
+ *   level != 0): dsss_register_edge rejects every row that did not finish at level 0 or that touched a border on the way.  With
+ *   level == -1, s.r is the top level's no-usable-shift record unchanged.  s.sx, s.sy = the centroid sums at the total shift t_0 when
+ *   level == 0, and 0 otherwise.  With levels == 1 every s equals dsss_mosaic_register_segments' row of the same call bit for bit,
+ *   and border_mask == s.r.on_border.
+ * sums_host (may be NULL): per row (2 radius + 1)^2 x 6 sums of the top level, then (2 refine + 1)^2 x 6 for each of the levels
+ *   L-2 .. 0; the tables of levels not reached are zero.
+ * Everything is an integer up to the scores.  A frame is rendered once per call, its layers of all levels built in one pass.
+ * Errors: those of dsss_mosaic_register_segments, and DSSS_E_ARG for levels or refine outside the rules (the parameters may be NULL:
+ * the default).  Every argument and capacity error is decided before anything is launched.  The whole frame as one segment is
+ * seg_pings >= N_b.                                                                                                              */
+typedef struct { int32_t levels, refine; } dsss_reg_pyr_params;                        /* defaults 1, 3 (untuned) */
+typedef struct { dsss_reg_seg s;                      /* the row of the finest level with a usable peak */
+                 int32_t level, border_mask;          /* that level (-1: none); bit l: the peak of level l lay on the border of its square */
+                 int32_t lx[4], ly[4]; double lz[4]; } dsss_reg_seg_pyr;   /* t_l and the peak zncc of level l (0, 0, -2: not reached, or no usable peak) */
+void dsss_reg_pyr_params_default(dsss_reg_pyr_params*);
+/* pure host arithmetic, no context: the level rule on ONE table, T_level around the centre (cx, cy).  min_cells and cell are the
+ * level-0 values.  *usable = 1: out = rec with the centre added as defined above (out->on_border is rec's), and for level > 0
+ * (*ncx, *ncy) = the next level's centre 2 t.  *usable = 0: out = the no-usable-shift record unchanged, *ncx, *ncy are not written.
+ * DSSS_E_ARG: a NULL pointer, radius outside 0..16, min_cells < 1, cell <= 0 or not finite, level outside 0..3, |cx| or |cy| > 2^28 */
+int  dsss_register_pyr_step(const uint64_t* sums, int radius, int min_cells, double cell, int level, int cx, int cy,
+                            dsss_reg_result* out, int32_t* usable, int32_t* ncx, int32_t* ncy);
+int  dsss_mosaic_register_segments_pyr(dsss_ctx*, const int* ids, int n, const double* rpy6, const int* ping_off, const dsss_mosaic_params*,
+                                       const int* pair_a, const int* pair_b, int npairs, int seg_pings, const dsss_reg_params*,
+                                       const dsss_reg_pyr_params*, dsss_reg_seg_pyr* out_host, int cap, int* nseg_host,
+                                       uint64_t* sums_host /* nseg x ((2r+1)^2 + (levels-1) (2 refine+1)^2) x 6, may be NULL */);
+
 /* ------------------------------------------------------------------ instrumentation
  * accumulated GPU time (ms, HIP events on the context stream) and launch count per kernel family        */
 #define DSSS_K_ROW_REDUCE   0   /* row_reduce_kernel: one f64 read of the waterfall */

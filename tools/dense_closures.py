@@ -3,7 +3,7 @@
 solved trajectory (dsss_mosaic_register_segments), the accepted offsets become pose-graph edges (dsss_mosaic_register_edges), the
 trajectory is solved again with them next to the feature-based closures, and the segments are registered once more under the result.
     python tools/dense_closures.py --frames 200 --rows 2000 --cols 1024 --cell 0.1 [--seg-pings 80] [--radius 8] [--calls 5] [--timeout 1500]
-                                   [--yaw-fan NYAW [--yaw-step RAD]]
+                                   [--yaw-fan NYAW [--yaw-step RAD]] [--pyramid L [--refine RHO]]
 Steps: 1. pipeline and dsss_posegraph_solve; 2. segments under the solved trajectory; 3. edges; 4. the edges of dsss_posegraph_select
 with the new ones behind them; 5. dsss_posegraph_solve_edges on the frames' dead-reckoning rows; 6. segments under the result.
 Prints one JSON line: segments and accepted edges; median and 95th percentile of |offset| in metres over the segments with a peak, the
@@ -14,6 +14,12 @@ call's time can be set against), each the median of --calls synchronised calls a
 (dsss_mosaic_register_segments_yaw) and turns the rows into edges that measure the heading (dsss_mosaic_register_edges_yaw): the same
 report, with the median and 95th percentile of |theta_hat| over the segments with a peak and the rows on the border of the fan, before
 and after, and the wall time of the fan call next to the translation-only call's.
+--pyramid L (2..4) registers every segment coarse to fine over L levels as well (dsss_mosaic_register_segments_pyr, --refine cells
+around twice the shift found above below the top level) and builds the edges from those rows through the unchanged
+dsss_mosaic_register_edges.  Under every trajectory that is registered (with --pyramid also the dead-reckoning one, "dr") it reports
+the rows per level, the rows with a border bit, the median and 95th percentile of the total shift in cells over the rows that finished at
+level 0, and the flat call's on_border count on the same pairs in the same process; and the wall time of the pyramid call next to the
+flat segment call's.
 The GPU work runs in a child process under a time limit (--timeout seconds); this process never opens the device."""
 import argparse
 import json
@@ -28,6 +34,7 @@ ap.add_argument("--cols", type=int, default=1024); ap.add_argument("--cell", typ
 ap.add_argument("--seg-pings", type=int, default=80)
 ap.add_argument("--radius", type=int, default=8); ap.add_argument("--min-cells", type=int, default=256)
 ap.add_argument("--yaw-fan", type=int, default=1); ap.add_argument("--yaw-step", type=float, default=0.01)
+ap.add_argument("--pyramid", type=int, default=1); ap.add_argument("--refine", type=int, default=3)
 ap.add_argument("--calls", type=int, default=5); ap.add_argument("--timeout", type=float, default=1500.0)
 ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)
 a = ap.parse_args()
@@ -35,6 +42,9 @@ if a.calls < 5:
     sys.exit("--calls must be at least 5")
 if a.yaw_fan < 1 or a.yaw_fan > 17 or a.yaw_fan % 2 == 0 or not a.yaw_step > 0:
     sys.exit("--yaw-fan must be odd and in 1..17, --yaw-step positive")
+
+if a.pyramid < 1 or a.pyramid > 4 or a.refine < 1 or a.refine > 16 or (a.pyramid > 1 and a.yaw_fan > 1):
+    sys.exit("--pyramid must be in 1..4, --refine in 1..16; the yaw fan over the pyramid is not built")
 
 if not a.worker:
     try:
@@ -79,9 +89,13 @@ def timed(fn):
 
 FAN = a.yaw_fan > 1
 yaw = capi.RegYawParams(a.yaw_fan, 0, a.yaw_step)
+PYR = a.pyramid > 1
+pyr = capi.RegPyrParams(a.pyramid, a.refine)
 
 
 def register(traj):
+    if PYR:
+        return ctx.mosaic_register_segments_pyr(ids, p, pairs, a.seg_pings, pyr=pyr, reg=reg, rpy6=traj, ping_off=off)
     if FAN:
         return ctx.mosaic_register_segments_yaw(ids, p, pairs, a.seg_pings, yaw=yaw, reg=reg, rpy6=traj, ping_off=off)
     return ctx.mosaic_register_segments(ids, p, pairs, a.seg_pings, reg=reg, rpy6=traj, ping_off=off)
@@ -89,6 +103,14 @@ def register(traj):
 
 def describe(segs, traj):
     fan = {}
+    if PYR:
+        done = segs["level"] == 0
+        t = np.hypot(segs["lx"][done, 0], segs["ly"][done, 0])
+        flat = ctx.mosaic_register_segments(ids, p, pairs, a.seg_pings, reg=reg, rpy6=traj, ping_off=off)["r"]
+        fan = dict(rows_per_level={str(l): int((segs["level"] == l).sum()) for l in range(-1, a.pyramid)}, border_rows=int((segs["border_mask"] != 0).sum()),
+                   total_shift_median_cells=float(np.median(t)) if done.any() else None, total_shift_p95_cells=float(np.percentile(t, 95)) if done.any() else None,
+                   flat_on_border=int((flat["on_border"][flat["zncc"] > -2.0] != 0).sum()), flat_with_peak=int((flat["zncc"] > -2.0).sum()))
+        segs = segs["s"]
     if FAN:
         ok = segs["s"]["r"]["zncc"] > -2.0
         t = np.abs(segs["theta_hat"][ok])
@@ -118,6 +140,9 @@ def rows_of(poses12):
 
 res["segments_ms"], res["segments_ms_min"] = timed(lambda: ctx.mosaic_register_segments(ids, p, pairs, a.seg_pings, reg=reg, rpy6=rpy, ping_off=off))
 res["whole_frame_ms"], res["whole_frame_ms_min"] = timed(lambda: ctx.mosaic_register(ids, p, pairs, reg=reg, rpy6=rpy, ping_off=off))
+if PYR:
+    res["pyramid"], res["refine"] = a.pyramid, a.refine
+    res["segments_pyr_ms"], res["segments_pyr_ms_min"] = timed(lambda: register(rpy))
 if FAN:
     res["yaw_fan"], res["yaw_step"] = a.yaw_fan, a.yaw_step
     res["segments_yaw_ms"], res["segments_yaw_ms_min"] = timed(lambda: register(rpy))
@@ -126,7 +151,7 @@ if FAN:                                                                         
     new, src = ctx.mosaic_register_edges_yaw(ids, p, pairs, before, edge_params=capi.RegEdgeYawParams(capi.reg_edge_params_default(), yaw, 1.0),
                                              rpy6=rpy, ping_off=off)
 else:
-    new, src = ctx.mosaic_register_edges(ids, p, pairs, before, rpy6=rpy, ping_off=off)
+    new, src = ctx.mosaic_register_edges(ids, p, pairs, np.ascontiguousarray(before["s"]) if PYR else before, rpy6=rpy, ping_off=off)
 old = ctx.posegraph_select(F)                                                                            # 4
 dr = np.ascontiguousarray(np.concatenate([i[0] for i in ins]))
 t0 = time.perf_counter()
@@ -138,5 +163,7 @@ true = np.ascontiguousarray(np.concatenate(sv.poses_true))
 res.update(segments=len(before), feature_edges=len(old), accepted_edges=len(new), lm_iterations_again=int(stats2[0]), solve_again_ms=round(solve_ms, 3),
            before=describe(before, rpy), after=describe(after, again),
            consistency_dr=float(ctx.mosaic_consistency(ids, p)[3]), consistency_true=float(ctx.mosaic_consistency(ids, p, rpy6=true, ping_off=off)[3]))
+if PYR:                                          # the same counts under dead reckoning, where the legs lie furthest from where they belong
+    res["dr"] = describe(register(dr), dr)
 print(json.dumps(res))
 pipe.close()
