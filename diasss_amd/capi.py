@@ -69,6 +69,12 @@ class RegResult(C.Structure):
 REG_DTYPE = np.dtype(RegResult)          # the rows Context.mosaic_register returns
 
 
+class RegCallInfo(C.Structure):
+    """dsss_reg_call_info: what the last registration call of a context that succeeded did: tables scored by mosaic_peak_kernel / by
+    the host, bytes it copied device -> host, stream synchronisations it made"""
+    _fields_ = [("tables_device", C.c_int64), ("tables_host", C.c_int64), ("bytes_down", C.c_int64), ("syncs", C.c_int64)]
+
+
 class RegSeg(C.Structure):
     """dsss_reg_seg: one (pair, segment) row of the registration by segments: pair = index into the pair list, pings [p0, p1) of the
     pair's frame b, r = the RegResult of the segment's table, sx, sy = sum of ix, iy over the overlapping cells at the peak shift"""
@@ -300,6 +306,10 @@ def lib():
         L.dsss_mosaic_register_segments_pyr.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(MosaicParams), C.c_void_p,
                                                         C.c_void_p, C.c_int, C.c_int, C.POINTER(RegParams), C.POINTER(RegPyrParams), C.c_void_p, C.c_int,
                                                         C.POINTER(C.c_int), C.c_void_p]
+        L.dsss_mosaic_register_peaks.restype = C.c_int
+        L.dsss_mosaic_register_peaks.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_void_p]
+        L.dsss_mosaic_register_info.restype = C.c_int
+        L.dsss_mosaic_register_info.argtypes = [C.c_void_p, C.POINTER(RegCallInfo)]
         _LIB = L
     return _LIB
 
@@ -1022,6 +1032,32 @@ class Context:
         self._chk(self.L.dsss_mosaic_register_segments_pyr(*args, _ptr(out), int(cap), C.byref(nseg), _ptr(sums)), "dsss_mosaic_register_segments_pyr")
         out = out[:nseg.value]
         return (out, sums[:nseg.value]) if want_sums else out
+
+    def mosaic_register_peaks(self, sums, radius, min_cells, cell, ntables=None, out=None):
+        """dsss_mosaic_register_peaks: the peak rule on many tables at once, on the device -> rows of REG_DTYPE, row k bit for bit what
+        mosaic_register_peak gives for table k.  sums: a numpy array of ntables x (2 radius + 1)^2 x 6 uint64 (ntables from its
+        size), or device memory -- a torch tensor, or an address -- with ntables given.  out: a REG_DTYPE array to write into."""
+        S = 2 * int(radius) + 1
+        if isinstance(sums, np.ndarray):
+            sums = np.ascontiguousarray(sums, np.uint64)
+            if ntables is None:
+                if not 0 <= int(radius) <= 16 or sums.size % (S * S * 6):
+                    raise ValueError("mosaic_register_peaks: %d sums for radius %d" % (sums.size, radius))
+                ntables = sums.size // (S * S * 6)
+        elif ntables is None:
+            raise ValueError("mosaic_register_peaks: ntables is needed with device memory")
+        if out is None:
+            out = np.zeros(max(int(ntables), 0), REG_DTYPE)
+        assert out.dtype == REG_DTYPE and out.flags.c_contiguous and len(out) >= ntables
+        self._chk(self.L.dsss_mosaic_register_peaks(self.h, _ptr(sums), int(ntables), int(radius), int(min_cells), C.c_double(cell),
+                                                    _ptr(out) if len(out) else None), "dsss_mosaic_register_peaks")
+        return out
+
+    def mosaic_register_info(self):
+        """dsss_mosaic_register_info -> a RegCallInfo of the last mosaic_register* call of this context that succeeded"""
+        info = RegCallInfo()
+        self._chk(self.L.dsss_mosaic_register_info(self.h, C.byref(info)), "dsss_mosaic_register_info")
+        return info
 
     # ---- instrumentation
     def profile(self, on=True):

@@ -31,6 +31,7 @@ dsss_switches dsss_switches_read()
     if (const char* v = getenv("DSSS_FS_THREADS")) sw.fs_threads = atoi(v);
     if (const char* v = getenv("DSSS_MT_GRID")) sw.mt_grid = atoi(v) != 0;
     sw.sift_hist_dump = getenv("DSSS_SIFT_HIST_DUMP");
+    if (const char* v = getenv("DSSS_REG_PEAKS")) sw.reg_peaks_host = strcmp(v, "host") == 0;
     return sw;
 }
 

@@ -181,7 +181,8 @@ struct dsss_ctx {
     dsss_buf pg_warm{"pg_warm"}; int pg_warm_n = 0;   // pose_t[pg_warm_n]
     std::vector<dsss_lc_edge> pg_inc_edges; unsigned long long lc_gen = 0, pg_inc_gen = 0;    // lc_gen counts LC result sets; the last one consumed
     dsss_buf mosaic_buf{"mosaic_buf"};                                        // device scratch of dsss_mosaic_*: accumulators, output layers, job table, trajectory rows (kept between calls)
-    dsss_buf mosaic_pinned{"mosaic_pinned", DSSS_PINNED};                     // page-locked landing area of the segment registration's table of sums (140 MB at the headline size: a pageable copy into fresh memory cost more than the kernels)
+    dsss_buf mosaic_pinned{"mosaic_pinned", DSSS_PINNED};                     // page-locked landing area of the segment registration: the records of mosaic_peak_kernel, or on the host path the table of sums (140 MB at the headline size: a pageable copy into fresh memory cost more than the kernels)
+    dsss_reg_call_info reg_info{0, 0, 0, 0};                                  // what the last registration call that returned DSSS_OK did (dsss_mosaic_register_info)
     dsss_buf pgr_buf{"pgr_buf"};                                           // device scratch of dsss_posegraph_edge_report (dsss_pg_report.hip), kept between calls
     dsss_prof prof;
 };
@@ -261,7 +262,7 @@ struct dsss_scope {
 };
 
 // The DSSS_* environment switches outside the pose graph (those: pg_switches, dsss_pg_sym.h).  Read ONCE PER CALL by the C entry that
-// needs them (dsss_frames_set, dsss_extract, dsss_extract_many, dsss_match_pairs) and handed down: one process may flip them between calls.
+// needs them (dsss_frames_set, dsss_extract, dsss_extract_many, dsss_match_pairs, the four dsss_mosaic_register* entries) and handed down: one process may flip them between calls.
 struct dsss_switches {
     size_t ex_scratch_mb = 24576;            // DSSS_EX_SCRATCH_MB: bound of the extraction's batch scratch, max(1, atoi)
     int ex_upload_batch = 8;                 // DSSS_EX_UPLOAD_BATCH: frames per batch while host images are still streamed in, max(1, atoi)
@@ -269,6 +270,7 @@ struct dsss_switches {
     int fs_threads = 0;                      // DSSS_FS_THREADS: atoi; not above 0 = dsss_frames_set's own rule
     bool mt_grid = true;                     // DSSS_MT_GRID: off only when set and atoi == 0
     const char* sift_hist_dump = nullptr;    // DSSS_SIFT_HIST_DUMP: the path
+    bool reg_peaks_host = false;             // DSSS_REG_PEAKS: on only when set to "host" (the registration decides its peaks on the host even without sums_host)
 };
 dsss_switches dsss_switches_read();      // dsss_ctx.hip
 

@@ -50,6 +50,73 @@ __device__ __forceinline__ void mosaic_scatter_samples(const double* P, const do
     }
 }
 
+// ---- the score, order and sub-cell rules of the registration ("overlap registration" in the header): ONE body for the host
+// (dsss_mosaic_register_peak) and the device (mosaic_peak_kernel), as dsss_rotate_row is for the fan.  Everything in it is an IEEE-754
+// basic operation -- 128-bit integer multiply and subtract, integer to the nearest double, * / sqrt + - in f64, unfused
+// (-ffp-contract=off) -- so both sides give the same bits.
+// exact integer -> the nearest double, ties to even (what Python's float() of an int does): below 2^64 the hardware conversion is that
+// already; above, the value is cut to 64 bits with a sticky bit first, which leaves the rounding of the 53-bit result unchanged
+__host__ __device__ inline double reg_i128_to_double(__int128 v)
+{
+    const bool neg = v < 0;
+    unsigned __int128 u = neg ? (unsigned __int128)0 - (unsigned __int128)v : (unsigned __int128)v;
+    double d;
+    if ((u >> 64) == 0) d = (double)(uint64_t)u;
+    else {
+        const int sh = 64 - __builtin_clzll((uint64_t)(u >> 64));            // bits above the low 64
+        const uint64_t top = (uint64_t)(u >> sh);
+        const bool sticky = (u & (((unsigned __int128)1 << sh) - 1)) != 0;
+        d = ldexp((double)(top | (sticky ? 1ull : 0ull)), sh);
+    }
+    return neg ? -d : d;
+}
+
+struct reg_score { double z; bool ok; };
+
+// one shift's six sums n, Sa, Sb, Sab, Saa, Sbb -> its score; not usable: -2
+__host__ __device__ inline reg_score reg_score_of(const uint64_t* s6, int min_cells)
+{
+    const __int128 n = s6[0], Sa = s6[1], Sb = s6[2], Sab = s6[3], Saa = s6[4], Sbb = s6[5];
+    const __int128 num = n * Sab - Sa * Sb, da = n * Saa - Sa * Sa, db = n * Sbb - Sb * Sb;
+    if (s6[0] < (uint64_t)min_cells || da <= 0 || db <= 0) return { -2.0, false };
+    return { reg_i128_to_double(num) / sqrt(reg_i128_to_double(da) * reg_i128_to_double(db)), true };
+}
+
+// the order of the peak among usable shifts: the larger z, then the smaller dx^2 + dy^2, then the smaller dy, then the smaller dx.
+// Total: two different shifts are never equal under it, so the winner does not depend on the order they are looked at in.
+__host__ __device__ inline bool reg_better(double z, int dx, int dy, double zb, int bx, int by)
+{
+    const int d2 = dx * dx + dy * dy, b2 = bx * bx + by * by;
+    return z > zb || (z == zb && (d2 < b2 || (d2 == b2 && (dy < by || (dy == by && dx < bx)))));
+}
+
+// the sub-cell position on one axis: the parabola through the peak z0 and its two neighbours, 0 where one is not usable or the
+// denominator is not below 0
+__host__ __device__ inline double reg_parabola(const reg_score& m, double z0, const reg_score& p)
+{
+    if (!m.ok || !p.ok) return 0.0;
+    const double den = m.z - 2.0 * z0 + p.z;
+    return den < 0.0 ? 0.5 * (m.z - p.z) / den : 0.0;
+}
+
+// the record of a table whose peak is known: found = a usable shift exists, (bx, by) = the peak, z0 and n0 = score and cells of the
+// zero shift, zp and np = those of the peak, xm, xp, ym, yp = the scores of its four neighbours (read only where the peak is not on
+// the border).  Every byte of *out is written.
+__host__ __device__ inline void reg_record(bool found, int bx, int by, int radius, double cell, const reg_score& z0, uint64_t n0, const reg_score& zp, uint64_t np,
+                                           const reg_score& xm, const reg_score& xp, const reg_score& ym, const reg_score& yp, dsss_reg_result* out)
+{
+    dsss_reg_result r;
+    r.dx = 0; r.dy = 0; r.off_x = 0.0; r.off_y = 0.0; r.zncc = -2.0; r.zncc0 = z0.z; r.n = (int64_t)n0; r.n0 = (int64_t)n0; r.on_border = 0; r.pad_ = 0;
+    if (found) {
+        r.dx = bx; r.dy = by; r.zncc = zp.z; r.n = (int64_t)np;
+        r.on_border = (bx == radius || bx == -radius || by == radius || by == -radius) ? 1 : 0;
+        double px = 0.0, py = 0.0;
+        if (!r.on_border) { px = reg_parabola(xm, zp.z, xp); py = reg_parabola(ym, zp.z, yp); }
+        r.off_x = ((double)bx + px) * cell; r.off_y = ((double)by + py) * cell;
+    }
+    *out = r;
+}
+
 // carves mosaic_buf into 256-byte aligned pieces
 struct carve { size_t off = 0; size_t take(size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; } };
 

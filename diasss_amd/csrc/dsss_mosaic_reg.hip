@@ -1,9 +1,9 @@
 // diasss_amd/csrc/dsss_mosaic_reg.hip -- dense overlap registration of frame pairs (include/dsss.h, section "mosaic", "overlap
 // registration").  Every frame of a pair is rendered alone into its window of the grid (mosaic_scatter_kernel, as the consistency map
 // does) and kept as one u16 per cell; mosaic_corr_kernel slides frame b over frame a and accumulates, per shift, the six integer sums
-// of the zero-normalised cross-correlation.  Score, peak, tie and sub-cell rules are host arithmetic on that table
-// (dsss_mosaic_register_peak), exact in integers up to one conversion per quantity, so a result is the same whatever the order of
-// frames, pairs, tiles and atomics.
+// of the zero-normalised cross-correlation.  Score, peak, tie and sub-cell rules are arithmetic on that table, exact in integers up
+// to one conversion per quantity, so a result is the same whatever the order of frames, pairs, tiles and atomics; they are written once
+// for host and device (dsss_mosaic_int.h): dsss_mosaic_register_peak on the host, mosaic_peak_kernel where the table lies.
 // Dense loop closures ("dense loop closures" in the header): the same registration with frame b cut into segments of pings
 // (dsss_mosaic_register_segments: one segmented scatter and one pack per frame, the correlation kernel through its job table,
 // mosaic_centroid_kernel for where the overlap lies), and a segment's offset as a pose-graph edge (dsss_register_edge, host arithmetic).
@@ -13,6 +13,10 @@
 // Over a cell pyramid ("dense loop closures over a cell pyramid"): the segments registered coarse to fine (dsss_mosaic_register_segments_pyr:
 // mosaic_pyr_kernel writes the pooled layers of all levels in one pass over a frame's accumulators, the correlation runs once per level
 // around each row's centre, the level rule is host arithmetic in one place, dsss_register_pyr_step).
+// Peaks on the device ("peaks on the device" in the header): when the caller asks for no sums, the four entries leave the table on
+// the device, mosaic_peak_kernel runs behind the correlation, and the records come down with the sample-limit flag in one copy;
+// with sums, or under DSSS_REG_PEAKS=host, the table comes down and the host decides, as before.  dsss_mosaic_register_peaks is the
+// kernel as a public entry on any tables, dsss_mosaic_register_info what the last call did.
 #include "dsss_mosaic_int.h"
 #include "dsss_pose.h"
 #include "dsss_wave.h"
@@ -277,68 +281,96 @@ __global__ __launch_bounds__(256) void mosaic_scatter_fan_kernel(const mosaic_jo
     mosaic_scatter_samples(s_row[0], s_sc, J, row, G, acc);
 }
 
-// exact integer -> the nearest double, ties to even (what Python's float() of an int does): below 2^64 the hardware conversion is that
-// already; above, the value is cut to 64 bits with a sticky bit first, which leaves the rounding of the 53-bit result unchanged
-double i128_to_double(__int128 v)
+// ---- peaks on the device ("peaks on the device" in the header)
+#define PEAK_WAVES 4                       // tables per workgroup of mosaic_peak_kernel: one wavefront each
+
+// One table of (2 radius + 1)^2 shifts x six sums -> its record, by one wavefront; rec[k] is what peak_of gives for table k, bit for
+// bit (the rules are the one body of dsss_mosaic_int.h).  The lanes stride over the shifts (a lane reads the 48 contiguous bytes of a
+// shift) and each keeps its best (z, shift) under reg_better; the order is total, so the butterfly over the wavefront ends with the
+// same winner in every lane whatever its shape.  The zero shift, the peak and its four neighbours are then scored again by six lanes
+// -- a score is a function of six integers, so it has the same bits as in the scan and no table of scores is kept anywhere -- and
+// lane 0 writes the 64 bytes.  No atomics, no LDS.  Radius, min_cells and cell are uniform per launch.
+__global__ __launch_bounds__(64 * PEAK_WAVES) void mosaic_peak_kernel(const unsigned long long* __restrict__ sums, long long ntables, int radius, int min_cells,
+                                                                      double cell, dsss_reg_result* __restrict__ rec)
 {
-    const bool neg = v < 0;
-    unsigned __int128 u = neg ? (unsigned __int128)0 - (unsigned __int128)v : (unsigned __int128)v;
-    double d;
-    if ((u >> 64) == 0) d = (double)(uint64_t)u;
-    else {
-        const int sh = 64 - __builtin_clzll((uint64_t)(u >> 64));            // bits above the low 64
-        const uint64_t top = (uint64_t)(u >> sh);
-        const bool sticky = (u & (((unsigned __int128)1 << sh) - 1)) != 0;
-        d = ldexp((double)(top | (sticky ? 1ull : 0ull)), sh);
+    const int lane = (int)threadIdx.x & 63;
+    const long long k = (long long)blockIdx.x * PEAK_WAVES + ((int)threadIdx.x >> 6);
+    if (k >= ntables) return;                                                   // (uniform per wavefront)
+    const int S = 2 * radius + 1, nshift = S * S;
+    const uint64_t* __restrict__ tab = reinterpret_cast<const uint64_t*>(sums) + (size_t)k * nshift * 6;
+    int best = -1; double zb = -2.0;                                            // this lane's best shift, -1: none usable so far
+    for (int s = lane; s < nshift; s += 64) {
+        const reg_score q = reg_score_of(tab + (size_t)s * 6, min_cells);
+        if (!q.ok) continue;
+        const int sy = s / S, sx = s - sy * S;
+        if (best < 0) { best = s; zb = q.z; continue; }
+        const int ty = best / S, tx = best - ty * S;
+        if (reg_better(q.z, sx - radius, sy - radius, zb, tx - radius, ty - radius)) { best = s; zb = q.z; }
     }
-    return neg ? -d : d;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int ob = __shfl_xor(best, d, 64); const double oz = __shfl_xor(zb, d, 64);
+        const int so = max(ob, 0), sb = max(best, 0);
+        const int sy = so / S, sx = so - sy * S, ty = sb / S, tx = sb - ty * S;
+        if (ob >= 0 && (best < 0 || reg_better(oz, sx - radius, sy - radius, zb, tx - radius, ty - radius))) { best = ob; zb = oz; }
+    }
+    const bool found = best >= 0;
+    const int zero = radius * S + radius, pk = found ? best : zero;
+    const int by = pk / S - radius, bx = pk - (pk / S) * S - radius;
+    const bool inner = found && bx != radius && bx != -radius && by != radius && by != -radius;      // the four neighbours exist
+    // lanes 0..5: the zero shift, the peak, x-, x+, y-, y+
+    int t = zero;
+    if (lane == 1) t = pk;
+    if (inner) { if (lane == 2) t = pk - 1; if (lane == 3) t = pk + 1; if (lane == 4) t = pk - S; if (lane == 5) t = pk + S; }
+    reg_score q = { -2.0, false }; unsigned long long nq = 0;
+    if (lane < 6) { q = reg_score_of(tab + (size_t)t * 6, min_cells); nq = tab[(size_t)t * 6]; }
+    reg_score g[6];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) { g[j].z = __shfl(q.z, j, 64); g[j].ok = __shfl((int)q.ok, j, 64) != 0; }
+    const unsigned long long n0 = __shfl(nq, 0, 64), np = __shfl(nq, 1, 64);
+    if (lane == 0) reg_record(found, bx, by, radius, cell, g[0], n0, g[1], np, g[2], g[3], g[4], g[5], rec + k);
 }
 
-struct reg_score { double z; bool ok; };
-
-reg_score score_of(const uint64_t* s6, int min_cells)
+// the launches of mosaic_peak_kernel over ntables tables, cut where one launch's workgroup count would not fit
+int reg_launch_peaks(dsss_ctx* c, const unsigned long long* d_tab, long long ntables, int radius, int min_cells, double cell, dsss_reg_result* d_rec)
 {
-    const __int128 n = s6[0], Sa = s6[1], Sb = s6[2], Sab = s6[3], Saa = s6[4], Sbb = s6[5];
-    const __int128 num = n * Sab - Sa * Sb, da = n * Saa - Sa * Sa, db = n * Sbb - Sb * Sb;
-    if (s6[0] < (uint64_t)min_cells || da <= 0 || db <= 0) return { -2.0, false };
-    return { i128_to_double(num) / sqrt(i128_to_double(da) * i128_to_double(db)), true };
+    const long long per = 0x7fffffffll * PEAK_WAVES;                            // tables of one launch
+    const size_t tsz = (size_t)(2 * radius + 1) * (2 * radius + 1) * 6;
+    for (long long k0 = 0; k0 < ntables; k0 += per) {
+        const long long nt = std::min(per, ntables - k0);
+        hipLaunchKernelGGL(mosaic_peak_kernel, dim3((unsigned)((nt + PEAK_WAVES - 1) / PEAK_WAVES)), dim3(64 * PEAK_WAVES), 0, c->stream,
+                           d_tab + (size_t)k0 * tsz, nt, radius, min_cells, cell, d_rec + k0);
+        HIPCHK(c, hipGetLastError());
+    }
+    return DSSS_OK;
 }
 
 int peak_of(const uint64_t* sums, int radius, int min_cells, double cell, dsss_reg_result* out)
 {
     const int S = 2 * radius + 1;
     std::vector<reg_score> z((size_t)S * S);
-    for (int s = 0; s < S * S; ++s) z[s] = score_of(sums + (size_t)s * 6, min_cells);
+    for (int s = 0; s < S * S; ++s) z[s] = reg_score_of(sums + (size_t)s * 6, min_cells);
     bool found = false; int bx = 0, by = 0;
     for (int dy = -radius; dy <= radius; ++dy)
         for (int dx = -radius; dx <= radius; ++dx) {
             const reg_score& q = z[(size_t)(dy + radius) * S + (dx + radius)];
             if (!q.ok) continue;
-            bool better = !found;
-            if (found) {
-                const double zb = z[(size_t)(by + radius) * S + (bx + radius)].z;
-                const int d2 = dx * dx + dy * dy, b2 = bx * bx + by * by;
-                better = q.z > zb || (q.z == zb && (d2 < b2 || (d2 == b2 && (dy < by || (dy == by && dx < bx)))));
-            }
-            if (better) { found = true; bx = dx; by = dy; }
+            if (!found || reg_better(q.z, dx, dy, z[(size_t)(by + radius) * S + (bx + radius)].z, bx, by)) { found = true; bx = dx; by = dy; }
         }
-    const size_t zero = (size_t)radius * S + radius;
-    memset(out, 0, sizeof *out);
-    out->zncc0 = z[zero].z; out->n0 = (int64_t)sums[zero * 6];
-    if (!found) { out->zncc = -2.0; out->n = out->n0; return DSSS_OK; }
-    const size_t pk = (size_t)(by + radius) * S + (bx + radius);
-    out->dx = bx; out->dy = by; out->zncc = z[pk].z; out->n = (int64_t)sums[pk * 6];
-    out->on_border = (abs(bx) == radius || abs(by) == radius) ? 1 : 0;
-    double px = 0.0, py = 0.0;
-    if (!out->on_border) {
-        const double z0 = z[pk].z;
-        const reg_score xm = z[pk - 1], xp = z[pk + 1], ym = z[pk - S], yp = z[pk + S];
-        if (xm.ok && xp.ok) { const double den = xm.z - 2.0 * z0 + xp.z; if (den < 0.0) px = 0.5 * (xm.z - xp.z) / den; }
-        if (ym.ok && yp.ok) { const double den = ym.z - 2.0 * z0 + yp.z; if (den < 0.0) py = 0.5 * (ym.z - yp.z) / den; }
-    }
-    out->off_x = ((double)bx + px) * cell; out->off_y = ((double)by + py) * cell;
+    const size_t zero = (size_t)radius * S + radius, pk = (size_t)(by + radius) * S + (bx + radius);
+    const bool inner = found && abs(bx) != radius && abs(by) != radius;      // the four neighbours exist
+    const reg_score none = { -2.0, false };
+    reg_record(found, bx, by, radius, cell, z[zero], sums[zero * 6], z[pk], sums[pk * 6], inner ? z[pk - 1] : none, inner ? z[pk + 1] : none,
+               inner ? z[pk - S] : none, inner ? z[pk + S] : none, out);
     return DSSS_OK;
 }
+
+// what a registration call did (dsss_reg_call_info), counted where the call enqueues its copies and synchronises
+struct reg_count {
+    dsss_reg_call_info I{0, 0, 0, 0};
+    void down(size_t bytes) { I.bytes_down += (int64_t)bytes; }
+    void sync() { I.syncs += 1; }
+};
 
 // ---- what dsss_mosaic_register and dsss_mosaic_register_segments share on the host
 // the argument rules of both entries; R = the parameters in force, slot = frame id -> its index in ids, rows = pings of all frames
@@ -428,13 +460,15 @@ bool cen_push_job(std::vector<cen_job>& cj, long long* blocks, const uint16_t* l
 }
 
 // all centroid jobs in one launch, and the nseg x 3 sums back in cen (d_cen was cleared before)
-int reg_launch_centroids(dsss_ctx* c, const std::vector<cen_job>& cj, long long cblocks, cen_job* d_cj, const unsigned long long* d_cen, std::vector<uint64_t>& cen)
+int reg_launch_centroids(dsss_ctx* c, const std::vector<cen_job>& cj, long long cblocks, cen_job* d_cj, const unsigned long long* d_cen, std::vector<uint64_t>& cen,
+                         reg_count& cnt)
 {
     HIPCHK(c, hipMemcpyAsync(d_cj, cj.data(), cj.size() * sizeof(cen_job), hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(mosaic_centroid_kernel, dim3((unsigned)cblocks), dim3(256), 0, c->stream, d_cj, (int)cj.size());
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(cen.data(), d_cen, cen.size() * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    cnt.down(cen.size() * 8); cnt.sync();
     return DSSS_OK;
 }
 
@@ -566,18 +600,25 @@ int edges_loop(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int
 bool pyr_ok(const dsss_reg_pyr_params& P) { return P.levels >= 1 && P.levels <= PYR_MAX_LEVELS && (P.levels == 1 || (P.refine >= 1 && P.refine <= REG_MAX_RADIUS)); }
 
 // the level rule of the header, "dense loop closures over a cell pyramid": the one place it is written.  sums = the table of level
-// `level` around the centre (cx, cy); min_cells and cell are the level-0 values.
-void pyr_step_of(const uint64_t* sums, int radius, int min_cells, double cell, int level, int cx, int cy, dsss_reg_result* out, int32_t* usable,
-                 int32_t* ncx, int32_t* ncy)
+// `level` around the centre (cx, cy); min_cells and cell are the level-0 values.  It has two parts: the record of the level's table
+// under pyr_min_cells and the level's cell (peak_of on the host, mosaic_peak_kernel on the device), and pyr_centre_of, which adds the
+// centre to that record (*out) and is host arithmetic on both paths.
+void pyr_centre_of(double cell, int level, int cx, int cy, dsss_reg_result* out, int32_t* usable, int32_t* ncx, int32_t* ncy)
 {
     const double cell_l = ldexp(cell, level);
-    peak_of(sums, radius, std::max(1, min_cells >> (2 * level)), cell_l, out);
     *usable = out->zncc > -2.0 ? 1 : 0;
     if (!*usable) return;                                                       // the no-usable-shift record as it is: no centre is added to it
     out->dx += cx; out->dy += cy;
     const double mx = (double)cx * cell_l, my = (double)cy * cell_l;            // one multiply and one add each, unfused (-ffp-contract=off)
     out->off_x = out->off_x + mx; out->off_y = out->off_y + my;
     if (level > 0) { *ncx = 2 * out->dx; *ncy = 2 * out->dy; }
+}
+int pyr_min_cells(int min_cells, int level) { return std::max(1, min_cells >> (2 * level)); }
+void pyr_step_of(const uint64_t* sums, int radius, int min_cells, double cell, int level, int cx, int cy, dsss_reg_result* out, int32_t* usable,
+                 int32_t* ncx, int32_t* ncy)
+{
+    peak_of(sums, radius, pyr_min_cells(min_cells, level), ldexp(cell, level), out);
+    pyr_centre_of(cell, level, cx, cy, out, usable, ncx, ncy);
 }
 
 // the window of level l that the fine window w covers (only ox, oy, bw, bh differ), moved by (-cx, -cy)
@@ -612,7 +653,9 @@ int dsss_mosaic_register(dsss_ctx* c, const int* ids, int n, const double* rpy6,
     int rc = reg_check(c, ids, n, rpy6, ping_off, p, pair_a, pair_b, npairs, rp, out_host, &R, slot, &rows); if (rc) return rc;
     std::vector<char> used(n, 0);
     for (int k = 0; k < npairs; ++k) used[slot[pair_a[k]]] = used[slot[pair_b[k]]] = 1;
-    if (npairs == 0) return DSSS_OK;
+    reg_count cnt;
+    if (npairs == 0) { c->reg_info = cnt.I; return DSSS_OK; }
+    const bool dev = !sums_host && !dsss_switches_read().reg_peaks_host;       // the peaks on the device: nobody reads the table on the host
     HIPCHK(c, hipSetDevice(c->device));
     const int r = R.radius, S = 2 * r + 1, nshift = S * S;
     // the window of every frame that occurs in a pair: the cells its geo extremes can reach (as the consistency map's)
@@ -631,21 +674,25 @@ int dsss_mosaic_register(dsss_ctx* c, const int* ids, int n, const double* rpy6,
     carve L;
     const size_t o_lay = L.take(lay_cells * 2), o_win = L.take(win_cells * 8), o_jobs = L.take((size_t)n * sizeof(mosaic_job)),
                  o_rows = L.take(rpy6 ? rows * 6 * sizeof(double) : 0), o_pairs = L.take((size_t)npairs * sizeof(reg_job)),
-                 o_tab = L.take((table + 1) * 8);                               // the sums and, behind them, the sample-limit flag: one download
+                 o_tab = L.take((table + 1) * 8),                               // the sums and, behind them, the sample-limit flag: one download
+                 o_rec = L.take(dev ? ((size_t)npairs + 1) * sizeof(dsss_reg_result) : 0);      // device path: the records and, behind them, the flag
     rc = c->mosaic_buf.reserve(c, L.off); if (rc) return rc;
+    if (dev) { rc = c->mosaic_pinned.reserve(c, (size_t)npairs * sizeof(dsss_reg_result) + 8); if (rc) return rc; }
     char* B = c->mosaic_buf.as<char>();
     uint16_t* d_lay = reinterpret_cast<uint16_t*>(B + o_lay);
     unsigned long long* d_win = reinterpret_cast<unsigned long long*>(B + o_win);
     mosaic_job* d_jobs = reinterpret_cast<mosaic_job*>(B + o_jobs);
     reg_job* d_pairs = reinterpret_cast<reg_job*>(B + o_pairs);
     unsigned long long* d_tab = reinterpret_cast<unsigned long long*>(B + o_tab);
-    int* d_flag = reinterpret_cast<int*>(d_tab + table);
+    dsss_reg_result* d_rec = reinterpret_cast<dsss_reg_result*>(B + o_rec);
+    int* d_flag = dev ? reinterpret_cast<int*>(d_rec + npairs) : reinterpret_cast<int*>(d_tab + table);
     std::vector<const double*> dev_rows;
     rc = upload_rows(c, ids, n, rpy6, ping_off, reinterpret_cast<double*>(B + o_rows), dev_rows); if (rc) return rc;
     std::vector<mosaic_job> jobs(n);
     for (int i = 0; i < n; ++i) { const dsss_frame& f = c->frames[ids[i]]; jobs[i] = mosaic_job{ dev_rows[i], f.gr, f.lvl[0], f.mask, f.N, f.M, 0, 0 }; }
     HIPCHK(c, hipMemcpyAsync(d_jobs, jobs.data(), (size_t)n * sizeof(mosaic_job), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemsetAsync(d_tab, 0, (table + 1) * 8, c->stream));
+    if (dev) HIPCHK(c, hipMemsetAsync(d_flag, 0, 8, c->stream));
     // 1. mean layers: scatter into the 64-bit window, pack into the frame's resident u16 layer
     for (int i = 0; i < n; ++i) {
         if (!on_grid[i]) continue;
@@ -665,22 +712,36 @@ int dsss_mosaic_register(dsss_ctx* c, const int* ids, int n, const double* rpy6,
             DSSS_FAIL(c, DSSS_E_ARG, "register: %d pairs are more than one launch takes", npairs);
     }
     rc = reg_launch_corr(c, pj, blocks, d_pairs, r); if (rc) return rc;
+    if (dev) {                                                                  // the records and the flag in one copy; the table stays where it is
+        rc = reg_launch_peaks(c, d_tab, npairs, r, R.min_cells, p->cell, d_rec); if (rc) return rc;
+        const size_t down = (size_t)npairs * sizeof(dsss_reg_result) + 8;
+        HIPCHK(c, hipMemcpyAsync(c->mosaic_pinned.p, d_rec, down, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        cnt.down(down); cnt.sync();
+        const dsss_reg_result* rec = c->mosaic_pinned.as<dsss_reg_result>();
+        if (*reinterpret_cast<const int*>(rec + npairs)) DSSS_FAIL(c, DSSS_E_CAPACITY, "mosaic: a cell received more than 2^24 samples of one frame (cell %g too coarse)", p->cell);
+        memcpy(out_host, rec, (size_t)npairs * sizeof(dsss_reg_result));
+        cnt.I.tables_device = npairs; c->reg_info = cnt.I;
+        return DSSS_OK;
+    }
     std::vector<uint64_t> own;
     uint64_t* tab = nullptr;
     own.resize(table + 1); tab = own.data();
     HIPCHK(c, hipMemcpyAsync(tab, d_tab, (table + 1) * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    cnt.down((table + 1) * 8); cnt.sync();
     if ((int)tab[table]) DSSS_FAIL(c, DSSS_E_CAPACITY, "mosaic: a cell received more than 2^24 samples of one frame (cell %g too coarse)", p->cell);
     for (int k = 0; k < npairs; ++k) peak_of(tab + (size_t)k * nshift * 6, r, R.min_cells, p->cell, out_host + k);
     if (sums_host) memcpy(sums_host, tab, table * 8);
+    cnt.I.tables_host = npairs; c->reg_info = cnt.I;
     return DSSS_OK;
 }
 
 // The segments of frame b against the whole of frame a.  Per frame that occurs as b: ONE segmented scatter into the accumulators of all
 // its segments (each segment its own window, one behind the other) and ONE mosaic_mean_kernel over that whole area, whatever the number
 // of segments and of pairs that name the frame; the layers use the accumulators' offsets, so the pack needs no segment table.  The
-// correlation is mosaic_corr_kernel with one job per (pair, segment); the peaks are decided on the host, then mosaic_centroid_kernel
-// runs once over the rows that have one.
+// correlation is mosaic_corr_kernel with one job per (pair, segment); the peaks are decided by mosaic_peak_kernel behind it (on the
+// host when the sums are asked for), then mosaic_centroid_kernel runs once over the rows that have one.
 int dsss_mosaic_register_segments(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, const dsss_mosaic_params* p,
                                   const int* pair_a, const int* pair_b, int npairs, int seg_pings, const dsss_reg_params* rp,
                                   dsss_reg_seg* out_host, int cap, int* nseg_host, uint64_t* sums_host)
@@ -698,8 +759,10 @@ int dsss_mosaic_register_segments(dsss_ctx* c, const int* ids, int n, const doub
     if (total > 0x7fffffffll) DSSS_FAIL(c, DSSS_E_ARG, "register: %lld segments", total);
     *nseg_host = (int)total;                                                    // also when there is no room for them: the caller learns how many
     if (total > cap) DSSS_FAIL(c, DSSS_E_CAPACITY, "register: %lld segments, room for %d", total, cap);
-    if (total == 0) return DSSS_OK;
+    reg_count cnt;
+    if (total == 0) { c->reg_info = cnt.I; return DSSS_OK; }
     const int nseg = (int)total;
+    const bool dev = !sums_host && !dsss_switches_read().reg_peaks_host;       // the peaks on the device: nobody reads the table on the host
     std::vector<char> as_a(n, 0), as_b(n, 0);
     for (int k = 0; k < npairs; ++k) { as_a[slot[pair_a[k]]] = 1; as_b[slot[pair_b[k]]] = 1; }
     HIPCHK(c, hipSetDevice(c->device));
@@ -735,8 +798,11 @@ int dsss_mosaic_register_segments(dsss_ctx* c, const int* ids, int n, const doub
     const size_t o_lay = L.take(lay_cells * 2), o_win = L.take(win_cells * 8), o_jobs = L.take((size_t)n * sizeof(mosaic_job)),
                  o_rows = L.take(rpy6 ? rows * 6 * sizeof(double) : 0), o_segs = L.take(hseg.size() * sizeof(mosaic_seg)),
                  o_pairs = L.take((size_t)nseg * sizeof(reg_job)), o_cj = L.take((size_t)nseg * sizeof(cen_job)),
-                 o_cen = L.take((size_t)nseg * 3 * 8), o_tab = L.take((table + 1) * 8);      // the sums and, behind them, the sample-limit flag
+                 o_cen = L.take((size_t)nseg * 3 * 8), o_tab = L.take((table + 1) * 8),      // the sums and, behind them, the sample-limit flag
+                 o_rec = L.take(dev ? ((size_t)nseg + 1) * sizeof(dsss_reg_result) : 0);      // device path: the records and, behind them, the flag
     rc = c->mosaic_buf.reserve(c, L.off); if (rc) return rc;
+    const size_t down = dev ? (size_t)nseg * sizeof(dsss_reg_result) + 8 : (table + 1) * 8;      // what comes down behind the correlation
+    rc = c->mosaic_pinned.reserve(c, down); if (rc) return rc;
     char* B = c->mosaic_buf.as<char>();
     uint16_t* d_lay = reinterpret_cast<uint16_t*>(B + o_lay);
     unsigned long long* d_win = reinterpret_cast<unsigned long long*>(B + o_win);
@@ -746,7 +812,8 @@ int dsss_mosaic_register_segments(dsss_ctx* c, const int* ids, int n, const doub
     cen_job* d_cj = reinterpret_cast<cen_job*>(B + o_cj);
     unsigned long long* d_cen = reinterpret_cast<unsigned long long*>(B + o_cen);
     unsigned long long* d_tab = reinterpret_cast<unsigned long long*>(B + o_tab);
-    int* d_flag = reinterpret_cast<int*>(d_tab + table);
+    dsss_reg_result* d_rec = reinterpret_cast<dsss_reg_result*>(B + o_rec);
+    int* d_flag = dev ? reinterpret_cast<int*>(d_rec + nseg) : reinterpret_cast<int*>(d_tab + table);
     std::vector<const double*> dev_rows;
     rc = upload_rows(c, ids, n, rpy6, ping_off, reinterpret_cast<double*>(B + o_rows), dev_rows); if (rc) return rc;
     std::vector<mosaic_job> jobs(n);
@@ -754,6 +821,7 @@ int dsss_mosaic_register_segments(dsss_ctx* c, const int* ids, int n, const doub
     HIPCHK(c, hipMemcpyAsync(d_jobs, jobs.data(), (size_t)n * sizeof(mosaic_job), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(d_segs, hseg.data(), hseg.size() * sizeof(mosaic_seg), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemsetAsync(d_tab, 0, (table + 1) * 8, c->stream));
+    if (dev) HIPCHK(c, hipMemsetAsync(d_flag, 0, 8, c->stream));
     HIPCHK(c, hipMemsetAsync(d_cen, 0, (size_t)nseg * 3 * 8, c->stream));
     // 1. mean layers: a frame's whole layer where it is an a, the layers of all its segments (one scatter, one pack) where it is a b
     const mosaic_win grid{ p->x0, p->y0, p->cell, p->W, p->H, 0, 0, 0, 0, p->use_mask != 0 };
@@ -793,17 +861,21 @@ int dsss_mosaic_register_segments(dsss_ctx* c, const int* ids, int n, const doub
         }
     }
     rc = reg_launch_corr(c, pj, blocks, d_pairs, r); if (rc) return rc;
-    rc = c->mosaic_pinned.reserve(c, (table + 1) * 8); if (rc) return rc;
-    const uint64_t* tab = c->mosaic_pinned.as<uint64_t>();
-    HIPCHK(c, hipMemcpyAsync(c->mosaic_pinned.p, d_tab, (table + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    if (dev) { rc = reg_launch_peaks(c, d_tab, nseg, r, R.min_cells, p->cell, d_rec); if (rc) return rc; }
+    const uint64_t* tab = c->mosaic_pinned.as<uint64_t>();                      // host path: the table and the flag
+    const dsss_reg_result* rec = c->mosaic_pinned.as<dsss_reg_result>();        // device path: the records and the flag
+    HIPCHK(c, hipMemcpyAsync(c->mosaic_pinned.p, dev ? (const void*)d_rec : (const void*)d_tab, down, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if ((int)tab[table]) DSSS_FAIL(c, DSSS_E_CAPACITY, "mosaic: a cell received more than 2^24 samples of one frame (cell %g too coarse)", p->cell);
-    // 3. peaks on the host, then the centroid sums of the rows that have one: one launch, one download
+    cnt.down(down); cnt.sync();
+    if (dev ? *reinterpret_cast<const int*>(rec + nseg) : (int)tab[table])
+        DSSS_FAIL(c, DSSS_E_CAPACITY, "mosaic: a cell received more than 2^24 samples of one frame (cell %g too coarse)", p->cell);
+    (dev ? cnt.I.tables_device : cnt.I.tables_host) = nseg;
+    // 3. the peaks (the device's records, or decided here from the table), then the centroid sums of the rows that have one: one launch, one download
     std::vector<cen_job> cj;
     long long cblocks = 0;
     for (row = 0; row < nseg; ++row) {
         dsss_reg_result& q = out_host[row].r;
-        peak_of(tab + (size_t)row * nshift * 6, r, R.min_cells, p->cell, &q);
+        if (dev) q = rec[row]; else peak_of(tab + (size_t)row * nshift * 6, r, R.min_cells, p->cell, &q);
         if (!(q.zncc > -2.0)) continue;                                         // no usable shift: sx = sy = 0
         if (!cen_push_job(cj, &cblocks, d_lay + lay_off[row_a[row]], wins[row_a[row]], d_lay + seg_lay[slot[pair_b[out_host[row].pair]]] + hseg[row_g[row]].off,
                           sw[row_g[row]], q, d_cen + (size_t)row * 3))
@@ -811,7 +883,7 @@ int dsss_mosaic_register_segments(dsss_ctx* c, const int* ids, int n, const doub
     }
     if (!cj.empty()) {
         std::vector<uint64_t> cen((size_t)nseg * 3);
-        rc = reg_launch_centroids(c, cj, cblocks, d_cj, d_cen, cen); if (rc) return rc;
+        rc = reg_launch_centroids(c, cj, cblocks, d_cj, d_cen, cen, cnt); if (rc) return rc;
         for (row = 0; row < nseg; ++row) {
             dsss_reg_seg& o = out_host[row];
             if (!(o.r.zncc > -2.0)) continue;
@@ -822,6 +894,7 @@ int dsss_mosaic_register_segments(dsss_ctx* c, const int* ids, int n, const doub
         }
     }
     if (sums_host) memcpy(sums_host, tab, table * 8);
+    c->reg_info = cnt.I;
     return DSSS_OK;
 }
 
@@ -865,9 +938,10 @@ int dsss_register_yaw_peak(const dsss_reg_result* per_angle, int nyaw, double st
 // dsss_mosaic_register_segments under every angle of the fan.  Per frame that occurs as b: ONE memset, ONE mosaic_scatter_fan_kernel into
 // the accumulators of all its (segment, angle) windows and ONE mosaic_mean_kernel over that whole area; the windows of the rotated
 // segments come from the host's twin of the kernel's rotation (rotate_rows -> dsss_rotate_row).  The correlation runs in PASSES, one
-// per angle, each mosaic_corr_kernel with one job per (pair, segment) and one download of a table of ONE angle's size: the
-// page-locked landing area stays what the translation-only call needs instead of nyaw times that, and the peaks of a pass are
-// decided on the host while nothing else needs the host.  The centroid runs once, for the chosen angle of every row.
+// per angle, each mosaic_corr_kernel with one job per (pair, segment) and one download: of that angle's records (mosaic_peak_kernel),
+// or, when the sums are asked for, of a table of ONE angle's size, whose peaks the host decides -- the page-locked landing area stays
+// what the translation-only call needs instead of nyaw times that.  The angle rule is the host's on both paths.  The centroid runs
+// once, for the chosen angle of every row.
 int dsss_mosaic_register_segments_yaw(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, const dsss_mosaic_params* p,
                                       const int* pair_a, const int* pair_b, int npairs, int seg_pings, const dsss_reg_params* rp,
                                       const dsss_reg_yaw_params* yp, dsss_reg_seg_yaw* out_host, int cap, int* nseg_host, uint64_t* sums_host)
@@ -893,8 +967,10 @@ int dsss_mosaic_register_segments_yaw(dsss_ctx* c, const int* ids, int n, const 
     if (total > 0x7fffffffll) DSSS_FAIL(c, DSSS_E_ARG, "register: %lld segments", total);
     *nseg_host = (int)total;                                                    // also when there is no room for them: the caller learns how many
     if (total > cap) DSSS_FAIL(c, DSSS_E_CAPACITY, "register: %lld segments, room for %d", total, cap);
-    if (total == 0) return DSSS_OK;
+    reg_count cnt;
+    if (total == 0) { c->reg_info = cnt.I; return DSSS_OK; }
     const int nseg = (int)total;
+    const bool dev = !sums_host && !dsss_switches_read().reg_peaks_host;       // the peaks on the device: nobody reads the table on the host
     std::vector<char> as_a(n, 0), as_b(n, 0);
     for (int k = 0; k < npairs; ++k) { as_a[slot[pair_a[k]]] = 1; as_b[slot[pair_b[k]]] = 1; }
     const int r = R.radius, S = 2 * r + 1, nshift = S * S;
@@ -940,9 +1016,11 @@ int dsss_mosaic_register_segments_yaw(dsss_ctx* c, const int* ids, int n, const 
     const size_t o_lay = L.take(lay_cells * 2), o_win = L.take(win_cells * 8), o_jobs = L.take((size_t)n * sizeof(mosaic_job)),
                  o_rows = L.take(rpy6 ? rows * 6 * sizeof(double) : 0), o_fan = L.take(hfan.size() * sizeof(mosaic_fan)),
                  o_pairs = L.take((size_t)nseg * sizeof(reg_job)), o_cj = L.take((size_t)nseg * sizeof(cen_job)),
-                 o_cen = L.take((size_t)nseg * 3 * 8), o_tab = L.take((table + 1) * 8);      // the sums and, behind them, the sample-limit flag
+                 o_cen = L.take((size_t)nseg * 3 * 8), o_tab = L.take((table + 1) * 8),      // the sums and, behind them, the sample-limit flag
+                 o_rec = L.take(dev ? ((size_t)nseg + 1) * sizeof(dsss_reg_result) : 0);      // device path: one angle's records and, behind them, the flag
     rc = c->mosaic_buf.reserve(c, L.off); if (rc) return rc;
-    rc = c->mosaic_pinned.reserve(c, (table + 1) * 8); if (rc) return rc;
+    const size_t down = dev ? (size_t)nseg * sizeof(dsss_reg_result) + 8 : (table + 1) * 8;      // what comes down per pass
+    rc = c->mosaic_pinned.reserve(c, down); if (rc) return rc;
     char* B = c->mosaic_buf.as<char>();
     uint16_t* d_lay = reinterpret_cast<uint16_t*>(B + o_lay);
     unsigned long long* d_win = reinterpret_cast<unsigned long long*>(B + o_win);
@@ -952,7 +1030,8 @@ int dsss_mosaic_register_segments_yaw(dsss_ctx* c, const int* ids, int n, const 
     cen_job* d_cj = reinterpret_cast<cen_job*>(B + o_cj);
     unsigned long long* d_cen = reinterpret_cast<unsigned long long*>(B + o_cen);
     unsigned long long* d_tab = reinterpret_cast<unsigned long long*>(B + o_tab);
-    int* d_flag = reinterpret_cast<int*>(d_tab + table);
+    dsss_reg_result* d_rec = reinterpret_cast<dsss_reg_result*>(B + o_rec);
+    int* d_flag = dev ? reinterpret_cast<int*>(d_rec + nseg) : reinterpret_cast<int*>(d_tab + table);
     // the rows and every pass's jobs, laid out by pair and then by segment, before anything is launched: what one launch cannot take
     // is refused here.  A row's centroid region lies inside the correlation region of its angle, so the largest of those bounds it.
     memset(out_host, 0, (size_t)nseg * sizeof(dsss_reg_seg_yaw));
@@ -1012,15 +1091,21 @@ int dsss_mosaic_register_segments_yaw(dsss_ctx* c, const int* ids, int n, const 
         }
     }
     // 2. one pass per angle: the table cleared, one correlation job per (pair, segment), one download, the records of the angle
-    const uint64_t* tab = c->mosaic_pinned.as<uint64_t>();
+    const uint64_t* tab = c->mosaic_pinned.as<uint64_t>();                      // host path: the table and the flag
+    const dsss_reg_result* rec = c->mosaic_pinned.as<dsss_reg_result>();        // device path: the records and the flag
     std::vector<dsss_reg_result> per((size_t)nseg * nyaw);
     for (int a = 0; a < nyaw; ++a) {
         HIPCHK(c, hipMemsetAsync(d_tab, 0, table * 8, c->stream));
         rc = reg_launch_corr(c, pj[a], blocks[a], d_pairs, r); if (rc) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->mosaic_pinned.p, d_tab, (table + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+        if (dev) { rc = reg_launch_peaks(c, d_tab, nseg, r, R.min_cells, p->cell, d_rec); if (rc) return rc; }
+        HIPCHK(c, hipMemcpyAsync(c->mosaic_pinned.p, dev ? (const void*)d_rec : (const void*)d_tab, down, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        if ((int)tab[table]) DSSS_FAIL(c, DSSS_E_CAPACITY, "mosaic: a cell received more than 2^24 samples of one frame (cell %g too coarse)", p->cell);
+        cnt.down(down); cnt.sync();
+        if (dev ? *reinterpret_cast<const int*>(rec + nseg) : (int)tab[table])
+            DSSS_FAIL(c, DSSS_E_CAPACITY, "mosaic: a cell received more than 2^24 samples of one frame (cell %g too coarse)", p->cell);
+        (dev ? cnt.I.tables_device : cnt.I.tables_host) += nseg;
         for (row = 0; row < nseg; ++row) {
+            if (dev) { per[(size_t)row * nyaw + a] = rec[row]; continue; }
             peak_of(tab + (size_t)row * nshift * 6, r, R.min_cells, p->cell, &per[(size_t)row * nyaw + a]);
             if (sums_host) memcpy(sums_host + ((size_t)row * nyaw + a) * nshift * 6, tab + (size_t)row * nshift * 6, (size_t)nshift * 6 * 8);
         }
@@ -1041,7 +1126,7 @@ int dsss_mosaic_register_segments_yaw(dsss_ctx* c, const int* ids, int n, const 
     }
     if (!cj.empty()) {
         std::vector<uint64_t> cen((size_t)nseg * 3);
-        rc = reg_launch_centroids(c, cj, cblocks, d_cj, d_cen, cen); if (rc) return rc;
+        rc = reg_launch_centroids(c, cj, cblocks, d_cj, d_cen, cen, cnt); if (rc) return rc;
         for (row = 0; row < nseg; ++row) {
             dsss_reg_seg& o = out_host[row].s;
             if (!(o.r.zncc > -2.0)) continue;
@@ -1051,6 +1136,7 @@ int dsss_mosaic_register_segments_yaw(dsss_ctx* c, const int* ids, int n, const 
             o.sx = (int64_t)cen[(size_t)row * 3 + 1]; o.sy = (int64_t)cen[(size_t)row * 3 + 2];
         }
     }
+    c->reg_info = cnt.I;
     return DSSS_OK;
 }
 
@@ -1100,8 +1186,9 @@ int dsss_register_pyr_step(const uint64_t* sums, int radius, int min_cells, doub
 // dsss_mosaic_register_segments coarse to fine.  Per frame: ONE memset, the unchanged scatter kernels into the accumulators of its whole
 // window (where it is an a) and of all its segments (where it is a b), and ONE mosaic_pyr_kernel over all those areas that writes
 // the layers of every level; the layers of all levels stay resident.  Per level, from the top: mosaic_corr_kernel with one job per row
-// that is still alive (the segment's window moved by minus the row's centre), one download of that level's tables, the level rule on
-// the host (pyr_step_of).  mosaic_centroid_kernel runs once, at the total shift, for the rows that finished at level 0.  What one
+// that is still alive (the segment's window moved by minus the row's centre), one download -- of the records of the live rows, whose
+// tables then lie one behind the other (mosaic_peak_kernel with the level's radius, min_cells and cell), or of that level's tables of
+// all rows when the sums are asked for -- and the level rule on the host (pyr_step_of; on the device path its second part, pyr_centre_of).  mosaic_centroid_kernel runs once, at the total shift, for the rows that finished at level 0.  What one
 // launch cannot take is bounded and refused before anything is launched.
 int dsss_mosaic_register_segments_pyr(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, const dsss_mosaic_params* p,
                                       const int* pair_a, const int* pair_b, int npairs, int seg_pings, const dsss_reg_params* rp,
@@ -1124,8 +1211,10 @@ int dsss_mosaic_register_segments_pyr(dsss_ctx* c, const int* ids, int n, const 
     if (total > 0x7fffffffll) DSSS_FAIL(c, DSSS_E_ARG, "register: %lld segments", total);
     *nseg_host = (int)total;                                                    // also when there is no room for them: the caller learns how many
     if (total > cap) DSSS_FAIL(c, DSSS_E_CAPACITY, "register: %lld segments, room for %d", total, cap);
-    if (total == 0) return DSSS_OK;
+    reg_count cnt;
+    if (total == 0) { c->reg_info = cnt.I; return DSSS_OK; }
     const int nseg = (int)total;
+    const bool dev = !sums_host && !dsss_switches_read().reg_peaks_host;       // the peaks on the device: nobody reads the table on the host
     std::vector<char> as_a(n, 0), as_b(n, 0);
     for (int k = 0; k < npairs; ++k) { as_a[slot[pair_a[k]]] = 1; as_b[slot[pair_b[k]]] = 1; }
     auto radius_of = [&](int l) { return l == L - 1 ? R.radius : P.refine; };
@@ -1210,9 +1299,10 @@ int dsss_mosaic_register_segments_pyr(dsss_ctx* c, const int* ids, int n, const 
     const size_t o_lay = Cv.take(lay_cells * 2), o_win = Cv.take(win_cells * 8), o_jobs = Cv.take((size_t)n * sizeof(mosaic_job)),
                  o_rows = Cv.take(rpy6 ? rows * 6 * sizeof(double) : 0), o_segs = Cv.take(hseg.size() * sizeof(mosaic_seg)),
                  o_pj = Cv.take(hpj.size() * sizeof(pyr_job)), o_pairs = Cv.take((size_t)nseg * sizeof(reg_job)), o_cj = Cv.take((size_t)nseg * sizeof(cen_job)),
-                 o_cen = Cv.take((size_t)nseg * 3 * 8), o_tab = Cv.take((1 + table_max) * 8);      // the sample-limit flag and, behind it, one level's sums
+                 o_cen = Cv.take((size_t)nseg * 3 * 8), o_tab = Cv.take((1 + table_max) * 8),      // the sample-limit flag and, behind it, one level's sums
+                 o_rec = Cv.take(dev ? ((size_t)nseg + 1) * sizeof(dsss_reg_result) : 0);      // device path: the flag in the last 8 bytes of a first record's room, behind it one level's records
     rc = c->mosaic_buf.reserve(c, Cv.off); if (rc) return rc;
-    rc = c->mosaic_pinned.reserve(c, (1 + table_max) * 8); if (rc) return rc;
+    rc = c->mosaic_pinned.reserve(c, dev ? 8 + (size_t)nseg * sizeof(dsss_reg_result) : (1 + table_max) * 8); if (rc) return rc;
     char* B = c->mosaic_buf.as<char>();
     uint16_t* d_lay = reinterpret_cast<uint16_t*>(B + o_lay);
     unsigned long long* d_win = reinterpret_cast<unsigned long long*>(B + o_win);
@@ -1223,7 +1313,8 @@ int dsss_mosaic_register_segments_pyr(dsss_ctx* c, const int* ids, int n, const 
     cen_job* d_cj = reinterpret_cast<cen_job*>(B + o_cj);
     unsigned long long* d_cen = reinterpret_cast<unsigned long long*>(B + o_cen);
     unsigned long long* d_tab = reinterpret_cast<unsigned long long*>(B + o_tab) + 1;
-    int* d_flag = reinterpret_cast<int*>(B + o_tab);
+    dsss_reg_result* d_rec = reinterpret_cast<dsss_reg_result*>(B + o_rec) + 1;
+    int* d_flag = dev ? reinterpret_cast<int*>(reinterpret_cast<char*>(d_rec) - 8) : reinterpret_cast<int*>(B + o_tab);
     std::vector<const double*> dev_rows;
     rc = upload_rows(c, ids, n, rpy6, ping_off, reinterpret_cast<double*>(B + o_rows), dev_rows); if (rc) return rc;
     std::vector<mosaic_job> jobs(n);
@@ -1244,26 +1335,49 @@ int dsss_mosaic_register_segments_pyr(dsss_ctx* c, const int* ids, int n, const 
         HIPCHK(c, hipGetLastError());
     }
     // 2. level by level from the top: the rows still alive around their centres, one launch, one download, the level rule on the host
-    const uint64_t* tab = c->mosaic_pinned.as<uint64_t>() + 1;
+    const uint64_t* tab = c->mosaic_pinned.as<uint64_t>() + 1;                  // the flag is tab[-1] on both paths
+    const dsss_reg_result* rec = reinterpret_cast<const dsss_reg_result*>(tab); // device path: the records of the level's live rows, in their order
+    std::vector<int> live; live.reserve(nseg);                                  // device path: the rows still alive, whose tables lie one behind the other
     const size_t row_sums = (nshift_of(L - 1) + (size_t)(L - 1) * nshift_of(0)) * 6;
     std::vector<char> alive(nseg, 1); std::vector<int32_t> cx(nseg, 0), cy(nseg, 0);
     std::vector<reg_job> pj; pj.reserve(nseg);
     for (int l = L - 1; l >= 0; --l) {
         const int r = radius_of(l); const size_t tsz = nshift_of(l) * 6;
-        pj.clear();
+        pj.clear(); live.clear();
         long long blocks = 0;
         for (int row = 0; row < nseg; ++row) {
             const int ia = row_a[row], g = row_g[row];
-            if (!alive[row] || !on_grid[ia] || sw[g].bw == 0) continue;
+            if (!alive[row]) continue;
+            const size_t at_tab = dev ? live.size() : (size_t)row;              // host path: every row keeps its place
+            live.push_back(row);                                                // (a live row off the grid has no job: its table stays zero)
+            if (!on_grid[ia] || sw[g].bw == 0) continue;
             if (!reg_push_job(pj, &blocks, d_lay + a_lay[ia].off[l], pyr_window(wins[ia], l, 0, 0), d_lay + seg_lay[g].off[l], pyr_window(sw[g], l, cx[row], cy[row]),
-                              r, d_tab + (size_t)row * tsz))
+                              r, d_tab + at_tab * tsz))
                 DSSS_FAIL(c, DSSS_E_NUMERIC, "register: internal error, level %d of %d segments takes more workgroups than was bounded", l, nseg);
         }
-        HIPCHK(c, hipMemsetAsync(d_tab, 0, (size_t)nseg * tsz * 8, c->stream));
+        const size_t ntab = dev ? live.size() : (size_t)nseg;
+        const size_t down = dev ? 8 + ntab * sizeof(dsss_reg_result) : (1 + ntab * tsz) * 8;
+        HIPCHK(c, hipMemsetAsync(d_tab, 0, ntab * tsz * 8, c->stream));
         rc = reg_launch_corr(c, pj, blocks, d_pairs, r); if (rc) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->mosaic_pinned.p, d_flag, (1 + (size_t)nseg * tsz) * 8, hipMemcpyDeviceToHost, c->stream));
+        if (dev) { rc = reg_launch_peaks(c, d_tab, (long long)ntab, r, pyr_min_cells(R.min_cells, l), ldexp(p->cell, l), d_rec); if (rc) return rc; }
+        HIPCHK(c, hipMemcpyAsync(c->mosaic_pinned.p, d_flag, down, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
+        cnt.down(down); cnt.sync();
         if ((int)tab[-1]) DSSS_FAIL(c, DSSS_E_CAPACITY, "mosaic: a cell received more than 2^24 samples of one frame (cell %g too coarse)", p->cell);
+        (dev ? cnt.I.tables_device : cnt.I.tables_host) += (int64_t)live.size();
+        if (dev) {                                                              // the level rule's centre on the downloaded records
+            for (size_t k = 0; k < live.size(); ++k) {
+                const int row = live[k];
+                dsss_reg_seg_pyr& o = out_host[row];
+                dsss_reg_result q = rec[k]; int32_t usable = 0, nx = 0, ny = 0;
+                pyr_centre_of(p->cell, l, cx[row], cy[row], &q, &usable, &nx, &ny);
+                if (!usable) { alive[row] = 0; if (l == L - 1) o.s.r = q; continue; }
+                o.s.r = q; o.level = l; o.lx[l] = q.dx; o.ly[l] = q.dy; o.lz[l] = q.zncc;
+                if (q.on_border) o.border_mask |= 1 << l;
+                cx[row] = nx; cy[row] = ny;
+            }
+            continue;
+        }
         const size_t at = l == L - 1 ? 0 : (nshift_of(L - 1) + (size_t)(L - 2 - l) * nshift_of(0)) * 6;      // this level's table within a row of sums_host
         for (int row = 0; row < nseg; ++row) {
             if (sums_host) {
@@ -1293,7 +1407,7 @@ int dsss_mosaic_register_segments_pyr(dsss_ctx* c, const int* ids, int n, const 
     }
     if (!cj.empty()) {
         std::vector<uint64_t> cen((size_t)nseg * 3);
-        rc = reg_launch_centroids(c, cj, cblocks, d_cj, d_cen, cen); if (rc) return rc;
+        rc = reg_launch_centroids(c, cj, cblocks, d_cj, d_cen, cen, cnt); if (rc) return rc;
         for (int row = 0; row < nseg; ++row) {
             dsss_reg_seg& o = out_host[row].s;
             if (out_host[row].level != 0) continue;
@@ -1303,6 +1417,50 @@ int dsss_mosaic_register_segments_pyr(dsss_ctx* c, const int* ids, int n, const 
             o.sx = (int64_t)cen[(size_t)row * 3 + 1]; o.sy = (int64_t)cen[(size_t)row * 3 + 2];
         }
     }
+    c->reg_info = cnt.I;
+    return DSSS_OK;
+}
+
+// ---- peaks on the device: the public batched entry and what the last call did
+int dsss_mosaic_register_peaks(dsss_ctx* c, const uint64_t* sums, int64_t ntables, int radius, int min_cells, double cell, dsss_reg_result* out_host)
+{
+    if (!c) return DSSS_E_ARG;
+    if (ntables < 0) DSSS_FAIL(c, DSSS_E_ARG, "register: ntables = %lld", (long long)ntables);
+    if (ntables > 0 && (!sums || !out_host)) DSSS_FAIL(c, DSSS_E_ARG, "register: %lld tables without %s", (long long)ntables, sums ? "a result array" : "their sums");
+    if (radius < 0 || radius > REG_MAX_RADIUS) DSSS_FAIL(c, DSSS_E_ARG, "register: radius %d outside 0..%d", radius, REG_MAX_RADIUS);
+    if (min_cells < 1) DSSS_FAIL(c, DSSS_E_ARG, "register: min_cells = %d", min_cells);
+    if (!(cell > 0.0) || !std::isfinite(cell)) DSSS_FAIL(c, DSSS_E_ARG, "register: cell = %g", cell);
+    reg_count cnt;
+    if (ntables == 0) { c->reg_info = cnt.I; return DSSS_OK; }
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t tsz = (size_t)(2 * radius + 1) * (2 * radius + 1) * 6, nt = (size_t)ntables;
+    hipPointerAttribute_t at;
+    const bool on_dev = (hipPointerGetAttributes(&at, sums) == hipSuccess) && at.type == hipMemoryTypeDevice;
+    (void)hipGetLastError();
+    carve L;
+    const size_t o_rec = L.take(nt * sizeof(dsss_reg_result)), o_tab = L.take(on_dev ? 0 : nt * tsz * 8);      // host tables go up into mosaic_buf
+    int rc = c->mosaic_buf.reserve(c, L.off); if (rc) return rc;
+    rc = c->mosaic_pinned.reserve(c, nt * sizeof(dsss_reg_result)); if (rc) return rc;
+    char* B = c->mosaic_buf.as<char>();
+    dsss_reg_result* d_rec = reinterpret_cast<dsss_reg_result*>(B + o_rec);
+    const unsigned long long* d_tab = reinterpret_cast<const unsigned long long*>(sums);
+    if (!on_dev) {
+        HIPCHK(c, hipMemcpyAsync(B + o_tab, sums, nt * tsz * 8, hipMemcpyHostToDevice, c->stream));
+        d_tab = reinterpret_cast<const unsigned long long*>(B + o_tab);
+    }
+    rc = reg_launch_peaks(c, d_tab, ntables, radius, min_cells, cell, d_rec); if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->mosaic_pinned.p, d_rec, nt * sizeof(dsss_reg_result), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    cnt.down(nt * sizeof(dsss_reg_result)); cnt.sync();
+    memcpy(out_host, c->mosaic_pinned.p, nt * sizeof(dsss_reg_result));
+    cnt.I.tables_device = ntables; c->reg_info = cnt.I;
+    return DSSS_OK;
+}
+
+int dsss_mosaic_register_info(const dsss_ctx* c, dsss_reg_call_info* out)
+{
+    if (!c || !out) return DSSS_E_ARG;
+    *out = c->reg_info;
     return DSSS_OK;
 }
 

@@ -544,6 +544,28 @@ int  dsss_mosaic_register_segments_pyr(dsss_ctx*, const int* ids, int n, const d
                                        const dsss_reg_pyr_params*, dsss_reg_seg_pyr* out_host, int cap, int* nseg_host,
                                        uint64_t* sums_host /* nseg x ((2r+1)^2 + (levels-1) (2 refine+1)^2) x 6, may be NULL */);
 
+/* ---- peaks on the device.  The peak rule is a pure function of a table's integer sums, so it is evaluated where the table lies:
+ * mosaic_peak_kernel turns every table into its 64-byte record on the device, and the four registration entries above download records
+ * instead of tables whenever the caller did not ask for the sums (sums_host == NULL).  The records are bit for bit those of
+ * dsss_mosaic_register_peak: one body of the score, order and parabola rules is compiled for host and device, and everything in it is
+ * an IEEE-754 basic operation.  With sums_host the table comes down anyway and the host decides, as before.  The environment switch
+ * DSSS_REG_PEAKS=host, read once per call, forces that path without sums_host (an A/B switch; any other value: the rule above).   */
+/* dsss_mosaic_register_peak's rules on ntables tables at once, on the device.
+ * sums: ntables x (2 radius + 1)^2 x 6, host or device memory.
+ * out_host[k] is bit for bit the record dsss_mosaic_register_peak gives for table k (pad_ = 0).
+ * ntables == 0 is valid and launches nothing. Any rank may call it (no frames involved).
+ * DSSS_E_ARG, decided before anything is launched: NULL sums or out_host with ntables > 0,
+ * ntables < 0, radius outside 0..16, min_cells < 1, cell <= 0 or not finite.            */
+int  dsss_mosaic_register_peaks(dsss_ctx*, const uint64_t* sums, int64_t ntables, int radius,
+                                int min_cells, double cell, dsss_reg_result* out_host);
+typedef struct { int64_t tables_device, tables_host, bytes_down, syncs; } dsss_reg_call_info;
+/* the last dsss_mosaic_register* / dsss_mosaic_register_peaks call of this context that returned DSSS_OK:
+ * tables scored by mosaic_peak_kernel / by the host; bytes the call copied device -> host;
+ * stream synchronisations it made. Zeros before any such call.  Counted from the sizes of the copies the call enqueues and from
+ * the synchronisations written in the entry, not measured (a synchronisation that a growing buffer makes is not among them).
+ * DSSS_E_ARG: a NULL pointer.                                                                                                 */
+int  dsss_mosaic_register_info(const dsss_ctx*, dsss_reg_call_info* out);
+
 /* ------------------------------------------------------------------ instrumentation
  * accumulated GPU time (ms, HIP events on the context stream) and launch count per kernel family        */
 #define DSSS_K_ROW_REDUCE   0   /* row_reduce_kernel: one f64 read of the waterfall */

@@ -3,7 +3,7 @@
 solved trajectory (dsss_mosaic_register_segments), the accepted offsets become pose-graph edges (dsss_mosaic_register_edges), the
 trajectory is solved again with them next to the feature-based closures, and the segments are registered once more under the result.
     python tools/dense_closures.py --frames 200 --rows 2000 --cols 1024 --cell 0.1 [--seg-pings 80] [--radius 8] [--calls 5] [--timeout 1500]
-                                   [--yaw-fan NYAW [--yaw-step RAD]] [--pyramid L [--refine RHO]]
+                                   [--yaw-fan NYAW [--yaw-step RAD]] [--pyramid L [--refine RHO]] [--peaks-ab]
 Steps: 1. pipeline and dsss_posegraph_solve; 2. segments under the solved trajectory; 3. edges; 4. the edges of dsss_posegraph_select
 with the new ones behind them; 5. dsss_posegraph_solve_edges on the frames' dead-reckoning rows; 6. segments under the result.
 Prints one JSON line: segments and accepted edges; median and 95th percentile of |offset| in metres over the segments with a peak, the
@@ -20,6 +20,11 @@ dsss_mosaic_register_edges.  Under every trajectory that is registered (with --p
 the rows per level, the rows with a border bit, the median and 95th percentile of the total shift in cells over the rows that finished at
 level 0, and the flat call's on_border count on the same pairs in the same process; and the wall time of the pyramid call next to the
 flat segment call's.
+--peaks-ab measures where the peaks are decided instead of steps 2 to 6: for each registration call timed here (the flat segment call,
+and the fan's or the pyramid's when asked for) it alternates, in this one process, the host path (DSSS_REG_PEAKS=host, read per call)
+and the device path: one warm-up of each, then --calls rounds of host, device, host, each call synchronised and timed with a host clock.
+It reports median and minimum per path, the host path's spread against itself (the two interleaved host series), and per path the
+bytes copied down and the synchronisations (dsss_mosaic_register_info), and asserts the rows of both paths identical as bytes.
 The GPU work runs in a child process under a time limit (--timeout seconds); this process never opens the device."""
 import argparse
 import json
@@ -36,6 +41,7 @@ ap.add_argument("--radius", type=int, default=8); ap.add_argument("--min-cells",
 ap.add_argument("--yaw-fan", type=int, default=1); ap.add_argument("--yaw-step", type=float, default=0.01)
 ap.add_argument("--pyramid", type=int, default=1); ap.add_argument("--refine", type=int, default=3)
 ap.add_argument("--calls", type=int, default=5); ap.add_argument("--timeout", type=float, default=1500.0)
+ap.add_argument("--peaks-ab", action="store_true")
 ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)
 a = ap.parse_args()
 if a.calls < 5:
@@ -137,6 +143,41 @@ def rows_of(poses12):
     return np.ascontiguousarray(np.stack([np.arctan2(P[:, 7], P[:, 8]), np.arctan2(-P[:, 6], np.hypot(P[:, 7], P[:, 8])), np.arctan2(P[:, 3], P[:, 0]),
                                           P[:, 9], P[:, 10], P[:, 11]], 1))
 
+
+def peaks_ab(fn):
+    """host path against device path of one registration call, interleaved in this process"""
+    def run(host):
+        if host:
+            os.environ["DSSS_REG_PEAKS"] = "host"
+        try:
+            t0 = time.perf_counter(); rows = fn(); dt = time.perf_counter() - t0
+        finally:
+            os.environ.pop("DSSS_REG_PEAKS", None)
+        return dt, rows.tobytes(), ctx.mosaic_register_info()
+    _, want, ih = run(True)
+    _, got, idv = run(False)
+    assert ih.tables_device == 0 and idv.tables_host == 0 and idv.tables_device == ih.tables_host
+    ts = dict(host_a=[], device=[], host_b=[])
+    for _ in range(a.calls):
+        for key in ("host_a", "device", "host_b"):
+            dt, rows, _i = run(key != "device")
+            assert rows == want, "peaks-ab: the rows of the %s path differ" % key
+            ts[key].append(1e3 * dt)
+    assert got == want
+    out = dict(runs=a.calls, tables=int(ih.tables_host))
+    for key, v in ts.items():
+        out[key + "_ms_median"] = round(float(np.median(v)), 3); out[key + "_ms_min"] = round(min(v), 3)
+    out["host_spread_ms"] = round(abs(out["host_a_ms_median"] - out["host_b_ms_median"]), 3)
+    out.update(host_bytes_down=int(ih.bytes_down), device_bytes_down=int(idv.bytes_down), host_syncs=int(ih.syncs), device_syncs=int(idv.syncs))
+    return out
+
+
+if a.peaks_ab:
+    ab = dict(segments=peaks_ab(lambda: ctx.mosaic_register_segments(ids, p, pairs, a.seg_pings, reg=reg, rpy6=rpy, ping_off=off)))
+    if PYR or FAN:
+        ab["segments_pyr" if PYR else "segments_yaw"] = peaks_ab(lambda: register(rpy))
+    res["peaks_ab"] = ab
+    print(json.dumps(res)); pipe.close(); sys.exit(0)
 
 res["segments_ms"], res["segments_ms_min"] = timed(lambda: ctx.mosaic_register_segments(ids, p, pairs, a.seg_pings, reg=reg, rpy6=rpy, ping_off=off))
 res["whole_frame_ms"], res["whole_frame_ms_min"] = timed(lambda: ctx.mosaic_register(ids, p, pairs, reg=reg, rpy6=rpy, ping_off=off))
