@@ -350,6 +350,12 @@ def mosaic_grid(bbox4, cell):
     return p
 
 
+def _reg_pairs(pairs):
+    """[(a, b), ...] -> (the pairs as an n x 2 int32 array, their a column, their b column), each contiguous"""
+    pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+    return pairs, np.ascontiguousarray(pairs[:, 0]), np.ascontiguousarray(pairs[:, 1])
+
+
 def reg_params_default():
     r = RegParams(); lib().dsss_reg_params_default(C.byref(r)); return r
 
@@ -912,8 +918,7 @@ class Context:
         in cells, the offset in metres that b lies from where the overlap says it belongs, ZNCC and cells at the peak and at zero shift.
         want_sums=True returns (rows, sums) with sums[npairs, 2 r + 1, 2 r + 1, 6] uint64 (dy, dx; n, Sa, Sb, Sab, Saa, Sbb)."""
         ids, rpy6, ping_off = self._mosaic_traj(ids, rpy6, ping_off)
-        pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
-        pa = np.ascontiguousarray(pairs[:, 0]); pb = np.ascontiguousarray(pairs[:, 1])
+        pairs, pa, pb = _reg_pairs(pairs)
         r = reg if reg is not None else reg_params_default()
         S = 2 * max(0, min(int(r.radius), 16)) + 1
         out = np.zeros(len(pairs), REG_DTYPE)
@@ -928,82 +933,68 @@ class Context:
         record r of the segment's table, and the centroid sums sx, sy of the overlapping cells at the peak.  want_sums=True returns
         (rows, sums) with sums[nseg, 2 r + 1, 2 r + 1, 6] uint64.  cap: room for that many rows (None: as many as there will be)."""
         ids, rpy6, ping_off = self._mosaic_traj(ids, rpy6, ping_off)
-        pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
-        pa = np.ascontiguousarray(pairs[:, 0]); pb = np.ascontiguousarray(pairs[:, 1])
+        pairs, pa, pb = _reg_pairs(pairs)
         r = reg if reg is not None else reg_params_default()
         S = 2 * max(0, min(int(r.radius), 16)) + 1
         args = (self.h, _ptr(ids), len(ids), _ptr(rpy6), _ptr(ping_off), C.byref(params), _ptr(pa), _ptr(pb), len(pairs), int(seg_pings), C.byref(r))
+        return self._reg_segment_rows(self.L.dsss_mosaic_register_segments, "dsss_mosaic_register_segments", args, REGSEG_DTYPE, (S, S, 6), want_sums, cap)
+
+    def _reg_segment_rows(self, fn, name, args, dtype, sums_shape, want_sums, cap):
+        """the capacity protocol of the three segment entries: fn(*args, rows, cap, &nseg, sums) -> the nseg rows of `dtype`, with
+        want_sums (rows, sums[nseg, *sums_shape]).  cap None: as many rows as there will be."""
         nseg = C.c_int(0)
         if cap is None:                                    # the library counts the rows before it launches anything: ask with no room
-            one = np.zeros(1, REGSEG_DTYPE)
-            rc = self.L.dsss_mosaic_register_segments(*args, _ptr(one), 0, C.byref(nseg), None)
+            one = np.zeros(1, dtype)
+            rc = fn(*args, _ptr(one), 0, C.byref(nseg), None)
             if rc != -5:                                   # DSSS_E_CAPACITY: nseg rows are needed; 0: there are none; anything else is an error
-                self._chk(rc, "dsss_mosaic_register_segments")
+                self._chk(rc, name)
             cap = nseg.value
-        out = np.zeros(max(cap, 1), REGSEG_DTYPE)
-        sums = np.zeros((max(cap, 1), S, S, 6), np.uint64) if want_sums else None
-        self._chk(self.L.dsss_mosaic_register_segments(*args, _ptr(out), int(cap), C.byref(nseg), _ptr(sums)), "dsss_mosaic_register_segments")
+        out = np.zeros(max(cap, 1), dtype)
+        sums = np.zeros((max(cap, 1),) + tuple(sums_shape), np.uint64) if want_sums else None
+        self._chk(fn(*args, _ptr(out), int(cap), C.byref(nseg), _ptr(sums)), name)
         out = out[:nseg.value]
         return (out, sums[:nseg.value]) if want_sums else out
+
+    def _reg_edges(self, fn, name, dtype, pair_of, ids, params, pairs, segs, edge_params, rpy6, ping_off, cap):
+        """the body of the two edges bindings: segs as rows of `dtype`, pair_of(segs) = the pair each row names -> (edges, edge_seg)"""
+        ids, rpy6, ping_off = self._mosaic_traj(ids, rpy6, ping_off)
+        pairs, pa, pb = _reg_pairs(pairs)
+        segs = np.ascontiguousarray(segs, dtype)
+        if len(segs) and (pair_of(segs).min() < 0 or pair_of(segs).max() >= len(pairs)):
+            raise ValueError("%s: a row names a pair outside the %d given" % (name[len("dsss_"):], len(pairs)))
+        cap = len(segs) if cap is None else int(cap)
+        edges = np.zeros(max(cap, 1), LCEDGE_DTYPE); src = np.zeros(max(cap, 1), np.int32); ne = C.c_int(0)
+        self._chk(fn(self.h, _ptr(ids), len(ids), _ptr(rpy6), _ptr(ping_off), C.byref(params), _ptr(pa), _ptr(pb), _ptr(segs), len(segs),
+                     C.byref(edge_params) if edge_params is not None else None, _ptr(edges), _ptr(src), cap, C.byref(ne)), name)
+        return edges[:ne.value].copy(), src[:ne.value].copy()
 
     def mosaic_register_edges(self, ids, params, pairs, segs, edge_params=None, rpy6=None, ping_off=None, cap=None):
         """register_edge on every row of segs (REGSEG_DTYPE, as mosaic_register_segments returned them for `pairs`) under the trajectory
         that was registered -> (edges, edge_seg): the accepted rows as LCEDGE_DTYPE records over the pose-graph indices ping_off[i] + ping
         (ping_off None: the frames of ids one behind the other), and the row each edge came from.  Launches no GPU work."""
-        ids, rpy6, ping_off = self._mosaic_traj(ids, rpy6, ping_off)
-        pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
-        pa = np.ascontiguousarray(pairs[:, 0]); pb = np.ascontiguousarray(pairs[:, 1])
-        segs = np.ascontiguousarray(segs, REGSEG_DTYPE)
-        if len(segs) and (segs["pair"].min() < 0 or segs["pair"].max() >= len(pairs)):
-            raise ValueError("mosaic_register_edges: a row names a pair outside the %d given" % len(pairs))
-        cap = len(segs) if cap is None else int(cap)
-        edges = np.zeros(max(cap, 1), LCEDGE_DTYPE); src = np.zeros(max(cap, 1), np.int32); ne = C.c_int(0)
-        self._chk(self.L.dsss_mosaic_register_edges(self.h, _ptr(ids), len(ids), _ptr(rpy6), _ptr(ping_off), C.byref(params), _ptr(pa), _ptr(pb),
-                                                    _ptr(segs), len(segs), C.byref(edge_params) if edge_params is not None else None,
-                                                    _ptr(edges), _ptr(src), cap, C.byref(ne)), "dsss_mosaic_register_edges")
-        return edges[:ne.value].copy(), src[:ne.value].copy()
+        return self._reg_edges(self.L.dsss_mosaic_register_edges, "dsss_mosaic_register_edges", REGSEG_DTYPE, lambda s: s["pair"],
+                               ids, params, pairs, segs, edge_params, rpy6, ping_off, cap)
 
     def mosaic_register_segments_yaw(self, ids, params, pairs, seg_pings, yaw=None, reg=None, rpy6=None, ping_off=None, want_sums=False, cap=None):
         """mosaic_register_segments with every segment registered under the angles of the fan `yaw` (a RegYawParams, None = the default
         of one angle) as well -> rows of REGSEGYAW_DTYPE: s = the row of the best angle k, with theta, theta_hat, yaw_on_border and the
         unrotated angle's ZNCC.  want_sums=True returns (rows, sums) with sums[nseg, nyaw, 2 r + 1, 2 r + 1, 6] uint64."""
         ids, rpy6, ping_off = self._mosaic_traj(ids, rpy6, ping_off)
-        pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
-        pa = np.ascontiguousarray(pairs[:, 0]); pb = np.ascontiguousarray(pairs[:, 1])
+        pairs, pa, pb = _reg_pairs(pairs)
         r = reg if reg is not None else reg_params_default()
         y = yaw if yaw is not None else reg_yaw_params_default()
         S = 2 * max(0, min(int(r.radius), 16)) + 1
         A = max(1, min(int(y.nyaw), 17))
         args = (self.h, _ptr(ids), len(ids), _ptr(rpy6), _ptr(ping_off), C.byref(params), _ptr(pa), _ptr(pb), len(pairs), int(seg_pings), C.byref(r),
                 C.byref(y))
-        nseg = C.c_int(0)
-        if cap is None:                                    # the library counts the rows before it launches anything: ask with no room
-            one = np.zeros(1, REGSEGYAW_DTYPE)
-            rc = self.L.dsss_mosaic_register_segments_yaw(*args, _ptr(one), 0, C.byref(nseg), None)
-            if rc != -5:                                   # DSSS_E_CAPACITY: nseg rows are needed; 0: there are none; anything else is an error
-                self._chk(rc, "dsss_mosaic_register_segments_yaw")
-            cap = nseg.value
-        out = np.zeros(max(cap, 1), REGSEGYAW_DTYPE)
-        sums = np.zeros((max(cap, 1), A, S, S, 6), np.uint64) if want_sums else None
-        self._chk(self.L.dsss_mosaic_register_segments_yaw(*args, _ptr(out), int(cap), C.byref(nseg), _ptr(sums)), "dsss_mosaic_register_segments_yaw")
-        out = out[:nseg.value]
-        return (out, sums[:nseg.value]) if want_sums else out
+        return self._reg_segment_rows(self.L.dsss_mosaic_register_segments_yaw, "dsss_mosaic_register_segments_yaw", args, REGSEGYAW_DTYPE, (A, S, S, 6),
+                                      want_sums, cap)
 
     def mosaic_register_edges_yaw(self, ids, params, pairs, segs, edge_params=None, rpy6=None, ping_off=None, cap=None):
         """mosaic_register_edges for the rows of mosaic_register_segments_yaw (REGSEGYAW_DTYPE); edge_params: a RegEdgeYawParams that names
         the fan the rows were registered with -> (edges, edge_seg).  The edges measure the heading too.  Launches no GPU work."""
-        ids, rpy6, ping_off = self._mosaic_traj(ids, rpy6, ping_off)
-        pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
-        pa = np.ascontiguousarray(pairs[:, 0]); pb = np.ascontiguousarray(pairs[:, 1])
-        segs = np.ascontiguousarray(segs, REGSEGYAW_DTYPE)
-        if len(segs) and (segs["s"]["pair"].min() < 0 or segs["s"]["pair"].max() >= len(pairs)):
-            raise ValueError("mosaic_register_edges_yaw: a row names a pair outside the %d given" % len(pairs))
-        cap = len(segs) if cap is None else int(cap)
-        edges = np.zeros(max(cap, 1), LCEDGE_DTYPE); src = np.zeros(max(cap, 1), np.int32); ne = C.c_int(0)
-        self._chk(self.L.dsss_mosaic_register_edges_yaw(self.h, _ptr(ids), len(ids), _ptr(rpy6), _ptr(ping_off), C.byref(params), _ptr(pa), _ptr(pb),
-                                                        _ptr(segs), len(segs), C.byref(edge_params) if edge_params is not None else None,
-                                                        _ptr(edges), _ptr(src), cap, C.byref(ne)), "dsss_mosaic_register_edges_yaw")
-        return edges[:ne.value].copy(), src[:ne.value].copy()
+        return self._reg_edges(self.L.dsss_mosaic_register_edges_yaw, "dsss_mosaic_register_edges_yaw", REGSEGYAW_DTYPE, lambda s: s["s"]["pair"],
+                               ids, params, pairs, segs, edge_params, rpy6, ping_off, cap)
 
     def mosaic_register_segments_pyr(self, ids, params, pairs, seg_pings, pyr=None, reg=None, rpy6=None, ping_off=None, want_sums=False, cap=None):
         """mosaic_register_segments coarse to fine over the cell pyramid `pyr` (a RegPyrParams, None = the default of one level): the top
@@ -1012,26 +1003,15 @@ class Context:
         level 0 away from every border), level, border_mask and the shift and ZNCC per level.  want_sums=True returns (rows, sums)
         with sums[nseg, (2 r + 1)^2 + (levels - 1) (2 refine + 1)^2, 6] uint64: the top level's table, then those of the levels below."""
         ids, rpy6, ping_off = self._mosaic_traj(ids, rpy6, ping_off)
-        pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
-        pa = np.ascontiguousarray(pairs[:, 0]); pb = np.ascontiguousarray(pairs[:, 1])
+        pairs, pa, pb = _reg_pairs(pairs)
         r = reg if reg is not None else reg_params_default()
         q = pyr if pyr is not None else reg_pyr_params_default()
         S = 2 * max(0, min(int(r.radius), 16)) + 1
         lv = max(1, min(int(q.levels), 4)); Sr = 2 * max(0, min(int(q.refine), 16)) + 1
         args = (self.h, _ptr(ids), len(ids), _ptr(rpy6), _ptr(ping_off), C.byref(params), _ptr(pa), _ptr(pb), len(pairs), int(seg_pings), C.byref(r),
                 C.byref(q))
-        nseg = C.c_int(0)
-        if cap is None:                                    # the library counts the rows before it launches anything: ask with no room
-            one = np.zeros(1, REGSEGPYR_DTYPE)
-            rc = self.L.dsss_mosaic_register_segments_pyr(*args, _ptr(one), 0, C.byref(nseg), None)
-            if rc != -5:                                   # DSSS_E_CAPACITY: nseg rows are needed; 0: there are none; anything else is an error
-                self._chk(rc, "dsss_mosaic_register_segments_pyr")
-            cap = nseg.value
-        out = np.zeros(max(cap, 1), REGSEGPYR_DTYPE)
-        sums = np.zeros((max(cap, 1), S * S + (lv - 1) * Sr * Sr, 6), np.uint64) if want_sums else None
-        self._chk(self.L.dsss_mosaic_register_segments_pyr(*args, _ptr(out), int(cap), C.byref(nseg), _ptr(sums)), "dsss_mosaic_register_segments_pyr")
-        out = out[:nseg.value]
-        return (out, sums[:nseg.value]) if want_sums else out
+        return self._reg_segment_rows(self.L.dsss_mosaic_register_segments_pyr, "dsss_mosaic_register_segments_pyr", args, REGSEGPYR_DTYPE,
+                                      (S * S + (lv - 1) * Sr * Sr, 6), want_sums, cap)
 
     def mosaic_register_peaks(self, sums, radius, min_cells, cell, ntables=None, out=None):
         """dsss_mosaic_register_peaks: the peak rule on many tables at once, on the device -> rows of REG_DTYPE, row k bit for bit what

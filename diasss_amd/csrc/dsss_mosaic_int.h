@@ -1,11 +1,17 @@
 // diasss_amd/csrc/dsss_mosaic_int.h -- what dsss_mosaic.hip (mosaic, consistency map) and dsss_mosaic_reg.hip (overlap registration)
 // share: the job and window records of mosaic_scatter_kernel, the argument checks, a frame's window of the grid, the upload of a
-// caller's trajectory and the scatter launch.  The definitions are in dsss_mosaic.hip.
+// caller's trajectory and the scatter launch.  The definitions are in dsss_mosaic.hip.  Below them: the score, order and sub-cell
+// rules of the registration, one body for host and device, and what dsss_mosaic_reg.hip needs of the registration's host arithmetic
+// (dsss_mosaic_edge.cpp).
 #pragma once
 #include "dsss_internal.h"
 
 #define MOSAIC_MAX_CELLS (1ll << 28)
 #define MOSAIC_MAX_SAMPLES (1u << 24)      // per cell: 255 * 2^24 < 2^32, the u32 sum cannot wrap below it
+#define REG_MAX_RADIUS 16                  // the registration's search radius, in cells
+#define REG_MAX_YAW 17                     // angles of a yaw fan
+#define PYR_MAX_LEVELS 4                   // levels of a cell pyramid
+#define PYR_MAX_CENTRE (1 << 28)           // |cx|, |cy| of a level's centre: twice the centre plus the radius stays an int32
 
 // one frame of a launch: its pose rows (the frame's own or the caller's trajectory), geometry and images; blk0 = its first workgroup
 struct mosaic_job { const double* pose; const double* gr; const uint8_t* img; const uint8_t* mask; int N, M, blk0, pad; };
@@ -129,3 +135,13 @@ int upload_rows(dsss_ctx* c, const int* ids, int n, const double* rpy6, const in
 void launch_scatter(dsss_ctx* c, const mosaic_job* d_jobs, int njobs, int blocks, const mosaic_win& G, unsigned long long* acc);
 // the segmented form for ONE frame (d_job: its record, blk0 = 0; blocks = its pings): ping p goes into d_segs[p / seg_pings]
 void launch_scatter_seg(dsss_ctx* c, const mosaic_job* d_job, int blocks, const mosaic_win& G, unsigned long long* acc, const mosaic_seg* d_segs, int seg_pings);
+
+// ---- the registration's host arithmetic (dsss_mosaic_edge.cpp), as far as the orchestration in dsss_mosaic_reg.hip needs it
+int peak_of(const uint64_t* sums, int radius, int min_cells, double cell, dsss_reg_result* out);      // one table -> its record: mosaic_peak_kernel's twin
+bool fan_ok(int nyaw, double step);
+double fan_theta(int k, int nyaw, double step);
+void rotate_rows(const double* rows_b, int p0, int p1, double theta, double* out);
+void yaw_peak_of(const dsss_reg_result* z, int nyaw, double step, int32_t* k, int32_t* border, double* theta, double* theta_hat);
+bool pyr_ok(const dsss_reg_pyr_params& P);
+int pyr_min_cells(int min_cells, int level);
+void pyr_centre_of(double cell, int level, int cx, int cy, dsss_reg_result* out, int32_t* usable, int32_t* ncx, int32_t* ncy);

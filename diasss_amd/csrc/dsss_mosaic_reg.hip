@@ -17,12 +17,16 @@
 // the device, mosaic_peak_kernel runs behind the correlation, and the records come down with the sample-limit flag in one copy;
 // with sums, or under DSSS_REG_PEAKS=host, the table comes down and the host decides, as before.  dsss_mosaic_register_peaks is the
 // kernel as a public entry on any tables, dsss_mosaic_register_info what the last call did.
+// Where things live: this file holds the seven kernels with their job records and launch helpers, the registration plan -- what the
+// four entries share on the host, each concern with one owner: reg_rows (argument rules, rows and where the peaks are decided),
+// reg_layers (frame-a windows), reg_mem (the device memory in typed pieces and the place of the sample-limit flag), reg_upload_jobs,
+// reg_render_a / reg_render_b, reg_fetch (what follows every correlation launch), reg_centroids, pyr_apply -- and the four entries,
+// each a short list over that plan.  The host arithmetic that launches nothing (peak_of, the angle rule, the level rule, edges) is in
+// dsss_mosaic_edge.cpp; the rules shared with the device and the declarations are in dsss_mosaic_int.h.
 #include "dsss_mosaic_int.h"
-#include "dsss_pose.h"
 #include "dsss_wave.h"
 #include <algorithm>
 
-#define REG_MAX_RADIUS 16
 #define REG_TILE 32                        // a workgroup stages 32 x 32 cells of a and the (32 + 2 r)^2 halo of b
 #define REG_HALO (REG_TILE + 2 * REG_MAX_RADIUS)
 #define REG_STRIP 8                        // tiles (along x) a workgroup walks before it flushes: 8 x 1024 x 255^2 < 2^32, the u32 partials cannot wrap
@@ -55,7 +59,6 @@ __global__ __launch_bounds__(256) void mosaic_mean_kernel(const unsigned long lo
 }
 
 // ---- the pyramid of mean layers ("dense loop closures over a cell pyramid" in the header)
-#define PYR_MAX_LEVELS 4
 #define PYR_TW 64                          // a workgroup of mosaic_pyr_kernel owns 64 x 32 fine cells, aligned to 8 = 2^(PYR_MAX_LEVELS - 1) in grid coordinates
 #define PYR_TH 32
 #define PYR_ROWS 8                         // fine cells one below the other per thread: the vertical partners of every level are its own registers
@@ -345,26 +348,6 @@ int reg_launch_peaks(dsss_ctx* c, const unsigned long long* d_tab, long long nta
     return DSSS_OK;
 }
 
-int peak_of(const uint64_t* sums, int radius, int min_cells, double cell, dsss_reg_result* out)
-{
-    const int S = 2 * radius + 1;
-    std::vector<reg_score> z((size_t)S * S);
-    for (int s = 0; s < S * S; ++s) z[s] = reg_score_of(sums + (size_t)s * 6, min_cells);
-    bool found = false; int bx = 0, by = 0;
-    for (int dy = -radius; dy <= radius; ++dy)
-        for (int dx = -radius; dx <= radius; ++dx) {
-            const reg_score& q = z[(size_t)(dy + radius) * S + (dx + radius)];
-            if (!q.ok) continue;
-            if (!found || reg_better(q.z, dx, dy, z[(size_t)(by + radius) * S + (bx + radius)].z, bx, by)) { found = true; bx = dx; by = dy; }
-        }
-    const size_t zero = (size_t)radius * S + radius, pk = (size_t)(by + radius) * S + (bx + radius);
-    const bool inner = found && abs(bx) != radius && abs(by) != radius;      // the four neighbours exist
-    const reg_score none = { -2.0, false };
-    reg_record(found, bx, by, radius, cell, z[zero], sums[zero * 6], z[pk], sums[pk * 6], inner ? z[pk - 1] : none, inner ? z[pk + 1] : none,
-               inner ? z[pk - S] : none, inner ? z[pk + S] : none, out);
-    return DSSS_OK;
-}
-
 // what a registration call did (dsss_reg_call_info), counted where the call enqueues its copies and synchronises
 struct reg_count {
     dsss_reg_call_info I{0, 0, 0, 0};
@@ -372,31 +355,7 @@ struct reg_count {
     void sync() { I.syncs += 1; }
 };
 
-// ---- what dsss_mosaic_register and dsss_mosaic_register_segments share on the host
-// the argument rules of both entries; R = the parameters in force, slot = frame id -> its index in ids, rows = pings of all frames
-int reg_check(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, const dsss_mosaic_params* p, const int* pair_a,
-              const int* pair_b, int npairs, const dsss_reg_params* rp, const void* out_host, dsss_reg_params* R, std::vector<int>& slot, size_t* rows)
-{
-    if (dsss_comm_world(c) > 1) DSSS_FAIL(c, DSSS_E_STATE, "mosaic: registration runs on a single rank (communicator of %d)", dsss_comm_world(c));
-    int rc = mosaic_check_frames(c, ids, n, rpy6, ping_off, true, rows); if (rc) return rc;
-    rc = mosaic_check_params(c, p); if (rc) return rc;
-    dsss_reg_params_default(R);
-    if (rp) *R = *rp;
-    if (R->radius < 0 || R->radius > REG_MAX_RADIUS) DSSS_FAIL(c, DSSS_E_ARG, "register: radius %d outside 0..%d", R->radius, REG_MAX_RADIUS);
-    if (R->min_cells < 1) DSSS_FAIL(c, DSSS_E_ARG, "register: min_cells = %d", R->min_cells);
-    if (npairs < 0) DSSS_FAIL(c, DSSS_E_ARG, "register: npairs = %d", npairs);
-    if (npairs > 0 && (!pair_a || !pair_b || !out_host)) DSSS_FAIL(c, DSSS_E_ARG, "register: %d pairs without %s", npairs, out_host ? "their frames" : "a result array");
-    slot.assign(c->max_frames, -1);
-    for (int i = 0; i < n; ++i) slot[ids[i]] = i;
-    for (int k = 0; k < npairs; ++k) {
-        const int a = pair_a[k], b = pair_b[k];
-        if (a < 0 || a >= c->max_frames || slot[a] < 0 || b < 0 || b >= c->max_frames || slot[b] < 0)
-            DSSS_FAIL(c, DSSS_E_ARG, "register: pair %d = (%d, %d) names a frame that is not listed", k, a, b);
-        if (a == b) DSSS_FAIL(c, DSSS_E_ARG, "register: pair %d is frame %d with itself", k, a);
-    }
-    return DSSS_OK;
-}
-
+// ---- what the registration entries share on the host
 // the window of the pings [r0, r1) of a frame: the cells their geo extremes can reach (as the consistency map's); false: none on the grid
 bool reg_window(const dsss_frame& f, const double* rows, int r0, int r1, const dsss_mosaic_params* p, mosaic_win* w)
 {
@@ -459,168 +418,276 @@ bool cen_push_job(std::vector<cen_job>& cj, long long* blocks, const uint16_t* l
     return true;
 }
 
-// all centroid jobs in one launch, and the nseg x 3 sums back in cen (d_cen was cleared before)
-int reg_launch_centroids(dsss_ctx* c, const std::vector<cen_job>& cj, long long cblocks, cen_job* d_cj, const unsigned long long* d_cen, std::vector<uint64_t>& cen,
-                         reg_count& cnt)
+// ---- the registration plan: what the four entries share on the host, each concern written once
+
+// cells of a layer, or of a window's accumulators, rounded up so that the next one starts on 256 bytes
+inline size_t reg_round(size_t cells) { return (cells + 127) & ~(size_t)127; }
+// the 64-bit sums of one table
+inline size_t reg_table_words(int r) { return (size_t)(2 * r + 1) * (2 * r + 1) * 6; }
+// the grid without a window: what the segmented scatters take, and what a segment keeps that has no cell on the grid (bw = 0)
+inline mosaic_win reg_grid(const dsss_mosaic_params* p) { return mosaic_win{ p->x0, p->y0, p->cell, p->W, p->H, 0, 0, 0, 0, p->use_mask != 0 }; }
+
+// What the argument rules establish: the parameters in force, the frames' places in ids, which frames occur as a and as b, where the
+// peaks are decided, and for the segment entries the rows -- by pair and then by segment of the pair's frame b.
+struct reg_rows {
+    dsss_ctx* c = nullptr; const int* ids = nullptr; const double* rpy6 = nullptr; const int* ping_off = nullptr;
+    const int* pair_a = nullptr; const int* pair_b = nullptr;
+    int n = 0, npairs = 0, seg_pings = 1, nseg = 0;
+    dsss_reg_params R; std::vector<int> slot; size_t traj_rows = 0;            // slot: frame id -> its index in ids; traj_rows = pings of all frames
+    bool dev = false;                                                           // the peaks on the device: nobody reads the table on the host
+    std::vector<char> as_a, as_b;
+    std::vector<int> row_a, row_b; std::vector<size_t> row_g;                   // a row's frames (index in ids) and its segment's first entry in the entry's window list
+
+    const dsss_frame& frame(int i) const { return c->frames[ids[i]]; }
+    const double* rows_of(int i) const { return rpy6 ? rpy6 + (size_t)ping_off[i] * 6 : frame(i).h_geo; }
+    int segs_of(int i) const { return (int)(((long long)frame(i).N + seg_pings - 1) / seg_pings); }
+    int seg_end(int s, int N) const { return (int)std::min((long long)(s + 1) * seg_pings, (long long)N); }
+
+    // the argument rules of all four entries
+    int check(dsss_ctx* ctx, const int* ids_, int n_, const double* rpy6_, const int* ping_off_, const dsss_mosaic_params* p, const int* pa, const int* pb,
+              int npairs_, const dsss_reg_params* rp, const void* out_host)
+    {
+        c = ctx; ids = ids_; n = n_; rpy6 = rpy6_; ping_off = ping_off_; pair_a = pa; pair_b = pb; npairs = npairs_;
+        if (dsss_comm_world(c) > 1) DSSS_FAIL(c, DSSS_E_STATE, "mosaic: registration runs on a single rank (communicator of %d)", dsss_comm_world(c));
+        int rc = mosaic_check_frames(c, ids, n, rpy6, ping_off, true, &traj_rows); if (rc) return rc;
+        rc = mosaic_check_params(c, p); if (rc) return rc;
+        dsss_reg_params_default(&R);
+        if (rp) R = *rp;
+        if (R.radius < 0 || R.radius > REG_MAX_RADIUS) DSSS_FAIL(c, DSSS_E_ARG, "register: radius %d outside 0..%d", R.radius, REG_MAX_RADIUS);
+        if (R.min_cells < 1) DSSS_FAIL(c, DSSS_E_ARG, "register: min_cells = %d", R.min_cells);
+        if (npairs < 0) DSSS_FAIL(c, DSSS_E_ARG, "register: npairs = %d", npairs);
+        if (npairs > 0 && (!pair_a || !pair_b || !out_host)) DSSS_FAIL(c, DSSS_E_ARG, "register: %d pairs without %s", npairs, out_host ? "their frames" : "a result array");
+        slot.assign(c->max_frames, -1);
+        for (int i = 0; i < n; ++i) slot[ids[i]] = i;
+        for (int k = 0; k < npairs; ++k) {
+            const int a = pair_a[k], b = pair_b[k];
+            if (a < 0 || a >= c->max_frames || slot[a] < 0 || b < 0 || b >= c->max_frames || slot[b] < 0)
+                DSSS_FAIL(c, DSSS_E_ARG, "register: pair %d = (%d, %d) names a frame that is not listed", k, a, b);
+            if (a == b) DSSS_FAIL(c, DSSS_E_ARG, "register: pair %d is frame %d with itself", k, a);
+        }
+        return DSSS_OK;
+    }
+    // ... and those of the segment entries
+    int check_segments(int seg_pings_, const int* nseg_host, int cap)
+    {
+        if (seg_pings_ < 1) DSSS_FAIL(c, DSSS_E_ARG, "register: seg_pings = %d", seg_pings_);
+        if (!nseg_host || cap < 0) DSSS_FAIL(c, DSSS_E_ARG, "register: %s", nseg_host ? "negative capacity" : "nowhere to write the number of segments");
+        seg_pings = seg_pings_;
+        return DSSS_OK;
+    }
+    // which frames occur as what, and the path: the switch is read here, once per call
+    void mark(const uint64_t* sums_host)
+    {
+        dev = !sums_host && !dsss_switches_read().reg_peaks_host;
+        as_a.assign(n, 0); as_b.assign(n, 0);
+        for (int k = 0; k < npairs; ++k) { as_a[slot[pair_a[k]]] = 1; as_b[slot[pair_b[k]]] = 1; }
+    }
+    // the number of rows (a ping of frame b takes nyaw workgroups of its scatter); nseg = 0: nothing to do
+    int count(int nyaw, int cap, int* nseg_host, const uint64_t* sums_host)
+    {
+        long long total = 0;
+        for (int k = 0; k < npairs; ++k) {
+            const int ib = slot[pair_b[k]];
+            if ((long long)frame(ib).N * nyaw > 0x7fffffffll) DSSS_FAIL(c, DSSS_E_ARG, "register: frame %d has %d pings, too many for %d angles in one launch", ids[ib], frame(ib).N, nyaw);
+            total += segs_of(ib);
+        }
+        if (total > 0x7fffffffll) DSSS_FAIL(c, DSSS_E_ARG, "register: %lld segments", total);
+        *nseg_host = (int)total;                                                // also when there is no room for them: the caller learns how many
+        if (total > cap) DSSS_FAIL(c, DSSS_E_CAPACITY, "register: %lld segments, room for %d", total, cap);
+        nseg = (int)total;
+        if (nseg) mark(sums_host);
+        return DSSS_OK;
+    }
+    // the rows laid out: the header of row `row` goes to seg_of(row); segment s of frame b is entry first[ib] + s * per of the window list
+    template <class SegOf> void layout(const std::vector<size_t>& first, int per, SegOf seg_of)
+    {
+        row_a.resize(nseg); row_b.resize(nseg); row_g.resize(nseg);
+        int row = 0;
+        for (int k = 0; k < npairs; ++k) {
+            const int ia = slot[pair_a[k]], ib = slot[pair_b[k]];
+            for (int s = 0; s < segs_of(ib); ++s, ++row) {
+                dsss_reg_seg& o = seg_of(row);
+                o.pair = k; o.seg = s; o.p0 = s * seg_pings; o.p1 = seg_end(s, frame(ib).N);
+                row_a[row] = ia; row_b[row] = ib; row_g[row] = first[ib] + (size_t)s * per;
+            }
+        }
+    }
+};
+
+// The frames as an a: the window of the cells a frame's geo extremes can reach (as the consistency map's) and where its u16 layer
+// starts; win_cells = the accumulators the largest render needs, lay_cells = the cells of all layers laid out so far.
+struct reg_layers {
+    std::vector<mosaic_win> wins; std::vector<char> on_grid; std::vector<size_t> lay_off;
+    size_t win_cells = 1, lay_cells = 0;
+    explicit reg_layers(int n) : wins(n), on_grid(n, 0), lay_off(n, 0) {}
+    void add_a(const reg_rows& Q, int i, const dsss_mosaic_params* p)
+    {
+        const dsss_frame& f = Q.frame(i);
+        if (!reg_window(f, Q.rows_of(i), 0, f.N, p, &wins[i])) return;
+        on_grid[i] = 1;
+        const size_t wc = (size_t)wins[i].bw * wins[i].bh;
+        win_cells = std::max(win_cells, wc);
+        lay_off[i] = lay_cells; lay_cells += reg_round(wc);
+    }
+    // the layers of a frame's segments as b: `cells` accumulators, one window behind the other -> where their layers start
+    size_t add_b(size_t cells) { win_cells = std::max(win_cells, cells); const size_t o = lay_cells; lay_cells += cells; return o; }
+};
+
+// mosaic_buf in typed, 256-byte aligned pieces: take<T>(count) before reserve, at(piece) after it.  A piece that comes down behind a
+// correlation launch is taken with take_flagged: the sample-limit flag lies in the 8 bytes in front of it, so one copy that starts
+// at flag_of(piece) brings the flag and the payload.  The one place the flag's position is decided.
+template <class T> struct reg_piece { size_t off = 0; };
+struct reg_arena {
+    carve L; char* B = nullptr;
+    template <class T> reg_piece<T> take(size_t count) { return reg_piece<T>{ L.take(count * sizeof(T)) }; }
+    template <class T> reg_piece<T> take_flagged(size_t count) { return reg_piece<T>{ L.take(256 + count * sizeof(T)) + 256 }; }
+    int reserve(dsss_ctx* c) { const int rc = c->mosaic_buf.reserve(c, L.off); B = c->mosaic_buf.as<char>(); return rc; }
+    template <class T> T* at(reg_piece<T> p) const { return reinterpret_cast<T*>(B + p.off); }
+    template <class T> int* flag_of(reg_piece<T> p) const { return reinterpret_cast<int*>(B + p.off - 8); }
+};
+
+// The device memory of a registration call: the pieces every entry needs (an entry's own go through A between take and reserve).
+// tab = the sums of one pass, rec = its records on the device path, flag = the sample-limit flag in front of whichever comes down.
+struct reg_mem {
+    reg_arena A; bool dev = false;
+    uint16_t* lay = nullptr; unsigned long long* win = nullptr; mosaic_job* jobs = nullptr; double* rows = nullptr; reg_job* pairs = nullptr;
+    cen_job* cj = nullptr; unsigned long long* cen = nullptr; unsigned long long* tab = nullptr; dsss_reg_result* rec = nullptr; int* flag = nullptr;
+    reg_piece<uint16_t> o_lay; reg_piece<unsigned long long> o_win, o_cen, o_tab; reg_piece<mosaic_job> o_jobs; reg_piece<double> o_rows;
+    reg_piece<reg_job> o_pairs; reg_piece<cen_job> o_cj; reg_piece<dsss_reg_result> o_rec;
+
+    // n frames, traj_rows pings of a caller's trajectory (0: the frames' own), nrows tables of at most table_words sums in all per pass
+    void take(size_t lay_cells, size_t win_cells, int n, size_t traj_rows, size_t nrows, bool centroids, size_t table_words, bool on_device)
+    {
+        dev = on_device;
+        o_lay = A.take<uint16_t>(lay_cells); o_win = A.take<unsigned long long>(win_cells); o_jobs = A.take<mosaic_job>(n);
+        o_rows = A.take<double>(traj_rows * 6); o_pairs = A.take<reg_job>(nrows);
+        o_cj = A.take<cen_job>(centroids ? nrows : 0); o_cen = A.take<unsigned long long>(centroids ? nrows * 3 : 0);
+        o_tab = A.take_flagged<unsigned long long>(table_words); o_rec = A.take_flagged<dsss_reg_result>(dev ? nrows : 0);
+    }
+    int reserve(dsss_ctx* c)
+    {
+        const int rc = A.reserve(c); if (rc) return rc;
+        lay = A.at(o_lay); win = A.at(o_win); jobs = A.at(o_jobs); rows = A.at(o_rows); pairs = A.at(o_pairs); cj = A.at(o_cj); cen = A.at(o_cen);
+        tab = A.at(o_tab); rec = A.at(o_rec); flag = dev ? A.flag_of(o_rec) : A.flag_of(o_tab);
+        return DSSS_OK;
+    }
+    // what one copy brings down behind a pass of ntab tables of tsz sums: the flag and the records, or the flag and the tables
+    size_t down_bytes(size_t ntab, size_t tsz) const { return 8 + (dev ? ntab * sizeof(dsss_reg_result) : ntab * tsz * 8); }
+    // the flag and `words` sums cleared: one memset where the flag lies in front of the table, two where it lies in front of the records
+    int clear_both(dsss_ctx* c, size_t words) const
+    {
+        if (!dev) { HIPCHK(c, hipMemsetAsync(flag, 0, 8 + words * 8, c->stream)); return DSSS_OK; }
+        HIPCHK(c, hipMemsetAsync(tab, 0, words * 8, c->stream));
+        HIPCHK(c, hipMemsetAsync(flag, 0, 8, c->stream));
+        return DSSS_OK;
+    }
+};
+
+// the trajectory rows and the mosaic_job table of the frames go up; jobs = the table as the host keeps it
+int reg_upload_jobs(const reg_rows& Q, const reg_mem& M, std::vector<mosaic_job>& jobs)
 {
-    HIPCHK(c, hipMemcpyAsync(d_cj, cj.data(), cj.size() * sizeof(cen_job), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(mosaic_centroid_kernel, dim3((unsigned)cblocks), dim3(256), 0, c->stream, d_cj, (int)cj.size());
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(cen.data(), d_cen, cen.size() * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    cnt.down(cen.size() * 8); cnt.sync();
+    dsss_ctx* c = Q.c;
+    std::vector<const double*> dev_rows;
+    const int rc = upload_rows(c, Q.ids, Q.n, Q.rpy6, Q.ping_off, M.rows, dev_rows); if (rc) return rc;
+    jobs.resize(Q.n);
+    for (int i = 0; i < Q.n; ++i) { const dsss_frame& f = Q.frame(i); jobs[i] = mosaic_job{ dev_rows[i], f.gr, f.lvl[0], f.mask, f.N, f.M, 0, 0 }; }
+    HIPCHK(c, hipMemcpyAsync(M.jobs, jobs.data(), (size_t)Q.n * sizeof(mosaic_job), hipMemcpyHostToDevice, c->stream));
     return DSSS_OK;
 }
 
-// ---- the yaw fan
-#define REG_MAX_YAW 17
-
-bool fan_ok(int nyaw, double step) { return nyaw >= 1 && nyaw <= REG_MAX_YAW && (nyaw & 1) && step > 0.0 && std::isfinite(step); }
-double fan_theta(int k, int nyaw, double step) { return (double)(k - (nyaw - 1) / 2) * step; }
-
-// the pings [p0, p1) of rows_b rotated by theta about the position of ping (p0 + p1) / 2 -> out, (p1 - p0) x 6
-void rotate_rows(const double* rows_b, int p0, int p1, double theta, double* out)
+// wc accumulators of M.win -> the u16 layer at lay_off, with the sample-limit flag: the one launch of mosaic_mean_kernel
+int reg_pack(dsss_ctx* c, const reg_mem& M, size_t wc, size_t lay_off)
 {
-    const double* piv = rows_b + (size_t)(((long long)p0 + p1) / 2) * 6;
-    double s, co; dsss_sincos(theta, &s, &co);
-    for (int i = p0; i < p1; ++i) dsss_rotate_row(rows_b + (size_t)i * 6, piv[3], piv[4], theta, s, co, out + (size_t)(i - p0) * 6);
+    hipLaunchKernelGGL(mosaic_mean_kernel, dim3((unsigned)((wc + 255) / 256)), dim3(256), 0, c->stream, M.win, wc, M.lay + lay_off, M.flag);
+    HIPCHK(c, hipGetLastError());
+    return DSSS_OK;
 }
 
-// the angle rule of the header, "dense loop closures with a yaw fan": the one place it is written
-void yaw_peak_of(const dsss_reg_result* z, int nyaw, double step, int32_t* k, int32_t* border, double* theta, double* theta_hat)
+// frame i as an a: scatter into the 64-bit window, pack into the frame's resident u16 layer
+int reg_render_a(dsss_ctx* c, const reg_mem& M, const reg_layers& W, int i, int pings)
 {
-    const int mid = (nyaw - 1) / 2;
-    int best = -1;
-    for (int i = 0; i < nyaw; ++i) {
-        if (!(z[i].zncc > -2.0)) continue;
-        if (best < 0 || z[i].zncc > z[best].zncc || (z[i].zncc == z[best].zncc && abs(i - mid) < abs(best - mid))) best = i;   // equals at one distance: the lower k came first
-    }
-    if (best < 0) { *k = mid; *border = 0; *theta = 0.0; *theta_hat = 0.0; return; }
-    *k = best; *border = (nyaw > 1 && (best == 0 || best == nyaw - 1)) ? 1 : 0;
-    *theta = fan_theta(best, nyaw, step);
-    double q = 0.0;
-    if (!*border && nyaw > 1 && z[best - 1].zncc > -2.0 && z[best + 1].zncc > -2.0) {
-        const double zm = z[best - 1].zncc, z0 = z[best].zncc, zp = z[best + 1].zncc;
-        const double den = zm - 2.0 * z0 + zp;
-        if (den < 0.0) q = 0.5 * (zm - zp) / den;
-    }
-    *theta_hat = *theta + q * step;
+    const size_t wc = (size_t)W.wins[i].bw * W.wins[i].bh;
+    HIPCHK(c, hipMemsetAsync(M.win, 0, wc * 8, c->stream));
+    launch_scatter(c, M.jobs + i, 1, pings, W.wins[i], M.win);
+    return reg_pack(c, M, wc, W.lay_off[i]);
 }
 
-// dsss_register_edge and dsss_register_edge_yaw: the segment row s as an edge, its pings rotated by theta where the anchor ping is
-// looked for and by theta_hat where it is measured (both 0: the rows as they are), s_yaw = the sigma of the yaw
-int edge_of(const dsss_reg_seg* s, const dsss_mosaic_params* grid, const double* rows_a, int Na, int base_a, const double* rows_b, int Nb, int base_b,
-            const dsss_reg_edge_params& E, double theta, double theta_hat, double s_yaw, dsss_lc_edge* edge)
+// all segments of a frame as b, their windows one behind the other in `cells` accumulators: ONE scatter (the entry's) and ONE pack
+template <class Scatter> int reg_render_b(dsss_ctx* c, const reg_mem& M, size_t cells, size_t lay_off, Scatter scatter)
 {
-    if (!s || !grid || !rows_a || !rows_b || !edge || Na < 1 || Nb < 1) return DSSS_E_ARG;
-    if (s->p0 < 0 || s->p0 >= s->p1 || s->p1 > Nb) return DSSS_E_ARG;
-    if (!(grid->cell > 0.0) || !std::isfinite(grid->cell)) return DSSS_E_ARG;
-    const double sig[4] = { E.sigma_xy_cells, E.sigma_z, E.sigma_rot, s_yaw };
-    for (double v : sig) if (!(v > 0.0) || !std::isfinite(v)) return DSSS_E_ARG;
-    if (!std::isfinite(theta) || !std::isfinite(theta_hat)) return DSSS_E_ARG;
-    if (!(s->r.zncc >= E.min_zncc) || s->r.on_border != 0) return 0;
-    if (s->r.n <= 0) return DSSS_E_ARG;
-    const double cell = grid->cell;
-    const double cx = grid->x0 + ((double)s->sx / (double)s->r.n + 0.5) * cell, cy = grid->y0 + ((double)s->sy / (double)s->r.n + 0.5) * cell;
-    // the ping whose scan line (through the ping, across the heading) passes nearest the point: the lowest index among equals
-    auto anchor = [](const double* rows, int r0, int r1, double px, double py) {
-        int best = r0; double dbest = INFINITY;
-        for (int i = r0; i < r1; ++i) {
-            const double* P = rows + (size_t)i * 6;
-            const double d = fabs(cos(P[2]) * (px - P[3]) + sin(P[2]) * (py - P[4]));
-            if (d < dbest) { dbest = d; best = i; }
-        }
-        return best;
-    };
-    const int i = anchor(rows_a, 0, Na, cx, cy);
-    std::vector<double> rot((size_t)(s->p1 - s->p0) * 6);                       // the segment's rows under theta (theta == 0: a copy)
-    rotate_rows(rows_b, s->p0, s->p1, theta, rot.data());
-    const int j = s->p0 + anchor(rot.data(), 0, s->p1 - s->p0, cx + s->r.off_x, cy + s->r.off_y);      // b's rendering lies off from where it belongs
-    double rowj[6], sh, ch;                                                     // row j of the rows under theta_hat
-    const double* piv = rows_b + (size_t)(((long long)s->p0 + s->p1) / 2) * 6;
-    dsss_sincos(theta_hat, &sh, &ch);
-    dsss_rotate_row(rows_b + (size_t)j * 6, piv[3], piv[4], theta_hat, sh, ch, rowj);
-    pose_t Xa, Xb, rel;
-    pose_from_rodrigues(rows_a + (size_t)i * 6, &Xa);
-    pose_from_rodrigues(rowj, &Xb);
-    Xb.t[0] -= s->r.off_x; Xb.t[1] -= s->r.off_y;
-    const long long ga = (long long)base_a + i, gb = (long long)base_b + j;
-    if (ga < 0 || gb < 0 || ga > 0x7fffffffll || gb > 0x7fffffffll) return DSSS_E_ARG;
-    if (ga < gb) { edge->a = (int32_t)ga; edge->b = (int32_t)gb; pose_between(&Xa, &Xb, &rel); }
-    else { edge->a = (int32_t)gb; edge->b = (int32_t)ga; pose_between(&Xb, &Xa, &rel); }
-    memcpy(edge->rel, rel.R, 9 * sizeof(double)); memcpy(edge->rel + 9, rel.t, 3 * sizeof(double));
-    const double sxy = E.sigma_xy_cells * cell;
-    edge->var[0] = edge->var[1] = E.sigma_rot * E.sigma_rot; edge->var[2] = s_yaw * s_yaw;
-    edge->var[3] = edge->var[4] = sxy * sxy; edge->var[5] = E.sigma_z * E.sigma_z;
-    return 1;
+    HIPCHK(c, hipMemsetAsync(M.win, 0, cells * 8, c->stream));
+    scatter();
+    return reg_pack(c, M, cells, lay_off);
 }
 
-// the row loop of dsss_mosaic_register_edges and dsss_mosaic_register_edges_yaw: seg_of(k) = the (pair, segment) part of row k,
-// edge_fn(k, rows_a, Na, base_a, rows_b, Nb, base_b, &e) = what dsss_register_edge(_yaw) says about it
-template <class SegOf, class EdgeFn>
-int edges_loop(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, const dsss_mosaic_params* p, const int* pair_a, const int* pair_b,
-               bool have_segs, int nsegs, dsss_lc_edge* edges_host, int32_t* edge_seg_host, int cap, int* n_edges, SegOf seg_of, EdgeFn edge_fn)
-{
-    if (!c) return DSSS_E_ARG;
-    if (dsss_comm_world(c) > 1) DSSS_FAIL(c, DSSS_E_STATE, "mosaic: registration runs on a single rank (communicator of %d)", dsss_comm_world(c));
-    size_t rows = 0;
-    int rc = mosaic_check_frames(c, ids, n, rpy6, ping_off, false, &rows); if (rc) return rc;
-    rc = mosaic_check_params(c, p); if (rc) return rc;
-    if (nsegs < 0 || cap < 0 || !n_edges) DSSS_FAIL(c, DSSS_E_ARG, "register: nsegs = %d, cap = %d%s", nsegs, cap, n_edges ? "" : ", nowhere to write the number of edges");
-    if (nsegs > 0 && (!pair_a || !pair_b || !have_segs)) DSSS_FAIL(c, DSSS_E_ARG, "register: %d segments without %s", nsegs, have_segs ? "their pairs" : "their rows");
-    std::vector<int> slot(c->max_frames, -1), base(n);
-    int run = 0;
-    for (int i = 0; i < n; ++i) { slot[ids[i]] = i; base[i] = ping_off ? ping_off[i] : run; run += c->frames[ids[i]].N; }
-    int ne = 0;
-    for (int k = 0; k < nsegs; ++k) {
-        const dsss_reg_seg& sg = seg_of(k);
-        if (sg.pair < 0) DSSS_FAIL(c, DSSS_E_ARG, "register: row %d names pair %d", k, sg.pair);
-        const int a = pair_a[sg.pair], b = pair_b[sg.pair];
-        if (a < 0 || a >= c->max_frames || slot[a] < 0 || b < 0 || b >= c->max_frames || slot[b] < 0)
-            DSSS_FAIL(c, DSSS_E_ARG, "register: row %d, pair (%d, %d) names a frame that is not listed", k, a, b);
-        const int ia = slot[a], ib = slot[b];
-        const dsss_frame& fa = c->frames[a]; const dsss_frame& fb = c->frames[b];
-        dsss_lc_edge e;
-        rc = edge_fn(k, rpy6 ? rpy6 + (size_t)ping_off[ia] * 6 : fa.h_geo, fa.N, base[ia],
-                     rpy6 ? rpy6 + (size_t)ping_off[ib] * 6 : fb.h_geo, fb.N, base[ib], &e);
-        if (rc < 0) DSSS_FAIL(c, rc, "register: row %d (pair %d, segment %d, pings %d..%d) is not a valid segment result", k, sg.pair, sg.seg, sg.p0, sg.p1);
-        if (rc == 0) continue;
-        if (ne >= cap || !edges_host) DSSS_FAIL(c, DSSS_E_CAPACITY, "register: more than %d edges", edges_host ? cap : 0);
-        edges_host[ne] = e;
-        if (edge_seg_host) edge_seg_host[ne] = k;
-        ++ne;
+// one correlation launch's radius, min_cells and cell: uniform over its tables
+struct reg_pass { int radius, min_cells; double cell; };
+
+// what reg_fetch brought down, read by index: a record on either path (the device's, or decided here from the table), a table on the host path
+struct reg_view {
+    bool dev; const dsss_reg_result* rec; const uint64_t* tab; size_t tsz; reg_pass P;
+    dsss_reg_result record(size_t k) const
+    {
+        if (dev) return rec[k];
+        dsss_reg_result q; peak_of(tab + k * tsz, P.radius, P.min_cells, P.cell, &q);
+        return q;
     }
-    *n_edges = ne;
+    const uint64_t* table(size_t k) const { return tab + k * tsz; }
+};
+
+// The step behind every correlation launch over ntab tables: on the device path mosaic_peak_kernel, then ONE copy of the flag and
+// the records (or the tables) to `land`, ONE synchronisation, the bookkeeping (`decided` tables count as decided) and the flag.
+int reg_fetch(dsss_ctx* c, const reg_mem& M, size_t ntab, size_t decided, const reg_pass& P, double grid_cell, void* land, reg_count& cnt, reg_view* v)
+{
+    const size_t tsz = reg_table_words(P.radius), down = M.down_bytes(ntab, tsz);
+    if (M.dev) { const int rc = reg_launch_peaks(c, M.tab, (long long)ntab, P.radius, P.min_cells, P.cell, M.rec); if (rc) return rc; }
+    HIPCHK(c, hipMemcpyAsync(land, M.flag, down, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    cnt.down(down); cnt.sync();
+    if (*static_cast<const int*>(land)) DSSS_FAIL(c, DSSS_E_CAPACITY, "mosaic: a cell received more than 2^24 samples of one frame (cell %g too coarse)", grid_cell);
+    (M.dev ? cnt.I.tables_device : cnt.I.tables_host) += (int64_t)decided;
+    const char* payload = static_cast<const char*>(land) + 8;
+    *v = reg_view{ M.dev, reinterpret_cast<const dsss_reg_result*>(payload), reinterpret_cast<const uint64_t*>(payload), tsz, P };
+    return DSSS_OK;
+}
+
+// a row that gets a centroid: its two layers with their windows, and the row, whose record holds the peak
+struct cen_src { const uint16_t* la; const mosaic_win* A; const uint16_t* lb; const mosaic_win* Bw; dsss_reg_seg* o; };
+
+// The centroid sums of the rows that have a peak: row_of(row, &src) says which (false: the row keeps sx = sy = 0).  One launch, one
+// download, n held against the record's, sx and sy written.  bounded: the entry has bounded the workgroups before it launched anything.
+template <class RowOf> int reg_centroids(dsss_ctx* c, const reg_mem& M, int nseg, bool bounded, reg_count& cnt, RowOf row_of)
+{
+    std::vector<cen_job> cj; std::vector<dsss_reg_seg*> into(nseg, nullptr);
+    long long cblocks = 0;
+    for (int row = 0; row < nseg; ++row) {
+        cen_src s;
+        if (!row_of(row, &s)) continue;
+        into[row] = s.o;
+        if (cen_push_job(cj, &cblocks, s.la, *s.A, s.lb, *s.Bw, s.o->r, M.cen + (size_t)row * 3)) continue;
+        if (bounded) DSSS_FAIL(c, DSSS_E_NUMERIC, "register: internal error, the centroid of %d segments takes more workgroups than was bounded", nseg);
+        DSSS_FAIL(c, DSSS_E_ARG, "register: %d segments are more than one launch takes", nseg);
+    }
+    if (cj.empty()) return DSSS_OK;
+    std::vector<uint64_t> cen((size_t)nseg * 3);
+    HIPCHK(c, hipMemcpyAsync(M.cj, cj.data(), cj.size() * sizeof(cen_job), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(mosaic_centroid_kernel, dim3((unsigned)cblocks), dim3(256), 0, c->stream, M.cj, (int)cj.size());
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(cen.data(), M.cen, cen.size() * 8, hipMemcpyDeviceToHost, c->stream));      // (M.cen was cleared before the first launch)
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    cnt.down(cen.size() * 8); cnt.sync();
+    for (int row = 0; row < nseg; ++row) {
+        dsss_reg_seg* o = into[row];
+        if (!o) continue;
+        if ((int64_t)cen[(size_t)row * 3] != o->r.n)
+            DSSS_FAIL(c, DSSS_E_NUMERIC, "register: internal error, row %d has %lld cells at its peak and %lld in its centroid", row,
+                      (long long)o->r.n, (long long)cen[(size_t)row * 3]);
+        o->sx = (int64_t)cen[(size_t)row * 3 + 1]; o->sy = (int64_t)cen[(size_t)row * 3 + 2];
+    }
     return DSSS_OK;
 }
 
 // ---- the cell pyramid
-#define PYR_MAX_CENTRE (1 << 28)           // |cx|, |cy| of a level's centre: twice the centre plus the radius stays an int32
-
-bool pyr_ok(const dsss_reg_pyr_params& P) { return P.levels >= 1 && P.levels <= PYR_MAX_LEVELS && (P.levels == 1 || (P.refine >= 1 && P.refine <= REG_MAX_RADIUS)); }
-
-// the level rule of the header, "dense loop closures over a cell pyramid": the one place it is written.  sums = the table of level
-// `level` around the centre (cx, cy); min_cells and cell are the level-0 values.  It has two parts: the record of the level's table
-// under pyr_min_cells and the level's cell (peak_of on the host, mosaic_peak_kernel on the device), and pyr_centre_of, which adds the
-// centre to that record (*out) and is host arithmetic on both paths.
-void pyr_centre_of(double cell, int level, int cx, int cy, dsss_reg_result* out, int32_t* usable, int32_t* ncx, int32_t* ncy)
-{
-    const double cell_l = ldexp(cell, level);
-    *usable = out->zncc > -2.0 ? 1 : 0;
-    if (!*usable) return;                                                       // the no-usable-shift record as it is: no centre is added to it
-    out->dx += cx; out->dy += cy;
-    const double mx = (double)cx * cell_l, my = (double)cy * cell_l;            // one multiply and one add each, unfused (-ffp-contract=off)
-    out->off_x = out->off_x + mx; out->off_y = out->off_y + my;
-    if (level > 0) { *ncx = 2 * out->dx; *ncy = 2 * out->dy; }
-}
-int pyr_min_cells(int min_cells, int level) { return std::max(1, min_cells >> (2 * level)); }
-void pyr_step_of(const uint64_t* sums, int radius, int min_cells, double cell, int level, int cx, int cy, dsss_reg_result* out, int32_t* usable,
-                 int32_t* ncx, int32_t* ncy)
-{
-    peak_of(sums, radius, pyr_min_cells(min_cells, level), ldexp(cell, level), out);
-    pyr_centre_of(cell, level, cx, cy, out, usable, ncx, ncy);
-}
-
 // the window of level l that the fine window w covers (only ox, oy, bw, bh differ), moved by (-cx, -cy)
 mosaic_win pyr_window(const mosaic_win& w, int l, int cx, int cy)
 {
@@ -631,109 +698,62 @@ mosaic_win pyr_window(const mosaic_win& w, int l, int cx, int cy)
     return q;
 }
 
+// A row after level l, q = the level's record with the centre added (pyr_centre_of).  Not usable: the row dies, and no level having a
+// usable peak leaves the top level's record; otherwise the level, its shift, score and border bit, and (nx, ny) = the centre below.
+void pyr_apply(dsss_reg_seg_pyr& o, const dsss_reg_result& q, bool usable, int l, bool top, int32_t nx, int32_t ny, char* alive, int32_t* cx, int32_t* cy)
+{
+    if (!usable) { *alive = 0; if (top) o.s.r = q; return; }
+    o.s.r = q; o.level = l; o.lx[l] = q.dx; o.ly[l] = q.dy; o.lz[l] = q.zncc;
+    if (q.on_border) o.border_mask |= 1 << l;
+    *cx = nx; *cy = ny;
+}
+
 } // namespace
 
 extern "C" {
-
-void dsss_reg_params_default(dsss_reg_params* p) { if (p) { p->radius = 8; p->min_cells = 256; } }
-
-int dsss_mosaic_register_peak(const uint64_t* sums, int radius, int min_cells, double cell, dsss_reg_result* out)
-{
-    if (!sums || !out || radius < 0 || radius > REG_MAX_RADIUS || min_cells < 1 || !(cell > 0.0) || !std::isfinite(cell)) return DSSS_E_ARG;
-    return peak_of(sums, radius, min_cells, cell, out);
-}
 
 int dsss_mosaic_register(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, const dsss_mosaic_params* p,
                          const int* pair_a, const int* pair_b, int npairs, const dsss_reg_params* rp,
                          dsss_reg_result* out_host, uint64_t* sums_host)
 {
     if (!c) return DSSS_E_ARG;
-    size_t rows = 0;
-    dsss_reg_params R; std::vector<int> slot;                                   // slot: frame id -> its index in ids
-    int rc = reg_check(c, ids, n, rpy6, ping_off, p, pair_a, pair_b, npairs, rp, out_host, &R, slot, &rows); if (rc) return rc;
-    std::vector<char> used(n, 0);
-    for (int k = 0; k < npairs; ++k) used[slot[pair_a[k]]] = used[slot[pair_b[k]]] = 1;
+    reg_rows Q;
+    int rc = Q.check(c, ids, n, rpy6, ping_off, p, pair_a, pair_b, npairs, rp, out_host); if (rc) return rc;
     reg_count cnt;
     if (npairs == 0) { c->reg_info = cnt.I; return DSSS_OK; }
-    const bool dev = !sums_host && !dsss_switches_read().reg_peaks_host;       // the peaks on the device: nobody reads the table on the host
+    Q.mark(sums_host);
     HIPCHK(c, hipSetDevice(c->device));
-    const int r = R.radius, S = 2 * r + 1, nshift = S * S;
-    // the window of every frame that occurs in a pair: the cells its geo extremes can reach (as the consistency map's)
-    std::vector<mosaic_win> wins(n); std::vector<char> on_grid(n, 0); std::vector<size_t> lay_off(n, 0);
-    size_t win_cells = 1, lay_cells = 0;
-    for (int i = 0; i < n; ++i) {
-        if (!used[i]) continue;
-        const dsss_frame& f = c->frames[ids[i]];
-        if (!reg_window(f, rpy6 ? rpy6 + (size_t)ping_off[i] * 6 : f.h_geo, 0, f.N, p, &wins[i])) continue;
-        on_grid[i] = 1;
-        const size_t wc = (size_t)wins[i].bw * wins[i].bh;
-        win_cells = std::max(win_cells, wc);
-        lay_off[i] = lay_cells; lay_cells += (wc + 127) & ~(size_t)127;        // layers start on 256 bytes
-    }
-    const size_t table = (size_t)npairs * nshift * 6;
-    carve L;
-    const size_t o_lay = L.take(lay_cells * 2), o_win = L.take(win_cells * 8), o_jobs = L.take((size_t)n * sizeof(mosaic_job)),
-                 o_rows = L.take(rpy6 ? rows * 6 * sizeof(double) : 0), o_pairs = L.take((size_t)npairs * sizeof(reg_job)),
-                 o_tab = L.take((table + 1) * 8),                               // the sums and, behind them, the sample-limit flag: one download
-                 o_rec = L.take(dev ? ((size_t)npairs + 1) * sizeof(dsss_reg_result) : 0);      // device path: the records and, behind them, the flag
-    rc = c->mosaic_buf.reserve(c, L.off); if (rc) return rc;
-    if (dev) { rc = c->mosaic_pinned.reserve(c, (size_t)npairs * sizeof(dsss_reg_result) + 8); if (rc) return rc; }
-    char* B = c->mosaic_buf.as<char>();
-    uint16_t* d_lay = reinterpret_cast<uint16_t*>(B + o_lay);
-    unsigned long long* d_win = reinterpret_cast<unsigned long long*>(B + o_win);
-    mosaic_job* d_jobs = reinterpret_cast<mosaic_job*>(B + o_jobs);
-    reg_job* d_pairs = reinterpret_cast<reg_job*>(B + o_pairs);
-    unsigned long long* d_tab = reinterpret_cast<unsigned long long*>(B + o_tab);
-    dsss_reg_result* d_rec = reinterpret_cast<dsss_reg_result*>(B + o_rec);
-    int* d_flag = dev ? reinterpret_cast<int*>(d_rec + npairs) : reinterpret_cast<int*>(d_tab + table);
-    std::vector<const double*> dev_rows;
-    rc = upload_rows(c, ids, n, rpy6, ping_off, reinterpret_cast<double*>(B + o_rows), dev_rows); if (rc) return rc;
-    std::vector<mosaic_job> jobs(n);
-    for (int i = 0; i < n; ++i) { const dsss_frame& f = c->frames[ids[i]]; jobs[i] = mosaic_job{ dev_rows[i], f.gr, f.lvl[0], f.mask, f.N, f.M, 0, 0 }; }
-    HIPCHK(c, hipMemcpyAsync(d_jobs, jobs.data(), (size_t)n * sizeof(mosaic_job), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(d_tab, 0, (table + 1) * 8, c->stream));
-    if (dev) HIPCHK(c, hipMemsetAsync(d_flag, 0, 8, c->stream));
-    // 1. mean layers: scatter into the 64-bit window, pack into the frame's resident u16 layer
-    for (int i = 0; i < n; ++i) {
-        if (!on_grid[i]) continue;
-        const size_t wc = (size_t)wins[i].bw * wins[i].bh;
-        HIPCHK(c, hipMemsetAsync(d_win, 0, wc * 8, c->stream));
-        launch_scatter(c, d_jobs + i, 1, jobs[i].N, wins[i], d_win);
-        hipLaunchKernelGGL(mosaic_mean_kernel, dim3((unsigned)((wc + 255) / 256)), dim3(256), 0, c->stream, d_win, wc, d_lay + lay_off[i], d_flag);
-        HIPCHK(c, hipGetLastError());
-    }
+    const reg_pass P{ Q.R.radius, Q.R.min_cells, p->cell };
+    const size_t tsz = reg_table_words(P.radius), table = (size_t)npairs * tsz;
+    reg_layers W(n);                                                            // every frame that occurs in a pair is rendered whole
+    for (int i = 0; i < n; ++i) if (Q.as_a[i] || Q.as_b[i]) W.add_a(Q, i, p);
+    reg_mem M;
+    M.take(W.lay_cells, W.win_cells, n, rpy6 ? Q.traj_rows : 0, npairs, false, table, Q.dev);
+    rc = M.reserve(c); if (rc) return rc;
+    if (Q.dev) { rc = c->mosaic_pinned.reserve(c, M.down_bytes(npairs, tsz)); if (rc) return rc; }
+    std::vector<mosaic_job> jobs;
+    rc = reg_upload_jobs(Q, M, jobs); if (rc) return rc;
+    rc = M.clear_both(c, table); if (rc) return rc;
+    // 1. mean layers
+    for (int i = 0; i < n; ++i) if (W.on_grid[i]) { rc = reg_render_a(c, M, W, i, jobs[i].N); if (rc) return rc; }
     // 2. all pairs in one launch
     std::vector<reg_job> pj; pj.reserve(npairs);
     long long blocks = 0;
     for (int k = 0; k < npairs; ++k) {
-        const int ia = slot[pair_a[k]], ib = slot[pair_b[k]];
-        if (!on_grid[ia] || !on_grid[ib]) continue;
-        if (!reg_push_job(pj, &blocks, d_lay + lay_off[ia], wins[ia], d_lay + lay_off[ib], wins[ib], r, d_tab + (size_t)k * nshift * 6))
+        const int ia = Q.slot[pair_a[k]], ib = Q.slot[pair_b[k]];
+        if (!W.on_grid[ia] || !W.on_grid[ib]) continue;
+        if (!reg_push_job(pj, &blocks, M.lay + W.lay_off[ia], W.wins[ia], M.lay + W.lay_off[ib], W.wins[ib], P.radius, M.tab + (size_t)k * tsz))
             DSSS_FAIL(c, DSSS_E_ARG, "register: %d pairs are more than one launch takes", npairs);
     }
-    rc = reg_launch_corr(c, pj, blocks, d_pairs, r); if (rc) return rc;
-    if (dev) {                                                                  // the records and the flag in one copy; the table stays where it is
-        rc = reg_launch_peaks(c, d_tab, npairs, r, R.min_cells, p->cell, d_rec); if (rc) return rc;
-        const size_t down = (size_t)npairs * sizeof(dsss_reg_result) + 8;
-        HIPCHK(c, hipMemcpyAsync(c->mosaic_pinned.p, d_rec, down, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        cnt.down(down); cnt.sync();
-        const dsss_reg_result* rec = c->mosaic_pinned.as<dsss_reg_result>();
-        if (*reinterpret_cast<const int*>(rec + npairs)) DSSS_FAIL(c, DSSS_E_CAPACITY, "mosaic: a cell received more than 2^24 samples of one frame (cell %g too coarse)", p->cell);
-        memcpy(out_host, rec, (size_t)npairs * sizeof(dsss_reg_result));
-        cnt.I.tables_device = npairs; c->reg_info = cnt.I;
-        return DSSS_OK;
-    }
+    rc = reg_launch_corr(c, pj, blocks, M.pairs, P.radius); if (rc) return rc;
+    // 3. the records come down into the page-locked area; a table of the whole-frame form (138 MB-class) into pageable memory of this call
     std::vector<uint64_t> own;
-    uint64_t* tab = nullptr;
-    own.resize(table + 1); tab = own.data();
-    HIPCHK(c, hipMemcpyAsync(tab, d_tab, (table + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    cnt.down((table + 1) * 8); cnt.sync();
-    if ((int)tab[table]) DSSS_FAIL(c, DSSS_E_CAPACITY, "mosaic: a cell received more than 2^24 samples of one frame (cell %g too coarse)", p->cell);
-    for (int k = 0; k < npairs; ++k) peak_of(tab + (size_t)k * nshift * 6, r, R.min_cells, p->cell, out_host + k);
-    if (sums_host) memcpy(sums_host, tab, table * 8);
-    cnt.I.tables_host = npairs; c->reg_info = cnt.I;
+    if (!Q.dev) own.resize(1 + table);
+    reg_view v;
+    rc = reg_fetch(c, M, npairs, npairs, P, p->cell, Q.dev ? c->mosaic_pinned.p : (void*)own.data(), cnt, &v); if (rc) return rc;
+    for (int k = 0; k < npairs; ++k) out_host[k] = v.record(k);
+    if (sums_host) memcpy(sums_host, v.table(0), table * 8);
+    c->reg_info = cnt.I;
     return DSSS_OK;
 }
 
@@ -747,191 +767,78 @@ int dsss_mosaic_register_segments(dsss_ctx* c, const int* ids, int n, const doub
                                   dsss_reg_seg* out_host, int cap, int* nseg_host, uint64_t* sums_host)
 {
     if (!c) return DSSS_E_ARG;
-    size_t rows = 0;
-    dsss_reg_params R; std::vector<int> slot;
-    int rc = reg_check(c, ids, n, rpy6, ping_off, p, pair_a, pair_b, npairs, rp, out_host, &R, slot, &rows); if (rc) return rc;
-    if (seg_pings < 1) DSSS_FAIL(c, DSSS_E_ARG, "register: seg_pings = %d", seg_pings);
-    if (!nseg_host || cap < 0) DSSS_FAIL(c, DSSS_E_ARG, "register: %s", nseg_host ? "negative capacity" : "nowhere to write the number of segments");
-    auto segs_of = [&](int i) { return (int)(((long long)c->frames[ids[i]].N + seg_pings - 1) / seg_pings); };
-    auto seg_end = [&](int s, int N) { return (int)std::min((long long)(s + 1) * seg_pings, (long long)N); };
-    long long total = 0;
-    for (int k = 0; k < npairs; ++k) total += segs_of(slot[pair_b[k]]);
-    if (total > 0x7fffffffll) DSSS_FAIL(c, DSSS_E_ARG, "register: %lld segments", total);
-    *nseg_host = (int)total;                                                    // also when there is no room for them: the caller learns how many
-    if (total > cap) DSSS_FAIL(c, DSSS_E_CAPACITY, "register: %lld segments, room for %d", total, cap);
+    reg_rows Q;
+    int rc = Q.check(c, ids, n, rpy6, ping_off, p, pair_a, pair_b, npairs, rp, out_host); if (rc) return rc;
+    rc = Q.check_segments(seg_pings, nseg_host, cap); if (rc) return rc;
+    rc = Q.count(1, cap, nseg_host, sums_host); if (rc) return rc;
     reg_count cnt;
-    if (total == 0) { c->reg_info = cnt.I; return DSSS_OK; }
-    const int nseg = (int)total;
-    const bool dev = !sums_host && !dsss_switches_read().reg_peaks_host;       // the peaks on the device: nobody reads the table on the host
-    std::vector<char> as_a(n, 0), as_b(n, 0);
-    for (int k = 0; k < npairs; ++k) { as_a[slot[pair_a[k]]] = 1; as_b[slot[pair_b[k]]] = 1; }
+    if (Q.nseg == 0) { c->reg_info = cnt.I; return DSSS_OK; }
+    const int nseg = Q.nseg;
     HIPCHK(c, hipSetDevice(c->device));
-    const int r = R.radius, S = 2 * r + 1, nshift = S * S;
+    const reg_pass P{ Q.R.radius, Q.R.min_cells, p->cell };
+    const size_t tsz = reg_table_words(P.radius), table = (size_t)nseg * tsz;
     // windows: the whole frame where it occurs as a, every segment where it occurs as b
-    std::vector<mosaic_win> wins(n); std::vector<char> on_grid(n, 0); std::vector<size_t> lay_off(n, 0), seg_lay(n, 0), seg_cells(n, 0);
-    std::vector<int> seg0(n, 0);                                                // a frame's first segment in sw / hseg
+    reg_layers W(n);
+    std::vector<size_t> seg0(n, 0), seg_lay(n, 0), seg_cells(n, 0);             // a frame's first segment in sw / hseg, its segments' layers and accumulators
     std::vector<mosaic_win> sw; std::vector<mosaic_seg> hseg;
-    size_t win_cells = 1, lay_cells = 0;
     for (int i = 0; i < n; ++i) {
-        const dsss_frame& f = c->frames[ids[i]];
-        const double* fr = rpy6 ? rpy6 + (size_t)ping_off[i] * 6 : f.h_geo;
-        if (as_a[i] && reg_window(f, fr, 0, f.N, p, &wins[i])) {
-            on_grid[i] = 1;
-            const size_t wc = (size_t)wins[i].bw * wins[i].bh;
-            win_cells = std::max(win_cells, wc);
-            lay_off[i] = lay_cells; lay_cells += (wc + 127) & ~(size_t)127;    // layers start on 256 bytes
-        }
-        if (!as_b[i]) continue;
-        seg0[i] = (int)sw.size();
+        if (Q.as_a[i]) W.add_a(Q, i, p);
+        if (!Q.as_b[i]) continue;
+        const dsss_frame& f = Q.frame(i);
+        seg0[i] = sw.size();
         size_t cells = 0;
-        for (int s = 0; s < segs_of(i); ++s) {
-            mosaic_win w{ p->x0, p->y0, p->cell, p->W, p->H, 0, 0, 0, 0, p->use_mask != 0 };      // bw = 0: not on the grid
-            reg_window(f, fr, s * seg_pings, seg_end(s, f.N), p, &w);
+        for (int s = 0; s < Q.segs_of(i); ++s) {
+            mosaic_win w = reg_grid(p);
+            reg_window(f, Q.rows_of(i), s * seg_pings, Q.seg_end(s, f.N), p, &w);
             sw.push_back(w); hseg.push_back(mosaic_seg{ w.ox, w.oy, w.bw, w.bh, (unsigned long long)cells });
-            cells += ((size_t)w.bw * w.bh + 127) & ~(size_t)127;
+            cells += reg_round((size_t)w.bw * w.bh);
         }
-        seg_cells[i] = cells; win_cells = std::max(win_cells, cells);
-        seg_lay[i] = lay_cells; lay_cells += cells;
+        seg_cells[i] = cells; seg_lay[i] = W.add_b(cells);
     }
-    const size_t table = (size_t)nseg * nshift * 6;
-    carve L;
-    const size_t o_lay = L.take(lay_cells * 2), o_win = L.take(win_cells * 8), o_jobs = L.take((size_t)n * sizeof(mosaic_job)),
-                 o_rows = L.take(rpy6 ? rows * 6 * sizeof(double) : 0), o_segs = L.take(hseg.size() * sizeof(mosaic_seg)),
-                 o_pairs = L.take((size_t)nseg * sizeof(reg_job)), o_cj = L.take((size_t)nseg * sizeof(cen_job)),
-                 o_cen = L.take((size_t)nseg * 3 * 8), o_tab = L.take((table + 1) * 8),      // the sums and, behind them, the sample-limit flag
-                 o_rec = L.take(dev ? ((size_t)nseg + 1) * sizeof(dsss_reg_result) : 0);      // device path: the records and, behind them, the flag
-    rc = c->mosaic_buf.reserve(c, L.off); if (rc) return rc;
-    const size_t down = dev ? (size_t)nseg * sizeof(dsss_reg_result) + 8 : (table + 1) * 8;      // what comes down behind the correlation
-    rc = c->mosaic_pinned.reserve(c, down); if (rc) return rc;
-    char* B = c->mosaic_buf.as<char>();
-    uint16_t* d_lay = reinterpret_cast<uint16_t*>(B + o_lay);
-    unsigned long long* d_win = reinterpret_cast<unsigned long long*>(B + o_win);
-    mosaic_job* d_jobs = reinterpret_cast<mosaic_job*>(B + o_jobs);
-    mosaic_seg* d_segs = reinterpret_cast<mosaic_seg*>(B + o_segs);
-    reg_job* d_pairs = reinterpret_cast<reg_job*>(B + o_pairs);
-    cen_job* d_cj = reinterpret_cast<cen_job*>(B + o_cj);
-    unsigned long long* d_cen = reinterpret_cast<unsigned long long*>(B + o_cen);
-    unsigned long long* d_tab = reinterpret_cast<unsigned long long*>(B + o_tab);
-    dsss_reg_result* d_rec = reinterpret_cast<dsss_reg_result*>(B + o_rec);
-    int* d_flag = dev ? reinterpret_cast<int*>(d_rec + nseg) : reinterpret_cast<int*>(d_tab + table);
-    std::vector<const double*> dev_rows;
-    rc = upload_rows(c, ids, n, rpy6, ping_off, reinterpret_cast<double*>(B + o_rows), dev_rows); if (rc) return rc;
-    std::vector<mosaic_job> jobs(n);
-    for (int i = 0; i < n; ++i) { const dsss_frame& f = c->frames[ids[i]]; jobs[i] = mosaic_job{ dev_rows[i], f.gr, f.lvl[0], f.mask, f.N, f.M, 0, 0 }; }
-    HIPCHK(c, hipMemcpyAsync(d_jobs, jobs.data(), (size_t)n * sizeof(mosaic_job), hipMemcpyHostToDevice, c->stream));
+    reg_mem M;
+    M.take(W.lay_cells, W.win_cells, n, rpy6 ? Q.traj_rows : 0, nseg, true, table, Q.dev);
+    const reg_piece<mosaic_seg> o_segs = M.A.take<mosaic_seg>(hseg.size());
+    rc = M.reserve(c); if (rc) return rc;
+    rc = c->mosaic_pinned.reserve(c, M.down_bytes(nseg, tsz)); if (rc) return rc;
+    mosaic_seg* d_segs = M.A.at(o_segs);
+    std::vector<mosaic_job> jobs;
+    rc = reg_upload_jobs(Q, M, jobs); if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(d_segs, hseg.data(), hseg.size() * sizeof(mosaic_seg), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(d_tab, 0, (table + 1) * 8, c->stream));
-    if (dev) HIPCHK(c, hipMemsetAsync(d_flag, 0, 8, c->stream));
-    HIPCHK(c, hipMemsetAsync(d_cen, 0, (size_t)nseg * 3 * 8, c->stream));
+    rc = M.clear_both(c, table); if (rc) return rc;
+    HIPCHK(c, hipMemsetAsync(M.cen, 0, (size_t)nseg * 3 * 8, c->stream));
     // 1. mean layers: a frame's whole layer where it is an a, the layers of all its segments (one scatter, one pack) where it is a b
-    const mosaic_win grid{ p->x0, p->y0, p->cell, p->W, p->H, 0, 0, 0, 0, p->use_mask != 0 };
+    const mosaic_win grid = reg_grid(p);
     for (int i = 0; i < n; ++i) {
-        if (on_grid[i]) {
-            const size_t wc = (size_t)wins[i].bw * wins[i].bh;
-            HIPCHK(c, hipMemsetAsync(d_win, 0, wc * 8, c->stream));
-            launch_scatter(c, d_jobs + i, 1, jobs[i].N, wins[i], d_win);
-            hipLaunchKernelGGL(mosaic_mean_kernel, dim3((unsigned)((wc + 255) / 256)), dim3(256), 0, c->stream, d_win, wc, d_lay + lay_off[i], d_flag);
-            HIPCHK(c, hipGetLastError());
-        }
-        if (as_b[i] && seg_cells[i]) {
-            const size_t wc = seg_cells[i];
-            HIPCHK(c, hipMemsetAsync(d_win, 0, wc * 8, c->stream));
-            launch_scatter_seg(c, d_jobs + i, jobs[i].N, grid, d_win, d_segs + seg0[i], seg_pings);
-            hipLaunchKernelGGL(mosaic_mean_kernel, dim3((unsigned)((wc + 255) / 256)), dim3(256), 0, c->stream, d_win, wc, d_lay + seg_lay[i], d_flag);
-            HIPCHK(c, hipGetLastError());
+        if (W.on_grid[i]) { rc = reg_render_a(c, M, W, i, jobs[i].N); if (rc) return rc; }
+        if (Q.as_b[i] && seg_cells[i]) {
+            rc = reg_render_b(c, M, seg_cells[i], seg_lay[i], [&] { launch_scatter_seg(c, M.jobs + i, jobs[i].N, grid, M.win, d_segs + seg0[i], seg_pings); });
+            if (rc) return rc;
         }
     }
-    // 2. one correlation job per (pair, segment), all in one launch; the rows are laid out here, by pair and then by segment
+    // 2. one correlation job per row, all in one launch
     memset(out_host, 0, (size_t)nseg * sizeof(dsss_reg_seg));
+    Q.layout(seg0, 1, [&](int row) -> dsss_reg_seg& { return out_host[row]; });
+    auto layer_b = [&](int row) { return M.lay + seg_lay[Q.row_b[row]] + hseg[Q.row_g[row]].off; };
     std::vector<reg_job> pj; pj.reserve(nseg);
-    std::vector<int> row_a(nseg), row_g(nseg);                                  // a row's frame a (index in ids) and its segment in sw / hseg
     long long blocks = 0;
-    int row = 0;
-    for (int k = 0; k < npairs; ++k) {
-        const int ia = slot[pair_a[k]], ib = slot[pair_b[k]];
-        const int Nb = c->frames[ids[ib]].N;
-        for (int s = 0; s < segs_of(ib); ++s, ++row) {
-            dsss_reg_seg& o = out_host[row];
-            o.pair = k; o.seg = s; o.p0 = s * seg_pings; o.p1 = seg_end(s, Nb);
-            const int g = seg0[ib] + s;
-            row_a[row] = ia; row_g[row] = g;
-            if (!on_grid[ia] || sw[g].bw == 0) continue;
-            if (!reg_push_job(pj, &blocks, d_lay + lay_off[ia], wins[ia], d_lay + seg_lay[ib] + hseg[g].off, sw[g], r, d_tab + (size_t)row * nshift * 6))
-                DSSS_FAIL(c, DSSS_E_ARG, "register: %d segments are more than one launch takes", nseg);
-        }
-    }
-    rc = reg_launch_corr(c, pj, blocks, d_pairs, r); if (rc) return rc;
-    if (dev) { rc = reg_launch_peaks(c, d_tab, nseg, r, R.min_cells, p->cell, d_rec); if (rc) return rc; }
-    const uint64_t* tab = c->mosaic_pinned.as<uint64_t>();                      // host path: the table and the flag
-    const dsss_reg_result* rec = c->mosaic_pinned.as<dsss_reg_result>();        // device path: the records and the flag
-    HIPCHK(c, hipMemcpyAsync(c->mosaic_pinned.p, dev ? (const void*)d_rec : (const void*)d_tab, down, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    cnt.down(down); cnt.sync();
-    if (dev ? *reinterpret_cast<const int*>(rec + nseg) : (int)tab[table])
-        DSSS_FAIL(c, DSSS_E_CAPACITY, "mosaic: a cell received more than 2^24 samples of one frame (cell %g too coarse)", p->cell);
-    (dev ? cnt.I.tables_device : cnt.I.tables_host) = nseg;
-    // 3. the peaks (the device's records, or decided here from the table), then the centroid sums of the rows that have one: one launch, one download
-    std::vector<cen_job> cj;
-    long long cblocks = 0;
-    for (row = 0; row < nseg; ++row) {
-        dsss_reg_result& q = out_host[row].r;
-        if (dev) q = rec[row]; else peak_of(tab + (size_t)row * nshift * 6, r, R.min_cells, p->cell, &q);
-        if (!(q.zncc > -2.0)) continue;                                         // no usable shift: sx = sy = 0
-        if (!cen_push_job(cj, &cblocks, d_lay + lay_off[row_a[row]], wins[row_a[row]], d_lay + seg_lay[slot[pair_b[out_host[row].pair]]] + hseg[row_g[row]].off,
-                          sw[row_g[row]], q, d_cen + (size_t)row * 3))
+    for (int row = 0; row < nseg; ++row) {
+        const int ia = Q.row_a[row]; const size_t g = Q.row_g[row];
+        if (!W.on_grid[ia] || sw[g].bw == 0) continue;
+        if (!reg_push_job(pj, &blocks, M.lay + W.lay_off[ia], W.wins[ia], layer_b(row), sw[g], P.radius, M.tab + (size_t)row * tsz))
             DSSS_FAIL(c, DSSS_E_ARG, "register: %d segments are more than one launch takes", nseg);
     }
-    if (!cj.empty()) {
-        std::vector<uint64_t> cen((size_t)nseg * 3);
-        rc = reg_launch_centroids(c, cj, cblocks, d_cj, d_cen, cen, cnt); if (rc) return rc;
-        for (row = 0; row < nseg; ++row) {
-            dsss_reg_seg& o = out_host[row];
-            if (!(o.r.zncc > -2.0)) continue;
-            if ((int64_t)cen[(size_t)row * 3] != o.r.n)
-                DSSS_FAIL(c, DSSS_E_NUMERIC, "register: internal error, row %d has %lld cells at its peak and %lld in its centroid", row,
-                          (long long)o.r.n, (long long)cen[(size_t)row * 3]);
-            o.sx = (int64_t)cen[(size_t)row * 3 + 1]; o.sy = (int64_t)cen[(size_t)row * 3 + 2];
-        }
-    }
-    if (sums_host) memcpy(sums_host, tab, table * 8);
+    rc = reg_launch_corr(c, pj, blocks, M.pairs, P.radius); if (rc) return rc;
+    reg_view v;
+    rc = reg_fetch(c, M, nseg, nseg, P, p->cell, c->mosaic_pinned.p, cnt, &v); if (rc) return rc;
+    // 3. the peaks, then the centroid sums of the rows that have one
+    for (int row = 0; row < nseg; ++row) out_host[row].r = v.record(row);
+    rc = reg_centroids(c, M, nseg, false, cnt, [&](int row, cen_src* s) {
+        if (!(out_host[row].r.zncc > -2.0)) return false;                       // no usable shift: sx = sy = 0
+        *s = cen_src{ M.lay + W.lay_off[Q.row_a[row]], &W.wins[Q.row_a[row]], layer_b(row), &sw[Q.row_g[row]], &out_host[row] };
+        return true; });
+    if (rc) return rc;
+    if (sums_host) memcpy(sums_host, v.table(0), table * 8);
     c->reg_info = cnt.I;
-    return DSSS_OK;
-}
-
-void dsss_reg_edge_params_default(dsss_reg_edge_params* e) { if (e) { e->min_zncc = 0.5; e->sigma_xy_cells = 1.0; e->sigma_z = 10.0; e->sigma_rot = 1.0; } }
-
-int dsss_register_edge(const dsss_reg_seg* s, const dsss_mosaic_params* grid, const double* rows_a, int Na, int base_a,
-                       const double* rows_b, int Nb, int base_b, const dsss_reg_edge_params* ep, dsss_lc_edge* edge)
-{
-    dsss_reg_edge_params E; dsss_reg_edge_params_default(&E);
-    if (ep) E = *ep;
-    return edge_of(s, grid, rows_a, Na, base_a, rows_b, Nb, base_b, E, 0.0, 0.0, E.sigma_rot, edge);
-}
-
-int dsss_mosaic_register_edges(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, const dsss_mosaic_params* p,
-                               const int* pair_a, const int* pair_b, const dsss_reg_seg* segs, int nsegs, const dsss_reg_edge_params* ep,
-                               dsss_lc_edge* edges_host, int32_t* edge_seg_host, int cap, int* n_edges)
-{
-    return edges_loop(c, ids, n, rpy6, ping_off, p, pair_a, pair_b, segs != nullptr, nsegs, edges_host, edge_seg_host, cap, n_edges,
-                      [&](int k) -> const dsss_reg_seg& { return segs[k]; },
-                      [&](int k, const double* ra, int Na, int ba, const double* rb, int Nb, int bb, dsss_lc_edge* e) {
-                          return dsss_register_edge(segs + k, p, ra, Na, ba, rb, Nb, bb, ep, e); });
-}
-
-// ---- dense loop closures with a yaw fan
-void dsss_reg_yaw_params_default(dsss_reg_yaw_params* y) { if (y) { y->nyaw = 1; y->pad_ = 0; y->step = 0.01; } }
-
-int dsss_register_rotate_rows(const double* rows_b, int Nb, int p0, int p1, double theta, double* out)
-{
-    if (!rows_b || !out || p0 < 0 || p0 >= p1 || p1 > Nb || !std::isfinite(theta)) return DSSS_E_ARG;
-    rotate_rows(rows_b, p0, p1, theta, out);
-    return DSSS_OK;
-}
-
-int dsss_register_yaw_peak(const dsss_reg_result* per_angle, int nyaw, double step, int32_t* k, int32_t* yaw_on_border, double* theta, double* theta_hat)
-{
-    if (!per_angle || !k || !yaw_on_border || !theta || !theta_hat || !fan_ok(nyaw, step)) return DSSS_E_ARG;
-    yaw_peak_of(per_angle, nyaw, step, k, yaw_on_border, theta, theta_hat);
     return DSSS_OK;
 }
 
@@ -947,239 +854,121 @@ int dsss_mosaic_register_segments_yaw(dsss_ctx* c, const int* ids, int n, const 
                                       const dsss_reg_yaw_params* yp, dsss_reg_seg_yaw* out_host, int cap, int* nseg_host, uint64_t* sums_host)
 {
     if (!c) return DSSS_E_ARG;
-    size_t rows = 0;
-    dsss_reg_params R; std::vector<int> slot;
-    int rc = reg_check(c, ids, n, rpy6, ping_off, p, pair_a, pair_b, npairs, rp, out_host, &R, slot, &rows); if (rc) return rc;
-    if (seg_pings < 1) DSSS_FAIL(c, DSSS_E_ARG, "register: seg_pings = %d", seg_pings);
-    if (!nseg_host || cap < 0) DSSS_FAIL(c, DSSS_E_ARG, "register: %s", nseg_host ? "negative capacity" : "nowhere to write the number of segments");
+    reg_rows Q;
+    int rc = Q.check(c, ids, n, rpy6, ping_off, p, pair_a, pair_b, npairs, rp, out_host); if (rc) return rc;
+    rc = Q.check_segments(seg_pings, nseg_host, cap); if (rc) return rc;
     dsss_reg_yaw_params Y; dsss_reg_yaw_params_default(&Y);
     if (yp) Y = *yp;
     if (!fan_ok(Y.nyaw, Y.step)) DSSS_FAIL(c, DSSS_E_ARG, "register: a fan of %d angles, %g rad apart (an odd number up to %d, a positive step)", Y.nyaw, Y.step, REG_MAX_YAW);
     const int nyaw = Y.nyaw, mid = (nyaw - 1) / 2;
-    auto segs_of = [&](int i) { return (int)(((long long)c->frames[ids[i]].N + seg_pings - 1) / seg_pings); };
-    auto seg_end = [&](int s, int N) { return (int)std::min((long long)(s + 1) * seg_pings, (long long)N); };
-    long long total = 0;
-    for (int k = 0; k < npairs; ++k) {
-        const int ib = slot[pair_b[k]];
-        if ((long long)c->frames[ids[ib]].N * nyaw > 0x7fffffffll) DSSS_FAIL(c, DSSS_E_ARG, "register: frame %d has %d pings, too many for %d angles in one launch", ids[ib], c->frames[ids[ib]].N, nyaw);
-        total += segs_of(ib);
-    }
-    if (total > 0x7fffffffll) DSSS_FAIL(c, DSSS_E_ARG, "register: %lld segments", total);
-    *nseg_host = (int)total;                                                    // also when there is no room for them: the caller learns how many
-    if (total > cap) DSSS_FAIL(c, DSSS_E_CAPACITY, "register: %lld segments, room for %d", total, cap);
+    rc = Q.count(nyaw, cap, nseg_host, sums_host); if (rc) return rc;
     reg_count cnt;
-    if (total == 0) { c->reg_info = cnt.I; return DSSS_OK; }
-    const int nseg = (int)total;
-    const bool dev = !sums_host && !dsss_switches_read().reg_peaks_host;       // the peaks on the device: nobody reads the table on the host
-    std::vector<char> as_a(n, 0), as_b(n, 0);
-    for (int k = 0; k < npairs; ++k) { as_a[slot[pair_a[k]]] = 1; as_b[slot[pair_b[k]]] = 1; }
-    const int r = R.radius, S = 2 * r + 1, nshift = S * S;
+    if (Q.nseg == 0) { c->reg_info = cnt.I; return DSSS_OK; }
+    const int nseg = Q.nseg;
+    const reg_pass P{ Q.R.radius, Q.R.min_cells, p->cell };
+    const size_t tsz = reg_table_words(P.radius), table = (size_t)nseg * tsz;   // one angle's sums
     // windows: the whole frame where it occurs as a, every (segment, angle) where it occurs as b
-    std::vector<mosaic_win> wins(n); std::vector<char> on_grid(n, 0); std::vector<size_t> lay_off(n, 0), fan_lay(n, 0), fan_cells(n, 0);
-    std::vector<size_t> fan0(n, 0);                                             // a frame's first entry in sw / hfan; (segment s, angle k) is entry s nyaw + k behind it
+    reg_layers W(n);
+    std::vector<size_t> fan0(n, 0), fan_lay(n, 0), fan_cells(n, 0);             // a frame's first entry in sw / hfan; (segment s, angle k) is entry s nyaw + k behind it
     std::vector<mosaic_win> sw; std::vector<mosaic_fan> hfan;
     std::vector<double> rot;
-    size_t win_cells = 1, lay_cells = 0;
     for (int i = 0; i < n; ++i) {
-        const dsss_frame& f = c->frames[ids[i]];
-        const double* fr = rpy6 ? rpy6 + (size_t)ping_off[i] * 6 : f.h_geo;
-        if (as_a[i] && reg_window(f, fr, 0, f.N, p, &wins[i])) {
-            on_grid[i] = 1;
-            const size_t wc = (size_t)wins[i].bw * wins[i].bh;
-            win_cells = std::max(win_cells, wc);
-            lay_off[i] = lay_cells; lay_cells += (wc + 127) & ~(size_t)127;    // layers start on 256 bytes
-        }
-        if (!as_b[i]) continue;
+        if (Q.as_a[i]) W.add_a(Q, i, p);
+        if (!Q.as_b[i]) continue;
+        const dsss_frame& f = Q.frame(i);
+        const double* fr = Q.rows_of(i);
         fan0[i] = sw.size();
         size_t cells = 0;
-        for (int s = 0; s < segs_of(i); ++s) {
-            const int p0 = s * seg_pings, p1 = seg_end(s, f.N);
+        for (int s = 0; s < Q.segs_of(i); ++s) {
+            const int p0 = s * seg_pings, p1 = Q.seg_end(s, f.N);
             const double* piv = fr + (size_t)(((long long)p0 + p1) / 2) * 6;
             rot.resize((size_t)(p1 - p0) * 6);
             for (int k = 0; k < nyaw; ++k) {
-                mosaic_win w{ p->x0, p->y0, p->cell, p->W, p->H, 0, 0, 0, 0, p->use_mask != 0 };  // bw = 0: not on the grid
+                mosaic_win w = reg_grid(p);
                 mosaic_fan F; F.cx = piv[3]; F.cy = piv[4]; F.theta = fan_theta(k, nyaw, Y.step);
                 dsss_sincos(F.theta, &F.s, &F.c);
                 rotate_rows(fr, p0, p1, F.theta, rot.data());
                 reg_window(f, rot.data(), 0, p1 - p0, p, &w);
                 F.ox = w.ox; F.oy = w.oy; F.bw = w.bw; F.bh = w.bh; F.off = (unsigned long long)cells;
                 sw.push_back(w); hfan.push_back(F);
-                cells += ((size_t)w.bw * w.bh + 127) & ~(size_t)127;
+                cells += reg_round((size_t)w.bw * w.bh);
             }
         }
-        fan_cells[i] = cells; win_cells = std::max(win_cells, cells);
-        fan_lay[i] = lay_cells; lay_cells += cells;
+        fan_cells[i] = cells; fan_lay[i] = W.add_b(cells);
     }
-    const size_t table = (size_t)nseg * nshift * 6;                             // one angle's sums
     HIPCHK(c, hipSetDevice(c->device));
-    carve L;
-    const size_t o_lay = L.take(lay_cells * 2), o_win = L.take(win_cells * 8), o_jobs = L.take((size_t)n * sizeof(mosaic_job)),
-                 o_rows = L.take(rpy6 ? rows * 6 * sizeof(double) : 0), o_fan = L.take(hfan.size() * sizeof(mosaic_fan)),
-                 o_pairs = L.take((size_t)nseg * sizeof(reg_job)), o_cj = L.take((size_t)nseg * sizeof(cen_job)),
-                 o_cen = L.take((size_t)nseg * 3 * 8), o_tab = L.take((table + 1) * 8),      // the sums and, behind them, the sample-limit flag
-                 o_rec = L.take(dev ? ((size_t)nseg + 1) * sizeof(dsss_reg_result) : 0);      // device path: one angle's records and, behind them, the flag
-    rc = c->mosaic_buf.reserve(c, L.off); if (rc) return rc;
-    const size_t down = dev ? (size_t)nseg * sizeof(dsss_reg_result) + 8 : (table + 1) * 8;      // what comes down per pass
-    rc = c->mosaic_pinned.reserve(c, down); if (rc) return rc;
-    char* B = c->mosaic_buf.as<char>();
-    uint16_t* d_lay = reinterpret_cast<uint16_t*>(B + o_lay);
-    unsigned long long* d_win = reinterpret_cast<unsigned long long*>(B + o_win);
-    mosaic_job* d_jobs = reinterpret_cast<mosaic_job*>(B + o_jobs);
-    mosaic_fan* d_fan = reinterpret_cast<mosaic_fan*>(B + o_fan);
-    reg_job* d_pairs = reinterpret_cast<reg_job*>(B + o_pairs);
-    cen_job* d_cj = reinterpret_cast<cen_job*>(B + o_cj);
-    unsigned long long* d_cen = reinterpret_cast<unsigned long long*>(B + o_cen);
-    unsigned long long* d_tab = reinterpret_cast<unsigned long long*>(B + o_tab);
-    dsss_reg_result* d_rec = reinterpret_cast<dsss_reg_result*>(B + o_rec);
-    int* d_flag = dev ? reinterpret_cast<int*>(d_rec + nseg) : reinterpret_cast<int*>(d_tab + table);
-    // the rows and every pass's jobs, laid out by pair and then by segment, before anything is launched: what one launch cannot take
-    // is refused here.  A row's centroid region lies inside the correlation region of its angle, so the largest of those bounds it.
+    reg_mem M;
+    M.take(W.lay_cells, W.win_cells, n, rpy6 ? Q.traj_rows : 0, nseg, true, table, Q.dev);
+    const reg_piece<mosaic_fan> o_fan = M.A.take<mosaic_fan>(hfan.size());
+    rc = M.reserve(c); if (rc) return rc;
+    rc = c->mosaic_pinned.reserve(c, M.down_bytes(nseg, tsz)); if (rc) return rc;
+    mosaic_fan* d_fan = M.A.at(o_fan);
+    // the rows and every pass's jobs before anything is launched: what one launch cannot take is refused here.  A row's centroid
+    // region lies inside the correlation region of its angle, so the largest of those bounds it.
     memset(out_host, 0, (size_t)nseg * sizeof(dsss_reg_seg_yaw));
+    Q.layout(fan0, nyaw, [&](int row) -> dsss_reg_seg& { return out_host[row].s; });
+    auto layer_b = [&](int row, int a) { return M.lay + fan_lay[Q.row_b[row]] + hfan[Q.row_g[row] + a].off; };
     std::vector<std::vector<reg_job>> pj(nyaw);
     std::vector<long long> blocks(nyaw, 0);
-    std::vector<int> row_a(nseg); std::vector<size_t> row_g(nseg);              // a row's frame a (index in ids) and its segment's first entry in sw / hfan
     long long cen_bound = 0;
-    int row = 0;
-    for (int k = 0; k < npairs; ++k) {
-        const int ia = slot[pair_a[k]], ib = slot[pair_b[k]];
-        const int Nb = c->frames[ids[ib]].N;
-        for (int s = 0; s < segs_of(ib); ++s, ++row) {
-            dsss_reg_seg& o = out_host[row].s;
-            o.pair = k; o.seg = s; o.p0 = s * seg_pings; o.p1 = seg_end(s, Nb);
-            const size_t g = fan0[ib] + (size_t)s * nyaw;
-            row_a[row] = ia; row_g[row] = g;
-            if (!on_grid[ia]) continue;
-            long long most = 0;
-            for (int a = 0; a < nyaw; ++a) {
-                if (sw[g + a].bw == 0) continue;
-                const size_t before = pj[a].size();
-                if (!reg_push_job(pj[a], &blocks[a], d_lay + lay_off[ia], wins[ia], d_lay + fan_lay[ib] + hfan[g + a].off, sw[g + a], r, d_tab + (size_t)row * nshift * 6))
-                    DSSS_FAIL(c, DSSS_E_ARG, "register: %d segments are more than one launch takes", nseg);
-                if (pj[a].size() == before) continue;
-                const reg_job& J = pj[a].back();
-                most = std::max(most, (long long)((J.rx1 - J.rx0) / CEN_TW + 2) * ((J.ry1 - J.ry0) / CEN_TH + 2));
-            }
-            cen_bound += most;
+    for (int row = 0; row < nseg; ++row) {
+        const int ia = Q.row_a[row]; const size_t g = Q.row_g[row];
+        if (!W.on_grid[ia]) continue;
+        long long most = 0;
+        for (int a = 0; a < nyaw; ++a) {
+            if (sw[g + a].bw == 0) continue;
+            const size_t before = pj[a].size();
+            if (!reg_push_job(pj[a], &blocks[a], M.lay + W.lay_off[ia], W.wins[ia], layer_b(row, a), sw[g + a], P.radius, M.tab + (size_t)row * tsz))
+                DSSS_FAIL(c, DSSS_E_ARG, "register: %d segments are more than one launch takes", nseg);
+            if (pj[a].size() == before) continue;
+            const reg_job& J = pj[a].back();
+            most = std::max(most, (long long)((J.rx1 - J.rx0) / CEN_TW + 2) * ((J.ry1 - J.ry0) / CEN_TH + 2));
         }
+        cen_bound += most;
     }
     if (cen_bound > 0x7fffffffll) DSSS_FAIL(c, DSSS_E_ARG, "register: %d segments are more than one launch takes", nseg);
-    std::vector<const double*> dev_rows;
-    rc = upload_rows(c, ids, n, rpy6, ping_off, reinterpret_cast<double*>(B + o_rows), dev_rows); if (rc) return rc;
-    std::vector<mosaic_job> jobs(n);
-    for (int i = 0; i < n; ++i) { const dsss_frame& f = c->frames[ids[i]]; jobs[i] = mosaic_job{ dev_rows[i], f.gr, f.lvl[0], f.mask, f.N, f.M, 0, 0 }; }
-    HIPCHK(c, hipMemcpyAsync(d_jobs, jobs.data(), (size_t)n * sizeof(mosaic_job), hipMemcpyHostToDevice, c->stream));
+    std::vector<mosaic_job> jobs;
+    rc = reg_upload_jobs(Q, M, jobs); if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(d_fan, hfan.data(), hfan.size() * sizeof(mosaic_fan), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(d_flag, 0, 8, c->stream));
-    HIPCHK(c, hipMemsetAsync(d_cen, 0, (size_t)nseg * 3 * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(M.flag, 0, 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(M.cen, 0, (size_t)nseg * 3 * 8, c->stream));
     // 1. mean layers: a frame's whole layer where it is an a, the layers of all its segments under all angles (one scatter, one pack) where it is a b
-    const mosaic_win grid{ p->x0, p->y0, p->cell, p->W, p->H, 0, 0, 0, 0, p->use_mask != 0 };
+    const mosaic_win grid = reg_grid(p);
     for (int i = 0; i < n; ++i) {
-        if (on_grid[i]) {
-            const size_t wc = (size_t)wins[i].bw * wins[i].bh;
-            HIPCHK(c, hipMemsetAsync(d_win, 0, wc * 8, c->stream));
-            launch_scatter(c, d_jobs + i, 1, jobs[i].N, wins[i], d_win);
-            hipLaunchKernelGGL(mosaic_mean_kernel, dim3((unsigned)((wc + 255) / 256)), dim3(256), 0, c->stream, d_win, wc, d_lay + lay_off[i], d_flag);
-            HIPCHK(c, hipGetLastError());
-        }
-        if (as_b[i] && fan_cells[i]) {
-            const size_t wc = fan_cells[i];
-            HIPCHK(c, hipMemsetAsync(d_win, 0, wc * 8, c->stream));
-            hipLaunchKernelGGL(mosaic_scatter_fan_kernel, dim3((unsigned)jobs[i].N * (unsigned)nyaw), dim3(256), 0, c->stream, d_jobs + i, grid, d_win,
-                               d_fan + fan0[i], seg_pings, nyaw);
-            hipLaunchKernelGGL(mosaic_mean_kernel, dim3((unsigned)((wc + 255) / 256)), dim3(256), 0, c->stream, d_win, wc, d_lay + fan_lay[i], d_flag);
-            HIPCHK(c, hipGetLastError());
+        if (W.on_grid[i]) { rc = reg_render_a(c, M, W, i, jobs[i].N); if (rc) return rc; }
+        if (Q.as_b[i] && fan_cells[i]) {
+            rc = reg_render_b(c, M, fan_cells[i], fan_lay[i], [&] {
+                hipLaunchKernelGGL(mosaic_scatter_fan_kernel, dim3((unsigned)jobs[i].N * (unsigned)nyaw), dim3(256), 0, c->stream, M.jobs + i, grid, M.win,
+                                   d_fan + fan0[i], seg_pings, nyaw); });
+            if (rc) return rc;
         }
     }
-    // 2. one pass per angle: the table cleared, one correlation job per (pair, segment), one download, the records of the angle
-    const uint64_t* tab = c->mosaic_pinned.as<uint64_t>();                      // host path: the table and the flag
-    const dsss_reg_result* rec = c->mosaic_pinned.as<dsss_reg_result>();        // device path: the records and the flag
+    // 2. one pass per angle: the table cleared, one correlation job per row, one download, the records of the angle
     std::vector<dsss_reg_result> per((size_t)nseg * nyaw);
     for (int a = 0; a < nyaw; ++a) {
-        HIPCHK(c, hipMemsetAsync(d_tab, 0, table * 8, c->stream));
-        rc = reg_launch_corr(c, pj[a], blocks[a], d_pairs, r); if (rc) return rc;
-        if (dev) { rc = reg_launch_peaks(c, d_tab, nseg, r, R.min_cells, p->cell, d_rec); if (rc) return rc; }
-        HIPCHK(c, hipMemcpyAsync(c->mosaic_pinned.p, dev ? (const void*)d_rec : (const void*)d_tab, down, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        cnt.down(down); cnt.sync();
-        if (dev ? *reinterpret_cast<const int*>(rec + nseg) : (int)tab[table])
-            DSSS_FAIL(c, DSSS_E_CAPACITY, "mosaic: a cell received more than 2^24 samples of one frame (cell %g too coarse)", p->cell);
-        (dev ? cnt.I.tables_device : cnt.I.tables_host) += nseg;
-        for (row = 0; row < nseg; ++row) {
-            if (dev) { per[(size_t)row * nyaw + a] = rec[row]; continue; }
-            peak_of(tab + (size_t)row * nshift * 6, r, R.min_cells, p->cell, &per[(size_t)row * nyaw + a]);
-            if (sums_host) memcpy(sums_host + ((size_t)row * nyaw + a) * nshift * 6, tab + (size_t)row * nshift * 6, (size_t)nshift * 6 * 8);
+        HIPCHK(c, hipMemsetAsync(M.tab, 0, table * 8, c->stream));
+        rc = reg_launch_corr(c, pj[a], blocks[a], M.pairs, P.radius); if (rc) return rc;
+        reg_view v;
+        rc = reg_fetch(c, M, nseg, nseg, P, p->cell, c->mosaic_pinned.p, cnt, &v); if (rc) return rc;
+        for (int row = 0; row < nseg; ++row) {
+            per[(size_t)row * nyaw + a] = v.record(row);
+            if (sums_host) memcpy(sums_host + ((size_t)row * nyaw + a) * tsz, v.table(row), tsz * 8);
         }
     }
-    // 3. the angle of every row on the host, then the centroid sums of the rows that have one under that angle: one launch, one download
-    std::vector<cen_job> cj;
-    long long cblocks = 0;
-    for (row = 0; row < nseg; ++row) {
+    // 3. the angle of every row on the host, then the centroid sums of the rows that have a peak under that angle
+    for (int row = 0; row < nseg; ++row) {
         dsss_reg_seg_yaw& o = out_host[row];
         const dsss_reg_result* z = per.data() + (size_t)row * nyaw;
         yaw_peak_of(z, nyaw, Y.step, &o.k, &o.yaw_on_border, &o.theta, &o.theta_hat);
         o.s.r = z[o.k]; o.zncc_k0 = z[mid].zncc;
-        if (!(o.s.r.zncc > -2.0)) continue;                                     // no usable shift under any angle: sx = sy = 0
-        const size_t g = row_g[row] + o.k;
-        if (!cen_push_job(cj, &cblocks, d_lay + lay_off[row_a[row]], wins[row_a[row]], d_lay + fan_lay[slot[pair_b[o.s.pair]]] + hfan[g].off, sw[g], o.s.r,
-                          d_cen + (size_t)row * 3))
-            DSSS_FAIL(c, DSSS_E_NUMERIC, "register: internal error, the centroid of %d segments takes more workgroups than was bounded", nseg);
     }
-    if (!cj.empty()) {
-        std::vector<uint64_t> cen((size_t)nseg * 3);
-        rc = reg_launch_centroids(c, cj, cblocks, d_cj, d_cen, cen, cnt); if (rc) return rc;
-        for (row = 0; row < nseg; ++row) {
-            dsss_reg_seg& o = out_host[row].s;
-            if (!(o.r.zncc > -2.0)) continue;
-            if ((int64_t)cen[(size_t)row * 3] != o.r.n)
-                DSSS_FAIL(c, DSSS_E_NUMERIC, "register: internal error, row %d has %lld cells at its peak and %lld in its centroid", row,
-                          (long long)o.r.n, (long long)cen[(size_t)row * 3]);
-            o.sx = (int64_t)cen[(size_t)row * 3 + 1]; o.sy = (int64_t)cen[(size_t)row * 3 + 2];
-        }
-    }
+    rc = reg_centroids(c, M, nseg, true, cnt, [&](int row, cen_src* s) {
+        dsss_reg_seg_yaw& o = out_host[row];
+        if (!(o.s.r.zncc > -2.0)) return false;                                 // no usable shift under any angle: sx = sy = 0
+        *s = cen_src{ M.lay + W.lay_off[Q.row_a[row]], &W.wins[Q.row_a[row]], layer_b(row, o.k), &sw[Q.row_g[row] + o.k], &o.s };
+        return true; });
+    if (rc) return rc;
     c->reg_info = cnt.I;
-    return DSSS_OK;
-}
-
-void dsss_reg_edge_yaw_params_default(dsss_reg_edge_yaw_params* e)
-{
-    if (e) { dsss_reg_edge_params_default(&e->e); dsss_reg_yaw_params_default(&e->fan); e->sigma_yaw_steps = 1.0; }
-}
-
-int dsss_register_edge_yaw(const dsss_reg_seg_yaw* s, const dsss_mosaic_params* grid, const double* rows_a, int Na, int base_a,
-                           const double* rows_b, int Nb, int base_b, const dsss_reg_edge_yaw_params* ep, dsss_lc_edge* edge)
-{
-    dsss_reg_edge_yaw_params E; dsss_reg_edge_yaw_params_default(&E);
-    if (ep) E = *ep;
-    if (!s || !fan_ok(E.fan.nyaw, E.fan.step) || !(E.sigma_yaw_steps > 0.0) || !std::isfinite(E.sigma_yaw_steps)) return DSSS_E_ARG;
-    const double s_yaw = E.fan.nyaw == 1 ? E.e.sigma_rot : E.sigma_yaw_steps * E.fan.step;
-    // the row's own acceptance comes first in edge_of; a fan row on the border of the fan is rejected after it was found valid
-    dsss_lc_edge e;
-    const int rc = edge_of(&s->s, grid, rows_a, Na, base_a, rows_b, Nb, base_b, E.e, s->theta, s->theta_hat, s_yaw, edge ? &e : nullptr);
-    if (rc != 1) return rc;
-    if (s->yaw_on_border != 0) return 0;
-    *edge = e;
-    return 1;
-}
-
-int dsss_mosaic_register_edges_yaw(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, const dsss_mosaic_params* p,
-                                   const int* pair_a, const int* pair_b, const dsss_reg_seg_yaw* segs, int nsegs, const dsss_reg_edge_yaw_params* ep,
-                                   dsss_lc_edge* edges_host, int32_t* edge_seg_host, int cap, int* n_edges)
-{
-    return edges_loop(c, ids, n, rpy6, ping_off, p, pair_a, pair_b, segs != nullptr, nsegs, edges_host, edge_seg_host, cap, n_edges,
-                      [&](int k) -> const dsss_reg_seg& { return segs[k].s; },
-                      [&](int k, const double* ra, int Na, int ba, const double* rb, int Nb, int bb, dsss_lc_edge* e) {
-                          return dsss_register_edge_yaw(segs + k, p, ra, Na, ba, rb, Nb, bb, ep, e); });
-}
-
-// ---- dense loop closures over a cell pyramid
-void dsss_reg_pyr_params_default(dsss_reg_pyr_params* q) { if (q) { q->levels = 1; q->refine = 3; } }
-
-int dsss_register_pyr_step(const uint64_t* sums, int radius, int min_cells, double cell, int level, int cx, int cy,
-                           dsss_reg_result* out, int32_t* usable, int32_t* ncx, int32_t* ncy)
-{
-    if (!sums || !out || !usable || !ncx || !ncy || radius < 0 || radius > REG_MAX_RADIUS || min_cells < 1 || !(cell > 0.0) || !std::isfinite(cell) ||
-        level < 0 || level >= PYR_MAX_LEVELS || cx < -PYR_MAX_CENTRE || cx > PYR_MAX_CENTRE || cy < -PYR_MAX_CENTRE || cy > PYR_MAX_CENTRE) return DSSS_E_ARG;
-    pyr_step_of(sums, radius, min_cells, cell, level, cx, cy, out, usable, ncx, ncy);
     return DSSS_OK;
 }
 
@@ -1188,42 +977,33 @@ int dsss_register_pyr_step(const uint64_t* sums, int radius, int min_cells, doub
 // the layers of every level; the layers of all levels stay resident.  Per level, from the top: mosaic_corr_kernel with one job per row
 // that is still alive (the segment's window moved by minus the row's centre), one download -- of the records of the live rows, whose
 // tables then lie one behind the other (mosaic_peak_kernel with the level's radius, min_cells and cell), or of that level's tables of
-// all rows when the sums are asked for -- and the level rule on the host (pyr_step_of; on the device path its second part, pyr_centre_of).  mosaic_centroid_kernel runs once, at the total shift, for the rows that finished at level 0.  What one
+// all rows when the sums are asked for -- and the level rule on the host: the level's record (reg_view), then pyr_centre_of and
+// pyr_apply on both paths.  mosaic_centroid_kernel runs once, at the total shift, for the rows that finished at level 0.  What one
 // launch cannot take is bounded and refused before anything is launched.
 int dsss_mosaic_register_segments_pyr(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, const dsss_mosaic_params* p,
                                       const int* pair_a, const int* pair_b, int npairs, int seg_pings, const dsss_reg_params* rp,
                                       const dsss_reg_pyr_params* pp, dsss_reg_seg_pyr* out_host, int cap, int* nseg_host, uint64_t* sums_host)
 {
     if (!c) return DSSS_E_ARG;
-    size_t rows = 0;
-    dsss_reg_params R; std::vector<int> slot;
-    int rc = reg_check(c, ids, n, rpy6, ping_off, p, pair_a, pair_b, npairs, rp, out_host, &R, slot, &rows); if (rc) return rc;
-    if (seg_pings < 1) DSSS_FAIL(c, DSSS_E_ARG, "register: seg_pings = %d", seg_pings);
-    if (!nseg_host || cap < 0) DSSS_FAIL(c, DSSS_E_ARG, "register: %s", nseg_host ? "negative capacity" : "nowhere to write the number of segments");
+    reg_rows Q;
+    int rc = Q.check(c, ids, n, rpy6, ping_off, p, pair_a, pair_b, npairs, rp, out_host); if (rc) return rc;
+    rc = Q.check_segments(seg_pings, nseg_host, cap); if (rc) return rc;
     dsss_reg_pyr_params P; dsss_reg_pyr_params_default(&P);
     if (pp) P = *pp;
     if (!pyr_ok(P)) DSSS_FAIL(c, DSSS_E_ARG, "register: a pyramid of %d levels refined within %d cells (1..%d levels, 1..%d cells)", P.levels, P.refine, PYR_MAX_LEVELS, REG_MAX_RADIUS);
     const int L = P.levels;
-    auto segs_of = [&](int i) { return (int)(((long long)c->frames[ids[i]].N + seg_pings - 1) / seg_pings); };
-    auto seg_end = [&](int s, int N) { return (int)std::min((long long)(s + 1) * seg_pings, (long long)N); };
-    long long total = 0;
-    for (int k = 0; k < npairs; ++k) total += segs_of(slot[pair_b[k]]);
-    if (total > 0x7fffffffll) DSSS_FAIL(c, DSSS_E_ARG, "register: %lld segments", total);
-    *nseg_host = (int)total;                                                    // also when there is no room for them: the caller learns how many
-    if (total > cap) DSSS_FAIL(c, DSSS_E_CAPACITY, "register: %lld segments, room for %d", total, cap);
+    rc = Q.count(1, cap, nseg_host, sums_host); if (rc) return rc;
     reg_count cnt;
-    if (total == 0) { c->reg_info = cnt.I; return DSSS_OK; }
-    const int nseg = (int)total;
-    const bool dev = !sums_host && !dsss_switches_read().reg_peaks_host;       // the peaks on the device: nobody reads the table on the host
-    std::vector<char> as_a(n, 0), as_b(n, 0);
-    for (int k = 0; k < npairs; ++k) { as_a[slot[pair_a[k]]] = 1; as_b[slot[pair_b[k]]] = 1; }
-    auto radius_of = [&](int l) { return l == L - 1 ? R.radius : P.refine; };
-    auto nshift_of = [&](int l) { const int S = 2 * radius_of(l) + 1; return (size_t)S * S; };
+    if (Q.nseg == 0) { c->reg_info = cnt.I; return DSSS_OK; }
+    const int nseg = Q.nseg; const bool dev = Q.dev;
+    auto radius_of = [&](int l) { return l == L - 1 ? Q.R.radius : P.refine; };
+    auto words_of = [&](int l) { return reg_table_words(radius_of(l)); };
     // areas: the whole frame where it occurs as a, every segment where it occurs as b; an area's accumulators lie behind the frame's
-    // first, its layers of all levels in d_lay
+    // first, its layers of all levels in M.lay
     struct area_lay { size_t off[PYR_MAX_LEVELS]; };
     std::vector<mosaic_win> wins(n); std::vector<char> on_grid(n, 0); std::vector<area_lay> a_lay(n);
-    std::vector<int> seg0(n, 0), job0(n, 0), njobs(n, 0);                       // a frame's first segment in sw / hseg, its areas in hpj
+    std::vector<size_t> seg0(n, 0);                                             // a frame's first segment in sw / hseg
+    std::vector<int> job0(n, 0), njobs(n, 0);                                   // a frame's areas in hpj
     std::vector<size_t> a_cells(n, 0), acc_cells(n, 0); std::vector<long long> pyr_blocks(n, 0);
     std::vector<mosaic_win> sw; std::vector<mosaic_seg> hseg; std::vector<area_lay> seg_lay; std::vector<pyr_job> hpj;
     size_t win_cells = 1, lay_cells = 0;
@@ -1234,189 +1014,131 @@ int dsss_mosaic_register_segments_pyr(dsss_ctx* c, const int* ids, int n, const 
             lay->off[l] = J.lay[l] = lay_cells;
             if (l >= L) continue;
             const mosaic_win q = pyr_window(w, l, 0, 0);
-            lay_cells += ((size_t)q.bw * q.bh + 127) & ~(size_t)127;            // layers start on 256 bytes
+            lay_cells += reg_round((size_t)q.bw * q.bh);
         }
         J.tiles_x = (w.ox + w.bw - 1 - J.bx0) / PYR_TW + 1; J.blk0 = (int)pyr_blocks[i];
         pyr_blocks[i] += (long long)J.tiles_x * ((w.oy + w.bh - 1 - J.by0) / PYR_TH + 1);
         if (pyr_blocks[i] <= 0x7fffffffll) { hpj.push_back(J); ++njobs[i]; }   // (more is refused below, before anything is launched)
     };
     for (int i = 0; i < n; ++i) {
-        const dsss_frame& f = c->frames[ids[i]];
-        const double* fr = rpy6 ? rpy6 + (size_t)ping_off[i] * 6 : f.h_geo;
+        const dsss_frame& f = Q.frame(i);
+        const double* fr = Q.rows_of(i);
         job0[i] = (int)hpj.size();
-        if (as_a[i] && reg_window(f, fr, 0, f.N, p, &wins[i])) {
+        if (Q.as_a[i] && reg_window(f, fr, 0, f.N, p, &wins[i])) {
             on_grid[i] = 1;
             add_area(i, wins[i], 0, &a_lay[i]);
-            a_cells[i] = ((size_t)wins[i].bw * wins[i].bh + 127) & ~(size_t)127;
+            a_cells[i] = reg_round((size_t)wins[i].bw * wins[i].bh);
         }
         size_t cells = 0;
-        if (as_b[i]) {
-            seg0[i] = (int)sw.size();
-            for (int s = 0; s < segs_of(i); ++s) {
-                mosaic_win w{ p->x0, p->y0, p->cell, p->W, p->H, 0, 0, 0, 0, p->use_mask != 0 };  // bw = 0: not on the grid
+        if (Q.as_b[i]) {
+            seg0[i] = sw.size();
+            for (int s = 0; s < Q.segs_of(i); ++s) {
+                mosaic_win w = reg_grid(p);
                 area_lay al{};
-                if (reg_window(f, fr, s * seg_pings, seg_end(s, f.N), p, &w)) add_area(i, w, a_cells[i] + cells, &al);
+                if (reg_window(f, fr, s * seg_pings, Q.seg_end(s, f.N), p, &w)) add_area(i, w, a_cells[i] + cells, &al);
                 sw.push_back(w); seg_lay.push_back(al); hseg.push_back(mosaic_seg{ w.ox, w.oy, w.bw, w.bh, (unsigned long long)cells });
-                cells += ((size_t)w.bw * w.bh + 127) & ~(size_t)127;
+                cells += reg_round((size_t)w.bw * w.bh);
             }
         }
         acc_cells[i] = a_cells[i] + cells; win_cells = std::max(win_cells, acc_cells[i]);
         if (pyr_blocks[i] > 0x7fffffffll) DSSS_FAIL(c, DSSS_E_ARG, "register: the areas of frame %d are more than one launch takes", ids[i]);
     }
-    // the rows, by pair and then by segment, and what the launches of every level and of the centroid can need at most: a level's
-    // region lies inside the segment's window of that level dilated by the radius, the centroid's inside the segment's fine window
+    // the rows, and what the launches of every level and of the centroid can need at most: a level's region lies inside the
+    // segment's window of that level dilated by the radius, the centroid's inside the segment's fine window
     memset(out_host, 0, (size_t)nseg * sizeof(dsss_reg_seg_pyr));
-    std::vector<int> row_a(nseg), row_b(nseg), row_g(nseg);                     // a row's frames (index in ids) and its segment in sw / hseg
+    Q.layout(seg0, 1, [&](int row) -> dsss_reg_seg& { return out_host[row].s; });
     {
         long long bound[PYR_MAX_LEVELS] = { 0, 0, 0, 0 }, cen_bound = 0;
-        int row = 0;
-        for (int k = 0; k < npairs; ++k) {
-            const int ia = slot[pair_a[k]], ib = slot[pair_b[k]];
-            const int Nb = c->frames[ids[ib]].N;
-            for (int s = 0; s < segs_of(ib); ++s, ++row) {
-                dsss_reg_seg_pyr& o = out_host[row];
-                o.s.pair = k; o.s.seg = s; o.s.p0 = s * seg_pings; o.s.p1 = seg_end(s, Nb);
-                o.level = -1;
-                for (int l = 0; l < PYR_MAX_LEVELS; ++l) o.lz[l] = -2.0;
-                const int g = seg0[ib] + s;
-                row_a[row] = ia; row_b[row] = ib; row_g[row] = g;
-                if (!on_grid[ia] || sw[g].bw == 0) continue;
-                for (int l = 0; l < L; ++l) {
-                    const mosaic_win A = pyr_window(wins[ia], l, 0, 0), Bw = pyr_window(sw[g], l, 0, 0);
-                    const long long w = std::min(A.bw, Bw.bw + 2 * radius_of(l)), h = std::min(A.bh, Bw.bh + 2 * radius_of(l));
-                    bound[l] += (((w - 1) / REG_TILE + 1) + REG_STRIP - 1) / REG_STRIP * ((h - 1) / REG_TILE + 1);
-                }
-                cen_bound += (long long)((std::min(wins[ia].bw, sw[g].bw) - 1) / CEN_TW + 1) * ((std::min(wins[ia].bh, sw[g].bh) - 1) / CEN_TH + 1);
+        for (int row = 0; row < nseg; ++row) {
+            dsss_reg_seg_pyr& o = out_host[row];
+            o.level = -1;
+            for (int l = 0; l < PYR_MAX_LEVELS; ++l) o.lz[l] = -2.0;
+            const int ia = Q.row_a[row]; const size_t g = Q.row_g[row];
+            if (!on_grid[ia] || sw[g].bw == 0) continue;
+            for (int l = 0; l < L; ++l) {
+                const mosaic_win A = pyr_window(wins[ia], l, 0, 0), Bw = pyr_window(sw[g], l, 0, 0);
+                const long long w = std::min(A.bw, Bw.bw + 2 * radius_of(l)), h = std::min(A.bh, Bw.bh + 2 * radius_of(l));
+                bound[l] += (((w - 1) / REG_TILE + 1) + REG_STRIP - 1) / REG_STRIP * ((h - 1) / REG_TILE + 1);
             }
+            cen_bound += (long long)((std::min(wins[ia].bw, sw[g].bw) - 1) / CEN_TW + 1) * ((std::min(wins[ia].bh, sw[g].bh) - 1) / CEN_TH + 1);
         }
         for (int l = 0; l < L; ++l)
             if (bound[l] > 0x7fffffffll || cen_bound > 0x7fffffffll) DSSS_FAIL(c, DSSS_E_ARG, "register: %d segments are more than one launch takes", nseg);
     }
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t nshift_max = std::max(nshift_of(L - 1), nshift_of(0));
-    const size_t table_max = (size_t)nseg * nshift_max * 6;
-    carve Cv;
-    const size_t o_lay = Cv.take(lay_cells * 2), o_win = Cv.take(win_cells * 8), o_jobs = Cv.take((size_t)n * sizeof(mosaic_job)),
-                 o_rows = Cv.take(rpy6 ? rows * 6 * sizeof(double) : 0), o_segs = Cv.take(hseg.size() * sizeof(mosaic_seg)),
-                 o_pj = Cv.take(hpj.size() * sizeof(pyr_job)), o_pairs = Cv.take((size_t)nseg * sizeof(reg_job)), o_cj = Cv.take((size_t)nseg * sizeof(cen_job)),
-                 o_cen = Cv.take((size_t)nseg * 3 * 8), o_tab = Cv.take((1 + table_max) * 8),      // the sample-limit flag and, behind it, one level's sums
-                 o_rec = Cv.take(dev ? ((size_t)nseg + 1) * sizeof(dsss_reg_result) : 0);      // device path: the flag in the last 8 bytes of a first record's room, behind it one level's records
-    rc = c->mosaic_buf.reserve(c, Cv.off); if (rc) return rc;
-    rc = c->mosaic_pinned.reserve(c, dev ? 8 + (size_t)nseg * sizeof(dsss_reg_result) : (1 + table_max) * 8); if (rc) return rc;
-    char* B = c->mosaic_buf.as<char>();
-    uint16_t* d_lay = reinterpret_cast<uint16_t*>(B + o_lay);
-    unsigned long long* d_win = reinterpret_cast<unsigned long long*>(B + o_win);
-    mosaic_job* d_jobs = reinterpret_cast<mosaic_job*>(B + o_jobs);
-    mosaic_seg* d_segs = reinterpret_cast<mosaic_seg*>(B + o_segs);
-    pyr_job* d_pj = reinterpret_cast<pyr_job*>(B + o_pj);
-    reg_job* d_pairs = reinterpret_cast<reg_job*>(B + o_pairs);
-    cen_job* d_cj = reinterpret_cast<cen_job*>(B + o_cj);
-    unsigned long long* d_cen = reinterpret_cast<unsigned long long*>(B + o_cen);
-    unsigned long long* d_tab = reinterpret_cast<unsigned long long*>(B + o_tab) + 1;
-    dsss_reg_result* d_rec = reinterpret_cast<dsss_reg_result*>(B + o_rec) + 1;
-    int* d_flag = dev ? reinterpret_cast<int*>(reinterpret_cast<char*>(d_rec) - 8) : reinterpret_cast<int*>(B + o_tab);
-    std::vector<const double*> dev_rows;
-    rc = upload_rows(c, ids, n, rpy6, ping_off, reinterpret_cast<double*>(B + o_rows), dev_rows); if (rc) return rc;
-    std::vector<mosaic_job> jobs(n);
-    for (int i = 0; i < n; ++i) { const dsss_frame& f = c->frames[ids[i]]; jobs[i] = mosaic_job{ dev_rows[i], f.gr, f.lvl[0], f.mask, f.N, f.M, 0, 0 }; }
-    HIPCHK(c, hipMemcpyAsync(d_jobs, jobs.data(), (size_t)n * sizeof(mosaic_job), hipMemcpyHostToDevice, c->stream));
+    const size_t words_max = std::max(words_of(L - 1), words_of(0));
+    reg_mem M;
+    M.take(lay_cells, win_cells, n, rpy6 ? Q.traj_rows : 0, nseg, true, (size_t)nseg * words_max, dev);
+    const reg_piece<mosaic_seg> o_segs = M.A.take<mosaic_seg>(hseg.size());
+    const reg_piece<pyr_job> o_pj = M.A.take<pyr_job>(hpj.size());
+    rc = M.reserve(c); if (rc) return rc;
+    rc = c->mosaic_pinned.reserve(c, M.down_bytes(nseg, words_max)); if (rc) return rc;
+    mosaic_seg* d_segs = M.A.at(o_segs); pyr_job* d_pj = M.A.at(o_pj);
+    std::vector<mosaic_job> jobs;
+    rc = reg_upload_jobs(Q, M, jobs); if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(d_segs, hseg.data(), hseg.size() * sizeof(mosaic_seg), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(d_pj, hpj.data(), hpj.size() * sizeof(pyr_job), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(d_flag, 0, 8, c->stream));
-    HIPCHK(c, hipMemsetAsync(d_cen, 0, (size_t)nseg * 3 * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(M.flag, 0, 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(M.cen, 0, (size_t)nseg * 3 * 8, c->stream));
     // 1. the layers of all levels: per frame one memset, its scatters and one pyramid launch over all its areas
-    const mosaic_win grid{ p->x0, p->y0, p->cell, p->W, p->H, 0, 0, 0, 0, p->use_mask != 0 };
+    const mosaic_win grid = reg_grid(p);
     for (int i = 0; i < n; ++i) {
         if (!njobs[i]) continue;
-        HIPCHK(c, hipMemsetAsync(d_win, 0, acc_cells[i] * 8, c->stream));
-        if (on_grid[i]) launch_scatter(c, d_jobs + i, 1, jobs[i].N, wins[i], d_win);
-        if (acc_cells[i] > a_cells[i]) launch_scatter_seg(c, d_jobs + i, jobs[i].N, grid, d_win + a_cells[i], d_segs + seg0[i], seg_pings);
-        hipLaunchKernelGGL(mosaic_pyr_kernel, dim3((unsigned)pyr_blocks[i]), dim3(256), 0, c->stream, d_pj + job0[i], njobs[i], L, d_win, d_lay, d_flag);
+        HIPCHK(c, hipMemsetAsync(M.win, 0, acc_cells[i] * 8, c->stream));
+        if (on_grid[i]) launch_scatter(c, M.jobs + i, 1, jobs[i].N, wins[i], M.win);
+        if (acc_cells[i] > a_cells[i]) launch_scatter_seg(c, M.jobs + i, jobs[i].N, grid, M.win + a_cells[i], d_segs + seg0[i], seg_pings);
+        hipLaunchKernelGGL(mosaic_pyr_kernel, dim3((unsigned)pyr_blocks[i]), dim3(256), 0, c->stream, d_pj + job0[i], njobs[i], L, M.win, M.lay, M.flag);
         HIPCHK(c, hipGetLastError());
     }
     // 2. level by level from the top: the rows still alive around their centres, one launch, one download, the level rule on the host
-    const uint64_t* tab = c->mosaic_pinned.as<uint64_t>() + 1;                  // the flag is tab[-1] on both paths
-    const dsss_reg_result* rec = reinterpret_cast<const dsss_reg_result*>(tab); // device path: the records of the level's live rows, in their order
-    std::vector<int> live; live.reserve(nseg);                                  // device path: the rows still alive, whose tables lie one behind the other
-    const size_t row_sums = (nshift_of(L - 1) + (size_t)(L - 1) * nshift_of(0)) * 6;
+    std::vector<int> live; live.reserve(nseg);                                  // the rows still alive; device path: their tables lie one behind the other
+    const size_t row_sums = words_of(L - 1) + (size_t)(L - 1) * words_of(0);
     std::vector<char> alive(nseg, 1); std::vector<int32_t> cx(nseg, 0), cy(nseg, 0);
     std::vector<reg_job> pj; pj.reserve(nseg);
     for (int l = L - 1; l >= 0; --l) {
-        const int r = radius_of(l); const size_t tsz = nshift_of(l) * 6;
+        const reg_pass Pl{ radius_of(l), pyr_min_cells(Q.R.min_cells, l), ldexp(p->cell, l) };
+        const size_t tsz = words_of(l);
+        auto place = [&](size_t k) { return dev ? k : (size_t)live[k]; };       // host path: every row keeps its place
         pj.clear(); live.clear();
         long long blocks = 0;
         for (int row = 0; row < nseg; ++row) {
-            const int ia = row_a[row], g = row_g[row];
+            const int ia = Q.row_a[row]; const size_t g = Q.row_g[row];
             if (!alive[row]) continue;
-            const size_t at_tab = dev ? live.size() : (size_t)row;              // host path: every row keeps its place
             live.push_back(row);                                                // (a live row off the grid has no job: its table stays zero)
             if (!on_grid[ia] || sw[g].bw == 0) continue;
-            if (!reg_push_job(pj, &blocks, d_lay + a_lay[ia].off[l], pyr_window(wins[ia], l, 0, 0), d_lay + seg_lay[g].off[l], pyr_window(sw[g], l, cx[row], cy[row]),
-                              r, d_tab + at_tab * tsz))
+            if (!reg_push_job(pj, &blocks, M.lay + a_lay[ia].off[l], pyr_window(wins[ia], l, 0, 0), M.lay + seg_lay[g].off[l], pyr_window(sw[g], l, cx[row], cy[row]),
+                              Pl.radius, M.tab + place(live.size() - 1) * tsz))
                 DSSS_FAIL(c, DSSS_E_NUMERIC, "register: internal error, level %d of %d segments takes more workgroups than was bounded", l, nseg);
         }
         const size_t ntab = dev ? live.size() : (size_t)nseg;
-        const size_t down = dev ? 8 + ntab * sizeof(dsss_reg_result) : (1 + ntab * tsz) * 8;
-        HIPCHK(c, hipMemsetAsync(d_tab, 0, ntab * tsz * 8, c->stream));
-        rc = reg_launch_corr(c, pj, blocks, d_pairs, r); if (rc) return rc;
-        if (dev) { rc = reg_launch_peaks(c, d_tab, (long long)ntab, r, pyr_min_cells(R.min_cells, l), ldexp(p->cell, l), d_rec); if (rc) return rc; }
-        HIPCHK(c, hipMemcpyAsync(c->mosaic_pinned.p, d_flag, down, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        cnt.down(down); cnt.sync();
-        if ((int)tab[-1]) DSSS_FAIL(c, DSSS_E_CAPACITY, "mosaic: a cell received more than 2^24 samples of one frame (cell %g too coarse)", p->cell);
-        (dev ? cnt.I.tables_device : cnt.I.tables_host) += (int64_t)live.size();
-        if (dev) {                                                              // the level rule's centre on the downloaded records
-            for (size_t k = 0; k < live.size(); ++k) {
-                const int row = live[k];
-                dsss_reg_seg_pyr& o = out_host[row];
-                dsss_reg_result q = rec[k]; int32_t usable = 0, nx = 0, ny = 0;
-                pyr_centre_of(p->cell, l, cx[row], cy[row], &q, &usable, &nx, &ny);
-                if (!usable) { alive[row] = 0; if (l == L - 1) o.s.r = q; continue; }
-                o.s.r = q; o.level = l; o.lx[l] = q.dx; o.ly[l] = q.dy; o.lz[l] = q.zncc;
-                if (q.on_border) o.border_mask |= 1 << l;
-                cx[row] = nx; cy[row] = ny;
-            }
-            continue;
-        }
-        const size_t at = l == L - 1 ? 0 : (nshift_of(L - 1) + (size_t)(L - 2 - l) * nshift_of(0)) * 6;      // this level's table within a row of sums_host
-        for (int row = 0; row < nseg; ++row) {
-            if (sums_host) {
-                if (alive[row]) memcpy(sums_host + (size_t)row * row_sums + at, tab + (size_t)row * tsz, tsz * 8);
+        HIPCHK(c, hipMemsetAsync(M.tab, 0, ntab * tsz * 8, c->stream));
+        rc = reg_launch_corr(c, pj, blocks, M.pairs, Pl.radius); if (rc) return rc;
+        reg_view v;
+        rc = reg_fetch(c, M, ntab, live.size(), Pl, p->cell, c->mosaic_pinned.p, cnt, &v); if (rc) return rc;
+        if (sums_host) {
+            const size_t at = l == L - 1 ? 0 : words_of(L - 1) + (size_t)(L - 2 - l) * words_of(0);      // this level's table within a row of sums_host
+            for (int row = 0; row < nseg; ++row) {
+                if (alive[row]) memcpy(sums_host + (size_t)row * row_sums + at, v.table(row), tsz * 8);
                 else memset(sums_host + (size_t)row * row_sums + at, 0, tsz * 8);
             }
-            if (!alive[row]) continue;
-            dsss_reg_seg_pyr& o = out_host[row];
-            dsss_reg_result q; int32_t usable = 0, nx = 0, ny = 0;
-            pyr_step_of(tab + (size_t)row * tsz, r, R.min_cells, p->cell, l, cx[row], cy[row], &q, &usable, &nx, &ny);
-            if (!usable) { alive[row] = 0; if (l == L - 1) o.s.r = q; continue; }              // no level has a usable peak: the top level's record
-            o.s.r = q; o.level = l; o.lx[l] = q.dx; o.ly[l] = q.dy; o.lz[l] = q.zncc;
-            if (q.on_border) o.border_mask |= 1 << l;
-            cx[row] = nx; cy[row] = ny;
+        }
+        for (size_t k = 0; k < live.size(); ++k) {
+            const int row = live[k];
+            dsss_reg_result q = v.record(place(k)); int32_t usable = 0, nx = 0, ny = 0;
+            pyr_centre_of(p->cell, l, cx[row], cy[row], &q, &usable, &nx, &ny);
+            pyr_apply(out_host[row], q, usable != 0, l, l == L - 1, nx, ny, &alive[row], &cx[row], &cy[row]);
         }
     }
-    // 3. the centroid sums at the total shift of the rows that finished at level 0: one launch, one download
-    std::vector<cen_job> cj;
-    long long cblocks = 0;
+    // 3. the centroid sums at the total shift of the rows that finished at level 0
     for (int row = 0; row < nseg; ++row) {
         dsss_reg_seg_pyr& o = out_host[row];
-        if (o.level < 0) continue;                                              // the no-usable-shift record stays as it is
-        if (o.level == 0 && !cen_push_job(cj, &cblocks, d_lay + a_lay[row_a[row]].off[0], wins[row_a[row]], d_lay + seg_lay[row_g[row]].off[0], sw[row_g[row]], o.s.r,
-                                          d_cen + (size_t)row * 3))
-            DSSS_FAIL(c, DSSS_E_NUMERIC, "register: internal error, the centroid of %d segments takes more workgroups than was bounded", nseg);
-        o.s.r.on_border = (o.border_mask != 0 || o.level != 0) ? 1 : 0;
+        if (o.level >= 0) o.s.r.on_border = (o.border_mask != 0 || o.level != 0) ? 1 : 0;      // the no-usable-shift record stays as it is
     }
-    if (!cj.empty()) {
-        std::vector<uint64_t> cen((size_t)nseg * 3);
-        rc = reg_launch_centroids(c, cj, cblocks, d_cj, d_cen, cen, cnt); if (rc) return rc;
-        for (int row = 0; row < nseg; ++row) {
-            dsss_reg_seg& o = out_host[row].s;
-            if (out_host[row].level != 0) continue;
-            if ((int64_t)cen[(size_t)row * 3] != o.r.n)
-                DSSS_FAIL(c, DSSS_E_NUMERIC, "register: internal error, row %d has %lld cells at its peak and %lld in its centroid", row,
-                          (long long)o.r.n, (long long)cen[(size_t)row * 3]);
-            o.sx = (int64_t)cen[(size_t)row * 3 + 1]; o.sy = (int64_t)cen[(size_t)row * 3 + 2];
-        }
-    }
+    rc = reg_centroids(c, M, nseg, true, cnt, [&](int row, cen_src* s) {
+        if (out_host[row].level != 0) return false;
+        *s = cen_src{ M.lay + a_lay[Q.row_a[row]].off[0], &wins[Q.row_a[row]], M.lay + seg_lay[Q.row_g[row]].off[0], &sw[Q.row_g[row]], &out_host[row].s };
+        return true; });
+    if (rc) return rc;
     c->reg_info = cnt.I;
     return DSSS_OK;
 }
@@ -1433,20 +1155,20 @@ int dsss_mosaic_register_peaks(dsss_ctx* c, const uint64_t* sums, int64_t ntable
     reg_count cnt;
     if (ntables == 0) { c->reg_info = cnt.I; return DSSS_OK; }
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t tsz = (size_t)(2 * radius + 1) * (2 * radius + 1) * 6, nt = (size_t)ntables;
+    const size_t tsz = reg_table_words(radius), nt = (size_t)ntables;
     hipPointerAttribute_t at;
     const bool on_dev = (hipPointerGetAttributes(&at, sums) == hipSuccess) && at.type == hipMemoryTypeDevice;
     (void)hipGetLastError();
-    carve L;
-    const size_t o_rec = L.take(nt * sizeof(dsss_reg_result)), o_tab = L.take(on_dev ? 0 : nt * tsz * 8);      // host tables go up into mosaic_buf
-    int rc = c->mosaic_buf.reserve(c, L.off); if (rc) return rc;
+    reg_arena A;
+    const reg_piece<dsss_reg_result> o_rec = A.take<dsss_reg_result>(nt);
+    const reg_piece<unsigned long long> o_tab = A.take<unsigned long long>(on_dev ? 0 : nt * tsz);      // host tables go up into mosaic_buf
+    int rc = A.reserve(c); if (rc) return rc;
     rc = c->mosaic_pinned.reserve(c, nt * sizeof(dsss_reg_result)); if (rc) return rc;
-    char* B = c->mosaic_buf.as<char>();
-    dsss_reg_result* d_rec = reinterpret_cast<dsss_reg_result*>(B + o_rec);
+    dsss_reg_result* d_rec = A.at(o_rec);
     const unsigned long long* d_tab = reinterpret_cast<const unsigned long long*>(sums);
     if (!on_dev) {
-        HIPCHK(c, hipMemcpyAsync(B + o_tab, sums, nt * tsz * 8, hipMemcpyHostToDevice, c->stream));
-        d_tab = reinterpret_cast<const unsigned long long*>(B + o_tab);
+        HIPCHK(c, hipMemcpyAsync(A.at(o_tab), sums, nt * tsz * 8, hipMemcpyHostToDevice, c->stream));
+        d_tab = A.at(o_tab);
     }
     rc = reg_launch_peaks(c, d_tab, ntables, radius, min_cells, cell, d_rec); if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(c->mosaic_pinned.p, d_rec, nt * sizeof(dsss_reg_result), hipMemcpyDeviceToHost, c->stream));

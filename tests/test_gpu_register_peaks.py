@@ -255,6 +255,44 @@ def test_pyramid(ctx, orc, data, trajectories, traj, seg_pings, use_mask):
     _bounds(idev, ihst, sum(alive), len(dev), LEVELS + 1, host_bytes)
 
 
+@pytest.mark.parametrize("entry", ["pair", "segments", "fan", "pyramid"])
+def test_call_accounting_is_exact(ctx, orc, data, trajectories, entry):
+    """what _bounds holds to inequalities, as equalities: a call is a number of passes (one correlation launch and its fetch: one for the
+    pair and the flat entry, one per angle, one per level) and, where a row has a peak to take a centroid at, one centroid download.
+    A pass brings down the 8 bytes of the sample-limit flag and n_l records of 64 bytes (device path) or n_l tables (host path)."""
+    from diasss_amd import capi
+    radius, nyaw, levels = min(r for r in P.RADII if r > 0), 3, 3
+    rows = trajectories["true"]
+    p = TS._grid(orc, data, [0, 1], rows, CELL, 0)
+    rpy, off = TS._traj(rows)
+    kw = dict(reg=TS._reg(radius=radius), rpy6=rpy, ping_off=off)
+    fn, a = {"pair": (ctx.mosaic_register, ()), "segments": (ctx.mosaic_register_segments, (80,)),
+             "fan": (ctx.mosaic_register_segments_yaw, (80, capi.RegYawParams(nyaw, 0, STEP))),
+             "pyramid": (ctx.mosaic_register_segments_pyr, (80, capi.RegPyrParams(levels, REFINE)))}[entry]
+    dev = fn([0, 1], p, [(0, 1)], *a, **kw); idev = _info(ctx)
+    hst, sums = fn([0, 1], p, [(0, 1)], *a, want_sums=True, **kw); ihst = _info(ctx)
+    assert dev.tobytes() == hst.tobytes()
+    n, top = len(dev), 48 * (2 * radius + 1) ** 2                      # rows (pairs for the pair entry), bytes of a table of the full radius
+    if entry == "pair":
+        assert n == 1
+        n_dev = n_host = [n]; tab = [top]; cen = False
+    elif entry == "segments":
+        assert n == N // 80
+        n_dev = n_host = [n]; tab = [top]; cen = bool((dev["r"]["zncc"] > -2.0).any())
+    elif entry == "fan":
+        assert n == N // 80
+        n_dev = n_host = [n] * nyaw; tab = [top] * nyaw; cen = bool((dev["s"]["r"]["zncc"] > -2.0).any())
+    else:
+        assert n == N // 80
+        n_dev = [n] + [int((dev["lz"][:, l + 1] > -2.0).sum()) for l in range(levels - 2, -1, -1)]      # alive: all at the top, below it those with a peak one level up
+        n_host = [n] * levels; tab = [top] + [48 * (2 * REFINE + 1) ** 2] * (levels - 1); cen = bool((dev["level"] == 0).any())
+    decided, syncs, cen_bytes = sum(n_dev), len(n_dev) + (1 if cen else 0), 24 * n if cen else 0
+    print("%s: device path %s, host path %s, tables per pass %s, centroid %s" % (entry, idev, ihst, n_dev, cen))
+    assert cen == (entry != "pair")                                     # the true trajectory: rows with a peak, so the centroid term is exercised
+    assert idev == (decided, 0, sum(8 + 64 * k for k in n_dev) + cen_bytes, syncs)
+    assert ihst == (0, decided, sum(8 + k * t for k, t in zip(n_host, tab)) + cen_bytes, syncs)
+
+
 # ---------------------------------------------------------------- 4. cases that must survive the routing
 def test_no_overlap_and_segments_off_the_grid(ctx, orc, data, trajectories):
     """a zero table gives the no-usable-shift record: frame 2 moved 300 m aside (windows on the grid, none within the radius), and the
