@@ -693,9 +693,15 @@ class Context:
         return int(self.L.dsss_features_pack_bytes(self.h))
 
     def features_pack(self, fid, buf):
+        """dsss_features_pack: the frame's record [int32 n, N, M, 0][bbox 4 f64][kps K][desc K x 32][geo K x 2 f64]( + [desc128 K x 128]
+        under DESC_SIFT128) written into buf: pack_bytes() bytes of a contiguous uint8 numpy array, of a torch tensor on the host or
+        on the device, or at a raw address.  Only the first n rows of a section mean anything.  DESC_SIFT128 on a frame without SIFT
+        rows: DSSS_E_STATE, and buf is not written."""
         self._chk(self.L.dsss_features_pack(self.h, fid, _ptr(buf)), "dsss_features_pack")
 
     def features_unpack(self, fid, buf):
+        """dsss_features_unpack: a record of features_pack's layout (numpy array, host or device tensor, raw address) into frame fid.
+        A count outside [0, K]: DSSS_E_CAPACITY; another N x M than the geometry the frame has: DSSS_E_ARG; the frame stays as it was."""
         self._chk(self.L.dsss_features_unpack(self.h, fid, _ptr(buf)), "dsss_features_unpack")
 
     # ---- matcher

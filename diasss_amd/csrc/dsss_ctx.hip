@@ -682,6 +682,7 @@ int dsss_features_pack(dsss_ctx* c, int id, void* buf)
     if (id < 0 || id >= c->max_frames) DSSS_FAIL(c, DSSS_E_ARG, "frame id out of range");
     dsss_frame& f = c->frames[id];
     if (!f.has_feat) DSSS_FAIL(c, DSSS_E_STATE, "frame %d has no features", id);
+    if (c->op.descriptor == DSSS_DESC_SIFT128 && !f.has_sift) DSSS_FAIL(c, DSSS_E_STATE, "frame %d has no SIFT rows", id);      // before a copy into the caller's buffer is queued
     { int rc = dsss_sync_bboxes(c); if (rc) return rc; }
     size_t K = c->kcap; char* p = (char*)buf;
     int32_t hdr[4] = { f.nkp, f.N, f.M, 0 };
@@ -691,7 +692,6 @@ int dsss_features_pack(dsss_ctx* c, int id, void* buf)
     HIPCHK(c, hipMemcpyAsync(p + 48 + K * sizeof(dsss_kp), c->desc + id * K * 32, K * 32, hipMemcpyDefault, c->stream));
     HIPCHK(c, hipMemcpyAsync(p + 48 + K * sizeof(dsss_kp) + K * 32, c->geo + id * K * 2, K * 16, hipMemcpyDefault, c->stream));
     if (c->op.descriptor == DSSS_DESC_SIFT128) {
-        if (!f.has_sift) DSSS_FAIL(c, DSSS_E_STATE, "frame %d has no SIFT rows", id);
         HIPCHK(c, hipMemcpyAsync(p + 48 + K * sizeof(dsss_kp) + K * 48, c->desc128.as<uint8_t>() + (size_t)id * K * 128, K * 128, hipMemcpyDefault, c->stream));
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -733,10 +733,46 @@ __device__ inline int ag_owner(int nframes, int world, int f)
     while (r > 0 && (long long)nframes * r / world > f) --r;
     return r;
 }
+// What the host needs of the gathered headers, and the verdict on them, in one block that exists twice: in device memory (ag_home,
+// written by ag_check_kernel) and page-locked on the host (ag_host, where one download lands it).  Fm = max_frames.
+struct ag_home_view {
+    int *n, *rows, *cols;      // [Fm] count, N, M of every gathered frame as its owner sent them
+    int *expect;               // [Fm][2] host -> device: the N, M this context holds for a frame with geometry, -1 -1 for one without
+    int *bad;                  // [4] bad[0] = the first gathered frame whose header is refused, -1 when every header passes
+    double *bbox;              // [Fm][4]
+    static size_t ints(int Fm) { const size_t k = (size_t)Fm * 5 + 4; return k + (k & 1); }
+    static size_t bytes(int Fm) { return ints(Fm) * sizeof(int) + (size_t)Fm * 4 * sizeof(double); }
+    ag_home_view(void* p, int Fm) : n(static_cast<int*>(p)), rows(n + Fm), cols(rows + Fm), expect(cols + Fm), bad(expect + 2 * (size_t)Fm), bbox(reinterpret_cast<double*>(n + ints(Fm))) {}
+};
+// Every gathered header is judged BEFORE the unpack pass writes a byte into the tables and stores (one block; the headers of a rank's
+// peers are a few hundred): count in [0, K], N x M the geometry this context holds for the frame where it holds one.  A refused header
+// raises bad[0], at which the unpack pass returns at once: a refused gather leaves every frame as it was, on the device as on the host.
+__global__ __launch_bounds__(256) void ag_check_kernel(int nframes, int world, int rank, const char* __restrict__ buf, size_t slice, size_t nb, int K, ag_home_view H)
+{
+    __shared__ int first_bad;
+    if (threadIdx.x == 0) first_bad = 0x7fffffff;
+    __syncthreads();
+    for (int f = threadIdx.x; f < nframes; f += 256) {
+        const int r = ag_owner(nframes, world, f);
+        if (r == rank) continue;
+        const int g0 = (int)((long long)nframes * r / world);
+        const char* rec = buf + (size_t)r * slice + (size_t)(f - g0) * nb;
+        const int* h = reinterpret_cast<const int*>(rec); const double* bb = reinterpret_cast<const double*>(rec + 16);
+        const int n = h[0], N = h[1], M = h[2];
+        H.n[f] = n; H.rows[f] = N; H.cols[f] = M;
+        for (int q = 0; q < 4; ++q) H.bbox[(size_t)f * 4 + q] = bb[q];
+        const int eN = H.expect[2 * f], eM = H.expect[2 * f + 1];
+        if (n < 0 || n > K || (eN >= 0 && (eN != N || eM != M))) atomicMin(&first_bad, f);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) H.bad[0] = first_bad == 0x7fffffff ? -1 : first_bad;
+}
 __global__ __launch_bounds__(256) void ag_copy_kernel(int nframes, int world, int rank, int unpack, char* __restrict__ buf, size_t slice, size_t nb, int K,
                                                       dsss_kp* __restrict__ kps, uint8_t* __restrict__ desc, double* __restrict__ geo, int* __restrict__ nkp,
-                                                      int* __restrict__ rows, int* __restrict__ cols, double* __restrict__ bbox, uint8_t* __restrict__ desc128)
+                                                      int* __restrict__ rows, int* __restrict__ cols, double* __restrict__ bbox, uint8_t* __restrict__ desc128,
+                                                      const int* __restrict__ bad)
 {
+    if (unpack && bad[0] >= 0) return;                    // a refused header (ag_check_kernel): nothing is unpacked
     const int f = blockIdx.y;
     const int r = ag_owner(nframes, world, f);
     if (unpack ? r == rank : r != rank) return;           // pack: own frames into the own slice; unpack: everybody else's out of theirs
@@ -766,42 +802,50 @@ int dsss_features_allgather(dsss_ctx* c, int nframes)
     const int world = dsss_comm_world(c), rank = dsss_comm_rank(c);
     if (world == 1) return DSSS_OK;
     HIPCHK(c, hipSetDevice(c->device));
+    const bool sift = c->op.descriptor == DSSS_DESC_SIFT128;
     const int f0 = (int)((long long)nframes * rank / world), f1 = (int)((long long)nframes * (rank + 1) / world);
-    for (int f = f0; f < f1; ++f) if (!c->frames[f].has_feat) DSSS_FAIL(c, DSSS_E_STATE, "frame %d (owned by this rank) has no features", f);
+    for (int f = f0; f < f1; ++f) {                           // before anything is sent
+        if (!c->frames[f].has_feat) DSSS_FAIL(c, DSSS_E_STATE, "frame %d (owned by this rank) has no features", f);
+        if (sift && !c->frames[f].has_sift) DSSS_FAIL(c, DSSS_E_STATE, "frame %d (owned by this rank) has no SIFT rows", f);      // (as dsss_features_pack: the receivers take the rows for valid)
+    }
     { int rc = dsss_sync_bboxes(c); if (rc) return rc; }     // the boxes of the own frames are on the device
     const size_t nb = dsss_features_pack_bytes(c);
     int per = 0;
     for (int r = 0; r < world; ++r) per = std::max(per, (int)((long long)nframes * (r + 1) / world - (long long)nframes * r / world));
     const size_t slice = (size_t)per * nb;
-    const size_t hbytes = (size_t)c->max_frames * (3 * sizeof(int) + 4 * sizeof(double)) + 16;
-    { int r1; if ((r1 = c->ag_buf.reserve(c, slice * world)) || (r1 = c->ag_host.reserve(c, hbytes))) return r1; }
+    const size_t hbytes = ag_home_view::bytes(c->max_frames);
+    { int r1; if ((r1 = c->ag_buf.reserve(c, slice * world)) || (r1 = c->ag_host.reserve(c, hbytes)) || (r1 = c->ag_home.reserve(c, hbytes))) return r1; }
     char* d_buf = c->ag_buf.as<char>();
     const hipStream_t st = c->stream;
     const dim3 grid(8, nframes);
     uint8_t* d128 = nullptr;
-    if (c->op.descriptor == DSSS_DESC_SIFT128) { int r2 = dsss_ensure_sift_store(c); if (r2) return r2; d128 = c->desc128.as<uint8_t>(); }
-    hipLaunchKernelGGL(ag_copy_kernel, grid, dim3(256), 0, st, nframes, world, rank, 0, d_buf, slice, nb, c->kcap, c->kps, c->desc, c->geo, c->nkp_dev, c->rows_dev, c->cols_dev, c->bbox_dev, d128);
+    if (sift) { int r2 = dsss_ensure_sift_store(c); if (r2) return r2; d128 = c->desc128.as<uint8_t>(); }
+    const ag_home_view H(c->ag_host.p, c->max_frames), D(c->ag_home.p, c->max_frames);
+    for (int f = 0; f < nframes; ++f) { const dsss_frame& fr = c->frames[f]; H.expect[2 * f] = fr.has_geom ? fr.N : -1; H.expect[2 * f + 1] = fr.has_geom ? fr.M : -1; }
+    HIPCHK(c, hipMemcpyAsync(D.expect, H.expect, sizeof(int) * 2 * nframes, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(ag_copy_kernel, grid, dim3(256), 0, st, nframes, world, rank, 0, d_buf, slice, nb, c->kcap, c->kps, c->desc, c->geo, c->nkp_dev, c->rows_dev, c->cols_dev, c->bbox_dev, d128, D.bad);
     HIPCHK(c, hipGetLastError());
     int rc = dsss_comm_allgather(c, d_buf, slice, st);
     if (rc) return rc;
-    hipLaunchKernelGGL(ag_copy_kernel, grid, dim3(256), 0, st, nframes, world, rank, 1, d_buf, slice, nb, c->kcap, c->kps, c->desc, c->geo, c->nkp_dev, c->rows_dev, c->cols_dev, c->bbox_dev, d128);
+    hipLaunchKernelGGL(ag_check_kernel, dim3(1), dim3(256), 0, st, nframes, world, rank, d_buf, slice, nb, c->kcap, D);
     HIPCHK(c, hipGetLastError());
-    // the host's view of the gathered frames: counts, sizes and boxes in one download
-    int* h_n = c->ag_host.as<int>(); int* h_r = h_n + c->max_frames; int* h_c = h_r + c->max_frames;
-    double* h_bb = reinterpret_cast<double*>(h_c + c->max_frames + (c->max_frames & 1));
-    HIPCHK(c, hipMemcpyAsync(h_n, c->nkp_dev, sizeof(int) * nframes, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(h_r, c->rows_dev, sizeof(int) * nframes, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(h_c, c->cols_dev, sizeof(int) * nframes, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(h_bb, c->bbox_dev, sizeof(double) * 4 * nframes, hipMemcpyDeviceToHost, st));
+    hipLaunchKernelGGL(ag_copy_kernel, grid, dim3(256), 0, st, nframes, world, rank, 1, d_buf, slice, nb, c->kcap, c->kps, c->desc, c->geo, c->nkp_dev, c->rows_dev, c->cols_dev, c->bbox_dev, d128, D.bad);
+    HIPCHK(c, hipGetLastError());
+    // the host's view of the gathered frames -- counts, sizes, boxes -- and the verdict on their headers in one download
+    HIPCHK(c, hipMemcpyAsync(c->ag_host.p, c->ag_home.p, hbytes, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
+    if (H.bad[0] >= 0) {                                      // nothing was unpacked and no frame of the host's is touched
+        const int f = H.bad[0];
+        if (f >= nframes) DSSS_FAIL(c, DSSS_E_HIP, "gathered headers: verdict names frame %d of %d", f, nframes);
+        if (H.n[f] < 0 || H.n[f] > c->kcap) DSSS_FAIL(c, DSSS_E_CAPACITY, "gathered frame %d: %d features exceed the per-frame capacity %d", f, H.n[f], c->kcap);
+        DSSS_FAIL(c, DSSS_E_ARG, "gathered frame %d: geometry mismatch (%d x %d here, %d x %d at its owner)", f, c->frames[f].N, c->frames[f].M, H.rows[f], H.cols[f]);
+    }
     for (int f = 0; f < nframes; ++f) {
         if (f >= f0 && f < f1) continue;
         dsss_frame& fr = c->frames[f];
-        if (h_n[f] < 0 || h_n[f] > c->kcap) DSSS_FAIL(c, DSSS_E_CAPACITY, "gathered frame %d: %d features exceed the per-frame capacity %d", f, h_n[f], c->kcap);
-        if (!fr.has_geom) { fr.N = h_r[f]; fr.M = h_c[f]; }
-        else if (fr.N != h_r[f] || fr.M != h_c[f]) DSSS_FAIL(c, DSSS_E_ARG, "gathered frame %d: geometry mismatch (%d x %d here, %d x %d at its owner)", f, fr.N, fr.M, h_r[f], h_c[f]);
-        fr.nkp = h_n[f]; fr.has_feat = true; fr.has_sift = d128 != nullptr;
-        memcpy(fr.bbox, h_bb + (size_t)f * 4, 4 * sizeof(double)); fr.has_bbox = true; fr.bbox_async = false;
+        if (!fr.has_geom) { fr.N = H.rows[f]; fr.M = H.cols[f]; }
+        fr.nkp = H.n[f]; fr.has_feat = true; fr.has_sift = d128 != nullptr;
+        memcpy(fr.bbox, H.bbox + (size_t)f * 4, 4 * sizeof(double)); fr.has_bbox = true; fr.bbox_async = false;
     }
     return DSSS_OK;
 }

@@ -168,7 +168,8 @@ struct dsss_ctx {
     int pg_parts = 0;                   // pose-graph partitions (0: one per rank); > ranks only to exercise the interface logic on few GPUs
     dsss_buf tmp_dev{"tmp_dev"};                   // 64 ints of device scratch for one-value results (dsss_descriptor_distance)
     dsss_buf ag_buf{"ag_buf"};                                            // staging of dsss_features_allgather: world x (frames per rank) packed records, kept between calls
-    dsss_buf ag_host{"ag_host", DSSS_PINNED};                              // page-locked landing place of the gathered headers (keypoint counts, boxes, sizes)
+    dsss_buf ag_host{"ag_host", DSSS_PINNED};                              // page-locked landing place of the gathered headers (keypoint counts, boxes, sizes) and of the verdict on them
+    dsss_buf ag_home{"ag_home"};                                          // its device twin: ag_check_kernel writes it before the unpack pass runs, ONE download brings it home
     dsss_buf xch_dev{"xch_dev"};                                           // device scratch of the loop-closure exchange between ranks (dsss_posegraph_solve)
     dsss_buf pg_edges_host{"pg_edges_host", DSSS_PINNED};                        // page-locked staging of the selected LC edges (dsss_posegraph_solve)
     dsss_buf pg_ab_host{"pg_ab_host", DSSS_PINNED};                     // their end points as packed (a, b) pairs

@@ -103,7 +103,10 @@ int dsss_comm_stats(dsss_ctx*, int* rank, int* world, double* allreduce_bytes, i
 /* frames are owned in contiguous blocks: rank r owns frames [nframes r / world, nframes (r+1) / world)                     */
 int dsss_comm_frame_owner(const dsss_ctx*, int nframes, int frame);
 /* after every rank extracted the frames it owns: exchange the per-frame feature records (C1 of SURVEY.md 2a, one all-gather)
- * so that every rank holds the features of all nframes frames                                                             */
+ * so that every rank holds the features of all nframes frames.  Refusals: an owned frame without features -- or, under
+ * DSSS_DESC_SIFT128, without SIFT rows -- is DSSS_E_STATE before anything is sent; a gathered record whose count lies outside
+ * [0, capacity] is DSSS_E_CAPACITY, one whose N x M is not the geometry this context holds for the frame DSSS_E_ARG, and then
+ * NO frame has changed, on the device or on the host: the headers are judged before a record is unpacked.                   */
 int dsss_features_allgather(dsss_ctx*, int nframes);
 /* number of pose-graph partitions (default 0 = one per rank); more partitions than ranks only exercise the interface path */
 int dsss_set_pg_partitions(dsss_ctx*, int nparts);

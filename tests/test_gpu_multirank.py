@@ -397,6 +397,66 @@ def test_reversed_edges_across_ranks(orc, world):
         assert (res[0][1] == res[r][1]).all()
 
 
+def _single_rank_record(F, raws, poses, alts, grs):
+    """the single-rank pipeline on a survey and everything the ranks of a sharded run exchange about it: per-frame features and boxes,
+    the selected loop closures, the trajectory and the LM's stats"""
+    from diasss_amd.pipeline import Pipeline
+    pipe = Pipeline(F, device=0)
+    traj, stats = pipe.run(raws, poses, alts, grs)
+    one = dict(traj=traj.copy(), stats=np.array(stats), nb=pipe.ctx.pack_bytes(), edges=pipe.ctx.posegraph_select(F),
+               feats=[pipe.ctx.features_get(f) + (pipe.ctx.frame_bbox(f),) for f in range(F)])
+    pipe.close()
+    return one
+
+
+@pytest.mark.parametrize("F,W", [(7, 3), (5, 4)])
+def test_uneven_blocks_in_lockstep(F, W):
+    """Uneven splits through the whole pipeline: the ranks run in lock step inside this process (tools/emulate_ranks.py:record, one
+    context and one thread per rank over the host-callback transport); 7 frames on 3 ranks are blocks of 2, 2, 3, and of 5 frames on
+    4 ranks rank 0 owns frame 0 alone, matches no pair and contributes no loop closure (tests/feature_transport_ref.py: LOCKSTEP).
+    Held to a single-rank Pipeline on the same survey: the trajectory to 1e-9 with the same iteration count (every rank's bits are
+    rank 0's: record() asserts it), and WHAT TRAVELLED to the bit -- every record of the feature all-gather parsed in numpy (count,
+    N, M, box, the first n rows of kps, desc, geo), and the loop closures of the edge exchange: unequal counts per rank, and the
+    first cnt[r] records of the rows, in rank order, are the single-rank selection in its order, a, b, rel and var bit for bit (a
+    pair's mini-LM reads that pair's rows and nothing else, and the rows come from features that are the single-rank ones)."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import emulate_ranks as E
+    from diasss_amd import capi
+    from tests import feature_transport_ref as R
+    assert (F, W) in R.LOCKSTEP
+    N, M = 700, 480
+    log, traj, stats, data = E.record(dict(F=F, N=N, M=M), 91, W)   # seed 91 = _survey()'s survey
+    one = _single_rank_record(F, *data)                             # the very frames the ranks extracted
+    assert len(one["edges"]) > 20
+    assert stats[0] == one["stats"][0] and np.abs(traj - one["traj"]).max() < 1e-9
+    ops = log[0]                                                    # (every rank receives the same result of a collective)
+    assert all(len(log[r]) == len(ops) for r in range(W))
+    # the feature all-gather: the first collective of a step
+    nb = one["nb"]; K = R.capacity(nb, False)
+    assert ops[0][0] == 1 and ops[0][1].shape == (W, R.slice_bytes(F, W, nb))
+    for f in range(F):
+        p = R.parse_record(R.record_at(ops[0][1][R.owner(F, W, f)], F, W, f, nb), K, False)
+        kps, desc, geo, bb = one["feats"][f]
+        n = len(kps)
+        assert n > 0 and (p["n"], p["N"], p["M"]) == (n, N, M), f
+        assert p["bbox"].tobytes() == bb.tobytes(), f
+        assert p["kps"][:n].tobytes() == kps.tobytes() and p["desc"][:n].tobytes() == desc.tobytes() and p["geo"][:n].tobytes() == geo.tobytes(), f
+    # the edge exchange: the counts (an all-reduce as long as the world), then the records (an all-gather of the largest count)
+    assert ops[1][0] == 0 and ops[1][1].shape == (W,) and ops[2][0] == 1
+    cnt = ops[1][1].astype(np.int64)
+    assert (cnt == ops[1][1]).all() and (cnt >= 0).all()
+    assert len(set(cnt.tolist())) > 1                               # unequal counts: what the case is for
+    if (F, W) == (5, 4):
+        assert cnt[0] == 0 and (cnt[1:] > 0).all()                  # the rank that matched nothing: padding alone in its row
+    size = capi.LCEDGE_DTYPE.itemsize
+    assert ops[2][1].shape == (W, int(cnt.max()) * size)
+    got = np.concatenate([np.ascontiguousarray(ops[2][1][r][:int(cnt[r]) * size]).view(capi.LCEDGE_DTYPE) for r in range(W)])
+    want = one["edges"]
+    assert len(got) == len(want) == int(cnt.sum())
+    assert (got["a"] == want["a"]).all() and (got["b"] == want["b"]).all()
+    assert got["rel"].tobytes() == want["rel"].tobytes() and got["var"].tobytes() == want["var"].tobytes()
+
+
 def test_emulated_ranks_replay_reproduces_lockstep():
     """tools/emulate_ranks.py (bench.py --emulate-rank): three ranks in lock step inside one process over the host-callback
     transport, then every rank ALONE through the device-callback transport replaying the recorded collectives: same trajectory to
