@@ -54,6 +54,12 @@ class MosaicParams(C.Structure):
                 ("use_mask", C.c_int32), ("pad_", C.c_int32)]
 
 
+class GainParams(C.Structure):
+    """dsss_gain_params: the fewest samples a column (with its window) needs to get a gain of its own, the half-width of the window
+    in columns (0..16, never across the nadir) and the grey level the columns are brought to (0: the pooled mean)"""
+    _fields_ = [("min_count", C.c_int32), ("smooth", C.c_int32), ("target", C.c_int32), ("pad_", C.c_int32)]
+
+
 class RegParams(C.Structure):
     """dsss_reg_params: search radius in cells (0..16) and the fewest overlapping cells a shift needs to be usable"""
     _fields_ = [("radius", C.c_int32), ("min_cells", C.c_int32)]
@@ -260,6 +266,16 @@ def lib():
         L.dsss_posegraph_solve_gated.restype = C.c_int
         L.dsss_posegraph_solve_gated.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(PGGateParams), C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
+        L.dsss_gain_params_default.restype = None
+        L.dsss_gain_params_default.argtypes = [C.POINTER(GainParams)]
+        L.dsss_mosaic_gain_stats.restype = C.c_int
+        L.dsss_mosaic_gain_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.dsss_mosaic_gain_table.restype = C.c_int
+        L.dsss_mosaic_gain_table.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(GainParams), C.c_void_p, C.POINTER(C.c_int32)]
+        L.dsss_mosaic_gain_set.restype = C.c_int
+        L.dsss_mosaic_gain_set.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.dsss_mosaic_gain_get.restype = C.c_int
+        L.dsss_mosaic_gain_get.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
         L.dsss_reg_params_default.restype = None
         L.dsss_reg_params_default.argtypes = [C.POINTER(RegParams)]
         L.dsss_mosaic_register.restype = C.c_int
@@ -348,6 +364,32 @@ def mosaic_grid(bbox4, cell):
         e.code = rc
         raise e
     return p
+
+
+def gain_params_default():
+    g = GainParams(); lib().dsss_gain_params_default(C.byref(g)); return g
+
+
+def mosaic_gain_table(sum, cnt, params=None):
+    """dsss_mosaic_gain_table: the column statistics S, C (M uint64 each, as Context.mosaic_gain_stats returns them) -> (gain, T): the
+    range-gain table (M uint16, Q8) and the grey level it brings the columns to.  params: a GainParams, None = the defaults.
+    Host arithmetic, no context."""
+    L = lib()
+    if sum is not None:
+        sum = np.ascontiguousarray(sum, np.uint64)
+    if cnt is not None:
+        cnt = np.ascontiguousarray(cnt, np.uint64)
+    M = len(sum) if sum is not None else (len(cnt) if cnt is not None else 0)
+    if sum is not None and cnt is not None and sum.shape != cnt.shape:
+        raise ValueError("mosaic_gain_table: %d sums and %d counts" % (sum.size, cnt.size))
+    gain = np.empty(max(M, 0), np.uint16)
+    T = C.c_int32(0)
+    rc = L.dsss_mosaic_gain_table(_ptr(sum), _ptr(cnt), int(M), C.byref(params) if params is not None else None, _ptr(gain), C.byref(T))
+    if rc != 0:
+        e = DsssError("dsss_mosaic_gain_table: %s (M %d)" % (L.dsss_strerror(rc).decode(), M))
+        e.code = rc
+        raise e
+    return gain, int(T.value)
 
 
 def _reg_pairs(pairs):
@@ -917,6 +959,41 @@ class Context:
         self._chk(self.L.dsss_mosaic_consistency(self.h, _ptr(ids), len(ids), _ptr(rpy6), _ptr(ping_off), C.byref(params),
                                                  _ptr(nfr), _ptr(s1), _ptr(s2), C.byref(score)), "dsss_mosaic_consistency")
         return nfr, s1, s2, score.value
+
+    def mosaic_gain_stats(self, ids, use_mask=1):
+        """dsss_mosaic_gain_stats: the column statistics of the listed frames (all of one M) -> (S, C), M uint64 each: the sum and the
+        number of the kept samples of every column (use_mask != 0: the samples the filter mask keeps)"""
+        ids = np.ascontiguousarray(ids, np.int32)
+        M = C.c_int(0)                                           # the columns of the first frame: the library holds every other one to it
+        if len(ids):
+            self._chk(self.L.dsss_frame_get_level(self.h, int(ids[0]), 0, None, None, C.byref(M)), "dsss_mosaic_gain_stats (the frame's size)")
+        M = M.value
+        S = np.zeros(max(M, 1), np.uint64); Cn = np.zeros(max(M, 1), np.uint64)
+        self._chk(self.L.dsss_mosaic_gain_stats(self.h, _ptr(ids), len(ids), int(use_mask), _ptr(S), _ptr(Cn)), "dsss_mosaic_gain_stats")
+        return S[:M], Cn[:M]
+
+    def mosaic_gain_set(self, table):
+        """dsss_mosaic_gain_set: install the range-gain table (M uint16, Q8) every mosaic and registration entry applies from now on;
+        None clears it"""
+        if table is None:
+            self._chk(self.L.dsss_mosaic_gain_set(self.h, None, 0), "dsss_mosaic_gain_set")
+            return
+        table = np.ascontiguousarray(table, np.uint16)
+        self._chk(self.L.dsss_mosaic_gain_set(self.h, _ptr(table), int(table.size)), "dsss_mosaic_gain_set")
+
+    def mosaic_gain_get(self, cap=None):
+        """dsss_mosaic_gain_get: the table in force, read back from the device (M uint16), or None when none is set.  cap: the room
+        offered (None: what the table needs)"""
+        M = C.c_int(0)
+        if cap is None:                                          # ask for the size first: *M is written also when the room does not suffice
+            rc = self.L.dsss_mosaic_gain_get(self.h, None, 0, C.byref(M))
+            if M.value == 0:
+                self._chk(rc, "dsss_mosaic_gain_get")
+                return None
+            cap = M.value
+        out = np.empty(max(int(cap), 1), np.uint16)
+        self._chk(self.L.dsss_mosaic_gain_get(self.h, _ptr(out), int(cap), C.byref(M)), "dsss_mosaic_gain_get")
+        return out[:M.value].copy() if M.value else None
 
     def mosaic_register(self, ids, params, pairs, reg=None, rpy6=None, ping_off=None, want_sums=False):
         """dense overlap registration of the frame pairs `pairs` = [(a, b), ...] (frame ids, both in ids) under the trajectory: frame b slid

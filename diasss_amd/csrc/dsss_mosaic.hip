@@ -81,6 +81,109 @@ __global__ __launch_bounds__(256) void mosaic_fold_kernel(const unsigned long lo
     nfr[g] += 1; s1[g] += m; s2[g] += m * m;
 }
 
+// ---- range-gain normalisation ("range-gain normalisation" in the header)
+#define COLSTAT_COLS 4                     // consecutive columns a lane owns: one dword of a row
+#define COLSTAT_LANES 64                   // lanes across a row at most: a wavefront reads 256 consecutive bytes of it (the whole workgroup across took four times the atomics and 0.36 ms where this takes 0.22: DESIGN.md section 4, "Range-gain normalisation")
+#define COLSTAT_ROWS 128                   // rows a lane walks: 128 x 255 < 2^16, far inside the u32 partials
+#define COLSTAT_BATCH 8                    // rows a lane has in flight (two dwords each)
+
+// a frame's workgroups: chunks of tpr x 4 columns x blocks of (256 / tpr) x COLSTAT_ROWS rows, tpr = the power of two of lanes that
+// cover a row's groups of four columns, COLSTAT_LANES at most
+__host__ __device__ inline int colstat_tpr(int M)
+{
+    const int groups = (M + COLSTAT_COLS - 1) / COLSTAT_COLS;
+    int tpr = 1;
+    while (tpr < groups && tpr < COLSTAT_LANES) tpr <<= 1;
+    return tpr;
+}
+__host__ __device__ inline int colstat_chunks(int M) { const int tpr = colstat_tpr(M); return ((M + COLSTAT_COLS - 1) / COLSTAT_COLS + tpr - 1) / tpr; }
+
+// one dword of image and one of mask into the partials of the lane's four columns
+template <bool MASK> __device__ __forceinline__ void colstat_add(uint32_t v, uint32_t m, uint32_t (&s)[COLSTAT_COLS], uint32_t (&n)[COLSTAT_COLS])
+{
+#pragma unroll
+    for (int k = 0; k < COLSTAT_COLS; ++k) {
+        const bool keep = !MASK || ((m >> (8 * k)) & 0xffu) != 0;
+        s[k] += keep ? (v >> (8 * k)) & 0xffu : 0u; n[k] += keep ? 1u : 0u;
+    }
+}
+
+// the rows row0, row0 + rl, ... below row1 of the lane's dword column.  nmin (uniform per workgroup) = the rows every lane of the
+// workgroup has, COLSTAT_ROWS but in a frame's last block: they go in batches whose trip count no lane disagrees about, so
+// COLSTAT_BATCH rows are loaded before the first is used; what is left, at most COLSTAT_BATCH rows a lane, goes one by one.
+template <bool MASK> __device__ __forceinline__ void colstat_words(const uint32_t* __restrict__ img, const uint32_t* __restrict__ msk, size_t M4, int row0, int row1, int rl,
+                                                                   int nmin, uint32_t (&s)[COLSTAT_COLS], uint32_t (&n)[COLSTAT_COLS])
+{
+    const uint32_t* __restrict__ pi = img + (size_t)row0 * M4; const uint32_t* __restrict__ pm = msk + (size_t)row0 * M4;
+    const size_t step = (size_t)rl * M4;
+    const int nb = nmin - nmin % COLSTAT_BATCH;
+    for (int i = 0; i < nb; i += COLSTAT_BATCH) {
+        uint32_t v[COLSTAT_BATCH], m[COLSTAT_BATCH];
+#pragma unroll
+        for (int j = 0; j < COLSTAT_BATCH; ++j) { v[j] = pi[(size_t)(i + j) * step]; m[j] = MASK ? pm[(size_t)(i + j) * step] : 0u; }
+#pragma unroll
+        for (int j = 0; j < COLSTAT_BATCH; ++j) colstat_add<MASK>(v[j], m[j], s, n);
+    }
+    for (int row = row0 + nb * rl; row < row1; row += rl) colstat_add<MASK>(img[(size_t)row * M4], MASK ? msk[(size_t)row * M4] : 0u, s, n);
+}
+
+// S[c] = sum of the kept samples of column c, C[c] = their number, over all frames of the job table: out[c] += S, out[M + c] += C.
+// A streaming integer reduction, two bytes read per sample and nothing else.  A lane owns four consecutive columns; tpr lanes (a
+// wavefront at most) lie across a row, so a wavefront reads consecutive dwords of it, and the 256 / tpr lanes that share a column group
+// take rows `rl` apart -- four wavefronts four rows, and a narrow frame still fills the workgroup.  A lane walks COLSTAT_ROWS rows with
+// the eight u32 partials of its columns in registers, COLSTAT_BATCH rows in flight; the lanes of a group add their partials up through
+// LDS, and the first of them leaves through 64-bit atomics without return -- integers, so the result does not depend on their order --
+// only for columns that kept a sample.  Rows are dword-aligned where M % 4 == 0 and the images are; otherwise (uniform per launch: all
+// frames have one M) a lane reads its four bytes one by one, and the columns behind M are skipped.
+__global__ __launch_bounds__(256) void mosaic_colstat_kernel(const mosaic_job* __restrict__ jobs, int njobs, int use_mask, unsigned long long* __restrict__ out)
+{
+    __shared__ uint32_t s_part[2 * COLSTAT_COLS][256];
+    int lo = 0, hi = njobs - 1;
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (jobs[mid].blk0 <= (int)blockIdx.x) lo = mid; else hi = mid - 1; }
+    const mosaic_job J = jobs[lo];
+    const int M = J.M, tpr = colstat_tpr(M), rl = 256 / tpr, chunks = colstat_chunks(M), rows_wg = rl * COLSTAT_ROWS;
+    const int wg = (int)blockIdx.x - J.blk0;
+    const int rb = wg / chunks, ch = wg - rb * chunks;
+    const int col = (ch * tpr + ((int)threadIdx.x & (tpr - 1))) * COLSTAT_COLS;
+    const int row0 = rb * rows_wg + (int)threadIdx.x / tpr, row1 = min(J.N, (rb + 1) * rows_wg);
+    const int nmin = (row1 - rb * rows_wg) / rl;                                  // rows every lane of the workgroup has
+    uint32_t s[COLSTAT_COLS] = { 0, 0, 0, 0 }, n[COLSTAT_COLS] = { 0, 0, 0, 0 };
+    if (col < M) {
+        if (M % 4 == 0 && (((uintptr_t)J.img | (uintptr_t)J.mask) & 3) == 0) {
+            const uint32_t* img = reinterpret_cast<const uint32_t*>(J.img + col); const uint32_t* msk = reinterpret_cast<const uint32_t*>(J.mask + col);
+            if (use_mask) colstat_words<true>(img, msk, (size_t)(M / 4), row0, row1, rl, nmin, s, n);
+            else colstat_words<false>(img, msk, (size_t)(M / 4), row0, row1, rl, nmin, s, n);
+        } else {
+            const int nc = min(COLSTAT_COLS, M - col);
+            for (int row = row0; row < row1; row += rl) {
+                const uint8_t* __restrict__ img = J.img + (size_t)row * M + col;
+                const uint8_t* __restrict__ msk = J.mask + (size_t)row * M + col;
+#pragma unroll
+                for (int k = 0; k < COLSTAT_COLS; ++k) {
+                    if (k >= nc) continue;
+                    const bool keep = !use_mask || msk[k] != 0;
+                    s[k] += keep ? (uint32_t)img[k] : 0u; n[k] += keep ? 1u : 0u;
+                }
+            }
+        }
+    }
+    if (rl > 1) {                                                                  // (uniform per launch)
+#pragma unroll
+        for (int k = 0; k < COLSTAT_COLS; ++k) { s_part[k][threadIdx.x] = s[k]; s_part[COLSTAT_COLS + k][threadIdx.x] = n[k]; }
+        __syncthreads();
+        if ((int)threadIdx.x >= tpr) return;
+        for (int r = 1; r < rl; ++r) {
+#pragma unroll
+            for (int k = 0; k < COLSTAT_COLS; ++k) { s[k] += s_part[k][threadIdx.x + r * tpr]; n[k] += s_part[COLSTAT_COLS + k][threadIdx.x + r * tpr]; }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < COLSTAT_COLS; ++k) {
+        if (col + k >= M || n[k] == 0) continue;
+        atomicAdd(&out[col + k], (unsigned long long)s[k]); atomicAdd(&out[M + col + k], (unsigned long long)n[k]);
+    }
+}
+
 } // namespace
 
 // ---- host helpers shared with dsss_mosaic_reg.hip (dsss_mosaic_int.h)
@@ -175,6 +278,26 @@ int upload_rows(dsss_ctx* c, const int* ids, int n, const double* rpy6, const in
     return DSSS_OK;
 }
 
+int mosaic_check_gain(dsss_ctx* c, const int* ids, int n)
+{
+    if (!c->mosaic_gain_M) return DSSS_OK;
+    for (int i = 0; i < n; ++i)
+        if (c->frames[ids[i]].M != c->mosaic_gain_M)
+            DSSS_FAIL(c, DSSS_E_ARG, "mosaic: the range-gain table has %d columns, frame %d has %d", c->mosaic_gain_M, ids[i], c->frames[ids[i]].M);
+    return DSSS_OK;
+}
+
+int mosaic_fill_jobs(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, double* d_rows, std::vector<mosaic_job>& jobs)
+{
+    int rc = mosaic_check_gain(c, ids, n); if (rc) return rc;
+    std::vector<const double*> dev_rows;
+    rc = upload_rows(c, ids, n, rpy6, ping_off, d_rows, dev_rows); if (rc) return rc;
+    const uint16_t* gain = c->mosaic_gain_M ? c->mosaic_gain.as<uint16_t>() : nullptr;
+    jobs.resize(n);
+    for (int i = 0; i < n; ++i) { const dsss_frame& f = c->frames[ids[i]]; jobs[i] = mosaic_job{ dev_rows[i], f.gr, f.lvl[0], f.mask, gain, f.N, f.M, 0, 0 }; }
+    return DSSS_OK;
+}
+
 void launch_scatter(dsss_ctx* c, const mosaic_job* d_jobs, int njobs, int blocks, const mosaic_win& G, unsigned long long* acc)
 {
     hipLaunchKernelGGL(mosaic_scatter_kernel, dim3((unsigned)blocks), dim3(256), 0, c->stream, d_jobs, njobs, G, acc);
@@ -221,6 +344,7 @@ int dsss_mosaic_render(dsss_ctx* c, const int* ids, int n, const double* rpy6, c
     size_t rows = 0;
     int rc = mosaic_check_frames(c, ids, n, rpy6, ping_off, true, &rows); if (rc) return rc;
     rc = mosaic_check_params(c, p); if (rc) return rc;
+    rc = mosaic_check_gain(c, ids, n); if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t cells = (size_t)p->W * p->H;
     carve L;
@@ -235,15 +359,14 @@ int dsss_mosaic_render(dsss_ctx* c, const int* ids, int n, const double* rpy6, c
     uint8_t* d_img = img_host ? reinterpret_cast<uint8_t*>(B + o_img) : nullptr;
     mosaic_job* d_jobs = reinterpret_cast<mosaic_job*>(B + o_jobs);
     int* d_flag = reinterpret_cast<int*>(B + o_flag);
-    std::vector<const double*> dev_rows;
-    rc = upload_rows(c, ids, n, rpy6, ping_off, reinterpret_cast<double*>(B + o_rows), dev_rows); if (rc) return rc;
+    std::vector<mosaic_job> jobs;
+    rc = mosaic_fill_jobs(c, ids, n, rpy6, ping_off, reinterpret_cast<double*>(B + o_rows), jobs); if (rc) return rc;
     HIPCHK(c, hipMemsetAsync(acc, 0, cells * 8, c->stream));
     HIPCHK(c, hipMemsetAsync(d_flag, 0, sizeof(int), c->stream));
     const mosaic_win G{ p->x0, p->y0, p->cell, p->W, p->H, 0, 0, p->W, p->H, p->use_mask != 0 };
     const unsigned ublocks = (unsigned)((cells + 255) / 256);
     // launches of at most 2^31 samples, the sample limit checked between them: a cell's count then stays far below 2^32 until the
     // check sees it, so the packed accumulator cannot wrap unnoticed whatever the number of frames
-    std::vector<mosaic_job> jobs(n);
     int j0 = 0;
     while (j0 < n) {
         int j1 = j0, blocks = 0; size_t samples = 0;
@@ -251,7 +374,7 @@ int dsss_mosaic_render(dsss_ctx* c, const int* ids, int n, const double* rpy6, c
             const dsss_frame& f = c->frames[ids[j1]];
             const size_t s = (size_t)f.N * f.M;
             if (j1 > j0 && samples + s > (1ull << 31)) break;
-            jobs[j1] = mosaic_job{ dev_rows[j1], f.gr, f.lvl[0], f.mask, f.N, f.M, blocks, 0 };
+            jobs[j1].blk0 = blocks;
             blocks += f.N; samples += s; ++j1;
         }
         HIPCHK(c, hipMemcpyAsync(d_jobs + j0, jobs.data() + j0, (size_t)(j1 - j0) * sizeof(mosaic_job), hipMemcpyHostToDevice, c->stream));
@@ -273,6 +396,107 @@ int dsss_mosaic_render(dsss_ctx* c, const int* ids, int n, const double* rpy6, c
     return DSSS_OK;
 }
 
+// ---- range-gain normalisation
+void dsss_gain_params_default(dsss_gain_params* p) { if (p) { p->min_count = 256; p->smooth = 0; p->target = 0; p->pad_ = 0; } }
+
+int dsss_mosaic_gain_stats(dsss_ctx* c, const int* ids, int n, int use_mask, uint64_t* sum_host, uint64_t* cnt_host)
+{
+    if (!c) return DSSS_E_ARG;
+    if (!sum_host || !cnt_host) DSSS_FAIL(c, DSSS_E_ARG, "gain: nowhere to write the column %s", sum_host ? "counts" : "sums");
+    size_t rows = 0;
+    int rc = mosaic_check_frames(c, ids, n, nullptr, nullptr, true, &rows); if (rc) return rc;
+    const int M = c->frames[ids[0]].M;
+    if (M < 2) DSSS_FAIL(c, DSSS_E_ARG, "gain: frames of %d columns", M);
+    for (int i = 1; i < n; ++i)
+        if (c->frames[ids[i]].M != M) DSSS_FAIL(c, DSSS_E_ARG, "gain: frame %d has %d columns, frame %d has %d", ids[0], M, ids[i], c->frames[ids[i]].M);
+    HIPCHK(c, hipSetDevice(c->device));
+    carve L;
+    const size_t o_out = L.take((size_t)M * 16), o_jobs = L.take((size_t)n * sizeof(mosaic_job));
+    rc = c->mosaic_buf.reserve(c, L.off); if (rc) return rc;
+    char* B = c->mosaic_buf.as<char>();
+    unsigned long long* d_out = reinterpret_cast<unsigned long long*>(B + o_out);
+    mosaic_job* d_jobs = reinterpret_cast<mosaic_job*>(B + o_jobs);
+    // the statistics are those of the uncorrected samples whatever table is set: the jobs carry the images alone
+    std::vector<mosaic_job> jobs(n);
+    const int chunks = colstat_chunks(M), rows_wg = (256 / colstat_tpr(M)) * COLSTAT_ROWS;
+    long long blocks = 0;
+    for (int i = 0; i < n; ++i) {
+        const dsss_frame& f = c->frames[ids[i]];
+        jobs[i] = mosaic_job{ nullptr, nullptr, f.lvl[0], f.mask, nullptr, f.N, f.M, (int)blocks, 0 };
+        blocks += (long long)chunks * ((f.N + rows_wg - 1) / rows_wg);
+    }
+    if (blocks > 0x7fffffffll) DSSS_FAIL(c, DSSS_E_ARG, "gain: %d frames of %d columns are more than one launch takes", n, M);
+    HIPCHK(c, hipMemcpyAsync(d_jobs, jobs.data(), (size_t)n * sizeof(mosaic_job), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_out, 0, (size_t)M * 16, c->stream));
+    if (blocks) hipLaunchKernelGGL(mosaic_colstat_kernel, dim3((unsigned)blocks), dim3(256), 0, c->stream, d_jobs, n, use_mask != 0, d_out);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(sum_host, d_out, (size_t)M * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(cnt_host, d_out + M, (size_t)M * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return DSSS_OK;
+}
+
+int dsss_mosaic_gain_table(const uint64_t* sum, const uint64_t* cnt, int M, const dsss_gain_params* gp, uint16_t* gain_q8, int32_t* target_out)
+{
+    dsss_gain_params P;
+    dsss_gain_params_default(&P);
+    if (gp) P = *gp;
+    if (!sum || !cnt || !gain_q8 || M < 2) return DSSS_E_ARG;
+    if (P.min_count < 1 || P.smooth < 0 || P.smooth > 16 || P.target < 0 || P.target > 255) return DSSS_E_ARG;
+    typedef unsigned __int128 u128;
+    const int half = M / 2;
+    std::vector<u128> Ss(M), Cs(M);
+    std::vector<char> elig(M);
+    u128 tS = 0, tC = 0;
+    bool any = false;
+    for (int c = 0; c < M; ++c) {
+        const int lo = std::max(c - P.smooth, c < half ? 0 : half), hi = std::min(c + P.smooth, c < half ? half - 1 : M - 1);      // never across the nadir
+        u128 s = 0, n = 0;
+        for (int k = lo; k <= hi; ++k) { s += sum[k]; n += cnt[k]; }
+        Ss[c] = s; Cs[c] = n;
+        elig[c] = n >= (u128)P.min_count && s > 0;
+        if (elig[c]) { any = true; tS += sum[c]; tC += cnt[c]; }
+    }
+    u128 T = 0;
+    if (any) { if (P.target) T = (u128)P.target; else if (tC > 0) T = (tS + tC / 2) / tC; else any = false; }
+    for (int c = 0; c < M; ++c) {
+        if (!any || !elig[c]) { gain_q8[c] = 256; continue; }
+        const u128 g = (T * Cs[c] * 256 + Ss[c] / 2) / Ss[c];
+        gain_q8[c] = g > 65535 ? (uint16_t)65535 : (uint16_t)g;
+    }
+    if (target_out) *target_out = any ? (int32_t)std::min<u128>(T, 0x7fffffff) : 0;
+    return DSSS_OK;
+}
+
+// The new table goes into a block of its own and takes the old one's place only after its upload succeeded: an error leaves the old
+// table in force.  (Every entry that reads the table synchronises before it returns, so no queued kernel still reads the old block.)
+int dsss_mosaic_gain_set(dsss_ctx* c, const uint16_t* gain_q8_host, int M)
+{
+    if (!c) return DSSS_E_ARG;
+    if (!gain_q8_host) { c->mosaic_gain_M = 0; return DSSS_OK; }
+    if (M < 2) DSSS_FAIL(c, DSSS_E_ARG, "gain: a table of %d columns", M);
+    HIPCHK(c, hipSetDevice(c->device));
+    dsss_buf nb{"mosaic_gain"};
+    const int rc = nb.reserve(c, (size_t)M * sizeof(uint16_t)); if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(nb.p, gain_q8_host, (size_t)M * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->mosaic_gain = std::move(nb); c->mosaic_gain_M = M;
+    return DSSS_OK;
+}
+
+int dsss_mosaic_gain_get(dsss_ctx* c, uint16_t* gain_q8_host, int cap, int* M)
+{
+    if (!c) return DSSS_E_ARG;
+    if (!M) DSSS_FAIL(c, DSSS_E_ARG, "gain: nowhere to write the number of columns");
+    *M = c->mosaic_gain_M;                                                      // also when there is no room for them: the caller learns how many
+    if (!c->mosaic_gain_M) return DSSS_OK;
+    if (!gain_q8_host || cap < c->mosaic_gain_M) DSSS_FAIL(c, DSSS_E_ARG, "gain: a table of %d columns, room for %d", c->mosaic_gain_M, gain_q8_host ? cap : 0);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(gain_q8_host, c->mosaic_gain.p, (size_t)c->mosaic_gain_M * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return DSSS_OK;
+}
+
 int dsss_mosaic_consistency(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, const dsss_mosaic_params* p,
                             uint32_t* nfr_host, uint32_t* s1_host, uint32_t* s2_host, double* score_host)
 {
@@ -280,6 +504,7 @@ int dsss_mosaic_consistency(dsss_ctx* c, const int* ids, int n, const double* rp
     size_t rows = 0;
     int rc = mosaic_check_frames(c, ids, n, rpy6, ping_off, true, &rows); if (rc) return rc;
     rc = mosaic_check_params(c, p); if (rc) return rc;
+    rc = mosaic_check_gain(c, ids, n); if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t cells = (size_t)p->W * p->H;
     // every frame is rendered alone into a window of the grid: the cells its geo extremes can reach
@@ -304,10 +529,8 @@ int dsss_mosaic_consistency(dsss_ctx* c, const int* ids, int n, const double* rp
     unsigned long long* d_win = reinterpret_cast<unsigned long long*>(B + o_win);
     mosaic_job* d_jobs = reinterpret_cast<mosaic_job*>(B + o_jobs);
     int* d_flag = reinterpret_cast<int*>(B + o_flag);
-    std::vector<const double*> dev_rows;
-    rc = upload_rows(c, ids, n, rpy6, ping_off, reinterpret_cast<double*>(B + o_rows), dev_rows); if (rc) return rc;
-    std::vector<mosaic_job> jobs(n);
-    for (int i = 0; i < n; ++i) { const dsss_frame& f = c->frames[ids[i]]; jobs[i] = mosaic_job{ dev_rows[i], f.gr, f.lvl[0], f.mask, f.N, f.M, 0, 0 }; }
+    std::vector<mosaic_job> jobs;
+    rc = mosaic_fill_jobs(c, ids, n, rpy6, ping_off, reinterpret_cast<double*>(B + o_rows), jobs); if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(d_jobs, jobs.data(), (size_t)n * sizeof(mosaic_job), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemsetAsync(d_nfr, 0, cells * 12, c->stream));
     HIPCHK(c, hipMemsetAsync(d_flag, 0, sizeof(int), c->stream));

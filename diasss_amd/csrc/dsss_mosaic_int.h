@@ -13,8 +13,9 @@
 #define PYR_MAX_LEVELS 4                   // levels of a cell pyramid
 #define PYR_MAX_CENTRE (1 << 28)           // |cx|, |cy| of a level's centre: twice the centre plus the radius stays an int32
 
-// one frame of a launch: its pose rows (the frame's own or the caller's trajectory), geometry and images; blk0 = its first workgroup
-struct mosaic_job { const double* pose; const double* gr; const uint8_t* img; const uint8_t* mask; int N, M, blk0, pad; };
+// one frame of a launch: its pose rows (the frame's own or the caller's trajectory), geometry and images; blk0 = its first workgroup;
+// gain = the context's range-gain table (M x u16, Q8), null: none set -- the same in every job of a launch, so the test is uniform
+struct mosaic_job { const double* pose; const double* gr; const uint8_t* img; const uint8_t* mask; const uint16_t* gain; int N, M, blk0, pad; };
 // the grid (x0, y0, cell, W, H: where a point falls and whether it is kept) and the window of it the accumulators cover
 // (ox, oy, bw, bh: the whole grid for the mosaic, one frame's cell bounding box for the consistency map and the registration)
 struct mosaic_win { double x0, y0, cell; int W, H, ox, oy, bw, bh, use_mask; };
@@ -31,6 +32,7 @@ __device__ __forceinline__ void mosaic_scatter_samples(const double* P, const do
     const int M = J.M, half = M / 2;
     const uint8_t* __restrict__ img = J.img + (size_t)row * M;
     const uint8_t* __restrict__ mask = J.mask + (size_t)row * M;
+    const uint16_t* __restrict__ gain = J.gain;                                    // (uniform per workgroup)
     const int lane = threadIdx.x & 63;
     for (int c0 = 0; c0 < M; c0 += 256) {
         const int col = c0 + (int)threadIdx.x;
@@ -42,7 +44,11 @@ __device__ __forceinline__ void mosaic_scatter_samples(const double* P, const do
             const double fx = floor((x - G.x0) / G.cell), fy = floor((y - G.y0) / G.cell);
             if (fx >= 0.0 && fx < (double)G.W && fy >= 0.0 && fy < (double)G.H) {  // on the f64 values: NaN, infinite and huge points drop out here
                 const int ix = (int)fx - G.ox, iy = (int)fy - G.oy;
-                if (ix >= 0 && ix < G.bw && iy >= 0 && iy < G.bh) { key = iy * G.bw + ix; v = (1u << 16) | img[col]; }
+                if (ix >= 0 && ix < G.bw && iy >= 0 && iy < G.bh) {
+                    unsigned g = img[col];
+                    if (gain) g = min(255u, (g * gain[col] + 128u) >> 8);           // the corrected sample ("range-gain normalisation" in the header)
+                    key = iy * G.bw + ix; v = (1u << 16) | g;
+                }
             }
         }
         const int prev = __shfl_up(key, 1);
@@ -132,6 +138,13 @@ void frame_extent(const dsss_frame& f, const double* rows, double* bb);
 void frame_extent_rows(const dsss_frame& f, const double* rows, int r0, int r1, double* bb);      // pings [r0, r1) only
 bool cell_range(double lo, double hi, double origin, double cell, int n, int* a, int* b);
 int upload_rows(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, double* d_rows, std::vector<const double*>& dev_rows);
+// the rule of the range-gain table, part of the argument checks of every entry that bins samples (behind mosaic_check_frames, before
+// anything is reserved, cleared or launched): a table is set and a listed frame has another M -> DSSS_E_ARG
+int mosaic_check_gain(dsss_ctx* c, const int* ids, int n);
+// The mosaic_job table of the listed frames as the host keeps it (blk0 = 0), the ONE place a job of the scatter kernels is filled: mosaic_check_gain once
+// more (a job never carries a table of another M, whatever the caller checked), then the trajectory rows go up (upload_rows into
+// d_rows) and every job gets its rows, geometry, images and the context's table.
+int mosaic_fill_jobs(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, double* d_rows, std::vector<mosaic_job>& jobs);
 void launch_scatter(dsss_ctx* c, const mosaic_job* d_jobs, int njobs, int blocks, const mosaic_win& G, unsigned long long* acc);
 // the segmented form for ONE frame (d_job: its record, blk0 = 0; blocks = its pings): ping p goes into d_segs[p / seg_pings]
 void launch_scatter_seg(dsss_ctx* c, const mosaic_job* d_job, int blocks, const mosaic_win& G, unsigned long long* acc, const mosaic_seg* d_segs, int seg_pings);

@@ -451,6 +451,7 @@ struct reg_rows {
         if (dsss_comm_world(c) > 1) DSSS_FAIL(c, DSSS_E_STATE, "mosaic: registration runs on a single rank (communicator of %d)", dsss_comm_world(c));
         int rc = mosaic_check_frames(c, ids, n, rpy6, ping_off, true, &traj_rows); if (rc) return rc;
         rc = mosaic_check_params(c, p); if (rc) return rc;
+        rc = mosaic_check_gain(c, ids, n); if (rc) return rc;
         dsss_reg_params_default(&R);
         if (rp) R = *rp;
         if (R.radius < 0 || R.radius > REG_MAX_RADIUS) DSSS_FAIL(c, DSSS_E_ARG, "register: radius %d outside 0..%d", R.radius, REG_MAX_RADIUS);
@@ -587,10 +588,7 @@ struct reg_mem {
 int reg_upload_jobs(const reg_rows& Q, const reg_mem& M, std::vector<mosaic_job>& jobs)
 {
     dsss_ctx* c = Q.c;
-    std::vector<const double*> dev_rows;
-    const int rc = upload_rows(c, Q.ids, Q.n, Q.rpy6, Q.ping_off, M.rows, dev_rows); if (rc) return rc;
-    jobs.resize(Q.n);
-    for (int i = 0; i < Q.n; ++i) { const dsss_frame& f = Q.frame(i); jobs[i] = mosaic_job{ dev_rows[i], f.gr, f.lvl[0], f.mask, f.N, f.M, 0, 0 }; }
+    const int rc = mosaic_fill_jobs(c, Q.ids, Q.n, Q.rpy6, Q.ping_off, M.rows, jobs); if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(M.jobs, jobs.data(), (size_t)Q.n * sizeof(mosaic_job), hipMemcpyHostToDevice, c->stream));
     return DSSS_OK;
 }

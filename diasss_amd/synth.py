@@ -55,6 +55,15 @@ def quantise(img, dtype):
     raise TypeError("waterfall dtype %s: uint8, uint16, float32 or float64 expected" % name)
 
 
+def column_profile(M, amp):
+    """A sensor-fixed profile across the swath, as the beam pattern and a residual time-varied gain leave it: a factor per column,
+    1 + amp cos(3 r) on starboard and 1 + 0.8 amp cos(3 r) on port, r = |c - M/2| / (M/2).  The survey's own ripple is +-5 %; the
+    range-gain tools multiply the raw frames by this to have something to normalise (float64 numpy, M)."""
+    c = np.arange(M, dtype=np.float64)
+    r = np.abs(c - M / 2) / (M / 2)
+    return 1.0 + amp * np.cos(3.0 * r) * np.where(c >= M / 2, 1.0, 0.8)
+
+
 class Survey:
     """F legs of N pings x M bins."""
 

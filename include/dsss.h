@@ -356,6 +356,37 @@ int dsss_mosaic_consistency(dsss_ctx*, const int* ids, int n, const double* rpy6
                             const dsss_mosaic_params*, uint32_t* nfr_host, uint32_t* s1_host, uint32_t* s2_host,
                             double* score_host);
 
+/* ---- range-gain normalisation: a per-column gain table that takes the sensor-fixed profile across the swath (beam pattern, residual
+ * time-varied gain; port and starboard differ) out of every sample before it is binned.  Estimated on the device, held by the context,
+ * applied inside the scatter of every entry that bins samples.  All arithmetic is integer: results stay independent of frame, pair, tile
+ * and atomic order and identical from call to call.  Nothing changes while no table is set.
+ * Column statistics, over the listed frames, which all have the same M: S[c] = sum of norm[row, c], C[c] = the number of samples, over
+ *   the kept samples of column c; a sample is kept iff use_mask == 0 or flt_mask[row, c] != 0.  Both uint64 and exact for any number of
+ *   pings the mosaic accepts (total < 2^31).
+ * Table (pure host arithmetic, no context, as dsss_mosaic_register_peak): parameters min_count (>= 1, default 256), smooth (0..16,
+ *   default 0), target (0..255, default 0).  S'[c], C'[c] = the sums of S, C over the columns c' with |c' - c| <= smooth, 0 <= c' < M, on
+ *   the same side as c (c' < M/2 iff c < M/2: the window never crosses the nadir).  Column c is eligible iff C'[c] >= min_count and
+ *   S'[c] > 0.  T = target where target != 0, else (sum S + (sum C) / 2) / sum C over the UNsmoothed S, C of the eligible columns, floor
+ *   division; with no eligible column (or, under smooth > 0 and target == 0, none that holds a sample of its own: sum C = 0) every gain
+ *   is 256 and T = 0.  gain[c] = min(65535, (T C'[c] 256 + S'[c] / 2) / S'[c]) for an eligible column, 256 otherwise.  Gains are
+ *   uint16, Q8; every intermediate value fits 64 bits for counts up to 2^31 (the function itself computes in 128).
+ * Corrected sample: v' = min(255, (v gain[c] + 128) >> 8).  A gain of 256 returns v exactly, so a table of 256s reproduces the layers
+ *   without a table bit for bit; v' <= 255, so the 2^24-samples-per-cell rule holds unchanged.
+ * Where the table applies: dsss_mosaic_render, _consistency, _register, _register_segments, _register_segments_yaw and
+ *   _register_segments_pyr, and with them the segment rows the _edges entries read.  Extraction, matching and the solves do not see it.
+ * Errors.  DSSS_E_ARG: ids the mosaic entries reject, frames of differing M in one stats call, M < 2, a NULL output, parameters out of
+ *   range, cap < M; and from every entry above, before anything is launched or cleared, when a table is set and a listed frame has
+ *   another M.  DSSS_E_STATE: frames not extracted (the rule of dsss_mosaic_render).  Every error leaves the context usable and a table
+ *   that was set in place.  Estimation and installation are two calls on purpose: a caller may install a calibrated table.             */
+typedef struct { int32_t min_count, smooth, target, pad_; } dsss_gain_params;
+void dsss_gain_params_default(dsss_gain_params*);
+/* S -> sum_host[M], C -> cnt_host[M] of the listed frames (mosaic_colstat_kernel: one launch for all frames) */
+int  dsss_mosaic_gain_stats(dsss_ctx*, const int* ids, int n, int use_mask, uint64_t* sum_host /* M */, uint64_t* cnt_host /* M */);
+int  dsss_mosaic_gain_table(const uint64_t* sum, const uint64_t* cnt, int M, const dsss_gain_params* /* NULL: defaults */,
+                            uint16_t* gain_q8 /* M */, int32_t* target_out /* may be NULL */);
+int  dsss_mosaic_gain_set(dsss_ctx*, const uint16_t* gain_q8_host, int M);      /* NULL: clear (M ignored) */
+int  dsss_mosaic_gain_get(dsss_ctx*, uint16_t* gain_q8_host, int cap, int* M);  /* *M = 0: none set; read back from the device copy */
+
 /* ---- overlap registration: how far, in metres and in which direction, frame b lies from where its overlap with frame a says it belongs.
  * An independent, metric, per-pair measure of a trajectory (the consistency score has no unit of length, the edge report measures the
  * loop closures against the trajectory they produced).  All quantities are integers up to the final score, so results do not depend on

@@ -3,7 +3,7 @@
 solved trajectory (dsss_mosaic_register_segments), the accepted offsets become pose-graph edges (dsss_mosaic_register_edges), the
 trajectory is solved again with them next to the feature-based closures, and the segments are registered once more under the result.
     python tools/dense_closures.py --frames 200 --rows 2000 --cols 1024 --cell 0.1 [--seg-pings 80] [--radius 8] [--calls 5] [--timeout 1500]
-                                   [--yaw-fan NYAW [--yaw-step RAD]] [--pyramid L [--refine RHO]] [--peaks-ab]
+                                   [--yaw-fan NYAW [--yaw-step RAD]] [--pyramid L [--refine RHO]] [--peaks-ab] [--profile AMP] [--gain]
 Steps: 1. pipeline and dsss_posegraph_solve; 2. segments under the solved trajectory; 3. edges; 4. the edges of dsss_posegraph_select
 with the new ones behind them; 5. dsss_posegraph_solve_edges on the frames' dead-reckoning rows; 6. segments under the result.
 Prints one JSON line: segments and accepted edges; median and 95th percentile of |offset| in metres over the segments with a peak, the
@@ -25,6 +25,10 @@ and the fan's or the pyramid's when asked for) it alternates, in this one proces
 and the device path: one warm-up of each, then --calls rounds of host, device, host, each call synchronised and timed with a host clock.
 It reports median and minimum per path, the host path's spread against itself (the two interleaved host series), and per path the
 bytes copied down and the synchronisations (dsss_mosaic_register_info), and asserts the rows of both paths identical as bytes.
+--profile AMP multiplies the raw frames by the sensor profile synth.column_profile(M, AMP) before they are set.  --gain runs steps 2 to 6
+a second time in the same process under the range-gain table of the frames' own statistics (dsss_mosaic_gain_stats, dsss_mosaic_gain_table
+with the default parameters, dsss_mosaic_gain_set) and reports them under "gain": segments with a peak and accepted edges, the median ZNCC
+at the peak and at zero shift, and the consistency score before and after solving again, next to the same figures without the table.
 The GPU work runs in a child process under a time limit (--timeout seconds); this process never opens the device."""
 import argparse
 import json
@@ -42,6 +46,7 @@ ap.add_argument("--yaw-fan", type=int, default=1); ap.add_argument("--yaw-step",
 ap.add_argument("--pyramid", type=int, default=1); ap.add_argument("--refine", type=int, default=3)
 ap.add_argument("--calls", type=int, default=5); ap.add_argument("--timeout", type=float, default=1500.0)
 ap.add_argument("--peaks-ab", action="store_true")
+ap.add_argument("--profile", type=float, default=0.0, metavar="AMP"); ap.add_argument("--gain", action="store_true")
 ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)
 a = ap.parse_args()
 if a.calls < 5:
@@ -63,11 +68,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from diasss_amd import capi                      # noqa: E402
 from diasss_amd.pipeline import Pipeline         # noqa: E402
-from diasss_amd.synth import Survey              # noqa: E402
+from diasss_amd.synth import Survey, column_profile   # noqa: E402
 
 F, N, M = a.frames, a.rows, a.cols
 sv = Survey(F, N, M, seed=20240601 + 2, device="cuda:0")
 raws = [sv.frame(f) for f in range(F)]
+if a.profile:
+    import torch                                 # noqa: E402
+    prof = torch.from_numpy(column_profile(M, a.profile)).to(raws[0].device)
+    raws = [(r * prof[None, :]).contiguous() for r in raws]
 ins = [sv.inputs(f) for f in range(F)]
 pipe = Pipeline(F, device=0)
 pipe.run(raws, [i[0] for i in ins], [i[1] for i in ins], [i[2] for i in ins])
@@ -80,7 +89,7 @@ pairs = [(i, j) for i in range(F) for j in range(i + 1, F)
          if boxes[i][0] <= boxes[j][1] and boxes[j][0] <= boxes[i][1] and boxes[i][2] <= boxes[j][3] and boxes[j][2] <= boxes[i][3]]
 reg = capi.RegParams(a.radius, a.min_cells)
 res = dict(frames=F, rows=N, cols=M, cell=a.cell, grid=[p.W, p.H], radius=a.radius, min_cells=a.min_cells, seg_pings=a.seg_pings, pairs=len(pairs),
-           calls=a.calls, lm_iterations=int(stats[0]))
+           calls=a.calls, lm_iterations=int(stats[0]), profile=a.profile)
 if not pairs:
     print(json.dumps(res)); pipe.close(); sys.exit(0)
 
@@ -134,7 +143,7 @@ def _describe(segs, traj):
     z0 = r["zncc0"][r["zncc0"] > -2.0]
     return dict(with_peak=int(ok.sum()), on_border=int((r["on_border"][ok] != 0).sum()),
                 offset_median_m=float(np.median(d)) if ok.any() else None, offset_p95_m=float(np.percentile(d, 95)) if ok.any() else None,
-                zncc0_median=float(np.median(z0)) if len(z0) else None, consistency=float(ctx.mosaic_consistency(ids, p, rpy6=traj, ping_off=off)[3]))
+                zncc_peak_median=float(np.median(r["zncc"][ok])) if ok.any() else None, zncc0_median=float(np.median(z0)) if len(z0) else None, consistency=float(ctx.mosaic_consistency(ids, p, rpy6=traj, ping_off=off)[3]))
 
 
 def rows_of(poses12):
@@ -187,23 +196,36 @@ if PYR:
 if FAN:
     res["yaw_fan"], res["yaw_step"] = a.yaw_fan, a.yaw_step
     res["segments_yaw_ms"], res["segments_yaw_ms_min"] = timed(lambda: register(rpy))
-before = register(rpy)                                                                                   # 2
-if FAN:                                                                                                  # 3
-    new, src = ctx.mosaic_register_edges_yaw(ids, p, pairs, before, edge_params=capi.RegEdgeYawParams(capi.reg_edge_params_default(), yaw, 1.0),
-                                             rpy6=rpy, ping_off=off)
-else:
-    new, src = ctx.mosaic_register_edges(ids, p, pairs, np.ascontiguousarray(before["s"]) if PYR else before, rpy6=rpy, ping_off=off)
-old = ctx.posegraph_select(F)                                                                            # 4
 dr = np.ascontiguousarray(np.concatenate([i[0] for i in ins]))
-t0 = time.perf_counter()
-poses, stats2 = ctx.posegraph_solve_edges(dr, np.concatenate([old, new]))                                # 5
-solve_ms = 1e3 * (time.perf_counter() - t0)
-again = rows_of(poses)
-after = register(again)                                                                                 # 6
 true = np.ascontiguousarray(np.concatenate(sv.poses_true))
-res.update(segments=len(before), feature_edges=len(old), accepted_edges=len(new), lm_iterations_again=int(stats2[0]), solve_again_ms=round(solve_ms, 3),
-           before=describe(before, rpy), after=describe(after, again),
-           consistency_dr=float(ctx.mosaic_consistency(ids, p)[3]), consistency_true=float(ctx.mosaic_consistency(ids, p, rpy6=true, ping_off=off)[3]))
+old = ctx.posegraph_select(F)                                                                            # 4 (the feature-based closures)
+
+
+def closures():
+    """steps 2 to 6 under whatever range-gain table the context holds"""
+    before = register(rpy)                                                                               # 2
+    if FAN:                                                                                              # 3
+        new, src = ctx.mosaic_register_edges_yaw(ids, p, pairs, before, edge_params=capi.RegEdgeYawParams(capi.reg_edge_params_default(), yaw, 1.0),
+                                                 rpy6=rpy, ping_off=off)
+    else:
+        new, src = ctx.mosaic_register_edges(ids, p, pairs, np.ascontiguousarray(before["s"]) if PYR else before, rpy6=rpy, ping_off=off)
+    t0 = time.perf_counter()
+    poses, stats2 = ctx.posegraph_solve_edges(dr, np.concatenate([old, new]))                            # 5
+    solve_ms = 1e3 * (time.perf_counter() - t0)
+    again = rows_of(poses)
+    after = register(again)                                                                             # 6
+    return dict(segments=len(before), feature_edges=len(old), accepted_edges=len(new), lm_iterations_again=int(stats2[0]), solve_again_ms=round(solve_ms, 3),
+                before=describe(before, rpy), after=describe(after, again),
+                consistency_dr=float(ctx.mosaic_consistency(ids, p)[3]), consistency_true=float(ctx.mosaic_consistency(ids, p, rpy6=true, ping_off=off)[3]))
+
+
+res.update(closures())
+if a.gain:
+    S, C = ctx.mosaic_gain_stats(ids)
+    table, T = capi.mosaic_gain_table(S, C)
+    ctx.mosaic_gain_set(table)
+    res["gain"] = dict(closures(), target=T, gain_min=int(table.min()), gain_max=int(table.max()))
+    ctx.mosaic_gain_set(None)
 if PYR:                                          # the same counts under dead reckoning, where the legs lie furthest from where they belong
     res["dr"] = describe(register(dr), dr)
 print(json.dumps(res))
