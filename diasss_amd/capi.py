@@ -60,6 +60,22 @@ class GainParams(C.Structure):
     _fields_ = [("min_count", C.c_int32), ("smooth", C.c_int32), ("target", C.c_int32), ("pad_", C.c_int32)]
 
 
+class CompParams(C.Structure):
+    """dsss_comp_params: the priority a cell's winner is chosen by (COMP_NEAR, COMP_FAR, COMP_MID, COMP_FIRST) and the radius, in cells
+    (0..4, 0: none), within which enclosed holes are filled"""
+    _fields_ = [("mode", C.c_int32), ("fill_radius", C.c_int32)]
+
+
+class CompInfo(C.Structure):
+    """dsss_comp_info: the cells that hold a sample, the cells filled and the cells left empty; they sum to W H"""
+    _fields_ = [("direct", C.c_int64), ("filled", C.c_int64), ("empty", C.c_int64)]
+
+
+COMP_NEAR, COMP_FAR, COMP_MID, COMP_FIRST = 0, 1, 2, 3          # include/dsss.h DSSS_COMP_*
+COMP_MODES = {"near": COMP_NEAR, "far": COMP_FAR, "mid": COMP_MID, "first": COMP_FIRST}
+COMP_LAYERS = (("img", np.uint8), ("src_frame", np.int32), ("src_ping", np.int32), ("src_col", np.int32), ("fill", np.uint8))   # in the order of the C arguments
+
+
 class RegParams(C.Structure):
     """dsss_reg_params: search radius in cells (0..16) and the fewest overlapping cells a shift needs to be usable"""
     _fields_ = [("radius", C.c_int32), ("min_cells", C.c_int32)]
@@ -277,6 +293,15 @@ def lib():
         L.dsss_mosaic_gain_get.restype = C.c_int
         L.dsss_mosaic_gain_get.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
         L.dsss_reg_params_default.restype = None
+        L.dsss_comp_params_default.restype = None
+        L.dsss_comp_params_default.argtypes = [C.POINTER(CompParams)]
+        L.dsss_mosaic_comp_rank.restype = C.c_int
+        L.dsss_mosaic_comp_rank.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]
+        L.dsss_mosaic_fill_host.restype = C.c_int
+        L.dsss_mosaic_fill_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.dsss_mosaic_composite.restype = C.c_int
+        L.dsss_mosaic_composite.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(MosaicParams), C.POINTER(CompParams)] + [C.c_void_p] * 5 + [
+            C.POINTER(CompInfo)]
         L.dsss_reg_params_default.argtypes = [C.POINTER(RegParams)]
         L.dsss_mosaic_register.restype = C.c_int
         L.dsss_mosaic_register.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(MosaicParams), C.c_void_p, C.c_void_p,
@@ -390,6 +415,35 @@ def mosaic_gain_table(sum, cnt, params=None):
         e.code = rc
         raise e
     return gain, int(T.value)
+
+
+def comp_params_default():
+    p = CompParams(); lib().dsss_comp_params_default(C.byref(p)); return p
+
+
+def mosaic_comp_rank(mode, M, col):
+    """dsss_mosaic_comp_rank: the priority rank q (smaller wins) of column col of a frame of M columns under `mode` (a COMP_* value or
+    its name).  Host arithmetic, no context."""
+    L = lib()
+    q = C.c_int32(-1)
+    rc = L.dsss_mosaic_comp_rank(int(COMP_MODES.get(mode, mode)), int(M), int(col), C.byref(q))
+    if rc != 0:
+        raise _host_error(L, "dsss_mosaic_comp_rank", rc)
+    return int(q.value)
+
+
+def mosaic_fill_host(valid, R):
+    """dsss_mosaic_fill_host: the gap-fill rule on a layer of validity flags (H x W, != 0: the cell holds a sample) -> (donor, fill):
+    donor (int32, H x W) = the cell index iy W + ix each cell takes its value from (its own where it holds a sample, -1 where it stays
+    empty), fill (uint8) = 0, the donor's dx^2 + dy^2, or 255.  Host arithmetic, no context."""
+    L = lib()
+    valid = np.ascontiguousarray(valid, np.uint8); assert valid.ndim == 2
+    H, W = valid.shape
+    donor = np.empty((H, W), np.int32); fill = np.empty((H, W), np.uint8)
+    rc = L.dsss_mosaic_fill_host(_ptr(valid), int(W), int(H), int(R), _ptr(donor), _ptr(fill))
+    if rc != 0:
+        raise _host_error(L, "dsss_mosaic_fill_host", rc)
+    return donor, fill
 
 
 def _reg_pairs(pairs):
@@ -959,6 +1013,23 @@ class Context:
         self._chk(self.L.dsss_mosaic_consistency(self.h, _ptr(ids), len(ids), _ptr(rpy6), _ptr(ping_off), C.byref(params),
                                                  _ptr(nfr), _ptr(s1), _ptr(s2), C.byref(score)), "dsss_mosaic_consistency")
         return nfr, s1, s2, score.value
+
+    def mosaic_composite(self, ids, params, mode=COMP_NEAR, fill_radius=0, rpy6=None, ping_off=None, want=("img", "src_frame", "src_ping", "src_col", "fill")):
+        """dsss_mosaic_composite: one winning sample per cell under the priority `mode` (a COMP_* value or its name), enclosed holes
+        filled within fill_radius cells -> (layers, info): layers = a dict of the H x W layers named in `want` (img uint8; src_frame,
+        src_ping, src_col int32, -1 where empty; fill uint8), info = a CompInfo or None.  want=() builds the mosaic on the device and
+        downloads nothing (timing); add "info" to get the cell counts alone."""
+        ids, rpy6, ping_off = self._mosaic_traj(ids, rpy6, ping_off)
+        known = [n for n, _ in COMP_LAYERS] + ["info"]
+        for w in want:
+            if w not in known:
+                raise ValueError("mosaic_composite: no layer %r (%s)" % (w, ", ".join(known)))
+        out = {n: np.empty((params.H, params.W), t) for n, t in COMP_LAYERS if n in want}
+        info = CompInfo() if (out or "info" in want) else None
+        cp = CompParams(int(COMP_MODES.get(mode, mode)), int(fill_radius))
+        self._chk(self.L.dsss_mosaic_composite(self.h, _ptr(ids), len(ids), _ptr(rpy6), _ptr(ping_off), C.byref(params), C.byref(cp),
+                                               *[_ptr(out.get(n)) for n, _ in COMP_LAYERS], C.byref(info) if info is not None else None), "dsss_mosaic_composite")
+        return out, info
 
     def mosaic_gain_stats(self, ids, use_mask=1):
         """dsss_mosaic_gain_stats: the column statistics of the listed frames (all of one M) -> (S, C), M uint64 each: the sum and the

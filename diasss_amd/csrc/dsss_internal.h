@@ -336,11 +336,17 @@ __host__ __device__ inline void dsss_geo_side(const double* P, bool starboard, d
 {
     dsss_sincos(starboard ? P[2] + DSSS_PI_REF / 2 : P[2] - DSSS_PI_REF / 2, s, c);
 }
-__host__ __device__ inline void dsss_geo_bin(const double* P, const double* gr, int M, int col, double s, double c, double* x, double* y)
+// the ground-range index of a column: the bins of a side counted from the nadir (the port columns 0 and 1 share the last one)
+__host__ __device__ inline int dsss_geo_index(int M, int col)
 {
     int half = M / 2, idx;
     if (col >= half) idx = col - half;
     else { idx = half - col; if (idx > half - 1) idx = half - 1; }
+    return idx;
+}
+__host__ __device__ inline void dsss_geo_bin(const double* P, const double* gr, int M, int col, double s, double c, double* x, double* y)
+{
+    const int idx = dsss_geo_index(M, col);
     *x = (P[3] - 0.0) + gr[idx] * c;
     *y = (P[4] - 0.0) + gr[idx] * s;
 }

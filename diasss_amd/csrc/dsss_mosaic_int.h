@@ -1,5 +1,5 @@
-// diasss_amd/csrc/dsss_mosaic_int.h -- what dsss_mosaic.hip (mosaic, consistency map) and dsss_mosaic_reg.hip (overlap registration)
-// share: the job and window records of mosaic_scatter_kernel, the argument checks, a frame's window of the grid, the upload of a
+// diasss_amd/csrc/dsss_mosaic_int.h -- what dsss_mosaic.hip (mosaic, consistency map), dsss_mosaic_reg.hip (overlap registration) and
+// dsss_mosaic_comp.hip (composite mosaic) share: the job and window records of mosaic_scatter_kernel, the argument checks, a frame's window of the grid, the upload of a
 // caller's trajectory and the scatter launch.  The definitions are in dsss_mosaic.hip.  Below them: the score, order and sub-cell
 // rules of the registration, one body for host and device, and what dsss_mosaic_reg.hip needs of the registration's host arithmetic
 // (dsss_mosaic_edge.cpp).
@@ -15,7 +15,8 @@
 
 // one frame of a launch: its pose rows (the frame's own or the caller's trajectory), geometry and images; blk0 = its first workgroup;
 // gain = the context's range-gain table (M x u16, Q8), null: none set -- the same in every job of a launch, so the test is uniform
-struct mosaic_job { const double* pose; const double* gr; const uint8_t* img; const uint8_t* mask; const uint16_t* gain; int N, M, blk0, pad; };
+// g0 = the canonical number of the frame's first ping (composite mosaic; the other kernels do not read it)
+struct mosaic_job { const double* pose; const double* gr; const uint8_t* img; const uint8_t* mask; const uint16_t* gain; int N, M, blk0, g0; };
 // the grid (x0, y0, cell, W, H: where a point falls and whether it is kept) and the window of it the accumulators cover
 // (ox, oy, bw, bh: the whole grid for the mosaic, one frame's cell bounding box for the consistency map and the registration)
 struct mosaic_win { double x0, y0, cell; int W, H, ox, oy, bw, bh, use_mask; };
@@ -23,34 +24,45 @@ struct mosaic_win { double x0, y0, cell; int W, H, ox, oy, bw, bh, use_mask; };
 // accumulators start, in cells, behind the frame's first
 struct mosaic_seg { int ox, oy, bw, bh; unsigned long long off; };
 
-// The samples of one ping, by the 256 threads of its workgroup (mosaic_scatter_kernel's comment in dsss_mosaic.hip): P = the ping's
-// pose row, sc = sin and cos of the bearing of the port and of the starboard side (dsss_geo_side on P, in LDS), row = the ping's row
-// in the frame's images, G = grid and window, acc = the window's accumulators.  The one place a sample is binned on the device.
+// the corrected sample ("range-gain normalisation" in the header); gain == null: none set
+__device__ __forceinline__ unsigned mosaic_gain_apply(unsigned v, const uint16_t* __restrict__ gain, int col)
+{
+    return gain ? min(255u, (v * gain[col] + 128u) >> 8) : v;
+}
+
+// The one place a sample is binned on the device: the cell of the window G that the sample (row, col) falls into, -1 when it is
+// dropped (mask, off the grid or the window, not finite), and *val = its corrected value.  P = the ping's pose row, sc = sin and cos of
+// the bearing of the port and of the starboard side (dsss_geo_side on P, in LDS), img, mask = the ping's row of the frame's images.
+// The mean scatter, the yaw fan and the composite scatter call it; a caller that does not use *val pays nothing for it.
+__device__ __forceinline__ int mosaic_sample_cell(const double* P, const double* sc, const mosaic_job& J, const uint8_t* __restrict__ img,
+                                                  const uint8_t* __restrict__ mask, int col, const mosaic_win& G, unsigned* val)
+{
+    const int M = J.M, half = M / 2;
+    if (col >= M || (G.use_mask && mask[col] == 0)) return -1;
+    const int side = col >= half;
+    double x, y;
+    dsss_geo_bin(P, J.gr, M, col, sc[2 * side], sc[2 * side + 1], &x, &y);
+    const double fx = floor((x - G.x0) / G.cell), fy = floor((y - G.y0) / G.cell);
+    if (!(fx >= 0.0 && fx < (double)G.W && fy >= 0.0 && fy < (double)G.H)) return -1;   // on the f64 values: NaN, infinite and huge points drop out here
+    const int ix = (int)fx - G.ox, iy = (int)fy - G.oy;
+    if (!(ix >= 0 && ix < G.bw && iy >= 0 && iy < G.bh)) return -1;
+    *val = mosaic_gain_apply(img[col], J.gain, col);                               // (J.gain: uniform per workgroup)
+    return iy * G.bw + ix;
+}
+
+// The samples of one ping, by the 256 threads of its workgroup (mosaic_scatter_kernel's comment in dsss_mosaic.hip): row = the ping's
+// row in the frame's images, acc = the window's accumulators.
 __device__ __forceinline__ void mosaic_scatter_samples(const double* P, const double* sc, const mosaic_job& J, int row, const mosaic_win& G,
                                                        unsigned long long* __restrict__ acc)
 {
-    const int M = J.M, half = M / 2;
+    const int M = J.M;
     const uint8_t* __restrict__ img = J.img + (size_t)row * M;
     const uint8_t* __restrict__ mask = J.mask + (size_t)row * M;
-    const uint16_t* __restrict__ gain = J.gain;                                    // (uniform per workgroup)
     const int lane = threadIdx.x & 63;
     for (int c0 = 0; c0 < M; c0 += 256) {
-        const int col = c0 + (int)threadIdx.x;
-        int key = -1; unsigned v = 0;                                              // v: count << 16 | sum within the wavefront
-        if (col < M && (!G.use_mask || mask[col] != 0)) {
-            const int side = col >= half;
-            double x, y;
-            dsss_geo_bin(P, J.gr, M, col, sc[2 * side], sc[2 * side + 1], &x, &y);
-            const double fx = floor((x - G.x0) / G.cell), fy = floor((y - G.y0) / G.cell);
-            if (fx >= 0.0 && fx < (double)G.W && fy >= 0.0 && fy < (double)G.H) {  // on the f64 values: NaN, infinite and huge points drop out here
-                const int ix = (int)fx - G.ox, iy = (int)fy - G.oy;
-                if (ix >= 0 && ix < G.bw && iy >= 0 && iy < G.bh) {
-                    unsigned g = img[col];
-                    if (gain) g = min(255u, (g * gain[col] + 128u) >> 8);           // the corrected sample ("range-gain normalisation" in the header)
-                    key = iy * G.bw + ix; v = (1u << 16) | g;
-                }
-            }
-        }
+        unsigned g = 0;
+        const int key = mosaic_sample_cell(P, sc, J, img, mask, c0 + (int)threadIdx.x, G, &g);
+        unsigned v = key >= 0 ? (1u << 16) | g : 0u;                               // v: count << 16 | sum within the wavefront
         const int prev = __shfl_up(key, 1);
         const bool head = lane == 0 || prev != key;
         const unsigned long long hb = __ballot(head);
@@ -60,6 +72,40 @@ __device__ __forceinline__ void mosaic_scatter_samples(const double* P, const do
         const bool tail = lane == 63 || ((hb >> (lane + 1)) & 1ull);
         if (tail && key >= 0) atomicAdd(&acc[key], ((unsigned long long)(v >> 16) << 32) | (v & 0xffffu));
     }
+}
+
+// ---- composite mosaic ("composite mosaic" in the header; dsss_mosaic_comp.hip).  A cell's key: q << 47 | g << 16 | col, 15 + 31 + 16
+// bits, so the top two bits of a sample's key are 0 and all ones, the value the cells are cleared to, is no sample's key.
+#define COMP_EMPTY (~0ull)
+#define COMP_MAX_M 65534                   // q <= half - 1 <= 32766 and col < 2^16
+#define COMP_MAX_FILL 4                    // the fill radius, in cells
+// the priority rank of a column, ONE body for dsss_mosaic_comp_rank and mosaic_composite_kernel (mode 0..3, M even)
+__host__ __device__ inline int comp_rank(int mode, int M, int col)
+{
+    const int half = M / 2, idx = dsss_geo_index(M, col);
+    if (mode == DSSS_COMP_NEAR) return idx;
+    if (mode == DSSS_COMP_FAR) return half - 1 - idx;
+    if (mode == DSSS_COMP_MID) { const int d = 2 * idx - (half - 1); return d < 0 ? -d : d; }
+    return 0;
+}
+// The fill rule of one empty cell, ONE body for dsss_mosaic_fill_host and mosaic_fill_kernel: valid(x, y) = 1 where the cell is in V0,
+// 0 elsewhere and outside the grid.  Returns dx^2 + dy^2 of the donor and its offset, or 0 when the cell is not enclosed.  A candidate
+// is packed as d2 << 16 | dy + 4 << 8 | dx + 4, so the smallest integer is the first under (d2, dy, dx) whatever the order of the
+// visit; a cell outside V0 gets the bits 0x7f000000 on top and never wins.  Integer arithmetic alone: no branch, no lane mask per cell.
+template <class V>
+__host__ __device__ inline int comp_fill_rule(const V& valid, int ix, int iy, int R, int* ddx, int* ddy)
+{
+    int l = 0, r = 0, u = 0, d = 0;
+    for (int a = 1; a <= R; ++a) { l |= valid(ix - a, iy); r |= valid(ix + a, iy); u |= valid(ix, iy - a); d |= valid(ix, iy + a); }
+    if (!((l & r) | (u & d))) return 0;
+    int best = 0x7fffffff;
+    for (int dy = -R; dy <= R; ++dy)
+        for (int dx = -R; dx <= R; ++dx) {
+            const int cand = ((dx * dx + dy * dy) << 16) | ((dy + COMP_MAX_FILL) << 8) | (dx + COMP_MAX_FILL) | ((valid(ix + dx, iy + dy) - 1) & 0x7f000000);
+            best = cand < best ? cand : best;
+        }
+    *ddx = (best & 0xff) - COMP_MAX_FILL; *ddy = ((best >> 8) & 0xff) - COMP_MAX_FILL;
+    return best >> 16;
 }
 
 // ---- the score, order and sub-cell rules of the registration ("overlap registration" in the header): ONE body for the host

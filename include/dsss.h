@@ -387,6 +387,51 @@ int  dsss_mosaic_gain_table(const uint64_t* sum, const uint64_t* cnt, int M, con
 int  dsss_mosaic_gain_set(dsss_ctx*, const uint16_t* gain_q8_host, int M);      /* NULL: clear (M ignored) */
 int  dsss_mosaic_gain_get(dsss_ctx*, uint16_t* gain_q8_host, int cap, int* M);  /* *M = 0: none set; read back from the device copy */
 
+/* ---- composite mosaic: the deliverable picture.  dsss_mosaic_render's img is the mean of every sample of a cell: right for the
+ * consistency score and the ZNCC, but a blend of frames that see a patch from opposite sides.  Here a cell holds ONE sample, the winner
+ * under a stated priority, with its source (frame, ping, column); enclosed holes are optionally filled from the nearest cell that holds a
+ * sample.  Integer work only: independent of the order of ids, of atomic order and of the call.  No existing entry changes.
+ * Samples: exactly those of dsss_mosaic_render (frames, rpy6 / ping_off, grid, use_mask, the f64 cell arithmetic and range test).  A
+ *   sample's value is the normalised u8, corrected by the context's gain table when one is set (v' = min(255, (v gain[c] + 128) >> 8)).
+ * Ground-range index of a column, as in the geometry of a bin: half = M / 2; col >= half: idx = col - half; otherwise
+ *   idx = min(half - col, half - 1) (the port columns 0 and 1 share an index).
+ * Priority rank q, smaller wins, an integer in [0, 32766]: DSSS_COMP_NEAR: idx (nearest to the track); DSSS_COMP_FAR: half - 1 - idx;
+ *   DSSS_COMP_MID: |2 idx - (half - 1)| (mid-swath); DSSS_COMP_FIRST: 0 (the first line on top).
+ * Canonical ping number g: the listed frames ordered by ascending frame id, NOT by their position in ids; g = the sum of N over the
+ *   listed frames of a smaller id, plus the ping's row.  The mosaic refuses 2^31 pings or more in a call, so g < 2^31.
+ * Winner of a cell: the sample with the smallest (q, g, col), compared lexicographically.  The triple is unique per sample, so the winner
+ *   is unique and depends neither on the order of ids nor on the order of execution.  A cell with no sample is empty.
+ * Frames: every listed frame has an even M, 4 <= M <= 65534 (q and col have 15 and 16 bits of the device's key).
+ * Outputs, H x W row-major, any may be NULL: img (u8) the winner's value, 0 where empty; src_frame (int32) its frame id, src_ping (int32)
+ *   its row in that frame, src_col (int32) its column, each -1 where empty; fill (u8) below; info: the cells that hold a sample, the
+ *   cells filled, the cells left empty (direct + filled + empty = W H).
+ * Gap fill, fill_radius R in 0..4 (0: none).  V0 = the cells that hold a sample; cells outside the grid are not in V0.  An empty cell
+ *   (ix, iy) is enclosed iff there are a, b in [1, R] with (ix - a, iy) and (ix + b, iy) both in V0, or the same along y.  An enclosed
+ *   cell takes the value and the source of its donor: the cell of V0 in the square |dx|, |dy| <= R that minimises (dx^2 + dy^2, dy, dx),
+ *   the registration's tie order; one always exists.  fill = 0 for a cell of V0, dx^2 + dy^2 of the donor (1..32; in fact at most R^2,
+ *   since an enclosed cell has a cell of V0 on one of its axes within R) for a filled cell, 255
+ *   for a cell left empty.  Donors come from V0 only, never from filled cells: the result does not depend on the order the holes are
+ *   visited in, and nothing is extrapolated beyond the covered area.
+ * Errors.  DSSS_E_ARG, before anything is reserved, cleared or launched: everything dsss_mosaic_render refuses (a gain table of another
+ *   M included), a frame whose M is odd or outside [4, 65534], a mode outside 0..3, fill_radius outside 0..4; for the host functions a NULL
+ *   pointer, M < 4 or odd or above 65534, col outside [0, M), W or H < 1, W H > 2^28, R outside 0..4.  DSSS_E_STATE: as dsss_mosaic_render.
+ *   There is no sample limit per cell: nothing is summed, DSSS_E_CAPACITY does not occur.  Every error leaves the context usable and a
+ *   gain table that was set in place.  With all outputs NULL the mosaic is built on the device and nothing is downloaded.            */
+#define DSSS_COMP_NEAR  0
+#define DSSS_COMP_FAR   1
+#define DSSS_COMP_MID   2
+#define DSSS_COMP_FIRST 3
+typedef struct { int32_t mode, fill_radius; } dsss_comp_params;      /* defaults DSSS_COMP_NEAR, 0 */
+typedef struct { int64_t direct, filled, empty; } dsss_comp_info;
+void dsss_comp_params_default(dsss_comp_params*);
+/* pure host arithmetic, no context: the rank of a column; the fill rule on a layer of validity flags */
+int  dsss_mosaic_comp_rank(int mode, int M, int col, int32_t* q);
+int  dsss_mosaic_fill_host(const uint8_t* valid /* H x W, != 0: in V0 */, int W, int H, int R,
+                           int32_t* donor /* cell index iy W + ix of the donor; own index in V0; -1 left empty */, uint8_t* fill);
+int  dsss_mosaic_composite(dsss_ctx*, const int* ids, int n, const double* rpy6, const int* ping_off, const dsss_mosaic_params*,
+                           const dsss_comp_params* /* NULL: defaults */, uint8_t* img_host, int32_t* src_frame_host,
+                           int32_t* src_ping_host, int32_t* src_col_host, uint8_t* fill_host, dsss_comp_info* info_host);
+
 /* ---- overlap registration: how far, in metres and in which direction, frame b lies from where its overlap with frame a says it belongs.
  * An independent, metric, per-pair measure of a trajectory (the consistency score has no unit of length, the edge report measures the
  * loop closures against the trajectory they produced).  All quantities are integers up to the final score, so results do not depend on

@@ -1,14 +1,17 @@
 #!/usr/bin/env python3
 """Time of the georeferenced mosaic (dsss_mosaic_render) on a synthetic survey whose images are resident on the device, under the
 dead-reckoning poses and under the solved trajectory, and the overlap-consistency score under dead-reckoning, optimised and true poses.
-    python tools/mosaic_time.py --frames 200 --rows 2000 --cols 1024 --cell 0.1 [--calls 7] [--profile AMP] [--gain]
+    python tools/mosaic_time.py --frames 200 --rows 2000 --cols 1024 --cell 0.1 [--calls 7] [--profile AMP] [--gain] [--composite MODE [--fill R]]
 Prints one JSON line.  Times are wall clock around the call, which ends with a synchronisation of the context's stream and downloads
 nothing (download=False): median of --calls calls after one warm-up.  dropped_fraction counts the pixels the filter mask rejects and the
 ones that fall outside the grid.
 --profile AMP multiplies the raw frames by the sensor profile synth.column_profile(M, AMP) before they are set.  --gain adds the
 range-gain normalisation: the time of dsss_mosaic_gain_stats (median and fastest of --calls, the bytes per second two bytes a sample
 imply, and that as a fraction of the 6.3 TB/s copy ceiling), the render with and without the table of those statistics (default
-parameters) in one process, interleaved call by call, and the consistency score under the three trajectories with and without it."""
+parameters) in one process, interleaved call by call, and the consistency score under the three trajectories with and without it.
+--composite MODE (near, far, mid, first) adds the composite mosaic: dsss_mosaic_composite with nothing downloaded against
+dsss_mosaic_render in one process, interleaved call by call (median, fastest and slowest of --calls after a warm-up round), and the
+three cell counts; --fill R fills enclosed holes within R cells.  With --gain both run under the table."""
 import argparse
 import json
 import os
@@ -29,6 +32,7 @@ ap.add_argument("--frames", type=int, default=200); ap.add_argument("--rows", ty
 ap.add_argument("--cols", type=int, default=1024); ap.add_argument("--cell", type=float, default=0.1)
 ap.add_argument("--calls", type=int, default=7)
 ap.add_argument("--profile", type=float, default=0.0, metavar="AMP"); ap.add_argument("--gain", action="store_true")
+ap.add_argument("--composite", choices=sorted(capi.COMP_MODES), default=None, metavar="MODE"); ap.add_argument("--fill", type=int, default=0, metavar="R")
 a = ap.parse_args()
 F, N, M = a.frames, a.rows, a.cols
 if a.calls < 5:
@@ -103,6 +107,23 @@ if a.gain:
     ctx.mosaic_gain_set(table)
     for name, traj in trajs:
         res["score_" + name + "_gain"] = ctx.mosaic_consistency(ids, p, **traj)[3]
+    ctx.mosaic_gain_set(None)
+
+if a.composite:
+    if a.gain:
+        ctx.mosaic_gain_set(table)
+    t_mean, t_comp = [], []
+    for k in range(a.calls + 1):
+        t0 = time.perf_counter(); ctx.mosaic_render(ids, p, download=False); dt_mean = time.perf_counter() - t0
+        t0 = time.perf_counter(); ctx.mosaic_composite(ids, p, mode=a.composite, fill_radius=a.fill, want=()); dt_comp = time.perf_counter() - t0
+        if k:                                                     # (the first round warms up)
+            t_mean.append(dt_mean); t_comp.append(dt_comp)
+    _, info = ctx.mosaic_composite(ids, p, mode=a.composite, fill_radius=a.fill, want=("info",))
+    res.update(composite_mode=a.composite, composite_fill=a.fill, composite_under_table=bool(a.gain),
+               composite_ms=round(1e3 * float(np.median(t_comp)), 3), composite_ms_min=round(1e3 * min(t_comp), 3), composite_ms_max=round(1e3 * max(t_comp), 3),
+               render_ms_beside=round(1e3 * float(np.median(t_mean)), 3), render_ms_beside_min=round(1e3 * min(t_mean), 3),
+               render_ms_beside_max=round(1e3 * max(t_mean), 3),
+               cells_direct=int(info.direct), cells_filled=int(info.filled), cells_empty=int(info.empty))
     ctx.mosaic_gain_set(None)
 print(json.dumps(res))
 pipe.close()
