@@ -10,7 +10,7 @@ namespace {
 // One workgroup per ping, one wavefront per 64 consecutive bins.  The bearing of each side is evaluated once per ping (dsss_geo_side)
 // and shared through LDS; the bins then cost a multiply-add and two divisions each.  Consecutive bins of a ping walk through the
 // grid, so lanes that hit the cell of their neighbour form runs: (sum, count) is reduced within a run with a segmented scan over
-// the wavefront and the last lane of the run issues ONE 64-bit atomic without return, count in the high word and sum in the low
+// the wavefront (mosaic_run_reduce) and the last lane of the run issues ONE 64-bit atomic without return, count in the high word and sum in the low
 // one.  A wavefront adds at most 64 x 255 to a sum, and below 2^24 samples per cell (checked by mosaic_unpack_kernel) the low word
 // cannot carry into the high one.  (One atomic per pixel took 13.3 ms where this takes 6.7: DESIGN.md section 4, "Mosaic".)
 //
@@ -23,19 +23,13 @@ __device__ __forceinline__ void mosaic_scatter_body(const mosaic_job* __restrict
                                                     const mosaic_seg* __restrict__ segs, int seg_pings)
 {
     __shared__ double s_sc[4];
-    int lo = 0, hi = njobs - 1;
-    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (jobs[mid].blk0 <= (int)blockIdx.x) lo = mid; else hi = mid - 1; }
-    const mosaic_job J = jobs[lo];
-    const int row = (int)blockIdx.x - J.blk0;
-    if (row >= J.N) return;                                                        // (uniform per workgroup; cannot happen with the host's blk0)
+    mosaic_job J; int row; const double* P;
+    if (!mosaic_ping_of(jobs, njobs, s_sc, J, row, P)) return;
     if (SEG) {
         const mosaic_seg sg = segs[row / seg_pings];
         if (sg.bw <= 0) return;                                                    // a segment with no cell on the grid (uniform per workgroup)
         G.ox = sg.ox; G.oy = sg.oy; G.bw = sg.bw; G.bh = sg.bh; acc += sg.off;
     }
-    const double* P = J.pose + (size_t)row * 6;
-    if (threadIdx.x < 2) dsss_geo_side(P, threadIdx.x == 1, &s_sc[2 * threadIdx.x], &s_sc[2 * threadIdx.x + 1]);
-    __syncthreads();
     mosaic_scatter_samples(P, s_sc, J, row, G, acc);
 }
 
@@ -138,9 +132,7 @@ template <bool MASK> __device__ __forceinline__ void colstat_words(const uint32_
 __global__ __launch_bounds__(256) void mosaic_colstat_kernel(const mosaic_job* __restrict__ jobs, int njobs, int use_mask, unsigned long long* __restrict__ out)
 {
     __shared__ uint32_t s_part[2 * COLSTAT_COLS][256];
-    int lo = 0, hi = njobs - 1;
-    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (jobs[mid].blk0 <= (int)blockIdx.x) lo = mid; else hi = mid - 1; }
-    const mosaic_job J = jobs[lo];
+    const mosaic_job J = mosaic_job_of(jobs, njobs);
     const int M = J.M, tpr = colstat_tpr(M), rl = 256 / tpr, chunks = colstat_chunks(M), rows_wg = rl * COLSTAT_ROWS;
     const int wg = (int)blockIdx.x - J.blk0;
     const int rb = wg / chunks, ch = wg - rb * chunks;
@@ -217,6 +209,13 @@ int mosaic_check_params(dsss_ctx* c, const dsss_mosaic_params* p)
     return DSSS_OK;
 }
 
+int mosaic_check_args(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, const dsss_mosaic_params* p, size_t* rows)
+{
+    int rc = mosaic_check_frames(c, ids, n, rpy6, ping_off, true, rows); if (rc) return rc;
+    rc = mosaic_check_params(c, p); if (rc) return rc;
+    return mosaic_check_gain(c, ids, n);
+}
+
 // geo extremes of one frame under the given pose rows: x = px + g c is monotone in g for a fixed bearing, so only the smallest and the
 // largest ground range of a side can be extreme (what geo_bbox_kernel evaluates).  On the host: two bearings per ping, off the hot
 // path, and the same arithmetic bit for bit.  Non-finite points compare false and are left out.
@@ -259,6 +258,28 @@ bool cell_range(double lo, double hi, double origin, double cell, int n, int* a,
     if (!(fh >= 0.0) || !(fl < (double)n)) return false;
     *a = fl < 0.0 ? 0 : (int)fl; *b = fh >= (double)n ? n - 1 : (int)fh;
     return true;
+}
+
+mosaic_win mosaic_grid_win(const dsss_mosaic_params* p) { return mosaic_win{ p->x0, p->y0, p->cell, p->W, p->H, 0, 0, p->W, p->H, p->use_mask != 0 }; }
+
+bool mosaic_window(const dsss_frame& f, const double* rows, int r0, int r1, const dsss_mosaic_params* p, mosaic_win* w)
+{
+    double bb[4] = { INFINITY, -INFINITY, INFINITY, -INFINITY };
+    frame_extent_rows(f, rows, r0, r1, bb);
+    int ax, bx, ay, by;
+    if (!cell_range(bb[0], bb[1], p->x0, p->cell, p->W, &ax, &bx) || !cell_range(bb[2], bb[3], p->y0, p->cell, p->H, &ay, &by)) return false;
+    *w = mosaic_grid_win(p);
+    w->ox = ax; w->oy = ay; w->bw = bx - ax + 1; w->bh = by - ay + 1;
+    return true;
+}
+
+int mosaic_flag_down(dsss_ctx* c, const int* d_flag, const char* fmt, double cell)
+{
+    int flag = 0;
+    HIPCHK(c, hipMemcpyAsync(&flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (flag) DSSS_FAIL(c, DSSS_E_CAPACITY, fmt, cell);
+    return DSSS_OK;
 }
 
 // the caller's trajectory rows of the listed frames go up packed in the order of ids (neighbouring frames that are neighbours in
@@ -342,28 +363,22 @@ int dsss_mosaic_render(dsss_ctx* c, const int* ids, int n, const double* rpy6, c
 {
     if (!c) return DSSS_E_ARG;
     size_t rows = 0;
-    int rc = mosaic_check_frames(c, ids, n, rpy6, ping_off, true, &rows); if (rc) return rc;
-    rc = mosaic_check_params(c, p); if (rc) return rc;
-    rc = mosaic_check_gain(c, ids, n); if (rc) return rc;
+    int rc = mosaic_check_args(c, ids, n, rpy6, ping_off, p, &rows); if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t cells = (size_t)p->W * p->H;
-    carve L;
-    const size_t o_acc = L.take(cells * 8), o_sum = L.take(sum_host ? cells * 4 : 0), o_cnt = L.take(cnt_host ? cells * 4 : 0),
-                 o_img = L.take(img_host ? cells : 0), o_jobs = L.take((size_t)n * sizeof(mosaic_job)), o_rows = L.take(rpy6 ? rows * 6 * sizeof(double) : 0),
-                 o_flag = L.take(sizeof(int));
-    rc = c->mosaic_buf.reserve(c, L.off); if (rc) return rc;
-    char* B = c->mosaic_buf.as<char>();
-    unsigned long long* acc = reinterpret_cast<unsigned long long*>(B + o_acc);
-    uint32_t* d_sum = sum_host ? reinterpret_cast<uint32_t*>(B + o_sum) : nullptr;
-    uint32_t* d_cnt = cnt_host ? reinterpret_cast<uint32_t*>(B + o_cnt) : nullptr;
-    uint8_t* d_img = img_host ? reinterpret_cast<uint8_t*>(B + o_img) : nullptr;
-    mosaic_job* d_jobs = reinterpret_cast<mosaic_job*>(B + o_jobs);
-    int* d_flag = reinterpret_cast<int*>(B + o_flag);
+    mosaic_arena A;
+    const auto o_acc = A.take<unsigned long long>(cells);
+    const auto o_sum = A.take<uint32_t>(sum_host ? cells : 0), o_cnt = A.take<uint32_t>(cnt_host ? cells : 0);
+    const auto o_img = A.take<uint8_t>(img_host ? cells : 0);
+    const auto o_jobs = A.take<mosaic_job>(n); const auto o_rows = A.take<double>(rpy6 ? rows * 6 : 0); const auto o_flag = A.take<int>(1);
+    rc = A.reserve(c); if (rc) return rc;
+    unsigned long long* acc = A.at(o_acc); mosaic_job* d_jobs = A.at(o_jobs); int* d_flag = A.at(o_flag);
+    uint32_t* d_sum = A.opt(o_sum); uint32_t* d_cnt = A.opt(o_cnt); uint8_t* d_img = A.opt(o_img);
     std::vector<mosaic_job> jobs;
-    rc = mosaic_fill_jobs(c, ids, n, rpy6, ping_off, reinterpret_cast<double*>(B + o_rows), jobs); if (rc) return rc;
+    rc = mosaic_fill_jobs(c, ids, n, rpy6, ping_off, A.at(o_rows), jobs); if (rc) return rc;
     HIPCHK(c, hipMemsetAsync(acc, 0, cells * 8, c->stream));
     HIPCHK(c, hipMemsetAsync(d_flag, 0, sizeof(int), c->stream));
-    const mosaic_win G{ p->x0, p->y0, p->cell, p->W, p->H, 0, 0, p->W, p->H, p->use_mask != 0 };
+    const mosaic_win G = mosaic_grid_win(p);
     const unsigned ublocks = (unsigned)((cells + 255) / 256);
     // launches of at most 2^31 samples, the sample limit checked between them: a cell's count then stays far below 2^32 until the
     // check sees it, so the packed accumulator cannot wrap unnoticed whatever the number of frames
@@ -385,10 +400,7 @@ int dsss_mosaic_render(dsss_ctx* c, const int* ids, int n, const double* rpy6, c
     }
     hipLaunchKernelGGL(mosaic_unpack_kernel, dim3(ublocks), dim3(256), 0, c->stream, acc, cells, d_sum, d_cnt, d_img, d_flag);
     HIPCHK(c, hipGetLastError());
-    int flag = 0;
-    HIPCHK(c, hipMemcpyAsync(&flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (flag) DSSS_FAIL(c, DSSS_E_CAPACITY, "mosaic: a cell received more than 2^24 samples (cell %g too coarse for these frames)", p->cell);
+    rc = mosaic_flag_down(c, d_flag, "mosaic: a cell received more than 2^24 samples (cell %g too coarse for these frames)", p->cell); if (rc) return rc;
     if (sum_host) HIPCHK(c, hipMemcpyAsync(sum_host, d_sum, cells * 4, hipMemcpyDeviceToHost, c->stream));
     if (cnt_host) HIPCHK(c, hipMemcpyAsync(cnt_host, d_cnt, cells * 4, hipMemcpyDeviceToHost, c->stream));
     if (img_host) HIPCHK(c, hipMemcpyAsync(img_host, d_img, cells, hipMemcpyDeviceToHost, c->stream));
@@ -410,12 +422,10 @@ int dsss_mosaic_gain_stats(dsss_ctx* c, const int* ids, int n, int use_mask, uin
     for (int i = 1; i < n; ++i)
         if (c->frames[ids[i]].M != M) DSSS_FAIL(c, DSSS_E_ARG, "gain: frame %d has %d columns, frame %d has %d", ids[0], M, ids[i], c->frames[ids[i]].M);
     HIPCHK(c, hipSetDevice(c->device));
-    carve L;
-    const size_t o_out = L.take((size_t)M * 16), o_jobs = L.take((size_t)n * sizeof(mosaic_job));
-    rc = c->mosaic_buf.reserve(c, L.off); if (rc) return rc;
-    char* B = c->mosaic_buf.as<char>();
-    unsigned long long* d_out = reinterpret_cast<unsigned long long*>(B + o_out);
-    mosaic_job* d_jobs = reinterpret_cast<mosaic_job*>(B + o_jobs);
+    mosaic_arena A;
+    const auto o_out = A.take<unsigned long long>((size_t)M * 2); const auto o_jobs = A.take<mosaic_job>(n);
+    rc = A.reserve(c); if (rc) return rc;
+    unsigned long long* d_out = A.at(o_out); mosaic_job* d_jobs = A.at(o_jobs);
     // the statistics are those of the uncorrected samples whatever table is set: the jobs carry the images alone
     std::vector<mosaic_job> jobs(n);
     const int chunks = colstat_chunks(M), rows_wg = (256 / colstat_tpr(M)) * COLSTAT_ROWS;
@@ -502,9 +512,7 @@ int dsss_mosaic_consistency(dsss_ctx* c, const int* ids, int n, const double* rp
 {
     if (!c) return DSSS_E_ARG;
     size_t rows = 0;
-    int rc = mosaic_check_frames(c, ids, n, rpy6, ping_off, true, &rows); if (rc) return rc;
-    rc = mosaic_check_params(c, p); if (rc) return rc;
-    rc = mosaic_check_gain(c, ids, n); if (rc) return rc;
+    int rc = mosaic_check_args(c, ids, n, rpy6, ping_off, p, &rows); if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t cells = (size_t)p->W * p->H;
     // every frame is rendered alone into a window of the grid: the cells its geo extremes can reach
@@ -512,25 +520,18 @@ int dsss_mosaic_consistency(dsss_ctx* c, const int* ids, int n, const double* rp
     size_t win_cells = 1;
     for (int i = 0; i < n; ++i) {
         const dsss_frame& f = c->frames[ids[i]];
-        double bb[4] = { INFINITY, -INFINITY, INFINITY, -INFINITY };
-        frame_extent(f, rpy6 ? rpy6 + (size_t)ping_off[i] * 6 : f.h_geo, bb);
-        int ax, bx, ay, by;
-        if (!cell_range(bb[0], bb[1], p->x0, p->cell, p->W, &ax, &bx) || !cell_range(bb[2], bb[3], p->y0, p->cell, p->H, &ay, &by)) continue;
+        if (!mosaic_window(f, rpy6 ? rpy6 + (size_t)ping_off[i] * 6 : f.h_geo, 0, f.N, p, &wins[i])) continue;
         on_grid[i] = 1;
-        wins[i] = mosaic_win{ p->x0, p->y0, p->cell, p->W, p->H, ax, ay, bx - ax + 1, by - ay + 1, p->use_mask != 0 };
         win_cells = std::max(win_cells, (size_t)wins[i].bw * wins[i].bh);
     }
-    carve L;
-    const size_t o_lay = L.take(cells * 12), o_win = L.take(win_cells * 8), o_jobs = L.take((size_t)n * sizeof(mosaic_job)),
-                 o_rows = L.take(rpy6 ? rows * 6 * sizeof(double) : 0), o_flag = L.take(sizeof(int));
-    rc = c->mosaic_buf.reserve(c, L.off); if (rc) return rc;
-    char* B = c->mosaic_buf.as<char>();
-    uint32_t* d_nfr = reinterpret_cast<uint32_t*>(B + o_lay); uint32_t* d_s1 = d_nfr + cells; uint32_t* d_s2 = d_s1 + cells;
-    unsigned long long* d_win = reinterpret_cast<unsigned long long*>(B + o_win);
-    mosaic_job* d_jobs = reinterpret_cast<mosaic_job*>(B + o_jobs);
-    int* d_flag = reinterpret_cast<int*>(B + o_flag);
+    mosaic_arena A;
+    const auto o_lay = A.take<uint32_t>(cells * 3); const auto o_win = A.take<unsigned long long>(win_cells);      // lay: nfr, s1, s2 behind one another
+    const auto o_jobs = A.take<mosaic_job>(n); const auto o_rows = A.take<double>(rpy6 ? rows * 6 : 0); const auto o_flag = A.take<int>(1);
+    rc = A.reserve(c); if (rc) return rc;
+    uint32_t* d_nfr = A.at(o_lay); uint32_t* d_s1 = d_nfr + cells; uint32_t* d_s2 = d_s1 + cells;
+    unsigned long long* d_win = A.at(o_win); mosaic_job* d_jobs = A.at(o_jobs); int* d_flag = A.at(o_flag);
     std::vector<mosaic_job> jobs;
-    rc = mosaic_fill_jobs(c, ids, n, rpy6, ping_off, reinterpret_cast<double*>(B + o_rows), jobs); if (rc) return rc;
+    rc = mosaic_fill_jobs(c, ids, n, rpy6, ping_off, A.at(o_rows), jobs); if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(d_jobs, jobs.data(), (size_t)n * sizeof(mosaic_job), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemsetAsync(d_nfr, 0, cells * 12, c->stream));
     HIPCHK(c, hipMemsetAsync(d_flag, 0, sizeof(int), c->stream));
@@ -542,10 +543,7 @@ int dsss_mosaic_consistency(dsss_ctx* c, const int* ids, int n, const double* rp
         hipLaunchKernelGGL(mosaic_fold_kernel, dim3((unsigned)((wc + 255) / 256)), dim3(256), 0, c->stream, d_win, wins[i], d_nfr, d_s1, d_s2, d_flag);
         HIPCHK(c, hipGetLastError());
     }
-    int flag = 0;
-    HIPCHK(c, hipMemcpyAsync(&flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (flag) DSSS_FAIL(c, DSSS_E_CAPACITY, "mosaic: a cell received more than 2^24 samples of one frame (cell %g too coarse)", p->cell);
+    rc = mosaic_flag_down(c, d_flag, "mosaic: a cell received more than 2^24 samples of one frame (cell %g too coarse)", p->cell); if (rc) return rc;
     // the score needs the three layers whether the caller wants them or not
     std::vector<uint32_t> own[3];
     uint32_t* host[3] = { nfr_host, s1_host, s2_host };

@@ -15,43 +15,31 @@ namespace {
 // mosaic_scatter_kernel's launch shape: one workgroup per ping, the job table, the bearing of each side once per ping through LDS,
 // and the sample is binned by the one body (mosaic_sample_cell).  All samples of a ping share g, so within a wavefront the order of
 // two keys is that of (q, col): 31 bits.  Lanes that hit the cell of their neighbour form runs; the minimum of a run is taken with the
-// segmented scan of the mean scatter (min for +) and the last lane of the run issues ONE 64-bit atomicMin without return.
+// segmented scan of the mean scatter (mosaic_run_reduce: min for +) and the last lane of the run issues ONE 64-bit atomicMin without return.
 __global__ __launch_bounds__(256) void mosaic_composite_kernel(const mosaic_job* __restrict__ jobs, int njobs, mosaic_win G, int mode,
                                                                unsigned long long* __restrict__ keys)
 {
     __shared__ double s_sc[4];
-    int lo = 0, hi = njobs - 1;
-    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (jobs[mid].blk0 <= (int)blockIdx.x) lo = mid; else hi = mid - 1; }
-    const mosaic_job J = jobs[lo];
-    const int row = (int)blockIdx.x - J.blk0;
-    if (row >= J.N) return;                                                        // (uniform per workgroup; cannot happen with the host's blk0)
-    const double* P = J.pose + (size_t)row * 6;
-    if (threadIdx.x < 2) dsss_geo_side(P, threadIdx.x == 1, &s_sc[2 * threadIdx.x], &s_sc[2 * threadIdx.x + 1]);
-    __syncthreads();
+    mosaic_job J; int row; const double* P;
+    if (!mosaic_ping_of(jobs, njobs, s_sc, J, row, P)) return;
     const int M = J.M;
     const uint8_t* __restrict__ img = J.img + (size_t)row * M;
     const uint8_t* __restrict__ mask = J.mask + (size_t)row * M;
     const unsigned long long gbits = (unsigned long long)(unsigned)(J.g0 + row) << 16;
-    const int lane = threadIdx.x & 63;
     for (int c0 = 0; c0 < M; c0 += 256) {
         const int col = c0 + (int)threadIdx.x;
         unsigned unused;
         const int cell = mosaic_sample_cell(P, s_sc, J, img, mask, col, G, &unused);
         unsigned v = cell >= 0 ? ((unsigned)comp_rank(mode, M, col) << 16) | (unsigned)col : ~0u;      // q << 16 | col; ~0u: no sample
-        const int prev = __shfl_up(cell, 1);
-        const bool head = lane == 0 || prev != cell;
-        const unsigned long long hb = __ballot(head);
-        const int start = 63 - __clzll((long long)(hb & (~0ull >> (63 - lane))));   // first lane of this lane's run
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const unsigned t = __shfl_up(v, d); if (lane - d >= start) v = min(v, t); }
-        const bool tail = lane == 63 || ((hb >> (lane + 1)) & 1ull);
+        const bool tail = mosaic_run_reduce(cell, v, [](unsigned a, unsigned b) { return min(a, b); });
         if (tail && cell >= 0) atomicMin(&keys[cell], ((unsigned long long)(v >> 16) << 47) | gbits | (v & 0xffffu));
     }
 }
 
 // One thread per cell and RESOLVE_CELLS cells after one another per thread: the key back into the winner's value and source.  The frame
 // of g by binary search over the jobs' g0, which the host sorts by frame id and hence by g0; ids[j] = the frame id of job j.  The g0 of up
-// to RESOLVE_G0 jobs are staged in LDS; a longer table is searched where it lies.  fill gets 0 / 255 here (mosaic_fill_kernel overwrites
+// to RESOLVE_G0 jobs are staged in LDS; a longer table is searched where it lies (a search per cell on another key and from two places:
+// its own two lines, not mosaic_job_of, which a key and an accessor as parameters would only obscure).  fill gets 0 / 255 here (mosaic_fill_kernel overwrites
 // the holes it fills).  The cells that hold a sample are counted with a wave sum and one integer atomic per wavefront -- after its
 // RESOLVE_CELLS cells, and into one of COMP_SLOTS counters the host adds up: with an atomic per 64 cells on ONE address the kernel ran at
 // the rate of that address (6.9 ms for 41 M cells where this takes 0.2: DESIGN.md, "Composite mosaic").
@@ -180,9 +168,7 @@ int dsss_mosaic_composite(dsss_ctx* c, const int* ids, int n, const double* rpy6
 {
     if (!c) return DSSS_E_ARG;
     size_t rows = 0;
-    int rc = mosaic_check_frames(c, ids, n, rpy6, ping_off, true, &rows); if (rc) return rc;
-    rc = mosaic_check_params(c, p); if (rc) return rc;
-    rc = mosaic_check_gain(c, ids, n); if (rc) return rc;
+    int rc = mosaic_check_args(c, ids, n, rpy6, ping_off, p, &rows); if (rc) return rc;
     dsss_comp_params P;
     dsss_comp_params_default(&P);
     if (cp) P = *cp;
@@ -202,31 +188,25 @@ int dsss_mosaic_composite(dsss_ctx* c, const int* ids, int n, const double* rpy6
     const size_t cells = (size_t)p->W * p->H;
     const int R = P.fill_radius;
     // the fill copies a donor's resolved layers, so the layers asked for live on the device; nothing else does
-    carve L;
-    const size_t o_keys = L.take(cells * 8), o_img = L.take(img_host ? cells : 0), o_fr = L.take(src_frame_host ? cells * 4 : 0),
-                 o_pg = L.take(src_ping_host ? cells * 4 : 0), o_col = L.take(src_col_host ? cells * 4 : 0), o_fill = L.take(fill_host ? cells : 0),
-                 o_jobs = L.take((size_t)n * sizeof(mosaic_job)), o_ids = L.take((size_t)n * sizeof(int)),
-                 o_rows = L.take(rpy6 ? rows * 6 * sizeof(double) : 0), o_cnt = L.take((COMP_SLOTS + 1) * sizeof(unsigned long long));
-    rc = c->mosaic_buf.reserve(c, L.off); if (rc) return rc;
-    char* B = c->mosaic_buf.as<char>();
-    unsigned long long* d_keys = reinterpret_cast<unsigned long long*>(B + o_keys);
-    uint8_t* d_img = img_host ? reinterpret_cast<uint8_t*>(B + o_img) : nullptr;
-    int32_t* d_fr = src_frame_host ? reinterpret_cast<int32_t*>(B + o_fr) : nullptr;
-    int32_t* d_pg = src_ping_host ? reinterpret_cast<int32_t*>(B + o_pg) : nullptr;
-    int32_t* d_col = src_col_host ? reinterpret_cast<int32_t*>(B + o_col) : nullptr;
-    uint8_t* d_fill = fill_host ? reinterpret_cast<uint8_t*>(B + o_fill) : nullptr;
-    mosaic_job* d_jobs = reinterpret_cast<mosaic_job*>(B + o_jobs);
-    int* d_ids = reinterpret_cast<int*>(B + o_ids);
-    unsigned long long* d_cnt = reinterpret_cast<unsigned long long*>(B + o_cnt);
+    mosaic_arena A;
+    const auto o_keys = A.take<unsigned long long>(cells);
+    const auto o_img = A.take<uint8_t>(img_host ? cells : 0);
+    const auto o_fr = A.take<int32_t>(src_frame_host ? cells : 0), o_pg = A.take<int32_t>(src_ping_host ? cells : 0), o_col = A.take<int32_t>(src_col_host ? cells : 0);
+    const auto o_fill = A.take<uint8_t>(fill_host ? cells : 0);
+    const auto o_jobs = A.take<mosaic_job>(n); const auto o_ids = A.take<int>(n); const auto o_rows = A.take<double>(rpy6 ? rows * 6 : 0);
+    const auto o_cnt = A.take<unsigned long long>(COMP_SLOTS + 1);
+    rc = A.reserve(c); if (rc) return rc;
+    unsigned long long* d_keys = A.at(o_keys); mosaic_job* d_jobs = A.at(o_jobs); int* d_ids = A.at(o_ids); unsigned long long* d_cnt = A.at(o_cnt);
+    uint8_t* d_img = A.opt(o_img); int32_t* d_fr = A.opt(o_fr); int32_t* d_pg = A.opt(o_pg); int32_t* d_col = A.opt(o_col); uint8_t* d_fill = A.opt(o_fill);
     std::vector<mosaic_job> jobs;
-    rc = mosaic_fill_jobs(c, sid.data(), n, rpy6, soff.data(), reinterpret_cast<double*>(B + o_rows), jobs); if (rc) return rc;
+    rc = mosaic_fill_jobs(c, sid.data(), n, rpy6, soff.data(), A.at(o_rows), jobs); if (rc) return rc;
     int g0 = 0;                                                                    // (mosaic_check_frames: fewer than 2^31 pings in all)
     for (int i = 0; i < n; ++i) { jobs[i].blk0 = g0; jobs[i].g0 = g0; g0 += jobs[i].N; }
     HIPCHK(c, hipMemcpyAsync(d_jobs, jobs.data(), (size_t)n * sizeof(mosaic_job), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(d_ids, sid.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemsetAsync(d_keys, 0xff, cells * 8, c->stream));
     HIPCHK(c, hipMemsetAsync(d_cnt, 0, (COMP_SLOTS + 1) * sizeof(unsigned long long), c->stream));
-    const mosaic_win G{ p->x0, p->y0, p->cell, p->W, p->H, 0, 0, p->W, p->H, p->use_mask != 0 };
+    const mosaic_win G = mosaic_grid_win(p);
     if (g0) hipLaunchKernelGGL(mosaic_composite_kernel, dim3((unsigned)g0), dim3(256), 0, c->stream, d_jobs, n, G, P.mode, d_keys);
     HIPCHK(c, hipGetLastError());
     hipLaunchKernelGGL(mosaic_resolve_kernel, dim3((unsigned)((cells + 256 * RESOLVE_CELLS - 1) / (256 * RESOLVE_CELLS))), dim3(256), 0, c->stream, d_keys, cells, d_jobs, d_ids, n,

@@ -1,8 +1,10 @@
 // diasss_amd/csrc/dsss_mosaic_int.h -- what dsss_mosaic.hip (mosaic, consistency map), dsss_mosaic_reg.hip (overlap registration) and
-// dsss_mosaic_comp.hip (composite mosaic) share: the job and window records of mosaic_scatter_kernel, the argument checks, a frame's window of the grid, the upload of a
-// caller's trajectory and the scatter launch.  The definitions are in dsss_mosaic.hip.  Below them: the score, order and sub-cell
-// rules of the registration, one body for host and device, and what dsss_mosaic_reg.hip needs of the registration's host arithmetic
-// (dsss_mosaic_edge.cpp).
+// dsss_mosaic_comp.hip (composite mosaic) share.  Device: the job and window records of mosaic_scatter_kernel, the binning of a sample, the
+// kernels' scaffolding written once (job lookup mosaic_job_of, ping prologue mosaic_ping_of, segmented reduction mosaic_run_reduce), then
+// the rules of the composite and the score, order and sub-cell rules of the registration, one body for host and device.  Host: the typed
+// arena over mosaic_buf, the argument rules (mosaic_check_args), the windows of the grid (mosaic_grid_win, mosaic_window), the sample-limit
+// flag (mosaic_flag_down), the upload of a caller's trajectory and the scatter launch, defined in dsss_mosaic.hip, and what
+// dsss_mosaic_reg.hip needs of the registration's host arithmetic (dsss_mosaic_edge.cpp).
 #pragma once
 #include "dsss_internal.h"
 
@@ -50,6 +52,43 @@ __device__ __forceinline__ int mosaic_sample_cell(const double* P, const double*
     return iy * G.bw + ix;
 }
 
+// The job of this workgroup in a table whose blk0 ascend from 0: the last one whose blk0 is not above blockIdx.x.  The one job lookup
+// of the family; JOB needs a blk0 and nothing else (mosaic_job here, the registration's own records in dsss_mosaic_reg.hip).
+template <class JOB> __device__ __forceinline__ JOB mosaic_job_of(const JOB* __restrict__ jobs, int njobs)
+{
+    int lo = 0, hi = njobs - 1;
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (jobs[mid].blk0 <= (int)blockIdx.x) lo = mid; else hi = mid - 1; }
+    return jobs[lo];
+}
+
+// What a workgroup of one ping does first (mosaic_scatter_kernel, mosaic_composite_kernel): its job J, the ping's row in the frame and
+// pose row P, and sin and cos of the bearing of each side in s_sc (the kernel's __shared__ double[4]), behind the barrier.  False: the
+// workgroup has no ping; it leaves in front of the barrier (uniform per workgroup; cannot happen with the host's blk0).
+__device__ __forceinline__ bool mosaic_ping_of(const mosaic_job* __restrict__ jobs, int njobs, double* s_sc, mosaic_job& J, int& row, const double*& P)
+{
+    J = mosaic_job_of(jobs, njobs); row = (int)blockIdx.x - J.blk0;
+    if (row >= J.N) return false;
+    P = J.pose + (size_t)row * 6;
+    if (threadIdx.x < 2) dsss_geo_side(P, threadIdx.x == 1, &s_sc[2 * threadIdx.x], &s_sc[2 * threadIdx.x + 1]);
+    __syncthreads();
+    return true;
+}
+
+// The segmented reduction of the family, written once: lanes of a wavefront that hold the same key as their neighbour form a run, v is
+// reduced with op over the lane's run (afterwards v = op over the run's lanes up to this one), and the last lane of a run gets true: it
+// holds the run's value and issues the run's ONE atomic.  op is associative; the mean scatter reduces with +, the composite with min.
+template <class T, class OP> __device__ __forceinline__ bool mosaic_run_reduce(int key, T& v, OP op)
+{
+    const int lane = threadIdx.x & 63;
+    const int prev = __shfl_up(key, 1);
+    const bool head = lane == 0 || prev != key;
+    const unsigned long long hb = __ballot(head);
+    const int start = 63 - __clzll((long long)(hb & (~0ull >> (63 - lane))));       // first lane of this lane's run
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const T t = __shfl_up(v, d); if (lane - d >= start) v = op(v, t); }
+    return lane == 63 || ((hb >> (lane + 1)) & 1ull);
+}
+
 // The samples of one ping, by the 256 threads of its workgroup (mosaic_scatter_kernel's comment in dsss_mosaic.hip): row = the ping's
 // row in the frame's images, acc = the window's accumulators.
 __device__ __forceinline__ void mosaic_scatter_samples(const double* P, const double* sc, const mosaic_job& J, int row, const mosaic_win& G,
@@ -58,18 +97,11 @@ __device__ __forceinline__ void mosaic_scatter_samples(const double* P, const do
     const int M = J.M;
     const uint8_t* __restrict__ img = J.img + (size_t)row * M;
     const uint8_t* __restrict__ mask = J.mask + (size_t)row * M;
-    const int lane = threadIdx.x & 63;
     for (int c0 = 0; c0 < M; c0 += 256) {
         unsigned g = 0;
         const int key = mosaic_sample_cell(P, sc, J, img, mask, c0 + (int)threadIdx.x, G, &g);
         unsigned v = key >= 0 ? (1u << 16) | g : 0u;                               // v: count << 16 | sum within the wavefront
-        const int prev = __shfl_up(key, 1);
-        const bool head = lane == 0 || prev != key;
-        const unsigned long long hb = __ballot(head);
-        const int start = 63 - __clzll((long long)(hb & (~0ull >> (63 - lane))));   // first lane of this lane's run
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const unsigned t = __shfl_up(v, d); if (lane - d >= start) v += t; }
-        const bool tail = lane == 63 || ((hb >> (lane + 1)) & 1ull);
+        const bool tail = mosaic_run_reduce(key, v, [](unsigned a, unsigned b) { return a + b; });
         if (tail && key >= 0) atomicAdd(&acc[key], ((unsigned long long)(v >> 16) << 32) | (v & 0xffffu));
     }
 }
@@ -175,14 +207,34 @@ __host__ __device__ inline void reg_record(bool found, int bx, int by, int radiu
     *out = r;
 }
 
-// carves mosaic_buf into 256-byte aligned pieces
-struct carve { size_t off = 0; size_t take(size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; } };
+// mosaic_buf in typed, 256-byte aligned pieces: take<T>(count) before reserve, at(piece) after it; the one place an offset of mosaic_buf
+// becomes a pointer.  An output layer the caller did not ask for is a piece of no elements: no bytes, and opt(piece) reads it back as
+// null.  A piece that comes down behind a correlation launch is taken with take_flagged: the registration's sample-limit flag lies in
+// the 8 bytes in front of it, so one copy that starts at flag_of(piece) brings the flag and the payload.
+template <class T> struct mosaic_piece { size_t off = 0, count = 0; };
+struct mosaic_arena {
+    size_t bytes = 0; char* B = nullptr;
+    template <class T> mosaic_piece<T> take(size_t count, size_t lead = 0) { const size_t o = bytes + lead; bytes += (lead + count * sizeof(T) + 255) & ~(size_t)255; return { o, count }; }
+    template <class T> mosaic_piece<T> take_flagged(size_t count) { return take<T>(count, 256); }
+    int reserve(dsss_ctx* c) { const int rc = c->mosaic_buf.reserve(c, bytes); B = c->mosaic_buf.as<char>(); return rc; }
+    template <class T> T* at(mosaic_piece<T> p) const { return reinterpret_cast<T*>(B + p.off); }
+    template <class T> T* opt(mosaic_piece<T> p) const { return p.count ? at(p) : nullptr; }
+    template <class T> int* flag_of(mosaic_piece<T> p) const { return reinterpret_cast<int*>(B + p.off - 8); }
+};
 
 int mosaic_check_frames(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, bool need_img, size_t* rows);
 int mosaic_check_params(dsss_ctx* c, const dsss_mosaic_params* p);
+// the argument rules of every entry that bins samples onto a grid, in the order the error precedence rests on: the frames
+// (mosaic_check_frames with their images; *rows = their pings), then the grid, then the range-gain table
+int mosaic_check_args(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, const dsss_mosaic_params* p, size_t* rows);
 void frame_extent(const dsss_frame& f, const double* rows, double* bb);
 void frame_extent_rows(const dsss_frame& f, const double* rows, int r0, int r1, double* bb);      // pings [r0, r1) only
 bool cell_range(double lo, double hi, double origin, double cell, int n, int* a, int* b);
+mosaic_win mosaic_grid_win(const dsss_mosaic_params* p);      // the grid p with the whole of it as the window: what the mean render and the composite scatter into
+// the window of the pings [r0, r1) of a frame on the grid p: the cells their geo extremes can reach; false: none on the grid, *w untouched
+bool mosaic_window(const dsss_frame& f, const double* rows, int r0, int r1, const dsss_mosaic_params* p, mosaic_win* w);
+// the sample-limit flag of a finished render copied down, the stream synchronised; set: DSSS_E_CAPACITY with the entry's own message (fmt takes the cell)
+int mosaic_flag_down(dsss_ctx* c, const int* d_flag, const char* fmt, double cell);
 int upload_rows(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, double* d_rows, std::vector<const double*>& dev_rows);
 // the rule of the range-gain table, part of the argument checks of every entry that bins samples (behind mosaic_check_frames, before
 // anything is reserved, cleared or launched): a table is set and a listed frame has another M -> DSSS_E_ARG

@@ -107,9 +107,7 @@ template <int NV> __device__ __forceinline__ void pyr_down(const unsigned long l
 __global__ __launch_bounds__(256) void mosaic_pyr_kernel(const pyr_job* __restrict__ jobs, int njobs, int levels, const unsigned long long* __restrict__ acc,
                                                          uint16_t* __restrict__ lay, int* __restrict__ flag)
 {
-    int lo = 0, hi = njobs - 1;
-    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (jobs[mid].blk0 <= (int)blockIdx.x) lo = mid; else hi = mid - 1; }
-    const pyr_job J = jobs[lo];
+    const pyr_job J = mosaic_job_of(jobs, njobs);
     const int wg = (int)blockIdx.x - J.blk0;
     const int ty = wg / J.tiles_x, tx = wg - ty * J.tiles_x;
     const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
@@ -152,9 +150,7 @@ __global__ __launch_bounds__(REG_MAX_THREADS) void mosaic_corr_kernel(const reg_
     __shared__ __attribute__((aligned(16))) uint16_t s_a[REG_TILE * REG_TILE];
     __shared__ __attribute__((aligned(16))) uint16_t s_b[REG_HALO * REG_HALO];
     __shared__ uint32_t s_am[REG_TILE];
-    int lo = 0, hi = njobs - 1;
-    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (jobs[mid].blk0 <= (int)blockIdx.x) lo = mid; else hi = mid - 1; }
-    const reg_job J = jobs[lo];
+    const reg_job J = mosaic_job_of(jobs, njobs);
     const int wg = (int)blockIdx.x - J.blk0;
     const int ty = wg / J.strips_x, tx0 = (wg - ty * J.strips_x) * REG_STRIP;
     const int tx1 = min(tx0 + REG_STRIP, J.tiles_x);
@@ -236,9 +232,7 @@ struct cen_job {
 // only where n > 0.  Integers: the order is irrelevant.  A tile holds 1024 cells with ix, iy < 2^28, so its sums fit 2^38.
 __global__ __launch_bounds__(256) void mosaic_centroid_kernel(const cen_job* __restrict__ jobs, int njobs)
 {
-    int lo = 0, hi = njobs - 1;
-    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (jobs[mid].blk0 <= (int)blockIdx.x) lo = mid; else hi = mid - 1; }
-    const cen_job J = jobs[lo];
+    const cen_job J = mosaic_job_of(jobs, njobs);
     const int wg = (int)blockIdx.x - J.blk0;
     const int ty = wg / J.tiles_x, tx = wg - ty * J.tiles_x;
     const int gx = J.rx0 + tx * CEN_TW + ((int)threadIdx.x & 63);
@@ -355,18 +349,7 @@ struct reg_count {
     void sync() { I.syncs += 1; }
 };
 
-// ---- what the registration entries share on the host
-// the window of the pings [r0, r1) of a frame: the cells their geo extremes can reach (as the consistency map's); false: none on the grid
-bool reg_window(const dsss_frame& f, const double* rows, int r0, int r1, const dsss_mosaic_params* p, mosaic_win* w)
-{
-    double bb[4] = { INFINITY, -INFINITY, INFINITY, -INFINITY };
-    frame_extent_rows(f, rows, r0, r1, bb);
-    int ax, bx, ay, by;
-    if (!cell_range(bb[0], bb[1], p->x0, p->cell, p->W, &ax, &bx) || !cell_range(bb[2], bb[3], p->y0, p->cell, p->H, &ay, &by)) return false;
-    *w = mosaic_win{ p->x0, p->y0, p->cell, p->W, p->H, ax, ay, bx - ax + 1, by - ay + 1, p->use_mask != 0 };
-    return true;
-}
-
+// ---- what the registration entries share on the host (a frame's window of the grid is mosaic_window, the consistency map's too)
 // the job of layer la (window A) against layer lb (window Bw) with its sums at out, appended to pj; *blocks = workgroups so far.
 // Windows that do not come within the radius give no job: all sums stay 0.  False: more workgroups than one launch takes.
 bool reg_push_job(std::vector<reg_job>& pj, long long* blocks, const uint16_t* la, const mosaic_win& A, const uint16_t* lb, const mosaic_win& Bw,
@@ -425,7 +408,7 @@ inline size_t reg_round(size_t cells) { return (cells + 127) & ~(size_t)127; }
 // the 64-bit sums of one table
 inline size_t reg_table_words(int r) { return (size_t)(2 * r + 1) * (2 * r + 1) * 6; }
 // the grid without a window: what the segmented scatters take, and what a segment keeps that has no cell on the grid (bw = 0)
-inline mosaic_win reg_grid(const dsss_mosaic_params* p) { return mosaic_win{ p->x0, p->y0, p->cell, p->W, p->H, 0, 0, 0, 0, p->use_mask != 0 }; }
+inline mosaic_win reg_grid(const dsss_mosaic_params* p) { mosaic_win w = mosaic_grid_win(p); w.bw = w.bh = 0; return w; }
 
 // What the argument rules establish: the parameters in force, the frames' places in ids, which frames occur as a and as b, where the
 // peaks are decided, and for the segment entries the rows -- by pair and then by segment of the pair's frame b.
@@ -449,9 +432,7 @@ struct reg_rows {
     {
         c = ctx; ids = ids_; n = n_; rpy6 = rpy6_; ping_off = ping_off_; pair_a = pa; pair_b = pb; npairs = npairs_;
         if (dsss_comm_world(c) > 1) DSSS_FAIL(c, DSSS_E_STATE, "mosaic: registration runs on a single rank (communicator of %d)", dsss_comm_world(c));
-        int rc = mosaic_check_frames(c, ids, n, rpy6, ping_off, true, &traj_rows); if (rc) return rc;
-        rc = mosaic_check_params(c, p); if (rc) return rc;
-        rc = mosaic_check_gain(c, ids, n); if (rc) return rc;
+        const int rc = mosaic_check_args(c, ids, n, rpy6, ping_off, p, &traj_rows); if (rc) return rc;
         dsss_reg_params_default(&R);
         if (rp) R = *rp;
         if (R.radius < 0 || R.radius > REG_MAX_RADIUS) DSSS_FAIL(c, DSSS_E_ARG, "register: radius %d outside 0..%d", R.radius, REG_MAX_RADIUS);
@@ -524,7 +505,7 @@ struct reg_layers {
     void add_a(const reg_rows& Q, int i, const dsss_mosaic_params* p)
     {
         const dsss_frame& f = Q.frame(i);
-        if (!reg_window(f, Q.rows_of(i), 0, f.N, p, &wins[i])) return;
+        if (!mosaic_window(f, Q.rows_of(i), 0, f.N, p, &wins[i])) return;
         on_grid[i] = 1;
         const size_t wc = (size_t)wins[i].bw * wins[i].bh;
         win_cells = std::max(win_cells, wc);
@@ -534,27 +515,15 @@ struct reg_layers {
     size_t add_b(size_t cells) { win_cells = std::max(win_cells, cells); const size_t o = lay_cells; lay_cells += cells; return o; }
 };
 
-// mosaic_buf in typed, 256-byte aligned pieces: take<T>(count) before reserve, at(piece) after it.  A piece that comes down behind a
-// correlation launch is taken with take_flagged: the sample-limit flag lies in the 8 bytes in front of it, so one copy that starts
-// at flag_of(piece) brings the flag and the payload.  The one place the flag's position is decided.
-template <class T> struct reg_piece { size_t off = 0; };
-struct reg_arena {
-    carve L; char* B = nullptr;
-    template <class T> reg_piece<T> take(size_t count) { return reg_piece<T>{ L.take(count * sizeof(T)) }; }
-    template <class T> reg_piece<T> take_flagged(size_t count) { return reg_piece<T>{ L.take(256 + count * sizeof(T)) + 256 }; }
-    int reserve(dsss_ctx* c) { const int rc = c->mosaic_buf.reserve(c, L.off); B = c->mosaic_buf.as<char>(); return rc; }
-    template <class T> T* at(reg_piece<T> p) const { return reinterpret_cast<T*>(B + p.off); }
-    template <class T> int* flag_of(reg_piece<T> p) const { return reinterpret_cast<int*>(B + p.off - 8); }
-};
-
-// The device memory of a registration call: the pieces every entry needs (an entry's own go through A between take and reserve).
-// tab = the sums of one pass, rec = its records on the device path, flag = the sample-limit flag in front of whichever comes down.
+// The device memory of a registration call: the pieces every entry needs, out of the family's arena (an entry's own go through A
+// between take and reserve).  tab = the sums of one pass, rec = its records on the device path, flag = the sample-limit flag in front
+// of whichever comes down (take_flagged / flag_of: the one place the flag's position is decided).
 struct reg_mem {
-    reg_arena A; bool dev = false;
+    mosaic_arena A; bool dev = false;
     uint16_t* lay = nullptr; unsigned long long* win = nullptr; mosaic_job* jobs = nullptr; double* rows = nullptr; reg_job* pairs = nullptr;
     cen_job* cj = nullptr; unsigned long long* cen = nullptr; unsigned long long* tab = nullptr; dsss_reg_result* rec = nullptr; int* flag = nullptr;
-    reg_piece<uint16_t> o_lay; reg_piece<unsigned long long> o_win, o_cen, o_tab; reg_piece<mosaic_job> o_jobs; reg_piece<double> o_rows;
-    reg_piece<reg_job> o_pairs; reg_piece<cen_job> o_cj; reg_piece<dsss_reg_result> o_rec;
+    mosaic_piece<uint16_t> o_lay; mosaic_piece<unsigned long long> o_win, o_cen, o_tab; mosaic_piece<mosaic_job> o_jobs; mosaic_piece<double> o_rows;
+    mosaic_piece<reg_job> o_pairs; mosaic_piece<cen_job> o_cj; mosaic_piece<dsss_reg_result> o_rec;
 
     // n frames, traj_rows pings of a caller's trajectory (0: the frames' own), nrows tables of at most table_words sums in all per pass
     void take(size_t lay_cells, size_t win_cells, int n, size_t traj_rows, size_t nrows, bool centroids, size_t table_words, bool on_device)
@@ -787,7 +756,7 @@ int dsss_mosaic_register_segments(dsss_ctx* c, const int* ids, int n, const doub
         size_t cells = 0;
         for (int s = 0; s < Q.segs_of(i); ++s) {
             mosaic_win w = reg_grid(p);
-            reg_window(f, Q.rows_of(i), s * seg_pings, Q.seg_end(s, f.N), p, &w);
+            mosaic_window(f, Q.rows_of(i), s * seg_pings, Q.seg_end(s, f.N), p, &w);
             sw.push_back(w); hseg.push_back(mosaic_seg{ w.ox, w.oy, w.bw, w.bh, (unsigned long long)cells });
             cells += reg_round((size_t)w.bw * w.bh);
         }
@@ -795,7 +764,7 @@ int dsss_mosaic_register_segments(dsss_ctx* c, const int* ids, int n, const doub
     }
     reg_mem M;
     M.take(W.lay_cells, W.win_cells, n, rpy6 ? Q.traj_rows : 0, nseg, true, table, Q.dev);
-    const reg_piece<mosaic_seg> o_segs = M.A.take<mosaic_seg>(hseg.size());
+    const mosaic_piece<mosaic_seg> o_segs = M.A.take<mosaic_seg>(hseg.size());
     rc = M.reserve(c); if (rc) return rc;
     rc = c->mosaic_pinned.reserve(c, M.down_bytes(nseg, tsz)); if (rc) return rc;
     mosaic_seg* d_segs = M.A.at(o_segs);
@@ -886,7 +855,7 @@ int dsss_mosaic_register_segments_yaw(dsss_ctx* c, const int* ids, int n, const 
                 mosaic_fan F; F.cx = piv[3]; F.cy = piv[4]; F.theta = fan_theta(k, nyaw, Y.step);
                 dsss_sincos(F.theta, &F.s, &F.c);
                 rotate_rows(fr, p0, p1, F.theta, rot.data());
-                reg_window(f, rot.data(), 0, p1 - p0, p, &w);
+                mosaic_window(f, rot.data(), 0, p1 - p0, p, &w);
                 F.ox = w.ox; F.oy = w.oy; F.bw = w.bw; F.bh = w.bh; F.off = (unsigned long long)cells;
                 sw.push_back(w); hfan.push_back(F);
                 cells += reg_round((size_t)w.bw * w.bh);
@@ -897,7 +866,7 @@ int dsss_mosaic_register_segments_yaw(dsss_ctx* c, const int* ids, int n, const 
     HIPCHK(c, hipSetDevice(c->device));
     reg_mem M;
     M.take(W.lay_cells, W.win_cells, n, rpy6 ? Q.traj_rows : 0, nseg, true, table, Q.dev);
-    const reg_piece<mosaic_fan> o_fan = M.A.take<mosaic_fan>(hfan.size());
+    const mosaic_piece<mosaic_fan> o_fan = M.A.take<mosaic_fan>(hfan.size());
     rc = M.reserve(c); if (rc) return rc;
     rc = c->mosaic_pinned.reserve(c, M.down_bytes(nseg, tsz)); if (rc) return rc;
     mosaic_fan* d_fan = M.A.at(o_fan);
@@ -1022,7 +991,7 @@ int dsss_mosaic_register_segments_pyr(dsss_ctx* c, const int* ids, int n, const 
         const dsss_frame& f = Q.frame(i);
         const double* fr = Q.rows_of(i);
         job0[i] = (int)hpj.size();
-        if (Q.as_a[i] && reg_window(f, fr, 0, f.N, p, &wins[i])) {
+        if (Q.as_a[i] && mosaic_window(f, fr, 0, f.N, p, &wins[i])) {
             on_grid[i] = 1;
             add_area(i, wins[i], 0, &a_lay[i]);
             a_cells[i] = reg_round((size_t)wins[i].bw * wins[i].bh);
@@ -1033,7 +1002,7 @@ int dsss_mosaic_register_segments_pyr(dsss_ctx* c, const int* ids, int n, const 
             for (int s = 0; s < Q.segs_of(i); ++s) {
                 mosaic_win w = reg_grid(p);
                 area_lay al{};
-                if (reg_window(f, fr, s * seg_pings, Q.seg_end(s, f.N), p, &w)) add_area(i, w, a_cells[i] + cells, &al);
+                if (mosaic_window(f, fr, s * seg_pings, Q.seg_end(s, f.N), p, &w)) add_area(i, w, a_cells[i] + cells, &al);
                 sw.push_back(w); seg_lay.push_back(al); hseg.push_back(mosaic_seg{ w.ox, w.oy, w.bw, w.bh, (unsigned long long)cells });
                 cells += reg_round((size_t)w.bw * w.bh);
             }
@@ -1067,8 +1036,8 @@ int dsss_mosaic_register_segments_pyr(dsss_ctx* c, const int* ids, int n, const 
     const size_t words_max = std::max(words_of(L - 1), words_of(0));
     reg_mem M;
     M.take(lay_cells, win_cells, n, rpy6 ? Q.traj_rows : 0, nseg, true, (size_t)nseg * words_max, dev);
-    const reg_piece<mosaic_seg> o_segs = M.A.take<mosaic_seg>(hseg.size());
-    const reg_piece<pyr_job> o_pj = M.A.take<pyr_job>(hpj.size());
+    const mosaic_piece<mosaic_seg> o_segs = M.A.take<mosaic_seg>(hseg.size());
+    const mosaic_piece<pyr_job> o_pj = M.A.take<pyr_job>(hpj.size());
     rc = M.reserve(c); if (rc) return rc;
     rc = c->mosaic_pinned.reserve(c, M.down_bytes(nseg, words_max)); if (rc) return rc;
     mosaic_seg* d_segs = M.A.at(o_segs); pyr_job* d_pj = M.A.at(o_pj);
@@ -1157,9 +1126,9 @@ int dsss_mosaic_register_peaks(dsss_ctx* c, const uint64_t* sums, int64_t ntable
     hipPointerAttribute_t at;
     const bool on_dev = (hipPointerGetAttributes(&at, sums) == hipSuccess) && at.type == hipMemoryTypeDevice;
     (void)hipGetLastError();
-    reg_arena A;
-    const reg_piece<dsss_reg_result> o_rec = A.take<dsss_reg_result>(nt);
-    const reg_piece<unsigned long long> o_tab = A.take<unsigned long long>(on_dev ? 0 : nt * tsz);      // host tables go up into mosaic_buf
+    mosaic_arena A;
+    const mosaic_piece<dsss_reg_result> o_rec = A.take<dsss_reg_result>(nt);
+    const mosaic_piece<unsigned long long> o_tab = A.take<unsigned long long>(on_dev ? 0 : nt * tsz);      // host tables go up into mosaic_buf
     int rc = A.reserve(c); if (rc) return rc;
     rc = c->mosaic_pinned.reserve(c, nt * sizeof(dsss_reg_result)); if (rc) return rc;
     dsss_reg_result* d_rec = A.at(o_rec);

@@ -1,7 +1,7 @@
 // diasss_amd/csrc/dsss_wave.h -- the wave scan, the workgroup scan and the wave sum of the kernels (device only, wave64).
 // Every caller sits on an order-sensitive path (candidate order, kept keypoints, kp7 offsets, edge order, the normal
 // stream, the bit-reproducible mean), so there is one copy of each.  Sums only: the min / max butterflies, the segmented
-// scan of the mosaic, the two-step sums of the fronts and the matcher's fold are different code and stay where they are.
+// scan of the mosaic (mosaic_run_reduce, + or min), the two-step sums of the fronts and the matcher's fold are different code and stay where they are.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -245,6 +245,100 @@ def test_order_and_repeat(pair, legs):
         assert a[3] == b[3] == r[3]
 
 
+# ---------------------------------------------------------------- 9. small and wide frames, a table of three jobs
+def _shape_ctx(orc, rows, cols, poses):
+    """a context of its own that holds the speckle frame of the extraction's wide shapes once per pose in `poses`, extracted under the
+    small-frame mask -> (context, the oracle's (gx, gy, norm, mask) of every frame)"""
+    from diasss_amd import capi
+    from tests import extract_shapes_ref as X
+    nf = [s[3] for s in X.WIDE_SHAPES if s[:2] == (rows, cols)][0]
+    raw, orb, oref = X.wide_case(orc, rows, cols, 1, nf)
+    _, alt, gr = X.dr_inputs(rows, cols)
+    frames = [orc.geo_img(pose, gr, cols) + (oref["norm"], oref["mask"]) for pose in poses]
+    c = capi.Context(max_frames=len(poses))
+    try:
+        mp, op = X.device_params(c, X.SMALL_MASK, orb)
+        c.set_params(mask=mp, orb=op)
+        for f, pose in enumerate(poses):
+            c.frame_set(f, raw, rows, cols, pose, alt, gr)
+        c.extract_many(list(range(len(poses))))
+    except Exception:
+        c.close()
+        raise
+    return c, frames
+
+
+def _extremes_grid(capi, frames, cell):
+    gx = np.concatenate([f[0].ravel() for f in frames]); gy = np.concatenate([f[1].ravel() for f in frames])
+    return capi.mosaic_grid((gx.min(), gx.max(), gy.min(), gy.max()), cell)
+
+
+@pytest.mark.parametrize("shape", [(69, 86), (69, 1234)], ids=lambda s: "%dx%d" % s)
+def test_render_frame_shapes(orc, shape):
+    """the mean scatter at the composite's frame shapes.  69 x 86: one column chunk whose second wavefront is part full (64 + 22), and
+    columns 0 and 1 of a ping are one point, so a run starts in lane 0; 69 x 1234: five column chunks, the last with 210 columns.  On the
+    grid of the frame's own extremes the unmasked reference keeps every sample, at cell 0.13 its fullest cell holds a run, and the
+    mask keeps some samples and drops others"""
+    from diasss_amd import capi
+    from tests import extract_shapes_ref as X
+    rows, cols = shape
+    c, frames = _shape_ctx(orc, rows, cols, [X.dr_inputs(rows, cols)[0]])
+    try:
+        gx, gy = frames[0][:2]
+        assert gx[5, 0] == gx[5, 1] and gy[5, 0] == gy[5, 1]                        # columns 0 and 1 are one point
+        for cell in (0.05, 0.13):
+            p = _extremes_grid(capi, frames, cell)
+            kept = {}
+            for use_mask in (0, 1):
+                q = _params(capi, p, use_mask=use_mask)
+                S, Cn, I, kept[use_mask] = ref_render(frames, q, use_mask)
+                s, cn, img = c.mosaic_render([0], q)
+                print("%d x %d cell %g mask %d: grid %d x %d, %d samples kept, fullest cell %d" % (rows, cols, cell, use_mask, p.W, p.H, kept[use_mask], Cn.max()))
+                assert _same(cn, Cn), "cnt differs"
+                assert _same(s, S), "sum differs"
+                assert _same(img, I), "img differs"
+                if cell == 0.13:
+                    assert Cn.max() >= 2
+            assert kept[0] == rows * cols
+            assert 0 < kept[1] < kept[0]
+    finally:
+        c.close()
+
+
+def test_three_job_table(orc):
+    """the 69 x 86 frame as frames 0, 1 and 2 under poses 0.07 m apart across the track, so that they overlap: the job lookup of the
+    scatter with more than two jobs (the render) and with a table per frame (the consistency map), listed as (2, 0, 1) and as (0, 1, 2)"""
+    from diasss_amd import capi
+    from tests import extract_shapes_ref as X
+    rows, cols = 69, 86
+    pose = X.dr_inputs(rows, cols)[0]
+    poses = []
+    for f in range(3):
+        pf = pose.copy(); pf[:, 4] += 0.07 * f; pf[:, 3] += 0.013 * (f % 7)
+        poses.append(pf)
+    c, frames = _shape_ctx(orc, rows, cols, poses)
+    try:
+        p = _extremes_grid(capi, frames, 0.13)
+        for use_mask in (0, 1):
+            q = _params(capi, p, use_mask=use_mask)
+            S, Cn, I, kept = ref_render(frames, q, use_mask)
+            R = ref_consistency(frames, q, use_mask)
+            print("mask %d: grid %d x %d, %d samples kept, %d cells seen by three frames, reference score %.15g" % (
+                use_mask, p.W, p.H, kept, int((R[0] == 3).sum()), R[3]))
+            assert int(R[0].max()) == 3 and R[3] > 0
+            a = c.mosaic_render([2, 0, 1], q)
+            assert _same(a[1], Cn) and _same(a[0], S) and _same(a[2], I)
+            m = c.mosaic_consistency([2, 0, 1], q)
+            assert _same(m[0], R[0]) and _same(m[1], R[1]) and _same(m[2], R[2])
+            assert abs(m[3] - R[3]) <= 1e-12 * R[3]
+            b = c.mosaic_render([0, 1, 2], q); n = c.mosaic_consistency([0, 1, 2], q)
+            for x, y in zip(list(a) + list(m[:3]), list(b) + list(n[:3])):
+                assert x.tobytes() == y.tobytes()
+            assert m[3] == n[3]
+    finally:
+        c.close()
+
+
 # ---------------------------------------------------------------- 8. errors
 def test_errors_leave_the_context_usable(pair, legs):
     from diasss_amd import capi
