@@ -229,8 +229,10 @@ __device__ inline int cvfloorf_dev(float v) { const int i = (int)v; return i - (
 
 // cv::resize(INTER_LINEAR) of one pyramid level from the previous one, OpenCV's scalar u8 path: 11-bit fixed-point weights per
 // output column / row (tables built once per geometry by resize_tables(), the same float arithmetic OpenCV uses), horizontal pass
-// in int, vertical pass with the two 16-bit shifts.  A thread produces FOUR consecutive bytes of the level (flat index, so the
-// 4-byte store is always aligned, a group may wrap into the next row) -- the one-byte-per-thread form stored at 7 % of HBM speed.
+// in int, vertical pass with the two 16-bit shifts.  THE FLAT FORM, for the geometries whose 12-byte windows do not fit (the flag
+// behind the x table; resize_strip_kernel below does the others, each kernel reads the one flag): a thread produces FOUR
+// consecutive bytes of the level (flat index, so the 4-byte store is always aligned, a group may wrap into the next row) -- the
+// one-byte-per-thread form stored at 7 % of HBM speed.
 typedef uint16_t u16_unaligned __attribute__((aligned(1)));
 // RS_K groups of four pixels per thread, 1024 pixels apart, written as four straight-line phases (indices, tables, pixels,
 // arithmetic): with one group per thread the kernel waited three dependent memory latencies (frame record, tables, pixels)
@@ -244,11 +246,16 @@ typedef uint16_t u16_unaligned __attribute__((aligned(1)));
 #endif
 typedef unsigned short rs_u16x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t rs_u32x3 __attribute__((ext_vector_type(3)));
-__global__ __launch_bounds__(256) void resize_kernel(const ex_frame* __restrict__ frs, int level, int rest_only)
+// the vertical pass and the rounding of one pixel from its two row sums (weights <= 2048, row sums >> 4 < 2^16: 24-bit multiplies, full rate)
+__device__ __forceinline__ uint32_t rs_vertical(uint32_t b0, uint32_t r0, uint32_t b1, uint32_t r1)
+{
+    return (((__umul24(b0, r0 >> 4) >> 16) + (__umul24(b1, r1 >> 4) >> 16) + 2u) >> 2) & 255u;
+}
+__global__ __launch_bounds__(256) void resize_kernel(const ex_frame* __restrict__ frs, int level)
 {
     const ex_frame& f = frs[blockIdx.y];
     if (level >= f.nlevels) return;
-    if (rest_only && f.xt[level][f.cols[level] + 4].sx != 0) return;      // resize_strip_kernel has done this frame
+    if (f.xt[level][f.cols[level] + 4].sx != 0) return;                   // the windows fit: resize_strip_kernel does this frame
     // pointers read from the frame record are generic to the compiler (flat loads, 64-bit address arithmetic per access): say
     // they are global, and index them with 32-bit offsets from the wave-uniform base
     const DSSS_GLOBAL uint8_t* __restrict__ src = (const DSSS_GLOBAL uint8_t*)f.lvl[level - 1]; DSSS_GLOBAL uint8_t* __restrict__ dst = (DSSS_GLOBAL uint8_t*)f.lvl[level];
@@ -266,7 +273,7 @@ __global__ __launch_bounds__(256) void resize_kernel(const ex_frame* __restrict_
                 int r0, r1;
                 if (X.a1) { r0 = S0[X.sx] * X.a0 + S0[X.sx + 1] * X.a1; r1 = S1[X.sx] * X.a0 + S1[X.sx + 1] * X.a1; }
                 else { r0 = S0[X.sx] * X.a0; r1 = S1[X.sx] * X.a0; }
-                dst[g] = (uint8_t)((((Y.b0 * (r0 >> 4)) >> 16) + ((Y.b1 * (r1 >> 4)) >> 16) + 2) >> 2);
+                dst[g] = (uint8_t)rs_vertical((uint32_t)Y.b0, (uint32_t)r0, (uint32_t)Y.b1, (uint32_t)r1);
             }
         return;
     }
@@ -291,62 +298,26 @@ __global__ __launch_bounds__(256) void resize_kernel(const ex_frame* __restrict_
         const uint4 xb = *reinterpret_cast<const DSSS_GLOBAL uint4*>(reinterpret_cast<const DSSS_GLOBAL char*>(xt) + rr[k] * 8u + 16u);
         xs[k][0] = xa.x; xw[k][0] = xa.y; xs[k][1] = xa.z; xw[k][1] = xa.w; xs[k][2] = xb.x; xw[k][2] = xb.y; xs[k][3] = xb.z; xw[k][3] = xb.w;
     }
-    const bool windowed = xt[dw + 4].sx != 0;
+    // pixels: one unaligned 16-bit pair per pixel and source row; a pixel past the end of the row takes the next row's
     uint32_t outv[RS_K];
-    if (windowed) {
-        // The 14 loads per group of the first form (8 unaligned 16-bit pixel pairs) made the kernel wait for the texture
-        // addresser (one wave-load per ~20 cycles).  The source bytes of the four pixels of a group lie within six consecutive
-        // bytes of each of the two source rows: ONE aligned 12-byte load per row, the pairs come out of it by v_perm.
-        uint32_t W0[RS_K][3], W1[RS_K][3], m0[RS_K], m1[RS_K];
-#pragma unroll
-        for (int k = 0; k < RS_K; ++k) {
-            const uint32_t b0 = __umul24((uint32_t)Y0[k].ya, (uint32_t)sw) + xs[k][0], b1 = __umul24((uint32_t)Y0[k].yb, (uint32_t)sw) + xs[k][0];
-            m0[k] = b0 & 3u; m1[k] = b1 & 3u;                            // the level base is 256-byte aligned
-            const rs_u32x3 w0 = *reinterpret_cast<const DSSS_GLOBAL rs_u32x3*>(src + (b0 & ~3u));
-            const rs_u32x3 w1 = *reinterpret_cast<const DSSS_GLOBAL rs_u32x3*>(src + (b1 & ~3u));
-            W0[k][0] = w0.x; W0[k][1] = w0.y; W0[k][2] = w0.z; W1[k][0] = w1.x; W1[k][1] = w1.y; W1[k][2] = w1.z;
-        }
-#pragma unroll
-        for (int k = 0; k < RS_K; ++k) {
-            uint32_t out = 0;
-            const uint32_t b0 = (uint32_t)Y0[k].b0, b1 = (uint32_t)Y0[k].b1;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const uint32_t d = xs[k][u] - xs[k][0];                   // 0 .. 4
-                const uint32_t o0 = m0[k] + d, o1 = m1[k] + d;            // byte index of the left pixel in the 12-byte window: 0 .. 7
-                const uint32_t lo0 = o0 & 4u ? W0[k][1] : W0[k][0], hi0 = o0 & 4u ? W0[k][2] : W0[k][1];
-                const uint32_t lo1 = o1 & 4u ? W1[k][1] : W1[k][0], hi1 = o1 & 4u ? W1[k][2] : W1[k][1];
-                const rs_u16x2 w = __builtin_bit_cast(rs_u16x2, xw[k][u]);
-                const uint32_t r0 = __builtin_amdgcn_udot2(__builtin_bit_cast(rs_u16x2, __builtin_amdgcn_perm(hi0, lo0, 0x0c010c00u + (o0 & 3u) * 0x00010001u)), w, 0u, false);
-                const uint32_t r1 = __builtin_amdgcn_udot2(__builtin_bit_cast(rs_u16x2, __builtin_amdgcn_perm(hi1, lo1, 0x0c010c00u + (o1 & 3u) * 0x00010001u)), w, 0u, false);
-                const uint32_t v = (((__umul24(b0, r0 >> 4) >> 16) + (__umul24(b1, r1 >> 4) >> 16) + 2u) >> 2) & 255u;        // (weights <= 2048, row sums >> 4 < 2^16: 24-bit multiplies, full rate)
-                out |= v << (8 * u);
-            }
-            outv[k] = out;
-        }
-    }
-    // groups that run over the end of a row (one in a row), and every group of a geometry the windows do not fit: pixel by pixel
 #pragma unroll
     for (int k = 0; k < RS_K; ++k) {
-        if (!windowed || rr[k] + 3u >= (uint32_t)dw) {
-            const resize_ytab Y1k = *reinterpret_cast<const DSSS_GLOBAL resize_ytab*>(reinterpret_cast<const DSSS_GLOBAL char*>(yt) + q1[k] * (uint32_t)sizeof(resize_ytab));
-            const uint32_t A0 = __umul24((uint32_t)Y0[k].ya, (uint32_t)sw), A1 = __umul24((uint32_t)Y0[k].yb, (uint32_t)sw);      // rows, columns < 65536
-            const uint32_t B0 = __umul24((uint32_t)Y1k.ya, (uint32_t)sw), B1 = __umul24((uint32_t)Y1k.yb, (uint32_t)sw);
-            uint32_t out = 0;
+        const resize_ytab Y1k = *reinterpret_cast<const DSSS_GLOBAL resize_ytab*>(reinterpret_cast<const DSSS_GLOBAL char*>(yt) + q1[k] * (uint32_t)sizeof(resize_ytab));
+        const uint32_t A0 = __umul24((uint32_t)Y0[k].ya, (uint32_t)sw), A1 = __umul24((uint32_t)Y0[k].yb, (uint32_t)sw);      // rows, columns < 65536
+        const uint32_t B0 = __umul24((uint32_t)Y1k.ya, (uint32_t)sw), B1 = __umul24((uint32_t)Y1k.yb, (uint32_t)sw);
+        uint32_t out = 0;
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const bool wr = rr[k] + (uint32_t)u >= (uint32_t)dw;
-                const uint32_t p0 = *reinterpret_cast<const DSSS_GLOBAL u16_unaligned*>(src + ((wr ? B0 : A0) + xs[k][u]));
-                const uint32_t p1 = *reinterpret_cast<const DSSS_GLOBAL u16_unaligned*>(src + ((wr ? B1 : A1) + xs[k][u]));
-                const uint32_t b0 = (uint32_t)(wr ? Y1k.b0 : Y0[k].b0), b1 = (uint32_t)(wr ? Y1k.b1 : Y0[k].b1);
-                const rs_u16x2 w = __builtin_bit_cast(rs_u16x2, xw[k][u]);
-                const uint32_t r0 = __builtin_amdgcn_udot2(__builtin_bit_cast(rs_u16x2, __builtin_amdgcn_perm(0u, p0, 0x0c010c00u)), w, 0u, false);
-                const uint32_t r1 = __builtin_amdgcn_udot2(__builtin_bit_cast(rs_u16x2, __builtin_amdgcn_perm(0u, p1, 0x0c010c00u)), w, 0u, false);
-                const uint32_t v = (((__umul24(b0, r0 >> 4) >> 16) + (__umul24(b1, r1 >> 4) >> 16) + 2u) >> 2) & 255u;        // (weights <= 2048, row sums >> 4 < 2^16: 24-bit multiplies, full rate)
-                out |= v << (8 * u);
-            }
-            outv[k] = out;
+        for (int u = 0; u < 4; ++u) {
+            const bool wr = rr[k] + (uint32_t)u >= (uint32_t)dw;
+            const uint32_t p0 = *reinterpret_cast<const DSSS_GLOBAL u16_unaligned*>(src + ((wr ? B0 : A0) + xs[k][u]));
+            const uint32_t p1 = *reinterpret_cast<const DSSS_GLOBAL u16_unaligned*>(src + ((wr ? B1 : A1) + xs[k][u]));
+            const uint32_t b0 = (uint32_t)(wr ? Y1k.b0 : Y0[k].b0), b1 = (uint32_t)(wr ? Y1k.b1 : Y0[k].b1);
+            const rs_u16x2 w = __builtin_bit_cast(rs_u16x2, xw[k][u]);
+            const uint32_t r0 = __builtin_amdgcn_udot2(__builtin_bit_cast(rs_u16x2, __builtin_amdgcn_perm(0u, p0, 0x0c010c00u)), w, 0u, false);
+            const uint32_t r1 = __builtin_amdgcn_udot2(__builtin_bit_cast(rs_u16x2, __builtin_amdgcn_perm(0u, p1, 0x0c010c00u)), w, 0u, false);
+            out |= rs_vertical(b0, r0, b1, r1) << (8 * u);
         }
+        outv[k] = out;
     }
 #pragma unroll
     for (int k = 0; k < RS_K; ++k) {
@@ -372,7 +343,7 @@ __global__ __launch_bounds__(256) void resize_strip_kernel(const ex_frame* __res
     const DSSS_GLOBAL uint8_t* __restrict__ src = (const DSSS_GLOBAL uint8_t*)f.lvl[level - 1]; DSSS_GLOBAL uint8_t* __restrict__ dst = (DSSS_GLOBAL uint8_t*)f.lvl[level];
     const int sw = f.cols[level - 1], dh = f.rows[level], dw = f.cols[level];
     const DSSS_GLOBAL resize_xtab* __restrict__ xt = (const DSSS_GLOBAL resize_xtab*)f.xt[level]; const DSSS_GLOBAL resize_ytab* __restrict__ yt = (const DSSS_GLOBAL resize_ytab*)f.yt[level];
-    if (xt[dw + 4].sx == 0) return;                                       // windows do not fit: resize_kernel(rest_only) does this frame
+    if (xt[dw + 4].sx == 0) return;                                       // windows do not fit: resize_kernel does this frame
     const uint32_t G = (uint32_t)(dw + 3) >> 2, nch = (uint32_t)(dh + RS_R - 1) / RS_R;
     const uint32_t t = blockIdx.x * 256u + threadIdx.x;
     if (t >= G * nch) return;
@@ -941,7 +912,7 @@ struct level_geom {
     fast_cell* d_cells = nullptr;         // device copy (per geometry, cached in the context)
     int* d_lrows = nullptr; float* d_lscale = nullptr;
     resize_xtab* d_xt[DSSS_MAX_LEVELS] = { nullptr }; resize_ytab* d_yt[DSSS_MAX_LEVELS] = { nullptr };
-    bool strips[DSSS_MAX_LEVELS] = { false };                  // level l is resized by resize_strip_kernel (the windowed loads fit)
+    bool strips[DSSS_MAX_LEVELS] = { false };                  // the flag behind level l's x table: resize_strip_kernel does the level, else resize_kernel
     ~level_geom() { hipFree(d_cells); hipFree(d_lrows); hipFree(d_lscale); for (int l = 0; l < DSSS_MAX_LEVELS; ++l) { hipFree(d_xt[l]); hipFree(d_yt[l]); } }
 };
 
@@ -1019,8 +990,8 @@ void resize_tables(int sh, int sw, int dh, int dw, std::vector<resize_xtab>& xt,
         xt[dx].sx = sx; xt[dx].a0 = (short)lrintf((1.f - fx) * 2048.f); xt[dx].a1 = (short)lrintf(fx * 2048.f);
     }
     // four more entries = the first four again (a group of four pixels that runs over the end of a row reads xt[dx .. dx + 3]
-    // as one piece), then one entry whose sx says whether the windowed loads of resize_kernel are valid for this geometry: the
-    // source bytes of four consecutive output pixels span at most six
+    // as one piece), then one entry whose sx says which kernel resizes this geometry: resize_strip_kernel when its 12-byte
+    // windows fit (the source bytes of four consecutive output pixels span at most six), resize_kernel otherwise
     int span = 0;
     for (int dx = 0; dx + 3 < dw; ++dx) span = std::max(span, xt[dx + 3].sx + 1 - xt[dx].sx);
     for (int u = 0; u < 4; ++u) { const resize_xtab e = xt[u % dw]; xt.push_back(e); }
@@ -1316,7 +1287,7 @@ struct ex_run {
               bool strips = false, rest = false;
               for (int s = 0; s < nb; ++s) { const level_geom& g = *G[bt.b0 + s]; if (l < g.nlevels) (g.strips[l] ? strips : rest) = true; }
               if (strips) hipLaunchKernelGGL(resize_strip_kernel, dim3((unsigned)(((size_t)((bt.max_cols[l] + 3) / 4) * ((bt.max_rows[l] + RS_R - 1) / RS_R) + 255) / 256), nb), dim3(256), 0, st, d_exf, l);
-              if (rest) hipLaunchKernelGGL(resize_kernel, dim3((unsigned)(((size_t)bt.max_cols[l] * bt.max_rows[l] / 4 + 256 * RS_K) / (256 * RS_K)), nb), dim3(256), 0, st, d_exf, l, strips ? 1 : 0);
+              if (rest) hipLaunchKernelGGL(resize_kernel, dim3((unsigned)(((size_t)bt.max_cols[l] * bt.max_rows[l] / 4 + 256 * RS_K) / (256 * RS_K)), nb), dim3(256), 0, st, d_exf, l);
           } }
         bool qt_used[2] = { false, false };
         const int rc = level_groups(bt, qt_used); if (rc) return rc;

@@ -16,18 +16,102 @@
 // (FEAmatcher.cpp:152-161) come out exactly as in the scalar loop.
 // MODE 0: Hamming on the 32 ORB bytes; 1: L2 on the same 32 bytes (what the shipped reference feeds its L2 branch); 2: L2 on the 128-element
 // rows of DSSS_DESC_SIFT128 (`desc` is then the 128-byte store).  The elements are integers 0..255, so the squared distance is an exact
-// integer: |a|^2 + |b|^2 - 2 a.b with the dot product on v_dot4_u32_u8 (32 of them per candidate).
-__device__ inline unsigned dot128(const uint4 (&q)[8], const uint4* __restrict__ b)
+// integer: |a|^2 + |b|^2 - 2 a.b with the dot products on v_dot4_u32_u8 (NW uint4 of four words each; 32 per product of 128-byte rows).
+template <int NW>
+__device__ inline unsigned mt_dot(const uint4 (&q)[NW], const uint4* __restrict__ b)
 {
     unsigned acc = 0;
 #pragma unroll
-    for (int w = 0; w < 8; ++w) {
+    for (int w = 0; w < NW; ++w) {
         const uint4 v = b[w];
         acc = __builtin_amdgcn_udot4(q[w].x, v.x, acc, false); acc = __builtin_amdgcn_udot4(q[w].y, v.y, acc, false);
         acc = __builtin_amdgcn_udot4(q[w].z, v.z, acc, false); acc = __builtin_amdgcn_udot4(q[w].w, v.w, acc, false);
     }
     return acc;
 }
+// ---- the rules of the first stage, each said once (match_nn_kernel, match_grid_kernel, mt_grid_count_kernel; scc_kernel takes the first)
+// directed pair pd = 2 p + dir: the query frame fa is the pair's source in direction 0, its target in direction 1
+struct mt_dir { int p, dir, fa, fb; };
+__device__ __forceinline__ mt_dir mt_dir_of(const int* __restrict__ act_s, const int* __restrict__ act_t, int pd)
+{
+    const int p = pd >> 1, dir = pd & 1;
+    return { p, dir, dir ? act_t[p] : act_s[p], dir ? act_s[p] : act_t[p] };
+}
+// the geo box of the reference frame; a query outside it has no match (FEAmatcher.cpp:84): ordered comparisons, a NaN is NOT outside
+struct mt_box { double x0, x1, y0, y1; };
+__device__ __forceinline__ mt_box mt_box_of(const double* __restrict__ bbox, int fb) { return { bbox[fb * 4 + 0], bbox[fb * 4 + 1], bbox[fb * 4 + 2], bbox[fb * 4 + 3] }; }
+__device__ __forceinline__ bool mt_outside(double x, double y, const mt_box& B) { return x < B.x0 || y < B.y0 || x > B.x1 || y > B.y1; }
+__device__ __forceinline__ int mt_hamming256(const unsigned* a, const unsigned* b)
+{
+    int d = 0;
+#pragma unroll
+    for (int w = 0; w < 8; ++w) d += __popc(a[w] ^ b[w]);
+    return d;
+}
+// the query's descriptor and its distance to a candidate's; where the candidate's words (and, MODE 2, its squared norm) come from --
+// an LDS tile, the sorted copy, the store -- is the caller's business
+template <int MODE>
+struct mt_query {
+    uint4 w[MODE == 2 ? 8 : 2]; unsigned n2;                   // the 32 bytes as (lo, hi), or the 128-byte row and |q|^2
+    __device__ __forceinline__ void load(const uint4* __restrict__ d)
+    {
+#pragma unroll
+        for (int i = 0; i < (MODE == 2 ? 8 : 2); ++i) w[i] = d[i];
+        if constexpr (MODE != 0) n2 = mt_dot(w, d);
+    }
+    __device__ __forceinline__ int dist(const uint4& lo, const uint4& hi) const        // MODE 0, 1: the candidate's 32 bytes
+    {
+        if constexpr (MODE == 0) {
+            const unsigned wa[8] = { w[0].x, w[0].y, w[0].z, w[0].w, w[1].x, w[1].y, w[1].z, w[1].w };
+            const unsigned wb[8] = { lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w };
+            return mt_hamming256(wa, wb);
+        } else {
+            const uint4 b[2] = { lo, hi };
+            return dist(b, mt_dot(b, b));
+        }
+    }
+    __device__ __forceinline__ int dist(const uint4* __restrict__ b, unsigned bn2) const { return (int)(n2 + bn2 - 2u * mt_dot(w, b)); }      // MODE 1, 2
+};
+// (best, second, lowest index at the minimum, number of candidates) of a query, FEAmatcher.cpp:86-161.  The scalar loop's "first
+// index wins" (:152-161) is take_in_order() when the candidates come in index order; take() and fold() say the same without the
+// order: the two smallest distances (a tie at the minimum makes the second equal to it) and the lowest index at the minimum.
+struct mt_best2 {
+    int best, second, id, nc;
+    template <bool L2> __device__ __forceinline__ static mt_best2 none() { return { L2 ? 1000000 : 1000, L2 ? 1000000 : 1000, -1, 0 }; }
+    __device__ __forceinline__ void take_in_order(int d, int i)
+    {
+        ++nc;
+        if (d < best) { second = best; best = d; id = i; } else if (d < second) second = d;
+    }
+    __device__ __forceinline__ void take(int d, int i)
+    {
+        ++nc;
+        if (d < best) { second = best; best = d; id = i; } else if (d == best) { second = d; if (i < id) id = i; } else if (d < second) second = d;
+    }
+    // another part of the same query's candidates: the two smallest of the union, the lowest index among the minima, the counts added
+    __device__ __forceinline__ void fold(const mt_best2& o)
+    {
+        if (o.best < best) { second = min(best, o.second); best = o.best; id = o.id; }
+        else if (o.best == best) { second = best; id = min(id, o.id); }      // (both -1 when nothing beat the initial value)
+        else second = min(second, o.best);
+        nc += o.nc;
+    }
+    // the accepted candidate or -1 (FEAmatcher.cpp:99-131)
+    template <bool L2> __device__ __forceinline__ int accept(int fa, int fb, int bound_same, int bound_diff, double l2_bound, double ratio_max) const
+    {
+        if (nc == 0) return -1;
+        if (!L2) {
+            const int bound = ((fa % 2) != (fb % 2)) ? bound_diff : bound_same;
+            const double r = (double)best / (double)second;
+            if (id != -1 && best <= bound && r <= ratio_max && second != 1000) return id;
+            return nc == 1 && best <= bound ? id : -1;
+        }
+        const double bd = sqrt((double)best), sd = sqrt((double)second);   // cv::norm(NORM_L2), FEAmatcher.cpp:113
+        const double r = bd / sd;
+        if (id != -1 && bd < l2_bound && r <= ratio_max) return id;
+        return nc == 1 && bd < l2_bound ? id : -1;
+    }
+};
 template <int MODE>
 __global__ __launch_bounds__(MT_TILE) void match_nn_kernel(
     const int* __restrict__ act_s, const int* __restrict__ act_t, const int* __restrict__ nkp,
@@ -37,40 +121,29 @@ __global__ __launch_bounds__(MT_TILE) void match_nn_kernel(
 {
     constexpr bool L2 = MODE != 0;
     constexpr int DW = MODE == 2 ? 8 : 1;          // uint4 per half-descriptor slot
+    constexpr int DB = MODE == 2 ? 128 : 32;       // bytes per descriptor
     __shared__ uint4 s_lo[MT_TILE * DW], s_hi[MODE == 2 ? 1 : MT_TILE];
     __shared__ unsigned s_n2[MODE == 2 ? MT_TILE : 1];
     __shared__ double2 s_geo[MT_TILE];
-    const int pd = blockIdx.y, p = pd >> 1, dir = pd & 1;
-    const int fa = dir ? act_t[p] : act_s[p];
-    const int fb = dir ? act_s[p] : act_t[p];
-    const int na = nkp[fa], nb = nkp[fb];
+    const int pd = blockIdx.y;
+    const mt_dir D = mt_dir_of(act_s, act_t, pd);
+    const int fa = D.fa, fb = D.fb, na = nkp[fa], nb = nkp[fb];
     const int a = blockIdx.x * MT_TILE + threadIdx.x;
     if (blockIdx.x * MT_TILE >= na) return;                       // whole block beyond the query frame
     int32_t* out = corres_nn + (size_t)pd * kcap;
-    const double bx0 = bbox[fb * 4 + 0], bx1 = bbox[fb * 4 + 1], by0 = bbox[fb * 4 + 2], by1 = bbox[fb * 4 + 3];
+    const mt_box B = mt_box_of(bbox, fb);
     double ax = 0, ay = 0;
-    uint4 alo = make_uint4(0, 0, 0, 0), ahi = alo;
-    uint4 q[8]; unsigned qn2 = 0;
-#pragma unroll
-    for (int w = 0; w < 8; ++w) q[w] = make_uint4(0, 0, 0, 0);
+    mt_query<MODE> Q = {};
     bool live = a < na;
     if (live) {
         const double2 g = reinterpret_cast<const double2*>(geo)[(size_t)fa * kcap + a];
         ax = g.x; ay = g.y;
-        live = !(ax < bx0 || ay < by0 || ax > bx1 || ay > by1);   // FEAmatcher.cpp:84
-        if (MODE == 2) {
-            const uint4* d = reinterpret_cast<const uint4*>(desc + ((size_t)fa * kcap + a) * 128);
-#pragma unroll
-            for (int w = 0; w < 8; ++w) q[w] = d[w];
-            qn2 = dot128(q, d);
-        } else {
-            const uint4* d = reinterpret_cast<const uint4*>(desc + ((size_t)fa * kcap + a) * 32);
-            alo = d[0]; ahi = d[1];
-        }
+        live = !mt_outside(ax, ay, B);
+        Q.load(reinterpret_cast<const uint4*>(desc + ((size_t)fa * kcap + a) * DB));
     }
     if (!__syncthreads_or(live)) { if (a < na) out[a] = -1; return; }
-    int best = L2 ? 1000000 : 1000, second = best, best_id = -1, nc = 0;
-    const uint4* bdesc = reinterpret_cast<const uint4*>(desc + (size_t)fb * kcap * (MODE == 2 ? 128 : 32));
+    mt_best2 R = mt_best2::none<L2>();
+    const uint4* bdesc = reinterpret_cast<const uint4*>(desc + (size_t)fb * kcap * DB);
     const double2* bgeo = reinterpret_cast<const double2*>(geo) + (size_t)fb * kcap;
     for (int b0 = 0; b0 < nb; b0 += MT_TILE) {
         const int bj = b0 + threadIdx.x;
@@ -79,7 +152,7 @@ __global__ __launch_bounds__(MT_TILE) void match_nn_kernel(
                 uint4 t[8];
 #pragma unroll
                 for (int w = 0; w < 8; ++w) { t[w] = bdesc[8 * bj + w]; s_lo[threadIdx.x * 8 + w] = t[w]; }
-                s_n2[threadIdx.x] = dot128(t, bdesc + 8 * bj);
+                s_n2[threadIdx.x] = mt_dot(t, bdesc + 8 * bj);
             } else { s_lo[threadIdx.x] = bdesc[2 * bj]; s_hi[threadIdx.x] = bdesc[2 * bj + 1]; }
             s_geo[threadIdx.x] = bgeo[bj];
         }
@@ -92,50 +165,15 @@ __global__ __launch_bounds__(MT_TILE) void match_nn_kernel(
                 const double d2 = dx * dx + dy * dy;
                 if (d2 < gate_T) {                               // sqrt(d2) < radius, FEAmatcher.cpp:92-93
                     int d;
-                    if (MODE == 2) {
-                        d = (int)(qn2 + s_n2[j] - 2u * dot128(q, s_lo + 8 * j));
-                    } else {
-                    const uint4 lo = s_lo[j], hi = s_hi[j];
-                    if (!L2) {
-                        d = __popc(alo.x ^ lo.x) + __popc(alo.y ^ lo.y) + __popc(alo.z ^ lo.z) + __popc(alo.w ^ lo.w)
-                          + __popc(ahi.x ^ hi.x) + __popc(ahi.y ^ hi.y) + __popc(ahi.z ^ hi.z) + __popc(ahi.w ^ hi.w);
-                    } else {
-                        const unsigned wa[8] = { alo.x, alo.y, alo.z, alo.w, ahi.x, ahi.y, ahi.z, ahi.w };
-                        const unsigned wb[8] = { lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w };
-                        d = 0;
-#pragma unroll
-                        for (int w = 0; w < 8; ++w)
-#pragma unroll
-                            for (int k = 0; k < 4; ++k) {
-                                const int e = (int)((wa[w] >> (8 * k)) & 255u) - (int)((wb[w] >> (8 * k)) & 255u);
-                                d += e * e;
-                            }
-                    }
-                    }
-                    ++nc;
-                    if (d < best) { second = best; best = d; best_id = b0 + j; }
-                    else if (d < second) second = d;
+                    if constexpr (MODE == 2) d = Q.dist(s_lo + 8 * j, s_n2[j]);
+                    else d = Q.dist(s_lo[j], s_hi[j]);
+                    R.take_in_order(d, b0 + j);                  // b in index order
                 }
             }
         }
         __syncthreads();
     }
-    if (a >= na) return;
-    int res = -1;
-    if (live && nc > 0) {
-        if (!L2) {
-            const int bound = ((fa % 2) != (fb % 2)) ? bound_diff : bound_same;
-            const double r = (double)best / (double)second;
-            if (best_id != -1 && best <= bound && r <= ratio_max && second != 1000) res = best_id;
-            else if (nc == 1 && best <= bound) res = best_id;
-        } else {
-            const double bd = sqrt((double)best), sd = sqrt((double)second);   // cv::norm(NORM_L2), FEAmatcher.cpp:113
-            const double r = bd / sd;
-            if (best_id != -1 && bd < l2_bound && r <= ratio_max) res = best_id;
-            else if (nc == 1 && bd < l2_bound) res = best_id;
-        }
-    }
-    out[a] = res;
+    if (a < na) out[a] = R.template accept<L2>(fa, fb, bound_same, bound_diff, l2_bound, ratio_max);      // (a query outside the box has met no candidate)
 }
 
 // ------------------------------------------------------------------ K9 on a geo grid
@@ -209,6 +247,23 @@ __global__ __launch_bounds__(MTG_THREADS) void mt_grid_build_kernel(
 #ifndef MT_SUB
 #define MT_SUB 2                 // cells per radius: a query walks (2 MT_SUB + 1)^2 cells, 25 cells of 4 m = 400 m^2 against 9 of 8 m = 576 m^2 (the circle: 201 m^2)
 #endif
+// the rows a query at (x, y) walks in the grid of frame fb: the clamped columns c0 .. c1 of the 2 MT_SUB + 1 rows around its cell
+struct mt_rows {
+    const int* start; int W, H, cy, c0, c1;
+    // row r of the 2 MT_SUB + 1: the range [jb, je) of the sorted arrays, empty for a row outside the grid
+    __device__ __forceinline__ void range(int r, int& jb, int& je) const
+    {
+        const int row = cy - MT_SUB + r;
+        const bool ok = row >= 0 && row < H;
+        jb = ok ? start[row * W + c0] : 0; je = ok ? start[row * W + c1 + 1] : 0;
+    }
+};
+__device__ __forceinline__ mt_rows mt_rows_of(const mt_grid* __restrict__ tab, const int* __restrict__ start_all, int fb, const mt_box& B, double x, double y, double inv_cs)
+{
+    const mt_grid T = tab[fb];
+    const int cx = mt_cell(x, B.x0, inv_cs, T.W), cy = mt_cell(y, B.y0, inv_cs, T.H);
+    return { start_all + T.off, T.W, T.H, cy, max(cx - MT_SUB, 0), min(cx + MT_SUB, T.W - 1) };
+}
 template <int MODE>          // as match_nn_kernel; MODE 2 reads the 128-byte rows of the feature store through the sorted index (s_desc = the store)
 __global__ __launch_bounds__(MT_TILE) void match_grid_kernel(
     const int* __restrict__ act_s, const int* __restrict__ act_t, const int* __restrict__ nkp, const double* __restrict__ bbox,
@@ -217,40 +272,26 @@ __global__ __launch_bounds__(MT_TILE) void match_grid_kernel(
     int32_t* __restrict__ corres_nn)
 {
     constexpr bool L2 = MODE != 0;
-    const int pd = blockIdx.y, p = pd >> 1, dir = pd & 1;
-    const int fa = dir ? act_t[p] : act_s[p];
-    const int fb = dir ? act_s[p] : act_t[p];
-    const int na = nkp[fa];
+    const int pd = blockIdx.y;
+    const mt_dir D = mt_dir_of(act_s, act_t, pd);
+    const int fa = D.fa, fb = D.fb, na = nkp[fa];
     const int t = blockIdx.x * (MT_TILE / MT_LPQ) + (threadIdx.x / MT_LPQ), sub = threadIdx.x & (MT_LPQ - 1);
     if (t >= na) return;                                         // (whole groups of eight lanes leave together: the shuffles below stay inside a group)
     const size_t sa = (size_t)fa * kcap + t;
     const double2 ga = s_geo[sa];
     const int a = s_idx[sa];
     int32_t* out = corres_nn + (size_t)pd * kcap;
-    const double bx0 = bbox[fb * 4 + 0], bx1 = bbox[fb * 4 + 1], by0 = bbox[fb * 4 + 2], by1 = bbox[fb * 4 + 3];
+    const mt_box B = mt_box_of(bbox, fb);
     const double ax = ga.x, ay = ga.y;
-    if (ax < bx0 || ay < by0 || ax > bx1 || ay > by1) { if (sub == 0) out[a] = -1; return; }      // FEAmatcher.cpp:84
-    uint4 alo = make_uint4(0, 0, 0, 0), ahi = alo;
-    uint4 q[8]; unsigned qn2 = 0;
-    if (MODE == 2) {
-        const uint4* d = s_desc + ((size_t)fa * kcap + a) * 8;
-#pragma unroll
-        for (int w = 0; w < 8; ++w) q[w] = d[w];
-        qn2 = dot128(q, d);
-    } else { alo = s_desc[2 * sa]; ahi = s_desc[2 * sa + 1]; }
-    const mt_grid T = tab[fb];
-    const int* __restrict__ start = start_all + T.off;
-    const int cx = mt_cell(ax, bx0, inv_cs, T.W), cy = mt_cell(ay, by0, inv_cs, T.H);
-    const int c0 = max(cx - MT_SUB, 0), c1 = min(cx + MT_SUB, T.W - 1);
+    if (mt_outside(ax, ay, B)) { if (sub == 0) out[a] = -1; return; }
+    mt_query<MODE> Q;
+    Q.load(MODE == 2 ? s_desc + ((size_t)fa * kcap + a) * 8 : s_desc + 2 * sa);
+    const mt_rows rows = mt_rows_of(tab, start_all, fb, B, ax, ay, inv_cs);
     int jb[2 * MT_SUB + 1], je[2 * MT_SUB + 1];                  // the rows' ranges, fetched together
 #pragma unroll
-    for (int r = 0; r < 2 * MT_SUB + 1; ++r) {
-        const int row = cy - MT_SUB + r;
-        const bool ok = row >= 0 && row < T.H;
-        jb[r] = ok ? start[row * T.W + c0] : 0; je[r] = ok ? start[row * T.W + c1 + 1] : 0;
-    }
+    for (int r = 0; r < 2 * MT_SUB + 1; ++r) rows.range(r, jb[r], je[r]);
     const size_t sb = (size_t)fb * kcap;
-    int best = L2 ? 1000000 : 1000, second = best, best_id = -1, nc = 0;
+    mt_best2 R = mt_best2::none<L2>();
 #pragma unroll
     for (int r = 0; r < 2 * MT_SUB + 1; ++r)
         for (int j = jb[r] + sub; j < je[r]; j += MT_LPQ) {
@@ -260,63 +301,20 @@ __global__ __launch_bounds__(MT_TILE) void match_grid_kernel(
             if (d2 < gate_T) {                                   // sqrt(d2) < radius, FEAmatcher.cpp:92-93
                 const int id = s_idx[sb + j];
                 int d;
-                if (MODE == 2) {
+                if constexpr (MODE == 2) {
                     const uint4* bd = s_desc + (sb + id) * 8;
                     uint4 t[8];
 #pragma unroll
                     for (int w = 0; w < 8; ++w) t[w] = bd[w];
-                    d = (int)(qn2 + dot128(t, bd) - 2u * dot128(q, bd));
-                } else {
-                const uint4 lo = s_desc[2 * (sb + j)], hi = s_desc[2 * (sb + j) + 1];
-                if (!L2) {
-                    d = __popc(alo.x ^ lo.x) + __popc(alo.y ^ lo.y) + __popc(alo.z ^ lo.z) + __popc(alo.w ^ lo.w)
-                      + __popc(ahi.x ^ hi.x) + __popc(ahi.y ^ hi.y) + __popc(ahi.z ^ hi.z) + __popc(ahi.w ^ hi.w);
-                } else {
-                    const unsigned wa[8] = { alo.x, alo.y, alo.z, alo.w, ahi.x, ahi.y, ahi.z, ahi.w };
-                    const unsigned wb[8] = { lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w };
-                    d = 0;
-#pragma unroll
-                    for (int w = 0; w < 8; ++w)
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            const int e = (int)((wa[w] >> (8 * k)) & 255u) - (int)((wb[w] >> (8 * k)) & 255u);
-                            d += e * e;
-                        }
-                }
-                }
-                ++nc;
-                // the scalar loop's "first index wins" (FEAmatcher.cpp:152-161) without its order: the two smallest distances of the
-                // candidates (a tie at the minimum makes the second equal to it) and the lowest index at the minimum
-                if (d < best) { second = best; best = d; best_id = id; }
-                else if (d == best) { second = d; if (id < best_id) best_id = id; }
-                else if (d < second) second = d;
+                    d = Q.dist(bd, mt_dot(t, bd));
+                } else d = Q.dist(s_desc[2 * (sb + j)], s_desc[2 * (sb + j) + 1]);
+                R.take(d, id);                                   // cells in any order
             }
         }
-    // fold the eight lanes of the query: the two smallest of the union, the lowest index among the minima, the counts added
 #pragma unroll
-    for (int o = 1; o < MT_LPQ; o <<= 1) {
-        const int ob = __shfl_xor(best, o, 64), os = __shfl_xor(second, o, 64), oi = __shfl_xor(best_id, o, 64), on = __shfl_xor(nc, o, 64);
-        if (ob < best) { second = min(best, os); best = ob; best_id = oi; }
-        else if (ob == best) { second = best; best_id = min(best_id, oi); }      // (both -1 when nothing beat the initial value)
-        else second = min(second, ob);
-        nc += on;
-    }
-    if (sub != 0) return;
-    int res = -1;
-    if (nc > 0) {
-        if (!L2) {
-            const int bound = ((fa % 2) != (fb % 2)) ? bound_diff : bound_same;
-            const double r = (double)best / (double)second;
-            if (best_id != -1 && best <= bound && r <= ratio_max && second != 1000) res = best_id;
-            else if (nc == 1 && best <= bound) res = best_id;
-        } else {
-            const double bd = sqrt((double)best), sd = sqrt((double)second);   // cv::norm(NORM_L2), FEAmatcher.cpp:113
-            const double r = bd / sd;
-            if (best_id != -1 && bd < l2_bound && r <= ratio_max) res = best_id;
-            else if (nc == 1 && bd < l2_bound) res = best_id;
-        }
-    }
-    out[a] = res;
+    for (int o = 1; o < MT_LPQ; o <<= 1)                         // the eight lanes of the query
+        R.fold(mt_best2{ __shfl_xor(R.best, o, 64), __shfl_xor(R.second, o, 64), __shfl_xor(R.id, o, 64), __shfl_xor(R.nc, o, 64) });
+    if (sub == 0) out[a] = R.template accept<L2>(fa, fb, bound_same, bound_diff, l2_bound, ratio_max);
 }
 
 // per-kernel profile only (outside the matcher's timed scope): the gate evaluations match_grid_kernel performs = the sizes of the row
@@ -329,20 +327,15 @@ __global__ __launch_bounds__(MT_TILE) void mt_grid_count_kernel(
     __shared__ unsigned long long s_tot;
     if (threadIdx.x == 0) s_tot = 0;
     __syncthreads();
-    const int pd = blockIdx.y, p = pd >> 1, dir = pd & 1;
-    const int fa = dir ? act_t[p] : act_s[p];
-    const int fb = dir ? act_s[p] : act_t[p];
+    const mt_dir D = mt_dir_of(act_s, act_t, blockIdx.y);
     const int t = blockIdx.x * MT_TILE + threadIdx.x;
-    if (t < nkp[fa]) {
-        const double2 ga = s_geo[(size_t)fa * kcap + t];
-        const double bx0 = bbox[fb * 4 + 0], bx1 = bbox[fb * 4 + 1], by0 = bbox[fb * 4 + 2], by1 = bbox[fb * 4 + 3];
-        if (!(ga.x < bx0 || ga.y < by0 || ga.x > bx1 || ga.y > by1)) {
-            const mt_grid T = tab[fb];
-            const int* __restrict__ start = start_all + T.off;
-            const int cx = mt_cell(ga.x, bx0, inv_cs, T.W), cy = mt_cell(ga.y, by0, inv_cs, T.H);
-            const int c0 = max(cx - MT_SUB, 0), c1 = min(cx + MT_SUB, T.W - 1);
+    if (t < nkp[D.fa]) {
+        const double2 ga = s_geo[(size_t)D.fa * kcap + t];
+        const mt_box B = mt_box_of(bbox, D.fb);
+        if (!mt_outside(ga.x, ga.y, B)) {
+            const mt_rows rows = mt_rows_of(tab, start_all, D.fb, B, ga.x, ga.y, inv_cs);
             int tot = 0;
-            for (int row = max(cy - MT_SUB, 0); row <= min(cy + MT_SUB, T.H - 1); ++row) tot += start[row * T.W + c1 + 1] - start[row * T.W + c0];
+            for (int r = 0; r < 2 * MT_SUB + 1; ++r) { int jb, je; rows.range(r, jb, je); tot += je - jb; }
             atomicAdd(&s_tot, (unsigned long long)tot);
         }
     }
@@ -351,6 +344,16 @@ __global__ __launch_bounds__(MT_TILE) void mt_grid_count_kernel(
 }
 
 // ------------------------------------------------------------------ K10: SCC_x (FEAmatcher.cpp:186-248)
+// the model of hypothesis `it`: the mean of the two matches its RNG words draw (:201), summed in the reference's order
+__device__ __forceinline__ double scc_model_of(const float* xv, const uint32_t* __restrict__ rng_raw, int it, int nloc)
+{
+    const int s0 = (int)(rng_raw[2 * it] % (uint32_t)nloc), s1 = (int)(rng_raw[2 * it + 1] % (uint32_t)nloc);
+    double model = 0.0;
+    model = model + xv[s0];
+    model = model + xv[s1];
+    model = model / 2;
+    return model;
+}
 // one block per directed active pair; hypotheses are independent given the fixed cv::RNG stream (the reference
 // default-constructs the generator on every call, :59), so each lane evaluates whole hypotheses and the
 // "first strictly larger inlier set wins" rule (:237) becomes max count, then lowest iteration index.
@@ -368,10 +371,9 @@ __global__ __launch_bounds__(256) void scc_kernel(
     __shared__ int s_w[4];
     __shared__ int s_best_it, s_hist, s_nloc;
     __shared__ double s_model;
-    const int pd = blockIdx.x, p = pd >> 1, dir = pd & 1;
-    const int fa = dir ? act_t[p] : act_s[p];
-    const int fb = dir ? act_s[p] : act_t[p];
-    const int na = nkp[fa];
+    const int pd = blockIdx.x;
+    const mt_dir D = mt_dir_of(act_s, act_t, pd);
+    const int fa = D.fa, fb = D.fb, na = nkp[fa];
     const bool flip = (fa % 2) != (fb % 2);
     const float rows_ref = (float)frows[fb];
     const dsss_kp* ka = kps + (size_t)fa * kcap;
@@ -401,11 +403,7 @@ __global__ __launch_bounds__(256) void scc_kernel(
         return;
     }
     for (int it = threadIdx.x; it < iters; it += 256) {
-        const int s0 = (int)(rng_raw[2 * it] % (uint32_t)nloc), s1 = (int)(rng_raw[2 * it + 1] % (uint32_t)nloc);  // :201
-        double model = 0.0;
-        model = model + xv[s0];
-        model = model + xv[s1];
-        model = model / 2;
+        const double model = scc_model_of(xv, rng_raw, it, nloc);
         int cnt = 0;
         for (int k = 0; k < nloc; ++k) cnt += fabs(model - (double)xv[k]) <= pix_err;
         cnts[it] = cnt;
@@ -415,11 +413,7 @@ __global__ __launch_bounds__(256) void scc_kernel(
         int fin = 0, best_it = -1, hist = 0;
         for (int it = 0; it < iters; ++it) if (fin < cnts[it]) { fin = cnts[it]; best_it = it; ++hist; }   // :237-242
         s_best_it = best_it; s_hist = hist;
-        double model = 0.0;
-        if (best_it >= 0) {
-            const int s0 = (int)(rng_raw[2 * best_it] % (uint32_t)nloc), s1 = (int)(rng_raw[2 * best_it + 1] % (uint32_t)nloc);
-            model = model + xv[s0]; model = model + xv[s1]; model = model / 2;
-        }
+        const double model = best_it >= 0 ? scc_model_of(xv, rng_raw, best_it, nloc) : 0.0;
         s_model = model;
         scc_hist[pd] = hist; scc_count[pd] = fin; scc_model[pd] = model;
     }
@@ -551,11 +545,7 @@ __global__ void scan2_kernel(const int* __restrict__ a, const int* __restrict__ 
 
 __global__ void hamming_one_kernel(const uint8_t* a, const uint8_t* b, int* out)
 {
-    const uint32_t* pa = reinterpret_cast<const uint32_t*>(a);
-    const uint32_t* pb = reinterpret_cast<const uint32_t*>(b);
-    int d = 0;
-    for (int i = 0; i < 8; ++i) d += __popc(pa[i] ^ pb[i]);
-    *out = d;
+    *out = mt_hamming256(reinterpret_cast<const unsigned*>(a), reinterpret_cast<const unsigned*>(b));
 }
 
 // threshold T with sqrt(d) < radius  <=>  d < T for correctly rounded sqrt

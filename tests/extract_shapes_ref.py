@@ -89,6 +89,15 @@ def shape_class(orc, rows, cols, nlevels=1, scale=1.2):
                 nrows=[g["nrows"] for g in cells], roots=[n_roots(r, c) for r, c in lv])
 
 
+def resize_strips(sw, dw):
+    """whether a level of dw columns made from one of sw takes resize_strip_kernel (True) or the flat resize_kernel: the x table of
+    cv::resize(INTER_LINEAR) as dsss_extract.hip:resize_tables builds it (scale in double, fx in float), and the strips' condition that
+    the source columns of four consecutive output columns span at most five"""
+    fx = ((np.arange(dw) + 0.5) * (1.0 / (float(dw) / sw)) - 0.5).astype(np.float32)
+    sx = np.clip(np.floor(fx).astype(int), 0, sw - 1)
+    return bool(dw >= 8 and (sx[3:] + 1 - sx[:-3]).max() <= 5)
+
+
 def patch_inside(x, y, rows, cols):
     """orient_desc_kernel loads the 49 x 49 patch of a keypoint at level coordinates (x, y) as dwords when this holds (the last dword of a
     patch row reaches three bytes past the patch), and byte by byte through reflect-101 indices otherwise"""
@@ -120,6 +129,9 @@ SMALL_ROWS = (69, 70, 91, 92, 121, 122)
 SMALL_COLS = (70, 72, 74, 90, 92, 120, 122, 272)
 SMALL_SHAPES = [(r, c, 1, 1.2) for r in SMALL_ROWS for c in SMALL_COLS] + [(100, 100, 2, 1.1)]
 SMALL_NFEATURES = 60
+# (rows, cols, nlevels, scale, resize_strips of levels 1 ..): pyramids whose levels the flat resize_kernel makes, the smallest whose top
+# level is still a FAST cell (69 px): at 2.0 and 1.5 no level fits the strips' windows; at 1.334 one level of the frame does and the other not
+PYRAMID_SHAPES = [(278, 282, 3, 2.0, (False, False)), (158, 170, 3, 1.5, (False, False)), (124, 126, 3, 1.334, (False, True)), (124, 132, 3, 1.334, (True, False))]
 
 # (rows, cols, nlevels, nfeatures, roots of level 0)
 WIDE_SHAPES = [(69, 86, 1, 50, 1), (69, 88, 1, 50, 2), (69, 124, 1, 50, 2), (69, 126, 1, 50, 3), (69, 1234, 1, 100, 32), (69, 1236, 1, 100, 33),
@@ -223,7 +235,7 @@ def unfiltered_keypoints(orc, ref):
 def small_case(orc, rows, cols, nlevels, scale):
     raw = speckle(rows, cols, 7 * rows + cols)
     orb = dict(nfeatures=SMALL_NFEATURES, nlevels=nlevels, scale=scale)
-    return raw, orb, oracle_stages(orc, raw, SMALL_MASK, orb, key=("small", rows, cols, nlevels))
+    return raw, orb, oracle_stages(orc, raw, SMALL_MASK, orb, key=("small", rows, cols, nlevels, scale))
 
 
 def wide_case(orc, rows, cols, nlevels, nfeatures):

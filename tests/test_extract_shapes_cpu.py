@@ -41,6 +41,24 @@ def test_small_shape_table_covers_every_cell_class(orc):
     assert [w[2:4] for w in X.fast_cells(92, 92)["windows"]] == [(36, 36), (30, 36), (36, 30), (30, 30)]
 
 
+def test_pyramid_shape_table_names_the_resize_kernel_of_every_level(orc):
+    """the strips flag of every level as resize_tables derives it: the two frames the existing device test puts into one batch come out
+    as that test says, and the table holds all-flat pyramids at 2.0 and 1.5 and both orders of strips and flat at 1.334, odd level sizes
+    among them, every level with candidates"""
+    def flags(r, c, nl, sc):
+        lv = X.level_sizes(orc, r, c, X.orb_params(orc, nlevels=nl, scale=sc))
+        return tuple(X.resize_strips(lv[l - 1][1], lv[l][1]) for l in range(1, nl))
+    assert flags(500, 300, 2, 1.334) == (True,) and flags(500, 302, 2, 1.334) == (False,)
+    assert flags(501, 334, 4, 1.1) == (True, True, True) and flags(1000, 802, 4, 2.0) == (False, False, False)
+    for r, c, nl, sc, want in X.PYRAMID_SHAPES:
+        assert flags(r, c, nl, sc) == want, (r, c, sc)
+        raw, orb, ref = X.small_case(orc, r, c, nl, sc)
+        assert [lv.shape for lv in ref["levels"]] == X.level_sizes(orc, r, c, ref["op"]) and min(min(lv.shape) for lv in ref["levels"]) >= 69
+        assert all(len(cd[0]) > 0 for cd in ref["cands"]) and len(ref["kps"]) > 0, (r, c, sc)
+    assert {w for s in X.PYRAMID_SHAPES for w in s[4:]} == {(False, False), (False, True), (True, False)}
+    assert any(lv.shape[1] % 2 for s in X.PYRAMID_SHAPES for lv in X.small_case(orc, *s[:4])[2]["levels"])
+
+
 def test_wide_shape_table_covers_the_root_counts(orc):
     roots = [X.n_roots(r, c) for r, c, _, _, _ in X.WIDE_SHAPES]
     assert roots == [s[4] for s in X.WIDE_SHAPES]

@@ -76,8 +76,8 @@ def test_extract_small_orb_config_and_reuse(ctx, orc):
 
 @pytest.mark.parametrize("scale,N,M", [(2.0, 1000, 802), (1.5, 801, 598), (1.1, 501, 334)])
 def test_extract_other_scale_factors(ctx, orc, scale, N, M):
-    """pyramid scale factors other than 1.2 and odd sizes: at 2.0 the source bytes of four output pixels do not fit the
-    12-byte windows of resize_kernel and the pixel-by-pixel form runs; every level must match the oracle's byte for byte"""
+    """pyramid scale factors other than 1.2 and odd sizes: at 2.0 and 1.5 the source bytes of four output pixels do not fit the
+    12-byte windows of resize_strip_kernel and the flat form (resize_kernel) runs; every level must match the oracle's byte for byte"""
     raw, pose, alt, gr = _frame(N, M, 11, hot=False)
     mp, op, mt, pg = ctx.default_params()
     op.nfeatures = 600; op.nlevels = 4; op.scale = scale

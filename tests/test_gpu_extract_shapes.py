@@ -91,6 +91,33 @@ def test_small_frame_cell_classes(ctx, orc, rows):
             _run(ctx, orc, 0, raw, ref, "%d x %d %s" % (r, c, X.shape_class(orc, r, c, nl, sc)))
 
 
+@pytest.mark.parametrize("shape", X.PYRAMID_SHAPES, ids=lambda s: "%dx%d@%g" % (s[0], s[1], s[3]))
+def test_pyramid_levels_of_the_flat_resize(ctx, orc, shape):
+    """three levels at scale 2.0, 1.5 and 1.334 on the smallest frames whose top level is still a FAST cell: resize_kernel (the flat form)
+    makes every level at 2.0 and 1.5, and at 1.334 one level of the frame while resize_strip_kernel makes the other, in either order.
+    Every level byte for byte orc_resize_linear_u8's, then candidates, keypoints and descriptors"""
+    rows, cols, nl, sc, strips = shape
+    raw, orb, ref = X.small_case(orc, rows, cols, nl, sc)
+    with _params(ctx, X.SMALL_MASK, orb):
+        _run(ctx, orc, 0, raw, ref, "%d x %d at %g, strips %s" % (rows, cols, sc, strips))
+
+
+def test_pyramid_strips_and_flat_levels_swap_in_one_batch(ctx, orc):
+    """the two 1.334 frames of the table in ONE extract_many: at level 1 the first takes resize_kernel and the second resize_strip_kernel,
+    at level 2 the other way round -- both kernels run over the batch at both levels and each leaves the other's frame alone"""
+    shapes = [s for s in X.PYRAMID_SHAPES if s[3] == 1.334]
+    assert [s[4] for s in shapes] == [(False, True), (True, False)]
+    cases = [X.small_case(orc, *s[:4]) for s in shapes]
+    dr = [X.dr_inputs(*c[0].shape) for c in cases]
+    with _params(ctx, X.SMALL_MASK, cases[0][1]):
+        for order in ([0, 1], [1, 0]):
+            for i, (raw, _, _) in enumerate(cases): ctx.frame_set(i, raw, raw.shape[0], raw.shape[1], *dr[i])
+            ctx.extract_many(order)
+            for i in order:
+                _check_images(ctx, i, cases[i][2], "frame %d in the batch %s" % (i, order))
+                _check_features(ctx, orc, i, cases[i][2], dr[i][0], dr[i][2], "frame %d in the batch %s" % (i, order))
+
+
 @pytest.mark.parametrize("shape", X.WIDE_SHAPES, ids=lambda s: "%dx%d" % s[:2])
 def test_wide_frames_and_quadtree_roots(ctx, orc, shape):
     """1, 2, 3, 10 / 11, 32, 33 and 53 initial nodes: the stable partition by root, its pcnt bookkeeping, the passes without the pre-sort.

@@ -253,6 +253,40 @@ def _geo_grid_corner_case(ctx, orc, kind, grid, use_l2, monkeypatch):
     assert (nn >= 0).sum() > 10
 
 
+@pytest.mark.parametrize("use_l2", [0, 1])
+@pytest.mark.parametrize("grid", ["1", "0"])
+def test_first_stage_decision_table(ctx, orc, grid, use_l2, monkeypatch):
+    """every exit of the first stage's acceptance rule on designed queries (tests/matcher_decision_ref.py: nothing inside the radius, query
+    outside the other box, one candidate inside / beyond the bound, ratio passing / failing, best beyond the bound, a tie at the minimum, a
+    Hamming distance between the two parity bounds, the L2 bound either side of its strict <), through the geo grid and the all-pairs kernel,
+    Hamming and L2 on the bytes, under the default ratio and under ratio = 1 (the tie's lowest index shows).  The oracle gives exactly the
+    written table; the device gives what the oracle gives, and SCC, rows and kp7 behind it."""
+    from tests import matcher_decision_ref as D
+    monkeypatch.setenv("DSSS_MT_GRID", grid)
+    fr = D.frames(use_l2)
+    for f, a in fr.items():
+        assert len(a["kps"]) <= 8
+        ctx.frame_set(f, None, a["N"], a["M"], a["pose"], a["alt"], a["gr"])
+        ctx.features_set(f, a["N"], a["M"], a["kps"], a["desc"], geo=a["geo"], bbox=a["bb"])
+    mp, op, mt, pg = ctx.default_params()
+    try:
+        for ratio in (0.35, 1.0):
+            mt.use_l2 = use_l2; mt.ratio = ratio
+            ctx.set_params(match=mt)
+            ctx.match_pairs([0, 0], [1, 2])
+            for p, other in enumerate((1, 2)):
+                for d in (0, 1):
+                    ref = D.oracle_nn(use_l2, ratio, other, d)
+                    assert ref.tolist() == D.EXPECT[use_l2][ratio][other, d], "the oracle leaves the table (frame %d, direction %d)" % (other, d)
+                    nn = ctx.match_dir(p, d)[0][:len(ref)]
+                    print("grid %s use_l2 %d ratio %.2f pair (0, %d) dir %d: device %s" % (grid, use_l2, ratio, other, d, nn.tolist()))
+                    assert (nn == ref).all(), "first-stage CorresID differs (frame %d, direction %d)" % (other, d)
+                _check_pair(ctx, orc, p, 0, other, fr, D.params(use_l2, ratio))
+    finally:
+        mt.use_l2 = 0; mt.ratio = 0.35
+        ctx.set_params(match=mt)
+
+
 @pytest.mark.parametrize("WH", [(1, 1), (31, 33), (32, 32), (41, 25), (64, 48), (1, 2049)])
 def test_matcher_geo_grid_chunk_seams(ctx, orc, WH, monkeypatch):
     """the build of the geo grid (mt_grid_build_kernel: one workgroup scans the cell counts 1 024 cells at a time and carries the running

@@ -207,3 +207,18 @@ def test_corner_case_geometry_under_both_descriptor_rules(orc, kind, accepted, t
         multi = d["ncand"] > 1
         assert (d["nn"] >= 0).sum() == accepted[use_l2] > 10
         assert (d["best"][multi] == d["second"][multi]).sum() == ties[use_l2] > 10
+
+
+@pytest.mark.parametrize("use_l2", [0, 1])
+def test_first_stage_decision_table_is_the_oracles(orc, use_l2):
+    """tests/matcher_decision_ref.py: the written table of first-stage results is what the oracle computes, so no designed query misses its
+    exit; every exit occurs (accepted and refused in both directions of both pairs, and the ratio decides where the table says it does)"""
+    from tests import matcher_decision_ref as D
+    for ratio, by_dir in D.EXPECT[use_l2].items():
+        for (other, d), want in by_dir.items():
+            assert D.oracle_nn(use_l2, ratio, other, d).tolist() == want, (use_l2, ratio, other, d)
+    a, b = D.EXPECT[use_l2][0.35], D.EXPECT[use_l2][1.0]
+    assert [k for k in a if a[k] != b[k]] == [(1, 0), (2, 0)] and a[1, 0][6] == -1 and b[1, 0][6] == 5 and b[2, 0][4] == 2 and b[2, 0][6] == 6
+    if use_l2 == 0:                                             # 85 flipped bits: refused with ids of different parity, accepted with the same
+        assert a[1, 0][3] == -1 and a[2, 0][3] == 1
+
