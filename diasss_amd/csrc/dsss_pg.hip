@@ -113,13 +113,17 @@ struct pg_solve {
     const pg_switches sw = pg_switches_read();
     const hipStream_t st;
     // ---- the plan: ranks and partitions, edge end points, separators, the level-1 chain, segment orders
-    int world = 1, rank = 0, nparts = 1, part_lo = 0, part_hi = 1, mp0 = 0, mp1 = 0;      // a rank owns the poses [mp0, mp1)
+    int world = 1, rank = 0, nparts = 1, part_lo = 0, part_hi = 1;
+    // the two levels of the chain condensation: L0 condenses the poses onto the level-1 chain (ends sep1), L1 the level-1 chain onto the
+    // true separators (ends t2).  A rank owns the poses [mp0, mp1) -- L0's range -- and with them the level-1 nodes [L1.lo, L1.hi)
+    pg_level L0 = {}, L1 = {};
+    int &mp0 = L0.lo, &mp1 = L0.hi;
     std::vector<int> foff, pbound;
     pg_weights W;
     std::vector<int> ea, eb, eo; std::vector<pose_t> emeas; std::vector<double> ew;
     std::vector<unsigned long long> tbits; std::vector<int> tpre;
     std::vector<int> sep1, sep_pose, t2, sym_part, ord1, ord2, adj_ptr, adj_edge, lc_link;
-    int ns = 0, nseg = 0, ns1 = 0, nseg1 = 0, kp0 = 0, kp1 = 0, nf = 0, nblk = 0;
+    int ns = 0, ns1 = 0, nf = 0, nblk = 0;                              // true separators, nodes of the level-1 chain, factors
     std::vector<std::pair<int, int>> redges;
     std::vector<double> cx, cy, sxy; std::vector<unsigned long long> fp;
     static constexpr int chunk = 16;                                   // (8 and 24 reach the same optimum; measured flat in round 2)
@@ -133,9 +137,8 @@ struct pg_solve {
     // ---- the chain elimination's device arrays
     pg_dev dv;
     pose_t *d_X, *d_Xn, *d_meas, *d_emeas; int *d_ea, *d_eb, *d_eo, *d_adj_ptr, *d_adj_edge, *d_lc_link = nullptr;
-    int *d_sep, *d_sep1, *d_t2, *d_ord1, *d_ord2, *d_foff = nullptr; unsigned long long* d_fp = nullptr;
-    double *d_dr6, *d_sxy, *d_ew, *d_r, *d_Ji, *d_r2, *d_Ji2, *d_D, *d_C, *d_g, *d_delta, *d_E, *d_Dl, *d_gi, *d_sDL, *d_sDR, *d_sGL, *d_sGR, *d_sS;
-    double *d_D1, *d_C1, *d_g1, *d_E1, *d_Dl1, *d_gi1, *d_delta1, *d_s2DL, *d_s2DR, *d_s2GL, *d_s2GR, *d_s2S;
+    int *d_sep, *d_foff = nullptr; unsigned long long* d_fp = nullptr;
+    double *d_dr6, *d_sxy, *d_ew, *d_r, *d_Ji, *d_r2, *d_Ji2;
     double *d_part, *d_scal, *d_red; int* d_fail;
     // ---- the analysis tables on the device and the two schedules (this rank's fronts, the interface fronts)
     int *d_perm, *d_binperm = nullptr, *d_colptr, *d_rowidx, *d_rlptr, *d_rlcol, *d_rlpos, *d_rlrow, *d_binptr, *d_bincols, *d_dest, *d_map; long long* d_mapptr;
@@ -263,7 +266,7 @@ struct pg_solve {
         for (int v : sep_pose) mark(v);                                      // the gap fillers too
         tpre.assign(tbits.size() + 1, 0);
         for (size_t w = 0; w < tbits.size(); ++w) tpre[w + 1] = tpre[w] + __builtin_popcountll(tbits[w]);
-        ns = (int)sep_pose.size(); nseg = ns - 1;
+        ns = (int)sep_pose.size(); L1.nseg = ns - 1;
         redges.reserve((size_t)ns + ne);                                     // (the reduced edges themselves are written by the analysis thread)
         sym_part.resize(ns);
         { int p = 0; for (int k = 0; k < ns; ++k) { while (p + 1 < nparts && sep_pose[k] >= pbound[p + 1]) ++p; sym_part[k] = p; } }      // (the separators ascend: one sweep)
@@ -370,10 +373,10 @@ struct pg_solve {
             if (a <= bm) { t2.push_back((int)sep1.size()); sep1.push_back((int)a); ++it; if (a == bm) m += chunk; }
             else { sep1.push_back((int)bm); m += chunk; }
         }
-        ns1 = (int)sep1.size(); nseg1 = ns1 - 1;
+        ns1 = (int)sep1.size(); L0.nseg = ns1 - 1;
         // this rank's range of the level-1 chain (its poses are [mp0, mp1))
-        kp0 = (int)(std::lower_bound(sep1.begin(), sep1.end(), mp0) - sep1.begin()); kp1 = (int)(std::lower_bound(sep1.begin(), sep1.end(), mp1) - sep1.begin());
-        dv.later(&d_sep1, sep1); dv.later(&d_t2, t2);
+        L1.lo = (int)(std::lower_bound(sep1.begin(), sep1.end(), mp0) - sep1.begin()); L1.hi = (int)(std::lower_bound(sep1.begin(), sep1.end(), mp1) - sep1.begin());
+        dv.later(&L0.ends, sep1); dv.later(&L1.ends, t2);
         // segments of both passes in descending order of length (stable counting sort: ties stay in chain order)
         auto by_length = [](const std::vector<int>& ends, std::vector<int>& ord) {
             const int m = (int)ends.size() - 1;
@@ -386,8 +389,14 @@ struct pg_solve {
             for (int k = 0; k < m; ++k) ord[cnt[maxlen - (ends[k + 1] - ends[k])]++] = k;
         };
         by_length(sep1, ord1); by_length(t2, ord2);
-        dv.later(&d_ord1, ord1); dv.later(&d_ord2, ord2);
+        dv.later(&L0.order, ord1); dv.later(&L1.order, ord2);
         return dv.flush(c, st);                                         // level-1 chain and segment orders: one upload
+    }
+    // the device arrays of a level of the condensation: seven per node, five per segment
+    void alloc_level(pg_level& lv, size_t nodes, size_t segs) {
+        dv.alloc(c, &lv.D, nodes * 36); dv.alloc(c, &lv.C, nodes * 36); dv.alloc(c, &lv.g, nodes * 6); dv.alloc(c, &lv.delta, nodes * 6);
+        dv.alloc(c, &lv.E, nodes * 36); dv.alloc(c, &lv.Dl, nodes * 36); dv.alloc(c, &lv.gi, nodes * 6);
+        dv.alloc(c, &lv.segDL, segs * 36); dv.alloc(c, &lv.segDR, segs * 36); dv.alloc(c, &lv.segGL, segs * 6); dv.alloc(c, &lv.segGR, segs * 6); dv.alloc(c, &lv.segS, segs * 36);
     }
     // incidence lists of the poses (edge order) and the links of duplicate loop closures: only the device kernels read them, so they are
     // built while the analysis runs; then the chain's device arrays (nothing here reads S)
@@ -416,7 +425,6 @@ struct pg_solve {
             }
         }
         nf = n + ne; nblk = (nf + 255) / 256;
-        const size_t sg = std::max(nseg, 1);
         dv.alloc(c, &d_X, n); dv.alloc(c, &d_Xn, n); dv.alloc(c, &d_meas, n); dv.upload(c, &d_emeas, emeas);
         dv.upload(c, &d_ea, ea); dv.upload(c, &d_eb, eb); dv.upload(c, &d_eo, eo); dv.upload(c, &d_ew, ew);
         dv.upload(c, &d_adj_ptr, adj_ptr); dv.upload(c, &d_adj_edge, adj_edge);
@@ -425,14 +433,8 @@ struct pg_solve {
         // a second set of residuals and Jacobians: the linearisation that measures a trial's error at X (+) delta IS the next iteration's
         // linearisation when the trial is accepted (same kernel, same point, same bits) -- it writes them here and the sets swap
         dv.alloc(c, &d_r2, (size_t)nf * 6); dv.alloc(c, &d_Ji2, (size_t)nf * 36);
-        dv.alloc(c, &d_D, (size_t)n * 36); dv.alloc(c, &d_C, (size_t)n * 36); dv.alloc(c, &d_g, (size_t)n * 6); dv.alloc(c, &d_delta, (size_t)n * 6);
-        dv.alloc(c, &d_E, (size_t)n * 36); dv.alloc(c, &d_Dl, (size_t)n * 36); dv.alloc(c, &d_gi, (size_t)n * 6);
-        dv.alloc(c, &d_sDL, (size_t)nseg1 * 36); dv.alloc(c, &d_sDR, (size_t)nseg1 * 36); dv.alloc(c, &d_sGL, (size_t)nseg1 * 6);
-        dv.alloc(c, &d_sGR, (size_t)nseg1 * 6); dv.alloc(c, &d_sS, (size_t)nseg1 * 36);
-        // level-1 chain (true separators + chunk ends) and its condensation onto the true separators (pass 2)
-        dv.alloc(c, &d_D1, (size_t)ns1 * 36); dv.alloc(c, &d_C1, (size_t)ns1 * 36); dv.alloc(c, &d_g1, (size_t)ns1 * 6); dv.alloc(c, &d_delta1, (size_t)ns1 * 6);
-        dv.alloc(c, &d_E1, (size_t)ns1 * 36); dv.alloc(c, &d_Dl1, (size_t)ns1 * 36); dv.alloc(c, &d_gi1, (size_t)ns1 * 6);
-        dv.alloc(c, &d_s2DL, sg * 36); dv.alloc(c, &d_s2DR, sg * 36); dv.alloc(c, &d_s2GL, sg * 6); dv.alloc(c, &d_s2GR, sg * 6); dv.alloc(c, &d_s2S, sg * 36);
+        alloc_level(L0, n, L0.nseg);
+        alloc_level(L1, ns1, std::max(L1.nseg, 1));     // level-1 chain (true separators + chunk ends) and its condensation onto the true separators (pass 2)
         dv.alloc(c, &d_rdiag, (size_t)ns * 6);      // reciprocal diagonals of the binned columns' pivots (forward -> backward substitution)
         dv.alloc(c, &d_x, (size_t)ns * 6); dv.alloc(c, &d_part, (size_t)nblk); dv.alloc(c, &d_scal, 8); dv.alloc(c, &d_fail, 1); dv.alloc(c, &d_red, 8);
         return dv.rc;
@@ -510,10 +512,10 @@ struct pg_solve {
     void chain_part() {
         hipMemsetAsync(d_fail, 0, sizeof(int), st);
         // blocks of the ends of the level-1 chain only: pass 1 forms those of the interior poses from the Jacobians (pg_segment_kernel<true>)
-        hipLaunchKernelGGL(pg_assemble_kernel, dim3((ns1 + PG_ASM_POSES - 1) / PG_ASM_POSES), dim3(6 * PG_ASM_POSES), 0, st, n, W, d_r, d_Ji, d_adj_ptr, d_adj_edge, d_ew, d_scal + 3, d_D, d_C, d_g, d_eo, mp0, mp1, d_sep1, ns1);
-        hipLaunchKernelGGL(pg_segment_kernel<true>, dim3((nseg1 + 31) / 32), dim3(256), 0, st, nseg1, d_ord1, d_sep1, d_D, d_C, d_g, d_E, d_Dl, d_gi, d_sDL, d_sDR, d_sGL, d_sGR, d_sS, d_fail, mp0, mp1, d_r, d_Ji, W, d_scal + 3);
-        hipLaunchKernelGGL(pg_chain1_kernel, dim3((unsigned)(((long long)ns1 * 42 + 255) / 256)), dim3(256), 0, st, ns1, d_sep1, d_D, d_g, d_sDL, d_sDR, d_sGL, d_sGR, d_sS, d_D1, d_C1, d_g1, mp0, mp1);
-        if (nseg > 0) hipLaunchKernelGGL(pg_segment_kernel<false>, dim3((nseg + 31) / 32), dim3(256), 0, st, nseg, d_ord2, d_t2, d_D1, d_C1, d_g1, d_E1, d_Dl1, d_gi1, d_s2DL, d_s2DR, d_s2GL, d_s2GR, d_s2S, d_fail, kp0, kp1, (const double*)nullptr, (const double*)nullptr, W, (const double*)nullptr);
+        hipLaunchKernelGGL(pg_assemble_kernel, dim3((ns1 + PG_ASM_POSES - 1) / PG_ASM_POSES), dim3(6 * PG_ASM_POSES), 0, st, n, W, d_r, d_Ji, d_adj_ptr, d_adj_edge, d_ew, d_scal + 3, L0.D, L0.C, L0.g, d_eo, mp0, mp1, L0.ends, ns1);
+        hipLaunchKernelGGL(pg_segment_kernel<true>, dim3((L0.nseg + 31) / 32), dim3(256), 0, st, L0, d_fail, d_r, d_Ji, W, d_scal + 3);
+        hipLaunchKernelGGL(pg_chain1_kernel, dim3((unsigned)(((long long)ns1 * 42 + 255) / 256)), dim3(256), 0, st, L0, L1);
+        if (L1.nseg > 0) hipLaunchKernelGGL(pg_segment_kernel<false>, dim3((L1.nseg + 31) / 32), dim3(256), 0, st, L1, d_fail, (const double*)nullptr, (const double*)nullptr, W, (const double*)nullptr);
     }
     // First linearisation and the chain part of the first trial, before the analysis is in.  The bottom of the tree (ordering, column
     // structures, bins, update lists, destinations) is final about a millisecond before the fronts and the schedule are: with one
@@ -602,8 +604,7 @@ struct pg_solve {
     void bottom_trial(double bins_flops) {
         hipMemsetAsync(d_L, 0, nnzL * 36 * sizeof(double), st);
         if (nparts > 1) hipMemsetAsync(d_comm, 0, comm_total * sizeof(double), st);
-        hipLaunchKernelGGL(pg_scatter_base_kernel, dim3((unsigned)(((long long)ns * 78 + 255) / 256)), dim3(256), 0, st, ns, d_t2, d_perm, d_D1, d_g1, d_s2DL, d_s2DR, d_s2GL, d_s2GR, d_s2S, d_dest, d_L, d_aval, d_x,
-                           d_ifslot, d_avalif, d_xif, kp0, kp1);
+        hipLaunchKernelGGL(pg_scatter_base_kernel, dim3((unsigned)(((long long)ns * 78 + 255) / 256)), dim3(256), 0, st, L1, d_perm, d_dest, d_L, d_aval, d_x, d_ifslot, d_avalif, d_xif);
         if (ne > 0) hipLaunchKernelGGL(pg_scatter_lc_kernel, dim3((unsigned)(((long long)ne * 36 + 255) / 256)), dim3(256), 0, st, n, ne, ns, d_Ji, d_ew, d_dest, d_L, d_aval, d_avalif, d_eo, mp0, mp1, d_lc_link);
         if (nbins > 0) { dsss_scope s1(c, DSSS_K_PG_SUBTREE, bins_flops);      // flops of the binned columns
                          hipLaunchKernelGGL(sw.bins_serial ? pg_factor_subtree_serial_kernel : pg_factor_subtree_kernel, dim3(nbins), dim3(256), 0, st, d_binperm + bin_lo, d_binptr, d_bincols, d_colptr, d_rlptr, d_rlcol, d_rlpos, d_mapptr, d_map, d_L, d_x, d_fail,
@@ -772,12 +773,11 @@ struct pg_solve {
         run_levels_bwd(A.SO, DO);
         if (nbins > 0) { dsss_scope s7(c, DSSS_K_PG_SUBTREE);
             hipLaunchKernelGGL(pg_bwd_subtree_kernel, dim3(nbins), dim3(64), 0, st, d_binperm + bin_lo, d_binptr, d_bincols, d_colptr, d_rowidx, d_L, d_x, d_rdiag); }
-        hipLaunchKernelGGL(pg_sep_delta_kernel, dim3((ns + 255) / 256), dim3(256), 0, st, ns, d_t2, d_perm, d_x, d_delta1);
-        if (nseg > 0)
-            hipLaunchKernelGGL(pg_backsub_kernel<false>, dim3((nseg + 31) / 32), dim3(256), 0, st, nseg, d_ord2, d_t2, d_C1, d_E1, d_Dl1, d_gi1, d_delta1, kp0, kp1, (const double*)nullptr, W);
-        hipLaunchKernelGGL(pg_sep_delta_kernel, dim3((ns1 + 255) / 256), dim3(256), 0, st, ns1, d_sep1, (const int*)nullptr, d_delta1, d_delta);
-        hipLaunchKernelGGL(pg_backsub_kernel<true>, dim3((nseg1 + 31) / 32), dim3(256), 0, st, nseg1, d_ord1, d_sep1, d_C, d_E, d_Dl, d_gi, d_delta, mp0, mp1, d_Ji, W);
-        hipLaunchKernelGGL(pg_linerr_kernel, dim3(nblk), dim3(256), 0, st, n, ne, W, d_ea, d_eb, d_eo, d_ew, d_r, d_Ji, d_delta, d_part, mp0, mp1);
+        hipLaunchKernelGGL(pg_sep_delta_kernel, dim3((ns + 255) / 256), dim3(256), 0, st, L1, d_perm, d_x);
+        if (L1.nseg > 0) hipLaunchKernelGGL(pg_backsub_kernel<false>, dim3((L1.nseg + 31) / 32), dim3(256), 0, st, L1, (const double*)nullptr, W);
+        hipLaunchKernelGGL(pg_sep_delta_kernel, dim3((ns1 + 255) / 256), dim3(256), 0, st, L0, (const int*)nullptr, L1.delta);
+        hipLaunchKernelGGL(pg_backsub_kernel<true>, dim3((L0.nseg + 31) / 32), dim3(256), 0, st, L0, d_Ji, W);
+        hipLaunchKernelGGL(pg_linerr_kernel, dim3(nblk), dim3(256), 0, st, n, ne, W, d_ea, d_eb, d_eo, d_ew, d_r, d_Ji, L0.delta, d_part, mp0, mp1);
         hipLaunchKernelGGL(pg_final_sum_kernel, dim3(1), dim3(256), 0, st, d_part, nblk, 0.5, d_scal + 1);
         return DSSS_OK;
     }
@@ -797,8 +797,8 @@ struct pg_solve {
             for (;;) {
                 if (const int rc = trial()) return rc;
                 ++nfact;
-                // X and Xn swap between trials, so these two stay outside the captured graph
-                hipLaunchKernelGGL(pg_retract_kernel, dim3((n + 255) / 256), dim3(256), 0, st, n, d_X, d_delta, d_Xn);
+                // the trial's error at X (+) delta, into the second set: X / Xn and the sets swap when the trial is accepted
+                hipLaunchKernelGGL(pg_retract_kernel, dim3((n + 255) / 256), dim3(256), 0, st, n, d_X, L0.delta, d_Xn);
                 hipLaunchKernelGGL(pg_linearize_kernel<true>, dim3(nblk), dim3(256), 0, st, n, ne, d_Xn, d_meas, W, d_ea, d_eb, d_eo, d_emeas, d_ew, d_r2, d_Ji2, d_part, mp0, mp1);
                 hipLaunchKernelGGL(pg_final_sum_kernel, dim3(1), dim3(256), 0, st, d_part, nblk, 0.5, d_scal + 2);
                 HIPCHK(c, hipGetLastError());
@@ -895,7 +895,7 @@ __global__ __launch_bounds__(256) void lc_edge_flag_kernel(const unsigned long l
     }
     flags[g] = f;
 }
-// (lc_edge_compact_kernel, the ordered compaction behind it, sits beside its twin in dsss_pg_chain.hip)
+// (lc_edge_compact_kernel, the ordered compaction behind it, sits beside its twin in dsss_pg_init.hip)
 
 // ends != NULL (dsss_posegraph_solve, one rank): the END POINTS of the edges also come back as packed (a, b) pairs in the context's
 // page-locked buffer (*ends): the first passes of the solve (separators, partition boundaries, reduced edges) walk 8 bytes per edge

@@ -1,7 +1,9 @@
 // diasss_amd/csrc/dsss_pg_chain.hip -- the pose CHAIN of the batch LM (dsss_pg.hip): factors and their linearisation, per-pose Hessian
 // blocks, the two-level condensation of the chain onto the separators and its back-substitution, the scatter of the reduced system into
-// the factor / the fronts' value array, what the ranks pack for the all-reduce, initial values (optimizer.cpp:150-160) and the
-// trajectory rows (optimizer.cpp:1164-1214).  Everything here runs at -ffp-contract=off.
+// the factor / the fronts' value array, and what the ranks pack for the all-reduce.  (Initial values, the compactions and the
+// trajectory rows: dsss_pg_init.hip.)  Everything here runs at -ffp-contract=off: the order of the source is the order of the result, and a
+// sum that several kernels must form alike is ONE function below -- pg_jtj_row / pg_jtr (a factor's share of a pose's block row and
+// gradient) and pg_condensed (a node's block and gradient after its two segments are condensed).
 #include "dsss_pg_kernels.h"
 #include "dsss_pg_dev.h"
 // (the factors themselves -- factor_eval -- and the fixed block sum live in dsss_pg_dev.h: the report kernel of dsss_pg_report.hip evaluates the same ones)
@@ -9,12 +11,11 @@
 // LC edge (a, b) to the owner of its HIGHER pose eo = max(a, b) -- the rule the analysis builds the interface on (dsss_pg_sym.cpp:
 // "a factor belongs to the rank of its higher pose and adds to the diagonal block of the lower one").  The pipeline's own edges
 // have a < b, so eo = b there; dsss_posegraph_solve_edges also takes a > b.  Every kernel below skips what the rank does not
-// own; with one rank [mp0, mp1) is everything.
-__device__ inline bool pg_owned_factor(int k, int n, const int* __restrict__ eo, int mp0, int mp1)
-{
-    const int p = k < n ? k : eo[k - n];
-    return p >= mp0 && p < mp1;
-}
+// own; with one rank [mp0, mp1) is everything.  A SEGMENT of a level of the condensation (pg_level) belongs to the owner of its
+// first interior node, in that level's indices.
+__device__ __forceinline__ bool pg_owns(int p, int lo, int hi) { return p >= lo && p < hi; }
+__device__ inline bool pg_owned_factor(int k, int n, const int* __restrict__ eo, int mp0, int mp1) { return pg_owns(k < n ? k : eo[k - n], mp0, mp1); }
+__device__ __forceinline__ bool pg_owned_segment(const pg_level& lv, int s) { return pg_owns(lv.ends[s] + 1, lv.lo, lv.hi); }
 template <bool WJ>        // WJ: residuals AND Jacobians (r, Ji both given); otherwise the error alone (r, Ji null)
 __global__ __launch_bounds__(256) void pg_linearize_kernel(int n, int ne, const pose_t* __restrict__ X, const pose_t* __restrict__ meas,
                                                            pg_weights W, const int* __restrict__ ea, const int* __restrict__ eb, const int* __restrict__ eo,
@@ -73,40 +74,42 @@ __global__ __launch_bounds__(256) void pg_final_sum_kernel(const double* __restr
     if (threadIdx.x == 0) *out = s * scale;
 }
 
-// per-pose Hessian blocks: D (diagonal), C = H(i, i+1), g = J^T r.  LC contributions are summed over the
-// pose's incidence list in a fixed order (no atomics).  SIX LANES PER POSE: lane a builds row a of D and C and g[a] (one
-// thread per pose held 2 x 36 accumulators + a Jacobian: 280 registers, one wavefront per SIMD); the six lanes read the same
-// Jacobian, which the memory pipeline broadcasts.  Every entry is summed in the order of the one-thread form.
-// `plist` (round 5): the blocks of the np listed poses only -- the ends of the level-1 chain, whose D, C, g the chain kernels read; the
-// interior poses of the segments carry chain factors alone, and pg_segment_kernel<true> / pg_backsub_kernel<true> form their blocks
-// from the Jacobians themselves (the same sums in the same order).  NULL: every pose.
+// A factor's share of the block row of its FIRST variable, from its Jacobian J (6 x 6 row-major): ja = column a of J, sb = row a of
+// J^T J, every entry summed over q ascending; then (J^T r)[a].  pg_assemble_kernel (ends of the level-1 chain, loop closures) and
+// pg_seg_from_j (interior poses) form the blocks of the pose chain with these, so they are the same sums in the same order.
+__device__ __forceinline__ void pg_jtj_row(const double* J, int a, double* ja, double* sb)
+{
+#pragma unroll
+    for (int q = 0; q < 6; ++q) ja[q] = J[q * 6 + a];
+#pragma unroll
+    for (int q = 0; q < 6; ++q)
+#pragma unroll
+        for (int b = 0; b < 6; ++b) sb[b] += ja[q] * J[q * 6 + b];
+}
+__device__ __forceinline__ double pg_jtr(const double* ja, const double* rr)
+{
+    double s = 0;
+#pragma unroll
+    for (int q = 0; q < 6; ++q) s += ja[q] * rr[q];
+    return s;
+}
+// per-pose Hessian blocks: D (diagonal), C = H(i, i+1), g = J^T r, of the np poses of `plist` -- the ends of the level-1 chain, whose
+// D, C, g the chain kernels read; the interior poses of the segments carry chain factors alone, and pg_segment_kernel<true> /
+// pg_backsub_kernel<true> form their blocks from the Jacobians themselves.  LC contributions are summed over the pose's incidence
+// list in a fixed order (no atomics).  SIX LANES PER POSE: lane a builds row a of D and C and g[a] (one thread per pose held 2 x 36
+// accumulators + a Jacobian: 280 registers, one wavefront per SIMD); the six lanes read the same Jacobian, which the memory pipeline
+// broadcasts.  Every entry is summed in the order of the one-thread form.
 __global__ __launch_bounds__(6 * PG_ASM_POSES) void pg_assemble_kernel(int n, pg_weights W, const double* __restrict__ r, const double* __restrict__ Ji,
                                                           const int* __restrict__ adj_ptr, const int* __restrict__ adj_edge,
                                                           const double* __restrict__ ew, const double* __restrict__ lambda_ptr,
                                                           double* __restrict__ D, double* __restrict__ C, double* __restrict__ g,
                                                           const int* __restrict__ eo, int mp0, int mp1, const int* __restrict__ plist, int np)
 {
-    // (a thread's six values of a block row are 48 contiguous bytes, the threads of a wavefront 48 bytes apart: stored directly, every
-    // store instruction touched 24 cache lines for a sixth each.  The rows go through LDS and leave as 16-byte stores of whole lines.)
-    __shared__ double s_dc[2][PG_ASM_POSES * 36];
-    __shared__ double s_j[PG_ASM_POSES * 36];            // Jacobians of the chain factors i + 1 of the workgroup's poses: one contiguous 9 KB read
-    const int slot_ = blockIdx.x * PG_ASM_POSES + threadIdx.x / 6, a = threadIdx.x % 6;
-    const int i = plist ? (slot_ < np ? plist[slot_] : n) : slot_;
-    const bool live = i < n;
-    if (!plist) {
-        const size_t jb = ((size_t)blockIdx.x * PG_ASM_POSES + 1) * 36, lim = (size_t)n * 36;      // factor k lives at Ji + 36 k, k < n
-#pragma unroll
-        for (int u = 0; u < 3; ++u) {
-            const int e = 2 * (u * (6 * PG_ASM_POSES) + (int)threadIdx.x);
-            double2 v = make_double2(0.0, 0.0);
-            if (jb + e + 1 < lim) v = *reinterpret_cast<const double2*>(Ji + jb + e);
-            s_j[e] = v.x; s_j[e + 1] = v.y;
-        }
-    }
-    __syncthreads();
+    const int slot = blockIdx.x * PG_ASM_POSES + threadIdx.x / 6, a = threadIdx.x % 6;
+    if (slot >= np) return;
+    const int i = plist[slot];
     double Dd[6] = { 0, 0, 0, 0, 0, 0 }, Cc[6] = { 0, 0, 0, 0, 0, 0 }, gg = 0;
-    if (live) {
-    const bool own_i = i >= mp0 && i < mp1, own_next = i + 1 >= mp0 && i + 1 < mp1;
+    const bool own_i = pg_owns(i, mp0, mp1), own_next = pg_owns(i + 1, mp0, mp1);
     // factor i with this pose as the second variable (Jacobian W)
     const double* w2 = i == 0 ? W.prior : W.odo;
     if (own_i) {
@@ -116,24 +119,15 @@ __global__ __launch_bounds__(6 * PG_ASM_POSES) void pg_assemble_kernel(int n, pg
         gg += wa * r[(size_t)i * 6 + a];
     }
     if (i + 1 < n && own_next) {   // factor i+1 with this pose as the first variable
-        const double* J = plist ? Ji + (size_t)(i + 1) * 36 : s_j + (threadIdx.x / 6) * 36; const double* rr = r + (size_t)(i + 1) * 6;
-        double ja[6], sb[6] = { 0, 0, 0, 0, 0, 0 };            // column a of J; row a of J^T J
-#pragma unroll
-        for (int q = 0; q < 6; ++q) ja[q] = J[q * 6 + a];
-#pragma unroll
-        for (int q = 0; q < 6; ++q)
-#pragma unroll
-            for (int b = 0; b < 6; ++b) sb[b] += ja[q] * J[q * 6 + b];
+        double ja[6], sb[6] = { 0, 0, 0, 0, 0, 0 };
+        pg_jtj_row(Ji + (size_t)(i + 1) * 36, a, ja, sb);
 #pragma unroll
         for (int b = 0; b < 6; ++b) { Dd[b] += sb[b]; Cc[b] = ja[b] * W.odo[b]; }       // C = Ji^T W
-        double s = 0;
-#pragma unroll
-        for (int q = 0; q < 6; ++q) s += ja[q] * rr[q];
-        gg += s;
+        gg += pg_jtr(ja, r + (size_t)(i + 1) * 6);
     }
     for (int p = adj_ptr[i]; p < adj_ptr[i + 1]; ++p) {
         const int code = adj_edge[p], e = code >> 1, second = code & 1;
-        if (eo[e] < mp0 || eo[e] >= mp1) continue;             // the edge belongs to another rank
+        if (!pg_owns(eo[e], mp0, mp1)) continue;               // the edge belongs to another rank
         const double* rr = r + (size_t)(n + e) * 6;
         if (second) {
             const double wa = ew[(size_t)e * 6 + a];
@@ -141,20 +135,11 @@ __global__ __launch_bounds__(6 * PG_ASM_POSES) void pg_assemble_kernel(int n, pg
             for (int b = 0; b < 6; ++b) if (b == a) Dd[b] += wa * wa;
             gg += wa * rr[a];
         } else {
-            const double* J = Ji + (size_t)(n + e) * 36;
             double ja[6], sb[6] = { 0, 0, 0, 0, 0, 0 };
-#pragma unroll
-            for (int q = 0; q < 6; ++q) ja[q] = J[q * 6 + a];
-#pragma unroll
-            for (int q = 0; q < 6; ++q)
-#pragma unroll
-                for (int b = 0; b < 6; ++b) sb[b] += ja[q] * J[q * 6 + b];
+            pg_jtj_row(Ji + (size_t)(n + e) * 36, a, ja, sb);
 #pragma unroll
             for (int b = 0; b < 6; ++b) Dd[b] += sb[b];
-            double s = 0;
-#pragma unroll
-            for (int q = 0; q < 6; ++q) s += ja[q] * rr[q];
-            gg += s;
+            gg += pg_jtr(ja, rr);
         }
     }
     const double lambda = *lambda_ptr;
@@ -163,27 +148,8 @@ __global__ __launch_bounds__(6 * PG_ASM_POSES) void pg_assemble_kernel(int n, pg
         for (int b = 0; b < 6; ++b) if (b == a) Dd[b] += lambda;
     }
     g[(size_t)i * 6 + a] = gg;
-    if (plist) {                                               // scattered poses: the row straight out
 #pragma unroll
-        for (int b = 0; b < 6; ++b) { D[(size_t)i * 36 + a * 6 + b] = Dd[b]; C[(size_t)i * 36 + a * 6 + b] = Cc[b]; }
-    }
-    }       // live
-    if (plist) return;
-#pragma unroll
-    for (int b = 0; b < 6; ++b) { s_dc[0][threadIdx.x * 6 + b] = Dd[b]; s_dc[1][threadIdx.x * 6 + b] = Cc[b]; }
-    __syncthreads();
-    {   // 32 poses x 36 doubles per array = 576 pairs of doubles: three 16-byte stores per thread and array, consecutive threads consecutive pairs
-        const size_t base = (size_t)blockIdx.x * PG_ASM_POSES * 36;
-        const size_t lim = (size_t)n * 36;
-#pragma unroll
-        for (int u = 0; u < 3; ++u) {
-            const int e = 2 * (u * (6 * PG_ASM_POSES) + (int)threadIdx.x);
-            if (base + e + 1 < lim) {                        // (n * 36 is even: a pair is either inside or outside)
-                *reinterpret_cast<double2*>(D + base + e) = make_double2(s_dc[0][e], s_dc[0][e + 1]);
-                *reinterpret_cast<double2*>(C + base + e) = make_double2(s_dc[1][e], s_dc[1][e + 1]);
-            }
-        }
-    }
+    for (int b = 0; b < 6; ++b) { D[(size_t)i * 36 + a * 6 + b] = Dd[b]; C[(size_t)i * 36 + a * 6 + b] = Cc[b]; }
 }
 
 // Schur complement of the interior of segment s (poses L+1 .. R-1) onto its end points L, R (block Thomas recursion).
@@ -227,37 +193,30 @@ __device__ __forceinline__ void pg_seg_from_j(const double* __restrict__ Jl, con
         for (int u = 0; u < 5; ++u) { const int a = c + PG_SEG_LANES * u; if (a < 36) { const int row = a / 6, col = a - 6 * row; nC[u] = Jl[col * 6 + row] * Wl[col]; } }
         if (c < 6) {
             double ja[6], sb[6] = { 0, 0, 0, 0, 0, 0 };
-#pragma unroll
-            for (int q = 0; q < 6; ++q) ja[q] = Jl[q * 6 + c];
-#pragma unroll
-            for (int q = 0; q < 6; ++q)
-#pragma unroll
-                for (int b = 0; b < 6; ++b) sb[b] += ja[q] * Jl[q * 6 + b];
+            pg_jtj_row(Jl, c, ja, sb);
 #pragma unroll
             for (int b = 0; b < 6; ++b) { double d = b == c ? 0.0 + wa * wa : 0.0; d += sb[b]; if (b == c) d += lambda; pre[b] = d; }
-            double gg = 0.0 + wa * rp, s2 = 0;
-#pragma unroll
-            for (int q = 0; q < 6; ++q) s2 += ja[q] * Rn[q];
-            gpre = gg + s2;
+            const double gg = 0.0 + wa * rp;
+            gpre = gg + pg_jtr(ja, Rn);
         }
     }
 }
 template <bool FROMJ>
-__global__ __launch_bounds__(256, 2) void pg_segment_kernel(int nseg, const int* __restrict__ seg_order, const int* __restrict__ sep_pose, const double* __restrict__ D,
-                                                         const double* __restrict__ C, const double* __restrict__ g,
-                                                         double* __restrict__ E, double* __restrict__ Dl, double* __restrict__ gi,
-                                                         double* __restrict__ segDL, double* __restrict__ segDR, double* __restrict__ segGL,
-                                                         double* __restrict__ segGR, double* __restrict__ segS, int* __restrict__ fail, int mp0, int mp1,
-                                                         const double* __restrict__ rf, const double* __restrict__ Jf, pg_weights W, const double* __restrict__ lambda_ptr)
+__global__ __launch_bounds__(256, 2) void pg_segment_kernel(pg_level lv, int* __restrict__ fail, const double* __restrict__ rf, const double* __restrict__ Jf,
+                                                            pg_weights W, const double* __restrict__ lambda_ptr)
 {
+    const double* __restrict__ D = lv.D; const double* __restrict__ C = lv.C; const double* __restrict__ g = lv.g;
+    double* __restrict__ E = lv.E; double* __restrict__ Dl = lv.Dl; double* __restrict__ gi = lv.gi;
+    double* __restrict__ segDL = lv.segDL; double* __restrict__ segDR = lv.segDR; double* __restrict__ segGL = lv.segGL;
+    double* __restrict__ segGR = lv.segGR; double* __restrict__ segS = lv.segS;
     __shared__ pg_seg_lds sh_all[256 / PG_SEG_LANES];
     const int grp = threadIdx.x / PG_SEG_LANES, c = threadIdx.x % PG_SEG_LANES;
     const int slot = blockIdx.x * (256 / PG_SEG_LANES) + grp;
-    if (slot >= nseg) return;                                   // whole groups leave together
-    const int s = seg_order[slot];                              // descending length: the eight segments of a wavefront run the same number of steps
+    if (slot >= lv.nseg) return;                                // whole groups leave together
+    const int s = lv.order[slot];                               // descending length: the eight segments of a wavefront run the same number of steps
     pg_seg_lds& sh = sh_all[grp];
-    const int L = sep_pose[s], R = sep_pose[s + 1];
-    if (L + 1 < mp0 || L + 1 >= mp1) return;
+    const int L = lv.ends[s], R = lv.ends[s + 1];
+    if (!pg_owned_segment(lv, s)) return;
     if (R == L + 1) {
         for (int a = c; a < 36; a += PG_SEG_LANES) { segDL[(size_t)s * 36 + a] = 0; segDR[(size_t)s * 36 + a] = 0; segS[(size_t)s * 36 + a] = C[(size_t)L * 36 + a]; }
         if (c < 6) { segGL[(size_t)s * 6 + c] = 0; segGR[(size_t)s * 6 + c] = 0; }
@@ -428,79 +387,66 @@ __global__ __launch_bounds__(256, 2) void pg_segment_kernel(int nseg, const int*
     for (int a = c; a < 36; a += PG_SEG_LANES) { segDR[(size_t)s * 36 + a] = sh.D[cb][a]; segS[(size_t)s * 36 + a] = sh.E[cb][a]; }
     if (c < 6) segGR[(size_t)s * 6 + c] = sh.G[cb][c];
 }
-template __global__ void pg_segment_kernel<false>(int, const int* __restrict__, const int* __restrict__, const double* __restrict__, const double* __restrict__, const double* __restrict__, double* __restrict__, double* __restrict__, double* __restrict__, double* __restrict__, double* __restrict__, double* __restrict__, double* __restrict__, double* __restrict__, int* __restrict__, int, int, const double* __restrict__, const double* __restrict__, pg_weights, const double* __restrict__);
-template __global__ void pg_segment_kernel<true>(int, const int* __restrict__, const int* __restrict__, const double* __restrict__, const double* __restrict__, const double* __restrict__, double* __restrict__, double* __restrict__, double* __restrict__, double* __restrict__, double* __restrict__, double* __restrict__, double* __restrict__, double* __restrict__, int* __restrict__, int, int, const double* __restrict__, const double* __restrict__, pg_weights, const double* __restrict__);
+template __global__ void pg_segment_kernel<false>(pg_level, int* __restrict__, const double* __restrict__, const double* __restrict__, pg_weights, const double* __restrict__);
+template __global__ void pg_segment_kernel<true>(pg_level, int* __restrict__, const double* __restrict__, const double* __restrict__, pg_weights, const double* __restrict__);
 
+// Node k of a level (lv.ends[k]) once its two segments are condensed onto it: segment k - 1 ends in it and adds segDR / segGR, segment k
+// starts in it and adds segDL / segGL -- each only on the rank that owns the segment, so the value is a partial sum on an interface
+// node.  el < 36: element el of the diagonal block; otherwise component el - 36 of the gradient.
+__device__ __forceinline__ bool pg_seg_left(const pg_level& lv, int k) { return k > 0 && pg_owned_segment(lv, k - 1); }
+__device__ __forceinline__ bool pg_seg_right(const pg_level& lv, int k) { return k < lv.nseg && pg_owned_segment(lv, k); }
+__device__ __forceinline__ double pg_condensed(const pg_level& lv, int k, int el)
+{
+    const bool blk = el < 36;
+    const int w = blk ? 36 : 6, a = blk ? el : el - 36;
+    double v = (blk ? lv.D : lv.g)[(size_t)lv.ends[k] * w + a];
+    if (pg_seg_left(lv, k)) v += (blk ? lv.segDR : lv.segGR)[(size_t)(k - 1) * w + a];
+    if (pg_seg_right(lv, k)) v += (blk ? lv.segDL : lv.segGL)[(size_t)k * w + a];
+    return v;
+}
 // the level-1 chain after pass 1: diagonal block, coupling to the next entry and gradient of every chunk end / true separator
 // (what pass 2 of pg_segment_kernel condenses; same meaning as D, C, g of the pose chain).  Partial sums on interface entries.
-__global__ __launch_bounds__(256) void pg_chain1_kernel(int ns1, const int* __restrict__ sep1, const double* __restrict__ D, const double* __restrict__ g,
-                                                        const double* __restrict__ segDL, const double* __restrict__ segDR,
-                                                        const double* __restrict__ segGL, const double* __restrict__ segGR, const double* __restrict__ segS,
-                                                        double* __restrict__ D1, double* __restrict__ C1, double* __restrict__ g1, int mp0, int mp1)
+__global__ __launch_bounds__(256) void pg_chain1_kernel(pg_level lv0, pg_level lv1)
 {
+    double* __restrict__ D1 = lv1.D; double* __restrict__ C1 = lv1.C; double* __restrict__ g1 = lv1.g;
     // one thread per element (36 of D1 / C1 + 6 of g1 per node): a thread per node read its eight 288-byte rows alone (114 us)
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
     const int k = (int)(t / 42), a = (int)(t - 42LL * k);
-    if (k >= ns1) return;
-    const int p = sep1[k];
-    const bool segl = k > 0 && sep1[k - 1] + 1 >= mp0 && sep1[k - 1] + 1 < mp1, segr = k + 1 < ns1 && p + 1 >= mp0 && p + 1 < mp1;
+    if (k > lv0.nseg) return;
     if (a < 36) {
-        double v = D[(size_t)p * 36 + a];
-        if (segl) v += segDR[(size_t)(k - 1) * 36 + a];
-        if (segr) v += segDL[(size_t)k * 36 + a];
-        D1[(size_t)k * 36 + a] = v;
-        C1[(size_t)k * 36 + a] = segr ? segS[(size_t)k * 36 + a] : 0.0;
-    } else {
-        const int b = a - 36;
-        double v = g[(size_t)p * 6 + b];
-        if (segl) v += segGR[(size_t)(k - 1) * 6 + b];
-        if (segr) v += segGL[(size_t)k * 6 + b];
-        g1[(size_t)k * 6 + b] = v;
-    }
+        D1[(size_t)k * 36 + a] = pg_condensed(lv0, k, a);
+        C1[(size_t)k * 36 + a] = pg_seg_right(lv0, k) ? lv0.segS[(size_t)k * 36 + a] : 0.0;
+    } else g1[(size_t)k * 6 + a - 36] = pg_condensed(lv0, k, a);
 }
 
 // reduced system: diagonal blocks, chain couplings and right-hand side (one thread per separator, chain order).  Value index
 // k = diagonal block of separator k, ns + k = chain coupling S(k, k+1), 2 ns - 1 + e = LC edge e (dsss_pg_sym.h).  A value
 // whose destination column is binned goes straight into the block-sparse factor (dest >= 0: position << 1 | transpose); the
 // others go, untransposed, into the value array the fronts assemble from.
-__global__ __launch_bounds__(256) void pg_scatter_base_kernel(int ns, const int* __restrict__ sep_pose, const int* __restrict__ perm,
-                                                              const double* __restrict__ D, const double* __restrict__ g,
-                                                              const double* __restrict__ segDL, const double* __restrict__ segDR,
-                                                              const double* __restrict__ segGL, const double* __restrict__ segGR,
-                                                              const double* __restrict__ segS, const int* __restrict__ dest,
+__global__ __launch_bounds__(256) void pg_scatter_base_kernel(pg_level lv, const int* __restrict__ perm, const int* __restrict__ dest,
                                                               double* __restrict__ Lvals, double* __restrict__ aval, double* __restrict__ rhs,
-                                                              const int* __restrict__ if_slot, double* __restrict__ aval_if, double* __restrict__ x_if, int mp0, int mp1)
+                                                              const int* __restrict__ if_slot, double* __restrict__ aval_if, double* __restrict__ x_if)
 {
     // one thread per element: 36 of the diagonal block, 6 of the right-hand side, 36 of the coupling S(k, k+1)
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-    const int k = (int)(t / 78), el = (int)(t - 78LL * k);
+    const int k = (int)(t / 78), el = (int)(t - 78LL * k), ns = lv.nseg + 1;
     if (k >= ns) return;
-    const int p = sep_pose[k];
-    // segment k-1 ends in this separator, segment k starts in it; each belongs to the owner of its first interior pose
-    const bool segl = k > 0 && sep_pose[k - 1] + 1 >= mp0 && sep_pose[k - 1] + 1 < mp1, segr = k + 1 < ns && p + 1 >= mp0 && p + 1 < mp1;
     const int code = dest[k];
-    const bool iface = code <= -2, own = p >= mp0 && p < mp1;
+    const bool iface = code <= -2, own = pg_owns(lv.ends[k], lv.lo, lv.hi);
     if (el < 42) {
         if (!(iface || own)) return;
         // an interface separator takes a partial sum from every rank (summed by the all-reduce), an interior one is complete
         if (el < 36) {
             double* dst = code >= 0 ? Lvals + (size_t)(code >> 1) * 36 : (iface ? aval_if + (size_t)(-2 - code) * 36 : aval + (size_t)k * 36);
-            double v = D[(size_t)p * 36 + el];
-            if (segl) v += segDR[(size_t)(k - 1) * 36 + el];
-            if (segr) v += segDL[(size_t)k * 36 + el];
-            dst[el] = v;
+            dst[el] = pg_condensed(lv, k, el);
         } else {
-            const int a = el - 36;
             double* rr = iface ? x_if + (size_t)if_slot[k] * 6 : rhs + (size_t)perm[k] * 6;
-            double v = g[(size_t)p * 6 + a];
-            if (segl) v += segGR[(size_t)(k - 1) * 6 + a];
-            if (segr) v += segGL[(size_t)k * 6 + a];
-            rr[a] = -v;
+            rr[el - 36] = -pg_condensed(lv, k, el);
         }
-    } else if (segr) {     // S(k, k+1), written by the owner of segment k: the factor holds the (larger index, smaller index) block
+    } else if (pg_seg_right(lv, k)) {     // S(k, k+1), written by the owner of segment k: the factor holds the (larger index, smaller index) block
         const int e = el - 42, a = e / 6, b = e - 6 * a;
         const int cc = dest[ns + k];
-        const double* S = segS + (size_t)k * 36;
+        const double* S = lv.segS + (size_t)k * 36;
         if (cc >= 0) Lvals[(size_t)(cc >> 1) * 36 + e] = (cc & 1) ? S[b * 6 + a] : S[e];
         else (cc <= -2 ? aval_if + (size_t)(-2 - cc) * 36 : aval + (size_t)(ns + k) * 36)[e] = S[e];
     }
@@ -518,7 +464,7 @@ __global__ __launch_bounds__(256) void pg_scatter_lc_kernel(int n, int ne, int n
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;          // one thread per element of the 6 x 6 block
     const int e = (int)(t / 36), el = (int)(t - 36LL * e);
     if (e >= ne) return;
-    if (eo[e] < mp0 || eo[e] >= mp1) return;
+    if (!pg_owns(eo[e], mp0, mp1)) return;
     const int code = dest[2 * ns - 1 + e];
     if (code >= 0) {                                                        // element el of the factor's block (a group shares code >> 1)
         if (lc_link && !lc_link[2 * e]) return;
@@ -562,11 +508,12 @@ __global__ void pg_comm_scal_kernel(const double* __restrict__ scal, const int* 
     if (threadIdx.x == 3) red[3] = (double)*fail;
 }
 
-__global__ __launch_bounds__(256) void pg_sep_delta_kernel(int ns, const int* __restrict__ sep_pose, const int* __restrict__ perm,
-                                                           const double* __restrict__ x, double* __restrict__ delta)
+// the solution at the ends of a level's segments, out of x: the solver's vector through `perm`, or (perm NULL) the delta of the level above
+__global__ __launch_bounds__(256) void pg_sep_delta_kernel(pg_level lv, const int* __restrict__ perm, const double* __restrict__ x)
 {
+    const int* __restrict__ sep_pose = lv.ends; double* __restrict__ delta = lv.delta;
     const int k = blockIdx.x * 256 + threadIdx.x;
-    if (k >= ns) return;
+    if (k > lv.nseg) return;
     const int src = perm ? perm[k] : k;
     if (src < 0) return;                                     // (rank-local analysis: another rank's interior separator -- not solved here, not read here)
     for (int a = 0; a < 6; ++a) delta[(size_t)sep_pose[k] * 6 + a] = x[(size_t)src * 6 + a];
@@ -597,15 +544,15 @@ __device__ __forceinline__ void pg_bs_load(pg_bs_blk& B, int i, int aa, const do
         for (int k = 0; k <= r; ++k) B.Lm[r * (r + 1) / 2 + k] = Dl[(size_t)i * 36 + r * 6 + k];
 }
 template <bool FROMJ>
-__global__ __launch_bounds__(256) void pg_backsub_kernel(int nseg, const int* __restrict__ seg_order, const int* __restrict__ sep_pose, const double* __restrict__ C,
-                                                         const double* __restrict__ E, const double* __restrict__ Dl, const double* __restrict__ gi,
-                                                         double* __restrict__ delta, int mp0, int mp1, const double* __restrict__ Jf, pg_weights W)
+__global__ __launch_bounds__(256) void pg_backsub_kernel(pg_level lv, const double* __restrict__ Jf, pg_weights W)
 {
+    const double* __restrict__ C = lv.C; const double* __restrict__ E = lv.E; const double* __restrict__ Dl = lv.Dl;
+    const double* __restrict__ gi = lv.gi; double* __restrict__ delta = lv.delta;
     const int slot = blockIdx.x * (256 / PG_BS_LANES) + threadIdx.x / PG_BS_LANES, a = threadIdx.x % PG_BS_LANES;
-    if (slot >= nseg) return;                                   // whole groups leave together
-    const int s = seg_order[slot];                              // descending length, as in pg_segment_kernel
-    const int L = sep_pose[s], R = sep_pose[s + 1];
-    if (L + 1 < mp0 || L + 1 >= mp1 || R == L + 1) return;
+    if (slot >= lv.nseg) return;                                // whole groups leave together
+    const int s = lv.order[slot];                               // descending length, as in pg_segment_kernel
+    const int L = lv.ends[s], R = lv.ends[s + 1];
+    if (!pg_owned_segment(lv, s) || R == L + 1) return;
     const int aa = a < 6 ? a : 5;                               // lanes 6 and 7 shadow lane 5 and store nothing
     double dL[6], dn[6];
 #pragma unroll
@@ -632,8 +579,8 @@ __global__ __launch_bounds__(256) void pg_backsub_kernel(int nseg, const int* __
         cur = nxt;
     }
 }
-template __global__ void pg_backsub_kernel<false>(int, const int* __restrict__, const int* __restrict__, const double* __restrict__, const double* __restrict__, const double* __restrict__, const double* __restrict__, double* __restrict__, int, int, const double* __restrict__, pg_weights);
-template __global__ void pg_backsub_kernel<true>(int, const int* __restrict__, const int* __restrict__, const double* __restrict__, const double* __restrict__, const double* __restrict__, const double* __restrict__, double* __restrict__, int, int, const double* __restrict__, pg_weights);
+template __global__ void pg_backsub_kernel<false>(pg_level, const double* __restrict__, pg_weights);
+template __global__ void pg_backsub_kernel<true>(pg_level, const double* __restrict__, pg_weights);
 
 // 0.5 * || J delta + r ||^2 over all factors (linear.error(delta))
 __global__ __launch_bounds__(256) void pg_linerr_kernel(int n, int ne, pg_weights W, const int* __restrict__ ea, const int* __restrict__ eb, const int* __restrict__ eo,
@@ -668,159 +615,5 @@ __global__ __launch_bounds__(256) void pg_retract_kernel(int n, const pose_t* __
     pose_t o;
     pose_retract(&X[i], delta + (size_t)i * 6, &o);
     Xn[i] = o;
-}
-
-// ------------------------------------------------------------------ initial values on the device
-// std::default_random_engine (minstd_rand0, seed 1) + std::normal_distribution<double> (libstdc++ Marsaglia polar,
-// optimizer.cpp:30-31,154-158) without the sequential dependency: polar attempt a always consumes engine outputs
-// 4a+1 .. 4a+4 (two generate_canonical calls of two engine calls each), so every attempt is evaluated independently
-// after an O(log a) jump-ahead of the LCG; accepted attempts are compacted in order and each yields (y*mult, x*mult).
-__device__ inline unsigned long long minstd_pow(unsigned long long e)
-{
-    unsigned long long r = 1, b = 16807ULL;
-    const unsigned long long m = 2147483647ULL;
-    while (e) { if (e & 1) r = (r * b) % m; b = (b * b) % m; e >>= 1; }
-    return r;
-}
-__global__ __launch_bounds__(256) void pg_rng_attempts_kernel(long long nattempts, double* __restrict__ pairs, int* __restrict__ flags)
-{
-    const long long a0 = ((long long)blockIdx.x * 256 + threadIdx.x) * RNG_PER_THREAD;
-    if (a0 >= nattempts) return;
-    const unsigned long long m = 2147483647ULL;
-    unsigned long long x = minstd_pow((unsigned long long)(4 * a0));        // state after 4*a0 engine calls (seed 1)
-    const double R = 2147483646.0;
-    for (int k = 0; k < RNG_PER_THREAD && a0 + k < nattempts; ++k) {
-        double cn[2];
-        for (int q = 0; q < 2; ++q) {
-            x = (x * 16807ULL) % m; const double e1 = (double)(x - 1);
-            x = (x * 16807ULL) % m; const double e2 = (double)(x - 1);
-            double can = (e1 + e2 * R) / (R * R);
-            if (can >= 1.0) can = 0.99999999999999988897769753748;   // nextafter(1, 0)
-            cn[q] = can;
-        }
-        const double u = 2.0 * cn[0] - 1.0, v = 2.0 * cn[1] - 1.0, r2 = u * u + v * v;
-        const bool ok = !(r2 > 1.0 || r2 == 0.0);
-        double mult = 0;
-        if (ok) mult = sqrt(-2 * log(r2) / r2);
-        pairs[2 * (a0 + k)] = v * mult; pairs[2 * (a0 + k) + 1] = u * mult;
-        flags[a0 + k] = ok ? 1 : 0;
-    }
-}
-// exclusive scan of flags in three steps (block sums, scan of block sums by one block, compaction)
-__global__ __launch_bounds__(256) void pg_flag_blocksum_kernel(const int* __restrict__ flags, long long n, int* __restrict__ bsum)
-{
-    __shared__ int s_w[4];
-    const long long i0 = (long long)blockIdx.x * 4096;
-    int acc = 0;
-    for (int k = threadIdx.x; k < 4096; k += 256) if (i0 + k < n) acc += flags[i0 + k];
-    acc = dsss_wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) bsum[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-}
-__global__ __launch_bounds__(256) void pg_flag_scan_kernel(int* __restrict__ bsum, int nb, int* __restrict__ total)
-{
-    if (threadIdx.x == 0) { int run = 0; for (int i = 0; i < nb; ++i) { const int v = bsum[i]; bsum[i] = run; run += v; } *total = run; }
-}
-// the compaction of one block of 4096 flags, shared by the two kernels below: store(i, pos) for every set flag i, pos = its rank among
-// the set flags of the whole list (bsum[] holds the ranks at the block starts).  The rank so far is carried in a register.
-template <typename STORE>
-__device__ inline void pg_compact_block(const int* __restrict__ flags, long long n, const int* __restrict__ bsum, STORE store)
-{
-    __shared__ int s_w[4];
-    const long long i0 = (long long)blockIdx.x * 4096;
-    int run = bsum[blockIdx.x];
-    for (int c = 0; c < 4096; c += 256) {
-        const long long i = i0 + c + threadIdx.x;
-        const int f = (i < n) ? flags[i] : 0;
-        int tot;
-        const int pos = run + dsss_block_scan_excl<4, int>(f, &tot, s_w);
-        if (f) store(i, pos);
-        run += tot;
-    }
-}
-__global__ __launch_bounds__(256) void pg_flag_compact_kernel(const int* __restrict__ flags, const double* __restrict__ pairs, long long n,
-                                                              const int* __restrict__ bsum, long long need_pairs, double* __restrict__ normals)
-{
-    pg_compact_block(flags, n, bsum, [&](long long i, int pos) {
-        if (pos < need_pairs) { normals[2 * (size_t)pos] = pairs[2 * i]; normals[2 * (size_t)pos + 1] = pairs[2 * i + 1]; }
-    });
-}
-// edges in ascending target pose id (the reference's loop order), ordered compaction over blocks of 4096 poses
-__global__ __launch_bounds__(256) void lc_edge_compact_kernel(const int* __restrict__ flags, const int* __restrict__ bsum, const unsigned long long* __restrict__ slot,
-                                                              int total, const int* __restrict__ kp7_off, const double* __restrict__ kp7,
-                                                              const dsss_lc* __restrict__ lcs, const int* __restrict__ act_s, const int* __restrict__ frame_off,
-                                                              int cap, dsss_lc_edge* __restrict__ edges, int2* __restrict__ ab)
-{
-    pg_compact_block(flags, total, bsum, [&](long long g, int pos) {
-        if (pos >= cap) return;
-        const unsigned long long key = slot[g];
-        const int p = (int)(key >> 32) - 1, k = (int)(0xffffffffu - (unsigned)(key & 0xffffffffu));
-        const int i = kp7_off[p] + k;
-        dsss_lc_edge ed;
-        ed.a = frame_off[act_s[p]] + (int)kp7[(size_t)i * 7 + 0];
-        ed.b = (int)g;
-        for (int q = 0; q < 12; ++q) ed.rel[q] = lcs[i].rel[q];
-        for (int q = 0; q < 6; ++q) ed.var[q] = lcs[i].var[q];
-        edges[pos] = ed;
-        if (ab) ab[pos] = make_int2(ed.a, ed.b);
-    });
-}
-// DR rows of the frames (device copies kept by dsss_frame_set) into one array, frame after frame
-__global__ __launch_bounds__(256) void pg_gather_dr_kernel(const unsigned long long* __restrict__ fptr, const int* __restrict__ foff, double* __restrict__ out)
-{
-    const int f = blockIdx.y;
-    const double* __restrict__ src = reinterpret_cast<const double*>(fptr[f]);
-    const size_t n6 = (size_t)(foff[f + 1] - foff[f]) * 6;
-    double* __restrict__ dst = out + (size_t)foff[f] * 6;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n6; i += (size_t)gridDim.x * 256) dst[i] = src[i];
-}
-// poses picked out of a trajectory by index (the frozen end points of a window update)
-__global__ __launch_bounds__(256) void pg_gather_pose_kernel(int n, const int* __restrict__ idx, const pose_t* __restrict__ X, pose_t* __restrict__ out)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) out[i] = X[idx[i]];
-}
-// x, y of the separator poses (the coordinates the nested dissection bisects)
-__global__ __launch_bounds__(256) void pg_sep_xy_kernel(int ns, const int* __restrict__ sep_pose, const double* __restrict__ dr6, double* __restrict__ xy)
-{
-    const int k = blockIdx.x * 256 + threadIdx.x;
-    if (k >= ns) return;
-    xy[2 * k] = dr6[(size_t)sep_pose[k] * 6 + 3]; xy[2 * k + 1] = dr6[(size_t)sep_pose[k] * 6 + 4];
-}
-// DR poses, odometry measurements and initial estimate (optimizer.cpp:150-200)
-__global__ __launch_bounds__(256) void pg_init_kernel(int n, const double* __restrict__ dr6, const double* __restrict__ normals, int add_noise,
-                                                      pose_t* __restrict__ X, pose_t* __restrict__ meas)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const double PI = DSSS_PI_REF;
-    pose_t cur, prev, m;
-    pose_from_rodrigues(dr6 + (size_t)i * 6, &cur);
-    if (i == 0) m = cur;
-    else { pose_from_rodrigues(dr6 + (size_t)(i - 1) * 6, &prev); pose_between(&prev, &cur, &m); }
-    meas[i] = m;
-    if (add_noise) {
-        const double* z = normals + (size_t)i * 6;
-        const double noise_xyz = 0.5, noise_rpy = 0.5 * PI / 180;
-        const double w[3] = { z[0] * noise_rpy, z[1] * noise_rpy, z[2] * noise_rpy };
-        pose_t N, o;
-        so3_exp(w, N.R);
-        N.t[0] = z[3] * noise_xyz; N.t[1] = z[4] * noise_xyz; N.t[2] = z[5] * noise_xyz;
-        pose_compose(&cur, &N, &o);
-        X[i] = o;
-    } else X[i] = cur;
-}
-
-// trajectory rows "r p y x y z" of SaveTrajactoryAll (optimizer.cpp:1199-1203), computed where the poses live
-__global__ __launch_bounds__(256) void pg_rpy_kernel(int n, const pose_t* __restrict__ X, double* __restrict__ rpy6)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const pose_t T = X[i];
-    double rpy[3];
-    pose_rpy(&T, rpy);
-    double* o = rpy6 + (size_t)i * 6;
-    o[0] = rpy[0]; o[1] = rpy[1]; o[2] = rpy[2]; o[3] = T.t[0]; o[4] = T.t[1]; o[5] = T.t[2];
 }
 

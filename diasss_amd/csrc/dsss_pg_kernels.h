@@ -2,7 +2,8 @@
 // constants both sides size things with, and the kernels' declarations (a kernel is defined in ONE file and launched from dsss_pg.hip:
 // the host-side stub of a __global__ function is an ordinary external symbol, no relocatable device code is involved).
 //     dsss_pg_chain.hip    factors and linearisation, per-pose blocks, chain condensation and its back-substitution, scatter into the
-//                          reduced system, rank packing, initial values, trajectory rows
+//                          reduced system, rank packing
+//     dsss_pg_init.hip     initial values, ordered compaction (normal pairs, loop-closure edges), gathers, trajectory rows
 //     dsss_pg_bins.hip     the bottom of the elimination tree: index lists built on the device, left-looking block columns per bin
 //     dsss_pg_fronts.hip   the multifrontal top: extend-add, panel Cholesky, row solve, trailing update, back-substitution
 //     dsss_pg.hip          the solve itself (host): analysis hand-over, LM loop, loop-closure selection, the C ABI
@@ -12,6 +13,19 @@
 #include "dsss_pg_sym.h"
 
 struct pg_weights { double prior[6], odo[6]; };
+
+// One level of the chain condensation.  Its NODES form a block-tridiagonal chain (D, C = H(i, i+1), g per node); consecutive `ends`
+// (node indices, nseg + 1 of them) bound a segment, whose interior is condensed onto its two ends.  Level 0: the poses between the ends
+// of the level-1 chain; level 1: the level-1 chain between the true separators.  Per node: E (fill towards the left end), Dl (pivot
+// factors), gi (updated gradients) -- the records of the back-substitution -- and delta (the solution).  Per segment: what its
+// interior adds to the left / right end's diagonal block and gradient (segDL, segDR, segGL, segGR) and the coupling it leaves between
+// them (segS).  [lo, hi): the nodes this rank owns.  The kernels take a level by value and only read `order` and `ends`.
+struct pg_level {
+    int nseg, lo, hi;
+    int *order, *ends;                  // segments by descending length; the segments' end nodes
+    double *D, *g, *C, *E, *Dl, *gi, *delta;      // (C .. delta side by side: the back-substitution fetches them as one piece of the argument block)
+    double *segDL, *segDR, *segGL, *segGR, *segS;
+};
 
 // update matrices that cross from a rank's interior into the interface (pg_comm_pack_kernel)
 struct pg_pack { const double* U; const double* g; double* dst; int cld, cb; };
@@ -38,17 +52,18 @@ struct pg_child { const double* U; const double* g; long long relptr; int cld, c
 template <bool WJ> __global__ void pg_linearize_kernel(int n, int ne, const pose_t* __restrict__ X, const pose_t* __restrict__ meas, pg_weights W, const int* __restrict__ ea, const int* __restrict__ eb, const int* __restrict__ eo, const pose_t* __restrict__ emeas, const double* __restrict__ ew, double* __restrict__ r, double* __restrict__ Ji, double* __restrict__ partial, int mp0, int mp1);
 __global__ void pg_final_sum_kernel(const double* __restrict__ partial, int n, double scale, double* __restrict__ out);
 __global__ void pg_assemble_kernel(int n, pg_weights W, const double* __restrict__ r, const double* __restrict__ Ji, const int* __restrict__ adj_ptr, const int* __restrict__ adj_edge, const double* __restrict__ ew, const double* __restrict__ lambda_ptr, double* __restrict__ D, double* __restrict__ C, double* __restrict__ g, const int* __restrict__ eo, int mp0, int mp1, const int* __restrict__ plist, int np);
-template <bool FROMJ> __global__ void pg_segment_kernel(int nseg, const int* __restrict__ seg_order, const int* __restrict__ sep_pose, const double* __restrict__ D, const double* __restrict__ C, const double* __restrict__ g, double* __restrict__ E, double* __restrict__ Dl, double* __restrict__ gi, double* __restrict__ segDL, double* __restrict__ segDR, double* __restrict__ segGL, double* __restrict__ segGR, double* __restrict__ segS, int* __restrict__ fail, int mp0, int mp1, const double* __restrict__ rf, const double* __restrict__ Jf, pg_weights W, const double* __restrict__ lambda_ptr);
-__global__ void pg_chain1_kernel(int ns1, const int* __restrict__ sep1, const double* __restrict__ D, const double* __restrict__ g, const double* __restrict__ segDL, const double* __restrict__ segDR, const double* __restrict__ segGL, const double* __restrict__ segGR, const double* __restrict__ segS, double* __restrict__ D1, double* __restrict__ C1, double* __restrict__ g1, int mp0, int mp1);
-__global__ void pg_scatter_base_kernel(int ns, const int* __restrict__ sep_pose, const int* __restrict__ perm, const double* __restrict__ D, const double* __restrict__ g, const double* __restrict__ segDL, const double* __restrict__ segDR, const double* __restrict__ segGL, const double* __restrict__ segGR, const double* __restrict__ segS, const int* __restrict__ dest, double* __restrict__ Lvals, double* __restrict__ aval, double* __restrict__ rhs, const int* __restrict__ if_slot, double* __restrict__ aval_if, double* __restrict__ x_if, int mp0, int mp1);
+template <bool FROMJ> __global__ void pg_segment_kernel(pg_level lv, int* __restrict__ fail, const double* __restrict__ rf, const double* __restrict__ Jf, pg_weights W, const double* __restrict__ lambda_ptr);
+__global__ void pg_chain1_kernel(pg_level lv0, pg_level lv1);
+__global__ void pg_scatter_base_kernel(pg_level lv, const int* __restrict__ perm, const int* __restrict__ dest, double* __restrict__ Lvals, double* __restrict__ aval, double* __restrict__ rhs, const int* __restrict__ if_slot, double* __restrict__ aval_if, double* __restrict__ x_if);
 __global__ void pg_scatter_lc_kernel(int n, int ne, int ns, const double* __restrict__ Ji, const double* __restrict__ ew, const int* __restrict__ dest, double* __restrict__ Lvals, double* __restrict__ aval, double* __restrict__ aval_if, const int* __restrict__ eo, int mp0, int mp1, const int* __restrict__ lc_link);
 __global__ void pg_comm_pack_kernel(const int* __restrict__ it_child, const int* __restrict__ it_row, const pg_pack* __restrict__ PK);
 __global__ void pg_comm_xif_kernel(int nif, const int* __restrict__ if_sep, const int* __restrict__ perm, const double* __restrict__ x_if, double* __restrict__ x);
 __global__ void pg_comm_scal_kernel(const double* __restrict__ scal, const int* __restrict__ fail, double* __restrict__ red);
-__global__ void pg_sep_delta_kernel(int ns, const int* __restrict__ sep_pose, const int* __restrict__ perm, const double* __restrict__ x, double* __restrict__ delta);
-template <bool FROMJ> __global__ void pg_backsub_kernel(int nseg, const int* __restrict__ seg_order, const int* __restrict__ sep_pose, const double* __restrict__ C, const double* __restrict__ E, const double* __restrict__ Dl, const double* __restrict__ gi, double* __restrict__ delta, int mp0, int mp1, const double* __restrict__ Jf, pg_weights W);
+__global__ void pg_sep_delta_kernel(pg_level lv, const int* __restrict__ perm, const double* __restrict__ x);
+template <bool FROMJ> __global__ void pg_backsub_kernel(pg_level lv, const double* __restrict__ Jf, pg_weights W);
 __global__ void pg_linerr_kernel(int n, int ne, pg_weights W, const int* __restrict__ ea, const int* __restrict__ eb, const int* __restrict__ eo, const double* __restrict__ ew, const double* __restrict__ r, const double* __restrict__ Ji, const double* __restrict__ delta, double* __restrict__ partial, int mp0, int mp1);
 __global__ void pg_retract_kernel(int n, const pose_t* __restrict__ X, const double* __restrict__ delta, pose_t* __restrict__ Xn);
+// ---- dsss_pg_init.hip
 __global__ void pg_rng_attempts_kernel(long long nattempts, double* __restrict__ pairs, int* __restrict__ flags);
 __global__ void pg_flag_blocksum_kernel(const int* __restrict__ flags, long long n, int* __restrict__ bsum);
 __global__ void pg_flag_scan_kernel(int* __restrict__ bsum, int nb, int* __restrict__ total);
