@@ -60,6 +60,17 @@ class GainParams(C.Structure):
     _fields_ = [("min_count", C.c_int32), ("smooth", C.c_int32), ("target", C.c_int32), ("pad_", C.c_int32)]
 
 
+class GainBands(C.Structure):
+    """dsss_gain_bands: nbands (1..16) altitude bands of width dalt from alt0; the band of an altitude a is floor((a - alt0) / dalt),
+    held to [0, nbands - 1] (NaN and everything below alt0: band 0)"""
+    _fields_ = [("alt0", C.c_double), ("dalt", C.c_double), ("nbands", C.c_int32), ("pad_", C.c_int32)]
+
+
+def _bands(bands):
+    """a GainBands, or (alt0, dalt, nbands) -> GainBands"""
+    return bands if isinstance(bands, GainBands) else GainBands(float(bands[0]), float(bands[1]), int(bands[2]), 0)
+
+
 class CompParams(C.Structure):
     """dsss_comp_params: the priority a cell's winner is chosen by (COMP_NEAR, COMP_FAR, COMP_MID, COMP_FIRST) and the radius, in cells
     (0..4, 0: none), within which enclosed holes are filled"""
@@ -292,6 +303,18 @@ def lib():
         L.dsss_mosaic_gain_set.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.dsss_mosaic_gain_get.restype = C.c_int
         L.dsss_mosaic_gain_get.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        L.dsss_gain_band.restype = C.c_int
+        L.dsss_gain_band.argtypes = [C.POINTER(GainBands), C.c_double, C.POINTER(C.c_int32)]
+        L.dsss_mosaic_gain_stats_banded.restype = C.c_int
+        L.dsss_mosaic_gain_stats_banded.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(GainBands), C.c_void_p, C.c_void_p]
+        L.dsss_mosaic_gain_table_banded.restype = C.c_int
+        L.dsss_mosaic_gain_table_banded.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(GainParams), C.c_void_p, C.POINTER(C.c_int32)]
+        L.dsss_mosaic_gain_set_banded.restype = C.c_int
+        L.dsss_mosaic_gain_set_banded.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(GainBands)]
+        L.dsss_mosaic_gain_get_banded.restype = C.c_int
+        L.dsss_mosaic_gain_get_banded.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(GainBands)]
+        L.dsss_frame_get_corrected.restype = C.c_int
+        L.dsss_frame_get_corrected.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.dsss_reg_params_default.restype = None
         L.dsss_comp_params_default.restype = None
         L.dsss_comp_params_default.argtypes = [C.POINTER(CompParams)]
@@ -395,23 +418,47 @@ def gain_params_default():
     g = GainParams(); lib().dsss_gain_params_default(C.byref(g)); return g
 
 
-def mosaic_gain_table(sum, cnt, params=None):
+def gain_band(bands, alt):
+    """dsss_gain_band: the band of the altitude `alt` under `bands` (a GainBands or (alt0, dalt, nbands)).  Host arithmetic, no context."""
+    L = lib()
+    b = C.c_int32(-1)
+    rc = L.dsss_gain_band(C.byref(_bands(bands)) if bands is not None else None, C.c_double(alt), C.byref(b))
+    if rc != 0:
+        e = DsssError("dsss_gain_band: %s" % L.dsss_strerror(rc).decode())
+        e.code = rc
+        raise e
+    return int(b.value)
+
+
+def mosaic_gain_table(sum, cnt, params=None, nbands=None):
     """dsss_mosaic_gain_table: the column statistics S, C (M uint64 each, as Context.mosaic_gain_stats returns them) -> (gain, T): the
     range-gain table (M uint16, Q8) and the grey level it brings the columns to.  params: a GainParams, None = the defaults.
+    nbands: dsss_mosaic_gain_table_banded on S, C of nbands x M (as mosaic_gain_stats(..., bands=) returns them) -> (gain nbands x M, T).
     Host arithmetic, no context."""
     L = lib()
     if sum is not None:
         sum = np.ascontiguousarray(sum, np.uint64)
     if cnt is not None:
         cnt = np.ascontiguousarray(cnt, np.uint64)
-    M = len(sum) if sum is not None else (len(cnt) if cnt is not None else 0)
     if sum is not None and cnt is not None and sum.shape != cnt.shape:
         raise ValueError("mosaic_gain_table: %d sums and %d counts" % (sum.size, cnt.size))
-    gain = np.empty(max(M, 0), np.uint16)
+    first = sum if sum is not None else cnt
     T = C.c_int32(0)
-    rc = L.dsss_mosaic_gain_table(_ptr(sum), _ptr(cnt), int(M), C.byref(params) if params is not None else None, _ptr(gain), C.byref(T))
+    pp = C.byref(params) if params is not None else None
+    if nbands is None:
+        M = len(first) if first is not None else 0
+        gain = np.empty(max(M, 0), np.uint16)
+        rc = L.dsss_mosaic_gain_table(_ptr(sum), _ptr(cnt), int(M), pp, _ptr(gain), C.byref(T))
+        name = "dsss_mosaic_gain_table"
+    else:
+        M = first.shape[-1] if first is not None and first.ndim == 2 else 0
+        if first is not None and first.shape != (int(nbands), M):
+            raise ValueError("mosaic_gain_table: statistics of shape %s for %d bands" % (first.shape, nbands))
+        gain = np.empty((max(int(nbands), 0), M), np.uint16)
+        rc = L.dsss_mosaic_gain_table_banded(_ptr(sum), _ptr(cnt), int(M), int(nbands), pp, _ptr(gain), C.byref(T))
+        name = "dsss_mosaic_gain_table_banded"
     if rc != 0:
-        e = DsssError("dsss_mosaic_gain_table: %s (M %d)" % (L.dsss_strerror(rc).decode(), M))
+        e = DsssError("%s: %s (M %d)" % (name, L.dsss_strerror(rc).decode(), M))
         e.code = rc
         raise e
     return gain, int(T.value)
@@ -1031,26 +1078,60 @@ class Context:
                                                *[_ptr(out.get(n)) for n, _ in COMP_LAYERS], C.byref(info) if info is not None else None), "dsss_mosaic_composite")
         return out, info
 
-    def mosaic_gain_stats(self, ids, use_mask=1):
+    def mosaic_gain_stats(self, ids, use_mask=1, bands=None):
         """dsss_mosaic_gain_stats: the column statistics of the listed frames (all of one M) -> (S, C), M uint64 each: the sum and the
-        number of the kept samples of every column (use_mask != 0: the samples the filter mask keeps)"""
+        number of the kept samples of every column (use_mask != 0: the samples the filter mask keeps).  bands (a GainBands or
+        (alt0, dalt, nbands)): dsss_mosaic_gain_stats_banded -> (S, C) of nbands x M, per band of the pings' altitudes."""
         ids = np.ascontiguousarray(ids, np.int32)
         M = C.c_int(0)                                           # the columns of the first frame: the library holds every other one to it
         if len(ids):
             self._chk(self.L.dsss_frame_get_level(self.h, int(ids[0]), 0, None, None, C.byref(M)), "dsss_mosaic_gain_stats (the frame's size)")
         M = M.value
-        S = np.zeros(max(M, 1), np.uint64); Cn = np.zeros(max(M, 1), np.uint64)
-        self._chk(self.L.dsss_mosaic_gain_stats(self.h, _ptr(ids), len(ids), int(use_mask), _ptr(S), _ptr(Cn)), "dsss_mosaic_gain_stats")
-        return S[:M], Cn[:M]
+        if bands is None:
+            S = np.zeros(max(M, 1), np.uint64); Cn = np.zeros(max(M, 1), np.uint64)
+            self._chk(self.L.dsss_mosaic_gain_stats(self.h, _ptr(ids), len(ids), int(use_mask), _ptr(S), _ptr(Cn)), "dsss_mosaic_gain_stats")
+            return S[:M], Cn[:M]
+        b = _bands(bands)
+        nb = min(max(int(b.nbands), 1), 16)                     # room for what a valid call writes: the library refuses the rest
+        S = np.zeros((nb, max(M, 1)), np.uint64); Cn = np.zeros_like(S)
+        self._chk(self.L.dsss_mosaic_gain_stats_banded(self.h, _ptr(ids), len(ids), int(use_mask), C.byref(b), _ptr(S), _ptr(Cn)), "dsss_mosaic_gain_stats_banded")
+        return S.reshape(-1)[:nb * M].reshape(nb, M), Cn.reshape(-1)[:nb * M].reshape(nb, M)
 
-    def mosaic_gain_set(self, table):
+    def mosaic_gain_set(self, table, bands=None):
         """dsss_mosaic_gain_set: install the range-gain table (M uint16, Q8) every mosaic and registration entry applies from now on;
-        None clears it"""
+        None clears it.  bands (a GainBands or (alt0, dalt, nbands)): dsss_mosaic_gain_set_banded with a table of nbands x M."""
         if table is None:
             self._chk(self.L.dsss_mosaic_gain_set(self.h, None, 0), "dsss_mosaic_gain_set")
             return
         table = np.ascontiguousarray(table, np.uint16)
-        self._chk(self.L.dsss_mosaic_gain_set(self.h, _ptr(table), int(table.size)), "dsss_mosaic_gain_set")
+        if bands is None:
+            self._chk(self.L.dsss_mosaic_gain_set(self.h, _ptr(table), int(table.size)), "dsss_mosaic_gain_set")
+            return
+        b = _bands(bands)
+        if table.ndim != 2 or table.shape[0] != b.nbands:
+            raise ValueError("mosaic_gain_set: a table of shape %s for %d bands" % (table.shape, b.nbands))
+        self._chk(self.L.dsss_mosaic_gain_set_banded(self.h, _ptr(table), int(table.shape[1]), C.byref(b)), "dsss_mosaic_gain_set_banded")
+
+    def mosaic_gain_get_banded(self):
+        """dsss_mosaic_gain_get_banded: the table in force, whatever its bands, read back from the device -> (table nbands x M uint16,
+        GainBands), or None when none is set"""
+        M = C.c_int(0); b = GainBands()
+        rc = self.L.dsss_mosaic_gain_get_banded(self.h, None, 0, C.byref(M), C.byref(b))      # the size first: *M and the bands are written also without room
+        if M.value == 0:
+            self._chk(rc, "dsss_mosaic_gain_get_banded")
+            return None
+        out = np.empty((b.nbands, M.value), np.uint16)
+        self._chk(self.L.dsss_mosaic_gain_get_banded(self.h, _ptr(out), int(out.size), C.byref(M), C.byref(b)), "dsss_mosaic_gain_get_banded")
+        return out, b
+
+    def frame_corrected(self, id):
+        """dsss_frame_get_corrected: the frame's normalised image under the range-gain table in force (N x M uint8; with no table the
+        normalised image itself)"""
+        N = C.c_int(0); M = C.c_int(0)
+        self._chk(self.L.dsss_frame_get_level(self.h, int(id), 0, None, C.byref(N), C.byref(M)), "dsss_frame_get_corrected (the frame's size)")
+        out = np.empty((max(N.value, 1), max(M.value, 1)), np.uint8)
+        self._chk(self.L.dsss_frame_get_corrected(self.h, int(id), _ptr(out)), "dsss_frame_get_corrected")
+        return out
 
     def mosaic_gain_get(self, cap=None):
         """dsss_mosaic_gain_get: the table in force, read back from the device (M uint16), or None when none is set.  cap: the room

@@ -183,7 +183,8 @@ struct dsss_ctx {
     std::vector<dsss_lc_edge> pg_inc_edges; unsigned long long lc_gen = 0, pg_inc_gen = 0;    // lc_gen counts LC result sets; the last one consumed
     dsss_buf mosaic_buf{"mosaic_buf"};                                        // device scratch of dsss_mosaic_*: accumulators, output layers, job table, trajectory rows (kept between calls)
     dsss_buf mosaic_pinned{"mosaic_pinned", DSSS_PINNED};                     // page-locked landing area of the segment registration: the records of mosaic_peak_kernel, or on the host path the table of sums (140 MB at the headline size: a pageable copy into fresh memory cost more than the kernels)
-    dsss_buf mosaic_gain{"mosaic_gain"}; int mosaic_gain_M = 0;              // the range-gain table (dsss_mosaic_gain_set): M x u16 gains, Q8, on the device; M = 0: none set
+    dsss_buf mosaic_gain{"mosaic_gain"}; int mosaic_gain_M = 0;              // the range-gain table (dsss_mosaic_gain_set, _set_banded): nbands x M u16 gains, Q8, on the device; M = 0: none set
+    dsss_gain_bands mosaic_bands{0.0, 1.0, 1, 0};                             // the altitude bands of that table (dsss_mosaic_gain_set_banded): nbands rows of M gains; one band: the column table
     dsss_reg_call_info reg_info{0, 0, 0, 0};                                  // what the last registration call that returned DSSS_OK did (dsss_mosaic_register_info)
     dsss_buf pgr_buf{"pgr_buf"};                                           // device scratch of dsss_posegraph_edge_report (dsss_pg_report.hip), kept between calls
     dsss_prof prof;

@@ -176,6 +176,134 @@ __global__ __launch_bounds__(256) void mosaic_colstat_kernel(const mosaic_job* _
     }
 }
 
+// ---- altitude-banded range gain ("altitude-banded range gain" in the header)
+#define BAND_MAX 16                        // bands of a table
+
+// the workgroup's table in LDS: tab[band][sum | count][k][lane across the row], u32 -- a workgroup sees rl x COLSTAT_ROWS <= 2^15 rows
+// of a column, 2^15 x 255 < 2^32
+__device__ __forceinline__ int bandstat_slot(int tpr, int band, int what, int k, int lt) { return ((band * 2 + what) * COLSTAT_COLS + k) * tpr + lt; }
+
+// the lane's partials, which are those of `band`, into the workgroup's table (LDS atomics without return), and back to zero
+__device__ __forceinline__ void bandstat_flush(uint32_t* __restrict__ tab, int tpr, int band, int lt, uint32_t (&s)[COLSTAT_COLS], uint32_t (&n)[COLSTAT_COLS])
+{
+#pragma unroll
+    for (int k = 0; k < COLSTAT_COLS; ++k) {
+        if (n[k]) { atomicAdd(&tab[bandstat_slot(tpr, band, 0, k, lt)], s[k]); atomicAdd(&tab[bandstat_slot(tpr, band, 1, k, lt)], n[k]); }
+        s[k] = 0; n[k] = 0;
+    }
+}
+
+// colstat_words where the rows of the workgroup lie in more than one band: band[i * rl] = the band of the lane's row i.  A batch whose
+// rows all lie in the band the partials belong to (cur) goes as colstat_words' batch does; otherwise its rows go one by one, the
+// partials leaving for the table wherever the band changes.
+template <bool MASK> __device__ __forceinline__ void bandstat_words(const uint32_t* __restrict__ img, const uint32_t* __restrict__ msk, size_t M4, int row0, int row1, int rl,
+                                                                    int nmin, const uint8_t* __restrict__ band, uint32_t* __restrict__ tab, int tpr, int lt, int& cur,
+                                                                    uint32_t (&s)[COLSTAT_COLS], uint32_t (&n)[COLSTAT_COLS])
+{
+    const uint32_t* __restrict__ pi = img + (size_t)row0 * M4; const uint32_t* __restrict__ pm = msk + (size_t)row0 * M4;
+    const size_t step = (size_t)rl * M4;
+    const int nb = nmin - nmin % COLSTAT_BATCH;
+    for (int i = 0; i < nb; i += COLSTAT_BATCH) {
+        uint32_t v[COLSTAT_BATCH], m[COLSTAT_BATCH]; int b[COLSTAT_BATCH];
+        bool same = true;
+#pragma unroll
+        for (int j = 0; j < COLSTAT_BATCH; ++j) {
+            v[j] = pi[(size_t)(i + j) * step]; m[j] = MASK ? pm[(size_t)(i + j) * step] : 0u;
+            b[j] = band[(i + j) * rl]; same = same && b[j] == cur;
+        }
+        if (same) {
+#pragma unroll
+            for (int j = 0; j < COLSTAT_BATCH; ++j) colstat_add<MASK>(v[j], m[j], s, n);
+        } else {
+#pragma unroll
+            for (int j = 0; j < COLSTAT_BATCH; ++j) {
+                if (b[j] != cur) { bandstat_flush(tab, tpr, cur, lt, s, n); cur = b[j]; }
+                colstat_add<MASK>(v[j], m[j], s, n);
+            }
+        }
+    }
+    for (int i = nb, row = row0 + nb * rl; row < row1; row += rl, ++i) {
+        const int b = band[i * rl];
+        if (b != cur) { bandstat_flush(tab, tpr, cur, lt, s, n); cur = b; }
+        colstat_add<MASK>(img[(size_t)row * M4], MASK ? msk[(size_t)row * M4] : 0u, s, n);
+    }
+}
+
+// S[b][c], C[b][c] over all frames of the job table: out[b M + c] += S, out[(nbands + b) M + c] += C.  mosaic_colstat_kernel's lane
+// layout, load paths and row blocks; a job carries its frame's altitudes and the bands.  The workgroup first writes the band of each of
+// its rows into LDS (one f64 division a row, not one a lane and row) and learns with the same barrier whether they all lie in one
+// band.  If so -- the rule on real data, where the altitude moves through a band over hundreds of pings -- the lanes run colstat_words
+// itself.  Otherwise a lane keeps the partials of ONE band, that of its last row, in registers, and adds them to the workgroup's
+// table in LDS (u32 atomics without return) when its next row lies in another: a band that changes on every ping costs eight LDS atomics
+// a row and lane, and nothing global.  The table leaves through 64-bit atomics without return, only for the entries that kept a sample.
+// Integers throughout: the result depends on no order.  Dynamic LDS: nbands x 8 x tpr words and rows_wg bytes, 33 KB at most.
+__global__ __launch_bounds__(256) void mosaic_bandstat_kernel(const mosaic_job* __restrict__ jobs, int njobs, int use_mask, unsigned long long* __restrict__ out)
+{
+    extern __shared__ uint32_t s_band_dyn[];
+    const mosaic_job J = mosaic_job_of(jobs, njobs);
+    const int M = J.M, tpr = colstat_tpr(M), rl = 256 / tpr, chunks = colstat_chunks(M), rows_wg = rl * COLSTAT_ROWS, nbands = J.bands.nbands;
+    const int wg = (int)blockIdx.x - J.blk0;
+    const int rb = wg / chunks, ch = wg - rb * chunks;
+    const int lt = (int)threadIdx.x & (tpr - 1), col = (ch * tpr + lt) * COLSTAT_COLS;
+    const int rbase = rb * rows_wg, row0 = rbase + (int)threadIdx.x / tpr, row1 = min(J.N, rbase + rows_wg);
+    const int nmin = (row1 - rbase) / rl;                                          // rows every lane of the workgroup has
+    uint32_t* __restrict__ tab = s_band_dyn;
+    const int ntab = nbands * 2 * COLSTAT_COLS * tpr;
+    uint8_t* __restrict__ s_band = reinterpret_cast<uint8_t*>(s_band_dyn + ntab);
+    for (int e = (int)threadIdx.x; e < ntab; e += 256) tab[e] = 0;
+    int cur = 0, differs = 0;
+    if (nbands > 1) {                                                              // (uniform per launch; rbase < J.N with the host's blocks)
+        cur = gain_band(J.bands, J.alt[rbase]);
+        for (int r = rbase + (int)threadIdx.x; r < row1; r += 256) { const int b = gain_band(J.bands, J.alt[r]); s_band[r - rbase] = (uint8_t)b; differs |= b != cur; }
+    }
+    const bool mixed = __syncthreads_or(differs) != 0;                             // (uniform per workgroup)
+    uint32_t s[COLSTAT_COLS] = { 0, 0, 0, 0 }, n[COLSTAT_COLS] = { 0, 0, 0, 0 };
+    if (col < M) {
+        if (M % 4 == 0 && (((uintptr_t)J.img | (uintptr_t)J.mask) & 3) == 0) {
+            const uint32_t* img = reinterpret_cast<const uint32_t*>(J.img + col); const uint32_t* msk = reinterpret_cast<const uint32_t*>(J.mask + col);
+            const size_t M4 = (size_t)(M / 4);
+            if (!mixed) { if (use_mask) colstat_words<true>(img, msk, M4, row0, row1, rl, nmin, s, n); else colstat_words<false>(img, msk, M4, row0, row1, rl, nmin, s, n); }
+            else if (use_mask) bandstat_words<true>(img, msk, M4, row0, row1, rl, nmin, s_band + (row0 - rbase), tab, tpr, lt, cur, s, n);
+            else bandstat_words<false>(img, msk, M4, row0, row1, rl, nmin, s_band + (row0 - rbase), tab, tpr, lt, cur, s, n);
+        } else {
+            const int nc = min(COLSTAT_COLS, M - col);
+            for (int row = row0; row < row1; row += rl) {
+                const uint8_t* __restrict__ img = J.img + (size_t)row * M + col;
+                const uint8_t* __restrict__ msk = J.mask + (size_t)row * M + col;
+                if (mixed) { const int b = s_band[row - rbase]; if (b != cur) { bandstat_flush(tab, tpr, cur, lt, s, n); cur = b; } }
+#pragma unroll
+                for (int k = 0; k < COLSTAT_COLS; ++k) {
+                    if (k >= nc) continue;
+                    const bool keep = !use_mask || msk[k] != 0;
+                    s[k] += keep ? (uint32_t)img[k] : 0u; n[k] += keep ? 1u : 0u;
+                }
+            }
+        }
+        bandstat_flush(tab, tpr, cur, lt, s, n);
+    }
+    __syncthreads();
+    const int ncl = COLSTAT_COLS * tpr;                                            // the columns of the chunk, consecutive lanes consecutive columns
+    for (int e = (int)threadIdx.x; e < nbands * ncl; e += 256) {
+        const int b = e / ncl, cl = e - b * ncl, c = ch * ncl + cl;
+        const uint32_t cnt = tab[bandstat_slot(tpr, b, 1, cl & 3, cl >> 2)];
+        if (c >= M || cnt == 0) continue;
+        atomicAdd(&out[(size_t)b * M + c], (unsigned long long)tab[bandstat_slot(tpr, b, 0, cl & 3, cl >> 2)]);
+        atomicAdd(&out[(size_t)(nbands + b) * M + c], (unsigned long long)cnt);
+    }
+}
+
+// The corrected waterfall of one frame: a streaming pass, one workgroup per ping, the band once per ping and the gain per column through
+// mosaic_gain_apply -- the sample every entry that bins bins.  J.gain == null: the normalised image itself.
+__global__ __launch_bounds__(256) void mosaic_correct_kernel(mosaic_job J, uint8_t* __restrict__ out)
+{
+    const int row = (int)blockIdx.x, M = J.M;
+    if (row >= J.N) return;
+    const uint16_t* __restrict__ gain = mosaic_gain_row(J, row);
+    const uint8_t* __restrict__ img = J.img + (size_t)row * M;
+    uint8_t* __restrict__ o = out + (size_t)row * M;
+    for (int col = (int)threadIdx.x; col < M; col += 256) o[col] = (uint8_t)mosaic_gain_apply(img[col], gain, col);
+}
+
 } // namespace
 
 // ---- host helpers shared with dsss_mosaic_reg.hip (dsss_mosaic_int.h)
@@ -315,7 +443,7 @@ int mosaic_fill_jobs(dsss_ctx* c, const int* ids, int n, const double* rpy6, con
     rc = upload_rows(c, ids, n, rpy6, ping_off, d_rows, dev_rows); if (rc) return rc;
     const uint16_t* gain = c->mosaic_gain_M ? c->mosaic_gain.as<uint16_t>() : nullptr;
     jobs.resize(n);
-    for (int i = 0; i < n; ++i) { const dsss_frame& f = c->frames[ids[i]]; jobs[i] = mosaic_job{ dev_rows[i], f.gr, f.lvl[0], f.mask, gain, f.N, f.M, 0, 0 }; }
+    for (int i = 0; i < n; ++i) { const dsss_frame& f = c->frames[ids[i]]; jobs[i] = mosaic_job{ dev_rows[i], f.gr, f.lvl[0], f.mask, gain, f.N, f.M, 0, 0, f.alt, gain ? c->mosaic_bands : dsss_gain_bands{ 0.0, 1.0, 1, 0 } }; }
     return DSSS_OK;
 }
 
@@ -411,38 +539,80 @@ int dsss_mosaic_render(dsss_ctx* c, const int* ids, int n, const double* rpy6, c
 // ---- range-gain normalisation
 void dsss_gain_params_default(dsss_gain_params* p) { if (p) { p->min_count = 256; p->smooth = 0; p->target = 0; p->pad_ = 0; } }
 
-int dsss_mosaic_gain_stats(dsss_ctx* c, const int* ids, int n, int use_mask, uint64_t* sum_host, uint64_t* cnt_host)
+// the argument rules of the two statistics entries; *M = the columns of the listed frames
+static int gain_stats_check(dsss_ctx* c, const int* ids, int n, const uint64_t* sum_host, const uint64_t* cnt_host, int* M)
 {
-    if (!c) return DSSS_E_ARG;
     if (!sum_host || !cnt_host) DSSS_FAIL(c, DSSS_E_ARG, "gain: nowhere to write the column %s", sum_host ? "counts" : "sums");
     size_t rows = 0;
     int rc = mosaic_check_frames(c, ids, n, nullptr, nullptr, true, &rows); if (rc) return rc;
-    const int M = c->frames[ids[0]].M;
-    if (M < 2) DSSS_FAIL(c, DSSS_E_ARG, "gain: frames of %d columns", M);
+    *M = c->frames[ids[0]].M;
+    if (*M < 2) DSSS_FAIL(c, DSSS_E_ARG, "gain: frames of %d columns", *M);
     for (int i = 1; i < n; ++i)
-        if (c->frames[ids[i]].M != M) DSSS_FAIL(c, DSSS_E_ARG, "gain: frame %d has %d columns, frame %d has %d", ids[0], M, ids[i], c->frames[ids[i]].M);
+        if (c->frames[ids[i]].M != *M) DSSS_FAIL(c, DSSS_E_ARG, "gain: frame %d has %d columns, frame %d has %d", ids[0], *M, ids[i], c->frames[ids[i]].M);
+    return DSSS_OK;
+}
+
+static bool gain_bands_ok(const dsss_gain_bands* b)
+{
+    return b && b->nbands >= 1 && b->nbands <= BAND_MAX && std::isfinite(b->alt0) && std::isfinite(b->dalt) && b->dalt > 0.0;
+}
+
+// The statistics of the listed frames, bands == null: per column (mosaic_colstat_kernel), otherwise per band and column
+// (mosaic_bandstat_kernel): the one job table, launch shape and download of both entries.  The statistics are those of the uncorrected
+// samples whatever table is set: the jobs carry the images, and the frame's altitudes with the caller's bands, alone.
+static int gain_stats_run(dsss_ctx* c, const int* ids, int n, int use_mask, const dsss_gain_bands* bands, int M, uint64_t* sum_host, uint64_t* cnt_host)
+{
     HIPCHK(c, hipSetDevice(c->device));
+    const size_t entries = (size_t)M * (bands ? bands->nbands : 1);
     mosaic_arena A;
-    const auto o_out = A.take<unsigned long long>((size_t)M * 2); const auto o_jobs = A.take<mosaic_job>(n);
-    rc = A.reserve(c); if (rc) return rc;
+    const auto o_out = A.take<unsigned long long>(entries * 2); const auto o_jobs = A.take<mosaic_job>(n);
+    int rc = A.reserve(c); if (rc) return rc;
     unsigned long long* d_out = A.at(o_out); mosaic_job* d_jobs = A.at(o_jobs);
-    // the statistics are those of the uncorrected samples whatever table is set: the jobs carry the images alone
     std::vector<mosaic_job> jobs(n);
-    const int chunks = colstat_chunks(M), rows_wg = (256 / colstat_tpr(M)) * COLSTAT_ROWS;
+    const int tpr = colstat_tpr(M), chunks = colstat_chunks(M), rows_wg = (256 / tpr) * COLSTAT_ROWS;
     long long blocks = 0;
     for (int i = 0; i < n; ++i) {
         const dsss_frame& f = c->frames[ids[i]];
         jobs[i] = mosaic_job{ nullptr, nullptr, f.lvl[0], f.mask, nullptr, f.N, f.M, (int)blocks, 0 };
+        if (bands) { jobs[i].alt = f.alt; jobs[i].bands = *bands; }
         blocks += (long long)chunks * ((f.N + rows_wg - 1) / rows_wg);
     }
     if (blocks > 0x7fffffffll) DSSS_FAIL(c, DSSS_E_ARG, "gain: %d frames of %d columns are more than one launch takes", n, M);
     HIPCHK(c, hipMemcpyAsync(d_jobs, jobs.data(), (size_t)n * sizeof(mosaic_job), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(d_out, 0, (size_t)M * 16, c->stream));
-    if (blocks) hipLaunchKernelGGL(mosaic_colstat_kernel, dim3((unsigned)blocks), dim3(256), 0, c->stream, d_jobs, n, use_mask != 0, d_out);
+    HIPCHK(c, hipMemsetAsync(d_out, 0, entries * 16, c->stream));
+    if (blocks && !bands) hipLaunchKernelGGL(mosaic_colstat_kernel, dim3((unsigned)blocks), dim3(256), 0, c->stream, d_jobs, n, use_mask != 0, d_out);
+    if (blocks && bands) {
+        const size_t lds = ((size_t)bands->nbands * 2 * COLSTAT_COLS * tpr) * sizeof(uint32_t) + (size_t)rows_wg;      // the table, then a band per row
+        hipLaunchKernelGGL(mosaic_bandstat_kernel, dim3((unsigned)blocks), dim3(256), lds, c->stream, d_jobs, n, use_mask != 0, d_out);
+    }
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(sum_host, d_out, (size_t)M * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(cnt_host, d_out + M, (size_t)M * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(sum_host, d_out, entries * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(cnt_host, d_out + entries, entries * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return DSSS_OK;
+}
+
+int dsss_mosaic_gain_stats(dsss_ctx* c, const int* ids, int n, int use_mask, uint64_t* sum_host, uint64_t* cnt_host)
+{
+    if (!c) return DSSS_E_ARG;
+    int M = 0;
+    const int rc = gain_stats_check(c, ids, n, sum_host, cnt_host, &M); if (rc) return rc;
+    return gain_stats_run(c, ids, n, use_mask, nullptr, M, sum_host, cnt_host);
+}
+
+int dsss_mosaic_gain_stats_banded(dsss_ctx* c, const int* ids, int n, int use_mask, const dsss_gain_bands* bands, uint64_t* sum_host, uint64_t* cnt_host)
+{
+    if (!c) return DSSS_E_ARG;
+    if (!gain_bands_ok(bands)) DSSS_FAIL(c, DSSS_E_ARG, "gain: bands %s", bands ? "outside the rules (nbands 1..16, alt0 and dalt finite, dalt > 0)" : "missing");
+    int M = 0;
+    const int rc = gain_stats_check(c, ids, n, sum_host, cnt_host, &M); if (rc) return rc;
+    return gain_stats_run(c, ids, n, use_mask, bands, M, sum_host, cnt_host);
+}
+
+int dsss_gain_band(const dsss_gain_bands* bands, double alt, int32_t* band)
+{
+    if (!gain_bands_ok(bands) || !band) return DSSS_E_ARG;
+    *band = gain_band(*bands, alt);
     return DSSS_OK;
 }
 
@@ -478,19 +648,75 @@ int dsss_mosaic_gain_table(const uint64_t* sum, const uint64_t* cnt, int M, cons
     return DSSS_OK;
 }
 
+int dsss_mosaic_gain_table_banded(const uint64_t* sum, const uint64_t* cnt, int M, int nbands, const dsss_gain_params* gp, uint16_t* gain_q8, int32_t* target_out)
+{
+    dsss_gain_params P;
+    dsss_gain_params_default(&P);
+    if (gp) P = *gp;
+    if (!sum || !cnt || !gain_q8 || M < 2 || nbands < 1 || nbands > BAND_MAX) return DSSS_E_ARG;
+    std::vector<uint64_t> Sp(M, 0), Cp(M, 0);
+    for (int b = 0; b < nbands; ++b)
+        for (int c = 0; c < M; ++c) { Sp[c] += sum[(size_t)b * M + c]; Cp[c] += cnt[(size_t)b * M + c]; }
+    std::vector<uint16_t> pooled(M);
+    int32_t Tp = 0;
+    const int rc = dsss_mosaic_gain_table(Sp.data(), Cp.data(), M, &P, pooled.data(), &Tp); if (rc) return rc;      // (the parameter rules are its)
+    typedef unsigned __int128 u128;
+    const int half = M / 2;
+    const u128 T = (u128)Tp;
+    for (int b = 0; b < nbands; ++b) {
+        const uint64_t* S = sum + (size_t)b * M; const uint64_t* C = cnt + (size_t)b * M;
+        for (int c = 0; c < M; ++c) {
+            const int lo = std::max(c - P.smooth, c < half ? 0 : half), hi = std::min(c + P.smooth, c < half ? half - 1 : M - 1);      // never across the nadir
+            u128 s = 0, n = 0;
+            for (int k = lo; k <= hi; ++k) { s += S[k]; n += C[k]; }
+            if (!(n >= (u128)P.min_count && s > 0 && T > 0)) { gain_q8[(size_t)b * M + c] = pooled[c]; continue; }      // a thin band: the pooled column
+            const u128 g = (T * n * 256 + s / 2) / s;
+            gain_q8[(size_t)b * M + c] = g > 65535 ? (uint16_t)65535 : (uint16_t)g;
+        }
+    }
+    if (target_out) *target_out = Tp;
+    return DSSS_OK;
+}
+
 // The new table goes into a block of its own and takes the old one's place only after its upload succeeded: an error leaves the old
 // table in force.  (Every entry that reads the table synchronises before it returns, so no queued kernel still reads the old block.)
+static int gain_install(dsss_ctx* c, const uint16_t* gain_q8_host, int M, const dsss_gain_bands& bands)
+{
+    if (!gain_q8_host) { c->mosaic_gain_M = 0; c->mosaic_bands = dsss_gain_bands{ 0.0, 1.0, 1, 0 }; return DSSS_OK; }
+    if (M < 2) DSSS_FAIL(c, DSSS_E_ARG, "gain: a table of %d columns", M);
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t bytes = (size_t)M * bands.nbands * sizeof(uint16_t);
+    dsss_buf nb{"mosaic_gain"};
+    const int rc = nb.reserve(c, bytes); if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(nb.p, gain_q8_host, bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->mosaic_gain = std::move(nb); c->mosaic_gain_M = M; c->mosaic_bands = bands; c->mosaic_bands.pad_ = 0;
+    return DSSS_OK;
+}
+
 int dsss_mosaic_gain_set(dsss_ctx* c, const uint16_t* gain_q8_host, int M)
 {
     if (!c) return DSSS_E_ARG;
-    if (!gain_q8_host) { c->mosaic_gain_M = 0; return DSSS_OK; }
-    if (M < 2) DSSS_FAIL(c, DSSS_E_ARG, "gain: a table of %d columns", M);
+    return gain_install(c, gain_q8_host, M, dsss_gain_bands{ 0.0, 1.0, 1, 0 });
+}
+
+int dsss_mosaic_gain_set_banded(dsss_ctx* c, const uint16_t* gain_q8_host, int M, const dsss_gain_bands* bands)
+{
+    if (!c) return DSSS_E_ARG;
+    if (!gain_q8_host) return gain_install(c, nullptr, 0, dsss_gain_bands{ 0.0, 1.0, 1, 0 });
+    if (!gain_bands_ok(bands)) DSSS_FAIL(c, DSSS_E_ARG, "gain: bands %s", bands ? "outside the rules (nbands 1..16, alt0 and dalt finite, dalt > 0)" : "missing");
+    return gain_install(c, gain_q8_host, M, *bands);
+}
+
+// the table in force, all its bands, read back from the device copy
+static int gain_download(dsss_ctx* c, uint16_t* gain_q8_host, int cap)
+{
+    const long long need = (long long)c->mosaic_gain_M * c->mosaic_bands.nbands;
+    if (!gain_q8_host || cap < need)
+        DSSS_FAIL(c, DSSS_E_ARG, "gain: a table of %d bands x %d columns, room for %d gains", c->mosaic_bands.nbands, c->mosaic_gain_M, gain_q8_host ? cap : 0);
     HIPCHK(c, hipSetDevice(c->device));
-    dsss_buf nb{"mosaic_gain"};
-    const int rc = nb.reserve(c, (size_t)M * sizeof(uint16_t)); if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(nb.p, gain_q8_host, (size_t)M * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(gain_q8_host, c->mosaic_gain.p, (size_t)need * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->mosaic_gain = std::move(nb); c->mosaic_gain_M = M;
     return DSSS_OK;
 }
 
@@ -498,11 +724,40 @@ int dsss_mosaic_gain_get(dsss_ctx* c, uint16_t* gain_q8_host, int cap, int* M)
 {
     if (!c) return DSSS_E_ARG;
     if (!M) DSSS_FAIL(c, DSSS_E_ARG, "gain: nowhere to write the number of columns");
+    if (c->mosaic_gain_M && c->mosaic_bands.nbands > 1)
+        DSSS_FAIL(c, DSSS_E_STATE, "gain: a table of %d bands is set (dsss_mosaic_gain_get_banded reads it)", c->mosaic_bands.nbands);
     *M = c->mosaic_gain_M;                                                      // also when there is no room for them: the caller learns how many
     if (!c->mosaic_gain_M) return DSSS_OK;
-    if (!gain_q8_host || cap < c->mosaic_gain_M) DSSS_FAIL(c, DSSS_E_ARG, "gain: a table of %d columns, room for %d", c->mosaic_gain_M, gain_q8_host ? cap : 0);
+    return gain_download(c, gain_q8_host, cap);
+}
+
+int dsss_mosaic_gain_get_banded(dsss_ctx* c, uint16_t* gain_q8_host, int cap, int* M, dsss_gain_bands* bands)
+{
+    if (!c) return DSSS_E_ARG;
+    if (!M || !bands) DSSS_FAIL(c, DSSS_E_ARG, "gain: nowhere to write the %s", M ? "bands" : "number of columns");
+    *M = c->mosaic_gain_M; *bands = c->mosaic_bands;                            // also when there is no room for the gains
+    if (!c->mosaic_gain_M) return DSSS_OK;
+    return gain_download(c, gain_q8_host, cap);
+}
+
+int dsss_frame_get_corrected(dsss_ctx* c, int id, uint8_t* out_host)
+{
+    if (!c) return DSSS_E_ARG;
+    if (!out_host) DSSS_FAIL(c, DSSS_E_ARG, "corrected waterfall: nowhere to write it");
+    if (id < 0 || id >= c->max_frames) DSSS_FAIL(c, DSSS_E_ARG, "frame id %d out of range [0,%d)", id, c->max_frames);
+    const dsss_frame& f = c->frames[id];
+    if (!f.has_geom || !f.has_norm || !f.lvl[0] || !f.mask) DSSS_FAIL(c, DSSS_E_STATE, "frame %d not extracted yet", id);
+    int rc = mosaic_check_gain(c, &id, 1); if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(gain_q8_host, c->mosaic_gain.p, (size_t)c->mosaic_gain_M * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
+    const size_t bytes = (size_t)f.N * f.M;
+    mosaic_arena A;
+    const auto o_out = A.take<uint8_t>(bytes);
+    rc = A.reserve(c); if (rc) return rc;
+    std::vector<mosaic_job> jobs;
+    rc = mosaic_fill_jobs(c, &id, 1, nullptr, nullptr, nullptr, jobs); if (rc) return rc;
+    hipLaunchKernelGGL(mosaic_correct_kernel, dim3((unsigned)f.N), dim3(256), 0, c->stream, jobs[0], A.at(o_out));
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(out_host, A.at(o_out), bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return DSSS_OK;
 }

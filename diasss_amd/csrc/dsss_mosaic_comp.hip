@@ -72,7 +72,7 @@ __global__ __launch_bounds__(256) void mosaic_resolve_kernel(const unsigned long
             else while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (jobs[mid].g0 <= g) lo = mid; else hi = mid - 1; }
             const mosaic_job& J = jobs[lo];
             row = g - J.g0; fr = ids[lo];
-            if (img) v = (int)mosaic_gain_apply(J.img[(size_t)row * J.M + col], J.gain, col);
+            if (img) v = (int)mosaic_gain_apply(J.img[(size_t)row * J.M + col], mosaic_gain_row(J, row), col);      // the band of the winning ping
             ++held;
         }
         if (img) img[i] = (uint8_t)v;

@@ -18,7 +18,10 @@
 // one frame of a launch: its pose rows (the frame's own or the caller's trajectory), geometry and images; blk0 = its first workgroup;
 // gain = the context's range-gain table (M x u16, Q8), null: none set -- the same in every job of a launch, so the test is uniform
 // g0 = the canonical number of the frame's first ping (composite mosaic; the other kernels do not read it)
-struct mosaic_job { const double* pose; const double* gr; const uint8_t* img; const uint8_t* mask; const uint16_t* gain; int N, M, blk0, g0; };
+// alt, bands = the frame's altitudes and the bands of a banded table ("altitude-banded range gain" in the header): gain then holds
+// bands.nbands rows of M, and a ping reads the row of its altitude's band; nbands == 1 (a column table, or none): alt is not read
+struct mosaic_job { const double* pose; const double* gr; const uint8_t* img; const uint8_t* mask; const uint16_t* gain; int N, M, blk0, g0;
+                    const double* alt = nullptr; dsss_gain_bands bands = { 0.0, 1.0, 1, 0 }; };
 // the grid (x0, y0, cell, W, H: where a point falls and whether it is kept) and the window of it the accumulators cover
 // (ox, oy, bw, bh: the whole grid for the mosaic, one frame's cell bounding box for the consistency map and the registration)
 struct mosaic_win { double x0, y0, cell; int W, H, ox, oy, bw, bh, use_mask; };
@@ -30,6 +33,20 @@ struct mosaic_seg { int ox, oy, bw, bh; unsigned long long off; };
 __device__ __forceinline__ unsigned mosaic_gain_apply(unsigned v, const uint16_t* __restrict__ gain, int col)
 {
     return gain ? min(255u, (v * gain[col] + 128u) >> 8) : v;
+}
+
+// the band of an altitude, ONE body for dsss_gain_band and the kernels (B as the entries admit it: nbands >= 1, dalt > 0, both finite)
+__host__ __device__ inline int gain_band(const dsss_gain_bands& B, double alt)
+{
+    const double t = floor((alt - B.alt0) / B.dalt);
+    if (!(t >= 0.0)) return 0;                                                     // on the f64 value: NaN, -inf and altitudes below alt0
+    if (t >= (double)B.nbands) return B.nbands - 1;
+    return (int)t;
+}
+// the row of the job's table that the ping `row` of its frame is corrected with (uniform per ping); null: no table set
+__device__ __forceinline__ const uint16_t* mosaic_gain_row(const mosaic_job& J, int row)
+{
+    return J.bands.nbands > 1 ? J.gain + (size_t)gain_band(J.bands, J.alt[row]) * J.M : J.gain;
 }
 
 // The one place a sample is binned on the device: the cell of the window G that the sample (row, col) falls into, -1 when it is
@@ -69,6 +86,7 @@ __device__ __forceinline__ bool mosaic_ping_of(const mosaic_job* __restrict__ jo
     J = mosaic_job_of(jobs, njobs); row = (int)blockIdx.x - J.blk0;
     if (row >= J.N) return false;
     P = J.pose + (size_t)row * 6;
+    J.gain = mosaic_gain_row(J, row);                                              // the ping's band, once per workgroup: the samples see a column table
     if (threadIdx.x < 2) dsss_geo_side(P, threadIdx.x == 1, &s_sc[2 * threadIdx.x], &s_sc[2 * threadIdx.x + 1]);
     __syncthreads();
     return true;

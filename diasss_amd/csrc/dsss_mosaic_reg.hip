@@ -264,9 +264,10 @@ __global__ __launch_bounds__(256) void mosaic_scatter_fan_kernel(const mosaic_jo
                                                                  const mosaic_fan* __restrict__ fan, int seg_pings, int nyaw)
 {
     __shared__ double s_sc[4], s_row[2][6];                                        // the rotated row once per side: the two lanes that need it for the bearing write it
-    const mosaic_job J = *job;
+    mosaic_job J = *job;
     const int row = (int)(blockIdx.x / (unsigned)nyaw), k = (int)(blockIdx.x - (unsigned)row * (unsigned)nyaw);
     if (row >= J.N) return;                                                        // (uniform per workgroup; cannot happen with the host's grid)
+    J.gain = mosaic_gain_row(J, row);                                              // the ping's band, as in mosaic_ping_of
     const mosaic_fan F = fan[(size_t)(row / seg_pings) * nyaw + k];
     if (F.bw <= 0) return;                                                         // nothing of this segment under this angle on the grid (uniform)
     G.ox = F.ox; G.oy = F.oy; G.bw = F.bw; G.bh = F.bh; acc += F.off;

@@ -64,6 +64,18 @@ def column_profile(M, amp):
     return 1.0 + amp * np.cos(3.0 * r) * np.where(c >= M / 2, 1.0, 0.8)
 
 
+def angle_profile(M, alt, gr, amp, k):
+    """A profile fixed to the grazing angle, as a beam pattern is: a factor per ping and column, 1 + amp cos(k theta) on starboard and
+    1 + 0.8 amp cos(k theta) on port, theta = atan2(gr[idx], alt[row]) with idx the ground-range index of the column (col >= M/2:
+    col - M/2; otherwise min(M/2 - col, M/2 - 1)).  Under a changing altitude no profile per column describes it; the banded
+    range-gain tools multiply the raw frames by this (float64 numpy, N x M)."""
+    half = M // 2
+    col = np.arange(M)
+    idx = np.where(col >= half, col - half, np.minimum(half - col, half - 1))
+    theta = np.arctan2(np.asarray(gr, np.float64)[idx][None, :], np.asarray(alt, np.float64)[:, None])
+    return 1.0 + amp * np.cos(k * theta) * np.where(col >= half, 1.0, 0.8)[None, :]
+
+
 class Survey:
     """F legs of N pings x M bins."""
 

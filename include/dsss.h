@@ -377,7 +377,8 @@ int dsss_mosaic_consistency(dsss_ctx*, const int* ids, int n, const double* rpy6
  * Errors.  DSSS_E_ARG: ids the mosaic entries reject, frames of differing M in one stats call, M < 2, a NULL output, parameters out of
  *   range, cap < M; and from every entry above, before anything is launched or cleared, when a table is set and a listed frame has
  *   another M.  DSSS_E_STATE: frames not extracted (the rule of dsss_mosaic_render).  Every error leaves the context usable and a table
- *   that was set in place.  Estimation and installation are two calls on purpose: a caller may install a calibrated table.             */
+ *   that was set in place.  Estimation and installation are two calls on purpose: a caller may install a calibrated table.
+ * One row per altitude band instead of one for all pings, and the corrected waterfall as an output: "altitude-banded range gain" below. */
 typedef struct { int32_t min_count, smooth, target, pad_; } dsss_gain_params;
 void dsss_gain_params_default(dsss_gain_params*);
 /* S -> sum_host[M], C -> cnt_host[M] of the listed frames (mosaic_colstat_kernel: one launch for all frames) */
@@ -386,6 +387,43 @@ int  dsss_mosaic_gain_table(const uint64_t* sum, const uint64_t* cnt, int M, con
                             uint16_t* gain_q8 /* M */, int32_t* target_out /* may be NULL */);
 int  dsss_mosaic_gain_set(dsss_ctx*, const uint16_t* gain_q8_host, int M);      /* NULL: clear (M ignored) */
 int  dsss_mosaic_gain_get(dsss_ctx*, uint16_t* gain_q8_host, int cap, int* M);  /* *M = 0: none set; read back from the device copy */
+
+/* ---- altitude-banded range gain: the table above with one row per altitude BAND.  A column is a slant range, a beam pattern is fixed
+ * to the grazing angle, and column c looks at atan(gr[c] / h) from the altitude h: one profile per column is right only while the
+ * altitude hardly moves.  A banded table holds nbands rows of M gains; a ping is corrected with the row of its altitude's band.
+ * Integer arithmetic throughout, as above.  While no banded table is set, every layer of every entry is the byte it was.
+ * Bands: nbands in 1..16, alt0 finite, dalt finite and > 0.  The band of an altitude a: t = floor((a - alt0) / dalt) in f64; band = 0
+ *   when !(t >= 0) (NaN, -inf and altitudes below alt0), nbands - 1 when t >= nbands, (int)t otherwise; the comparisons are made on the
+ *   f64 values before any conversion, as in the cell arithmetic.  dsss_gain_band evaluates it on the host (no context): the one body
+ *   the kernels run.  The altitude of a sample is alt[row] as the frame was set, never a row of the trajectory passed to an entry.
+ * Statistics: S[b][c], C[b][c] = the sum and the number of the kept samples of column c over the pings whose band is b (nbands x M
+ *   uint64 each; mosaic_bandstat_kernel, one launch for all frames).  Kept-sample rule, frame rules and errors are those of
+ *   dsss_mosaic_gain_stats, and summed over b the result is exactly its output.
+ * Table (pure host arithmetic, no context): Sp[c] = sum_b S[b][c], Cp likewise; gp[c] and T = exactly what dsss_mosaic_gain_table
+ *   returns on (Sp, Cp) with the same parameters.  S'_b, C'_b = the same-side smoothing window of that rule within band b.  Entry (b, c)
+ *   is eligible iff C'_b[c] >= min_count and S'_b[c] > 0 and T > 0; then gain[b][c] = min(65535, (T C'_b[c] 256 + S'_b[c] / 2) / S'_b[c]),
+ *   otherwise gain[b][c] = gp[c]: a thin band falls back to the pooled column, never to 256.  nbands == 1 reproduces
+ *   dsss_mosaic_gain_table exactly.
+ * Installation: dsss_mosaic_gain_set_banded installs nbands x M gains with their bands (NULL table: clear); dsss_mosaic_gain_set
+ *   installs a one-band table as before.  dsss_mosaic_gain_get is DSSS_E_STATE while a table of more than one band is set, and writes
+ *   nothing; dsss_mosaic_gain_get_banded reads any table back (*M = 0: none set; cap counts gains: nbands x M are needed; the bands of
+ *   a table set through dsss_mosaic_gain_set read alt0 0, dalt 1, nbands 1).
+ * Corrected sample: v' = min(255, (v gain[band(alt[row])][c] + 128) >> 8), in every entry the column table applies to and in the
+ *   composite; the rule that every listed frame has the table's M is unchanged.
+ * Corrected waterfall: dsss_frame_get_corrected returns the frame's normalised image (N x M uint8) under the table in force -- banded,
+ *   one-band or none (then the normalised image itself) -- by mosaic_correct_kernel.  DSSS_E_STATE: the frame is not extracted;
+ *   DSSS_E_ARG: a NULL output, a table of another M.
+ * Errors of the new entries, DSSS_E_ARG before anything is reserved or launched: nbands outside 1..16, alt0 or dalt not finite,
+ *   dalt <= 0, a NULL pointer, and whatever the column entries refuse.  An error leaves the context usable and the table in place.  */
+typedef struct { double alt0, dalt; int32_t nbands, pad_; } dsss_gain_bands;
+int  dsss_gain_band(const dsss_gain_bands*, double alt, int32_t* band);
+int  dsss_mosaic_gain_stats_banded(dsss_ctx*, const int* ids, int n, int use_mask, const dsss_gain_bands*,
+                                   uint64_t* sum_host /* nbands x M */, uint64_t* cnt_host /* nbands x M */);
+int  dsss_mosaic_gain_table_banded(const uint64_t* sum, const uint64_t* cnt, int M, int nbands, const dsss_gain_params* /* NULL: defaults */,
+                                   uint16_t* gain_q8 /* nbands x M */, int32_t* target_out /* may be NULL */);
+int  dsss_mosaic_gain_set_banded(dsss_ctx*, const uint16_t* gain_q8_host /* nbands x M; NULL: clear */, int M, const dsss_gain_bands*);
+int  dsss_mosaic_gain_get_banded(dsss_ctx*, uint16_t* gain_q8_host, int cap, int* M, dsss_gain_bands* bands);
+int  dsss_frame_get_corrected(dsss_ctx*, int id, uint8_t* out_host /* N x M */);
 
 /* ---- composite mosaic: the deliverable picture.  dsss_mosaic_render's img is the mean of every sample of a cell: right for the
  * consistency score and the ZNCC, but a blend of frames that see a patch from opposite sides.  Here a cell holds ONE sample, the winner

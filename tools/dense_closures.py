@@ -3,7 +3,7 @@
 solved trajectory (dsss_mosaic_register_segments), the accepted offsets become pose-graph edges (dsss_mosaic_register_edges), the
 trajectory is solved again with them next to the feature-based closures, and the segments are registered once more under the result.
     python tools/dense_closures.py --frames 200 --rows 2000 --cols 1024 --cell 0.1 [--seg-pings 80] [--radius 8] [--calls 5] [--timeout 1500]
-                                   [--yaw-fan NYAW [--yaw-step RAD]] [--pyramid L [--refine RHO]] [--peaks-ab] [--profile AMP] [--gain]
+                                   [--yaw-fan NYAW [--yaw-step RAD]] [--pyramid L [--refine RHO]] [--peaks-ab] [--profile AMP] [--gain [--gain-bands B]]
 Steps: 1. pipeline and dsss_posegraph_solve; 2. segments under the solved trajectory; 3. edges; 4. the edges of dsss_posegraph_select
 with the new ones behind them; 5. dsss_posegraph_solve_edges on the frames' dead-reckoning rows; 6. segments under the result.
 Prints one JSON line: segments and accepted edges; median and 95th percentile of |offset| in metres over the segments with a peak, the
@@ -29,6 +29,8 @@ bytes copied down and the synchronisations (dsss_mosaic_register_info), and asse
 a second time in the same process under the range-gain table of the frames' own statistics (dsss_mosaic_gain_stats, dsss_mosaic_gain_table
 with the default parameters, dsss_mosaic_gain_set) and reports them under "gain": segments with a peak and accepted edges, the median ZNCC
 at the peak and at zero shift, and the consistency score before and after solving again, next to the same figures without the table.
+--gain-bands B (with --gain) makes that table an altitude-banded one: B bands of equal width over the frames' altitudes
+(dsss_mosaic_gain_stats_banded, dsss_mosaic_gain_table_banded, dsss_mosaic_gain_set_banded).
 The GPU work runs in a child process under a time limit (--timeout seconds); this process never opens the device."""
 import argparse
 import json
@@ -47,6 +49,7 @@ ap.add_argument("--pyramid", type=int, default=1); ap.add_argument("--refine", t
 ap.add_argument("--calls", type=int, default=5); ap.add_argument("--timeout", type=float, default=1500.0)
 ap.add_argument("--peaks-ab", action="store_true")
 ap.add_argument("--profile", type=float, default=0.0, metavar="AMP"); ap.add_argument("--gain", action="store_true")
+ap.add_argument("--gain-bands", type=int, default=0, metavar="B")
 ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)
 a = ap.parse_args()
 if a.calls < 5:
@@ -221,9 +224,11 @@ def closures():
 
 res.update(closures())
 if a.gain:
-    S, C = ctx.mosaic_gain_stats(ids)
-    table, T = capi.mosaic_gain_table(S, C)
-    ctx.mosaic_gain_set(table)
+    alts = np.concatenate([i[1] for i in ins])
+    bands = capi.GainBands(float(alts.min()), float(np.ptp(alts)) / a.gain_bands or 1.0, a.gain_bands, 0) if a.gain_bands else None
+    S, C = ctx.mosaic_gain_stats(ids, bands=bands)
+    table, T = capi.mosaic_gain_table(S, C, nbands=a.gain_bands or None)
+    ctx.mosaic_gain_set(table, bands=bands)
     res["gain"] = dict(closures(), target=T, gain_min=int(table.min()), gain_max=int(table.max()))
     ctx.mosaic_gain_set(None)
 if PYR:                                          # the same counts under dead reckoning, where the legs lie furthest from where they belong

@@ -11,7 +11,13 @@ imply, and that as a fraction of the 6.3 TB/s copy ceiling), the render with and
 parameters) in one process, interleaved call by call, and the consistency score under the three trajectories with and without it.
 --composite MODE (near, far, mid, first) adds the composite mosaic: dsss_mosaic_composite with nothing downloaded against
 dsss_mosaic_render in one process, interleaved call by call (median, fastest and slowest of --calls after a warm-up round), and the
-three cell counts; --fill R fills enclosed holes within R cells.  With --gain both run under the table."""
+three cell counts; --fill R fills enclosed holes within R cells.  With --gain both run under the table.
+--gain-bands B [--alt-swing METRES] --angle-profile AMP adds the altitude-banded range gain: the raw frames are multiplied by
+synth.angle_profile(M, alt, gr, AMP, 6) (--alt-swing replaces the survey's altitudes by 10 + METRES sin(2 pi s / 20 + 0.9 f) first), B bands
+of equal width cover the altitudes, and the tool reports the banded statistics and table (min_count 64, smooth 8), the consistency
+score under the TRUE poses with no table, the column table and the banded table, and, interleaved call by call in one process (median,
+fastest and slowest of --calls after a warm-up round), dsss_mosaic_gain_stats (mosaic_colstat_kernel) against
+dsss_mosaic_gain_stats_banded (mosaic_bandstat_kernel) on the same frames and the render under the column against the banded table."""
 import argparse
 import json
 import os
@@ -22,7 +28,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from diasss_amd import capi                      # noqa: E402
 from diasss_amd.pipeline import Pipeline         # noqa: E402
-from diasss_amd.synth import Survey, column_profile   # noqa: E402
+from diasss_amd.synth import Survey, angle_profile, column_profile   # noqa: E402
 
 HBM_PEAK = 8.0e12                                # bytes / s, the roof of DESIGN.md section 4
 COPY_CEILING = 6.3e12                            # bytes / s a device-to-device copy reaches
@@ -33,6 +39,8 @@ ap.add_argument("--cols", type=int, default=1024); ap.add_argument("--cell", typ
 ap.add_argument("--calls", type=int, default=7)
 ap.add_argument("--profile", type=float, default=0.0, metavar="AMP"); ap.add_argument("--gain", action="store_true")
 ap.add_argument("--composite", choices=sorted(capi.COMP_MODES), default=None, metavar="MODE"); ap.add_argument("--fill", type=int, default=0, metavar="R")
+ap.add_argument("--gain-bands", type=int, default=0, metavar="B"); ap.add_argument("--alt-swing", type=float, default=None, metavar="METRES")
+ap.add_argument("--angle-profile", type=float, default=0.0, metavar="AMP")
 a = ap.parse_args()
 F, N, M = a.frames, a.rows, a.cols
 if a.calls < 5:
@@ -45,6 +53,12 @@ if a.profile:
     prof = torch.from_numpy(column_profile(M, a.profile)).to(raws[0].device)
     raws = [(r * prof[None, :]).contiguous() for r in raws]
 ins = [sv.inputs(f) for f in range(F)]
+if a.gain_bands:
+    import torch
+    if a.alt_swing is not None:
+        s_along = (np.arange(N) + 0.5) * sv.res
+        ins = [(i[0], 10.0 + a.alt_swing * np.sin(2 * np.pi * s_along / 20.0 + 0.9 * f), i[2]) for f, i in enumerate(ins)]
+    raws = [(r * torch.from_numpy(angle_profile(M, ins[f][1], ins[f][2], a.angle_profile, 6.0)).to(r.device)).contiguous() for f, r in enumerate(raws)]
 pipe = Pipeline(F, device=0)
 pipe.run(raws, [i[0] for i in ins], [i[1] for i in ins], [i[2] for i in ins])
 ctx = pipe.ctx
@@ -108,6 +122,40 @@ if a.gain:
     for name, traj in trajs:
         res["score_" + name + "_gain"] = ctx.mosaic_consistency(ids, p, **traj)[3]
     ctx.mosaic_gain_set(None)
+
+if a.gain_bands:
+    alts = np.concatenate([i[1] for i in ins])
+    lo, hi = float(alts.min()), float(alts.max())
+    bands = capi.GainBands(lo, (hi - lo) / a.gain_bands if hi > lo else 1.0, a.gain_bands, 0)
+    gp = capi.GainParams(64, 8, 0, 0)
+    t_col, t_band = [], []
+    for k in range(a.calls + 1):
+        t0 = time.perf_counter(); cS, cC = ctx.mosaic_gain_stats(ids); dt_col = time.perf_counter() - t0
+        t0 = time.perf_counter(); bS, bC = ctx.mosaic_gain_stats(ids, bands=bands); dt_band = time.perf_counter() - t0
+        if k:                                                     # (the first round warms up)
+            t_col.append(dt_col); t_band.append(dt_band)
+    assert (bS.sum(axis=0) == cS).all() and (bC.sum(axis=0) == cC).all()
+    ctab, cT = capi.mosaic_gain_table(cS, cC, gp)
+    btab, bT = capi.mosaic_gain_table(bS, bC, gp, nbands=a.gain_bands)
+    r_col, r_band = [], []
+    for k in range(a.calls + 1):
+        for tab, bd, ts in ((ctab, None, r_col), (btab, bands, r_band)):
+            ctx.mosaic_gain_set(tab, bands=bd)
+            t0 = time.perf_counter(); ctx.mosaic_render(ids, p, download=False); dt = time.perf_counter() - t0
+            if k:
+                ts.append(dt)
+    tt = dict(rpy6=true, ping_off=off)
+    for name, tab, bd in (("none", None, None), ("column", ctab, None), ("banded", btab, bands)):
+        ctx.mosaic_gain_set(tab, bands=bd)
+        res["score_true_bands_" + name] = ctx.mosaic_consistency(ids, p, **tt)[3]
+    ctx.mosaic_gain_set(None)
+
+    def mmm(ts):
+        return [round(1e3 * float(np.median(ts)), 3), round(1e3 * min(ts), 3), round(1e3 * max(ts), 3)]
+    res.update(gain_bands=a.gain_bands, alt_swing=a.alt_swing, angle_profile=a.angle_profile, bands_alt0=bands.alt0, bands_dalt=bands.dalt,
+               bands_target=bT, bands_pings=[int(v) for v in np.bincount([capi.gain_band(bands, v) for v in alts], minlength=a.gain_bands)],
+               bands_fallback_entries=int((btab == ctab[None, :]).sum()), colstat_ms_med_min_max=mmm(t_col), bandstat_ms_med_min_max=mmm(t_band),
+               render_ms_column_med_min_max=mmm(r_col), render_ms_banded_med_min_max=mmm(r_band))
 
 if a.composite:
     if a.gain:
