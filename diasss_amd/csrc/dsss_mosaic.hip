@@ -75,11 +75,12 @@ __global__ __launch_bounds__(256) void mosaic_fold_kernel(const unsigned long lo
     nfr[g] += 1; s1[g] += m; s2[g] += m * m;
 }
 
-// ---- range-gain normalisation ("range-gain normalisation" in the header)
+// ---- range-gain statistics ("range-gain normalisation" and "altitude-banded range gain" in the header)
 #define COLSTAT_COLS 4                     // consecutive columns a lane owns: one dword of a row
-#define COLSTAT_LANES 64                   // lanes across a row at most: a wavefront reads 256 consecutive bytes of it (the whole workgroup across took four times the atomics and 0.36 ms where this takes 0.22: DESIGN.md section 4, "Range-gain normalisation")
+#define COLSTAT_LANES 64                   // lanes across a row at most: a wavefront reads 256 consecutive bytes of it (why: mosaic_gainstat_kernel's comment)
 #define COLSTAT_ROWS 128                   // rows a lane walks: 128 x 255 < 2^16, far inside the u32 partials
 #define COLSTAT_BATCH 8                    // rows a lane has in flight (two dwords each)
+#define BAND_MAX 16                        // bands of a table
 
 // a frame's workgroups: chunks of tpr x 4 columns x blocks of (256 / tpr) x COLSTAT_ROWS rows, tpr = the power of two of lanes that
 // cover a row's groups of four columns, COLSTAT_LANES at most
@@ -121,66 +122,8 @@ template <bool MASK> __device__ __forceinline__ void colstat_words(const uint32_
     for (int row = row0 + nb * rl; row < row1; row += rl) colstat_add<MASK>(img[(size_t)row * M4], MASK ? msk[(size_t)row * M4] : 0u, s, n);
 }
 
-// S[c] = sum of the kept samples of column c, C[c] = their number, over all frames of the job table: out[c] += S, out[M + c] += C.
-// A streaming integer reduction, two bytes read per sample and nothing else.  A lane owns four consecutive columns; tpr lanes (a
-// wavefront at most) lie across a row, so a wavefront reads consecutive dwords of it, and the 256 / tpr lanes that share a column group
-// take rows `rl` apart -- four wavefronts four rows, and a narrow frame still fills the workgroup.  A lane walks COLSTAT_ROWS rows with
-// the eight u32 partials of its columns in registers, COLSTAT_BATCH rows in flight; the lanes of a group add their partials up through
-// LDS, and the first of them leaves through 64-bit atomics without return -- integers, so the result does not depend on their order --
-// only for columns that kept a sample.  Rows are dword-aligned where M % 4 == 0 and the images are; otherwise (uniform per launch: all
-// frames have one M) a lane reads its four bytes one by one, and the columns behind M are skipped.
-__global__ __launch_bounds__(256) void mosaic_colstat_kernel(const mosaic_job* __restrict__ jobs, int njobs, int use_mask, unsigned long long* __restrict__ out)
-{
-    __shared__ uint32_t s_part[2 * COLSTAT_COLS][256];
-    const mosaic_job J = mosaic_job_of(jobs, njobs);
-    const int M = J.M, tpr = colstat_tpr(M), rl = 256 / tpr, chunks = colstat_chunks(M), rows_wg = rl * COLSTAT_ROWS;
-    const int wg = (int)blockIdx.x - J.blk0;
-    const int rb = wg / chunks, ch = wg - rb * chunks;
-    const int col = (ch * tpr + ((int)threadIdx.x & (tpr - 1))) * COLSTAT_COLS;
-    const int row0 = rb * rows_wg + (int)threadIdx.x / tpr, row1 = min(J.N, (rb + 1) * rows_wg);
-    const int nmin = (row1 - rb * rows_wg) / rl;                                  // rows every lane of the workgroup has
-    uint32_t s[COLSTAT_COLS] = { 0, 0, 0, 0 }, n[COLSTAT_COLS] = { 0, 0, 0, 0 };
-    if (col < M) {
-        if (M % 4 == 0 && (((uintptr_t)J.img | (uintptr_t)J.mask) & 3) == 0) {
-            const uint32_t* img = reinterpret_cast<const uint32_t*>(J.img + col); const uint32_t* msk = reinterpret_cast<const uint32_t*>(J.mask + col);
-            if (use_mask) colstat_words<true>(img, msk, (size_t)(M / 4), row0, row1, rl, nmin, s, n);
-            else colstat_words<false>(img, msk, (size_t)(M / 4), row0, row1, rl, nmin, s, n);
-        } else {
-            const int nc = min(COLSTAT_COLS, M - col);
-            for (int row = row0; row < row1; row += rl) {
-                const uint8_t* __restrict__ img = J.img + (size_t)row * M + col;
-                const uint8_t* __restrict__ msk = J.mask + (size_t)row * M + col;
-#pragma unroll
-                for (int k = 0; k < COLSTAT_COLS; ++k) {
-                    if (k >= nc) continue;
-                    const bool keep = !use_mask || msk[k] != 0;
-                    s[k] += keep ? (uint32_t)img[k] : 0u; n[k] += keep ? 1u : 0u;
-                }
-            }
-        }
-    }
-    if (rl > 1) {                                                                  // (uniform per launch)
-#pragma unroll
-        for (int k = 0; k < COLSTAT_COLS; ++k) { s_part[k][threadIdx.x] = s[k]; s_part[COLSTAT_COLS + k][threadIdx.x] = n[k]; }
-        __syncthreads();
-        if ((int)threadIdx.x >= tpr) return;
-        for (int r = 1; r < rl; ++r) {
-#pragma unroll
-            for (int k = 0; k < COLSTAT_COLS; ++k) { s[k] += s_part[k][threadIdx.x + r * tpr]; n[k] += s_part[COLSTAT_COLS + k][threadIdx.x + r * tpr]; }
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < COLSTAT_COLS; ++k) {
-        if (col + k >= M || n[k] == 0) continue;
-        atomicAdd(&out[col + k], (unsigned long long)s[k]); atomicAdd(&out[M + col + k], (unsigned long long)n[k]);
-    }
-}
-
-// ---- altitude-banded range gain ("altitude-banded range gain" in the header)
-#define BAND_MAX 16                        // bands of a table
-
-// the workgroup's table in LDS: tab[band][sum | count][k][lane across the row], u32 -- a workgroup sees rl x COLSTAT_ROWS <= 2^15 rows
-// of a column, 2^15 x 255 < 2^32
+// a slot of the workgroup's table in LDS (mosaic_gainstat_kernel): tab[band][sum | count][k][lane across the row], u32 -- a workgroup
+// sees rl x COLSTAT_ROWS <= 2^15 rows of a column, 2^15 x 255 < 2^32
 __device__ __forceinline__ int bandstat_slot(int tpr, int band, int what, int k, int lt) { return ((band * 2 + what) * COLSTAT_COLS + k) * tpr + lt; }
 
 // the lane's partials, which are those of `band`, into the workgroup's table (LDS atomics without return), and back to zero
@@ -229,15 +172,26 @@ template <bool MASK> __device__ __forceinline__ void bandstat_words(const uint32
     }
 }
 
-// S[b][c], C[b][c] over all frames of the job table: out[b M + c] += S, out[(nbands + b) M + c] += C.  mosaic_colstat_kernel's lane
-// layout, load paths and row blocks; a job carries its frame's altitudes and the bands.  The workgroup first writes the band of each of
-// its rows into LDS (one f64 division a row, not one a lane and row) and learns with the same barrier whether they all lie in one
-// band.  If so -- the rule on real data, where the altitude moves through a band over hundreds of pings -- the lanes run colstat_words
-// itself.  Otherwise a lane keeps the partials of ONE band, that of its last row, in registers, and adds them to the workgroup's
-// table in LDS (u32 atomics without return) when its next row lies in another: a band that changes on every ping costs eight LDS atomics
-// a row and lane, and nothing global.  The table leaves through 64-bit atomics without return, only for the entries that kept a sample.
-// Integers throughout: the result depends on no order.  Dynamic LDS: nbands x 8 x tpr words and rows_wg bytes, 33 KB at most.
-__global__ __launch_bounds__(256) void mosaic_bandstat_kernel(const mosaic_job* __restrict__ jobs, int njobs, int use_mask, unsigned long long* __restrict__ out)
+// S[b][c] = sum of the kept samples of column c over the pings of band b, C[b][c] = their number, over all frames of the job table:
+// out[b M + c] += S, out[(nbands + b) M + c] += C.  One band (the column statistics; gain_one_band()): out[c], out[M + c].  A streaming
+// integer reduction, two bytes read per sample and nothing else.
+// Lanes: a lane owns four consecutive columns; tpr lanes (a wavefront at most: the whole workgroup across a row took four times the
+// atomics and 0.36 ms where this takes 0.22, DESIGN.md section 4, "Range-gain normalisation") lie across a row, so a wavefront reads
+// consecutive dwords of it, and the 256 / tpr lanes that share a column group take rows `rl` apart -- four wavefronts four rows, and a
+// narrow frame still fills the workgroup.  A lane walks COLSTAT_ROWS rows with the eight u32 partials of its columns in registers.
+// Loads: rows are dword-aligned where M % 4 == 0 and the images are, and go COLSTAT_BATCH in flight (colstat_words, bandstat_words);
+// otherwise (uniform per launch: all frames have one M) a lane reads its four bytes one by one, and the columns behind M are skipped.
+// Bands: sixteen bands of eight partials do not fit a lane's registers, so a lane keeps the partials of ONE band, that of its last row.
+// With more than one band the workgroup first writes the band of each of its rows into LDS (one f64 division a row, not one a lane and
+// row) and learns with the same barrier whether they all lie in one band.  If so -- the rule on real data, where the altitude moves
+// through a band over hundreds of pings, and always with one band, where J.alt is not read -- the lanes run colstat_words.  Otherwise
+// a lane's partials leave for the table when its next row lies in another band: a band that changes on every ping costs eight LDS
+// atomics a row and lane, and nothing global.
+// Table: tab[band][sum | count][k][lane] in LDS, u32, is the one reduction across the lanes that share a column (ds_add without
+// return); dynamic LDS is nbands x 8 x tpr words and, behind them, rows_wg bytes for the bands of the rows, 33 KB at most.
+// Exit: the table leaves through 64-bit atomics without return, only for the entries that kept a sample.  Integers throughout, so the
+// result depends on no order.
+__global__ __launch_bounds__(256) void mosaic_gainstat_kernel(const mosaic_job* __restrict__ jobs, int njobs, int use_mask, unsigned long long* __restrict__ out)
 {
     extern __shared__ uint32_t s_band_dyn[];
     const mosaic_job J = mosaic_job_of(jobs, njobs);
@@ -443,7 +397,7 @@ int mosaic_fill_jobs(dsss_ctx* c, const int* ids, int n, const double* rpy6, con
     rc = upload_rows(c, ids, n, rpy6, ping_off, d_rows, dev_rows); if (rc) return rc;
     const uint16_t* gain = c->mosaic_gain_M ? c->mosaic_gain.as<uint16_t>() : nullptr;
     jobs.resize(n);
-    for (int i = 0; i < n; ++i) { const dsss_frame& f = c->frames[ids[i]]; jobs[i] = mosaic_job{ dev_rows[i], f.gr, f.lvl[0], f.mask, gain, f.N, f.M, 0, 0, f.alt, gain ? c->mosaic_bands : dsss_gain_bands{ 0.0, 1.0, 1, 0 } }; }
+    for (int i = 0; i < n; ++i) { const dsss_frame& f = c->frames[ids[i]]; jobs[i] = mosaic_job{ dev_rows[i], f.gr, f.lvl[0], f.mask, gain, f.N, f.M, 0, 0, f.alt, gain ? c->mosaic_bands : gain_one_band() }; }
     return DSSS_OK;
 }
 
@@ -557,34 +511,37 @@ static bool gain_bands_ok(const dsss_gain_bands* b)
     return b && b->nbands >= 1 && b->nbands <= BAND_MAX && std::isfinite(b->alt0) && std::isfinite(b->dalt) && b->dalt > 0.0;
 }
 
-// The statistics of the listed frames, bands == null: per column (mosaic_colstat_kernel), otherwise per band and column
-// (mosaic_bandstat_kernel): the one job table, launch shape and download of both entries.  The statistics are those of the uncorrected
-// samples whatever table is set: the jobs carry the images, and the frame's altitudes with the caller's bands, alone.
-static int gain_stats_run(dsss_ctx* c, const int* ids, int n, int use_mask, const dsss_gain_bands* bands, int M, uint64_t* sum_host, uint64_t* cnt_host)
+// the rule of a caller's bands, with its message: the two banded entries that take a context
+static int gain_check_bands(dsss_ctx* c, const dsss_gain_bands* b)
+{
+    if (!gain_bands_ok(b)) DSSS_FAIL(c, DSSS_E_ARG, "gain: bands %s", b ? "outside the rules (nbands 1..16, alt0 and dalt finite, dalt > 0)" : "missing");
+    return DSSS_OK;
+}
+
+// The statistics of the listed frames per band and column (mosaic_gainstat_kernel; the column entry passes gain_one_band()): the one job
+// table, launch and download of both entries.  The statistics are those of the uncorrected samples whatever table is set: the jobs carry
+// the images, and the frame's altitudes (which one band never reads) with the caller's bands, alone.
+static int gain_stats_run(dsss_ctx* c, const int* ids, int n, int use_mask, dsss_gain_bands bands, int M, uint64_t* sum_host, uint64_t* cnt_host)
 {
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t entries = (size_t)M * (bands ? bands->nbands : 1);
+    const size_t entries = (size_t)M * bands.nbands;
     mosaic_arena A;
     const auto o_out = A.take<unsigned long long>(entries * 2); const auto o_jobs = A.take<mosaic_job>(n);
     int rc = A.reserve(c); if (rc) return rc;
     unsigned long long* d_out = A.at(o_out); mosaic_job* d_jobs = A.at(o_jobs);
     std::vector<mosaic_job> jobs(n);
     const int tpr = colstat_tpr(M), chunks = colstat_chunks(M), rows_wg = (256 / tpr) * COLSTAT_ROWS;
+    const size_t lds = ((size_t)bands.nbands * 2 * COLSTAT_COLS * tpr) * sizeof(uint32_t) + (size_t)rows_wg;      // the table, then a band per row
     long long blocks = 0;
     for (int i = 0; i < n; ++i) {
         const dsss_frame& f = c->frames[ids[i]];
-        jobs[i] = mosaic_job{ nullptr, nullptr, f.lvl[0], f.mask, nullptr, f.N, f.M, (int)blocks, 0 };
-        if (bands) { jobs[i].alt = f.alt; jobs[i].bands = *bands; }
+        jobs[i] = mosaic_job{ nullptr, nullptr, f.lvl[0], f.mask, nullptr, f.N, f.M, (int)blocks, 0, f.alt, bands };
         blocks += (long long)chunks * ((f.N + rows_wg - 1) / rows_wg);
     }
     if (blocks > 0x7fffffffll) DSSS_FAIL(c, DSSS_E_ARG, "gain: %d frames of %d columns are more than one launch takes", n, M);
     HIPCHK(c, hipMemcpyAsync(d_jobs, jobs.data(), (size_t)n * sizeof(mosaic_job), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemsetAsync(d_out, 0, entries * 16, c->stream));
-    if (blocks && !bands) hipLaunchKernelGGL(mosaic_colstat_kernel, dim3((unsigned)blocks), dim3(256), 0, c->stream, d_jobs, n, use_mask != 0, d_out);
-    if (blocks && bands) {
-        const size_t lds = ((size_t)bands->nbands * 2 * COLSTAT_COLS * tpr) * sizeof(uint32_t) + (size_t)rows_wg;      // the table, then a band per row
-        hipLaunchKernelGGL(mosaic_bandstat_kernel, dim3((unsigned)blocks), dim3(256), lds, c->stream, d_jobs, n, use_mask != 0, d_out);
-    }
+    if (blocks) hipLaunchKernelGGL(mosaic_gainstat_kernel, dim3((unsigned)blocks), dim3(256), lds, c->stream, d_jobs, n, use_mask != 0, d_out);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(sum_host, d_out, entries * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(cnt_host, d_out + entries, entries * 8, hipMemcpyDeviceToHost, c->stream));
@@ -597,16 +554,16 @@ int dsss_mosaic_gain_stats(dsss_ctx* c, const int* ids, int n, int use_mask, uin
     if (!c) return DSSS_E_ARG;
     int M = 0;
     const int rc = gain_stats_check(c, ids, n, sum_host, cnt_host, &M); if (rc) return rc;
-    return gain_stats_run(c, ids, n, use_mask, nullptr, M, sum_host, cnt_host);
+    return gain_stats_run(c, ids, n, use_mask, gain_one_band(), M, sum_host, cnt_host);
 }
 
 int dsss_mosaic_gain_stats_banded(dsss_ctx* c, const int* ids, int n, int use_mask, const dsss_gain_bands* bands, uint64_t* sum_host, uint64_t* cnt_host)
 {
     if (!c) return DSSS_E_ARG;
-    if (!gain_bands_ok(bands)) DSSS_FAIL(c, DSSS_E_ARG, "gain: bands %s", bands ? "outside the rules (nbands 1..16, alt0 and dalt finite, dalt > 0)" : "missing");
+    int rc = gain_check_bands(c, bands); if (rc) return rc;
     int M = 0;
-    const int rc = gain_stats_check(c, ids, n, sum_host, cnt_host, &M); if (rc) return rc;
-    return gain_stats_run(c, ids, n, use_mask, bands, M, sum_host, cnt_host);
+    rc = gain_stats_check(c, ids, n, sum_host, cnt_host, &M); if (rc) return rc;
+    return gain_stats_run(c, ids, n, use_mask, *bands, M, sum_host, cnt_host);
 }
 
 int dsss_gain_band(const dsss_gain_bands* bands, double alt, int32_t* band)
@@ -616,6 +573,30 @@ int dsss_gain_band(const dsss_gain_bands* bands, double alt, int32_t* band)
     return DSSS_OK;
 }
 
+// ---- the table rule, said once for the column and the banded table (S, C: one row of M sums and counts)
+typedef unsigned __int128 u128;
+struct gain_window { u128 s, n; };      // S', C'
+
+// S and C of the columns within `smooth` of c on c's side: the window never crosses the nadir at M / 2
+static gain_window gain_window_of(const uint64_t* S, const uint64_t* C, int M, int smooth, int c)
+{
+    const int half = M / 2;
+    const int lo = std::max(c - smooth, c < half ? 0 : half), hi = std::min(c + smooth, c < half ? half - 1 : M - 1);
+    gain_window w = { 0, 0 };
+    for (int k = lo; k <= hi; ++k) { w.s += S[k]; w.n += C[k]; }
+    return w;
+}
+
+// a window that gets a gain of its own
+static bool gain_eligible(const gain_window& w, int min_count) { return w.n >= (u128)min_count && w.s > 0; }
+
+// the Q8 gain that takes an eligible window's mean S' / C' to T, to the nearest, 65535 at most
+static uint16_t gain_q8_of(u128 T, const gain_window& w)
+{
+    const u128 g = (T * w.n * 256 + w.s / 2) / w.s;
+    return g > 65535 ? (uint16_t)65535 : (uint16_t)g;
+}
+
 int dsss_mosaic_gain_table(const uint64_t* sum, const uint64_t* cnt, int M, const dsss_gain_params* gp, uint16_t* gain_q8, int32_t* target_out)
 {
     dsss_gain_params P;
@@ -623,27 +604,16 @@ int dsss_mosaic_gain_table(const uint64_t* sum, const uint64_t* cnt, int M, cons
     if (gp) P = *gp;
     if (!sum || !cnt || !gain_q8 || M < 2) return DSSS_E_ARG;
     if (P.min_count < 1 || P.smooth < 0 || P.smooth > 16 || P.target < 0 || P.target > 255) return DSSS_E_ARG;
-    typedef unsigned __int128 u128;
-    const int half = M / 2;
-    std::vector<u128> Ss(M), Cs(M);
-    std::vector<char> elig(M);
+    std::vector<gain_window> win(M);
     u128 tS = 0, tC = 0;
     bool any = false;
     for (int c = 0; c < M; ++c) {
-        const int lo = std::max(c - P.smooth, c < half ? 0 : half), hi = std::min(c + P.smooth, c < half ? half - 1 : M - 1);      // never across the nadir
-        u128 s = 0, n = 0;
-        for (int k = lo; k <= hi; ++k) { s += sum[k]; n += cnt[k]; }
-        Ss[c] = s; Cs[c] = n;
-        elig[c] = n >= (u128)P.min_count && s > 0;
-        if (elig[c]) { any = true; tS += sum[c]; tC += cnt[c]; }
+        win[c] = gain_window_of(sum, cnt, M, P.smooth, c);
+        if (gain_eligible(win[c], P.min_count)) { any = true; tS += sum[c]; tC += cnt[c]; }
     }
     u128 T = 0;
     if (any) { if (P.target) T = (u128)P.target; else if (tC > 0) T = (tS + tC / 2) / tC; else any = false; }
-    for (int c = 0; c < M; ++c) {
-        if (!any || !elig[c]) { gain_q8[c] = 256; continue; }
-        const u128 g = (T * Cs[c] * 256 + Ss[c] / 2) / Ss[c];
-        gain_q8[c] = g > 65535 ? (uint16_t)65535 : (uint16_t)g;
-    }
+    for (int c = 0; c < M; ++c) gain_q8[c] = any && gain_eligible(win[c], P.min_count) ? gain_q8_of(T, win[c]) : (uint16_t)256;
     if (target_out) *target_out = any ? (int32_t)std::min<u128>(T, 0x7fffffff) : 0;
     return DSSS_OK;
 }
@@ -660,20 +630,11 @@ int dsss_mosaic_gain_table_banded(const uint64_t* sum, const uint64_t* cnt, int 
     std::vector<uint16_t> pooled(M);
     int32_t Tp = 0;
     const int rc = dsss_mosaic_gain_table(Sp.data(), Cp.data(), M, &P, pooled.data(), &Tp); if (rc) return rc;      // (the parameter rules are its)
-    typedef unsigned __int128 u128;
-    const int half = M / 2;
-    const u128 T = (u128)Tp;
-    for (int b = 0; b < nbands; ++b) {
-        const uint64_t* S = sum + (size_t)b * M; const uint64_t* C = cnt + (size_t)b * M;
+    for (int b = 0; b < nbands; ++b)
         for (int c = 0; c < M; ++c) {
-            const int lo = std::max(c - P.smooth, c < half ? 0 : half), hi = std::min(c + P.smooth, c < half ? half - 1 : M - 1);      // never across the nadir
-            u128 s = 0, n = 0;
-            for (int k = lo; k <= hi; ++k) { s += S[k]; n += C[k]; }
-            if (!(n >= (u128)P.min_count && s > 0 && T > 0)) { gain_q8[(size_t)b * M + c] = pooled[c]; continue; }      // a thin band: the pooled column
-            const u128 g = (T * n * 256 + s / 2) / s;
-            gain_q8[(size_t)b * M + c] = g > 65535 ? (uint16_t)65535 : (uint16_t)g;
+            const gain_window w = gain_window_of(sum + (size_t)b * M, cnt + (size_t)b * M, M, P.smooth, c);
+            gain_q8[(size_t)b * M + c] = gain_eligible(w, P.min_count) && Tp > 0 ? gain_q8_of((u128)Tp, w) : pooled[c];      // a thin band: the pooled column
         }
-    }
     if (target_out) *target_out = Tp;
     return DSSS_OK;
 }
@@ -682,7 +643,7 @@ int dsss_mosaic_gain_table_banded(const uint64_t* sum, const uint64_t* cnt, int 
 // table in force.  (Every entry that reads the table synchronises before it returns, so no queued kernel still reads the old block.)
 static int gain_install(dsss_ctx* c, const uint16_t* gain_q8_host, int M, const dsss_gain_bands& bands)
 {
-    if (!gain_q8_host) { c->mosaic_gain_M = 0; c->mosaic_bands = dsss_gain_bands{ 0.0, 1.0, 1, 0 }; return DSSS_OK; }
+    if (!gain_q8_host) { c->mosaic_gain_M = 0; c->mosaic_bands = gain_one_band(); return DSSS_OK; }
     if (M < 2) DSSS_FAIL(c, DSSS_E_ARG, "gain: a table of %d columns", M);
     HIPCHK(c, hipSetDevice(c->device));
     const size_t bytes = (size_t)M * bands.nbands * sizeof(uint16_t);
@@ -697,14 +658,14 @@ static int gain_install(dsss_ctx* c, const uint16_t* gain_q8_host, int M, const 
 int dsss_mosaic_gain_set(dsss_ctx* c, const uint16_t* gain_q8_host, int M)
 {
     if (!c) return DSSS_E_ARG;
-    return gain_install(c, gain_q8_host, M, dsss_gain_bands{ 0.0, 1.0, 1, 0 });
+    return gain_install(c, gain_q8_host, M, gain_one_band());
 }
 
 int dsss_mosaic_gain_set_banded(dsss_ctx* c, const uint16_t* gain_q8_host, int M, const dsss_gain_bands* bands)
 {
     if (!c) return DSSS_E_ARG;
-    if (!gain_q8_host) return gain_install(c, nullptr, 0, dsss_gain_bands{ 0.0, 1.0, 1, 0 });
-    if (!gain_bands_ok(bands)) DSSS_FAIL(c, DSSS_E_ARG, "gain: bands %s", bands ? "outside the rules (nbands 1..16, alt0 and dalt finite, dalt > 0)" : "missing");
+    if (!gain_q8_host) return gain_install(c, nullptr, 0, gain_one_band());
+    const int rc = gain_check_bands(c, bands); if (rc) return rc;
     return gain_install(c, gain_q8_host, M, *bands);
 }
 

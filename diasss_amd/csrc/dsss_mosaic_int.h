@@ -15,13 +15,16 @@
 #define PYR_MAX_LEVELS 4                   // levels of a cell pyramid
 #define PYR_MAX_CENTRE (1 << 28)           // |cx|, |cy| of a level's centre: twice the centre plus the radius stays an int32
 
+// the one-band record: what a column table, or no table, is to everything that carries bands (every altitude lies in band 0)
+__host__ __device__ constexpr dsss_gain_bands gain_one_band() { return dsss_gain_bands{ 0.0, 1.0, 1, 0 }; }
+
 // one frame of a launch: its pose rows (the frame's own or the caller's trajectory), geometry and images; blk0 = its first workgroup;
 // gain = the context's range-gain table (M x u16, Q8), null: none set -- the same in every job of a launch, so the test is uniform
 // g0 = the canonical number of the frame's first ping (composite mosaic; the other kernels do not read it)
 // alt, bands = the frame's altitudes and the bands of a banded table ("altitude-banded range gain" in the header): gain then holds
 // bands.nbands rows of M, and a ping reads the row of its altitude's band; nbands == 1 (a column table, or none): alt is not read
 struct mosaic_job { const double* pose; const double* gr; const uint8_t* img; const uint8_t* mask; const uint16_t* gain; int N, M, blk0, g0;
-                    const double* alt = nullptr; dsss_gain_bands bands = { 0.0, 1.0, 1, 0 }; };
+                    const double* alt = nullptr; dsss_gain_bands bands = gain_one_band(); };
 // the grid (x0, y0, cell, W, H: where a point falls and whether it is kept) and the window of it the accumulators cover
 // (ox, oy, bw, bh: the whole grid for the mosaic, one frame's cell bounding box for the consistency map and the registration)
 struct mosaic_win { double x0, y0, cell; int W, H, ox, oy, bw, bh, use_mask; };

@@ -381,7 +381,7 @@ int dsss_mosaic_consistency(dsss_ctx*, const int* ids, int n, const double* rpy6
  * One row per altitude band instead of one for all pings, and the corrected waterfall as an output: "altitude-banded range gain" below. */
 typedef struct { int32_t min_count, smooth, target, pad_; } dsss_gain_params;
 void dsss_gain_params_default(dsss_gain_params*);
-/* S -> sum_host[M], C -> cnt_host[M] of the listed frames (mosaic_colstat_kernel: one launch for all frames) */
+/* S -> sum_host[M], C -> cnt_host[M] of the listed frames (mosaic_gainstat_kernel at one band: one launch for all frames) */
 int  dsss_mosaic_gain_stats(dsss_ctx*, const int* ids, int n, int use_mask, uint64_t* sum_host /* M */, uint64_t* cnt_host /* M */);
 int  dsss_mosaic_gain_table(const uint64_t* sum, const uint64_t* cnt, int M, const dsss_gain_params* /* NULL: defaults */,
                             uint16_t* gain_q8 /* M */, int32_t* target_out /* may be NULL */);
@@ -397,7 +397,7 @@ int  dsss_mosaic_gain_get(dsss_ctx*, uint16_t* gain_q8_host, int cap, int* M);  
  *   f64 values before any conversion, as in the cell arithmetic.  dsss_gain_band evaluates it on the host (no context): the one body
  *   the kernels run.  The altitude of a sample is alt[row] as the frame was set, never a row of the trajectory passed to an entry.
  * Statistics: S[b][c], C[b][c] = the sum and the number of the kept samples of column c over the pings whose band is b (nbands x M
- *   uint64 each; mosaic_bandstat_kernel, one launch for all frames).  Kept-sample rule, frame rules and errors are those of
+ *   uint64 each; mosaic_gainstat_kernel, one launch for all frames).  Kept-sample rule, frame rules and errors are those of
  *   dsss_mosaic_gain_stats, and summed over b the result is exactly its output.
  * Table (pure host arithmetic, no context): Sp[c] = sum_b S[b][c], Cp likewise; gp[c] and T = exactly what dsss_mosaic_gain_table
  *   returns on (Sp, Cp) with the same parameters.  S'_b, C'_b = the same-side smoothing window of that rule within band b.  Entry (b, c)

@@ -7,7 +7,7 @@ fixed to the grazing angle, which no table per column describes.  Binned under t
 (7.0, 1.0, 6), min_count 64, smooth 8.  Everything expected is the oracle's (normalize, mask, geo_img) and the numpy references';
 nothing here calls the library.  Computed once per session.
 
-The shape table: the shapes at which mosaic_bandstat_kernel takes another path and the altitude series that drive its band logic."""
+The shape table: the shapes at which mosaic_gainstat_kernel takes another path and the altitude series that drive its band logic."""
 import numpy as np
 
 from tests import mosaic_gain_bands_ref as B

@@ -1,6 +1,6 @@
 """GPU parity of the range-gain normalisation: dsss_mosaic_gain_stats exact against the reference at the shapes where
-mosaic_colstat_kernel takes another path, and every entry that bins samples (render, consistency, register, segments, yaw fan, pyramid)
-under a table against its existing numpy reference fed the corrected grey levels, bit for bit.
+mosaic_gainstat_kernel (here at one band) takes another path, and every entry that bins samples (render, consistency, register,
+segments, yaw fan, pyramid) under a table against its existing numpy reference fed the corrected grey levels, bit for bit.
 
 Nothing expected comes from the code under test: grey levels and masks are the oracle's, the statistics, the table and the corrected
 samples come from tests/mosaic_gain_ref.py, geo coordinates from the oracle's geo_img.  Frames 0 and 1 are the two legs of

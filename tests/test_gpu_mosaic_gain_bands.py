@@ -1,7 +1,8 @@
 """GPU parity of the altitude-banded range gain, everything exact: dsss_mosaic_gain_stats_banded against the reference at the shapes
-where mosaic_bandstat_kernel takes another path and under the altitude series that drive its band logic, dsss_frame_get_corrected on
-the same frames, and every entry that bins samples (render, consistency, register, segments, yaw fan, pyramid, composite) under a
-banded table against its existing numpy reference fed the grey levels of mosaic_gain_bands_ref.apply_banded.
+where mosaic_gainstat_kernel takes another path and under the altitude series that drive its band logic (and, on the same frames, the
+one-band launch behind dsss_mosaic_gain_stats against mosaic_gain_ref.col_stats), dsss_frame_get_corrected on the same frames, and
+every entry that bins samples (render, consistency, register, segments, yaw fan, pyramid, composite) under a banded table against
+its existing numpy reference fed the grey levels of mosaic_gain_bands_ref.apply_banded.
 
 Nothing expected comes from the code under test: grey levels and masks are the oracle's, the statistics, the table and the corrected
 samples come from tests/mosaic_gain_bands_ref.py, geo coordinates from the oracle's geo_img.  Frames 0 and 1 are the two legs of the
@@ -56,6 +57,8 @@ def _check_stats(c, ids, frames, alts, what):
             assert S.tolist() == rS, "%s bands %d mask %d: sums differ" % (what, bands[2], use_mask)
             cS, cC = c.mosaic_gain_stats(ids, use_mask)
             assert S.sum(axis=0).tolist() == cS.tolist() and C.sum(axis=0).tolist() == cC.tolist()      # summed over the bands: the column entry
+            gS, gC = G.col_stats(frames, use_mask)                                                     # ... which is the one kernel at one band: held to the reference itself
+            assert cS.tolist() == gS and cC.tolist() == gC, "%s mask %d: the column entry differs from the reference" % (what, use_mask)
 
 
 def _check_corrected(c, fid, norm, alt, what):

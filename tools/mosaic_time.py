@@ -16,8 +16,8 @@ three cell counts; --fill R fills enclosed holes within R cells.  With --gain bo
 synth.angle_profile(M, alt, gr, AMP, 6) (--alt-swing replaces the survey's altitudes by 10 + METRES sin(2 pi s / 20 + 0.9 f) first), B bands
 of equal width cover the altitudes, and the tool reports the banded statistics and table (min_count 64, smooth 8), the consistency
 score under the TRUE poses with no table, the column table and the banded table, and, interleaved call by call in one process (median,
-fastest and slowest of --calls after a warm-up round), dsss_mosaic_gain_stats (mosaic_colstat_kernel) against
-dsss_mosaic_gain_stats_banded (mosaic_bandstat_kernel) on the same frames and the render under the column against the banded table."""
+fastest and slowest of --calls after a warm-up round), dsss_mosaic_gain_stats (mosaic_gainstat_kernel at one band) against
+dsss_mosaic_gain_stats_banded (the same kernel at B bands) on the same frames and the render under the column against the banded table."""
 import argparse
 import json
 import os
