@@ -16,9 +16,9 @@ admits a library function a few ulps worse than glibc's and still fails a wrong 
 
 The exponential leaves the device only as ONE SCALAR: with two poses, dr6 = [0, xi], both supplied poses the identity and no closures,
 sums3[0] = 0.5 sum_a (odo_a Log(Pose3(Rodrigues(xi[:3]), xi[3:])^-1)_a)^2 -- a functional of pg_init_kernel's so3_exp and the logarithm, not
-the full map.  The device's pose_exp translation, pose_adjoint, pose_rpy and pose_retract are not reachable through today's API: they stay
-covered through the host build of the same text (test_pose_algebra_cpu.py) and the solve tests; how the device's atan2 and sin differ from
-glibc's outside these probes remains unprobed."""
+the full map.  This module keeps the view through the library's own entry.  The functions that leave through no entry -- pose_exp's
+translation, pose_adjoint, pose_rpy, pose_retract, and with them the device's atan2 -- are evaluated on the device one at a time by the
+stand-alone probe diasss_amd/host/dev_probe.hip and held to the same references and the same rule in tests/test_gpu_dev_probe.py."""
 import numpy as np
 import pytest
 

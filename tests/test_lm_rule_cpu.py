@@ -1,9 +1,10 @@
 """CPU: the LM decisions shared by lc_kernel, tri_kernel and the pose-graph LM (diasss_amd/csrc/dsss_lm.h) against a hand-written truth
 table of GTSAM's rule as oracle/orc_lc.c states it: the trial verdict on both sides of every comparison (linChange negative, zero, at and
 above eps * oldLin; fidelity at, below and above minFid; |costChange| around relTol * err; err == 0; NaN and infinite errors), the lambda
-schedule up to lamMax exactly, and the outer condition at maxIter - 1 / maxIter and with a non-finite cur.  The table lives in a stand-alone
-program (diasss_amd/host/lm_rule_check.cpp, own main) built with -fsanitize=address,undefined on the host side; nothing is preloaded and
-nothing is loaded into Python."""
+schedule up to lamMax exactly, and the outer condition at maxIter - 1 / maxIter and with a non-finite cur.  The rows are in
+diasss_amd/host/lm_rule_table.h; a stand-alone program walks them (diasss_amd/host/lm_rule_check.cpp, own main) built with
+-fsanitize=address,undefined on the host side; nothing is preloaded and nothing is loaded into Python.  The device walks the same rows in
+tests/test_gpu_dev_probe.py."""
 import os
 import subprocess
 
