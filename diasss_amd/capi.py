@@ -82,6 +82,19 @@ class CompInfo(C.Structure):
     _fields_ = [("direct", C.c_int64), ("filled", C.c_int64), ("empty", C.c_int64)]
 
 
+class FootprintParams(C.Structure):
+    """dsss_footprint_params: the most sub-samples of a sample along each of its two steps (1..8; 1: point samples) and the longest
+    step, in metres, that is bridged (finite, > 0).  The library's defaults are 4 and 1.0 (footprint_params_default)"""
+    _fields_ = [("max_steps", C.c_int32), ("pad_", C.c_int32), ("max_gap", C.c_double)]
+
+
+def _footprint(footprint):
+    """None (the library's defaults), a FootprintParams, or (max_steps, max_gap) -> what goes to the C argument"""
+    if footprint is None or isinstance(footprint, FootprintParams):
+        return footprint
+    return FootprintParams(int(footprint[0]), 0, float(footprint[1]))
+
+
 COMP_NEAR, COMP_FAR, COMP_MID, COMP_FIRST = 0, 1, 2, 3          # include/dsss.h DSSS_COMP_*
 COMP_MODES = {"near": COMP_NEAR, "far": COMP_FAR, "mid": COMP_MID, "first": COMP_FIRST}
 COMP_LAYERS = (("img", np.uint8), ("src_frame", np.int32), ("src_ping", np.int32), ("src_col", np.int32), ("fill", np.uint8))   # in the order of the C arguments
@@ -325,6 +338,16 @@ def lib():
         L.dsss_mosaic_composite.restype = C.c_int
         L.dsss_mosaic_composite.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(MosaicParams), C.POINTER(CompParams)] + [C.c_void_p] * 5 + [
             C.POINTER(CompInfo)]
+        L.dsss_footprint_params_default.restype = None
+        L.dsss_footprint_params_default.argtypes = [C.POINTER(FootprintParams)]
+        L.dsss_mosaic_footprint_steps.restype = C.c_int
+        L.dsss_mosaic_footprint_steps.argtypes = [C.POINTER(FootprintParams), C.c_double, C.c_double, C.c_double, C.POINTER(C.c_int32)]
+        L.dsss_mosaic_render_footprint.restype = C.c_int
+        L.dsss_mosaic_render_footprint.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(MosaicParams), C.POINTER(FootprintParams)] + [
+            C.c_void_p] * 3
+        L.dsss_mosaic_composite_footprint.restype = C.c_int
+        L.dsss_mosaic_composite_footprint.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(MosaicParams), C.POINTER(CompParams),
+                                                      C.POINTER(FootprintParams)] + [C.c_void_p] * 5 + [C.POINTER(CompInfo)]
         L.dsss_reg_params_default.argtypes = [C.POINTER(RegParams)]
         L.dsss_mosaic_register.restype = C.c_int
         L.dsss_mosaic_register.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(MosaicParams), C.c_void_p, C.c_void_p,
@@ -491,6 +514,22 @@ def mosaic_fill_host(valid, R):
     if rc != 0:
         raise _host_error(L, "dsss_mosaic_fill_host", rc)
     return donor, fill
+
+
+def footprint_params_default():
+    p = FootprintParams(); lib().dsss_footprint_params_default(C.byref(p)); return p
+
+
+def mosaic_footprint_steps(footprint, cell, sx, sy):
+    """dsss_mosaic_footprint_steps: the sub-samples along the step (sx, sy) on a grid of edge `cell` under `footprint` (a FootprintParams
+    or (max_steps, max_gap)).  Host arithmetic, no context."""
+    L = lib()
+    n = C.c_int32(-1)
+    fp = _footprint(footprint)
+    rc = L.dsss_mosaic_footprint_steps(C.byref(fp) if fp is not None else None, C.c_double(cell), C.c_double(sx), C.c_double(sy), C.byref(n))
+    if rc != 0:
+        raise _host_error(L, "dsss_mosaic_footprint_steps", rc)
+    return int(n.value)
 
 
 def _reg_pairs(pairs):
@@ -1076,6 +1115,36 @@ class Context:
         cp = CompParams(int(COMP_MODES.get(mode, mode)), int(fill_radius))
         self._chk(self.L.dsss_mosaic_composite(self.h, _ptr(ids), len(ids), _ptr(rpy6), _ptr(ping_off), C.byref(params), C.byref(cp),
                                                *[_ptr(out.get(n)) for n, _ in COMP_LAYERS], C.byref(info) if info is not None else None), "dsss_mosaic_composite")
+        return out, info
+
+    def mosaic_render_footprint(self, ids, params, rpy6=None, ping_off=None, download=True, footprint=None):
+        """dsss_mosaic_render_footprint: mosaic_render over the sub-samples of the samples' footprints.  footprint: a FootprintParams or
+        (max_steps, max_gap), None = the library's defaults (4, 1.0); max_steps 1 gives mosaic_render's layers bit for bit."""
+        ids, rpy6, ping_off = self._mosaic_traj(ids, rpy6, ping_off)
+        fp = _footprint(footprint)
+        out = (np.empty((params.H, params.W), np.uint32), np.empty((params.H, params.W), np.uint32),
+               np.empty((params.H, params.W), np.uint8)) if download else (None, None, None)
+        self._chk(self.L.dsss_mosaic_render_footprint(self.h, _ptr(ids), len(ids), _ptr(rpy6), _ptr(ping_off), C.byref(params),
+                                                      C.byref(fp) if fp is not None else None, _ptr(out[0]), _ptr(out[1]), _ptr(out[2])),
+                  "dsss_mosaic_render_footprint")
+        return out if download else None
+
+    def mosaic_composite_footprint(self, ids, params, mode=COMP_NEAR, fill_radius=0, rpy6=None, ping_off=None,
+                                   want=("img", "src_frame", "src_ping", "src_col", "fill"), footprint=None):
+        """dsss_mosaic_composite_footprint: mosaic_composite over the sub-samples of the samples' footprints, each with its parent's key,
+        value and source.  footprint as in mosaic_render_footprint; everything else as in mosaic_composite."""
+        ids, rpy6, ping_off = self._mosaic_traj(ids, rpy6, ping_off)
+        known = [n for n, _ in COMP_LAYERS] + ["info"]
+        for w in want:
+            if w not in known:
+                raise ValueError("mosaic_composite_footprint: no layer %r (%s)" % (w, ", ".join(known)))
+        out = {n: np.empty((params.H, params.W), t) for n, t in COMP_LAYERS if n in want}
+        info = CompInfo() if (out or "info" in want) else None
+        cp = CompParams(int(COMP_MODES.get(mode, mode)), int(fill_radius))
+        fp = _footprint(footprint)
+        self._chk(self.L.dsss_mosaic_composite_footprint(self.h, _ptr(ids), len(ids), _ptr(rpy6), _ptr(ping_off), C.byref(params), C.byref(cp),
+                                                         C.byref(fp) if fp is not None else None, *[_ptr(out.get(n)) for n, _ in COMP_LAYERS],
+                                                         C.byref(info) if info is not None else None), "dsss_mosaic_composite_footprint")
         return out, info
 
     def mosaic_gain_stats(self, ids, use_mask=1, bands=None):

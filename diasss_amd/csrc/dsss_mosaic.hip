@@ -45,6 +45,18 @@ __global__ __launch_bounds__(256) void mosaic_scatter_seg_kernel(const mosaic_jo
     mosaic_scatter_body<true>(jobs, njobs, G, acc, segs, seg_pings);
 }
 
+// The footprint form of mosaic_scatter_kernel ("footprint rendering" in the header), in its launch shape: the ping's prologue in the
+// partner form (sin and cos of both sides of the next ping beside the ping's own in LDS), then the sub-samples of the ping's samples
+// by the one body (mosaic_scatter_footprints, dsss_mosaic_int.h).  A kernel of its own: dsss_mosaic_render keeps the one above.
+__global__ __launch_bounds__(256) void mosaic_scatter_fp_kernel(const mosaic_job* __restrict__ jobs, int njobs, mosaic_win G, dsss_footprint_params F,
+                                                                unsigned long long* __restrict__ acc)
+{
+    __shared__ double s_sc[8];
+    mosaic_job J; int row; const double* P; const double* PP; bool last;
+    if (!mosaic_ping_of(jobs, njobs, s_sc, J, row, P, &PP, &last)) return;
+    mosaic_scatter_footprints(P, PP, last, s_sc, J, row, G, F, acc);
+}
+
 // accumulators -> the host layers' layout; flags a cell over the sample limit (also run with no outputs, as the check alone)
 __global__ __launch_bounds__(256) void mosaic_unpack_kernel(const unsigned long long* __restrict__ acc, size_t n, uint32_t* __restrict__ sum,
                                                             uint32_t* __restrict__ cnt, uint8_t* __restrict__ img, int* __restrict__ flag)
@@ -298,6 +310,24 @@ int mosaic_check_args(dsss_ctx* c, const int* ids, int n, const double* rpy6, co
     return mosaic_check_gain(c, ids, n);
 }
 
+bool footprint_params_ok(const dsss_footprint_params& F)
+{
+    return F.max_steps >= 1 && F.max_steps <= FP_MAX_STEPS && std::isfinite(F.max_gap) && F.max_gap > 0.0;
+}
+
+int mosaic_check_footprint(dsss_ctx* c, const int* ids, int n, const dsss_footprint_params* fp, dsss_footprint_params* out)
+{
+    dsss_footprint_params_default(out);
+    if (fp) *out = *fp;
+    out->pad_ = 0;
+    if (!footprint_params_ok(*out)) DSSS_FAIL(c, DSSS_E_ARG, "footprint: max_steps %d, max_gap %g (1..%d; finite and > 0)", out->max_steps, out->max_gap, FP_MAX_STEPS);
+    for (int i = 0; i < n; ++i) {
+        const int M = c->frames[ids[i]].M;
+        if (M < 4 || (M & 1)) DSSS_FAIL(c, DSSS_E_ARG, "footprint: frame %d has %d columns (even, at least 4)", ids[i], M);
+    }
+    return DSSS_OK;
+}
+
 // geo extremes of one frame under the given pose rows: x = px + g c is monotone in g for a fixed bearing, so only the smallest and the
 // largest ground range of a side can be extreme (what geo_bbox_kernel evaluates).  On the host: two bearings per ping, off the hot
 // path, and the same arithmetic bit for bit.  Non-finite points compare false and are left out.
@@ -440,12 +470,12 @@ int dsss_mosaic_bounds(dsss_ctx* c, const int* ids, int n, const double* rpy6, c
     return DSSS_OK;
 }
 
-int dsss_mosaic_render(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, const dsss_mosaic_params* p,
-                       uint32_t* sum_host, uint32_t* cnt_host, uint8_t* img_host)
+// The render behind the argument checks, for both entries: fp == null bins the samples as points (mosaic_scatter_kernel), otherwise the
+// sub-samples of their footprints (mosaic_scatter_fp_kernel); jobs, arena, sample-limit check and download are the same.
+static int render_run(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, const dsss_mosaic_params* p, size_t rows,
+                      const dsss_footprint_params* fp, uint32_t* sum_host, uint32_t* cnt_host, uint8_t* img_host)
 {
-    if (!c) return DSSS_E_ARG;
-    size_t rows = 0;
-    int rc = mosaic_check_args(c, ids, n, rpy6, ping_off, p, &rows); if (rc) return rc;
+    int rc;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t cells = (size_t)p->W * p->H;
     mosaic_arena A;
@@ -462,20 +492,22 @@ int dsss_mosaic_render(dsss_ctx* c, const int* ids, int n, const double* rpy6, c
     HIPCHK(c, hipMemsetAsync(d_flag, 0, sizeof(int), c->stream));
     const mosaic_win G = mosaic_grid_win(p);
     const unsigned ublocks = (unsigned)((cells + 255) / 256);
-    // launches of at most 2^31 samples, the sample limit checked between them: a cell's count then stays far below 2^32 until the
-    // check sees it, so the packed accumulator cannot wrap unnoticed whatever the number of frames
+    // launches of at most 2^31 samples (sub-samples: max_steps^2 a sample at most), the sample limit checked between them: a cell's count
+    // then stays far below 2^32 until the check sees it, so the packed accumulator cannot wrap unnoticed whatever the number of frames
+    const size_t per_sample = fp ? (size_t)fp->max_steps * fp->max_steps : 1;
     int j0 = 0;
     while (j0 < n) {
         int j1 = j0, blocks = 0; size_t samples = 0;
         while (j1 < n) {
             const dsss_frame& f = c->frames[ids[j1]];
-            const size_t s = (size_t)f.N * f.M;
+            const size_t s = (size_t)f.N * f.M * per_sample;
             if (j1 > j0 && samples + s > (1ull << 31)) break;
             jobs[j1].blk0 = blocks;
             blocks += f.N; samples += s; ++j1;
         }
         HIPCHK(c, hipMemcpyAsync(d_jobs + j0, jobs.data() + j0, (size_t)(j1 - j0) * sizeof(mosaic_job), hipMemcpyHostToDevice, c->stream));
-        launch_scatter(c, d_jobs + j0, j1 - j0, blocks, G, acc);
+        if (!fp) launch_scatter(c, d_jobs + j0, j1 - j0, blocks, G, acc);
+        else hipLaunchKernelGGL(mosaic_scatter_fp_kernel, dim3((unsigned)blocks), dim3(256), 0, c->stream, d_jobs + j0, j1 - j0, G, *fp, acc);
         HIPCHK(c, hipGetLastError());
         if (j1 < n) { hipLaunchKernelGGL(mosaic_unpack_kernel, dim3(ublocks), dim3(256), 0, c->stream, acc, cells, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint8_t*)nullptr, d_flag); HIPCHK(c, hipGetLastError()); }
         j0 = j1;
@@ -488,6 +520,36 @@ int dsss_mosaic_render(dsss_ctx* c, const int* ids, int n, const double* rpy6, c
     if (img_host) HIPCHK(c, hipMemcpyAsync(img_host, d_img, cells, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return DSSS_OK;
+}
+
+int dsss_mosaic_render(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, const dsss_mosaic_params* p,
+                       uint32_t* sum_host, uint32_t* cnt_host, uint8_t* img_host)
+{
+    if (!c) return DSSS_E_ARG;
+    size_t rows = 0;
+    const int rc = mosaic_check_args(c, ids, n, rpy6, ping_off, p, &rows); if (rc) return rc;
+    return render_run(c, ids, n, rpy6, ping_off, p, rows, nullptr, sum_host, cnt_host, img_host);
+}
+
+// ---- footprint rendering
+void dsss_footprint_params_default(dsss_footprint_params* p) { if (p) { p->max_steps = 4; p->pad_ = 0; p->max_gap = 1.0; } }
+
+int dsss_mosaic_footprint_steps(const dsss_footprint_params* fp, double cell, double sx, double sy, int32_t* n)
+{
+    if (!fp || !n || !footprint_params_ok(*fp) || !(cell > 0.0) || !std::isfinite(cell)) return DSSS_E_ARG;
+    *n = footprint_steps(*fp, cell, sx, sy);
+    return DSSS_OK;
+}
+
+int dsss_mosaic_render_footprint(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, const dsss_mosaic_params* p,
+                                 const dsss_footprint_params* fp, uint32_t* sum_host, uint32_t* cnt_host, uint8_t* img_host)
+{
+    if (!c) return DSSS_E_ARG;
+    size_t rows = 0;
+    int rc = mosaic_check_args(c, ids, n, rpy6, ping_off, p, &rows); if (rc) return rc;
+    dsss_footprint_params F;
+    rc = mosaic_check_footprint(c, ids, n, fp, &F); if (rc) return rc;
+    return render_run(c, ids, n, rpy6, ping_off, p, rows, &F, sum_host, cnt_host, img_host);
 }
 
 // ---- range-gain normalisation

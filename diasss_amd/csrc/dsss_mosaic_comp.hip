@@ -36,6 +36,26 @@ __global__ __launch_bounds__(256) void mosaic_composite_kernel(const mosaic_job*
     }
 }
 
+// The footprint form ("footprint rendering" in the header), in the same launch shape: the ping's prologue in the partner form, the
+// sub-samples by the one body of the footprint kernels (mosaic_footprint_samples).  A sub-sample competes with its parent's q << 16 | col,
+// so the sub-samples of one parent in a cell are one key: the minimum over a run and the atomicMin see them as one sample.
+__global__ __launch_bounds__(256) void mosaic_composite_fp_kernel(const mosaic_job* __restrict__ jobs, int njobs, mosaic_win G, dsss_footprint_params F,
+                                                                  int mode, unsigned long long* __restrict__ keys)
+{
+    __shared__ double s_sc[8];
+    mosaic_job J; int row; const double* P; const double* PP; bool last;
+    if (!mosaic_ping_of(jobs, njobs, s_sc, J, row, P, &PP, &last)) return;
+    const int M = J.M;
+    const unsigned long long gbits = (unsigned long long)(unsigned)(J.g0 + row) << 16;
+    mosaic_footprint_samples(P, PP, last, s_sc, J, row, G, F,
+        [&](int col) { return ((unsigned)comp_rank(mode, M, col) << 16) | (unsigned)col; },
+        [&](int cell, unsigned k) {
+            unsigned v = cell >= 0 ? k : ~0u;
+            const bool tail = mosaic_run_reduce(cell, v, [](unsigned a, unsigned b) { return min(a, b); });
+            if (tail && cell >= 0) atomicMin(&keys[cell], ((unsigned long long)(v >> 16) << 47) | gbits | (v & 0xffffu));
+        });
+}
+
 // One thread per cell and RESOLVE_CELLS cells after one another per thread: the key back into the winner's value and source.  The frame
 // of g by binary search over the jobs' g0, which the host sorts by frame id and hence by g0; ids[j] = the frame id of job j.  The g0 of up
 // to RESOLVE_G0 jobs are staged in LDS; a longer table is searched where it lies (a search per cell on another key and from two places:
@@ -162,22 +182,30 @@ int dsss_mosaic_fill_host(const uint8_t* valid, int W, int H, int R, int32_t* do
     return DSSS_OK;
 }
 
-int dsss_mosaic_composite(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, const dsss_mosaic_params* p,
-                          const dsss_comp_params* cp, uint8_t* img_host, int32_t* src_frame_host, int32_t* src_ping_host, int32_t* src_col_host,
-                          uint8_t* fill_host, dsss_comp_info* info_host)
+// the argument rules of both composite entries: those of the mean render, then the composite's parameters (*P: the caller's or the
+// defaults) and the frames' M; *rows = the pings of the listed frames
+static int comp_check(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, const dsss_mosaic_params* p,
+                      const dsss_comp_params* cp, dsss_comp_params* P, size_t* rows)
 {
-    if (!c) return DSSS_E_ARG;
-    size_t rows = 0;
-    int rc = mosaic_check_args(c, ids, n, rpy6, ping_off, p, &rows); if (rc) return rc;
-    dsss_comp_params P;
-    dsss_comp_params_default(&P);
-    if (cp) P = *cp;
-    if (P.mode < 0 || P.mode > DSSS_COMP_FIRST) DSSS_FAIL(c, DSSS_E_ARG, "composite: mode %d", P.mode);
-    if (P.fill_radius < 0 || P.fill_radius > COMP_MAX_FILL) DSSS_FAIL(c, DSSS_E_ARG, "composite: fill_radius %d outside 0..%d", P.fill_radius, COMP_MAX_FILL);
+    const int rc = mosaic_check_args(c, ids, n, rpy6, ping_off, p, rows); if (rc) return rc;
+    dsss_comp_params_default(P);
+    if (cp) *P = *cp;
+    if (P->mode < 0 || P->mode > DSSS_COMP_FIRST) DSSS_FAIL(c, DSSS_E_ARG, "composite: mode %d", P->mode);
+    if (P->fill_radius < 0 || P->fill_radius > COMP_MAX_FILL) DSSS_FAIL(c, DSSS_E_ARG, "composite: fill_radius %d outside 0..%d", P->fill_radius, COMP_MAX_FILL);
     for (int i = 0; i < n; ++i) {
         const int M = c->frames[ids[i]].M;
         if (M < 4 || (M & 1) || M > COMP_MAX_M) DSSS_FAIL(c, DSSS_E_ARG, "composite: frame %d has %d columns (even, 4..%d)", ids[i], M, COMP_MAX_M);
     }
+    return DSSS_OK;
+}
+
+// The composite behind the argument checks, for both entries: fp == null scatters the samples as points (mosaic_composite_kernel),
+// otherwise the sub-samples of their footprints (mosaic_composite_fp_kernel); resolve, fill, counts and downloads are the same.
+static int comp_run(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, const dsss_mosaic_params* p, size_t rows,
+                    const dsss_comp_params& P, const dsss_footprint_params* fp, uint8_t* img_host, int32_t* src_frame_host, int32_t* src_ping_host,
+                    int32_t* src_col_host, uint8_t* fill_host, dsss_comp_info* info_host)
+{
+    int rc;
     HIPCHK(c, hipSetDevice(c->device));
     // the canonical order: ascending frame id, whatever the order of ids; the job table is sorted by it and hence by g0 and blk0
     std::vector<int> order(n);
@@ -207,7 +235,8 @@ int dsss_mosaic_composite(dsss_ctx* c, const int* ids, int n, const double* rpy6
     HIPCHK(c, hipMemsetAsync(d_keys, 0xff, cells * 8, c->stream));
     HIPCHK(c, hipMemsetAsync(d_cnt, 0, (COMP_SLOTS + 1) * sizeof(unsigned long long), c->stream));
     const mosaic_win G = mosaic_grid_win(p);
-    if (g0) hipLaunchKernelGGL(mosaic_composite_kernel, dim3((unsigned)g0), dim3(256), 0, c->stream, d_jobs, n, G, P.mode, d_keys);
+    if (g0 && !fp) hipLaunchKernelGGL(mosaic_composite_kernel, dim3((unsigned)g0), dim3(256), 0, c->stream, d_jobs, n, G, P.mode, d_keys);
+    if (g0 && fp) hipLaunchKernelGGL(mosaic_composite_fp_kernel, dim3((unsigned)g0), dim3(256), 0, c->stream, d_jobs, n, G, *fp, P.mode, d_keys);
     HIPCHK(c, hipGetLastError());
     hipLaunchKernelGGL(mosaic_resolve_kernel, dim3((unsigned)((cells + 256 * RESOLVE_CELLS - 1) / (256 * RESOLVE_CELLS))), dim3(256), 0, c->stream, d_keys, cells, d_jobs, d_ids, n,
                        d_img, d_fr, d_pg, d_col, d_fill, d_cnt);
@@ -233,6 +262,30 @@ int dsss_mosaic_composite(dsss_ctx* c, const int* ids, int n, const double* rpy6
         info_host->empty = (int64_t)(cells - direct - cnt[COMP_SLOTS]);
     }
     return DSSS_OK;
+}
+
+int dsss_mosaic_composite(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, const dsss_mosaic_params* p,
+                          const dsss_comp_params* cp, uint8_t* img_host, int32_t* src_frame_host, int32_t* src_ping_host, int32_t* src_col_host,
+                          uint8_t* fill_host, dsss_comp_info* info_host)
+{
+    if (!c) return DSSS_E_ARG;
+    size_t rows = 0;
+    dsss_comp_params P;
+    const int rc = comp_check(c, ids, n, rpy6, ping_off, p, cp, &P, &rows); if (rc) return rc;
+    return comp_run(c, ids, n, rpy6, ping_off, p, rows, P, nullptr, img_host, src_frame_host, src_ping_host, src_col_host, fill_host, info_host);
+}
+
+int dsss_mosaic_composite_footprint(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, const dsss_mosaic_params* p,
+                                    const dsss_comp_params* cp, const dsss_footprint_params* fp, uint8_t* img_host, int32_t* src_frame_host,
+                                    int32_t* src_ping_host, int32_t* src_col_host, uint8_t* fill_host, dsss_comp_info* info_host)
+{
+    if (!c) return DSSS_E_ARG;
+    size_t rows = 0;
+    dsss_comp_params P;
+    int rc = comp_check(c, ids, n, rpy6, ping_off, p, cp, &P, &rows); if (rc) return rc;
+    dsss_footprint_params F;
+    rc = mosaic_check_footprint(c, ids, n, fp, &F); if (rc) return rc;
+    return comp_run(c, ids, n, rpy6, ping_off, p, rows, P, &F, img_host, src_frame_host, src_ping_host, src_col_host, fill_host, info_host);
 }
 
 } // extern "C"

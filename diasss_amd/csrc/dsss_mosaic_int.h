@@ -1,6 +1,7 @@
 // diasss_amd/csrc/dsss_mosaic_int.h -- what dsss_mosaic.hip (mosaic, consistency map), dsss_mosaic_reg.hip (overlap registration) and
 // dsss_mosaic_comp.hip (composite mosaic) share.  Device: the job and window records of mosaic_scatter_kernel, the binning of a sample, the
-// kernels' scaffolding written once (job lookup mosaic_job_of, ping prologue mosaic_ping_of, segmented reduction mosaic_run_reduce), then
+// kernels' scaffolding written once (job lookup mosaic_job_of, ping prologue mosaic_ping_of, segmented reduction mosaic_run_reduce), the
+// sub-samples of the footprint kernels (footprint_steps, mosaic_footprint_samples), then
 // the rules of the composite and the score, order and sub-cell rules of the registration, one body for host and device.  Host: the typed
 // arena over mosaic_buf, the argument rules (mosaic_check_args), the windows of the grid (mosaic_grid_win, mosaic_window), the sample-limit
 // flag (mosaic_flag_down), the upload of a caller's trajectory and the scatter launch, defined in dsss_mosaic.hip, and what
@@ -52,6 +53,29 @@ __device__ __forceinline__ const uint16_t* mosaic_gain_row(const mosaic_job& J, 
     return J.bands.nbands > 1 ? J.gain + (size_t)gain_band(J.bands, J.alt[row]) * J.M : J.gain;
 }
 
+// The three rules of a sample on the device, each written once: the mask test (mosaic_sample_kept: -1 for a column behind M or one the
+// mask rejects, what kept() returns otherwise; mask = the ping's row of the frame's mask), the cell of the window G a point falls into
+// (mosaic_point_cell: -1 off the grid or the window or not finite, otherwise the cell, after kept() ran) and the corrected value
+// (mosaic_gain_apply above).  mosaic_sample_cell puts them together for a point sample, mosaic_footprint_samples for the sub-samples of
+// a footprint.  What follows a test is handed in and runs in tail position, so a caller's code is what it was with the tests written
+// out in it (the point kernels' instructions did not change when these were split off).
+template <class KEPT>
+__device__ __forceinline__ int mosaic_sample_kept(int M, const uint8_t* __restrict__ mask, int col, const mosaic_win& G, KEPT kept)
+{
+    if (col >= M || (G.use_mask && mask[col] == 0)) return -1;
+    return kept();
+}
+template <class KEPT>
+__device__ __forceinline__ int mosaic_point_cell(double x, double y, const mosaic_win& G, KEPT kept)
+{
+    const double fx = floor((x - G.x0) / G.cell), fy = floor((y - G.y0) / G.cell);
+    if (!(fx >= 0.0 && fx < (double)G.W && fy >= 0.0 && fy < (double)G.H)) return -1;   // on the f64 values: NaN, infinite and huge points drop out here
+    const int ix = (int)fx - G.ox, iy = (int)fy - G.oy;
+    if (!(ix >= 0 && ix < G.bw && iy >= 0 && iy < G.bh)) return -1;
+    kept();
+    return iy * G.bw + ix;
+}
+
 // The one place a sample is binned on the device: the cell of the window G that the sample (row, col) falls into, -1 when it is
 // dropped (mask, off the grid or the window, not finite), and *val = its corrected value.  P = the ping's pose row, sc = sin and cos of
 // the bearing of the port and of the starboard side (dsss_geo_side on P, in LDS), img, mask = the ping's row of the frame's images.
@@ -60,16 +84,12 @@ __device__ __forceinline__ int mosaic_sample_cell(const double* P, const double*
                                                   const uint8_t* __restrict__ mask, int col, const mosaic_win& G, unsigned* val)
 {
     const int M = J.M, half = M / 2;
-    if (col >= M || (G.use_mask && mask[col] == 0)) return -1;
-    const int side = col >= half;
-    double x, y;
-    dsss_geo_bin(P, J.gr, M, col, sc[2 * side], sc[2 * side + 1], &x, &y);
-    const double fx = floor((x - G.x0) / G.cell), fy = floor((y - G.y0) / G.cell);
-    if (!(fx >= 0.0 && fx < (double)G.W && fy >= 0.0 && fy < (double)G.H)) return -1;   // on the f64 values: NaN, infinite and huge points drop out here
-    const int ix = (int)fx - G.ox, iy = (int)fy - G.oy;
-    if (!(ix >= 0 && ix < G.bw && iy >= 0 && iy < G.bh)) return -1;
-    *val = mosaic_gain_apply(img[col], J.gain, col);                               // (J.gain: uniform per workgroup)
-    return iy * G.bw + ix;
+    return mosaic_sample_kept(M, mask, col, G, [&] {
+        const int side = col >= half;
+        double x, y;
+        dsss_geo_bin(P, J.gr, M, col, sc[2 * side], sc[2 * side + 1], &x, &y);
+        return mosaic_point_cell(x, y, G, [&] { *val = mosaic_gain_apply(img[col], J.gain, col); });      // (J.gain: uniform per workgroup)
+    });
 }
 
 // The job of this workgroup in a table whose blk0 ascend from 0: the last one whose blk0 is not above blockIdx.x.  The one job lookup
@@ -84,13 +104,22 @@ template <class JOB> __device__ __forceinline__ JOB mosaic_job_of(const JOB* __r
 // What a workgroup of one ping does first (mosaic_scatter_kernel, mosaic_composite_kernel): its job J, the ping's row in the frame and
 // pose row P, and sin and cos of the bearing of each side in s_sc (the kernel's __shared__ double[4]), behind the barrier.  False: the
 // workgroup has no ping; it leaves in front of the barrier (uniform per workgroup; cannot happen with the host's blk0).
-__device__ __forceinline__ bool mosaic_ping_of(const mosaic_job* __restrict__ jobs, int njobs, double* s_sc, mosaic_job& J, int& row, const double*& P)
+// The partner form (PP given; the footprint kernels): *PP = the pose row of the ping's partner, the next ping of the frame, or the one
+// before for the frame's last ping (*last; a frame of one ping is its own partner), and s_sc is the kernel's __shared__ double[8]: behind
+// the ping's four values, sin and cos of both sides of the partner.
+__device__ __forceinline__ bool mosaic_ping_of(const mosaic_job* __restrict__ jobs, int njobs, double* s_sc, mosaic_job& J, int& row, const double*& P,
+                                               const double** PP = nullptr, bool* last = nullptr)
 {
     J = mosaic_job_of(jobs, njobs); row = (int)blockIdx.x - J.blk0;
     if (row >= J.N) return false;
     P = J.pose + (size_t)row * 6;
     J.gain = mosaic_gain_row(J, row);                                              // the ping's band, once per workgroup: the samples see a column table
-    if (threadIdx.x < 2) dsss_geo_side(P, threadIdx.x == 1, &s_sc[2 * threadIdx.x], &s_sc[2 * threadIdx.x + 1]);
+    if (PP) {
+        *last = row == J.N - 1;
+        *PP = J.pose + (size_t)(*last ? (row > 0 ? row - 1 : row) : row + 1) * 6;
+        if (threadIdx.x < 4) dsss_geo_side(threadIdx.x < 2 ? P : *PP, threadIdx.x & 1, &s_sc[2 * threadIdx.x], &s_sc[2 * threadIdx.x + 1]);
+    }
+    else if (threadIdx.x < 2) dsss_geo_side(P, threadIdx.x == 1, &s_sc[2 * threadIdx.x], &s_sc[2 * threadIdx.x + 1]);
     __syncthreads();
     return true;
 }
@@ -125,6 +154,85 @@ __device__ __forceinline__ void mosaic_scatter_samples(const double* P, const do
         const bool tail = mosaic_run_reduce(key, v, [](unsigned a, unsigned b) { return a + b; });
         if (tail && key >= 0) atomicAdd(&acc[key], ((unsigned long long)(v >> 16) << 32) | (v & 0xffffu));
     }
+}
+
+// ---- footprint rendering ("footprint rendering" in the header): a sample stands for the area up to the next ping and the next bin
+#define FP_MAX_STEPS 8
+// the sub-samples along a step S = (sx, sy), ONE body for dsss_mosaic_footprint_steps and the kernels (F and cell as the entries admit
+// them); every comparison on the f64 values: a NaN or infinite component fails the first test
+__host__ __device__ inline int footprint_steps(const dsss_footprint_params& F, double cell, double sx, double sy)
+{
+    const double ax = fabs(sx), ay = fabs(sy);
+    if (!(ax <= 1.7976931348623157e308 && ay <= 1.7976931348623157e308)) return 1;  // not finite
+    const double l = ax > ay ? ax : ay;
+    if (l > F.max_gap) return 1;                                                   // a jump is not bridged
+    const double t = ceil(l / cell);
+    if (t < 1.0) return 1;
+    if (t > (double)F.max_steps) return F.max_steps;
+    return (int)t;
+}
+
+// The sub-samples of one ping, by the 256 threads of its workgroup: what mosaic_scatter_samples does for the samples.  PP = the pose row
+// of the partner ping and last (mosaic_ping_of's partner form), sc = the eight values it left in LDS.  A lane owns a column: its point,
+// the partner ping's and its across neighbour's (three dsss_geo_bin), the along step A and the across step B, and na, nc sub-samples
+// along them -- 0 for a lane whose sample is not kept.  The (i, j) loops run to the wavefront's maxima of na and nc, uniform over the
+// wavefront, because the shuffles of mosaic_run_reduce need every lane; a lane with i >= na or j >= nc carries key -1.  Consecutive
+// columns still walk through the grid for a fixed (i, j), so runs form as they do for the samples.  value(col) = what the lane
+// contributes, once per kept sample; emit(key, v) = the reduction over the runs and the run's one atomic.  Every operation on a
+// coordinate is one unfused IEEE operation in the order of the header; x + (i / na) ax does not depend on j and is formed once per i.
+template <class VALUE, class EMIT>
+__device__ __forceinline__ void mosaic_footprint_samples(const double* P, const double* PP, bool last, const double* sc, const mosaic_job& J, int row,
+                                                         const mosaic_win& G, const dsss_footprint_params& F, VALUE value, EMIT emit)
+{
+    const int M = J.M, half = M / 2;
+    const uint8_t* __restrict__ mask = J.mask + (size_t)row * M;
+    for (int c0 = 0; c0 < M; c0 += 256) {
+        const int col = c0 + (int)threadIdx.x;
+        double x = 0.0, y = 0.0, ax = 0.0, ay = 0.0, bx = 0.0, by = 0.0;
+        int na = 0, nc = 0;
+        unsigned v = 0;
+        mosaic_sample_kept(M, mask, col, G, [&] {
+            const int side = col >= half, idx = dsss_geo_index(M, col);
+            const bool outer = idx >= half - 1;                                    // the side's last index: the step comes from the bin inside
+            const int nidx = outer ? idx - 1 : idx + 1, ncol = side ? half + nidx : half - nidx;
+            const double s = sc[2 * side], c = sc[2 * side + 1];
+            double xn, yn, xp, yp;
+            dsss_geo_bin(P, J.gr, M, col, s, c, &x, &y);
+            dsss_geo_bin(P, J.gr, M, ncol, s, c, &xn, &yn);
+            dsss_geo_bin(PP, J.gr, M, col, sc[4 + 2 * side], sc[5 + 2 * side], &xp, &yp);
+            ax = last ? x - xp : xp - x; ay = last ? y - yp : yp - y;              // (a frame of one ping: x - x, one sub-sample either way)
+            bx = outer ? x - xn : xn - x; by = outer ? y - yn : yn - y;
+            na = footprint_steps(F, G.cell, ax, ay); nc = footprint_steps(F, G.cell, bx, by);
+            v = value(col);
+            return 0;
+        });
+        int na_max = 0, nc_max = 0;                                                // over the wavefront: scalar
+#pragma unroll
+        for (int k = 0; k < FP_MAX_STEPS; ++k) { na_max += __ballot(na > k) != 0ull; nc_max += __ballot(nc > k) != 0ull; }
+        for (int i = 0; i < na_max; ++i) {
+            double xi = x, yi = y;
+            if (i > 0) { const double q = (double)i / (double)na; xi = xi + q * ax; yi = yi + q * ay; }
+            for (int j = 0; j < nc_max; ++j) {
+                double xs = xi, ys = yi;
+                if (j > 0) { const double q = (double)j / (double)nc; xs = xs + q * bx; ys = ys + q * by; }
+                emit(i < na && j < nc ? mosaic_point_cell(xs, ys, G, [] {}) : -1, v);
+            }
+        }
+    }
+}
+
+// the mean's sub-samples: mosaic_scatter_samples' sum and count over the runs, the parent's corrected value
+__device__ __forceinline__ void mosaic_scatter_footprints(const double* P, const double* PP, bool last, const double* sc, const mosaic_job& J, int row,
+                                                          const mosaic_win& G, const dsss_footprint_params& F, unsigned long long* __restrict__ acc)
+{
+    const uint8_t* __restrict__ img = J.img + (size_t)row * J.M;
+    mosaic_footprint_samples(P, PP, last, sc, J, row, G, F,
+        [&](int col) { return (1u << 16) | mosaic_gain_apply(img[col], J.gain, col); },
+        [&](int key, unsigned g) {
+            unsigned v = key >= 0 ? g : 0u;
+            const bool tail = mosaic_run_reduce(key, v, [](unsigned a, unsigned b) { return a + b; });
+            if (tail && key >= 0) atomicAdd(&acc[key], ((unsigned long long)(v >> 16) << 32) | (v & 0xffffu));
+        });
 }
 
 // ---- composite mosaic ("composite mosaic" in the header; dsss_mosaic_comp.hip).  A cell's key: q << 47 | g << 16 | col, 15 + 31 + 16
@@ -248,6 +356,10 @@ int mosaic_check_params(dsss_ctx* c, const dsss_mosaic_params* p);
 // the argument rules of every entry that bins samples onto a grid, in the order the error precedence rests on: the frames
 // (mosaic_check_frames with their images; *rows = their pings), then the grid, then the range-gain table
 int mosaic_check_args(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, const dsss_mosaic_params* p, size_t* rows);
+// the one rule the footprint entries add, behind mosaic_check_args: *out = the caller's parameters, or the defaults for null, inside
+// their ranges, and every listed frame has an even M of at least 4
+bool footprint_params_ok(const dsss_footprint_params& F);
+int mosaic_check_footprint(dsss_ctx* c, const int* ids, int n, const dsss_footprint_params* fp, dsss_footprint_params* out);
 void frame_extent(const dsss_frame& f, const double* rows, double* bb);
 void frame_extent_rows(const dsss_frame& f, const double* rows, int r0, int r1, double* bb);      // pings [r0, r1) only
 bool cell_range(double lo, double hi, double origin, double cell, int n, int* a, int* b);

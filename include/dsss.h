@@ -470,6 +470,59 @@ int  dsss_mosaic_composite(dsss_ctx*, const int* ids, int n, const double* rpy6,
                            const dsss_comp_params* /* NULL: defaults */, uint8_t* img_host, int32_t* src_frame_host,
                            int32_t* src_ping_host, int32_t* src_col_host, uint8_t* fill_host, dsss_comp_info* info_host);
 
+/* ---- footprint rendering: mosaics without holes between pings and bins.  The entries above bin every sample as a point, so a cell
+ * edge at or below the ping spacing or the bin spacing leaves empty rows between pings and empty columns between bins.  Here a sample
+ * stands for its footprint, the area up to the next ping and the next bin, and is binned at up to max_steps x max_steps sub-samples of
+ * it.  Integer work behind the f64 cell arithmetic, as everywhere in this section: independent of the order of ids, of execution and
+ * of the call.  No existing entry changes.
+ * Parameters: max_steps in 1..8 (default 4), max_gap in metres, finite and > 0 (default 1.0).  Neither default has been tuned on any
+ *   data, as the registration's defaults have not.
+ * Points: P(r, c) = (x, y) = dsss_frame_get_geo's point of ping r and column c under the rows in force (rpy6 / ping_off, or the frame's
+ *   own pose6).  idx = the ground-range index of c ("composite mosaic" above), half = M / 2, N = the frame's pings.
+ * Along step A(r, c), each component ONE f64 subtraction: r < N - 1: P(r + 1, c) - P(r, c); the last ping: P(N - 1, c) - P(N - 2, c),
+ *   the step before it, so that consecutive frames of a leg leave no stripe between them; N == 1: (0, 0).
+ * Across step B(r, c), outward on the sample's own side: idx < half - 1: P(r, c+) - P(r, c), c+ = the column of the same side with
+ *   index idx + 1 (c + 1 on starboard, c - 1 on port); the outermost index (starboard M - 1, and port 0 and 1, which share it):
+ *   P(r, c) - P(r, c-), c- = the same side's point of index idx - 1 (column M - 2 on starboard, 2 on port; with M == 4 the port side
+ *   has no column of index 0 and the point is gr[0] under the port bearing).
+ * Step count n(S) of a step S = (sx, sy), every comparison on the f64 values before any conversion: sx or sy not finite: 1;
+ *   l = the larger of |sx| and |sy| (per axis, so consecutive sub-samples move at most one cell on either axis); l > max_gap: 1 (a jump
+ *   is not bridged); t = ceil(l / cell); n = 1 if t < 1, max_steps if t > max_steps, (int)t otherwise.  dsss_mosaic_footprint_steps
+ *   evaluates it on the host (no context): the one body the kernels run.
+ * Sub-samples of a sample (r, c).  The parent is kept iff use_mask == 0 or flt_mask[r, c] != 0: the only test on the parent, which need
+ *   not lie on the grid itself.  na = n(A), nc = n(B); for i in [0, na), j in [0, nc): X = x; if i > 0: X = X + ((double)i / (double)na) Ax;
+ *   if j > 0: X = X + ((double)j / (double)nc) Bx; Y the same with the same two quotients.  Every operation is a single unfused IEEE
+ *   operation in exactly this order; sub-sample (0, 0) is the point itself and is never recomputed.  Each sub-sample is binned and
+ *   range-tested on its own by the f64 cell arithmetic above.  Its value is the parent's normalised u8, corrected by the gain table in
+ *   force with the parent's column and the parent's altitude band.
+ * dsss_mosaic_render_footprint: sum, cnt and img of dsss_mosaic_render over the sub-samples (mosaic_scatter_fp_kernel).  The 2^24 rule
+ *   counts sub-samples; DSSS_E_CAPACITY as there.
+ * dsss_mosaic_composite_footprint: the layers and info of dsss_mosaic_composite over the sub-samples (mosaic_composite_fp_kernel).  A
+ *   sub-sample competes with its parent's key (q, g, col) and carries its parent's value and source (frame, ping, col); several
+ *   sub-samples of one parent in a cell are one key and one value, so the winner stays unique and order-free.  V0 = the cells that hold
+ *   a sub-sample; fill and the gap fill work on that V0 unchanged.
+ * Consequences: with max_steps == 1 both entries equal dsss_mosaic_render / dsss_mosaic_composite bit for bit in every layer; for any
+ *   parameters cnt of the footprint render >= cnt of the point render in every cell.
+ * Out of scope: dsss_mosaic_consistency and every registration entry keep point samples (their mean layers are defined on one another,
+ *   and a footprint would change the ZNCC tables); the strip between port index 1 and starboard index 0, the nadir, where a frame holds
+ *   no sample, is not covered; values are not blended between pings (the value is the parent's, so the composite's source layers stay
+ *   true); the extrapolated step of a frame's last ping may reach beyond dsss_mosaic_bounds: such sub-samples are off the grid and are
+ *   dropped.
+ * Errors.  DSSS_E_ARG, before anything is reserved, cleared or launched: whatever the point entry refuses (a gain table of another M
+ *   included), max_steps outside 1..8, max_gap not finite or <= 0, a listed frame whose M is odd or below 4 (both entries: the across
+ *   step needs index half - 2); for the host function a NULL pointer, a cell <= 0 or not finite, parameters out of range.  DSSS_E_STATE
+ *   as dsss_mosaic_render.  Every error leaves the context usable and a gain table that was set in place.                            */
+typedef struct { int32_t max_steps, pad_; double max_gap; } dsss_footprint_params;      /* defaults 4, 1.0: not tuned on any data */
+void dsss_footprint_params_default(dsss_footprint_params*);
+/* pure host arithmetic, no context: the step count n(S), the one body the kernels run */
+int  dsss_mosaic_footprint_steps(const dsss_footprint_params*, double cell, double sx, double sy, int32_t* n);
+int  dsss_mosaic_render_footprint(dsss_ctx*, const int* ids, int n, const double* rpy6, const int* ping_off, const dsss_mosaic_params*,
+                                  const dsss_footprint_params* /* NULL: defaults */, uint32_t* sum_host, uint32_t* cnt_host, uint8_t* img_host);
+int  dsss_mosaic_composite_footprint(dsss_ctx*, const int* ids, int n, const double* rpy6, const int* ping_off, const dsss_mosaic_params*,
+                                     const dsss_comp_params* /* NULL: defaults */, const dsss_footprint_params* /* NULL: defaults */,
+                                     uint8_t* img_host, int32_t* src_frame_host, int32_t* src_ping_host, int32_t* src_col_host,
+                                     uint8_t* fill_host, dsss_comp_info* info_host);
+
 /* ---- overlap registration: how far, in metres and in which direction, frame b lies from where its overlap with frame a says it belongs.
  * An independent, metric, per-pair measure of a trajectory (the consistency score has no unit of length, the edge report measures the
  * loop closures against the trajectory they produced).  All quantities are integers up to the final score, so results do not depend on

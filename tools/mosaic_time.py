@@ -17,7 +17,13 @@ synth.angle_profile(M, alt, gr, AMP, 6) (--alt-swing replaces the survey's altit
 of equal width cover the altitudes, and the tool reports the banded statistics and table (min_count 64, smooth 8), the consistency
 score under the TRUE poses with no table, the column table and the banded table, and, interleaved call by call in one process (median,
 fastest and slowest of --calls after a warm-up round), dsss_mosaic_gain_stats (mosaic_gainstat_kernel at one band) against
-dsss_mosaic_gain_stats_banded (the same kernel at B bands) on the same frames and the render under the column against the banded table."""
+dsss_mosaic_gain_stats_banded (the same kernel at B bands) on the same frames and the render under the column against the banded table.
+--footprint STEPS [--max-gap METRES] [--ping-stride K] adds the footprint rendering: dsss_mosaic_render_footprint at max_steps STEPS
+against dsss_mosaic_render, and with --composite dsss_mosaic_composite_footprint against dsss_mosaic_composite, in one process,
+interleaved call by call (median, fastest and slowest of --calls after a warm-up round), with the sub-samples binned, the empty cells
+and the enclosed single-cell holes (an empty cell with a cell that holds a sample directly on both sides along x or along y) of both.
+--ping-stride K renders both under a trajectory that moves ping r of a frame to K times its distance from the frame's middle ping (the
+dead-reckoning rows stretched along the track): a ping spacing of K bins out of the survey's one, on a grid over the stretched extent."""
 import argparse
 import json
 import os
@@ -41,6 +47,8 @@ ap.add_argument("--profile", type=float, default=0.0, metavar="AMP"); ap.add_arg
 ap.add_argument("--composite", choices=sorted(capi.COMP_MODES), default=None, metavar="MODE"); ap.add_argument("--fill", type=int, default=0, metavar="R")
 ap.add_argument("--gain-bands", type=int, default=0, metavar="B"); ap.add_argument("--alt-swing", type=float, default=None, metavar="METRES")
 ap.add_argument("--angle-profile", type=float, default=0.0, metavar="AMP")
+ap.add_argument("--footprint", type=int, default=0, metavar="STEPS"); ap.add_argument("--max-gap", type=float, default=1.0, metavar="METRES")
+ap.add_argument("--ping-stride", type=int, default=1, metavar="K")
 a = ap.parse_args()
 F, N, M = a.frames, a.rows, a.cols
 if a.calls < 5:
@@ -173,5 +181,44 @@ if a.composite:
                render_ms_beside_max=round(1e3 * max(t_mean), 3),
                cells_direct=int(info.direct), cells_filled=int(info.filled), cells_empty=int(info.empty))
     ctx.mosaic_gain_set(None)
+if a.footprint:
+    fp = capi.FootprintParams(a.footprint, 0, a.max_gap)
+    traj, pf = {}, p
+    if a.ping_stride > 1:
+        rows = [i[0].copy() for i in ins]
+        for r in rows:
+            mid = r[len(r) // 2, 3:5].copy()
+            r[:, 3:5] = mid + a.ping_stride * (r[:, 3:5] - mid)
+        traj = dict(rpy6=np.ascontiguousarray(np.concatenate(rows)), ping_off=off)
+        pf = capi.mosaic_grid(ctx.mosaic_bounds(ids, **traj), a.cell)
+
+    def mmm(ts):
+        return [round(1e3 * float(np.median(ts)), 3), round(1e3 * min(ts), 3), round(1e3 * max(ts), 3)]
+
+    def holes(cnt):
+        v = cnt > 0
+        h = np.zeros(v.shape, bool)
+        h[:, 1:-1] |= v[:, :-2] & v[:, 2:]; h[1:-1, :] |= v[:-2, :] & v[2:, :]
+        return int((~v).sum()), int((h & ~v).sum())
+    pairs = [("render", lambda: ctx.mosaic_render(ids, pf, download=False, **traj), lambda: ctx.mosaic_render_footprint(ids, pf, download=False, footprint=fp, **traj))]
+    if a.composite:
+        pairs.append(("composite", lambda: ctx.mosaic_composite(ids, pf, mode=a.composite, fill_radius=a.fill, want=(), **traj),
+                      lambda: ctx.mosaic_composite_footprint(ids, pf, mode=a.composite, fill_radius=a.fill, want=(), footprint=fp, **traj)))
+    out = dict(footprint_steps=a.footprint, footprint_max_gap=a.max_gap, ping_stride=a.ping_stride, footprint_grid=[pf.W, pf.H])
+    for name, point, foot in pairs:
+        t_point, t_foot = [], []
+        for k in range(a.calls + 1):
+            t0 = time.perf_counter(); point(); dt_p = time.perf_counter() - t0
+            t0 = time.perf_counter(); foot(); dt_f = time.perf_counter() - t0
+            if k:                                                 # (the first round warms up)
+                t_point.append(dt_p); t_foot.append(dt_f)
+        out[name + "_point_ms_med_min_max"] = mmm(t_point); out[name + "_footprint_ms_med_min_max"] = mmm(t_foot)
+    cnt_p = ctx.mosaic_render(ids, pf, **traj)[1]
+    cnt_f = ctx.mosaic_render_footprint(ids, pf, footprint=fp, **traj)[1]
+    assert (cnt_f >= cnt_p).all()
+    out.update(samples_binned=int(cnt_p.sum(dtype=np.int64)), subsamples_binned=int(cnt_f.sum(dtype=np.int64)))
+    out["point_empty_cells"], out["point_single_cell_holes"] = holes(cnt_p)
+    out["footprint_empty_cells"], out["footprint_single_cell_holes"] = holes(cnt_f)
+    res.update(out)
 print(json.dumps(res))
 pipe.close()
