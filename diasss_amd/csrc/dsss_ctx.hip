@@ -425,7 +425,14 @@ int dsss_frame_set_typed(dsss_ctx* c, int id, const void* raw, int raw_type, int
     if (!dsss_raw_type_size(raw_type)) DSSS_FAIL(c, DSSS_E_ARG, "unknown raw type %d", raw_type);
     HIPCHK(c, hipSetDevice(c->device));
     int rc = dsss_ensure_store(c); if (rc) return rc;
-    rc = frame_prepare(c, id, N, M, pose6, alt, grange); if (rc) return rc;
+    rc = frame_prepare(c, id, N, M, pose6, alt, grange);
+    // An extraction that dsss_frames_set STARTED on this frame read the image the frame had then: it is dropped, as another list of frames or
+    // changed parameters drop it.  Without this, dsss_extract_many over the started list only finished it and returned the features of the
+    // image that had been replaced (tests/test_gpu_inflight.py, scenario frames_again: a frame set again between the start and the extraction).
+    // Only a frame of the started list drops it (a rank sets the geometry of frames it does not extract), and not a call refused for its
+    // arguments, which has touched nothing.
+    if (rc != DSSS_E_ARG && c->ex_eager_valid && std::find(c->ex_eager_ids.begin(), c->ex_eager_ids.end(), id) != c->ex_eager_ids.end()) c->ex_eager_valid = false;
+    if (rc) return rc;
     HIPCHK(c, frame_fill(c, id, c->frames[id].h_pack, pose6, alt, grange));
     return frame_submit(c, id, raw, raw_type, true);
 }
@@ -561,7 +568,13 @@ int dsss_features_set_sift(dsss_ctx* c, int id, const float* d128, int n)
     int rc = dsss_ensure_sift_store(c); if (rc) return rc;
     std::vector<uint8_t> b((size_t)n * 128);
     for (size_t i = 0; i < b.size(); ++i) { const float v = std::nearbyint(d128[i]); b[i] = (uint8_t)(v < 0 ? 0 : v > 255 ? 255 : v); }
-    if (n > 0) HIPCHK(c, hipMemcpy(c->desc128.as<uint8_t>() + (size_t)id * c->kcap * 128, b.data(), b.size(), hipMemcpyHostToDevice));
+    // On the context's stream, as dsss_features_set copies: dsss_ensure_sift_store clears a NEW desc128 with hipMemsetAsync on that stream,
+    // and a null-stream copy is not ordered behind it (the streams are non-blocking) -- while the stream lags, the clear ran AFTER the rows
+    // had landed and wiped them.  Found by tests/test_gpu_inflight.py, scenario features_and_match behind a held-back stream.
+    if (n > 0) {
+        HIPCHK(c, hipMemcpyAsync(c->desc128.as<uint8_t>() + (size_t)id * c->kcap * 128, b.data(), b.size(), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));         // b is of this call
+    }
     f.has_sift = true;
     return DSSS_OK;
 }
@@ -708,7 +721,11 @@ int dsss_features_unpack(dsss_ctx* c, int id, const void* buf)
                                (const double*)(p + 48 + K * sizeof(dsss_kp) + K * 32), bbox, hdr[0]);
     if (rc == DSSS_OK && c->op.descriptor == DSSS_DESC_SIFT128) {
         rc = dsss_ensure_sift_store(c); if (rc) return rc;
-        HIPCHK(c, hipMemcpy(c->desc128.as<uint8_t>() + (size_t)id * K * 128, p + 48 + K * sizeof(dsss_kp) + K * 48, K * 128, hipMemcpyDefault));
+        // on the context's stream, behind the clear of a NEW desc128: the pair of dsss_features_set_sift, found here by reading.  No test has
+        // shown it: dsss_features_set above has just drained the stream, so the clear is over within microseconds (scenario features_and_match,
+        // the context whose first SIFT rows arrive in a record, passes with either copy)
+        HIPCHK(c, hipMemcpyAsync(c->desc128.as<uint8_t>() + (size_t)id * K * 128, p + 48 + K * sizeof(dsss_kp) + K * 48, K * 128, hipMemcpyDefault, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));         // the caller's buffer is free again when the call returns
         c->frames[id].has_sift = true;
     }
     return rc;

@@ -14,6 +14,28 @@
  *     output pointers named *_host are host memory;
  *   - frames are identified by their img_id (0..F-1), which is also the index diasss2.cpp:84 uses;
  *   - there is NO CPU fallback: without a HIP device dsss_create fails with DSSS_E_NODEVICE.
+ *   - ORDER.  The work of a context is ordered on its own stream (dsss_stream), which does not synchronise with the null stream; one thread
+ *     at a time calls into a context, and contexts of different threads share nothing a caller can see.  Three kinds of entry:
+ *       * entries that return with device work QUEUED, asynchronous until dsss_sync or the next entry that downloads: dsss_frame_set[_typed]
+ *         and dsss_frames_set[_typed] (the geometry upload and the geo boxes; for images in HBM dsss_frames_set also the started extraction),
+ *         and dsss_lc_solve_all and dsss_lc_solve_pairs, which ends in it (the mini-LM launch);
+ *       * entries that answer from host state and neither queue nor wait: the parameter and partition setters (dsss_set_params waits only
+ *         when the keypoint capacity changes), dsss_posegraph_reset / _online_edges / _schedule_get, dsss_frame_raw_info, dsss_comm_stats,
+ *         dsss_comm_frame_owner, dsss_mosaic_bounds, dsss_mosaic_register_info, dsss_mosaic_register_edges[_yaw], and the getters where
+ *         they are asked for a count alone;
+ *       * every other entry has synchronised the stream before it returns: its *_host outputs are complete, and an error it reports covers
+ *         everything it queued (dsss_mosaic_render and its kin therefore synchronise even with every output NULL: DSSS_E_CAPACITY is read back).
+ *     A caller relies on the outputs and on the list of the first kind; whether an entry of the third kind waits once or several times, and
+ *     where, is not part of the contract.
+ *     An entry may be called whatever the stream still holds -- work of earlier entries, or the caller's own work queued on dsss_stream:
+ *     every copy into memory that queued work reads or writes is ordered on the stream.
+ *   - CALLER BUFFERS.  A PAGEABLE host input (images, geometry, features, records, edges, trajectory rows, tables) has been copied, to the
+ *     device or to a staging area of the context, when the call returns: the caller may reuse or free it at once, also after the entries
+ *     that return with work queued.  Page-locked raw images and device pointers are the two exceptions, stated at dsss_frame_set.
+ *     What is tested (tests/test_gpu_inflight.py): every entry called with the stream held back gives the bytes it gives on an idle stream,
+ *     dsss_frames_set over images in HBM returns before the stream has caught up, dsss_mosaic_render does not.  The three kinds are not
+ *     told apart entry by entry there, and no test overwrites a pageable input straight after the call: that rule stands by the code, where
+ *     every such input is copied by a host-blocking copy, or into a staging area, before the entry returns.
  */
 #ifndef DSSS_H
 #define DSSS_H

@@ -363,6 +363,37 @@ def tri_reference(orc, frames, s, t, kp7, key=None):
     return res
 
 
+# ---------------------------------------------------------------- results as bytes
+def result_bytes(x):
+    """the bytes of a result: arrays (NaNs compare as their bits), scalars, nested tuples and lists"""
+    if isinstance(x, (tuple, list)):
+        return b"|".join(result_bytes(v) for v in x)
+    return np.ascontiguousarray(x).tobytes() if x is not None else b"none"
+
+
+def first_difference(a, b, where="result"):
+    """None when two nested results have the same bytes (result_bytes), else the path of the first leaf that differs with what differs
+    there: "result[3][0]: 2 of 4800 bytes differ, first at byte 17".  One flipped bit anywhere is reported; NaNs count by their bits."""
+    if isinstance(a, (tuple, list)) or isinstance(b, (tuple, list)):
+        if not (isinstance(a, (tuple, list)) and isinstance(b, (tuple, list))):
+            return "%s: a %s against a %s" % (where, type(a).__name__, type(b).__name__)
+        if len(a) != len(b):
+            return "%s: %d items against %d" % (where, len(a), len(b))
+        for k, (u, v) in enumerate(zip(a, b)):
+            d = first_difference(u, v, "%s[%d]" % (where, k))
+            if d is not None:
+                return d
+        return None
+    x, y = result_bytes(a), result_bytes(b)
+    if x == y:
+        return None
+    if len(x) != len(y):
+        return "%s: %d bytes against %d" % (where, len(x), len(y))
+    u = np.frombuffer(x, np.uint8); v = np.frombuffer(y, np.uint8)
+    bad = np.nonzero(u != v)[0]
+    return "%s: %d of %d bytes differ, first at byte %d (0x%02x against 0x%02x)" % (where, len(bad), len(x), bad[0], u[bad[0]], v[bad[0]])
+
+
 # ---------------------------------------------------------------- small inputs shared by several GPU test modules
 MOSAIC_SIZES = ((640, 400), (500, 700))          # the two legs of the mosaic tests: the smallest sizes test_gpu_extract.py extracts at
 

@@ -7,6 +7,8 @@ Inputs are the smallest the tests of each entry already use.  No test provokes a
 import numpy as np
 import pytest
 
+from tests.helpers import result_bytes as _bytes          # the bytes of a result: arrays (NaNs by their bits), scalars, nested tuples and lists
+
 pytestmark = pytest.mark.gpu
 
 
@@ -16,13 +18,6 @@ def _ctx(max_frames=4, orb=None):
     if orb is not None:
         c.set_params(orb=orb)
     return c
-
-
-def _bytes(x):
-    """the bytes of a result: arrays (NaNs compare as their bits), scalars, nested tuples and lists"""
-    if isinstance(x, (tuple, list)):
-        return b"|".join(_bytes(v) for v in x)
-    return np.ascontiguousarray(x).tobytes() if x is not None else b"none"
 
 
 def _run_sequence(steps, fresh, make):
