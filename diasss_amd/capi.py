@@ -95,6 +95,19 @@ def _footprint(footprint):
     return FootprintParams(int(footprint[0]), 0, float(footprint[1]))
 
 
+class CanvasParams(C.Structure):
+    """dsss_canvas_params (include/dsss_canvas.h): footprint 0 = point samples, move = CANVAS_MOVE_AUTO or CANVAS_MOVE_SPLIT, fp = the
+    footprint parameters of a footprint canvas"""
+    _fields_ = [("footprint", C.c_int32), ("move", C.c_int32), ("fp", FootprintParams)]
+
+
+class CanvasPutInfo(C.Structure):
+    """dsss_canvas_put_info: frames added, moved and skipped by a put, the workgroups it launched and the window (ox, oy, bw, bh; bw = 0:
+    none) it touched"""
+    _fields_ = [("added", C.c_int32), ("moved", C.c_int32), ("skipped", C.c_int32), ("pad_", C.c_int32), ("pings", C.c_int64), ("win", C.c_int32 * 4)]
+
+
+CANVAS_MOVE_AUTO, CANVAS_MOVE_SPLIT = 0, 1                        # include/dsss_canvas.h DSSS_CANVAS_MOVE_*
 COMP_NEAR, COMP_FAR, COMP_MID, COMP_FIRST = 0, 1, 2, 3          # include/dsss.h DSSS_COMP_*
 COMP_MODES = {"near": COMP_NEAR, "far": COMP_FAR, "mid": COMP_MID, "first": COMP_FIRST}
 COMP_LAYERS = (("img", np.uint8), ("src_frame", np.int32), ("src_ping", np.int32), ("src_col", np.int32), ("fill", np.uint8))   # in the order of the C arguments
@@ -397,6 +410,20 @@ def lib():
         L.dsss_mosaic_register_peaks.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_void_p]
         L.dsss_mosaic_register_info.restype = C.c_int
         L.dsss_mosaic_register_info.argtypes = [C.c_void_p, C.POINTER(RegCallInfo)]
+        L.dsss_canvas_params_default.restype = None
+        L.dsss_canvas_params_default.argtypes = [C.POINTER(CanvasParams)]
+        L.dsss_canvas_create.argtypes = [C.c_void_p, C.POINTER(MosaicParams), C.POINTER(CanvasParams), C.POINTER(C.c_void_p)]
+        L.dsss_canvas_destroy.argtypes = [C.c_void_p]
+        L.dsss_canvas_put.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(CanvasPutInfo)]
+        L.dsss_canvas_remove.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.dsss_canvas_clear.argtypes = [C.c_void_p]
+        L.dsss_canvas_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.dsss_canvas_dirty.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.dsss_canvas_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        L.dsss_canvas_rows.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.dsss_canvas_frame_window.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        for name in ("create", "destroy", "put", "remove", "clear", "read", "dirty", "frames", "rows", "frame_window"):
+            getattr(L, "dsss_canvas_" + name).restype = C.c_int
         _LIB = L
     return _LIB
 
@@ -518,6 +545,10 @@ def mosaic_fill_host(valid, R):
 
 def footprint_params_default():
     p = FootprintParams(); lib().dsss_footprint_params_default(C.byref(p)); return p
+
+
+def canvas_params_default():
+    p = CanvasParams(); lib().dsss_canvas_params_default(C.byref(p)); return p
 
 
 def mosaic_footprint_steps(footprint, cell, sx, sy):
@@ -678,6 +709,8 @@ class Context:
         self.max_frames = max_frames
 
     def close(self):
+        for cv in list(self.__dict__.get("_canvases", ())):      # the canvases that are left go first: dsss_destroy would free them under their wrappers
+            cv.close()
         if getattr(self, "h", None):
             self.L.dsss_destroy(self.h)
             self.h = None
@@ -1343,6 +1376,11 @@ class Context:
         self._chk(self.L.dsss_mosaic_register_info(self.h, C.byref(info)), "dsss_mosaic_register_info")
         return info
 
+    def canvas(self, params, footprint=None, move=CANVAS_MOVE_AUTO):
+        """dsss_canvas_create: a mosaic canvas on the grid `params` (include/dsss_canvas.h).  footprint: None = point samples, a
+        FootprintParams or (max_steps, max_gap) = a footprint canvas; move: CANVAS_MOVE_AUTO or CANVAS_MOVE_SPLIT"""
+        return Canvas(self, params, footprint, move)
+
     # ---- instrumentation
     def profile(self, on=True):
         self._chk(self.L.dsss_profile_enable(self.h, 1 if on else 0), "dsss_profile_enable")
@@ -1356,3 +1394,86 @@ class Context:
         self._chk(self.L.dsss_profile_get(self.h, _ptr(ms), _ptr(n)), "dsss_profile_get")
         self._chk(self.L.dsss_profile_get_work(self.h, _ptr(wk)), "dsss_profile_get_work")
         return {K_NAMES[i]: (float(ms[i]), int(n[i]), float(wk[i])) for i in range(K) if not K_NAMES[i].startswith("k2")}
+
+
+class Canvas:
+    """dsss_canvas (include/dsss_canvas.h): a mean mosaic kept on the device; frames are put (added, moved, skipped) and removed, and it
+    always reads what a fresh render of its frames under their stored rows reads.  Made by Context.canvas."""
+
+    def __init__(self, ctx, params, footprint=None, move=CANVAS_MOVE_AUTO):
+        self.ctx, self.L, self.h = ctx, ctx.L, None
+        cp = canvas_params_default()
+        cp.move = int(move)
+        if footprint is not None:
+            cp.footprint = 1; cp.fp = _footprint(footprint)
+        h = C.c_void_p()
+        ctx._chk(self.L.dsss_canvas_create(ctx.h, C.byref(params), C.byref(cp), C.byref(h)), "dsss_canvas_create")
+        self.h = h
+        self.W, self.H = int(params.W), int(params.H)
+        ctx.__dict__.setdefault("_canvases", []).append(self)
+
+    def close(self):
+        if self.h is not None:
+            if self.ctx.h:
+                self.L.dsss_canvas_destroy(self.h)
+            self.h = None
+            self.ctx._canvases.remove(self)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def put(self, ids, rpy6=None, ping_off=None):
+        """dsss_canvas_put -> a CanvasPutInfo.  rpy6 (host rows "r p y x y z", frame ids[i] from row ping_off[i]) or None: the poses the
+        frames were set with"""
+        ids, rpy6, ping_off = Context._mosaic_traj(ids, rpy6, ping_off)
+        info = CanvasPutInfo()
+        self.ctx._chk(self.L.dsss_canvas_put(self.h, _ptr(ids), len(ids), _ptr(rpy6), _ptr(ping_off), C.byref(info)), "dsss_canvas_put")
+        return info
+
+    def remove(self, ids):
+        ids = np.ascontiguousarray(ids, np.int32)
+        self.ctx._chk(self.L.dsss_canvas_remove(self.h, _ptr(ids), len(ids)), "dsss_canvas_remove")
+
+    def clear(self):
+        self.ctx._chk(self.L.dsss_canvas_clear(self.h), "dsss_canvas_clear")
+
+    def read(self, win=None, want=("sum", "cnt", "img")):
+        """dsss_canvas_read -> (sum, cnt, img) of the window win = (ox, oy, bw, bh), None: the grid; bh x bw uint32, uint32, uint8 (None for
+        a layer not in `want`)"""
+        w = None if win is None else np.ascontiguousarray(win, np.int32)
+        bw, bh = (self.W, self.H) if w is None else (max(int(w[2]), 0), max(int(w[3]), 0))
+        out = [np.empty((bh, bw), t) if n in want else None for n, t in (("sum", np.uint32), ("cnt", np.uint32), ("img", np.uint8))]
+        self.ctx._chk(self.L.dsss_canvas_read(self.h, _ptr(w), _ptr(out[0]), _ptr(out[1]), _ptr(out[2])), "dsss_canvas_read")
+        return tuple(out)
+
+    def dirty(self, reset=True):
+        """dsss_canvas_dirty -> (ox, oy, bw, bh) of everything touched since the last reset, None when nothing was"""
+        w = np.zeros(4, np.int32)
+        self.ctx._chk(self.L.dsss_canvas_dirty(self.h, _ptr(w), 1 if reset else 0), "dsss_canvas_dirty")
+        return tuple(int(v) for v in w) if w[2] > 0 else None
+
+    def frames(self):
+        """the ids on the canvas, ascending"""
+        n = C.c_int(0)
+        self.L.dsss_canvas_frames(self.h, None, 0, C.byref(n))      # (DSSS_E_CAPACITY with frames on it: the call that asks how many)
+        ids = np.zeros(max(n.value, 1), np.int32)
+        self.ctx._chk(self.L.dsss_canvas_frames(self.h, _ptr(ids), len(ids), C.byref(n)), "dsss_canvas_frames")
+        return ids[:n.value].tolist()
+
+    def rows(self, id, N):
+        """dsss_canvas_rows: the N x 6 rows frame `id` is on the canvas with, downloaded from the canvas's device copy"""
+        out = np.empty((int(N), 6), np.float64)
+        self.ctx._chk(self.L.dsss_canvas_rows(self.h, int(id), _ptr(out)), "dsss_canvas_rows")
+        return out
+
+    def frame_window(self, id, rows=None):
+        """dsss_canvas_frame_window -> (ox, oy, bw, bh) of the cells frame `id` can reach under `rows` (None: the stored rows), None when
+        it reaches none"""
+        if rows is not None:
+            rows = np.ascontiguousarray(rows, np.float64)
+        w = np.zeros(4, np.int32)
+        self.ctx._chk(self.L.dsss_canvas_frame_window(self.h, int(id), _ptr(rows), _ptr(w)), "dsss_canvas_frame_window")
+        return tuple(int(v) for v in w) if w[2] > 0 else None

@@ -118,7 +118,9 @@ static void free_frame(dsss_frame& f)
     hipFree(f.mask);
     if (f.pack_ev) hipEventDestroy(f.pack_ev);
     for (int l = 0; l < DSSS_MAX_LEVELS; ++l) hipFree(f.lvl[l]);
+    const unsigned long long epoch = f.epoch;
     f = dsss_frame();                    // (move assignment: releases raw_owned)
+    f.epoch = epoch;                     // a frame's epoch only ever grows
 }
 
 static void free_store(dsss_ctx* c) { c->desc128.release(); dsss_family_release(c->store_cap, store_family(c)); }
@@ -133,7 +135,7 @@ void dsss_destroy(dsss_ctx* c)
     c->gbatches.clear();
     dsss_mt_free(c); free_store(c);
     if (c->geoms && c->geoms_free) c->geoms_free(c->geoms);
-    dsss_pg_free(c); dsss_comm_free(c);
+    dsss_pg_free(c); dsss_comm_free(c); dsss_canvas_free_all(c);
     hipEventDestroy(c->prof.e0); hipEventDestroy(c->prof.e1);
     dsss_prof_flush(c);
     for (hipEvent_t e : c->prof.pool) hipEventDestroy(e);
@@ -382,7 +384,7 @@ static int frame_submit(dsss_ctx* c, int id, const void* raw, int raw_type, bool
         HIPCHK(c, hipMemcpyAsync(f.d_pack, f.h_pack, pack * sizeof(double), hipMemcpyHostToDevice, c->stream));   // pinned: truly asynchronous
         HIPCHK(c, hipEventRecord(f.pack_ev, c->stream));
     }
-    f.has_geom = true; f.has_feat = false; f.has_norm = false; f.nkp = 0;          // no synchronisation: the sources above live in the context
+    f.has_geom = true; f.has_feat = false; f.has_norm = false; ++f.epoch; f.nkp = 0;          // no synchronisation: the sources above live in the context
     if (raw) {
         hipPointerAttribute_t at;
         bool on_dev = (hipPointerGetAttributes(&at, raw) == hipSuccess) && at.type == hipMemoryTypeDevice;

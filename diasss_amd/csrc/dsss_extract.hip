@@ -1347,7 +1347,7 @@ struct ex_run {
         for (int s = 0; s < bt.nb; ++s) {
             const int id = ids[bt.b0 + s]; dsss_frame& f = c->frames[id];
             if (h_err[s]) DSSS_FAIL(c, DSSS_E_CAPACITY, "frame %d: extraction capacity exceeded (code %d; 7 = FAST candidates, else quadtree lists)", id, h_err[s]);
-            f.nkp = h_nkp[id]; f.has_feat = true; f.has_norm = true; f.has_sift = sift;
+            f.nkp = h_nkp[id]; f.has_feat = true; f.has_norm = true; ++f.epoch; f.has_sift = sift;
         }
         return DSSS_OK;
     }

@@ -59,6 +59,7 @@ struct dsss_frame {
     int N = 0, M = 0;
     bool has_geom = false, has_raw = false, has_feat = false, has_norm = false;
     bool has_sift = false;            // the frame's rows of desc128 are valid (extracted with DSSS_DESC_SIFT128 or imported)
+    unsigned long long epoch = 0;     // bumped wherever has_norm is cleared or set, never reset: what a mosaic canvas recorded of the frame is stale once it differs
     const void* raw = nullptr;        // device; borrowed when the caller passed a device pointer
     int raw_type = DSSS_RAW_F64;      // element type of raw (dsss_raw_type)
     dsss_buf raw_owned{"raw_owned"};  // device; owned copy of a host image (at least raw_bytes(): a re-set with a wider type regrows it, a narrower one keeps the block)
@@ -185,6 +186,8 @@ struct dsss_ctx {
     dsss_buf mosaic_pinned{"mosaic_pinned", DSSS_PINNED};                     // page-locked landing area of the segment registration: the records of mosaic_peak_kernel, or on the host path the table of sums (140 MB at the headline size: a pageable copy into fresh memory cost more than the kernels)
     dsss_buf mosaic_gain{"mosaic_gain"}; int mosaic_gain_M = 0;              // the range-gain table (dsss_mosaic_gain_set, _set_banded): nbands x M u16 gains, Q8, on the device; M = 0: none set
     dsss_gain_bands mosaic_bands{0.0, 1.0, 1, 0};                             // the altitude bands of that table (dsss_mosaic_gain_set_banded): nbands rows of M gains; one band: the column table
+    unsigned long long gain_epoch = 0;                                        // bumped by every change of that table (gain_install): a mosaic canvas records it
+    std::vector<struct dsss_canvas*> canvases;                                // the mosaic canvases of this context (dsss_mosaic_canvas.hip); dsss_destroy frees what is left
     dsss_reg_call_info reg_info{0, 0, 0, 0};                                  // what the last registration call that returned DSSS_OK did (dsss_mosaic_register_info)
     dsss_buf pgr_buf{"pgr_buf"};                                           // device scratch of dsss_posegraph_edge_report (dsss_pg_report.hip), kept between calls
     dsss_prof prof;
@@ -295,6 +298,7 @@ void dsss_mt_clear_results(dsss_ctx* c);                      // the EMPTY resul
 void dsss_mt_free(dsss_ctx* c);                               // every buffer above and the geo grid's, and the result set they held (dsss_destroy, dsss_set_params)
 void dsss_pg_free(dsss_ctx* c);
 void dsss_comm_free(dsss_ctx* c);
+void dsss_canvas_free_all(dsss_ctx* c);      // dsss_mosaic_canvas.hip: the canvases dsss_canvas_destroy has not freed
 int dsss_comm_rank(const dsss_ctx* c);
 int dsss_comm_world(const dsss_ctx* c);
 int dsss_comm_allreduce(dsss_ctx* c, double* dev, size_t n, hipStream_t st);

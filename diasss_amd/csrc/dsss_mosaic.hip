@@ -705,7 +705,7 @@ int dsss_mosaic_gain_table_banded(const uint64_t* sum, const uint64_t* cnt, int 
 // table in force.  (Every entry that reads the table synchronises before it returns, so no queued kernel still reads the old block.)
 static int gain_install(dsss_ctx* c, const uint16_t* gain_q8_host, int M, const dsss_gain_bands& bands)
 {
-    if (!gain_q8_host) { c->mosaic_gain_M = 0; c->mosaic_bands = gain_one_band(); return DSSS_OK; }
+    if (!gain_q8_host) { c->mosaic_gain_M = 0; c->mosaic_bands = gain_one_band(); ++c->gain_epoch; return DSSS_OK; }
     if (M < 2) DSSS_FAIL(c, DSSS_E_ARG, "gain: a table of %d columns", M);
     HIPCHK(c, hipSetDevice(c->device));
     const size_t bytes = (size_t)M * bands.nbands * sizeof(uint16_t);
@@ -713,7 +713,7 @@ static int gain_install(dsss_ctx* c, const uint16_t* gain_q8_host, int M, const 
     const int rc = nb.reserve(c, bytes); if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(nb.p, gain_q8_host, bytes, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->mosaic_gain = std::move(nb); c->mosaic_gain_M = M; c->mosaic_bands = bands; c->mosaic_bands.pad_ = 0;
+    c->mosaic_gain = std::move(nb); c->mosaic_gain_M = M; c->mosaic_bands = bands; c->mosaic_bands.pad_ = 0; ++c->gain_epoch;
     return DSSS_OK;
 }
 
