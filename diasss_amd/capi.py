@@ -108,6 +108,28 @@ class CanvasPutInfo(C.Structure):
 
 
 CANVAS_MOVE_AUTO, CANVAS_MOVE_SPLIT = 0, 1                        # include/dsss_canvas.h DSSS_CANVAS_MOVE_*
+
+
+class PingStat(C.Structure):
+    """dsss_ping_stat (include/dsss_profile.h): one ping of a profiled frame, [0] port and [1] starboard: the binned samples, the samples
+    compared against the mosaic of the other frames, and sum |d|, sum d^2 and sum d of their differences"""
+    _fields_ = [("binned", C.c_uint32 * 2), ("n", C.c_uint32 * 2), ("sad", C.c_uint32 * 2), ("ssd", C.c_uint32 * 2), ("sd", C.c_int32 * 2)]
+
+
+class ProfileParams(C.Structure):
+    """dsss_profile_params: the fewest samples of other frames a cell needs for a sample in it to be compared (1..2^24)"""
+    _fields_ = [("min_count", C.c_int32), ("pad_", C.c_int32)]
+
+
+class ProfileInfo(C.Structure):
+    """dsss_profile_info: the records of a call summed, and rms = n ? sqrt(ssd / n) : 0"""
+    _fields_ = [("pings", C.c_int64), ("binned", C.c_int64), ("n", C.c_int64), ("sad", C.c_int64), ("ssd", C.c_int64), ("sd", C.c_int64), ("rms", C.c_double)]
+
+
+assert C.sizeof(PingStat) == 40 and C.sizeof(ProfileParams) == 8 and C.sizeof(ProfileInfo) == 56
+PING_DTYPE = np.dtype(PingStat)          # the rows Context.profile_mosaic and Canvas.profile return: ten integers, five fields of (port, starboard)
+PROFILE_NONE = -32768                    # include/dsss_profile.h DSSS_PROFILE_NONE: a sample of a residual layer that is not compared
+PROFILE_OUTPUTS = ("stats", "diff", "info")
 COMP_NEAR, COMP_FAR, COMP_MID, COMP_FIRST = 0, 1, 2, 3          # include/dsss.h DSSS_COMP_*
 COMP_MODES = {"near": COMP_NEAR, "far": COMP_FAR, "mid": COMP_MID, "first": COMP_FIRST}
 COMP_LAYERS = (("img", np.uint8), ("src_frame", np.int32), ("src_ping", np.int32), ("src_col", np.int32), ("fill", np.uint8))   # in the order of the C arguments
@@ -424,6 +446,15 @@ def lib():
         L.dsss_canvas_frame_window.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         for name in ("create", "destroy", "put", "remove", "clear", "read", "dirty", "frames", "rows", "frame_window"):
             getattr(L, "dsss_canvas_" + name).restype = C.c_int
+        L.dsss_profile_params_default.restype = None
+        L.dsss_profile_params_default.argtypes = [C.POINTER(ProfileParams)]
+        L.dsss_profile_summary.restype = C.c_int
+        L.dsss_profile_summary.argtypes = [C.c_void_p, C.c_int64, C.POINTER(ProfileInfo)]
+        L.dsss_profile_mosaic.restype = C.c_int
+        L.dsss_profile_mosaic.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(MosaicParams), C.c_void_p, C.c_int,
+                                          C.POINTER(ProfileParams), C.c_void_p, C.c_void_p, C.POINTER(ProfileInfo)]
+        L.dsss_profile_canvas.restype = C.c_int
+        L.dsss_profile_canvas.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(ProfileParams), C.c_void_p, C.c_void_p, C.POINTER(ProfileInfo)]
         _LIB = L
     return _LIB
 
@@ -545,6 +576,41 @@ def mosaic_fill_host(valid, R):
 
 def footprint_params_default():
     p = FootprintParams(); lib().dsss_footprint_params_default(C.byref(p)); return p
+
+
+def profile_params_default():
+    p = ProfileParams(); lib().dsss_profile_params_default(C.byref(p)); return p
+
+
+def profile_summary(stats):
+    """dsss_profile_summary: rows of PING_DTYPE -> their ProfileInfo (host arithmetic)"""
+    stats = np.ascontiguousarray(stats, PING_DTYPE)
+    info = ProfileInfo()
+    rc = lib().dsss_profile_summary(_ptr(stats) if len(stats) else None, len(stats), C.byref(info))
+    if rc:
+        raise _host_error(lib(), "dsss_profile_summary", rc)
+    return info
+
+
+def _profile_outputs(sizes, want):
+    """the host arrays of a profile call over frames of `sizes` = [(N, M), ...] -> (stats, diff, info), None where not in `want`"""
+    for w in want:
+        if w not in PROFILE_OUTPUTS:
+            raise ValueError("profile: no output %r (%s)" % (w, ", ".join(PROFILE_OUTPUTS)))
+    pings = sum(N for N, M in sizes); samples = sum(N * M for N, M in sizes)
+    stats = np.zeros(max(pings, 1), PING_DTYPE) if "stats" in want else None
+    diff = np.zeros(max(samples, 1), np.int16) if "diff" in want else None
+    return stats, diff, (ProfileInfo() if "info" in want else None)
+
+
+def _profile_result(sizes, stats, diff, info):
+    """-> (rows of PING_DTYPE over the pings of the profiled frames, the residual layers as a list of N x M int16 arrays, ProfileInfo)"""
+    layers = None
+    if diff is not None:
+        layers, o = [], 0
+        for N, M in sizes:
+            layers.append(diff[o:o + N * M].reshape(N, M)); o += N * M
+    return (stats[:sum(N for N, M in sizes)] if stats is not None else None), layers, info
 
 
 def canvas_params_default():
@@ -1376,6 +1442,31 @@ class Context:
         self._chk(self.L.dsss_mosaic_register_info(self.h, C.byref(info)), "dsss_mosaic_register_info")
         return info
 
+    def _frame_sizes(self, ids):
+        """(N, M) of the listed frames; (0, 0) for one the library does not know: the entry that follows refuses it"""
+        out = []
+        for i in ids:
+            N = C.c_int(0); M = C.c_int(0)
+            rc = self.L.dsss_frame_get_level(self.h, int(i), 0, None, C.byref(N), C.byref(M))
+            out.append((N.value, M.value) if rc == 0 else (0, 0))
+        return out
+
+    def profile_mosaic(self, ids, params, prof=None, min_count=1, rpy6=None, ping_off=None, want=PROFILE_OUTPUTS):
+        """dsss_profile_mosaic (include/dsss_profile.h): every ping of the frames ids[prof] (prof None: all, in order) held against the
+        mosaic of all OTHER listed frames on the grid `params` -> (stats, diff, info): rows of PING_DTYPE, one per ping, the frames one
+        after the other; the residual layers as a list of N x M int16 arrays (PROFILE_NONE where a sample is not compared); a
+        ProfileInfo.  Each is None when it is not named in `want`."""
+        ids, rpy6, ping_off = self._mosaic_traj(ids, rpy6, ping_off)
+        pr = None if prof is None else np.ascontiguousarray(prof, np.int32)
+        which = range(len(ids)) if pr is None else [int(k) for k in pr if 0 <= int(k) < len(ids)]
+        sizes = self._frame_sizes([ids[k] for k in which])
+        stats, diff, info = _profile_outputs(sizes, want)
+        pp = ProfileParams(int(min_count), 0)
+        room = pr if pr is None or len(pr) else np.zeros(1, np.int32)      # an empty list still goes down as a list
+        self._chk(self.L.dsss_profile_mosaic(self.h, _ptr(ids), len(ids), _ptr(rpy6), _ptr(ping_off), C.byref(params), _ptr(room), 0 if pr is None else len(pr),
+                                             C.byref(pp), _ptr(stats), _ptr(diff), C.byref(info) if info is not None else None), "dsss_profile_mosaic")
+        return _profile_result(sizes, stats, diff, info)
+
     def canvas(self, params, footprint=None, move=CANVAS_MOVE_AUTO):
         """dsss_canvas_create: a mosaic canvas on the grid `params` (include/dsss_canvas.h).  footprint: None = point samples, a
         FootprintParams or (max_steps, max_gap) = a footprint canvas; move: CANVAS_MOVE_AUTO or CANVAS_MOVE_SPLIT"""
@@ -1468,6 +1559,18 @@ class Canvas:
         out = np.empty((int(N), 6), np.float64)
         self.ctx._chk(self.L.dsss_canvas_rows(self.h, int(id), _ptr(out)), "dsss_canvas_rows")
         return out
+
+    def profile(self, ids, min_count=1, want=PROFILE_OUTPUTS):
+        """dsss_profile_canvas (include/dsss_profile.h): every ping of the listed frames of the canvas held against the canvas without the
+        frame itself -> (stats, diff, info) as Context.profile_mosaic returns them, the frames in the order of ids.  The canvas is not
+        changed."""
+        ids = np.ascontiguousarray(ids, np.int32)
+        sizes = self.ctx._frame_sizes(ids)
+        stats, diff, info = _profile_outputs(sizes, want)
+        pp = ProfileParams(int(min_count), 0)
+        self.ctx._chk(self.L.dsss_profile_canvas(self.h, _ptr(ids), len(ids), C.byref(pp), _ptr(stats), _ptr(diff),
+                                                 C.byref(info) if info is not None else None), "dsss_profile_canvas")
+        return _profile_result(sizes, stats, diff, info)
 
     def frame_window(self, id, rows=None):
         """dsss_canvas_frame_window -> (ox, oy, bw, bh) of the cells frame `id` can reach under `rows` (None: the stored rows), None when

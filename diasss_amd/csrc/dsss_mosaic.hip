@@ -441,6 +441,42 @@ void launch_scatter_seg(dsss_ctx* c, const mosaic_job* d_job, int blocks, const 
     hipLaunchKernelGGL(mosaic_scatter_seg_kernel, dim3((unsigned)blocks), dim3(256), 0, c->stream, d_job, 1, G, acc, d_segs, seg_pings);
 }
 
+// The accumulators of a render, for the render entries and the profile (dsss_mosaic_profile.hip): acc and the flag cleared, the frames
+// scattered (fp == null: as points, otherwise the sub-samples of their footprints), then the unpack into the layers given (null: the
+// sample-limit check alone).  jobs = the host's table (mosaic_fill_jobs), whose blk0 are set here; d_jobs = room for it on the device.
+int mosaic_render_acc(dsss_ctx* c, const int* ids, int n, std::vector<mosaic_job>& jobs, mosaic_job* d_jobs, const dsss_mosaic_params* p,
+                      const dsss_footprint_params* fp, unsigned long long* acc, int* d_flag, uint32_t* d_sum, uint32_t* d_cnt, uint8_t* d_img)
+{
+    const size_t cells = (size_t)p->W * p->H;
+    HIPCHK(c, hipMemsetAsync(acc, 0, cells * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_flag, 0, sizeof(int), c->stream));
+    const mosaic_win G = mosaic_grid_win(p);
+    const unsigned ublocks = (unsigned)((cells + 255) / 256);
+    // launches of at most 2^31 samples (sub-samples: max_steps^2 a sample at most), the sample limit checked between them: a cell's count
+    // then stays far below 2^32 until the check sees it, so the packed accumulator cannot wrap unnoticed whatever the number of frames
+    const size_t per_sample = fp ? (size_t)fp->max_steps * fp->max_steps : 1;
+    int j0 = 0;
+    while (j0 < n) {
+        int j1 = j0, blocks = 0; size_t samples = 0;
+        while (j1 < n) {
+            const dsss_frame& f = c->frames[ids[j1]];
+            const size_t s = (size_t)f.N * f.M * per_sample;
+            if (j1 > j0 && samples + s > (1ull << 31)) break;
+            jobs[j1].blk0 = blocks;
+            blocks += f.N; samples += s; ++j1;
+        }
+        HIPCHK(c, hipMemcpyAsync(d_jobs + j0, jobs.data() + j0, (size_t)(j1 - j0) * sizeof(mosaic_job), hipMemcpyHostToDevice, c->stream));
+        if (!fp) launch_scatter(c, d_jobs + j0, j1 - j0, blocks, G, acc);
+        else hipLaunchKernelGGL(mosaic_scatter_fp_kernel, dim3((unsigned)blocks), dim3(256), 0, c->stream, d_jobs + j0, j1 - j0, G, *fp, acc);
+        HIPCHK(c, hipGetLastError());
+        if (j1 < n) { hipLaunchKernelGGL(mosaic_unpack_kernel, dim3(ublocks), dim3(256), 0, c->stream, acc, cells, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint8_t*)nullptr, d_flag); HIPCHK(c, hipGetLastError()); }
+        j0 = j1;
+    }
+    hipLaunchKernelGGL(mosaic_unpack_kernel, dim3(ublocks), dim3(256), 0, c->stream, acc, cells, d_sum, d_cnt, d_img, d_flag);
+    HIPCHK(c, hipGetLastError());
+    return DSSS_OK;
+}
+
 extern "C" {
 
 int dsss_mosaic_grid(const double* bbox4, double cell, dsss_mosaic_params* out)
@@ -488,32 +524,7 @@ static int render_run(dsss_ctx* c, const int* ids, int n, const double* rpy6, co
     uint32_t* d_sum = A.opt(o_sum); uint32_t* d_cnt = A.opt(o_cnt); uint8_t* d_img = A.opt(o_img);
     std::vector<mosaic_job> jobs;
     rc = mosaic_fill_jobs(c, ids, n, rpy6, ping_off, A.at(o_rows), jobs); if (rc) return rc;
-    HIPCHK(c, hipMemsetAsync(acc, 0, cells * 8, c->stream));
-    HIPCHK(c, hipMemsetAsync(d_flag, 0, sizeof(int), c->stream));
-    const mosaic_win G = mosaic_grid_win(p);
-    const unsigned ublocks = (unsigned)((cells + 255) / 256);
-    // launches of at most 2^31 samples (sub-samples: max_steps^2 a sample at most), the sample limit checked between them: a cell's count
-    // then stays far below 2^32 until the check sees it, so the packed accumulator cannot wrap unnoticed whatever the number of frames
-    const size_t per_sample = fp ? (size_t)fp->max_steps * fp->max_steps : 1;
-    int j0 = 0;
-    while (j0 < n) {
-        int j1 = j0, blocks = 0; size_t samples = 0;
-        while (j1 < n) {
-            const dsss_frame& f = c->frames[ids[j1]];
-            const size_t s = (size_t)f.N * f.M * per_sample;
-            if (j1 > j0 && samples + s > (1ull << 31)) break;
-            jobs[j1].blk0 = blocks;
-            blocks += f.N; samples += s; ++j1;
-        }
-        HIPCHK(c, hipMemcpyAsync(d_jobs + j0, jobs.data() + j0, (size_t)(j1 - j0) * sizeof(mosaic_job), hipMemcpyHostToDevice, c->stream));
-        if (!fp) launch_scatter(c, d_jobs + j0, j1 - j0, blocks, G, acc);
-        else hipLaunchKernelGGL(mosaic_scatter_fp_kernel, dim3((unsigned)blocks), dim3(256), 0, c->stream, d_jobs + j0, j1 - j0, G, *fp, acc);
-        HIPCHK(c, hipGetLastError());
-        if (j1 < n) { hipLaunchKernelGGL(mosaic_unpack_kernel, dim3(ublocks), dim3(256), 0, c->stream, acc, cells, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint8_t*)nullptr, d_flag); HIPCHK(c, hipGetLastError()); }
-        j0 = j1;
-    }
-    hipLaunchKernelGGL(mosaic_unpack_kernel, dim3(ublocks), dim3(256), 0, c->stream, acc, cells, d_sum, d_cnt, d_img, d_flag);
-    HIPCHK(c, hipGetLastError());
+    rc = mosaic_render_acc(c, ids, n, jobs, d_jobs, p, fp, acc, d_flag, d_sum, d_cnt, d_img); if (rc) return rc;
     rc = mosaic_flag_down(c, d_flag, "mosaic: a cell received more than 2^24 samples (cell %g too coarse for these frames)", p->cell); if (rc) return rc;
     if (sum_host) HIPCHK(c, hipMemcpyAsync(sum_host, d_sum, cells * 4, hipMemcpyDeviceToHost, c->stream));
     if (cnt_host) HIPCHK(c, hipMemcpyAsync(cnt_host, d_cnt, cells * 4, hipMemcpyDeviceToHost, c->stream));

@@ -4,6 +4,7 @@
 // fresh render of its frames reads.  The building blocks of the render kernels (dsss_mosaic_int.h) are used as they are; the kernels
 // here add the sign of a job, the fused move and the window form of the unpack.
 #include "dsss_mosaic_int.h"
+#include "dsss_mosaic_profile.h"
 #include "../../include/dsss_canvas.h"
 #include <algorithm>
 #include <map>
@@ -600,6 +601,39 @@ int dsss_canvas_frame_window(dsss_canvas* cv, int id, const double* rows, int32_
     if (!f.has_geom || !f.h_geo) DSSS_FAIL(c, DSSS_E_STATE, "frame %d has no geometry", id);
     canvas_window(cv, f, rows, win4);
     return DSSS_OK;
+}
+
+// The per-ping profile of frames of S against the canvas (include/dsss_profile.h), beside struct dsss_canvas because it reads the
+// accumulators and the row store: the canvas's accumulators are A, every listed frame is profiled under the device copy of its stored
+// rows with its stored window, and the launches are those of dsss_profile_mosaic (profile_plan).  Nothing of the canvas is written.
+int dsss_profile_canvas(dsss_canvas* cv, const int* ids, int n, const dsss_profile_params* pp, dsss_ping_stat* stats_host, int16_t* diff_host,
+                        dsss_profile_info* info)
+{
+    if (!cv) return DSSS_E_ARG;
+    dsss_ctx* c = cv->c;
+    if (info) memset(info, 0, sizeof *info);
+    if (cv->broken) DSSS_FAIL(c, DSSS_E_STATE, "canvas: broken by an earlier HIP error (dsss_canvas_clear starts over)");
+    if (cv->par.footprint) DSSS_FAIL(c, DSSS_E_ARG, "profile: a footprint canvas cannot be profiled");
+    int rc = canvas_check(cv, ids, n, nullptr, nullptr, true); if (rc) return rc;
+    profile_plan plan;
+    rc = profile_check_params(c, pp, &plan.min_count); if (rc) return rc;
+    for (int i = 0; i < n; ++i) { rc = profile_check_frame(c, ids[i]); if (rc) return rc; }
+    plan.want_stats = stats_host || info; plan.want_diff = diff_host != nullptr;
+    if (!plan.want_stats && !plan.want_diff) return DSSS_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    plan.frames.resize(n);
+    for (int i = 0; i < n; ++i) {
+        const canvas_entry& e = cv->S.find(ids[i])->second;
+        canvas_job j;
+        rc = canvas_job_of(c, ids[i], e.slot(e.cur), nullptr, +1, &j); if (rc) return rc;
+        profile_frame& f = plan.frames[i];
+        f.job = j; f.w = mosaic_grid_win(&cv->grid); f.on_grid = e.win[2] > 0;
+        if (f.on_grid) { f.w.ox = e.win[0]; f.w.oy = e.win[1]; f.w.bw = e.win[2]; f.w.bh = e.win[3]; }
+    }
+    mosaic_arena A;
+    plan.take(A, cv->cells());
+    rc = A.reserve(c); if (rc) return rc;
+    return canvas_fail(cv, plan.run(c, A, &cv->grid, cv->acc.as<unsigned long long>(), stats_host, diff_host, info));
 }
 
 } // extern "C"

@@ -106,8 +106,10 @@ template <class JOB> __device__ __forceinline__ JOB mosaic_job_of(const JOB* __r
 // workgroup has no ping; it leaves in front of the barrier (uniform per workgroup; cannot happen with the host's blk0).
 // The partner form (PP given; the footprint kernels): *PP = the pose row of the ping's partner, the next ping of the frame, or the one
 // before for the frame's last ping (*last; a frame of one ping is its own partner), and s_sc is the kernel's __shared__ double[8]: behind
-// the ping's four values, sin and cos of both sides of the partner.
-__device__ __forceinline__ bool mosaic_ping_of(const mosaic_job* __restrict__ jobs, int njobs, double* s_sc, mosaic_job& J, int& row, const double*& P,
+// the ping's four values, sin and cos of both sides of the partner.  JOB = mosaic_job, or a record that derives from it (the
+// profile's prof_job, dsss_mosaic_profile.hip).
+template <class JOB>
+__device__ __forceinline__ bool mosaic_ping_of(const JOB* __restrict__ jobs, int njobs, double* s_sc, JOB& J, int& row, const double*& P,
                                                const double** PP = nullptr, bool* last = nullptr)
 {
     J = mosaic_job_of(jobs, njobs); row = (int)blockIdx.x - J.blk0;
@@ -377,6 +379,10 @@ int mosaic_check_gain(dsss_ctx* c, const int* ids, int n);
 // d_rows) and every job gets its rows, geometry, images and the context's table.
 int mosaic_fill_jobs(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, double* d_rows, std::vector<mosaic_job>& jobs);
 void launch_scatter(dsss_ctx* c, const mosaic_job* d_jobs, int njobs, int blocks, const mosaic_win& G, unsigned long long* acc);
+// the accumulators of a render on the grid p (acc: W x H, cleared here) and the unpack into the layers given, null: the sample-limit
+// check alone (d_flag, cleared here; mosaic_flag_down reads it); jobs = mosaic_fill_jobs' table, d_jobs = room for it on the device
+int mosaic_render_acc(dsss_ctx* c, const int* ids, int n, std::vector<mosaic_job>& jobs, mosaic_job* d_jobs, const dsss_mosaic_params* p,
+                      const dsss_footprint_params* fp, unsigned long long* acc, int* d_flag, uint32_t* d_sum, uint32_t* d_cnt, uint8_t* d_img);
 // the segmented form for ONE frame (d_job: its record, blk0 = 0; blocks = its pings): ping p goes into d_segs[p / seg_pings]
 void launch_scatter_seg(dsss_ctx* c, const mosaic_job* d_job, int blocks, const mosaic_win& G, unsigned long long* acc, const mosaic_seg* d_segs, int seg_pings);
 
