@@ -63,12 +63,11 @@ __global__ __launch_bounds__(256) void mosaic_unpack_kernel(const unsigned long 
 {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const unsigned long long a = acc[i];
-    const uint32_t c = (uint32_t)(a >> 32), s = (uint32_t)a;
-    if (c > MOSAIC_MAX_SAMPLES) *flag = 1;
-    if (sum) sum[i] = s;
-    if (cnt) cnt[i] = c;
-    if (img) img[i] = c ? (uint8_t)((s + c / 2) / c) : (uint8_t)0;
+    const mosaic_acc a(acc[i]);
+    if (a.over_limit()) *flag = 1;
+    if (sum) sum[i] = a.s;
+    if (cnt) cnt[i] = a.c;
+    if (img) img[i] = a.c ? (uint8_t)a.mean() : (uint8_t)0;
 }
 
 // one frame's window folded into the three layers of the consistency map: one frame at a time, so plain stores
@@ -77,11 +76,10 @@ __global__ __launch_bounds__(256) void mosaic_fold_kernel(const unsigned long lo
 {
     const size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (j >= (size_t)G.bw * G.bh) return;
-    const unsigned long long a = win[j];
-    const uint32_t c = (uint32_t)(a >> 32), s = (uint32_t)a;
-    if (c == 0) return;
-    if (c > MOSAIC_MAX_SAMPLES) *flag = 1;
-    const uint32_t m = (s + c / 2) / c;
+    const mosaic_acc a(win[j]);
+    if (a.c == 0) return;
+    if (a.over_limit()) *flag = 1;
+    const uint32_t m = a.mean();
     const int jy = (int)(j / G.bw), jx = (int)(j - (size_t)jy * G.bw);
     const size_t g = (size_t)(G.oy + jy) * G.W + (G.ox + jx);
     nfr[g] += 1; s1[g] += m; s2[g] += m * m;
@@ -374,12 +372,15 @@ bool cell_range(double lo, double hi, double origin, double cell, int n, int* a,
 
 mosaic_win mosaic_grid_win(const dsss_mosaic_params* p) { return mosaic_win{ p->x0, p->y0, p->cell, p->W, p->H, 0, 0, p->W, p->H, p->use_mask != 0 }; }
 
-bool mosaic_window(const dsss_frame& f, const double* rows, int r0, int r1, const dsss_mosaic_params* p, mosaic_win* w)
+// (grow = 0 leaves the point windows their bits: x - 0.0 is x for every double, and x + 0.0 differs from x in the sign of a zero alone,
+// which cell_range's differences, comparisons and conversion do not see)
+bool mosaic_window(const dsss_frame& f, const double* rows, int r0, int r1, const dsss_mosaic_params* p, mosaic_win* w, double grow)
 {
     double bb[4] = { INFINITY, -INFINITY, INFINITY, -INFINITY };
     frame_extent_rows(f, rows, r0, r1, bb);
     int ax, bx, ay, by;
-    if (!cell_range(bb[0], bb[1], p->x0, p->cell, p->W, &ax, &bx) || !cell_range(bb[2], bb[3], p->y0, p->cell, p->H, &ay, &by)) return false;
+    if (!cell_range(bb[0] - grow, bb[1] + grow, p->x0, p->cell, p->W, &ax, &bx) ||
+        !cell_range(bb[2] - grow, bb[3] + grow, p->y0, p->cell, p->H, &ay, &by)) return false;
     *w = mosaic_grid_win(p);
     w->ox = ax; w->oy = ay; w->bw = bx - ax + 1; w->bh = by - ay + 1;
     return true;
@@ -444,7 +445,7 @@ void launch_scatter_seg(dsss_ctx* c, const mosaic_job* d_job, int blocks, const 
 // The accumulators of a render, for the render entries and the profile (dsss_mosaic_profile.hip): acc and the flag cleared, the frames
 // scattered (fp == null: as points, otherwise the sub-samples of their footprints), then the unpack into the layers given (null: the
 // sample-limit check alone).  jobs = the host's table (mosaic_fill_jobs), whose blk0 are set here; d_jobs = room for it on the device.
-int mosaic_render_acc(dsss_ctx* c, const int* ids, int n, std::vector<mosaic_job>& jobs, mosaic_job* d_jobs, const dsss_mosaic_params* p,
+int mosaic_render_acc(dsss_ctx* c, std::vector<mosaic_job>& jobs, mosaic_job* d_jobs, const dsss_mosaic_params* p,
                       const dsss_footprint_params* fp, unsigned long long* acc, int* d_flag, uint32_t* d_sum, uint32_t* d_cnt, uint8_t* d_img)
 {
     const size_t cells = (size_t)p->W * p->H;
@@ -452,25 +453,13 @@ int mosaic_render_acc(dsss_ctx* c, const int* ids, int n, std::vector<mosaic_job
     HIPCHK(c, hipMemsetAsync(d_flag, 0, sizeof(int), c->stream));
     const mosaic_win G = mosaic_grid_win(p);
     const unsigned ublocks = (unsigned)((cells + 255) / 256);
-    // launches of at most 2^31 samples (sub-samples: max_steps^2 a sample at most), the sample limit checked between them: a cell's count
-    // then stays far below 2^32 until the check sees it, so the packed accumulator cannot wrap unnoticed whatever the number of frames
-    const size_t per_sample = fp ? (size_t)fp->max_steps * fp->max_steps : 1;
-    int j0 = 0;
-    while (j0 < n) {
-        int j1 = j0, blocks = 0; size_t samples = 0;
-        while (j1 < n) {
-            const dsss_frame& f = c->frames[ids[j1]];
-            const size_t s = (size_t)f.N * f.M * per_sample;
-            if (j1 > j0 && samples + s > (1ull << 31)) break;
-            jobs[j1].blk0 = blocks;
-            blocks += f.N; samples += s; ++j1;
-        }
-        HIPCHK(c, hipMemcpyAsync(d_jobs + j0, jobs.data() + j0, (size_t)(j1 - j0) * sizeof(mosaic_job), hipMemcpyHostToDevice, c->stream));
-        if (!fp) launch_scatter(c, d_jobs + j0, j1 - j0, blocks, G, acc);
-        else hipLaunchKernelGGL(mosaic_scatter_fp_kernel, dim3((unsigned)blocks), dim3(256), 0, c->stream, d_jobs + j0, j1 - j0, G, *fp, acc);
+    // the sample limit is checked between the launches (mosaic_cut_launches' comment)
+    for (const mosaic_launch& L : mosaic_cut_launches(jobs, fp)) {
+        if (L.j0 > 0) { hipLaunchKernelGGL(mosaic_unpack_kernel, dim3(ublocks), dim3(256), 0, c->stream, acc, cells, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint8_t*)nullptr, d_flag); HIPCHK(c, hipGetLastError()); }
+        HIPCHK(c, hipMemcpyAsync(d_jobs + L.j0, jobs.data() + L.j0, (size_t)(L.j1 - L.j0) * sizeof(mosaic_job), hipMemcpyHostToDevice, c->stream));
+        if (!fp) launch_scatter(c, d_jobs + L.j0, L.j1 - L.j0, L.blocks, G, acc);
+        else hipLaunchKernelGGL(mosaic_scatter_fp_kernel, dim3((unsigned)L.blocks), dim3(256), 0, c->stream, d_jobs + L.j0, L.j1 - L.j0, G, *fp, acc);
         HIPCHK(c, hipGetLastError());
-        if (j1 < n) { hipLaunchKernelGGL(mosaic_unpack_kernel, dim3(ublocks), dim3(256), 0, c->stream, acc, cells, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint8_t*)nullptr, d_flag); HIPCHK(c, hipGetLastError()); }
-        j0 = j1;
     }
     hipLaunchKernelGGL(mosaic_unpack_kernel, dim3(ublocks), dim3(256), 0, c->stream, acc, cells, d_sum, d_cnt, d_img, d_flag);
     HIPCHK(c, hipGetLastError());
@@ -516,19 +505,15 @@ static int render_run(dsss_ctx* c, const int* ids, int n, const double* rpy6, co
     const size_t cells = (size_t)p->W * p->H;
     mosaic_arena A;
     const auto o_acc = A.take<unsigned long long>(cells);
-    const auto o_sum = A.take<uint32_t>(sum_host ? cells : 0), o_cnt = A.take<uint32_t>(cnt_host ? cells : 0);
-    const auto o_img = A.take<uint8_t>(img_host ? cells : 0);
+    const mosaic_layers L(A, cells, sum_host, cnt_host, img_host);
     const auto o_jobs = A.take<mosaic_job>(n); const auto o_rows = A.take<double>(rpy6 ? rows * 6 : 0); const auto o_flag = A.take<int>(1);
     rc = A.reserve(c); if (rc) return rc;
     unsigned long long* acc = A.at(o_acc); mosaic_job* d_jobs = A.at(o_jobs); int* d_flag = A.at(o_flag);
-    uint32_t* d_sum = A.opt(o_sum); uint32_t* d_cnt = A.opt(o_cnt); uint8_t* d_img = A.opt(o_img);
     std::vector<mosaic_job> jobs;
     rc = mosaic_fill_jobs(c, ids, n, rpy6, ping_off, A.at(o_rows), jobs); if (rc) return rc;
-    rc = mosaic_render_acc(c, ids, n, jobs, d_jobs, p, fp, acc, d_flag, d_sum, d_cnt, d_img); if (rc) return rc;
+    rc = mosaic_render_acc(c, jobs, d_jobs, p, fp, acc, d_flag, A.opt(L.o_sum), A.opt(L.o_cnt), A.opt(L.o_img)); if (rc) return rc;
     rc = mosaic_flag_down(c, d_flag, "mosaic: a cell received more than 2^24 samples (cell %g too coarse for these frames)", p->cell); if (rc) return rc;
-    if (sum_host) HIPCHK(c, hipMemcpyAsync(sum_host, d_sum, cells * 4, hipMemcpyDeviceToHost, c->stream));
-    if (cnt_host) HIPCHK(c, hipMemcpyAsync(cnt_host, d_cnt, cells * 4, hipMemcpyDeviceToHost, c->stream));
-    if (img_host) HIPCHK(c, hipMemcpyAsync(img_host, d_img, cells, hipMemcpyDeviceToHost, c->stream));
+    rc = L.down(c, A); if (rc) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return DSSS_OK;
 }

@@ -1,8 +1,9 @@
 // diasss_amd/csrc/dsss_mosaic_canvas.hip -- the mosaic canvas (include/dsss_canvas.h): the accumulators of one grid kept on the device
 // between calls, frames added, moved and removed by signed scatters.  The accumulator of a cell is count << 32 | sum, filled by 64-bit
 // atomic adds, so what a frame added is taken out again exactly by adding its two's complement, and the canvas always reads what a
-// fresh render of its frames reads.  The building blocks of the render kernels (dsss_mosaic_int.h) are used as they are; the kernels
-// here add the sign of a job, the fused move and the window form of the unpack.
+// fresh render of its frames reads.  That holds because the canvas kernels run the render kernels' own prologue, sample loops and
+// accumulator word (dsss_mosaic_int.h) with the sign of a job; what is written here is the fused move's loop and the window form of the
+// unpack.
 #include "dsss_mosaic_int.h"
 #include "dsss_mosaic_profile.h"
 #include "../../include/dsss_canvas.h"
@@ -15,83 +16,43 @@ namespace {
 // workgroup) and, for the fused move, the rows the frame moves to (pose: out, pose2: in)
 struct canvas_job : mosaic_job { const double* pose2 = nullptr; int sign = 1, pad_ = 0; };
 
-// what a run of `v` (count << 16 | sum within the wavefront) adds to its cell.  The packed word is modular: a negative job adds the
-// two's complement, and while the jobs of one call are in flight a borrow or carry may pass between the sum and the count field.  That
-// is harmless: the adds commute, every job of a call has landed before anything is read, and then both fields are what a fresh render
-// of the canvas's frames gives -- only the final fields are ever read.
-__device__ __forceinline__ void canvas_add(unsigned long long* __restrict__ acc, int key, unsigned v, bool negative)
-{
-    const unsigned long long packed = ((unsigned long long)(v >> 16) << 32) | (v & 0xffffu);
-    atomicAdd(&acc[key], negative ? 0ull - packed : packed);                       // (result unused: the atomic without return)
-}
+// the second row of the fused move's prologue (mosaic_ping_of's partner form): the row the ping moves to; no ping is the last
+struct canvas_moved_row {
+    __device__ __forceinline__ const double* operator()(const canvas_job& J, int row, bool& last) const { last = false; return J.pose2 + (size_t)row * 6; }
+};
 
-// The signed form of mosaic_scatter_kernel, in its launch shape: one workgroup per ping through the job table, 256 threads, the
-// segmented run reduce, one 64-bit atomic without return per run.  Add jobs and remove jobs share a launch.
+// The signed form of mosaic_scatter_kernel: its prologue and its body (mosaic_ping_of, mosaic_scatter_samples) with the sign of the
+// job, which is uniform per workgroup.  Add jobs and remove jobs share a launch.
 __global__ __launch_bounds__(256) void mosaic_canvas_kernel(const canvas_job* __restrict__ jobs, int njobs, mosaic_win G, unsigned long long* __restrict__ acc)
 {
     __shared__ double s_sc[4];
-    canvas_job J = mosaic_job_of(jobs, njobs);
-    const int row = (int)blockIdx.x - J.blk0;
-    if (row >= J.N) return;                                                        // (uniform per workgroup; cannot happen with the host's blk0)
-    const double* P = J.pose + (size_t)row * 6;
-    J.gain = mosaic_gain_row(J, row);
-    if (threadIdx.x < 2) dsss_geo_side(P, threadIdx.x == 1, &s_sc[2 * threadIdx.x], &s_sc[2 * threadIdx.x + 1]);
-    __syncthreads();
-    const int M = J.M;
-    const bool negative = J.sign < 0;
-    const uint8_t* __restrict__ img = J.img + (size_t)row * M;
-    const uint8_t* __restrict__ mask = J.mask + (size_t)row * M;
-    for (int c0 = 0; c0 < M; c0 += 256) {
-        unsigned g = 0;
-        const int key = mosaic_sample_cell(P, s_sc, J, img, mask, c0 + (int)threadIdx.x, G, &g);
-        unsigned v = key >= 0 ? (1u << 16) | g : 0u;
-        const bool tail = mosaic_run_reduce(key, v, [](unsigned a, unsigned b) { return a + b; });
-        if (tail && key >= 0) canvas_add(acc, key, v, negative);
-    }
+    canvas_job J; int row; const double* P;
+    if (!mosaic_ping_of(jobs, njobs, s_sc, J, row, P)) return;
+    mosaic_scatter_samples<true>(P, s_sc, J, row, G, acc, J.sign < 0);
 }
 
-// The signed form of mosaic_scatter_fp_kernel: the ping and its partner (the next ping, the one before for the frame's last) with sin
-// and cos of both sides of both in LDS, then the sub-samples by the one body (mosaic_footprint_samples).
+// The signed form of mosaic_scatter_fp_kernel: the prologue in the partner form, then the sub-samples by the one body
+// (mosaic_scatter_footprints) with the sign of the job.
 __global__ __launch_bounds__(256) void mosaic_canvas_fp_kernel(const canvas_job* __restrict__ jobs, int njobs, mosaic_win G, dsss_footprint_params F,
                                                                unsigned long long* __restrict__ acc)
 {
     __shared__ double s_sc[8];
-    canvas_job J = mosaic_job_of(jobs, njobs);
-    const int row = (int)blockIdx.x - J.blk0;
-    if (row >= J.N) return;
-    const bool last = row == J.N - 1;
-    const double* P = J.pose + (size_t)row * 6;
-    const double* PP = J.pose + (size_t)(last ? (row > 0 ? row - 1 : row) : row + 1) * 6;
-    J.gain = mosaic_gain_row(J, row);
-    if (threadIdx.x < 4) dsss_geo_side(threadIdx.x < 2 ? P : PP, threadIdx.x & 1, &s_sc[2 * threadIdx.x], &s_sc[2 * threadIdx.x + 1]);
-    __syncthreads();
-    const bool negative = J.sign < 0;
-    const uint8_t* __restrict__ img = J.img + (size_t)row * J.M;
-    mosaic_footprint_samples(P, PP, last, s_sc, J, row, G, F,
-        [&](int col) { return (1u << 16) | mosaic_gain_apply(img[col], J.gain, col); },
-        [&](int key, unsigned g) {
-            unsigned v = key >= 0 ? g : 0u;
-            const bool tail = mosaic_run_reduce(key, v, [](unsigned a, unsigned b) { return a + b; });
-            if (tail && key >= 0) canvas_add(acc, key, v, negative);
-        });
+    canvas_job J; int row; const double* P; const double* PP; bool last;
+    if (!mosaic_ping_of(jobs, njobs, s_sc, J, row, P, &PP, &last)) return;
+    mosaic_scatter_footprints<true>(P, PP, last, s_sc, J, row, G, F, acc, J.sign < 0);
 }
 
 // The fused move of a point canvas: one workgroup per ping of a moved frame, the bearings of the old row (J.pose) and of the new one
-// (J.pose2) in LDS as 8 doubles.  A lane bins its sample under both rows; the value is the same under both, because the mask, the
-// gain column and the altitude band do not depend on the pose.  A sample whose cell is the same under both rows issues nothing -- the
-// scatter runs at the rate of its atomics, and a centimetre-level correction leaves most samples where they were.  The others go through
-// two run reductions: the old keys are subtracted, the new keys are added.  A row that is not finite has key -1 on its side.
+// (J.pose2) in LDS as 8 doubles (the prologue's partner form with canvas_moved_row).  A lane bins its sample under both rows; the value
+// is the same under both, because the mask, the gain column and the altitude band do not depend on the pose.  A sample whose cell is
+// the same under both rows issues nothing -- the scatter runs at the rate of its atomics, and a centimetre-level correction leaves most
+// samples where they were.  The others go through two run reductions (mosaic_run_add): the old keys are subtracted, the new keys are
+// added.  A row that is not finite has key -1 on its side.  Two keys per sample and the skip are why this loop is its own.
 __global__ __launch_bounds__(256) void mosaic_canvas_move_kernel(const canvas_job* __restrict__ jobs, int njobs, mosaic_win G, unsigned long long* __restrict__ acc)
 {
     __shared__ double s_sc[8];
-    canvas_job J = mosaic_job_of(jobs, njobs);
-    const int row = (int)blockIdx.x - J.blk0;
-    if (row >= J.N) return;
-    const double* P0 = J.pose + (size_t)row * 6;
-    const double* P1 = J.pose2 + (size_t)row * 6;
-    J.gain = mosaic_gain_row(J, row);
-    if (threadIdx.x < 4) dsss_geo_side(threadIdx.x < 2 ? P0 : P1, threadIdx.x & 1, &s_sc[2 * threadIdx.x], &s_sc[2 * threadIdx.x + 1]);
-    __syncthreads();
+    canvas_job J; int row; const double* P0; const double* P1; bool last;      // (last: the partner form's, false for every ping here)
+    if (!mosaic_ping_of(jobs, njobs, s_sc, J, row, P0, &P1, &last, canvas_moved_row())) return;
     const int M = J.M;
     const uint8_t* __restrict__ img = J.img + (size_t)row * M;
     const uint8_t* __restrict__ mask = J.mask + (size_t)row * M;
@@ -103,11 +64,9 @@ __global__ __launch_bounds__(256) void mosaic_canvas_move_kernel(const canvas_jo
         const unsigned g = k0 >= 0 ? g0 : g1;
         if (k0 == k1) { k0 = -1; k1 = -1; }                                        // the sample stays in its cell (or is dropped under both rows)
         if (__ballot(k0 != k1) == 0ull) continue;                                  // no lane of the wavefront moved (uniform over the wavefront)
-        unsigned v0 = k0 >= 0 ? (1u << 16) | g : 0u, v1 = k1 >= 0 ? (1u << 16) | g : 0u;
-        const bool tail0 = mosaic_run_reduce(k0, v0, [](unsigned a, unsigned b) { return a + b; });
-        if (tail0 && k0 >= 0) canvas_add(acc, k0, v0, true);
-        const bool tail1 = mosaic_run_reduce(k1, v1, [](unsigned a, unsigned b) { return a + b; });
-        if (tail1 && k1 >= 0) canvas_add(acc, k1, v1, false);
+        const unsigned v0 = k0 >= 0 ? (1u << 16) | g : 0u, v1 = k1 >= 0 ? (1u << 16) | g : 0u;
+        mosaic_run_add<true>(acc, k0, v0, true);
+        mosaic_run_add<true>(acc, k1, v1, false);
     }
 }
 
@@ -119,12 +78,11 @@ __global__ __launch_bounds__(256) void mosaic_canvas_unpack_kernel(const unsigne
     const size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (j >= (size_t)bw * bh) return;
     const int jy = (int)(j / (size_t)bw), jx = (int)(j - (size_t)jy * bw);
-    const unsigned long long a = acc[(size_t)(oy + jy) * W + (ox + jx)];
-    const uint32_t c = (uint32_t)(a >> 32), s = (uint32_t)a;
-    if (c > MOSAIC_MAX_SAMPLES) *flag = 1;
-    if (sum) sum[j] = s;
-    if (cnt) cnt[j] = c;
-    if (img) img[j] = c ? (uint8_t)((s + c / 2) / c) : (uint8_t)0;
+    const mosaic_acc a(acc[(size_t)(oy + jy) * W + (ox + jx)]);
+    if (a.over_limit()) *flag = 1;
+    if (sum) sum[j] = a.s;
+    if (cnt) cnt[j] = a.c;
+    if (img) img[j] = a.c ? (uint8_t)a.mean() : (uint8_t)0;
 }
 
 // ---- the row store: the device copies of the frames' rows, the canvas's own memory (mosaic_buf is scratch that other mosaic entries
@@ -193,22 +151,20 @@ struct dsss_canvas {
 
 namespace {
 
+// the one refusal of a broken canvas: every entry but clear and destroy starts with it
+int canvas_refuse_broken(const dsss_canvas* cv)
+{
+    if (cv->broken) DSSS_FAIL(cv->c, DSSS_E_STATE, "canvas: broken by an earlier HIP error (dsss_canvas_clear starts over)");
+    return DSSS_OK;
+}
+
 // the window of a frame under `rows` on the canvas's grid (include/dsss_canvas.h, "Windows"); none: bw = 0
 void canvas_window(const dsss_canvas* cv, const dsss_frame& f, const double* rows, int32_t* w)
 {
     win_none(w);
-    if (!cv->par.footprint) {
-        mosaic_win mw;
-        if (mosaic_window(f, rows, 0, f.N, &cv->grid, &mw)) { w[0] = mw.ox; w[1] = mw.oy; w[2] = mw.bw; w[3] = mw.bh; }
-        return;
-    }
-    double bb[4] = { INFINITY, -INFINITY, INFINITY, -INFINITY };
-    frame_extent_rows(f, rows, 0, f.N, bb);
-    const double grow = 2.0 * cv->par.fp.max_gap;                                  // a sub-sample lies within (7/8) 2 max_gap per axis of its parent
-    int ax, bx, ay, by;
-    if (!cell_range(bb[0] - grow, bb[1] + grow, cv->grid.x0, cv->grid.cell, cv->grid.W, &ax, &bx) ||
-        !cell_range(bb[2] - grow, bb[3] + grow, cv->grid.y0, cv->grid.cell, cv->grid.H, &ay, &by)) return;
-    w[0] = ax; w[1] = ay; w[2] = bx - ax + 1; w[3] = by - ay + 1;
+    const double grow = cv->par.footprint ? 2.0 * cv->par.fp.max_gap : 0.0;        // a sub-sample lies within (7/8) 2 max_gap per axis of its parent
+    mosaic_win mw;
+    if (mosaic_window(f, rows, 0, f.N, &cv->grid, &mw, grow)) { w[0] = mw.ox; w[1] = mw.oy; w[2] = mw.bw; w[3] = mw.bh; }
 }
 
 void canvas_launch_jobs(dsss_canvas* cv, const canvas_launch& L, const canvas_job* d_jobs, const canvas_job* d_moves)
@@ -222,22 +178,10 @@ void canvas_launch_jobs(dsss_canvas* cv, const canvas_launch& L, const canvas_jo
     else hipLaunchKernelGGL(mosaic_canvas_kernel, dim3((unsigned)L.blocks), dim3(256), 0, c->stream, d_jobs + L.j0, nj, G, acc);
 }
 
-// the launches of a table, cut at 2^31 (sub-)samples as dsss_mosaic_render cuts them; blk0 of every job is set
+// the launches of a table, the render's cut (mosaic_cut_launches); blk0 of every job is set
 void canvas_plan(dsss_canvas* cv, std::vector<canvas_job>& tab, bool fused, std::vector<canvas_launch>& out)
 {
-    const size_t per_sample = cv->par.footprint ? (size_t)cv->par.fp.max_steps * cv->par.fp.max_steps : 1;
-    const int n = (int)tab.size();
-    int j0 = 0;
-    while (j0 < n) {
-        int j1 = j0; long long blocks = 0; size_t samples = 0;
-        while (j1 < n) {
-            const size_t s = (size_t)tab[j1].N * tab[j1].M * per_sample;
-            if (j1 > j0 && (samples + s > (1ull << 31) || blocks + tab[j1].N > 0x7fffffffll)) break;
-            tab[j1].blk0 = (int)blocks; blocks += tab[j1].N; samples += s; ++j1;
-        }
-        out.push_back({ fused, j0, j1, (int)blocks });
-        j0 = j1;
-    }
+    for (const mosaic_launch& L : mosaic_cut_launches(tab, cv->par.footprint ? &cv->par.fp : nullptr)) out.push_back({ fused, L.j0, L.j1, L.blocks });
 }
 
 // the same jobs with the signs flipped: a scatter job changes its sign, a fused move swaps the rows it moves between
@@ -316,9 +260,9 @@ int canvas_job_of(dsss_ctx* c, int id, const double* pose, const double* pose2, 
 int canvas_check(dsss_canvas* cv, const int* ids, int n, const double* rpy6, const int* ping_off, bool must_be_in)
 {
     dsss_ctx* c = cv->c;
-    if (cv->broken) DSSS_FAIL(c, DSSS_E_STATE, "canvas: broken by an earlier HIP error (dsss_canvas_clear starts over)");
+    int rc = canvas_refuse_broken(cv); if (rc) return rc;
     size_t rows = 0;
-    int rc = mosaic_check_frames(c, ids, n, rpy6, ping_off, true, &rows); if (rc) return rc;
+    rc = mosaic_check_frames(c, ids, n, rpy6, ping_off, true, &rows); if (rc) return rc;
     if (cv->par.footprint) { dsss_footprint_params F; rc = mosaic_check_footprint(c, ids, n, &cv->par.fp, &F); if (rc) return rc; }
     rc = mosaic_check_gain(c, ids, n); if (rc) return rc;
     if (must_be_in)
@@ -521,7 +465,7 @@ int dsss_canvas_read(dsss_canvas* cv, const int32_t* win4, uint32_t* sum, uint32
 {
     if (!cv) return DSSS_E_ARG;
     dsss_ctx* c = cv->c;
-    if (cv->broken) DSSS_FAIL(c, DSSS_E_STATE, "canvas: broken by an earlier HIP error (dsss_canvas_clear starts over)");
+    int rc = canvas_refuse_broken(cv); if (rc) return rc;
     int32_t w[4] = { 0, 0, cv->grid.W, cv->grid.H };
     if (win4) memcpy(w, win4, sizeof w);
     if (w[0] < 0 || w[1] < 0 || w[2] < 1 || w[3] < 1 || (long long)w[0] + w[2] > cv->grid.W || (long long)w[1] + w[3] > cv->grid.H)
@@ -529,17 +473,13 @@ int dsss_canvas_read(dsss_canvas* cv, const int32_t* win4, uint32_t* sum, uint32
     HIPCHK(c, hipSetDevice(c->device));
     const size_t cells = (size_t)w[2] * w[3];
     mosaic_arena A;
-    const auto o_sum = A.take<uint32_t>(sum ? cells : 0), o_cnt = A.take<uint32_t>(cnt ? cells : 0);
-    const auto o_img = A.take<uint8_t>(img ? cells : 0); const auto o_flag = A.take<int>(1);
-    const int rc = A.reserve(c); if (rc) return rc;
-    uint32_t* d_sum = A.opt(o_sum); uint32_t* d_cnt = A.opt(o_cnt); uint8_t* d_img = A.opt(o_img);
-    if (sum || cnt || img) {
+    const mosaic_layers L(A, cells, sum, cnt, img); const auto o_flag = A.take<int>(1);
+    rc = A.reserve(c); if (rc) return rc;
+    if (L.any()) {
         hipLaunchKernelGGL(mosaic_canvas_unpack_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, c->stream, cv->acc.as<unsigned long long>(), cv->grid.W,
-                           w[0], w[1], w[2], w[3], d_sum, d_cnt, d_img, A.at(o_flag));
+                           w[0], w[1], w[2], w[3], A.opt(L.o_sum), A.opt(L.o_cnt), A.opt(L.o_img), A.at(o_flag));
         HIPCHK(c, hipGetLastError());
-        if (sum) HIPCHK(c, hipMemcpyAsync(sum, d_sum, cells * 4, hipMemcpyDeviceToHost, c->stream));
-        if (cnt) HIPCHK(c, hipMemcpyAsync(cnt, d_cnt, cells * 4, hipMemcpyDeviceToHost, c->stream));
-        if (img) HIPCHK(c, hipMemcpyAsync(img, d_img, cells, hipMemcpyDeviceToHost, c->stream));
+        rc = L.down(c, A); if (rc) return rc;
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return DSSS_OK;
@@ -548,7 +488,7 @@ int dsss_canvas_read(dsss_canvas* cv, const int32_t* win4, uint32_t* sum, uint32
 int dsss_canvas_dirty(dsss_canvas* cv, int32_t* win4, int reset)
 {
     if (!cv) return DSSS_E_ARG;
-    if (cv->broken) DSSS_FAIL(cv->c, DSSS_E_STATE, "canvas: broken by an earlier HIP error (dsss_canvas_clear starts over)");
+    const int rc = canvas_refuse_broken(cv); if (rc) return rc;
     if (!win4) DSSS_FAIL(cv->c, DSSS_E_ARG, "canvas: nowhere to write the dirty window");
     memcpy(win4, cv->dirty, sizeof cv->dirty);
     if (reset) win_none(cv->dirty);
@@ -559,7 +499,7 @@ int dsss_canvas_frames(const dsss_canvas* cv, int* ids_host, int cap, int* n)
 {
     if (!cv) return DSSS_E_ARG;
     dsss_ctx* c = cv->c;
-    if (cv->broken) DSSS_FAIL(c, DSSS_E_STATE, "canvas: broken by an earlier HIP error (dsss_canvas_clear starts over)");
+    const int rc = canvas_refuse_broken(cv); if (rc) return rc;
     if (!n) DSSS_FAIL(c, DSSS_E_ARG, "canvas: nowhere to write the number of frames");
     *n = (int)cv->S.size();                                                        // also when there is no room for them: the caller learns how many
     if (cv->S.empty()) return DSSS_OK;
@@ -573,7 +513,7 @@ int dsss_canvas_rows(dsss_canvas* cv, int id, double* rows_host)
 {
     if (!cv) return DSSS_E_ARG;
     dsss_ctx* c = cv->c;
-    if (cv->broken) DSSS_FAIL(c, DSSS_E_STATE, "canvas: broken by an earlier HIP error (dsss_canvas_clear starts over)");
+    const int rc = canvas_refuse_broken(cv); if (rc) return rc;
     if (!rows_host) DSSS_FAIL(c, DSSS_E_ARG, "canvas: nowhere to write the rows");
     const auto it = cv->S.find(id);
     if (it == cv->S.end()) DSSS_FAIL(c, DSSS_E_ARG, "canvas: frame %d is not on the canvas", id);
@@ -587,7 +527,7 @@ int dsss_canvas_frame_window(dsss_canvas* cv, int id, const double* rows, int32_
 {
     if (!cv) return DSSS_E_ARG;
     dsss_ctx* c = cv->c;
-    if (cv->broken) DSSS_FAIL(c, DSSS_E_STATE, "canvas: broken by an earlier HIP error (dsss_canvas_clear starts over)");
+    const int rc = canvas_refuse_broken(cv); if (rc) return rc;
     if (!win4) DSSS_FAIL(c, DSSS_E_ARG, "canvas: nowhere to write the window");
     if (id < 0 || id >= c->max_frames) DSSS_FAIL(c, DSSS_E_ARG, "frame id %d out of range [0,%d)", id, c->max_frames);
     const dsss_frame& f = c->frames[id];
@@ -612,9 +552,9 @@ int dsss_profile_canvas(dsss_canvas* cv, const int* ids, int n, const dsss_profi
     if (!cv) return DSSS_E_ARG;
     dsss_ctx* c = cv->c;
     if (info) memset(info, 0, sizeof *info);
-    if (cv->broken) DSSS_FAIL(c, DSSS_E_STATE, "canvas: broken by an earlier HIP error (dsss_canvas_clear starts over)");
+    int rc = canvas_refuse_broken(cv); if (rc) return rc;
     if (cv->par.footprint) DSSS_FAIL(c, DSSS_E_ARG, "profile: a footprint canvas cannot be profiled");
-    int rc = canvas_check(cv, ids, n, nullptr, nullptr, true); if (rc) return rc;
+    rc = canvas_check(cv, ids, n, nullptr, nullptr, true); if (rc) return rc;
     profile_plan plan;
     rc = profile_check_params(c, pp, &plan.min_count); if (rc) return rc;
     for (int i = 0; i < n; ++i) { rc = profile_check_frame(c, ids[i]); if (rc) return rc; }

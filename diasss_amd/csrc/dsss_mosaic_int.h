@@ -1,11 +1,15 @@
-// diasss_amd/csrc/dsss_mosaic_int.h -- what dsss_mosaic.hip (mosaic, consistency map), dsss_mosaic_reg.hip (overlap registration) and
-// dsss_mosaic_comp.hip (composite mosaic) share.  Device: the job and window records of mosaic_scatter_kernel, the binning of a sample, the
-// kernels' scaffolding written once (job lookup mosaic_job_of, ping prologue mosaic_ping_of, segmented reduction mosaic_run_reduce), the
-// sub-samples of the footprint kernels (footprint_steps, mosaic_footprint_samples), then
-// the rules of the composite and the score, order and sub-cell rules of the registration, one body for host and device.  Host: the typed
-// arena over mosaic_buf, the argument rules (mosaic_check_args), the windows of the grid (mosaic_grid_win, mosaic_window), the sample-limit
-// flag (mosaic_flag_down), the upload of a caller's trajectory and the scatter launch, defined in dsss_mosaic.hip, and what
-// dsss_mosaic_reg.hip needs of the registration's host arithmetic (dsss_mosaic_edge.cpp).
+// diasss_amd/csrc/dsss_mosaic_int.h -- what the mosaic family shares (dsss_mosaic.hip, dsss_mosaic_comp.hip, dsss_mosaic_reg.hip,
+// dsss_mosaic_canvas.hip, dsss_mosaic_profile.hip); every rule here is written once and nowhere else.  Device: the job and window
+// records and the job lookup (mosaic_job_of); the ping prologue of every ping-per-workgroup kernel (mosaic_ping_of: pose row, gain row,
+// bearings in LDS, in the partner form a second row, the neighbouring ping or one the caller names); the rules of a sample (mask, cell,
+// corrected value: mosaic_sample_cell) and the sub-samples of a footprint (footprint_steps, mosaic_footprint_samples); the segmented
+// reduction (mosaic_run_reduce) and the accumulator word count << 32 | sum (mosaic_acc: packing a run, the signed add, count and sum of
+// a word, the sample limit, the rounded mean); the two sample loops of the mean, each with a sign (mosaic_scatter_samples,
+// mosaic_scatter_footprints); the rules of the composite and the score, order and sub-cell rules of the registration, one body for host
+// and device.  Host: the typed arena over mosaic_buf and the three layers of a read in it (mosaic_layers), the argument rules
+// (mosaic_check_args), the windows of the grid (mosaic_grid_win, mosaic_window with its metric growth), the cut of a job table into
+// launches (mosaic_cut_launches), the sample-limit flag (mosaic_flag_down), the upload of a caller's trajectory and the scatter launch,
+// defined in dsss_mosaic.hip, and what dsss_mosaic_reg.hip needs of the registration's host arithmetic (dsss_mosaic_edge.cpp).
 #pragma once
 #include "dsss_internal.h"
 
@@ -101,24 +105,29 @@ template <class JOB> __device__ __forceinline__ JOB mosaic_job_of(const JOB* __r
     return jobs[lo];
 }
 
-// What a workgroup of one ping does first (mosaic_scatter_kernel, mosaic_composite_kernel): its job J, the ping's row in the frame and
+// the footprint kernels' partner of a ping: the next ping of the frame, the one before for its last (a frame of one ping: itself)
+struct mosaic_partner_neighbour {
+    template <class JOB> __device__ __forceinline__ const double* operator()(const JOB& J, int row, bool& last) const
+    { last = row == J.N - 1; return J.pose + (size_t)(last ? (row > 0 ? row - 1 : row) : row + 1) * 6; }
+};
+
+// What a workgroup of one ping does first, in every ping-per-workgroup kernel of the family: its job J, the ping's row in the frame and
 // pose row P, and sin and cos of the bearing of each side in s_sc (the kernel's __shared__ double[4]), behind the barrier.  False: the
 // workgroup has no ping; it leaves in front of the barrier (uniform per workgroup; cannot happen with the host's blk0).
-// The partner form (PP given; the footprint kernels): *PP = the pose row of the ping's partner, the next ping of the frame, or the one
-// before for the frame's last ping (*last; a frame of one ping is its own partner), and s_sc is the kernel's __shared__ double[8]: behind
-// the ping's four values, sin and cos of both sides of the partner.  JOB = mosaic_job, or a record that derives from it (the
-// profile's prof_job, dsss_mosaic_profile.hip).
-template <class JOB>
+// The partner form (PP given): *PP = partner(J, row, *last), a second pose row -- the ping's neighbour for the footprint kernels
+// (mosaic_partner_neighbour), the row the frame moves to for the canvas's fused move -- and s_sc is the kernel's __shared__ double[8]:
+// behind the ping's four values, sin and cos of both sides of the partner.  JOB = mosaic_job, or a record that derives from it (the
+// profile's prof_job, the canvas's canvas_job).
+template <class JOB, class PARTNER = mosaic_partner_neighbour>
 __device__ __forceinline__ bool mosaic_ping_of(const JOB* __restrict__ jobs, int njobs, double* s_sc, JOB& J, int& row, const double*& P,
-                                               const double** PP = nullptr, bool* last = nullptr)
+                                               const double** PP = nullptr, bool* last = nullptr, PARTNER partner = PARTNER())
 {
     J = mosaic_job_of(jobs, njobs); row = (int)blockIdx.x - J.blk0;
     if (row >= J.N) return false;
     P = J.pose + (size_t)row * 6;
     J.gain = mosaic_gain_row(J, row);                                              // the ping's band, once per workgroup: the samples see a column table
     if (PP) {
-        *last = row == J.N - 1;
-        *PP = J.pose + (size_t)(*last ? (row > 0 ? row - 1 : row) : row + 1) * 6;
+        *PP = partner(J, row, *last);
         if (threadIdx.x < 4) dsss_geo_side(threadIdx.x < 2 ? P : *PP, threadIdx.x & 1, &s_sc[2 * threadIdx.x], &s_sc[2 * threadIdx.x + 1]);
     }
     else if (threadIdx.x < 2) dsss_geo_side(P, threadIdx.x == 1, &s_sc[2 * threadIdx.x], &s_sc[2 * threadIdx.x + 1]);
@@ -141,10 +150,34 @@ template <class T, class OP> __device__ __forceinline__ bool mosaic_run_reduce(i
     return lane == 63 || ((hb >> (lane + 1)) & 1ull);
 }
 
+// The accumulator word of a cell of the mean mosaic, count << 32 | sum, in its one place: a word read back is taken apart (c, s, the
+// sample limit, the rounded mean), a run's value v (count << 16 | sum within the wavefront) is packed and added, signed.  The word is
+// modular: a negative add (the canvas) adds the two's complement, and while the jobs of one call are in flight a borrow or carry may
+// pass between sum and count.  That is harmless: the adds commute, every job of a call has landed before anything is read, and then
+// both fields are what a fresh render of the same frames gives -- only the final fields are ever read.
+struct mosaic_acc {
+    uint32_t c, s;
+    __device__ __forceinline__ explicit mosaic_acc(unsigned long long a) : c((uint32_t)(a >> 32)), s((uint32_t)a) {}
+    __device__ __forceinline__ bool over_limit() const { return c > MOSAIC_MAX_SAMPLES; }
+    __device__ __forceinline__ uint32_t mean() const { return (s + c / 2) / c; }   // c > 0
+    static __device__ __forceinline__ unsigned long long word(unsigned v) { return ((unsigned long long)(v >> 16) << 32) | (v & 0xffffu); }
+    template <bool SIGNED> static __device__ __forceinline__ void add(unsigned long long* acc, int key, unsigned v, bool negative)
+    { atomicAdd(&acc[key], SIGNED && negative ? 0ull - word(v) : word(v)); }      // (SIGNED false: always added, the render kernels; the atomic without return)
+};
+
+// what the lanes of a wavefront add to their cells: v (0 under key -1) summed over the runs, the run's ONE atomic by its tail lane
+template <bool SIGNED> __device__ __forceinline__ void mosaic_run_add(unsigned long long* __restrict__ acc, int key, unsigned v, bool negative)
+{
+    const bool tail = mosaic_run_reduce(key, v, [](unsigned a, unsigned b) { return a + b; });
+    if (tail && key >= 0) mosaic_acc::add<SIGNED>(acc, key, v, negative);
+}
+
 // The samples of one ping, by the 256 threads of its workgroup (mosaic_scatter_kernel's comment in dsss_mosaic.hip): row = the ping's
-// row in the frame's images, acc = the window's accumulators.
+// row in the frame's images, acc = the window's accumulators.  SIGNED (the canvas): negative = the samples are taken out, uniform per
+// workgroup; everywhere else the sign is no question at compile time.
+template <bool SIGNED = false>
 __device__ __forceinline__ void mosaic_scatter_samples(const double* P, const double* sc, const mosaic_job& J, int row, const mosaic_win& G,
-                                                       unsigned long long* __restrict__ acc)
+                                                       unsigned long long* __restrict__ acc, bool negative = false)
 {
     const int M = J.M;
     const uint8_t* __restrict__ img = J.img + (size_t)row * M;
@@ -152,9 +185,7 @@ __device__ __forceinline__ void mosaic_scatter_samples(const double* P, const do
     for (int c0 = 0; c0 < M; c0 += 256) {
         unsigned g = 0;
         const int key = mosaic_sample_cell(P, sc, J, img, mask, c0 + (int)threadIdx.x, G, &g);
-        unsigned v = key >= 0 ? (1u << 16) | g : 0u;                               // v: count << 16 | sum within the wavefront
-        const bool tail = mosaic_run_reduce(key, v, [](unsigned a, unsigned b) { return a + b; });
-        if (tail && key >= 0) atomicAdd(&acc[key], ((unsigned long long)(v >> 16) << 32) | (v & 0xffffu));
+        mosaic_run_add<SIGNED>(acc, key, key >= 0 ? (1u << 16) | g : 0u, negative);     // v: count << 16 | sum within the wavefront
     }
 }
 
@@ -223,18 +254,15 @@ __device__ __forceinline__ void mosaic_footprint_samples(const double* P, const 
     }
 }
 
-// the mean's sub-samples: mosaic_scatter_samples' sum and count over the runs, the parent's corrected value
+// the mean's sub-samples: mosaic_scatter_samples' sum and count over the runs and its sign, the parent's corrected value
+template <bool SIGNED = false>
 __device__ __forceinline__ void mosaic_scatter_footprints(const double* P, const double* PP, bool last, const double* sc, const mosaic_job& J, int row,
-                                                          const mosaic_win& G, const dsss_footprint_params& F, unsigned long long* __restrict__ acc)
+                                                          const mosaic_win& G, const dsss_footprint_params& F, unsigned long long* __restrict__ acc, bool negative = false)
 {
     const uint8_t* __restrict__ img = J.img + (size_t)row * J.M;
     mosaic_footprint_samples(P, PP, last, sc, J, row, G, F,
         [&](int col) { return (1u << 16) | mosaic_gain_apply(img[col], J.gain, col); },
-        [&](int key, unsigned g) {
-            unsigned v = key >= 0 ? g : 0u;
-            const bool tail = mosaic_run_reduce(key, v, [](unsigned a, unsigned b) { return a + b; });
-            if (tail && key >= 0) atomicAdd(&acc[key], ((unsigned long long)(v >> 16) << 32) | (v & 0xffffu));
-        });
+        [&](int key, unsigned g) { mosaic_run_add<SIGNED>(acc, key, key >= 0 ? g : 0u, negative); });
 }
 
 // ---- composite mosaic ("composite mosaic" in the header; dsss_mosaic_comp.hip).  A cell's key: q << 47 | g << 16 | col, 15 + 31 + 16
@@ -353,6 +381,22 @@ struct mosaic_arena {
     template <class T> int* flag_of(mosaic_piece<T> p) const { return reinterpret_cast<int*>(B + p.off - 8); }
 };
 
+// The three layers of a read (sum, cnt, img of `cells` cells each) in the arena, taken before the reserve: a layer whose host pointer
+// is null takes no bytes and reads back (opt) as the null device pointer the unpack kernels skip; down() queues the copies of the others.
+struct mosaic_layers {
+    size_t cells; uint32_t* h_sum; uint32_t* h_cnt; uint8_t* h_img;
+    mosaic_piece<uint32_t> o_sum, o_cnt; mosaic_piece<uint8_t> o_img;
+    mosaic_layers(mosaic_arena& A, size_t cells_, uint32_t* sum, uint32_t* cnt, uint8_t* img) : cells(cells_), h_sum(sum), h_cnt(cnt), h_img(img),
+        o_sum(A.take<uint32_t>(sum ? cells_ : 0)), o_cnt(A.take<uint32_t>(cnt ? cells_ : 0)), o_img(A.take<uint8_t>(img ? cells_ : 0)) {}
+    bool any() const { return h_sum || h_cnt || h_img; }
+    int down(dsss_ctx* c, const mosaic_arena& A) const {
+        if (h_sum) HIPCHK(c, hipMemcpyAsync(h_sum, A.at(o_sum), cells * 4, hipMemcpyDeviceToHost, c->stream));
+        if (h_cnt) HIPCHK(c, hipMemcpyAsync(h_cnt, A.at(o_cnt), cells * 4, hipMemcpyDeviceToHost, c->stream));
+        if (h_img) HIPCHK(c, hipMemcpyAsync(h_img, A.at(o_img), cells, hipMemcpyDeviceToHost, c->stream));
+        return DSSS_OK;
+    }
+};
+
 int mosaic_check_frames(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, bool need_img, size_t* rows);
 int mosaic_check_params(dsss_ctx* c, const dsss_mosaic_params* p);
 // the argument rules of every entry that bins samples onto a grid, in the order the error precedence rests on: the frames
@@ -366,8 +410,9 @@ void frame_extent(const dsss_frame& f, const double* rows, double* bb);
 void frame_extent_rows(const dsss_frame& f, const double* rows, int r0, int r1, double* bb);      // pings [r0, r1) only
 bool cell_range(double lo, double hi, double origin, double cell, int n, int* a, int* b);
 mosaic_win mosaic_grid_win(const dsss_mosaic_params* p);      // the grid p with the whole of it as the window: what the mean render and the composite scatter into
-// the window of the pings [r0, r1) of a frame on the grid p: the cells their geo extremes can reach; false: none on the grid, *w untouched
-bool mosaic_window(const dsss_frame& f, const double* rows, int r0, int r1, const dsss_mosaic_params* p, mosaic_win* w);
+// the window of the pings [r0, r1) of a frame on the grid p: the cells their geo extremes, grown by `grow` metres on every side, can
+// reach (0: the point samples; 2 max_gap: the sub-samples of a footprint); false: none on the grid, *w untouched
+bool mosaic_window(const dsss_frame& f, const double* rows, int r0, int r1, const dsss_mosaic_params* p, mosaic_win* w, double grow = 0.0);
 // the sample-limit flag of a finished render copied down, the stream synchronised; set: DSSS_E_CAPACITY with the entry's own message (fmt takes the cell)
 int mosaic_flag_down(dsss_ctx* c, const int* d_flag, const char* fmt, double cell);
 int upload_rows(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, double* d_rows, std::vector<const double*>& dev_rows);
@@ -378,10 +423,30 @@ int mosaic_check_gain(dsss_ctx* c, const int* ids, int n);
 // more (a job never carries a table of another M, whatever the caller checked), then the trajectory rows go up (upload_rows into
 // d_rows) and every job gets its rows, geometry, images and the context's table.
 int mosaic_fill_jobs(dsss_ctx* c, const int* ids, int n, const double* rpy6, const int* ping_off, double* d_rows, std::vector<mosaic_job>& jobs);
+// The one cut of a job table (one workgroup per ping) into launches: jobs [j0, j1) with `blocks` workgroups, at most 2^31 samples a
+// launch (sub-samples under fp: max_steps^2 a sample at most), blk0 of every job set.  With the sample limit checked between the launches
+// a cell's count stays far below 2^32 until the check sees it, so the packed accumulator cannot wrap unnoticed whatever the number of
+// frames.  blocks fits an int: frames have 4 columns or more, so several jobs have 2^29 pings at most, one alone 2^31 - 1 (mosaic_check_frames).
+struct mosaic_launch { int j0, j1, blocks; };
+template <class JOB> std::vector<mosaic_launch> mosaic_cut_launches(std::vector<JOB>& jobs, const dsss_footprint_params* fp)
+{
+    const size_t per_sample = fp ? (size_t)fp->max_steps * fp->max_steps : 1;
+    const int n = (int)jobs.size(); std::vector<mosaic_launch> out;
+    for (int j0 = 0; j0 < n;) {
+        int j1 = j0, blocks = 0; size_t samples = 0;
+        while (j1 < n) {
+            const size_t s = (size_t)jobs[j1].N * jobs[j1].M * per_sample;
+            if (j1 > j0 && samples + s > (1ull << 31)) break;
+            jobs[j1].blk0 = blocks; blocks += jobs[j1].N; samples += s; ++j1;
+        }
+        out.push_back({ j0, j1, blocks }); j0 = j1;
+    }
+    return out;
+}
 void launch_scatter(dsss_ctx* c, const mosaic_job* d_jobs, int njobs, int blocks, const mosaic_win& G, unsigned long long* acc);
 // the accumulators of a render on the grid p (acc: W x H, cleared here) and the unpack into the layers given, null: the sample-limit
 // check alone (d_flag, cleared here; mosaic_flag_down reads it); jobs = mosaic_fill_jobs' table, d_jobs = room for it on the device
-int mosaic_render_acc(dsss_ctx* c, const int* ids, int n, std::vector<mosaic_job>& jobs, mosaic_job* d_jobs, const dsss_mosaic_params* p,
+int mosaic_render_acc(dsss_ctx* c, std::vector<mosaic_job>& jobs, mosaic_job* d_jobs, const dsss_mosaic_params* p,
                       const dsss_footprint_params* fp, unsigned long long* acc, int* d_flag, uint32_t* d_sum, uint32_t* d_cnt, uint8_t* d_img);
 // the segmented form for ONE frame (d_job: its record, blk0 = 0; blocks = its pings): ping p goes into d_segs[p / seg_pings]
 void launch_scatter_seg(dsss_ctx* c, const mosaic_job* d_job, int blocks, const mosaic_win& G, unsigned long long* acc, const mosaic_seg* d_segs, int seg_pings);

@@ -16,7 +16,8 @@ constexpr size_t PROFILE_ARENA_CELLS = (size_t)1 << 25;
 // One workgroup per ping, 256 threads, in the launch shape of mosaic_scatter_kernel: job lookup and ping prologue by mosaic_ping_of,
 // every sample binned by mosaic_sample_cell with the frame's window as G -- the mask, cell and gain rules stay in their one place.  The
 // cell of the grid follows from the cell of the window.  A lane reads A[g] and A_f[key], subtracts them as one u64 (the frame's sum and
-// count are each at most the map's: no borrow crosses the words), tests the count of the others against min_count and forms m and d.
+// count are each at most the map's: no borrow crosses the words; mosaic_acc takes the difference apart and forms the mean), tests the
+// count of the others against min_count and forms d.
 // A lane keeps the five integers of either side in registers over the c0 loop (M / 2 need not be a multiple of 256: a lane's column
 // changes sides once, so both sets are live); sd is summed as u32, which is the i32 sum modulo 2^32.  The ten integers are summed over
 // the wavefront (dsss_wave_sum), the four wavefronts through LDS, and ten lanes of the first wavefront store the ping's record with
@@ -45,11 +46,10 @@ __global__ __launch_bounds__(256) void mosaic_profile_kernel(const prof_job* __r
         int d = DSSS_PROFILE_NONE;
         if (key >= 0) {
             const int iy = key / G.bw, ix = key - iy * G.bw;
-            const unsigned long long o = acc[(size_t)(G.oy + iy) * G.W + (G.ox + ix)] - own[key];
-            const uint32_t oc = (uint32_t)(o >> 32), os = (uint32_t)o;
+            const mosaic_acc o(acc[(size_t)(G.oy + iy) * G.W + (G.ox + ix)] - own[key]);
             e[0] = 1;
-            if (oc >= min_count) {
-                d = (int)v - (int)((os + oc / 2) / oc);
+            if (o.c >= min_count) {
+                d = (int)v - (int)o.mean();
                 e[1] = 1; e[2] = (uint32_t)(d < 0 ? -d : d); e[3] = (uint32_t)(d * d); e[4] = (uint32_t)d;
             }
         }
@@ -212,7 +212,7 @@ int dsss_profile_mosaic(dsss_ctx* c, const int* ids, int n, const double* rpy6, 
     rc = mosaic_fill_jobs(c, ids, n, rpy6, ping_off, A.at(o_rows), jobs); if (rc) return rc;
     for (size_t k = 0; k < plan.frames.size(); ++k) plan.frames[k].job = jobs[which[k]];
     // A = the render's accumulators, by the render's launches and under its sample limit
-    rc = mosaic_render_acc(c, ids, n, jobs, A.at(o_jobs), p, nullptr, acc, d_flag, nullptr, nullptr, nullptr); if (rc) return rc;
+    rc = mosaic_render_acc(c, jobs, A.at(o_jobs), p, nullptr, acc, d_flag, nullptr, nullptr, nullptr); if (rc) return rc;
     // the windows of the profiled frames, the cells their geo extremes can reach under the rows they are profiled with: host arithmetic,
     // two bearings per ping, BEHIND the render's launches so that it runs while the device scatters
     for (size_t k = 0; k < plan.frames.size(); ++k) {

@@ -52,10 +52,9 @@ __global__ __launch_bounds__(256) void mosaic_mean_kernel(const unsigned long lo
 {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const unsigned long long a = win[i];
-    const uint32_t c = (uint32_t)(a >> 32), s = (uint32_t)a;
-    if (c > MOSAIC_MAX_SAMPLES) *flag = 1;
-    lay[i] = c ? (uint16_t)(0x100u | ((s + c / 2) / c)) : (uint16_t)0;
+    const mosaic_acc a(win[i]);
+    if (a.over_limit()) *flag = 1;
+    lay[i] = a.c ? (uint16_t)(0x100u | a.mean()) : (uint16_t)0;
 }
 
 // ---- the pyramid of mean layers ("dense loop closures over a cell pyramid" in the header)
@@ -119,12 +118,12 @@ __global__ __launch_bounds__(256) void mosaic_pyr_kernel(const pyr_job* __restri
 #pragma unroll
     for (int k = 0; k < PYR_ROWS; ++k) {
         const int y = gy0 + k - J.oy;
-        unsigned long long a = 0;
-        if (x >= 0 && x < J.bw && y >= 0 && y < J.bh) a = win[(size_t)y * J.bw + x];
-        const uint32_t c = (uint32_t)(a >> 32), s = (uint32_t)a;
-        over |= c > MOSAIC_MAX_SAMPLES;
-        c0[k] = c; s0[k] = s;
-        if (x >= 0 && x < J.bw && y >= 0 && y < J.bh) lay[J.lay[0] + (size_t)y * J.bw + x] = c ? (uint16_t)(0x100u | ((s + c / 2) / c)) : (uint16_t)0;
+        unsigned long long w = 0;
+        if (x >= 0 && x < J.bw && y >= 0 && y < J.bh) w = win[(size_t)y * J.bw + x];
+        const mosaic_acc a(w);
+        over |= a.over_limit();
+        c0[k] = a.c; s0[k] = a.s;
+        if (x >= 0 && x < J.bw && y >= 0 && y < J.bh) lay[J.lay[0] + (size_t)y * J.bw + x] = a.c ? (uint16_t)(0x100u | a.mean()) : (uint16_t)0;
     }
     if (over) *flag = 1;
     if (levels < 2) return;                                                    // (uniform: no lane leaves before the exchanges it takes part in)
