@@ -287,6 +287,43 @@ def test_first_stage_decision_table(ctx, orc, grid, use_l2, monkeypatch):
         ctx.set_params(match=mt)
 
 
+@pytest.mark.parametrize("grid", ["1", "0"])
+def test_first_stage_decision_table_l2_128(ctx, orc, grid, monkeypatch):
+    """the same table for use_l2 = 2 (the MODE 2 instantiations: eight uint4 per row, s_n2 beside the LDS tile of match_nn_kernel, rows
+    fetched from the feature store through the sorted index in match_grid_kernel): 128-byte rows that differ from frame 0's in bytes 32 to
+    127 only and in two 16-byte words at least, so that 32 bytes of a row, or rows strided by 32, fail every line; the bound either side
+    of its strict <, the ratio at 0.5 exactly, a lone candidate above the 1 000 000 sentinel and the same as the second of two, the tie,
+    a candidate exactly `radius` away, and at ratio 0.2 the nc == 1 exit deciding alone.  First stage against the written table and the
+    oracle, SCC, rows and kp7 behind it"""
+    from diasss_amd import capi
+    from tests import matcher_decision_ref as D
+    monkeypatch.setenv("DSSS_MT_GRID", grid)
+    fr = D.frames(2)
+    mp, op, mt, pg = ctx.default_params()
+    op.descriptor = capi.DESC_SIFT128
+    ctx.set_params(orb=op)
+    try:
+        for f, a in fr.items():
+            ctx.frame_set(f, None, a["N"], a["M"], a["pose"], a["alt"], a["gr"])
+            ctx.features_set(f, a["N"], a["M"], a["kps"], a["orb"], geo=a["geo"], bbox=a["bb"])
+            ctx.features_set_sift(f, a["desc"].astype(np.float32))
+        for ratio in D.RATIOS128:
+            mt.use_l2 = 2; mt.ratio = ratio
+            ctx.set_params(match=mt)
+            ctx.match_pairs([0, 0], [1, 2])
+            for p, other in enumerate((1, 2)):
+                for d in (0, 1):
+                    ref = D.oracle_nn(2, ratio, other, d)
+                    assert ref.tolist() == D.EXPECT[2][ratio][other, d], "the oracle leaves the table (frame %d, direction %d)" % (other, d)
+                    nn = ctx.match_dir(p, d)[0][:len(ref)]
+                    print("grid %s use_l2 2 ratio %.2f pair (0, %d) dir %d: device %s" % (grid, ratio, other, d, nn.tolist()))
+                    assert (nn == ref).all(), "first-stage CorresID differs (ratio %.2f, frame %d, direction %d): %s, the table %s" % (ratio, other, d, nn.tolist(), ref.tolist())
+                _check_pair(ctx, orc, p, 0, other, fr, D.params(2, ratio))
+    finally:
+        mp, op, mt, pg = ctx.default_params()
+        ctx.set_params(orb=op, match=mt)
+
+
 @pytest.mark.parametrize("WH", [(1, 1), (31, 33), (32, 32), (41, 25), (64, 48), (1, 2049)])
 def test_matcher_geo_grid_chunk_seams(ctx, orc, WH, monkeypatch):
     """the build of the geo grid (mt_grid_build_kernel: one workgroup scans the cell counts 1 024 cells at a time and carries the running

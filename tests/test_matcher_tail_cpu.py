@@ -222,3 +222,64 @@ def test_first_stage_decision_table_is_the_oracles(orc, use_l2):
     if use_l2 == 0:                                             # 85 flipped bits: refused with ids of different parity, accepted with the same
         assert a[1, 0][3] == -1 and a[2, 0][3] == 1
 
+
+
+def _first_stage_restated(a, b, ratio, nbytes=128, strict=True, l2_bound=350.0, radius=8.0):
+    """the L2 branch of orc_match_nn in numpy; nbytes = 32 reads a quarter of every row, strict = False turns `best < l2_bound` into `<=`"""
+    out = []
+    for i in range(len(a["kps"])):
+        x, y = a["geo"][i]
+        nn = -1
+        if not (x < b["bb"][0] or y < b["bb"][2] or x > b["bb"][1] or y > b["bb"][3]):
+            best = second = 1000.0; bid = -1; nc = 0
+            for j in range(len(b["kps"])):
+                if not np.sqrt((x - b["geo"][j, 0]) ** 2 + (y - b["geo"][j, 1]) ** 2) < radius: continue
+                nc += 1
+                d = np.sqrt(float(((a["desc"][i, :nbytes].astype(int) - b["desc"][j, :nbytes].astype(int)) ** 2).sum()))
+                if d < best: second, best, bid = best, d, j
+                elif d < second: second = d
+            inside = (best < l2_bound) if strict else (best <= l2_bound)
+            with np.errstate(invalid="ignore"):              # 0 / 0 is a NaN as in C: the ratio test fails
+                r = np.float64(best) / np.float64(second)
+            if nc and ((bid != -1 and inside and r <= ratio) or (nc == 1 and inside)): nn = bid
+        out.append(nn)
+    return out
+
+
+def test_first_stage_decision_table_of_the_l2_128_design_is_the_oracles(orc):
+    """the written table of use_l2 = 2 (tests/matcher_decision_ref.py) is what the oracle computes at every ratio, the rows are built as the
+    module says (every difference in bytes 32 to 127 and in two 16-byte words or more, bytes of 128 and above in every base row), and the
+    restated rule shows what the table is worth: read 32 bytes of a row, or accept at the bound, and it fails"""
+    from tests import matcher_decision_ref as D
+    fr = D.frames(2)
+    assert [len(fr[f]["kps"]) for f in (0, 1, 2)] == [12, 14, 13] and all(fr[f]["desc"].shape[1] == 128 for f in fr)
+    for ratio in D.RATIOS128:
+        for (other, d), want in D.EXPECT[2][ratio].items():
+            got = D.oracle_nn(2, ratio, other, d).tolist()
+            print("use_l2 2 ratio %.2f frame %d direction %d: oracle %s" % (ratio, other, d, got))
+            assert got == want, (ratio, other, d)
+    # the rows
+    site0 = {s: k for k, s in enumerate("ABCDEFGHIJKL")}
+    sq = {"S100": 100, "S400": 400, "S900": 900, "S1600": 1600, "BELOW": 350 * 350 - 1, "AT": 350 * 350}
+    for f in (1, 2):
+        for k, (site, _, diffs, _) in enumerate(D.FRAME128[f]):
+            delta = fr[f]["desc"][k].astype(int) - fr[0]["desc"][site0[site]].astype(int)
+            if diffs == "far":
+                assert (np.abs(delta) == 90).all() and (delta ** 2).sum() == 1036800 > 1000000
+                continue
+            assert (delta[:32] == 0).all() and len({p // 16 for p in np.nonzero(delta)[0]}) >= 2, (f, k)
+            assert (delta ** 2).sum() == sum(v * v for v in diffs) and (delta ** 2).sum() in sq.values()
+    assert all((fr[0]["desc"][k][:32] >= 128).any() and (fr[0]["desc"][k][32:] >= 128).sum() == 48 for k in range(12))
+    assert (fr[1]["desc"][5] != fr[1]["desc"][6]).any() and (fr[2]["desc"][6] != fr[2]["desc"][7]).any(), "the tied candidates are different rows"
+    # what decides where: the ratio at 0.5 exactly, the tie's lower index, the nc == 1 exit alone at 0.2
+    E = D.EXPECT[2]
+    assert E[0.35][1, 0][8] == -1 and E[0.5][1, 0][8] == 8 and E[0.5][2, 0][8] == 9
+    assert E[0.35][1, 0][6] == -1 and E[1.0][1, 0][6] == 5 and E[1.0][2, 0][6] == 6
+    assert E[0.2][1, 0][2] == 1 and E[0.2][2, 0][3] == 1 and E[0.2][1, 0][4] == -1
+    pairs = [(ratio, other, d) for ratio in D.RATIOS128 for other in (1, 2) for d in (0, 1)]
+    def restated(ratio, other, d, **kw):
+        a, b = (fr[0], fr[other]) if d == 0 else (fr[other], fr[0])
+        return _first_stage_restated(a, b, ratio, **kw)
+    assert all(restated(*p) == E[p[0]][p[1], p[2]] for p in pairs)
+    assert all(restated(*p, nbytes=32) != E[p[0]][p[1], p[2]] for p in pairs), "32 bytes of a row: every directed pair at every ratio fails"
+    assert all(restated(*p, strict=False) != E[p[0]][p[1], p[2]] for p in pairs), "best <= l2_bound: every directed pair at every ratio fails"
