@@ -18,6 +18,7 @@ int dsss_quadtree_cull(const float* xs, const float* ys, const float* resp, int 
                        int minX, int maxX, int minY, int maxY, int quota, std::vector<int>& keep);
 
 #define EDGE_T 19
+inline int fast_range(int dim) { return dim - 2 * (EDGE_T - 3); }      // FAST runs on [EDGE_T - 3, dim - EDGE_T + 3) of a level's rows or columns: the W and H of its quadtree
 #define HALF_PATCH 15
 #define CELL_MAX 66            // FAST window: cell (ceil(width/nCols) < 60) + 6; 37 once a level is >= 900 px wide
 #define CELL_STRIDE 68
@@ -653,7 +654,7 @@ __global__ __launch_bounds__(256) void scan_counts_kernel(const ex_frame* __rest
         if (i < n) offs[i] = base + p;
         base += tot;
     }
-    if (threadIdx.x == 0) { offs[n] = base; if (base > f.cand_cap) *f.err = 7; }   // cannot happen with the exact bound; never silent
+    if (threadIdx.x == 0) { offs[n] = base; if (base > f.cand_cap) *f.err = QT_E_CAND; }   // cannot happen with the exact bound; never silent
 }
 
 // candidates in reference order with the cell offset applied (ORBextractor.cpp:820-825)
@@ -1032,7 +1033,7 @@ static int get_geom(dsss_ctx* c, int N, int M, level_geom** out)
         // whose roots could overrun it is refused here, before anything is launched
         long long keep = 0;
         for (int l = 0; l < g->nlevels; ++l)
-            keep += std::max(g->quota[l] + 3, 4 * qt_n_roots(g->cols[l] - 2 * (EDGE_T - 3), g->rows[l] - 2 * (EDGE_T - 3)));
+            keep += std::max(g->quota[l] + 3, 4 * qt_n_roots(fast_range(g->cols[l]), fast_range(g->rows[l])));
         if (keep > c->kcap)
             DSSS_FAIL(c, DSSS_E_ARG, "%d x %d frame: the quadtree roots of its levels (one per round(W / H) of a level) can keep %lld keypoints, the store of nfeatures = %d holds %d; raise nfeatures",
                       N, M, keep, c->op.nfeatures, c->kcap);
@@ -1097,9 +1098,9 @@ static ex_layout make_layout(int N, const level_geom& g, int kcap, bool sift)
     for (int l = 0; l < DSSS_MAX_LEVELS; ++l) {
         // the first pass divides every root whatever the quota is, so a level with R roots lists up to 4 R nodes and pools 5 R before
         // the quota says anything (one root: the sizes the quota alone gives); pcnt, 4 * list_cap ints, holds the R root counts
-        const int extra = l < g.nlevels ? qt_n_roots(g.cols[l] - 2 * (EDGE_T - 3), g.rows[l] - 2 * (EDGE_T - 3)) - 1 : 0;
+        const int extra = l < g.nlevels ? qt_n_roots(fast_range(g.cols[l]), fast_range(g.rows[l])) - 1 : 0;
         L.list_cap[l] = 4 * g.quota[l] + 128 + 4 * extra; L.pool_cap[l] = 16 * g.quota[l] + 1024 + 8 * extra;
-        L.work[l] = l < g.nlevels ? take(sizeof(int) * ((size_t)8 * L.pool_cap[l] + (size_t)10 * L.list_cap[l])) : 0;
+        L.work[l] = l < g.nlevels ? take(sizeof(int) * qt_work_layout(L.pool_cap[l], L.list_cap[l]).ints) : 0;
     }
     L.out_idx = take(sizeof(int) * (size_t)DSSS_MAX_LEVELS * L.out_cap); L.out_n = take(sizeof(int) * DSSS_MAX_LEVELS);
     L.kin = take(sizeof(kp_in) * kcap); L.nk = take(sizeof(int)); L.err = take(sizeof(int));
@@ -1261,7 +1262,7 @@ struct ex_run {
             for (int l = 0; l < g.nlevels; ++l) {
                 qt_inst& q = h_inst[(size_t)l * B + bt.lev_cnt[l]++];
                 q.offs = e.offs; q.cell_begin = g.cell_begin[l]; q.cell_end = g.cell_begin[l + 1]; q.xs = e.xs; q.ys = e.ys; q.rs = e.rs;
-                q.W = (g.cols[l] - EDGE_T + 3) - (EDGE_T - 3); q.H = (g.rows[l] - EDGE_T + 3) - (EDGE_T - 3); q.quota = g.quota[l];
+                q.W = fast_range(g.cols[l]); q.H = fast_range(g.rows[l]); q.quota = g.quota[l];
                 q.keys0 = (unsigned long long*)(S + L.keys0); q.keys1 = (unsigned long long*)(S + L.keys1); q.work = (int*)(S + L.work[l]);
                 q.list_cap = L.list_cap[l]; q.pool_cap = L.pool_cap[l]; q.err = e.err; q.cand_cap = L.cand_cap;
                 q.out_idx = out_idx + (size_t)l * L.out_cap; q.out_n = out_n + l; q.out_cap = L.out_cap;
@@ -1346,7 +1347,8 @@ struct ex_run {
         HIPCHK(c, hipStreamSynchronize(st));
         for (int s = 0; s < bt.nb; ++s) {
             const int id = ids[bt.b0 + s]; dsss_frame& f = c->frames[id];
-            if (h_err[s]) DSSS_FAIL(c, DSSS_E_CAPACITY, "frame %d: extraction capacity exceeded (code %d; 7 = FAST candidates, else quadtree lists)", id, h_err[s]);
+            if (h_err[s]) DSSS_FAIL(c, DSSS_E_CAPACITY, "frame %d: extraction capacity exceeded (code %d; quadtree: %d node pool, %d node list, %d kept candidates of a level, %d keypoints of the frame, %d candidate index; %d FAST candidates)",
+                                    id, h_err[s], QT_E_POOL, QT_E_LIST, QT_E_OUT, QT_E_KCAP, QT_E_INDEX, QT_E_CAND);
             f.nkp = h_nkp[id]; f.has_feat = true; f.has_norm = true; ++f.epoch; f.has_sift = sift;
         }
         return DSSS_OK;

@@ -8,13 +8,14 @@
 //   - nIni = max(1, round(width/height))      (the reference divides by zero for tall levels, :543-545)
 //   - equal-size nodes are split in creation order (the reference compares heap addresses, :684)
 #include "dsss_internal.h"
+#include "dsss_quadtree.h"
 #include <algorithm>
 #include <list>
 
 namespace {
 
 struct Cell {
-    int x0, y0, x1, y1;            // [x0,x1) x [y0,y1) in candidate coordinates
+    qt_box box;
     std::vector<int> pts;          // candidate indices, original order preserved
     bool leaf = false;             // holds exactly one point: never split again
     int serial = 0;                // creation order
@@ -32,17 +33,9 @@ struct Splitter {
     void split(CellList::iterator it, Cell out[4]) const
     {
         const Cell& c = *it;
-        const int hx = (int)std::ceil((float)(c.x1 - c.x0) / 2), hy = (int)std::ceil((float)(c.y1 - c.y0) / 2);
-        const int mx = c.x0 + hx, my = c.y0 + hy;
-        out[0].x0 = c.x0; out[0].y0 = c.y0; out[0].x1 = mx;   out[0].y1 = my;
-        out[1].x0 = mx;   out[1].y0 = c.y0; out[1].x1 = c.x1; out[1].y1 = my;
-        out[2].x0 = c.x0; out[2].y0 = my;   out[2].x1 = mx;   out[2].y1 = c.y1;
-        out[3].x0 = mx;   out[3].y0 = my;   out[3].x1 = c.x1; out[3].y1 = c.y1;
-        for (int k = 0; k < 4; ++k) { out[k].pts.clear(); out[k].pts.reserve(c.pts.size()); out[k].leaf = false; }
-        for (int id : c.pts) {
-            const bool left = xs[id] < (float)mx, top = ys[id] < (float)my;
-            out[left ? (top ? 0 : 2) : (top ? 1 : 3)].pts.push_back(id);
-        }
+        const float mx = (float)qt_mid(c.box.x0, c.box.x1), my = (float)qt_mid(c.box.y0, c.box.y1);
+        for (int k = 0; k < 4; ++k) { out[k].box = qt_child_box(c.box, k); out[k].pts.clear(); out[k].pts.reserve(c.pts.size()); out[k].leaf = false; }
+        for (int id : c.pts) out[qt_quadrant(xs[id], ys[id], mx, my)].pts.push_back(id);
         for (int k = 0; k < 4; ++k) out[k].leaf = out[k].pts.size() == 1;
     }
 
@@ -74,22 +67,17 @@ int dsss_quadtree_cull(const float* xs, const float* ys, const float* resp, int 
     keep.clear();
     if (n <= 0) return 0;
     Splitter S; S.xs = xs; S.ys = ys;
-    int nroot = (int)std::round((float)(maxX - minX) / (float)(maxY - minY));
-    if (nroot < 1) nroot = 1;
-    const float hX = (float)(maxX - minX) / nroot;
+    const int W = maxX - minX, H = maxY - minY, nroot = qt_n_roots(W, H);
+    const float hX = qt_root_width(W, nroot);
     std::vector<CellList::iterator> roots(nroot);
     for (int i = 0; i < nroot; ++i) {
         Cell c;
-        c.x0 = (int)(hX * (float)i); c.x1 = (int)(hX * (float)(i + 1)); c.y0 = 0; c.y1 = maxY - minY;
+        c.box = qt_root_box(i, hX, H);
         c.serial = S.next_serial++;
         S.cells.push_back(std::move(c));
         roots[i] = std::prev(S.cells.end());
     }
-    for (int i = 0; i < n; ++i) {
-        int r = (int)(xs[i] / hX);
-        if (r >= nroot) r = nroot - 1;
-        roots[r]->pts.push_back(i);
-    }
+    for (int i = 0; i < n; ++i) roots[qt_root_of(xs[i], hX, nroot)]->pts.push_back(i);
     for (auto it = S.cells.begin(); it != S.cells.end();) {
         if (it->pts.size() == 1) { it->leaf = true; ++it; }
         else if (it->pts.empty()) it = S.cells.erase(it);

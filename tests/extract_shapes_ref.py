@@ -1,6 +1,7 @@
 """Frames, shape tables and oracle references that hold the extraction kernels (dsss_extract.hip, dsss_quadtree.hip) to the oracle at the
 shapes the survey-sized tests never reach: small levels (one to three FAST cells an axis, windows of 30 to 59 px, both LDS strides of
-fast_cells_kernel), wide frames (two to 53 quadtree roots), keypoints in the border band (the byte-wise reflect-101 patch loading of
+fast_cells_kernel), wide frames (two to 53 quadtree roots), level quotas of one and zero and a quota whose size-ordered refinement starts
+with more nodes than quadtree_kernel stages in LDS, keypoints in the border band (the byte-wise reflect-101 patch loading of
 orient_desc_kernel), cells that are empty at iniThFAST and not at minThFAST, hot pixels at the image borders, mask parameters other than
 the defaults.  Shared by tests/test_extract_shapes_cpu.py (oracle only: every frame is in the class it is named for, so that no GPU
 comparison is vacuous) and tests/test_gpu_extract_shapes.py.  Plain functions, no fixtures; references are computed once per session.
@@ -89,6 +90,44 @@ def shape_class(orc, rows, cols, nlevels=1, scale=1.2):
                 nrows=[g["nrows"] for g in cells], roots=[n_roots(r, c) for r, c in lv])
 
 
+def level_quotas(nfeatures, nlevels, scale=1.2):
+    """mnFeaturesPerLevel (ORBextractor.cpp:431-444) as build_geom restates it, in float"""
+    f = np.float32
+    factor = f(1.0) / f(scale)
+    desired = f(nfeatures) * (f(1) - factor) / (f(1) - f(float(factor) ** nlevels))
+    out = []
+    for _ in range(nlevels - 1):
+        out.append(int(np.rint(desired))); desired = desired * factor
+    return out + [max(nfeatures - sum(out), 0)]
+
+
+def whole_list_passes(xs, ys, W, H, depth):
+    """[(S_p, X_p) for p = 1 .. depth]: non-empty cells and cells of two or more candidates at depth p of DivideNode's boxes under ONE
+    root (0, 0, W, H).  While every pass of DistributeOctTree divides the whole list these are its nodes and its expandable nodes after
+    pass p: a node of one candidate is never divided and stays one cell at every depth below"""
+    x, y = xs.astype(np.int64), ys.astype(np.int64)
+    assert (x == xs).all() and (y == ys).all()
+    x0 = np.zeros_like(x); y0 = np.zeros_like(x); x1 = np.full_like(x, W); y1 = np.full_like(x, H); code = np.zeros_like(x)
+    out = []
+    for _ in range(depth):
+        mx, my = x0 + (x1 - x0 + 1) // 2, y0 + (y1 - y0 + 1) // 2          # lo + ceil((hi - lo) / 2)
+        left, top = x < mx, y < my
+        code = code * 4 + np.where(left, np.where(top, 0, 2), np.where(top, 1, 3))
+        x1 = np.where(left, mx, x1); x0 = np.where(left, x0, mx); y1 = np.where(top, my, y1); y0 = np.where(top, y0, my)
+        sizes = np.unique(code, return_counts=True)[1]
+        out.append((len(sizes), int((sizes > 1).sum())))
+    return out
+
+
+def first_verdict(passes, quota):
+    """(p, S_p, X_p, refinement) at the first pass after which DistributeOctTree stops dividing the whole list: at its quota (False) or
+    within 3 X_p of it (True: the size-ordered refinement starts with X_p expandable nodes); None when neither comes within `passes`"""
+    for p, (S, X) in enumerate(passes, 1):
+        if S >= quota: return p, S, X, False
+        if S + 3 * X > quota: return p, S, X, True
+    return None
+
+
 def resize_strips(sw, dw):
     """whether a level of dw columns made from one of sw takes resize_strip_kernel (True) or the flat resize_kernel: the x table of
     cv::resize(INTER_LINEAR) as dsss_extract.hip:resize_tables builds it (scale in double, fx in float), and the strips' condition that
@@ -136,6 +175,14 @@ PYRAMID_SHAPES = [(278, 282, 3, 2.0, (False, False)), (158, 170, 3, 1.5, (False,
 # (rows, cols, nlevels, nfeatures, roots of level 0)
 WIDE_SHAPES = [(69, 86, 1, 50, 1), (69, 88, 1, 50, 2), (69, 124, 1, 50, 2), (69, 126, 1, 50, 3), (69, 1234, 1, 100, 32), (69, 1236, 1, 100, 33),
                (69, 2000, 1, 150, 53), (100, 700, 2, 150, 10)]
+
+# the same row, frames of one root whose QUOTA takes quadtree_kernel where no other frame does (wide_case makes them too).
+#   100 x 100, nfeatures 1 on two levels: the quotas are (1, 0) -- the keys are written without a pre-sort, the root is divided once by the
+#     whole workgroup and the tree is over its quota at once, keeping up to four nodes a level;
+#   900 x 640, nfeatures 25000 on one level: six passes leave 4096 nodes, the seventh more than RANK_STAGED expandable ones and fewer
+#     nodes than the quota -- the size-ordered refinement starts with more (size, id) pairs than the kernel stages in LDS
+QUOTA_SHAPES = [(100, 100, 2, 1, 1), (900, 640, 1, 25000, 1)]
+RANK_STAGED = 4096
 
 RAMP_SHAPES = ((160, 272), (200, 400))
 THRESHOLDS = ((12, 7), (20, 20), (7, 12), (40, 3), (254, 1))

@@ -152,20 +152,49 @@ def test_border_hot_pixels_follow_the_erasers_rule(orc):
     assert Mw % 4 == 2 and (Nw * Mw) % 16 != 0
 
 
-@pytest.mark.parametrize("shape", X.WIDE_SHAPES, ids=lambda s: "%dx%d" % s[:2])
-def test_host_twin_builds_the_oracles_tree_at_every_root_count(orc, shape):
-    """quadtree.cpp (the host twin of quadtree_kernel) keeps the oracle's candidates in the oracle's order on the wide frames' own
-    candidates: the root rule has no upper limit on either side"""
+def _twin_keeps_what_the_oracle_keeps(orc, cands, rows, cols, quota):
+    """quadtree.cpp on the candidates of a rows x cols level: the oracle's kept candidates in the oracle's order; how many"""
     import ctypes as C
     from diasss_amd import capi
-    rows, cols, nl, nf, roots = shape
-    raw, orb, ref = X.wide_case(orc, rows, cols, nl, nf)
-    xs, ys, rs = (np.ascontiguousarray(a) for a in ref["cands"][0])
+    xs, ys, rs = (np.ascontiguousarray(a) for a in cands)
     n = len(xs)
-    quota = nf if nl == 1 else nf // 2
     k_o = np.zeros(n, np.int32); k_p = np.zeros(n, np.int32); npk = C.c_int(0)
     no = orc.lib().orc_quadtree(orc.fp(xs), orc.fp(ys), orc.fp(rs), n, 16, cols - 16, 16, rows - 16, quota, orc.ip(k_o))
     rc = capi.lib().dsss_host_quadtree(xs.ctypes.data_as(C.c_void_p), ys.ctypes.data_as(C.c_void_p), rs.ctypes.data_as(C.c_void_p), n,
                                        16, cols - 16, 16, rows - 16, quota, k_p.ctypes.data_as(C.c_void_p), C.byref(npk))
     assert rc == 0 and npk.value == no and quota <= no < n
     assert (k_p[:no] == k_o[:no]).all()
+    return no
+
+
+@pytest.mark.parametrize("shape", X.WIDE_SHAPES + X.QUOTA_SHAPES, ids=lambda s: "%dx%d" % s[:2])
+def test_host_twin_builds_the_oracles_tree_at_every_root_count(orc, shape):
+    """quadtree.cpp (the host twin of quadtree_kernel) keeps the oracle's candidates in the oracle's order on the wide frames' own
+    candidates: the root rule has no upper limit on either side"""
+    rows, cols, nl, nf, roots = shape
+    raw, orb, ref = X.wide_case(orc, rows, cols, nl, nf)
+    _twin_keeps_what_the_oracle_keeps(orc, ref["cands"][0], rows, cols, nf if nl == 1 else nf // 2)
+
+
+def test_quota_frames_take_the_tree_where_they_say(orc):
+    """the two frames of QUOTA_SHAPES are in the class they are named for, and the host twin is the oracle on them"""
+    rows, cols, nl, nf, roots = X.QUOTA_SHAPES[0]
+    assert X.level_quotas(nf, nl) == [1, 0]
+    raw, orb, ref = X.wide_case(orc, rows, cols, nl, nf)
+    assert X.shape_class(orc, rows, cols, nl)["roots"] == [1, 1]
+    for (r, c), cands, quota in zip(X.level_sizes(orc, rows, cols, ref["op"]), ref["cands"], (1, 0)):
+        kept = _twin_keeps_what_the_oracle_keeps(orc, cands, r, c, quota)
+        assert 2 <= kept <= 4 < len(cands[0]), "one division of the root, whatever the quota"
+    assert len(X.unfiltered_keypoints(orc, ref)) > 4 and set(ref["kps"]["octave"]) == {0, 1}, "both levels keep keypoints, after the mask too"
+
+    rows, cols, nl, nf, roots = X.QUOTA_SHAPES[1]
+    raw, orb, ref = X.wide_case(orc, rows, cols, nl, nf)
+    xs, ys, _ = ref["cands"][0]
+    assert X.n_roots(rows, cols) == roots == 1 and X.level_quotas(nf, nl) == [nf]
+    passes = X.whole_list_passes(xs, ys, cols - 2 * X.BORDER, rows - 2 * X.BORDER, 8)
+    p, S, Xp, refinement = X.first_verdict(passes, nf)
+    print("%d candidates, (nodes, expandable) per pass %s: pass %d ends the whole-list passes" % (len(xs), passes, p))
+    assert passes[:6] == [(4 ** d, 4 ** d) for d in range(1, 7)], "every cell down to the pre-sort's deepest holds two candidates or more"
+    assert refinement and S < nf and Xp > X.RANK_STAGED and p == 7
+    nk = len(X.unfiltered_keypoints(orc, ref))
+    assert nf <= nk <= nf + 3 and len(xs) > 2 * nk, "the refinement ends at the quota, far below the candidate count"

@@ -59,7 +59,7 @@ def _check_stages(ctx, fid, ref, what):
 def _check_features(ctx, orc, fid, ref, pose, gr, what, sel=None):
     """final keypoints in order, descriptors and geo samples; sel: a boolean pick of the oracle's keypoints (the counts are compared first)"""
     kps, desc = ref["kps"], ref["desc"]
-    g_kps, g_desc, g_geo = ctx.features_get(fid)
+    g_kps, g_desc, g_geo = ctx.features_get(fid, cap=max(16384, len(kps) + 64))
     assert len(g_kps) == len(kps), "%s: %d keypoints, the oracle %d" % (what, len(g_kps), len(kps))
     s = slice(None) if sel is None else sel
     for fld in FIELDS:
@@ -118,10 +118,11 @@ def test_pyramid_strips_and_flat_levels_swap_in_one_batch(ctx, orc):
                 _check_features(ctx, orc, i, cases[i][2], dr[i][0], dr[i][2], "frame %d in the batch %s" % (i, order))
 
 
-@pytest.mark.parametrize("shape", X.WIDE_SHAPES, ids=lambda s: "%dx%d" % s[:2])
+@pytest.mark.parametrize("shape", X.WIDE_SHAPES + X.QUOTA_SHAPES, ids=lambda s: "%dx%d" % s[:2])
 def test_wide_frames_and_quadtree_roots(ctx, orc, shape):
     """1, 2, 3, 10 / 11, 32, 33 and 53 initial nodes: the stable partition by root, its pcnt bookkeeping, the passes without the pre-sort.
-    The ORDER of the final keypoints is the tree's list order, which is what a different set of roots changes first"""
+    The ORDER of the final keypoints is the tree's list order, which is what a different set of roots changes first.  Then the two quotas
+    of QUOTA_SHAPES on one root: (1, 0), and one whose refinement ranks more nodes than the kernel stages in LDS"""
     rows, cols, nl, nf, roots = shape
     raw, orb, ref = X.wide_case(orc, rows, cols, nl, nf)
     with _params(ctx, X.SMALL_MASK, orb):
